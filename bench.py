@@ -1,6 +1,11 @@
 """bench.py -- denoised frames/sec of the DDPM sampling hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (metric, value, ms_per_step, ...).  --full adds the
+secondary legs: roofline over every kernel of the step, the YAML-literal Y shape, BASELINE.json configs[3] / configs[4], the
+training step and the CPU baseline (each can be switched off again with its --no-* option).  --dump-outputs DIR writes what the
+last timed step returned (rank 0) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 N > 1: one rank per GPU over RCCL.  Either the caller launches the ranks (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: WORLD_SIZE is set) or, when WORLD_SIZE is unset, this process spawns them itself through
@@ -122,6 +127,24 @@ def log(msg):
     print(f'[bench +{time.time() - _T0:6.1f}s] {msg}', file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET = 60 * 10 ** 6                  # bytes of array data over all --dump-outputs files: under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, at most `budget` bytes in all.  An array larger than its equal
+    share of the budget is replaced by a fixed sample of it: every k-th element of the flattened array, the same on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // len(arrays)
+    for name, a in arrays.items():
+        a, what = np.ascontiguousarray(a, dtype=np.float32), 'whole'
+        if a.nbytes > share:
+            k = -(-a.size // (share // 4))
+            a, what = a.reshape(-1)[::k].copy(), f'every {k}-th element'
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+        log(f'dumped {name}: {tuple(a.shape)} float32 ({what})')
+
+
 _T0 = time.time()
 
 
@@ -138,6 +161,10 @@ def parse_args(argv=None):
     ap.add_argument('--act-storage', default=os.environ.get('VDX_BENCH_ACT', 'auto'), choices=['auto', 'f32', 'bf16'],
                     help='storage of the inter-kernel activations (auto: bf16 in bf16 mode, as GaussianDiffusion.sample does)')
     ap.add_argument('--attn-fp8', action='store_true', help='bf16 mode: fp8 (e4m3) QK^T / PV in the <= 16-token attention blocks (BASELINE configs[4]); off by default')
+    ap.add_argument('--full', action='store_true', help='also run the secondary legs (roofline, Y shape, configs[3] / [4], training, CPU baseline); '
+                                                        'off: the run times the headline sampling step only')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='after the timed steps write what the last timed step returned (rank 0): '
+                                                                      'DIR/x.npy (the batch after the step) and DIR/eps.npy (the UNet output of the step), float32')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-y-shape', action='store_true', help='skip the secondary timing of the YAML-literal config_v2_2 (dim 32, 10 frames)')
@@ -219,9 +246,10 @@ def train_leg(args, dev, world, rank):
             'what': 'q_sample + Unet3D fwd (bf16 activation storage kept for the backward in bf16 mode) + l2 loss + staged backward + bucketed sum all-reduce + Adam + EMA'}
 
 
-def sampling_leg(args, dev, world, rank, dim, Fr, S, B, steps, warmup, roofline):
+def sampling_leg(args, dev, world, rank, dim, Fr, S, B, steps, warmup, roofline, keep_outputs=False):
     """K graph-replayed reverse-diffusion steps of a dim / Fr x S x S network at batch B on this rank, bracketed by barrier +
-    synchronize on both sides, max over ranks.  Returns (ms_per_step, act, roofline records or None)."""
+    synchronize on both sides, max over ranks.  Returns (ms_per_step, act, roofline records or None, outputs): `keep_outputs`:
+    host copies of what the last timed step left (x, eps), taken before the roofline leg steps on; else None."""
     import torch
     import torch.distributed as dist
     from video_diffusion_nnx_amd import _lib as L
@@ -260,6 +288,7 @@ def sampling_leg(args, dev, world, rank, dim, Fr, S, B, steps, warmup, roofline)
             dist.barrier()
         torch.cuda.synchronize(dev)
         elapsed = time.perf_counter() - t0
+        outputs = {'x': img.cpu().numpy(), 'eps': eps.cpu().numpy()} if keep_outputs else None
         if rank == 0 and roofline:
             log('roofline leg: events around every kernel launch of 5 eager steps of the same loop ...')
             rec = time_kernels_in_step(lambda n: run(n, 0), dev)
@@ -272,7 +301,7 @@ def sampling_leg(args, dev, world, rank, dim, Fr, S, B, steps, warmup, roofline)
     del img, eps, ws
     unet._ws.clear()
     torch.cuda.empty_cache()
-    return elapsed / steps * 1e3, act, rec
+    return elapsed / steps * 1e3, act, rec, outputs
 
 
 def other_configs_leg(dev, world):
@@ -345,6 +374,9 @@ def kernel_row(key, d, mode, ms_per_step):
 
 def main():
     args = parse_args()
+    roofline = args.full and not args.no_roofline
+    if args.launch_seq and not roofline:
+        sys.exit('bench.py: --launch-seq is written by the roofline leg: it needs --full (without --no-roofline)')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
 
@@ -366,7 +398,11 @@ def main():
         log(f'rank {rank}/{world} on cuda:{local}: process group up: {backend}')
 
     B, Fr, S = args.batch, args.frames, args.size
-    ms_per_step, act, rec = sampling_leg(args, dev, world, rank, args.dim, Fr, S, B, args.steps, args.warmup, not args.no_roofline)
+    dump = bool(args.dump_outputs) and rank == 0
+    ms_per_step, act, rec, outputs = sampling_leg(args, dev, world, rank, args.dim, Fr, S, B, args.steps, args.warmup, roofline, keep_outputs=dump)
+    if dump:
+        dump_outputs(args.dump_outputs, outputs)
+        del outputs
     value = world * B * Fr / (T_STEPS * ms_per_step * 1e-3)
 
     line = {
@@ -380,21 +416,21 @@ def main():
                    'process_group': backend or 'none (single process)'},
     }
     log(f'timed region done: {ms_per_step:.3f} ms/step')
-    if not args.no_y_shape:
+    if args.full and not args.no_y_shape:
         # secondary: the YAML-literal config_v2_2 (configs/config_v2_2.yaml: dim 32, 10 frames, 64 x 64) -- what `sample.py --config
         # configs/config_v2_2.yaml` runs; same loop, same batch, fewer steps
-        yms, _, _ = sampling_leg(args, dev, world, rank, 32, 10, 64, B, max(5, args.steps // 2), 3, False)
+        yms, _, _, _ = sampling_leg(args, dev, world, rank, 32, 10, 64, B, max(5, args.steps // 2), 3, False)
         line['y_shape'] = {'workload': f'configs/config_v2_2.yaml as written: Unet3D dim=32 C=1, 10f x 64x64, T={T_STEPS}', 'batch_per_gpu': B,
                            'ms_per_step': yms, 'frames_per_s': world * B * 10 / (T_STEPS * yms * 1e-3),
                            'tflops': world * B * 54.09e9 / (yms * 1e-3) / 1e12, 'n_shape_tflops': world * B * 250.77e9 / (ms_per_step * 1e-3) / 1e12}
         log(f"Y shape: {yms:.3f} ms/step, {line['y_shape']['frames_per_s']:.1f} frames/s")
-    if rank == 0 and not args.no_other_configs:
+    if rank == 0 and args.full and not args.no_other_configs:
         try:                                              # secondary object: a failure here must not cost the line its primary fields
             line['other_configs'] = other_configs_leg(dev, world)
         except Exception as e:                            # noqa: BLE001
             line['other_configs'] = {'error': f'{type(e).__name__}: {e}'}
             log(f'other_configs leg failed: {e}')
-    if not args.no_train:
+    if args.full and not args.no_train:
         log('training leg (p_losses fwd+bwd + bucketed all-reduce + Adam/EMA) ...')
         line['train'] = train_leg(args, dev, world, rank)         # every rank takes part (collectives inside)
         log(f"training leg done: {line['train']['ms_per_step']:.2f} ms/step, {line['train']['samples_per_s']:.1f} samples/s")
@@ -428,7 +464,7 @@ def main():
                             'all_kernels': [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()} for r in rows]}
         if args.launch_seq:
             json.dump({'batch': B, 'mode': args.mode, 'dim': args.dim, 'act': act, 'sequence': sequence}, open(args.launch_seq, 'w'))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         log('cpu_baseline leg (oracle on host cores) ...')
         line['cpu_baseline'] = cpu_baseline(args.dim, Fr, S)
     if rank == 0:

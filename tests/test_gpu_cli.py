@@ -47,3 +47,28 @@ def test_train_then_sample(tmp_path, mode):
                  '--batch-size', '2', '--seed', '1', '--output-path', str(out), '--mode', mode, '--load-ema-params'])
     gifs = sorted(out.glob('sample_*.gif'))
     assert len(gifs) == 2 and all(g.stat().st_size > 100 for g in gifs)
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """`bench.py` without --full: the result line carries the headline fields and nothing of the secondary legs; --dump-outputs
+    writes the batch after the last timed step and the UNet output of that step.  Seeded inputs: a second run writes the same
+    arrays (up to the last-bit jitter of the GroupNorm statistics' atomics)."""
+    import subprocess
+    import numpy as np
+    B, Fr, S = 2, 4, 16
+    outs = []
+    for run in ('a', 'b'):
+        cmd = [sys.executable, str(ROOT / 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '2', '--dim', '16', '--frames', str(Fr),
+               '--size', str(S), '--batch', str(B), '--dump-outputs', str(tmp_path / run)]
+        p = subprocess.run(cmd, cwd=str(ROOT), capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        line = json.loads(p.stdout.strip().splitlines()[-1])
+        assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'} <= set(line)
+        assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0
+        assert not {'roofline', 'y_shape', 'other_configs', 'train', 'cpu_baseline'} & set(line)
+        x, eps = np.load(tmp_path / run / 'x.npy'), np.load(tmp_path / run / 'eps.npy')
+        assert x.dtype == eps.dtype == np.float32 and x.shape == (B, 1, Fr, S, S) and eps.shape == (B, Fr, S, S, 1)
+        assert np.isfinite(x).all() and np.isfinite(eps).all() and np.abs(eps).max() > 0
+        outs.append((x, eps))
+    for a, b in zip(*outs):
+        assert np.linalg.norm(a - b) <= 1e-3 * np.linalg.norm(b)

@@ -94,3 +94,37 @@ def test_bench_parent_spawns_ranks_without_touching_torch(monkeypatch):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     out = subprocess.run([sys.executable, '-c', code], cwd=str(ROOT), env=env, capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip().endswith('ok'), out.stderr
+
+
+def test_bench_plain_run_leaves_the_secondary_legs_to_full(monkeypatch):
+    """A plain `bench.py` run times the headline step only; --full switches the secondary legs on.  --launch-seq is written by
+    the roofline leg, so without --full it is refused before anything touches the GPU."""
+    import sys
+    import bench
+    a = bench.parse_args(['--gpus', '1', '--steps', '3', '--warmup', '1'])
+    assert not a.full and a.dump_outputs == '' and a.steps == 3 and a.warmup == 1
+    a = bench.parse_args(['--full', '--no-train', '--dump-outputs', 'd'])
+    assert a.full and a.no_train and a.dump_outputs == 'd'
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--launch-seq', 'seq.json'])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert '--full' in str(e.value.code)
+
+
+def test_bench_dump_outputs_stay_within_budget(tmp_path):
+    """--dump-outputs: float32 .npy per array; an array over its share of the budget becomes a fixed sample (every k-th element),
+    the same on every run."""
+    import bench
+    rng = np.random.default_rng(5)
+    small = rng.standard_normal((4, 3)).astype(np.float64)
+    big = rng.standard_normal((64, 100)).astype(np.float32)             # 25.6 kB > share 16 kB -> every 2nd element
+    budget = 32000
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), {'small': small, 'big': big}, budget=budget)
+    got = {n: np.load(tmp_path / 'a' / f'{n}.npy') for n in ('small', 'big')}
+    assert all(v.dtype == np.float32 for v in got.values())
+    np.testing.assert_array_equal(got['small'], small.astype(np.float32))
+    np.testing.assert_array_equal(got['big'], big.reshape(-1)[::2])
+    assert sum(v.nbytes for v in got.values()) <= budget
+    for n, v in got.items():
+        np.testing.assert_array_equal(np.load(tmp_path / 'b' / f'{n}.npy'), v)

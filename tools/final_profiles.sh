@@ -7,7 +7,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out
 cd "$root"
 if [ "$part" = a ] || [ "$part" = all ]; then
-  python3 bench.py > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.log"; tail -2 "$out/${tag}_bench.log"
+  python3 bench.py --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.log"; tail -2 "$out/${tag}_bench.log"
   bash tools/prof_step.sh "$tag" > "$out/${tag}_step.txt" 2>&1; head -3 "$out/${tag}_step.txt"
   bash tools/traffic.sh "${tag}_traffic" "$out/prof_step_$tag/seq.json" > "$out/${tag}_traffic.txt" 2>&1; tail -1 "$out/${tag}_traffic.txt"
 fi
