@@ -110,8 +110,9 @@ def test_conv_concat_and_prologue(mode):
 @pytest.mark.parametrize('act_bf16,B,Fr', [(False, 2, 32), (True, 2, 32), (True, 3, 22)])
 def test_persistent_c64_conv(act_bf16, B, Fr):
     """The persistent level-0 specialisations (3x3, 64 -> 64 channels, bf16 mode, >= 1024 tiles of 16x16 pixels; fp32 tensors:
-    conv64p_kernel, weights resident in LDS; bf16 tensors: conv64r_kernel, weights in registers + a three-deep LDS-DMA tile ring, the
-    prologue applied in place one tile ahead): plain form with statistics, then the fused-prologue form consuming it, several samples
+    conv64p_kernel, weights resident in LDS; bf16 tensors: conv64r_kernel for the plain form, weights in registers + a three-deep
+    LDS-DMA tile ring, and conv64q_kernel<64, true> for the prologue form, the prologue applied in place one tile ahead): plain form
+    with statistics, then the fused-prologue form consuming it, several samples
     so that the per-sample flush of the register-resident statistics and the coefficient switch are exercised.  (3, 22): 1056 tiles = 5
     per workgroup, so workgroups 70 and 140 walk ACROSS a sample boundary (tiles 352, 704)."""
     from video_diffusion_nnx_amd import ops
@@ -150,8 +151,8 @@ def test_persistent_c64_conv(act_bf16, B, Fr):
 
 @pytest.mark.parametrize('concat', [True, False])
 def test_persistent_c128_to_64_conv(concat):
-    """conv128x64p_kernel: 3x3, 128 -> 64 channels (two-pointer concat of 64 + 64, or one 128-channel tensor), bf16 tensors,
-    >= 1024 tiles; each workgroup owns half of the output channels; statistics of two samples."""
+    """conv64q_kernel<128, ...>: 3x3, 128 -> 64 channels (two-pointer concat of 64 + 64, or one 128-channel tensor), bf16 tensors,
+    >= 1024 tiles, two 64-channel plane passes per tile; statistics of two samples."""
     from video_diffusion_nnx_amd import ops
     dev = torch.device('cuda:0')
     g = torch.Generator().manual_seed(13)
@@ -267,9 +268,9 @@ def test_weight_streaming_conv(case, y_bf16):
 
 @pytest.mark.parametrize('res_bf16', [False, True])
 def test_persistent_conv64_with_residual(res_bf16):
-    """conv64p_kernel<true, false, *, true>: the level-0 3x3 64->64 conv with a residual added in the epilogue (in training: the data
-    gradient of a ResnetBlock's first conv + the gradient of the skip path), 1024 tiles = the persistent form's threshold.  (A bf16
-    residual takes the generic kernel: same check.)"""
+    """conv64d_kernel<false, true>: the level-0 3x3 64->64 conv with an fp32 residual added in the epilogue (in training: the data
+    gradient of a ResnetBlock's first conv + the gradient of the skip path), 1024 tiles = the persistent form's threshold; the plain
+    form it is compared with is conv64r_kernel.  (A bf16 residual takes the generic kernel: same check.)"""
     from video_diffusion_nnx_amd import ops
     dev = torch.device('cuda:0')
     B, Fr, S, C = 4, 16, 64, 64

@@ -150,7 +150,7 @@ def test_bf16_storage_needs_bf16_mode_and_blocks_backward():
 
 
 def test_north_star_shape_bf16_storage():
-    """B = 4: 1024 level-0 tiles, so the persistent conv64p kernel, the one-wave-per-head attention / SLA kernels and the
+    """B = 4: 1024 level-0 tiles, so the persistent 64-channel conv kernels, the one-wave-per-head attention / SLA kernels and the
     16-byte tail all run in place, exactly as in the benchmark."""
     kw = dict(dim=64, channels=1)
     cfg = R.UnetConfig(**kw)
@@ -164,7 +164,7 @@ def test_north_star_shape_bf16_storage():
     m.load_state_dict(p)
     m.act_bf16 = True
     assert _rel(m(x, t).cpu().double(), ref) < TOL_ACT16
-    m.act_bf16 = False                                   # fp32 storage at the same batch: conv64p with fp32 / bf16 inputs mixed
+    m.act_bf16 = False                                   # fp32 storage at the same batch: conv64p (fp32 inputs) and conv64q (bf16 y1) mixed
     assert _rel(m(x, t).cpu().double(), ref) < TOL['bf16']
 
 

@@ -433,9 +433,6 @@ __global__ __launch_bounds__(512) void attention_h8_kernel(const AttnArgs P, con
     // (ds_write_b128 over 8-lane groups at a 132-dword row stride: conflict-free) instead of two 8-byte pieces whose 16 rows collide two
     // by two (39 % of the kernel's LDS cycles were those conflicts: profiles/r02_pmc_step.md).  The out-projection's weight fragments
     // are loaded with the same permutation of K, so the product is unchanged.
-#ifndef VDX_H8_DIAG
-#define VDX_H8_DIAG 0        // knock-out switches for timing experiments (tools/mkvariant.sh); none in the product build
-#endif
 #ifndef VDX_H8_OSP
 #define VDX_H8_OSP 2
 #endif
@@ -693,16 +690,10 @@ __global__ __launch_bounds__(512) void attention_h8_kernel(const AttnArgs P, con
             if (do_a) {
 #pragma unroll
                 for (int u = 0; u < XP; ++u) xres[PAR][u] = xpre[u];
-#if !(VDX_H8_DIAG & 4)
                 if (more) fetch(sg_first + (long)(it + 1) * 4);
-#endif
-#if !(VDX_H8_DIAG & 1)
                 phase_a(smem + PAR * BUF, os2[PAR]);
-#endif
             }
-#if !(VDX_H8_DIAG & 2)
             if (it >= 1 && it - 1 < nv) phase_b(os2[PAR ^ 1], ys2[PAR ^ 1]);
-#endif
             if (do_a && more) put(smem + (PAR ^ 1) * BUF);
             __syncthreads();
         };
@@ -748,10 +739,7 @@ static hipError_t launch_attn_h8_t(const AttnArgs& a, hipStream_t st) {
     constexpr int NBUF = (MODE == MODE_BF16 && NKT == 1) ? 2 : 1;     // PIPE (see the kernel): os and ys double-buffered
     const size_t lds = 2 * (size_t)NKT * 64 * ROW_STRIDE + NBUF * ((size_t)64 * (256 * M::ES + 16) + (size_t)64 * (NKT * M::KT * 4 + 16));
     auto kfn = attention_h8_kernel<MODE, NKT, TMO, TNO, IO16, F8, FULL>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const long subtiles = (a.nseq + 3) / 4;
     // sub-tiles per workgroup: the per-head weight fragments (12 KB per wave) are loaded once per workgroup, so fatter workgroups
     // amortise them as long as ~1024 workgroups remain to fill the chip
@@ -1027,26 +1015,20 @@ __global__ __launch_bounds__(64 * VDX_AW_NW) void attention_w_kernel(const AttnA
     }
 }
 
-#ifndef VDX_ATTN_W
-#define VDX_ATTN_W 1
-#endif
 static bool attn_w_eligible(const AttnArgs& a) {
-    return VDX_ATTN_W && a.io_bf16 && (a.C == 64 || a.C == 32) && a.CPad == 64 && a.HDPad == 256 && a.heads == 8 && a.L >= 1 && a.L <= 16 && a.inner % 4 == 0 &&
+    return a.io_bf16 && (a.C == 64 || a.C == 32) && a.CPad == 64 && a.HDPad == 256 && a.heads == 8 && a.L >= 1 && a.L <= 16 && a.inner % 4 == 0 &&
            a.nseq % 4 == 0 && a.nseq >= 256 && a.nseq < (1L << 29) && 3 * a.inner_stride + 15 * a.tok_stride + a.C < (1L << 30);
 }
 template <bool F8>
 static hipError_t launch_attn_w(const AttnArgs& a, hipStream_t st) {
     const size_t lds = 3 * 256 * 128 + (size_t)a.C * 512 + (3 * 256 + 64) * 4;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
     const long ngroups = a.nseq / VDX_AW_SB;
-    const long waves = std::min<long>((long)cus * VDX_AW_NW, ngroups);
-    const int gpw = (int)((ngroups + waves - 1) / waves);
-    const long blocks = (ngroups + (long)gpw * VDX_AW_NW - 1) / ((long)gpw * VDX_AW_NW);
+    const PersistentSplit s = persistent_split(ngroups, (long)device_cus() * VDX_AW_NW);      // over waves
+    const int gpw = (int)s.per;
+    const long blocks = (s.workers + VDX_AW_NW - 1) / VDX_AW_NW;
     const AttnWork aw = attn_work(a, 2, true);
     auto go = [&](auto kfn) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
         LaunchScope ls(st, "attention_w_kernel", aw.flops, aw.bytes, "<fp8 %d> C%d L%d nseq%ld", (int)F8, a.C, a.L, a.nseq);
         hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(64 * VDX_AW_NW), lds, st, a, gpw, ngroups);
         return hipGetLastError();
@@ -1216,10 +1198,7 @@ hipError_t launch_attention_heads(AttnArgs a, hipStream_t st) {
     spb = (spb + 8 * NS - 1) / (8 * NS) * (8 * NS);
     const long chunks = (a.nseq + spb - 1) / spb;
     auto go = [&](auto kfn) -> hipError_t {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
         const AttnWork aw = attn_work(a, 2, false);
         LaunchScope ls(st, "attention_head_kernel", aw.flops, aw.bytes, "<io16 %d, %d, fp8 %d, lt %d> C%d L%d nseq%ld", a.io_bf16, TT, a.fp8_core, LT, a.C, a.L, a.nseq);
         hipLaunchKernelGGL(kfn, dim3((unsigned)((chunks + 7) / 8 * 64)), dim3(512), lds, st, a, (int)spb, (int)chunks);
@@ -1263,10 +1242,7 @@ static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t st) {
     constexpr int RSV = NCHL * 64 + 16;
     const size_t lds = 512 + (size_t)(64 * 4 + 96) * ROW_STRIDE + (size_t)(NSEQ * 32 + 64) * RSV;
     auto kfn = attention_kernel<MODE, LP, TMO>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const long blocks = (a.nseq + NSEQ - 1) / NSEQ;
     const AttnWork aw = attn_work(a, Mma<MODE>::ES, true);
     LaunchScope ls(st, "attention_kernel", aw.flops, aw.bytes, "<%d, %d, %d> C%d L%d nseq%ld io16 %d", MODE, LP, TMO, a.C, a.L, a.nseq, a.io_bf16);
@@ -1286,12 +1262,10 @@ static hipError_t launch_attn_l(const AttnArgs& a, hipStream_t st) {
 
 template <int MODE>
 static hipError_t launch_attn_m(const AttnArgs& a, hipStream_t st) {
-    const bool use_reg = true;        // debugging switch: force the LDS-staged kernel
-    const bool use_h8 = true;        // debugging switch: skip the one-wave-per-head kernel
     const bool h8_ok = a.L <= 16 && a.heads == 8 && a.inner % 4 == 0 && a.nseq % 4 == 0 && a.nseq < (1L << 31) &&
                        3 * a.inner_stride + 15 * a.tok_stride + a.C < (1L << 31);
     if constexpr (MODE != MODE_F16) {                  // (the one-wave-per-head kernels hard-code the bf16 / f32 register formats)
-    if (h8_ok && use_reg && use_h8) {
+    if (h8_ok) {
         const int nkt = a.CPad / Mma<MODE>::KT;
         if constexpr (MODE == MODE_BF16) {
             if (a.fp8_core) {                                 // fp8 QK^T / PV (vdx_set_attention_fp8)
@@ -1313,8 +1287,12 @@ static hipError_t launch_attn_m(const AttnArgs& a, hipStream_t st) {
         if (a.C == 128 && nkt == 2) return launch_attn_h8_t<MODE, 2, 1, 4, false>(a, st);
     }
     }
-    if (a.L <= 16 && use_reg && !(MODE == MODE_F32 && a.C > 512)) return launch_attn_reg<MODE>(a, st);    // (f32 weight tiles of C = 1024 exceed the LDS: staged form)
-    if (a.L <= 16) return launch_attn_l<MODE, 16>(a, st);
+    if (a.L <= 16) {
+        if constexpr (MODE == MODE_F32) {              // f32 weight tiles of 512 < C <= 1024 exceed the LDS: staged form
+            if (a.C > 512) return a.C <= 1024 ? launch_attn_t<MODE, 16, 16>(a, st) : hipErrorInvalidValue;
+        }
+        return launch_attn_reg<MODE>(a, st);
+    }
     if (a.L <= 32) return launch_attn_l<MODE, 32>(a, st);
     if (a.L <= 64) return launch_attn_l<MODE, 64>(a, st);
     return hipErrorInvalidValue;
@@ -1368,10 +1346,7 @@ hipError_t launch_attention_long_core(const float* qkv, float* o, long nseq, int
     const size_t lds = (size_t)L * 64 * 4;
     if (lds > 160 * 1024 || nseq <= 0 || nseq >= (1L << 31)) return hipErrorInvalidValue;            // L <= 640 tokens
     auto kfn = attention_long_core_kernel;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     LaunchScope ls(st, "attention_long_core_kernel", 4.0 * nseq * L * L * heads * 32, 4.0 * nseq * L * heads * 32 * 4, "L%d nseq%ld heads%d", L, nseq, heads);
     hipLaunchKernelGGL(kfn, dim3((unsigned)nseq, heads), dim3(256), lds, st, qkv, o, L, heads, scale);
     return hipGetLastError();

@@ -383,12 +383,9 @@ hipError_t launch_attn_bwd_fused(const AttnBwdXArgs& a, hipStream_t st) {
     if (a.L < 1 || a.L > 16 || a.nseq < 1) return hipErrorInvalidValue;
     const size_t lds = (size_t)768 * AX_RSW + 768 * 4 + (size_t)8 * 4 * 16 * AB_RS;
     auto kfn = attn_bwd16x_kernel;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const long want = (a.nseq + 7) / 8;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)std::min<long>(want, cus)), dim3(512), lds, st, a);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)std::min<long>(want, device_cus())), dim3(512), lds, st, a);
     return hipGetLastError();
 }
 
@@ -780,10 +777,7 @@ hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st) {
     }
     const size_t lds = ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
     auto kfn = attn_core_bwd_kernel;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kfn, dim3((unsigned)a.nseq, (unsigned)a.heads), dim3(256), lds, st, a);
     return hipGetLastError();
 }

@@ -399,12 +399,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && TN == 2) ? 4 : 2) void conv_ig
 #ifndef VDX_C32_PRO_WAVES
 #define VDX_C32_PRO_WAVES 2     // waves per SIMD the C = 32 prologue form is compiled for: 2 = one workgroup per CU, no scratch (Y-shape step 9.66 ms); 4 = two per CU with 156 bytes of scratch (10.03 ms)
 #endif
-#ifndef VDX_C64P_EARLY
-#define VDX_C64P_EARLY 0      // 1: issue the loads of tile t + 2 inside the tap loop of tile t (measured SLOWER: 495 vs 413 us, r03)
-#endif
-#ifndef VDX_C64P_DIAG
-#define VDX_C64P_DIAG 0      // knock-out switches of conv64p_kernel for timing experiments; none in the product build
-#endif
 constexpr int C64_HALO = 18 * 18;
 __device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + 16 * (chunk ^ (row & 7)); }
 // the same for rows of C bf16 channels: C = 32 -> 64-byte rows of 4 chunks, chunk ^= 2 on rows with bit 2 set (conflict-free for the
@@ -414,10 +408,12 @@ template <int C> __device__ __forceinline__ int swz_c(int row, int chunk) {
     else return row * 64 + 16 * (chunk ^ ((row >> 1) & 2));
 }
 
-// PRO / OUT16 / RES: prologue present, bf16 output, residual epilogue (plain form only: the data gradient of a ResnetBlock's first
-// conv) -- compile-time, so the unused path costs no registers or issue slots
-// C = Cin = Cout: 64 (levels 0 / 1 of the N shape) or 32 (level 0 of the YAML-literal config_v2_2: one 32-deep K chunk, two output-channel
-// tiles, 64-byte LDS rows -- memory-bound, 36 MFMAs per wave and tile)
+// The product build runs two roles of it (bf16 64 -> 64 convs go to conv64q / conv64r / conv64d below):
+//   C = 64, fp32 input (IN16 = false: bf16 mode with fp32 activation storage), with or without the prologue;
+//   C = 32, bf16 tensors (level 0 of the YAML-literal config_v2_2: one 32-deep K chunk, two output-channel tiles, 64-byte LDS rows --
+//   memory-bound, 36 MFMAs per wave and tile).
+// PRO / OUT16: prologue present, bf16 output -- compile-time, so the unused path costs no registers or issue slots.  RES is always false
+// (the residual form is conv64d_kernel).
 template <bool IN16, bool PRO, bool OUT16, bool RES = false, int C = 64>
 __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) void conv64p_kernel(const ConvArgs P, const int tiles_per_block, const int total_tiles) {
     using M = Mma<MODE_BF16>;
@@ -425,7 +421,7 @@ __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) v
     constexpr int PPR = C / PCH;                      // pieces per pixel
     constexpr int RB = C * 2;                         // LDS row bytes (bf16)
     constexpr int NTM = C / 16, NCH = C / 32;         // output-channel tiles, 32-deep K chunks
-    static_assert(C == 64 || (C == 32 && IN16 && !RES), "C = 32: bf16 tensors, no residual epilogue");
+    static_assert(!RES && IN16 == (C == 32), "C = 64: fp32 input; C = 32: bf16 tensors; no residual epilogue");
     auto swz = [](int row, int chunk) __attribute__((always_inline)) { return swz_c<C>(row, chunk); };
     constexpr int NPIECE = C64_HALO * PPR;
     constexpr int NU = (NPIECE + 511) / 512;
@@ -496,7 +492,7 @@ __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) v
             const bool ok = (okmask >> u) & 1u;
             if (IN16) {
                 u32x4 v = sreg[u];
-                if (PRO && !(VDX_C64P_DIAG & 2)) {
+                if (PRO) {
                     float ca[PCH], cd[PCH];                           // (LDS broadcast-free reads: 4 x 16 B per piece; registers spilled, r02)
 #pragma unroll
                     for (int k = 0; k < PCH; k += 4) {
@@ -588,14 +584,12 @@ __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) v
     // The global loads of tile t + 1 are issued as soon as the staging registers are free -- right after tile t has been written to LDS,
     // i.e. inside the tap loop of tile t - 1 -- not at the top of tile t: the epilogue, the barrier and ~2 taps more of latency slack (the
     // knock-out timings of round 3: tap loop and memory pipeline did not overlap, 224 us of 420 was the load -> LDS -> store skeleton alone)
-    bool preloaded = false;
     for (int t = t0; t < t1; ++t) {
         const int buf = (t - t0) & 1;
         const bool more = t + 1 < t1;
         int fn = fcur, tyn = tyc, txn = txc, bn = bcur;
         if (more) {
-            if (!preloaded) stage_load(t + 1);
-            preloaded = false;
+            stage_load(t + 1);
             decode(t + 1, fn, tyn, txn);
             bn = fn / P.F;
             if (bn != bcoef) { make_coef(bn); bcoef = bn; }          // uniform; nobody reads the coefficients during the MFMAs
@@ -605,17 +599,6 @@ __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) v
         f32x4 acc[NTM][2];
 #pragma unroll
         for (int i = 0; i < NTM; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        // residual epilogue (the data gradient of a ResnetBlock's first conv: + the gradient of the skip path), plain form only:
-        // fetched before the MFMAs so that the epilogue does not wait for it
-        float4 rpre[RES ? 4 : 1][2];
-        if constexpr (RES) {
-            const int oy0 = tyc * 16 + 2 * wave, ox = txc * 16 + lp;
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm)
-                    rpre[tm][tn] = *reinterpret_cast<const float4*>(P.res + ((size_t)(fcur * P.H + oy0 + tn) * P.W + ox) * 64 + tm * 16 + 4 * q);   // fp32 res only: 8 plain loads, no format branch between them
-        }
         const char* At = Al + buf * (C64_HALO * RB);
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
@@ -623,13 +606,10 @@ __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) v
             // With a prologue the write is VALU work (SiLU): two pieces per tap over three taps, and the two waves of a SIMD (w, w + 4)
             // take DIFFERENT taps, so one wave's VALU block runs under the other's MFMAs instead of both stalling the matrix pipe at once
             if (more) {
-                if (!PRO) { if (tap == 5) { stage_store(buf ^ 1); if (VDX_C64P_EARLY && t + 2 < t1) { stage_load(t + 2); preloaded = true; } } }
+                if (!PRO) { if (tap == 5) stage_store(buf ^ 1); }
                 else {
                     const int first = wave_u < 4 ? 4 : 6;
-                    if (tap >= 4 && tap - first >= 0 && tap - first < 3) {
-                        stage_store(buf ^ 1, 2 * (tap - first), tap - first == 2 ? NU : 2 * (tap - first) + 2);
-                        if (VDX_C64P_EARLY && tap - first == 2 && t + 2 < t1) { stage_load(t + 2); preloaded = true; }      // (wave-uniform)
-                    }
+                    if (tap >= 4 && tap - first >= 0 && tap - first < 3) stage_store(buf ^ 1, 2 * (tap - first), tap - first == 2 ? NU : 2 * (tap - first) + 2);
                 }
             }
             const int dy = tap / 3, dx = tap % 3;
@@ -638,7 +618,7 @@ __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) v
             for (int tn = 0; tn < 2; ++tn) { const int hp = hpb[tn] + dy * 18 + dx; boff[tn] = swz(hp, q); }
             const int woff = swz(tap * C + lp, q);
 #pragma unroll
-            for (int ch = 0; ch < ((VDX_C64P_DIAG & 4) ? 0 : NCH); ++ch) {
+            for (int ch = 0; ch < NCH; ++ch) {
                 uint4 af[NTM], bf[2];
 #pragma unroll
                 for (int tm = 0; tm < NTM; ++tm) af[tm] = *reinterpret_cast<const uint4*>(Wl + ((woff + tm * 16 * RB) ^ (ch * 64)));
@@ -651,9 +631,6 @@ __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) v
             }
         }
         // ---- epilogue of tile t ----
-#if VDX_C64P_DIAG & 1
-        if (acc[0][0][0] == 12345.678f && acc[1][1][1] == 3.f && acc[2][0][2] == 1.f && acc[3][1][3] == 7.f)     // diagnostic: no epilogue (never true on real data)
-#endif
         {
             const int oy0 = tyc * 16 + 2 * wave, ox = txc * 16 + lp;
             float4 bias4[NTM];
@@ -664,8 +641,7 @@ __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) v
                 const unsigned gout = (unsigned)(((fcur * P.H + oy0 + tn) * P.W + ox) * C + 4 * q);
 #pragma unroll
                 for (int tm = 0; tm < NTM; ++tm) {
-                    float4 v = make_float4(acc[tm][tn][0] + bias4[tm].x, acc[tm][tn][1] + bias4[tm].y, acc[tm][tn][2] + bias4[tm].z, acc[tm][tn][3] + bias4[tm].w);
-                    if constexpr (RES) { const float4 r4 = rpre[tm][tn]; v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
+                    const float4 v = make_float4(acc[tm][tn][0] + bias4[tm].x, acc[tm][tn][1] + bias4[tm].y, acc[tm][tn][2] + bias4[tm].z, acc[tm][tn][3] + bias4[tm].w);
                     if constexpr (OUT16) __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack_bf16x2(v.x, v.y), pack_bf16x2(v.z, v.w)}, rsy, (gout + tm * 16) * 2u, 0, 0);
                     else __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)}, rsy, (gout + tm * 16) * 4u, 0, 0);
                     ssum[tm][0] += v.x; ssum[tm][1] += v.y; ssum[tm][2] += v.z; ssum[tm][3] += v.w;
@@ -685,19 +661,11 @@ __global__ __launch_bounds__(512, C == 32 ? (PRO ? VDX_C32_PRO_WAVES : 4) : 2) v
 // through the tap loop, applies the prologue and writes the tile with ds_write_b128; its prologue form sits on the 256-register limit
 // with a 60-byte spill and 39 % of its wave life is spent parked (rocprofv3 PMC, profiles/r02_pmc_step.md).  Here the next tile lands
 // in the other LDS buffer by global_load_lds (lane l fetches the chunk that belongs at its swizzled position, out-of-image pieces
-// read a zero page: conv128x64p_kernel's scheme) -- no staging registers, no LDS store instructions.  Plain form only (no prologue;
-// optional residual epilogue): 254 -> 245 us per launch at B = 64.  The prologue form was built the same way (every thread
-// transforming the pieces it issued in place behind counted vmcnt waits, coefficients in registers) and measured SLOWER than the
-// register-staged conv64p_kernel (340 vs 323 us: the in-place pass adds a ds_read_b128 per piece and its waits), so it is not kept.
-#ifndef VDX_C64D_LATEWAIT
-#define VDX_C64D_LATEWAIT 1
-#endif
-#ifndef VDX_C64D_SWP
-#define VDX_C64D_SWP 0
-#endif
-#ifndef VDX_C64D_DIAG
-#define VDX_C64D_DIAG 0      // knock-out switches for timing experiments (tools/mkvariant.sh); the product build has none
-#endif
+// read a zero page) -- no staging registers, no LDS store instructions.  No prologue: 254 -> 245 us per launch at B = 64.  The product
+// build runs only the residual form (RES = true: the data gradient of a ResnetBlock's first conv, fp32 residual); the plain form is
+// conv64r_kernel.  The prologue form was built the same way (every thread transforming the pieces it issued in place behind counted
+// vmcnt waits, coefficients in registers) and measured SLOWER than the register-staged conv64p_kernel (340 vs 323 us: the in-place pass
+// adds a ds_read_b128 per piece and its waits), so it is not kept.
 constexpr int C64D_AROWS = 328;                       // 324 halo rows padded to 41 DMA instructions of 8 rows
 constexpr int C64D_APL = C64D_AROWS * 128;
 __device__ __attribute__((aligned(16))) unsigned g_zero_page_c64d[4];
@@ -705,6 +673,7 @@ __device__ __attribute__((aligned(16))) unsigned g_zero_page_c64d[4];
 template <bool OUT16, bool RES>
 __global__ __launch_bounds__(512) void conv64d_kernel(const ConvArgs P, const int tiles_per_block, const int total_tiles) {
     using M = Mma<MODE_BF16>;
+    static_assert(RES, "the plain form is conv64r_kernel");
     constexpr int NDMA = 41, NK = (NDMA + 7) / 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Wl = smem;                                  // [9 * 64 rows][128 B]
@@ -796,15 +765,13 @@ __global__ __launch_bounds__(512) void conv64d_kernel(const ConvArgs P, const in
         if (more) {
             decode(t + 1, fn, tyn, txn);
             bn = fn / P.F;
-#if !(VDX_C64D_DIAG & 2)
             dma(t + 1, buf ^ 1);                      // the other buffer was last read during tile t - 1 (barrier since)
-#endif
         }
         f32x4 acc[4][2];
 #pragma unroll
         for (int i = 0; i < 4; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        float4 rpre[RES ? 4 : 1][2];
-        if constexpr (RES) {                          // (fp32 residual: issued after the DMA, so the waits below cover it)
+        float4 rpre[4][2];                            // (fp32 residual: issued after the DMA, so the waits below cover it)
+        {
             const int oy0 = tyc * 16 + 2 * wave, ox = txc * 16 + lp;
 #pragma unroll
             for (int tn = 0; tn < 2; ++tn)
@@ -813,44 +780,6 @@ __global__ __launch_bounds__(512) void conv64d_kernel(const ConvArgs P, const in
                     rpre[tm][tn] = *reinterpret_cast<const float4*>(P.res + ((size_t)(fcur * P.H + oy0 + tn) * P.W + ox) * 64 + tm * 16 + 4 * q);
         }
         const char* At = Al + buf * C64D_APL;
-#if VDX_C64D_DIAG & 4
-        uint4 af_once[4], bf_once[2];
-#endif
-#if VDX_C64D_SWP
-        // software pipeline over the 18 (tap, K chunk) steps: the 6 fragment reads of step s + 1 are issued BEFORE the 8 MFMAs of step s
-        // (two register sets), so an MFMA never waits a whole LDS round trip for reads issued right in front of it.  The compiler's own
-        // order puts each pair of reads 2-4 MFMAs ahead of its use with an s_waitcnt behind it: MFMA busy 45 % (profiles/r02_pmc_step.md)
-        auto frag_load = [&](int st, uint4 (&af)[4], uint4 (&bf)[2]) __attribute__((always_inline)) {
-            const int tap = st >> 1, ch = st & 1, dy = tap / 3, dx = tap % 3;
-            const int woff = swz(tap * 64 + lp, q);
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm) af[tm] = *reinterpret_cast<const uint4*>(Wl + ((woff + tm * 16 * 128) ^ (ch * 64)));
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn) bf[tn] = *reinterpret_cast<const uint4*>(At + (swz(hpb[tn] + dy * 18 + dx, q) ^ (ch * 64)));
-        };
-        uint4 af[2][4], bf[2][2];
-        frag_load(0, af[0], bf[0]);
-#pragma unroll
-        for (int st = 0; st < 18; ++st) {
-            if (st + 1 < 18) frag_load(st + 1, af[(st + 1) & 1], bf[(st + 1) & 1]);
-#if VDX_C64D_SWP == 1
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-#pragma unroll
-            for (int tm = 0; tm < 4; ++tm)
-#pragma unroll
-                for (int tn = 0; tn < 2; ++tn) M::mma(acc[tm][tn], af[st & 1][tm], bf[st & 1][tn]);
-#if VDX_C64D_SWP == 1
-            __builtin_amdgcn_sched_barrier(0);
-#else
-            if (st + 1 < 18) {                                     // one read behind each of the first six MFMAs of the step
-#pragma unroll
-                for (int i = 0; i < 6; ++i) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); }
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-            } else __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
-#endif
-        }
-#else
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int dy = tap / 3, dx = tap % 3;
@@ -860,36 +789,17 @@ __global__ __launch_bounds__(512) void conv64d_kernel(const ConvArgs P, const in
             const int woff = swz(tap * 64 + lp, q);
 #pragma unroll
             for (int ch = 0; ch < 2; ++ch) {
-#if VDX_C64D_DIAG & 4
-                uint4 (&af)[4] = af_once; uint4 (&bf)[2] = bf_once;                     // diagnostic: no fragment reads inside the tap loop
-                if (tap == 0 && ch == 0) {
-#else
                 uint4 af[4], bf[2];
-                {
-#endif
 #pragma unroll
                 for (int tm = 0; tm < 4; ++tm) af[tm] = *reinterpret_cast<const uint4*>(Wl + ((woff + tm * 16 * 128) ^ (ch * 64)));
 #pragma unroll
                 for (int tn = 0; tn < 2; ++tn) bf[tn] = *reinterpret_cast<const uint4*>(At + (boff[tn] ^ (ch * 64)));
-                }
-#if VDX_C64D_DIAG & 8
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm) acc[tm][0][0] += __uint_as_float((af[tm].x ^ bf[0].y ^ bf[1].z) & 0x3F800000u);      // diagnostic: reads only, no MFMA
-#else
 #pragma unroll
                 for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
                     for (int tn = 0; tn < 2; ++tn) M::mma(acc[tm][tn], af[tm], bf[tn]);
-#endif
             }
         }
-#endif
-#if !VDX_C64D_LATEWAIT
-        wait_vm<0>();                                 // the next tile has landed (before the stores below: the wait covers the DMA only)
-#endif
-#if VDX_C64D_DIAG & 1
-        if (acc[0][0][0] == 12345.678f && acc[1][1][1] == 3.f && acc[2][0][2] == 1.f && acc[3][1][3] == 7.f)     // diagnostic: no epilogue (never true on real data)
-#endif
         {
             const int oy0 = tyc * 16 + 2 * wave, ox = txc * 16 + lp;
 #pragma unroll
@@ -898,17 +808,15 @@ __global__ __launch_bounds__(512) void conv64d_kernel(const ConvArgs P, const in
 #pragma unroll
                 for (int tm = 0; tm < 4; ++tm) {
                     float4 v = make_float4(acc[tm][tn][0] + bias4[tm].x, acc[tm][tn][1] + bias4[tm].y, acc[tm][tn][2] + bias4[tm].z, acc[tm][tn][3] + bias4[tm].w);
-                    if constexpr (RES) { const float4 r4 = rpre[tm][tn]; v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w; }
+                    const float4 r4 = rpre[tm][tn]; v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
                     store4_f32_or_bf16(P.y, gout + tm * 16 + 4 * q, v, OUT16 ? 1 : 0);
                     ssum[tm][0] += v.x; ssum[tm][1] += v.y; ssum[tm][2] += v.z; ssum[tm][3] += v.w;
                     ssq[tm][0] += v.x * v.x; ssq[tm][1] += v.y * v.y; ssq[tm][2] += v.z * v.z; ssq[tm][3] += v.w * v.w;
                 }
             }
         }
-#if VDX_C64D_LATEWAIT
         wait_vm<8>();                                 // everything older than this tile's 8 stores -- the next tile's DMA -- has landed: the
                                                       // epilogue's arithmetic and store issue overlap the tail of the DMA instead of following it
-#endif
         if (more && bn != bcur) { flush_stats(bcur); bcur = bn; }    // uniform: the next tile belongs to another sample
         fcur = fn; tyc = tyn; txc = txn;
         __syncthreads();                              // next tile landed everywhere; everybody is done reading this one
@@ -916,26 +824,20 @@ __global__ __launch_bounds__(512) void conv64d_kernel(const ConvArgs P, const in
     flush_stats(bcur);
 }
 
-static hipError_t launch_conv64d(const ConvArgs& a, hipStream_t st) {
+// the persistent 16 x 16-tile kernels of this file: 512-thread workgroups, at most `slots` of them, each walking a contiguous tile range
+template <typename K>
+static hipError_t launch_tiles16(K kfn, const ConvArgs& a, size_t lds, long slots, hipStream_t st) {
     const int total = a.NF * (a.H >> 4) * (a.W >> 4);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-    const int grid = std::min(total, cus);
-    const int tpb = (total + grid - 1) / grid;
-    const int nblocks = (total + tpb - 1) / tpb;
+    const PersistentSplit s = persistent_split(total, slots);
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)s.workers), dim3(512), lds, st, a, (int)s.per, total);
+    return hipGetLastError();
+}
+
+static hipError_t launch_conv64d(const ConvArgs& a, hipStream_t st) {
+    if (a.pro || !a.x0_bf16 || !a.res || a.res_bf16) return hipErrorInvalidValue;
     const size_t lds = 9 * 64 * 128 + 2 * (size_t)C64D_APL + 128 * 8;
-    auto launch = [&](auto kfn) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kfn, dim3(nblocks), dim3(512), lds, st, a, tpb, total);
-        return hipGetLastError();
-    };
-    if (a.pro || !a.x0_bf16) return hipErrorInvalidValue;
-    if (a.res) {
-        if (a.res_bf16) return hipErrorInvalidValue;
-        return a.y_bf16 ? launch(conv64d_kernel<true, true>) : launch(conv64d_kernel<false, true>);
-    }
-    return a.y_bf16 ? launch(conv64d_kernel<true, false>) : launch(conv64d_kernel<false, false>);
+    return launch_tiles16(a.y_bf16 ? conv64d_kernel<true, true> : conv64d_kernel<false, true>, a, lds, device_cus(), st);
 }
 
 // ---- weights-in-registers form of the persistent 64 -> 64 conv (bf16 tensors, no prologue): "conv64r" ---------------------------------
@@ -946,9 +848,6 @@ static hipError_t launch_conv64d(const ConvArgs& a, hipStream_t st) {
 // no weight image in LDS, so THREE input tiles fit (two tiles of LDS-DMA in flight: a tile has two periods to land), and a step reads 4
 // pixel fragments for 8 MFMAs (72 reads per wave and tile instead of 108).  Swizzle key of a halo row = its COLUMN, so a fragment address
 // is a register per (dx, K chunk) + the wave's row base + an immediate.
-#ifndef VDX_C64R_DIAG
-#define VDX_C64R_DIAG 0            // timing knock-outs (wrong results): 1 = no MFMAs, 2 = no fragment reads
-#endif
 template <bool OUT16>
 __global__ __launch_bounds__(512) void conv64r_kernel(const ConvArgs P, const int tiles_per_block, const int total_tiles) {
     using M = Mma<MODE_BF16>;
@@ -1064,10 +963,7 @@ __global__ __launch_bounds__(512) void conv64r_kernel(const ConvArgs P, const in
         uint4 bf[2][3];                                  // fragments of step s = 2 hr + ch in bf[s & 1]: step s + 1 is read before step s's MFMAs
         auto frag_read = [&](uint4 (&d)[3], int hr, int ch) {
 #pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                if constexpr (VDX_C64R_DIAG & 2) d[dx] = uint4{(unsigned)lane, (unsigned)dx, (unsigned)t, (unsigned)ch};
-                else d[dx] = *reinterpret_cast<const uint4*>(At + bdx[dx][ch] + hr * (18 * 128));
-            }
+            for (int dx = 0; dx < 3; ++dx) d[dx] = *reinterpret_cast<const uint4*>(At + bdx[dx][ch] + hr * (18 * 128));
         };
         frag_read(bf[0], 0, 0);
 #pragma unroll
@@ -1085,10 +981,7 @@ __global__ __launch_bounds__(512) void conv64r_kernel(const ConvArgs P, const in
                         const int tn = hr - dy;
                         if (tn < 0 || tn > 3) continue;
 #pragma unroll
-                        for (int tm = 0; tm < 2; ++tm) {
-                            if constexpr (VDX_C64R_DIAG & 1) acc[tm][tn][0] += __uint_as_float(bf[s_ & 1][dx].x ^ wf[dy * 3 + dx][ch][tm].x);
-                            else M::mma(acc[tm][tn], wf[dy * 3 + dx][ch][tm], bf[s_ & 1][dx]);
-                        }
+                        for (int tm = 0; tm < 2; ++tm) M::mma(acc[tm][tn], wf[dy * 3 + dx][ch][tm], bf[s_ & 1][dx]);
                     }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1126,21 +1019,9 @@ __global__ __launch_bounds__(512) void conv64r_kernel(const ConvArgs P, const in
 }
 
 static hipError_t launch_conv64r(const ConvArgs& a, hipStream_t st) {
-    const int total = a.NF * (a.H >> 4) * (a.W >> 4);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-    const int grid = std::min(total, cus);
-    const int tpb = (total + grid - 1) / grid;
-    const int nblocks = (total + tpb - 1) / tpb;
-    const size_t lds = 3 * (size_t)C64D_APL + 128 * 8 + 64 * 4;
-    auto launch = [&](auto kfn) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kfn, dim3(nblocks), dim3(512), lds, st, a, tpb, total);
-        return hipGetLastError();
-    };
     if (a.pro || !a.x0_bf16 || a.res) return hipErrorInvalidValue;
-    return a.y_bf16 ? launch(conv64r_kernel<true>) : launch(conv64r_kernel<false>);
+    const size_t lds = 3 * (size_t)C64D_APL + 128 * 8 + 64 * 4;
+    return launch_tiles16(a.y_bf16 ? conv64r_kernel<true> : conv64r_kernel<false>, a, lds, device_cus(), st);
 }
 
 // ---- "conv64q": the weights-in-registers scheme with 16 output channels x 128 pixels per wave ------------------------------------------
@@ -1460,20 +1341,9 @@ __global__ __launch_bounds__(512) void conv64q_kernel(const ConvArgs P, const in
 }
 
 static hipError_t launch_conv64q(const ConvArgs& a, hipStream_t st) {
-    const int total = a.NF * (a.H >> 4) * (a.W >> 4);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-    const int grid = std::min(total, cus);
-    const int tpb = (total + grid - 1) / grid;
-    const int nblocks = (total + tpb - 1) / tpb;
-    const size_t lds = 3 * (size_t)C64D_APL + 128 * 8 + 64 * 4 + (64 + 64 + 64) * 4;
-    auto launch = [&](auto kfn) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kfn, dim3(nblocks), dim3(512), lds, st, a, tpb, total);
-        return hipGetLastError();
-    };
     if (!a.x0_bf16 || a.res || (a.C1 && !a.x1_bf16)) return hipErrorInvalidValue;
+    const size_t lds = 3 * (size_t)C64D_APL + 128 * 8 + 64 * 4 + (64 + 64 + 64) * 4;
+    auto launch = [&](auto kfn) { return launch_tiles16(kfn, a, lds, device_cus(), st); };
     if (a.Cout == 32) {                               // dim-32 networks: 64 (= 32 + 32 or 64) or 128 (= 64 + 64) input channels, bf16 output
         if (a.pro || !a.y_bf16) return hipErrorInvalidValue;
         return a.C0 + a.C1 == 128 ? launch(conv64q_kernel<128, false, true, 32>) : launch(conv64q_kernel<64, false, true, 32>);
@@ -1482,235 +1352,23 @@ static hipError_t launch_conv64q(const ConvArgs& a, hipStream_t st) {
         if (a.pro) return hipErrorInvalidValue;
         return a.y_bf16 ? launch(conv64q_kernel<128, false, true>) : launch(conv64q_kernel<128, false, false>);
     }
-    if (a.pro) return a.y_bf16 ? launch(conv64q_kernel<64, true, true>) : launch(conv64q_kernel<64, true, false>);
-    return a.y_bf16 ? launch(conv64q_kernel<64, false, true>) : launch(conv64q_kernel<64, false, false>);
+    if (!a.pro) return hipErrorInvalidValue;          // (the plain 64 -> 64 conv is conv64r_kernel)
+    return a.y_bf16 ? launch(conv64q_kernel<64, true, true>) : launch(conv64q_kernel<64, true, false>);
 }
 
 static hipError_t launch_conv64p(const ConvArgs& a, hipStream_t st) {
-    const int total = a.NF * (a.H >> 4) * (a.W >> 4);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-    const int grid = std::min(total, cus);
-    const int tpb = (total + grid - 1) / grid;
-    const int nblocks = (total + tpb - 1) / tpb;
-    const size_t lds = 9 * 64 * 128 + 2 * (size_t)C64_HALO * 128 + (64 + 64 + 64) * 4 + 128 * 8 + 64 * 4;      // weights, 2 halo tiles, coefA / coefD / gmean, chs, bias
-    auto launch = [&](auto kfn) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kfn, dim3(nblocks), dim3(512), lds, st, a, tpb, total);
-        return hipGetLastError();
-    };
-    const int v = (a.x0_bf16 ? 4 : 0) | (a.pro ? 2 : 0) | (a.y_bf16 ? 1 : 0);
+    if (a.res) return hipErrorInvalidValue;
     if (a.Cout == 32) {                               // C = 32 form: bf16 tensors only; 62 KB of LDS, two workgroups per CU
-        if (!a.x0_bf16 || !a.y_bf16 || a.res) return hipErrorInvalidValue;
-        const int grid2 = std::min(total, ((a.pro ? VDX_C32_PRO_WAVES : 4) / 2) * cus), tpb2 = (total + grid2 - 1) / grid2, nb2 = (total + tpb2 - 1) / tpb2;
-        const size_t lds2 = 9 * 32 * 64 + 2 * (size_t)C64_HALO * 64 + (64 + 64 + 64) * 4 + 128 * 8 + 64 * 4;
-        auto launch2 = [&](auto kfn) -> hipError_t {
-            hipLaunchKernelGGL(kfn, dim3(nb2), dim3(512), lds2, st, a, tpb2, total);
-            return hipGetLastError();
-        };
-        return a.pro ? launch2(conv64p_kernel<true, true, true, false, 32>) : launch2(conv64p_kernel<true, false, true, false, 32>);
+        if (!a.x0_bf16 || !a.y_bf16) return hipErrorInvalidValue;
+        const size_t lds = 9 * 32 * 64 + 2 * (size_t)C64_HALO * 64 + (64 + 64 + 64) * 4 + 128 * 8 + 64 * 4;
+        const long slots = (long)((a.pro ? VDX_C32_PRO_WAVES : 4) / 2) * device_cus();
+        return launch_tiles16(a.pro ? conv64p_kernel<true, true, true, false, 32> : conv64p_kernel<true, false, true, false, 32>, a, lds, slots, st);
     }
-    if (a.res) {
-        if (a.pro || !a.x0_bf16 || a.res_bf16) return hipErrorInvalidValue;      // (the fp32-input form with 32 more registers would spill)
-        return a.y_bf16 ? launch(conv64p_kernel<true, false, true, true>) : launch(conv64p_kernel<true, false, false, true>);
-    }
-    switch (v) {
-        case 0: return launch(conv64p_kernel<false, false, false>);
-        case 1: return launch(conv64p_kernel<false, false, true>);
-        case 2: return launch(conv64p_kernel<false, true, false>);
-        case 3: return launch(conv64p_kernel<false, true, true>);
-        case 4: return launch(conv64p_kernel<true, false, false>);
-        case 5: return launch(conv64p_kernel<true, false, true>);
-        case 6: return launch(conv64p_kernel<true, true, false>);
-        default: return launch(conv64p_kernel<true, true, true>);
-    }
-}
-
-// ---- persistent 3x3 conv with Cin = 128 (two-pointer concat of 64 + 64, or one 128-channel tensor), Cout = 64, bf16 inputs ----
-// Same scheme as conv64p_kernel, but a workgroup owns HALF of the output channels (32 x 128 x 9 bf16 weights = 72 KB resident);
-// two workgroups on the same XCD walk the same tile range, so the second reader of a tile finds it in L2.
-// The 128-channel halo tile does not fit twice beside the weights, so the pipeline runs in PLANE steps (round 2, second form): the
-// two 64-channel planes of the input have one LDS buffer each; while the 72 MFMAs of plane 0 of tile t run, plane 1 of tile t
-// lands in the other buffer by LDS-DMA (global_load_lds, no staging registers, no LDS store instructions), and while plane 1 runs,
-// plane 0 of tile t + 1 lands in the first.  One s_waitcnt vmcnt(0) + barrier per plane step.  (First form: both planes single-
-// buffered, next tile prefetched into 44 registers and written between two barriers with the matrix pipe idle: 758 us per launch at
-// B = 64; this form 626 us.  The MFMA phase itself is LDS-read bound -- one ds_read_b128 per MFMA with 32 x 32 wave tiles.  Measured
-// without gain on top of it: fragment reads software-pipelined two groups ahead of their MFMAs (626 us: LDS latency is not what is
-// exposed); the LDS-DMA pieces issued one per MFMA group instead of all after the barrier (667 us).)
-// A wave-instruction of the DMA covers 8 halo rows x 128 B; lane l fetches the global chunk (l & 7) ^ (l >> 3) of row l >> 3 so that
-// it lands at the swizzled position.  Out-of-image pieces read a zero page.  No prologue (these are the first convs of
-// ResnetBlocks whose input is a concat).
-constexpr int C128_WPL = 9 * 32 * 128;                // bytes per weight plane [9 taps x 32 rows][128 B]
-constexpr int C128_AROWS = 328;                       // 324 halo rows padded to 41 DMA instructions of 8 rows
-constexpr int C128_APL = C128_AROWS * 128;            // bytes per activation plane buffer
-__device__ __attribute__((aligned(16))) unsigned g_zero_page_c128[4];
-
-__global__ __launch_bounds__(512) void conv128x64p_kernel(const ConvArgs P, const int tiles_per_block, const int total_tiles) {
-    using M = Mma<MODE_BF16>;
-    constexpr int NDMA = 41, NK = (NDMA + 7) / 8;      // DMA instructions per plane; per wave at most NK
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Wl = smem;                                   // [2 planes][288 rows][128 B]
-    char* Al = Wl + 2 * C128_WPL;                      // [2 planes][328 rows][128 B]
-    double* chs = reinterpret_cast<double*>(Al + 2 * C128_APL); // [2][32] (f64: order-independent)
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    const int lp = lane & 15, q = lane >> 4;
-    // workgroup ids are dealt round-robin to the 8 XCDs: ids i and i + 8 (same XCD, same L2, dispatched together) are the two
-    // channel halves of one tile range, so the second reader of a tile finds it in L2 (ids 2r / 2r + 1 sit on different XCDs
-    // and both fetched every tile from HBM: 1.49 GB per launch measured against 0.81 GB algorithmic)
-    const int half = (blockIdx.x >> 3) & 1, co0 = half * 32;
-    const int range = (blockIdx.x >> 4) * 8 + (blockIdx.x & 7);
-    const int tiles_x = P.W >> 4, tiles_pf = tiles_x * (P.H >> 4);
-    const int t0 = range * tiles_per_block, t1 = min(t0 + tiles_per_block, total_tiles);
-    if (t0 >= t1) return;
-
-    for (int i = tid; i < 9 * 32 * 16; i += 512) {     // packed [tap][64 co][128 ci] bf16: 256-byte rows
-        const int row = i >> 4, c = i & 15;            // row = tap * 32 + local co
-        const int tap = row >> 5, col = row & 31;
-        const uint4 v = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(P.wp) + ((size_t)(tap * 64 + co0 + col) * 256) + c * 16);
-        *reinterpret_cast<uint4*>(Wl + (c >> 3) * C128_WPL + swz(row, c & 7)) = v;
-    }
-    if (tid < 64) chs[tid] = 0.0;
-
-    // DMA pieces of this lane: instruction u = wave + 8 k covers halo rows 8 u .. 8 u + 7; the lane's row is 8 u + (lane >> 3)
-    int pyx[NK];                                       // (halo row << 5) | halo column; row 100 = padding row / no instruction
-    const int cbyte = ((lane & 7) ^ (lane >> 3)) * 16; // global chunk that lands at LDS position lane & 7 of a row with key lane >> 3
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-        const int u = wave + 8 * k, hp = u * 8 + (lane >> 3);
-        pyx[k] = (((u < NDMA && hp < C64_HALO) ? hp / 18 : 100) << 5) | (hp % 18);
-    }
-    const char* const zero_page = reinterpret_cast<const char*>(g_zero_page_c128);
-    const char* const xb0 = reinterpret_cast<const char*>(P.x0);
-    const char* const xb1 = P.C1 ? reinterpret_cast<const char*>(P.x1) : xb0 + 128;       // plane 1: second tensor, or channels 64..127
-    const int rowb = P.C1 ? 128 : 256;                 // bytes per pixel row of a plane's tensor
-    const unsigned al_base = lds_addr(Al);
-    auto decode = [&](int t, int& f, int& ty, int& tx) { f = t / tiles_pf; const int r = t - f * tiles_pf; ty = r / tiles_x; tx = r - ty * tiles_x; };
-    auto dma = [&](int t, int pl) {                    // plane pl of tile t -> buffer pl
-        int f, ty, tx; decode(t, f, ty, tx);
-        const char* xb = pl ? xb1 : xb0;
-        const unsigned dst = al_base + pl * C128_APL + wave_u * 1024;
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            if (wave_u + 8 * k >= NDMA) continue;      // (uniform)
-            const int gy = ty * 16 - 1 + (pyx[k] >> 5), gx = tx * 16 - 1 + (pyx[k] & 31);
-            const bool ok = gy >= 0 && gy < P.H && gx >= 0 && gx < P.W;
-            const size_t off = (size_t)((f * P.H + gy) * P.W + gx) * rowb + cbyte;
-            glds16(ok ? static_cast<const void*>(xb + off) : static_cast<const void*>(zero_page), dst + k * 8 * 1024);
-        }
-    };
-    f32x4 ssum[2], ssq[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { ssum[i] = f32x4{0.f, 0.f, 0.f, 0.f}; ssq[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-    auto flush_stats = [&](int b) {
-        if (!P.out_stats) return;
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float s1 = reduce16(ssum[tm][e]), s2 = reduce16(ssq[tm][e]);
-                if (lp == 0) { unsafeAtomicAdd(&chs[tm * 16 + 4 * q + e], (double)s1); unsafeAtomicAdd(&chs[32 + tm * 16 + 4 * q + e], (double)s2); }
-                ssum[tm][e] = 0.f; ssq[tm][e] = 0.f;
-            }
-        __syncthreads();
-        const int cpg = 64 / P.out_groups, ng = 32 / cpg;       // groups inside this half
-        if (tid < 2 * ng) {
-            const int g = tid >> 1, which = tid & 1;
-            double t = 0.0;
-            for (int c = g * cpg; c < (g + 1) * cpg; ++c) t += chs[which * 32 + c];
-            unsafeAtomicAdd(P.out_stats + (((size_t)b * GN_SLOTS + ((blockIdx.x >> 1) % GN_SLOTS)) * P.out_groups + half * ng + g) * 2 + which, t);
-        }
-        __syncthreads();
-        if (tid < 64) chs[tid] = 0.0;
-        __syncthreads();
-    };
-    int hpb[2];
-    hpb[0] = (2 * wave) * 18 + lp; hpb[1] = hpb[0] + 18;
-    float4 bias4[2];
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) bias4[tm] = P.bias ? *reinterpret_cast<const float4*>(P.bias + co0 + tm * 16 + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
-
-    f32x4 acc[2][2];
-    auto plane_mma = [&](int pl) {                     // 9 taps x 2 chunks x (2 x 2) MFMAs on plane pl
-        const char* Wp = Wl + pl * C128_WPL;
-        const char* Ap = Al + pl * C128_APL;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int dy = tap / 3, dx = tap % 3;
-            int boff[2];
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn) { const int hp = hpb[tn] + dy * 18 + dx; boff[tn] = swz(hp, q); }
-            const int woff = swz(tap * 32 + lp, q);
-#pragma unroll
-            for (int ch = 0; ch < 2; ++ch) {
-                uint4 af[2], bf[2];
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm) af[tm] = *reinterpret_cast<const uint4*>(Wp + ((woff + tm * 16 * 128) ^ (ch * 64)));
-#pragma unroll
-                for (int tn = 0; tn < 2; ++tn) bf[tn] = *reinterpret_cast<const uint4*>(Ap + (boff[tn] ^ (ch * 64)));
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-                    for (int tn = 0; tn < 2; ++tn) M::mma(acc[tm][tn], af[tm], bf[tn]);
-            }
-        }
-    };
-
-    int fcur, tyc, txc;
-    decode(t0, fcur, tyc, txc);
-    int bcur = fcur / P.F;
-    dma(t0, 0);
-    wait_vm<0>();
-    __syncthreads();                                   // weights, chs and plane 0 of the first tile visible
-    for (int t = t0; t < t1; ++t) {
-        const bool more = t + 1 < t1;
-        int fn = fcur, tyn = tyc, txn = txc, bn = bcur;
-        if (more) { decode(t + 1, fn, tyn, txn); bn = fn / P.F; }
-        dma(t, 1);                                     // buffer 1 was last read during plane 1 of tile t - 1 (barrier since)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        plane_mma(0);
-        wait_vm<0>();                                  // this wave's pieces of plane 1 (and the stores of tile t - 1) are done
-        __syncthreads();                               // everybody's are; every wave is done reading buffer 0
-        if (more) dma(t + 1, 0);
-        plane_mma(1);
-        wait_vm<0>();                                  // before the stores below: the wait covers the DMA only
-        {
-            const int oy0 = tyc * 16 + 2 * wave, ox = txc * 16 + lp;
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn) {
-                const size_t gout = ((size_t)(fcur * P.H + oy0 + tn) * P.W + ox) * 64 + co0;
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm) {
-                    const float4 v = make_float4(acc[tm][tn][0] + bias4[tm].x, acc[tm][tn][1] + bias4[tm].y, acc[tm][tn][2] + bias4[tm].z, acc[tm][tn][3] + bias4[tm].w);
-                    store4_f32_or_bf16(P.y, gout + tm * 16 + 4 * q, v, P.y_bf16);
-                    ssum[tm][0] += v.x; ssum[tm][1] += v.y; ssum[tm][2] += v.z; ssum[tm][3] += v.w;
-                    ssq[tm][0] += v.x * v.x; ssq[tm][1] += v.y * v.y; ssq[tm][2] += v.z * v.z; ssq[tm][3] += v.w * v.w;
-                }
-            }
-        }
-        if (more && bn != bcur) { flush_stats(bcur); bcur = bn; }
-        fcur = fn; tyc = tyn; txc = txn;
-        __builtin_amdgcn_s_barrier();                  // plane 0 of tile t + 1 landed everywhere; every wave is done reading buffer 1
-    }
-    flush_stats(bcur);
-}
-
-static hipError_t launch_conv128x64p(const ConvArgs& a, hipStream_t st) {
-    const int total = a.NF * (a.H >> 4) * (a.W >> 4);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-    const int ranges = std::max(1, std::min(total, cus / 2));
-    const int tpb = (total + ranges - 1) / ranges;
-    const int nranges = (total + tpb - 1) / tpb;
-    const size_t lds = 2 * (size_t)C128_WPL + 2 * (size_t)C128_APL + 64 * 8;
-    auto kfn = conv128x64p_kernel;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kfn, dim3((nranges + 7) / 8 * 16), dim3(512), lds, st, a, tpb, total);
-    return hipGetLastError();
+    if (a.x0_bf16) return hipErrorInvalidValue;       // (bf16 input: conv64q / conv64r / conv64d)
+    const size_t lds = 9 * 64 * 128 + 2 * (size_t)C64_HALO * 128 + (64 + 64 + 64) * 4 + 128 * 8 + 64 * 4;      // weights, 2 halo tiles, coefA / coefD / gmean, chs, bias
+    auto launch = [&](auto kfn) { return launch_tiles16(kfn, a, lds, device_cus(), st); };
+    if (a.pro) return a.y_bf16 ? launch(conv64p_kernel<false, true, true>) : launch(conv64p_kernel<false, true, false>);
+    return a.y_bf16 ? launch(conv64p_kernel<false, false, true>) : launch(conv64p_kernel<false, false, false>);
 }
 
 // Flax kernel [taps][Cin][Cout] fp32  ->  packed [taps][Cout][CinPad] in the MMA element type, zero padded.
@@ -1879,6 +1537,42 @@ ConvWork conv_work(int mode, const ConvArgs& a) {
 }
 }  // namespace
 
+// ---- routing of the level-0 persistent forms: one predicate per (kernel, case), tried by launch_conv in this order.  Their channel shapes
+//      are disjoint, so at most one holds for a conv.  Common to all: bf16 mode, 3x3 / stride 1, whole 16 x 16 tiles, at least 1024 of them.
+static bool tiles16_3x3(int mode, const ConvArgs& a) {
+    return mode == MODE_BF16 && a.kind == 0 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.H % 16 == 0 && a.W % 16 == 0 &&
+           (long)a.NF * (a.H / 16) * (a.W / 16) >= 1024;
+}
+// 64 -> 64 (levels 0 / 1 of the N shape; the input may be a slice of a wider weight packing), residual only with a bf16 input and no prologue.
+// The input format picks the kernel: conv64q (bf16 + prologue), conv64r (bf16), conv64d (bf16 + fp32 residual), conv64p (fp32).
+static bool conv64_shape(int mode, const ConvArgs& a) {
+    return tiles16_3x3(mode, a) && a.C0 == 64 && a.C1 == 0 && a.Cout == 64 && a.wrows >= 64 && a.wrow0 >= 0 && a.wrow0 + 64 <= a.wrows &&
+           (!a.res || (!a.pro && a.x0_bf16 && !a.res_bf16)) && (size_t)a.NF * a.H * a.W * 64 * (a.y_bf16 ? 2 : 4) < 0xFFFFFFF0ull &&
+           (!a.pro || (a.groups <= 32 && 64 % a.groups == 0)) && (!a.out_stats || (a.out_groups <= 32 && 64 % a.out_groups == 0));
+}
+static bool conv64q_pro_eligible(int mode, const ConvArgs& a) { return conv64_shape(mode, a) && a.x0_bf16 && a.pro; }
+static bool conv64r_eligible(int mode, const ConvArgs& a) { return conv64_shape(mode, a) && a.x0_bf16 && !a.pro && !a.res; }
+static bool conv64d_eligible(int mode, const ConvArgs& a) { return conv64_shape(mode, a) && a.x0_bf16 && !a.pro && a.res; }
+static bool conv64p_eligible(int mode, const ConvArgs& a) { return conv64_shape(mode, a) && !a.x0_bf16; }
+// 32 -> 32 (level 0 of dim-32 networks, the YAML-literal config_v2_2): conv64p_kernel with 32-channel tiles, bf16 tensors
+static bool conv64p_c32_eligible(int mode, const ConvArgs& a) {
+    return tiles16_3x3(mode, a) && a.C0 == 32 && a.C1 == 0 && a.Cout == 32 && a.wrows == 32 && a.wrow0 == 0 && a.CinPad == 64 && a.x0_bf16 &&
+           a.y_bf16 && !a.res && (!a.pro || (a.groups <= 32 && 32 % a.groups == 0)) && (!a.out_stats || (a.out_groups <= 32 && 32 % a.out_groups == 0));
+}
+// concat inputs of dim-32 networks with 32 output channels: 64 = 32 + 32 -> 32 at level 0, 128 = 64 + 64 -> 32 at level 1 (they ran on the
+// generic kernel: 278 / 117 us at B = 64)
+static bool conv64q_cout32_eligible(int mode, const ConvArgs& a) {
+    return tiles16_3x3(mode, a) && a.Cout == 32 && a.x0_bf16 && a.x1_bf16 && !a.pro && a.y_bf16 && ((a.C0 == 32 && a.C1 == 32) || (a.C0 == 64 && a.C1 == 64)) &&
+           a.CinPad == a.C0 + a.C1 && a.wrows == 32 && a.wrow0 == 0 && !a.res &&
+           (!a.out_stats || (a.out_groups <= 32 && 32 % a.out_groups == 0 && (32 / a.out_groups) <= 8 && 8 % (32 / a.out_groups) == 0));
+}
+// 128 -> 64: a 64 + 64 concat or one 128-channel tensor, bf16 inputs; 32-bit offsets of the 256-byte input pixels (larger: generic kernel)
+static bool conv64q_cin128_eligible(int mode, const ConvArgs& a) {
+    return tiles16_3x3(mode, a) && a.Cout == 64 && a.x0_bf16 && (!a.C1 || a.x1_bf16) && !a.pro && ((a.C0 == 64 && a.C1 == 64) || (a.C0 == 128 && a.C1 == 0)) &&
+           a.wrows == 64 && a.wrow0 == 0 && !a.res && (!a.out_stats || (a.out_groups <= 32 && 32 % (64 / a.out_groups) == 0 && 64 % a.out_groups == 0)) &&
+           (long)a.NF * a.H * a.W * 256 < 0xFFFFFFF0l;
+}
+
 hipError_t launch_conv(int mode, ConvArgs a, hipStream_t st) {
     // geometry completion
     const int K = a.kind ? 2 : a.kh;
@@ -1911,66 +1605,40 @@ hipError_t launch_conv(int mode, ConvArgs a, hipStream_t st) {
         LaunchScope ls(st, "conv1x1_pw_kernel", cw.flops, cw.bytes, "<%d> %s", conv1x1_pw_rows(a), cw.shape);
         return launch_conv1x1_pw(a, st);
     }
-    {   // persistent specialisation for the level-0 shape (see conv64p_kernel)
-        const int use64p = 1;
-        const long tiles = (long)a.NF * (a.H / 16) * (a.W / 16);
-        if (use64p && mode == MODE_BF16 && a.kind == 0 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.C0 == 64 && a.C1 == 0 && a.Cout == 64 &&
-            a.wrows >= 64 && a.wrow0 >= 0 && a.wrow0 + 64 <= a.wrows && (!a.res || (!a.pro && a.x0_bf16 && !a.res_bf16)) && a.H % 16 == 0 && a.W % 16 == 0 && tiles >= 1024 && npix * 64 * (a.y_bf16 ? 2 : 4) < 0xFFFFFFF0ull && (!a.pro || (a.groups <= 32 && 64 % a.groups == 0)) &&
-            (!a.out_stats || (a.out_groups <= 32 && 64 % a.out_groups == 0))) {
-#ifndef VDX_C64_NODMA
-#define VDX_C64_NODMA 0
-#endif
-            const bool dma_form = a.x0_bf16 && !a.pro && !VDX_C64_NODMA;               // bf16 input, no prologue: input staged by LDS-DMA (conv64d_kernel)
-#ifndef VDX_C64R
-#define VDX_C64R 1
-#endif
-#ifndef VDX_C64Q
-#define VDX_C64Q 13            // conv64q_kernel (16 channels x 128 pixels per wave) for: 1 = the prologue form, 2 = the plain form, 4 = 128 input channels, 8 = 32 output channels
-#endif
-            if (a.x0_bf16 && !a.res && !VDX_C64_NODMA && (VDX_C64Q & (a.pro ? 1 : 2))) {
-                const ConvWork cw = conv_work(mode, a);
-                LaunchScope ls(st, "conv64q_kernel", cw.flops, cw.bytes, "<cin 64, pro %d, y16 %d> %s", a.pro, a.y_bf16, cw.shape);
-                return launch_conv64q(a, st);
-            }
-            if (VDX_C64R && a.x0_bf16 && !a.pro && !a.res && !VDX_C64_NODMA) {      // weights in registers, three-deep tile ring (conv64r_kernel; its prologue form -- in-place transform with
-                                                                                       // the coefficients re-read per piece, 256 registers + scratch -- measured 449 us against conv64p_kernel's 422 and was removed)
-                const ConvWork cw = conv_work(mode, a);
-                LaunchScope ls(st, "conv64r_kernel", cw.flops, cw.bytes, "<pro 0, y16 %d> %s", a.y_bf16, cw.shape);
-                return launch_conv64r(a, st);
-            }
-            const ConvWork cw = conv_work(mode, a);
-            LaunchScope ls(st, dma_form ? "conv64d_kernel" : "conv64p_kernel", cw.flops, cw.bytes, "<x16 %d, pro %d, y16 %d, res %d> %s", a.x0_bf16, a.pro, a.y_bf16, a.res ? 1 : 0, cw.shape);
-            return dma_form ? launch_conv64d(a, st) : launch_conv64p(a, st);
-        }
-        // level 0 of dim-32 networks (the YAML-literal config_v2_2): the same kernel with 32-channel tiles, bf16 tensors
-        if (use64p && mode == MODE_BF16 && a.kind == 0 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.C0 == 32 && a.C1 == 0 && a.Cout == 32 && a.wrows == 32 &&
-            a.wrow0 == 0 && a.CinPad == 64 && a.x0_bf16 && a.y_bf16 && !a.res && a.H % 16 == 0 && a.W % 16 == 0 && tiles >= 1024 &&
-            (!a.pro || (a.groups <= 32 && 32 % a.groups == 0)) && (!a.out_stats || (a.out_groups <= 32 && 32 % a.out_groups == 0))) {
-            const ConvWork cw = conv_work(mode, a);
-            LaunchScope ls(st, "conv64p_kernel", cw.flops, cw.bytes, "<x16 1, pro %d, y16 1, res 0, C 32> %s", a.pro, cw.shape);
-            return launch_conv64p(a, st);
-        }
-        const bool in16c = a.x0_bf16 && (!a.C1 || a.x1_bf16);
-        // dim-32 networks (the YAML-literal config_v2_2): the 3x3 convs on a concat input with 32 output channels (64 = 32 + 32 -> 32 at level 0,
-        // 128 = 64 + 64 -> 32 at level 1) ran on the generic kernel (278 / 117 us at B = 64)
-        if ((VDX_C64Q & 8) && use64p && mode == MODE_BF16 && a.kind == 0 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.Cout == 32 && in16c && !a.pro && a.y_bf16 &&
-            ((a.C0 == 32 && a.C1 == 32) || (a.C0 == 64 && a.C1 == 64)) && a.CinPad == a.C0 + a.C1 && a.wrows == 32 && a.wrow0 == 0 && !a.res && a.H % 16 == 0 && a.W % 16 == 0 &&
-            tiles >= 1024 && (!a.out_stats || (a.out_groups <= 32 && 32 % a.out_groups == 0 && (32 / a.out_groups) <= 8 && 8 % (32 / a.out_groups) == 0))) {
-            const ConvWork cw = conv_work(mode, a);
-            LaunchScope ls(st, "conv64q_kernel", cw.flops, cw.bytes, "<cin %d, pro 0, y16 1, cout 32> %s", a.C0 + a.C1, cw.shape);
-            return launch_conv64q(a, st);
-        }
-        if (use64p && mode == MODE_BF16 && a.kind == 0 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.Cout == 64 && in16c && !a.pro &&
-            ((a.C0 == 64 && a.C1 == 64) || (a.C0 == 128 && a.C1 == 0)) && a.wrows == 64 && a.wrow0 == 0 && !a.res && a.H % 16 == 0 && a.W % 16 == 0 &&
-            tiles >= 1024 && (!a.out_stats || (a.out_groups <= 32 && 32 % (64 / a.out_groups) == 0 && 64 % a.out_groups == 0))) {
-            const ConvWork cw = conv_work(mode, a);
-            if ((VDX_C64Q & 4) && (long)a.NF * a.H * a.W * 256 < 0xFFFFFFF0l) {
-                LaunchScope ls(st, "conv64q_kernel", cw.flops, cw.bytes, "<cin 128, pro 0, y16 %d> %s", a.y_bf16, cw.shape);
-                return launch_conv64q(a, st);
-            }
-            LaunchScope ls(st, "conv128x64p_kernel", cw.flops, cw.bytes, "%s", cw.shape);
-            return launch_conv128x64p(a, st);
-        }
+    if (conv64q_pro_eligible(mode, a)) {                                      // level-0 persistent forms: 64 -> 64, bf16 input, prologue
+        const ConvWork cw = conv_work(mode, a);
+        LaunchScope ls(st, "conv64q_kernel", cw.flops, cw.bytes, "<cin 64, pro %d, y16 %d> %s", a.pro, a.y_bf16, cw.shape);
+        return launch_conv64q(a, st);
+    }
+    if (conv64r_eligible(mode, a)) {                                          // 64 -> 64, bf16 input
+        const ConvWork cw = conv_work(mode, a);
+        LaunchScope ls(st, "conv64r_kernel", cw.flops, cw.bytes, "<pro 0, y16 %d> %s", a.y_bf16, cw.shape);
+        return launch_conv64r(a, st);
+    }
+    if (conv64d_eligible(mode, a)) {                                          // 64 -> 64, bf16 input, fp32 residual
+        const ConvWork cw = conv_work(mode, a);
+        LaunchScope ls(st, "conv64d_kernel", cw.flops, cw.bytes, "<x16 %d, pro %d, y16 %d, res %d> %s", a.x0_bf16, a.pro, a.y_bf16, a.res ? 1 : 0, cw.shape);
+        return launch_conv64d(a, st);
+    }
+    if (conv64p_eligible(mode, a)) {                                          // 64 -> 64, fp32 input
+        const ConvWork cw = conv_work(mode, a);
+        LaunchScope ls(st, "conv64p_kernel", cw.flops, cw.bytes, "<x16 %d, pro %d, y16 %d, res %d> %s", a.x0_bf16, a.pro, a.y_bf16, a.res ? 1 : 0, cw.shape);
+        return launch_conv64p(a, st);
+    }
+    if (conv64p_c32_eligible(mode, a)) {                                      // 32 -> 32 (level 0 of dim-32 networks)
+        const ConvWork cw = conv_work(mode, a);
+        LaunchScope ls(st, "conv64p_kernel", cw.flops, cw.bytes, "<x16 1, pro %d, y16 1, res 0, C 32> %s", a.pro, cw.shape);
+        return launch_conv64p(a, st);
+    }
+    if (conv64q_cout32_eligible(mode, a)) {                                   // concat -> 32 (levels 0 / 1 of dim-32 networks)
+        const ConvWork cw = conv_work(mode, a);
+        LaunchScope ls(st, "conv64q_kernel", cw.flops, cw.bytes, "<cin %d, pro 0, y16 1, cout 32> %s", a.C0 + a.C1, cw.shape);
+        return launch_conv64q(a, st);
+    }
+    if (conv64q_cin128_eligible(mode, a)) {                                   // 128 -> 64
+        const ConvWork cw = conv_work(mode, a);
+        LaunchScope ls(st, "conv64q_kernel", cw.flops, cw.bytes, "<cin 128, pro 0, y16 %d> %s", a.y_bf16, cw.shape);
+        return launch_conv64q(a, st);
     }
     // variant: 64-channel tiles take 256 pixels per workgroup (stride 1) so every wave owns a 64x64 tile
     const int BC = a.Cout <= 64 ? 64 : 128;
@@ -1998,10 +1666,7 @@ hipError_t launch_conv(int mode, ConvArgs a, hipStream_t st) {
 #define VDX_LAUNCH_CONV_K(KFN_, NTH_)                                                                    \
     do {                                                                                                  \
         auto kfn = KFN_;                                                                                  \
-        if (lds > 64 * 1024) {                                                                            \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return e;                                                                \
-        }                                                                                                 \
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;                               \
         hipLaunchKernelGGL(kfn, grid, dim3(NTH_), lds, st, a);                                            \
     } while (0)
     // 64-pixel-per-wave shapes run as 8 waves x 32 pixels (measured better than 4 waves x 64 pixels); stride-2 64-channel tiles as 4 x 32

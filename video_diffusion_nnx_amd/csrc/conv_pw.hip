@@ -200,8 +200,7 @@ bool conv1x1_pw_eligible(int mode, const ConvArgs& a) {
 hipError_t launch_conv1x1_pw(const ConvArgs& a, hipStream_t st) {
     const int cin = a.C0 + a.C1, rows = conv1x1_pw_rows(a), nct = a.Cout / rows;
     const int ngroups = (int)((size_t)a.NF * a.H * a.W / 32);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
+    const int cus = device_cus();
     // ranges: a multiple of 8 (XCD decode), ~ cus / nct of them, each a multiple of 8 groups (one per wave and pass)
     const size_t lds = (size_t)rows * (cin * 2 + 16) + rows * 4;
     // two workgroups per CU when the weight image allows it (<= 80 KB, and the 128-row form needs < 128 registers): the kernel waits on
@@ -211,10 +210,7 @@ hipError_t launch_conv1x1_pw(const ConvArgs& a, hipStream_t st) {
     int gpr = ((ngroups + nranges - 1) / nranges + 7) / 8 * 8;
     nranges = ((ngroups + gpr - 1) / gpr + 7) / 8 * 8;
     auto go = [&](auto kfn) -> hipError_t {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
         hipLaunchKernelGGL(kfn, dim3(nranges * nct), dim3(512), lds, st, a, nct, gpr, ngroups);
         return hipGetLastError();
     };

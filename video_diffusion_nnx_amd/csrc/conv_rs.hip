@@ -114,11 +114,9 @@ bool resample32_eligible(int mode, const ConvArgs& a) {
 hipError_t launch_resample32(const ConvArgs& a, hipStream_t st) {
     const bool down = a.kind == 0;
     const long tiles = (long)a.NF * (down ? a.H / 2 : a.H) * ((down ? a.W / 2 : a.W) / 16);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-    const long waves = std::min<long>(tiles, (long)cus * 8);              // 8 waves per CU (two workgroups of 4 at <= 256 registers)
-    const int tpw = (int)((tiles + waves - 1) / waves);
-    const long blocks = (tiles + (long)tpw * 4 - 1) / ((long)tpw * 4);
+    const PersistentSplit s = persistent_split(tiles, (long)device_cus() * 8);      // over waves: 8 per CU (two workgroups of 4 at <= 256 registers)
+    const int tpw = (int)s.per;
+    const long blocks = (s.workers + 3) / 4;
     if (down) hipLaunchKernelGGL(resample32_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, st, a, tpw, tiles);
     else hipLaunchKernelGGL(resample32_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, a, tpw, tiles);
     return hipGetLastError();

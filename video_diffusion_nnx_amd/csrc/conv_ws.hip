@@ -680,8 +680,7 @@ bool conv4x4_ws_eligible(int mode, const ConvArgs& a) {
 hipError_t launch_conv4x4_ws(const ConvArgs& a, hipStream_t st) {
     const int geo = ws4_geo(a), bco = a.Cout == 64 ? 64 : 128, nct = a.Cout / bco, up = a.kind == 1;
     const int total = (int)((long)a.NF * geo * geo / 256) * (up ? 4 : 1);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
+    const int cus = device_cus();
     const int unit = 8 * nct;
     int grid = std::max(unit, cus / unit * unit);
     grid = std::min(grid, (total * nct + unit - 1) / unit * unit);
@@ -690,8 +689,7 @@ hipError_t launch_conv4x4_ws(const ConvArgs& a, hipStream_t st) {
     if (up) tpr = (tpr + 3) / 4 * 4;                      // a range = whole groups of 4 phases (the weight stream's phase follows t & 3)
     const size_t lds = (size_t)WS_NS * bco * 128 + 2 * (size_t)(geo == 32 ? 321 : 257) * 128 + 512;
     auto go = [&](auto kfn) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, st, a, tpr, total, nct);
         return hipGetLastError();
     };
@@ -727,8 +725,7 @@ hipError_t launch_conv3x3_ws(const ConvArgs& a, hipStream_t st) {
     const int nct = a.Cout / 128;
     const int npf = geo == 0 ? 1 : 256 / (a.H * a.W);
     const int total = geo == 0 ? a.NF * (a.H / 16) * (a.W / 16) : (a.NF / a.F) * ((a.F + npf - 1) / npf);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
+    const int cus = device_cus();
     const int unit = 8 * nct;                             // the decode deals ranges to the 8 XCDs
     int grid = std::max(unit, cus / unit * unit);
     grid = std::min(grid, (total * nct + unit - 1) / unit * unit);
@@ -738,8 +735,7 @@ hipError_t launch_conv3x3_ws(const ConvArgs& a, hipStream_t st) {
     const size_t lds = (size_t)WS_NS * WS_SLAB + 2 * (size_t)HPX * 128 + 512 + (a.pro ? (size_t)a.CinPad * 8 + 256 : 0);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     auto go = [&](auto kfn) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
 #ifndef VDX_WS_PIN_MB
 #define VDX_WS_PIN_MB 0        // pin output-channel tiles to XCDs when their weights together exceed this many MB (0: never).  Measured with 3 (r03, 512 -> 512 at 8 x 8):
                                // same time (251 vs 250 us plain, 307 vs 317 with the prologue) for MORE HBM traffic (401-454 vs 290-326 MB per launch: the input tiles

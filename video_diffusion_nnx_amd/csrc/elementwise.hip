@@ -352,10 +352,7 @@ static hipError_t launch_tail_rc16(const TailArgs& a, hipStream_t st) {
     const long need = (a.pix_per_sample / 16 + 3) / 4;
     const long gx = std::min<long>(need, std::max<long>(std::max<long>(1, need / 8), (2048 + a.batch - 1) / std::max(1, a.batch)));
     auto go = [&](auto kfn) -> hipError_t {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
         const double px = (double)a.batch * a.pix_per_sample;       // y2, x (concat) in + out, bf16; the 1x1 res_conv on the MFMA
         LaunchScope ls(st, "resblock_tail_rc16_kernel", 2.0 * px * CIN * COUT + (a.fin_w ? 2.0 * px * COUT : 0.0),
                        px * (CIN + (a.fin_w ? 1.0 : 2.0) * COUT) * 2 + (a.fin_w ? px * 4 : 0.0) + 2.0 * CIN * COUT, "<%d, %d, %s> px%ld x %d", CIN, COUT,

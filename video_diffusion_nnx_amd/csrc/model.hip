@@ -346,9 +346,6 @@ struct Fwd {
     double* stat(int i) const { return stats + (size_t)i * B * GN_SLOTS * m->cfg.resnet_groups * 2; }
 };
 
-#ifndef VDX_FUSE_HEAD
-#define VDX_FUSE_HEAD 1                                      // final 1x1 conv (one output channel) inside the last block's tail (inference storage)
-#endif
 #ifndef VDX_PREPASS_MIN_C
 #define VDX_PREPASS_MIN_C 256                                 // Block prologue as its own pass from this width on (sampling forward)
 #endif
@@ -411,7 +408,8 @@ static hipError_t run_res(const Fwd& f, const ResP& r, const float* x0, int c0, 
     t.ln_gamma = f.p + r.n2_s; t.ln_beta = f.p + r.n2_b;
     t.C = r.cout; t.batch = f.B; t.pix_per_sample = (long)m->cfg.num_frames * S * S;
     if (fuse_rc) { t.x0 = x0; t.x1 = x1; t.C0 = c0; t.C1 = c1; t.rc_w = f.pk + r.pk_rc; t.rc_b = f.p + r.rc_b; }
-    if (VDX_FUSE_HEAD && head_out && fuse_rc && c1 == c0 && m->out_dim == 1 && ((c0 + c1 == 128 && r.cout == 64) || (c0 + c1 == 64 && r.cout == 32))) {
+    // the final 1x1 conv (one output channel) inside the last block's tail (inference storage)
+    if (head_out && fuse_rc && c1 == c0 && m->out_dim == 1 && ((c0 + c1 == 128 && r.cout == 64) || (c0 + c1 == 64 && r.cout == 32))) {
         t.fin_w = f.p + m->fin_w; t.fin_b = f.p + m->fin_b; t.fin_out = head_out;
         *head_done = true;
     }
@@ -454,8 +452,7 @@ static hipError_t run_attn(const Fwd& f, const AttnP& ap, const float* x, float*
         return launch_conv(m->mode, c, f.st);
     }
     // wide levels in bf16 mode: per-head kernel (weights resident in LDS) + the out-projection as a 1x1 conv
-    const int use_heads = 1;
-    if (use_heads && m->mode == MODE_BF16 && (temporal ? a.L <= 16 : a.L <= 64) && a.heads == 8 && ap.C >= 256 && ap.C % 128 == 0 &&
+    if (m->mode == MODE_BF16 && (temporal ? a.L <= 16 : a.L <= 64) && a.heads == 8 && ap.C >= 256 && ap.C % 128 == 0 &&
         (size_t)96 * (ap.C * 2 + 32) <= 160 * 1024 && (size_t)Fr * S * S * a.heads * 64 <= m->sla_ws_bytes_per_sample) {
         a.oscratch = f.sla_ws;
         hipError_t e = launch_attention_heads(a, f.st);
@@ -480,8 +477,7 @@ static hipError_t run_sla(const Fwd& f, const SlaP& sp, const float* x, float* y
     a.workspace = f.sla_ws; a.C = sp.C; a.heads = m->cfg.attn_heads; a.NF = f.B * m->cfg.num_frames; a.N = S * S;
     a.io_bf16 = f.a16;
     // wide levels in bf16 mode: per-head kernel (weights resident in LDS) + to_out as a 1x1 conv
-    const int use_heads = 1;
-    if (use_heads && m->mode == MODE_BF16 && a.heads == 8 && sp.C >= 256 && sp.C % 128 == 0 && a.N % 16 == 0 &&
+    if (m->mode == MODE_BF16 && a.heads == 8 && sp.C >= 256 && sp.C % 128 == 0 && a.N % 16 == 0 &&
         (size_t)96 * (sp.C * 2 + 32) <= 160 * 1024 && (size_t)m->cfg.num_frames * a.N * a.heads * 64 <= m->sla_ws_bytes_per_sample) {
         hipError_t e = launch_sla_heads(a, f.sla_ws, f.st);
         if (e != hipSuccess) return e;

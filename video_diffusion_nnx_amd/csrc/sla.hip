@@ -1103,10 +1103,7 @@ hipError_t launch_sla_heads(SlaArgs a, void* O, hipStream_t st) {
     fpb = std::max<long>(8, (fpb + 7) / 8 * 8);
     const long chunks = (a.NF + fpb - 1) / fpb;
     auto go = [&](auto kfn) -> hipError_t {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
         const SlaWork sw = sla_work(a, 2, true, true, false);
         LaunchScope ls(st, "sla_head_kernel", sw.flops, sw.bytes, "<io16 %d, %d> C%d N%d NF%d", a.io_bf16, a.N % 64 == 0 ? 4 : 1, a.C, a.N, a.NF);
         hipLaunchKernelGGL(kfn, dim3((unsigned)((chunks + 7) / 8 * 64)), dim3(512), lds, st, a, O, (int)fpb, (int)chunks);
@@ -1139,10 +1136,7 @@ static hipError_t launch_sla_out_t(const SlaArgs& a, hipStream_t st) {
     constexpr int RSO = 256 * M::ES + 16;
     const size_t lds = std::max<size_t>((size_t)(64 + 256) * ROW_STRIDE, (size_t)4 * 64 * RSQ + (size_t)64 * RSO);
     auto kfn = sla_out_kernel<MODE, TMO>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const int tiles = (a.N + 63) / 64;
     const SlaWork sw = sla_work(a, M::ES, false, true, true);
     LaunchScope ls(st, "sla_out_kernel", sw.flops, sw.bytes, "<%d, %d> C%d N%d NF%d io16 %d", MODE, TMO, a.C, a.N, a.NF, a.io_bf16);
@@ -1150,26 +1144,19 @@ static hipError_t launch_sla_out_t(const SlaArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-#ifndef VDX_SLA_W
-#define VDX_SLA_W 1
-#endif
 #ifndef VDX_SLA_W_MIN_N
 #define VDX_SLA_W_MIN_N 2048
 #endif
 static bool sla_out_w_eligible(const SlaArgs& a) {
     // (frames of 1024 pixels = 2 groups per wave and frame: the per-frame context load + barrier cost more than the staging they replace: 103 vs 90 us)
-    return VDX_SLA_W && a.io_bf16 && a.C == 64 && a.CPad == 64 && a.heads == 8 && a.N % 64 == 0 && a.N >= VDX_SLA_W_MIN_N && a.NF >= 128 && (size_t)a.NF * a.N * 128 < (1ull << 40);
+    return a.io_bf16 && a.C == 64 && a.CPad == 64 && a.heads == 8 && a.N % 64 == 0 && a.N >= VDX_SLA_W_MIN_N && a.NF >= 128 && (size_t)a.NF * a.N * 128 < (1ull << 40);
 }
 static hipError_t launch_sla_out_w(const SlaArgs& a, hipStream_t st) {
     const size_t lds = 256 * 128 + 64 * 512 + 2 * 256 * 72;
     auto kfn = sla_out_w_kernel<0>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
-    const int blocks0 = std::min(a.NF, cus);
-    const int fpb = (a.NF + blocks0 - 1) / blocks0;
-    const int blocks = (a.NF + fpb - 1) / fpb;
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
+    const PersistentSplit s = persistent_split(a.NF, device_cus());
+    const int fpb = (int)s.per, blocks = (int)s.workers;
     const SlaWork sw = sla_work(a, 2, false, true, true);
     LaunchScope ls(st, "sla_out_w_kernel", sw.flops, sw.bytes, "C%d N%d NF%d", a.C, a.N, a.NF);
     hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, st, a, fpb);
@@ -1185,8 +1172,8 @@ static hipError_t launch_sla8_t(const SlaArgs& a, hipStream_t st) {
     auto kc = sla_ctx8_kernel<MODE, NKT, IO16>;
     auto ko = sla_out8_kernel<MODE, NKT, TMO, TNO, IO16>;
     hipError_t e;
-    if (lds_ctx > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(kc), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ctx)) != hipSuccess) return e;
-    if (lds_out > 64 * 1024 && (e = hipFuncSetAttribute(reinterpret_cast<const void*>(ko), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_out)) != hipSuccess) return e;
+    if ((e = lds_opt_in(kc, lds_ctx)) != hipSuccess) return e;
+    if ((e = lds_opt_in(ko, lds_out)) != hipSuccess) return e;
     {
         const SlaWork sw = sla_work(a, M::ES, true, false, false);
         LaunchScope ls(st, "sla_ctx8_kernel", sw.flops, sw.bytes, "<%d, %d, %d> C%d N%d NF%d nchunk%d", MODE, NKT, (int)IO16, a.C, a.N, a.NF, a.nchunk);
@@ -1227,10 +1214,9 @@ static hipError_t launch_sla_m(SlaArgs a, hipStream_t st) {
     const size_t part_bytes = (((size_t)a.NF * a.nchunk * a.heads * SLA_PART * 4) + 255) / 256 * 256;
     a.part = reinterpret_cast<float*>(a.workspace);
     a.ctxT = reinterpret_cast<char*>(a.workspace) + part_bytes;
-    const bool generic_only = false;
     const int nkt = a.CPad / M::KT;
     if constexpr (MODE != MODE_F16)                           // (the one-wave-per-head kernels hard-code the bf16 / f32 register formats)
-    if (a.heads == 8 && (a.C % 64 == 0 || a.C == 32) && !generic_only) {     // one wave per head; x tile double-buffered in LDS
+    if (a.heads == 8 && (a.C % 64 == 0 || a.C == 32)) {       // one wave per head; x tile double-buffered in LDS
         if constexpr (MODE == MODE_BF16) {
             if (a.io_bf16 && a.C == 64) return launch_sla8_t<MODE, 1, 1, 2, true>(a, st);
             if (a.io_bf16 && a.C == 128) return launch_sla8_t<MODE, 2, 1, 4, true>(a, st);

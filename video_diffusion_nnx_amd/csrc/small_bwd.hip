@@ -339,10 +339,7 @@ hipError_t launch_resblock_ss_bwd(const float* params, float* grads, const float
                                   float* dss_base, float* dtemb, int temb_dim, int B, hipStream_t st, float* part, size_t part_cap) {
     const size_t lds = ((size_t)B * temb_dim + 16) * 4;
     auto kfn = resblock_ss_bwd_kernel;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kfn, dim3(nlayers), dim3(256), lds, st, params, grads, temb, layers, lin_base, dss_base, dtemb, temb_dim, B);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -361,10 +358,7 @@ hipError_t launch_time_mlp_bwd(const TimeMlpArgs& a, const float* dtemb, float* 
     const size_t lds = (size_t)B * (a.dim + 2 * a.time_dim + 64) * 4;
     if (lds > 150 * 1024) return hipErrorInvalidValue;             // B <= ~60 at the N shape
     auto kfn = time_mlp_bwd_kernel;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     hipLaunchKernelGGL(kfn, dim3((a.time_dim + 63) / 64), dim3(256), lds, st, a, dtemb, dw1, db1, dw2, db2, dnull, B);
     return hipGetLastError();
 }

@@ -31,6 +31,29 @@ struct LaunchScope {
     LaunchScope& operator=(const LaunchScope&) = delete;
 };
 
+// Compute units of the current device (256 when the query fails): the width of the persistent launches.
+inline int device_cus() {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess) { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v; }
+    return cus;
+}
+
+// Persistent split of `total` (>= 1) work items over at most `slots` workers (workgroups or waves): each worker walks `per` consecutive
+// items; `workers` of them get work.
+struct PersistentSplit { long per, workers; };
+inline PersistentSplit persistent_split(long total, long slots) {
+    const long n = std::min(total, slots);
+    const long per = (total + n - 1) / n;
+    return {per, (total + per - 1) / per};
+}
+
+// A kernel launched with more than the default 64 KB of dynamic LDS has to opt in first; at or below it nothing is set.
+template <typename K>
+inline hipError_t lds_opt_in(K kfn, size_t lds) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 // Arguments of conv_igemm_kernel (POD, passed by value).  Caller fills the first block; launch_conv
 // completes the geometry.
 struct ConvArgs {

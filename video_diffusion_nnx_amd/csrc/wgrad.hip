@@ -812,7 +812,7 @@ hipError_t launch_conv_wgrad(WgradArgs a, hipStream_t st) {
         a.pwl = a.PW == 8 ? 3 : 4;
         const size_t lds16 = ((size_t)IH * IW + (size_t)a.PH * a.sb * a.PW * a.sb) * WG_RSB + 4 * 64 * 4 + 32 * 4;
 #define VDX_WG16(NT_, NG_, PF_, X16_, DY16_) do { auto kfn = conv_wgrad16_kernel<NT_, NG_, PF_, X16_, DY16_>;                                                \
-        if (lds16 > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16); if (e != hipSuccess) return e; } \
+        if (hipError_t e = lds_opt_in(kfn, lds16); e != hipSuccess) return e; \
         hipLaunchKernelGGL(kfn, grid, dim3(256 * NG_), lds16, st, a); } while (0)
         a.m_iw = (unsigned)((1ull << 32) / (unsigned)IW) + 1u;
         a.m_bw = (unsigned)((1ull << 32) / (unsigned)(a.PW * a.sb)) + 1u;
@@ -821,8 +821,7 @@ hipError_t launch_conv_wgrad(WgradArgs a, hipStream_t st) {
             if ((long)IH * IW * 16 > 6 * nth || (long)a.PH * a.sb * a.PW * a.sb * 16 > 4 * nth) return hipErrorInvalidValue;
         }
         // projections: the split-K GEMM form (wide output tiles when Cout allows: x is staged Cout / 256 times instead of Cout / 64)
-        const int use_1x1 = 2;   // 0: patch kernel, 1: GEMM form for wide outputs only, 2: always
-        if (use_1x1 && NT == 1 && a.kind == 0 && a.stride == 1 && !a.pro && (a.Cout % 256 == 0 || use_1x1 == 2)) {
+        if (NT == 1 && a.kind == 0 && a.stride == 1 && !a.pro) {
             const long wgs4 = 512;
             a.part = part_in;
             if (a.Cout % 256 == 0) {
@@ -832,10 +831,9 @@ hipError_t launch_conv_wgrad(WgradArgs a, hipStream_t st) {
             if (a.x0_bf16) return a.dy_bf16 ? launch_wgrad1x1_t<true, true, 1>(a, target_wgs, st) : launch_wgrad1x1_t<true, false, 1>(a, target_wgs, st);
             return a.dy_bf16 ? launch_wgrad1x1_t<false, true, 1>(a, target_wgs, st) : launch_wgrad1x1_t<false, false, 1>(a, target_wgs, st);
         }
-        const bool pf1 = false;
 #define VDX_WG16_IO(NT_, NG_, PF_) do { if (a.x0_bf16) { if (a.dy_bf16) VDX_WG16(NT_, NG_, PF_, true, true); else VDX_WG16(NT_, NG_, PF_, true, false); } \
                                         else { if (a.dy_bf16) VDX_WG16(NT_, NG_, PF_, false, true); else VDX_WG16(NT_, NG_, PF_, false, false); } } while (0)
-        if (NT == 1) { if (pf1) VDX_WG16_IO(1, 1, true); else VDX_WG16_IO(1, 1, false); }
+        if (NT == 1) VDX_WG16_IO(1, 1, false);
         else if (NT == 9) VDX_WG16_IO(9, 2, true);
         else VDX_WG16_IO(8, 2, true);
 #undef VDX_WG16_IO
@@ -844,7 +842,7 @@ hipError_t launch_conv_wgrad(WgradArgs a, hipStream_t st) {
         return wgrad_det_finish(a, chunks, st);
     }
 #define VDX_WG(NT_) do { auto kfn = conv_wgrad_kernel<NT_>;                                                           \
-        if (lds > 64 * 1024) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e != hipSuccess) return e; } \
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e; \
         hipLaunchKernelGGL(kfn, grid, dim3(256), lds, st, a); } while (0)
     if (NT == 1) VDX_WG(1); else if (NT == 9) VDX_WG(9); else VDX_WG(8);
 #undef VDX_WG
