@@ -318,6 +318,56 @@ int vdx_ddim_sample_loop_dyn(vdx_handle* h, const float* params, const void* pac
                              int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf, void* workspace,
                              size_t workspace_bytes, int batch, int use_graph, void* stream);
 
+/* Frame-conditioned sampling (EXTENSION: the replacement method of Ho et al. 2022, "Video Diffusion Models" sec. 3.1, with
+ * optional RePaint resampling, Lugmayr et al. 2022).  known = 2 video - 1 [B,C,F,H,W]; mask [B,C,F,H,W] bytes, nonzero = known;
+ * mask_tables: device fp32 [4][T] = sqrt_ac | sqrt(1 - ac) | sqrt(alpha) | sqrt(beta).  s is the global step counter (0, 1, ...
+ * over every reverse step incl. the resampling ones).  Draws: x_T = Philox(seed, 0), step noise 1 + s (as vdx_p_sample_loop), the
+ * known region's noise VDX_DRAW_KNOWN + s, the re-noise VDX_DRAW_RENOISE + s.  per_sample % 4 == 0 everywhere, and the kernels move
+ * 4 elements at a time: x / img, known and out must be 16-byte aligned, mask 4-byte aligned (checked: VDX_ERR_INVALID). */
+#define VDX_DRAW_KNOWN (1ull << 62)
+#define VDX_DRAW_RENOISE (1ull << 63)
+
+/* First merge, in place: x = mask ? sqrt_ac[t0] known + sqrt(1 - ac[t0]) x : x (the known region noised with x_T's own noise).
+ * n = B*C*F*H*W, n % 4 == 0; t0 = T-1 for the ancestral chain. */
+int vdx_inpaint_init(float* x, const float* known, const unsigned char* mask, const float* mask_tables, int timesteps, int t0,
+                     long n, void* stream);
+
+/* One masked ancestral step at t = t[b], s = step + (*step_dev if step_dev): x' = vdx_p_sample_step(x, Philox(seed, 1 + s));
+ * kn = t == 0 ? known : sqrt_ac[t-1] known + sqrt(1 - ac[t-1]) Philox(seed, VDX_DRAW_KNOWN + s); out = mask ? kn : x';
+ * then, when s % resample_steps != resample_steps - 1, out = sqrt(alpha_t) out + sqrt(beta_t) Philox(seed, VDX_DRAW_RENOISE + s)
+ * (back to level t).  tables / thres / clip as vdx_p_sample_step.  An all-zero mask with resample_steps 1 is vdx_p_sample_step
+ * with offset 1 + s, bit for bit.  x and out may alias. */
+int vdx_p_sample_step_masked(const float* x, const float* eps_hat, float* out, const int* t, const float* tables, int timesteps,
+                             const float* known, const unsigned char* mask, const float* mask_tables, int resample_steps,
+                             uint64_t seed, uint64_t step, const uint64_t* step_dev, const float* thres, int clip_denoised,
+                             int batch, int channels, long per_sample, void* stream);
+
+/* vdx_p_sample_loop_dyn with the masked step: one step = Unet3D forward + (dynamic threshold) + vdx_p_sample_step_masked with
+ * s = *step_dev + { t -= 1 when s % resample_steps == resample_steps - 1 ; s += 1 }, so one captured step serves every (t, u).
+ * img holds vdx_inpaint_init's output on entry; t_dev = T-1, *step_dev = 0.  nsteps <= timesteps * resample_steps.  Own graph
+ * slot: does not evict the graphs of the unconditional loops. */
+int vdx_p_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                             uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                             int clip_denoised, float percentile, float* thres_buf, const float* known, const unsigned char* mask,
+                             const float* mask_tables, int resample_steps, void* workspace, size_t workspace_bytes, int batch,
+                             int use_graph, void* stream);
+
+/* One masked DDIM step (eta = 0; no resampling): x' = vdx_ddim_step(x) from seq[j] to seq[j+1], j = *step_dev (or 0);
+ * kn = seq[j+1] < 0 ? known : sqrt_ac[tn] known + sqrt(1 - ac[tn]) Philox(seed, VDX_DRAW_KNOWN + j); out = mask ? kn : x'.
+ * mask_tables has rows of length `timesteps`.  The DDIM chain starts from vdx_inpaint_init with t0 = seq[0].  An all-zero mask is
+ * vdx_ddim_step bit for bit.  x and out may alias. */
+int vdx_ddim_step_masked(const float* x, const float* eps_hat, float* out, const float* alphas_cumprod, const int* seq,
+                         const uint64_t* step_dev, const float* thres, int clip_denoised, const float* known, const unsigned char* mask,
+                         const float* mask_tables, int timesteps, uint64_t seed, int batch, int channels, long per_sample, void* stream);
+
+/* vdx_ddim_sample_loop_dyn with vdx_ddim_step_masked as the step (draw of step j: VDX_DRAW_KNOWN + j).  timesteps is required
+ * (mask_tables' row length) even without the dynamic threshold.  Own graph slot, as vdx_p_sample_loop_masked. */
+int vdx_ddim_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                                uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                                int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf,
+                                const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
+                                void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */

@@ -2,7 +2,8 @@
 --output-path, --checkpoint-path, --step, --seed, --batch-size, --load-ema-params) and its YAML schema, then runs
 GaussianDiffusion.sample on the GPU and writes one GIF per video (batch-global min-max to uint8, 120 ms/frame).
 Extensions: --mode {bf16,f16,f32}; --random-init (no checkpoint); --timesteps N (shorter chain for smoke runs); --ddim-steps S;
---attn-fp8 (bf16 mode: QK^T / PV of the <= 16-token attention blocks on fp8 MFMA operands)."""
+--attn-fp8 (bf16 mode: QK^T / PV of the <= 16-token attention blocks on fp8 MFMA operands);
+--context PATH.npy [--context-frames K] [--extend-frames N] [--resample-steps U] (video prediction / extension from given frames)."""
 import argparse
 import logging
 import os
@@ -24,6 +25,11 @@ FLAGS = (   # (flag, kwargs)
     ('--timesteps', dict(type=int, default=None, help='override diffusion.timesteps')),
     ('--ddim-steps', dict(type=int, default=None, help='sample with an S-step DDIM chain (eta = 0) instead of the T-step ancestral one')),
     ('--attn-fp8', dict(action='store_true', help='bf16 mode: fp8 (e4m3) QK^T / PV in the attention blocks over <= 16 tokens')),
+    ('--context', dict(type=str, default=None, help='[B,C,F,H,W] .npy clip (float in [0,1], or uint8 / 255): generate its continuation '
+                                                    'instead of sampling from noise; sets the batch')),
+    ('--context-frames', dict(type=int, default=None, help='with --context: keep its first K frames (default: all)')),
+    ('--extend-frames', dict(type=int, default=0, help='with --context: the videos get num_frames + N frames')),
+    ('--resample-steps', dict(type=int, default=1, help='with --context: RePaint resampling steps per noise level (ancestral chain only)')),
 )
 
 
@@ -38,11 +44,30 @@ def build_models(cfg, mode, timesteps=None, attn_fp8=False):
     return unet, gd
 
 
-def main(argv=None):
-    logging.basicConfig(level=logging.INFO, force=True)
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     for flag, kw in FLAGS:
         ap.add_argument(flag, **kw)
+    return ap
+
+
+def load_context(path, num_frames, context_frames=None, extend_frames=0):
+    """--context: (the first K frames of the clip as float32 [B,C,K,H,W] in [0,1], frames to generate = num_frames + N - K)."""
+    import numpy as np
+    v = np.load(path)
+    if v.ndim != 5:
+        raise ValueError(f'--context must hold a [B,C,F,H,W] array, got shape {v.shape}')
+    v = v.astype(np.float32) / 255.0 if v.dtype == np.uint8 else v.astype(np.float32)
+    k = v.shape[2] if context_frames is None else int(context_frames)
+    total = num_frames + int(extend_frames)
+    if not 1 <= k <= v.shape[2] or k >= total:
+        raise ValueError(f'--context-frames must be in [1, {min(v.shape[2], total - 1)}], got {k}')
+    return np.ascontiguousarray(v[:, :, :k]), total - k
+
+
+def main(argv=None):
+    logging.basicConfig(level=logging.INFO, force=True)
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.checkpoint_path is None and not a.random_init:
         ap.error('--checkpoint-path is required (or pass --random-init)')
@@ -81,7 +106,18 @@ def _run(a, ap, rank, world):
         ckpt = pathlib.Path(a.checkpoint_path).resolve()
         gd, _ = load_checkpoint(gd, a.step, str(ckpt), load_ema_params=a.load_ema_params)
         logging.info('restored step %d from %s', a.step, ckpt)
-    videos = gd.sample(a.seed, batch_size=a.batch_size, ddim_steps=a.ddim_steps)          # this rank's shard of the global batch
+    if a.context:
+        import torch
+        try:
+            ctx, n_new = load_context(a.context, gd.num_frames, a.context_frames, a.extend_frames)
+        except ValueError as e:
+            ap.error(str(e))
+        # the first window conditions on every kept frame (up to num_frames - 1), later windows on at least num_frames // 2
+        window_ctx = min(max(ctx.shape[2], gd.num_frames // 2), gd.num_frames - 1)
+        videos = gd.extend(a.seed, torch.from_numpy(ctx), n_new, context_frames=window_ctx, ddim_steps=a.ddim_steps,
+                           resample_steps=a.resample_steps)            # this rank's shard of the global batch
+    else:
+        videos = gd.sample(a.seed, batch_size=a.batch_size, ddim_steps=a.ddim_steps)          # this rank's shard of the global batch
     logging.info('rank %d drew %d videos', rank, len(videos))
     lo_hi = None
     if world > 1:                                      # the uint8 scaling is batch-GLOBAL (reference sample.py:107-110): two scalars cross ranks

@@ -78,14 +78,30 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     }
 }
 
+// the per-element arithmetic of one ancestral reverse step, shared by p_sample_kernel and p_sample_masked_kernel
+struct PStepCoef { float k_recip, k_recipm1, c1, c2, sigma, s; int clip; };
+
+__device__ __forceinline__ PStepCoef p_step_coef(const PSampleArgs& P, int b, int tb) {
+    PStepCoef k;
+    k.k_recip = P.tables[tb]; k.k_recipm1 = P.tables[P.T + tb];
+    k.c1 = P.tables[2 * P.T + tb]; k.c2 = P.tables[3 * P.T + tb];
+    k.sigma = (tb == 0) ? 0.f : expf(0.5f * P.tables[4 * P.T + tb]);
+    k.s = P.thres ? P.thres[b] : 1.0f;
+    k.clip = P.clip;
+    return k;
+}
+
+__device__ __forceinline__ float p_step_elem(const PStepCoef& k, float x, float eps, float z) {
+    float x0 = k.k_recip * x - k.k_recipm1 * eps;                      // predict_start_from_noise  (:133-136)
+    if (k.clip) x0 = fminf(fmaxf(x0, -k.s), k.s) / k.s;                 // :220
+    const float mean = k.c1 * x0 + k.c2 * x;                           // q_posterior (:153-156)
+    return mean + k.sigma * z;                                         // :261
+}
+
 // one reverse step.  tables: [5][T] = sqrt_recip_ac | sqrt_recipm1_ac | post_mean_coef1 | post_mean_coef2 | post_logvar_clipped
 __global__ __launch_bounds__(256) void p_sample_kernel(PSampleArgs P) {
     const int b = blockIdx.y;
-    const int tb = P.t[b];
-    const float k_recip = P.tables[tb], k_recipm1 = P.tables[P.T + tb];
-    const float c1 = P.tables[2 * P.T + tb], c2 = P.tables[3 * P.T + tb];
-    const float sigma = (tb == 0) ? 0.f : expf(0.5f * P.tables[4 * P.T + tb]);
-    const float s = P.thres ? P.thres[b] : 1.0f;
+    const PStepCoef kc = p_step_coef(P, b, P.t[b]);
     unsigned long long off = P.offset;
     if (P.dev_offset) off += *P.dev_offset;
     const long per = P.per_sample, fhw = P.per_sample / P.C;
@@ -112,12 +128,91 @@ __global__ __launch_bounds__(256) void p_sample_kernel(PSampleArgs P) {
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float x0 = k_recip * xv[k] - k_recipm1 * ev[k];                // predict_start_from_noise  (:133-136)
-            if (P.clip) x0 = fminf(fmaxf(x0, -s), s) / s;                  // :220
-            const float mean = c1 * x0 + c2 * xv[k];                       // q_posterior (:153-156)
-            const float o = mean + sigma * nv[k];                          // :261
+            const float o = p_step_elem(kc, xv[k], ev[k], nv[k]);
             if (i + k < per) P.out[base + i + k] = o * P.post_scale + P.post_shift;
         }
+    }
+}
+
+// Replacement-method conditioning (Ho et al. 2022, sec. 3.1) + RePaint resampling (Lugmayr et al. 2022): one pass that does the
+// ancestral step, merges the known region and optionally re-noises back to level t.  s = M.step + *M.step_dev (global step counter):
+//   x' = p_step(x, eps, Philox(seed, 1 + s))
+//   kn = t == 0 ? k : sqrt_ac[t-1] k + sqrt_1mac[t-1] Philox(seed, VDX_DRAW_KNOWN + s)
+//   x  = m ? kn : x'
+//   if s % U != U-1:  x = sqrt(alpha_t) x + sqrt(beta_t) Philox(seed, VDX_DRAW_RENOISE + s)
+// Needs per_sample % 4 == 0 (float4 x / known / out, uchar4 mask).  x and out may alias.
+__global__ __launch_bounds__(256) void p_sample_masked_kernel(PSampleArgs P, MaskArgs M) {
+    const int b = blockIdx.y;
+    const int tb = P.t[b];
+    const PStepCoef kc = p_step_coef(P, b, tb);
+    const unsigned long long s = M.step + (M.step_dev ? *M.step_dev : 0ull);
+    const bool renoise = (s % (unsigned long long)M.U) != (unsigned long long)(M.U - 1);
+    const float ka = tb > 0 ? M.mtab[tb - 1] : 1.f, kb = tb > 0 ? M.mtab[P.T + tb - 1] : 0.f;
+    const float ra = M.mtab[2 * P.T + tb], rb = M.mtab[3 * P.T + tb];
+    const long per = P.per_sample, fhw = P.per_sample / P.C;
+    const size_t base = (size_t)b * per;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; 4 * q < per; q += (long)gridDim.x * blockDim.x) {
+        const long i = 4 * q;
+        const unsigned long long ctr = (unsigned long long)(base / 4 + q);      // element index of the whole tensor / 4
+        const float4 x4 = *reinterpret_cast<const float4*>(P.x + base + i);
+        const uchar4 m4 = *reinterpret_cast<const uchar4*>(M.mask + base + i);
+        const float xv[4] = {x4.x, x4.y, x4.z, x4.w};
+        const bool mk[4] = {m4.x != 0, m4.y != 0, m4.z != 0, m4.w != 0};
+        float ev[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long e = i + k, c = e / fhw, r = e - c * fhw;                 // [C,F,H,W] -> channel-last [F,H,W,C]
+            ev[k] = P.eps[base + r * P.C + c];
+        }
+        const float4 z = randn4(ctr, P.seed, 1ull + s);
+        const float nv[4] = {z.x, z.y, z.z, z.w};
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = p_step_elem(kc, xv[k], ev[k], nv[k]);
+        if (mk[0] | mk[1] | mk[2] | mk[3]) {                                   // the known-region draw only where a lane needs it
+            const float4 k4 = *reinterpret_cast<const float4*>(M.known + base + i);
+            const float kv[4] = {k4.x, k4.y, k4.z, k4.w};
+            float zk[4] = {0.f, 0.f, 0.f, 0.f};
+            if (tb > 0) { const float4 w = randn4(ctr, P.seed, VDX_DRAW_KNOWN + s); zk[0] = w.x; zk[1] = w.y; zk[2] = w.z; zk[3] = w.w; }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (mk[k]) o[k] = tb > 0 ? ka * kv[k] + kb * zk[k] : kv[k];
+        }
+        if (renoise) {
+            const float4 w = randn4(ctr, P.seed, VDX_DRAW_RENOISE + s);
+            const float zr[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = ra * o[k] + rb * zr[k];
+        }
+        *reinterpret_cast<float4*>(P.out + base + i) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+// after a masked step: t[b] -= 1 (floor 0) when s % U == U-1, then s += 1 -- one captured step serves every (t, u)
+__global__ void resample_advance_kernel(int* t, int B, unsigned long long* step_dev, int U) {
+    const unsigned long long s = *step_dev;
+    if (s % (unsigned long long)U == (unsigned long long)(U - 1))
+        for (int i = threadIdx.x; i < B; i += blockDim.x)
+            if (t[i] > 0) t[i] -= 1;
+    __syncthreads();
+    if (threadIdx.x == 0) *step_dev = s + 1;
+}
+
+// first merge of the known region: x = m ? sqrt_ac[t0] k + sqrt_1mac[t0] x : x  (x_T's own noise; in place)
+__global__ __launch_bounds__(256) void inpaint_init_kernel(float* __restrict__ x, const float* __restrict__ known,
+                                                           const unsigned char* __restrict__ mask, const float* __restrict__ mtab,
+                                                           int T, int t0, long n) {
+    const float a = mtab[t0], bb = mtab[T + t0];
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; 4 * q < n; q += (long)gridDim.x * blockDim.x) {
+        const uchar4 m4 = *reinterpret_cast<const uchar4*>(mask + 4 * q);
+        if (!(m4.x | m4.y | m4.z | m4.w)) continue;
+        float4 x4 = *reinterpret_cast<const float4*>(x + 4 * q);
+        const float4 k4 = *reinterpret_cast<const float4*>(known + 4 * q);
+        if (m4.x) x4.x = a * k4.x + bb * x4.x;
+        if (m4.y) x4.y = a * k4.y + bb * x4.y;
+        if (m4.z) x4.z = a * k4.z + bb * x4.z;
+        if (m4.w) x4.w = a * k4.w + bb * x4.w;
+        *reinterpret_cast<float4*>(x + 4 * q) = x4;
     }
 }
 
@@ -128,26 +223,86 @@ __global__ __launch_bounds__(256) void p_sample_kernel(PSampleArgs P) {
 //   eps' = (x - sqrt(ac_t) x0) / sqrt(1 - ac_t)       (re-derived from the CLIPPED x0, as the usual implementations do)
 //   out = sqrt(ac_next) x0 + sqrt(1 - ac_next) eps'
 // (x and out may alias -- vdx.h -- so neither is __restrict__)
+// the per-element arithmetic of one DDIM step, shared by ddim_step_kernel and ddim_step_masked_kernel
+struct DdimCoef { float sa, s1, na, n1, s; int clip; };
+
+__device__ __forceinline__ DdimCoef ddim_coef(const float* ac, int tb, int tn, const float* thres, int b, int clip) {
+    const float a_t = ac[tb], a_n = tn >= 0 ? ac[tn] : 1.0f;
+    DdimCoef k;
+    k.sa = sqrtf(a_t); k.s1 = sqrtf(1.0f - a_t); k.na = sqrtf(a_n); k.n1 = sqrtf(1.0f - a_n);
+    k.s = thres ? thres[b] : 1.0f;
+    k.clip = clip;
+    return k;
+}
+
+__device__ __forceinline__ float ddim_mix(float a, float x, float b, float y) {
+#pragma clang fp contract(off)
+    return a * x + b * y;
+}
+
+// The contractions are spelled out: the one-element form and the four-element form would otherwise be fused differently by the
+// compiler (packed multiplies vs fma), and an all-zero mask must give vdx_ddim_step's values bit for bit.
+__device__ __forceinline__ float ddim_elem(const DdimCoef& k, float xv, float ev) {
+    float x0 = fmaf(-k.s1, ev, xv) / k.sa;
+    if (k.clip) x0 = fminf(fmaxf(x0, -k.s), k.s) / k.s;
+    const float e2 = fmaf(-k.sa, x0, xv) / k.s1;                    // eps re-derived from the clipped x0
+    return ddim_mix(k.na, x0, k.n1, e2);
+}
+
 __global__ __launch_bounds__(256) void ddim_step_kernel(const float* x, const float* __restrict__ eps, float* out,
                                                         const float* __restrict__ ac, const int* __restrict__ seq,
                                                         const unsigned long long* __restrict__ step_dev, const float* __restrict__ thres,
                                                         int clip, int C, long per_sample) {
     const int b = blockIdx.y;
     const int k = step_dev ? (int)*step_dev : 0;
-    const int tb = seq[k], tn = seq[k + 1];
-    const float a_t = ac[tb], a_n = tn >= 0 ? ac[tn] : 1.0f;
-    const float sa = sqrtf(a_t), s1 = sqrtf(1.0f - a_t), na = sqrtf(a_n), n1 = sqrtf(1.0f - a_n);
-    const float s = thres ? thres[b] : 1.0f;
+    const DdimCoef kc = ddim_coef(ac, seq[k], seq[k + 1], thres, b, clip);
     const long per = per_sample, fhw = per_sample / C;
     const size_t base = (size_t)b * per;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < per; e += (long)gridDim.x * blockDim.x) {
         const float xv = x[base + e];
         const long c = e / fhw, r = e - c * fhw;                         // [C,F,H,W] -> channel-last [F,H,W,C]
-        const float ev = eps[base + r * C + c];
-        float x0 = (xv - s1 * ev) / sa;
-        if (clip) x0 = fminf(fmaxf(x0, -s), s) / s;
-        const float e2 = (xv - sa * x0) / s1;
-        out[base + e] = na * x0 + n1 * e2;
+        out[base + e] = ddim_elem(kc, xv, eps[base + r * C + c]);
+    }
+}
+
+// masked DDIM step (eta = 0), 4 elements per thread: x' = ddim step (seq[j] -> seq[j+1]), j = *step_dev (or 0);
+//   kn = seq[j+1] < 0 ? k : sqrt_ac[tn] k + sqrt_1mac[tn] Philox(seed, VDX_DRAW_KNOWN + j);  out = m ? kn : x'
+__global__ __launch_bounds__(256) void ddim_step_masked_kernel(const float* x, const float* __restrict__ eps, float* out,
+                                                               const float* __restrict__ ac, const int* __restrict__ seq,
+                                                               const unsigned long long* __restrict__ step_dev, const float* __restrict__ thres,
+                                                               int clip, int C, long per_sample, MaskArgs M, int T, unsigned long long seed) {
+    const int b = blockIdx.y;
+    const int j = step_dev ? (int)*step_dev : 0;
+    const int tn = seq[j + 1];
+    const DdimCoef kc = ddim_coef(ac, seq[j], tn, thres, b, clip);
+    const float ka = tn >= 0 ? M.mtab[tn] : 1.f, kb = tn >= 0 ? M.mtab[T + tn] : 0.f;
+    const long per = per_sample, fhw = per_sample / C;
+    const size_t base = (size_t)b * per;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; 4 * q < per; q += (long)gridDim.x * blockDim.x) {
+        const long i = 4 * q;
+        const float4 x4 = *reinterpret_cast<const float4*>(x + base + i);
+        const uchar4 m4 = *reinterpret_cast<const uchar4*>(M.mask + base + i);
+        const float xv[4] = {x4.x, x4.y, x4.z, x4.w};
+        const bool mk[4] = {m4.x != 0, m4.y != 0, m4.z != 0, m4.w != 0};
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long e = i + k, c = e / fhw, r = e - c * fhw;                 // [C,F,H,W] -> channel-last [F,H,W,C]
+            o[k] = ddim_elem(kc, xv[k], eps[base + r * C + c]);
+        }
+        if (mk[0] | mk[1] | mk[2] | mk[3]) {
+            const float4 k4 = *reinterpret_cast<const float4*>(M.known + base + i);
+            const float kv[4] = {k4.x, k4.y, k4.z, k4.w};
+            float zk[4] = {0.f, 0.f, 0.f, 0.f};
+            if (tn >= 0) {
+                const float4 w = randn4((unsigned long long)(base / 4 + q), seed, VDX_DRAW_KNOWN + (unsigned long long)j);
+                zk[0] = w.x; zk[1] = w.y; zk[2] = w.z; zk[3] = w.w;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (mk[k]) o[k] = tn >= 0 ? ka * kv[k] + kb * zk[k] : kv[k];
+        }
+        *reinterpret_cast<float4*>(out + base + i) = make_float4(o[0], o[1], o[2], o[3]);
     }
 }
 
@@ -255,6 +410,24 @@ hipError_t launch_p_sample(const PSampleArgs& a, int B, hipStream_t st) {
     return hipGetLastError();
 }
 
+hipError_t launch_p_sample_masked(const PSampleArgs& a, const MaskArgs& m, int B, hipStream_t st) {
+    LaunchScope ls(st, "p_sample_masked_kernel", 0.0, 17.0 * B * a.per_sample, "B%d px%ld", B, a.per_sample);
+    hipLaunchKernelGGL(p_sample_masked_kernel, dim3(ew_blocks(a.per_sample / 4), B), dim3(256), 0, st, a, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_advance(int* t, int B, unsigned long long* step_dev, int U, hipStream_t st) {
+    LaunchScope ls(st, "resample_advance_kernel", 0.0, 0.0, "B%d", B);
+    hipLaunchKernelGGL(resample_advance_kernel, dim3(1), dim3(1024), 0, st, t, B, step_dev, U);
+    return hipGetLastError();
+}
+
+hipError_t launch_inpaint_init(float* x, const float* known, const unsigned char* mask, const float* mtab, int T, int t0, long n, hipStream_t st) {
+    LaunchScope ls(st, "inpaint_init_kernel", 0.0, 13.0 * n, "n%ld", n);
+    hipLaunchKernelGGL(inpaint_init_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, st, x, known, mask, mtab, T, t0, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_advance(int* t, int B, unsigned long long* dev_offset, hipStream_t st) {
     LaunchScope ls(st, "advance_kernel", 0.0, 0.0, "B%d", B);
     hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1024), 0, st, t, B, dev_offset);
@@ -265,6 +438,15 @@ hipError_t launch_ddim_step(const float* x, const float* eps, float* out, const 
                             const float* thres, int clip, int B, int C, long per_sample, hipStream_t st) {
     LaunchScope ls(st, "ddim_step_kernel", 0.0, 12.0 * B * per_sample, "B%d px%ld", B, per_sample);
     hipLaunchKernelGGL(ddim_step_kernel, dim3(ew_blocks(per_sample), B), dim3(256), 0, st, x, eps, out, ac, seq, step_dev, thres, clip, C, per_sample);
+    return hipGetLastError();
+}
+
+hipError_t launch_ddim_step_masked(const float* x, const float* eps, float* out, const float* ac, const int* seq, const unsigned long long* step_dev,
+                                   const float* thres, int clip, int B, int C, long per_sample, const MaskArgs& m, int T, unsigned long long seed,
+                                   hipStream_t st) {
+    LaunchScope ls(st, "ddim_step_masked_kernel", 0.0, 17.0 * B * per_sample, "B%d px%ld", B, per_sample);
+    hipLaunchKernelGGL(ddim_step_masked_kernel, dim3(ew_blocks(per_sample / 4), B), dim3(256), 0, st, x, eps, out, ac, seq, step_dev, thres, clip, C,
+                       per_sample, m, T, seed);
     return hipGetLastError();
 }
 

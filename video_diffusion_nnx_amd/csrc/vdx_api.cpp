@@ -9,8 +9,8 @@
 struct vdx_handle {
     vdx::Model model;
     // every argument a captured sampling step bakes in (full pointers: two workspaces / streams never alias one key)
-    struct GraphKey { const void* p[12]; unsigned long long seed; int i[4]; size_t ws; float f; };
-    // one cached graph per loop kind: 0 = DDPM p_sample_loop, 1 = DDIM
+    struct GraphKey { const void* p[16]; unsigned long long seed; int i[5]; size_t ws; float f; };
+    // one cached graph per loop kind: 0 = DDPM p_sample_loop, 1 = DDIM, 2 = masked DDPM, 3 = masked DDIM
     // `last` = the stream the exec was last launched on: replays may still be running when the graph has to go
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key; hipStream_t last = nullptr;
@@ -20,7 +20,7 @@ struct vdx_handle {
             if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
             last = nullptr;
         }
-    } gs[2];
+    } gs[4];
     void drop_graphs() { for (GraphSlot& g : gs) g.drop(); }
     vdx::BwdState bwd;
     vdx::Comm comm;
@@ -487,6 +487,78 @@ int vdx_p_sample_loop(vdx_handle* h, const float* params, const void* packed, fl
                                  0.f, nullptr, workspace, workspace_bytes, batch, use_graph, stream);
 }
 
+// the masked kernels move 16-byte float4 and 4-byte uchar4 vectors
+static bool masked_aligned(const void* x, const void* known, const void* out, const void* mask) {
+    return !((uintptr_t)x % 16 || (uintptr_t)known % 16 || (uintptr_t)out % 16 || (uintptr_t)mask % 4);
+}
+
+int vdx_inpaint_init(float* x, const float* known, const unsigned char* mask, const float* mask_tables, int timesteps, int t0,
+                     long n, void* stream) {
+    if (!x || !known || !mask || !mask_tables || timesteps < 1 || t0 < 0 || t0 >= timesteps || n < 0) VDX_FAIL(VDX_ERR_INVALID, "inpaint_init: bad argument");
+    if (n % 4) VDX_FAIL(VDX_ERR_INVALID, "inpaint_init: n must be a multiple of 4");
+    if (!masked_aligned(x, known, x, mask)) VDX_FAIL(VDX_ERR_INVALID, "inpaint_init: x / known must be 16-byte and mask 4-byte aligned");
+    if (n) VDX_HIP(vdx::launch_inpaint_init(x, known, mask, mask_tables, timesteps, t0, n, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_p_sample_step_masked(const float* x, const float* eps_hat, float* out, const int* t, const float* tables, int timesteps,
+                             const float* known, const unsigned char* mask, const float* mask_tables, int resample_steps,
+                             uint64_t seed, uint64_t step, const uint64_t* step_dev, const float* thres, int clip_denoised,
+                             int batch, int channels, long per_sample, void* stream) {
+    if (!x || !eps_hat || !out || !t || !tables || !known || !mask || !mask_tables || timesteps < 1 || batch < 1 || channels < 1 || per_sample < 1)
+        VDX_FAIL(VDX_ERR_INVALID, "p_sample_masked: bad argument");
+    if (resample_steps < 1) VDX_FAIL(VDX_ERR_INVALID, "p_sample_masked: resample_steps must be >= 1");
+    if (per_sample % channels || per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "p_sample_masked: per_sample must be a multiple of channels and of 4");
+    if (!masked_aligned(x, known, out, mask)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_masked: x / known / out must be 16-byte and mask 4-byte aligned");
+    vdx::PSampleArgs a;
+    fill_psample(a, x, eps_hat, out, t, tables, timesteps, nullptr, seed, 0, nullptr, thres, clip_denoised, channels, per_sample);
+    const vdx::MaskArgs m = {known, mask, mask_tables, resample_steps, step, reinterpret_cast<const unsigned long long*>(step_dev)};
+    VDX_HIP(vdx::launch_p_sample_masked(a, m, batch, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_p_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                             uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                             int clip_denoised, float percentile, float* thres_buf, const float* known, const unsigned char* mask,
+                             const float* mask_tables, int resample_steps, void* workspace, size_t workspace_bytes, int batch,
+                             int use_graph, void* stream) {
+    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !tables || !workspace || !known || !mask || !mask_tables)
+        VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: null argument");
+    if (!h->model.d_ss_layers) VDX_FAIL(VDX_ERR_STATE, "p_sample_loop_masked: handle was created without a GPU");
+    if (resample_steps < 1) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: resample_steps must be >= 1");
+    if (timesteps < 1 || nsteps < 0 || (long)nsteps > (long)timesteps * resample_steps) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: nsteps out of range");
+    const bool dyn = percentile > 0.f && clip_denoised;
+    if (dyn && (!thres_buf || percentile > 1.f)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: dynamic threshold needs thres_buf and a percentile in (0, 1]");
+    const vdx::Model& m = h->model;
+    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
+    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: C*F*H*W must be a multiple of 4");
+    if (m.out_dim != m.cfg.channels) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: out_dim must equal channels");
+    if (!masked_aligned(img, known, img, mask)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: img / known must be 16-byte and mask 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* sd = reinterpret_cast<unsigned long long*>(step_dev);
+    auto step = [&]() -> int {
+        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
+        if (rc != VDX_OK) return rc;
+        hipError_t e = hipSuccess;
+        if (dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
+        vdx::PSampleArgs a;
+        fill_psample(a, img, eps_buf, img, t_dev, tables, timesteps, nullptr, seed, 0, nullptr, dyn ? thres_buf : nullptr, clip_denoised, m.cfg.channels, per_sample);
+        const vdx::MaskArgs ma = {known, mask, mask_tables, resample_steps, 0ull, sd};
+        if (e == hipSuccess) e = vdx::launch_p_sample_masked(a, ma, batch, st);
+        if (e == hipSuccess) e = vdx::launch_resample_advance(t_dev, batch, sd, resample_steps, st);
+        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        return VDX_OK;
+    };
+    vdx_handle::GraphKey key;
+    memset(&key, 0, sizeof(key));
+    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
+    key.p[6] = tables; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = dyn ? thres_buf : nullptr;
+    key.p[11] = known; key.p[12] = mask; key.p[13] = mask_tables;
+    key.seed = seed; key.i[0] = timesteps; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch; key.i[4] = resample_steps;
+    key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
+    return run_steps(h, 2, key, nsteps, use_graph, st, step);
+}
+
 int vdx_ddim_step(const float* x, const float* eps_hat, float* out, const float* alphas_cumprod, const int* seq,
                   const uint64_t* step_dev, const float* thres, int clip_denoised, int batch, int channels, long per_sample, void* stream) {
     if (!x || !eps_hat || !out || !alphas_cumprod || !seq || batch < 1 || channels < 1 || per_sample < 1 || per_sample % channels)
@@ -534,6 +606,61 @@ int vdx_ddim_sample_loop(vdx_handle* h, const float* params, const void* packed,
                          int clip_denoised, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
     return vdx_ddim_sample_loop_dyn(h, params, packed, img, eps_buf, t_dev, step_dev, alphas_cumprod, seq, seq_len, nsteps, cond, clip_denoised,
                                     nullptr, 0, 0.f, nullptr, workspace, workspace_bytes, batch, use_graph, stream);
+}
+
+int vdx_ddim_step_masked(const float* x, const float* eps_hat, float* out, const float* alphas_cumprod, const int* seq,
+                         const uint64_t* step_dev, const float* thres, int clip_denoised, const float* known, const unsigned char* mask,
+                         const float* mask_tables, int timesteps, uint64_t seed, int batch, int channels, long per_sample, void* stream) {
+    if (!x || !eps_hat || !out || !alphas_cumprod || !seq || !known || !mask || !mask_tables || timesteps < 1 || batch < 1 || channels < 1 ||
+        per_sample < 1 || per_sample % channels)
+        VDX_FAIL(VDX_ERR_INVALID, "ddim_step_masked: bad argument");
+    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "ddim_step_masked: per_sample must be a multiple of 4");
+    if (!masked_aligned(x, known, out, mask)) VDX_FAIL(VDX_ERR_INVALID, "ddim_step_masked: x / known / out must be 16-byte and mask 4-byte aligned");
+    const vdx::MaskArgs m = {known, mask, mask_tables, 1, 0ull, nullptr};
+    VDX_HIP(vdx::launch_ddim_step_masked(x, eps_hat, out, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev), thres,
+                                         clip_denoised, batch, channels, per_sample, m, timesteps, seed, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_ddim_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                                uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                                int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf,
+                                const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
+                                void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !alphas_cumprod || !seq || !workspace || !known || !mask || !mask_tables)
+        VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: null argument");
+    if (!h->model.d_ss_layers) VDX_FAIL(VDX_ERR_STATE, "ddim_sample_loop_masked: handle was created without a GPU");
+    if (seq_len < 1 || nsteps < 0 || nsteps > seq_len) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: nsteps out of range");
+    if (timesteps < 1) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: timesteps (the row length of mask_tables) must be >= 1");
+    const bool dyn = percentile > 0.f && clip_denoised;
+    if (dyn && (!thres_buf || !tables || percentile > 1.f)) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: dynamic threshold needs tables, thres_buf and a percentile in (0, 1]");
+    const vdx::Model& m = h->model;
+    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
+    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: C*F*H*W must be a multiple of 4");
+    if (m.out_dim != m.cfg.channels) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: out_dim must equal channels");
+    if (!masked_aligned(img, known, img, mask)) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: img / known must be 16-byte and mask 4-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const vdx::MaskArgs ma = {known, mask, mask_tables, 1, 0ull, nullptr};
+    auto step = [&]() -> int {
+        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
+        if (rc != VDX_OK) return rc;
+        hipError_t e = hipSuccess;
+        if (dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
+        if (e == hipSuccess) e = vdx::launch_ddim_step_masked(img, eps_buf, img, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev),
+                                                              dyn ? thres_buf : nullptr, clip_denoised, batch, m.cfg.channels, per_sample, ma,
+                                                              timesteps, seed, st);
+        if (e == hipSuccess) e = vdx::launch_ddim_advance(t_dev, batch, seq, reinterpret_cast<unsigned long long*>(step_dev), st);
+        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        return VDX_OK;
+    };
+    vdx_handle::GraphKey key;
+    memset(&key, 0, sizeof(key));
+    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
+    key.p[6] = alphas_cumprod; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = seq; key.p[11] = dyn ? (const void*)thres_buf : nullptr;
+    key.p[12] = known; key.p[13] = mask; key.p[14] = mask_tables; key.p[15] = dyn ? (const void*)tables : nullptr;
+    key.seed = seed; key.i[0] = seq_len; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch; key.i[3] = timesteps;
+    key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
+    return run_steps(h, 3, key, nsteps, use_graph, st, step);
 }
 
 int vdx_pack_conv_weights_t(int mode, const float* kernel, void* packed, int taps, int cin, int cout, void* stream) {

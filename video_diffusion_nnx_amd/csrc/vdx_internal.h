@@ -177,6 +177,19 @@ hipError_t launch_q_sample(const float* x0, const int* t, const float* noise, fl
                            int B, long per_sample, float pre_scale, float pre_shift, hipStream_t st);
 hipError_t launch_p_sample(const PSampleArgs& a, int B, hipStream_t st);
 hipError_t launch_advance(int* t, int B, unsigned long long* dev_offset, hipStream_t st);
+struct MaskArgs {                                        // the known region of a masked (inpainting) reverse step
+    const float* known; const unsigned char* mask;       // k = 2 video - 1 and the element mask (1 = known), both [B,C,F,H,W]
+    const float* mtab;                                   // [4][T] = sqrt_ac | sqrt_1mac | sqrt(alpha) | sqrt(beta)
+    int U;                                               // resample steps per noise level
+    unsigned long long step; const unsigned long long* step_dev;   // global step counter s = step + *step_dev
+};
+// P.noise / P.offset / P.dev_offset are not read: the draws are 1 + s, VDX_DRAW_KNOWN + s, VDX_DRAW_RENOISE + s
+hipError_t launch_p_sample_masked(const PSampleArgs& a, const MaskArgs& m, int B, hipStream_t st);
+hipError_t launch_resample_advance(int* t, int B, unsigned long long* step_dev, int U, hipStream_t st);
+hipError_t launch_ddim_step_masked(const float* x, const float* eps, float* out, const float* ac, const int* seq, const unsigned long long* step_dev,
+                                   const float* thres, int clip, int B, int C, long per_sample, const MaskArgs& m, int T, unsigned long long seed,
+                                   hipStream_t st);
+hipError_t launch_inpaint_init(float* x, const float* known, const unsigned char* mask, const float* mtab, int T, int t0, long n, hipStream_t st);
 hipError_t launch_ddim_step(const float* x, const float* eps, float* out, const float* ac, const int* seq, const unsigned long long* step_dev,
                             const float* thres, int clip, int B, int C, long per_sample, hipStream_t st);
 hipError_t launch_ddim_advance(int* t, int B, const int* seq, unsigned long long* step_dev, hipStream_t st);

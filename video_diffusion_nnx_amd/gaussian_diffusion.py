@@ -31,6 +31,51 @@ vdx_ddim_step = L._sig('vdx_ddim_step', C.c_int, [_vp] * 7 + [C.c_int, C.c_int, 
 vdx_ddim_sample_loop = L._sig('vdx_ddim_sample_loop', C.c_int, [_vp] * 9 + [C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, _vp])
 vdx_ddim_sample_loop_dyn = L._sig('vdx_ddim_sample_loop_dyn', C.c_int, [_vp] * 9 + [C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_float, _vp, _vp, C.c_size_t,
                                                                        C.c_int, C.c_int, _vp])
+vdx_inpaint_init = L._sig('vdx_inpaint_init', C.c_int, [_vp] * 4 + [C.c_int, C.c_int, C.c_long, _vp])
+vdx_p_sample_step_masked = L._sig('vdx_p_sample_step_masked', C.c_int, [_vp] * 5 + [C.c_int, _vp, _vp, _vp, C.c_int, _u64, _u64, _vp, _vp, C.c_int,
+                                                                             C.c_int, C.c_int, C.c_long, _vp])
+vdx_p_sample_loop_masked = L._sig('vdx_p_sample_loop_masked', C.c_int, [_vp] * 8 + [C.c_int, C.c_int, _vp, _u64, C.c_int, C.c_float, _vp, _vp, _vp, _vp,
+                                                                             C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, _vp])
+vdx_ddim_step_masked = L._sig('vdx_ddim_step_masked', C.c_int, [_vp] * 7 + [C.c_int] + [_vp] * 3 + [C.c_int, _u64, C.c_int, C.c_int, C.c_long, _vp])
+vdx_ddim_sample_loop_masked = L._sig('vdx_ddim_sample_loop_masked', C.c_int, [_vp] * 9 + [C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_float]
+                                     + [_vp] * 4 + [_u64, _vp, C.c_size_t, C.c_int, C.c_int, _vp])
+
+
+def extend_plan(have: int, num_new: int, num_frames: int, context_frames: int):
+    """The windows of GaussianDiffusion.extend as (ctx, new) pairs: a window of `num_frames` holds the last ctx = min(context_frames,
+    frames so far) frames as known frames and keeps the next new = min(num_frames - ctx, frames still missing) generated ones."""
+    if not 1 <= context_frames < num_frames:
+        raise ValueError(f'context_frames must be in [1, {num_frames - 1}], got {context_frames}')
+    if have < 1 or num_new < 0:
+        raise ValueError(f'need at least one given frame and num_new >= 0, got {have}, {num_new}')
+    plan = []
+    while num_new > 0:
+        ctx = min(context_frames, have)
+        new = min(num_frames - ctx, num_new)
+        plan.append((ctx, new))
+        have, num_new = have + new, num_new - new
+    return plan
+
+
+def frame_mask(mask, shape) -> torch.Tensor:
+    """The element mask of `inpaint` (1 = known) as contiguous uint8 of `shape` = [B,C,F,H,W], on `mask`'s device.  `mask` is [F]
+    (the same frames of every video), [B,F] (per video) or anything that broadcasts to `shape`; bool or uint8."""
+    B, _, Fr, _, _ = shape
+    m = torch.as_tensor(mask)
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f'mask must be bool or uint8, got {m.dtype}')
+    if m.dim() == 1 and m.shape[0] == Fr:
+        m = m.reshape(1, 1, Fr, 1, 1)
+    elif m.dim() == 2 and tuple(m.shape) == (B, Fr):
+        m = m.reshape(B, 1, Fr, 1, 1)
+    else:
+        try:
+            ok = torch.broadcast_shapes(tuple(m.shape), tuple(shape)) == torch.Size(shape)
+        except RuntimeError:
+            ok = False
+        if not ok:
+            raise ValueError(f'mask of shape {tuple(m.shape)} is neither [F], [B, F] nor broadcastable to {tuple(shape)}')
+    return (m != 0).to(torch.uint8).expand(*shape).contiguous()
 
 
 def ddim_time_sequence(timesteps: int, steps: int) -> np.ndarray:
@@ -135,6 +180,10 @@ class GaussianDiffusion:
         # the five tables the reverse step needs, stacked [5][T] for the kernel
         self._ptab = torch.stack([self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod, self.posterior_mean_coef1,
                                   self.posterior_mean_coef2, self.posterior_log_variance_clipped]).contiguous()
+        # the factors of the masked (inpainting) steps, stacked [4][T]: sqrt_ac | sqrt(1 - ac) | sqrt(alpha) | sqrt(beta)
+        betas = cosine_beta_schedule(self.num_timesteps)
+        self._mtab = torch.from_numpy(np.stack([tabs['sqrt_alphas_cumprod'], tabs['sqrt_one_minus_alphas_cumprod'],
+                                                np.sqrt(np.float32(1) - betas), np.sqrt(betas)]).astype(np.float32)).to(self.device)
         self._sample_stream = None
 
     # -- closed forms (table look-ups) -------------------------------------------------------------
@@ -325,6 +374,166 @@ class GaussianDiffusion:
         if ddim_steps:
             return self.ddim_sample_loop(shape, key, steps=int(ddim_steps), cond=cond, cond_scale=cond_scale, **kw)
         return self.p_sample_loop(shape, key, cond=cond, cond_scale=cond_scale, **kw)
+
+    def inpaint(self, key, video, mask, *, cond=None, cond_scale: float = 1.0, ddim_steps: Optional[int] = None, resample_steps: int = 1,
+                use_graph: bool = True, x_T=None):
+        """Frame-conditioned sampling (EXTENSION): generate the unknown part of `video` ([B,C,F,H,W] in [0,1]) with the
+        unconditionally trained denoiser by the replacement method (Ho et al. 2022, sec. 3.1); resample_steps U > 1 adds RePaint
+        resampling (Lugmayr et al. 2022, ancestral chain only).  mask: [F], [B,F] or broadcastable to `video`, bool / uint8, 1 = known
+        (frame_mask).  ddim_steps S: an S-step DDIM chain (eta = 0) instead of the T-step ancestral one.  The known region of the
+        result is `video` up to one affine rounding; an all-zero mask with U = 1 is p_sample_loop / ddim_sample_loop.
+        Data parallel as sample(): `video` (and `mask`, `cond`, `x_T`) are the GLOBAL batch, rank r returns its rows, drawn with
+        shard_key(key, r).  Draws: vdx.h (VDX_DRAW_KNOWN, VDX_DRAW_RENOISE)."""
+        shape = self._check_inpaint(video, ddim_steps, resample_steps, x_T)
+        m = frame_mask(mask, shape)
+        rank, world = dist_rank_world()
+        if world > 1:
+            assert shape[0] % world == 0, 'batch_size must be divisible by number of devices'
+            rows = slice(rank * shape[0] // world, (rank + 1) * shape[0] // world)
+            video, m, key = video[rows], m[rows], shard_key(key, rank, world)
+            cond = None if cond is None else cond[rows]
+            x_T = None if x_T is None else x_T[rows]
+        return self._inpaint_local(key, video, m, cond, cond_scale, ddim_steps, int(resample_steps), use_graph, x_T)
+
+    def _check_inpaint(self, video, ddim_steps, resample_steps, x_T):
+        if int(resample_steps) < 1:
+            raise ValueError(f'resample_steps must be >= 1, got {resample_steps}')
+        if ddim_steps and int(resample_steps) > 1:
+            raise ValueError('resampling (resample_steps > 1) is defined for the ancestral chain only, not with ddim_steps')
+        shape = tuple(video.shape)
+        if len(shape) != 5 or shape[1:] != (self.channels, self.num_frames, self.image_size, self.image_size):
+            raise ValueError(f'video must be [B, {self.channels}, {self.num_frames}, {self.image_size}, {self.image_size}], got {shape}')
+        if x_T is not None and tuple(x_T.shape) != shape:
+            raise ValueError(f'x_T must have the shape of video {shape}, got {tuple(x_T.shape)}')
+        return shape
+
+    def _inpaint_bufs(self, B, steps):
+        """Device buffers of the masked loops, kept across calls of the same batch size: the captured step bakes their addresses
+        in, so a second call (another window of extend(), say) replays the cached graph when the seed is the same."""
+        key = (B, steps)
+        if getattr(self, '_ibuf_key', None) != key:
+            shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
+            dev = self.device
+            self._ibuf = dict(img=torch.empty(shape, device=dev), known=torch.empty(shape, device=dev),
+                              mask=torch.empty(shape, dtype=torch.uint8, device=dev),
+                              eps=torch.empty(B, self.num_frames, self.image_size, self.image_size, self.denoise_fn.out_dim, device=dev),
+                              t=torch.empty(B, dtype=torch.int32, device=dev), step=torch.zeros(1, dtype=torch.int64, device=dev),
+                              thres=torch.empty(B, device=dev),
+                              seq=None if not steps else torch.from_numpy(ddim_time_sequence(self.num_timesteps, steps)).to(dev))
+            self._ibuf_key = key
+        return self._ibuf
+
+    def _inpaint_local(self, key, video, m, cond, cond_scale, ddim_steps, U, use_graph, x_T):
+        seed = int(key) & 0xFFFFFFFFFFFFFFFF
+        B = video.shape[0]
+        S = int(ddim_steps) if ddim_steps else 0
+        unet = self.denoise_fn
+        T = self.num_timesteps
+        if self._sample_stream is None:
+            self._sample_stream = torch.cuda.Stream(device=self.device)
+        cur, st = torch.cuda.current_stream(self.device), self._sample_stream
+        st.wait_stream(cur)
+        keep_storage = unet.act_bf16
+        unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
+        try:
+            with torch.cuda.stream(st):
+                buf = self._inpaint_bufs(B, S)
+                img, known, mk = buf['img'], buf['known'], buf['mask']
+                n, per = img.numel(), self._per_sample(img)
+                if x_T is None:
+                    L.check(vdx_randn(L.ptr(img), n, seed, 0, 0, L.stream_ptr()))
+                else:
+                    img.copy_(self._dev(x_T))
+                vd = self._dev(video)
+                L.check(vdx_affine(L.ptr(vd), L.ptr(known), n, 2.0, -1.0, L.stream_ptr()))      # normalize_img
+                mk.copy_(m)
+                seq_host = ddim_time_sequence(T, S) if S else None
+                t0 = int(seq_host[0]) if S else T - 1
+                L.check(vdx_inpaint_init(L.ptr(img), L.ptr(known), L.ptr(mk), L.ptr(self._mtab), T, t0, n, L.stream_ptr()))
+                guided = cond is not None and unet.has_cond and cond_scale != 1
+                thres = buf['thres'] if self.use_dynamic_thres else None
+                perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
+                if guided:                                   # two forwards per step: eager, with the numbering of the captured loops
+                    if S:
+                        for j in range(S):
+                            t = torch.full((B,), int(seq_host[j]), dtype=torch.int32, device=self.device)
+                            eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
+                            buf['step'].fill_(j)
+                            th = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
+                            L.check(vdx_ddim_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']),
+                                                         L.ptr(buf['step']), L.ptr(th), 1, L.ptr(known), L.ptr(mk), L.ptr(self._mtab), T, seed,
+                                                         B, self.channels, per, L.stream_ptr()))
+                    else:
+                        s = 0
+                        for i in reversed(range(T)):
+                            t = torch.full((B,), i, dtype=torch.int32, device=self.device)
+                            for _ in range(U):
+                                eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
+                                th = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
+                                L.check(vdx_p_sample_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(t), L.ptr(self._ptab), T, L.ptr(known),
+                                                                 L.ptr(mk), L.ptr(self._mtab), U, seed, s, 0, L.ptr(th), 1, B, self.channels, per,
+                                                                 L.stream_ptr()))
+                                s += 1
+                else:
+                    condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
+                    h = unet.handle(self.num_frames, self.image_size)
+                    unet.apply_activation_storage(h)
+                    ws = unet.workspace(B, self.num_frames, self.image_size)
+                    buf['t'].fill_(t0)
+                    buf['step'].zero_()
+                    if S:
+                        L.check(vdx_ddim_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
+                                                            L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']), S, S,
+                                                            L.ptr(condd), 1, L.ptr(self._ptab), T, perc, L.ptr(thres), L.ptr(known), L.ptr(mk),
+                                                            L.ptr(self._mtab), seed, L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
+                    else:
+                        L.check(vdx_p_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
+                                                         L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self._ptab), T, T * U, L.ptr(condd), seed, 1,
+                                                         perc, L.ptr(thres), L.ptr(known), L.ptr(mk), L.ptr(self._mtab), U, L.ptr(ws), ws.numel(),
+                                                         B, int(use_graph), L.stream_ptr()))
+                out = torch.empty_like(img)
+                L.check(vdx_affine(L.ptr(img), L.ptr(out), n, 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
+        finally:
+            unet.act_bf16 = keep_storage
+        cur.wait_stream(st)
+        return out
+
+    def extend(self, key, video, num_new_frames: int, *, context_frames: Optional[int] = None, **inpaint_kw):
+        """Grow `video` ([B,C,F0,H,W] in [0,1], any F0 >= 1) by `num_new_frames` frames, autoregressively (EXTENSION): window w
+        holds the last `ctx` frames so far as known frames and generates the next ones with inpaint() (extend_plan; context_frames
+        defaults to num_frames // 2).  Window keys: split_key(key, n_windows).  Returns [B,C,F0 + N,H,W]; its first F0 frames are
+        `video` itself.  Data parallel as sample(): sharded once (rows and shard_key), not per window."""
+        ctx = self.num_frames // 2 if context_frames is None else int(context_frames)
+        video = torch.as_tensor(video)
+        if video.dim() != 5 or tuple(video.shape[1:2] + video.shape[3:]) != (self.channels, self.image_size, self.image_size):
+            raise ValueError(f'video must be [B, {self.channels}, F, {self.image_size}, {self.image_size}], got {tuple(video.shape)}')
+        plan = extend_plan(video.shape[2], int(num_new_frames), self.num_frames, ctx)
+        if plan:
+            probe = video.new_zeros((video.shape[0], self.channels, self.num_frames, self.image_size, self.image_size))
+            self._check_inpaint(probe, inpaint_kw.get('ddim_steps'), inpaint_kw.get('resample_steps', 1), inpaint_kw.get('x_T'))
+        rank, world = dist_rank_world()
+        cond = inpaint_kw.pop('cond', None)
+        if world > 1:
+            assert video.shape[0] % world == 0, 'batch_size must be divisible by number of devices'
+            rows = slice(rank * video.shape[0] // world, (rank + 1) * video.shape[0] // world)
+            video, key = video[rows], shard_key(key, rank, world)
+            cond = None if cond is None else cond[rows]
+        video = self._dev(video)
+        B, F0 = video.shape[0], video.shape[2]
+        clip = torch.empty(B, self.channels, F0 + int(num_new_frames), self.image_size, self.image_size, device=self.device)
+        clip[:, :, :F0] = video
+        window = torch.zeros(B, self.channels, self.num_frames, self.image_size, self.image_size, device=self.device)
+        ddim_steps, U = inpaint_kw.pop('ddim_steps', None), int(inpaint_kw.pop('resample_steps', 1))
+        have = F0
+        for (c, n), k in zip(plan, split_key(key, len(plan))):
+            window[:, :, :c] = clip[:, :, have - c:have]
+            frames = torch.arange(self.num_frames, device=self.device) < c
+            m = frame_mask(frames, tuple(window.shape))
+            out = self._inpaint_local(k, window, m, cond, inpaint_kw.get('cond_scale', 1.0), ddim_steps, U, inpaint_kw.get('use_graph', True),
+                                      inpaint_kw.get('x_T'))
+            clip[:, :, have:have + n] = out[:, :, c:c + n]
+            have += n
+        return clip
 
     def interpolate(self, x1, x2, t: Optional[int] = None, lam: float = 0.5, key: int = 0):
         """reference :360-398 with the intended behaviour (the reference omits the mandatory keys, Q18)."""
