@@ -438,6 +438,98 @@ int vdx_sla_core_backward_ex(const float* q, const float* k, const float* v, con
 int vdx_colsum(const float* x, float* out, long rows, int c, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Backward forms of the network (test-facing).  vdx_unet_backward sets flags on the launchers that the block-level entry points
+ * above never set: bf16 TENSORS (not only bf16 operands), the q|k|v split epilogue, fused bias sums, per-workgroup slots with a
+ * fixed-order second pass, interleaved [rows][dq|dk|dv] outputs, row slices of a transposed packing.  The functions below fill the
+ * launchers' argument structs the way model_bwd.hip does and call the same launchers, so that each of those kernel forms can be
+ * compared with a reference on its own (tests/test_gpu_backward_forms.py).  No kernel is specific to them.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Weight gradient as model_bwd.hip's wgrad() (:102-117), wgrad1x1() (:179-190) and wgrad1x1_qkv() (:193-206) launch it.
+ * Served forms (anything else is VDX_ERR_INVALID): 1x1 and 3x3 at stride 1, 4x4 at stride 2, kind 1; the prologue only with 3x3 and no
+ * split; split only with 1x1.
+ *   x_bf16 / dy_bf16: x0 (and x1) / dy hold bf16 elements (bf16_operands only; channel counts multiples of 8).  wgrad() passes
+ *     x_bf16 = activation storage (block inputs) or 1 (the prologue form reading y1), dy_bf16 = 1 in bf16 mode;
+ *   split > 0 (a multiple of 64 dividing cout into <= 3 blocks): column block co / split of dy goes to (dw, dw1, dw2), each
+ *     [taps][c0+c1][split], and to (db, db1, db2) -- the q|k|v launch (split = heads * 32);
+ *   db (db1, db2): bias gradient(s) [cout] (or [split]) accumulated in the same pass, or NULL;
+ *   scratch / scratch_floats: per-workgroup slots (wgrad(): vdx_wgrad_scratch_floats()).  When the launch's slots fit, every
+ *     workgroup stores its partial tile and a second pass adds the slots in a fixed order: two runs are bit-identical.  When they do
+ *     not fit (or scratch is NULL) the kernels add with float atomics.  Either way the outputs are ACCUMULATED into. */
+typedef struct {
+    const void* x0; const void* x1; int c0, c1; int x_bf16;
+    const void* dy; int cout; int dy_bf16;
+    float* dw; float* dw1; float* dw2; int split;
+    float* db; float* db1; float* db2;
+    int batch, frames, h, w;
+    int kind, kh, kw, stride;
+    const double* in_stats; const float* gamma; const float* beta; int groups;
+    const float* scale_shift; int scale_shift_stride;
+    int bf16_operands;
+    float* scratch; size_t scratch_floats;
+} vdx_wgrad_ex_desc;
+int vdx_conv_backward_weights_ex(const vdx_wgrad_ex_desc* d, void* stream);
+/* Floats of slot scratch vdx_unet_backward hands every weight gradient (per stream): tests pass the same size, so that a launch
+ * takes the slot or the atomic path exactly where the network's does. */
+size_t vdx_wgrad_scratch_floats(void);
+
+/* The fixed-order second pass on its own (launch_slot_sum): d[e'] += sum over k < nslots, in order, of part[k * slot_stride + e],
+ * e < e_count.  split == 0: d0[e].  split > 0: e = row * cout + co goes to (d0, d1, d2)[co / split][row * split + co % split].
+ * nslots >= 32 runs slot_sum16_kernel (16 lanes per element), fewer slot_sum_kernel. */
+int vdx_slot_sum(const float* part, int nslots, size_t slot_stride, long e_count, int cout, int split, float* d0, float* d1, float* d2,
+                 void* stream);
+
+/* vdx_norm_act_backward with the tensor types and the deterministic parameter-gradient path of model_bwd.hip's res_bwd() (:128-137
+ * tail, :144-151 prologue): y_bf16 / r_bf16 = y / r hold bf16, dy_bf16 = dy is WRITTEN as bf16 (one rounding of the fp32 result);
+ * dact, dr stay fp32.  dgp: NULL (parameter gradients by float atomics) or scratch [batch][4][c] floats, uninitialised: the
+ * per-sample rows are stored there and added in sample order -- two runs are bit-identical.  scratch as vdx_norm_act_backward:
+ * uninitialised in every mode (the reduce pass stores each workgroup's row, nothing accumulates into it; the network keeps it at a
+ * fixed offset of its workspace for the same reason). */
+int vdx_norm_act_backward_ex(const float* dact, const void* y, int y_bf16, void* dy, int dy_bf16, const double* stats, const float* gamma,
+                             const float* beta, int groups, const float* scale_shift, int scale_shift_stride, float* d_gamma, float* d_beta,
+                             float* dss, const void* r, int r_bf16, const float* ln_gamma, float* dr, float* d_ln_gamma, float* d_ln_beta,
+                             float* scratch, float* dgp, int c, int batch, long pix_per_sample, void* stream);
+
+/* vdx_attention_core_backward_ex as attn_bwd() launches it (model_bwd.hip:234-243): ONE output buffer dqkv [rows][dq|dk|dv] with
+ * dstride = 3 * heads * 32 in the network (a wider row, a multiple of 8, leaves the columns behind dq|dk|dv untouched; dk / dv start
+ * heads*32 / 2*heads*32 elements into the row, in the buffer's own element size); io_bf16:
+ * qkv, d_o, o, dqkv hold bf16.  bf16 tensors exist for the bf16 MFMA kernel only: io_bf16 without bf16_operands, or with more than
+ * 16 tokens per sequence, is VDX_ERR_INVALID. */
+int vdx_attention_core_backward_io(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, int batch, int frames,
+                                   int h, int w, int heads, int temporal, int bf16_operands, void* stream);
+
+/* vdx_temporal_attention_backward_fused with x_bf16 (model_bwd.hip:219-227 under bf16 activation storage): x holds bf16. */
+int vdx_temporal_attention_backward_fused_ex(const void* x, int x_bf16, const float* dy, const void* packed_wqkv, const float* bqkv,
+                                             const void* packed_wo_t, void* o_bf16, void* dqkv_bf16, float* dx, int batch, int frames, int h,
+                                             int w, void* stream);
+
+/* vdx_sla_core_backward_ex as sla_bwd() launches it (model_bwd.hip:261-268): one dqkv [rows][dq|dk|dv] buffer, dstride = 768 (or wider);
+ * io_bf16: q, k, v, d_out, o, dqkv hold bf16 (bf16_operands only). */
+int vdx_sla_core_backward_io(const void* q, const void* k, const void* v, const void* d_out, void* o, void* dqkv, int dstride, int io_bf16,
+                             float* scratch, int nframes, int npix, int heads, int bf16_operands, void* stream);
+
+/* vdx_conv_forward reading rows [w_row0, w_row0 + cout) of a packing with w_rows rows per tap: the data gradient of one half of a
+ * concat input from the transposed packing of the whole kernel (model_bwd.hip dgrad() :89-100, res_bwd() :156-160), usually with
+ * d->res.  Multiples of 4. */
+int vdx_conv_forward_rows(int mode, const vdx_conv_desc* d, int w_rows, int w_row0, void* stream);
+
+/* Backward of vdx_final_conv (model_bwd.hip:392): dx [npix][d] written; dw [d][cout], db [cout] ACCUMULATED.  x_bf16: x holds bf16.
+ * d a multiple of 4, <= 256; cout <= 4.  scratch: optional slots for the fixed-order sums (atomics when NULL or too small). */
+int vdx_final_conv_backward(const void* x, int x_bf16, const float* d_out, const float* kernel, float* dx, float* dw, float* db, long npix, int d,
+                            int cout, float* scratch, size_t scratch_floats, void* stream);
+
+/* Weight and bias gradient of vdx_init_conv (model_bwd.hip:465): x external [B,Cin,F,H,W], dy channel-last [B,F,H,W,Cout];
+ * dw Flax (k,k,Cin,Cout), db [Cout] ACCUMULATED.  scratch as above. */
+int vdx_init_conv_backward_weights(const float* x, const float* dy, float* dw, float* db, int batch, int cin, int frames, int h, int w, int cout,
+                                   int k, float* scratch, size_t scratch_floats, void* stream);
+
+/* Backward of vdx_time_mlp (model_bwd.hip:456-461): dtemb [batch][4*dim + cond_dim]; dw1 [dim][4 dim], db1, dw2 [4 dim][4 dim], db2 and
+ * dnull [cond_dim] (rows whose sample used null_cond_emb: cond_mask, else null_all) are ACCUMULATED. */
+int vdx_time_mlp_backward(const int* time, const float* w1, const float* b1, const float* w2, const float* b2, int dim, const unsigned char* cond_mask,
+                          int null_all, int cond_dim, const float* dtemb, float* dw1, float* db1, float* dw2, float* db2, float* dnull, int batch,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Train step (reference trainer.py:322-392).
  * ---------------------------------------------------------------------------------------------- */
 

@@ -1,0 +1,303 @@
+"""Comparison helpers shared by the block-level parity tests of the backward forms (tests/test_gpu_backward_forms.py) and by
+the CPU-only sensitivity tests that prove they bite (tests/test_host_parity_helpers.py).  A plain module: nothing here is
+collected, nothing here touches the GPU.
+
+Where the numbers come from.  No bound in this file is derived from a kernel's output:
+
+* exact-products forms (bf16-representable operands, fp32 accumulate, fp32 result): the project states 5e-6 for the weight
+  gradient and 2e-6 for the forward under this contract (tests/test_gpu_conv_backward.py, tests/test_gpu_conv.py), measured at
+  tensors of the size of one slice here.  `exact_products_bounds` keeps that figure where the arithmetic allows it and, for long
+  reductions, replaces it by 8 x the error of the same contraction evaluated in fp32 on the CPU against fp64 (a CPU GEMM sums in a
+  more favourable order than a chunked GPU sum; 8 x covers the difference).  A bound of 1e-4 or more is refused: one bf16 rounding
+  is 2^-9 = 2e-3, and a test looser than two orders below that no longer separates a kernel fault from arithmetic.
+* bf16 stores: the kernel rounds an fp32 value once, so an element is bf16(ref) or, when the fp32 error moved the value across a
+  rounding boundary, its neighbour -- never further.  `assert_bf16_store` checks that per element and caps the share of elements
+  that differ from bf16(ref) at all by 4 x the share of reference elements close enough to a rounding boundary to flip.
+* attention / SLA cores round probabilities and score gradients to bf16 inside: `attn_core`, `sla_core` and `fused_attention` with
+  emulate=True restate the kernels' rounding points in fp64; the per-group bound is 3 x the worst group of that
+  emulation against the plain fp64 reference (the emulation cannot reproduce the MFMA summation order, hence the margin).
+"""
+import math
+
+import torch
+
+BF16_ROUNDING = 2.0 ** -9          # half an ulp of bf16 relative to the binade's lower end
+EXACT_CEILING = 1e-4               # an exact-products bound must stay below this (see above)
+WGRAD_STATED = 5e-6                # the project's stated bound for the exact-products weight gradient
+FWD_STATED = 2e-6                  # ... and for the exact-products forward / data gradient
+
+
+def bf16r(t: torch.Tensor) -> torch.Tensor:
+    """Round-trip through bf16 (round to nearest even), keeping the dtype."""
+    return t.float().to(torch.bfloat16).to(t.dtype)
+
+
+def bf16_trunc(t: torch.Tensor) -> torch.Tensor:
+    """bf16 by TRUNCATION of the fp32 bit pattern (what a kernel that drops the low 16 bits would store); keeps the dtype."""
+    bits = t.float().contiguous().view(torch.int32) & -65536
+    return bits.view(torch.float32).to(t.dtype)
+
+
+def rel(a: torch.Tensor, b: torch.Tensor) -> float:
+    """rel-L2 of a against the reference b."""
+    return ((a.double() - b.double()).norm() / (b.double().norm() + 1e-300)).item()
+
+
+def bf16_ulp(t: torch.Tensor) -> torch.Tensor:
+    """Spacing of bf16 numbers in the binade of each element (fp64; 0 for 0)."""
+    t = t.double().abs()
+    _, e = torch.frexp(t)                                   # t = m 2^e, m in [0.5, 1)
+    ulp = torch.ldexp(torch.ones_like(t), e - 8)            # 8 significant bits
+    return torch.where(t > 0, ulp, torch.zeros_like(t))
+
+
+# ---- slices -------------------------------------------------------------------------------------------------------------
+
+
+def wgrad_slices(shape, tile=64):
+    """Slices of a Flax weight gradient [..taps.., Cin, Cout]: one per (tap, 64-input-channel tile, 64-output-channel tile) -- the unit a
+    weight-gradient workgroup owns.  -> list of (label, index tuple) on the tensor viewed as [taps, Cin, Cout]."""
+    cin, cout = shape[-2], shape[-1]
+    taps = 1
+    for s in shape[:-2]:
+        taps *= s
+    out = []
+    for t in range(taps):
+        for ci in range(0, cin, tile):
+            for co in range(0, cout, tile):
+                out.append((f'tap{t}/ci{ci}/co{co}', (t, slice(ci, min(ci + tile, cin)), slice(co, min(co + tile, cout)))))
+    return out
+
+
+def sample_slices(shape):
+    """One slice per sample (leading axis) of an activation tensor."""
+    return [(f'sample{b}', (b,)) for b in range(shape[0])]
+
+
+def _view3(t):
+    return t.reshape(-1, t.shape[-2], t.shape[-1])
+
+
+def slice_rels(got, ref64, slices, view=None):
+    """rel-L2 per slice -> list of (label, rel)."""
+    v = view or (lambda t: t)
+    g, r = v(got.double()), v(ref64.double())
+    return [(lab, rel(g[idx], r[idx])) for lab, idx in slices]
+
+
+# ---- exact products ---------------------------------------------------------------------------------------------------------
+
+
+def exact_products_bounds(ref32, ref64, slices=None, view=None, stated=WGRAD_STATED):
+    """Bounds for a kernel under the exact-products contract, from the reference side alone: ref32 = the same contraction
+    evaluated in fp32 on the CPU, ref64 in fp64, both on the same bf16-representable operands.
+    -> (global bound, {slice label: bound}, global floor): bound = max(stated, 8 x floor), refused when >= 1e-4."""
+    floor = rel(ref32, ref64)
+    bound = max(stated, 8.0 * floor)
+    assert bound < EXACT_CEILING, f'exact-products bound {bound:.2e} (floor {floor:.2e}) does not separate a kernel fault from arithmetic'
+    sb = {}
+    if slices:
+        for lab, f in slice_rels(ref32, ref64, slices, view):
+            sb[lab] = max(stated, 8.0 * f)
+            assert sb[lab] < EXACT_CEILING, f'slice {lab}: bound {sb[lab]:.2e} too loose'
+    return bound, sb, floor
+
+
+def assert_exact_products(got, ref64, floor, slices=None, slice_floors=None, view=None, what=''):
+    """rel-L2 of `got` against the fp64 reference (computed on the same bf16-representable operands) below `floor` (the bound from
+    exact_products_bounds or a stated figure), and below `slice_floors[label]` (default: `floor`) on every slice, so that one bad tile
+    cannot hide in the global norm.  Prints measured value and bound.  -> (global rel, worst slice label, worst slice rel)"""
+    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
+    assert torch.isfinite(got).all(), f'{what}: non-finite output'
+    r = rel(got, ref64)
+    worst = ('-', 0.0, floor)
+    bad = []
+    for lab, sr in (slice_rels(got, ref64, slices, view) if slices else []):
+        b = (slice_floors or {}).get(lab, floor)
+        if sr / b > worst[1] / worst[2]:
+            worst = (lab, sr, b)
+        if not sr < b:
+            bad.append((lab, sr, b))
+    print(f'[exact] {what}: rel {r:.3e} (bound {floor:.3e}); worst slice {worst[0]} {worst[1]:.3e} (bound {worst[2]:.3e})')
+    assert r < floor, f'{what}: rel-L2 {r:.3e} >= {floor:.3e}'
+    assert not bad, f'{what}: {len(bad)} slice(s) over their bound, first {bad[0][0]}: {bad[0][1]:.3e} >= {bad[0][2]:.3e}'
+    return r, worst[0], worst[1]
+
+
+# ---- bf16 stores -----------------------------------------------------------------------------------------------------------
+
+
+def bf16_flip_cap(ref64, fp32_floor):
+    """Share of reference elements closer to a bf16 rounding boundary (the midpoint of two neighbouring bf16 numbers) than
+    fp32_floor * |ref|, times 4: only those elements can legitimately be stored as the neighbour of bf16(ref)."""
+    r = ref64.double()
+    rb = bf16r(r)
+    dist = (bf16_ulp(r) * 0.5 - (r - rb).abs()).abs()       # distance of ref to the nearer boundary of its rounding interval
+    near = (dist < fp32_floor * r.abs()) & (r != 0)
+    return 4.0 * near.double().mean().item()
+
+
+def assert_bf16_store(got_bf16, ref64, fp32_floor, what=''):
+    """For a kernel that rounds an fp32 result to bf16 once.  Every element within one bf16 ulp of bf16(ref) plus
+    fp32_floor * rms(ref) (the absolute term is for elements that are small through cancellation) -- no element is exempt; and the
+    share of elements that differ from bf16(ref) at all at most bf16_flip_cap(ref, fp32_floor).  A kernel that truncates, or rounds
+    twice, differs on a large share and fails the cap although every element is within one ulp.  -> (share, cap, worst excess)"""
+    assert got_bf16.shape == ref64.shape, (what, got_bf16.shape, ref64.shape)
+    g = got_bf16.double()
+    assert torch.isfinite(g).all(), f'{what}: non-finite output'
+    r = ref64.double()
+    rb = bf16r(r)
+    rms = r.pow(2).mean().sqrt().item()
+    tol = torch.maximum(bf16_ulp(rb), bf16_ulp(g)) + fp32_floor * rms
+    excess = ((g - rb).abs() / tol).max().item()
+    share = (g != rb).double().mean().item()
+    cap = bf16_flip_cap(r, fp32_floor)
+    print(f'[bf16 store] {what}: differing share {share:.3e} (cap {cap:.3e}); worst |got - bf16(ref)| = {excess:.3f} x (1 ulp + {fp32_floor:.1e} rms)')
+    assert excess <= 1.0, f'{what}: an element is {excess:.2f} x (one ulp + floor) away from bf16(ref)'
+    assert share <= cap, f'{what}: {share:.3e} of the elements differ from bf16(ref), cap {cap:.3e} (truncation or a second rounding?)'
+    return share, cap, excess
+
+
+# ---- groups ----------------------------------------------------------------------------------------------------------------
+
+
+def per_group_rel(got, ref, group_shape):
+    """rel-L2 per group: both tensors are viewed as [*group_shape, -1] (the caller permutes so that the group axes lead: attention
+    sequences, (frame, head) pairs).  -> (worst rel, index of the worst group, tensor of all)"""
+    n = 1
+    for s in group_shape:
+        n *= s
+    g, r = got.double().reshape(n, -1), ref.double().reshape(n, -1)
+    rels = (g - r).norm(dim=1) / (r.norm(dim=1) + 1e-300)
+    i = int(rels.argmax())
+    return rels[i].item(), i, rels.reshape(*group_shape)
+
+
+def assert_groups(got, ref, group_shape, bound, what=''):
+    w, i, _ = per_group_rel(got, ref, group_shape)
+    print(f'[groups] {what}: worst group {i} rel {w:.3e} (bound {bound:.3e})')
+    assert w < bound, f'{what}: group {i} rel-L2 {w:.3e} >= {bound:.3e}'
+    return w
+
+
+# ---- fp64 references and emulations of the attention cores --------------------------------------------------------------------
+
+
+def _seq_view(rows, B, Fr, HW, heads, temporal, parts):
+    """[rows][parts*heads*32] -> [nseq..., L, parts, heads, 32] with the token axis third from... (b, hw, f, ..) or (b, f, hw, ..)."""
+    x = rows.reshape(B, Fr, HW, parts, heads, 32)
+    return x.permute(0, 2, 1, 3, 4, 5) if temporal else x
+
+
+def _seq_unview(t, temporal):
+    """inverse of _seq_view for [b, s, L, heads, 32]-shaped results -> [rows][heads*32]"""
+    t = t.permute(0, 2, 1, 3, 4) if temporal else t
+    return t.reshape(-1, t.shape[-2] * 32)
+
+
+def attn_core(qkv, d_o, B, Fr, HW, heads, temporal, emulate=False, round_out=False, dtype=torch.float64):
+    """Attention core backward in `dtype` (fp64 = the reference), closed form (autodiff of softmax(q k^T / sqrt 32) v per sequence and head).
+    emulate: probabilities P and score gradients dS are rounded to bf16 before the second products, as attn_core_bwd16_kernel
+    does (q, k, v, d_o are expected bf16-representable already); round_out: o, dq, dk, dv rounded to bf16 (the io_bf16 store).
+    -> o [rows][HD], dqkv [rows][3 HD]"""
+    s = _seq_view(qkv.to(dtype), B, Fr, HW, heads, temporal, 3)
+    q, k, v = s[..., 0, :, :], s[..., 1, :, :], s[..., 2, :, :]                     # [b, s, L, h, d]
+    do = _seq_view(d_o.to(dtype), B, Fr, HW, heads, temporal, 1)[..., 0, :, :]
+    sc = 1.0 / math.sqrt(32.0)
+    S = torch.einsum('bsihd,bsjhd->bshij', q, k) * sc
+    P = torch.softmax(S, -1)
+    dP = torch.einsum('bsihd,bsjhd->bshij', do, v)
+    dS = P * (dP - (P * dP).sum(-1, keepdim=True))
+    if emulate:
+        P, dS = bf16r(P), bf16r(dS)
+    o = torch.einsum('bshij,bsjhd->bsihd', P, v)
+    dv = torch.einsum('bshij,bsihd->bsjhd', P, do)
+    dq = torch.einsum('bshij,bsjhd->bsihd', dS, k) * sc
+    dk = torch.einsum('bshij,bsihd->bsjhd', dS, q) * sc
+    outs = [_seq_unview(t, temporal) for t in (o, dq, dk, dv)]
+    if round_out:
+        outs = [bf16r(t) for t in outs]
+    return outs[0], torch.cat(outs[1:], -1)
+
+
+def sla_core(q, k, v, d_out, NF, N, emulate=False, round_out=False, dtype=torch.float64):
+    """SpatialLinearAttention core backward in fp64, closed form, 8 heads x 32 (autodiff of out = ctx^T softmax_d(q),
+    ctx = softmax_n(k)^T v per (frame, head)).  emulate: the rounding points of sla_bwd_a16_kernel / sla_bwd_b16_kernel:
+    exp(k - max), softmax_d(q) rounded to bf16 for the two reductions; ctx, dctx, softmax_d(q), softmax_n(k) rounded to bf16 for the
+    four per-pixel products (the elementwise factors stay unrounded).  -> o [rows][256], dqkv [rows][768]"""
+    hs = lambda t: t.to(dtype).reshape(NF, N, 8, 32).permute(0, 2, 1, 3)            # [f, h, n, d]
+    Q, K, V, D = hs(q), hs(k), hs(v), hs(d_out)
+    rd = bf16r if emulate else (lambda t: t)
+    qs = torch.softmax(Q, -1)
+    ek = torch.exp(K - K.max(dim=2, keepdim=True).values)
+    ksum = ek.sum(2, keepdim=True)
+    ks = ek / ksum
+    ctx = torch.einsum('fhnd,fhne->fhde', rd(ek), V) / ksum.transpose(2, 3)
+    dctx = torch.einsum('fhnd,fhne->fhde', rd(qs), D)
+    T = (ctx * dctx).sum(-1)                                                       # [f, h, d]
+    o = torch.einsum('fhde,fhnd->fhne', rd(ctx), rd(qs))
+    dqs = torch.einsum('fhde,fhne->fhnd', rd(ctx), D)
+    dq = qs * (dqs - (qs * dqs).sum(-1, keepdim=True))
+    dv = torch.einsum('fhde,fhnd->fhne', rd(dctx), rd(ks))
+    dks = torch.einsum('fhde,fhne->fhnd', rd(dctx), V)
+    dk = ks * (dks - T[:, :, None, :])
+    back = lambda t: t.permute(0, 2, 1, 3).reshape(NF * N, 256)
+    outs = [back(t) for t in (o, dq, dk, dv)]
+    if round_out:
+        outs = [bf16r(t) for t in outs]
+    return outs[0], torch.cat(outs[1:], -1)
+
+
+def fused_attention(x, dy, wqkv, bqkv, wo, B, Fr, HW, emulate=False, dtype=torch.float64):
+    """Backward of y = MHA(x) + x over the frames of every pixel (8 heads x 32, C = 64) in fp64, closed form.  emulate: the rounding
+    points of attn_bwd16x_kernel: q|k|v = bf16(x W + b), dO = bf16(dy Wo^T), the core as attn_core(emulate), o and dq|dk|dv stored
+    as bf16 and read back as such for dx = dy + dqkv W^T (x, dy, W, Wo are expected bf16-representable already).
+    -> dx [rows][64], o [rows][256], dqkv [rows][768]"""
+    X, G = x.to(dtype).reshape(-1, 64), dy.to(dtype).reshape(-1, 64)
+    W, Wo = wqkv.to(dtype), wo.to(dtype)
+    rd = bf16r if emulate else (lambda t: t)
+    qkv = rd(X @ W + bqkv.to(dtype))
+    dO = rd(G @ Wo.t())
+    o, dqkv = attn_core(qkv, dO, B, Fr, HW, 8, True, emulate=emulate, round_out=emulate, dtype=dtype)
+    dx = G + dqkv @ W.t()
+    return dx, o, dqkv
+
+
+def group_bound(emulated, ref64, group_shape, margin=3.0):
+    """Per-group bound for a kernel with bf16 rounding inside: margin x the worst group of the fp64 emulation of its rounding points
+    against the plain fp64 reference."""
+    return margin * per_group_rel(emulated, ref64, group_shape)[0]
+
+
+# ---- small closed forms --------------------------------------------------------------------------------------------------------
+
+
+def gn_stats_slab(y, groups=8):
+    """GroupNorm statistics slab [B][32 slots][groups][2] (sum, sum of squares; slot 0 holds everything) of a channel-last tensor, fp64."""
+    B, C = y.shape[0], y.shape[-1]
+    yg = y.double().reshape(B, -1, groups, C // groups)
+    stats = torch.zeros(B, 32, groups, 2, dtype=torch.float64)
+    stats[:, 0, :, 0] = yg.sum(dim=(1, 3))
+    stats[:, 0, :, 1] = (yg * yg).sum(dim=(1, 3))
+    return stats
+
+
+def slot_pattern(nslots, e_count, slot_stride):
+    """Hand-made slots for the fixed-order pass: slot k holds (k + 1) + 3 (e % 11) in element e, the last element carries 1000 more
+    and the last slot 7 more, the padding between slots -1e6 (never to be read).  Every sum is an integer below 2^24, so the
+    expected result is exact in fp32 whatever the order: a dropped slot or a ragged tail is an exact integer mismatch.
+    -> (part [nslots * slot_stride] fp32, expected sums [e_count] fp64)"""
+    k = torch.arange(nslots, dtype=torch.float64)[:, None]
+    e = torch.arange(e_count, dtype=torch.float64)[None, :]
+    val = (k + 1) + 3 * (e % 11) + 1000 * (e == e_count - 1) + 7 * (k == nslots - 1)
+    part = torch.full((nslots, slot_stride), -1e6, dtype=torch.float64)
+    part[:, :e_count] = val
+    exp = val.sum(0)
+    assert exp.max() < 2 ** 24
+    return part.reshape(-1).float(), exp
+
+
+def split_columns(flat, cout, split):
+    """[rows * cout] laid out [rows][cout] -> list of [rows][split] column blocks (the q|k|v split epilogue's targets)."""
+    m = flat.reshape(-1, cout)
+    return [m[:, i * split:(i + 1) * split].contiguous() for i in range(cout // split)]

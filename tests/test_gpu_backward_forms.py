@@ -1,0 +1,652 @@
+"""Block-level parity of the backward forms that only vdx_unet_backward reaches: bf16 TENSORS in and out, the q|k|v split epilogue, fused
+bias sums, per-workgroup slots with the fixed-order second pass, interleaved [rows][dq|dk|dv] outputs, row slices of a transposed
+packing, and the small backward kernels -- through the test-facing entry points of include/vdx.h ("Backward forms of the network").
+
+Every input is made bf16-representable on the host before it goes to either side, so input rounding is not part of any error.
+References are fp64 torch.autograd through oracle/unet3d_ref.py (the attention cores: the fp64 closed forms of tests/_parity.py, which
+tests/test_host_parity_helpers.py pins to autograd).  Every bound comes from the reference side and is printed next to the measured
+value (run with -s); tests/_parity.py says where each number comes from, tests/test_host_parity_helpers.py shows on the CPU that a
+dropped patch row, a dropped slot, a misplaced column block, a truncating store and an unwritten sequence are rejected at these bounds."""
+import functools
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+import _parity as P
+from oracle import train_ref as TR
+from oracle import unet3d_ref as R
+
+DEV = 'cuda:0'
+F32, F64, BF = torch.float32, torch.float64, torch.bfloat16
+
+
+def _dev(t, dtype=F32):
+    return None if t is None else t.detach().to(dtype).to(DEV).contiguous()
+
+
+@pytest.fixture(scope='module')
+def slots():
+    """The slot scratch the network hands every weight gradient (12 Mi floats), NaN-filled: a slot read before it is written shows."""
+    from video_diffusion_nnx_amd import ops
+    return torch.full((ops.WG_PART_FLOATS,), float('nan'), dtype=F32, device=DEV)
+
+
+# ---- weight gradients -----------------------------------------------------------------------------------------------------------------
+
+# name: (B, F, H, W, c0, c1, cout, k, stride, kind, prologue, split)
+WG_CASES = {
+    # conv2 of a level-0 block at the north-star shape: the prologue form reading y1 (8 x 16 patches, 256 slots -> slot_sum16_kernel)
+    'n_l0_conv2_pro': (2, 16, 64, 64, 64, 0, 64, 3, 1, 0, True, 0),
+    # ups level 0 block1: two-pointer concat 64 + 64 -> 64
+    'n_ups0_concat': (1, 8, 64, 64, 64, 64, 64, 3, 1, 0, False, 0),
+    'l1_128': (1, 16, 32, 32, 128, 0, 128, 3, 1, 0, False, 0),
+    'l2_256': (1, 16, 16, 16, 256, 0, 256, 3, 1, 0, False, 0),
+    'l3_512': (1, 16, 8, 8, 512, 0, 512, 3, 1, 0, False, 0),          # W < 16: 8 x 8 patches; 4 slots -> slot_sum_kernel
+    # W >= 16 but not a multiple of 16, H not a multiple of 8, channel tiles partly filled
+    'ragged_20x24': (1, 3, 20, 24, 24, 0, 40, 3, 1, 0, False, 0),
+    'ragged_9x17': (1, 3, 9, 17, 24, 0, 40, 3, 1, 0, False, 0),
+    'ragged_9x17_pro': (2, 3, 9, 17, 24, 0, 40, 3, 1, 0, True, 0),
+    'down_64': (1, 4, 64, 64, 64, 0, 64, 4, 2, 0, False, 0),
+    'up_64': (1, 4, 32, 32, 64, 0, 64, 4, 1, 1, False, 0),
+    'down_128': (1, 8, 16, 16, 128, 0, 128, 4, 2, 0, False, 0),
+    'up_128': (1, 8, 16, 16, 128, 0, 128, 4, 1, 1, False, 0),
+    # 1x1 (wgrad1x1_kernel: 64-row tiles, `per` consecutive tiles per workgroup = ceil(tiles / min(tiles, target / channel tiles)), target
+    # 512 for NCO = 4 and 1024 for NCO = 1).  The q|k|v launch (split = 256, three bias outputs):
+    'qkv_64_768': (2, 16, 16, 16, 64, 0, 768, 1, 1, 0, False, 256),         # 128 tiles, one per workgroup
+    'qkv_64_768_ragged': (1, 3, 5, 7, 64, 0, 768, 1, 1, 0, False, 256),     # 105 rows: one full tile + a ragged one, one per workgroup
+    # the north-star launch: 131072 rows = 2048 tiles, 170 workgroups -> per = 13, 158 slots, the last workgroup walks 7 tiles
+    'qkv_64_768_n': (2, 16, 64, 64, 64, 0, 768, 1, 1, 0, False, 256),
+    # 61425 rows = 959 tiles + 49 rows: per = 6, 160 workgroups of exactly 6 tiles, the last tile ragged
+    'qkv_64_768_tail': (1, 15, 63, 65, 64, 0, 768, 1, 1, 0, False, 256),
+    # 65536 rows = 1024 tiles: per = 7, 147 slots, the last workgroup walks 2 tiles
+    'qkv_64_768_1024': (1, 16, 64, 64, 64, 0, 768, 1, 1, 0, False, 256),
+    'out_256_64': (2, 16, 16, 16, 256, 0, 64, 1, 1, 0, False, 0),          # out projection, NCO = 1
+    'out_256_64_ragged': (1, 5, 9, 11, 256, 0, 64, 1, 1, 0, False, 0),     # 495 rows, one tile per workgroup
+    'out_256_64_n': (2, 16, 64, 64, 256, 0, 64, 1, 1, 0, False, 0),        # north-star: 2048 tiles, 256 workgroups of 8
+    'out_256_64_tail': (1, 9, 61, 61, 256, 0, 64, 1, 1, 0, False, 0),      # 33489 rows = 523 tiles + 17 rows: per = 3, 175 slots, last: 2 tiles
+    'pw_72_256': (1, 3, 5, 7, 72, 0, 256, 1, 1, 0, False, 0),              # split-K NCO = 4, ragged rows and channels
+    'rc_128_128_256': (1, 4, 12, 12, 128, 128, 256, 1, 1, 0, False, 0),    # res_conv over a concat input, 9 row tiles
+}
+
+
+def _conv_wgrad_ref(xhat, dy, k, stride, kind):
+    """Weight gradient by autograd through the oracle's forward, in the dtype of xhat (the kernel value does not enter: linear)."""
+    kk = 4 if kind else k
+    kern = torch.zeros(1, kk, kk, xhat.shape[-1], dy.shape[-1], dtype=xhat.dtype, requires_grad=True)
+    if kind == 1:
+        y = R.conv_transpose_144(xhat, kern, None)
+    elif k == 1:
+        y = R.conv_pointwise(xhat, kern[0], None)
+    else:
+        y = R.conv_1kk(xhat, kern, None, stride=stride)
+    assert y.shape == dy.shape, (y.shape, dy.shape)
+    (g,) = torch.autograd.grad(y, kern, dy)
+    return g
+
+
+def _prologue(y1, gamma, beta, ss, dt):
+    C = y1.shape[-1]
+    s = ss.to(dt)
+    h = R.group_norm(y1.to(dt), gamma.to(dt), beta.to(dt), 8) * (s[:, None, None, None, :C] + 1) + s[:, None, None, None, C:]
+    return R.silu(h)
+
+
+@functools.lru_cache(maxsize=2)
+def _wg_case(name):
+    """Operands (fp32 host tensors holding bf16-representable values), fp64 reference and the bounds of one case."""
+    B, Fr, H, W, c0, c1, cout, k, stride, kind, pro, split = WG_CASES[name]
+    g = torch.Generator().manual_seed(sum(map(ord, name)))
+    Ho, Wo = (2 * H, 2 * W) if kind else (H // stride, W // stride)
+    x0 = P.bf16r(torch.randn(B, Fr, H, W, c0, generator=g) * 1.5 + (0.3 if pro else 0.0))
+    x1 = P.bf16r(torch.randn(B, Fr, H, W, c1, generator=g)) if c1 else None
+    dy = P.bf16r(torch.randn(B, Fr, Ho, Wo, cout, generator=g))
+    case = dict(x0=x0, x1=x1, dy=dy, pro=None)
+    shape = (1, 4 if kind else k, 4 if kind else k, c0 + c1, cout)
+    sl = P.wgrad_slices(shape)
+    if pro:
+        gamma, beta = 1 + 0.2 * torch.randn(c0, generator=g), 0.2 * torch.randn(c0, generator=g)
+        ss = 0.3 * torch.randn(B, 2 * c0, generator=g)
+        ss[B - 1] *= 3.0                                                    # samples of different scale
+        case['pro'] = (P.gn_stats_slab(x0), gamma, beta, ss)
+        # the kernel rounds the recomputed activation to bf16 once; the reference rounds SiLU(GN(y1)(1+s)+sh) at the same point
+        xh64 = P.bf16r(_prologue(x0, gamma, beta, ss, F64))
+        xh32 = P.bf16r(_prologue(x0, gamma, beta, ss, F32)).double()
+        ref = _conv_wgrad_ref(xh64, dy.double(), k, stride, kind)
+        alt = _conv_wgrad_ref(xh32, dy.double(), k, stride, kind)
+        # floor = the contraction with the activation computed in fp64-then-rounded against fp32-then-rounded (rounding-boundary
+        # flips); bound = 4 x that (the GPU evaluates the norm in another fp32 order).  Replaces the 8e-3 of the fp32-tensor twin.
+        # The flip count of a small tensor is a small integer (often 0 on the CPU): the floor is not taken below the effect of ONE
+        # flipped element of rms size, bf16_ulp(rms) / ||xhat|| over the input channels that feed the slice -- a figure of the number
+        # format and the shape alone.
+        def one_flip(lo, hi):
+            xs = xh64[..., lo:hi]
+            return (P.bf16_ulp(xs.pow(2).mean().sqrt()) / xs.norm()).item()
+        floor = max(P.rel(alt, ref), one_flip(0, c0))
+        bound = max(P.WGRAD_STATED, 4.0 * floor)
+        sb = {}
+        for (lab, idx), (_, f) in zip(sl, P.slice_rels(alt, ref, sl, P._view3)):
+            sb[lab] = max(P.WGRAD_STATED, 4.0 * max(f, one_flip(idx[1].start, idx[1].stop)))
+        # 8e-3 is what the fp32-tensor twin is held to; this form must stay more than an order below it whatever the case data
+        assert bound < 5e-4 and max(sb.values()) < 5e-4
+    else:
+        xin = x0 if x1 is None else torch.cat((x0, x1), -1)
+        ref = _conv_wgrad_ref(xin.double(), dy.double(), k, stride, kind)
+        ref32 = _conv_wgrad_ref(xin, dy, k, stride, kind)
+        bound, sb, floor = P.exact_products_bounds(ref32, ref, sl, P._view3)
+    print(f'[wgrad {name}] reference-side floor {floor:.3e} -> bound {bound:.3e}, worst slice bound {max(sb.values()):.3e}')
+    case.update(ref=ref, refb=dy.double().sum(dim=(0, 1, 2, 3)), shape=shape, sl=sl, bound=bound, sb=sb)
+    return case
+
+
+def _run_wgrad(name, c, x16, dy16, scratch, bias, bf16_operands=True):
+    from video_diffusion_nnx_amd import ops
+    B, Fr, H, W, c0, c1, cout, k, stride, kind, pro, split = WG_CASES[name]
+    xt = BF if x16 else F32
+    kw = {}
+    if c['pro'] is not None:
+        stats, gamma, beta, ss = c['pro']
+        kw = dict(in_stats=stats.reshape(-1).to(DEV), gamma=_dev(gamma), beta=_dev(beta), scale_shift=_dev(ss))
+    if scratch is not None:
+        scratch.fill_(float('nan'))              # every run: a slot that is read without having been written in THIS launch shows
+    dws, dbs = ops.conv_backward_weights_ex(_dev(c['x0'], xt), _dev(c['dy'], BF if dy16 else F32), c['shape'], x1=_dev(c['x1'], xt), kind=kind,
+                                            k=k, stride=stride, split=split, bias=bias, scratch=scratch, bf16_operands=bf16_operands, **kw)
+    torch.cuda.synchronize()
+    dw = torch.cat([t.cpu() for t in dws], -1)
+    db = None if dbs is None else torch.cat([t.cpu() for t in dbs], -1)
+    return dw, db
+
+
+@pytest.mark.parametrize('x16,dy16', [(False, False), (True, False), (False, True), (True, True)])
+@pytest.mark.parametrize('name', list(WG_CASES))
+def test_wgrad_bf16_tensors_split_bias_slots(name, x16, dy16, slots):
+    c = _wg_case(name)
+    tiny = torch.full((1024,), float('nan'), dtype=F32, device=DEV)        # too small for any launch: falls back to atomics
+    got = {}
+    for label, scr in (('atomics', None), ('slots', slots), ('slots too small', tiny)):
+        what = f'wgrad {name} x16={int(x16)} dy16={int(dy16)} {label}'
+        dw, db = _run_wgrad(name, c, x16, dy16, scr, bias=True)
+        P.assert_exact_products(dw, c['ref'], c['bound'], c['sl'], c['sb'], P._view3, what)
+        # bias sums: exact products with 1 (no prologue on dy), fp32 accumulate: the stated weight-gradient figure
+        P.assert_exact_products(db, c['refb'], P.WGRAD_STATED, what=what + ' db')
+        got[label] = (dw, db)
+    dw2, db2 = _run_wgrad(name, c, x16, dy16, slots, bias=True)
+    assert torch.equal(dw2, got['slots'][0]) and torch.equal(db2, got['slots'][1]), f'{name}: two runs with slots are not bit-identical'
+    r = P.rel(got['slots'][0], got['atomics'][0])
+    print(f'[wgrad {name}] slots vs atomics rel {r:.3e} (bound {c["bound"]:.3e})')
+    assert r < c['bound']
+
+
+@pytest.mark.parametrize('name', ['ragged_20x24', 'ragged_9x17_pro', 'down_128', 'up_128', 'qkv_64_768_ragged', 'rc_128_128_256'])
+def test_wgrad_f32_operands_split_bias_slots(name, slots):
+    """The exact-f32 kernel with the same epilogues (what an f32-mode handle's backward launches): fp32 tensors only."""
+    c = _wg_case(name)
+    pro = c['pro'] is not None
+    # without bf16 rounding inside, the prologue form is held to the figure its fp32-tensor twin states (test_wgrad_concat_and_prologue)
+    bound = 2e-5 if pro else P.WGRAD_STATED
+    ref = c['ref']
+    if pro:
+        stats, gamma, beta, ss = c['pro']
+        B, Fr, H, W, c0, c1, cout, k, stride, kind, _, split = WG_CASES[name]
+        ref = _conv_wgrad_ref(_prologue(c['x0'], gamma, beta, ss, F64), c['dy'].double(), k, stride, kind)
+    for label, scr in (('atomics', None), ('slots', slots)):
+        dw, db = _run_wgrad(name, c, False, False, scr, bias=True, bf16_operands=False)
+        P.assert_exact_products(dw, ref, bound, c['sl'], None, P._view3, f'wgrad f32 {name} {label}')
+        P.assert_exact_products(db, c['refb'], P.WGRAD_STATED, what=f'wgrad f32 {name} {label} db')
+    dw2, db2 = _run_wgrad(name, c, False, False, slots, bias=True, bf16_operands=False)
+    assert torch.equal(dw2, dw) and torch.equal(db2, db)
+
+
+@pytest.mark.parametrize('nslots', [1, 7, 31, 32, 40, 257])
+@pytest.mark.parametrize('E,cout,split', [(1, 0, 0), (15, 0, 0), (17, 0, 0), (1000, 0, 0), (4099, 0, 0), (3 * 768, 768, 256), (5 * 128, 128, 64)])
+def test_slot_sum_fixed_order_pass(nslots, E, cout, split):
+    """Slots filled with a known integer pattern (tests/_parity.py slot_pattern): a dropped slot or a ragged tail is an exact mismatch.
+    nslots >= 32 runs slot_sum16_kernel, fewer slot_sum_kernel; the destination is accumulated into (pre-filled with 5)."""
+    from video_diffusion_nnx_amd import ops
+    stride = E + 5
+    part, exp = P.slot_pattern(nslots, E, stride)
+    nb = cout // split if split else 1
+    dsts = [torch.full((E // nb,), 5.0, dtype=F32, device=DEV) for _ in range(nb)]
+    ops.slot_sum(part.to(DEV), nslots, stride, E, dsts, cout, split)
+    torch.cuda.synchronize()
+    want = P.split_columns(exp, cout, split) if split else [exp]
+    for i in range(nb):
+        assert torch.equal(dsts[i].cpu().double(), want[i].reshape(-1) + 5.0), (nslots, E, split, i)
+
+
+# ---- norm / activation backward ---------------------------------------------------------------------------------------------------
+
+NORM_CASES = [(16, 2, (3, 5, 5), True, False), (64, 2, (4, 8, 8), True, False), (64, 1, (2, 8, 8), False, True),
+              (256, 2, (2, 4, 4), False, True), (512, 1, (2, 2, 2), True, False), (1024, 1, (2, 2, 2), False, True),
+              (24, 1, (2, 3, 3), False, True),
+              (64, 2, (16, 64, 64), True, False), (64, 2, (16, 64, 64), False, True), (128, 2, (16, 32, 32), True, True)]
+# The fp32-tensor twin of the kernel is held to 3e-5 of the fp64 reference (tests/test_gpu_conv_backward.py::test_norm_act_backward).
+# The bf16-tensor form computes the same fp32 values from bf16-representable inputs and rounds dy once, so 3e-5 is the error that may
+# move a value across a bf16 rounding boundary (fp32_floor of assert_bf16_store), and the bound of every fp32 output.
+NORM_FP32 = 3e-5
+
+
+@pytest.mark.parametrize('C,B,shape,use_ss,tail', NORM_CASES)
+def test_norm_act_backward_bf16_tensors(C, B, shape, use_ss, tail):
+    from video_diffusion_nnx_amd import ops
+    g = torch.Generator().manual_seed(C + B + shape[0])
+    mk = lambda *s: torch.randn(*s, generator=g)
+    y32 = P.bf16r(mk(B, *shape, C) * 1.5 + 0.3)
+    gamma32, beta32 = 1 + 0.2 * mk(C), 0.2 * mk(C)
+    ss32 = 0.3 * mk(B, 2 * C) if use_ss else None
+    r32 = P.bf16r(mk(B, *shape, C)) if tail else None
+    lg32, lb32 = (1 + 0.2 * mk(C), 0.1 * mk(C)) if tail else (None, None)
+    dout32 = mk(B, *shape, C)
+
+    def reference(dt):
+        lf = lambda t: None if t is None else t.to(dt).requires_grad_(True)
+        y, gamma, beta, ss, r, lg, lb = map(lf, (y32, gamma32, beta32, ss32, r32, lg32, lb32))
+        h = R.group_norm(y, gamma, beta, 8)
+        if use_ss:
+            h = h * (ss[:, None, None, None, :C] + 1) + ss[:, None, None, None, C:]
+        out = R.silu(h)
+        if tail:
+            out = out + R.layer_norm(r, lg, lb)
+        names = ['dy', 'd_gamma', 'd_beta'] + (['dss'] if use_ss else []) + (['dr', 'd_ln_gamma', 'd_ln_beta'] if tail else [])
+        wrt = [y, gamma, beta] + ([ss] if use_ss else []) + ([r, lg, lb] if tail else [])
+        return dict(zip(names, torch.autograd.grad(out, wrt, dout32.to(dt))))
+
+    ref = reference(F64)
+    cpu32 = reference(F32)
+    print(f'[norm C={C} B={B} {shape}] CPU fp32 evaluation vs fp64: ' + ', '.join(f'{k} {P.rel(cpu32[k], ref[k]):.1e}' for k in ref))
+    stats = P.gn_stats_slab(y32).reshape(-1).to(DEV)
+    runs = {}
+    for det in (False, True):
+        for rep in range(2 if det else 1):
+            res = ops.norm_act_backward_ex(_dev(dout32), _dev(y32, BF), stats, _dev(gamma32), _dev(beta32), 8, scale_shift=_dev(ss32),
+                                           r=_dev(r32, BF), ln_gamma=_dev(lg32), dy_bf16=True, deterministic=det)
+            torch.cuda.synchronize()
+            res = {k: v.cpu() for k, v in res.items() if v is not None}
+            what = f'norm C={C} B={B} {shape} ss={int(use_ss)} tail={int(tail)} dgp={int(det)}'
+            assert res['dy'].dtype == BF
+            P.assert_bf16_store(res['dy'], ref['dy'], NORM_FP32, what + ' dy')
+            for k in ref:
+                if k != 'dy':
+                    rr = P.rel(res[k], ref[k])
+                    print(f'[norm] {what} {k}: rel {rr:.3e} (bound {NORM_FP32:.1e})')
+                    assert rr < NORM_FP32, (what, k, rr)
+            runs[(det, rep)] = res
+    for k in runs[(True, 0)]:
+        assert torch.equal(runs[(True, 0)][k], runs[(True, 1)][k]), f'{k}: two runs with dgp are not bit-identical'
+    # fp32 dy from bf16 y / r (the storage-only combination): the twin's bound, per sample as well
+    res = ops.norm_act_backward_ex(_dev(dout32), _dev(y32, BF), stats, _dev(gamma32), _dev(beta32), 8, scale_shift=_dev(ss32),
+                                   r=_dev(r32, BF), ln_gamma=_dev(lg32), dy_bf16=False, deterministic=True)
+    P.assert_exact_products(res['dy'].cpu(), ref['dy'], NORM_FP32, P.sample_slices(ref['dy'].shape), what=f'norm C={C} {shape} fp32 dy from bf16 y')
+    if tail:
+        P.assert_exact_products(res['dr'].cpu(), ref['dr'], NORM_FP32, P.sample_slices(ref['dr'].shape), what=f'norm C={C} {shape} dr from bf16 r')
+
+
+# ---- attention core / fused temporal attention / SLA core -----------------------------------------------------------------------------
+
+ATTN_CASES = [(1, 16, 4, 4, 8, True), (2, 10, 2, 3, 8, True), (1, 2, 8, 8, 8, False), (1, 3, 5, 5, 4, False),
+              (2, 3, 4, 4, 8, False), (1, 2, 3, 5, 8, False),      # spatial sequences of 16 / 15 tokens: the bf16 core with inner = 1 (a 4 x 4 level)
+              (1, 16, 64, 64, 8, True), (2, 10, 24, 22, 8, True), (1, 10, 5, 7, 8, True)]     # 35 sequences: the last workgroup of 4 is ragged
+SENTINEL = -768.0
+PAD = 64          # extra columns behind dq|dk|dv that the kernels must leave alone
+
+
+def _seqs(t, B, Fr, HW, temporal):
+    t = t.reshape(B, Fr, HW, -1)
+    return t.permute(0, 2, 1, 3) if temporal else t
+
+
+@pytest.mark.parametrize('io16', [True, False])
+@pytest.mark.parametrize('B,Fr,H,W,heads,temporal', ATTN_CASES)
+def test_attention_core_backward_interleaved(B, Fr, H, W, heads, temporal, io16):
+    from video_diffusion_nnx_amd import ops
+    from video_diffusion_nnx_amd._lib import VdxError
+    g = torch.Generator().manual_seed(B + Fr + H)
+    HD, HW, L = heads * 32, H * W, (Fr if temporal else H * W)
+    npix = B * Fr * HW
+    qkv = P.bf16r(torch.randn(npix, 3 * HD, generator=g))
+    d_o = P.bf16r(torch.randn(npix, HD, generator=g))
+    dt = BF if io16 else F32
+    if io16 and L > 16:
+        # bf16 tensors exist for the bf16 MFMA kernel only: rejected, never routed to the fp32 kernel with bf16 pointers
+        with pytest.raises(VdxError):
+            ops.attention_core_backward_io(_dev(qkv, dt), _dev(d_o, dt), B, Fr, H, W, heads, temporal)
+        return
+    o_ref, g_ref = P.attn_core(qkv, d_o, B, Fr, HW, heads, temporal)
+    groups = (B, HW) if temporal else (B, Fr)
+    if L <= 16:
+        # global: the bound the fp32-tensor twin states for the bf16 core; per sequence: 3 x the fp64 emulation of its rounding points
+        o_em, g_em = P.attn_core(qkv, d_o, B, Fr, HW, heads, temporal, emulate=True, round_out=io16)
+        tol = 1.5e-2
+        gb_o = P.group_bound(_seqs(o_em, B, Fr, HW, temporal), _seqs(o_ref, B, Fr, HW, temporal), groups)
+        gb_g = P.group_bound(_seqs(g_em, B, Fr, HW, temporal), _seqs(g_ref, B, Fr, HW, temporal), groups)
+    else:
+        tol = gb_o = gb_g = 2e-5                     # longer sequences run the exact fp32 kernel: the twin's figure, per sequence too
+    for pad in (0, PAD):
+        o, dqkv = ops.attention_core_backward_io(_dev(qkv, dt), _dev(d_o, dt), B, Fr, H, W, heads, temporal, sentinel=SENTINEL, pad_cols=pad)
+        torch.cuda.synchronize()
+        o, dqkv = o.cpu().double(), dqkv.cpu().double()
+        what = f'attn core {(B, Fr, H, W, heads, temporal)} io16={int(io16)} pad={pad}'
+        assert torch.equal(dqkv[:, 3 * HD:], torch.full((npix, pad), SENTINEL, dtype=F64)), what + ': columns behind dq|dk|dv were written'
+        dqkv = dqkv[:, :3 * HD]
+        ro, rg = P.rel(o, o_ref), P.rel(dqkv, g_ref)
+        print(f'[attn] {what}: o rel {ro:.3e}, dqkv rel {rg:.3e} (bound {tol:.1e})')
+        assert ro < tol and rg < tol
+        for nm, a, b in (('dq', 0, HD), ('dk', HD, 2 * HD), ('dv', 2 * HD, 3 * HD)):
+            assert P.rel(dqkv[:, a:b], g_ref[:, a:b]) < tol, (what, nm)
+        P.assert_groups(_seqs(o, B, Fr, HW, temporal), _seqs(o_ref, B, Fr, HW, temporal), groups, gb_o, what + ' o per sequence')
+        P.assert_groups(_seqs(dqkv, B, Fr, HW, temporal), _seqs(g_ref, B, Fr, HW, temporal), groups, gb_g, what + ' dqkv per sequence')
+
+
+@pytest.mark.parametrize('x16', [True, False])
+@pytest.mark.parametrize('B,Fr,H,W', [(1, 16, 4, 4), (2, 5, 3, 3), (1, 16, 16, 16), (1, 16, 64, 64), (2, 10, 24, 22), (1, 10, 5, 7)])
+def test_temporal_attention_backward_fused_bf16_input(B, Fr, H, W, x16):
+    from video_diffusion_nnx_amd import ops
+    g = torch.Generator().manual_seed(100 + B + Fr + H)
+    HW = H * W
+    x = P.bf16r(torch.randn(B, Fr, H, W, 64, generator=g))
+    dy = P.bf16r(torch.randn(B, Fr, H, W, 64, generator=g))
+    wqkv, bqkv = P.bf16r(torch.randn(64, 768, generator=g) * 0.15), torch.randn(768, generator=g) * 0.1
+    wo = P.bf16r(torch.randn(256, 64, generator=g) * 0.1)
+    dx_ref, o_ref, g_ref = P.fused_attention(x, dy, wqkv, bqkv, wo, B, Fr, HW)
+    dx_em, o_em, g_em = P.fused_attention(x, dy, wqkv, bqkv, wo, B, Fr, HW, emulate=True)
+    dyr = dy.double().reshape(-1, 64)
+    sq = lambda t: _seqs(t, B, Fr, HW, True)
+    dx, o, dqkv = ops.temporal_attention_backward_fused_ex(_dev(x, BF if x16 else F32), _dev(dy), _dev(wqkv), _dev(bqkv), _dev(wo))
+    torch.cuda.synchronize()
+    dx, o, dqkv = dx.cpu().double().reshape(-1, 64), o.float().cpu().double(), dqkv.float().cpu().double()
+    what = f'fused attention {(B, Fr, H, W)} x16={int(x16)}'
+    rels = dict(o=P.rel(o, o_ref), dqkv=P.rel(dqkv, g_ref), dx=P.rel(dx, dx_ref), branch=P.rel(dx - dyr, dx_ref - dyr))
+    print(f'[fused] {what}: ' + ', '.join(f'{k} {v:.3e}' for k, v in rels.items()) + ' (bounds 1.5e-2, branch 2.5e-2)')
+    assert rels['o'] < 1.5e-2 and rels['dqkv'] < 1.5e-2 and rels['dx'] < 1.5e-2 and rels['branch'] < 2.5e-2
+    for nm, got, ref, em in (('o', o, o_ref, o_em), ('dqkv', dqkv, g_ref, g_em), ('branch', dx - dyr, dx_ref - dyr, dx_em - dyr)):
+        P.assert_groups(sq(got), sq(ref), (B, HW), P.group_bound(sq(em), sq(ref), (B, HW)), f'{what} {nm} per sequence')
+
+
+@pytest.mark.parametrize('io16', [True, False])
+@pytest.mark.parametrize('NF,H,W', [(2, 8, 8), (3, 5, 7), (1, 20, 20), (2, 64, 64)])      # N = 35: ragged tiles; N = 4096: the level-0 frame
+def test_sla_core_backward_interleaved(NF, H, W, io16):
+    from video_diffusion_nnx_amd import ops
+    g = torch.Generator().manual_seed(NF + H)
+    N = H * W
+    q, k, v = [P.bf16r(2 * torch.randn(NF * N, 256, generator=g)) for _ in range(3)]
+    d_out = P.bf16r(torch.randn(NF * N, 256, generator=g))
+    o_ref, g_ref = P.sla_core(q, k, v, d_out, NF, N)
+    o_em, g_em = P.sla_core(q, k, v, d_out, NF, N, emulate=True, round_out=io16)
+    fh = lambda t: t.reshape(NF, N, -1, 8, 32).permute(0, 3, 1, 2, 4)        # (frame, head) groups
+    dt = BF if io16 else F32
+    for pad in (0, PAD):
+        o, dqkv = ops.sla_core_backward_io(_dev(q, dt), _dev(k, dt), _dev(v, dt), _dev(d_out, dt), NF, N, sentinel=SENTINEL, pad_cols=pad)
+        torch.cuda.synchronize()
+        o, dqkv = o.cpu().double(), dqkv.cpu().double()
+        what = f'sla core NF={NF} N={N} io16={int(io16)} pad={pad}'
+        assert torch.equal(dqkv[:, 768:], torch.full((NF * N, pad), SENTINEL, dtype=F64)), what + ': columns behind dq|dk|dv were written'
+        dqkv = dqkv[:, :768]
+        ro = P.rel(o, o_ref)
+        rg = [P.rel(dqkv[:, a:a + 256], g_ref[:, a:a + 256]) for a in (0, 256, 512)]
+        print(f'[sla] {what}: o rel {ro:.3e} (bound 1e-2), dq/dk/dv rel {rg[0]:.3e} {rg[1]:.3e} {rg[2]:.3e} (bound 2e-2)')
+        assert ro < 1e-2 and max(rg) < 2e-2
+        P.assert_groups(fh(o), fh(o_ref), (NF, 8), P.group_bound(fh(o_em), fh(o_ref), (NF, 8)), what + ' o per (frame, head)')
+        for nm, a in (('dq', 0), ('dk', 256), ('dv', 512)):
+            s = slice(a, a + 256)
+            P.assert_groups(fh(dqkv[:, s]), fh(g_ref[:, s]), (NF, 8), P.group_bound(fh(g_em[:, s]), fh(g_ref[:, s]), (NF, 8)),
+                            f'{what} {nm} per (frame, head)')
+
+
+# ---- data gradient through a row slice of the transposed packing ----------------------------------------------------------------------
+
+
+@pytest.mark.parametrize('mode,dy16', [('f32', False), ('bf16', False), ('bf16', True)])
+@pytest.mark.parametrize('k,B,Fr,H,W,cin,cout', [(3, 1, 16, 64, 64, 128, 64),       # ups level 0 block1 (concat 64 | 64): the persistent 64-channel kernel
+                                                 (1, 1, 16, 16, 16, 512, 256),      # res_conv of a wide level (256 | 256)
+                                                 (3, 1, 3, 9, 17, 48, 40)])         # generic kernel, ragged
+def test_dgrad_row_slice_with_res(mode, dy16, k, B, Fr, H, W, cin, cout):
+    from video_diffusion_nnx_amd import ops
+    g = torch.Generator().manual_seed(k + cin + cout)
+    kern = P.bf16r(torch.randn(1, k, k, cin, cout, generator=g) / (k * k * cout) ** 0.5)
+    dy = P.bf16r(torch.randn(B, Fr, H, W, cout, generator=g))
+    res = P.bf16r(torch.randn(B, Fr, H, W, cin, generator=g))
+
+    def gx_of(dt):
+        x = torch.zeros(B, Fr, H, W, cin, dtype=dt, requires_grad=True)
+        y = R.conv_pointwise(x, kern.to(dt)[0, 0], None) if k == 1 else R.conv_1kk(x, kern.to(dt), None)
+        (gx,) = torch.autograd.grad(y, x, dy.to(dt))
+        return gx + res.to(dt)
+
+    ref, ref32 = gx_of(F64), gx_of(F32)
+    pwt = ops.pack_conv_weights_t(_dev(kern), mode)
+    half = cin // 2
+    for row0 in (0, half):
+        sl = P.sample_slices(ref.shape) + [(f'frame{f}', (slice(None), f)) for f in range(Fr)]
+        r64, r32 = ref[..., row0:row0 + half], ref32[..., row0:row0 + half]
+        bound, sb, floor = P.exact_products_bounds(r32, r64, sl, stated=P.FWD_STATED)
+        got = ops.conv_dgrad_rows(_dev(dy, BF if dy16 else F32), pwt, cin, row0, half, mode=mode, k=k, res=_dev(res[..., row0:row0 + half]))
+        torch.cuda.synchronize()
+        P.assert_exact_products(got.cpu(), r64, bound, sl, sb, what=f'dgrad rows k={k} {cin}->({half}|{half}) row0={row0} {mode} dy16={int(dy16)} (CPU floor {floor:.1e})')
+
+
+# ---- small backward kernels -----------------------------------------------------------------------------------------------------------
+
+FP32_ULP = 2.0 ** -23
+
+
+def _small_bound(ref32, ref64):
+    """fp32 evaluation of the reference formulas against fp64 gives the floor; 4 x margin.  The floor is not taken below one fp32
+    ulp (2^-23): a handful of numbers can come out of the CPU evaluation exactly right, which says nothing about fp32."""
+    return 4.0 * max(P.rel(ref32, ref64), FP32_ULP)
+
+
+def _sum_err(got, ref64, scale):
+    """Error of an output whose elements are long sums, measured against the scale of the sum, ||addends||_2 per element (`scale`),
+    instead of its value: a sum of 131072 signed addends cancels to 1/300 of sum |addends|, and the bias gradient of a 1-channel
+    conv is ONE such number, so an error relative to the value is ill-conditioned."""
+    return ((got.double() - ref64).norm() / scale.norm()).item()
+
+
+def _sum_bound(ref32, ref64, scale, terms):
+    """Bound for _sum_err: 4 x the floor.  Floor = the fp32 CPU evaluation in the same metric, and not below 2^-24 sqrt(terms): adding
+    `terms` addends of rms size s one after another in fp32 commits a rounding error of about 2^-24 |partial sum| per step, partial sums
+    grow like s sqrt(k), so the error's rms is 2^-24 s terms / sqrt 2 against the scale s sqrt(terms).  The CPU's pairwise / blocked
+    order is far below that; the kernels (per-thread runs, then atomics or slots in arrival / slot order) lie in between.  At 131072
+    pixels the bound is 8.6e-5 of the scale; a workgroup dropped from 512 moves the sum by 4.4e-2 of it."""
+    return 4.0 * max(_sum_err(ref32, ref64, scale), 2.0 ** -24 * terms ** 0.5)
+
+
+@pytest.mark.parametrize('x16', [False, True])
+@pytest.mark.parametrize('D,Cout,lead', [(64, 1, (1, 3, 7, 5)), (16, 3, (1, 3, 7, 5)), (32, 2, (1, 3, 7, 5)), (64, 1, (2, 16, 64, 64))])
+def test_final_conv_backward(D, Cout, lead, x16, slots):
+    from video_diffusion_nnx_amd import ops
+    g = torch.Generator().manual_seed(2 + D)
+    x = P.bf16r(torch.randn(*lead, D, generator=g))
+    kern, d_out = torch.randn(1, D, Cout, generator=g), torch.randn(*lead, Cout, generator=g)
+
+    def grads(dt, sq=False):
+        f = (lambda t: t.to(dt) ** 2) if sq else (lambda t: t.to(dt))
+        xx, kk, bb = f(x).requires_grad_(True), kern.to(dt).requires_grad_(True), torch.zeros(Cout, dtype=dt, requires_grad=True)
+        return torch.autograd.grad(R.conv_pointwise(xx, kk, bb), (xx, kk, bb), f(d_out))
+
+    ref, ref32 = grads(F64), grads(F32)
+    npix = x.numel() // D
+    scale = [None] + [t.sqrt() for t in grads(F64, sq=True)[1:]]          # dw, db: sums over the pixels; sqrt(sum of addends^2) per element
+    bounds = [_small_bound(ref32[0], ref[0])] + [_sum_bound(ref32[i], ref[i], scale[i], npix) for i in (1, 2)]
+    outs = {}
+    for label, scr in (('atomics', None), ('slots', slots), ('slots again', slots)):
+        slots.fill_(float('nan'))
+        dx, dw, db = ops.final_conv_backward(_dev(x, BF if x16 else F32), _dev(d_out), _dev(kern), scratch=scr)
+        torch.cuda.synchronize()
+        outs[label] = got = (dx.cpu(), dw.cpu().reshape(1, D, Cout), db.cpu())
+        for nm, a, b, bd, sc in zip(('dx', 'dw', 'db'), got, ref, bounds, scale):
+            rr = P.rel(a, b) if sc is None else _sum_err(a, b, sc)
+            print(f'[final_conv D={D} Cout={Cout} {lead} x16={int(x16)} {label}] {nm}: rel {rr:.3e} (bound {bd:.3e})')
+            assert rr < bd, (nm, rr, bd)
+    assert all(torch.equal(a, b) for a, b in zip(outs['slots'], outs['slots again'])), 'two runs with slots are not bit-identical'
+
+
+@pytest.mark.parametrize('Cin,D,k', [(1, 64, 7), (3, 16, 7), (3, 40, 3)])
+def test_init_conv_backward_weights(Cin, D, k, slots):
+    from video_diffusion_nnx_amd import ops
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(2, Cin, 3, 20, 12, generator=g)
+    dy = torch.randn(2, 3, 20, 12, D, generator=g)
+
+    def grads(dt, sq=False):
+        f = (lambda t: t.to(dt) ** 2) if sq else (lambda t: t.to(dt))
+        kern, bias = torch.zeros(1, k, k, Cin, D, dtype=dt, requires_grad=True), torch.zeros(D, dtype=dt, requires_grad=True)
+        return torch.autograd.grad(R.conv_1kk(f(x).permute(0, 2, 3, 4, 1), kern, bias), (kern, bias), f(dy))
+
+    ref, ref32 = grads(F64), grads(F32)
+    scale = [t.sqrt() for t in grads(F64, sq=True)]                      # sums over the pixels: sqrt(sum of addends^2) per element
+    bounds = [_sum_bound(a, b, sc, dy.numel() // D) for a, b, sc in zip(ref32, ref, scale)]
+    outs = {}
+    for label, scr in (('atomics', None), ('slots', slots), ('slots again', slots)):
+        slots.fill_(float('nan'))
+        outs[label] = got = tuple(t.cpu() for t in ops.init_conv_backward_weights(_dev(x), _dev(dy), k, scratch=scr))
+        for nm, a, b, bd, sc in zip(('dw', 'db'), got, ref, bounds, scale):
+            rr = _sum_err(a, b, sc)
+            print(f'[init_conv Cin={Cin} D={D} k={k} {label}] {nm}: rel {rr:.3e} (bound {bd:.3e})')
+            assert rr < bd, (nm, rr, bd)
+    assert all(torch.equal(a, b) for a, b in zip(outs['slots'], outs['slots again'])), 'two runs with slots are not bit-identical'
+
+
+@pytest.mark.parametrize('dim,cond_dim', [(64, 0), (16, 32), (32, 768)])
+def test_time_mlp_backward(dim, cond_dim):
+    from video_diffusion_nnx_amd import ops
+    g = torch.Generator().manual_seed(3)
+    B = 5
+    t = torch.tensor([0, 1, 437, 998, 999])
+    w1, b1 = torch.randn(dim, 4 * dim, generator=g) / dim ** 0.5, torch.randn(4 * dim, generator=g) * 0.1
+    w2, b2 = torch.randn(4 * dim, 4 * dim, generator=g) / (4 * dim) ** 0.5, torch.randn(4 * dim, generator=g) * 0.1
+    cond = torch.randn(B, cond_dim, generator=g) if cond_dim else None
+    null = torch.randn(1, cond_dim, generator=g) if cond_dim else None
+    mask = torch.tensor([0, 1, 0, 1, 1], dtype=torch.bool) if cond_dim else None
+    dtemb = torch.randn(B, 4 * dim + cond_dim, generator=g)
+
+    def grads(dt):
+        ps = [p.to(dt).requires_grad_(True) for p in (w1, b1, w2, b2)] + ([null.to(dt).requires_grad_(True)] if cond_dim else [])
+        e = R.sinusoidal_pos_emb(t, dim, dt)
+        out = R.gelu_tanh(e @ ps[0] + ps[1]) @ ps[2] + ps[3]
+        if cond_dim:
+            out = torch.cat((out, torch.where(mask[:, None], ps[4], cond.to(dt))), -1)
+        return torch.autograd.grad(out, ps, dtemb.to(dt))
+
+    # the fp32 evaluation carries the fp32 sin/cos of arguments up to ~1e3 rad, as the kernel's recompute does (tests/test_gpu_blocks.py
+    # test_time_mlp holds the forward to 2e-4 for the same reason)
+    ref, ref32 = grads(F64), grads(F32)
+    got = ops.time_mlp_backward(t.to(DEV), _dev(w1), _dev(b1), _dev(w2), _dev(b2), _dev(dtemb), cond_dim=cond_dim,
+                                cond_mask=None if mask is None else mask.to(DEV))
+    torch.cuda.synchronize()
+    for nm, a, b, b32 in zip(('dw1', 'db1', 'dw2', 'db2', 'dnull'), got, ref, ref32):
+        bd, rr = _small_bound(b32, b), P.rel(a.cpu().reshape(b.shape), b)
+        print(f'[time_mlp dim={dim} cond={cond_dim}] {nm}: rel {rr:.3e} (bound {bd:.3e})')
+        assert rr < bd, (nm, rr, bd)
+    assert (got[4] is None) == (cond_dim == 0)
+
+
+# ---- optimizer and loss gradient -----------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize('do_ema', [True, False])
+@pytest.mark.parametrize('grad_scale', [1.0, 0.5])
+@pytest.mark.parametrize('n', [1, 1023, 1000003])
+def test_adam_ema_six_steps(n, grad_scale, do_ema):
+    """6 consecutive steps from non-zero moments against oracle/train_ref.py in fp64: p, the update p - p0, m, v and ema.  The ABI takes
+    the hyper-parameters as floats, so the reference gets the same float32-representable values (1 - b in fp32 is then exact)."""
+    from video_diffusion_nnx_amd import ops
+    f = lambda v: torch.tensor(v, dtype=F32).item()
+    lr, b1, b2, eps, decay = f(1e-4), f(0.9), f(0.999), f(1e-8), f(0.995)
+    g = torch.Generator().manual_seed(n)
+    p0, m0 = torch.randn(n, generator=g), 0.1 * torch.randn(n, generator=g)
+    v0 = 0.01 * torch.rand(n, generator=g) + 1e-6
+    e0 = p0 + 0.01 * torch.randn(n, generator=g)
+    gs = [torch.randn(n, generator=g) * (0.1 + 0.05 * s) for s in range(6)]
+
+    def run(dt):
+        p, m, v, e = ({'w': t.to(dt)} for t in (p0, m0, v0, e0))
+        for s in range(6):
+            p, m, v = TR.adam_update(p, {'w': gs[s].to(dt) * grad_scale}, m, v, 10 + s, lr, b1, b2, eps)
+            if do_ema:
+                e = TR.ema_update(e, p, 1, 0, 1, decay)
+        return dict(p=p['w'], dp=p['w'] - p0.to(dt), m=m['w'], v=v['w'], ema=e['w'])
+
+    ref, ref32 = run(F64), run(F32)
+    p, m, v, e = (_dev(t).clone() for t in (p0, m0, v0, e0))
+    for s in range(6):
+        ops.adam_ema_step(p, _dev(gs[s]), m, v, e if do_ema else None, lr=lr, b1=b1, b2=b2, eps=eps, step_count=10 + s, grad_scale=grad_scale,
+                          do_ema=do_ema, ema_decay=decay)
+    torch.cuda.synchronize()
+    got = dict(p=p.cpu(), dp=p.cpu().double() - p0.double(), m=m.cpu(), v=v.cpu(), ema=e.cpu())
+    for k in ref:
+        bd, rr = _small_bound(ref32[k], ref[k]), P.rel(got[k], ref[k])
+        print(f'[adam n={n} scale={grad_scale} ema={int(do_ema)}] {k}: rel {rr:.3e} (bound {bd:.3e})')
+        assert rr < bd, (k, rr, bd)
+    if not do_ema:
+        assert torch.equal(got['ema'], e0), 'ema touched with do_ema = 0'
+
+
+@pytest.mark.parametrize('l2', [0, 1])
+@pytest.mark.parametrize('B,Cc,Fr,H,W', [(2, 3, 4, 8, 8), (1, 1, 3, 5, 7)])
+def test_loss_grad(B, Cc, Fr, H, W, l2):
+    """d(mean loss)/d(eps_hat) against autograd of the oracle loss (oracle/diffusion_ref.py: mean |.| or mean (.)^2), with elements
+    where eps_hat == noise exactly.  There the l1 gradient is 0: jnp.abs differentiates to sign(x) with sign(0) = 0 in the reference
+    project's loss (gaussian_diffusion.py:464), and torch.abs does the same, so autograd states the expected value."""
+    from video_diffusion_nnx_amd import ops
+    g = torch.Generator().manual_seed(B + Cc)
+    noise = torch.randn(B, Cc, Fr, H, W, generator=g)
+    eps_hat = torch.randn(B, Fr, H, W, Cc, generator=g)
+    tie = torch.rand(B, Fr, H, W, Cc, generator=g) < 0.1
+    eps_hat = torch.where(tie, noise.permute(0, 2, 3, 4, 1), eps_hat).contiguous()
+
+    def grad(dt):
+        e = eps_hat.to(dt).requires_grad_(True)
+        d = e.permute(0, 4, 1, 2, 3) - noise.to(dt)
+        loss = (d * d).mean() if l2 else d.abs().mean()
+        return torch.autograd.grad(loss, e)[0]
+
+    ref, ref32 = grad(F64), grad(F32)
+    got = ops.loss_grad(_dev(eps_hat), _dev(noise), l2).cpu()
+    bd, rr = _small_bound(ref32, ref), P.rel(got, ref)
+    print(f'[loss_grad l2={l2} {(B, Cc, Fr, H, W)}] rel {rr:.3e} (bound {bd:.3e}); {int(tie.sum())} exact ties')
+    assert rr < bd
+    assert (got[tie] == 0).all(), 'gradient at eps_hat == noise must be 0 (sign(0) = 0, as jnp.abs / the squared error give)'
+
+
+# ---- invalid combinations never launch ------------------------------------------------------------------------------------------------
+
+
+def test_backward_form_entry_points_reject_invalid_combinations():
+    from video_diffusion_nnx_amd import ops
+    from video_diffusion_nnx_amd._lib import VdxError
+    z = lambda *s, dt=F32: torch.zeros(*s, dtype=dt, device=DEV)
+    x, dy = z(1, 2, 8, 8, 64), z(1, 2, 8, 8, 768)
+    with pytest.raises(VdxError):      # bf16 tensors without bf16 operands
+        ops.conv_backward_weights_ex(x.to(BF), dy, (1, 1, 1, 64, 768), k=1, bf16_operands=False)
+    with pytest.raises(VdxError):      # bf16 input with a channel count that is not a multiple of 8
+        ops.conv_backward_weights_ex(z(1, 2, 8, 8, 12, dt=BF), z(1, 2, 8, 8, 16), (1, 3, 3, 12, 16))
+    with pytest.raises(VdxError):      # split that does not divide cout into whole 64-wide tiles
+        ops.conv_backward_weights_ex(x, z(1, 2, 8, 8, 96), (1, 1, 1, 64, 96), k=1, split=32)
+    with pytest.raises(VdxError):      # a form the network never launches: 3x3 at stride 2
+        ops.conv_backward_weights_ex(x, z(1, 2, 4, 4, 64), (1, 3, 3, 64, 64), k=3, stride=2)
+    with pytest.raises(VdxError):      # the prologue belongs to the 3x3 form
+        ops.conv_backward_weights_ex(x, z(1, 2, 8, 8, 64), (1, 1, 1, 64, 64), k=1, in_stats=torch.zeros(32 * 8 * 2, dtype=F64, device=DEV),
+                                     gamma=z(64), beta=z(64))
+    with pytest.raises(VdxError):      # slot pass: split that does not divide cout
+        ops.slot_sum(z(64), 2, 32, 30, [z(30)], cout=30, split=7)
+    with pytest.raises(VdxError):      # slots narrower than the elements summed
+        ops.slot_sum(z(64), 2, 16, 32, [z(32)])
+    y = z(1, 2, 4, 4, 16)
+    with pytest.raises(VdxError):      # groups must divide the channels
+        ops.norm_act_backward_ex(y, y.to(BF), torch.zeros(32 * 5 * 2, dtype=F64, device=DEV), z(16), z(16), groups=5)
+    with pytest.raises(VdxError):      # interleaved bf16 tensors without the bf16 MFMA core
+        ops.attention_core_backward_io(z(32, 768, dt=BF), z(32, 256, dt=BF), 1, 2, 4, 4, 8, True, bf16_operands=False)
+    with pytest.raises(VdxError):      # more than 16 frames
+        ops.temporal_attention_backward_fused_ex(z(1, 17, 2, 2, 64, dt=BF), z(1, 17, 2, 2, 64), z(64, 768), z(768), z(256, 64))
+    with pytest.raises(VdxError):      # bf16 SLA tensors without bf16 operands
+        ops.sla_core_backward_io(*[z(16, 256, dt=BF)] * 4, 1, 16, bf16_operands=False)
+    with pytest.raises(VdxError):      # row slice outside the packing
+        ops.conv_dgrad_rows(z(1, 2, 8, 8, 64), ops.pack_conv_weights_t(z(1, 3, 3, 128, 64), 'f32'), 128, 96, 64, mode='f32')
+    with pytest.raises(VdxError):      # final conv: more than 4 output channels
+        ops.final_conv_backward(z(1, 2, 4, 4, 64), z(1, 2, 4, 4, 5), z(1, 64, 5))
+    with pytest.raises(VdxError):      # init conv: even kernel
+        ops.init_conv_backward_weights(z(1, 1, 2, 8, 8), z(1, 2, 8, 8, 16), 4)
+    with pytest.raises(VdxError):      # time MLP: dim not a multiple of 4
+        ops.time_mlp_backward(torch.zeros(2, dtype=torch.int32, device=DEV), z(6, 24), z(24), z(24, 24), z(24), z(2, 24))

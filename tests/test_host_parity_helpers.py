@@ -1,0 +1,193 @@
+"""The comparison helpers of tests/_parity.py bite: CPU tensors only.
+
+Each test builds an fp64 reference and the clean fp32 CPU evaluation of the same operation, derives the bound exactly as
+tests/test_gpu_backward_forms.py does (from the reference side), checks that the clean evaluation passes, and then hands the helper
+a "kernel output" with one subtle, localized fault -- the class of fault the whole-network gradient tests (rel-L2 2.5e-2 .. 7e-2,
+five times that per tensor) cannot see.  The helper must reject every one of them."""
+import pytest
+import torch
+
+import _parity as P
+from oracle import unet3d_ref as R
+
+
+def _wgrad(x, dy, k=3):
+    """Weight gradient of a (1,k,k) SAME conv through the oracle, in the dtype of x."""
+    kern = torch.zeros(1, k, k, x.shape[-1], dy.shape[-1], dtype=x.dtype, requires_grad=True)
+    y = R.conv_1kk(x, kern, None)
+    (g,) = torch.autograd.grad(y, kern, dy)
+    return g
+
+
+@pytest.fixture(scope='module')
+def nshape_wgrad():
+    """conv2 of a level-0 block at the north-star shape: 64 -> 64, 16 frames of 64 x 64, B = 2; bf16-representable operands."""
+    g = torch.Generator().manual_seed(11)
+    x = P.bf16r(torch.randn(2, 16, 64, 64, 64, generator=g))
+    dy = P.bf16r(torch.randn(2, 16, 64, 64, 64, generator=g))
+    ref64 = _wgrad(x.double(), dy.double())
+    ref32 = _wgrad(x, dy)
+    return x, dy, ref64, ref32
+
+
+def test_dropped_boundary_row_of_one_patch_is_rejected(nshape_wgrad):
+    x, dy, ref64, ref32 = nshape_wgrad
+    sl = P.wgrad_slices(ref64.shape)
+    bound, sb, floor = P.exact_products_bounds(ref32, ref64, sl, P._view3)
+    print(f'N-shape wgrad: CPU fp32 floor {floor:.3e}, bound {bound:.3e}')
+    P.assert_exact_products(ref32, ref64, bound, sl, sb, P._view3, 'clean fp32 evaluation')
+    # an 8 x 16 patch of frame 5 of sample 1 (rows 24..31, columns 32..47) loses the halo row below it: the three taps that look one
+    # row down (ky = 2) miss the contribution of the patch's last row -- 16 of the 131072 positions of each weight element
+    b, f, y, x0 = 1, 5, 31, 32
+    got = ref32.clone()
+    for kx in range(3):
+        xs = x[b, f, y + 1, x0 + kx - 1:x0 + kx - 1 + 16, :]           # input pixels under tap (2, kx) of output row y
+        got[0, 2, kx] -= xs.t() @ dy[b, f, y, x0:x0 + 16, :]
+    whole = P.rel(got, ref64)
+    assert whole < 2.5e-2, 'the fault must be one the whole-network bound cannot see'
+    with pytest.raises(AssertionError):
+        P.assert_exact_products(got, ref64, bound, sl, sb, P._view3, 'dropped boundary row')
+    # and a single slice (tap 8) is enough to trip the per-slice check even where a generous global bound would not
+    with pytest.raises(AssertionError, match='slice'):
+        P.assert_exact_products(got, ref64, 1.0, sl, sb, P._view3, 'dropped boundary row, per-slice only')
+
+
+def test_omitted_last_slot_and_swapped_split_blocks_are_rejected():
+    # the q|k|v weight gradient (64 -> 768, split 256) as 40 per-workgroup slots added in a fixed order
+    g = torch.Generator().manual_seed(12)
+    rows, nslots = 40 * 64, 40
+    x = P.bf16r(torch.randn(rows, 64, generator=g))
+    dy = P.bf16r(torch.randn(rows, 768, generator=g))
+    ref64 = x.double().t() @ dy.double()
+    slots = torch.stack([x[k * 64:(k + 1) * 64].t() @ dy[k * 64:(k + 1) * 64] for k in range(nslots)])      # fp32 partial tiles
+    clean = torch.zeros(64, 768)
+    for k in range(nslots):
+        clean += slots[k]
+    sl = P.wgrad_slices(ref64.shape)
+    bound, sb, floor = P.exact_products_bounds(x.t() @ dy, ref64, sl, P._view3)
+    P.assert_exact_products(clean, ref64, bound, sl, sb, P._view3, 'clean slot sum')
+    with pytest.raises(AssertionError):
+        P.assert_exact_products(clean - slots[-1], ref64, bound, sl, sb, P._view3, 'last of 40 slots omitted')
+    # the exact-integer form the GPU test of the slot pass uses
+    part, exp = P.slot_pattern(40, 1000, 1003)
+    s = part.reshape(40, 1003)[:, :1000].double()
+    assert torch.equal(s.sum(0), exp)
+    assert not torch.equal(s[:-1].sum(0), exp)                              # dropped slot
+    assert not torch.equal(torch.cat((s.sum(0)[:-1], s.sum(0)[:1])), exp)  # ragged tail: last element wrong
+    # split epilogue that misplaces a column block of 4 channels: columns 4..7 and 8..11 of dWk swapped
+    blocks = P.split_columns(clean.reshape(-1), 768, 256)
+    refb = P.split_columns(ref64.reshape(-1), 768, 256)
+    bad = blocks[1].clone()
+    bad[:, 4:8], bad[:, 8:12] = blocks[1][:, 8:12], blocks[1][:, 4:8]
+    slb = P.wgrad_slices(refb[1].shape)
+    P.assert_exact_products(blocks[1], refb[1], bound, slb, None, P._view3, 'clean dWk')
+    assert P.rel(torch.cat([blocks[0], bad, blocks[2]], 1), ref64) < 0.35, 'the fault must be one the per-tensor whole-network bound cannot see'
+    with pytest.raises(AssertionError):
+        P.assert_exact_products(bad, refb[1], bound, slb, None, P._view3, 'swapped 4-channel column blocks')
+
+
+def test_truncation_instead_of_rounding_is_rejected():
+    # dL/dy of the block prologue act = SiLU(GroupNorm(y) * (1 + s) + sh), stored as bf16
+    g = torch.Generator().manual_seed(13)
+    C, B = 64, 2
+    y = P.bf16r(torch.randn(B, 4, 16, 16, C, generator=g) * 1.5 + 0.3)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.2 * torch.randn(C, generator=g)
+    ss = 0.3 * torch.randn(B, 2 * C, generator=g)
+    dact = torch.randn(y.shape, generator=g)
+
+    def dy_of(dt):
+        yy = y.to(dt).requires_grad_(True)
+        h = R.group_norm(yy, gamma.to(dt), beta.to(dt), 8) * (ss.to(dt)[:, None, None, None, :C] + 1) + ss.to(dt)[:, None, None, None, C:]
+        (gy,) = torch.autograd.grad(R.silu(h), yy, dact.to(dt))
+        return gy
+
+    ref64, ref32 = dy_of(torch.float64), dy_of(torch.float32)
+    floor = 3e-5          # what tests/test_gpu_backward_forms.py passes: the bound the fp32-tensor twin of the kernel is held to
+    P.assert_bf16_store(ref32.to(torch.bfloat16), ref64, floor, 'clean fp32 evaluation, rounded once')
+    trunc = P.bf16_trunc(ref32).to(torch.bfloat16)
+    # truncation stays within one ulp (+ floor) of bf16(ref) everywhere: the per-element check runs first and passes, only the cap sees it
+    with pytest.raises(AssertionError, match='differ'):
+        P.assert_bf16_store(trunc, ref64, floor, 'truncated')
+    # rounding twice (through fp16-like 11 bits, then 8): also within one ulp, also over the cap
+    m, e = torch.frexp(ref32.double())
+    twice = torch.ldexp(torch.round(m * 2 ** 9) / 2 ** 9, e).float().to(torch.bfloat16)
+    with pytest.raises(AssertionError):
+        P.assert_bf16_store(twice, ref64, floor, 'rounded twice')
+    # an element two ulps off is rejected however few there are
+    off = ref32.to(torch.bfloat16).clone()
+    off.view(-1)[7] = (off.view(-1)[7].double() + 2.5 * P.bf16_ulp(off.view(-1)[7].double())).to(torch.bfloat16)
+    with pytest.raises(AssertionError, match='ulp'):
+        P.assert_bf16_store(off, ref64, floor, 'one element 2.5 ulp off')
+
+
+def test_one_zeroed_attention_sequence_of_4096_is_rejected():
+    # temporal attention at level 0 of the north-star shape: 64 x 64 sequences of 16 frames, 8 heads
+    g = torch.Generator().manual_seed(14)
+    B, Fr, HW, heads = 1, 16, 4096, 8
+    qkv = P.bf16r(torch.randn(B * Fr * HW, 3 * heads * 32, generator=g))
+    d_o = P.bf16r(torch.randn(B * Fr * HW, heads * 32, generator=g))
+    o64, g64 = P.attn_core(qkv, d_o, B, Fr, HW, heads, True)
+    oe, ge = P.attn_core(qkv, d_o, B, Fr, HW, heads, True, emulate=True, round_out=True)
+    seqs = lambda t: t.reshape(B, Fr, HW, -1).permute(0, 2, 1, 3)
+    bound = P.group_bound(seqs(ge), seqs(g64), (B, HW))
+    print(f'per-sequence bound {bound:.3e}')
+    assert bound < 2e-2, 'the emulated bf16 roundings should cost well under the global 1.5e-2 per sequence'
+    _, clean = P.attn_core(qkv, d_o, B, Fr, HW, heads, True, emulate=True, round_out=True, dtype=torch.float32)
+    assert P.rel(clean, g64) < 1.5e-2
+    P.assert_groups(seqs(clean), seqs(g64), (B, HW), bound, 'clean fp32 evaluation')
+    bad = clean.clone().reshape(B, Fr, HW, -1)
+    bad[:, :, 1234, :] = 0                                                  # one sequence never written
+    bad = bad.reshape(clean.shape)
+    assert P.rel(bad, g64) < 2.5e-2, 'the fault must be one the whole-network bound cannot see'
+    with pytest.raises(AssertionError, match='group'):
+        P.assert_groups(seqs(bad), seqs(g64), (B, HW), bound, 'one sequence zeroed')
+
+
+def test_closed_forms_match_autograd():
+    """The fp64 closed forms that serve as references for the attention cores are autodiff of the oracle's forward."""
+    g = torch.Generator().manual_seed(15)
+    D = torch.float64
+    for B, Fr, H, W, heads, temporal in [(2, 5, 2, 3, 8, True), (1, 2, 3, 3, 4, False)]:
+        HD, npix = heads * 32, B * Fr * H * W
+        qkv = torch.randn(npix, 3 * HD, generator=g, dtype=D).requires_grad_(True)
+        d_o = torch.randn(npix, HD, generator=g, dtype=D)
+        x = qkv.reshape(B, Fr, H * W, 3, heads, 32)
+        seq = x.permute(0, 2, 1, 3, 4, 5) if temporal else x
+        q, k, v = seq[..., 0, :, :] / 32 ** 0.5, seq[..., 1, :, :], seq[..., 2, :, :]
+        o = torch.einsum('...hij,...jhd->...ihd', torch.softmax(torch.einsum('...ihd,...jhd->...hij', q, k), -1), v)
+        o_rows = (o.permute(0, 2, 1, 3, 4) if temporal else o).reshape(npix, HD)
+        (gq,) = torch.autograd.grad(o_rows, qkv, d_o)
+        o2, g2 = P.attn_core(qkv.detach(), d_o, B, Fr, H * W, heads, temporal)
+        assert P.rel(o2, o_rows.detach()) < 1e-12 and P.rel(g2, gq) < 1e-12
+    NF, N = 2, 35
+    q, k, v = [(2 * torch.randn(NF * N, 256, generator=g, dtype=D)).requires_grad_(True) for _ in range(3)]
+    d_out = torch.randn(NF * N, 256, generator=g, dtype=D)
+    hs = lambda t: t.reshape(NF, N, 8, 32).permute(0, 2, 3, 1)
+    ctx = torch.einsum('bhdn,bhen->bhde', torch.softmax(hs(k), -1), hs(v))
+    out = torch.einsum('bhde,bhdn->bhen', ctx, torch.softmax(hs(q), -2)).permute(0, 3, 1, 2).reshape(NF * N, 256)
+    gq, gk, gv = torch.autograd.grad(out, (q, k, v), d_out)
+    o2, g2 = P.sla_core(q.detach(), k.detach(), v.detach(), d_out, NF, N)
+    assert P.rel(o2, out.detach()) < 1e-12 and P.rel(g2, torch.cat((gq, gk, gv), -1)) < 1e-12
+    # fused temporal attention block
+    B, Fr, HW = 1, 5, 6
+    x = torch.randn(B, Fr, HW, 64, generator=g, dtype=D).requires_grad_(True)
+    dy = torch.randn(B, Fr, HW, 64, generator=g, dtype=D)
+    wqkv, bqkv, wo = torch.randn(64, 768, generator=g, dtype=D) * 0.15, torch.randn(768, generator=g, dtype=D) * 0.1, torch.randn(256, 64, generator=g, dtype=D) * 0.1
+    s = (x.reshape(-1, 64) @ wqkv + bqkv).reshape(B, Fr, HW, 3, 8, 32).permute(0, 2, 1, 3, 4, 5)
+    q, k, v = s[..., 0, :, :] / 32 ** 0.5, s[..., 1, :, :], s[..., 2, :, :]
+    o = torch.einsum('...hij,...jhd->...ihd', torch.softmax(torch.einsum('...ihd,...jhd->...hij', q, k), -1), v).permute(0, 2, 1, 3, 4).reshape(-1, 256)
+    y = (o @ wo).reshape(x.shape) + x
+    (gx,) = torch.autograd.grad(y, x, dy)
+    dx, o2, _ = P.fused_attention(x.detach(), dy, wqkv, bqkv, wo, B, Fr, HW)
+    assert P.rel(dx, gx.reshape(-1, 64)) < 1e-12 and P.rel(o2, o.detach()) < 1e-12
+
+
+def test_helper_primitives():
+    t = torch.tensor([1.0, 1.00390625, 3.0, -0.75, 0.0], dtype=torch.float64)
+    assert torch.equal(P.bf16_ulp(t), torch.tensor([2.0 ** -7, 2.0 ** -7, 2.0 ** -6, 2.0 ** -8, 0.0], dtype=torch.float64))
+    assert torch.equal(P.bf16r(torch.tensor([1.00390625])), torch.tensor([1.0]))            # tie to even
+    assert torch.equal(P.bf16_trunc(torch.tensor([1.0078124])), torch.tensor([1.0]))
+    w, i, allr = P.per_group_rel(torch.tensor([[1.0, 1.0], [2.0, 0.0]]), torch.tensor([[1.0, 1.0], [2.0, 2.0]]), (2,))
+    assert i == 1 and abs(w - 0.5 ** 0.5) < 1e-12 and allr.shape == (2,)
+    with pytest.raises(AssertionError):
+        P.exact_products_bounds(torch.tensor([1.0, 1.001]), torch.tensor([1.0, 1.0], dtype=torch.float64))      # floor too high to mean anything

@@ -91,7 +91,7 @@ void vdx_set_launch_hook(vdx_launch_hook hook, void* user) { vdx::g_launch_hook 
 
 size_t vdx_gn_stats_bytes(int batch, int groups) { return (size_t)batch * 32 /*GN_SLOTS*/ * groups * 2 * sizeof(double); }
 
-int vdx_conv_forward(int mode, const vdx_conv_desc* d, void* stream) {
+static int conv_forward_rows(int mode, const vdx_conv_desc* d, int w_rows, int w_row0, void* stream) {
     if (!d || !d->x0 || !d->packed_w || !d->y) VDX_FAIL(VDX_ERR_INVALID, "conv: null tensor");
     if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
     if (d->c0 % 4 || d->c1 % 4 || d->cout % 4) VDX_FAIL(VDX_ERR_INVALID, "conv: channel counts must be multiples of 4");
@@ -132,8 +132,18 @@ int vdx_conv_forward(int mode, const vdx_conv_desc* d, void* stream) {
         if (d->res_bf16 && mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "conv: bf16 tensors need VDX_MODE_BF16");
         a.res = (const float*)d->res; a.res_bf16 = d->res_bf16 ? 1 : 0;
     }
+    a.wrows = w_rows; a.wrow0 = w_row0;                    // (0, 0 = cout rows from 0)
     VDX_HIP(vdx::launch_conv(mode, a, (hipStream_t)stream));
     return VDX_OK;
+}
+
+int vdx_conv_forward(int mode, const vdx_conv_desc* d, void* stream) { return conv_forward_rows(mode, d, 0, 0, stream); }
+
+int vdx_conv_forward_rows(int mode, const vdx_conv_desc* d, int w_rows, int w_row0, void* stream) {
+    if (!d) VDX_FAIL(VDX_ERR_INVALID, "conv: null tensor");
+    if (w_rows < 1 || w_row0 < 0 || w_row0 + d->cout > w_rows) VDX_FAIL(VDX_ERR_INVALID, "conv_forward_rows: rows [w_row0, w_row0 + cout) must lie inside the w_rows packed rows");
+    if (w_rows % 4 || w_row0 % 4) VDX_FAIL(VDX_ERR_INVALID, "conv_forward_rows: w_rows and w_row0 must be multiples of 4");
+    return conv_forward_rows(mode, d, w_rows, w_row0, stream);
 }
 
 int vdx_resblock_tail(const float* y2, const float* r, float* out, const double* stats, const float* gn_gamma,
@@ -766,6 +776,175 @@ int vdx_sla_core_backward_ex(const float* q, const float* k, const float* v, con
 int vdx_colsum(const float* x, float* out, long rows, int c, void* stream) {
     if (!x || !out || rows < 0 || c < 1 || c % 4) VDX_FAIL(VDX_ERR_INVALID, "colsum: bad argument");
     if (rows) VDX_HIP(vdx::launch_colsum(x, out, rows, c, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+// ---- test-facing entry points for the forms only vdx_unet_backward sets on the launchers (vdx.h: "Backward forms of the network") ----
+
+int vdx_conv_backward_weights_ex(const vdx_wgrad_ex_desc* d, void* stream) {
+    if (!d || !d->x0 || !d->dy || !d->dw) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: null tensor");
+    if (d->c0 < 4 || d->c0 % 4 || d->c1 < 0 || d->c1 % 4 || d->cout < 4 || d->cout % 4 || (d->c1 && !d->x1)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bad channels");
+    if (d->batch < 1 || d->frames < 1 || d->h < 1 || d->w < 1) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bad geometry");
+    if (d->kind != 0 && d->kind != 1) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bad kind");
+    // only the forms model_bwd.hip launches: 1x1 and 3x3 at stride 1, Downsample 4x4 at stride 2, Upsample (kind 1)
+    if (d->kind == 0) {
+        const bool s1 = d->stride == 1 && d->kh == d->kw && (d->kh == 1 || d->kh == 3);
+        const bool s2 = d->stride == 2 && d->kh == 4 && d->kw == 4;
+        if (!s1 && !s2) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: kernel/stride must be 1x1 or 3x3 at stride 1, or 4x4 at stride 2");
+        if (s2 && (d->h % 2 || d->w % 2)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: stride 2 needs even H, W");
+    }
+    if (d->in_stats && (d->kind != 0 || d->kh != 3 || d->stride != 1 || d->split)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: the prologue form is the 3x3 stride-1 conv without split");
+    if (d->split && (d->kind != 0 || d->kh != 1)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: split is the 1x1 (q|k|v projection) form");
+    if ((d->x_bf16 || d->dy_bf16) && !d->bf16_operands) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bf16 tensors need bf16_operands (the exact-f32 kernel reads fp32 tensors only)");
+    if (d->x_bf16 && (d->c0 % 8 || d->c1 % 8)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bf16 inputs need channel counts that are multiples of 8");
+    if (d->dy_bf16 && d->cout % 8) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: a bf16 dy needs cout a multiple of 8");
+    if (d->split) {
+        // a 64-wide output tile never straddles two tensors (wgrad.hip); at most three targets
+        if (d->split < 0 || d->split % 64 || d->cout % d->split || d->cout / d->split > 3) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: split must be a multiple of 64 that divides cout into at most 3 blocks");
+        const int nb = d->cout / d->split;
+        if ((nb >= 2 && !d->dw1) || (nb >= 3 && !d->dw2)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: split needs dw1 / dw2");
+        if (d->db && ((nb >= 2 && !d->db1) || (nb >= 3 && !d->db2))) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: split with db needs db1 / db2");
+    } else if (d->dw1 || d->dw2 || d->db1 || d->db2) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: dw1 / dw2 / db1 / db2 need split");
+    if (!d->db && (d->db1 || d->db2)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: db1 / db2 need db");
+    if ((d->scratch == nullptr) != (d->scratch_floats == 0)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: scratch and scratch_floats go together");
+    vdx::WgradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x0 = (const float*)d->x0; a.x1 = (const float*)d->x1; a.C0 = d->c0; a.C1 = d->c1; a.dy = (const float*)d->dy; a.Cout = d->cout;
+    a.dW = d->dw; a.dW1 = d->dw1; a.dW2 = d->dw2; a.db = d->db; a.db1 = d->db1; a.db2 = d->db2; a.split = d->split;
+    a.NF = d->batch * d->frames; a.F = d->frames; a.H = d->h; a.W = d->w;
+    a.kind = d->kind; a.kh = d->kind ? 4 : d->kh; a.kw = d->kind ? 4 : d->kw; a.stride = d->kind ? 1 : d->stride;
+    if (d->in_stats) {
+        if (d->c1 || !d->gamma || !d->beta || d->groups <= 0 || d->groups > 32 || d->c0 % d->groups) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bad prologue");
+        if (d->scale_shift && d->scale_shift_stride < 2 * d->c0) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: scale_shift rows hold scale[c0] | shift[c0]");
+        a.pro = 1; a.in_stats = d->in_stats; a.gamma = d->gamma; a.beta = d->beta; a.groups = d->groups; a.ss = d->scale_shift; a.ss_stride = d->scale_shift_stride;
+    }
+    a.x0_bf16 = d->x_bf16 ? 1 : 0; a.dy_bf16 = d->dy_bf16 ? 1 : 0; a.bf16_mma = d->bf16_operands ? 1 : 0;
+    a.part = d->scratch; a.part_cap = d->scratch_floats;
+    VDX_HIP(vdx::launch_conv_wgrad(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+size_t vdx_wgrad_scratch_floats(void) { return vdx::WG_PART_FLOATS; }
+
+int vdx_slot_sum(const float* part, int nslots, size_t slot_stride, long e, int cout, int split, float* d0, float* d1, float* d2, void* stream) {
+    if (!part || !d0 || nslots < 1 || e < 1 || slot_stride < (size_t)e) VDX_FAIL(VDX_ERR_INVALID, "slot_sum: bad argument");
+    if (split) {
+        if (split < 0 || cout < 1 || cout % split || cout / split > 3 || e % cout) VDX_FAIL(VDX_ERR_INVALID, "slot_sum: split must divide cout into at most 3 blocks, cout must divide e");
+        const int nb = cout / split;
+        if ((nb >= 2 && !d1) || (nb >= 3 && !d2)) VDX_FAIL(VDX_ERR_INVALID, "slot_sum: split needs d1 / d2");
+    }
+    VDX_HIP(vdx::launch_slot_sum(part, nslots, slot_stride, e, cout, split, d0, d1, d2, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_norm_act_backward_ex(const float* dact, const void* y, int y_bf16, void* dy, int dy_bf16, const double* stats, const float* gamma,
+                             const float* beta, int groups, const float* scale_shift, int scale_shift_stride, float* d_gamma, float* d_beta,
+                             float* dss, const void* r, int r_bf16, const float* ln_gamma, float* dr, float* d_ln_gamma, float* d_ln_beta,
+                             float* scratch, float* dgp, int c, int batch, long pix_per_sample, void* stream) {
+    if (!dact || !y || !dy || !stats || !gamma || !beta || !d_gamma || !d_beta || !scratch) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: null tensor");
+    if (r && (!ln_gamma || !dr || !d_ln_gamma || !d_ln_beta)) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: incomplete LayerNorm branch");
+    if (r_bf16 && !r) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: r_bf16 without r");
+    if (c < 4 || c % 4 || c > 1024 || groups < 1 || groups > 32 || c % groups || batch < 1 || pix_per_sample < 1) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: bad channels/groups/shape");
+    if (scale_shift && scale_shift_stride < 2 * c) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: scale_shift rows hold scale[c] | shift[c]");
+    vdx::NormBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dact = dact; a.y = (const float*)y; a.y_bf16 = y_bf16 ? 1 : 0; a.dy = (float*)dy; a.dy_bf16 = dy_bf16 ? 1 : 0;
+    a.stats = stats; a.gamma = gamma; a.beta = beta; a.groups = groups;
+    a.ss = scale_shift; a.ss_stride = scale_shift_stride; a.d_gamma = d_gamma; a.d_beta = d_beta; a.dss = dss;
+    a.r = (const float*)r; a.r_bf16 = r_bf16 ? 1 : 0; a.ln_gamma = ln_gamma; a.dr = dr; a.d_ln_gamma = d_ln_gamma; a.d_ln_beta = d_ln_beta;
+    a.R = scratch; a.G = scratch + (vdx::norm_bwd_scratch_floats(c, batch, pix_per_sample) - (size_t)batch * 64);
+    a.dgp = dgp; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
+    VDX_HIP(vdx::launch_norm_bwd(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_attention_core_backward_io(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, int batch, int frames,
+                                   int h, int w, int heads, int temporal, int bf16_operands, void* stream) {
+    if (!qkv || !d_o || !o || !dqkv || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: bad argument");
+    const int HD = heads * 32;
+    if (dstride < 3 * HD || dstride % 8) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: dstride must be a multiple of 8, at least 3 * heads * 32 (one [rows][dq|dk|dv] buffer)");
+    vdx::AttnBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    const long hw = (long)h * w;
+    if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
+    else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
+    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: more than 64 tokens per sequence");
+    // bf16 tensors exist for the bf16 MFMA kernel only (vdx_internal.h AttnBwdArgs::io_bf16): never hand bf16 pointers to the fp32 kernel
+    if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: bf16 tensors need bf16_operands and at most 16 tokens per sequence");
+    a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
+    a.dq = (float*)dqkv;
+    const size_t es = io_bf16 ? 2 : 4;
+    a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)HD * es);
+    a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)2 * HD * es);
+    a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
+    VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_temporal_attention_backward_fused_ex(const void* x, int x_bf16, const float* dy, const void* packed_wqkv, const float* bqkv,
+                                             const void* packed_wo_t, void* o_bf16, void* dqkv_bf16, float* dx, int batch, int frames, int h,
+                                             int w, void* stream) {
+    if (!x || !dy || !packed_wqkv || !bqkv || !packed_wo_t || !o_bf16 || !dqkv_bf16 || !dx) VDX_FAIL(VDX_ERR_INVALID, "temporal_attention_backward_fused_ex: null argument");
+    if (batch < 1 || frames < 1 || frames > 16 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "temporal_attention_backward_fused_ex: 1..16 frames");
+    vdx::AttnBwdXArgs a;
+    memset(&a, 0, sizeof(a));
+    const long hw = (long)h * w;
+    a.x = (const float*)x; a.x_bf16 = x_bf16 ? 1 : 0; a.g = dy; a.wqkv = packed_wqkv; a.bqkv = bqkv; a.woT = packed_wo_t; a.O = o_bf16; a.dqkv = dqkv_bf16; a.dx = dx;
+    a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; a.scale = 1.0f / sqrtf(32.0f);
+    VDX_HIP(vdx::launch_attn_bwd_fused(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_sla_core_backward_io(const void* q, const void* k, const void* v, const void* d_out, void* o, void* dqkv, int dstride, int io_bf16,
+                             float* scratch, int nframes, int npix, int heads, int bf16_operands, void* stream) {
+    if (!q || !k || !v || !d_out || !o || !dqkv || !scratch || heads != 8 || nframes < 1 || npix < 1) VDX_FAIL(VDX_ERR_INVALID, "sla_core_backward_io: bad argument");
+    if (dstride < 768 || dstride % 8) VDX_FAIL(VDX_ERR_INVALID, "sla_core_backward_io: dstride must be a multiple of 8, at least 768 (one [rows][dq|dk|dv] buffer)");
+    if (io_bf16 && !bf16_operands) VDX_FAIL(VDX_ERR_INVALID, "sla_core_backward_io: bf16 tensors need bf16_operands");
+    vdx::SlaBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    const size_t es = io_bf16 ? 2 : 4;
+    a.q = (const float*)q; a.k = (const float*)k; a.v = (const float*)v; a.dOut = (const float*)d_out; a.O = (float*)o; a.dq = (float*)dqkv;
+    a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + 256 * es);
+    a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + 512 * es);
+    a.A = scratch; a.NF = nframes; a.N = npix; a.heads = heads;
+    a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
+    VDX_HIP(vdx::launch_sla_bwd(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_final_conv_backward(const void* x, int x_bf16, const float* d_out, const float* kernel, float* dx, float* dw, float* db, long npix, int d,
+                            int cout, float* scratch, size_t scratch_floats, void* stream) {
+    if (!x || !d_out || !kernel || !dx || !dw || !db || npix < 1) VDX_FAIL(VDX_ERR_INVALID, "final_conv_backward: bad argument");
+    if (d < 4 || d % 4 || d > 256 || cout < 1 || cout > 4) VDX_FAIL(VDX_ERR_INVALID, "final_conv_backward: d a multiple of 4 up to 256, cout 1..4");
+    if ((scratch == nullptr) != (scratch_floats == 0)) VDX_FAIL(VDX_ERR_INVALID, "final_conv_backward: scratch and scratch_floats go together");
+    VDX_HIP(vdx::launch_final_conv_bwd((const float*)x, d_out, kernel, dx, dw, db, npix, d, cout, x_bf16 ? 1 : 0, (hipStream_t)stream, scratch, scratch_floats));
+    return VDX_OK;
+}
+
+int vdx_init_conv_backward_weights(const float* x, const float* dy, float* dw, float* db, int batch, int cin, int frames, int h, int w, int cout,
+                                   int k, float* scratch, size_t scratch_floats, void* stream) {
+    if (!x || !dy || !dw || !db || batch < 1 || cin < 1 || frames < 1 || h < 1 || w < 1 || cout < 1) VDX_FAIL(VDX_ERR_INVALID, "init_conv_backward_weights: bad argument");
+    if (k < 1 || k % 2 == 0) VDX_FAIL(VDX_ERR_INVALID, "init_conv_backward_weights: odd kernel size");
+    // the staged input tile [cin][16 + k - 1]^2 + the dy tile must fit the default 64 KB of dynamic LDS
+    if (((size_t)cin * (16 + k - 1) * (16 + k - 1) + 256 * 17) * 4 > 64 * 1024) VDX_FAIL(VDX_ERR_INVALID, "init_conv_backward_weights: cin * (k + 15)^2 too large for one LDS tile");
+    if ((long)batch * frames > 65535 || (cout + 15) / 16 > 65535) VDX_FAIL(VDX_ERR_INVALID, "init_conv_backward_weights: batch * frames exceeds the grid");
+    if ((scratch == nullptr) != (scratch_floats == 0)) VDX_FAIL(VDX_ERR_INVALID, "init_conv_backward_weights: scratch and scratch_floats go together");
+    VDX_HIP(vdx::launch_init_conv_wgrad(x, dy, dw, db, batch, cin, frames, h, w, cout, k, (hipStream_t)stream, scratch, scratch_floats));
+    return VDX_OK;
+}
+
+int vdx_time_mlp_backward(const int* time, const float* w1, const float* b1, const float* w2, const float* b2, int dim, const unsigned char* cond_mask,
+                          int null_all, int cond_dim, const float* dtemb, float* dw1, float* db1, float* dw2, float* db2, float* dnull, int batch,
+                          void* stream) {
+    if (!time || !w1 || !b1 || !w2 || !b2 || !dtemb || !dw1 || !db1 || !dw2 || !db2 || batch < 1) VDX_FAIL(VDX_ERR_INVALID, "time_mlp_backward: null argument");
+    if (dim < 4 || dim % 4 || cond_dim < 0) VDX_FAIL(VDX_ERR_INVALID, "time_mlp_backward: dim must be a multiple of 4");
+    if (cond_dim && !dnull) VDX_FAIL(VDX_ERR_INVALID, "time_mlp_backward: cond_dim needs dnull");
+    vdx::TimeMlpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.time = time; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.dim = dim; a.time_dim = 4 * dim;
+    a.cond_mask = cond_mask; a.null_all = null_all; a.cond_dim = cond_dim; a.temb_dim = a.time_dim + cond_dim;
+    if ((size_t)batch * (a.dim + 2 * a.time_dim + 64) * 4 > 150 * 1024) VDX_FAIL(VDX_ERR_INVALID, "time_mlp_backward: batch too large for the LDS-resident recompute");
+    VDX_HIP(vdx::launch_time_mlp_bwd(a, dtemb, dw1, db1, dw2, db2, cond_dim ? dnull : nullptr, batch, (hipStream_t)stream));
     return VDX_OK;
 }
 

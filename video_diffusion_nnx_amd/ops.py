@@ -292,3 +292,211 @@ def sla_core_backward(q, k, v, d_out, nframes, npix, heads=8, bf16_operands=Fals
     L.check(_sla_core_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(d_out), *[L.ptr(t) for t in outs], L.ptr(scr), nframes, npix, heads,
                           int(bool(bf16_operands)), L.stream_ptr()))
     return outs      # o, dq, dk, dv
+
+
+# ---- backward forms of the network (vdx.h: "Backward forms of the network"): the flag combinations model_bwd.hip sets ---------------
+
+
+
+class WgradExDesc(C.Structure):
+    _fields_ = [('x0', C.c_void_p), ('x1', C.c_void_p), ('c0', C.c_int), ('c1', C.c_int), ('x_bf16', C.c_int),
+                ('dy', C.c_void_p), ('cout', C.c_int), ('dy_bf16', C.c_int),
+                ('dw', C.c_void_p), ('dw1', C.c_void_p), ('dw2', C.c_void_p), ('split', C.c_int),
+                ('db', C.c_void_p), ('db1', C.c_void_p), ('db2', C.c_void_p),
+                ('batch', C.c_int), ('frames', C.c_int), ('h', C.c_int), ('w', C.c_int),
+                ('kind', C.c_int), ('kh', C.c_int), ('kw', C.c_int), ('stride', C.c_int),
+                ('in_stats', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p), ('groups', C.c_int),
+                ('scale_shift', C.c_void_p), ('scale_shift_stride', C.c_int), ('bf16_operands', C.c_int),
+                ('scratch', C.c_void_p), ('scratch_floats', C.c_size_t)]
+
+
+WG_PART_FLOATS = L._sig('vdx_wgrad_scratch_floats', C.c_size_t, [])()          # the slot scratch model_bwd.hip hands every weight gradient
+_wgrad_ex = L._sig('vdx_conv_backward_weights_ex', C.c_int, [C.POINTER(WgradExDesc), C.c_void_p])
+_slot_sum = L._sig('vdx_slot_sum', C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+_norm_bwd_ex = L._sig('vdx_norm_act_backward_ex', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                      [C.c_int, C.c_int, C.c_long, C.c_void_p])
+_attn_core_bwd_io = L._sig('vdx_attention_core_backward_io', C.c_int, [C.c_void_p] * 4 + [C.c_int] * 9 + [C.c_void_p])
+_attn_bwd_fused_ex = L._sig('vdx_temporal_attention_backward_fused_ex', C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_void_p])
+_sla_core_bwd_io = L._sig('vdx_sla_core_backward_io', C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p])
+_conv_rows = L._sig('vdx_conv_forward_rows', C.c_int, [C.c_int, C.POINTER(L.ConvDesc), C.c_int, C.c_int, C.c_void_p])
+_final_bwd = L._sig('vdx_final_conv_backward', C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
+_init_wgrad = L._sig('vdx_init_conv_backward_weights', C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p])
+_time_mlp_bwd = L._sig('vdx_time_mlp_backward', C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p])
+
+
+def _is16(t) -> int:
+    assert t.dtype in (torch.float32, torch.bfloat16)
+    return int(t.dtype == torch.bfloat16)
+
+
+def conv_backward_weights_ex(x0, dy, kshape, *, x1=None, kind=0, k=3, stride=1, in_stats=None, gamma=None, beta=None, groups=8,
+                             scale_shift=None, bf16_operands=True, split=0, bias=False, scratch=None):
+    """Weight gradient as the network launches it.  x0 / x1 / dy: fp32 or bfloat16 tensors (x_bf16 / dy_bf16 follow the dtypes);
+    split > 0: returns one dW (and db) per column block of dy; bias: also the fused bias sums; scratch: float32 tensor for the
+    per-workgroup slots (fixed-order sums) or None (float atomics).  -> (list of dW, list of db or None)"""
+    B, Fr, H, W, c0 = x0.shape
+    c1 = 0 if x1 is None else x1.shape[-1]
+    cout = dy.shape[-1]
+    assert x1 is None or x1.dtype == x0.dtype
+    nb = cout // split if split else 1
+    shp = list(kshape)
+    if split:
+        shp[-1] = split
+    dws = [torch.zeros(shp, dtype=torch.float32, device=x0.device) for _ in range(nb)]
+    dbs = [torch.zeros(shp[-1], dtype=torch.float32, device=x0.device) for _ in range(nb)] if bias else None
+    d = WgradExDesc()
+    d.x0, d.x1, d.c0, d.c1, d.x_bf16 = L.ptr(x0), L.ptr(x1), c0, c1, _is16(x0)
+    d.dy, d.cout, d.dy_bf16 = L.ptr(dy), cout, _is16(dy)
+    d.dw, d.dw1, d.dw2 = [L.ptr(dws[i]) if i < nb else 0 for i in range(3)]
+    d.db, d.db1, d.db2 = [L.ptr(dbs[i]) if bias and i < nb else 0 for i in range(3)]
+    d.split = split
+    d.batch, d.frames, d.h, d.w = B, Fr, H, W
+    d.kind, d.kh, d.kw, d.stride = kind, k, k, stride
+    d.in_stats, d.gamma, d.beta, d.groups = L.ptr(in_stats), L.ptr(gamma), L.ptr(beta), groups
+    d.scale_shift = L.ptr(scale_shift)
+    d.scale_shift_stride = 0 if scale_shift is None else scale_shift.shape[-1]
+    d.bf16_operands = int(bool(bf16_operands))
+    d.scratch, d.scratch_floats = L.ptr(scratch), 0 if scratch is None else scratch.numel()
+    L.check(_wgrad_ex(C.byref(d), L.stream_ptr()))
+    return dws, dbs
+
+
+def slot_sum(part, nslots, slot_stride, e_count, dsts, cout=0, split=0):
+    """dsts[co // split][...] += sum over the slots in order (dsts: 1..3 float32 tensors, accumulated in place)."""
+    p = [L.ptr(t) for t in dsts] + [0, 0]
+    L.check(_slot_sum(L.ptr(part), nslots, slot_stride, e_count, cout, split, p[0], p[1], p[2], L.stream_ptr()))
+    return dsts
+
+
+def norm_act_backward_ex(dact, y, stats, gamma, beta, groups=8, scale_shift=None, r=None, ln_gamma=None, dy_bf16=False, deterministic=False):
+    """norm_act_backward on the network's tensor types: y / r fp32 or bfloat16, dy written as bfloat16 when dy_bf16; deterministic:
+    parameter gradients through the per-sample rows (dgp) instead of float atomics.  -> dict as norm_act_backward."""
+    B, Cc = y.shape[0], y.shape[-1]
+    pix = y.numel() // (B * Cc)
+    dev = y.device
+    z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+    out = dict(dy=torch.empty(y.shape, dtype=torch.bfloat16 if dy_bf16 else torch.float32, device=dev), d_gamma=z(Cc), d_beta=z(Cc),
+               dss=z(B, 2 * Cc) if scale_shift is not None else None,
+               dr=torch.empty(y.shape, dtype=torch.float32, device=dev) if r is not None else None,
+               d_ln_gamma=z(Cc) if r is not None else None, d_ln_beta=z(Cc) if r is not None else None)
+    # both scratches uninitialised on purpose (NaN-filled: anything read before it is written shows)
+    scratch = torch.full((_norm_bwd_scr(Cc, B, pix),), float('nan'), dtype=torch.float32, device=dev)
+    dgp = torch.full((B, 4, Cc), float('nan'), dtype=torch.float32, device=dev) if deterministic else None
+    L.check(_norm_bwd_ex(L.ptr(dact), L.ptr(y), _is16(y), L.ptr(out['dy']), int(bool(dy_bf16)), L.ptr(stats), L.ptr(gamma), L.ptr(beta), groups,
+                         L.ptr(scale_shift), 0 if scale_shift is None else scale_shift.shape[-1], L.ptr(out['d_gamma']), L.ptr(out['d_beta']),
+                         L.ptr(out['dss']), L.ptr(r), 0 if r is None else _is16(r), L.ptr(ln_gamma), L.ptr(out['dr']), L.ptr(out['d_ln_gamma']),
+                         L.ptr(out['d_ln_beta']), L.ptr(scratch), L.ptr(dgp), Cc, B, pix, L.stream_ptr()))
+    return out
+
+
+def attention_core_backward_io(qkv, d_o, B, Fr, H, W, heads, temporal, bf16_operands=True, sentinel=None, pad_cols=0):
+    """Interleaved form: qkv / d_o fp32 or bfloat16 (same dtype) -> o [rows][heads*32], dqkv [rows][3*heads*32 + pad_cols] of that dtype
+    (the network's buffer has pad_cols = 0).  sentinel: value dqkv is pre-filled with; the pad columns must keep it."""
+    assert qkv.dtype == d_o.dtype
+    HD = heads * 32
+    o = torch.empty_like(d_o)
+    dqkv = torch.empty(d_o.shape[0], 3 * HD + pad_cols, dtype=d_o.dtype, device=d_o.device)
+    if sentinel is not None:
+        dqkv.fill_(sentinel)
+    L.check(_attn_core_bwd_io(L.ptr(qkv), L.ptr(d_o), L.ptr(o), L.ptr(dqkv), 3 * HD + pad_cols, _is16(qkv), B, Fr, H, W, heads, int(temporal),
+                              int(bool(bf16_operands)), L.stream_ptr()))
+    return o, dqkv
+
+
+def temporal_attention_backward_fused_ex(x, dy, wqkv, bqkv, wo):
+    """temporal_attention_backward_fused with x fp32 or bfloat16 (bf16 activation storage)."""
+    B, Fr, H, W, C_ = x.shape
+    assert C_ == 64 and wqkv.shape == (64, 768) and wo.shape == (256, 64) and dy.dtype == torch.float32
+    pw = pack_conv_weights(wqkv, 'bf16')
+    pwo_t = pack_conv_weights_t(wo, 'bf16')
+    rows = B * Fr * H * W
+    o = torch.empty(rows, 256, dtype=torch.bfloat16, device=x.device)
+    dqkv = torch.empty(rows, 768, dtype=torch.bfloat16, device=x.device)
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    bq = bqkv.contiguous().float()
+    L.check(_attn_bwd_fused_ex(L.ptr(x), _is16(x), L.ptr(dy), L.ptr(pw), L.ptr(bq), L.ptr(pwo_t), L.ptr(o), L.ptr(dqkv), L.ptr(dx), B, Fr, H, W,
+                               L.stream_ptr()))
+    return dx, o, dqkv
+
+
+def sla_core_backward_io(q, k, v, d_out, nframes, npix, heads=8, bf16_operands=True, sentinel=None, pad_cols=0):
+    """Interleaved form: q, k, v, d_out fp32 or bfloat16 -> o [rows][256], dqkv [rows][768 + pad_cols] of that dtype."""
+    o = torch.empty_like(q)
+    dqkv = torch.empty(q.shape[0], 768 + pad_cols, dtype=q.dtype, device=q.device)
+    if sentinel is not None:
+        dqkv.fill_(sentinel)
+    scr = torch.empty(_sla_scr(nframes, heads), dtype=torch.float32, device=q.device)
+    L.check(_sla_core_bwd_io(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(d_out), L.ptr(o), L.ptr(dqkv), 768 + pad_cols, _is16(q), L.ptr(scr), nframes, npix, heads,
+                             int(bool(bf16_operands)), L.stream_ptr()))
+    return o, dqkv
+
+
+def conv_dgrad_rows(dy, packed_wt, w_rows, w_row0, nrows, *, mode, k=3, res=None):
+    """Data gradient of a stride-1 conv towards input channels [w_row0, w_row0 + nrows) of its w_rows input channels: packed_wt =
+    pack_conv_weights_t of the whole kernel; dy fp32 or bfloat16; res (fp32) is added.  -> fp32 [B,F,H,W,nrows]"""
+    B, Fr, H, W, cdy = dy.shape
+    y = torch.empty(B, Fr, H, W, nrows, dtype=torch.float32, device=dy.device)
+    d = L.ConvDesc()
+    d.x_bf16, d.y_bf16 = _is16(dy), 0
+    d.x0, d.x1, d.c0, d.c1 = L.ptr(dy), 0, cdy, 0
+    d.packed_w, d.bias, d.y, d.cout = L.ptr(packed_wt), 0, L.ptr(y), nrows
+    d.batch, d.frames, d.h, d.w = B, Fr, H, W
+    d.kind, d.kh, d.kw, d.stride = 0, k, k, 1
+    d.res, d.res_bf16 = L.ptr(res), 0
+    L.check(_conv_rows(_mode(mode), C.byref(d), w_rows, w_row0, L.stream_ptr()))
+    return y
+
+
+def final_conv_backward(x, d_out, kernel, scratch=None):
+    """x [.., D] fp32 or bfloat16, d_out [.., Cout], kernel Flax (1, D, Cout) -> dx [.., D], dw (D, Cout), db (Cout)."""
+    D_, cout = kernel.shape[-2], kernel.shape[-1]
+    npix = x.numel() // D_
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    dw = torch.zeros(D_, cout, dtype=torch.float32, device=x.device)
+    db = torch.zeros(cout, dtype=torch.float32, device=x.device)
+    L.check(_final_bwd(L.ptr(x), _is16(x), L.ptr(d_out), L.ptr(kernel.contiguous()), L.ptr(dx), L.ptr(dw), L.ptr(db), npix, D_, cout,
+                       L.ptr(scratch), 0 if scratch is None else scratch.numel(), L.stream_ptr()))
+    return dx, dw, db
+
+
+def init_conv_backward_weights(x, dy, k, scratch=None):
+    """x [B,C,F,H,W] (external layout), dy [B,F,H,W,D] -> dw (1,k,k,C,D), db (D)."""
+    B, Cin, Fr, H, W = x.shape
+    cout = dy.shape[-1]
+    dw = torch.zeros(1, k, k, Cin, cout, dtype=torch.float32, device=x.device)
+    db = torch.zeros(cout, dtype=torch.float32, device=x.device)
+    L.check(_init_wgrad(L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(db), B, Cin, Fr, H, W, cout, k, L.ptr(scratch),
+                        0 if scratch is None else scratch.numel(), L.stream_ptr()))
+    return dw, db
+
+
+def time_mlp_backward(time, w1, b1, w2, b2, dtemb, cond_dim=0, cond_mask=None, null_all=False):
+    """-> dw1, db1, dw2, db2, dnull (None without conditioning)."""
+    B, dim = time.shape[0], w1.shape[0]
+    t32 = time.to(torch.int32).contiguous()
+    cm = None if cond_mask is None else cond_mask.to(torch.uint8).contiguous()
+    outs = [torch.zeros_like(t) for t in (w1, b1, w2, b2)]
+    dnull = torch.zeros(cond_dim, dtype=torch.float32, device=w1.device) if cond_dim else None
+    L.check(_time_mlp_bwd(L.ptr(t32), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), dim, L.ptr(cm), int(null_all), cond_dim, L.ptr(dtemb),
+                          *[L.ptr(t) for t in outs], L.ptr(dnull), B, L.stream_ptr()))
+    return (*outs, dnull)
+
+
+_loss_grad = L._sig('vdx_loss_grad', C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p])
+_adam_ema = L._sig('vdx_adam_ema_step', C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_float] * 4 + [C.c_long, C.c_float, C.c_int, C.c_float, C.c_void_p])
+
+
+def loss_grad(eps_hat, noise, l2):
+    """eps_hat channel-last [B,F,H,W,C], noise external [B,C,F,H,W] -> d(mean loss)/d(eps_hat), channel-last."""
+    B, Cc = noise.shape[0], noise.shape[1]
+    fhw = noise.numel() // (B * Cc)
+    out = torch.empty_like(eps_hat)
+    L.check(_loss_grad(L.ptr(eps_hat), L.ptr(noise), L.ptr(out), B, Cc, fhw, int(bool(l2)), L.stream_ptr()))
+    return out
+
+
+def adam_ema_step(p, g, m, v, ema, *, lr, b1, b2, eps, step_count, grad_scale=1.0, do_ema=True, ema_decay=0.995):
+    """In place on p, m, v (and ema when do_ema)."""
+    L.check(_adam_ema(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), p.numel(), lr, b1, b2, eps, step_count, grad_scale, int(bool(do_ema)),
+                      ema_decay, L.stream_ptr()))
