@@ -180,6 +180,75 @@ int vdx_sla_forward_bf16(const void* x_bf16, void* y_bf16, const void* wq_packed
                          const void* wo_packed, void* workspace, int batch, int frames, int h, int w, int c, int heads, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Forward forms of the network (test-facing).  vdx_unet_forward composes launches and sets flags on the launchers that the
+ * operator-level entry points above never do: the per-head attention / SLA kernels of the wide levels followed by the 1x1
+ * out-projection with residual, the long attention core between two 1x1 convs, bf16 TENSORS on the tail, the final conv and the init
+ * conv, the final conv inside the last tail, the MFMA init conv, the scale/shift pass.  The functions below call the same
+ * compositions (model.hip: attention_block_forward, sla_block_forward) and the same launchers, so that each of those kernel forms can be
+ * compared with a reference on its own (tests/test_gpu_forward_forms.py).  No kernel is specific to them.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Scratch the two attention compositions need for a block of `batch` samples: the per-head output [rows][heads*32] bf16 of the heads
+ * path, or qkv + o [rows][4*heads*32] fp32 of the long path (h*w > 64, spatial). */
+size_t vdx_attention_heads_scratch_bytes(int batch, int frames, int h, int w);
+size_t vdx_attention_long_scratch_bytes(int batch, int frames, int h, int w, int heads);
+
+/* Attention block as run_attn launches it at the wide levels of a VDX_MODE_BF16 network: attention_head_kernel (q|k|v projection +
+ * core per head) -> o_scratch [rows][256] bf16 (caller-owned, so the core can be checked apart from the projection), then the 1x1
+ * out-projection + bias + residual -> y.  x, y fp32 or (io_bf16) bf16 channel-last [batch, frames, h, w, c]; 8 heads x 32; weights as
+ * vdx_attention_forward (VDX_MODE_BF16 packing).  VDX_ERR_INVALID exactly where run_attn would not take this path (c < 256, c % 128,
+ * more than 16 temporal / 64 spatial tokens, a scratch that is too small). */
+int vdx_attention_heads_forward(const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv, const void* wo_packed,
+                                const float* bo, void* o_scratch, size_t o_scratch_bytes, int batch, int frames, int h, int w, int c,
+                                int temporal, int fp8_core, void* stream);
+
+/* Spatial attention over more than 64 tokens as run_attn launches it: 1x1 q|k|v conv -> fp32 core (attention_long_core_kernel) -> 1x1
+ * out-projection + bias + residual.  scratch: vdx_attention_long_scratch_bytes, holds qkv [rows][3*heads*32] then o [rows][heads*32],
+ * fp32.  io_bf16 needs VDX_MODE_BF16.  h*w <= 64 is VDX_ERR_INVALID. */
+int vdx_attention_long_forward(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                               const void* wo_packed, const float* bo, void* scratch, size_t scratch_bytes, int batch, int frames, int h,
+                               int w, int c, int heads, void* stream);
+
+/* SpatialLinearAttention block as run_sla launches it at the wide levels: sla_head_kernel -> o_scratch [rows][256] bf16
+ * (caller-owned), then the 1x1 to_out + residual -> y.  VDX_ERR_INVALID where run_sla would not take this path (c < 256, c % 128,
+ * h*w % 16). */
+int vdx_sla_heads_forward(const void* x, void* y, int io_bf16, const void* wq_packed, const void* wk_packed, const void* wv_packed,
+                          const void* wo_packed, void* o_scratch, size_t o_scratch_bytes, int batch, int frames, int h, int w, int c,
+                          void* stream);
+
+/* vdx_resblock_tail with a storage type per tensor (run_res: y2 bf16 in bf16 mode, r / out bf16 under bf16 activation storage).
+ * All three bf16 with c % 8 == 0 runs resblock_tail16_kernel, anything else resblock_tail_kernel. */
+int vdx_resblock_tail_ex(const void* y2, int y2_bf16, const void* r, int r_bf16, void* out, int out_bf16, const double* stats,
+                         const float* gn_gamma, const float* gn_beta, int groups, const float* ln_gamma, const float* ln_beta, int c,
+                         int batch, long pix_per_sample, void* stream);
+
+/* vdx_resblock_tail_rc_bf16 with the network's one-channel head inside (the FIN form of resblock_tail_rc16_kernel, model.hip run_res
+ * for the last block): fin_out [batch * pix_per_sample] fp32 = out . fin_w[c] + fin_b[0] is written INSTEAD of out (the dot product
+ * takes the fp32 values of out, nothing is rounded to bf16).  Served: (c0 + c1, c) in {(128, 64), (64, 32)} with c1 == c0. */
+int vdx_resblock_tail_rc_head_bf16(const void* y2, const void* x0, const void* x1, int c0, int c1, const void* rc_w_packed,
+                                   const float* rc_bias, const double* stats, const float* gn_gamma, const float* gn_beta, int groups,
+                                   const float* ln_gamma, const float* ln_beta, int c, const float* fin_w, const float* fin_b,
+                                   float* fin_out, int batch, long pix_per_sample, void* stream);
+
+/* vdx_final_conv with x_bf16: x holds bf16 (d % 8 == 0; final_conv16_kernel for d in {8, 16, 32, 64, 128} and cout <= 4, else
+ * final_conv_kernel). */
+int vdx_final_conv_ex(const void* x, int x_bf16, const float* kernel, const float* bias, float* y, long npix, int d, int cout,
+                      void* stream);
+
+/* vdx_init_conv as the network launches it: mode VDX_MODE_BF16 with cin == 1 runs init_conv_mfma_kernel (x and the kernel rounded to
+ * bf16, fp32 accumulate); y_bf16: y is WRITTEN as bf16 (VDX_MODE_BF16 only). */
+int vdx_init_conv_ex(int mode, const float* x, const float* kernel, const float* bias, void* y, int y_bf16, int batch, int cin,
+                     int frames, int h, int w, int cout, int k, void* stream);
+
+/* Every ResnetBlock's (scale, shift) in one launch pair (resblock_ss_lin_kernel, resblock_ss_norm_kernel; reference modules.py:202-208,
+ * 233-238): for layer l and sample b, lin[out_off * batch + b * n ..] = SiLU(temb[b]) . W + bias and ss[same] = LayerNorm_n(lin).
+ * Offsets are in floats: w_off ([temb_dim][n] Flax kernel), b_off, g_off, be_off into params; out_off (per sample) into ss / lin.
+ * layers_dev: device array of nlayers entries; max_n = the widest layer (n <= 2048). */
+typedef struct { long w_off, b_off, g_off, be_off, out_off; int n; int pad_; } vdx_ss_layer;
+int vdx_resblock_scale_shift(const float* params, const float* temb, const vdx_ss_layer* layers_dev, int nlayers, float* ss, float* lin,
+                             int temb_dim, int batch, int max_n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Network-level entry points.
  * ---------------------------------------------------------------------------------------------- */
 

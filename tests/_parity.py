@@ -1,5 +1,6 @@
-"""Comparison helpers shared by the block-level parity tests of the backward forms (tests/test_gpu_backward_forms.py) and by
-the CPU-only sensitivity tests that prove they bite (tests/test_host_parity_helpers.py).  A plain module: nothing here is
+"""Comparison helpers shared by the block-level parity tests of the backward and forward forms (tests/test_gpu_backward_forms.py,
+tests/test_gpu_forward_forms.py, the bf16-store checks of tests/test_gpu_conv.py and tests/test_gpu_blocks.py) and by the CPU-only
+sensitivity tests that prove they bite (tests/test_host_parity_helpers.py).  A plain module: nothing here is
 collected, nothing here touches the GPU.
 
 Where the numbers come from.  No bound in this file is derived from a kernel's output:
@@ -301,3 +302,173 @@ def split_columns(flat, cout, split):
     """[rows * cout] laid out [rows][cout] -> list of [rows][split] column blocks (the q|k|v split epilogue's targets)."""
     m = flat.reshape(-1, cout)
     return [m[:, i * split:(i + 1) * split].contiguous() for i in range(cout // split)]
+
+
+# ---- forward forms -------------------------------------------------------------------------------------------------------------------
+
+
+def e4m3r(t: torch.Tensor) -> torch.Tensor:
+    """Round-trip through OCP e4m3 (round to nearest even, saturating at +-448: what v_cvt_pk_fp8_f32 does on gfx950), keeping the dtype."""
+    return t.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float().to(t.dtype)
+
+
+def have_e4m3() -> bool:
+    try:
+        return bool(torch.equal(e4m3r(torch.tensor([1.0, 1.06, 300.0, -0.3])), torch.tensor([1.0, 1.0, 288.0, -0.3125])))
+    except Exception:
+        return False
+
+
+def attention_block_fwd(x, wqkv, bqkv, wo, bo, B, Fr, H, W, temporal, emulate=False, fp8=False, round_out=False, unmasked_pad=0):
+    """y = MHA(x) + x (8 heads x 32) over the frames of every pixel (temporal) or the pixels of every frame, in fp64, closed form.
+    x [B, Fr, H, W, C]; wqkv [C, 768] = q | k | v column blocks, bqkv [768], wo [256, C], bo [C].
+    emulate: the rounding points of attention_head_kernel (attention.hip): q, k, v = bf16(x W + b) -- the projections' fp32 accumulators
+    become MFMA operands through pack_bf16x2 in Mma::mma16 (vdx_common.h:87-91; core_mma16 calls at attention.hip:1158-1159, 1181);
+    the scores stay fp32 and are scaled inside the exponential (:1171); the probabilities are rounded to bf16 as the operand of the PV
+    product (:1176 -> :1181); o is stored as bf16 (:1182-1183).  fp8: e4m3 instead of bf16 for q, k, v and P (mma16_fp8,
+    vdx_common.h:95-99; o is still stored as bf16).  round_out: y rounded to bf16 (the io_bf16 store of the 1x1 out-projection).
+    unmasked_pad > 0 (a FAULT, for the CPU proofs): that many padding keys with k = v = their bias take part in the softmax.
+    -> (o [rows][256], y [B, Fr, H, W, C])"""
+    dt = torch.float64
+    C_ = x.shape[-1]
+    X = x.to(dt).reshape(-1, C_)
+    qkv = X @ wqkv.to(dt) + bqkv.to(dt)
+    rd = (e4m3r if fp8 else bf16r) if emulate else (lambda t: t)
+    s = _seq_view(rd(qkv), B, Fr, H * W, 8, temporal, 3)
+    q, k, v = s[..., 0, :, :], s[..., 1, :, :], s[..., 2, :, :]                     # [b, s, L, h, d]
+    if unmasked_pad:
+        pad = rd(bqkv.to(dt)).reshape(3, 8, 32)
+        ext = lambda t, i: torch.cat((t, pad[i].expand(*t.shape[:2], unmasked_pad, 8, 32)), 2)
+        k, v = ext(k, 1), ext(v, 2)
+    S = torch.einsum('bsihd,bsjhd->bshij', q, k) / math.sqrt(32.0)
+    P = rd(torch.softmax(S, -1))
+    o = _seq_unview(torch.einsum('bshij,bsjhd->bsihd', P, v), temporal)
+    if emulate:
+        o = bf16r(o)
+    y = (o @ wo.to(dt) + bo.to(dt)).reshape(x.shape) + x.to(dt)
+    return o, (bf16r(y) if round_out else y)
+
+
+def sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W, emulate=False, round_out=False):
+    """y = SpatialLinearAttention(x) + x (8 heads x 32) in fp64, closed form: ctx = softmax_n(k)^T v, out = ctx^T softmax_d(q) per
+    (frame, head).  wq / wk / wv [C, 256], wo [256, C].  emulate: the rounding points of sla_head_kernel (sla.hip): exp(k - max) and v
+    are rounded to bf16 as the operands of the context product (Mma::mma16 at :1023) while the softmax denominator sums the unrounded
+    exponentials (:1006-1007) and divides the fp32 context (:1026-1033); ctx and softmax_d(q) are rounded to bf16 as the operands of
+    the output product (:1070-1071); o is stored as bf16 (:1072-1073).  (The kernel rounds exp(k - running max); rounding is relative,
+    so the final maximum gives the same relative error.)  -> (o [rows][256], y [B, Fr, H, W, C])"""
+    dt = torch.float64
+    C_, NF, N = x.shape[-1], B * Fr, H * W
+    X = x.to(dt).reshape(-1, C_)
+    hs = lambda t: t.reshape(NF, N, 8, 32).permute(0, 2, 1, 3)                      # [f, h, n, d]
+    Q, K, V = hs(X @ wq.to(dt)), hs(X @ wk.to(dt)), hs(X @ wv.to(dt))
+    rd = bf16r if emulate else (lambda t: t)
+    qs = torch.softmax(Q, -1)
+    ek = torch.exp(K - K.max(dim=2, keepdim=True).values)
+    ctx = torch.einsum('fhnd,fhne->fhde', rd(ek), rd(V)) / ek.sum(2, keepdim=True).transpose(2, 3)
+    o = torch.einsum('fhde,fhnd->fhne', rd(ctx), rd(qs)).permute(0, 2, 1, 3).reshape(NF * N, 256)
+    if emulate:
+        o = bf16r(o)
+    y = (o @ wo.to(dt)).reshape(x.shape) + x.to(dt)
+    return o, (bf16r(y) if round_out else y)
+
+
+def seq_head_groups(o, B, Fr, HW, temporal):
+    """o [rows][256] -> [sequences, heads, L * 32]: the groups of a per-head attention output."""
+    s = _seq_view(o, B, Fr, HW, 8, temporal, 1)[..., 0, :, :]                        # [b, s, L, h, d]
+    return s.permute(0, 1, 3, 2, 4).reshape(s.shape[0] * s.shape[1], 8, -1)
+
+
+def frame_head_groups(o, NF, N):
+    """o [rows][256] -> [frames, heads, N * 32]."""
+    return o.reshape(NF, N, 8, 32).permute(0, 2, 1, 3).reshape(NF, 8, -1)
+
+
+def norm_bound(ref32, ref64, slices=None, stated=FWD_STATED):
+    """Bound for an fp32 output of norm arithmetic (GroupNorm / LayerNorm / SiLU chains): max(stated, 8 x the same formula evaluated in
+    fp32 on the CPU against fp64), globally and per slice; refused at 1e-4 or more.  -> (bound, {label: bound}, floor)"""
+    return exact_products_bounds(ref32, ref64, slices, None, stated)
+
+
+def spread_slots(slab, seed=0):
+    """Sum-preserving split of a GroupNorm statistics slab [B][32][G][2] (everything in slot 0) over several of the 32 slots, as a
+    producing conv's workgroups leave it: slot k gets an uneven share w_k (some slots stay empty), slot 31 the remainder."""
+    g = torch.Generator().manual_seed(seed)
+    w = torch.rand(32, generator=g, dtype=torch.float64)
+    w[torch.rand(32, generator=g) < 0.4] = 0.0
+    w[0] = max(w[0].item(), 0.1)
+    w = w / w.sum()
+    tot = slab[:, 0]
+    out = tot[:, None] * w[None, :, None, None]
+    out[:, 31] += tot - out.sum(1)
+    return out
+
+
+def tile_slices(shape, tile=16):
+    """One slice per (frame, tile x tile block) of a channel-last [B, F, H, W, C] tensor: the unit a conv workgroup owns."""
+    B, Fr, H, W = shape[:4]
+    return [(f'b{b}/f{f}/y{y}/x{x}', (b, f, slice(y, min(y + tile, H)), slice(x, min(x + tile, W))))
+            for b in range(B) for f in range(Fr) for y in range(0, H, tile) for x in range(0, W, tile)]
+
+
+def tile_rels(got, ref, tile=16):
+    """rel-L2 per (frame, tile x tile block) of channel-last [B, F, H, W, C] tensors (H, W multiples of tile) -> [B, F, H/t, W/t]."""
+    B, Fr, H, W, C_ = ref.shape
+    v = lambda t: t.double().reshape(B, Fr, H // tile, tile, W // tile, tile, C_).permute(0, 1, 2, 4, 3, 5, 6).reshape(B, Fr, H // tile, W // tile, -1)
+    g, r = v(got), v(ref)
+    return (g - r).norm(dim=-1) / (r.norm(dim=-1) + 1e-300)
+
+
+def tile_bound(act32_rounded, act64_rounded, out_of, tile=16, stated=FWD_STATED, bf16_out=False):
+    """Per-tile bound of a fused-prologue conv: the kernel rounds the activation it recomputes to bf16; computed in fp32 it lands on the
+    other side of a rounding boundary for a few elements.  floor = the worst tile of out_of(activation computed in fp32, rounded)
+    against out_of(activation computed in fp64, rounded), not below the effect of ONE flipped element of rms size on a tile's output,
+    bf16_ulp(rms) / ||activation of one tile||; bound = max(stated, 4 x floor).  bf16_out: the output is stored as bf16 -- one rounding
+    moves an element by at most 2^-9 of itself, hence a tile's rel-L2 by at most 2^-9, which is added (a figure of the number format;
+    a tile row scaled by 0.9 is 0.1 / sqrt(16) = 2.5e-2, an order above it).  -> (bound, floor)"""
+    ref, alt = out_of(act64_rounded), out_of(act32_rounded)
+    t = min(tile, ref.shape[2], ref.shape[3])
+    floor = tile_rels(alt, ref, t).max().item()
+    a = act64_rounded.double()
+    one_flip = (bf16_ulp(a.pow(2).mean().sqrt()) / (a.pow(2).mean().sqrt() * math.sqrt(t * t * a.shape[-1]))).item()
+    floor = max(floor, one_flip)
+    return max(stated, 4.0 * floor) + (BF16_ROUNDING if bf16_out else 0.0), floor
+
+
+def assert_tiles(got, ref, bound, tile=16, what=''):
+    t = min(tile, ref.shape[2], ref.shape[3])
+    r = tile_rels(got, ref, t)
+    i = int(r.argmax())
+    print(f'[tiles] {what}: worst (frame, {t}x{t} tile) #{i} rel {r.max().item():.3e} (bound {bound:.3e})')
+    assert r.max().item() < bound, f'{what}: tile {i} rel-L2 {r.max().item():.3e} >= {bound:.3e}'
+    return r.max().item()
+
+
+def gn_sums(y, groups=8, dtype=torch.float64):
+    """[B, ..., C] -> (sum y, sum |y|, sum y^2), each [B, groups], accumulated in `dtype`."""
+    B, C_ = y.shape[0], y.shape[-1]
+    yg = y.to(dtype).reshape(B, -1, groups, C_ // groups)
+    return yg.sum(dim=(1, 3)), yg.abs().sum(dim=(1, 3)), (yg * yg).sum(dim=(1, 3))
+
+
+def gn_stats_errors(s1, s2, ref64, groups=8):
+    """|d sum y| / sum |y| and |d sum y^2| / sum y^2 per (sample, group) of sums s1, s2 [B, groups] against the fp64 tensor."""
+    r1, ra, r2 = gn_sums(ref64, groups)
+    return (s1.double() - r1).abs() / ra, (s2.double() - r2).abs() / r2
+
+
+def assert_gn_stats(stats, ref64, ref32, tiles_per_sample, groups=8, what=''):
+    """GroupNorm statistics epilogue of a conv: stats [B, groups, 2] (sum, sum of squares) against the fp64 conv output ref64, per
+    (sample, group).  Bound = 8 x the worst (sample, group) of the same two figures for ref32, the conv AND its sums evaluated in fp32
+    on the CPU.  Refused unless the bound is at most a quarter of the share one tile has in a sample's sums, 1 / tiles_per_sample: a
+    tile credited to the wrong sample changes sum y^2 by about that share.  -> (worst e1, worst e2, bound 1, bound 2)"""
+    f1, _, f2 = gn_sums(ref32.float(), groups, torch.float32)
+    fe1, fe2 = gn_stats_errors(f1, f2, ref64, groups)
+    b1, b2 = 8.0 * fe1.max().item(), 8.0 * fe2.max().item()
+    share = 1.0 / tiles_per_sample
+    assert max(b1, b2) <= 0.25 * share, f'{what}: statistics bound {max(b1, b2):.2e} is not below a quarter of one tile\'s share {share:.2e}'
+    e1, e2 = gn_stats_errors(stats[..., 0], stats[..., 1], ref64, groups)
+    assert torch.isfinite(stats).all(), f'{what}: non-finite statistics'
+    print(f'[gn stats] {what}: sum {e1.max().item():.3e} (bound {b1:.3e}), sum of squares {e2.max().item():.3e} (bound {b2:.3e}); one tile = {share:.1e}')
+    assert e1.max().item() <= b1, f'{what}: sum y off by {e1.max().item():.3e} of sum |y| at (sample, group) {divmod(int(e1.argmax()), groups)}, bound {b1:.3e}'
+    assert e2.max().item() <= b2, f'{what}: sum y^2 off by {e2.max().item():.3e} at (sample, group) {divmod(int(e2.argmax()), groups)}, bound {b2:.3e}'
+    return e1.max().item(), e2.max().item(), b1, b2

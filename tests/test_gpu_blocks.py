@@ -5,6 +5,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import _parity as P
 from oracle import unet3d_ref as R
 
 DEV = 'cuda:0'
@@ -59,6 +60,12 @@ def test_block_prologue_pass_bf16(C, B, shape, ss):
         h = h * (sc[:, :C].double().reshape(bc) + 1) + sc[:, C:].double().reshape(bc)
     ref = R.silu(h)
     assert _rel(out.float().cpu().double(), ref) < 4e-3          # one bf16 rounding of the result
+    # every element bf16(ref) or its neighbour, and only where the fp32 arithmetic can cross a rounding boundary: the floor is 8 x the
+    # same formula evaluated in fp32 on the CPU (tests/_parity.py)
+    h32 = R.group_norm(y, gg, gb, 8)
+    if ss:
+        h32 = h32 * (sc[:, :C].reshape(bc) + 1) + sc[:, C:].reshape(bc)
+    P.assert_bf16_store(out.cpu(), ref, 8.0 * P.rel(R.silu(h32), ref), f'gn_silu_apply16 C{C} B{B} {shape} ss={ss}')
 
 
 @pytest.mark.parametrize('c0,c1,C,B,shape', [(64, 64, 64, 2, (4, 16, 16)), (64, 0, 128, 1, (3, 8, 8)), (128, 128, 64, 2, (2, 8, 8)),
@@ -89,6 +96,9 @@ def test_resblock_tail_with_res_conv_bf16(c0, c1, C, B, shape):
     assert out.dtype == bf
     assert _rel(out.cpu().double(), ref) < 3e-3                         # bf16 output rounding: 2^-9 / sqrt(3) ~ 1.1e-3 rms
     assert (out.cpu().double() - ref).abs().max() < 2e-2 * ref.abs().max()
+    r32 = x.float() @ w.to(bf).float() + rb
+    ref32 = R.silu(R.group_norm(y2.float(), gg, gb, 8)) + R.layer_norm(r32, lg, lb)
+    P.assert_bf16_store(out.cpu(), ref, 8.0 * P.rel(ref32, ref), f'tail_rc16 {c0}+{c1}->{C} B{B} {shape}')
 
 
 def test_resblock_tail_with_res_conv_rejects_unserved_shapes():

@@ -5,6 +5,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import _parity as P
 from oracle import unet3d_ref as R
 
 
@@ -14,6 +15,39 @@ def _bf16r(t):
 
 def _rel(a, b):
     return ((a - b).norm() / (b.norm() + 1e-30)).item()
+
+
+def _check_stats(stats, B, ref64, ref32, what):
+    """The statistics epilogue against the fp64 conv, per (sample, group), at 8 x the conv and its sums evaluated in fp32 on the CPU
+    (tests/_parity.py assert_gn_stats); one tile = 256 output pixels, the unit a workgroup flushes."""
+    from video_diffusion_nnx_amd import ops
+    tiles = -(-ref64[0].numel() // ref64.shape[-1] // 256)
+    P.assert_gn_stats(ops.gn_stats_reduce(stats, B, 8).cpu(), ref64, ref32, tiles, what=what)
+
+
+def _check_prologue_conv(run, y1f, gamma, beta, ss, kern2, ref2, stats, bf16_out, what):
+    """A fused-prologue conv, per (frame, 16 x 16 tile), against the reference whose activation is rounded to bf16 where the kernel
+    rounds it; bound = max(2e-6, 4 x the rounding-boundary flip floor) (+ 2^-9 for a bf16 output), tests/_parity.py tile_bound.
+    run(slab) launches the conv with that statistics slab: the producer's own, then a hand-made one of y1 spread over the slots, so
+    that producer and consumer are judged separately.  y1f: the tensor the conv reads, fp64; ref2: the test's own fp64 reference of the
+    conv (activation rounded to bf16).  The flip floor is taken on the first two frames of every sample: the activation is elementwise
+    and a tile's output depends on its own frame alone, so more frames only repeat the CPU convs."""
+    C = y1f.shape[-1]
+    def act(dt):
+        h = R.group_norm(y1f.to(dt), gamma.to(dt), beta.to(dt), 8)
+        if ss is not None:
+            h = h * (ss.to(dt)[:, None, None, None, :C] + 1) + ss.to(dt)[:, None, None, None, C:]
+        return P.bf16r(R.silu(h)).double()
+    k2 = P.bf16r(kern2).double()
+    out_of = lambda a: R.conv_1kk(a[:, :2], k2, None)
+    bound, floor = P.tile_bound(act(torch.float32), act(torch.float64), out_of, bf16_out=bf16_out)
+    print(f'[prologue {what}] flip floor {floor:.3e} -> per-tile bound {bound:.3e}')
+    assert bound < 5e-3, 'a derived bound above the 5e-3 this test states would be a finding'
+    hand = P.spread_slots(P.gn_stats_slab(y1f), seed=C).reshape(-1).to(stats.device)
+    for label, slab in (('producer slab', stats), ('hand-made slab', hand)):
+        y2 = run(slab)
+        torch.cuda.synchronize()
+        P.assert_tiles(y2.float().cpu(), ref2, bound, what=f'{what}, {label}')
 
 
 CASES = [
@@ -133,10 +167,13 @@ def test_persistent_c64_conv(act_bf16, B, Fr):
     ref1 = R.conv_1kk(_bf16r(x).double(), _bf16r(kern).double(), bias.double())
     y1f = y1.float().cpu().double()
     assert _rel(y1f, ref1) < (4e-3 if act_bf16 else 2e-6)    # bf16 output: one rounding of the result
+    if act_bf16:
+        P.assert_bf16_store(y1.cpu(), ref1, P.FWD_STATED, f'conv64r B{B} F{Fr}')
     s = ops.gn_stats_reduce(stats1, B, 8).cpu()
     yg = ref1.reshape(B, -1, 8, C // 8)
     np.testing.assert_allclose(s[..., 0], yg.sum(dim=(1, 3)), rtol=2e-3, atol=5.0)       # statistics are taken before the output rounding
     np.testing.assert_allclose(s[..., 1], (yg * yg).sum(dim=(1, 3)), rtol=2e-3)
+    _check_stats(stats1, B, ref1, R.conv_1kk(_bf16r(x), _bf16r(kern), bias), f'c64 conv act_bf16={act_bf16} B{B} F{Fr}')
     gamma, beta = 1 + 0.1 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
     ss = torch.randn(B, 2 * C, generator=g) * 0.3
     kern2 = torch.randn(1, 3, 3, C, C, generator=g) / (9 * C) ** 0.5
@@ -147,6 +184,9 @@ def test_persistent_c64_conv(act_bf16, B, Fr):
     h = R.silu(h * (ss[:, None, None, None, :C].double() + 1) + ss[:, None, None, None, C:].double())
     ref2 = R.conv_1kk(_bf16r(h.float()).double(), _bf16r(kern2).double(), None)
     assert _rel(y2.float().cpu().double(), ref2) < 5e-3
+    _check_prologue_conv(lambda slab: ops.conv_forward(y1, pw2, C, mode='bf16', in_stats=slab, gamma=gamma.to(dev), beta=beta.to(dev),
+                                                       scale_shift=ss.to(dev), y_bf16=act_bf16),
+                         y1f, gamma, beta, ss, kern2, ref2, stats1, act_bf16, f'c64 conv act_bf16={act_bf16} B{B} F{Fr}')
 
 
 @pytest.mark.parametrize('concat', [True, False])
@@ -172,10 +212,12 @@ def test_persistent_c128_to_64_conv(concat):
     torch.cuda.synchronize()
     ref = R.conv_1kk(_bf16r(torch.cat((xa, xb), -1)).double(), _bf16r(kern).double(), bias.double())
     assert _rel(y.float().cpu().double(), ref) < 4e-3
+    P.assert_bf16_store(y.cpu(), ref, P.FWD_STATED, f'conv64q<128> concat={concat}')
     s = ops.gn_stats_reduce(stats, B, 8).cpu()
     yg = ref.reshape(B, -1, 8, 8)
     np.testing.assert_allclose(s[..., 0], yg.sum(dim=(1, 3)), rtol=2e-3, atol=5.0)
     np.testing.assert_allclose(s[..., 1], (yg * yg).sum(dim=(1, 3)), rtol=2e-3)
+    _check_stats(stats, B, ref, R.conv_1kk(_bf16r(torch.cat((xa, xb), -1)), _bf16r(kern), bias), f'conv64q<128> concat={concat}')
 
 
 @pytest.mark.parametrize('c,B,Fr,S', [(32, 2, 32, 64), (64, 16, 16, 32)])
@@ -198,10 +240,12 @@ def test_persistent_concat_conv_32_outputs(c, B, Fr, S):
     torch.cuda.synchronize()
     ref = R.conv_1kk(_bf16r(torch.cat((xa, xb), -1)).double(), _bf16r(kern).double(), bias.double())
     assert _rel(y.float().cpu().double(), ref) < 4e-3
+    P.assert_bf16_store(y.cpu(), ref, P.FWD_STATED, f'conv64q<{2 * c}, 32 outputs>')
     s = ops.gn_stats_reduce(stats, B, 8).cpu()
     yg = ref.reshape(B, -1, 8, 4)
     np.testing.assert_allclose(s[..., 0], yg.sum(dim=(1, 3)), rtol=2e-3, atol=5.0)
     np.testing.assert_allclose(s[..., 1], (yg * yg).sum(dim=(1, 3)), rtol=2e-3)
+    _check_stats(stats, B, ref, R.conv_1kk(_bf16r(torch.cat((xa, xb), -1)), _bf16r(kern), bias), f'conv64q<{2 * c}, 32 outputs>')
 
 
 WS_CASES = [
@@ -244,10 +288,13 @@ def test_weight_streaming_conv(case, y_bf16):
     y1f = y1.float().cpu().double()
     r1 = _rel(y1f, ref1)
     assert r1 < (4e-3 if y_bf16 else 2e-6), r1               # exact bf16 products, fp32 accumulate (+ one output rounding)
+    if y_bf16:
+        P.assert_bf16_store(y1.cpu(), ref1, P.FWD_STATED, f'conv3x3_ws {case}')
     s = ops.gn_stats_reduce(stats1, B, 8).cpu()
     yg = ref1.reshape(B, -1, 8, Cout // 8)
     np.testing.assert_allclose(s[..., 0], yg.sum(dim=(1, 3)), rtol=2e-3, atol=5.0)     # statistics are taken before the output rounding
     np.testing.assert_allclose(s[..., 1], (yg * yg).sum(dim=(1, 3)), rtol=2e-3)
+    _check_stats(stats1, B, ref1, R.conv_1kk(_bf16r(x), _bf16r(kern), bias), f'conv3x3_ws {case} y_bf16={y_bf16}')
     if not y_bf16:
         return                                               # the prologue form needs bf16 input tensors
     gamma, beta = 1 + 0.1 * torch.randn(Cout, generator=g), 0.1 * torch.randn(Cout, generator=g)
@@ -264,6 +311,9 @@ def test_weight_streaming_conv(case, y_bf16):
         ref2 = R.conv_1kk(_bf16r(R.silu(h).float()).double(), _bf16r(kern2).double(), None)
         r2 = _rel(y2.float().cpu().double(), ref2)
         assert r2 < 5e-3, (use_ss, r2)
+        _check_prologue_conv(lambda slab: ops.conv_forward(y1, pw2, 128, mode='bf16', in_stats=slab, gamma=gamma.to(dev), beta=beta.to(dev),
+                                                           scale_shift=ss.to(dev) if use_ss else None, out_stats=ops.gn_stats_zeros(B, 8, dev), y_bf16=True),
+                             y1f, gamma, beta, ss if use_ss else None, kern2, ref2, stats1, True, f'conv3x3_ws {case} use_ss={use_ss}')
 
 
 @pytest.mark.parametrize('res_bf16', [False, True])
@@ -341,6 +391,7 @@ def test_pointwise_conv_bf16(case):
     assert y.dtype == bf
     assert _rel(y.float().cpu().double(), ref) < 4e-3
     assert (y.float().cpu().double() - ref).abs().max() < 2e-2 * ref.abs().max()
+    P.assert_bf16_store(y.cpu(), ref, P.FWD_STATED, f'conv1x1_pw {case}')
 
 
 @pytest.mark.parametrize('case', PW32_CASES)
@@ -407,3 +458,5 @@ def test_weight_streaming_resampling_conv(case, y_bf16):
     assert tuple(y.shape) == tuple(ref.shape)
     r = _rel(y.float().cpu().double(), ref)
     assert r < (4e-3 if y_bf16 else 2e-6), r
+    if y_bf16:
+        P.assert_bf16_store(y.cpu(), ref, P.FWD_STATED, f'conv4x4_ws {case}')

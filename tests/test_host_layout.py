@@ -16,6 +16,10 @@ def test_library_exports_every_declared_symbol():
     hdr = open(os.path.join(ROOT, 'include', 'vdx.h')).read()
     names = set(re.findall(r'\b(vdx_[a-z0-9_]+)\s*\(', hdr))
     assert len(names) >= 20
+    # the test-facing forward forms ("Forward forms of the network") are part of what the header declares
+    assert {'vdx_attention_heads_forward', 'vdx_attention_long_forward', 'vdx_sla_heads_forward', 'vdx_resblock_tail_ex',
+            'vdx_resblock_tail_rc_head_bf16', 'vdx_final_conv_ex', 'vdx_init_conv_ex', 'vdx_resblock_scale_shift',
+            'vdx_attention_heads_scratch_bytes', 'vdx_attention_long_scratch_bytes'} <= names
     for n in sorted(names):
         assert hasattr(_lib.lib, n), f'libvdx.so does not export {n}'
     assert _lib.vdx_version() >= 1

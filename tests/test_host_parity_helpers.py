@@ -191,3 +191,195 @@ def test_helper_primitives():
     assert i == 1 and abs(w - 0.5 ** 0.5) < 1e-12 and allr.shape == (2,)
     with pytest.raises(AssertionError):
         P.exact_products_bounds(torch.tensor([1.0, 1.001]), torch.tensor([1.0, 1.0], dtype=torch.float64))      # floor too high to mean anything
+
+
+# ---- forward forms: the bounds of tests/test_gpu_forward_forms.py, tests/test_gpu_conv.py and tests/test_gpu_blocks.py bite ------------------
+# Data from the reference at the GPU tests' own shapes (tests/_forward_cases.py builds cases and bounds for both sides); one fault at a
+# time; the clean CPU evaluation passes, the fault is rejected at exactly the bound the GPU test uses.
+
+import _forward_cases as FC
+
+
+@pytest.fixture(scope='module')
+def c64_conv():
+    """test_persistent_c64_conv's plain form: (2, 32, 64, 64, 64), 3x3, 64 -> 64, bf16-rounded operands; fp64 and fp32 evaluations."""
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(2, 32, 64, 64, 64, generator=g)
+    x[1] *= 1.7
+    kern = torch.randn(1, 3, 3, 64, 64, generator=g) / (9 * 64) ** 0.5
+    bias = torch.randn(64, generator=g)
+    ref64 = R.conv_1kk(P.bf16r(x).double(), P.bf16r(kern).double(), bias.double())
+    ref32 = R.conv_1kk(P.bf16r(x), P.bf16r(kern), bias)
+    return ref64, ref32
+
+
+def test_truncating_store_and_scaled_tile_row_are_rejected(c64_conv):
+    ref64, ref32 = c64_conv
+    clean = ref32.to(torch.bfloat16)
+    P.assert_bf16_store(clean, ref64, P.FWD_STATED, 'clean fp32 evaluation, rounded once')
+    trunc = P.bf16_trunc(ref32).to(torch.bfloat16)
+    assert P.rel(trunc, ref64) < 4e-3, 'the fault must be one the global rel-L2 of the test cannot see'
+    with pytest.raises(AssertionError, match='differ'):
+        P.assert_bf16_store(trunc, ref64, P.FWD_STATED, 'truncated')
+    # one 16-pixel row of one 16 x 16 tile scaled by 0.9: what a wrong halo row does
+    bad = ref32.clone()
+    bad[1, 7, 16 + 5, 32:48, :] *= 0.9
+    bad = bad.to(torch.bfloat16)
+    assert P.rel(bad, ref64) < 4e-3
+    with pytest.raises(AssertionError, match='ulp'):
+        P.assert_bf16_store(bad, ref64, P.FWD_STATED, 'one tile row scaled')
+
+
+def test_scaled_tile_row_behind_a_prologue_is_rejected(c64_conv):
+    """The prologue form of test_persistent_c64_conv: per-(frame, tile) rel-L2 at max(2e-6, 4 x the flip floor)."""
+    ref64, _ = c64_conv
+    g = torch.Generator().manual_seed(12)
+    y1 = P.bf16r(ref64[:, :4].float())                                 # 4 frames are enough for the CPU proof
+    C = 64
+    gamma, beta = 1 + 0.1 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    ss = torch.randn(2, 2 * C, generator=g) * 0.3
+    kern2 = P.bf16r(torch.randn(1, 3, 3, C, C, generator=g) / (9 * C) ** 0.5)
+    act = lambda dt: P.bf16r(R.silu(R.group_norm(y1.to(dt), gamma.to(dt), beta.to(dt), 8) * (ss.to(dt)[:, None, None, None, :C] + 1) + ss.to(dt)[:, None, None, None, C:]))
+    out_of = lambda a: R.conv_1kk(a.double(), kern2.double(), None)
+    a64, a32 = act(torch.float64), act(torch.float32).double()
+    bound, floor = P.tile_bound(a32, a64, out_of)
+    print(f'prologue tile bound {bound:.3e} (flip floor {floor:.3e})')
+    assert bound < 5e-3, 'a derived bound above what the test states would be a finding'
+    ref2 = out_of(a64)
+    clean = R.conv_1kk(a32.float(), kern2, None)
+    P.assert_tiles(clean, ref2, bound, what='clean fp32 evaluation')
+    bad = clean.clone()
+    bad[1, 2, 16 + 5, 32:48, :] *= 0.9
+    assert P.rel(bad, ref2) < 5e-3
+    with pytest.raises(AssertionError, match='tile'):
+        P.assert_tiles(bad, ref2, bound, what='one tile row scaled')
+    # the same form with a bf16 output: one rounding of the result is within the 2^-9 the bound gains, the scaled row is not
+    bound16, _ = P.tile_bound(a32, a64, out_of, bf16_out=True)
+    assert abs(bound16 - bound - P.BF16_ROUNDING) < 1e-12
+    worst = P.assert_tiles(clean.to(torch.bfloat16), ref2, bound16, what='clean fp32 evaluation, bf16 output')
+    assert worst > bound, 'a bf16 output does not fit the fp32-output bound: the 2^-9 term is needed'
+    with pytest.raises(AssertionError, match='tile'):
+        P.assert_tiles(bad.to(torch.bfloat16), ref2, bound16, what='one tile row scaled, bf16 output')
+
+
+def test_tile_statistics_credited_to_the_neighbouring_sample_are_rejected(c64_conv):
+    ref64, ref32 = c64_conv
+    B, tiles = 2, 32 * 16                                               # 16 tiles of 16 x 16 per frame
+    s1, _, s2 = P.gn_sums(ref32, 8, torch.float32)
+    clean = torch.stack((s1, s2), -1).double()
+    P.assert_gn_stats(clean, ref64, ref32, tiles, what='clean fp32 evaluation')
+    # the last tile of sample 0 flushed into sample 1's sums (the per-sample flush of register-resident sums at a sample boundary)
+    t1, _, t2 = P.gn_sums(ref64[0:1, 31:, 48:, 48:], 8)
+    bad = clean.clone()
+    bad[1, :, 0] += t1[0]; bad[1, :, 1] += t2[0]
+    bad[0, :, 0] -= t1[0]; bad[0, :, 1] -= t2[0]
+    r2 = (ref64.reshape(2, -1, 8, 8) ** 2).sum(dim=(1, 3))
+    worst = ((bad[..., 1] - r2).abs() / r2).max().item()
+    print(f'one tile in the wrong sample moves sum y^2 by {worst:.2e}')
+    assert worst < 2.2e-3, 'the fault must be one rtol = 2e-3 misses or barely sees'
+    with pytest.raises(AssertionError, match='sum'):
+        P.assert_gn_stats(bad, ref64, ref32, tiles, what='one tile credited to the wrong sample')
+    # a bound that could not see one tile is refused
+    with pytest.raises(AssertionError, match='share'):
+        P.assert_gn_stats(clean, ref64, ref32, 10 ** 6, what='too many tiles for the bound')
+
+
+def test_consumer_reading_slot_0_only_and_unwritten_pixel_pass_are_rejected():
+    C, B, shape = FC.TAIL16[4]                                          # the multi-pass case: 35 pixel groups over 32 workgroups
+    c = FC.tail_case(C, B, shape, True)
+    slab = c['slab']
+    assert (slab[:, 1:].abs().sum() > 0) and torch.allclose(slab.sum(1), P.gn_stats_slab(c['y2'])[:, 0], rtol=1e-12)
+    clean = c['ref32'].to(torch.bfloat16)
+    P.assert_bf16_store(clean, c['ref64'], c['store_floor'], 'clean fp32 evaluation')
+    # statistics from slot 0 alone
+    n = c['y2'][0].numel() // 8
+    s0 = slab[:, 0]
+    mean = s0[..., 0] / n
+    rstd = torch.rsqrt((s0[..., 1] / n - mean * mean).clamp_min(0) + R.NORM_EPS)
+    bad = FC.tail_formula(c['y2'], c['r'], *c['par'], torch.float32, (mean, rstd)).to(torch.bfloat16)
+    with pytest.raises(AssertionError, match='ulp'):
+        P.assert_bf16_store(bad, c['ref64'], c['store_floor'], 'slot 0 only')
+    # the second pixel pass (pixels 1024..1099 of every sample) never written: NaN-filled output, or stale zeros
+    for fill, why in ((float('nan'), 'non-finite'), (0.0, 'ulp')):
+        bad = clean.clone().reshape(B, -1, C)
+        bad[:, 32 * 32:] = fill
+        with pytest.raises(AssertionError, match=why):
+            P.assert_bf16_store(bad.reshape(clean.shape), c['ref64'], c['store_floor'], 'second pass unwritten')
+    # the fp32-output form at its bound
+    m = FC.tail_case(*FC.TAIL_MIXED[0], False)
+    P.assert_exact_products(m['ref32'], m['ref64'], m['bound'], m['sl'], m['sb'], None, 'clean mixed tail')
+    s0 = m['slab'][:, 0]
+    n = m['y2'][0].numel() // 8
+    mean = s0[..., 0] / n
+    rstd = torch.rsqrt((s0[..., 1] / n - mean * mean).clamp_min(0) + R.NORM_EPS)
+    with pytest.raises(AssertionError, match='rel-L2'):
+        P.assert_exact_products(FC.tail_formula(m['y2'], m['r'], *m['par'], torch.float32, (mean, rstd)), m['ref64'], m['bound'], m['sl'], m['sb'], None, 'slot 0 only')
+
+
+def test_neighbouring_head_and_unmasked_keys_are_rejected():
+    shape = FC.ATTN_HEADS_TEMPORAL[1]                                   # (2, 10, 5, 7, 512): 10 of 16 key slots are real
+    B, Fr, H, W, C = shape
+    c = FC.attn_heads_case(shape, True, True, False)
+    og, nseq = c['og'], c['nseq']
+    P.assert_groups(og(c['oe']), og(c['o64']), (nseq, 8), c['bound_o'], 'clean emulation')
+    P.assert_groups(FC.seq_groups(c['ye'], True), FC.seq_groups(c['y64'], True), (nseq,), c['bound_y'], 'clean emulation, y')
+    # one (sequence, head) of o taken from the neighbouring head
+    bad = og(c['oe']).clone()
+    bad[37, 3] = bad[37, 4]
+    assert P.rel(bad, og(c['o64'])) < 8e-2, 'one of 560 groups: the tensor as a whole barely moves'
+    with pytest.raises(AssertionError, match='group'):
+        P.assert_groups(bad, og(c['o64']), (nseq, 8), c['bound_o'], 'neighbouring head')
+    # keys past L left unmasked: the 6 padding slots of the 16-token tile take part with k = v = bias
+    ob, yb = P.attention_block_fwd(c['x'], *c['w'], B, Fr, H, W, True, emulate=True, round_out=True, unmasked_pad=6)
+    with pytest.raises(AssertionError, match='group'):
+        P.assert_groups(og(ob), og(c['o64']), (nseq, 8), c['bound_o'], 'unmasked padding keys')
+    with pytest.raises(AssertionError, match='group'):
+        P.assert_groups(FC.seq_groups(yb, True), FC.seq_groups(c['y64'], True), (nseq,), c['bound_y'], 'unmasked padding keys, y')
+    # SLA: one (frame, head) from the neighbouring head
+    s = FC.sla_heads_case(FC.SLA_HEADS[1], True)
+    P.assert_groups(s['og'](s['oe']), s['og'](s['o64']), (s['NF'], 8), s['bound_o'], 'clean SLA emulation')
+    bad = s['og'](s['oe']).clone()
+    bad[40, 2] = bad[40, 1]
+    with pytest.raises(AssertionError, match='group'):
+        P.assert_groups(bad, s['og'](s['o64']), (s['NF'], 8), s['bound_o'], 'SLA neighbouring head')
+
+
+def test_scale_shift_row_of_the_wrong_sample_is_rejected():
+    c = FC.ss_case(96, 9)                                               # sample 8 opens the second group of 8
+    for i in range(len(c['layers'])):
+        bound, sb, _ = c['b_ss'][i]
+        clean = R.layer_norm(R.silu(c['temb']) @ c['layers'][i]['W'] + c['layers'][i]['b'], c['layers'][i]['g'], c['layers'][i]['be'])
+        P.assert_exact_products(clean, c['ss64'][i], bound, c['sl'], sb, None, f'clean layer {i}')
+        bad = clean.clone()
+        bad[8] = clean[0]
+        with pytest.raises(AssertionError, match='rel-L2'):
+            P.assert_exact_products(bad, c['ss64'][i], bound, c['sl'], sb, None, f'layer {i}: row 8 = row 0')
+        # ... and by the per-sample check alone, where a generous global bound would not see one row of nine
+        with pytest.raises(AssertionError, match=r'slice\(s\) over their bound, first sample8'):
+            P.assert_exact_products(bad, c['ss64'][i], 10.0, c['sl'], sb, None, f'layer {i}: row 8 = row 0, per sample only')
+
+
+def test_forward_closed_forms_match_the_oracle():
+    """attention_block_fwd / sla_block_fwd with emulate=False are the oracle's MultiheadAttention / SpatialLinearAttention + residual."""
+    g = torch.Generator().manual_seed(21)
+    for (B, Fr, H, W, C), temporal in (((2, 5, 2, 3, 64), True), ((1, 2, 3, 3, 32), False)):
+        x = torch.randn(B, Fr, H, W, C, generator=g, dtype=torch.float64)
+        w = [t.double() for t in FC.mha_weights(C, g)]
+        o, y = P.attention_block_fwd(x, *w, B, Fr, H, W, temporal)
+        p = FC.mha_oracle_params(*w)
+        if temporal:
+            xt = x.permute(0, 2, 3, 1, 4).reshape(B, H * W, Fr, C)
+            ref = R.multihead_attention(p, 'a', xt, 32).reshape(B, H, W, Fr, C).permute(0, 3, 1, 2, 4) + x
+        else:
+            ref = R.multihead_attention(p, 'a', x.reshape(B, Fr, H * W, C), 32).reshape(x.shape) + x
+        assert P.rel(y, ref) < 1e-12
+        assert P.seq_head_groups(o, B, Fr, H * W, temporal).shape == (B * (H * W if temporal else Fr), 8, (Fr if temporal else H * W) * 32)
+    B, Fr, H, W, C = 2, 2, 3, 5, 48
+    x = torch.randn(B, Fr, H, W, C, generator=g, dtype=torch.float64)
+    wq, wk, wv = [torch.randn(C, 256, generator=g, dtype=torch.float64) for _ in range(3)]
+    wo = torch.randn(256, C, generator=g, dtype=torch.float64) / 16
+    _, y = P.sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W)
+    p = {'a.q.kernel': wq[None], 'a.k.kernel': wk[None], 'a.v.kernel': wv[None], 'a.to_out.kernel': wo[None]}
+    assert P.rel(y, R.spatial_linear_attention(p, 'a', x, 8) + x) < 1e-12
+    if P.have_e4m3():
+        assert torch.equal(P.e4m3r(torch.tensor([0.3, 17.0, 500.0])), torch.tensor([0.3125, 16.0, 448.0]))

@@ -93,3 +93,22 @@ vdx_attention_forward_bf16 = _sig('vdx_attention_forward_bf16', c_int, [c_void_p
 vdx_sla_forward_bf16 = _sig('vdx_sla_forward_bf16', c_int, [c_void_p] * 7 + [c_int] * 6 + [c_void_p])
 vdx_sla_workspace_bytes = _sig('vdx_sla_workspace_bytes', c_size_t, [c_int] * 4)
 vdx_sla_forward = _sig('vdx_sla_forward', c_int, [c_int] + [c_void_p] * 7 + [c_int] * 6 + [c_void_p])
+
+
+# forward forms of the network (vdx.h: "Forward forms of the network (test-facing)")
+class SsLayer(C.Structure):
+    _fields_ = [('w_off', c_long), ('b_off', c_long), ('g_off', c_long), ('be_off', c_long), ('out_off', c_long), ('n', c_int), ('pad_', c_int)]
+
+
+vdx_attention_heads_scratch_bytes = _sig('vdx_attention_heads_scratch_bytes', c_size_t, [c_int] * 4)
+vdx_attention_long_scratch_bytes = _sig('vdx_attention_long_scratch_bytes', c_size_t, [c_int] * 5)
+vdx_attention_heads_forward = _sig('vdx_attention_heads_forward', c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 5 + [c_size_t] + [c_int] * 7 + [c_void_p])
+vdx_attention_long_forward = _sig('vdx_attention_long_forward', c_int, [c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 5 + [c_size_t] + [c_int] * 6 + [c_void_p])
+vdx_sla_heads_forward = _sig('vdx_sla_heads_forward', c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 5 + [c_size_t] + [c_int] * 5 + [c_void_p])
+vdx_resblock_tail_ex = _sig('vdx_resblock_tail_ex', c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                                            c_int, c_int, c_long, c_void_p])
+vdx_resblock_tail_rc_head_bf16 = _sig('vdx_resblock_tail_rc_head_bf16', c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_int] +
+                                      [c_void_p] * 3 + [c_int, c_long, c_void_p])
+vdx_final_conv_ex = _sig('vdx_final_conv_ex', c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_long, c_int, c_int, c_void_p])
+vdx_init_conv_ex = _sig('vdx_init_conv_ex', c_int, [c_int] + [c_void_p] * 4 + [c_int] * 8 + [c_void_p])
+vdx_resblock_scale_shift = _sig('vdx_resblock_scale_shift', c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p])

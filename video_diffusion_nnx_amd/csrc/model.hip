@@ -416,6 +416,49 @@ static hipError_t run_res(const Fwd& f, const ResP& r, const float* x0, int c0, 
     return launch_resblock_tail(t, f.st);
 }
 
+// The attention block as the network runs it.  `a` comes with tensors, weights, geometry (L, nseq, strides), io_bf16 and fp8_core filled in;
+// NF / Fr / H / W describe the same rows as a channel-last tensor for the 1x1 convs; scratch = the per-head output of the heads path or
+// qkv + o of the long path.  The ONE place the route is decided: model_forward passes ATTN_ANY, the test-facing entry points of vdx.h
+// ("Forward forms of the network") name the route they are about and get hipErrorInvalidValue where the network would not take it.
+hipError_t attention_block_forward(int mode, AttnArgs a, bool temporal, int NF, int Fr, int H, int W, void* scratch, size_t scratch_bytes,
+                                   int require, hipStream_t st) {
+    const int HD = a.heads * 32;
+    const size_t rows = (size_t)NF * H * W;
+    auto conv1x1 = [&](const float* x0, int c0, int x0_bf16, const void* wp, const float* bias, float* y, int cout, int y_bf16, const float* res, int res_bf16) {
+        ConvArgs c;
+        memset(&c, 0, sizeof(c));
+        c.x0 = x0; c.C0 = c0; c.x0_bf16 = x0_bf16; c.wp = wp; c.bias = bias; c.y = y; c.Cout = cout; c.y_bf16 = y_bf16;
+        c.res = res; c.res_bf16 = res_bf16;
+        c.NF = NF; c.F = Fr; c.H = H; c.W = W; c.kind = 0; c.kh = c.kw = 1; c.stride = 1; c.pad = 0;
+        return launch_conv(mode, c, st);
+    };
+    if (a.L > 64) {
+        // long sequences (spatial attention of a bottleneck larger than 8 x 8): q|k|v projection and out-projection (+ bias + residual)
+        // as 1x1 convs around the fp32 core of attention.hip; token-major rows = the channel-last tensor as it is
+        if (temporal) return hipErrorInvalidValue;                       // (a temporal axis of more than 64 frames is not served)
+        if (require != ATTN_ANY && require != ATTN_LONG) return hipErrorInvalidValue;
+        if (!scratch || rows * 4 * HD * sizeof(float) > scratch_bytes) return hipErrorInvalidValue;
+        float* qkv = reinterpret_cast<float*>(scratch);
+        float* o = qkv + rows * 3 * HD;
+        hipError_t e = conv1x1(a.x, a.C, a.io_bf16, a.wqkv, a.bqkv, qkv, 3 * HD, 0, nullptr, 0);
+        if (e != hipSuccess) return e;
+        e = launch_attention_long_core(qkv, o, a.nseq, a.L, a.heads, a.scale, st);
+        if (e != hipSuccess) return e;
+        return conv1x1(o, HD, 0, a.wo, a.bo, a.y, a.C, a.io_bf16, a.x, a.io_bf16);
+    }
+    // wide levels in bf16 mode: per-head kernel (weights resident in LDS) + the out-projection as a 1x1 conv
+    if (mode == MODE_BF16 && (temporal ? a.L <= 16 : a.L <= 64) && a.heads == 8 && a.C >= 256 && a.C % 128 == 0 &&
+        (size_t)96 * (a.C * 2 + 32) <= 160 * 1024 && scratch && rows * a.heads * 64 <= scratch_bytes) {
+        if (require != ATTN_ANY && require != ATTN_HEADS) return hipErrorInvalidValue;
+        a.oscratch = scratch;
+        hipError_t e = launch_attention_heads(a, st);
+        if (e != hipSuccess) return e;
+        return conv1x1(reinterpret_cast<const float*>(scratch), HD, 1, a.wo, a.bo, a.y, a.C, a.io_bf16, a.x, a.io_bf16);
+    }
+    if (require != ATTN_ANY) return hipErrorInvalidValue;
+    return launch_attention(mode, a, st);
+}
+
 static hipError_t run_attn(const Fwd& f, const AttnP& ap, const float* x, float* y, int lvl, bool temporal) {
     const Model* m = f.m;
     const long S = m->cfg.image_size >> lvl, hw = S * S, Fr = m->cfg.num_frames;
@@ -428,44 +471,28 @@ static hipError_t run_attn(const Fwd& f, const AttnP& ap, const float* x, float*
     else { a.L = (int)hw; a.nseq = f.B * Fr; a.inner = 1; a.inner_stride = 0; a.outer_stride = hw * ap.C; a.tok_stride = ap.C; }
     a.io_bf16 = f.a16;
     a.fp8_core = (m->attn_fp8 && m->mode == MODE_BF16) ? 1 : 0;
-    if (a.L > 64) {
-        // long sequences (spatial attention of a bottleneck larger than 8 x 8): q|k|v projection and out-projection (+ bias + residual)
-        // as 1x1 convs around the fp32 core of attention.hip; token-major rows = the channel-last tensor as it is
-        if (temporal) return hipErrorInvalidValue;                       // (a temporal axis of more than 64 frames is not served)
-        const int HD = a.heads * 32;
-        float* qkv = reinterpret_cast<float*>(f.sla_ws);
-        float* o = qkv + (size_t)f.B * Fr * hw * 3 * HD;
-        ConvArgs p;
-        memset(&p, 0, sizeof(p));
-        p.x0 = x; p.C0 = ap.C; p.x0_bf16 = f.a16; p.wp = f.pk + ap.pk_qkv; p.bias = reinterpret_cast<const float*>(f.pk + ap.pk_bqkv);
-        p.y = qkv; p.Cout = 3 * HD;
-        p.NF = f.B * (int)Fr; p.F = (int)Fr; p.H = (int)S; p.W = (int)S; p.kind = 0; p.kh = p.kw = 1; p.stride = 1; p.pad = 0;
-        hipError_t e = launch_conv(m->mode, p, f.st);
-        if (e != hipSuccess) return e;
-        e = launch_attention_long_core(qkv, o, a.nseq, a.L, a.heads, a.scale, f.st);
+    return attention_block_forward(m->mode, a, temporal, f.B * (int)Fr, (int)Fr, (int)S, (int)S, f.sla_ws, m->sla_ws_bytes_per_sample * f.B, ATTN_ANY, f.st);
+}
+
+// The SpatialLinearAttention block as the network runs it (see attention_block_forward): a.workspace serves the generic kernels, scratch
+// receives the per-head output of the heads path (model_forward passes the same buffer for both).
+hipError_t sla_block_forward(int mode, SlaArgs a, int Fr, int H, int W, void* scratch, size_t scratch_bytes, int require, hipStream_t st) {
+    // wide levels in bf16 mode: per-head kernel (weights resident in LDS) + to_out as a 1x1 conv
+    if (mode == MODE_BF16 && a.heads == 8 && a.C >= 256 && a.C % 128 == 0 && a.N % 16 == 0 &&
+        (size_t)96 * (a.C * 2 + 32) <= 160 * 1024 && scratch && (size_t)a.NF * a.N * a.heads * 64 <= scratch_bytes) {
+        if (require != ATTN_ANY && require != ATTN_HEADS) return hipErrorInvalidValue;
+        hipError_t e = launch_sla_heads(a, scratch, st);
         if (e != hipSuccess) return e;
         ConvArgs c;
         memset(&c, 0, sizeof(c));
-        c.x0 = o; c.C0 = HD; c.wp = f.pk + ap.pk_o; c.bias = f.p + ap.o_b; c.y = y; c.Cout = ap.C; c.y_bf16 = f.a16;
-        c.res = x; c.res_bf16 = f.a16;
-        c.NF = f.B * (int)Fr; c.F = (int)Fr; c.H = (int)S; c.W = (int)S; c.kind = 0; c.kh = c.kw = 1; c.stride = 1; c.pad = 0;
-        return launch_conv(m->mode, c, f.st);
+        c.x0 = reinterpret_cast<const float*>(scratch); c.C0 = a.heads * 32; c.x0_bf16 = 1;
+        c.wp = a.wo; c.y = a.y; c.Cout = a.C; c.y_bf16 = a.io_bf16;
+        c.res = a.x; c.res_bf16 = a.io_bf16;
+        c.NF = a.NF; c.F = Fr; c.H = H; c.W = W; c.kind = 0; c.kh = c.kw = 1; c.stride = 1; c.pad = 0;
+        return launch_conv(mode, c, st);
     }
-    // wide levels in bf16 mode: per-head kernel (weights resident in LDS) + the out-projection as a 1x1 conv
-    if (m->mode == MODE_BF16 && (temporal ? a.L <= 16 : a.L <= 64) && a.heads == 8 && ap.C >= 256 && ap.C % 128 == 0 &&
-        (size_t)96 * (ap.C * 2 + 32) <= 160 * 1024 && (size_t)Fr * S * S * a.heads * 64 <= m->sla_ws_bytes_per_sample) {
-        a.oscratch = f.sla_ws;
-        hipError_t e = launch_attention_heads(a, f.st);
-        if (e != hipSuccess) return e;
-        ConvArgs c;
-        memset(&c, 0, sizeof(c));
-        c.x0 = reinterpret_cast<const float*>(f.sla_ws); c.C0 = a.heads * 32; c.x0_bf16 = 1;
-        c.wp = f.pk + ap.pk_o; c.bias = f.p + ap.o_b; c.y = y; c.Cout = ap.C; c.y_bf16 = f.a16;
-        c.res = x; c.res_bf16 = f.a16;
-        c.NF = f.B * (int)Fr; c.F = (int)Fr; c.H = (int)S; c.W = (int)S; c.kind = 0; c.kh = c.kw = 1; c.stride = 1; c.pad = 0;
-        return launch_conv(m->mode, c, f.st);
-    }
-    return launch_attention(m->mode, a, f.st);
+    if (require != ATTN_ANY) return hipErrorInvalidValue;
+    return launch_sla(mode, a, st);
 }
 
 static hipError_t run_sla(const Fwd& f, const SlaP& sp, const float* x, float* y, int lvl) {
@@ -476,20 +503,7 @@ static hipError_t run_sla(const Fwd& f, const SlaP& sp, const float* x, float* y
     a.x = x; a.y = y; a.wq = f.pk + sp.pk[0]; a.wk = f.pk + sp.pk[1]; a.wv = f.pk + sp.pk[2]; a.wo = f.pk + sp.pk_o;
     a.workspace = f.sla_ws; a.C = sp.C; a.heads = m->cfg.attn_heads; a.NF = f.B * m->cfg.num_frames; a.N = S * S;
     a.io_bf16 = f.a16;
-    // wide levels in bf16 mode: per-head kernel (weights resident in LDS) + to_out as a 1x1 conv
-    if (m->mode == MODE_BF16 && a.heads == 8 && sp.C >= 256 && sp.C % 128 == 0 && a.N % 16 == 0 &&
-        (size_t)96 * (sp.C * 2 + 32) <= 160 * 1024 && (size_t)m->cfg.num_frames * a.N * a.heads * 64 <= m->sla_ws_bytes_per_sample) {
-        hipError_t e = launch_sla_heads(a, f.sla_ws, f.st);
-        if (e != hipSuccess) return e;
-        ConvArgs c;
-        memset(&c, 0, sizeof(c));
-        c.x0 = reinterpret_cast<const float*>(f.sla_ws); c.C0 = a.heads * 32; c.x0_bf16 = 1;
-        c.wp = f.pk + sp.pk_o; c.y = y; c.Cout = sp.C; c.y_bf16 = f.a16;
-        c.res = x; c.res_bf16 = f.a16;
-        c.NF = a.NF; c.F = m->cfg.num_frames; c.H = S; c.W = S; c.kind = 0; c.kh = c.kw = 1; c.stride = 1; c.pad = 0;
-        return launch_conv(m->mode, c, f.st);
-    }
-    return launch_sla(m->mode, a, f.st);
+    return sla_block_forward(m->mode, a, m->cfg.num_frames, S, S, f.sla_ws, m->sla_ws_bytes_per_sample * f.B, ATTN_ANY, f.st);
 }
 
 static hipError_t run_resample(const Fwd& f, const Level& L, const float* x, float* y, int lvl_in, bool up) {

@@ -293,6 +293,141 @@ int vdx_sla_forward_bf16(const void* x_bf16, void* y_bf16, const void* wq_packed
     return VDX_OK;
 }
 
+// ---- forward forms of the network (vdx.h: "Forward forms of the network"): the compositions and flags model.hip sets ----------------
+
+size_t vdx_attention_heads_scratch_bytes(int batch, int frames, int h, int w) { return (size_t)batch * frames * h * w * 8 * 32 * 2; }
+size_t vdx_attention_long_scratch_bytes(int batch, int frames, int h, int w, int heads) {
+    return (size_t)batch * frames * h * w * heads * 32 * 4 * sizeof(float);
+}
+
+static void fill_attn_geometry(vdx::AttnArgs& a, int batch, int frames, int h, int w, int c, int temporal) {
+    const long hw = (long)h * w;
+    a.scale = 1.0f / sqrtf(32.0f);
+    if (temporal) {
+        a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.inner_stride = c; a.outer_stride = (long)frames * hw * c; a.tok_stride = hw * c;
+    } else {
+        a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.inner_stride = 0; a.outer_stride = hw * c; a.tok_stride = c;
+    }
+}
+
+int vdx_attention_heads_forward(const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv, const void* wo_packed,
+                                const float* bo, void* o_scratch, size_t o_scratch_bytes, int batch, int frames, int h, int w, int c,
+                                int temporal, int fp8_core, void* stream) {
+    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo || !o_scratch) VDX_FAIL(VDX_ERR_INVALID, "attention_heads: null tensor");
+    if (batch < 1 || frames < 1 || h < 1 || w < 1 || c < 8 || c % 8 || c > 1024) VDX_FAIL(VDX_ERR_INVALID, "attention_heads: bad geometry");
+    vdx::AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
+    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = 8;
+    fill_attn_geometry(a, batch, frames, h, w, c, temporal);
+    a.fp8_core = fp8_core ? 1 : 0;
+    const hipError_t e = vdx::attention_block_forward(VDX_MODE_BF16, a, temporal != 0, batch * frames, frames, h, w, o_scratch, o_scratch_bytes,
+                                                      vdx::ATTN_HEADS, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) VDX_FAIL(VDX_ERR_INVALID, "attention_heads: the network does not run this shape on the per-head kernel");
+    VDX_HIP(e);
+    return VDX_OK;
+}
+
+int vdx_attention_long_forward(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                               const void* wo_packed, const float* bo, void* scratch, size_t scratch_bytes, int batch, int frames, int h,
+                               int w, int c, int heads, void* stream) {
+    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo || !scratch) VDX_FAIL(VDX_ERR_INVALID, "attention_long: null tensor");
+    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
+    if (io_bf16 && mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "attention_long: bf16 tensors need VDX_MODE_BF16");
+    if (batch < 1 || frames < 1 || h < 1 || w < 1 || heads < 1 || c % (io_bf16 ? 8 : 4) || c > 1024) VDX_FAIL(VDX_ERR_INVALID, "attention_long: bad geometry");
+    vdx::AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
+    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = heads;
+    fill_attn_geometry(a, batch, frames, h, w, c, 0);
+    const hipError_t e = vdx::attention_block_forward(mode, a, false, batch * frames, frames, h, w, scratch, scratch_bytes, vdx::ATTN_LONG, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) VDX_FAIL(VDX_ERR_INVALID, "attention_long: needs more than 64 tokens per frame and vdx_attention_long_scratch_bytes of scratch");
+    VDX_HIP(e);
+    return VDX_OK;
+}
+
+int vdx_sla_heads_forward(const void* x, void* y, int io_bf16, const void* wq_packed, const void* wk_packed, const void* wv_packed,
+                          const void* wo_packed, void* o_scratch, size_t o_scratch_bytes, int batch, int frames, int h, int w, int c,
+                          void* stream) {
+    if (!x || !y || !wq_packed || !wk_packed || !wv_packed || !wo_packed || !o_scratch) VDX_FAIL(VDX_ERR_INVALID, "sla_heads: null tensor");
+    if (batch < 1 || frames < 1 || h < 1 || w < 1 || c < 8 || c % 8 || c > 1024) VDX_FAIL(VDX_ERR_INVALID, "sla_heads: bad geometry");
+    vdx::SlaArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
+    a.wq = wq_packed; a.wk = wk_packed; a.wv = wv_packed; a.wo = wo_packed;
+    a.C = c; a.heads = 8; a.NF = batch * frames; a.N = h * w;
+    const hipError_t e = vdx::sla_block_forward(VDX_MODE_BF16, a, frames, h, w, o_scratch, o_scratch_bytes, vdx::ATTN_HEADS, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) VDX_FAIL(VDX_ERR_INVALID, "sla_heads: the network does not run this shape on the per-head kernel");
+    VDX_HIP(e);
+    return VDX_OK;
+}
+
+int vdx_resblock_tail_ex(const void* y2, int y2_bf16, const void* r, int r_bf16, void* out, int out_bf16, const double* stats,
+                         const float* gn_gamma, const float* gn_beta, int groups, const float* ln_gamma, const float* ln_beta, int c,
+                         int batch, long pix_per_sample, void* stream) {
+    if (!y2 || !r || !out || !stats || !gn_gamma || !gn_beta || !ln_gamma || !ln_beta) VDX_FAIL(VDX_ERR_INVALID, "tail: null tensor");
+    if (c % 4 || c > 1024 || groups <= 0 || groups > 32 || c % groups || batch < 1 || pix_per_sample < 1) VDX_FAIL(VDX_ERR_INVALID, "tail: bad channels/groups");
+    if ((y2_bf16 || r_bf16 || out_bf16) && c % 8) VDX_FAIL(VDX_ERR_INVALID, "tail: bf16 tensors need c % 8 == 0");
+    vdx::TailArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y2 = (const float*)y2; a.r = (const float*)r; a.out = (float*)out;
+    a.y2_bf16 = y2_bf16 ? 1 : 0; a.r_bf16 = r_bf16 ? 1 : 0; a.out_bf16 = out_bf16 ? 1 : 0;
+    a.stats = stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.groups = groups;
+    a.ln_gamma = ln_gamma; a.ln_beta = ln_beta; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
+    VDX_HIP(vdx::launch_resblock_tail(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_resblock_tail_rc_head_bf16(const void* y2, const void* x0, const void* x1, int c0, int c1, const void* rc_w_packed,
+                                   const float* rc_bias, const double* stats, const float* gn_gamma, const float* gn_beta, int groups,
+                                   const float* ln_gamma, const float* ln_beta, int c, const float* fin_w, const float* fin_b,
+                                   float* fin_out, int batch, long pix_per_sample, void* stream) {
+    if (!y2 || !x0 || !x1 || !rc_w_packed || !rc_bias || !stats || !gn_gamma || !gn_beta || !ln_gamma || !ln_beta || !fin_w || !fin_b || !fin_out)
+        VDX_FAIL(VDX_ERR_INVALID, "tail_rc_head: null tensor");
+    if (c1 != c0 || batch < 1 || groups <= 0 || groups > 32 || c % groups || !((c0 + c1 == 128 && c == 64) || (c0 + c1 == 64 && c == 32)) ||
+        !vdx::tail_rc16_supported(c0 + c1, c0, c, pix_per_sample))
+        VDX_FAIL(VDX_ERR_INVALID, "tail_rc_head: shape not served");
+    vdx::TailArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y2 = (const float*)y2; a.y2_bf16 = 1; a.out_bf16 = 1; a.r_bf16 = 1;
+    a.stats = stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.groups = groups;
+    a.ln_gamma = ln_gamma; a.ln_beta = ln_beta; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
+    a.x0 = (const float*)x0; a.x1 = (const float*)x1; a.C0 = c0; a.C1 = c1; a.rc_w = rc_w_packed; a.rc_b = rc_bias;
+    a.fin_w = fin_w; a.fin_b = fin_b; a.fin_out = fin_out;
+    VDX_HIP(vdx::launch_resblock_tail(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_final_conv_ex(const void* x, int x_bf16, const float* kernel, const float* bias, float* y, long npix, int d, int cout,
+                      void* stream) {
+    if (!x || !kernel || !bias || !y || npix < 1 || cout < 1 || d % (x_bf16 ? 8 : 4)) VDX_FAIL(VDX_ERR_INVALID, "final_conv: bad argument");
+    VDX_HIP(vdx::launch_final_conv((const float*)x, kernel, bias, y, npix, d, cout, x_bf16 ? 1 : 0, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_init_conv_ex(int mode, const float* x, const float* kernel, const float* bias, void* y, int y_bf16, int batch, int cin,
+                     int frames, int h, int w, int cout, int k, void* stream) {
+    if (!x || !kernel || !bias || !y) VDX_FAIL(VDX_ERR_INVALID, "init_conv: null tensor");
+    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "init_conv: bad mode");
+    if (k < 1 || k > 15 || !(k & 1) || cin < 1 || cin > 8 || cout % 4) VDX_FAIL(VDX_ERR_INVALID, "init_conv: bad kernel size / channels");
+    if (y_bf16 && mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "init_conv: a bf16 output needs VDX_MODE_BF16");
+    VDX_HIP(vdx::launch_init_conv_mode(mode, x, kernel, bias, (float*)y, batch, cin, frames, h, w, cout, k, y_bf16 ? 1 : 0, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+static_assert(sizeof(vdx_ss_layer) == sizeof(vdx::SsLayer) && offsetof(vdx_ss_layer, n) == offsetof(vdx::SsLayer, n) &&
+              offsetof(vdx_ss_layer, out_off) == offsetof(vdx::SsLayer, out_off), "vdx_ss_layer mirrors SsLayer");
+
+int vdx_resblock_scale_shift(const float* params, const float* temb, const vdx_ss_layer* layers_dev, int nlayers, float* ss, float* lin,
+                             int temb_dim, int batch, int max_n, void* stream) {
+    if (!params || !temb || !layers_dev || !ss || !lin) VDX_FAIL(VDX_ERR_INVALID, "scale_shift: null tensor");
+    if (nlayers < 1 || temb_dim < 1 || batch < 1 || max_n < 1 || max_n > 2048 || (size_t)temb_dim * 8 * 4 + 8192 > 64 * 1024)      // (the Linear's LDS: 8 samples of temb + the partial sums)
+        VDX_FAIL(VDX_ERR_INVALID, "scale_shift: bad geometry");
+    VDX_HIP(vdx::launch_resblock_ss(params, temb, reinterpret_cast<const vdx::SsLayer*>(layers_dev), nlayers, ss, lin, temb_dim, batch, max_n,
+                                    (hipStream_t)stream));
+    return VDX_OK;
+}
+
 int vdx_create(const vdx_config* cfg, vdx_handle** out) {
     if (!cfg || !out) VDX_FAIL(VDX_ERR_INVALID, "create: null argument");
     if (cfg->mode != VDX_MODE_F32 && cfg->mode != VDX_MODE_BF16 && cfg->mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");

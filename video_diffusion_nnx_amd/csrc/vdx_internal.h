@@ -146,6 +146,12 @@ hipError_t launch_attention_heads(AttnArgs a, hipStream_t st);
 // qkv [rows][3 * heads * 32] fp32 into o [rows][heads * 32] fp32; the projections are 1x1 convs by the caller
 hipError_t launch_attention_long_core(const float* qkv, float* o, long nseq, int L, int heads, float scale, hipStream_t st);
 
+// the attention / SLA block as the network composes it (model.hip; route decided there and only there): require = ATTN_ANY, or the
+// route a test-facing entry point is about (hipErrorInvalidValue when the network would take another)
+enum { ATTN_ANY = -1, ATTN_HEADS = 1, ATTN_LONG = 2 };
+hipError_t attention_block_forward(int mode, AttnArgs a, bool temporal, int NF, int Fr, int H, int W, void* scratch, size_t scratch_bytes,
+                                   int require, hipStream_t st);
+
 // y = SpatialLinearAttention(x) + x, x/y channel-last [NF][N][C]; 8 heads x 32
 struct SlaArgs {
     const float* x; float* y;
@@ -162,6 +168,8 @@ hipError_t launch_sla(int mode, SlaArgs a, hipStream_t st);
 // bf16 mode, 8 heads, N % 16 == 0: per-head kernel (weights resident in LDS, one wave per frame) -> O [NF * N rows][heads * 32] bf16;
 // to_out + residual is a 1x1 conv_igemm by the caller
 hipError_t launch_sla_heads(SlaArgs a, void* O, hipStream_t st);
+
+hipError_t sla_block_forward(int mode, SlaArgs a, int Fr, int H, int W, void* scratch, size_t scratch_bytes, int require, hipStream_t st);
 
 struct PSampleArgs {
     const float* x; const float* eps; float* out;       // x/out [B,C,F,H,W] (may alias); eps channel-last [B,F,H,W,C]

@@ -13,6 +13,11 @@ def _mode(mode) -> int:
     return L.MODES[mode] if isinstance(mode, str) else int(mode)
 
 
+def _is16(t) -> int:
+    assert t.dtype in (torch.float32, torch.bfloat16)
+    return int(t.dtype == torch.bfloat16)
+
+
 def pack_conv_weights(kernel: torch.Tensor, mode) -> torch.Tensor:
     """kernel: Flax layout (..., kh, kw, Cin, Cout) / (1, Cin, Cout) / (Cin, Cout) -> packed byte tensor."""
     m = _mode(mode)
@@ -72,15 +77,21 @@ def resblock_tail(y2, r, stats, gn_gamma, gn_beta, ln_gamma, ln_beta, groups=8):
     return out
 
 
+def _pack_rc(rc_kernel):
+    cin = rc_kernel.shape[0]
+    wp = rc_kernel.t().contiguous().to(torch.bfloat16)           # [C][Cin], K-contiguous: the packed operand layout
+    if cin % 64:                                                 # (rows padded to 64 input channels, as vdx_pack_conv_weights lays them out)
+        wp = torch.nn.functional.pad(wp, (0, 64 - cin % 64)).contiguous()
+    return wp
+
+
 def resblock_tail_rc_bf16(y2, x0, x1, rc_kernel, rc_bias, stats, gn_gamma, gn_beta, ln_gamma, ln_beta, groups=8):
     """Tail with the 1x1 res_conv inside (bf16 tensors): y2 [B,...,C], x0 [B,...,C0], x1 [B,...,C1] or None (all torch.bfloat16),
     rc_kernel Flax [C0+C1, C] fp32 -> out bf16."""
     B, C = y2.shape[0], y2.shape[-1]
     pix = y2.numel() // (B * C)
     c0, c1 = x0.shape[-1], (0 if x1 is None else x1.shape[-1])
-    wp = rc_kernel.t().contiguous().to(torch.bfloat16)           # [C][Cin], K-contiguous: the packed operand layout
-    if (c0 + c1) % 64:                                           # (rows padded to 64 input channels, as vdx_pack_conv_weights lays them out)
-        wp = torch.nn.functional.pad(wp, (0, 64 - (c0 + c1) % 64)).contiguous()
+    wp = _pack_rc(rc_kernel)
     out = torch.empty_like(y2)
     L.check(L.vdx_resblock_tail_rc_bf16(L.ptr(y2), L.ptr(x0), None if x1 is None else L.ptr(x1), c0, c1, L.ptr(wp), L.ptr(rc_bias),
                                         L.ptr(out), L.ptr(stats), L.ptr(gn_gamma), L.ptr(gn_beta), groups, L.ptr(ln_gamma),
@@ -178,6 +189,115 @@ def sla_forward_bf16(x, wq, wk, wv, wo, heads=8):
     L.check(L.vdx_sla_forward_bf16(L.ptr(x), L.ptr(y), L.ptr(pk[0]), L.ptr(pk[1]), L.ptr(pk[2]), L.ptr(pk[3]), L.ptr(ws),
                                    B, Fr, H, W, C_, heads, L.stream_ptr()))
     return y
+
+
+# ---- forward forms of the network (vdx.h: "Forward forms of the network"): the compositions and flags model.hip sets ----------------
+# Outputs and scratch are NaN-filled before the call: a row the kernels do not write shows.
+
+
+def _nan(shape, dtype, device):
+    return torch.full(shape, float('nan'), dtype=dtype, device=device)
+
+
+def attention_heads_forward(x, packed, temporal, fp8_core=False):
+    """The wide-level attention block of a bf16-mode network (attention_head_kernel + 1x1 out-projection with residual).  x fp32 or
+    bfloat16 [B, F, H, W, C]; packed = pack_mha(..., 'bf16').  -> (y like x, o [rows, 256] bfloat16: the core's output per head)"""
+    B, Fr, H, W, C_ = x.shape
+    assert x.is_contiguous()
+    y = _nan(x.shape, x.dtype, x.device)
+    o = _nan((B * Fr * H * W, 256), torch.bfloat16, x.device)
+    assert o.numel() * 2 == L.vdx_attention_heads_scratch_bytes(B, Fr, H, W)
+    wqkv, bqkv, wo, bo = packed
+    L.check(L.vdx_attention_heads_forward(L.ptr(x), L.ptr(y), _is16(x), L.ptr(wqkv), L.ptr(bqkv), L.ptr(wo), L.ptr(bo), L.ptr(o), o.numel() * 2,
+                                          B, Fr, H, W, C_, int(bool(temporal)), int(bool(fp8_core)), L.stream_ptr()))
+    return y, o
+
+
+def attention_long_forward(x, packed, heads, mode):
+    """Spatial attention over more than 64 tokens (1x1 q|k|v conv, fp32 core, 1x1 out-projection with residual).
+    -> (y like x, qkv [rows, 3 * heads * 32] fp32, o [rows, heads * 32] fp32: the scratch as the chain leaves it)"""
+    B, Fr, H, W, C_ = x.shape
+    assert x.is_contiguous()
+    rows, HD = B * Fr * H * W, heads * 32
+    y = _nan(x.shape, x.dtype, x.device)
+    scr = _nan((rows * 4 * HD,), torch.float32, x.device)
+    assert scr.numel() * 4 == L.vdx_attention_long_scratch_bytes(B, Fr, H, W, heads)
+    wqkv, bqkv, wo, bo = packed
+    L.check(L.vdx_attention_long_forward(_mode(mode), L.ptr(x), L.ptr(y), _is16(x), L.ptr(wqkv), L.ptr(bqkv), L.ptr(wo), L.ptr(bo), L.ptr(scr),
+                                         scr.numel() * 4, B, Fr, H, W, C_, heads, L.stream_ptr()))
+    return y, scr[:rows * 3 * HD].view(rows, 3 * HD), scr[rows * 3 * HD:].view(rows, HD)
+
+
+def sla_heads_forward(x, wq, wk, wv, wo):
+    """The wide-level SpatialLinearAttention block of a bf16-mode network (sla_head_kernel + 1x1 to_out with residual).  x fp32 or
+    bfloat16 [B, F, H, W, C]; wq/wk/wv: Flax (1, C, 256); wo: (1, 256, C).  -> (y like x, o [rows, 256] bfloat16)"""
+    B, Fr, H, W, C_ = x.shape
+    assert x.is_contiguous()
+    y = _nan(x.shape, x.dtype, x.device)
+    o = _nan((B * Fr * H * W, 256), torch.bfloat16, x.device)
+    pk = [pack_conv_weights(t, 'bf16') for t in (wq, wk, wv, wo)]
+    L.check(L.vdx_sla_heads_forward(L.ptr(x), L.ptr(y), _is16(x), L.ptr(pk[0]), L.ptr(pk[1]), L.ptr(pk[2]), L.ptr(pk[3]), L.ptr(o), o.numel() * 2,
+                                    B, Fr, H, W, C_, L.stream_ptr()))
+    return y, o
+
+
+def resblock_tail_ex(y2, r, stats, gn_gamma, gn_beta, ln_gamma, ln_beta, out_bf16=False, groups=8):
+    """resblock_tail with a storage type per tensor: y2 / r fp32 or bfloat16 (their dtypes), out bfloat16 when out_bf16."""
+    B, C_ = y2.shape[0], y2.shape[-1]
+    pix = y2.numel() // (B * C_)
+    out = _nan(y2.shape, torch.bfloat16 if out_bf16 else torch.float32, y2.device)
+    L.check(L.vdx_resblock_tail_ex(L.ptr(y2), _is16(y2), L.ptr(r), _is16(r), L.ptr(out), int(bool(out_bf16)), L.ptr(stats), L.ptr(gn_gamma),
+                                   L.ptr(gn_beta), groups, L.ptr(ln_gamma), L.ptr(ln_beta), C_, B, pix, L.stream_ptr()))
+    return out
+
+
+def resblock_tail_rc_head_bf16(y2, x0, x1, rc_kernel, rc_bias, stats, gn_gamma, gn_beta, ln_gamma, ln_beta, fin_kernel, fin_bias, groups=8):
+    """resblock_tail_rc_bf16 with the one-channel final conv inside (fin_kernel Flax (1, C, 1)): -> [B, ..., 1] fp32."""
+    B, C_ = y2.shape[0], y2.shape[-1]
+    pix = y2.numel() // (B * C_)
+    wp = _pack_rc(rc_kernel)
+    fw = fin_kernel.reshape(-1).contiguous().float()
+    assert fw.numel() == C_
+    out = _nan((*y2.shape[:-1], 1), torch.float32, y2.device)
+    L.check(L.vdx_resblock_tail_rc_head_bf16(L.ptr(y2), L.ptr(x0), L.ptr(x1), x0.shape[-1], x1.shape[-1], L.ptr(wp), L.ptr(rc_bias), L.ptr(stats),
+                                             L.ptr(gn_gamma), L.ptr(gn_beta), groups, L.ptr(ln_gamma), L.ptr(ln_beta), C_, L.ptr(fw), L.ptr(fin_bias),
+                                             L.ptr(out), B, pix, L.stream_ptr()))
+    return out
+
+
+def final_conv_ex(x, kernel, bias):
+    """final_conv on x fp32 or bfloat16 [.., D]."""
+    d, cout = kernel.shape[-2], kernel.shape[-1]
+    npix = x.numel() // d
+    y = _nan((*x.shape[:-1], cout), torch.float32, x.device)
+    L.check(L.vdx_final_conv_ex(L.ptr(x), _is16(x), L.ptr(kernel.contiguous()), L.ptr(bias), L.ptr(y), npix, d, cout, L.stream_ptr()))
+    return y
+
+
+def init_conv_ex(x, kernel, bias, mode, y_bf16=False):
+    """init_conv as the network launches it: mode 'bf16' with one input channel runs the MFMA kernel; y_bf16: bfloat16 output."""
+    B, Cin, Fr, H, W = x.shape
+    k, cout = kernel.shape[1], kernel.shape[-1]
+    y = _nan((B, Fr, H, W, cout), torch.bfloat16 if y_bf16 else torch.float32, x.device)
+    L.check(L.vdx_init_conv_ex(_mode(mode), L.ptr(x), L.ptr(kernel.contiguous()), L.ptr(bias), L.ptr(y), int(bool(y_bf16)), B, Cin, Fr, H, W, cout, k,
+                               L.stream_ptr()))
+    return y
+
+
+def resblock_scale_shift(params, temb, layers):
+    """Every ResnetBlock's (scale, shift) rows in one launch pair.  params: flat fp32 buffer; temb [B, temb_dim]; layers: list of dicts
+    (w_off, b_off, g_off, be_off, out_off, n), offsets in floats (out_off per sample).  -> (ss, lin): flat fp32 buffers, layer l /
+    sample b at [out_off * B + b * n, + n)."""
+    B, temb_dim = temb.shape
+    tab = (L.SsLayer * len(layers))()
+    for t, l in zip(tab, layers):
+        t.w_off, t.b_off, t.g_off, t.be_off, t.out_off, t.n = l['w_off'], l['b_off'], l['g_off'], l['be_off'], l['out_off'], l['n']
+    raw = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(params.device)
+    total = max(l['out_off'] + l['n'] for l in layers) * B
+    ss, lin = _nan((total,), torch.float32, params.device), _nan((total,), torch.float32, params.device)
+    L.check(L.vdx_resblock_scale_shift(L.ptr(params), L.ptr(temb), L.ptr(raw), len(layers), L.ptr(ss), L.ptr(lin), temb_dim, B,
+                                       max(l['n'] for l in layers), L.stream_ptr()))
+    return ss, lin
 
 
 # ---- backward building blocks ---------------------------------------------------------------------------
@@ -323,11 +443,6 @@ _conv_rows = L._sig('vdx_conv_forward_rows', C.c_int, [C.c_int, C.POINTER(L.Conv
 _final_bwd = L._sig('vdx_final_conv_backward', C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
 _init_wgrad = L._sig('vdx_init_conv_backward_weights', C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p, C.c_size_t, C.c_void_p])
 _time_mlp_bwd = L._sig('vdx_time_mlp_backward', C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_int, C.c_void_p])
-
-
-def _is16(t) -> int:
-    assert t.dtype in (torch.float32, torch.bfloat16)
-    return int(t.dtype == torch.bfloat16)
 
 
 def conv_backward_weights_ex(x0, dy, kshape, *, x1=None, kind=0, k=3, stride=1, in_stats=None, gamma=None, beta=None, groups=8,
