@@ -37,13 +37,15 @@ ATTN_HEADS_SPATIAL = [
 ]
 
 
-def mha_weights(C, g):
-    """wqkv [C, 768] (q | k | v), bqkv [768], wo [256, C], bo [C]; the kernels bf16-representable (the packing rounds them), the biases fp32."""
-    wqkv = P.bf16r(torch.randn(C, 768, generator=g) / C ** 0.5 * 2)
+def mha_weights(C, g, raw=False):
+    """wqkv [C, 768] (q | k | v), bqkv [768], wo [256, C], bo [C]; the kernels bf16-representable (the packing rounds them), the biases fp32.
+    raw: -> (those, the same with the kernels as drawn, before the rounding)"""
+    wqkv = torch.randn(C, 768, generator=g) / C ** 0.5 * 2
     bqkv = torch.randn(768, generator=g) * 0.2
-    wo = P.bf16r(torch.randn(256, C, generator=g) / 16)
+    wo = torch.randn(256, C, generator=g) / 16
     bo = torch.randn(C, generator=g) * 0.2
-    return wqkv, bqkv, wo, bo
+    w = P.bf16r(wqkv), bqkv, P.bf16r(wo), bo
+    return (w, (wqkv, bqkv, wo, bo)) if raw else w
 
 
 def mha_oracle_params(wqkv, bqkv, wo, bo):
@@ -148,14 +150,26 @@ SLA_HEADS = [
 
 
 @functools.lru_cache(maxsize=4)
+def sla_weights(C, g, raw=False):
+    """wq, wk, wv [C, 256] at 3 / sqrt C, wo [256, C] / 16, bf16-representable.  raw: -> (those, the same as drawn, before the rounding)"""
+    drawn = tuple([torch.randn(C, 256, generator=g) / C ** 0.5 * 3 for _ in range(3)] + [torch.randn(256, C, generator=g) / 16])
+    w = tuple(P.bf16r(t) for t in drawn)
+    return (w, drawn) if raw else w
+
+
+def sla_input(shape, g):
+    """x [B, F, H, W, C], bf16-representable, with a spike in the k logits of one pixel: the online-softmax rescale"""
+    B, Fr, H, W, C = shape
+    x = torch.randn(B, Fr, H, W, C, generator=g)
+    x[:, :, H // 2, W // 2] *= 6
+    return P.bf16r(x)
+
+
 def sla_heads_case(shape, io16):
     B, Fr, H, W, C = shape
     g = _gen(*shape, 7)
-    x = torch.randn(B, Fr, H, W, C, generator=g)
-    x[:, :, H // 2, W // 2] *= 6                                  # a spike in the k logits of one pixel: the online-softmax rescale
-    x = P.bf16r(x)
-    wq, wk, wv = [P.bf16r(torch.randn(C, 256, generator=g) / C ** 0.5 * 3) for _ in range(3)]
-    wo = P.bf16r(torch.randn(256, C, generator=g) / 16)
+    x = sla_input(shape, g)
+    wq, wk, wv, wo = sla_weights(C, g)
     o64, y64 = P.sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W)
     oe, ye = P.sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W, emulate=True, round_out=io16)
     NF, N = B * Fr, H * W

@@ -319,8 +319,10 @@ def have_e4m3() -> bool:
         return False
 
 
-def attention_block_fwd(x, wqkv, bqkv, wo, bo, B, Fr, H, W, temporal, emulate=False, fp8=False, round_out=False, unmasked_pad=0):
-    """y = MHA(x) + x (8 heads x 32) over the frames of every pixel (temporal) or the pixels of every frame, in fp64, closed form.
+def attention_block_fwd(x, wqkv, bqkv, wo, bo, B, Fr, H, W, temporal, emulate=False, fp8=False, round_out=False, unmasked_pad=0,
+                        q_scaled=False, dtype=torch.float64):
+    """y = MHA(x) + x (8 heads x 32) over the frames of every pixel (temporal) or the pixels of every frame, in `dtype` (fp64 = the
+    reference; fp32 = the floor of the f32-mode bounds), closed form.
     x [B, Fr, H, W, C]; wqkv [C, 768] = q | k | v column blocks, bqkv [768], wo [256, C], bo [C].
     emulate: the rounding points of attention_head_kernel (attention.hip): q, k, v = bf16(x W + b) -- the projections' fp32 accumulators
     become MFMA operands through pack_bf16x2 in Mma::mma16 (vdx_common.h:87-91; core_mma16 calls at attention.hip:1158-1159, 1181);
@@ -328,35 +330,82 @@ def attention_block_fwd(x, wqkv, bqkv, wo, bo, B, Fr, H, W, temporal, emulate=Fa
     product (:1176 -> :1181); o is stored as bf16 (:1182-1183).  fp8: e4m3 instead of bf16 for q, k, v and P (mma16_fp8,
     vdx_common.h:95-99; o is still stored as bf16).  round_out: y rounded to bf16 (the io_bf16 store of the 1x1 out-projection).
     unmasked_pad > 0 (a FAULT, for the CPU proofs): that many padding keys with k = v = their bias take part in the softmax.
+
+    The level-0 and narrow-level kernels of attention.hip in bf16 mode (tests/test_gpu_attention_groups.py) round at the same points:
+    * attention_w_kernel: q, k = bias + W x in fp32 accumulators (:894-925) become operands of the score product through core_mma16
+      (:930-931 -> Mma::mma16 / mma16_fp8, vdx_common.h:87-99); the mask and the softmax run in fp32 with 1 / sqrt(32) inside the exponent
+      (:933-979); P and v are rounded as the operands of the PV product (:988); o is packed to bf16 -- also with the fp8 core -- as the B
+      fragment of the out-projection (:994 -> :998), whose fp32 accumulators start from bo (:878-880); y = bf16(acc + x) (:1009-1012).
+    * attention_h8_kernel: the same core (:578-579 scores, :584-606 softmax, :613 PV); o goes to LDS as bf16 (:617-618, or store4 :621) for
+      the out-projection (:637-641); y = acc + x in fp32 (:666), or bf16(acc + x) on bf16 tensors (:660-663): round_out.  An fp32 x is
+      rounded to bf16 at staging (:489): the tests feed bf16-representable x.
+    * attention_reg_kernel: q = (acc + bias) * scale in fp32 BEFORE the operand rounding (:352-353 -> :359-360): q_scaled; P and v rounded
+      at :376, o rounded as the operand of the out-projection's mma16 (:380); y fp32 (:394-396).
+    * attention_kernel: q = bf16((acc + bias) * scale) (:140-141): q_scaled; k, v stored as bf16 (:143, :147-148), P stored as bf16
+      (:186), o stored as bf16 (:199); y fp32 (:231-233).
+    In f32 mode every one of them keeps fp32 throughout (Mma<MODE_F32>: f32 MFMA operands, 4-byte LDS elements): no rounding point, the
+    bound is the exact-products kind (f32_group_bounds).
+    q_scaled: q is multiplied by 1 / sqrt(32) before it is rounded (the scores are then not scaled again).
     -> (o [rows][256], y [B, Fr, H, W, C])"""
-    dt = torch.float64
+    dt = dtype
     C_ = x.shape[-1]
     X = x.to(dt).reshape(-1, C_)
     qkv = X @ wqkv.to(dt) + bqkv.to(dt)
     rd = (e4m3r if fp8 else bf16r) if emulate else (lambda t: t)
+    if q_scaled:
+        qkv = torch.cat((qkv[:, :256] / math.sqrt(32.0), qkv[:, 256:]), 1)
     s = _seq_view(rd(qkv), B, Fr, H * W, 8, temporal, 3)
     q, k, v = s[..., 0, :, :], s[..., 1, :, :], s[..., 2, :, :]                     # [b, s, L, h, d]
     if unmasked_pad:
         pad = rd(bqkv.to(dt)).reshape(3, 8, 32)
         ext = lambda t, i: torch.cat((t, pad[i].expand(*t.shape[:2], unmasked_pad, 8, 32)), 2)
         k, v = ext(k, 1), ext(v, 2)
-    S = torch.einsum('bsihd,bsjhd->bshij', q, k) / math.sqrt(32.0)
+    S = torch.einsum('bsihd,bsjhd->bshij', q, k)
+    if not q_scaled:
+        S = S / math.sqrt(32.0)
     P = rd(torch.softmax(S, -1))
     o = _seq_unview(torch.einsum('bshij,bsjhd->bsihd', P, v), temporal)
     if emulate:
         o = bf16r(o)
-    y = (o @ wo.to(dt) + bo.to(dt)).reshape(x.shape) + x.to(dt)
-    return o, (bf16r(y) if round_out else y)
+    return o, block_tail(o, x, wo, bo, round_out, dt)
 
 
-def sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W, emulate=False, round_out=False):
-    """y = SpatialLinearAttention(x) + x (8 heads x 32) in fp64, closed form: ctx = softmax_n(k)^T v, out = ctx^T softmax_d(q) per
+def block_tail(o, x, wo, bo=None, round_out=False, dtype=torch.float64):
+    """y = o Wo (+ bo) + x of an attention / SLA block from the per-head output o [rows][256]; round_out: y rounded to bf16."""
+    y = o.to(dtype) @ wo.to(dtype)
+    if bo is not None:
+        y = y + bo.to(dtype)
+    y = y.reshape(x.shape) + x.to(dtype)
+    return bf16r(y) if round_out else y
+
+
+def sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W, emulate=False, round_out=False, dtype=torch.float64, fault=None):
+    """y = SpatialLinearAttention(x) + x (8 heads x 32) in `dtype` (fp64 = the reference; fp32 = the floor of the f32-mode bounds), closed
+    form: ctx = softmax_n(k)^T v, out = ctx^T softmax_d(q) per
     (frame, head).  wq / wk / wv [C, 256], wo [256, C].  emulate: the rounding points of sla_head_kernel (sla.hip): exp(k - max) and v
     are rounded to bf16 as the operands of the context product (Mma::mma16 at :1023) while the softmax denominator sums the unrounded
     exponentials (:1006-1007) and divides the fp32 context (:1026-1033); ctx and softmax_d(q) are rounded to bf16 as the operands of
     the output product (:1070-1071); o is stored as bf16 (:1072-1073).  (The kernel rounds exp(k - running max); rounding is relative,
-    so the final maximum gives the same relative error.)  -> (o [rows][256], y [B, Fr, H, W, C])"""
-    dt = torch.float64
+    so the final maximum gives the same relative error.)
+
+    The narrow-level kernels in bf16 mode (tests/test_gpu_attention_groups.py) round at the same points:
+    * sla_ctx8_kernel: exp2 of the k logits against the running maximum in fp32 (ctx8_softmax_step, :436), the denominator sums the
+      unrounded exponentials (:439-441); e and v become bf16 as the operands of the context product (Mma::mma16 at :516); the fp32 context
+      is divided by the denominator and stored ONCE in the storage type of ctxT, bf16 -- by the kernel itself when a frame is one chunk
+      (:527-531), else by sla_combine_kernel from fp32 partials (:212-221) -- and read back as such: the rd(ctx) below, no second rounding.
+    * sla_out8_kernel: ctx^T fragments read from ctxT as bf16 (:584); softmax_d(q) in fp32 (:634-651), rounded as the operand of
+      Mma::mma16 (:660); o stored to LDS as bf16 (:661) for to_out (:674-681); y = acc + x in fp32 (:721-722) or bf16(acc + x) on bf16
+      tensors (:705-708): round_out.
+    * sla_out_w_kernel: ctx^T from the LDS image of ctxT, bf16 (:849); softmax_d(q) rounded at :883; o packed to bf16 as the B fragment
+      of to_out (:887 -> :892); y = bf16(acc + x) (:903-906).
+    * sla_ctx_kernel: e stored as bf16 (:156-157) while the sum takes the unrounded e (:158), v stored as bf16 (:171), context product
+      :181-183, fp32 partials (:189) -> sla_combine_kernel as above.  sla_out_kernel: softmax_d(q) stored as bf16 (:309), ctxT read as
+      bf16 (:320), o stored as bf16 (:329), y fp32 (:360-364).
+    In f32 mode all of them keep fp32 throughout (ctxT included: M::store1 of Mma<MODE_F32>): the bound is f32_group_bounds.
+    fault (for the CPU proofs): ('drop_ctx', f, h, n0) -- pixels n0.. of frame f are missing from head h's context, numerator and
+    denominator (a chunk partial the combine never adds); ('swap_ctx', f, n0, n1, f2) -- pixels n0..n1 of frame f take frame f2's context.
+    -> (o [rows][256], y [B, Fr, H, W, C])"""
+    dt = dtype
     C_, NF, N = x.shape[-1], B * Fr, H * W
     X = x.to(dt).reshape(-1, C_)
     hs = lambda t: t.reshape(NF, N, 8, 32).permute(0, 2, 1, 3)                      # [f, h, n, d]
@@ -364,12 +413,18 @@ def sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W, emulate=False, round_out=False
     rd = bf16r if emulate else (lambda t: t)
     qs = torch.softmax(Q, -1)
     ek = torch.exp(K - K.max(dim=2, keepdim=True).values)
+    if fault and fault[0] == 'drop_ctx':
+        ek = ek.clone()
+        ek[fault[1], fault[2], fault[3]:] = 0.0
     ctx = torch.einsum('fhnd,fhne->fhde', rd(ek), rd(V)) / ek.sum(2, keepdim=True).transpose(2, 3)
-    o = torch.einsum('fhde,fhnd->fhne', rd(ctx), rd(qs)).permute(0, 2, 1, 3).reshape(NF * N, 256)
+    o = torch.einsum('fhde,fhnd->fhne', rd(ctx), rd(qs))
+    if fault and fault[0] == 'swap_ctx':
+        _, f, n0, n1, f2 = fault
+        o[f, :, n0:n1] = torch.einsum('hde,hnd->hne', rd(ctx[f2]), rd(qs[f, :, n0:n1]))
+    o = o.permute(0, 2, 1, 3).reshape(NF * N, 256)
     if emulate:
         o = bf16r(o)
-    y = (o @ wo.to(dt)).reshape(x.shape) + x.to(dt)
-    return o, (bf16r(y) if round_out else y)
+    return o, block_tail(o, x, wo, None, round_out, dt)
 
 
 def seq_head_groups(o, B, Fr, HW, temporal):
@@ -381,6 +436,91 @@ def seq_head_groups(o, B, Fr, HW, temporal):
 def frame_head_groups(o, NF, N):
     """o [rows][256] -> [frames, heads, N * 32]."""
     return o.reshape(NF, N, 8, 32).permute(0, 2, 1, 3).reshape(NF, 8, -1)
+
+
+# ---- group views of a block's branch y - x (tests/test_gpu_attention_groups.py) ---------------------------------------------------------
+# A view maps a tensor to a LIST of 2-D tensors [groups, elements]: one row per group; a ragged last tile is a piece of its own (as the
+# slices of slice_rels), so that it is a group like any other.  Every SLA view leads with the frame axis of a [NF, N, C] tensor and no
+# group crosses a frame: the comparison may then walk the frames in chunks (`chunk`), which bounds the host memory of the largest case.
+
+
+def isolate_heads(wo):
+    """Head-isolating out-projection: Wo[h * 32 + d, c] = 0 unless c % 8 == h.  Channels c % 8 == h of the branch then depend on head h
+    alone (8 / 4 / 16 channels per head at C = 64 / 32 / 128), which localises a fault to a (sequence, head) through the block's own ABI."""
+    rows = torch.arange(wo.shape[0])[:, None] // 32
+    cols = torch.arange(wo.shape[1])[None, :] % 8
+    return wo * (rows == cols).to(wo.dtype)
+
+
+def seq_head_view(temporal):
+    """[B, F, H, W, C] -> one group per (sequence, head): the channels c % 8 == h of a sequence (isolate_heads)"""
+    def view(t):
+        B, Fr, H, W, C = t.shape
+        s = t.reshape(B, Fr, H * W, C // 8, 8)
+        s = s.permute(0, 2, 4, 1, 3) if temporal else s.permute(0, 1, 4, 2, 3)       # [b, sequence, head, token, C / 8]
+        return [s.reshape(s.shape[0] * s.shape[1] * 8, -1)]
+    return view
+
+
+def frame_view(t):
+    """[NF, N, C] -> one group per frame"""
+    return [t.reshape(t.shape[0], -1)]
+
+
+def frame_head_view(t):
+    """[NF, N, C] -> one group per (frame, head): the channels c % 8 == h of a frame (isolate_heads)"""
+    NF, N, C = t.shape
+    return [t.reshape(NF, N, C // 8, 8).permute(0, 3, 1, 2).reshape(NF * 8, -1)]
+
+
+def pixel_tile_view(tile=64):
+    """[NF, N, C] -> one group per (frame, `tile` consecutive pixels): what one wave of sla_out_w_kernel / one pass of sla_out8_kernel
+    owns; the ragged last tile of a frame is a group of its own (second piece)."""
+    def view(t):
+        NF, N, C = t.shape
+        full = N // tile
+        out = [t[:, :full * tile].reshape(NF * full, tile * C)] if full else []
+        if N % tile:
+            out.append(t[:, full * tile:].reshape(NF, -1))
+        return out
+    return view
+
+
+def view_rels(got, ref, view, chunk=None):
+    """rel-L2 of every group of `view` -> 1-D tensor (piece after piece; with `chunk`: per chunk of the leading axis, piece after piece)"""
+    if chunk:
+        return torch.cat([view_rels(got[i:i + chunk], ref[i:i + chunk], view) for i in range(0, ref.shape[0], chunk)])
+    return torch.cat([per_group_rel(g, r, (r.shape[0],))[2] for g, r in zip(view(got.double()), view(ref.double()))])
+
+
+def view_bound(emulated, ref64, view, chunk=None, margin=3.0):
+    """group_bound over every piece of a view: margin x the worst emulated group."""
+    if chunk:
+        return max(view_bound(emulated[i:i + chunk], ref64[i:i + chunk], view, None, margin) for i in range(0, ref64.shape[0], chunk))
+    return max(group_bound(e, r, (r.shape[0],), margin) for e, r in zip(view(emulated.double()), view(ref64.double())))
+
+
+def f32_group_bounds(eval32, ref64, view, chunk=None, stated=FWD_STATED):
+    """Per-group bounds of an f32-mode block: max(stated, 8 x the same formula evaluated in fp32 on the CPU against fp64), one figure per
+    group, in the order of view_rels; refused at EXACT_CEILING."""
+    b = (8.0 * view_rels(eval32, ref64, view, chunk)).clamp_min(stated)
+    assert b.max().item() < EXACT_CEILING, f'f32 group bound {b.max().item():.2e} does not separate a kernel fault from arithmetic'
+    return b
+
+
+def assert_views(got, ref, view, bound, what='', chunk=None):
+    """Every group of `view` below `bound` (one figure, or one per group in the order of view_rels); none is exempt, a non-finite group
+    fails.  Prints the bound next to the worst group.  -> worst rel"""
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    r = view_rels(got, ref, view, chunk)
+    b = bound if torch.is_tensor(bound) else torch.full_like(r, float(bound))
+    assert b.shape == r.shape, (what, b.shape, r.shape)
+    ratio = torch.where(torch.isfinite(r), r / b, torch.full_like(r, float('inf')))
+    i = int(ratio.argmax())
+    print(f'[groups] {what}: {r.numel()} groups, worst group {i} rel {r[i].item():.3e} (bound {b[i].item():.3e}; bounds {b.min().item():.3e} .. {b.max().item():.3e})')
+    nbad = int((~(ratio < 1.0)).sum())
+    assert nbad == 0, f'{what}: {nbad} group(s) over their bound, worst group {i} rel-L2 {r[i].item():.3e} >= {b[i].item():.3e}'
+    return r[i].item()
 
 
 def norm_bound(ref32, ref64, slices=None, stated=FWD_STATED):

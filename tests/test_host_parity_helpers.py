@@ -383,3 +383,190 @@ def test_forward_closed_forms_match_the_oracle():
     assert P.rel(y, R.spatial_linear_attention(p, 'a', x, 8) + x) < 1e-12
     if P.have_e4m3():
         assert torch.equal(P.e4m3r(torch.tensor([0.3, 17.0, 500.0])), torch.tensor([0.3125, 16.0, 448.0]))
+
+
+# ---- per-group bounds of the level-0 attention / SLA kernels (tests/test_gpu_attention_groups.py) ----------------------------------------
+# Each fault below is injected into the emulated output of a case of that file.  First it PASSES what tests/test_gpu_blocks.py asserts of
+# the same kernels (branch < 4e-2 and block < 1e-2 against the oracle on un-rounded weights), then the per-group assertion rejects it.
+# Two faults replace a whole group and cannot pass the 1e-2 at any case of the list (a tile on the neighbouring frame's context, a sequence
+# not written): of those the first half asserts that the old check catches them only marginally (_old_assertions_marginal).
+
+import _attention_cases as AC
+
+
+def _old_figures(branch, x, y_old, what):
+    """The global figures of test_attention_bf16_tensors / test_sla_bf16_tensors.  -> (branch rel, block rel)"""
+    xd = x.double()
+    rb, r = P.rel(branch, y_old - xd), P.rel(branch + xd, y_old)
+    print(f'[old assertions] {what}: branch {rb:.3e} (asserted 4e-2), block {r:.3e} (asserted 1e-2)')
+    return rb, r
+
+
+def _old_assertions_pass(rb, r, what):
+    assert rb < 4e-2 and r < 1e-2, f'{what}: the global figures do see this fault ({rb:.3e}, {r:.3e}): use a larger case'
+
+
+def _old_assertions_marginal(rb, r, n, what):
+    """A fault that replaces ONE WHOLE group of n by something unrelated has an error of up to sqrt(2) x the group's own size, sqrt(2 / n) of
+    the branch; no case of the list has enough groups to take that below the 1e-2 on the block (at 16384 tiles the swapped context still
+    reads 1.2e-2, and 8928 sequences are the most an attention case has).  What is true of such a fault is asserted instead: the branch
+    assertion passes, and the block assertion catches it by less than sqrt(2 / n) + the clean figure (< 1e-2) -- a margin below 3 where
+    the per-group bound has one of 30 and more."""
+    assert rb < 4e-2 and 1e-2 <= r < (2 / n) ** 0.5 + 1e-2 <= 3.3e-2, f'{what}: expected the old block assertion to catch this marginally ({rb:.3e}, {r:.3e})'
+
+
+def _rejected(c, branch, names, what):
+    for n in names:
+        with pytest.raises(AssertionError, match='over their bound'):
+            P.assert_views(branch, c['ref'], c['views'][n], c['bounds'][n], f'{what} per {n}', c['chunk'])
+
+
+def _clean_passes(c, what):
+    for n, v in c['views'].items():
+        P.assert_views(c['cmp'], c['ref'], v, c['bounds'][n], f'clean emulation, {what} per {n}', c['chunk'])
+
+
+def _fp32_attention_passes(c, io16, q_scaled, fp8=False):
+    """The rounding points evaluated in fp32 instead of fp64 -- the arithmetic of a correct kernel up to summation order -- inside every bound."""
+    y32 = P.attention_block_fwd(c['x'], *c['w'], *c['shape'][:4], c['temporal'], emulate=True, fp8=fp8, round_out=io16, q_scaled=q_scaled, dtype=torch.float32)[1]
+    for n, v in c['views'].items():
+        P.assert_views(y32.double() - c['x'].double(), c['ref'], v, c['bounds'][n], f"fp32 emulation, attention {c['shape']} fp8={int(fp8)} per {n}")
+
+
+def _fp32_sla_passes(c, io16):
+    b32 = AC.sla_eval(c['x'], c['w'], c['chunk'] or AC.SLA_CHUNK, emulate=True, round_out=io16, dtype=torch.float32)
+    for n, v in c['views'].items():
+        P.assert_views(b32, c['ref'], v, c['bounds'][n], f"fp32 emulation, SLA {c['shape']} per {n}", c['chunk'])
+
+
+def test_attention_faults_of_one_group_pass_the_global_figures_and_are_rejected_per_sequence():
+    # padding keys unmasked in the last group of 4 sequences: (2, 12, 16, 16, 64), 512 sequences, 4 of 16 key slots are padding
+    shape = (2, 12, 16, 16, 64)
+    B, Fr, H, W, C = shape
+    for iso in (False, True):
+        c = AC.attn_case(shape, True, True, 'bf16', False, iso)
+        _clean_passes(c, f'attention {shape} iso={int(iso)}')
+        _fp32_attention_passes(c, True, False)
+        y_old = AC.attn_old_oracle(c)
+        yb = P.attention_block_fwd(c['x'], *c['w'], B, Fr, H, W, True, emulate=True, round_out=True, unmasked_pad=4)[1] - c['x'].double()
+        bad = c['cmp'].clone()
+        bad[1, :, 15, 12:16] = yb[1, :, 15, 12:16]
+        _old_assertions_pass(*_old_figures(bad, c['x'], y_old, f'unmasked padding keys in one group of 4, iso={int(iso)}'), 'unmasked padding keys')
+        _rejected(c, bad, c['views'], 'unmasked padding keys in one group of 4')
+    # (1, 16, 96, 93, 64), 8928 sequences: one head replaced by its neighbour in ONE sequence
+    shape = (1, 16, 96, 93, 64)
+    B, Fr, H, W, C = shape
+    c = AC.attn_case(shape, True, True, 'bf16')
+    _clean_passes(c, f'attention {shape}')
+    y_old = AC.attn_old_oracle(c)
+    wqkv, bqkv, wo, bo = c['w']
+    o = P.attention_block_fwd(c['x'], *c['w'], B, Fr, H, W, True, emulate=True, round_out=True)[0]
+    pix = 95 * 93 + 90                                                      # a sequence of the last, half-empty workgroup
+    rows = torch.arange(Fr) * (H * W) + pix
+    o[rows, 7 * 32:8 * 32] = o[rows, 6 * 32:7 * 32]
+    bad = P.block_tail(o, c['x'], wo, bo, True) - c['x'].double()
+    assert torch.equal(bad.reshape(Fr, H * W, C)[:, :pix], c['cmp'].reshape(Fr, H * W, C)[:, :pix])     # (every other sequence untouched)
+    _old_assertions_pass(*_old_figures(bad, c['x'], y_old, 'head 7 := head 6 in one sequence'), 'head 7 := head 6')
+    _rejected(c, bad, ['sequence'], 'head 7 := head 6 in one sequence')
+    # one sequence of 8928 not written (y = x): sqrt(1 / 8928) = 1.06e-2 of the branch, at the largest attention case of the list: the old
+    # block assertion catches it, by a hair
+    bad = c['cmp'].clone()
+    bad.reshape(Fr, H * W, C)[:, pix] = 0.0
+    _old_assertions_marginal(*_old_figures(bad, c['x'], y_old, 'one sequence not written'), H * W, 'one sequence not written')
+    _rejected(c, bad, ['sequence'], 'one sequence not written')
+
+
+def test_sla_faults_of_one_frame_or_tile_pass_the_global_figures_and_are_rejected_per_group():
+    shape = (8, 16, 64, 32, 64)                                             # 128 frames of 2048 pixels = 4 chunks of 8 tiles
+    f, h = 77, 5
+    for iso in (False, True):
+        c = AC.sla_case(shape, True, 'bf16', iso)
+        _clean_passes(c, f'SLA {shape} iso={int(iso)}')
+        _fp32_sla_passes(c, True)
+        y_old = AC.sla_old_oracle(c)
+        x, w = c['x'], c['w']
+        kw = dict(emulate=True, round_out=True)
+        # the last chunk's partial of one (frame, head) never reaches the context
+        bad = c['cmp'].clone()
+        bad[f] = AC.sla_eval(x[f:f + 1], w, fault=('drop_ctx', 0, h, 1536), **kw)[0]
+        _old_assertions_pass(*_old_figures(bad, x, y_old, f'a dropped chunk partial of one (frame, head), iso={int(iso)}'), 'a dropped chunk partial')
+        _rejected(c, bad, c['views'], 'a dropped chunk partial of one (frame, head)')
+        if iso:
+            continue
+        # one 64-pixel tile computed with the neighbouring frame's context: a whole group of 128 x 32 replaced
+        bad = c['cmp'].clone()
+        bad[f] = AC.sla_eval(x[f:f + 2], w, fault=('swap_ctx', 0, 31 * 64, 32 * 64, 1), **kw)[0]
+        assert torch.equal(bad[f, :31 * 64], c['cmp'][f, :31 * 64])
+        _old_assertions_marginal(*_old_figures(bad, x, y_old, 'one tile on the neighbouring frame\'s context'), 128 * 32, 'tile on the neighbouring context')
+        _rejected(c, bad, ['(frame, 64-pixel tile)'], 'one tile on the neighbouring frame\'s context')
+
+
+def test_sla_tile_not_written_passes_the_global_figures_at_512_frames_and_is_rejected_per_tile():
+    """One 64-pixel tile left as y = x moves the block figure by sqrt(1 / tiles) of the branch's share: 1.6e-2 at the 4096 tiles of the
+    128-frame case, which the 1e-2 sees; at the 16384 tiles of the 512-frame case a typical tile passes.  The tile is the one of median
+    branch norm (tiles differ: one of the heaviest, tile 5 of frame 333 at 1.3 x the median, still reads 1.07e-2).  The case is walked
+    in chunks of frames."""
+    shape = (32, 16, 64, 32, 64)
+    c = AC.sla_case(shape, True, 'bf16', old=True)
+    step, faulty = c['chunk'], {}
+    norms = c['ref'].reshape(c['NF'], c['N'] // 64, -1).norm(dim=2).flatten()
+    f, t = divmod(int(norms.argsort()[norms.numel() // 2]), c['N'] // 64)
+    tile = slice(t * 64, (t + 1) * 64)
+    print(f'[tile not written] frame {f} tile {t}: branch norm {norms[f * (c["N"] // 64) + t]:.3e}, rms over the tiles {norms.square().mean().sqrt():.3e}, max {norms.max():.3e}')
+
+    def unwritten(i0, e):
+        if i0 <= f < i0 + step:
+            faulty['clean'], faulty['i0'] = e.clone(), i0
+            e[f - i0, tile] = 0.0
+            faulty['bad'] = e
+
+    rb, r = AC.sla_old_figures(c, unwritten, [f])
+    print(f'[old assertions] one tile of 16384 not written: branch {rb:.3e} (asserted 4e-2), block {r:.3e} (asserted 1e-2)')
+    _old_assertions_pass(rb, r, 'one tile of 16384 not written')
+    i0 = faulty['i0']
+    ref = c['ref'][i0:i0 + step]
+    for n, v in c['views'].items():
+        P.assert_views(faulty['clean'], ref, v, c['bounds'][n], f'clean emulation, frames {i0}.., per {n}')
+    with pytest.raises(AssertionError, match='1 group\\(s\\) over their bound'):
+        P.assert_views(faulty['bad'], ref, c['views']['(frame, 64-pixel tile)'], c['bounds']['(frame, 64-pixel tile)'], 'one tile not written')
+
+
+def test_fp32_evaluation_of_the_emulations_passes_every_group_bound():
+    """The rounding points evaluated in fp32 instead of fp64 -- the arithmetic of a correct kernel up to summation order -- stay inside
+    3 x the fp64 emulation in every group of every view (the masked C = 64 attention_w case and the 128-frame sla_out_w case: in the
+    fault tests above, where they are built anyway); and the f32-mode bounds are finite, per group and below the ceiling."""
+    for shape, temporal, io16, iso, qs in (((1, 16, 16, 16, 64), True, True, True, False), ((2, 10, 12, 12, 32), True, True, False, False),
+                                           ((1, 10, 6, 6, 128), True, True, False, False), ((1, 16, 2, 2, 256), True, False, False, True),
+                                           ((1, 2, 5, 5, 64), False, False, False, True)):
+        _fp32_attention_passes(AC.attn_case(shape, temporal, io16, 'bf16', False, iso, qs), io16, qs)
+        f = AC.attn_case(shape, temporal, False, 'f32', False, iso)
+        assert all(b.numel() == P.view_rels(f['ref'], f['ref'], f['views'][n]).numel() and P.FWD_STATED <= b.min() and b.max() < P.EXACT_CEILING
+                   for n, b in f['bounds'].items())
+    if P.have_e4m3():                                                       # the bounds of the fp8 core, on both kernels that have one
+        for shape in ((1, 16, 16, 16, 64), (1, 16, 8, 8, 64)):
+            _fp32_attention_passes(AC.attn_case(shape, True, True, 'bf16', True), True, False, fp8=True)
+    for shape, io16, iso in (((1, 16, 32, 32, 64), True, True), ((2, 10, 16, 16, 32), True, False), ((1, 1, 24, 24, 256), False, True),
+                             ((1, 2, 5, 7, 16), False, False)):
+        _fp32_sla_passes(AC.sla_case(shape, io16, 'bf16', iso), io16)
+    assert len(P.pixel_tile_view(64)(torch.zeros(2, 35, 16))) == 1 and P.pixel_tile_view(64)(torch.zeros(2, 600, 8))[1].shape == (2, 24 * 8)
+
+
+def test_head_isolating_out_projection_and_q_scaling_flag():
+    g = torch.Generator().manual_seed(5)
+    for C in (32, 64, 128):
+        wo = P.isolate_heads(torch.randn(256, C, generator=g, dtype=torch.float64))
+        o = torch.randn(7, 256, generator=g, dtype=torch.float64)
+        o2 = o.clone()
+        o2[:, 3 * 32:4 * 32] += 1.0                                          # head 3 moves ...
+        d = ((o2 - o) @ wo).abs().sum(0)
+        assert (d[torch.arange(C) % 8 == 3] > 0).all() and (d[torch.arange(C) % 8 != 3] == 0).all()     # ... channels c % 8 == 3 alone
+    # q_scaled changes where q is rounded, not the function: identical without emulation, different (slightly) with it
+    shape = (1, 16, 2, 2, 64)
+    x = P.bf16r(torch.randn(*shape, generator=g))
+    w = FC.mha_weights(64, g)
+    a = P.attention_block_fwd(x, *w, *shape[:4], True)[1]
+    b = P.attention_block_fwd(x, *w, *shape[:4], True, q_scaled=True)[1]
+    assert P.rel(b, a) < 1e-14
+    ae = P.attention_block_fwd(x, *w, *shape[:4], True, emulate=True)[1]
+    be = P.attention_block_fwd(x, *w, *shape[:4], True, emulate=True, q_scaled=True)[1]
+    assert 0 < P.rel(be, ae) < 1e-2
