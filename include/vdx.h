@@ -628,6 +628,29 @@ int vdx_loss_grad(const float* eps_hat, const float* noise, float* d_eps_hat, in
 int vdx_adam_ema_step(float* params, const float* grads, float* m, float* v, float* ema, long n, float lr, float b1, float b2,
                       float eps, long step_count, float grad_scale, int do_ema, float ema_decay, void* stream);
 
+/* Gradient accumulation and global-norm clipping on the flat gradient buffer (the reference documents gradient_accumulate_every and
+ * max_grad_norm, trainer.py:65,71, and ships clip_grad_norm, utils.py:127-152, without calling either).  All tensors are the caller's,
+ * all work goes on `stream`, nothing synchronises, and no float is added atomically: every result is a function of its inputs only.
+ *
+ * vdx_grad_accumulate: acc[i] += g[i], i < n.  Called on bucket sub-ranges of the flat buffers, so acc and g may each sit on any
+ * 4-byte boundary (also two different ones) and n >= 1 is arbitrary. */
+int vdx_grad_accumulate(float* acc, const float* g, long n, void* stream);
+
+/* *out = sum_i (double)g[i]^2 (a float squared is exact in double; no underflow, no float overflow).  A fixed grid writes one
+ * partial per workgroup into scratch[vdx_grad_sqnorm_scratch_doubles()], a second one-workgroup kernel adds them in index order: the
+ * bits of *out depend on (g's values, n) only -- not on the device, on g's alignment or on the run.  g: any 4-byte boundary. */
+size_t vdx_grad_sqnorm_scratch_doubles(void);
+int vdx_grad_sqnorm(const float* g, long n, double* scratch, double* out, void* stream);
+
+/* vdx_adam_ema_step behind clip_grad_norm of the averaged gradient grad_scale * g.  From *sqnorm = sum g^2 (device,
+ * vdx_grad_sqnorm) every thread derives, in double,
+ *     l2 = sqrt(grad_scale^2 * *sqnorm + 1e-6);  clip = min(max_grad_norm / (l2 + 1e-6), 1);  s = (float)(grad_scale * clip)
+ * and runs vdx_adam_ema_step's arithmetic with g * s in place of g * grad_scale (clip == 1: bit-identical results).
+ * max_grad_norm > 0; FLT_MAX = no clipping, only the norm.  norm_out (device float, may be NULL) receives l2, the pre-clip norm. */
+int vdx_adam_ema_step_clip(float* params, const float* grads, float* m, float* v, float* ema, long n, float lr, float b1, float b2,
+                           float eps, long step_count, float grad_scale, int do_ema, float ema_decay, const double* sqnorm,
+                           float max_grad_norm, float* norm_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel communicator (reference trainer.py:161-177, 307-320: the batch is sharded over a 'data' mesh axis and XLA inserts
  * the all-reduce of every gradient behind jax.value_and_grad, trainer.py:361 -- SURVEY section 2, collective C1).  Here: one

@@ -3,7 +3,8 @@
 to the Trainer defaults (the reference indexes them and raises KeyError for its own v1_0..v2_2 files).
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N train.py --config ...` = one process per GPU over RCCL;
 `train_batch_size` stays the GLOBAL batch and is split over ranks like the reference splits it over devices.
-Extensions: --mode {bf16,f32}; --train_num_steps N; --dataset_path P (e.g. synthetic:64)."""
+Extensions: --mode {bf16,f32}; --train_num_steps N; --dataset_path P (e.g. synthetic:64); --apply_grad_args (gradient accumulation and
+global-norm clipping as the YAML's trainer section asks; without it both keys are ignored, as in the reference)."""
 import argparse
 import logging
 import os
@@ -19,6 +20,7 @@ FLAGS = (
     ('--mode', dict(choices=('bf16', 'f16', 'f32'), default='bf16', help='MFMA operand precision')),
     ('--train_num_steps', dict(type=int, default=None, help='override trainer.train_num_steps')),
     ('--dataset_path', dict(type=str, default=None, help='override trainer.dataset_path')),
+    ('--apply_grad_args', dict(action='store_true', help="honour the trainer section's gradient_accumulate_every and max_grad_norm")),
 )
 
 
@@ -51,6 +53,8 @@ def main(argv=None):
         tc['train_num_steps'] = a.train_num_steps
     if a.dataset_path is not None:
         tc['dataset_path'] = a.dataset_path
+    if a.apply_grad_args:
+        Trainer.apply_grad_args = True
     tc.pop('resume_training_step', None)             # the command-line flag wins, as in the reference
     trainer = Trainer(diffusion_model=gd, folder=tc.pop('folder'), resume_training_step=a.resume_step, rng_seed=seed, **tc)
     trainer.train()

@@ -1119,6 +1119,30 @@ int vdx_adam_ema_step(float* params, const float* grads, float* m, float* v, flo
     return VDX_OK;
 }
 
+int vdx_grad_accumulate(float* acc, const float* g, long n, void* stream) {
+    if (!acc || !g || n < 1 || ((uintptr_t)acc & 3) || ((uintptr_t)g & 3)) VDX_FAIL(VDX_ERR_INVALID, "grad_accumulate: bad argument");
+    VDX_HIP(vdx::launch_grad_accumulate(acc, g, n, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+size_t vdx_grad_sqnorm_scratch_doubles(void) { return vdx::grad_sqnorm_scratch_doubles(); }
+
+int vdx_grad_sqnorm(const float* g, long n, double* scratch, double* out, void* stream) {
+    if (!g || !scratch || !out || n < 1 || ((uintptr_t)g & 3)) VDX_FAIL(VDX_ERR_INVALID, "grad_sqnorm: bad argument");
+    VDX_HIP(vdx::launch_grad_sqnorm(g, n, scratch, out, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_adam_ema_step_clip(float* params, const float* grads, float* m, float* v, float* ema, long n, float lr, float b1, float b2,
+                           float eps, long step_count, float grad_scale, int do_ema, float ema_decay, const double* sqnorm,
+                           float max_grad_norm, float* norm_out, void* stream) {
+    if (!params || !grads || !m || !v || (do_ema && !ema) || !sqnorm || n < 1 || step_count < 0 || !(max_grad_norm > 0.f))
+        VDX_FAIL(VDX_ERR_INVALID, "adam_ema_step_clip: bad argument");
+    VDX_HIP(vdx::launch_adam_ema_clip(params, grads, m, v, ema, n, lr, b1, b2, eps, step_count, grad_scale, do_ema, ema_decay, sqnorm,
+                                      max_grad_norm, norm_out, (hipStream_t)stream));
+    return VDX_OK;
+}
+
 int vdx_comm_unique_id(void* unique_id_out) {
     if (!unique_id_out) VDX_FAIL(VDX_ERR_INVALID, "comm_unique_id: null argument");
     return vdx::comm_unique_id(unique_id_out);

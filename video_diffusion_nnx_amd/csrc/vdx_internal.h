@@ -209,6 +209,12 @@ hipError_t launch_affine(const float* x, float* y, long n, float a, float b, hip
 hipError_t launch_loss_grad(const float* eps_hat, const float* noise, float* d_eps, int B, int Cc, long fhw, int l2, hipStream_t st);
 hipError_t launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
                            long step_count, float grad_scale, int do_ema, float decay, hipStream_t st);
+hipError_t launch_adam_ema_clip(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
+                                long step_count, float grad_scale, int do_ema, float decay, const double* sqnorm, float max_grad_norm,
+                                float* norm_out, hipStream_t st);
+hipError_t launch_grad_accumulate(float* acc, const float* g, long n, hipStream_t st);
+size_t grad_sqnorm_scratch_doubles();
+hipError_t launch_grad_sqnorm(const float* g, long n, double* scratch, double* out, hipStream_t st);
 
 // Weight gradient of a conv (kind 0: (kh,kw)/stride SAME; kind 1: ConvTranspose 4x4/2): dW += Xhat^T (*) dY
 struct WgradArgs {

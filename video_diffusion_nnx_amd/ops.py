@@ -615,3 +615,34 @@ def adam_ema_step(p, g, m, v, ema, *, lr, b1, b2, eps, step_count, grad_scale=1.
     """In place on p, m, v (and ema when do_ema)."""
     L.check(_adam_ema(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), p.numel(), lr, b1, b2, eps, step_count, grad_scale, int(bool(do_ema)),
                       ema_decay, L.stream_ptr()))
+
+
+_grad_accumulate = L._sig('vdx_grad_accumulate', C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p])
+_grad_sqnorm_scratch = L._sig('vdx_grad_sqnorm_scratch_doubles', C.c_size_t, [])
+_grad_sqnorm = L._sig('vdx_grad_sqnorm', C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p])
+_adam_ema_clip = L._sig('vdx_adam_ema_step_clip', C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_float] * 4 + [C.c_long, C.c_float, C.c_int, C.c_float,
+                                                            C.c_void_p, C.c_float, C.c_void_p, C.c_void_p])
+
+
+def grad_accumulate(acc, g):
+    """acc += g in place; flat fp32 tensors (or contiguous slices of them, at any 4-byte offset) of equal length."""
+    assert acc.numel() == g.numel() and acc.dtype == g.dtype == torch.float32
+    L.check(_grad_accumulate(L.ptr(acc), L.ptr(g), acc.numel(), L.stream_ptr()))
+
+
+def grad_sqnorm(g, out=None):
+    """sum of g^2 in double -> device tensor [1] (float64); g flat fp32 at any 4-byte offset."""
+    assert g.dtype == torch.float32
+    scratch = torch.empty(_grad_sqnorm_scratch(), dtype=torch.float64, device=g.device)
+    out = torch.empty(1, dtype=torch.float64, device=g.device) if out is None else out
+    L.check(_grad_sqnorm(L.ptr(g), g.numel(), L.ptr(scratch), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def adam_ema_step_clip(p, g, m, v, ema, sqnorm, max_grad_norm, *, lr, b1, b2, eps, step_count, grad_scale=1.0, do_ema=True, ema_decay=0.995):
+    """adam_ema_step on g clipped to max_grad_norm by its global norm (sqnorm = grad_sqnorm(g), device); in place on p, m, v (and ema);
+    returns the device float [1] of the pre-clip norm of grad_scale * g."""
+    norm = torch.empty(1, dtype=torch.float32, device=p.device)
+    L.check(_adam_ema_clip(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), p.numel(), lr, b1, b2, eps, step_count, grad_scale, int(bool(do_ema)),
+                           ema_decay, L.ptr(sqnorm), max_grad_norm, L.ptr(norm), L.stream_ptr()))
+    return norm

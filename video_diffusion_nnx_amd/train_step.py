@@ -1,5 +1,7 @@
 """The device side of one train step (reference `_pjit_train_step`, trainer.py:322-392), driven stage by stage so the
-gradient all-reduce of finished buckets overlaps the rest of the backward."""
+gradient all-reduce of finished buckets overlaps the rest of the backward.  Two parts: forward + loss + backward of one micro-batch
+(`forward_backward`) and the optimizer tail (`optimizer_tail`); `run_train_step` is one of each, `run_train_step_accum` (behind
+Trainer.apply_grad_args) K micro-batches and one tail with optional global-norm clipping."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,6 +14,12 @@ from .gaussian_diffusion import split_key, vdx_loss_sum, vdx_q_sample
 _vp = C.c_void_p
 vdx_loss_grad = L._sig('vdx_loss_grad', C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_long, C.c_int, _vp])
 vdx_adam_ema_step = L._sig('vdx_adam_ema_step', C.c_int, [_vp] * 5 + [C.c_long] + [C.c_float] * 4 + [C.c_long, C.c_float, C.c_int, C.c_float, _vp])
+vdx_grad_accumulate = L._sig('vdx_grad_accumulate', C.c_int, [_vp, _vp, C.c_long, _vp])
+vdx_grad_sqnorm_scratch_doubles = L._sig('vdx_grad_sqnorm_scratch_doubles', C.c_size_t, [])
+vdx_grad_sqnorm = L._sig('vdx_grad_sqnorm', C.c_int, [_vp, C.c_long, _vp, _vp, _vp])
+vdx_adam_ema_step_clip = L._sig('vdx_adam_ema_step_clip', C.c_int, [_vp] * 5 + [C.c_long] + [C.c_float] * 4 + [C.c_long, C.c_float, C.c_int, C.c_float,
+                                                                    _vp, C.c_float, _vp, _vp])
+FLT_MAX = 3.4028234663852886e+38
 
 
 def stage_of_param(name: str, n_levels: int) -> int:
@@ -33,21 +41,34 @@ def stage_of_param(name: str, n_levels: int) -> int:
     raise KeyError(name)
 
 
-def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, noise: torch.Tensor = None) -> torch.Tensor:
-    """loss, grads = value_and_grad(p_losses); Adam; EMA  (trainer.py:337-382) for this rank's shard of the batch.
+def micro_step_keys(rng_seed: int, rank: int, step: int, j: int = 0):
+    """(t_key, noise_key) of micro-step j of optimizer step `step`: one stream per (seed, rank), split per step like
+    `key, step_key = split(key)` (trainer.py:541).  j = 0 is the plain train step's pair; micro-step j >= 1 first moves to child 3 + j of
+    the step key (children 1-3 belong to the split below)."""
+    step_key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
+    if j > 0:
+        step_key = split_key(step_key, 3 + j)[-1]
+    _, t_key, loss_key = split_key(step_key, 3)
+    _, noise_key, _ = split_key(loss_key, 3)
+    return t_key, noise_key
 
-    `t` [B] / `noise` [B,C,F,H,W] override this rank's own draws (the reference threads `noise` through p_losses the same way,
-    gaussian_diffusion.py:423-445); the data-parallel tests use them to give N ranks the shards of ONE global draw."""
+
+def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, j: int = 0, grads: torch.Tensor = None,
+                     reducer=None) -> torch.Tensor:
+    """loss, grads = value_and_grad(p_losses) (trainer.py:337-361) of one micro-batch; returns the device scalar loss.
+
+    `grads` (default tr.grads) receives the gradient: the head stage of the backward zeroes it.  With a `reducer` the backward runs
+    in stage groups and hands finished buckets of tr.grads to it; when `grads` is a second buffer (micro-steps j >= 1), each finished
+    bucket is first added into tr.grads on the current stream.  Without a reducer the backward is one call and nothing is reduced
+    (the caller adds `grads` into tr.grads)."""
     gd, unet = tr.model, tr.unet
     dev = tr.device
+    grads = tr.grads if grads is None else grads
     x = torch.as_tensor(batch).to(dev, torch.float32).contiguous()
     B = x.shape[0]
     assert tuple(x.shape[1:]) == (gd.channels, gd.num_frames, gd.image_size, gd.image_size), \
         f'expected [b, {gd.channels}, {gd.num_frames}, {gd.image_size}, {gd.image_size}], got {tuple(x.shape)}'     # check_shape (:490)
-    # keys: one stream per (seed, rank), split per step like `key, step_key = split(key)` (trainer.py:541)
-    step_key = split_key(split_key(tr.rng_seed, tr.rank + 1)[-1], step + 1)[-1]
-    _, t_key, loss_key = split_key(step_key, 3)
-    _, noise_key, _ = split_key(loss_key, 3)
+    t_key, noise_key = micro_step_keys(tr.rng_seed, tr.rank, step, j)
     if t is None:
         g = torch.Generator().manual_seed(t_key & 0x7FFFFFFFFFFFFFFF)
         t = torch.randint(0, gd.num_timesteps, (B,), generator=g, dtype=torch.int32)
@@ -74,25 +95,101 @@ def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, n
     loss = (acc / float(x.numel())).to(torch.float32).reshape(())
     d_eps = torch.empty_like(eps_hat)
     L.check(vdx_loss_grad(L.ptr(eps_hat), L.ptr(noise), L.ptr(d_eps), B, gd.channels, fhw, l2, L.stream_ptr()))
+    if reducer is None:
+        unet.backward(d_eps, grads)
+        return loss
     # reverse pass in groups of stages that end where a gradient bucket becomes complete: finished buckets are all-reduced (RCCL)
     # while earlier stages still run.  One call per group, not per stage: a call ends with the main stream waiting for the
     # weight-gradient stream (vdx_unet_backward), which nothing needs between bucket boundaries -- and never on one GPU.
-    reducer = tr.make_reducer()
     ns = unet.num_stages
     cuts = sorted({min(max(b[2], 0), ns - 1) for b in tr.buckets} | {0}, reverse=True) if reducer.enabled else [0]
-    hi = ns - 1
+    hi, nxt = ns - 1, 0
     for lo in cuts:
         if lo > hi:
             continue
-        unet.backward(d_eps, tr.grads, hi, lo)
+        unet.backward(d_eps, grads, hi, lo)
+        if grads is not tr.grads:
+            nxt = _accumulate_ready(tr, grads, nxt, lo)
         for stage in range(hi, lo - 1, -1):
             reducer.stage_done(stage)
         hi = lo - 1
-    reducer.finish()
+    if grads is not tr.grads:
+        _accumulate_ready(tr, grads, nxt, -1)
+    return loss
+
+
+def _accumulate_ready(tr, micro: torch.Tensor, nxt: int, stage: int) -> int:
+    """tr.grads += micro over the buckets from index `nxt` that are complete once the backward has run `stage` (the test of
+    GradBucketReducer.stage_done); buckets are contiguous in ready order, so they go as one range.  Returns the next bucket index."""
+    first = nxt
+    while nxt < len(tr.buckets) and tr.buckets[nxt][2] >= stage:
+        nxt += 1
+    if nxt > first:
+        lo, hi = tr.buckets[nxt - 1][0], tr.buckets[first][1]
+        L.check(vdx_grad_accumulate(tr.grads.data_ptr() + 4 * lo, micro.data_ptr() + 4 * lo, hi - lo, L.stream_ptr()))
+    return nxt
+
+
+def optimizer_tail(tr, step: int, world: int, accum: int = 1, max_grad_norm=None, want_norm: bool = False) -> None:
+    """Adam + EMA on the summed gradient in tr.grads (trainer.py:367-382); the mean over ranks and micro-batches is folded into the
+    gradient read.  With max_grad_norm (or want_norm) the step goes through the sum of squares of tr.grads and the clipping form of
+    the kernel, and tr.last_grad_norm holds the device float of the pre-clip norm; the host reads nothing."""
+    unet = tr.unet
+    n = unet.flat_params.numel()
     lr = tr.current_lr(tr.opt_count)                                               # schedule at the pre-increment count (B.2)
     do_ema = int(step >= tr.step_start_ema and step % tr.update_ema_every == 0)    # trainer.py:373-374
-    L.check(vdx_adam_ema_step(L.ptr(unet.flat_params), L.ptr(tr.grads), L.ptr(tr.m), L.ptr(tr.v), L.ptr(tr.ema), unet.flat_params.numel(),
-                              lr, 0.9, 0.999, 1e-8, tr.opt_count, 1.0 / reducer.world, do_ema, tr.ema_decay, L.stream_ptr()))
+    grad_scale = 1.0 / (world * accum)
+    if max_grad_norm is None and not want_norm:
+        L.check(vdx_adam_ema_step(L.ptr(unet.flat_params), L.ptr(tr.grads), L.ptr(tr.m), L.ptr(tr.v), L.ptr(tr.ema), n,
+                                  lr, 0.9, 0.999, 1e-8, tr.opt_count, grad_scale, do_ema, tr.ema_decay, L.stream_ptr()))
+    else:
+        if getattr(tr, '_sqnorm', None) is None:
+            tr._sqnorm = torch.empty(vdx_grad_sqnorm_scratch_doubles() + 1, dtype=torch.float64, device=tr.device)
+            tr.last_grad_norm = torch.zeros(1, dtype=torch.float32, device=tr.device)
+        sq = tr._sqnorm
+        L.check(vdx_grad_sqnorm(L.ptr(tr.grads), n, sq.data_ptr() + 8, sq.data_ptr(), L.stream_ptr()))
+        L.check(vdx_adam_ema_step_clip(L.ptr(unet.flat_params), L.ptr(tr.grads), L.ptr(tr.m), L.ptr(tr.v), L.ptr(tr.ema), n,
+                                       lr, 0.9, 0.999, 1e-8, tr.opt_count, grad_scale, do_ema, tr.ema_decay, sq.data_ptr(),
+                                       FLT_MAX if max_grad_norm is None else float(max_grad_norm), L.ptr(tr.last_grad_norm), L.stream_ptr()))
     tr.opt_count += 1
     unet.mark_params_updated()
+
+
+def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, noise: torch.Tensor = None) -> torch.Tensor:
+    """loss, grads = value_and_grad(p_losses); Adam; EMA  (trainer.py:337-382) for this rank's shard of the batch.
+
+    `t` [B] / `noise` [B,C,F,H,W] override this rank's own draws (the reference threads `noise` through p_losses the same way,
+    gaussian_diffusion.py:423-445); the data-parallel tests use them to give N ranks the shards of ONE global draw."""
+    reducer = tr.make_reducer()
+    loss = forward_backward(tr, batch, step, t, noise, reducer=reducer)
+    reducer.finish()
+    optimizer_tail(tr, step, reducer.world)
     return loss
+
+
+def run_train_step_accum(tr, batches, step: int, ts=None, noises=None) -> torch.Tensor:
+    """One optimizer step on the mean gradient of K = len(batches) micro-batches of this rank (Trainer.apply_grad_args).
+
+    Micro-step 0 is run_train_step's path into tr.grads; micro-steps j >= 1 write tr.micro_grads and are added into tr.grads.  Only the
+    last micro-step runs the staged backward and starts the all-reduce, bucket by bucket, after the bucket's accumulation: one
+    reduction per optimizer step, still overlapped with the backward.  Returns the mean of the K device losses."""
+    K = len(batches)
+    assert K >= 1
+    ts = [None] * K if ts is None else ts
+    noises = [None] * K if noises is None else noises
+    if K > 1 and getattr(tr, 'micro_grads', None) is None:
+        tr.micro_grads = torch.zeros_like(tr.grads)
+    reducer = tr.make_reducer()
+    losses = []
+    for j in range(K):
+        grads = tr.grads if j == 0 else tr.micro_grads
+        if j < K - 1:
+            losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads))
+            if j > 0:
+                L.check(vdx_grad_accumulate(L.ptr(tr.grads), L.ptr(grads), grads.numel(), L.stream_ptr()))
+        else:
+            losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, reducer=reducer))
+    reducer.finish()
+    max_norm = tr.max_grad_norm
+    optimizer_tail(tr, step, reducer.world, accum=K, max_grad_norm=max_norm, want_norm=tr.track_grad_norm)
+    return losses[0] if K == 1 else torch.stack(losses).mean()

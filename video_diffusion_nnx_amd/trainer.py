@@ -5,8 +5,11 @@ Same constructor signature and `.train(prob_focus_present, focus_present_mask, l
 all-reduce -> Adam -> EMA, all on the device through libvdx.so; data parallelism = one process per GPU with
 `torch.distributed` (RCCL), the flat gradient buffer reduced in buckets in reverse-layer order so the
 all-reduce of early buckets overlaps the rest of the backward.
-Accepted-and-unused arguments are the reference's own: folder, num_frames, gradient_accumulate_every,
-save_and_sample_every, num_sample_rows, max_grad_norm, sample_text, cond_scale, add_loss_plot.
+Accepted-and-unused arguments are the reference's own: folder, num_frames, save_and_sample_every, num_sample_rows,
+sample_text, cond_scale, add_loss_plot.  gradient_accumulate_every and max_grad_norm are unused in the reference too (it marks the first
+TODO and never calls its clip_grad_norm); here they are honoured behind `Trainer.apply_grad_args = True`: one optimizer step then takes
+K = gradient_accumulate_every micro-batches per rank (one all-reduce per optimizer step) and clips the averaged gradient to
+max_grad_norm by its global L2 norm, on the device (train_step.run_train_step_accum).
 """
 from __future__ import annotations
 
@@ -130,6 +133,12 @@ class Trainer:
     # gradient all-reduce bucket size (floats): >= 16 MB per RCCL call keeps every xGMI ring step bandwidth-bound; the
     # constructor signature stays the reference's, so this is a class attribute
     min_bucket_floats = 4 << 20
+    # False: gradient_accumulate_every and max_grad_norm are stored and ignored, as in the reference.  True: train() takes
+    # K = max(1, gradient_accumulate_every) micro-batches per optimizer step (train_step_accum) and clips the averaged gradient to
+    # max_grad_norm (None = no clipping).  A class attribute for the same reason as the ones above.
+    apply_grad_args = False
+    # with apply_grad_args: compute the gradient norm (last_grad_norm, 'grad_norm/train') also when max_grad_norm is None
+    track_grad_norm = False
 
     def __init__(self, diffusion_model, folder: str, *, rng_seed: int = 0, dataset_path: str, num_frames: int = 16,
                  train_batch_size: int = 4, train_lr: float = 1e-4, train_num_steps: int = 100000,
@@ -169,6 +178,8 @@ class Trainer:
         self.ema = self.unet.flat_params.clone()
         self.grads = torch.zeros(n, dtype=torch.float32, device=self.device)
         self.opt_count = 0                                       # optax count: restarts at 0 on resume
+        self.micro_grads = None                                  # second gradient buffer, allocated by the first K > 1 step
+        self.last_grad_norm = None                               # device float of the last pre-clip gradient norm
         from .train_step import stage_of_param
         nlev = len(self.unet.dim_mults)
         self.buckets = make_buckets(self.unet.param_table, n, lambda nm: stage_of_param(nm, nlev), stage_of_param('__count__', nlev),
@@ -261,6 +272,19 @@ class Trainer:
         from .train_step import run_train_step
         return run_train_step(self, batch, step, t=t, noise=noise)
 
+    @property
+    def accum_steps(self) -> int:
+        """Micro-batches per optimizer step: gradient_accumulate_every behind apply_grad_args, else 1."""
+        return max(1, int(self.gradient_accumulate_every)) if self.apply_grad_args else 1
+
+    def train_step_accum(self, batches, step: int, ts=None, noises=None) -> torch.Tensor:
+        """One optimizer step on K = len(batches) shards of this rank: the gradient is the mean over the K micro-batches (and the
+        ranks), clipped to max_grad_norm when that is set.  Returns the (device) mean of the K losses; `last_grad_norm` holds the
+        device float of the pre-clip norm when one was computed.  ts / noises: optional per-micro-batch lists, as train_step's."""
+        from .train_step import run_train_step_accum
+        assert self.apply_grad_args, 'train_step_accum is the path behind Trainer.apply_grad_args = True'
+        return run_train_step_accum(self, list(batches), step, ts=ts, noises=noises)
+
     def train(self, prob_focus_present: float = 0.0, focus_present_mask=None, log_fn=noop):
         assert callable(log_fn)
         logging.info(f'Starting training loop from step {self.step}...')
@@ -280,12 +304,12 @@ class Trainer:
                 pass
         first_step = self.step
         while self.step < self.train_num_steps:
-            shard = next(shards)
+            shard = [next(shards) for _ in range(self.accum_steps)] if self.apply_grad_args else next(shards)
             t0 = time.time()
             traced = self.device.type == 'cuda' and self.step - first_step < max(0, int(self.profile_flush_step))
             if traced:
                 _range(True, f'train_step {self.step}')
-            loss = self.train_step(shard, self.step)
+            loss = self.train_step_accum(shard, self.step) if self.apply_grad_args else self.train_step(shard, self.step)
             if traced:
                 _range(False)
             if self.dist_on and self.world > 1:                  # global mean loss = mean of equal-size shard means (C2)
@@ -297,6 +321,8 @@ class Trainer:
             log_fn({'loss': current_loss, 'step': self.step})
             self._scalar('loss/train', current_loss, self.step)
             self._scalar('lr/train', self.current_lr(self.step), self.step)
+            if self.apply_grad_args and (self.max_grad_norm is not None or self.track_grad_norm) and self.last_grad_norm is not None:
+                self._scalar('grad_norm/train', float(self.last_grad_norm.item()), self.step)      # the host's only read of the norm
             if self.step > 0 and self.step % self.checkpoint_every_steps == 0:     # cadence: before step += 1 (trainer.py:593,604)
                 logging.info(f'Step: {self.step} | Saving checkpoint...')
                 self._save(self.step)
