@@ -437,6 +437,51 @@ int vdx_ddim_sample_loop_masked(vdx_handle* h, const float* params, const void* 
                                 const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
                                 void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
 
+/* DPM-Solver++(2M) sampling (EXTENSION, parity unpinned: no reference code.  Lu et al. 2022, "DPM-Solver++", the data-prediction
+ * multistep form): the same one network evaluation per step as DDIM, second order through one history tensor the size of the image.
+ * With a_t = alphas_cumprod[t]: alpha_t = sqrt(a_t), sigma_t = sqrt(1 - a_t), lambda_t = 0.5 ln(a_t / (1 - a_t)).  seq as in
+ * vdx_ddim_step (n + 1 entries, the last -1 = the data).  Step k = *step_dev (or 0 when step_dev is NULL) goes from s = seq[k] to
+ * n = seq[k+1]:
+ *   x0 = (x - sigma_s eps) / alpha_s                  clipped exactly as vdx_ddim_step does (+-1, or +-thres[b] then / thres[b])
+ *   n < 0:  out = x0                                  (the step into the data is first order; in [-1, 1] when clipping)
+ *   else    h = lambda_n - lambda_s
+ *           D = x0                                    if k == 0 or order == 1
+ *           D = (1 + c) x0 - c hist,  c = h / (2 (lambda_s - lambda_{seq[k-1]}))       otherwise
+ *           out = (sigma_n / sigma_s) x - alpha_n expm1(-h) D
+ *   hist = x0                                         (written on every step when hist is given)
+ * Whether a step is first or second order is decided from *step_dev on the device, so one captured step serves every k.  order is 1
+ * or 2; order 1 is algebraically vdx_ddim_step (including its re-derivation of eps from the clipped x0) and may pass hist = NULL.
+ * hist [B,C,F,H,W] floats: read (k >= 1, order 2) before it is written, by the same thread.  The kernels move 4 elements at a time:
+ * per_sample % 4 == 0, x / out / hist 16-byte aligned (checked: VDX_ERR_INVALID).  x and out may alias; hist may alias neither. */
+int vdx_dpm_step(const float* x, const float* eps_hat, float* out, float* hist, const float* alphas_cumprod, const int* seq,
+                 const uint64_t* step_dev, const float* thres, int clip_denoised, int order, int batch, int channels, long per_sample,
+                 void* stream);
+
+/* vdx_dpm_step with the known region merged as vdx_ddim_step_masked does: kn = seq[k+1] < 0 ? known : sqrt_ac[n] known +
+ * sqrt(1 - ac[n]) Philox(seed, VDX_DRAW_KNOWN + k); out = mask ? kn : x'.  hist holds the network's x0 everywhere.  An all-zero mask
+ * is vdx_dpm_step bit for bit. */
+int vdx_dpm_step_masked(const float* x, const float* eps_hat, float* out, float* hist, const float* alphas_cumprod, const int* seq,
+                        const uint64_t* step_dev, const float* thres, int clip_denoised, int order, const float* known,
+                        const unsigned char* mask, const float* mask_tables, int timesteps, uint64_t seed, int batch, int channels,
+                        long per_sample, void* stream);
+
+/* The DPM-Solver++ loop: nsteps x { Unet3D forward at t = seq[k] ; (dynamic threshold) ; vdx_dpm_step ; t = max(seq[k+1], 0), k += 1 },
+ * captured once in a hipGraph like vdx_ddim_sample_loop_dyn, whose arguments it takes plus hist and order.  t_dev [B] must hold seq[0]
+ * and *step_dev 0 on entry; a loop issued in pieces continues from t_dev / step_dev / hist.  percentile <= 0: static clip.  Own graph
+ * slot: does not evict the graphs of the other loops. */
+int vdx_dpm_sample_loop(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
+                        uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                        int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
+                        void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
+
+/* vdx_dpm_sample_loop with vdx_dpm_step_masked as the step; img holds vdx_inpaint_init's output (t0 = seq[0]) on entry.  timesteps is
+ * required (mask_tables' row length) even without the dynamic threshold.  Own graph slot. */
+int vdx_dpm_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
+                               uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                               int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
+                               const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
+                               void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */

@@ -2,6 +2,7 @@
 --output-path, --checkpoint-path, --step, --seed, --batch-size, --load-ema-params) and its YAML schema, then runs
 GaussianDiffusion.sample on the GPU and writes one GIF per video (batch-global min-max to uint8, 120 ms/frame).
 Extensions: --mode {bf16,f16,f32}; --random-init (no checkpoint); --timesteps N (shorter chain for smoke runs); --ddim-steps S;
+--dpm-steps S [--dpm-order 1|2] (DPM-Solver++(2M) chain; not together with --ddim-steps);
 --attn-fp8 (bf16 mode: QK^T / PV of the <= 16-token attention blocks on fp8 MFMA operands);
 --context PATH.npy [--context-frames K] [--extend-frames N] [--resample-steps U] (video prediction / extension from given frames)."""
 import argparse
@@ -24,6 +25,9 @@ FLAGS = (   # (flag, kwargs)
     ('--random-init', dict(action='store_true', help='skip the checkpoint, use freshly initialised weights')),
     ('--timesteps', dict(type=int, default=None, help='override diffusion.timesteps')),
     ('--ddim-steps', dict(type=int, default=None, help='sample with an S-step DDIM chain (eta = 0) instead of the T-step ancestral one')),
+    ('--dpm-steps', dict(type=int, default=None, help='sample with an S-step DPM-Solver++(2M) chain (about 20 steps do what DDIM needs 100 for); '
+                                                      'not together with --ddim-steps')),
+    ('--dpm-order', dict(type=int, choices=(1, 2), default=2, help='with --dpm-steps: 2 = second-order multistep, 1 = first order (= DDIM)')),
     ('--attn-fp8', dict(action='store_true', help='bf16 mode: fp8 (e4m3) QK^T / PV in the attention blocks over <= 16 tokens')),
     ('--context', dict(type=str, default=None, help='[B,C,F,H,W] .npy clip (float in [0,1], or uint8 / 255): generate its continuation '
                                                     'instead of sampling from noise; sets the batch')),
@@ -71,6 +75,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.checkpoint_path is None and not a.random_init:
         ap.error('--checkpoint-path is required (or pass --random-init)')
+    if a.dpm_steps is not None and a.ddim_steps is not None:
+        ap.error('--dpm-steps and --ddim-steps are two samplers: give one of them')
 
     # one process per GPU under `python -m torch.distributed.run --nproc-per-node N sample.py ...` (reference gaussian_diffusion.py:278-298
     # shards the batch over the local devices): every rank draws batch_size / N of the videos and writes its own GIFs
@@ -115,9 +121,10 @@ def _run(a, ap, rank, world):
         # the first window conditions on every kept frame (up to num_frames - 1), later windows on at least num_frames // 2
         window_ctx = min(max(ctx.shape[2], gd.num_frames // 2), gd.num_frames - 1)
         videos = gd.extend(a.seed, torch.from_numpy(ctx), n_new, context_frames=window_ctx, ddim_steps=a.ddim_steps,
-                           resample_steps=a.resample_steps)            # this rank's shard of the global batch
+                           resample_steps=a.resample_steps, dpm_steps=a.dpm_steps, dpm_order=a.dpm_order)      # this rank's shard of the global batch
     else:
-        videos = gd.sample(a.seed, batch_size=a.batch_size, ddim_steps=a.ddim_steps)          # this rank's shard of the global batch
+        videos = gd.sample(a.seed, batch_size=a.batch_size, ddim_steps=a.ddim_steps, dpm_steps=a.dpm_steps,
+                           dpm_order=a.dpm_order)                       # this rank's shard of the global batch
     logging.info('rank %d drew %d videos', rank, len(videos))
     lo_hi = None
     if world > 1:                                      # the uint8 scaling is batch-GLOBAL (reference sample.py:107-110): two scalars cross ranks

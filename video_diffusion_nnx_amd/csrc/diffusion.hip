@@ -306,6 +306,110 @@ __global__ __launch_bounds__(256) void ddim_step_masked_kernel(const float* x, c
     }
 }
 
+// DPM-Solver++(2M) step (Lu et al. 2022, data-prediction multistep form; NO reference code: EXTENSION, parity unpinned).  With
+// a_t = ac[t]: alpha_t = sqrt(a_t), sigma_t = sqrt(1 - a_t), lambda_t = 0.5 ln(a_t / (1 - a_t)).  Step k = *step_dev (or 0) goes
+// from s = seq[k] to n = seq[k+1]:
+//   x0 = (x - sigma_s eps) / alpha_s                 [clipped exactly as ddim_elem does]
+//   n < 0:  out = x0                                  (the step into the data is first order)
+//   else    h = lambda_n - lambda_s
+//           D = x0                                    if k == 0 or order == 1
+//           D = (1 + c) x0 - c hist,  c = h / (2 (lambda_s - lambda_{seq[k-1]}))   otherwise
+//           out = (sigma_n / sigma_s) x - alpha_n expm1(-h) D
+//   hist = x0                                         (every step; each thread reads its hist element before it writes it)
+// order == 1 is ddim_step_kernel's update written in lambda.  The per-step scalars are evaluated in double by one thread of the
+// workgroup (h and expm1(-h) are differences of nearly equal numbers on a fine sequence) and handed on as fp32.
+struct DpmCoef { float sa, s1, r, g, c1, c, s; int clip, last, second; };
+
+__device__ DpmCoef dpm_coef(const float* ac, const int* seq, int k, int order, const float* thres, int b, int clip) {
+    const int ts = seq[k], tn = seq[k + 1];
+    const double a_s = (double)ac[ts];
+    const double al_s = sqrt(a_s), sg_s = sqrt(1.0 - a_s);
+    DpmCoef K;
+    K.sa = (float)al_s; K.s1 = (float)sg_s;
+    K.s = thres ? thres[b] : 1.0f;
+    K.clip = clip;
+    K.last = tn < 0;
+    K.second = 0;
+    K.r = 0.f; K.g = 1.f; K.c1 = 1.f; K.c = 0.f;
+    if (tn >= 0) {
+        const double a_n = (double)ac[tn];
+        const double lam_s = 0.5 * log(a_s / (1.0 - a_s)), lam_n = 0.5 * log(a_n / (1.0 - a_n));
+        const double h = lam_n - lam_s;
+        K.r = (float)(sqrt(1.0 - a_n) / sg_s);
+        K.g = (float)(-sqrt(a_n) * expm1(-h));
+        if (order == 2 && k > 0) {
+            const double a_p = (double)ac[seq[k - 1]];
+            const double c = h / (2.0 * (lam_s - 0.5 * log(a_p / (1.0 - a_p))));
+            K.c1 = (float)(1.0 + c); K.c = (float)c;
+            K.second = 1;
+        }
+    }
+    return K;
+}
+
+// the contractions are spelled out, as in ddim_elem: an all-zero mask must give the unmasked kernel's values bit for bit
+__device__ __forceinline__ float dpm_elem(const DpmCoef& k, float xv, float ev, float hv, float* x0_out) {
+#pragma clang fp contract(off)
+    float x0 = fmaf(-k.s1, ev, xv) / k.sa;
+    if (k.clip) x0 = fminf(fmaxf(x0, -k.s), k.s) / k.s;
+    *x0_out = x0;
+    if (k.last) return x0;
+    const float d = k.second ? fmaf(k.c1, x0, -(k.c * hv)) : x0;
+    return fmaf(k.r, xv, k.g * d);
+}
+
+// 4 elements per thread (float4 x / hist / known / out, uchar4 mask; per_sample % 4 == 0).  x and out may alias.  MASKED merges the
+// known region exactly as ddim_step_masked_kernel does; hist holds the network's x0 in the known region too.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void dpm_step_kernel(const float* x, const float* __restrict__ eps, float* out, float* hist,
+                                                       const float* __restrict__ ac, const int* __restrict__ seq,
+                                                       const unsigned long long* __restrict__ step_dev, const float* __restrict__ thres,
+                                                       int clip, int order, int C, long per_sample, MaskArgs M, int T, unsigned long long seed) {
+    __shared__ DpmCoef coef;
+    const int b = blockIdx.y;
+    const int j = step_dev ? (int)*step_dev : 0;
+    if (threadIdx.x == 0) coef = dpm_coef(ac, seq, j, order, thres, b, clip);
+    __syncthreads();
+    const DpmCoef kc = coef;
+    const int tn = seq[j + 1];
+    float ka = 1.f, kb = 0.f;
+    if (MASKED && tn >= 0) { ka = M.mtab[tn]; kb = M.mtab[T + tn]; }
+    const long per = per_sample, fhw = per_sample / C;
+    const size_t base = (size_t)b * per;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; 4 * q < per; q += (long)gridDim.x * blockDim.x) {
+        const long i = 4 * q;
+        const float4 x4 = *reinterpret_cast<const float4*>(x + base + i);
+        float4 h4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (kc.second) h4 = *reinterpret_cast<const float4*>(hist + base + i);
+        const float xv[4] = {x4.x, x4.y, x4.z, x4.w};
+        const float hv[4] = {h4.x, h4.y, h4.z, h4.w};
+        float o[4], p[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long e = i + k, c = e / fhw, r = e - c * fhw;                 // [C,F,H,W] -> channel-last [F,H,W,C]
+            o[k] = dpm_elem(kc, xv[k], eps[base + r * C + c], hv[k], &p[k]);
+        }
+        if (hist) *reinterpret_cast<float4*>(hist + base + i) = make_float4(p[0], p[1], p[2], p[3]);
+        if (MASKED) {
+            const uchar4 m4 = *reinterpret_cast<const uchar4*>(M.mask + base + i);
+            const bool mk[4] = {m4.x != 0, m4.y != 0, m4.z != 0, m4.w != 0};
+            if (mk[0] | mk[1] | mk[2] | mk[3]) {
+                const float4 k4 = *reinterpret_cast<const float4*>(M.known + base + i);
+                const float kv[4] = {k4.x, k4.y, k4.z, k4.w};
+                float zk[4] = {0.f, 0.f, 0.f, 0.f};
+                if (tn >= 0) {
+                    const float4 w = randn4((unsigned long long)(base / 4 + q), seed, VDX_DRAW_KNOWN + (unsigned long long)j);
+                    zk[0] = w.x; zk[1] = w.y; zk[2] = w.z; zk[3] = w.w;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (mk[k]) o[k] = tn >= 0 ? ka * kv[k] + kb * zk[k] : kv[k];
+            }
+        }
+        *reinterpret_cast<float4*>(out + base + i) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
 // after a DDIM step: t[b] = max(seq[k + 1], 0) for the next forward, k += 1
 __global__ void ddim_advance_kernel(int* t, int B, const int* __restrict__ seq, unsigned long long* step_dev) {
     const int k = (int)*step_dev;
@@ -447,6 +551,22 @@ hipError_t launch_ddim_step_masked(const float* x, const float* eps, float* out,
     LaunchScope ls(st, "ddim_step_masked_kernel", 0.0, 17.0 * B * per_sample, "B%d px%ld", B, per_sample);
     hipLaunchKernelGGL(ddim_step_masked_kernel, dim3(ew_blocks(per_sample / 4), B), dim3(256), 0, st, x, eps, out, ac, seq, step_dev, thres, clip, C,
                        per_sample, m, T, seed);
+    return hipGetLastError();
+}
+
+hipError_t launch_dpm_step(const float* x, const float* eps, float* out, float* hist, const float* ac, const int* seq,
+                           const unsigned long long* step_dev, const float* thres, int clip, int order, int B, int C, long per_sample,
+                           const MaskArgs* m, int T, unsigned long long seed, hipStream_t st) {
+    const dim3 grid(ew_blocks(per_sample / 4), B);
+    if (m) {
+        LaunchScope ls(st, "dpm_step_masked_kernel", 0.0, 25.0 * B * per_sample, "B%d px%ld o%d", B, per_sample, order);
+        hipLaunchKernelGGL(dpm_step_kernel<true>, grid, dim3(256), 0, st, x, eps, out, hist, ac, seq, step_dev, thres, clip, order, C, per_sample,
+                           *m, T, seed);
+    } else {
+        LaunchScope ls(st, "dpm_step_kernel", 0.0, 20.0 * B * per_sample, "B%d px%ld o%d", B, per_sample, order);
+        hipLaunchKernelGGL(dpm_step_kernel<false>, grid, dim3(256), 0, st, x, eps, out, hist, ac, seq, step_dev, thres, clip, order, C, per_sample,
+                           MaskArgs{}, 0, 0ull);
+    }
     return hipGetLastError();
 }
 

@@ -9,8 +9,8 @@
 struct vdx_handle {
     vdx::Model model;
     // every argument a captured sampling step bakes in (full pointers: two workspaces / streams never alias one key)
-    struct GraphKey { const void* p[16]; unsigned long long seed; int i[5]; size_t ws; float f; };
-    // one cached graph per loop kind: 0 = DDPM p_sample_loop, 1 = DDIM, 2 = masked DDPM, 3 = masked DDIM
+    struct GraphKey { const void* p[17]; unsigned long long seed; int i[6]; size_t ws; float f; };
+    // one cached graph per loop kind: 0 = DDPM p_sample_loop, 1 = DDIM, 2 = masked DDPM, 3 = masked DDIM, 4 = DPM-Solver++, 5 = masked DPM-Solver++
     // `last` = the stream the exec was last launched on: replays may still be running when the graph has to go
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key; hipStream_t last = nullptr;
@@ -20,7 +20,7 @@ struct vdx_handle {
             if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
             last = nullptr;
         }
-    } gs[4];
+    } gs[6];
     void drop_graphs() { for (GraphSlot& g : gs) g.drop(); }
     vdx::BwdState bwd;
     vdx::Comm comm;
@@ -806,6 +806,104 @@ int vdx_ddim_sample_loop_masked(vdx_handle* h, const float* params, const void* 
     key.seed = seed; key.i[0] = seq_len; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch; key.i[3] = timesteps;
     key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
     return run_steps(h, 3, key, nsteps, use_graph, st, step);
+}
+
+int vdx_dpm_step(const float* x, const float* eps_hat, float* out, float* hist, const float* alphas_cumprod, const int* seq,
+                 const uint64_t* step_dev, const float* thres, int clip_denoised, int order, int batch, int channels, long per_sample,
+                 void* stream) {
+    if (!x || !eps_hat || !out || !alphas_cumprod || !seq || batch < 1 || channels < 1 || per_sample < 1 || per_sample % channels)
+        VDX_FAIL(VDX_ERR_INVALID, "dpm_step: bad argument");
+    if (order != 1 && order != 2) VDX_FAIL(VDX_ERR_INVALID, "dpm_step: order must be 1 or 2");
+    if (order == 2 && !hist) VDX_FAIL(VDX_ERR_INVALID, "dpm_step: order 2 needs hist");
+    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "dpm_step: per_sample must be a multiple of 4");
+    if ((uintptr_t)x % 16 || (uintptr_t)out % 16 || (uintptr_t)hist % 16) VDX_FAIL(VDX_ERR_INVALID, "dpm_step: x / out / hist must be 16-byte aligned");
+    VDX_HIP(vdx::launch_dpm_step(x, eps_hat, out, hist, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev), thres,
+                                 clip_denoised, order, batch, channels, per_sample, nullptr, 0, 0ull, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_dpm_step_masked(const float* x, const float* eps_hat, float* out, float* hist, const float* alphas_cumprod, const int* seq,
+                        const uint64_t* step_dev, const float* thres, int clip_denoised, int order, const float* known,
+                        const unsigned char* mask, const float* mask_tables, int timesteps, uint64_t seed, int batch, int channels,
+                        long per_sample, void* stream) {
+    if (!x || !eps_hat || !out || !alphas_cumprod || !seq || !known || !mask || !mask_tables || timesteps < 1 || batch < 1 || channels < 1 ||
+        per_sample < 1 || per_sample % channels)
+        VDX_FAIL(VDX_ERR_INVALID, "dpm_step_masked: bad argument");
+    if (order != 1 && order != 2) VDX_FAIL(VDX_ERR_INVALID, "dpm_step_masked: order must be 1 or 2");
+    if (order == 2 && !hist) VDX_FAIL(VDX_ERR_INVALID, "dpm_step_masked: order 2 needs hist");
+    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "dpm_step_masked: per_sample must be a multiple of 4");
+    if (!masked_aligned(x, known, out, mask) || (uintptr_t)hist % 16)
+        VDX_FAIL(VDX_ERR_INVALID, "dpm_step_masked: x / known / out / hist must be 16-byte and mask 4-byte aligned");
+    const vdx::MaskArgs m = {known, mask, mask_tables, 1, 0ull, nullptr};
+    VDX_HIP(vdx::launch_dpm_step(x, eps_hat, out, hist, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev), thres,
+                                 clip_denoised, order, batch, channels, per_sample, &m, timesteps, seed, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+// the two DPM-Solver++ loops: ma == nullptr is the unmasked one (graph slot 4), else the masked one (slot 5)
+static int dpm_loop(const char* who, vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
+                    uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                    int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
+                    const vdx::MaskArgs* ma, uint64_t seed, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    char msg[160];
+#define DPM_FAIL(code, text) do { snprintf(msg, sizeof(msg), "%s: %s", who, text); VDX_FAIL(code, msg); } while (0)
+    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !alphas_cumprod || !seq || !workspace) DPM_FAIL(VDX_ERR_INVALID, "null argument");
+    if (ma && (!ma->known || !ma->mask || !ma->mtab)) DPM_FAIL(VDX_ERR_INVALID, "null argument");
+    if (!h->model.d_ss_layers) DPM_FAIL(VDX_ERR_STATE, "handle was created without a GPU");
+    if (order != 1 && order != 2) DPM_FAIL(VDX_ERR_INVALID, "order must be 1 or 2");
+    if (order == 2 && !hist) DPM_FAIL(VDX_ERR_INVALID, "order 2 needs hist");
+    if (seq_len < 1 || nsteps < 0 || nsteps > seq_len) DPM_FAIL(VDX_ERR_INVALID, "nsteps out of range");
+    if (ma && timesteps < 1) DPM_FAIL(VDX_ERR_INVALID, "timesteps (the row length of mask_tables) must be >= 1");
+    const bool dyn = percentile > 0.f && clip_denoised;
+    if (dyn && (!thres_buf || !tables || timesteps < 1 || percentile > 1.f)) DPM_FAIL(VDX_ERR_INVALID, "dynamic threshold needs tables, thres_buf and a percentile in (0, 1]");
+    const vdx::Model& m = h->model;
+    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
+    if (per_sample % 4) DPM_FAIL(VDX_ERR_INVALID, "C*F*H*W must be a multiple of 4");
+    if (m.out_dim != m.cfg.channels) DPM_FAIL(VDX_ERR_INVALID, "out_dim must equal channels");
+    if ((uintptr_t)img % 16 || (uintptr_t)hist % 16 || (ma && !masked_aligned(img, ma->known, img, ma->mask)))
+        DPM_FAIL(VDX_ERR_INVALID, "img / hist / known must be 16-byte and mask 4-byte aligned");
+#undef DPM_FAIL
+    hipStream_t st = (hipStream_t)stream;
+    auto step = [&]() -> int {
+        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
+        if (rc != VDX_OK) return rc;
+        hipError_t e = hipSuccess;
+        if (dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
+        if (e == hipSuccess) e = vdx::launch_dpm_step(img, eps_buf, img, hist, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev),
+                                                      dyn ? thres_buf : nullptr, clip_denoised, order, batch, m.cfg.channels, per_sample, ma,
+                                                      timesteps, seed, st);
+        if (e == hipSuccess) e = vdx::launch_ddim_advance(t_dev, batch, seq, reinterpret_cast<unsigned long long*>(step_dev), st);
+        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        return VDX_OK;
+    };
+    vdx_handle::GraphKey key;
+    memset(&key, 0, sizeof(key));
+    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
+    key.p[6] = alphas_cumprod; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = seq; key.p[11] = dyn ? (const void*)thres_buf : nullptr;
+    if (ma) { key.p[12] = ma->known; key.p[13] = ma->mask; key.p[14] = ma->mtab; }
+    key.p[15] = dyn ? (const void*)tables : nullptr; key.p[16] = hist;
+    key.seed = ma ? seed : 0ull; key.i[0] = seq_len; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch;
+    key.i[3] = (ma || dyn) ? timesteps : 0; key.i[5] = order;
+    key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
+    return run_steps(h, ma ? 5 : 4, key, nsteps, use_graph, st, step);
+}
+
+int vdx_dpm_sample_loop(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
+                        uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                        int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
+                        void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    return dpm_loop("dpm_sample_loop", h, params, packed, img, eps_buf, hist, t_dev, step_dev, alphas_cumprod, seq, seq_len, nsteps, cond,
+                    clip_denoised, order, tables, timesteps, percentile, thres_buf, nullptr, 0, workspace, workspace_bytes, batch, use_graph, stream);
+}
+
+int vdx_dpm_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
+                               uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                               int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
+                               const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
+                               void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    const vdx::MaskArgs ma = {known, mask, mask_tables, 1, 0ull, nullptr};
+    return dpm_loop("dpm_sample_loop_masked", h, params, packed, img, eps_buf, hist, t_dev, step_dev, alphas_cumprod, seq, seq_len, nsteps, cond,
+                    clip_denoised, order, tables, timesteps, percentile, thres_buf, &ma, seed, workspace, workspace_bytes, batch, use_graph, stream);
 }
 
 int vdx_pack_conv_weights_t(int mode, const float* kernel, void* packed, int taps, int cin, int cout, void* stream) {

@@ -201,6 +201,10 @@ hipError_t launch_inpaint_init(float* x, const float* known, const unsigned char
 hipError_t launch_ddim_step(const float* x, const float* eps, float* out, const float* ac, const int* seq, const unsigned long long* step_dev,
                             const float* thres, int clip, int B, int C, long per_sample, hipStream_t st);
 hipError_t launch_ddim_advance(int* t, int B, const int* seq, unsigned long long* step_dev, hipStream_t st);
+// DPM-Solver++(2M) step; m != nullptr: the masked form (m->mtab rows of length T, draw VDX_DRAW_KNOWN + k of `seed`).  per_sample % 4 == 0
+hipError_t launch_dpm_step(const float* x, const float* eps, float* out, float* hist, const float* ac, const int* seq,
+                           const unsigned long long* step_dev, const float* thres, int clip, int order, int B, int C, long per_sample,
+                           const MaskArgs* m, int T, unsigned long long seed, hipStream_t st);
 hipError_t launch_dyn_thres(const float* x, const float* eps, const int* t, const float* tables, int T, float q, float* out, int B, int C,
                             long per_sample, hipStream_t st);
 hipError_t launch_loss(const float* eps_hat, const float* noise, double* acc, int B, int Cc, long fhw, int l2, hipStream_t st);

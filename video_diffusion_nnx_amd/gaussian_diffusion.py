@@ -39,6 +39,12 @@ vdx_p_sample_loop_masked = L._sig('vdx_p_sample_loop_masked', C.c_int, [_vp] * 8
 vdx_ddim_step_masked = L._sig('vdx_ddim_step_masked', C.c_int, [_vp] * 7 + [C.c_int] + [_vp] * 3 + [C.c_int, _u64, C.c_int, C.c_int, C.c_long, _vp])
 vdx_ddim_sample_loop_masked = L._sig('vdx_ddim_sample_loop_masked', C.c_int, [_vp] * 9 + [C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_float]
                                      + [_vp] * 4 + [_u64, _vp, C.c_size_t, C.c_int, C.c_int, _vp])
+vdx_dpm_step = L._sig('vdx_dpm_step', C.c_int, [_vp] * 8 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, _vp])
+vdx_dpm_step_masked = L._sig('vdx_dpm_step_masked', C.c_int, [_vp] * 8 + [C.c_int, C.c_int] + [_vp] * 3 + [C.c_int, _u64, C.c_int, C.c_int, C.c_long, _vp])
+vdx_dpm_sample_loop = L._sig('vdx_dpm_sample_loop', C.c_int, [_vp] * 10 + [C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_float, _vp, _vp,
+                                                             C.c_size_t, C.c_int, C.c_int, _vp])
+vdx_dpm_sample_loop_masked = L._sig('vdx_dpm_sample_loop_masked', C.c_int, [_vp] * 10 + [C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_float]
+                                    + [_vp] * 4 + [_u64, _vp, C.c_size_t, C.c_int, C.c_int, _vp])
 
 
 def extend_plan(have: int, num_new: int, num_frames: int, context_frames: int):
@@ -83,6 +89,21 @@ def ddim_time_sequence(timesteps: int, steps: int) -> np.ndarray:
     Evenly spaced as linspace(-1, T-1, S+1), the usual choice (denoising-diffusion-pytorch); the reference has no DDIM."""
     assert 1 <= steps <= timesteps
     return np.ascontiguousarray(np.linspace(-1, timesteps - 1, steps + 1).astype(np.int32)[::-1])
+
+
+def check_dpm_args(timesteps: int, dpm_steps, dpm_order=2, ddim_steps=None, resample_steps: int = 1) -> None:
+    """The argument rules of the DPM-Solver++ paths (dpm_steps is not None), checked before any device work."""
+    if dpm_steps is None:
+        return
+    if ddim_steps:
+        raise ValueError('dpm_steps and ddim_steps are two samplers: give one of them')
+    if int(resample_steps) > 1:
+        raise ValueError('resampling (resample_steps > 1) is defined for the ancestral chain only, not with dpm_steps')
+    if dpm_order not in (1, 2):
+        raise ValueError(f'dpm_order must be 1 or 2, got {dpm_order}')
+    if not 1 <= int(dpm_steps) <= int(timesteps):
+        raise ValueError(f'dpm_steps must be in [1, {int(timesteps)}], got {dpm_steps}')
+
 
 TABLE_NAMES = (
     'alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod', 'log_one_minus_alphas_cumprod',
@@ -351,13 +372,70 @@ class GaussianDiffusion:
         cur.wait_stream(st)
         return out
 
-    def sample(self, key, cond=None, cond_scale: float = 1.0, batch_size: int = 16, *, ddim_steps: Optional[int] = None, **kw):
+    def dpm_sample_loop(self, shape, key, steps: int = 20, order: int = 2, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True,
+                        x_T=None):
+        """DPM-Solver++(2M) sampling in `steps` network evaluations (EXTENSION, parity unpinned: no reference code; Lu et al. 2022,
+        data-prediction multistep form, the step of vdx.h).  order 2 reaches in 15-25 steps what DDIM (= order 1) needs about 100 for;
+        the cost per step is DDIM's plus one history tensor.  x_T = Philox(key, draw 0), deterministic afterwards.  Returns
+        unnormalize_img(x_0) in [0, 1]."""
+        check_dpm_args(self.num_timesteps, steps, order)
+        steps = int(steps)
+        B = int(shape[0])
+        shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
+        unet = self.denoise_fn
+        seq_host = ddim_time_sequence(self.num_timesteps, steps)
+        if self._sample_stream is None:
+            self._sample_stream = torch.cuda.Stream(device=self.device)
+        cur, st = torch.cuda.current_stream(self.device), self._sample_stream
+        st.wait_stream(cur)
+        keep_storage = unet.act_bf16
+        unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
+        try:
+            with torch.cuda.stream(st):
+                img = self.randn(shape, int(key) & 0xFFFFFFFFFFFFFFFF, 0) if x_T is None else self._dev(x_T).clone()
+                hist = torch.empty_like(img)
+                seq = torch.from_numpy(seq_host).to(self.device)
+                guided = cond is not None and unet.has_cond and cond_scale != 1
+                if guided:
+                    step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+                    for k in range(steps):
+                        t = torch.full((B,), int(seq_host[k]), dtype=torch.int32, device=self.device)
+                        eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
+                        step_dev.fill_(k)
+                        thres = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
+                        L.check(vdx_dpm_step(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(hist), L.ptr(self.alphas_cumprod), L.ptr(seq), L.ptr(step_dev),
+                                             L.ptr(thres), 1, order, B, self.channels, self._per_sample(img), L.stream_ptr()))
+                else:
+                    condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
+                    h = unet.handle(self.num_frames, self.image_size)
+                    unet.apply_activation_storage(h)
+                    ws = unet.workspace(B, self.num_frames, self.image_size)
+                    eps = torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=self.device)
+                    t_dev = torch.full((B,), int(seq_host[0]), dtype=torch.int32, device=self.device)
+                    step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+                    thres = torch.empty(B, dtype=torch.float32, device=self.device) if self.use_dynamic_thres else None
+                    L.check(vdx_dpm_sample_loop(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(hist), L.ptr(t_dev),
+                                                L.ptr(step_dev), L.ptr(self.alphas_cumprod), L.ptr(seq), steps, steps, L.ptr(condd), 1, order,
+                                                L.ptr(self._ptab), self.num_timesteps,
+                                                float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0, L.ptr(thres),
+                                                L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
+                out = torch.empty_like(img)
+                L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
+        finally:
+            unet.act_bf16 = keep_storage
+        cur.wait_stream(st)
+        return out
+
+    def sample(self, key, cond=None, cond_scale: float = 1.0, batch_size: int = 16, *, ddim_steps: Optional[int] = None,
+               dpm_steps: Optional[int] = None, dpm_order: int = 2, **kw):
         """reference :323-357.  ddim_steps (extension): sample with an S-step DDIM chain instead of the T-step ancestral one.
+        dpm_steps (extension): an S-step DPM-Solver++(2M) chain of order dpm_order (dpm_sample_loop); not together with ddim_steps.
 
         Data parallel (reference :278-298: the batch is split over the local devices, `P('data')`): inside an initialised
         torch.distributed group of W > 1 ranks, `batch_size` (and `cond`) describe the GLOBAL batch; rank r draws videos
         [r * per, (r + 1) * per), per = batch_size / W, from its own Philox stream shard_key(key, r) and returns ITS shard --
         no data-path collective.  W = 1 uses `key` itself (single-process behaviour unchanged)."""
+        check_dpm_args(self.num_timesteps, dpm_steps, dpm_order, ddim_steps)
         if is_list_str(cond):
             raise NotImplementedError('text -> BERT embedding needs the external video_diffusion_pytorch.text (network fetch); '
                                       'pass a ready [B, 768] tensor instead')
@@ -371,20 +449,23 @@ class GaussianDiffusion:
             if cond is not None:
                 cond = cond[rank * per:(rank + 1) * per]
         shape = (batch_size, self.channels, self.num_frames, self.image_size, self.image_size)
+        if dpm_steps is not None:
+            return self.dpm_sample_loop(shape, key, steps=int(dpm_steps), order=dpm_order, cond=cond, cond_scale=cond_scale, **kw)
         if ddim_steps:
             return self.ddim_sample_loop(shape, key, steps=int(ddim_steps), cond=cond, cond_scale=cond_scale, **kw)
         return self.p_sample_loop(shape, key, cond=cond, cond_scale=cond_scale, **kw)
 
     def inpaint(self, key, video, mask, *, cond=None, cond_scale: float = 1.0, ddim_steps: Optional[int] = None, resample_steps: int = 1,
-                use_graph: bool = True, x_T=None):
+                use_graph: bool = True, x_T=None, dpm_steps: Optional[int] = None, dpm_order: int = 2):
         """Frame-conditioned sampling (EXTENSION): generate the unknown part of `video` ([B,C,F,H,W] in [0,1]) with the
         unconditionally trained denoiser by the replacement method (Ho et al. 2022, sec. 3.1); resample_steps U > 1 adds RePaint
         resampling (Lugmayr et al. 2022, ancestral chain only).  mask: [F], [B,F] or broadcastable to `video`, bool / uint8, 1 = known
-        (frame_mask).  ddim_steps S: an S-step DDIM chain (eta = 0) instead of the T-step ancestral one.  The known region of the
-        result is `video` up to one affine rounding; an all-zero mask with U = 1 is p_sample_loop / ddim_sample_loop.
+        (frame_mask).  ddim_steps S: an S-step DDIM chain (eta = 0) instead of the T-step ancestral one; dpm_steps S: an S-step
+        DPM-Solver++(2M) chain of order dpm_order (vdx_dpm_step_masked).  The known region of the result is `video` up to one affine
+        rounding; an all-zero mask with U = 1 is p_sample_loop / ddim_sample_loop / dpm_sample_loop.
         Data parallel as sample(): `video` (and `mask`, `cond`, `x_T`) are the GLOBAL batch, rank r returns its rows, drawn with
         shard_key(key, r).  Draws: vdx.h (VDX_DRAW_KNOWN, VDX_DRAW_RENOISE)."""
-        shape = self._check_inpaint(video, ddim_steps, resample_steps, x_T)
+        shape = self._check_inpaint(video, ddim_steps, resample_steps, x_T, dpm_steps, dpm_order)
         m = frame_mask(mask, shape)
         rank, world = dist_rank_world()
         if world > 1:
@@ -393,11 +474,12 @@ class GaussianDiffusion:
             video, m, key = video[rows], m[rows], shard_key(key, rank, world)
             cond = None if cond is None else cond[rows]
             x_T = None if x_T is None else x_T[rows]
-        return self._inpaint_local(key, video, m, cond, cond_scale, ddim_steps, int(resample_steps), use_graph, x_T)
+        return self._inpaint_local(key, video, m, cond, cond_scale, ddim_steps, int(resample_steps), use_graph, x_T, dpm_steps, dpm_order)
 
-    def _check_inpaint(self, video, ddim_steps, resample_steps, x_T):
+    def _check_inpaint(self, video, ddim_steps, resample_steps, x_T, dpm_steps=None, dpm_order=2):
         if int(resample_steps) < 1:
             raise ValueError(f'resample_steps must be >= 1, got {resample_steps}')
+        check_dpm_args(self.num_timesteps, dpm_steps, dpm_order, ddim_steps, resample_steps)
         if ddim_steps and int(resample_steps) > 1:
             raise ValueError('resampling (resample_steps > 1) is defined for the ancestral chain only, not with ddim_steps')
         shape = tuple(video.shape)
@@ -423,10 +505,11 @@ class GaussianDiffusion:
             self._ibuf_key = key
         return self._ibuf
 
-    def _inpaint_local(self, key, video, m, cond, cond_scale, ddim_steps, U, use_graph, x_T):
+    def _inpaint_local(self, key, video, m, cond, cond_scale, ddim_steps, U, use_graph, x_T, dpm_steps=None, dpm_order=2):
         seed = int(key) & 0xFFFFFFFFFFFFFFFF
         B = video.shape[0]
-        S = int(ddim_steps) if ddim_steps else 0
+        dpm = dpm_steps is not None                      # S-step chain over ddim_time_sequence with the DPM-Solver++ step
+        S = int(dpm_steps) if dpm else int(ddim_steps) if ddim_steps else 0
         unet = self.denoise_fn
         T = self.num_timesteps
         if self._sample_stream is None:
@@ -453,6 +536,8 @@ class GaussianDiffusion:
                 guided = cond is not None and unet.has_cond and cond_scale != 1
                 thres = buf['thres'] if self.use_dynamic_thres else None
                 perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
+                if dpm and 'hist' not in buf:
+                    buf['hist'] = torch.empty_like(img)
                 if guided:                                   # two forwards per step: eager, with the numbering of the captured loops
                     if S:
                         for j in range(S):
@@ -460,9 +545,14 @@ class GaussianDiffusion:
                             eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
                             buf['step'].fill_(j)
                             th = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
-                            L.check(vdx_ddim_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']),
-                                                         L.ptr(buf['step']), L.ptr(th), 1, L.ptr(known), L.ptr(mk), L.ptr(self._mtab), T, seed,
-                                                         B, self.channels, per, L.stream_ptr()))
+                            if dpm:
+                                L.check(vdx_dpm_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(buf['hist']), L.ptr(self.alphas_cumprod),
+                                                            L.ptr(buf['seq']), L.ptr(buf['step']), L.ptr(th), 1, dpm_order, L.ptr(known), L.ptr(mk),
+                                                            L.ptr(self._mtab), T, seed, B, self.channels, per, L.stream_ptr()))
+                            else:
+                                L.check(vdx_ddim_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']),
+                                                             L.ptr(buf['step']), L.ptr(th), 1, L.ptr(known), L.ptr(mk), L.ptr(self._mtab), T, seed,
+                                                             B, self.channels, per, L.stream_ptr()))
                     else:
                         s = 0
                         for i in reversed(range(T)):
@@ -481,7 +571,13 @@ class GaussianDiffusion:
                     ws = unet.workspace(B, self.num_frames, self.image_size)
                     buf['t'].fill_(t0)
                     buf['step'].zero_()
-                    if S:
+                    if dpm:
+                        L.check(vdx_dpm_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
+                                                           L.ptr(buf['hist']), L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self.alphas_cumprod),
+                                                           L.ptr(buf['seq']), S, S, L.ptr(condd), 1, dpm_order, L.ptr(self._ptab), T, perc, L.ptr(thres),
+                                                           L.ptr(known), L.ptr(mk), L.ptr(self._mtab), seed, L.ptr(ws), ws.numel(), B, int(use_graph),
+                                                           L.stream_ptr()))
+                    elif S:
                         L.check(vdx_ddim_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
                                                             L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']), S, S,
                                                             L.ptr(condd), 1, L.ptr(self._ptab), T, perc, L.ptr(thres), L.ptr(known), L.ptr(mk),
@@ -510,7 +606,8 @@ class GaussianDiffusion:
         plan = extend_plan(video.shape[2], int(num_new_frames), self.num_frames, ctx)
         if plan:
             probe = video.new_zeros((video.shape[0], self.channels, self.num_frames, self.image_size, self.image_size))
-            self._check_inpaint(probe, inpaint_kw.get('ddim_steps'), inpaint_kw.get('resample_steps', 1), inpaint_kw.get('x_T'))
+            self._check_inpaint(probe, inpaint_kw.get('ddim_steps'), inpaint_kw.get('resample_steps', 1), inpaint_kw.get('x_T'),
+                                inpaint_kw.get('dpm_steps'), inpaint_kw.get('dpm_order', 2))
         rank, world = dist_rank_world()
         cond = inpaint_kw.pop('cond', None)
         if world > 1:
@@ -524,13 +621,14 @@ class GaussianDiffusion:
         clip[:, :, :F0] = video
         window = torch.zeros(B, self.channels, self.num_frames, self.image_size, self.image_size, device=self.device)
         ddim_steps, U = inpaint_kw.pop('ddim_steps', None), int(inpaint_kw.pop('resample_steps', 1))
+        dpm_steps, dpm_order = inpaint_kw.pop('dpm_steps', None), inpaint_kw.pop('dpm_order', 2)
         have = F0
         for (c, n), k in zip(plan, split_key(key, len(plan))):
             window[:, :, :c] = clip[:, :, have - c:have]
             frames = torch.arange(self.num_frames, device=self.device) < c
             m = frame_mask(frames, tuple(window.shape))
             out = self._inpaint_local(k, window, m, cond, inpaint_kw.get('cond_scale', 1.0), ddim_steps, U, inpaint_kw.get('use_graph', True),
-                                      inpaint_kw.get('x_T'))
+                                      inpaint_kw.get('x_T'), dpm_steps, dpm_order)
             clip[:, :, have:have + n] = out[:, :, c:c + n]
             have += n
         return clip
