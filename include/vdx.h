@@ -392,7 +392,14 @@ int vdx_ddim_sample_loop_dyn(vdx_handle* h, const float* params, const void* pac
  * mask_tables: device fp32 [4][T] = sqrt_ac | sqrt(1 - ac) | sqrt(alpha) | sqrt(beta).  s is the global step counter (0, 1, ...
  * over every reverse step incl. the resampling ones).  Draws: x_T = Philox(seed, 0), step noise 1 + s (as vdx_p_sample_loop), the
  * known region's noise VDX_DRAW_KNOWN + s, the re-noise VDX_DRAW_RENOISE + s.  per_sample % 4 == 0 everywhere, and the kernels move
- * 4 elements at a time: x / img, known and out must be 16-byte aligned, mask 4-byte aligned (checked: VDX_ERR_INVALID). */
+ * 4 elements at a time: x / img, known and out must be 16-byte aligned, mask 4-byte aligned (checked: VDX_ERR_INVALID).
+ *
+ * Clean context (for a denoiser trained with vdx_q_sample_masked / vdx_loss_sum_masked below, RaMViD): every kernel here forms the
+ * known region as mask_tables[0][.] * known + mask_tables[1][.] * z.  A mask_tables whose row 0 is all 1 and row 1 all 0 (rows 2, 3
+ * unchanged) makes that `known` exactly, at vdx_inpaint_init (x = mask ? known : x_T) and at every step of all three loops: the
+ * known frames then enter the network clean at every noise level, which is what such a denoiser was trained on.  No other kernel or
+ * argument changes; the VDX_DRAW_KNOWN draws are still made and multiplied by 0.  Not with resample_steps > 1: the re-noise of rows
+ * 2, 3 touches the whole tensor. */
 #define VDX_DRAW_KNOWN (1ull << 62)
 #define VDX_DRAW_RENOISE (1ull << 63)
 
@@ -666,6 +673,33 @@ int vdx_unet_backward(vdx_handle* h, const float* params, const void* packed, co
 
 /* d(mean loss)/d(eps_hat) for the l1 / l2 loss of gaussian_diffusion.py:463-466, written channel-last like eps_hat. */
 int vdx_loss_grad(const float* eps_hat, const float* noise, float* d_eps_hat, int batch, int channels, long fhw, int l2, void* stream);
+
+/* Frame-conditioned training (EXTENSION: RaMViD, Hoeppe et al. 2022, "Diffusion Models for Video Prediction and Infilling"; the
+ * reference trains unconditionally only).  A random subset of frames enters the network clean, the rest noised to level t, and the
+ * loss is taken over the noised elements.  mask is inpaint's: [B,C,F,H,W] bytes in the layout of x / noise, nonzero = known (clean
+ * context), zero = noised and learned from.  The kernels move 4 elements at a time: channels * fhw (per_sample) % 4 == 0, the
+ * [B,C,F,H,W] float tensors 16-byte aligned, mask 4-byte aligned (checked: VDX_ERR_INVALID).
+ *
+ * vdx_q_sample_masked: out = mask ? x0n : sqrt_ac[t] x0n + sqrt_1m_ac[t] noise, x0n = x_start * pre_scale + pre_shift.  The noised
+ * branch is vdx_q_sample's expression: an all-zero mask is vdx_q_sample bit for bit. */
+int vdx_q_sample_masked(const float* x_start, const int* t, const float* noise, const unsigned char* mask, float* out, const float* sqrt_ac,
+                        const float* sqrt_one_minus_ac, int batch, long per_sample, float pre_scale, float pre_shift, void* stream);
+
+/* out[0] = sum of |eps_hat - noise| (l2 == 0) or (eps_hat - noise)^2 over the elements whose mask is 0, out[1] = their number (device
+ * doubles; the loss is out[0] / max(out[1], 1)).  eps_hat channel-last [B,F,H,W,C] as in vdx_loss_sum; noise, mask [B,C,F,H,W].
+ * Deterministic: a fixed grid writes one (sum, count) partial per workgroup into scratch[vdx_loss_masked_scratch_doubles()], a second
+ * one-workgroup kernel adds them in index order (the scheme of vdx_grad_sqnorm); no atomics, the bits of out depend on the inputs only.
+ * out needs no zeroing. */
+size_t vdx_loss_masked_scratch_doubles(void);
+int vdx_loss_sum_masked(const float* eps_hat, const float* noise, const unsigned char* mask, double* scratch, double* out, int batch,
+                        int channels, long fhw, int l2, void* stream);
+
+/* d(out[0] / max(out[1], 1))/d(eps_hat) of vdx_loss_sum_masked, written channel-last like eps_hat: exactly 0.0f where the mask is
+ * nonzero.  count_dev = &out[1] on the device: the host reads nothing, the train step stays free of host syncs.  The factor is the
+ * correctly rounded 1.0f / (float)count, so with an all-zero mask (count = batch * channels * fhw) the result is vdx_loss_grad's
+ * bit for bit. */
+int vdx_loss_grad_masked(const float* eps_hat, const float* noise, const unsigned char* mask, const double* count_dev, float* d_eps_hat,
+                         int batch, int channels, long fhw, int l2, void* stream);
 
 /* optax.adam + EMA on flat fp32 buffers (trainer.py:367-382): m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
  * p -= lr * (m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + eps), t = step_count + 1; g is read as grad * grad_scale

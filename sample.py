@@ -4,7 +4,8 @@ GaussianDiffusion.sample on the GPU and writes one GIF per video (batch-global m
 Extensions: --mode {bf16,f16,f32}; --random-init (no checkpoint); --timesteps N (shorter chain for smoke runs); --ddim-steps S;
 --dpm-steps S [--dpm-order 1|2] (DPM-Solver++(2M) chain; not together with --ddim-steps);
 --attn-fp8 (bf16 mode: QK^T / PV of the <= 16-token attention blocks on fp8 MFMA operands);
---context PATH.npy [--context-frames K] [--extend-frames N] [--resample-steps U] (video prediction / extension from given frames)."""
+--context PATH.npy [--context-frames K] [--extend-frames N] [--resample-steps U] (video prediction / extension from given frames);
+--clean-context (with --context, for a checkpoint trained with train.py --frame_cond_max: the given frames stay un-noised at every step)."""
 import argparse
 import logging
 import os
@@ -34,6 +35,8 @@ FLAGS = (   # (flag, kwargs)
     ('--context-frames', dict(type=int, default=None, help='with --context: keep its first K frames (default: all)')),
     ('--extend-frames', dict(type=int, default=0, help='with --context: the videos get num_frames + N frames')),
     ('--resample-steps', dict(type=int, default=1, help='with --context: RePaint resampling steps per noise level (ancestral chain only)')),
+    ('--clean-context', dict(action='store_true', help='with --context: keep the given frames clean at every step (frame-conditioned '
+                                                       'checkpoints, train.py --frame_cond_max); not with --resample-steps > 1')),
 )
 
 
@@ -78,6 +81,11 @@ def main(argv=None):
     if a.dpm_steps is not None and a.ddim_steps is not None:
         ap.error('--dpm-steps and --ddim-steps are two samplers: give one of them')
 
+    if a.clean_context and not a.context:
+        ap.error('--clean-context needs --context')
+    if a.clean_context and a.resample_steps > 1:
+        ap.error('--clean-context keeps the given frames un-noised: not with --resample-steps > 1')
+
     # one process per GPU under `python -m torch.distributed.run --nproc-per-node N sample.py ...` (reference gaussian_diffusion.py:278-298
     # shards the batch over the local devices): every rank draws batch_size / N of the videos and writes its own GIFs
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
@@ -121,7 +129,8 @@ def _run(a, ap, rank, world):
         # the first window conditions on every kept frame (up to num_frames - 1), later windows on at least num_frames // 2
         window_ctx = min(max(ctx.shape[2], gd.num_frames // 2), gd.num_frames - 1)
         videos = gd.extend(a.seed, torch.from_numpy(ctx), n_new, context_frames=window_ctx, ddim_steps=a.ddim_steps,
-                           resample_steps=a.resample_steps, dpm_steps=a.dpm_steps, dpm_order=a.dpm_order)      # this rank's shard of the global batch
+                           resample_steps=a.resample_steps, dpm_steps=a.dpm_steps, dpm_order=a.dpm_order,
+                           clean_context=a.clean_context)               # this rank's shard of the global batch
     else:
         videos = gd.sample(a.seed, batch_size=a.batch_size, ddim_steps=a.ddim_steps, dpm_steps=a.dpm_steps,
                            dpm_order=a.dpm_order)                       # this rank's shard of the global batch

@@ -1,7 +1,8 @@
 """Cost of frame-conditioned sampling at the N shape (dim 64, 16f x 64 x 64, B 64, bf16 operands + bf16 activation storage, half the
 frames known): the hipGraph-replayed DDPM step of GaussianDiffusion.inpaint (vdx_p_sample_loop_masked, U = 1) against that of
 sample() (vdx_p_sample_loop_dyn), alternated, plus the reverse-step kernel alone (p_sample_masked_kernel vs p_sample_kernel), timed
-with device events.  Prints one JSON line.  Needs an MI355X."""
+with device events.  --clean-context: the masked step with the (1, 0) mask table of inpaint(clean_context=True).  Prints one JSON
+line.  Needs an MI355X."""
 import argparse
 import json
 import os
@@ -28,6 +29,7 @@ def main():
     ap.add_argument('--steps', type=int, default=20, help='replayed steps per timed window')
     ap.add_argument('--reps', type=int, default=5, help='alternating windows per variant')
     ap.add_argument('--kernel-iters', type=int, default=200)
+    ap.add_argument('--clean-context', action='store_true', help='the known frames stay clean: the (1, 0) mask table')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs an MI355X'
     B, Fr, S, T = a.batch, a.frames, a.size, 1000
@@ -41,12 +43,13 @@ def main():
     ws = unet.workspace(B, Fr, S)
     shape = (B, 1, Fr, S, S)
     per = Fr * S * S
+    mtab = gd._mtab_clean if a.clean_context else gd._mtab
     st = torch.cuda.Stream(device=dev)
     with torch.cuda.stream(st):
         img = gd.randn(shape, 1, 0)
         known = 2 * torch.rand(shape, device=dev) - 1
         mask = frame_mask(torch.arange(Fr, device=dev) < Fr // 2, shape)
-        L.check(vdx_inpaint_init(L.ptr(img), L.ptr(known), L.ptr(mask), L.ptr(gd._mtab), T, T - 1, img.numel(), L.stream_ptr()))
+        L.check(vdx_inpaint_init(L.ptr(img), L.ptr(known), L.ptr(mask), L.ptr(mtab), T, T - 1, img.numel(), L.stream_ptr()))
         eps = torch.empty(B, Fr, S, S, 1, device=dev)
         t_dev = torch.full((B,), T - 1, dtype=torch.int32, device=dev)
         step = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -54,7 +57,7 @@ def main():
 
         def run(masked, n):
             if masked:
-                L.check(vdx_p_sample_loop_masked(h.ptr, *common(), n, 0, 1, 1, 0.0, 0, L.ptr(known), L.ptr(mask), L.ptr(gd._mtab), 1,
+                L.check(vdx_p_sample_loop_masked(h.ptr, *common(), n, 0, 1, 1, 0.0, 0, L.ptr(known), L.ptr(mask), L.ptr(mtab), 1,
                                                  L.ptr(ws), ws.numel(), B, 1, L.stream_ptr()))
             else:
                 L.check(vdx_p_sample_loop_dyn(h.ptr, *common(), n, 0, 1, 1, 0.0, 0, L.ptr(ws), ws.numel(), B, 1, L.stream_ptr()))
@@ -80,7 +83,7 @@ def main():
             False: lambda: L.check(vdx_p_sample_step(L.ptr(img), L.ptr(eps), L.ptr(out), L.ptr(t_dev), L.ptr(gd._ptab), T, 0, 1, 1, 0, 0, 1,
                                                      B, 1, per, L.stream_ptr())),
             True: lambda: L.check(vdx_p_sample_step_masked(L.ptr(img), L.ptr(eps), L.ptr(out), L.ptr(t_dev), L.ptr(gd._ptab), T, L.ptr(known),
-                                                           L.ptr(mask), L.ptr(gd._mtab), 1, 1, 0, 0, 0, 1, B, 1, per, L.stream_ptr())),
+                                                           L.ptr(mask), L.ptr(mtab), 1, 1, 0, 0, 0, 1, B, 1, per, L.stream_ptr())),
         }
         for masked in (False, True):
             kern[masked]()
@@ -92,7 +95,7 @@ def main():
     kmed = {k: statistics.median(v) for k, v in kern_us.items()}
     n = B * per
     print(json.dumps({
-        'shape': f'dim {a.dim}, B {B}, {Fr}f x {S}x{S}, bf16 operands + bf16 storage, {Fr // 2} frames known',
+        'shape': f'dim {a.dim}, B {B}, {Fr}f x {S}x{S}, bf16 operands + bf16 storage, {Fr // 2} frames known', 'clean_context': bool(a.clean_context),
         'step_ms_sample': round(med[False], 4), 'step_ms_inpaint': round(med[True], 4),
         'step_overhead_pct': round(100 * (med[True] - med[False]) / med[False], 3),
         'step_ms_all': {'sample': [round(v, 4) for v in step_ms[False]], 'inpaint': [round(v, 4) for v in step_ms[True]]},

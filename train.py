@@ -4,7 +4,9 @@ to the Trainer defaults (the reference indexes them and raises KeyError for its 
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N train.py --config ...` = one process per GPU over RCCL;
 `train_batch_size` stays the GLOBAL batch and is split over ranks like the reference splits it over devices.
 Extensions: --mode {bf16,f32}; --train_num_steps N; --dataset_path P (e.g. synthetic:64); --apply_grad_args (gradient accumulation and
-global-norm clipping as the YAML's trainer section asks; without it both keys are ignored, as in the reference)."""
+global-norm clipping as the YAML's trainer section asks; without it both keys are ignored, as in the reference);
+--frame_cond_max K [--frame_cond_uncond_prob P] [--frame_cond_mode random|prefix] (frame-conditioned training, RaMViD: up to K random
+context frames per sample enter the network clean and carry no loss; sample such a model with sample.py --context ... --clean-context)."""
 import argparse
 import logging
 import os
@@ -21,6 +23,9 @@ FLAGS = (
     ('--train_num_steps', dict(type=int, default=None, help='override trainer.train_num_steps')),
     ('--dataset_path', dict(type=str, default=None, help='override trainer.dataset_path')),
     ('--apply_grad_args', dict(action='store_true', help="honour the trainer section's gradient_accumulate_every and max_grad_norm")),
+    ('--frame_cond_max', dict(type=int, default=None, help='frame-conditioned training: up to K clean context frames per sample (0 = off)')),
+    ('--frame_cond_uncond_prob', dict(type=float, default=None, help='with --frame_cond_max: probability of a sample without context (0.25)')),
+    ('--frame_cond_mode', dict(choices=('random', 'prefix'), default=None, help="with --frame_cond_max: any K frames, or the first K")),
 )
 
 
@@ -55,6 +60,17 @@ def main(argv=None):
         tc['dataset_path'] = a.dataset_path
     if a.apply_grad_args:
         Trainer.apply_grad_args = True
+    if a.frame_cond_max is not None:
+        frames = cfg.get('diffusion', {}).get('num_frames')
+        if a.frame_cond_max < 0 or (frames is not None and a.frame_cond_max > frames - 1):
+            ap.error(f'--frame_cond_max must be in [0, num_frames - 1], got {a.frame_cond_max}')
+        Trainer.frame_cond_max = a.frame_cond_max
+    if a.frame_cond_uncond_prob is not None:
+        if not 0.0 <= a.frame_cond_uncond_prob <= 1.0:
+            ap.error(f'--frame_cond_uncond_prob must be in [0, 1], got {a.frame_cond_uncond_prob}')
+        Trainer.frame_cond_uncond_prob = a.frame_cond_uncond_prob
+    if a.frame_cond_mode is not None:
+        Trainer.frame_cond_mode = a.frame_cond_mode
     tc.pop('resume_training_step', None)             # the command-line flag wins, as in the reference
     trainer = Trainer(diffusion_model=gd, folder=tc.pop('folder'), resume_training_step=a.resume_step, rng_seed=seed, **tc)
     trainer.train()

@@ -78,6 +78,32 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     }
 }
 
+// q_sample with clean context frames (frame-conditioned training, RaMViD: Hoeppe et al. 2022): out = m ? x0n : a[t_b] x0n + b[t_b] noise
+// with x0n = x0 * pre_scale + pre_shift.  The noised branch is q_sample_kernel's expression, so an all-zero mask gives its values bit
+// for bit.  Needs per_sample % 4 == 0 (float4 x0 / noise / out, uchar4 mask).
+__global__ __launch_bounds__(256) void q_sample_masked_kernel(const float* __restrict__ x0, const int* __restrict__ t,
+                                                              const float* __restrict__ noise, const unsigned char* __restrict__ mask,
+                                                              float* __restrict__ out, const float* __restrict__ sqrt_ac,
+                                                              const float* __restrict__ sqrt_1mac, long per_sample, float pre_scale,
+                                                              float pre_shift) {
+    const int b = blockIdx.y;
+    const float a = sqrt_ac[t[b]], s = sqrt_1mac[t[b]];
+    const size_t base = (size_t)b * per_sample;
+    for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < per_sample; i += (long)gridDim.x * blockDim.x * 4) {
+        const float4 x = *reinterpret_cast<const float4*>(x0 + base + i);
+        const float4 n = *reinterpret_cast<const float4*>(noise + base + i);
+        const uchar4 m = *reinterpret_cast<const uchar4*>(mask + base + i);
+        float4 o;
+        o.x = a * fmaf(x.x, pre_scale, pre_shift) + s * n.x; o.y = a * fmaf(x.y, pre_scale, pre_shift) + s * n.y;
+        o.z = a * fmaf(x.z, pre_scale, pre_shift) + s * n.z; o.w = a * fmaf(x.w, pre_scale, pre_shift) + s * n.w;
+        if (m.x) o.x = fmaf(x.x, pre_scale, pre_shift);
+        if (m.y) o.y = fmaf(x.y, pre_scale, pre_shift);
+        if (m.z) o.z = fmaf(x.z, pre_scale, pre_shift);
+        if (m.w) o.w = fmaf(x.w, pre_scale, pre_shift);
+        *reinterpret_cast<float4*>(out + base + i) = o;
+    }
+}
+
 // the per-element arithmetic of one ancestral reverse step, shared by p_sample_kernel and p_sample_masked_kernel
 struct PStepCoef { float k_recip, k_recipm1, c1, c2, sigma, s; int clip; };
 
@@ -488,6 +514,58 @@ __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ eps
     if (threadIdx.x == 0) unsafeAtomicAdd(acc, (double)(red[0] + red[1] + red[2] + red[3]));
 }
 
+// Masked loss (frame-conditioned training): the sum of |eps_hat - eps| or (eps_hat - eps)^2 and the number of elements, both over
+// the elements whose mask byte is 0 (the noised frames).  Pass 1: quad q of the [B,C,F,H,W] tensor belongs to thread q mod (grid * 256)
+// of a fixed grid, every thread adds in double, a fixed-order tree over the workgroup leaves one (sum, count) pair per workgroup in
+// partial[2 * blockIdx.x ..].  No atomics: the bits of the result depend on the inputs only (the scheme of grad_sqnorm_partial_kernel).
+constexpr int kLossMaskedBlocks = 256;
+__global__ __launch_bounds__(256) void loss_masked_partial_kernel(const float* __restrict__ eps_hat, const float* __restrict__ noise,
+                                                                  const unsigned char* __restrict__ mask, double* __restrict__ partial,
+                                                                  int B, int Cc, long fhw, int l2) {
+    __shared__ double red_s[256];
+    __shared__ double red_c[256];
+    const long n = (long)B * Cc * fhw, quads = n / 4;
+    double s = 0.0, cnt = 0.0;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+        const long i0 = 4 * q;
+        const uchar4 m4 = *reinterpret_cast<const uchar4*>(mask + i0);
+        if (m4.x && m4.y && m4.z && m4.w) continue;                       // a quad inside a context frame
+        const float4 n4 = *reinterpret_cast<const float4*>(noise + i0);
+        const float nv[4] = {n4.x, n4.y, n4.z, n4.w};
+        const bool mk[4] = {m4.x != 0, m4.y != 0, m4.z != 0, m4.w != 0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (mk[k]) continue;
+            const long i = i0 + k;
+            const long b = i / (Cc * fhw), r = i - b * Cc * fhw;
+            const long c = r / fhw, p = r - c * fhw;                      // [C,F,H,W] -> channel-last [F,H,W,C]
+            const float d = eps_hat[(b * fhw + p) * Cc + c] - nv[k];
+            s += l2 ? (double)d * (double)d : (double)fabsf(d);
+            cnt += 1.0;
+        }
+    }
+    red_s[threadIdx.x] = s; red_c[threadIdx.x] = cnt;
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) { red_s[threadIdx.x] += red_s[threadIdx.x + w]; red_c[threadIdx.x] += red_c[threadIdx.x + w]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = red_s[0]; partial[2 * blockIdx.x + 1] = red_c[0]; }
+}
+
+// pass 2, one workgroup: the partial pairs are staged in LDS and added by one thread in index order; out = (sum, count)
+__global__ __launch_bounds__(256) void loss_masked_final_kernel(const double* __restrict__ partial, double* __restrict__ out) {
+    __shared__ double part[2 * kLossMaskedBlocks];
+    for (int i = threadIdx.x; i < 2 * kLossMaskedBlocks; i += blockDim.x) part[i] = partial[i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0, c = 0.0;
+        for (int i = 0; i < kLossMaskedBlocks; ++i) { s += part[2 * i]; c += part[2 * i + 1]; }
+        out[0] = s; out[1] = c;
+    }
+}
+
 __global__ void affine_kernel(const float* __restrict__ x, float* __restrict__ y, long n, float a, float b) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = fmaf(x[i], a, b);
 }
@@ -585,6 +663,22 @@ hipError_t launch_dyn_thres(const float* x, const float* eps, const int* t, cons
 
 hipError_t launch_loss(const float* eps_hat, const float* noise, double* acc, int B, int Cc, long fhw, int l2, hipStream_t st) {
     hipLaunchKernelGGL(loss_kernel, dim3(ew_blocks((long)B * Cc * fhw)), dim3(256), 0, st, eps_hat, noise, acc, B, Cc, fhw, l2);
+    return hipGetLastError();
+}
+
+hipError_t launch_q_sample_masked(const float* x0, const int* t, const float* noise, const unsigned char* mask, float* out, const float* sqrt_ac,
+                                  const float* sqrt_1mac, int B, long per_sample, float pre_scale, float pre_shift, hipStream_t st) {
+    hipLaunchKernelGGL(q_sample_masked_kernel, dim3(ew_blocks(per_sample / 4), B), dim3(256), 0, st, x0, t, noise, mask, out, sqrt_ac, sqrt_1mac,
+                       per_sample, pre_scale, pre_shift);
+    return hipGetLastError();
+}
+
+size_t loss_masked_scratch_doubles() { return 2 * kLossMaskedBlocks; }
+
+hipError_t launch_loss_masked(const float* eps_hat, const float* noise, const unsigned char* mask, double* scratch, double* out, int B, int Cc,
+                              long fhw, int l2, hipStream_t st) {
+    hipLaunchKernelGGL(loss_masked_partial_kernel, dim3(kLossMaskedBlocks), dim3(256), 0, st, eps_hat, noise, mask, scratch, B, Cc, fhw, l2);
+    hipLaunchKernelGGL(loss_masked_final_kernel, dim3(1), dim3(256), 0, st, scratch, out);
     return hipGetLastError();
 }
 

@@ -18,6 +18,34 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
     }
 }
 
+// d(sum over the mask-0 elements / max(count, 1))/d(eps_hat) of the masked loss (frame-conditioned training), channel-last; exactly 0
+// where the mask is nonzero.  count is read from the device (loss_masked_final_kernel's out[1]), so the host never sees it.  The
+// reciprocal is the correctly rounded 1 / (float)count that launch_loss_grad forms on the host and the element expression is
+// loss_grad_kernel's: with an all-zero mask the two kernels write the same bits.  4 elements per thread (float4 noise, uchar4 mask).
+__global__ __launch_bounds__(256) void loss_grad_masked_kernel(const float* __restrict__ eps_hat, const float* __restrict__ noise,
+                                                               const unsigned char* __restrict__ mask, const double* __restrict__ count_dev,
+                                                               float* __restrict__ d_eps, int B, int Cc, long fhw, int l2) {
+    const float inv_count = __fdiv_rn(1.0f, (float)fmax(*count_dev, 1.0));
+    const long n = (long)B * Cc * fhw, quads = n / 4;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+        const long i0 = 4 * q;
+        const uchar4 m4 = *reinterpret_cast<const uchar4*>(mask + i0);
+        const float4 n4 = *reinterpret_cast<const float4*>(noise + i0);
+        const float nv[4] = {n4.x, n4.y, n4.z, n4.w};
+        const bool mk[4] = {m4.x != 0, m4.y != 0, m4.z != 0, m4.w != 0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long i = i0 + k;
+            const long b = i / (Cc * fhw), r = i - b * Cc * fhw;
+            const long c = r / fhw, p = r - c * fhw;
+            const long j = (b * fhw + p) * Cc + c;
+            const float d = eps_hat[j] - nv[k];
+            const float g = l2 ? 2.0f * d * inv_count : ((d > 0.f) - (d < 0.f)) * inv_count;
+            d_eps[j] = mk[k] ? 0.0f : g;
+        }
+    }
+}
+
 // The fused Adam + EMA update of one thread's elements of the flat buffers, g read as g * GRAD_SCALE: the body of adam_ema_kernel
 // (GRAD_SCALE = grad_scale) and of adam_ema_clip_kernel (GRAD_SCALE = grad_scale * clip).  One text for both, so that with clip == 1
 // the two kernels run the same arithmetic on the same values; a macro rather than a __device__ function because adam_ema_kernel then
@@ -138,6 +166,14 @@ hipError_t launch_loss_grad(const float* eps_hat, const float* noise, float* d_e
     const long n = (long)B * Cc * fhw;
     const int blocks = (int)std::max<long>(1, std::min<long>((n + 255) / 256, 2048));
     hipLaunchKernelGGL(loss_grad_kernel, dim3(blocks), dim3(256), 0, st, eps_hat, noise, d_eps, B, Cc, fhw, l2, 1.0f / (float)n);
+    return hipGetLastError();
+}
+
+hipError_t launch_loss_grad_masked(const float* eps_hat, const float* noise, const unsigned char* mask, const double* count_dev, float* d_eps,
+                                   int B, int Cc, long fhw, int l2, hipStream_t st) {
+    const long quads = (long)B * Cc * fhw / 4;
+    const int blocks = (int)std::max<long>(1, std::min<long>((quads + 255) / 256, 2048));
+    hipLaunchKernelGGL(loss_grad_masked_kernel, dim3(blocks), dim3(256), 0, st, eps_hat, noise, mask, count_dev, d_eps, B, Cc, fhw, l2);
     return hipGetLastError();
 }
 

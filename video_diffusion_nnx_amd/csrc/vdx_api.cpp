@@ -1210,6 +1210,43 @@ int vdx_loss_grad(const float* eps_hat, const float* noise, float* d_eps_hat, in
     return VDX_OK;
 }
 
+// ---- frame-conditioned training: the masked ends of the train step (float4 / uchar4 moves, as the masked sampling steps) ----
+
+int vdx_q_sample_masked(const float* x_start, const int* t, const float* noise, const unsigned char* mask, float* out, const float* sqrt_ac,
+                        const float* sqrt_one_minus_ac, int batch, long per_sample, float pre_scale, float pre_shift, void* stream) {
+    if (!x_start || !t || !noise || !mask || !out || !sqrt_ac || !sqrt_one_minus_ac || batch < 1 || per_sample < 1)
+        VDX_FAIL(VDX_ERR_INVALID, "q_sample_masked: bad argument");
+    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "q_sample_masked: per_sample must be a multiple of 4");
+    if ((uintptr_t)x_start % 16 || (uintptr_t)noise % 16 || (uintptr_t)out % 16 || (uintptr_t)mask % 4)
+        VDX_FAIL(VDX_ERR_INVALID, "q_sample_masked: x_start / noise / out must be 16-byte and mask 4-byte aligned");
+    VDX_HIP(vdx::launch_q_sample_masked(x_start, t, noise, mask, out, sqrt_ac, sqrt_one_minus_ac, batch, per_sample, pre_scale, pre_shift,
+                                        (hipStream_t)stream));
+    return VDX_OK;
+}
+
+size_t vdx_loss_masked_scratch_doubles(void) { return vdx::loss_masked_scratch_doubles(); }
+
+int vdx_loss_sum_masked(const float* eps_hat, const float* noise, const unsigned char* mask, double* scratch, double* out, int batch,
+                        int channels, long fhw, int l2, void* stream) {
+    if (!eps_hat || !noise || !mask || !scratch || !out || batch < 1 || channels < 1 || fhw < 1) VDX_FAIL(VDX_ERR_INVALID, "loss_sum_masked: bad argument");
+    if (((long)channels * fhw) % 4) VDX_FAIL(VDX_ERR_INVALID, "loss_sum_masked: channels * fhw must be a multiple of 4");
+    if ((uintptr_t)noise % 16 || (uintptr_t)mask % 4 || (uintptr_t)eps_hat % 4 || (uintptr_t)scratch % 8 || (uintptr_t)out % 8)
+        VDX_FAIL(VDX_ERR_INVALID, "loss_sum_masked: noise must be 16-byte and mask 4-byte aligned");
+    VDX_HIP(vdx::launch_loss_masked(eps_hat, noise, mask, scratch, out, batch, channels, fhw, l2, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_loss_grad_masked(const float* eps_hat, const float* noise, const unsigned char* mask, const double* count_dev, float* d_eps_hat,
+                         int batch, int channels, long fhw, int l2, void* stream) {
+    if (!eps_hat || !noise || !mask || !count_dev || !d_eps_hat || batch < 1 || channels < 1 || fhw < 1)
+        VDX_FAIL(VDX_ERR_INVALID, "loss_grad_masked: bad argument");
+    if (((long)channels * fhw) % 4) VDX_FAIL(VDX_ERR_INVALID, "loss_grad_masked: channels * fhw must be a multiple of 4");
+    if ((uintptr_t)noise % 16 || (uintptr_t)mask % 4 || (uintptr_t)eps_hat % 4 || (uintptr_t)d_eps_hat % 4 || (uintptr_t)count_dev % 8)
+        VDX_FAIL(VDX_ERR_INVALID, "loss_grad_masked: noise must be 16-byte and mask 4-byte aligned");
+    VDX_HIP(vdx::launch_loss_grad_masked(eps_hat, noise, mask, count_dev, d_eps_hat, batch, channels, fhw, l2, (hipStream_t)stream));
+    return VDX_OK;
+}
+
 int vdx_adam_ema_step(float* params, const float* grads, float* m, float* v, float* ema, long n, float lr, float b1, float b2,
                       float eps, long step_count, float grad_scale, int do_ema, float ema_decay, void* stream) {
     if (!params || !grads || !m || !v || (do_ema && !ema) || n < 1 || step_count < 0) VDX_FAIL(VDX_ERR_INVALID, "adam_ema_step: bad argument");

@@ -209,6 +209,15 @@ hipError_t launch_dyn_thres(const float* x, const float* eps, const int* t, cons
                             long per_sample, hipStream_t st);
 hipError_t launch_loss(const float* eps_hat, const float* noise, double* acc, int B, int Cc, long fhw, int l2, hipStream_t st);
 hipError_t launch_affine(const float* x, float* y, long n, float a, float b, hipStream_t st);
+// frame-conditioned training (mask [B,C,F,H,W] bytes, nonzero = clean context): masked q_sample, the deterministic (sum, count) of the
+// loss over the mask-0 elements (scratch: loss_masked_scratch_doubles()), and its gradient with the count read from the device
+hipError_t launch_q_sample_masked(const float* x0, const int* t, const float* noise, const unsigned char* mask, float* out, const float* sqrt_ac,
+                                  const float* sqrt_1mac, int B, long per_sample, float pre_scale, float pre_shift, hipStream_t st);
+size_t loss_masked_scratch_doubles();
+hipError_t launch_loss_masked(const float* eps_hat, const float* noise, const unsigned char* mask, double* scratch, double* out, int B, int Cc,
+                              long fhw, int l2, hipStream_t st);
+hipError_t launch_loss_grad_masked(const float* eps_hat, const float* noise, const unsigned char* mask, const double* count_dev, float* d_eps,
+                                   int B, int Cc, long fhw, int l2, hipStream_t st);
 
 hipError_t launch_loss_grad(const float* eps_hat, const float* noise, float* d_eps, int B, int Cc, long fhw, int l2, hipStream_t st);
 hipError_t launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,

@@ -22,6 +22,9 @@ vdx_randn = L._sig('vdx_randn', C.c_int, [_vp, C.c_long, _u64, _u64, _vp, _vp])
 vdx_q_sample = L._sig('vdx_q_sample', C.c_int, [_vp] * 6 + [C.c_int, C.c_long, C.c_float, C.c_float, _vp])
 vdx_p_sample_step = L._sig('vdx_p_sample_step', C.c_int, [_vp] * 5 + [C.c_int, _vp, _u64, _u64, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_long, _vp])
 vdx_loss_sum = L._sig('vdx_loss_sum', C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_long, C.c_int, _vp])
+vdx_q_sample_masked = L._sig('vdx_q_sample_masked', C.c_int, [_vp] * 7 + [C.c_int, C.c_long, C.c_float, C.c_float, _vp])
+vdx_loss_masked_scratch_doubles = L._sig('vdx_loss_masked_scratch_doubles', C.c_size_t, [])
+vdx_loss_sum_masked = L._sig('vdx_loss_sum_masked', C.c_int, [_vp] * 5 + [C.c_int, C.c_int, C.c_long, C.c_int, _vp])
 vdx_affine = L._sig('vdx_affine', C.c_int, [_vp, _vp, C.c_long, C.c_float, C.c_float, _vp])
 vdx_p_sample_loop = L._sig('vdx_p_sample_loop', C.c_int, [_vp] * 8 + [C.c_int, C.c_int, _vp, _u64, C.c_int, _vp, C.c_size_t, C.c_int, C.c_int, _vp])
 vdx_p_sample_loop_dyn = L._sig('vdx_p_sample_loop_dyn', C.c_int, [_vp] * 8 + [C.c_int, C.c_int, _vp, _u64, C.c_int, C.c_float, _vp, _vp, C.c_size_t,
@@ -82,6 +85,9 @@ def frame_mask(mask, shape) -> torch.Tensor:
         if not ok:
             raise ValueError(f'mask of shape {tuple(m.shape)} is neither [F], [B, F] nor broadcastable to {tuple(shape)}')
     return (m != 0).to(torch.uint8).expand(*shape).contiguous()
+
+
+_frame_mask = frame_mask      # (methods below take a `frame_mask` keyword)
 
 
 def ddim_time_sequence(timesteps: int, steps: int) -> np.ndarray:
@@ -205,6 +211,11 @@ class GaussianDiffusion:
         betas = cosine_beta_schedule(self.num_timesteps)
         self._mtab = torch.from_numpy(np.stack([tabs['sqrt_alphas_cumprod'], tabs['sqrt_one_minus_alphas_cumprod'],
                                                 np.sqrt(np.float32(1) - betas), np.sqrt(betas)]).astype(np.float32)).to(self.device)
+        # the same with rows 0, 1 = (1, 0): the masked kernels' `row0 * known + row1 * z` is then `known` itself at every level -- the
+        # clean context frames a frame-conditioned (RaMViD) denoiser was trained on (inpaint(clean_context=True))
+        self._mtab_clean = self._mtab.clone()
+        self._mtab_clean[0] = 1.0
+        self._mtab_clean[1] = 0.0
         self._sample_stream = None
 
     # -- closed forms (table look-ups) -------------------------------------------------------------
@@ -230,6 +241,13 @@ class GaussianDiffusion:
         out = torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
         L.check(vdx_randn(L.ptr(out), out.numel(), int(key) & 0xFFFFFFFFFFFFFFFF, offset, 0, L.stream_ptr()))
         return out
+
+    def _dev_mask(self, mask, shape):
+        """frame_mask(mask, shape) on the device; an element mask that is already there goes through untouched."""
+        if torch.is_tensor(mask) and mask.dtype == torch.uint8 and mask.device == self.device and mask.shape == torch.Size(shape) \
+                and mask.is_contiguous():
+            return mask
+        return _frame_mask(mask, tuple(shape)).to(self.device)
 
     def _per_sample(self, x):
         return x.numel() // x.shape[0]
@@ -456,7 +474,7 @@ class GaussianDiffusion:
         return self.p_sample_loop(shape, key, cond=cond, cond_scale=cond_scale, **kw)
 
     def inpaint(self, key, video, mask, *, cond=None, cond_scale: float = 1.0, ddim_steps: Optional[int] = None, resample_steps: int = 1,
-                use_graph: bool = True, x_T=None, dpm_steps: Optional[int] = None, dpm_order: int = 2):
+                use_graph: bool = True, x_T=None, dpm_steps: Optional[int] = None, dpm_order: int = 2, clean_context: bool = False):
         """Frame-conditioned sampling (EXTENSION): generate the unknown part of `video` ([B,C,F,H,W] in [0,1]) with the
         unconditionally trained denoiser by the replacement method (Ho et al. 2022, sec. 3.1); resample_steps U > 1 adds RePaint
         resampling (Lugmayr et al. 2022, ancestral chain only).  mask: [F], [B,F] or broadcastable to `video`, bool / uint8, 1 = known
@@ -464,8 +482,11 @@ class GaussianDiffusion:
         DPM-Solver++(2M) chain of order dpm_order (vdx_dpm_step_masked).  The known region of the result is `video` up to one affine
         rounding; an all-zero mask with U = 1 is p_sample_loop / ddim_sample_loop / dpm_sample_loop.
         Data parallel as sample(): `video` (and `mask`, `cond`, `x_T`) are the GLOBAL batch, rank r returns its rows, drawn with
-        shard_key(key, r).  Draws: vdx.h (VDX_DRAW_KNOWN, VDX_DRAW_RENOISE)."""
-        shape = self._check_inpaint(video, ddim_steps, resample_steps, x_T, dpm_steps, dpm_order)
+        shard_key(key, r).  Draws: vdx.h (VDX_DRAW_KNOWN, VDX_DRAW_RENOISE).
+        clean_context=True is for a denoiser trained with frame conditioning (Trainer.frame_cond_max > 0; RaMViD, Hoeppe et al. 2022):
+        the known region is `video` itself, un-noised, in the start tensor and after every step of all three chains (the same kernels
+        with the (1, 0) mask table, vdx.h), as such a network saw its context frames in training.  Not with resample_steps > 1."""
+        shape = self._check_inpaint(video, ddim_steps, resample_steps, x_T, dpm_steps, dpm_order, clean_context)
         m = frame_mask(mask, shape)
         rank, world = dist_rank_world()
         if world > 1:
@@ -474,11 +495,14 @@ class GaussianDiffusion:
             video, m, key = video[rows], m[rows], shard_key(key, rank, world)
             cond = None if cond is None else cond[rows]
             x_T = None if x_T is None else x_T[rows]
-        return self._inpaint_local(key, video, m, cond, cond_scale, ddim_steps, int(resample_steps), use_graph, x_T, dpm_steps, dpm_order)
+        return self._inpaint_local(key, video, m, cond, cond_scale, ddim_steps, int(resample_steps), use_graph, x_T, dpm_steps, dpm_order,
+                                   bool(clean_context))
 
-    def _check_inpaint(self, video, ddim_steps, resample_steps, x_T, dpm_steps=None, dpm_order=2):
+    def _check_inpaint(self, video, ddim_steps, resample_steps, x_T, dpm_steps=None, dpm_order=2, clean_context=False):
         if int(resample_steps) < 1:
             raise ValueError(f'resample_steps must be >= 1, got {resample_steps}')
+        if clean_context and int(resample_steps) > 1:
+            raise ValueError('clean_context keeps the known frames un-noised; resampling (resample_steps > 1) re-noises the whole tensor')
         check_dpm_args(self.num_timesteps, dpm_steps, dpm_order, ddim_steps, resample_steps)
         if ddim_steps and int(resample_steps) > 1:
             raise ValueError('resampling (resample_steps > 1) is defined for the ancestral chain only, not with ddim_steps')
@@ -505,8 +529,10 @@ class GaussianDiffusion:
             self._ibuf_key = key
         return self._ibuf
 
-    def _inpaint_local(self, key, video, m, cond, cond_scale, ddim_steps, U, use_graph, x_T, dpm_steps=None, dpm_order=2):
+    def _inpaint_local(self, key, video, m, cond, cond_scale, ddim_steps, U, use_graph, x_T, dpm_steps=None, dpm_order=2,
+                       clean_context=False):
         seed = int(key) & 0xFFFFFFFFFFFFFFFF
+        mtab = self._mtab_clean if clean_context else self._mtab      # (1, 0) rows: the known region is `known` at every level
         B = video.shape[0]
         dpm = dpm_steps is not None                      # S-step chain over ddim_time_sequence with the DPM-Solver++ step
         S = int(dpm_steps) if dpm else int(ddim_steps) if ddim_steps else 0
@@ -532,7 +558,7 @@ class GaussianDiffusion:
                 mk.copy_(m)
                 seq_host = ddim_time_sequence(T, S) if S else None
                 t0 = int(seq_host[0]) if S else T - 1
-                L.check(vdx_inpaint_init(L.ptr(img), L.ptr(known), L.ptr(mk), L.ptr(self._mtab), T, t0, n, L.stream_ptr()))
+                L.check(vdx_inpaint_init(L.ptr(img), L.ptr(known), L.ptr(mk), L.ptr(mtab), T, t0, n, L.stream_ptr()))
                 guided = cond is not None and unet.has_cond and cond_scale != 1
                 thres = buf['thres'] if self.use_dynamic_thres else None
                 perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
@@ -548,10 +574,10 @@ class GaussianDiffusion:
                             if dpm:
                                 L.check(vdx_dpm_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(buf['hist']), L.ptr(self.alphas_cumprod),
                                                             L.ptr(buf['seq']), L.ptr(buf['step']), L.ptr(th), 1, dpm_order, L.ptr(known), L.ptr(mk),
-                                                            L.ptr(self._mtab), T, seed, B, self.channels, per, L.stream_ptr()))
+                                                            L.ptr(mtab), T, seed, B, self.channels, per, L.stream_ptr()))
                             else:
                                 L.check(vdx_ddim_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']),
-                                                             L.ptr(buf['step']), L.ptr(th), 1, L.ptr(known), L.ptr(mk), L.ptr(self._mtab), T, seed,
+                                                             L.ptr(buf['step']), L.ptr(th), 1, L.ptr(known), L.ptr(mk), L.ptr(mtab), T, seed,
                                                              B, self.channels, per, L.stream_ptr()))
                     else:
                         s = 0
@@ -561,7 +587,7 @@ class GaussianDiffusion:
                                 eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
                                 th = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
                                 L.check(vdx_p_sample_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(t), L.ptr(self._ptab), T, L.ptr(known),
-                                                                 L.ptr(mk), L.ptr(self._mtab), U, seed, s, 0, L.ptr(th), 1, B, self.channels, per,
+                                                                 L.ptr(mk), L.ptr(mtab), U, seed, s, 0, L.ptr(th), 1, B, self.channels, per,
                                                                  L.stream_ptr()))
                                 s += 1
                 else:
@@ -575,17 +601,17 @@ class GaussianDiffusion:
                         L.check(vdx_dpm_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
                                                            L.ptr(buf['hist']), L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self.alphas_cumprod),
                                                            L.ptr(buf['seq']), S, S, L.ptr(condd), 1, dpm_order, L.ptr(self._ptab), T, perc, L.ptr(thres),
-                                                           L.ptr(known), L.ptr(mk), L.ptr(self._mtab), seed, L.ptr(ws), ws.numel(), B, int(use_graph),
+                                                           L.ptr(known), L.ptr(mk), L.ptr(mtab), seed, L.ptr(ws), ws.numel(), B, int(use_graph),
                                                            L.stream_ptr()))
                     elif S:
                         L.check(vdx_ddim_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
                                                             L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']), S, S,
                                                             L.ptr(condd), 1, L.ptr(self._ptab), T, perc, L.ptr(thres), L.ptr(known), L.ptr(mk),
-                                                            L.ptr(self._mtab), seed, L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
+                                                            L.ptr(mtab), seed, L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
                     else:
                         L.check(vdx_p_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
                                                          L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self._ptab), T, T * U, L.ptr(condd), seed, 1,
-                                                         perc, L.ptr(thres), L.ptr(known), L.ptr(mk), L.ptr(self._mtab), U, L.ptr(ws), ws.numel(),
+                                                         perc, L.ptr(thres), L.ptr(known), L.ptr(mk), L.ptr(mtab), U, L.ptr(ws), ws.numel(),
                                                          B, int(use_graph), L.stream_ptr()))
                 out = torch.empty_like(img)
                 L.check(vdx_affine(L.ptr(img), L.ptr(out), n, 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
@@ -598,7 +624,8 @@ class GaussianDiffusion:
         """Grow `video` ([B,C,F0,H,W] in [0,1], any F0 >= 1) by `num_new_frames` frames, autoregressively (EXTENSION): window w
         holds the last `ctx` frames so far as known frames and generates the next ones with inpaint() (extend_plan; context_frames
         defaults to num_frames // 2).  Window keys: split_key(key, n_windows).  Returns [B,C,F0 + N,H,W]; its first F0 frames are
-        `video` itself.  Data parallel as sample(): sharded once (rows and shard_key), not per window."""
+        `video` itself.  Data parallel as sample(): sharded once (rows and shard_key), not per window.  clean_context=True (with a
+        frame-conditioned denoiser): every window keeps its context frames un-noised, see inpaint()."""
         ctx = self.num_frames // 2 if context_frames is None else int(context_frames)
         video = torch.as_tensor(video)
         if video.dim() != 5 or tuple(video.shape[1:2] + video.shape[3:]) != (self.channels, self.image_size, self.image_size):
@@ -607,7 +634,7 @@ class GaussianDiffusion:
         if plan:
             probe = video.new_zeros((video.shape[0], self.channels, self.num_frames, self.image_size, self.image_size))
             self._check_inpaint(probe, inpaint_kw.get('ddim_steps'), inpaint_kw.get('resample_steps', 1), inpaint_kw.get('x_T'),
-                                inpaint_kw.get('dpm_steps'), inpaint_kw.get('dpm_order', 2))
+                                inpaint_kw.get('dpm_steps'), inpaint_kw.get('dpm_order', 2), inpaint_kw.get('clean_context', False))
         rank, world = dist_rank_world()
         cond = inpaint_kw.pop('cond', None)
         if world > 1:
@@ -628,7 +655,7 @@ class GaussianDiffusion:
             frames = torch.arange(self.num_frames, device=self.device) < c
             m = frame_mask(frames, tuple(window.shape))
             out = self._inpaint_local(k, window, m, cond, inpaint_kw.get('cond_scale', 1.0), ddim_steps, U, inpaint_kw.get('use_graph', True),
-                                      inpaint_kw.get('x_T'), dpm_steps, dpm_order)
+                                      inpaint_kw.get('x_T'), dpm_steps, dpm_order, bool(inpaint_kw.get('clean_context', False)))
             clip[:, :, have:have + n] = out[:, :, c:c + n]
             have += n
         return clip
@@ -646,8 +673,9 @@ class GaussianDiffusion:
         return img
 
     # -- forward process / loss ----------------------------------------------------------------------
-    def q_sample(self, x_start, t, key=None, noise=None, *, _pre=(1.0, 0.0)):
-        """reference :401-420."""
+    def q_sample(self, x_start, t, key=None, noise=None, *, frame_mask=None, _pre=(1.0, 0.0)):
+        """reference :401-420.  frame_mask (extension, frame-conditioned training): [F], [B,F] or anything frame_mask() takes, 1 = the
+        element stays clean (x_start, normalised), 0 = noised to level t (vdx_q_sample_masked); None = the reference's q_sample."""
         x_start = self._dev(x_start)
         t32 = self._dev(t, torch.int32)
         if noise is None:
@@ -655,13 +683,21 @@ class GaussianDiffusion:
             noise = self.randn(x_start.shape, key, 0)
         noise = self._dev(noise)
         out = torch.empty_like(x_start)
+        if frame_mask is not None:
+            mk = self._dev_mask(frame_mask, x_start.shape)
+            L.check(vdx_q_sample_masked(L.ptr(x_start), L.ptr(t32), L.ptr(noise), L.ptr(mk), L.ptr(out), L.ptr(self.sqrt_alphas_cumprod),
+                                        L.ptr(self.sqrt_one_minus_alphas_cumprod), x_start.shape[0], self._per_sample(x_start),
+                                        float(_pre[0]), float(_pre[1]), L.stream_ptr()))
+            return out
         L.check(vdx_q_sample(L.ptr(x_start), L.ptr(t32), L.ptr(noise), L.ptr(out), L.ptr(self.sqrt_alphas_cumprod),
                              L.ptr(self.sqrt_one_minus_alphas_cumprod), x_start.shape[0], self._per_sample(x_start),
                              float(_pre[0]), float(_pre[1]), L.stream_ptr()))
         return out
 
-    def p_losses(self, x_start, t, key=None, cond=None, noise=None, *, _pre=(1.0, 0.0), **kwargs):
-        """reference :423-470 (forward value; the training step with gradients lives in trainer.py)."""
+    def p_losses(self, x_start, t, key=None, cond=None, noise=None, *, frame_mask=None, _pre=(1.0, 0.0), **kwargs):
+        """reference :423-470 (forward value; the training step with gradients lives in trainer.py).  frame_mask (extension, RaMViD
+        frame conditioning; forms as q_sample's): the masked frames enter the denoiser clean and the loss is the mean over the other
+        elements, sum / max(count, 1), formed on the device (vdx_loss_sum_masked)."""
         if self.loss_type not in ('l1', 'l2'):
             raise ValueError(f'Unsupported loss type: {self.loss_type}')
         x_start = self._dev(x_start)
@@ -671,18 +707,31 @@ class GaussianDiffusion:
             _, noise_key, _ = split_key(key, 3)
             noise = self.randn(x_start.shape, noise_key, 0)
         noise = self._dev(noise)
-        x_noisy = self.q_sample(x_start, t32, noise=noise, _pre=_pre)
+        mk = None if frame_mask is None else self._dev_mask(frame_mask, x_start.shape)
+        x_noisy = self.q_sample(x_start, t32, noise=noise, frame_mask=mk, _pre=_pre)
         if is_list_str(cond):
             raise NotImplementedError('pass text conditioning as a ready embedding tensor')
         eps_hat = self.denoise_fn(x_noisy, t32, cond=cond, **kwargs)
-        acc = torch.zeros(1, dtype=torch.float64, device=self.device)
         B = x_start.shape[0]
         fhw = self._per_sample(x_start) // self.channels
+        if mk is not None:
+            return self.masked_loss(eps_hat, noise, mk)[0]
+        acc = torch.zeros(1, dtype=torch.float64, device=self.device)
         L.check(vdx_loss_sum(L.ptr(eps_hat), L.ptr(noise), L.ptr(acc), B, self.channels, fhw, int(self.loss_type == 'l2'), L.stream_ptr()))
         return (acc / float(x_start.numel())).to(torch.float32).reshape(())
 
+    def masked_loss(self, eps_hat, noise, mk):
+        """(loss, acc) of the masked objective: acc[0:2] = device doubles (sum, count) over the mask-0 elements (vdx_loss_sum_masked, the
+        rest of acc is its scratch) and loss = sum / max(count, 1) as a float32 device scalar; the host reads nothing."""
+        B = noise.shape[0]
+        fhw = self._per_sample(noise) // self.channels
+        acc = torch.empty(2 + vdx_loss_masked_scratch_doubles(), dtype=torch.float64, device=self.device)
+        L.check(vdx_loss_sum_masked(L.ptr(eps_hat), L.ptr(noise), L.ptr(mk), acc.data_ptr() + 16, acc.data_ptr(), B, self.channels, fhw,
+                                    int(self.loss_type == 'l2'), L.stream_ptr()))
+        return (acc[0] / acc[1].clamp_min(1.0)).to(torch.float32).reshape(()), acc
+
     def __call__(self, x, key, *args, **kwargs):
-        """reference :473-502: random t, normalize_img, p_losses."""
+        """reference :473-502: random t, normalize_img, p_losses (a frame_mask keyword goes there)."""
         b, c, f, h, w = x.shape
         assert (c, f, h, w) == (self.channels, self.num_frames, self.image_size, self.image_size), \
             f'expected [b, {self.channels}, {self.num_frames}, {self.image_size}, {self.image_size}], got {tuple(x.shape)}'

@@ -9,10 +9,11 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .gaussian_diffusion import split_key, vdx_loss_sum, vdx_q_sample
+from .gaussian_diffusion import frame_mask as expand_frame_mask, split_key, vdx_loss_sum, vdx_q_sample
 
 _vp = C.c_void_p
 vdx_loss_grad = L._sig('vdx_loss_grad', C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_long, C.c_int, _vp])
+vdx_loss_grad_masked = L._sig('vdx_loss_grad_masked', C.c_int, [_vp] * 5 + [C.c_int, C.c_int, C.c_long, C.c_int, _vp])
 vdx_adam_ema_step = L._sig('vdx_adam_ema_step', C.c_int, [_vp] * 5 + [C.c_long] + [C.c_float] * 4 + [C.c_long, C.c_float, C.c_int, C.c_float, _vp])
 vdx_grad_accumulate = L._sig('vdx_grad_accumulate', C.c_int, [_vp, _vp, C.c_long, _vp])
 vdx_grad_sqnorm_scratch_doubles = L._sig('vdx_grad_sqnorm_scratch_doubles', C.c_size_t, [])
@@ -53,9 +54,47 @@ def micro_step_keys(rng_seed: int, rank: int, step: int, j: int = 0):
     return t_key, noise_key
 
 
+def frame_cond_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
+    """Key of the frame-conditioning mask draw of micro-step j of optimizer step `step`: child 1 of the micro-step key, the child that
+    micro_step_keys' `_, t_key, loss_key = split(key, 3)` discards.  No other draw uses it (t and the noise hang off children 2 and 3,
+    the micro-steps j >= 1 off children 3 + j of the step key), so turning the masks on moves neither t nor the noise."""
+    step_key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
+    if j > 0:
+        step_key = split_key(step_key, 3 + j)[-1]
+    return split_key(step_key, 3)[0]
+
+
+def frame_cond_masks(batch: int, frames: int, k_max: int, uncond_prob: float = 0.25, mode: str = 'random', generator=None) -> torch.Tensor:
+    """The context-frame masks of one micro-batch of frame-conditioned training (RaMViD, Hoeppe et al. 2022): uint8 [batch, frames],
+    1 = the frame enters the network clean and carries no loss.  Per sample: with probability uncond_prob no frame is known (the
+    unconditional task, RaMViD's p_U); otherwise K ~ U{1..k_max} frames are, K distinct frames drawn uniformly (mode 'random') or
+    frames 0..K-1 (mode 'prefix', the prediction task).  1 <= k_max <= frames - 1, so every sample keeps a frame to learn from.  Pure
+    host function of (arguments, generator state); every sample consumes the same three draws whatever its outcome."""
+    if mode not in ('random', 'prefix'):
+        raise ValueError(f"frame_cond_mode must be 'random' or 'prefix', got {mode!r}")
+    if not 1 <= int(k_max) <= int(frames) - 1:
+        raise ValueError(f'frame_cond_max must be in [1, {int(frames) - 1}] for {int(frames)} frames, got {k_max}')
+    if not 0.0 <= float(uncond_prob) <= 1.0:
+        raise ValueError(f'frame_cond_uncond_prob must be in [0, 1], got {uncond_prob}')
+    masks = torch.zeros(int(batch), int(frames), dtype=torch.uint8)
+    for b in range(int(batch)):
+        u = float(torch.rand((), generator=generator))
+        k = int(torch.randint(1, int(k_max) + 1, (), generator=generator))
+        perm = torch.randperm(int(frames), generator=generator)
+        if u < float(uncond_prob):
+            continue
+        masks[b, torch.arange(k) if mode == 'prefix' else perm[:k]] = 1
+    return masks
+
+
 def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, j: int = 0, grads: torch.Tensor = None,
-                     reducer=None) -> torch.Tensor:
+                     reducer=None, frame_mask=None) -> torch.Tensor:
     """loss, grads = value_and_grad(p_losses) (trainer.py:337-361) of one micro-batch; returns the device scalar loss.
+
+    frame_mask ([F], [B,F] or anything gaussian_diffusion.frame_mask takes; default: drawn by frame_cond_masks under frame_cond_key when
+    tr.frame_cond_max > 0, else none): frame-conditioned training -- masked q_sample, the UNet forward unchanged, the loss and its
+    gradient over the noised elements only (vdx_loss_sum_masked / vdx_loss_grad_masked: the count stays on the device), the backward
+    unchanged.  tr.last_frame_mask holds the mask as given or drawn (None without one).
 
     `grads` (default tr.grads) receives the gradient: the head stage of the backward zeroes it.  With a `reducer` the backward runs
     in stage groups and hands finished buckets of tr.grads to it; when `grads` is a second buffer (micro-steps j >= 1), each finished
@@ -81,20 +120,35 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
         t = t.to(dev, torch.int32)
     noise = gd.randn(x.shape, noise_key, 0) if noise is None else torch.as_tensor(noise).to(dev, torch.float32).contiguous()
     tr.last_t, tr.last_noise_key = t, noise_key
-    x_noisy = gd.q_sample(x, t, noise=noise, _pre=(2.0, -1.0))                    # normalize_img folded in (:499)
+    if frame_mask is None and int(tr.frame_cond_max) > 0:
+        g = torch.Generator().manual_seed(frame_cond_key(tr.rng_seed, tr.rank, step, j) & 0x7FFFFFFFFFFFFFFF)
+        frame_mask = frame_cond_masks(B, gd.num_frames, tr.frame_cond_max, tr.frame_cond_uncond_prob, tr.frame_cond_mode, g)
+    tr.last_frame_mask = frame_mask
+    mk = None
+    if frame_mask is not None:
+        fm = torch.as_tensor(frame_mask)
+        if fm.device.type == 'cpu' and dev.type == 'cuda':
+            fm = fm.pin_memory().to(dev, non_blocking=True)               # as t: no pageable copy, no host sync
+        mk = expand_frame_mask(fm.to(dev), tuple(x.shape))
+    x_noisy = gd.q_sample(x, t, noise=noise, frame_mask=mk, _pre=(2.0, -1.0))     # normalize_img folded in (:499)
     keep_storage = unet.act_bf16
     unet.act_bf16 = 2 if (unet.mode == 'bf16' and tr.train_act_bf16) else False
     try:
         eps_hat = unet(x_noisy, t)
     finally:
         unet.act_bf16 = keep_storage
-    acc = torch.zeros(1, dtype=torch.float64, device=dev)
     fhw = x.numel() // (B * gd.channels)
     l2 = int(gd.loss_type == 'l2')
-    L.check(vdx_loss_sum(L.ptr(eps_hat), L.ptr(noise), L.ptr(acc), B, gd.channels, fhw, l2, L.stream_ptr()))
-    loss = (acc / float(x.numel())).to(torch.float32).reshape(())
     d_eps = torch.empty_like(eps_hat)
-    L.check(vdx_loss_grad(L.ptr(eps_hat), L.ptr(noise), L.ptr(d_eps), B, gd.channels, fhw, l2, L.stream_ptr()))
+    if mk is not None:
+        loss, acc = gd.masked_loss(eps_hat, noise, mk)                            # acc = device (sum, count | scratch)
+        L.check(vdx_loss_grad_masked(L.ptr(eps_hat), L.ptr(noise), L.ptr(mk), acc.data_ptr() + 8, L.ptr(d_eps), B, gd.channels, fhw, l2,
+                                     L.stream_ptr()))
+    else:
+        acc = torch.zeros(1, dtype=torch.float64, device=dev)
+        L.check(vdx_loss_sum(L.ptr(eps_hat), L.ptr(noise), L.ptr(acc), B, gd.channels, fhw, l2, L.stream_ptr()))
+        loss = (acc / float(x.numel())).to(torch.float32).reshape(())
+        L.check(vdx_loss_grad(L.ptr(eps_hat), L.ptr(noise), L.ptr(d_eps), B, gd.channels, fhw, l2, L.stream_ptr()))
     if reducer is None:
         unet.backward(d_eps, grads)
         return loss
@@ -155,28 +209,31 @@ def optimizer_tail(tr, step: int, world: int, accum: int = 1, max_grad_norm=None
     unet.mark_params_updated()
 
 
-def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, noise: torch.Tensor = None) -> torch.Tensor:
+def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, noise: torch.Tensor = None, frame_mask=None) -> torch.Tensor:
     """loss, grads = value_and_grad(p_losses); Adam; EMA  (trainer.py:337-382) for this rank's shard of the batch.
 
     `t` [B] / `noise` [B,C,F,H,W] override this rank's own draws (the reference threads `noise` through p_losses the same way,
-    gaussian_diffusion.py:423-445); the data-parallel tests use them to give N ranks the shards of ONE global draw."""
+    gaussian_diffusion.py:423-445); the data-parallel tests use them to give N ranks the shards of ONE global draw.  frame_mask: the
+    shard's context-frame mask (forward_backward); each shard divides its loss by its own count of noised elements."""
     reducer = tr.make_reducer()
-    loss = forward_backward(tr, batch, step, t, noise, reducer=reducer)
+    loss = forward_backward(tr, batch, step, t, noise, reducer=reducer, frame_mask=frame_mask)
     reducer.finish()
     optimizer_tail(tr, step, reducer.world)
     return loss
 
 
-def run_train_step_accum(tr, batches, step: int, ts=None, noises=None) -> torch.Tensor:
+def run_train_step_accum(tr, batches, step: int, ts=None, noises=None, frame_masks=None) -> torch.Tensor:
     """One optimizer step on the mean gradient of K = len(batches) micro-batches of this rank (Trainer.apply_grad_args).
 
     Micro-step 0 is run_train_step's path into tr.grads; micro-steps j >= 1 write tr.micro_grads and are added into tr.grads.  Only the
     last micro-step runs the staged backward and starts the all-reduce, bucket by bucket, after the bucket's accumulation: one
-    reduction per optimizer step, still overlapped with the backward.  Returns the mean of the K device losses."""
+    reduction per optimizer step, still overlapped with the backward.  Returns the mean of the K device losses.  frame_masks: optional
+    list of K context-frame masks (forward_backward); every micro-batch divides by its own count, then the K gradients are averaged."""
     K = len(batches)
     assert K >= 1
     ts = [None] * K if ts is None else ts
     noises = [None] * K if noises is None else noises
+    fms = [None] * K if frame_masks is None else frame_masks
     if K > 1 and getattr(tr, 'micro_grads', None) is None:
         tr.micro_grads = torch.zeros_like(tr.grads)
     reducer = tr.make_reducer()
@@ -184,11 +241,11 @@ def run_train_step_accum(tr, batches, step: int, ts=None, noises=None) -> torch.
     for j in range(K):
         grads = tr.grads if j == 0 else tr.micro_grads
         if j < K - 1:
-            losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads))
+            losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, frame_mask=fms[j]))
             if j > 0:
                 L.check(vdx_grad_accumulate(L.ptr(tr.grads), L.ptr(grads), grads.numel(), L.stream_ptr()))
         else:
-            losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, reducer=reducer))
+            losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, reducer=reducer, frame_mask=fms[j]))
     reducer.finish()
     max_norm = tr.max_grad_norm
     optimizer_tail(tr, step, reducer.world, accum=K, max_grad_norm=max_norm, want_norm=tr.track_grad_norm)

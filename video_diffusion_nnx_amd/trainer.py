@@ -139,6 +139,15 @@ class Trainer:
     apply_grad_args = False
     # with apply_grad_args: compute the gradient norm (last_grad_norm, 'grad_norm/train') also when max_grad_norm is None
     track_grad_norm = False
+    # Frame-conditioned training (extension; RaMViD, Hoeppe et al. 2022): frame_cond_max = K_max > 0 gives every sample of every
+    # (micro-)batch a random set of up to K_max context frames that enter the network clean and carry no loss (train_step.frame_cond_masks,
+    # drawn under train_step.frame_cond_key); with probability frame_cond_uncond_prob (RaMViD's p_U) a sample has none.  Mode 'random':
+    # any frames (prediction, infilling, extension alike); 'prefix': the first K (prediction).  0 = off: the reference's objective, the
+    # kernels and random streams of before.  Sample such a model with inpaint / extend(clean_context=True).  Class attributes for the
+    # same reason as the ones above.
+    frame_cond_max = 0
+    frame_cond_uncond_prob = 0.25
+    frame_cond_mode = 'random'
 
     def __init__(self, diffusion_model, folder: str, *, rng_seed: int = 0, dataset_path: str, num_frames: int = 16,
                  train_batch_size: int = 4, train_lr: float = 1e-4, train_num_steps: int = 100000,
@@ -180,6 +189,7 @@ class Trainer:
         self.opt_count = 0                                       # optax count: restarts at 0 on resume
         self.micro_grads = None                                  # second gradient buffer, allocated by the first K > 1 step
         self.last_grad_norm = None                               # device float of the last pre-clip gradient norm
+        self.last_frame_mask = None                              # context-frame mask of the last micro-batch (frame_cond_max > 0)
         from .train_step import stage_of_param
         nlev = len(self.unet.dim_mults)
         self.buckets = make_buckets(self.unet.param_table, n, lambda nm: stage_of_param(nm, nlev), stage_of_param('__count__', nlev),
@@ -266,24 +276,26 @@ class Trainer:
             red.enabled = False
         return red
 
-    def train_step(self, batch: torch.Tensor, step: int, t=None, noise=None) -> torch.Tensor:
+    def train_step(self, batch: torch.Tensor, step: int, t=None, noise=None, frame_mask=None) -> torch.Tensor:
         """One `_pjit_train_step` on this rank's shard of the batch.  Returns the (device) scalar loss of the shard.
-        t / noise: optional explicit timesteps / noise of the shard (default: this rank's own Philox draws)."""
+        t / noise: optional explicit timesteps / noise of the shard (default: this rank's own Philox draws).  frame_mask: optional
+        explicit context-frame mask of the shard ([F] or [B,F], 1 = clean context; default: drawn when frame_cond_max > 0)."""
         from .train_step import run_train_step
-        return run_train_step(self, batch, step, t=t, noise=noise)
+        return run_train_step(self, batch, step, t=t, noise=noise, frame_mask=frame_mask)
 
     @property
     def accum_steps(self) -> int:
         """Micro-batches per optimizer step: gradient_accumulate_every behind apply_grad_args, else 1."""
         return max(1, int(self.gradient_accumulate_every)) if self.apply_grad_args else 1
 
-    def train_step_accum(self, batches, step: int, ts=None, noises=None) -> torch.Tensor:
+    def train_step_accum(self, batches, step: int, ts=None, noises=None, frame_masks=None) -> torch.Tensor:
         """One optimizer step on K = len(batches) shards of this rank: the gradient is the mean over the K micro-batches (and the
         ranks), clipped to max_grad_norm when that is set.  Returns the (device) mean of the K losses; `last_grad_norm` holds the
-        device float of the pre-clip norm when one was computed.  ts / noises: optional per-micro-batch lists, as train_step's."""
+        device float of the pre-clip norm when one was computed.  ts / noises / frame_masks: optional per-micro-batch lists, as
+        train_step's."""
         from .train_step import run_train_step_accum
         assert self.apply_grad_args, 'train_step_accum is the path behind Trainer.apply_grad_args = True'
-        return run_train_step_accum(self, list(batches), step, ts=ts, noises=noises)
+        return run_train_step_accum(self, list(batches), step, ts=ts, noises=noises, frame_masks=frame_masks)
 
     def train(self, prob_focus_present: float = 0.0, focus_present_mask=None, log_fn=noop):
         assert callable(log_fn)
