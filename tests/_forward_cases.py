@@ -37,14 +37,15 @@ ATTN_HEADS_SPATIAL = [
 ]
 
 
-def mha_weights(C, g, raw=False):
+def mha_weights(C, g, raw=False, operand='bf16'):
     """wqkv [C, 768] (q | k | v), bqkv [768], wo [256, C], bo [C]; the kernels bf16-representable (the packing rounds them), the biases fp32.
-    raw: -> (those, the same with the kernels as drawn, before the rounding)"""
+    raw: -> (those, the same with the kernels as drawn, before the rounding); operand='f16': rounded as pack_weights_kernel<MODE_F16> does"""
+    rd = P.operand_rounding(operand)
     wqkv = torch.randn(C, 768, generator=g) / C ** 0.5 * 2
     bqkv = torch.randn(768, generator=g) * 0.2
     wo = torch.randn(256, C, generator=g) / 16
     bo = torch.randn(C, generator=g) * 0.2
-    w = P.bf16r(wqkv), bqkv, P.bf16r(wo), bo
+    w = rd(wqkv), bqkv, rd(wo), bo
     return (w, (wqkv, bqkv, wo, bo)) if raw else w
 
 
@@ -129,8 +130,8 @@ def attn_long_case(shape):
     assert b_core < P.EXACT_CEILING, f'long attention {shape}: core bound {b_core:.2e} does not separate a kernel fault from arithmetic'
     y_sl = [(f'seq{s}', (s // Fr, s % Fr)) for s in range(nseq)]
     b_out = {}
-    for mode in ('f32', 'bf16'):
-        oin = P.bf16r(o64.float()) if mode == 'bf16' else o64.float()
+    for mode in ('f32', 'bf16', 'f16'):
+        oin = P.bf16r(o64.float()) if mode == 'bf16' else P.f16r(o64.float()) if mode == 'f16' else o64.float()
         yo64 = (oin.double() @ wo.double() + bo.double()).reshape(x.shape) + x.double()
         yo32 = (oin @ wo + bo).reshape(x.shape) + x
         b_out[mode] = P.exact_products_bounds(yo32, yo64, y_sl, None, P.FWD_STATED)[:2]
@@ -150,19 +151,21 @@ SLA_HEADS = [
 
 
 @functools.lru_cache(maxsize=4)
-def sla_weights(C, g, raw=False):
-    """wq, wk, wv [C, 256] at 3 / sqrt C, wo [256, C] / 16, bf16-representable.  raw: -> (those, the same as drawn, before the rounding)"""
+def sla_weights(C, g, raw=False, operand='bf16'):
+    """wq, wk, wv [C, 256] at 3 / sqrt C, wo [256, C] / 16, bf16-representable (operand='f16': fp16-representable).
+    raw: -> (those, the same as drawn, before the rounding)"""
     drawn = tuple([torch.randn(C, 256, generator=g) / C ** 0.5 * 3 for _ in range(3)] + [torch.randn(256, C, generator=g) / 16])
-    w = tuple(P.bf16r(t) for t in drawn)
+    w = tuple(P.operand_rounding(operand)(t) for t in drawn)
     return (w, drawn) if raw else w
 
 
-def sla_input(shape, g):
-    """x [B, F, H, W, C], bf16-representable, with a spike in the k logits of one pixel: the online-softmax rescale"""
+def sla_input(shape, g, operand='bf16'):
+    """x [B, F, H, W, C], bf16-representable (operand='f16': fp16-representable), with a spike in the k logits of one pixel: the
+    online-softmax rescale"""
     B, Fr, H, W, C = shape
     x = torch.randn(B, Fr, H, W, C, generator=g)
     x[:, :, H // 2, W // 2] *= 6
-    return P.bf16r(x)
+    return P.operand_rounding(operand)(x)
 
 
 def sla_heads_case(shape, io16):

@@ -17,6 +17,9 @@ Where the numbers come from.  No bound in this file is derived from a kernel's o
 * attention / SLA cores round probabilities and score gradients to bf16 inside: `attn_core`, `sla_core` and `fused_attention` with
   emulate=True restate the kernels' rounding points in fp64; the per-group bound is 3 x the worst group of that
   emulation against the plain fp64 reference (the emulation cannot reproduce the MFMA summation order, hence the margin).
+* fp16 operand mode (operand='f16' of the emulations, `f16r`): the same 3 x bound, and -- because one stray bf16 rounding in an fp16
+  kernel stays inside it -- the distance to the emulation itself, in multiples of the distance between the emulation's fp32 and fp64
+  evaluations on the CPU (`assert_close_to_emulation`); the margins and how they were fixed are in tests/_attention_cases.py.
 """
 import math
 
@@ -31,6 +34,27 @@ FWD_STATED = 2e-6                  # ... and for the exact-products forward / da
 def bf16r(t: torch.Tensor) -> torch.Tensor:
     """Round-trip through bf16 (round to nearest even), keeping the dtype."""
     return t.float().to(torch.bfloat16).to(t.dtype)
+
+
+def f16r(t: torch.Tensor) -> torch.Tensor:
+    """Round-trip through IEEE half (round to nearest even, gradual underflow below 2^-14, overflow to inf past 65504 + half an ulp),
+    keeping the dtype: what v_cvt_f16_f32 / the (_Float16) casts of Mma<MODE_F16> do with subnormals enabled."""
+    return t.float().to(torch.float16).to(t.dtype)
+
+
+def f16r_ftz(t: torch.Tensor) -> torch.Tensor:
+    """f16r with results below 2^-14 in magnitude (the fp16 subnormals) set to zero: hardware that flushes them."""
+    r = f16r(t)
+    return torch.where(r.abs() < 2.0 ** -14, torch.zeros_like(r), r)
+
+
+ROUNDINGS = {'bf16': bf16r, 'f16': f16r, 'f16_ftz': f16r_ftz}
+
+
+def operand_rounding(operand):
+    """The rounding of an arithmetic mode's MFMA operand type: 'bf16' (the default everywhere), 'f16', or 'f16_ftz' (f16 with flushed
+    subnormals, for the underflow proofs)."""
+    return ROUNDINGS[operand]
 
 
 def bf16_trunc(t: torch.Tensor) -> torch.Tensor:
@@ -49,6 +73,14 @@ def bf16_ulp(t: torch.Tensor) -> torch.Tensor:
     t = t.double().abs()
     _, e = torch.frexp(t)                                   # t = m 2^e, m in [0.5, 1)
     ulp = torch.ldexp(torch.ones_like(t), e - 8)            # 8 significant bits
+    return torch.where(t > 0, ulp, torch.zeros_like(t))
+
+
+def f16_ulp(t: torch.Tensor) -> torch.Tensor:
+    """Spacing of fp16 numbers in the binade of each element (fp64; 0 for 0): 11 significant bits, 2^-24 in the subnormal range."""
+    t = t.double().abs()
+    _, e = torch.frexp(t)
+    ulp = torch.ldexp(torch.ones_like(t), (e - 11).clamp_min(-24))
     return torch.where(t > 0, ulp, torch.zeros_like(t))
 
 
@@ -320,7 +352,7 @@ def have_e4m3() -> bool:
 
 
 def attention_block_fwd(x, wqkv, bqkv, wo, bo, B, Fr, H, W, temporal, emulate=False, fp8=False, round_out=False, unmasked_pad=0,
-                        q_scaled=False, dtype=torch.float64):
+                        q_scaled=False, dtype=torch.float64, operand='bf16', stray=None):
     """y = MHA(x) + x (8 heads x 32) over the frames of every pixel (temporal) or the pixels of every frame, in `dtype` (fp64 = the
     reference; fp32 = the floor of the f32-mode bounds), closed form.
     x [B, Fr, H, W, C]; wqkv [C, 768] = q | k | v column blocks, bqkv [768], wo [256, C], bo [C].
@@ -346,12 +378,30 @@ def attention_block_fwd(x, wqkv, bqkv, wo, bo, B, Fr, H, W, temporal, emulate=Fa
     In f32 mode every one of them keeps fp32 throughout (Mma<MODE_F32>: f32 MFMA operands, 4-byte LDS elements): no rounding point, the
     bound is the exact-products kind (f32_group_bounds).
     q_scaled: q is multiplied by 1 / sqrt(32) before it is rounded (the scores are then not scaled again).
+
+    operand='f16' (mode 'f16', Mma<MODE_F16>): fp16 mode reaches attention_reg_kernel (L <= 16) and attention_kernel (17..64 tokens) alone
+    (launch_attn_m skips every attention_h8 / attention_w form, attention.hip:1267), and both round at the points listed above, every one
+    through the mode's type:
+    * attention_reg_kernel<2, TMA, false>: x staged with M::store4 (:288; exact for fp16-representable x); q = (acc + bias) * scale in fp32
+      (:352-353), q, k rounded by pack_f16x2 inside M::mma16 (:359-360 -> vdx_common.h:135-139): q_scaled; P and v rounded as the operands
+      of the PV product (:376, the same mma16); o rounded as the B operand of the out-projection's M::mma16 (:380), whose A operand is read
+      back exactly by M::load_w4 (:379); y = acc + bo + x in fp32 (:394-396).
+    * attention_kernel<2, LP, TMO>: x staged with M::store4 (:79); q = f16((acc + bias) * scale) (:140-141): q_scaled; k (:143) and v
+      (M::store1, :147-148) stored as fp16; P = s * inv stored with M::store4 (:186); o stored with M::store4 (:199); every product is
+      M::mma = v_mfma_f32_16x16x32_f16; y fp32 (:231-233).
+    No rounding point of either instantiation is hard-coded bf16; the only bf16 conversions in their text (load4_f32_or_bf16 /
+    store4_f32_or_bf16 with io_bf16) are unreachable: vdx_attention_forward_ex takes fp32 tensors, and the model refuses bf16 activation
+    storage on an f16 handle.  y stays fp32: round_out does not exist in this mode.
+    stray (a FAULT, for the CPU proofs): one of 'qkv', 'P', 'o' -- that rounding point alone rounds to bf16 instead of the operand type.
     -> (o [rows][256], y [B, Fr, H, W, C])"""
     dt = dtype
     C_ = x.shape[-1]
     X = x.to(dt).reshape(-1, C_)
     qkv = X @ wqkv.to(dt) + bqkv.to(dt)
-    rd = (e4m3r if fp8 else bf16r) if emulate else (lambda t: t)
+    assert stray in (None, 'qkv', 'P', 'o') and not (fp8 and operand != 'bf16')
+    rd_op = operand_rounding(operand)
+    at = lambda point: (lambda t: t) if not emulate else e4m3r if fp8 and point != 'o' else bf16r if stray == point else rd_op
+    rd = at('qkv')
     if q_scaled:
         qkv = torch.cat((qkv[:, :256] / math.sqrt(32.0), qkv[:, 256:]), 1)
     s = _seq_view(rd(qkv), B, Fr, H * W, 8, temporal, 3)
@@ -363,15 +413,15 @@ def attention_block_fwd(x, wqkv, bqkv, wo, bo, B, Fr, H, W, temporal, emulate=Fa
     S = torch.einsum('bsihd,bsjhd->bshij', q, k)
     if not q_scaled:
         S = S / math.sqrt(32.0)
-    P = rd(torch.softmax(S, -1))
-    o = _seq_unview(torch.einsum('bshij,bsjhd->bsihd', P, v), temporal)
-    if emulate:
-        o = bf16r(o)
-    return o, block_tail(o, x, wo, bo, round_out, dt)
+    P = at('P')(torch.softmax(S, -1))
+    o = at('o')(_seq_unview(torch.einsum('bshij,bsjhd->bsihd', P, v), temporal))
+    return o, block_tail(o, x, wo, bo, round_out, dt, operand)
 
 
-def block_tail(o, x, wo, bo=None, round_out=False, dtype=torch.float64):
-    """y = o Wo (+ bo) + x of an attention / SLA block from the per-head output o [rows][256]; round_out: y rounded to bf16."""
+def block_tail(o, x, wo, bo=None, round_out=False, dtype=torch.float64, operand='bf16'):
+    """y = o Wo (+ bo) + x of an attention / SLA block from the per-head output o [rows][256]; round_out: y rounded to bf16 (bf16 tensors
+    exist in bf16 mode only: in f16 mode y is fp32 and there is no output rounding)."""
+    assert not (round_out and operand != 'bf16'), 'f16 mode has no bf16 tensors: y is fp32'
     y = o.to(dtype) @ wo.to(dtype)
     if bo is not None:
         y = y + bo.to(dtype)
@@ -379,7 +429,19 @@ def block_tail(o, x, wo, bo=None, round_out=False, dtype=torch.float64):
     return bf16r(y) if round_out else y
 
 
-def sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W, emulate=False, round_out=False, dtype=torch.float64, fault=None):
+def running_max(K, tile, nsub):
+    """K [f, h, n, d] -> the maximum the generic SLA context kernel holds when it rounds the exponentials of each pixel: over the
+    `tile`-pixel sub-tiles of the pixel's chunk (nsub sub-tiles) up to and including its own (sla_ctx_kernel, sla.hip:138-144)."""
+    f, h, n, d = K.shape
+    nt = -(-n // tile)
+    pad = torch.full((f, h, nt * tile - n, d), -float('inf'), dtype=K.dtype)
+    tm = torch.cat((K, pad), 2).reshape(f, h, nt, tile, d).max(dim=3).values               # [f, h, nt, d]
+    run = torch.cat([tm[:, :, c:c + nsub].cummax(dim=2).values for c in range(0, nt, nsub)], 2)
+    return run.repeat_interleave(tile, dim=2)[:, :, :n]
+
+
+def sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W, emulate=False, round_out=False, dtype=torch.float64, fault=None, operand='bf16',
+                  stray=None, running=None):
     """y = SpatialLinearAttention(x) + x (8 heads x 32) in `dtype` (fp64 = the reference; fp32 = the floor of the f32-mode bounds), closed
     form: ctx = softmax_n(k)^T v, out = ctx^T softmax_d(q) per
     (frame, head).  wq / wk / wv [C, 256], wo [256, C].  emulate: the rounding points of sla_head_kernel (sla.hip): exp(k - max) and v
@@ -402,6 +464,20 @@ def sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W, emulate=False, round_out=False
       :181-183, fp32 partials (:189) -> sla_combine_kernel as above.  sla_out_kernel: softmax_d(q) stored as bf16 (:309), ctxT read as
       bf16 (:320), o stored as bf16 (:329), y fp32 (:360-364).
     In f32 mode all of them keep fp32 throughout (ctxT included: M::store1 of Mma<MODE_F32>): the bound is f32_group_bounds.
+    operand='f16' (mode 'f16', Mma<MODE_F16>): fp16 mode runs the generic kernels for EVERY channel count (launch_sla_m skips the
+    one-wave-per-head forms, sla.hip:1218), and they round at the points above, every one through the mode's type:
+    * sla_ctx_kernel<2>: x staged with M::store4 (:88; exact for fp16-representable x); e = exp(k - running max) stored with M::store1
+      (:156-157) while the sum takes the unrounded e (:158); v stored with M::store1 (:171); context product M::mma (:181-183), rescaled
+      by alpha in fp32 (:178); fp32 partials (:189-190).
+    * sla_combine_kernel<2>: partials merged and divided by the denominator in fp32 (:212-219), ctx stored ONCE with M::store1 (:221).
+    * sla_out_kernel<2, TMO>: x staged with M::store4 (:265); softmax_d(q) stored with M::store4 (:309); ctxT read as fp16 (:320); o
+      stored with M::store4 (:329); to_out M::mma (:349); y = acc + x in fp32 (:360-364).
+    No rounding point of the three is hard-coded bf16 (the io_bf16 loads / stores are unreachable: vdx_sla_forward takes fp32 tensors).
+    Unlike bf16, fp16 rounding is relative only down to 2^-14: below, the spacing is 2^-24 absolute.  exp(k - max) of most pixels of a
+    frame IS that small, so in this mode it matters which maximum the kernel subtracts before it rounds: `running`.
+    running = (tile, nsub): the exponentials are rounded against the running maximum of sla_ctx_kernel (running_max) and rescaled to the
+    final maximum unrounded, as the kernel's alpha (:142, :178) and the combine's exp(m_chunk - m) (:217) do in fp32.
+    stray (a FAULT, for the CPU proofs): one of 'ek', 'v', 'ctx', 'qs', 'o' -- that rounding point alone rounds to bf16.
     fault (for the CPU proofs): ('drop_ctx', f, h, n0) -- pixels n0.. of frame f are missing from head h's context, numerator and
     denominator (a chunk partial the combine never adds); ('swap_ctx', f, n0, n1, f2) -- pixels n0..n1 of frame f take frame f2's context.
     -> (o [rows][256], y [B, Fr, H, W, C])"""
@@ -410,21 +486,29 @@ def sla_block_fwd(x, wq, wk, wv, wo, B, Fr, H, W, emulate=False, round_out=False
     X = x.to(dt).reshape(-1, C_)
     hs = lambda t: t.reshape(NF, N, 8, 32).permute(0, 2, 1, 3)                      # [f, h, n, d]
     Q, K, V = hs(X @ wq.to(dt)), hs(X @ wk.to(dt)), hs(X @ wv.to(dt))
-    rd = bf16r if emulate else (lambda t: t)
+    assert stray in (None, 'ek', 'v', 'ctx', 'qs', 'o')
+    rd_op = operand_rounding(operand)
+    at = lambda point: (lambda t: t) if not emulate else bf16r if stray == point else rd_op
+    rd = rd_op if emulate else (lambda t: t)
     qs = torch.softmax(Q, -1)
-    ek = torch.exp(K - K.max(dim=2, keepdim=True).values)
+    kmax = K.max(dim=2, keepdim=True).values
+    ek = torch.exp(K - kmax)
     if fault and fault[0] == 'drop_ctx':
         ek = ek.clone()
         ek[fault[1], fault[2], fault[3]:] = 0.0
-    ctx = torch.einsum('fhnd,fhne->fhde', rd(ek), rd(V)) / ek.sum(2, keepdim=True).transpose(2, 3)
-    o = torch.einsum('fhde,fhnd->fhne', rd(ctx), rd(qs))
+    if running and emulate:
+        assert not fault
+        run = running_max(K, *running)
+        ekr = at('ek')(torch.exp(K - run)) * torch.exp(run - kmax)
+    else:
+        ekr = at('ek')(ek)
+    ctx = torch.einsum('fhnd,fhne->fhde', ekr, at('v')(V)) / ek.sum(2, keepdim=True).transpose(2, 3)
+    o = torch.einsum('fhde,fhnd->fhne', at('ctx')(ctx), at('qs')(qs))
     if fault and fault[0] == 'swap_ctx':
         _, f, n0, n1, f2 = fault
         o[f, :, n0:n1] = torch.einsum('hde,hnd->hne', rd(ctx[f2]), rd(qs[f, :, n0:n1]))
-    o = o.permute(0, 2, 1, 3).reshape(NF * N, 256)
-    if emulate:
-        o = bf16r(o)
-    return o, block_tail(o, x, wo, None, round_out, dt)
+    o = at('o')(o.permute(0, 2, 1, 3).reshape(NF * N, 256))
+    return o, block_tail(o, x, wo, None, round_out, dt, operand)
 
 
 def seq_head_groups(o, B, Fr, HW, temporal):
@@ -523,6 +607,26 @@ def assert_views(got, ref, view, bound, what='', chunk=None):
     return r[i].item()
 
 
+def assert_close_to_emulation(got, emu64, emu32, view, margin, what='', chunk=None):
+    """A kernel's output against the EMULATION of its rounding points, not against the plain reference: what can see a rounding of the
+    wrong type (one stray bf16 rounding in an fp16 kernel stays inside 3 x the emulation's own distance from the reference, but sits far
+    from the emulation).  emu64, emu32: the same emulation evaluated on the CPU in fp64 and in fp32 -- their distance is the floor a
+    correct kernel has too: values computed in fp32 land on the other side of a rounding boundary for a few elements.  Every group of
+    `view`: rel(got, emu64) <= max(FWD_STATED, margin x the worst group of rel(emu32, emu64)).  -> (worst rel, floor): worst / floor is the
+    figure to report."""
+    assert got.shape == emu64.shape == emu32.shape, (what, got.shape, emu64.shape, emu32.shape)
+    floor = view_rels(emu32, emu64, view, chunk).max().item()
+    bound = max(FWD_STATED, margin * floor)
+    r = view_rels(got, emu64, view, chunk)
+    r = torch.where(torch.isfinite(r), r, torch.full_like(r, float('inf')))
+    i = int(r.argmax())
+    print(f'[closeness] {what}: {r.numel()} groups, worst group {i} rel {r[i].item():.3e} to the emulation = {r[i].item() / floor:.2f} x the flip floor '
+          f'{floor:.3e} (bound {margin:g} x = {bound:.3e})')
+    nbad = int((~(r <= bound)).sum())
+    assert nbad == 0, f'{what}: {nbad} group(s) further than {bound:.3e} from the emulation, worst group {i} at {r[i].item():.3e}'
+    return r[i].item(), floor
+
+
 def norm_bound(ref32, ref64, slices=None, stated=FWD_STATED):
     """Bound for an fp32 output of norm arithmetic (GroupNorm / LayerNorm / SiLU chains): max(stated, 8 x the same formula evaluated in
     fp32 on the CPU against fp64), globally and per slice; refused at 1e-4 or more.  -> (bound, {label: bound}, floor)"""
@@ -558,18 +662,21 @@ def tile_rels(got, ref, tile=16):
     return (g - r).norm(dim=-1) / (r.norm(dim=-1) + 1e-300)
 
 
-def tile_bound(act32_rounded, act64_rounded, out_of, tile=16, stated=FWD_STATED, bf16_out=False):
+def tile_bound(act32_rounded, act64_rounded, out_of, tile=16, stated=FWD_STATED, bf16_out=False, operand='bf16'):
     """Per-tile bound of a fused-prologue conv: the kernel rounds the activation it recomputes to bf16; computed in fp32 it lands on the
     other side of a rounding boundary for a few elements.  floor = the worst tile of out_of(activation computed in fp32, rounded)
     against out_of(activation computed in fp64, rounded), not below the effect of ONE flipped element of rms size on a tile's output,
     bf16_ulp(rms) / ||activation of one tile||; bound = max(stated, 4 x floor).  bf16_out: the output is stored as bf16 -- one rounding
     moves an element by at most 2^-9 of itself, hence a tile's rel-L2 by at most 2^-9, which is added (a figure of the number format;
-    a tile row scaled by 0.9 is 0.1 / sqrt(16) = 2.5e-2, an order above it).  -> (bound, floor)"""
+    a tile row scaled by 0.9 is 0.1 / sqrt(16) = 2.5e-2, an order above it).  operand='f16': the activation is rounded to fp16 (the caller
+    rounds it so), one flipped element moves by an fp16 ulp; there are no bf16 outputs in that mode.  -> (bound, floor)"""
+    assert not (bf16_out and operand != 'bf16')
+    ulp = bf16_ulp if operand == 'bf16' else f16_ulp
     ref, alt = out_of(act64_rounded), out_of(act32_rounded)
     t = min(tile, ref.shape[2], ref.shape[3])
     floor = tile_rels(alt, ref, t).max().item()
     a = act64_rounded.double()
-    one_flip = (bf16_ulp(a.pow(2).mean().sqrt()) / (a.pow(2).mean().sqrt() * math.sqrt(t * t * a.shape[-1]))).item()
+    one_flip = (ulp(a.pow(2).mean().sqrt()) / (a.pow(2).mean().sqrt() * math.sqrt(t * t * a.shape[-1]))).item()
     floor = max(floor, one_flip)
     return max(stated, 4.0 * floor) + (BF16_ROUNDING if bf16_out else 0.0), floor
 

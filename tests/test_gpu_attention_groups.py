@@ -24,6 +24,7 @@ import _attention_cases as AC
 import _parity as P
 from _launch_hook import assert_launches, launches
 
+# (tests/test_gpu_f16_forms.py runs the shapes that only fp16 mode needs through _run_attention / _run_sla / _check of this module)
 DEV = 'cuda:0'
 F32, BF = torch.float32, torch.bfloat16
 
@@ -59,6 +60,9 @@ def _check(c, y, what):
         assert torch.isfinite(branch[i:i + step]).all(), f'{what}: non-finite output (a row the kernel did not write?)'
     for name, view in c['views'].items():
         P.assert_views(branch, ref, view, c['bounds'][name], f'{what} per {name}', c['chunk'])
+    if c.get('emu32') is not None:                                      # mode f16: close to the emulation of its rounding points as well
+        for name, view in c['views'].items():
+            P.assert_close_to_emulation(branch, c['cmp'], c['emu32'], view, AC.close_margin(c), f'{what} per {name}', c['chunk'])
 
 
 def _run_attention(c, mode, io16, fp8, what):
@@ -136,22 +140,37 @@ def test_attention_bf16_tensors_per_group(shape, fp8, iso, kernel, parts):
 # f32 packs rows in K tiles of 32 channels, bf16 of 64: nkt = CPad / KT.  attention_h8 takes C = 64 (nkt 1 or 2) and C = 128 with nkt = 2,
 # so C = 128 in f32 mode (nkt = 4) goes to attention_reg_kernel, like every C it has no form for; more than 16 tokens: attention_kernel
 # <MODE, LP, TMO>.  attention_reg_kernel and attention_kernel scale q before they round it (q_scaled).  attention_reg "<MODE, TMA, fp8>".
+# Mode f16 (MODE 2) has no attention_h8 / attention_w form at all: attention_reg_kernel up to 16 tokens, attention_kernel beyond; its cases
+# are held to the closeness-to-emulation check as well (_check).  The shapes only fp16 mode needs are in tests/test_gpu_f16_forms.py.
 ATTN32 = [
     # shape, temporal, iso, {mode: (kernel, parts, q_scaled)}
     ((1, 16, 8, 8, 64), True, False, {'f32': ('attention_h8_kernel', ['<0, 2, 1, 2, 0, 0, 0>', 'C64 L16 nseq64'], False),       # the nkt = 2 f32 form
-                                      'bf16': ('attention_h8_kernel', ['<1, 1, 1, 2, 0, 0, 0>', 'C64 L16 nseq64'], False)}),
+                                      'bf16': ('attention_h8_kernel', ['<1, 1, 1, 2, 0, 0, 0>', 'C64 L16 nseq64'], False),
+                                      'f16': ('attention_reg_kernel', ['<2, 4, fp8 0>', 'C64 L16 nseq64'], True)}),               # the shape the other modes serve with attention_h8
     ((1, 10, 6, 6, 128), True, False, {'f32': ('attention_reg_kernel', ['<0, 8, fp8 0>', 'C128 L10 nseq36'], False),            # 128 / 32 = 4 K tiles: no h8 form
-                                       'bf16': ('attention_h8_kernel', ['<1, 2, 1, 4, 0, 0, 0>', 'C128 L10 nseq36'], False)}),
+                                       'bf16': ('attention_h8_kernel', ['<1, 2, 1, 4, 0, 0, 0>', 'C128 L10 nseq36'], False),
+                                       'f16': ('attention_reg_kernel', ['<2, 8, fp8 0>', 'C128 L10 nseq36'], True)}),             # keys 10..15 masked
     ((1, 16, 2, 2, 256), True, False, {'f32': ('attention_reg_kernel', ['<0, 16, fp8 0>', 'C256 L16 nseq4'], False),
-                                       'bf16': ('attention_reg_kernel', ['<1, 16, fp8 0>', 'C256 L16 nseq4'], True)}),
+                                       'bf16': ('attention_reg_kernel', ['<1, 16, fp8 0>', 'C256 L16 nseq4'], True),
+                                       'f16': ('attention_reg_kernel', ['<2, 16, fp8 0>', 'C256 L16 nseq4'], True)}),
     ((1, 2, 5, 5, 64), False, False, {'f32': ('attention_kernel', ['<0, 32, 1>', 'C64 L25 nseq2'], False),                       # 25 tokens -> LP 32, keys 25..31 masked
-                                      'bf16': ('attention_kernel', ['<1, 32, 1>', 'C64 L25 nseq2'], True)}),
+                                      'bf16': ('attention_kernel', ['<1, 32, 1>', 'C64 L25 nseq2'], True),
+                                      'f16': ('attention_kernel', ['<2, 32, 1>', 'C64 L25 nseq2'], True)}),
     ((1, 3, 8, 8, 128), False, False, {'f32': ('attention_kernel', ['<0, 64, 2>', 'C128 L64 nseq3'], False),
-                                       'bf16': ('attention_kernel', ['<1, 64, 2>', 'C128 L64 nseq3'], True)}),
+                                       'bf16': ('attention_kernel', ['<1, 64, 2>', 'C128 L64 nseq3'], True),
+                                       'f16': ('attention_kernel', ['<2, 64, 2>', 'C128 L64 nseq3'], True)}),
+    # 9 sequences (inner = 9 is no multiple of 4: no h8 form in any mode): 3 workgroups of 4, the last one with a single sequence
+    ((1, 10, 3, 3, 64), True, False, {'f32': ('attention_reg_kernel', ['<0, 4, fp8 0>', 'C64 L10 nseq9'], False),
+                                      'bf16': ('attention_reg_kernel', ['<1, 4, fp8 0>', 'C64 L10 nseq9'], True),
+                                      'f16': ('attention_reg_kernel', ['<2, 4, fp8 0>', 'C64 L10 nseq9'], True)}),
+    # 32 frames (the temporal attention of BASELINE configs[3]): LP 32, workgroups of 2 sequences, 3 sequences: the last one half empty
+    ((1, 32, 1, 3, 128), True, False, {'f32': ('attention_kernel', ['<0, 32, 2>', 'C128 L32 nseq3'], False),
+                                       'bf16': ('attention_kernel', ['<1, 32, 2>', 'C128 L32 nseq3'], True),
+                                       'f16': ('attention_kernel', ['<2, 32, 2>', 'C128 L32 nseq3'], True)}),
 ]
 
 
-@pytest.mark.parametrize('mode', ['f32', 'bf16'])
+@pytest.mark.parametrize('mode', ['f32', 'bf16', 'f16'])
 @pytest.mark.parametrize('shape,temporal,iso,expect', ATTN32)
 def test_attention_fp32_tensors_per_group(shape, temporal, iso, expect, mode):
     kernel, parts, q_scaled = expect[mode]
@@ -207,14 +226,14 @@ def test_sla_bf16_tensors_per_group(shape, iso, expect):
 # one wave per head (sla_ctx8 / sla_out8) for C = 64 with nkt 1 or 2 and C = 128 with nkt = 2; everything else -- C = 128 in f32 mode (4 K
 # tiles), C = 256, C = 16 -- runs the generic sla_ctx_kernel -> sla_combine_kernel -> sla_out_kernel <MODE, TMO>.
 def _sla32(mode, C, N, NF, nchunk):
-    m = 0 if mode == 'f32' else 1
+    m = {'f32': 0, 'bf16': 1, 'f16': 2}[mode]
     nkt = -(-C // (32 if mode == 'f32' else 64))
-    if (C == 64 and nkt <= 2) or (C == 128 and nkt == 2):
+    if mode != 'f16' and ((C == 64 and nkt <= 2) or (C == 128 and nkt == 2)):      # (f16 has no one-wave-per-head form: always generic)
         seq = [('sla_ctx8_kernel', [f'<{m}, {nkt}, 0>', f'C{C} N{N} NF{NF} nchunk{nchunk}'])]
         if nchunk > 1:
             seq.append(('sla_combine_kernel', [f'<{m}>', f'NF{NF} nchunk{nchunk}']))
         return seq + [('sla_out8_kernel', [f'<{m}, {nkt}, 1, {2 if C == 64 else 4}, 0>', f'C{C} N{N} NF{NF}'])]
-    tmo = 1 if C <= 64 else 2 if C <= 128 else 4
+    tmo = 1 if C <= 64 else 2 if C <= 128 else 4 if C <= 256 else 8 if C <= 512 else 16
     return [('sla_ctx_kernel', [f'<{m}>', f'C{C} N{N} NF{NF} nchunk{nchunk}']), ('sla_combine_kernel', [f'<{m}>', f'NF{NF} nchunk{nchunk}']),
             ('sla_out_kernel', [f'<{m}, {tmo}>', f'C{C} N{N} NF{NF}'])]
 
@@ -229,7 +248,7 @@ SLA32 = [
 ]
 
 
-@pytest.mark.parametrize('mode', ['f32', 'bf16'])
+@pytest.mark.parametrize('mode', ['f32', 'bf16', 'f16'])
 @pytest.mark.parametrize('shape,iso,nchunk', SLA32)
 def test_sla_fp32_tensors_per_group(shape, iso, nchunk, mode):
     B, Fr, H, W, C = shape

@@ -15,6 +15,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import _parity as P
+from _launch_hook import assert_launches, launches, nan_outputs
 from oracle import train_ref as TR
 from oracle import unet3d_ref as R
 
@@ -396,7 +397,7 @@ def test_sla_core_backward_interleaved(NF, H, W, io16):
 # ---- data gradient through a row slice of the transposed packing ----------------------------------------------------------------------
 
 
-@pytest.mark.parametrize('mode,dy16', [('f32', False), ('bf16', False), ('bf16', True)])
+@pytest.mark.parametrize('mode,dy16', [('f32', False), ('bf16', False), ('bf16', True), ('f16', False)])
 @pytest.mark.parametrize('k,B,Fr,H,W,cin,cout', [(3, 1, 16, 64, 64, 128, 64),       # ups level 0 block1 (concat 64 | 64): the persistent 64-channel kernel
                                                  (1, 1, 16, 16, 16, 512, 256),      # res_conv of a wide level (256 | 256)
                                                  (3, 1, 3, 9, 17, 48, 40)])         # generic kernel, ragged
@@ -406,6 +407,8 @@ def test_dgrad_row_slice_with_res(mode, dy16, k, B, Fr, H, W, cin, cout):
     kern = P.bf16r(torch.randn(1, k, k, cin, cout, generator=g) / (k * k * cout) ** 0.5)
     dy = P.bf16r(torch.randn(B, Fr, H, W, cout, generator=g))
     res = P.bf16r(torch.randn(B, Fr, H, W, cin, generator=g))
+    if mode == 'f16':           # (representable in both types: only a bf16 number below 2^-17 is no fp16 number; every f16 conv runs conv_igemm_kernel<2, .., 0>)
+        kern, dy = P.f16r(kern), P.f16r(dy)
 
     def gx_of(dt):
         x = torch.zeros(B, Fr, H, W, cin, dtype=dt, requires_grad=True)
@@ -420,7 +423,17 @@ def test_dgrad_row_slice_with_res(mode, dy16, k, B, Fr, H, W, cin, cout):
         sl = P.sample_slices(ref.shape) + [(f'frame{f}', (slice(None), f)) for f in range(Fr)]
         r64, r32 = ref[..., row0:row0 + half], ref32[..., row0:row0 + half]
         bound, sb, floor = P.exact_products_bounds(r32, r64, sl, stated=P.FWD_STATED)
-        got = ops.conv_dgrad_rows(_dev(dy, BF if dy16 else F32), pwt, cin, row0, half, mode=mode, k=k, res=_dev(res[..., row0:row0 + half]))
+        run = lambda: ops.conv_dgrad_rows(_dev(dy, BF if dy16 else F32), pwt, cin, row0, half, mode=mode, k=k, res=_dev(res[..., row0:row0 + half]))
+        if mode == 'f16':       # no persistent / pointwise form may take mode 2: twice on NaN-filled outputs, bit-identical, the generic kernel both times
+            what = f'dgrad rows k={k} {cin}->({half}|{half}) row0={row0} f16'
+            with launches() as rec, nan_outputs():
+                got, again = run(), run()
+                torch.cuda.synchronize()
+            assert torch.equal(got.view(torch.uint8), again.view(torch.uint8)), f'{what}: two runs are not bit-identical'
+            print(f'[{what}] launched: {rec}')
+            assert_launches(rec, 2 * [('conv_igemm_kernel', [f'<2, {64 if half <= 64 else 128}, 2, 8, 0>', f'conv{k}x{k} {cout}->{half}', '+res'])], what)
+        else:
+            got = run()
         torch.cuda.synchronize()
         P.assert_exact_products(got.cpu(), r64, bound, sl, sb, what=f'dgrad rows k={k} {cin}->({half}|{half}) row0={row0} {mode} dy16={int(dy16)} (CPU floor {floor:.1e})')
 

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 
 import _forward_cases as FC
 import _parity as P
+from _launch_hook import assert_launches, launches
 from oracle import unet3d_ref as R
 
 DEV = 'cuda:0'
@@ -95,7 +96,7 @@ def test_attention_heads_rejects_what_the_network_routes_elsewhere():
 
 # ---- long attention core ------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize('mode,io16', [('f32', False), ('bf16', False), ('bf16', True)])
+@pytest.mark.parametrize('mode,io16', [('f32', False), ('bf16', False), ('bf16', True), ('f16', False)])
 @pytest.mark.parametrize('shape', FC.ATTN_LONG)
 def test_attention_long(shape, mode, io16):
     """1x1 q|k|v conv -> attention_long_core_kernel -> 1x1 out-projection + residual (more than 64 tokens).  Each stage is judged on
@@ -107,8 +108,13 @@ def test_attention_long(shape, mode, io16):
     wqkv, bqkv, wo, bo = c['w']
     packed = (ops.pack_conv_weights(_dev(wqkv), mode), _dev(bqkv), ops.pack_conv_weights(_dev(wo), mode), _dev(bo))
     x = _dev(c['x'], BF if io16 else F32)
-    y, qkv, o = _twice(lambda: ops.attention_long_forward(x, packed, 8, mode))
     what = f'long attention {shape} {mode} io16={int(io16)}'
+    with launches() as rec:                     # (ops.attention_long_forward NaN-fills y and the scratch itself)
+        y, qkv, o = _twice(lambda: ops.attention_long_forward(x, packed, 8, mode))
+    if mode == 'f16':           # both projections on the fp16 form of the generic conv (x and the weights here are fp16 numbers as well)
+        assert_launches(rec[:3], [('conv_igemm_kernel', ['<2, 128, 2, 8, 0>', 'conv1x1 128->768']), ('attention_long_core_kernel', [f"L{c['L']}"]),
+                                  ('conv_igemm_kernel', ['<2, 128, 2, 8, 0>', 'conv1x1 256->128', '+res'])], what)
+        assert rec[3:] == rec[:3]
     for t, n in ((qkv, 'qkv'), (o, 'o'), (y, 'y')):
         _finite(t, f'{what} {n}')
     P.assert_exact_products(qkv, c['qkv64'], c['b_qkv'], c['seq_sl'], c['sb_qkv'], None, what + ' qkv')
@@ -116,7 +122,7 @@ def test_attention_long(shape, mode, io16):
     nseq, L, hg = c['nseq'], c['L'], c['hg']
     P.assert_groups(hg(o), hg(FC.long_core(qkv, nseq, L, F64)), (nseq * 8,), c['b_core'], what + ' o per (sequence, head)')
     # the out-projection: reference = the o it read (bf16 mode: rounded to bf16 at staging) . Wo + bias + residual in fp64
-    oin = P.bf16r(o) if mode == 'bf16' else o
+    oin = P.bf16r(o) if mode == 'bf16' else P.f16r(o) if mode == 'f16' else o
     y64 = (oin.double() @ wo.double() + bo.double()).reshape(c['x'].shape) + c['x'].double()
     b_y, sb_y = c['b_out'][mode]
     if io16:

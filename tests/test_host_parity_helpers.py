@@ -570,3 +570,153 @@ def test_head_isolating_out_projection_and_q_scaling_flag():
     ae = P.attention_block_fwd(x, *w, *shape[:4], True, emulate=True)[1]
     be = P.attention_block_fwd(x, *w, *shape[:4], True, emulate=True, q_scaled=True)[1]
     assert 0 < P.rel(be, ae) < 1e-2
+
+
+# ---- fp16 operand mode (tests/test_gpu_f16_forms.py and the f16 entries of tests/test_gpu_attention_groups.py) --------------------------------
+# fp16 rounding is 8 x finer than bf16: ONE bf16 rounding left in an fp16 kernel stays inside 3 x the fp16 emulation's own distance from the
+# reference (and far inside the whole-network 4e-3).  What sees it is the distance to the EMULATION, measured in multiples of the distance
+# between the emulation's own fp32 and fp64 evaluations (P.assert_close_to_emulation).
+
+import test_gpu_attention_groups as G
+import test_gpu_f16_forms as G16
+
+
+def _f16_attention_cases():
+    return [(s, t, iso) for s, t, iso, e in G.ATTN32 if 'f16' in e] + [(s, t, iso) for s, t, iso, _, _ in G16.ATTN_F16]
+
+
+def _f16_sla_cases():
+    return [(s, iso) for s, iso, _ in G.SLA32] + [(s, iso) for s, iso, _ in G16.SLA_F16]
+
+
+def test_f16_rounding_known_answers():
+    t = lambda *v: torch.tensor(v, dtype=torch.float64)
+    x = t(1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, 65504.0, 65520.0, 2.0 ** -24, 2.0 ** -25, -(2.0 ** -14), -(2.0 ** -14) * (1 - 2.0 ** -10))
+    assert torch.equal(P.f16r(x), t(1.0, 1 + 2.0 ** -9, 65504.0, float('inf'), 2.0 ** -24, 0.0, -(2.0 ** -14), -(2.0 ** -14) * (1 - 2.0 ** -10)))
+    assert torch.equal(P.f16r_ftz(x), t(1.0, 1 + 2.0 ** -9, 65504.0, float('inf'), 0.0, 0.0, -(2.0 ** -14), 0.0))       # the smallest normal stays
+    assert P.f16r(x.float()).dtype == torch.float32 and P.f16r(x).dtype == torch.float64
+    assert torch.equal(P.f16_ulp(t(1.0, 1.5, 3.0, 2.0 ** -14, 2.0 ** -20, 0.0)), t(2.0 ** -10, 2.0 ** -10, 2.0 ** -9, 2.0 ** -24, 2.0 ** -24, 0.0))
+    assert P.operand_rounding('bf16') is P.bf16r and P.operand_rounding('f16') is P.f16r
+    # the running maximum of the generic SLA context kernel: per chunk of nsub tiles, up to and including the pixel's own tile
+    K = torch.tensor([1.0, 0.0, 5.0, 2.0, 3.0, 9.0, 0.0]).reshape(1, 1, 7, 1)
+    assert P.running_max(K, 2, 1).flatten().tolist() == [1.0, 1.0, 5.0, 5.0, 9.0, 9.0, 0.0]          # chunks of one tile: the tile's own maximum
+    assert P.running_max(K, 2, 4).flatten().tolist() == [1.0, 1.0, 5.0, 5.0, 9.0, 9.0, 9.0]          # one chunk: the ragged last tile keeps the 9
+    K = torch.tensor([5.0, 0.0, 1.0, 0.0, 2.0, 0.0, 1.0]).reshape(1, 1, 7, 1)
+    assert P.running_max(K, 2, 2).flatten().tolist() == [5.0, 5.0, 5.0, 5.0, 2.0, 2.0, 2.0]          # the second chunk starts afresh
+    # the default operand leaves the bf16 emulations as they were
+    g = torch.Generator().manual_seed(6)
+    x = P.bf16r(torch.randn(1, 4, 3, 3, 64, generator=g))
+    w = FC.mha_weights(64, g)
+    assert torch.equal(P.attention_block_fwd(x, *w, 1, 4, 3, 3, True, emulate=True)[1], P.attention_block_fwd(x, *w, 1, 4, 3, 3, True, emulate=True, operand='bf16')[1])
+    with pytest.raises(AssertionError):
+        P.block_tail(torch.zeros(36, 256), x, w[2], None, True, operand='f16')                   # no bf16 output in f16 mode
+
+
+def test_fp32_evaluation_of_the_f16_emulations_passes_and_underflow_does_not_decide():
+    """Every f16 case of the GPU tests: the emulation evaluated in fp32 -- a correct kernel up to summation order -- passes the case's
+    3 x bounds and (trivially, at ratio 1) the closeness check; the derived bounds sit in [5e-4, 5e-3]; and the emulation with fp16
+    subnormals flushed to zero differs from the IEEE one by less than a third of each bound, so that these tests do not depend on what the
+    hardware does with subnormals (tests/test_gpu_f16_forms.py test_conv_f16_subnormal_operands asks that question itself)."""
+    for shape, temporal, iso in _f16_attention_cases():
+        c = AC.attn_case(shape, temporal, False, 'f16', False, iso, True)
+        ftz = P.attention_block_fwd(c['x'], *c['w'], *shape[:4], temporal, emulate=True, q_scaled=True, operand='f16_ftz')[1] - c['x'].double()
+        _f16_case_checks(c, ftz, f'attention {shape} iso={int(iso)}')
+    for shape, iso in _f16_sla_cases():
+        c = AC.sla_case(shape, False, 'f16', iso)
+        ftz = AC.sla_eval(c['x'], c['w'], **dict(AC.sla_f16_kw(c['N']), operand='f16_ftz'))
+        _f16_case_checks(c, ftz, f'SLA {shape} iso={int(iso)}')
+
+
+def _f16_case_checks(c, ftz, what):
+    for n, v in c['views'].items():
+        b = c['bounds'][n]
+        assert 5e-4 < b < AC.F16_BOUND_CEILING
+        P.assert_views(c['emu32'], c['ref'], v, b, f'fp32 emulation, {what} per {n}')
+        P.assert_close_to_emulation(c['emu32'], c['cmp'], c['emu32'], v, AC.close_margin(c), f'fp32 emulation, {what} per {n}')
+        d = P.view_rels(ftz, c['cmp'], v).max().item()
+        print(f'[underflow] {what} per {n}: flushed subnormals move the emulation by {d:.3e} (bound {b:.3e})')
+        assert d < b / 3
+
+
+def _stray_figures(c, evaluate, points, what):
+    """One bf16 rounding at a time in the fp32 evaluation of the f16 emulation.  -> {point: (passes the reference bounds, smallest over
+    the views of distance to the emulation / flip floor, rel-L2 of y)}"""
+    out = {}
+    x = c['x'].double()
+    for pt in points:
+        bad = evaluate(pt)
+        passes = all(bool((P.view_rels(bad, c['ref'], v) < c['bounds'][n]).all()) for n, v in c['views'].items())
+        for n, v in c['views'].items():
+            print(f'[stray bf16 rounding] {what}, at {pt}, per {n}: worst group {P.view_rels(bad, c["ref"], v).max().item():.2e} from the reference '
+                  f'(bound {c["bounds"][n]:.2e})')
+        ratio = min(P.view_rels(bad, c['cmp'], v).max().item() / P.view_rels(c['emu32'], c['cmp'], v).max().item() for v in c['views'].values())
+        out[pt] = (passes, ratio, P.rel(bad + x, c['ref'] + x))
+        print(f'[stray bf16 rounding] {what}, at {pt}: {"inside" if passes else "REJECTED by"} the 3 x reference bounds; {ratio:.1f} x the flip floor from the '
+              f'emulation; y rel-L2 {out[pt][2]:.2e}')
+    return out
+
+
+def test_one_stray_bf16_rounding_in_an_f16_kernel_is_seen_by_the_closeness_check_only():
+    margin = AC.F16_CLOSE_MARGIN
+    smallest = {'attention': float('inf'), 'sla': float('inf')}
+    for shape, temporal in (((1, 16, 8, 8, 64), True), ((1, 32, 1, 3, 256), True)):           # attention_reg_kernel, attention_kernel
+        c = AC.attn_case(shape, temporal, False, 'f16', False, False, True)
+        ev = lambda pt: P.attention_block_fwd(c['x'], *c['w'], *shape[:4], temporal, emulate=True, q_scaled=True, operand='f16', stray=pt,
+                                              dtype=torch.float32)[1].double() - c['x'].double()
+        f = _stray_figures(c, ev, ('qkv', 'P', 'o'), f'attention {shape}')
+        assert [pt for pt, r in f.items() if not r[0]] == ['qkv'], 'the reference bound sees a bf16 rounding of q | k | v only'
+        assert all(r[1] >= 2 * margin['attention'] and r[2] < 4e-3 for r in f.values())
+        smallest['attention'] = min(smallest['attention'], *[r[1] for r in f.values()])
+    for shape in ((1, 1, 24, 24, 256), (1, 2, 64, 64, 64)):                                    # two chunks (ragged), eight chunks
+        c = AC.sla_case(shape, False, 'f16')
+        ev = lambda pt: AC.sla_eval(c['x'], c['w'], dtype=torch.float32, **dict(AC.sla_f16_kw(c['N']), stray=pt))
+        f = _stray_figures(c, ev, ('ek', 'v', 'ctx', 'qs', 'o'), f'SLA {shape}')
+        # SLA's emulation sits 3.5e-4 from the reference, half of attention's: its 3 x bound (1.1e-3) does reject one bf16 rounding anywhere
+        # but at exp(k), whose error the softmax denominator largely divides out -- 3.8e-4, inside every bound and a few flip floors from the
+        # emulation: the one rounding point neither check can see
+        assert [pt for pt, r in f.items() if r[0]] == ['ek']
+        assert all(r[1] >= 2 * margin['sla'] for pt, r in f.items() if pt != 'ek') and f['ek'][1] < 2 * margin['sla']
+        assert all(r[2] < 4e-3 for r in f.values()), 'the whole-network style figure lets every one of them pass'
+        smallest['sla'] = min(smallest['sla'], *[r[1] for pt, r in f.items() if pt != 'ek'])
+    print(f'[stray bf16 rounding] smallest ratios: {smallest}; margins in use {margin}, {AC.F16_CLOSE_MARGIN_OF_CASE}')
+    assert all(margin[k] <= smallest[k] / 2 for k in margin), 'a closeness margin above half the smallest single-stray ratio no longer sees it'
+    for (kind, shape, iso), m in AC.F16_CLOSE_MARGIN_OF_CASE.items():              # a case with a margin of its own: against its OWN stray ratios
+        assert kind == 'sla' and m <= smallest[kind] / 2
+        c = AC.sla_case(shape, False, 'f16', iso)
+        ev = lambda pt: AC.sla_eval(c['x'], c['w'], dtype=torch.float32, **dict(AC.sla_f16_kw(c['N']), stray=pt))
+        f = _stray_figures(c, ev, ('v', 'ctx', 'qs', 'o'), f'SLA {shape}')
+        assert all(r[1] >= 2 * m for r in f.values()), f'SLA {shape}: margin {m} no longer sees one stray rounding'
+    # and the check itself rejects
+    c = AC.attn_case((1, 16, 8, 8, 64), True, False, 'f16', False, False, True)
+    bad = P.attention_block_fwd(c['x'], *c['w'], 1, 16, 8, 8, True, emulate=True, q_scaled=True, operand='f16', stray='P', dtype=torch.float32)[1].double() - c['x'].double()
+    v = c['views']['sequence']
+    P.assert_views(bad, c['ref'], v, c['bounds']['sequence'], 'stray P against the reference')
+    with pytest.raises(AssertionError, match='from the emulation'):
+        P.assert_close_to_emulation(bad, c['cmp'], c['emu32'], v, margin['attention'], 'stray P')
+    nan = c['emu32'].clone()
+    nan[0, 3, 2, 1] = float('nan')
+    with pytest.raises(AssertionError, match='from the emulation'):
+        P.assert_close_to_emulation(nan, c['cmp'], c['emu32'], v, margin['attention'], 'one NaN')
+
+
+def test_f16_prologue_tile_bound_and_rounding_against_the_final_maximum():
+    """tile_bound on an fp16-rounded activation: the flip floor is an eighth of the bf16 one; and the SLA emulation that rounds exp(k)
+    against the final maximum (right for bf16, where rounding is relative at every magnitude) is further from the running-maximum
+    emulation than the flip floor: in fp16 mode the kernel's order matters."""
+    g = torch.Generator().manual_seed(12)
+    C = 32
+    y1 = torch.randn(2, 2, 16, 16, C, generator=g)
+    kern2 = P.f16r(torch.randn(1, 3, 3, C, C, generator=g) / (9 * C) ** 0.5)
+    out_of = lambda a: R.conv_1kk(a.double(), kern2.double(), None)
+    b = {}
+    for op in ('bf16', 'f16'):
+        act = lambda dt: P.operand_rounding(op)(R.silu(y1.to(dt))).double()
+        b[op] = P.tile_bound(act(torch.float32), act(torch.float64), out_of, operand=op)
+    print(f'prologue tile bounds (bound, floor): {b}')
+    assert b['f16'][1] < b['bf16'][1] / 4 and b['f16'][0] < 5e-3 / 8
+    c = AC.sla_case((1, 2, 64, 64, 64), False, 'f16')
+    final = AC.sla_eval(c['x'], c['w'], emulate=True, operand='f16')
+    for n, v in c['views'].items():
+        d, floor = P.view_rels(final, c['cmp'], v).max().item(), P.view_rels(c['emu32'], c['cmp'], v).max().item()
+        print(f'[final-maximum emulation] per {n}: {d:.3e} from the running-maximum emulation, flip floor {floor:.3e}')
+    assert P.view_rels(final, c['cmp'], P.frame_view).max().item() > P.view_rels(c['emu32'], c['cmp'], P.frame_view).max().item()
