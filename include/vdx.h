@@ -489,6 +489,50 @@ int vdx_dpm_sample_loop_masked(vdx_handle* h, const float* params, const void* p
                                const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
                                void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
 
+/* Classifier-free guidance (EXTENSION, parity unpinned: no reference code -- the reference's p_sample_loop drops cond; Ho & Salimans
+ * 2022, with the guidance rescale of Lin et al. 2023, sec. 3.4).  eps2 [2 * batch][per_sample] is the output of ONE forward over 2 * batch
+ * samples: rows [0, batch) conditioned (c), rows [batch, 2 * batch) on the null embedding (n).  out [batch][per_sample]:
+ *   g   = n + (c - n) * cond_scale          three separately rounded fp32 operations, no contraction: bit for bit what
+ *                                           Unet3D.forward_with_cond_scale forms with torch
+ *   out = g                                 rescale == 0 (one kernel)
+ *   out = g * (float)(rescale * std(c) / std(g) + 1 - rescale)          rescale in (0, 1], the standard deviations per sample
+ * For the rescale a statistics pass forms g again with the same three operations and adds sum c, sum c^2, sum g, sum g^2 per sample in
+ * double: a fixed grid whatever per_sample or the device, a fixed quad-to-thread map, a fixed-order tree per workgroup, one partial per
+ * workgroup in scratch, a second kernel that adds the partials in index order (the scheme of vdx_grad_sqnorm: no atomics, the bits of
+ * out depend on the values only).  std^2 = (sum x^2 - (sum x)^2 / per_sample) / (per_sample - 1), the n - 1 cancels in the ratio; where
+ * that of g is <= 0 or anything is not finite the factor is 1.  scratch: vdx_cfg_scratch_doubles(batch) doubles, 8-byte aligned (may be
+ * NULL with rescale == 0); its tail is the cond_mask of the guided loops below.  out may be eps2 itself (the first half is then
+ * overwritten in place) or disjoint from it.  The kernels move float4: per_sample % 4 == 0, eps2 / out 16-byte aligned, rescale in
+ * [0, 1] (checked: VDX_ERR_INVALID). */
+size_t vdx_cfg_scratch_doubles(int batch);
+int vdx_cfg_combine(const float* eps2, float* out, float cond_scale, float rescale, double* scratch, int batch, long per_sample, void* stream);
+
+/* The unmasked loops with classifier-free guidance inside the captured step: vdx_p_sample_loop_dyn, vdx_ddim_sample_loop_dyn and
+ * vdx_dpm_sample_loop with cond [batch, cond_dim] required, plus cond_scale, rescale and cfg_scratch (vdx_cfg_scratch_doubles(batch)
+ * doubles).  `batch` = B counts the videos; img [2B,C,F,H,W], t_dev [2B], eps_buf [2B,F,H,W,out_dim] and the workspace
+ * (vdx_workspace_bytes(h, 2B)) hold 2B samples, hist and thres_buf B.  On entry img[:B] = x_T, t_dev[0..2B) = T-1 or seq[0],
+ * *step_dev = 0; on return img[:B] = x_0.  One step, all of it on `stream` (a chain without parallel branches):
+ *   img[B:] = img[:B]  (device-to-device copy) ; one forward over 2B samples with cond_mask = 0 for rows [0, B), 1 for rows [B, 2B) (the
+ *   null rows never read cond) ; vdx_cfg_combine(eps_buf -> eps_buf[:B]) ; (dynamic threshold) ; the unguided loop's step kernel on the
+ *   first B samples, with its draws ; the unguided loop's advance over all 2B entries of t_dev.
+ * So the result is the bits of the step-by-step loop over Unet3D.forward_with_cond_scale and vdx_p_sample_step / vdx_ddim_step /
+ * vdx_dpm_step when rescale == 0.  Own graph slots; the key holds the bits of cond_scale and rescale, cond and cfg_scratch.  DDIM too
+ * needs C*F*H*W % 4 == 0 here. */
+int vdx_p_sample_loop_guided(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                             uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                             int clip_denoised, float percentile, float* thres_buf, float cond_scale, float rescale, double* cfg_scratch,
+                             void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
+int vdx_ddim_sample_loop_guided(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                                uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                                int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf, float cond_scale,
+                                float rescale, double* cfg_scratch, void* workspace, size_t workspace_bytes, int batch, int use_graph,
+                                void* stream);
+int vdx_dpm_sample_loop_guided(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
+                               uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                               int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
+                               float cond_scale, float rescale, double* cfg_scratch, void* workspace, size_t workspace_bytes, int batch,
+                               int use_graph, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */

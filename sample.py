@@ -5,7 +5,9 @@ Extensions: --mode {bf16,f16,f32}; --random-init (no checkpoint); --timesteps N 
 --dpm-steps S [--dpm-order 1|2] (DPM-Solver++(2M) chain; not together with --ddim-steps);
 --attn-fp8 (bf16 mode: QK^T / PV of the <= 16-token attention blocks on fp8 MFMA operands);
 --context PATH.npy [--context-frames K] [--extend-frames N] [--resample-steps U] (video prediction / extension from given frames);
---clean-context (with --context, for a checkpoint trained with train.py --frame_cond_max: the given frames stay un-noised at every step)."""
+--clean-context (with --context, for a checkpoint trained with train.py --frame_cond_max: the given frames stay un-noised at every step);
+--cond-path FILE.npy [--cond-scale 2.0] [--guidance-rescale 0.0] (classifier-free guidance with ready-made embeddings: the rows of the
+float32 [B, cond_dim] file are the batch; needs a config with use_bert_text_cond; works with --ddim-steps and --dpm-steps)."""
 import argparse
 import logging
 import os
@@ -37,6 +39,10 @@ FLAGS = (   # (flag, kwargs)
     ('--resample-steps', dict(type=int, default=1, help='with --context: RePaint resampling steps per noise level (ancestral chain only)')),
     ('--clean-context', dict(action='store_true', help='with --context: keep the given frames clean at every step (frame-conditioned '
                                                        'checkpoints, train.py --frame_cond_max); not with --resample-steps > 1')),
+    ('--cond-path', dict(type=str, default=None, help='float32 [B, cond_dim] .npy of conditions: one video per row (sets the batch); '
+                                                      'classifier-free guidance, needs a config with use_bert_text_cond')),
+    ('--cond-scale', dict(type=float, default=2.0, help='with --cond-path: guidance scale s in eps(0) + s (eps(c) - eps(0)); 1 = no guidance')),
+    ('--guidance-rescale', dict(type=float, default=0.0, help='with --cond-path: guidance rescale phi in [0, 1] (Lin et al. 2023); 0 = off')),
 )
 
 
@@ -72,6 +78,15 @@ def load_context(path, num_frames, context_frames=None, extend_frames=0):
     return np.ascontiguousarray(v[:, :, :k]), total - k
 
 
+def load_cond(path, cond_dim):
+    """--cond-path: the float32 [B, cond_dim] conditions of the batch."""
+    import numpy as np
+    c = np.load(path)
+    if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] != cond_dim:
+        raise ValueError(f'--cond-path must hold a [B, {cond_dim}] array, got shape {c.shape}')
+    return np.ascontiguousarray(c, dtype=np.float32)
+
+
 def main(argv=None):
     logging.basicConfig(level=logging.INFO, force=True)
     ap = build_parser()
@@ -81,6 +96,10 @@ def main(argv=None):
     if a.dpm_steps is not None and a.ddim_steps is not None:
         ap.error('--dpm-steps and --ddim-steps are two samplers: give one of them')
 
+    if a.cond_path and a.context:
+        ap.error('--cond-path samples from noise: not together with --context')
+    if not 0.0 <= a.guidance_rescale <= 1.0:
+        ap.error(f'--guidance-rescale must be in [0, 1], got {a.guidance_rescale}')
     if a.clean_context and not a.context:
         ap.error('--clean-context needs --context')
     if a.clean_context and a.resample_steps > 1:
@@ -115,7 +134,9 @@ def _run(a, ap, rank, world):
     with open(a.config) as fh:
         cfg = yaml.safe_load(fh)
     logging.info('config %s', a.config)
-    _, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8)
+    if a.cond_path and not cfg['unet'].get('use_bert_text_cond'):
+        ap.error('--cond-path needs a config whose unet.use_bert_text_cond is true (a conditioned network)')
+    unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8)
     if not a.random_init:
         ckpt = pathlib.Path(a.checkpoint_path).resolve()
         gd, _ = load_checkpoint(gd, a.step, str(ckpt), load_ema_params=a.load_ema_params)
@@ -131,6 +152,14 @@ def _run(a, ap, rank, world):
         videos = gd.extend(a.seed, torch.from_numpy(ctx), n_new, context_frames=window_ctx, ddim_steps=a.ddim_steps,
                            resample_steps=a.resample_steps, dpm_steps=a.dpm_steps, dpm_order=a.dpm_order,
                            clean_context=a.clean_context)               # this rank's shard of the global batch
+    elif a.cond_path:
+        import torch
+        try:
+            cond = load_cond(a.cond_path, unet.cond_dim)
+        except ValueError as e:
+            ap.error(str(e))
+        videos = gd.sample(a.seed, cond=torch.from_numpy(cond), cond_scale=a.cond_scale, ddim_steps=a.ddim_steps, dpm_steps=a.dpm_steps,
+                           dpm_order=a.dpm_order, guidance_rescale=a.guidance_rescale)      # this rank's shard of the global batch
     else:
         videos = gd.sample(a.seed, batch_size=a.batch_size, ddim_steps=a.ddim_steps, dpm_steps=a.dpm_steps,
                            dpm_order=a.dpm_order)                       # this rank's shard of the global batch

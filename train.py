@@ -6,7 +6,10 @@ Multi-GPU: `python -m torch.distributed.run --nproc-per-node N train.py --config
 Extensions: --mode {bf16,f32}; --train_num_steps N; --dataset_path P (e.g. synthetic:64); --apply_grad_args (gradient accumulation and
 global-norm clipping as the YAML's trainer section asks; without it both keys are ignored, as in the reference);
 --frame_cond_max K [--frame_cond_uncond_prob P] [--frame_cond_mode random|prefix] (frame-conditioned training, RaMViD: up to K random
-context frames per sample enter the network clean and carry no loss; sample such a model with sample.py --context ... --clean-context)."""
+context frames per sample enter the network clean and carry no loss; sample such a model with sample.py --context ... --clean-context);
+--cond_path P.npy [--null_cond_prob 0.1] (conditional training for classifier-free guidance: row i of the float32 [N, cond_dim] file is
+the condition of video i; every sample's condition is replaced by the null embedding with the given probability; needs a config with
+use_bert_text_cond; sample with sample.py --cond-path)."""
 import argparse
 import logging
 import os
@@ -26,6 +29,8 @@ FLAGS = (
     ('--frame_cond_max', dict(type=int, default=None, help='frame-conditioned training: up to K clean context frames per sample (0 = off)')),
     ('--frame_cond_uncond_prob', dict(type=float, default=None, help='with --frame_cond_max: probability of a sample without context (0.25)')),
     ('--frame_cond_mode', dict(choices=('random', 'prefix'), default=None, help="with --frame_cond_max: any K frames, or the first K")),
+    ('--cond_path', dict(type=str, default=None, help='conditional training: float32 [N, cond_dim] .npy, row i = the condition of video i')),
+    ('--null_cond_prob', dict(type=float, default=None, help='with --cond_path: probability of training a sample on the null embedding (0.1)')),
 )
 
 
@@ -71,6 +76,15 @@ def main(argv=None):
         Trainer.frame_cond_uncond_prob = a.frame_cond_uncond_prob
     if a.frame_cond_mode is not None:
         Trainer.frame_cond_mode = a.frame_cond_mode
+    if a.null_cond_prob is not None and a.cond_path is None:
+        ap.error('--null_cond_prob needs --cond_path')
+    if a.cond_path is not None:
+        if not cfg['unet'].get('use_bert_text_cond'):
+            ap.error('--cond_path needs a config whose unet.use_bert_text_cond is true (a conditioned network)')
+        p = 0.1 if a.null_cond_prob is None else a.null_cond_prob
+        if not 0.0 <= p <= 1.0:
+            ap.error(f'--null_cond_prob must be in [0, 1], got {p}')
+        Trainer.cond_path, Trainer.null_cond_prob = a.cond_path, p
     tc.pop('resume_training_step', None)             # the command-line flag wins, as in the reference
     trainer = Trainer(diffusion_model=gd, folder=tc.pop('folder'), resume_training_step=a.resume_step, rng_seed=seed, **tc)
     trainer.train()

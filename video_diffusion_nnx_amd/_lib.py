@@ -112,3 +112,14 @@ vdx_resblock_tail_rc_head_bf16 = _sig('vdx_resblock_tail_rc_head_bf16', c_int, [
 vdx_final_conv_ex = _sig('vdx_final_conv_ex', c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_long, c_int, c_int, c_void_p])
 vdx_init_conv_ex = _sig('vdx_init_conv_ex', c_int, [c_int] + [c_void_p] * 4 + [c_int] * 8 + [c_void_p])
 vdx_resblock_scale_shift = _sig('vdx_resblock_scale_shift', c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p])
+
+# classifier-free guidance (vdx.h: "Classifier-free guidance"): the combine kernel and the three guided loops
+_u64 = C.c_uint64
+vdx_cfg_scratch_doubles = _sig('vdx_cfg_scratch_doubles', c_size_t, [c_int])
+vdx_cfg_combine = _sig('vdx_cfg_combine', c_int, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_int, c_long, c_void_p])
+vdx_p_sample_loop_guided = _sig('vdx_p_sample_loop_guided', c_int, [c_void_p] * 8 + [c_int, c_int, c_void_p, _u64, c_int, c_float, c_void_p, c_float, c_float,
+                                                                    c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p])
+vdx_ddim_sample_loop_guided = _sig('vdx_ddim_sample_loop_guided', c_int, [c_void_p] * 9 + [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_float,
+                                                                          c_float, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p])
+vdx_dpm_sample_loop_guided = _sig('vdx_dpm_sample_loop_guided', c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p,
+                                                                        c_float, c_float, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p])

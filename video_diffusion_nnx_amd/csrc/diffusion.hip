@@ -566,6 +566,108 @@ __global__ __launch_bounds__(256) void loss_masked_final_kernel(const double* __
     }
 }
 
+// Classifier-free guidance (Ho & Salimans 2022; NO reference code: the reference's p_sample_loop drops cond -- EXTENSION, parity
+// unpinned).  eps2 [2B][per] = the batched forward's output, rows [0, B) conditioned (c), rows [B, 2B) on the null embedding (n):
+//   g = n + (c - n) s          three separately rounded operations: the bits torch forms in Unet3D.forward_with_cond_scale
+// With guidance rescale phi (Lin et al. 2023, sec. 3.4) out = g * (float)(phi std(c) / std(g) + 1 - phi), the standard deviations per
+// sample.  out may be eps2 itself (every thread reads its c and n before it writes g over c), so neither pointer is __restrict__.
+constexpr int kCfgBlocks = 16;                 // workgroups per sample of the statistics pass, whatever per_sample or the device
+
+// (plain operators under contract(off), as ddim_mix: __fmul_rn / __fadd_rn are `x * y` / `x + y` inlined from a header compiled with
+// contraction on, and the pair came out as v_pk_fma_f32)
+__device__ __forceinline__ float cfg_g(float c, float n, float s) {
+#pragma clang fp contract(off)
+    const float d = c - n;
+    const float p = d * s;
+    return n + p;
+}
+
+__device__ __forceinline__ float cfg_scale(float g, float f) {
+#pragma clang fp contract(off)
+    return g * f;
+}
+
+__global__ __launch_bounds__(256) void cfg_combine_kernel(const float* eps2, float* out, float s, const double* __restrict__ factor,
+                                                          int B, long per_sample) {
+    const int b = blockIdx.y;
+    const float f = factor ? (float)factor[b] : 1.0f;
+    const float* c = eps2 + (size_t)b * per_sample;
+    const float* n = eps2 + (size_t)(B + b) * per_sample;
+    float* o = out + (size_t)b * per_sample;
+    const long quads = per_sample / 4;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+        const float4 c4 = *reinterpret_cast<const float4*>(c + 4 * q);
+        const float4 n4 = *reinterpret_cast<const float4*>(n + 4 * q);
+        float4 g = make_float4(cfg_g(c4.x, n4.x, s), cfg_g(c4.y, n4.y, s), cfg_g(c4.z, n4.z, s), cfg_g(c4.w, n4.w, s));
+        if (factor) { g.x = cfg_scale(g.x, f); g.y = cfg_scale(g.y, f); g.z = cfg_scale(g.z, f); g.w = cfg_scale(g.w, f); }
+        *reinterpret_cast<float4*>(o + 4 * q) = g;
+    }
+}
+
+// Statistics of the rescale, pass 1: per sample the sums of c, c^2, g, g^2 in double, g formed again by cfg_g (no stored copy).  Quad q
+// of a sample belongs to thread q mod (kCfgBlocks * 256) of the sample's kCfgBlocks workgroups, a fixed-order tree over the workgroup
+// leaves four partials per workgroup in partial[(b * kCfgBlocks + blockIdx.x) * 4 ..].  No atomics (the scheme of
+// loss_masked_partial_kernel): the bits depend on the values only.
+__global__ __launch_bounds__(256) void cfg_stats_partial_kernel(const float* __restrict__ eps2, float s, double* __restrict__ partial,
+                                                                int B, long per_sample) {
+    __shared__ double red[4][256];
+    const int b = blockIdx.y;
+    const float* c = eps2 + (size_t)b * per_sample;
+    const float* n = eps2 + (size_t)(B + b) * per_sample;
+    const long quads = per_sample / 4;
+    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+        const float4 c4 = *reinterpret_cast<const float4*>(c + 4 * q);
+        const float4 n4 = *reinterpret_cast<const float4*>(n + 4 * q);
+        const float cv[4] = {c4.x, c4.y, c4.z, c4.w}, nv[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double cd = (double)cv[k], gd = (double)cfg_g(cv[k], nv[k], s);
+            a[0] += cd; a[1] += cd * cd; a[2] += gd; a[3] += gd * gd;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = a[k];
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) partial[((size_t)b * kCfgBlocks + blockIdx.x) * 4 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+__device__ __forceinline__ bool cfg_finite(double x) {      // on the bits: the library is built with -fno-honor-nans
+    return ((unsigned long long)__double_as_longlong(x) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
+}
+
+// pass 2, one workgroup, thread b = sample b: the sample's partials added in index order, then factor[b] = phi sqrt(SS_c / SS_g) + 1 - phi
+// with SS_x = sum x^2 - (sum x)^2 / per_sample (the n - 1 of the two variances cancels); 1 when SS_g <= 0 or anything is not finite
+__global__ __launch_bounds__(256) void cfg_stats_final_kernel(const double* __restrict__ partial, double* __restrict__ factor, float phi,
+                                                              int B, long per_sample) {
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        double a[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int i = 0; i < kCfgBlocks; ++i)
+            for (int k = 0; k < 4; ++k) a[k] += partial[((size_t)b * kCfgBlocks + i) * 4 + k];
+        const double cnt = (double)per_sample;
+        const double ss_c = a[1] - a[0] * a[0] / cnt, ss_g = a[3] - a[2] * a[2] / cnt;
+        double f = 1.0;
+        if (cfg_finite(ss_c) && cfg_finite(ss_g) && ss_g > 0.0) {
+            const double r = (double)phi * sqrt(fmax(ss_c, 0.0) / ss_g) + (1.0 - (double)phi);
+            if (cfg_finite(r)) f = r;
+        }
+        factor[b] = f;
+    }
+}
+
+// the constant cond_mask of the guided loops' batched forward: rows [0, B) conditioned (0), rows [B, 2B) on the null embedding (1)
+__global__ void cfg_mask_kernel(unsigned char* mask, int B) {
+    for (int i = threadIdx.x; i < 2 * B; i += blockDim.x) mask[i] = i >= B ? 1 : 0;
+}
+
 __global__ void affine_kernel(const float* __restrict__ x, float* __restrict__ y, long n, float a, float b) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = fmaf(x[i], a, b);
 }
@@ -679,6 +781,34 @@ hipError_t launch_loss_masked(const float* eps_hat, const float* noise, const un
                               long fhw, int l2, hipStream_t st) {
     hipLaunchKernelGGL(loss_masked_partial_kernel, dim3(kLossMaskedBlocks), dim3(256), 0, st, eps_hat, noise, mask, scratch, B, Cc, fhw, l2);
     hipLaunchKernelGGL(loss_masked_final_kernel, dim3(1), dim3(256), 0, st, scratch, out);
+    return hipGetLastError();
+}
+
+// scratch of the guidance kernels, in doubles: partials [B][kCfgBlocks][4] | factor [B] | the guided loops' cond_mask (2B bytes)
+static size_t cfg_factor_offset(int B) { return (size_t)B * kCfgBlocks * 4; }
+static size_t cfg_mask_offset(int B) { return cfg_factor_offset(B) + (size_t)B; }
+size_t cfg_scratch_doubles(int B) { return cfg_mask_offset(B) + ((size_t)2 * B + 7) / 8; }
+unsigned char* cfg_scratch_mask(double* scratch, int B) { return reinterpret_cast<unsigned char*>(scratch + cfg_mask_offset(B)); }
+
+hipError_t launch_cfg_mask(double* scratch, int B, hipStream_t st) {
+    hipLaunchKernelGGL(cfg_mask_kernel, dim3(1), dim3(256), 0, st, cfg_scratch_mask(scratch, B), B);
+    return hipGetLastError();
+}
+
+hipError_t launch_cfg_combine(const float* eps2, float* out, float cond_scale, float rescale, double* scratch, int B, long per_sample,
+                              hipStream_t st) {
+    double* factor = nullptr;
+    if (rescale > 0.f) {
+        factor = scratch + cfg_factor_offset(B);
+        {
+            LaunchScope ls(st, "cfg_stats_partial_kernel", 0.0, 8.0 * B * per_sample, "B%d px%ld", B, per_sample);
+            hipLaunchKernelGGL(cfg_stats_partial_kernel, dim3(kCfgBlocks, B), dim3(256), 0, st, eps2, cond_scale, scratch, B, per_sample);
+        }
+        LaunchScope ls(st, "cfg_stats_final_kernel", 0.0, 0.0, "B%d", B);
+        hipLaunchKernelGGL(cfg_stats_final_kernel, dim3(1), dim3(256), 0, st, scratch, factor, rescale, B, per_sample);
+    }
+    LaunchScope ls(st, "cfg_combine_kernel", 0.0, 12.0 * B * per_sample, "B%d px%ld", B, per_sample);
+    hipLaunchKernelGGL(cfg_combine_kernel, dim3(ew_blocks(per_sample / 4), B), dim3(256), 0, st, eps2, out, cond_scale, factor, B, per_sample);
     return hipGetLastError();
 }
 

@@ -9,8 +9,9 @@
 struct vdx_handle {
     vdx::Model model;
     // every argument a captured sampling step bakes in (full pointers: two workspaces / streams never alias one key)
-    struct GraphKey { const void* p[17]; unsigned long long seed; int i[6]; size_t ws; float f; };
-    // one cached graph per loop kind: 0 = DDPM p_sample_loop, 1 = DDIM, 2 = masked DDPM, 3 = masked DDIM, 4 = DPM-Solver++, 5 = masked DPM-Solver++
+    struct GraphKey { const void* p[18]; unsigned long long seed; int i[6]; size_t ws; float f; unsigned cfg[2]; };
+    // one cached graph per loop kind: 0 = DDPM p_sample_loop, 1 = DDIM, 2 = masked DDPM, 3 = masked DDIM, 4 = DPM-Solver++, 5 = masked DPM-Solver++,
+    // 6 / 7 / 8 = the guided (classifier-free guidance) DDPM / DDIM / DPM-Solver++ loops
     // `last` = the stream the exec was last launched on: replays may still be running when the graph has to go
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key; hipStream_t last = nullptr;
@@ -20,7 +21,7 @@ struct vdx_handle {
             if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
             last = nullptr;
         }
-    } gs[6];
+    } gs[9];
     void drop_graphs() { for (GraphSlot& g : gs) g.drop(); }
     vdx::BwdState bwd;
     vdx::Comm comm;
@@ -904,6 +905,116 @@ int vdx_dpm_sample_loop_masked(vdx_handle* h, const float* params, const void* p
     const vdx::MaskArgs ma = {known, mask, mask_tables, 1, 0ull, nullptr};
     return dpm_loop("dpm_sample_loop_masked", h, params, packed, img, eps_buf, hist, t_dev, step_dev, alphas_cumprod, seq, seq_len, nsteps, cond,
                     clip_denoised, order, tables, timesteps, percentile, thres_buf, &ma, seed, workspace, workspace_bytes, batch, use_graph, stream);
+}
+
+size_t vdx_cfg_scratch_doubles(int batch) { return batch > 0 ? vdx::cfg_scratch_doubles(batch) : 0; }
+
+int vdx_cfg_combine(const float* eps2, float* out, float cond_scale, float rescale, double* scratch, int batch, long per_sample, void* stream) {
+    if (!eps2 || !out || batch < 1 || per_sample < 1) VDX_FAIL(VDX_ERR_INVALID, "cfg_combine: bad argument");
+    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "cfg_combine: per_sample must be a multiple of 4");
+    if ((uintptr_t)eps2 % 16 || (uintptr_t)out % 16) VDX_FAIL(VDX_ERR_INVALID, "cfg_combine: eps2 / out must be 16-byte aligned");
+    if (!(rescale >= 0.f && rescale <= 1.f)) VDX_FAIL(VDX_ERR_INVALID, "cfg_combine: rescale must be in [0, 1]");
+    if (rescale > 0.f && (!scratch || (uintptr_t)scratch % 8)) VDX_FAIL(VDX_ERR_INVALID, "cfg_combine: rescale needs an 8-byte aligned scratch");
+    VDX_HIP(vdx::launch_cfg_combine(eps2, out, cond_scale, rescale, scratch, batch, per_sample, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+// The three guided loops (classifier-free guidance; EXTENSION, parity unpinned: the reference's p_sample_loop drops cond).  kind 0 = the
+// ancestral chain, 1 = DDIM, 2 = DPM-Solver++; graph slot 6 + kind.  img / t_dev / eps_buf / workspace hold 2 * batch samples; the step
+// kernels, the threshold and the result use the first `batch`.
+static int guided_loop(const char* who, int kind, vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist,
+                       int* t_dev, uint64_t* step_dev, const float* tables, int timesteps, const float* alphas_cumprod, const int* seq, int seq_len,
+                       int nsteps, const float* cond, uint64_t seed, int clip_denoised, int order, float percentile, float* thres_buf,
+                       float cond_scale, float rescale, double* cfg_scratch, void* workspace, size_t workspace_bytes, int batch, int use_graph,
+                       void* stream) {
+    char msg[160];
+#define CFG_FAIL(code, text) do { snprintf(msg, sizeof(msg), "%s: %s", who, text); VDX_FAIL(code, msg); } while (0)
+    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !workspace || !cond || !cfg_scratch) CFG_FAIL(VDX_ERR_INVALID, "null argument");
+    if (kind == 0 ? !tables : (!alphas_cumprod || !seq)) CFG_FAIL(VDX_ERR_INVALID, "null argument");
+    if (!h->model.d_ss_layers) CFG_FAIL(VDX_ERR_STATE, "handle was created without a GPU");
+    if (!h->model.cfg.cond_dim) CFG_FAIL(VDX_ERR_INVALID, "the network has no condition (cond_dim == 0)");
+    if (batch < 1) CFG_FAIL(VDX_ERR_INVALID, "batch must be >= 1");
+    if (kind == 0 ? (timesteps < 1 || nsteps < 0 || nsteps > timesteps) : (seq_len < 1 || nsteps < 0 || nsteps > seq_len)) CFG_FAIL(VDX_ERR_INVALID, "nsteps out of range");
+    if (kind == 2 && order != 1 && order != 2) CFG_FAIL(VDX_ERR_INVALID, "order must be 1 or 2");
+    if (kind == 2 && order == 2 && !hist) CFG_FAIL(VDX_ERR_INVALID, "order 2 needs hist");
+    if (!(rescale >= 0.f && rescale <= 1.f)) CFG_FAIL(VDX_ERR_INVALID, "rescale must be in [0, 1]");
+    const bool dyn = percentile > 0.f && clip_denoised;
+    if (dyn && (!thres_buf || !tables || timesteps < 1 || percentile > 1.f)) CFG_FAIL(VDX_ERR_INVALID, "dynamic threshold needs tables, thres_buf and a percentile in (0, 1]");
+    const vdx::Model& m = h->model;
+    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
+    if (per_sample % 4) CFG_FAIL(VDX_ERR_INVALID, "C*F*H*W must be a multiple of 4");
+    if (m.out_dim != m.cfg.channels) CFG_FAIL(VDX_ERR_INVALID, "out_dim must equal channels");
+    if ((uintptr_t)img % 16 || (uintptr_t)eps_buf % 16 || (uintptr_t)hist % 16 || (uintptr_t)cfg_scratch % 8)
+        CFG_FAIL(VDX_ERR_INVALID, "img / eps_buf / hist must be 16-byte and the cfg scratch 8-byte aligned");
+#undef CFG_FAIL
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* sd = reinterpret_cast<unsigned long long*>(step_dev);
+    const unsigned char* cond_mask = vdx::cfg_scratch_mask(cfg_scratch, batch);
+    const size_t half_bytes = (size_t)batch * per_sample * sizeof(float);
+    VDX_HIP(vdx::launch_cfg_mask(cfg_scratch, batch, st));
+    auto step = [&]() -> int {
+        // both halves of the batched forward see the same x_t; the null rows never read cond (time_mlp), so cond stays [batch, cond_dim]
+        hipError_t e = hipMemcpyAsync(img + (size_t)batch * per_sample, img, half_bytes, hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, cond_mask, 0, eps_buf, workspace, workspace_bytes, 2 * batch, st);
+        if (rc != VDX_OK) return rc;
+        e = vdx::launch_cfg_combine(eps_buf, eps_buf, cond_scale, rescale, cfg_scratch, batch, per_sample, st);
+        if (e == hipSuccess && dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
+        const float* th = dyn ? thres_buf : nullptr;
+        if (kind == 0) {
+            vdx::PSampleArgs a;
+            fill_psample(a, img, eps_buf, img, t_dev, tables, timesteps, nullptr, seed, 1, step_dev, th, clip_denoised, m.cfg.channels, per_sample);
+            if (e == hipSuccess) e = vdx::launch_p_sample(a, batch, st);
+            if (e == hipSuccess) e = vdx::launch_advance(t_dev, 2 * batch, sd, st);
+        } else {
+            if (e == hipSuccess && kind == 1) e = vdx::launch_ddim_step(img, eps_buf, img, alphas_cumprod, seq, sd, th, clip_denoised, batch, m.cfg.channels, per_sample, st);
+            if (e == hipSuccess && kind == 2) e = vdx::launch_dpm_step(img, eps_buf, img, hist, alphas_cumprod, seq, sd, th, clip_denoised, order, batch, m.cfg.channels,
+                                                                       per_sample, nullptr, 0, 0ull, st);
+            if (e == hipSuccess) e = vdx::launch_ddim_advance(t_dev, 2 * batch, seq, sd, st);
+        }
+        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        return VDX_OK;
+    };
+    vdx_handle::GraphKey key;
+    memset(&key, 0, sizeof(key));
+    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
+    key.p[6] = kind == 0 ? tables : alphas_cumprod; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = seq;
+    key.p[11] = dyn ? (const void*)thres_buf : nullptr; key.p[15] = (dyn && kind != 0) ? (const void*)tables : nullptr; key.p[16] = hist;
+    key.p[17] = cfg_scratch;
+    key.seed = kind == 0 ? seed : 0ull; key.i[0] = kind == 0 ? timesteps : seq_len; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch;
+    key.i[3] = (dyn && kind != 0) ? timesteps : 0; key.i[5] = kind == 2 ? order : 0;
+    key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
+    memcpy(&key.cfg[0], &cond_scale, sizeof(float)); memcpy(&key.cfg[1], &rescale, sizeof(float));
+    return run_steps(h, 6 + kind, key, nsteps, use_graph, st, step);
+}
+
+int vdx_p_sample_loop_guided(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                             uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                             int clip_denoised, float percentile, float* thres_buf, float cond_scale, float rescale, double* cfg_scratch,
+                             void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    return guided_loop("p_sample_loop_guided", 0, h, params, packed, img, eps_buf, nullptr, t_dev, step_dev, tables, timesteps, nullptr, nullptr, 0,
+                       nsteps, cond, seed, clip_denoised, 0, percentile, thres_buf, cond_scale, rescale, cfg_scratch, workspace, workspace_bytes,
+                       batch, use_graph, stream);
+}
+
+int vdx_ddim_sample_loop_guided(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                                uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                                int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf, float cond_scale,
+                                float rescale, double* cfg_scratch, void* workspace, size_t workspace_bytes, int batch, int use_graph,
+                                void* stream) {
+    return guided_loop("ddim_sample_loop_guided", 1, h, params, packed, img, eps_buf, nullptr, t_dev, step_dev, tables, timesteps, alphas_cumprod, seq,
+                       seq_len, nsteps, cond, 0, clip_denoised, 0, percentile, thres_buf, cond_scale, rescale, cfg_scratch, workspace,
+                       workspace_bytes, batch, use_graph, stream);
+}
+
+int vdx_dpm_sample_loop_guided(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
+                               uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                               int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
+                               float cond_scale, float rescale, double* cfg_scratch, void* workspace, size_t workspace_bytes, int batch,
+                               int use_graph, void* stream) {
+    return guided_loop("dpm_sample_loop_guided", 2, h, params, packed, img, eps_buf, hist, t_dev, step_dev, tables, timesteps, alphas_cumprod, seq,
+                       seq_len, nsteps, cond, 0, clip_denoised, order, percentile, thres_buf, cond_scale, rescale, cfg_scratch, workspace,
+                       workspace_bytes, batch, use_graph, stream);
 }
 
 int vdx_pack_conv_weights_t(int mode, const float* kernel, void* packed, int taps, int cin, int cout, void* stream) {

@@ -209,6 +209,13 @@ hipError_t launch_dyn_thres(const float* x, const float* eps, const int* t, cons
                             long per_sample, hipStream_t st);
 hipError_t launch_loss(const float* eps_hat, const float* noise, double* acc, int B, int Cc, long fhw, int l2, hipStream_t st);
 hipError_t launch_affine(const float* x, float* y, long n, float a, float b, hipStream_t st);
+// classifier-free guidance: out [B][per] = n + (c - n) s from eps2 [2B][per] (rows [0, B) = c, [B, 2B) = n; out may be eps2), times the
+// per-sample rescale factor when rescale > 0 (scratch: cfg_scratch_doubles(B), whose tail holds the guided loops' 2B-byte cond_mask)
+size_t cfg_scratch_doubles(int B);
+unsigned char* cfg_scratch_mask(double* scratch, int B);
+hipError_t launch_cfg_mask(double* scratch, int B, hipStream_t st);
+hipError_t launch_cfg_combine(const float* eps2, float* out, float cond_scale, float rescale, double* scratch, int B, long per_sample,
+                              hipStream_t st);
 // frame-conditioned training (mask [B,C,F,H,W] bytes, nonzero = clean context): masked q_sample, the deterministic (sum, count) of the
 // loss over the mask-0 elements (scratch: loss_masked_scratch_doubles()), and its gradient with the count read from the device
 hipError_t launch_q_sample_masked(const float* x0, const int* t, const float* noise, const unsigned char* mask, float* out, const float* sqrt_ac,

@@ -111,6 +111,14 @@ def check_dpm_args(timesteps: int, dpm_steps, dpm_order=2, ddim_steps=None, resa
         raise ValueError(f'dpm_steps must be in [1, {int(timesteps)}], got {dpm_steps}')
 
 
+def check_guidance_rescale(guidance_rescale) -> float:
+    """The guidance rescale phi of the guided loops (Lin et al. 2023, sec. 3.4) as a float; outside [0, 1] raises ValueError."""
+    phi = float(guidance_rescale)
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f'guidance_rescale must be in [0, 1], got {guidance_rescale}')
+    return phi
+
+
 TABLE_NAMES = (
     'alphas_cumprod', 'sqrt_alphas_cumprod', 'sqrt_one_minus_alphas_cumprod', 'log_one_minus_alphas_cumprod',
     'sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_variance',
@@ -288,13 +296,57 @@ class GaussianDiffusion:
                                   x.shape[0], self.channels, self._per_sample(x), L.stream_ptr()))
         return out
 
-    def p_sample_loop(self, shape, key, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None):
+    def _guided_loop(self, kind, unet, shape, seed, cond, cond_scale, guidance_rescale, use_graph, x_T, seq=None, steps=0, order=2):
+        """The classifier-free-guidance loops (EXTENSION, parity unpinned: the reference's p_sample_loop drops cond): kind 'ddpm' | 'ddim' |
+        'dpm' -> vdx_p_sample_loop_guided / vdx_ddim_sample_loop_guided / vdx_dpm_sample_loop_guided on the current stream.  One forward
+        over 2B samples (conditioned | null embedding), vdx_cfg_combine and the unguided step kernel per step, captured in a hipGraph
+        (use_graph) or run eagerly by the same step function.  Returns x_0 [B,C,F,H,W], still in [-1, 1]."""
+        B, T = shape[0], self.num_timesteps
+        per = int(np.prod(shape[1:]))
+        img = torch.empty((2 * B,) + tuple(shape[1:]), dtype=torch.float32, device=self.device)
+        if x_T is None:
+            L.check(vdx_randn(L.ptr(img), B * per, seed, 0, 0, L.stream_ptr()))          # x_T of the B videos: the first half
+        else:
+            img[:B].copy_(self._dev(x_T))
+        condd = self._dev(cond)
+        assert tuple(condd.shape) == (B, unet.cond_dim), f'cond must be [{B}, {unet.cond_dim}], got {tuple(condd.shape)}'
+        h = unet.handle(self.num_frames, self.image_size)
+        unet.apply_activation_storage(h)
+        ws = unet.workspace(2 * B, self.num_frames, self.image_size)
+        eps = torch.empty(2 * B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=self.device)
+        t_dev = torch.full((2 * B,), T - 1 if seq is None else int(seq[0]), dtype=torch.int32, device=self.device)
+        step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
+        thres = torch.empty(B, dtype=torch.float32, device=self.device) if self.use_dynamic_thres else None
+        perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
+        scratch = torch.empty(L.vdx_cfg_scratch_doubles(B), dtype=torch.float64, device=self.device)
+        tail = (float(cond_scale), float(guidance_rescale), L.ptr(scratch), L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr())
+        if kind == 'ddpm':
+            L.check(L.vdx_p_sample_loop_guided(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(t_dev),
+                                               L.ptr(step_dev), L.ptr(self._ptab), T, T, L.ptr(condd), seed, 1, perc, L.ptr(thres), *tail))
+        elif kind == 'ddim':
+            seq_dev = torch.from_numpy(seq).to(self.device)
+            L.check(L.vdx_ddim_sample_loop_guided(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(t_dev),
+                                                  L.ptr(step_dev), L.ptr(self.alphas_cumprod), L.ptr(seq_dev), steps, steps, L.ptr(condd), 1,
+                                                  L.ptr(self._ptab), T, perc, L.ptr(thres), *tail))
+        else:
+            seq_dev = torch.from_numpy(seq).to(self.device)
+            hist = torch.empty((B,) + tuple(shape[1:]), dtype=torch.float32, device=self.device)
+            L.check(L.vdx_dpm_sample_loop_guided(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(hist),
+                                                 L.ptr(t_dev), L.ptr(step_dev), L.ptr(self.alphas_cumprod), L.ptr(seq_dev), steps, steps,
+                                                 L.ptr(condd), 1, order, L.ptr(self._ptab), T, perc, L.ptr(thres), *tail))
+        return img[:B]
+
+    def p_sample_loop(self, shape, key, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None,
+                      guidance_rescale: float = 0.0):
         """reference :264-320.  As there, the caller's spatial `shape` is replaced by the model's own (Q10).
 
         x_T = Philox(key, draw 0); step k (t = T-1-k) uses draw 1+k.  Returns unnormalize_img(x_0) in [0,1].
-        With cond given and cond_scale != 1 the loop runs step-by-step (two forwards per step, classifier-free
-        guidance) -- an extension: the reference drops cond here.
+        With cond given and cond_scale != 1 the loop is the guided one (classifier-free guidance: one forward over 2B samples per
+        step, inside the captured step like the unguided loop; _guided_loop) -- an EXTENSION, parity unpinned: the reference drops cond
+        here.  guidance_rescale phi in [0, 1] (extension; Lin et al. 2023, sec. 3.4): the guided eps is scaled per sample by
+        phi std(eps(c)) / std(eps_guided) + 1 - phi; 0 = off.
         """
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         B = int(shape[0])
         shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
         seed = int(key) & 0xFFFFFFFFFFFFFFFF
@@ -308,24 +360,19 @@ class GaussianDiffusion:
         keep_storage = unet.act_bf16
         unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
         try:
-            out = self._p_sample_loop_on(st, unet, shape, B, T, seed, cond, cond_scale, use_graph, x_T)
+            out = self._p_sample_loop_on(st, unet, shape, B, T, seed, cond, cond_scale, use_graph, x_T, guidance_rescale)
         finally:
             unet.act_bf16 = keep_storage
         cur.wait_stream(st)
         return out
 
-    def _p_sample_loop_on(self, st, unet, shape, B, T, seed, cond, cond_scale, use_graph, x_T):
+    def _p_sample_loop_on(self, st, unet, shape, B, T, seed, cond, cond_scale, use_graph, x_T, guidance_rescale=0.0):
         with torch.cuda.stream(st):
-            img = self.randn(shape, seed, 0) if x_T is None else self._dev(x_T).clone()
             guided = cond is not None and unet.has_cond and cond_scale != 1
             if guided:
-                for k, i in enumerate(reversed(range(T))):
-                    t = torch.full((B,), i, dtype=torch.int32, device=self.device)
-                    eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
-                    thres = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
-                    L.check(vdx_p_sample_step(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(t), L.ptr(self._ptab), T, 0, seed, 1 + k, 0,
-                                              L.ptr(thres), 1, B, self.channels, self._per_sample(img), L.stream_ptr()))
+                img = self._guided_loop('ddpm', unet, shape, seed, cond, cond_scale, guidance_rescale, use_graph, x_T)
             else:
+                img = self.randn(shape, seed, 0) if x_T is None else self._dev(x_T).clone()
                 condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
                 h = unet.handle(self.num_frames, self.image_size)
                 unet.apply_activation_storage(h)
@@ -342,9 +389,12 @@ class GaussianDiffusion:
             L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
         return out
 
-    def ddim_sample_loop(self, shape, key, steps: int = 100, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None):
+    def ddim_sample_loop(self, shape, key, steps: int = 100, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None,
+                         guidance_rescale: float = 0.0):
         """DDIM sampling with eta = 0 in `steps` network evaluations (EXTENSION, BASELINE.json configs[3]; the reference has ancestral
-        sampling only).  x_T = Philox(key, draw 0), deterministic afterwards.  Returns unnormalize_img(x_0) in [0, 1]."""
+        sampling only).  x_T = Philox(key, draw 0), deterministic afterwards.  Returns unnormalize_img(x_0) in [0, 1].  cond with
+        cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         B = int(shape[0])
         shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
         unet = self.denoise_fn
@@ -357,19 +407,13 @@ class GaussianDiffusion:
         unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
         try:
             with torch.cuda.stream(st):
-                img = self.randn(shape, int(key) & 0xFFFFFFFFFFFFFFFF, 0) if x_T is None else self._dev(x_T).clone()
-                seq = torch.from_numpy(seq_host).to(self.device)
                 guided = cond is not None and unet.has_cond and cond_scale != 1
                 if guided:
-                    step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-                    for k in range(steps):
-                        t = torch.full((B,), int(seq_host[k]), dtype=torch.int32, device=self.device)
-                        eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
-                        step_dev.fill_(k)
-                        thres = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
-                        L.check(vdx_ddim_step(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(self.alphas_cumprod), L.ptr(seq), L.ptr(step_dev), L.ptr(thres), 1,
-                                              B, self.channels, self._per_sample(img), L.stream_ptr()))
+                    img = self._guided_loop('ddim', unet, shape, int(key) & 0xFFFFFFFFFFFFFFFF, cond, cond_scale, guidance_rescale, use_graph, x_T,
+                                            seq=seq_host, steps=int(steps))
                 else:
+                    img = self.randn(shape, int(key) & 0xFFFFFFFFFFFFFFFF, 0) if x_T is None else self._dev(x_T).clone()
+                    seq = torch.from_numpy(seq_host).to(self.device)
                     condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
                     h = unet.handle(self.num_frames, self.image_size)
                     unet.apply_activation_storage(h)
@@ -391,12 +435,13 @@ class GaussianDiffusion:
         return out
 
     def dpm_sample_loop(self, shape, key, steps: int = 20, order: int = 2, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True,
-                        x_T=None):
+                        x_T=None, guidance_rescale: float = 0.0):
         """DPM-Solver++(2M) sampling in `steps` network evaluations (EXTENSION, parity unpinned: no reference code; Lu et al. 2022,
         data-prediction multistep form, the step of vdx.h).  order 2 reaches in 15-25 steps what DDIM (= order 1) needs about 100 for;
         the cost per step is DDIM's plus one history tensor.  x_T = Philox(key, draw 0), deterministic afterwards.  Returns
-        unnormalize_img(x_0) in [0, 1]."""
+        unnormalize_img(x_0) in [0, 1].  cond with cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
         check_dpm_args(self.num_timesteps, steps, order)
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         steps = int(steps)
         B = int(shape[0])
         shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
@@ -410,20 +455,14 @@ class GaussianDiffusion:
         unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
         try:
             with torch.cuda.stream(st):
-                img = self.randn(shape, int(key) & 0xFFFFFFFFFFFFFFFF, 0) if x_T is None else self._dev(x_T).clone()
-                hist = torch.empty_like(img)
-                seq = torch.from_numpy(seq_host).to(self.device)
                 guided = cond is not None and unet.has_cond and cond_scale != 1
                 if guided:
-                    step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-                    for k in range(steps):
-                        t = torch.full((B,), int(seq_host[k]), dtype=torch.int32, device=self.device)
-                        eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
-                        step_dev.fill_(k)
-                        thres = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
-                        L.check(vdx_dpm_step(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(hist), L.ptr(self.alphas_cumprod), L.ptr(seq), L.ptr(step_dev),
-                                             L.ptr(thres), 1, order, B, self.channels, self._per_sample(img), L.stream_ptr()))
+                    img = self._guided_loop('dpm', unet, shape, int(key) & 0xFFFFFFFFFFFFFFFF, cond, cond_scale, guidance_rescale, use_graph, x_T,
+                                            seq=seq_host, steps=steps, order=order)
                 else:
+                    img = self.randn(shape, int(key) & 0xFFFFFFFFFFFFFFFF, 0) if x_T is None else self._dev(x_T).clone()
+                    hist = torch.empty_like(img)
+                    seq = torch.from_numpy(seq_host).to(self.device)
                     condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
                     h = unet.handle(self.num_frames, self.image_size)
                     unet.apply_activation_storage(h)
@@ -445,15 +484,17 @@ class GaussianDiffusion:
         return out
 
     def sample(self, key, cond=None, cond_scale: float = 1.0, batch_size: int = 16, *, ddim_steps: Optional[int] = None,
-               dpm_steps: Optional[int] = None, dpm_order: int = 2, **kw):
+               dpm_steps: Optional[int] = None, dpm_order: int = 2, guidance_rescale: float = 0.0, **kw):
         """reference :323-357.  ddim_steps (extension): sample with an S-step DDIM chain instead of the T-step ancestral one.
         dpm_steps (extension): an S-step DPM-Solver++(2M) chain of order dpm_order (dpm_sample_loop); not together with ddim_steps.
+        guidance_rescale (extension): the rescale phi in [0, 1] of the guided loops (cond given, cond_scale != 1; p_sample_loop).
 
         Data parallel (reference :278-298: the batch is split over the local devices, `P('data')`): inside an initialised
         torch.distributed group of W > 1 ranks, `batch_size` (and `cond`) describe the GLOBAL batch; rank r draws videos
         [r * per, (r + 1) * per), per = batch_size / W, from its own Philox stream shard_key(key, r) and returns ITS shard --
         no data-path collective.  W = 1 uses `key` itself (single-process behaviour unchanged)."""
         check_dpm_args(self.num_timesteps, dpm_steps, dpm_order, ddim_steps)
+        kw['guidance_rescale'] = check_guidance_rescale(guidance_rescale)
         if is_list_str(cond):
             raise NotImplementedError('text -> BERT embedding needs the external video_diffusion_pytorch.text (network fetch); '
                                       'pass a ready [B, 768] tensor instead')

@@ -148,6 +148,14 @@ class Trainer:
     frame_cond_max = 0
     frame_cond_uncond_prob = 0.25
     frame_cond_mode = 'random'
+    # Conditional training for classifier-free guidance (extension: the reference's training never drops the condition).  cond_path: a
+    # .npy float32 file [N, cond_dim] of ready-made embeddings, row i = the condition of video i of the dataset (synthetic:N included);
+    # the dataset then yields (video, cond_row) pairs, so shuffling keeps them together.  null_cond_prob = p > 0 replaces the condition of
+    # every sample with probability p by the network's null embedding (train_step.cond_drop_mask, drawn under train_step.cond_drop_key;
+    # Ho & Salimans use 0.1-0.2).  Without cond_path nothing changes, whatever null_cond_prob is.  Sample such a model with
+    # sample(cond=, cond_scale=) / sample.py --cond-path.  Class attributes for the same reason as the ones above.
+    cond_path = None
+    null_cond_prob = 0.0
 
     def __init__(self, diffusion_model, folder: str, *, rng_seed: int = 0, dataset_path: str, num_frames: int = 16,
                  train_batch_size: int = 4, train_lr: float = 1e-4, train_num_steps: int = 100000,
@@ -190,6 +198,7 @@ class Trainer:
         self.micro_grads = None                                  # second gradient buffer, allocated by the first K > 1 step
         self.last_grad_norm = None                               # device float of the last pre-clip gradient norm
         self.last_frame_mask = None                              # context-frame mask of the last micro-batch (frame_cond_max > 0)
+        self.last_cond_mask = None                               # condition-dropout mask of the last micro-batch (null_cond_prob > 0)
         from .train_step import stage_of_param
         nlev = len(self.unet.dim_mults)
         self.buckets = make_buckets(self.unet.param_table, n, lambda nm: stage_of_param(nm, nlev), stage_of_param('__count__', nlev),
@@ -205,6 +214,11 @@ class Trainer:
             self.ds = MovingMNIST(dataset_path, image_size=(self.image_size, self.image_size), num_frames=diffusion_model.num_frames,
                                   force_num_frames=True)
         assert len(self.ds) > 0, 'Dataset is empty. Check path and format.'
+        if not 0.0 <= float(self.null_cond_prob) <= 1.0:
+            raise ValueError(f'null_cond_prob must be in [0, 1], got {self.null_cond_prob}')
+        if self.cond_path is not None:
+            from .datasets import CondPairs, load_cond_file
+            self.ds = CondPairs(self.ds, load_cond_file(self.cond_path, len(self.ds), self.unet.cond_dim))
         g = torch.Generator().manual_seed(self.rng_seed)
         self.dl = cycle(torch.utils.data.DataLoader(self.ds, batch_size=self.batch_size, shuffle=True, drop_last=True, generator=g))
         # ---- results / checkpoints / logs ----
@@ -276,26 +290,29 @@ class Trainer:
             red.enabled = False
         return red
 
-    def train_step(self, batch: torch.Tensor, step: int, t=None, noise=None, frame_mask=None) -> torch.Tensor:
+    def train_step(self, batch: torch.Tensor, step: int, t=None, noise=None, frame_mask=None, cond=None, cond_mask=None) -> torch.Tensor:
         """One `_pjit_train_step` on this rank's shard of the batch.  Returns the (device) scalar loss of the shard.
         t / noise: optional explicit timesteps / noise of the shard (default: this rank's own Philox draws).  frame_mask: optional
-        explicit context-frame mask of the shard ([F] or [B,F], 1 = clean context; default: drawn when frame_cond_max > 0)."""
+        explicit context-frame mask of the shard ([F] or [B,F], 1 = clean context; default: drawn when frame_cond_max > 0).  cond: the
+        shard's conditions [B, cond_dim] (a conditioned UNet needs them); cond_mask: optional explicit condition-dropout mask [B], 1 = null
+        embedding (default: drawn when null_cond_prob > 0)."""
         from .train_step import run_train_step
-        return run_train_step(self, batch, step, t=t, noise=noise, frame_mask=frame_mask)
+        return run_train_step(self, batch, step, t=t, noise=noise, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask)
 
     @property
     def accum_steps(self) -> int:
         """Micro-batches per optimizer step: gradient_accumulate_every behind apply_grad_args, else 1."""
         return max(1, int(self.gradient_accumulate_every)) if self.apply_grad_args else 1
 
-    def train_step_accum(self, batches, step: int, ts=None, noises=None, frame_masks=None) -> torch.Tensor:
+    def train_step_accum(self, batches, step: int, ts=None, noises=None, frame_masks=None, conds=None, cond_masks=None) -> torch.Tensor:
         """One optimizer step on K = len(batches) shards of this rank: the gradient is the mean over the K micro-batches (and the
         ranks), clipped to max_grad_norm when that is set.  Returns the (device) mean of the K losses; `last_grad_norm` holds the
-        device float of the pre-clip norm when one was computed.  ts / noises / frame_masks: optional per-micro-batch lists, as
-        train_step's."""
+        device float of the pre-clip norm when one was computed.  ts / noises / frame_masks / conds / cond_masks: optional
+        per-micro-batch lists, as train_step's."""
         from .train_step import run_train_step_accum
         assert self.apply_grad_args, 'train_step_accum is the path behind Trainer.apply_grad_args = True'
-        return run_train_step_accum(self, list(batches), step, ts=ts, noises=noises, frame_masks=frame_masks)
+        return run_train_step_accum(self, list(batches), step, ts=ts, noises=noises, frame_masks=frame_masks, conds=conds,
+                                    cond_masks=cond_masks)
 
     def train(self, prob_focus_present: float = 0.0, focus_present_mask=None, log_fn=noop):
         assert callable(log_fn)
@@ -321,7 +338,12 @@ class Trainer:
             traced = self.device.type == 'cuda' and self.step - first_step < max(0, int(self.profile_flush_step))
             if traced:
                 _range(True, f'train_step {self.step}')
-            loss = self.train_step_accum(shard, self.step) if self.apply_grad_args else self.train_step(shard, self.step)
+            if self.cond_path is None:
+                loss = self.train_step_accum(shard, self.step) if self.apply_grad_args else self.train_step(shard, self.step)
+            elif self.apply_grad_args:                           # the prefetcher hands (video, cond) pairs on
+                loss = self.train_step_accum([s[0] for s in shard], self.step, conds=[s[1] for s in shard])
+            else:
+                loss = self.train_step(shard[0], self.step, cond=shard[1])
             if traced:
                 _range(False)
             if self.dist_on and self.world > 1:                  # global mean loss = mean of equal-size shard means (C2)
