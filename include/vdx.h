@@ -166,6 +166,13 @@ int vdx_attention_forward_bf16(const void* x_bf16, void* y_bf16, const void* wqk
                                const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads,
                                int temporal, int fp8_core, void* stream);
 
+/* The attention block with a pre-softmax bias, as the network runs its temporal blocks under vdx_set_temporal_pos_bias: bias is device fp32
+ * [heads][L][L] (L = frames when temporal, else h * w; at most 64), added to q_i . k_j / sqrt(d) before the key mask and the softmax.
+ * io_bf16: x and y hold bf16 (VDX_MODE_BF16 only).  Always the generic fused kernels (BIAS instantiations). */
+int vdx_attention_forward_bias(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                               const void* wo_packed, const float* bo, const float* bias, int batch, int frames, int h, int w, int c,
+                               int heads, int temporal, void* stream);
+
 /* SpatialLinearAttention + residual (reference: modules.py:64-129 inside Residual(PreNorm(..)), unet3d.py:170-178).
  * heads must be 8, head dim 32.  wq/wk/wv_packed: packed [C,256]; wo_packed: packed [256,C].
  * workspace: vdx_sla_workspace_bytes(mode, batch*frames, h*w, heads). */
@@ -291,6 +298,21 @@ int vdx_get_activation_storage(const vdx_handle* h);
  * of the bottleneck) keep bf16 operands.  Tolerance: tests/test_gpu_blocks.py (attention block 4e-2 of the attention branch). */
 int vdx_set_attention_fp8(vdx_handle* h, int on);
 int vdx_get_attention_fp8(const vdx_handle* h);
+
+/* Temporal relative position bias (reference: RelativePositionBias, modules.py:350-390, built by unet3d.py and handed to every temporal
+ * attention block -- where PreNorm drops it; DESIGN.md 9: an extension, parity unpinned).  Off (default): the network is the
+ * reference's, equivariant under permutations of its frames, bit for bit and launch for launch what it was.  On: the ten temporal
+ * attention blocks (init, downs, mid temporal, ups) compute softmax_j(q_i . k_j / sqrt(d) + bias[h][i][j]) v_j with
+ * bias[h][i][j] = embedding[buckets[i * F + j]][h] -- BEFORE the softmax (the T5 / Video Diffusion Models form; the reference's dead code
+ * would add it after).  The mid spatial attention gets none.  `buckets`: HOST int [F * F], values in [0, 32), F = the handle's
+ * num_frames (the map of modules.py:350-390 with its defaults of 32 buckets / max distance 128; the Python package computes it); it is
+ * uploaded here, once, never during a capture; ignored (may be null) when on == 0.  Every cached sampling graph of the handle is dropped.
+ * The embedding is the parameter "time_rel_pos_bias.relative_attention_bias.embedding" of the flat buffer: no new parameter.  With the
+ * switch on the temporal blocks run the generic fused kernels (attention_reg_kernel / attention_kernel, BIAS instantiations) and
+ * vdx_unet_backward the generic attention route, whose cores emit dBias deterministically (fixed grid of slots + ordered sum; the stem
+ * stage scatters it to the embedding's gradient).  VDX_ERR_STATE together with fp8 attention, VDX_ERR_INVALID for more than 64 frames. */
+int vdx_set_temporal_pos_bias(vdx_handle* h, int on, const int* buckets);
+int vdx_get_temporal_pos_bias(const vdx_handle* h);
 
 /* Flat fp32 parameter buffer layout (names = nnx state-tree paths, shapes = Flax shapes). */
 int vdx_param_count(const vdx_handle* h);
@@ -662,6 +684,15 @@ int vdx_norm_act_backward_ex(const float* dact, const void* y, int y_bf16, void*
  * 16 tokens per sequence, is VDX_ERR_INVALID. */
 int vdx_attention_core_backward_io(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, int batch, int frames,
                                    int h, int w, int heads, int temporal, int bf16_operands, void* stream);
+
+/* vdx_attention_core_backward_io with the pre-softmax bias of vdx_attention_forward_bias: logits = q_i . k_j / sqrt(d) + bias[h][i][j]
+ * (bias device fp32 [heads][L][L]); besides o and dqkv it ADDS dBias[h][i][j] = sum over the sequences of dS[h][i][j] into dbias
+ * (fp32 [heads][L][L]; the caller zeroes it).  Deterministic: a fixed grid of workgroups stores per-workgroup sums into `scratch`
+ * (scratch_floats >= vdx_attention_bias_backward_scratch_floats(heads, L)) and a second pass adds them in order -- no float atomics. */
+size_t vdx_attention_bias_backward_scratch_floats(int heads, int tokens);
+int vdx_attention_core_backward_bias(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias,
+                                     float* dbias, float* scratch, size_t scratch_floats, int batch, int frames, int h, int w, int heads,
+                                     int temporal, int bf16_operands, void* stream);
 
 /* vdx_temporal_attention_backward_fused with x_bf16 (model_bwd.hip:219-227 under bf16 activation storage): x holds bf16. */
 int vdx_temporal_attention_backward_fused_ex(const void* x, int x_bf16, const float* dy, const void* packed_wqkv, const float* bqkv,

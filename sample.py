@@ -37,6 +37,8 @@ FLAGS = (   # (flag, kwargs)
     ('--context-frames', dict(type=int, default=None, help='with --context: keep its first K frames (default: all)')),
     ('--extend-frames', dict(type=int, default=0, help='with --context: the videos get num_frames + N frames')),
     ('--resample-steps', dict(type=int, default=1, help='with --context: RePaint resampling steps per noise level (ancestral chain only)')),
+    ('--temporal-pos-bias', dict(action='store_true', help='temporal attention adds the relative position bias before the softmax (frame order; '
+                                                           'also unet.temporal_pos_bias in the YAML; for checkpoints trained with it)')),
     ('--clean-context', dict(action='store_true', help='with --context: keep the given frames clean at every step (frame-conditioned '
                                                        'checkpoints, train.py --frame_cond_max); not with --resample-steps > 1')),
     ('--cond-path', dict(type=str, default=None, help='float32 [B, cond_dim] .npy of conditions: one video per row (sets the batch); '
@@ -46,12 +48,15 @@ FLAGS = (   # (flag, kwargs)
 )
 
 
-def build_models(cfg, mode, timesteps=None, attn_fp8=False):
+def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=False):
+    """temporal_pos_bias: the command-line flag; the YAML's unet.temporal_pos_bias (absent = false) switches it on as well.  An architecture
+    argument like dim: checkpoints do not store it, so a model trained with it is sampled with it."""
     from video_diffusion_nnx_amd.gaussian_diffusion import GaussianDiffusion
     from video_diffusion_nnx_amd.unet3d import Rngs, Unet3D
     u, d = cfg['unet'], cfg['diffusion']
     unet = Unet3D(dim=u['dim'], rngs=Rngs(u['rngs_seed']), dim_mults=tuple(u['dim_mults']), channels=u['channels'],
-                  use_bert_text_cond=u['use_bert_text_cond'], mode=mode, attn_fp8=attn_fp8)
+                  use_bert_text_cond=u['use_bert_text_cond'], mode=mode, attn_fp8=attn_fp8,
+                  temporal_pos_bias=bool(temporal_pos_bias or u.get('temporal_pos_bias', False)))
     gd = GaussianDiffusion(denoise_fn=unet, image_size=d['image_size'], num_frames=d['num_frames'], channels=d['channels'],
                            timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'])
     return unet, gd
@@ -136,7 +141,9 @@ def _run(a, ap, rank, world):
     logging.info('config %s', a.config)
     if a.cond_path and not cfg['unet'].get('use_bert_text_cond'):
         ap.error('--cond-path needs a config whose unet.use_bert_text_cond is true (a conditioned network)')
-    unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8)
+    if a.attn_fp8 and (a.temporal_pos_bias or cfg['unet'].get('temporal_pos_bias')):
+        ap.error('--attn-fp8 and the temporal position bias exclude each other')
+    unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8, temporal_pos_bias=a.temporal_pos_bias)
     if not a.random_init:
         ckpt = pathlib.Path(a.checkpoint_path).resolve()
         gd, _ = load_checkpoint(gd, a.step, str(ckpt), load_ema_params=a.load_ema_params)

@@ -9,7 +9,9 @@ global-norm clipping as the YAML's trainer section asks; without it both keys ar
 context frames per sample enter the network clean and carry no loss; sample such a model with sample.py --context ... --clean-context);
 --cond_path P.npy [--null_cond_prob 0.1] (conditional training for classifier-free guidance: row i of the float32 [N, cond_dim] file is
 the condition of video i; every sample's condition is replaced by the null embedding with the given probability; needs a config with
-use_bert_text_cond; sample with sample.py --cond-path)."""
+use_bert_text_cond; sample with sample.py --cond-path); --temporal_pos_bias (or unet.temporal_pos_bias: true in the YAML: the temporal
+attention blocks add the relative position bias before the softmax, so the network can learn frame order; sample with
+sample.py --temporal-pos-bias or the same YAML key)."""
 import argparse
 import logging
 import os
@@ -29,6 +31,8 @@ FLAGS = (
     ('--frame_cond_max', dict(type=int, default=None, help='frame-conditioned training: up to K clean context frames per sample (0 = off)')),
     ('--frame_cond_uncond_prob', dict(type=float, default=None, help='with --frame_cond_max: probability of a sample without context (0.25)')),
     ('--frame_cond_mode', dict(choices=('random', 'prefix'), default=None, help="with --frame_cond_max: any K frames, or the first K")),
+    ('--temporal_pos_bias', dict(action='store_true', help='temporal attention adds the relative position bias before the softmax: the network '
+                                                           'learns frame order (also unet.temporal_pos_bias in the YAML; not stored in checkpoints)')),
     ('--cond_path', dict(type=str, default=None, help='conditional training: float32 [N, cond_dim] .npy, row i = the condition of video i')),
     ('--null_cond_prob', dict(type=float, default=None, help='with --cond_path: probability of training a sample on the null embedding (0.1)')),
 )
@@ -57,7 +61,8 @@ def main(argv=None):
         cfg = yaml.safe_load(fh)
     seed = a.rng_seed if a.rng_seed is not None else cfg.get('rng_seed', 0)
     logging.info('config %s, master seed %s', a.config, seed)
-    _, gd = build_models(cfg, a.mode)
+    # (the keyword only when the flag is given: callers that replace build_models with a (cfg, mode) function keep working)
+    _, gd = build_models(cfg, a.mode, **(dict(temporal_pos_bias=True) if a.temporal_pos_bias else {}))
     tc = dict(cfg['trainer'])
     if a.train_num_steps is not None:
         tc['train_num_steps'] = a.train_num_steps

@@ -21,7 +21,8 @@
 
 namespace vdx {
 
-template <int MODE, int LP, int TMO>
+// BIAS: P.pos_bias[h][i][j] (fp32, [heads][L][L]) is added to the scaled scores before the key mask and the softmax
+template <int MODE, int LP, int TMO, bool BIAS = false>
 __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs P) {
     using M = Mma<MODE>;
     constexpr int KT = M::KT, KC = M::KC, RS = ROW_STRIDE;
@@ -165,6 +166,17 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs P) {
                     M::mma(s[jt], a, bq);
                 }
             }
+            if constexpr (BIAS) {                             // lane (lp, q) of tile jt: query i = qt * 16 + lp, keys j = jt * 16 + 4q + r
+                const int qi = qt * 16 + lp;
+                const float* brow = P.pos_bias + ((size_t)h * P.L + qi) * P.L;
+#pragma unroll
+                for (int jt = 0; jt < QT; ++jt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int kj = jt * 16 + 4 * q + r;
+                        if (qi < P.L && kj < P.L) s[jt][r] += brow[kj];
+                    }
+            }
             float mx = -1e30f;
 #pragma unroll
             for (int jt = 0; jt < QT; ++jt)
@@ -244,7 +256,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs P) {
 //                                          B = the normalised scores, still in their accumulator registers
 //   y[c,i]   += sum_d Wo[c, h*32+d] O^T[d,i] : B = the O^T accumulator tiles, A = 4-element weight fragments from L2
 // never leave the register file: no q/k/v/P/O round trips through LDS, two workgroup barriers per head (weight tile only).
-template <int MODE, int TMA, bool F8>   // TMA = C / 16 output-channel tiles (all owned by every wave, for its 16 rows); F8: fp8 QK^T / PV
+template <int MODE, int TMA, bool F8, bool BIAS = false>   // TMA = C / 16 output-channel tiles (all owned by every wave, for its 16 rows); F8: fp8 QK^T / PV
 __global__ __launch_bounds__(256) void attention_reg_kernel(const AttnArgs P) {
     using M = Mma<MODE>;
     constexpr int KT = M::KT, RS = ROW_STRIDE;
@@ -358,6 +370,11 @@ __global__ __launch_bounds__(256) void attention_reg_kernel(const AttnArgs P) {
         f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
         core_mma16<M, F8>(s, ak[0], aq[0]);
         core_mma16<M, F8>(s, ak[1], aq[1]);
+        if constexpr (BIAS) {                                 // pos_bias[h][i = lp][j = 4q + r] on the scaled scores, before the key mask
+            const float* brow = P.pos_bias + ((size_t)h * P.L + lp) * P.L;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (lp < P.L && 4 * q + r < P.L) s[r] += brow[4 * q + r];
+        }
         float mx = -1e30f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) { if (4 * q + r >= P.L) s[r] = -1e30f; mx = fmaxf(mx, s[r]); }
@@ -1216,6 +1233,13 @@ static hipError_t launch_attn_reg_t(const AttnArgs& a, hipStream_t st) {
     const size_t lds = 512 + (size_t)(64 + 96) * ROW_STRIDE + (size_t)TMA * 16 * (32 * Mma<MODE>::ES + 16);
     const long blocks = (a.nseq + 3) / 4;
     const AttnWork aw = attn_work(a, Mma<MODE>::ES, true);
+    if (a.pos_bias) {                                  // pre-softmax bias (never together with the fp8 core: vdx_set_temporal_pos_bias)
+        auto kfn = attention_reg_kernel<MODE, TMA, false, true>;
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
+        LaunchScope ls(st, "attention_reg_kernel", aw.flops, aw.bytes, "<%d, %d, bias> C%d L%d nseq%ld io16 %d", MODE, TMA, a.C, a.L, a.nseq, a.io_bf16);
+        hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, st, a);
+        return hipGetLastError();
+    }
     LaunchScope ls(st, "attention_reg_kernel", aw.flops, aw.bytes, "<%d, %d, fp8 %d> C%d L%d nseq%ld io16 %d", MODE, TMA, a.fp8_core, a.C, a.L, a.nseq, a.io_bf16);
     if constexpr (MODE == MODE_BF16) {
         if (a.fp8_core) { hipLaunchKernelGGL((attention_reg_kernel<MODE, TMA, true>), dim3((unsigned)blocks), dim3(256), lds, st, a); return hipGetLastError(); }
@@ -1234,34 +1258,47 @@ static hipError_t launch_attn_reg(const AttnArgs& a, hipStream_t st) {
     return hipErrorInvalidValue;
 }
 
-template <int MODE, int LP, int TMO>
+template <int MODE, int LP, int TMO, bool BIAS = false>
 static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t st) {
     constexpr int KC = Mma<MODE>::KC;
     constexpr int NSEQ = 64 / LP;
     constexpr int NCHL = (LP + KC - 1) / KC;
     constexpr int RSV = NCHL * 64 + 16;
     const size_t lds = 512 + (size_t)(64 * 4 + 96) * ROW_STRIDE + (size_t)(NSEQ * 32 + 64) * RSV;
-    auto kfn = attention_kernel<MODE, LP, TMO>;
+    auto kfn = attention_kernel<MODE, LP, TMO, BIAS>;
     if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const long blocks = (a.nseq + NSEQ - 1) / NSEQ;
     const AttnWork aw = attn_work(a, Mma<MODE>::ES, true);
-    LaunchScope ls(st, "attention_kernel", aw.flops, aw.bytes, "<%d, %d, %d> C%d L%d nseq%ld io16 %d", MODE, LP, TMO, a.C, a.L, a.nseq, a.io_bf16);
+    LaunchScope ls(st, "attention_kernel", aw.flops, aw.bytes, BIAS ? "<%d, %d, %d, bias> C%d L%d nseq%ld io16 %d" : "<%d, %d, %d> C%d L%d nseq%ld io16 %d", MODE, LP, TMO, a.C, a.L, a.nseq, a.io_bf16);
     hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 
-template <int MODE, int LP>
+template <int MODE, int LP, bool BIAS = false>
 static hipError_t launch_attn_l(const AttnArgs& a, hipStream_t st) {
-    if (a.C <= 64) return launch_attn_t<MODE, LP, 1>(a, st);
-    if (a.C <= 128) return launch_attn_t<MODE, LP, 2>(a, st);
-    if (a.C <= 256) return launch_attn_t<MODE, LP, 4>(a, st);
-    if (a.C <= 512) return launch_attn_t<MODE, LP, 8>(a, st);
-    if (a.C <= 1024) return launch_attn_t<MODE, LP, 16>(a, st);
+    if (a.C <= 64) return launch_attn_t<MODE, LP, 1, BIAS>(a, st);
+    if (a.C <= 128) return launch_attn_t<MODE, LP, 2, BIAS>(a, st);
+    if (a.C <= 256) return launch_attn_t<MODE, LP, 4, BIAS>(a, st);
+    if (a.C <= 512) return launch_attn_t<MODE, LP, 8, BIAS>(a, st);
+    if (a.C <= 1024) return launch_attn_t<MODE, LP, 16, BIAS>(a, st);
     return hipErrorInvalidValue;
 }
 
 template <int MODE>
 static hipError_t launch_attn_m(const AttnArgs& a, hipStream_t st) {
+    if (a.pos_bias) {
+        // pre-softmax bias: the generic fused kernels only (the one-wave-per-head / per-group kernels have no bias instantiation yet)
+        if (a.fp8_core) return hipErrorInvalidValue;
+        if (a.L <= 16) {
+            if constexpr (MODE == MODE_F32) {
+                if (a.C > 512) return a.C <= 1024 ? launch_attn_t<MODE, 16, 16, true>(a, st) : hipErrorInvalidValue;
+            }
+            return launch_attn_reg<MODE>(a, st);
+        }
+        if (a.L <= 32) return launch_attn_l<MODE, 32, true>(a, st);
+        if (a.L <= 64) return launch_attn_l<MODE, 64, true>(a, st);
+        return hipErrorInvalidValue;
+    }
     const bool h8_ok = a.L <= 16 && a.heads == 8 && a.inner % 4 == 0 && a.nseq % 4 == 0 && a.nseq < (1L << 31) &&
                        3 * a.inner_stride + 15 * a.tok_stride + a.C < (1L << 31);
     if constexpr (MODE != MODE_F16) {                  // (the one-wave-per-head kernels hard-code the bf16 / f32 register formats)
@@ -1349,6 +1386,25 @@ hipError_t launch_attention_long_core(const float* qkv, float* o, long nseq, int
     if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     LaunchScope ls(st, "attention_long_core_kernel", 4.0 * nseq * L * L * heads * 32, 4.0 * nseq * L * heads * 32 * 4, "L%d nseq%ld heads%d", L, nseq, heads);
     hipLaunchKernelGGL(kfn, dim3((unsigned)nseq, heads), dim3(256), lds, st, qkv, o, L, heads, scale);
+    return hipGetLastError();
+}
+
+// ---- relative position bias of the temporal attention blocks (vdx_set_temporal_pos_bias) ----
+// table[h][i][j] = emb[buckets[i][j]][h]: one thread per element; runs at the top of every forward (the embedding is a trained parameter)
+__global__ __launch_bounds__(256) void pos_bias_table_kernel(const float* __restrict__ emb, const int* __restrict__ buckets, float* __restrict__ table,
+                                                             int heads, int nn) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= heads * nn) return;
+    const int h = i / nn, ij = i - h * nn;
+    const int b = min(max(buckets[ij], 0), 31);
+    table[i] = emb[b * heads + h];
+}
+
+hipError_t launch_pos_bias_table(const float* emb, const int* buckets, float* table, int heads, int n, hipStream_t st) {
+    if (!emb || !buckets || !table || heads < 1 || n < 1 || n > 64) return hipErrorInvalidValue;
+    const int total = heads * n * n;
+    LaunchScope ls(st, "pos_bias_table_kernel", 0.0, 8.0 * total, "heads%d n%d", heads, n);
+    hipLaunchKernelGGL(pos_bias_table_kernel, dim3((total + 255) / 256), dim3(256), 0, st, emb, buckets, table, heads, n * n);
     return hipGetLastError();
 }
 

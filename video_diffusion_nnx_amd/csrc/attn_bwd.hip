@@ -11,18 +11,17 @@ namespace vdx {
 
 // one workgroup = one (sequence, head) of L <= 64 tokens (blockIdx.y = head).  qkv [npix][3*HD] (+bias, q unscaled), dO [npix][HD]
 // -> O, dq, dk, dv [npix][HD] each.  Token t of sequence s is pixel row (s / inner) * outer_p + (s % inner) + t * tok_p.
-__global__ __launch_bounds__(256) void attn_core_bwd_kernel(AttnBwdArgs P) {
-    extern __shared__ float sm[];
+// BIAS: the scores get P.bias[h][a][b] before the softmax, and the thread adds the dS elements it owns (i = tid + 256 u) into dacc[u]
+template <bool BIAS>
+__device__ __forceinline__ void attn_core_bwd_seq(const AttnBwdArgs& P, float* sm, const long s, const int h, float (&dacc)[16]) {
     const int L = P.L, LD = 33, LP1 = L + 1;
     float* q = sm; float* k = q + L * LD; float* v = k + L * LD; float* dO = v + L * LD;
     float* Pm = dO + L * LD;                 // [L][L+1]
     float* dS = Pm + L * LP1;                // [L][L+1]
     const int tid = threadIdx.x;
-    const long s = blockIdx.x;
     const long row0 = (s / P.inner) * P.outer_p + (s % P.inner);
     const int HD = P.heads * 32;
     {
-        const int h = blockIdx.y;
         for (int i = tid; i < L * 32; i += 256) {
             const int t = i >> 5, d = i & 31;
             const size_t row = (size_t)(row0 + (long)t * P.tok_p);
@@ -36,6 +35,7 @@ __global__ __launch_bounds__(256) void attn_core_bwd_kernel(AttnBwdArgs P) {
             float acc = 0.f, acc2 = 0.f;
 #pragma unroll 8
             for (int d = 0; d < 32; ++d) { acc = fmaf(q[a * LD + d], k[b * LD + d], acc); acc2 = fmaf(dO[a * LD + d], v[b * LD + d], acc2); }
+            if constexpr (BIAS) acc += P.bias[((size_t)h * L + a) * L + b];
             Pm[a * LP1 + b] = acc; dS[a * LP1 + b] = acc2;           // scores, dP
         }
         __syncthreads();
@@ -50,6 +50,13 @@ __global__ __launch_bounds__(256) void attn_core_bwd_kernel(AttnBwdArgs P) {
             for (int j = 0; j < L; ++j) dS[tid * LP1 + j] = Pm[tid * LP1 + j] * (dS[tid * LP1 + j] - dr);
         }
         __syncthreads();
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const int i = tid + 256 * u;
+                if (i < L * L) { const int a = i / L, b = i - a * L; dacc[u] += dS[a * LP1 + b]; }
+            }
+        }
         for (int i = tid; i < L * 32; i += 256) {
             const int t = i >> 5, d = i & 31;
             float o = 0.f, dq = 0.f, dk = 0.f, dv = 0.f;
@@ -64,6 +71,43 @@ __global__ __launch_bounds__(256) void attn_core_bwd_kernel(AttnBwdArgs P) {
             P.O[o_] = o; P.dq[g_] = dq * P.scale; P.dk[g_] = dk; P.dv[g_] = dv;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void attn_core_bwd_kernel(AttnBwdArgs P) {
+    extern __shared__ float sm[];
+    float none[16];
+    attn_core_bwd_seq<false>(P, sm, blockIdx.x, blockIdx.y, none);
+}
+
+// Bias form: a FIXED grid (gridDim.x slots, blockIdx.y = head); workgroup x walks the sequences x, x + gridDim.x, ... in order and stores
+// the sum of their dS into its own slot P.part[x][h][L][L] -- no atomics, so dBias is bit-reproducible (second pass: attn_dbias_sum_kernel)
+__global__ __launch_bounds__(256) void attn_core_bwd_bias_kernel(AttnBwdArgs P) {
+    extern __shared__ float sm[];
+    const int L = P.L, h = blockIdx.y, tid = threadIdx.x;
+    float dacc[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) dacc[u] = 0.f;
+    for (long s = blockIdx.x; s < P.nseq; s += gridDim.x) {
+        __syncthreads();                                     // the previous sequence's readers of the LDS tiles are done
+        attn_core_bwd_seq<true>(P, sm, s, h, dacc);
+    }
+    float* slot = P.part + ((size_t)blockIdx.x * P.heads + h) * L * L;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        const int i = tid + 256 * u;
+        if (i < L * L) slot[i] = dacc[u];
+    }
+}
+
+// dbias[e] += part[0][e] + part[1][e] + ... (in slot order), e over [heads][L][L]; slots are [heads][LS][LS] with LS >= L
+__global__ __launch_bounds__(256) void attn_dbias_sum_kernel(const float* __restrict__ part, int nslots, int heads, int L, int LS, float* __restrict__ dbias) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= heads * L * L) return;
+    const int h = e / (L * L), ij = e - h * L * L, i = ij / L, j = ij - i * L;
+    const size_t stride = (size_t)heads * LS * LS, off = ((size_t)h * LS + i) * LS + j;
+    float acc = 0.f;
+    for (int k = 0; k < nslots; ++k) acc += part[k * stride + off];
+    dbias[e] += acc;
 }
 
 // ---- bf16-mode form for sequences of <= 16 tokens: one wave per sequence, loop over heads, everything on MFMA ----------
@@ -83,15 +127,15 @@ __device__ __forceinline__ s16x4b pack4_bf16(const f32x4& v) {
     return __builtin_bit_cast(s16x4b, u);
 }
 
-template <bool IO16>
-__global__ __launch_bounds__(256) void attn_core_bwd16_kernel(AttnBwdArgs P) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];      // [4 waves][4 images][16][AB_RS]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+// The work of one wave on sequence s, heads [h0, h1).  BIAS: logits = scale q.k + P.bias[h][a][b] (the scale can no longer ride in the
+// exponent: it is applied to the scores, and the exponent's factor is log2 e alone), and dacc += dS^T of a live wave: lane (a = lp, q) holds
+// dBias[h][a][4q + e].  P comes by value: through a reference to the kernel argument the unbiased instantiations took 4 VGPRs more
+template <bool IO16, bool BIAS>
+__device__ __forceinline__ void attn_core_bwd16_seq(const AttnBwdArgs P, char* img, const long s, const int h0, const int h1, f32x4& dacc) {
+    const int lane = threadIdx.x & 63;
     const int lp = lane & 15, q = lane >> 4;
-    char* img = smem + w * (4 * 16 * AB_RS);
     char* Qi = img; char* Ki = Qi + 16 * AB_RS; char* Vi = Ki + 16 * AB_RS; char* Di = Vi + 16 * AB_RS;
     const int HD = P.heads * 32;
-    const long s = (long)blockIdx.x * 4 + w;
     const bool live = s < P.nseq;                            // a dead wave still runs (EXEC must stay full for the tr reads): it
     const long sc = live ? s : 0;                            // recomputes sequence 0 and stores nothing
     const long row0 = (sc / P.inner) * P.outer_p + (sc % P.inner);
@@ -103,8 +147,8 @@ __global__ __launch_bounds__(256) void attn_core_bwd16_kernel(AttnBwdArgs P) {
     const int troff = (4 * q + (lp >> 2)) * AB_RS + (lp & 3) * 8;
     const size_t orow = (size_t)(row0 + (long)lp * P.tok_p);          // output: lane (token lp, q) writes channels 4q..4q+3 (+16)
     const bool ovalid = live && lp < P.L;
-    const float SL2E = P.scale * 1.44269504088896f;           // softmax(scale * s) = exp2((s - max s) * scale * log2 e) / sum
-    for (int h = 0; h < P.heads; ++h) {
+    const float SL2E = (BIAS ? 1.0f : P.scale) * 1.44269504088896f;   // softmax(scale * s) = exp2((s - max s) * scale * log2 e) / sum
+    for (int h = h0; h < h1; ++h) {
         // ---- stage the four images (wave-private: LDS ops of one wave stay in order).  q stays UNSCALED here: 1/sqrt(d) is folded
         //      into the exponent of both softmaxes and into the dq / dk outputs ----
 #pragma unroll
@@ -144,6 +188,16 @@ __global__ __launch_bounds__(256) void attn_core_bwd16_kernel(AttnBwdArgs P) {
         f32x4 S = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf, kf, z, 0, 0, 0);     // lane (b = lp, q): queries a = 4q+e
         f32x4 dPT = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, df, z, 0, 0, 0);   // dP^T[b][a]
         f32x4 dP = __builtin_amdgcn_mfma_f32_16x16x32_bf16(df, vf, z, 0, 0, 0);    // dP[a][b]
+        if constexpr (BIAS) {
+            const float* bh = P.bias + (size_t)h * P.L * P.L;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int r4 = 4 * q + e;
+                const bool in = lp < P.L && r4 < P.L;
+                ST[e] = fmaf(ST[e], P.scale, in ? bh[lp * P.L + r4] : 0.f);       // query lp, key 4q + e
+                S[e] = fmaf(S[e], P.scale, in ? bh[r4 * P.L + lp] : 0.f);         // query 4q + e, key lp
+            }
+        }
         // ---- orientation "T": query a = lp, its keys in (q, e) ----
         f32x4 PT, dST;
         {
@@ -162,6 +216,7 @@ __global__ __launch_bounds__(256) void attn_core_bwd16_kernel(AttnBwdArgs P) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) dST[e] = PT[e] * (dPT[e] - dr);
         }
+        if constexpr (BIAS) { if (live) dacc += dST; }
         // ---- orientation "N": key b = lp, queries a = 4q+e: the row reductions run over the 16 lanes of a DPP row ----
         f32x4 Pn, dSn;
 #pragma unroll
@@ -194,6 +249,37 @@ __global__ __launch_bounds__(256) void attn_core_bwd16_kernel(AttnBwdArgs P) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");        // images are rewritten for the next head
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+template <bool IO16>
+__global__ __launch_bounds__(256) void attn_core_bwd16_kernel(AttnBwdArgs P) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // [4 waves][4 images][16][AB_RS]
+    const int w = threadIdx.x >> 6;
+    f32x4 none;
+    attn_core_bwd16_seq<IO16, false>(P, smem + w * (4 * 16 * AB_RS), (long)blockIdx.x * 4 + w, 0, P.heads, none);
+}
+
+// Bias form: a FIXED grid (gridDim.x slots, blockIdx.y = head); workgroup x walks the groups of 4 sequences x, x + gridDim.x, ... in order
+// (a wave-uniform and workgroup-uniform trip count: dead waves of the last group run and add nothing), its 4 waves' sums meet in LDS in wave
+// order, and the workgroup stores P.part[x][h][16][16]
+template <bool IO16>
+__global__ __launch_bounds__(256) void attn_core_bwd16_bias_kernel(AttnBwdArgs P) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // [4 waves][4 images][16][AB_RS]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int h = blockIdx.y;
+    char* img = smem + w * (4 * 16 * AB_RS);
+    f32x4 dacc = f32x4{0.f, 0.f, 0.f, 0.f};
+    const long ngroups = (P.nseq + 3) / 4;
+    for (long g = blockIdx.x; g < ngroups; g += gridDim.x) attn_core_bwd16_seq<IO16, true>(P, img, g * 4 + w, h, h + 1, dacc);
+    *reinterpret_cast<f32x4*>(img + lane * 16) = dacc;               // the wave's own image region: its last reads are behind the fence above
+    __syncthreads();
+    if (w == 0) {
+        f32x4 t = dacc;
+#pragma unroll
+        for (int k = 1; k < 4; ++k) t += *reinterpret_cast<const f32x4*>(smem + k * (4 * 16 * AB_RS) + lane * 16);
+        const int lp = lane & 15, q = lane >> 4;
+        *reinterpret_cast<f32x4*>(P.part + (((size_t)blockIdx.x * P.heads + h) * 16 + lp) * 16 + 4 * q) = t;
     }
 }
 
@@ -768,7 +854,52 @@ __global__ __launch_bounds__(256) void sla_bwd_b16_kernel(SlaBwdArgs P) {
     }
 }
 
+constexpr int ATTN_BIAS_SLOTS = 128;       // workgroups per head of the bias forms = slots of the deterministic dBias sum (fixed: not a device property)
+size_t attn_bwd_bias_scratch_floats(int heads, int L) { const size_t ls = L <= 16 ? 16 : L; return (size_t)ATTN_BIAS_SLOTS * heads * ls * ls; }
+
+static hipError_t launch_attn_core_bwd_bias(const AttnBwdArgs& a, hipStream_t st) {
+    if (!a.dbias || !a.part || a.L < 1 || a.L > 64 || a.nseq < 1 || a.part_cap < attn_bwd_bias_scratch_floats(a.heads, a.L)) return hipErrorInvalidValue;
+    int slots, LS;
+    if (a.bf16_mma && a.L <= 16) {
+        slots = (int)std::min<long>((a.nseq + 3) / 4, ATTN_BIAS_SLOTS); LS = 16;
+        LaunchScope ls(st, "attn_core_bwd16_bias_kernel", 0.0, 0.0, "<io16 %d> L%d nseq%ld heads%d", a.io_bf16, a.L, a.nseq, a.heads);
+        if (a.io_bf16) hipLaunchKernelGGL(attn_core_bwd16_bias_kernel<true>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
+        else hipLaunchKernelGGL(attn_core_bwd16_bias_kernel<false>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
+    } else {
+        if (a.io_bf16) return hipErrorInvalidValue;
+        slots = (int)std::min<long>(a.nseq, ATTN_BIAS_SLOTS); LS = a.L;
+        const size_t lds = ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
+        auto kfn = attn_core_bwd_bias_kernel;
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
+        LaunchScope ls(st, "attn_core_bwd_bias_kernel", 0.0, 0.0, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads);
+        hipLaunchKernelGGL(kfn, dim3(slots, a.heads), dim3(256), lds, st, a);
+    }
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    const int total = a.heads * a.L * a.L;
+    LaunchScope ls(st, "attn_dbias_sum_kernel", 0.0, 0.0, "slots%d heads%d L%d", slots, a.heads, a.L);
+    hipLaunchKernelGGL(attn_dbias_sum_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a.part, slots, a.heads, a.L, LS, a.dbias);
+    return hipGetLastError();
+}
+
+// demb[b][h] = sum of dbias[h][i][j] over the (i, j) of bucket b, in (i, j) order: one thread per (b, h)
+__global__ __launch_bounds__(256) void pos_bias_scatter_kernel(const float* __restrict__ dbias, const int* __restrict__ buckets, float* __restrict__ demb, int heads, int nn) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= 32 * heads) return;
+    const int b = t / heads, h = t - b * heads;
+    float acc = 0.f;
+    for (int ij = 0; ij < nn; ++ij) if (buckets[ij] == b) acc += dbias[(size_t)h * nn + ij];
+    demb[t] = acc;
+}
+
+hipError_t launch_pos_bias_scatter(const float* dbias, const int* buckets, float* demb, int heads, int n, hipStream_t st) {
+    if (!dbias || !buckets || !demb || heads < 1 || n < 1) return hipErrorInvalidValue;
+    LaunchScope ls(st, "pos_bias_scatter_kernel", 0.0, 0.0, "heads%d n%d", heads, n);
+    hipLaunchKernelGGL(pos_bias_scatter_kernel, dim3((32 * heads + 255) / 256), dim3(256), 0, st, dbias, buckets, demb, heads, n * n);
+    return hipGetLastError();
+}
+
 hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st) {
+    if (a.bias) return launch_attn_core_bwd_bias(a, st);
     if (a.bf16_mma && a.L <= 16) {
         const long blocks = (a.nseq + 3) / 4;
         if (a.io_bf16) hipLaunchKernelGGL(attn_core_bwd16_kernel<true>, dim3((unsigned)blocks), dim3(256), 4 * 4 * 16 * AB_RS, st, a);

@@ -33,6 +33,10 @@ struct Model {
     vdx_config cfg;
     int mode, init_dim, out_dim, time_dim, temb_dim;
     int attn_fp8 = 0;                    // bf16 mode only: QK^T / PV of the <= 16-token attention cores on fp8 operands (forward only)
+    // pre-softmax relative position bias of the temporal attention blocks (vdx_set_temporal_pos_bias).  The three small device buffers belong
+    // to the handle (not to the workspace: its size and the slot table do not depend on the switch): the host's bucket map [F][F], the bias
+    // table [heads][F][F] every forward rebuilds from the embedding, and the backward's accumulator of dL/d(table)
+    int pos_bias = 0; int* d_pos_buckets = nullptr; float* d_pos_table = nullptr; float* d_pos_dbias = nullptr;
     int act16 = 0;                       // bf16 mode only: store every inter-kernel activation as bf16.  1 = inference (every fusion on); 2 = training forward
                                          // (every slot vdx_unet_backward reads is materialised: the 1x1 res_conv output is not folded into the block tail)
     std::vector<ParamInfo> params; long param_total = 0;

@@ -447,7 +447,8 @@ hipError_t attention_block_forward(int mode, AttnArgs a, bool temporal, int NF, 
         return conv1x1(o, HD, 0, a.wo, a.bo, a.y, a.C, a.io_bf16, a.x, a.io_bf16);
     }
     // wide levels in bf16 mode: per-head kernel (weights resident in LDS) + the out-projection as a 1x1 conv
-    if (mode == MODE_BF16 && (temporal ? a.L <= 16 : a.L <= 64) && a.heads == 8 && a.C >= 256 && a.C % 128 == 0 &&
+    // (a pre-softmax bias is served by the generic fused kernels only: launch_attention)
+    if (mode == MODE_BF16 && !a.pos_bias && (temporal ? a.L <= 16 : a.L <= 64) && a.heads == 8 && a.C >= 256 && a.C % 128 == 0 &&
         (size_t)96 * (a.C * 2 + 32) <= 160 * 1024 && scratch && rows * a.heads * 64 <= scratch_bytes) {
         if (require != ATTN_ANY && require != ATTN_HEADS) return hipErrorInvalidValue;
         a.oscratch = scratch;
@@ -471,6 +472,7 @@ static hipError_t run_attn(const Fwd& f, const AttnP& ap, const float* x, float*
     else { a.L = (int)hw; a.nseq = f.B * Fr; a.inner = 1; a.inner_stride = 0; a.outer_stride = hw * ap.C; a.tok_stride = ap.C; }
     a.io_bf16 = f.a16;
     a.fp8_core = (m->attn_fp8 && m->mode == MODE_BF16) ? 1 : 0;
+    if (temporal && m->pos_bias) a.pos_bias = m->d_pos_table;  // the mid spatial attention gets none (the reference passes pos_bias to temporal blocks only)
     return attention_block_forward(m->mode, a, temporal, f.B * (int)Fr, (int)Fr, (int)S, (int)S, f.sla_ws, m->sla_ws_bytes_per_sample * f.B, ATTN_ANY, f.st);
 }
 
@@ -545,6 +547,12 @@ int model_forward(const Model* m, const float* params, const void* packed, const
         VDX_E(hipMemsetAsync(f.stats, 0, stats_bytes, st));
     }
     const int S0 = c.image_size, Fr = c.num_frames;
+    // relative position bias table of the temporal attention blocks, from the embedding as it is in `params` now (vdx_set_temporal_pos_bias)
+    if (m->pos_bias) {
+        if (!m->d_pos_buckets || !m->d_pos_table) return vdx_set_error(VDX_ERR_STATE, "forward: temporal position bias is on without its bucket map", __FILE__, __LINE__);
+        if (m->attn_fp8) return vdx_set_error(VDX_ERR_STATE, "forward: temporal position bias and fp8 attention exclude each other", __FILE__, __LINE__);
+        VDX_E(launch_pos_bias_table(params + m->rel_pos_emb, m->d_pos_buckets, m->d_pos_table, c.attn_heads, Fr, st));
+    }
     // time embedding + every ResnetBlock's (scale, shift)   (unet3d.py:288-298, modules.py:233-238)
     {
         TimeMlpArgs t;

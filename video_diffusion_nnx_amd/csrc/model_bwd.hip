@@ -216,7 +216,8 @@ void attn_bwd(Bwd& b, const AttnP& ap, const float* g, const float* x, int lvl, 
     const long hw = (long)b.size(lvl) * b.size(lvl), Fr = m->cfg.num_frames;
     const int io16 = (m->mode == MODE_BF16 && (temporal ? Fr : hw) <= 16) ? 1 : 0;
     b.writes(b.S);                                                 // the scratch is rewritten from here on
-    if (m->mode == MODE_BF16 && temporal && C == 64 && H == 8 && Fr <= 16) {
+    const bool biased = temporal && m->pos_bias;                   // pre-softmax position bias: the generic route, whose cores have a bias form
+    if (m->mode == MODE_BF16 && temporal && C == 64 && H == 8 && Fr <= 16 && !biased) {
         // widest level: one fused kernel (attn_bwd16x_kernel) instead of recompute / dO projection / core / dx projection
         AttnBwdXArgs f;
         memset(&f, 0, sizeof(f));
@@ -240,6 +241,8 @@ void attn_bwd(Bwd& b, const AttnP& ap, const float* g, const float* x, int lvl, 
     if (temporal) { a.L = (int)Fr; a.nseq = b.B * hw; a.inner = hw; a.outer_p = Fr * hw; a.tok_p = hw; }
     else { a.L = (int)hw; a.nseq = b.B * Fr; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
     a.bf16_mma = (m->mode == MODE_BF16);
+    // the ten temporal blocks add into ONE accumulator, in the order of the reverse walk (main stream); the stem scatters it to the embedding
+    if (biased) { a.bias = m->d_pos_table; a.dbias = m->d_pos_dbias; a.part = b.part_main; a.part_cap = WG_PART_FLOATS; }
     b.ok(launch_attn_core_bwd(a, b.writes(b.S)));
     wgrad1x1(b, O, HD, g, C, ap.o_w, ap.o_b, lvl, io16);
     wgrad1x1_qkv(b, x, C, dq, HD, ap.w, ap.b, lvl, io16, b.a16);
@@ -340,6 +343,11 @@ int model_backward(const Model* m, BwdState* state, const float* params, const v
         if (sb * sb > 64 || c.num_frames > 64)
             return vdx_set_error(VDX_ERR_INVALID, "backward: attention over more than 64 tokens (frames larger than 64 x 64, or more than 64 frames) is forward-only", __FILE__, __LINE__);
     }
+    if (m->pos_bias && (!m->d_pos_buckets || !m->d_pos_table || !m->d_pos_dbias))
+        return vdx_set_error(VDX_ERR_STATE, "backward: temporal position bias is on without its buffers", __FILE__, __LINE__);
+    if (m->pos_bias && attn_bwd_bias_scratch_floats(c.attn_heads, c.num_frames) > WG_PART_FLOATS)
+        return vdx_set_error(VDX_ERR_INVALID, "backward: the dBias slots of the temporal position bias (128 x heads x frames^2 floats) do not fit the "
+                             "weight-gradient scratch: fewer heads or frames, or train with the switch off", __FILE__, __LINE__);
     if (stage_hi != top && state->next_stage != stage_hi) return vdx_set_error(VDX_ERR_STATE, "backward: stages must be run in descending order from the head", __FILE__, __LINE__);
     Bwd b;
     b.m = m; b.p = params; b.pk = reinterpret_cast<const char*>(packed); b.pt = reinterpret_cast<const char*>(packed_t);
@@ -387,6 +395,7 @@ int model_backward(const Model* m, BwdState* state, const float* params, const v
             VDX_E(hipMemsetAsync(grads, 0, (size_t)m->param_total * 4, st));
             VDX_E(hipMemsetAsync(b.dss, 0, (size_t)m->ss_floats_per_sample * B * 4, st));
             VDX_E(hipMemsetAsync(b.dtemb, 0, (size_t)m->temb_dim * B * 4, st));
+            if (m->pos_bias) VDX_E(hipMemsetAsync(m->d_pos_dbias, 0, (size_t)c.attn_heads * c.num_frames * c.num_frames * 4, st));
             // head: out = conv1x1(fin(concat(x_up, r)))
             const Level& U = m->ups[nl - 1];
             VDX_E(launch_final_conv_bwd(b.slot(m->fin.s_out), d_out, params + m->fin_w, b.lv[0].ga, grads + m->fin_w, grads + m->fin_b, pix0, c.dim, m->out_dim, b.a16, b.writes(b.lv[0].ga), b.part_main, WG_PART_FLOATS));
@@ -462,6 +471,8 @@ int model_backward(const Model* m, BwdState* state, const float* params, const v
             b.side_done(b.dtemb);
             float* o = other(LB, g);
             attn_bwd(b, m->init_attn, g, b.slot(m->s_init), 0, true, o); g = o;
+            // the last of the ten temporal blocks has added its dBias: the embedding's gradient is final here, in the stage that owns it
+            if (m->pos_bias) VDX_E(launch_pos_bias_scatter(m->d_pos_dbias, m->d_pos_buckets, grads + m->rel_pos_emb, c.attn_heads, c.num_frames, b.writes(nullptr)));
             VDX_E(launch_init_conv_wgrad(x, g, grads + m->init_w, grads + m->init_b, B, c.channels, c.num_frames, c.image_size, c.image_size,
                                          m->init_dim, c.init_kernel_size, b.writes(nullptr), b.part_main, WG_PART_FLOATS));
         }

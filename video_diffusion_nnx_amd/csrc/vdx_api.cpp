@@ -76,6 +76,9 @@ static int run_steps(vdx_handle* h, int which, const vdx_handle::GraphKey& key, 
 
 extern "C" {
 
+static void fill_attn_geometry(vdx::AttnArgs& a, int batch, int frames, int h, int w, int c, int temporal);
+static void free_pos_bias(vdx::Model& m);
+
 const char* vdx_last_error(void) { return g_err; }
 int vdx_version(void) { return 1; }
 
@@ -263,6 +266,24 @@ int vdx_attention_forward_bf16(const void* x_bf16, void* y_bf16, const void* wqk
     if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention: more than 64 tokens per sequence is not supported");
     a.fp8_core = fp8_core ? 1 : 0;
     VDX_HIP(vdx::launch_attention(VDX_MODE_BF16, a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_attention_forward_bias(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                               const void* wo_packed, const float* bo, const float* bias, int batch, int frames, int h, int w, int c,
+                               int heads, int temporal, void* stream) {
+    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo || !bias) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_bias: null tensor");
+    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
+    if (io_bf16 && mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_bias: bf16 tensors need VDX_MODE_BF16");
+    if (c % (io_bf16 ? 8 : 4) || c > 1024 || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_bias: C must be a multiple of 4 (8 for bf16 tensors) and <= 1024");
+    vdx::AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
+    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = heads; a.pos_bias = bias;
+    fill_attn_geometry(a, batch, frames, h, w, c, temporal);
+    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_bias: more than 64 tokens per sequence is not supported");
+    // the route of the network's temporal blocks with the switch on (model.hip: attention_block_forward)
+    VDX_HIP(vdx::attention_block_forward(mode, a, temporal != 0, batch * frames, frames, h, w, nullptr, 0, vdx::ATTN_ANY, (hipStream_t)stream));
     return VDX_OK;
 }
 
@@ -463,6 +484,7 @@ void vdx_destroy(vdx_handle* h) {
     h->drop_graphs();
     vdx::comm_destroy(&h->comm);
     vdx::bwd_state_free(&h->bwd);
+    free_pos_bias(h->model);
     if (h->model.d_ss_layers) (void)hipFree(h->model.d_ss_layers);
     if (h->model.d_pack_jobs) (void)hipFree(h->model.d_pack_jobs);
     if (h->model.d_pack_t_jobs) (void)hipFree(h->model.d_pack_t_jobs);
@@ -485,11 +507,45 @@ int vdx_get_activation_storage(const vdx_handle* h) { return h ? h->model.act16 
 int vdx_set_attention_fp8(vdx_handle* h, int on) {
     if (!h) VDX_FAIL(VDX_ERR_INVALID, "set_attention_fp8: null handle");
     if (on && h->model.mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "fp8 attention needs a VDX_MODE_BF16 handle");
+    if (on && h->model.pos_bias) VDX_FAIL(VDX_ERR_STATE, "set_attention_fp8: fp8 attention and the temporal position bias exclude each other (the fp8 cores have no bias form)");
     const int v = on ? 1 : 0;
     if (v != h->model.attn_fp8) { h->drop_graphs(); h->model.attn_fp8 = v; }
     return VDX_OK;
 }
 int vdx_get_attention_fp8(const vdx_handle* h) { return h ? h->model.attn_fp8 : 0; }
+
+static void free_pos_bias(vdx::Model& m) {
+    if (m.d_pos_buckets) { (void)hipFree(m.d_pos_buckets); m.d_pos_buckets = nullptr; }
+    if (m.d_pos_table) { (void)hipFree(m.d_pos_table); m.d_pos_table = nullptr; }
+    if (m.d_pos_dbias) { (void)hipFree(m.d_pos_dbias); m.d_pos_dbias = nullptr; }
+}
+
+int vdx_set_temporal_pos_bias(vdx_handle* h, int on, const int* buckets) {
+    if (!h) VDX_FAIL(VDX_ERR_INVALID, "set_temporal_pos_bias: null handle");
+    vdx::Model& m = h->model;
+    if (!on) {
+        if (m.pos_bias) { h->drop_graphs(); m.pos_bias = 0; }
+        return VDX_OK;
+    }
+    if (m.attn_fp8) VDX_FAIL(VDX_ERR_STATE, "set_temporal_pos_bias: the temporal position bias and fp8 attention exclude each other (the fp8 cores have no bias form)");
+    const int F = m.cfg.num_frames;
+    if (F < 1 || F > 64) VDX_FAIL(VDX_ERR_INVALID, "set_temporal_pos_bias: 1..64 frames");
+    if (!buckets) VDX_FAIL(VDX_ERR_INVALID, "set_temporal_pos_bias: null bucket map");
+    for (int i = 0; i < F * F; ++i) if (buckets[i] < 0 || buckets[i] >= 32) VDX_FAIL(VDX_ERR_INVALID, "set_temporal_pos_bias: bucket outside [0, 32)");
+    if (!m.d_ss_layers) VDX_FAIL(VDX_ERR_STATE, "set_temporal_pos_bias: handle was created without a GPU");
+    h->drop_graphs();                                // (also: no replay of this handle is in flight while the map is rewritten)
+    m.pos_bias = 0;
+    const size_t nb = (size_t)F * F * sizeof(int), nt = (size_t)m.cfg.attn_heads * F * F * sizeof(float);
+    hipError_t e = hipSuccess;
+    if (!m.d_pos_buckets) e = hipMalloc(reinterpret_cast<void**>(&m.d_pos_buckets), nb);
+    if (e == hipSuccess && !m.d_pos_table) e = hipMalloc(reinterpret_cast<void**>(&m.d_pos_table), nt);
+    if (e == hipSuccess && !m.d_pos_dbias) e = hipMalloc(reinterpret_cast<void**>(&m.d_pos_dbias), nt);
+    if (e == hipSuccess) e = hipMemcpy(m.d_pos_buckets, buckets, nb, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { free_pos_bias(m); return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__); }
+    m.pos_bias = 1;
+    return VDX_OK;
+}
+int vdx_get_temporal_pos_bias(const vdx_handle* h) { return h ? h->model.pos_bias : 0; }
 
 int vdx_param_count(const vdx_handle* h) { return h ? (int)h->model.params.size() : 0; }
 long vdx_param_total(const vdx_handle* h) { return h ? h->model.param_total : 0; }
@@ -1221,6 +1277,35 @@ int vdx_attention_core_backward_io(const void* qkv, const void* d_o, void* o, vo
     a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)HD * es);
     a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)2 * HD * es);
     a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
+    VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+size_t vdx_attention_bias_backward_scratch_floats(int heads, int tokens) {
+    return (heads < 1 || tokens < 1 || tokens > 64) ? 0 : vdx::attn_bwd_bias_scratch_floats(heads, tokens);
+}
+
+int vdx_attention_core_backward_bias(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias,
+                                     float* dbias, float* scratch, size_t scratch_floats, int batch, int frames, int h, int w, int heads,
+                                     int temporal, int bf16_operands, void* stream) {
+    if (!qkv || !d_o || !o || !dqkv || !bias || !dbias || !scratch || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: bad argument");
+    const int HD = heads * 32;
+    if (dstride < 3 * HD || dstride % 8) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: dstride must be a multiple of 8, at least 3 * heads * 32 (one [rows][dq|dk|dv] buffer)");
+    vdx::AttnBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    const long hw = (long)h * w;
+    if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
+    else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
+    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: more than 64 tokens per sequence");
+    if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: bf16 tensors need bf16_operands and at most 16 tokens per sequence");
+    if (scratch_floats < vdx::attn_bwd_bias_scratch_floats(heads, a.L)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: scratch too small (vdx_attention_bias_backward_scratch_floats)");
+    a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
+    a.dq = (float*)dqkv;
+    const size_t es = io_bf16 ? 2 : 4;
+    a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)HD * es);
+    a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)2 * HD * es);
+    a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
+    a.bias = bias; a.dbias = dbias; a.part = scratch; a.part_cap = scratch_floats;
     VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
     return VDX_OK;
 }

@@ -137,8 +137,12 @@ struct AttnArgs {
     int fp8_core;                             // bf16 mode, <= 16 tokens: QK^T and PV on fp8 (e4m3) MFMA operands (vdx_set_attention_fp8)
     void* oscratch;                           // [rows][heads*32] bf16: per-head attention output of launch_attention_heads
     int CPad, HDPad;                          // completed by the launcher
+    const float* pos_bias;                    // [heads][L][L] fp32 added to the scaled scores before the softmax (vdx_set_temporal_pos_bias), or null:
+                                              // the generic kernels only (attention_reg_kernel / attention_kernel, BIAS instantiations)
 };
 hipError_t launch_attention(int mode, AttnArgs a, hipStream_t st);
+// table[h][i][j] = emb[buckets[i * n + j]][h]: the [heads][n][n] bias of the temporal attention blocks from the [32][heads] embedding
+hipError_t launch_pos_bias_table(const float* emb, const int* buckets, float* table, int heads, int n, hipStream_t st);
 // bf16 mode, <= 16 tokens, 8 heads: q/k/v projection + attention core per head (one workgroup per head: its weights resident in LDS,
 // every wave streams its own sequences, no barriers) -> a.oscratch; the out-projection + residual is a 1x1 conv_igemm by the caller
 hipError_t launch_attention_heads(AttnArgs a, hipStream_t st);
@@ -296,8 +300,15 @@ struct AttnBwdArgs {
     int dstride;                                                     // row stride (elements) of dq / dk / dv: heads*32, or 3*heads*32 for one [rows][dq|dk|dv] buffer
     int io_bf16;                                                     // qkv, dO, O, dq, dk, dv are bf16 tensors (bf16 MFMA form only)
     int bf16_mma;                                                    // bf16 MFMA form (bf16 mode, L <= 16) instead of the exact fp32 VALU form
+    // pre-softmax bias (vdx_set_temporal_pos_bias): logits = scale q.k + bias[h][i][j].  The bias forms run on a fixed grid, every workgroup
+    // STORES the sum of dS over its sequences into its own slot of `part`, and a second pass adds the slots in order into dbias (+=)
+    const float* bias; float* dbias;                                 // [heads][L][L] each, or null / null
+    float* part; size_t part_cap;                                    // scratch for the slots and its capacity in floats (attn_bwd_bias_scratch_floats)
 };
+size_t attn_bwd_bias_scratch_floats(int heads, int L);
 hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st);
+// demb[b][h] = sum over (i, j) with buckets[i * n + j] == b, in (i, j) order, of dbias[h][i][j]   (one thread per (b, h): no atomics)
+hipError_t launch_pos_bias_scatter(const float* dbias, const int* buckets, float* demb, int heads, int n, hipStream_t st);
 // fused attention backward of the widest level (bf16 mode, C == 64, 8 heads x 32, <= 16 tokens): q/k/v recompute, dO = g Wo^T, the
 // core and dx = g + dq|dk|dv . Wqkv^T in one kernel; O and dq|dk|dv are written (bf16) for the weight-gradient kernels
 struct AttnBwdXArgs {

@@ -166,6 +166,23 @@ def attention_forward_bf16(x, packed, heads, temporal, fp8_core=False):
     return y
 
 
+_attn_fwd_bias = L._sig('vdx_attention_forward_bias', C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p])
+
+
+def attention_forward_bias(x, packed, bias, heads, temporal, mode):
+    """The attention block with a pre-softmax bias [heads, L, L] fp32 (the temporal blocks under Unet3D(temporal_pos_bias=True)).
+    x: fp32 or bfloat16 (mode 'bf16') channel-last [B, F, H, W, C]; y has x's dtype."""
+    B, Fr, H, W, C_ = x.shape
+    Ltok = Fr if temporal else H * W
+    bias = bias.to(x.device, torch.float32).contiguous()
+    assert x.is_contiguous() and tuple(bias.shape) == (heads, Ltok, Ltok)
+    y = torch.empty_like(x)
+    wqkv, bqkv, wo, bo = packed
+    L.check(_attn_fwd_bias(_mode(mode), L.ptr(x), L.ptr(y), _is16(x), L.ptr(wqkv), L.ptr(bqkv), L.ptr(wo), L.ptr(bo), L.ptr(bias),
+                           B, Fr, H, W, C_, heads, int(temporal), L.stream_ptr()))
+    return y
+
+
 def sla_forward(x, wq, wk, wv, wo, heads, mode):
     """wq/wk/wv: Flax (1, C, 256); wo: (1, 256, C)."""
     B, Fr, H, W, C_ = x.shape
@@ -517,6 +534,28 @@ def attention_core_backward_io(qkv, d_o, B, Fr, H, W, heads, temporal, bf16_oper
     L.check(_attn_core_bwd_io(L.ptr(qkv), L.ptr(d_o), L.ptr(o), L.ptr(dqkv), 3 * HD + pad_cols, _is16(qkv), B, Fr, H, W, heads, int(temporal),
                               int(bool(bf16_operands)), L.stream_ptr()))
     return o, dqkv
+
+
+_attn_bias_scr = L._sig('vdx_attention_bias_backward_scratch_floats', C.c_size_t, [C.c_int, C.c_int])
+_attn_core_bwd_bias = L._sig('vdx_attention_core_backward_bias', C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] +
+                             [C.c_int] * 7 + [C.c_void_p])
+
+
+def attention_core_backward_bias(qkv, d_o, bias, B, Fr, H, W, heads, temporal, bf16_operands=True):
+    """attention_core_backward_io with the pre-softmax bias [heads, L, L] fp32 -> o, dqkv (dtype of qkv), dbias [heads, L, L] fp32
+    (the sum of dS over the sequences; deterministic: per-workgroup slots + an ordered second pass)."""
+    assert qkv.dtype == d_o.dtype
+    HD = heads * 32
+    Ltok = Fr if temporal else H * W
+    bias = bias.to(qkv.device, torch.float32).contiguous()
+    assert tuple(bias.shape) == (heads, Ltok, Ltok)
+    o = torch.empty_like(d_o)
+    dqkv = torch.empty(d_o.shape[0], 3 * HD, dtype=d_o.dtype, device=d_o.device)
+    dbias = torch.zeros_like(bias)
+    scratch = torch.empty(_attn_bias_scr(heads, Ltok), dtype=torch.float32, device=qkv.device)
+    L.check(_attn_core_bwd_bias(L.ptr(qkv), L.ptr(d_o), L.ptr(o), L.ptr(dqkv), 3 * HD, _is16(qkv), L.ptr(bias), L.ptr(dbias), L.ptr(scratch),
+                                scratch.numel(), B, Fr, H, W, heads, int(temporal), int(bool(bf16_operands)), L.stream_ptr()))
+    return o, dqkv, dbias
 
 
 def temporal_attention_backward_fused_ex(x, dy, wqkv, bqkv, wo):

@@ -59,6 +59,8 @@ vdx_slot_info = L._sig('vdx_slot_info', C.c_int, [_vp, C.c_int, C.c_char_p, C.c_
 vdx_num_stages = L._sig('vdx_num_stages', C.c_int, [_vp])
 vdx_set_activation_storage = L._sig('vdx_set_activation_storage', C.c_int, [_vp, C.c_int])
 vdx_set_attention_fp8 = L._sig('vdx_set_attention_fp8', C.c_int, [_vp, C.c_int])
+vdx_set_temporal_pos_bias = L._sig('vdx_set_temporal_pos_bias', C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)])
+vdx_get_temporal_pos_bias = L._sig('vdx_get_temporal_pos_bias', C.c_int, [_vp])
 vdx_get_activation_storage = L._sig('vdx_get_activation_storage', C.c_int, [_vp])
 vdx_packed_bwd_bytes = L._sig('vdx_packed_bwd_bytes', C.c_size_t, [_vp])
 vdx_pack_params_bwd = L._sig('vdx_pack_params_bwd', C.c_int, [_vp, _vp, _vp, _vp])
@@ -77,6 +79,7 @@ class _Handle:
 
     def __init__(self, cfg: VdxConfig):
         self.ptr = _vp()
+        self.frames = int(cfg.num_frames)
         L.check(vdx_create(C.byref(cfg), C.byref(self.ptr)))
 
     def __del__(self):
@@ -114,17 +117,43 @@ def _trunc_normal(rng: np.random.Generator, shape, std: float) -> np.ndarray:
     return (out * (std / 0.87962566103423978)).astype(np.float32)
 
 
+def relative_position_buckets(n: int) -> torch.Tensor:
+    """int64 [n, n]: bucket(i, j) of query frame i and key frame j -- `_relative_position_bucket` of the reference's RelativePositionBias
+    (modules.py:350-390) as it is always called: 32 buckets, max distance 128.  Half of the buckets serve keys in the past (j < i, +16), half
+    keys in the future, so the map is NOT symmetric; offsets below 8 get a bucket each, larger ones share logarithmic buckets.  Same float32
+    operations in the same order as the reference: exact powers (|i - j| = 16, 32) sit on a bucket boundary, where one ulp decides."""
+    qpos = torch.arange(n)[:, None]
+    kpos = torch.arange(n)[None, :]
+    rel = qpos - kpos
+    num_buckets, max_distance = 32, 128
+    neg = -rel
+    num_buckets //= 2
+    ret = (neg < 0).to(torch.int64) * num_buckets
+    neg = neg.abs()
+    max_exact = num_buckets // 2
+    is_small = neg < max_exact
+    safe = neg.clamp_min(1).to(torch.float32)
+    val_if_large = max_exact + (torch.log(safe / max_exact) / math.log(max_distance / max_exact)
+                                * (num_buckets - max_exact)).to(torch.int64)
+    val_if_large = torch.minimum(val_if_large, torch.full_like(val_if_large, num_buckets - 1))
+    return ret + torch.where(is_small, neg, val_if_large)
+
+
 class Unet3D:
     """Space-time factorised 3-D U-Net denoiser (reference unet3d.py:58-75 signature).
 
     Extra keyword `mode` ('bf16' | 'f16' | 'f32') selects the MFMA arithmetic; `device` the GPU; `attn_fp8` (mode 'bf16', forward /
     sampling only) runs QK^T and PV of the <= 16-token attention blocks on fp8 (e4m3) MFMA operands (BASELINE.json configs[4]).
+    `temporal_pos_bias` (also a settable attribute): every temporal attention block adds the relative position bias of the parameter
+    `time_rel_pos_bias.relative_attention_bias.embedding` to its scores before the softmax -- the network can tell frame order.  Off,
+    the reference's behaviour: the parameter is dead and the network equivariant under frame permutations.  An architecture argument
+    like `dim`: not stored in checkpoints.  Excludes `attn_fp8`.
     """
 
     def __init__(self, dim: int, rngs=0, dim_mults=(1, 2, 4, 8), cond_dim=None, out_dim=None, channels=3,
                  attn_heads=8, attn_dim_head=32, use_bert_text_cond=False, init_dim=None, init_kernel_size=7,
                  use_sparse_linear_attn=True, block_type='resnet', resnet_groups=8, log_dims=False,
-                 *, mode: str = 'bf16', device=None, attn_fp8: bool = False):
+                 *, mode: str = 'bf16', device=None, attn_fp8: bool = False, temporal_pos_bias: bool = False):
         assert init_kernel_size % 2 == 1                                       # unet3d.py:105
         self.dim = dim
         self.dim_mults = tuple(dim_mults)
@@ -147,6 +176,9 @@ class Unet3D:
         if attn_fp8 and mode != 'bf16':
             raise ValueError("attn_fp8 needs mode='bf16'")
         self.attn_fp8 = bool(attn_fp8)
+        if attn_fp8 and temporal_pos_bias:
+            raise ValueError('attn_fp8 and temporal_pos_bias exclude each other (the fp8 attention cores have no bias form)')
+        self.temporal_pos_bias = bool(temporal_pos_bias)
         # default: the process's CURRENT device (a rank launched by torch.distributed.run has called set_device(LOCAL_RANK))
         if device is not None:
             self.device = torch.device(device)
@@ -313,7 +345,20 @@ class Unet3D:
         if self.act_bf16 and self.mode != 'bf16':
             raise ValueError("act_bf16 needs mode='bf16'")
         L.check(vdx_set_activation_storage(h.ptr, 2 if self.act_bf16 == 2 and self.act_bf16 is not True else int(bool(self.act_bf16))))
-        L.check(vdx_set_attention_fp8(h.ptr, int(self.attn_fp8)))
+        if self.attn_fp8 and self.temporal_pos_bias:
+            raise ValueError('attn_fp8 and temporal_pos_bias exclude each other (the fp8 attention cores have no bias form)')
+        on = int(bool(self.temporal_pos_bias))
+        if not on:
+            if vdx_get_temporal_pos_bias(h.ptr):
+                L.check(vdx_set_temporal_pos_bias(h.ptr, 0, None))
+            L.check(vdx_set_attention_fp8(h.ptr, int(self.attn_fp8)))
+            return
+        L.check(vdx_set_attention_fp8(h.ptr, 0))
+        if not vdx_get_temporal_pos_bias(h.ptr):          # the bucket map is uploaded once per handle and switch-on (never during a capture)
+            n = h.frames
+            host = relative_position_buckets(n).to(torch.int32).contiguous().view(-1)
+            arr = (C.c_int * (n * n))(*host.tolist())
+            L.check(vdx_set_temporal_pos_bias(h.ptr, 1, arr))
 
     def workspace(self, batch: int, frames: int, size: int) -> torch.Tensor:
         key = (batch, frames, size)
