@@ -6,12 +6,30 @@
 #include "model.h"
 #include "comm.h"
 
+// Everything a sampling step can bake into its captured graph: what the eleven vdx_*_sample_loop* entry points fill in and sample_loop()
+// runs.  A field the entry does not have stays zero.
+enum { CHAIN_ANCESTRAL = 0, CHAIN_DDIM = 1, CHAIN_DPM = 2 };
+struct LoopArgs {
+    int chain, masked, guided;                          // CHAIN_*; the masked (inpainting) step; classifier-free guidance over 2 * batch rows
+    const float* params; const void* packed;
+    float* img; float* eps_buf; float* hist; int* t_dev; uint64_t* step_dev;
+    const float* tables; int timesteps;                 // [5][T]: the ancestral step and the dynamic threshold; T is also mask_tables' row length
+    const float* alphas_cumprod; const int* seq; int seq_len;     // the two sequence chains
+    const float* cond; uint64_t seed; int clip_denoised, order;
+    float percentile; float* thres_buf;                 // dynamic threshold: percentile > 0 && clip_denoised
+    const float* known; const unsigned char* mask; const float* mask_tables; int resample_steps;
+    float cond_scale, rescale; double* cfg_scratch;
+    void* workspace; size_t workspace_bytes; int batch;
+};
+
 struct vdx_handle {
     vdx::Model model;
-    // every argument a captured sampling step bakes in (full pointers: two workspaces / streams never alias one key)
-    struct GraphKey { const void* p[18]; unsigned long long seed; int i[6]; size_t ws; float f; unsigned cfg[2]; };
-    // one cached graph per loop kind: 0 = DDPM p_sample_loop, 1 = DDIM, 2 = masked DDPM, 3 = masked DDIM, 4 = DPM-Solver++, 5 = masked DPM-Solver++,
-    // 6 / 7 / 8 = the guided (classifier-free guidance) DDPM / DDIM / DPM-Solver++ loops
+    // the key of a captured sampling step: the LoopArgs of the call with every field its step does not read set to zero (sample_loop()),
+    // the stream and the activation storage.  Full pointers: two workspaces / streams never alias one key.  Compared with memcmp, so it
+    // is zero-filled before the fields are assigned
+    struct GraphKey { LoopArgs a; const void* stream; int act16; };
+    // one cached graph per (chain, variant): slot = 3 * variant + chain with variant 0 = plain, 1 = masked, 2 = guided and chain 0 = the
+    // ancestral loop, 1 = DDIM, 2 = DPM-Solver++ -- no loop ever evicts another one's graph
     // `last` = the stream the exec was last launched on: replays may still be running when the graph has to go
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key; hipStream_t last = nullptr;
@@ -604,14 +622,15 @@ int vdx_q_sample(const float* x_start, const int* t, const float* noise, float* 
     return VDX_OK;
 }
 
-static int fill_psample(vdx::PSampleArgs& a, const float* x, const float* eps_hat, float* out, const int* t, const float* tables,
-                        int timesteps, const float* noise, uint64_t seed, uint64_t offset, const uint64_t* dev_offset,
-                        const float* thres, int clip, int channels, long per_sample) {
+static vdx::PSampleArgs psample_args(const float* x, const float* eps_hat, float* out, const int* t, const float* tables, int timesteps,
+                                     const float* noise, uint64_t seed, uint64_t offset, const uint64_t* dev_offset, const float* thres,
+                                     int clip, int channels, long per_sample) {
+    vdx::PSampleArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.eps = eps_hat; a.out = out; a.t = t; a.tables = tables; a.T = timesteps; a.noise = noise;
     a.seed = seed; a.offset = offset; a.dev_offset = reinterpret_cast<const unsigned long long*>(dev_offset);
     a.thres = thres; a.clip = clip; a.C = channels; a.per_sample = per_sample; a.post_scale = 1.f; a.post_shift = 0.f;
-    return 0;
+    return a;
 }
 
 int vdx_p_sample_step(const float* x, const float* eps_hat, float* out, const int* t, const float* tables, int timesteps,
@@ -620,8 +639,7 @@ int vdx_p_sample_step(const float* x, const float* eps_hat, float* out, const in
     if (!x || !eps_hat || !out || !t || !tables || timesteps < 1 || batch < 1 || channels < 1) VDX_FAIL(VDX_ERR_INVALID, "p_sample: bad argument");
     if (per_sample % channels) VDX_FAIL(VDX_ERR_INVALID, "p_sample: per_sample must be a multiple of channels");
     if (!noise && per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "p_sample: generated noise needs per_sample % 4 == 0");
-    vdx::PSampleArgs a;
-    fill_psample(a, x, eps_hat, out, t, tables, timesteps, noise, seed, offset, dev_offset, thres, clip_denoised, channels, per_sample);
+    const vdx::PSampleArgs a = psample_args(x, eps_hat, out, t, tables, timesteps, noise, seed, offset, dev_offset, thres, clip_denoised, channels, per_sample);
     VDX_HIP(vdx::launch_p_sample(a, batch, (hipStream_t)stream));
     return VDX_OK;
 }
@@ -644,49 +662,6 @@ int vdx_dynamic_threshold(const float* x, const float* eps_hat, const int* t, co
     if (!(percentile > 0.f && percentile <= 1.f) || per_sample % channels) VDX_FAIL(VDX_ERR_INVALID, "dynamic_threshold: percentile must be in (0, 1]");
     VDX_HIP(vdx::launch_dyn_thres(x, eps_hat, t, tables, timesteps, percentile, thres_out, batch, channels, per_sample, (hipStream_t)stream));
     return VDX_OK;
-}
-
-int vdx_p_sample_loop_dyn(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
-                          uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
-                          int clip_denoised, float percentile, float* thres_buf, void* workspace, size_t workspace_bytes, int batch,
-                          int use_graph, void* stream) {
-    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !tables || !workspace) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop: null argument");
-    if (!h->model.d_ss_layers) VDX_FAIL(VDX_ERR_STATE, "p_sample_loop: handle was created without a GPU");
-    if (nsteps < 0 || nsteps > timesteps) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop: nsteps out of range");
-    const bool dyn = percentile > 0.f && clip_denoised;
-    if (dyn && (!thres_buf || percentile > 1.f)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop: dynamic threshold needs thres_buf and a percentile in (0, 1]");
-    const vdx::Model& m = h->model;
-    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
-    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop: C*F*H*W must be a multiple of 4");
-    if (m.out_dim != m.cfg.channels) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop: out_dim must equal channels");
-    hipStream_t st = (hipStream_t)stream;
-    auto step = [&]() -> int {
-        // reference p_sample_loop never forwards cond (Q10); when a cond tensor is supplied it is used un-masked
-        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
-        if (rc != VDX_OK) return rc;
-        hipError_t e = hipSuccess;
-        if (dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
-        vdx::PSampleArgs a;
-        fill_psample(a, img, eps_buf, img, t_dev, tables, timesteps, nullptr, seed, 1, step_dev, dyn ? thres_buf : nullptr, clip_denoised, m.cfg.channels, per_sample);
-        if (e == hipSuccess) e = vdx::launch_p_sample(a, batch, st);
-        if (e == hipSuccess) e = vdx::launch_advance(t_dev, batch, reinterpret_cast<unsigned long long*>(step_dev), st);
-        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
-        return VDX_OK;
-    };
-    vdx_handle::GraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
-    key.p[6] = tables; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = dyn ? thres_buf : nullptr;
-    key.seed = seed; key.i[0] = timesteps; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch;
-    key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
-    return run_steps(h, 0, key, nsteps, use_graph, st, step);
-}
-
-int vdx_p_sample_loop(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
-                      uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
-                      int clip_denoised, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
-    return vdx_p_sample_loop_dyn(h, params, packed, img, eps_buf, t_dev, step_dev, tables, timesteps, nsteps, cond, seed, clip_denoised,
-                                 0.f, nullptr, workspace, workspace_bytes, batch, use_graph, stream);
 }
 
 // the masked kernels move 16-byte float4 and 4-byte uchar4 vectors
@@ -712,53 +687,10 @@ int vdx_p_sample_step_masked(const float* x, const float* eps_hat, float* out, c
     if (resample_steps < 1) VDX_FAIL(VDX_ERR_INVALID, "p_sample_masked: resample_steps must be >= 1");
     if (per_sample % channels || per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "p_sample_masked: per_sample must be a multiple of channels and of 4");
     if (!masked_aligned(x, known, out, mask)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_masked: x / known / out must be 16-byte and mask 4-byte aligned");
-    vdx::PSampleArgs a;
-    fill_psample(a, x, eps_hat, out, t, tables, timesteps, nullptr, seed, 0, nullptr, thres, clip_denoised, channels, per_sample);
+    const vdx::PSampleArgs a = psample_args(x, eps_hat, out, t, tables, timesteps, nullptr, seed, 0, nullptr, thres, clip_denoised, channels, per_sample);
     const vdx::MaskArgs m = {known, mask, mask_tables, resample_steps, step, reinterpret_cast<const unsigned long long*>(step_dev)};
     VDX_HIP(vdx::launch_p_sample_masked(a, m, batch, (hipStream_t)stream));
     return VDX_OK;
-}
-
-int vdx_p_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
-                             uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
-                             int clip_denoised, float percentile, float* thres_buf, const float* known, const unsigned char* mask,
-                             const float* mask_tables, int resample_steps, void* workspace, size_t workspace_bytes, int batch,
-                             int use_graph, void* stream) {
-    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !tables || !workspace || !known || !mask || !mask_tables)
-        VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: null argument");
-    if (!h->model.d_ss_layers) VDX_FAIL(VDX_ERR_STATE, "p_sample_loop_masked: handle was created without a GPU");
-    if (resample_steps < 1) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: resample_steps must be >= 1");
-    if (timesteps < 1 || nsteps < 0 || (long)nsteps > (long)timesteps * resample_steps) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: nsteps out of range");
-    const bool dyn = percentile > 0.f && clip_denoised;
-    if (dyn && (!thres_buf || percentile > 1.f)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: dynamic threshold needs thres_buf and a percentile in (0, 1]");
-    const vdx::Model& m = h->model;
-    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
-    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: C*F*H*W must be a multiple of 4");
-    if (m.out_dim != m.cfg.channels) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: out_dim must equal channels");
-    if (!masked_aligned(img, known, img, mask)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_masked: img / known must be 16-byte and mask 4-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    unsigned long long* sd = reinterpret_cast<unsigned long long*>(step_dev);
-    auto step = [&]() -> int {
-        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
-        if (rc != VDX_OK) return rc;
-        hipError_t e = hipSuccess;
-        if (dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
-        vdx::PSampleArgs a;
-        fill_psample(a, img, eps_buf, img, t_dev, tables, timesteps, nullptr, seed, 0, nullptr, dyn ? thres_buf : nullptr, clip_denoised, m.cfg.channels, per_sample);
-        const vdx::MaskArgs ma = {known, mask, mask_tables, resample_steps, 0ull, sd};
-        if (e == hipSuccess) e = vdx::launch_p_sample_masked(a, ma, batch, st);
-        if (e == hipSuccess) e = vdx::launch_resample_advance(t_dev, batch, sd, resample_steps, st);
-        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
-        return VDX_OK;
-    };
-    vdx_handle::GraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
-    key.p[6] = tables; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = dyn ? thres_buf : nullptr;
-    key.p[11] = known; key.p[12] = mask; key.p[13] = mask_tables;
-    key.seed = seed; key.i[0] = timesteps; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch; key.i[4] = resample_steps;
-    key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
-    return run_steps(h, 2, key, nsteps, use_graph, st, step);
 }
 
 int vdx_ddim_step(const float* x, const float* eps_hat, float* out, const float* alphas_cumprod, const int* seq,
@@ -768,46 +700,6 @@ int vdx_ddim_step(const float* x, const float* eps_hat, float* out, const float*
     VDX_HIP(vdx::launch_ddim_step(x, eps_hat, out, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev), thres,
                                   clip_denoised, batch, channels, per_sample, (hipStream_t)stream));
     return VDX_OK;
-}
-
-int vdx_ddim_sample_loop_dyn(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
-                             uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
-                             int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf, void* workspace,
-                             size_t workspace_bytes, int batch, int use_graph, void* stream) {
-    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !alphas_cumprod || !seq || !workspace) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop: null argument");
-    if (!h->model.d_ss_layers) VDX_FAIL(VDX_ERR_STATE, "ddim_sample_loop: handle was created without a GPU");
-    if (seq_len < 1 || nsteps < 0 || nsteps > seq_len) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop: nsteps out of range");
-    const bool dyn = percentile > 0.f && clip_denoised;
-    if (dyn && (!thres_buf || !tables || timesteps < 1 || percentile > 1.f)) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop: dynamic threshold needs tables, thres_buf and a percentile in (0, 1]");
-    const vdx::Model& m = h->model;
-    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
-    if (m.out_dim != m.cfg.channels) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop: out_dim must equal channels");
-    hipStream_t st = (hipStream_t)stream;
-    auto step = [&]() -> int {
-        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
-        if (rc != VDX_OK) return rc;
-        hipError_t e = hipSuccess;
-        if (dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
-        if (e == hipSuccess) e = vdx::launch_ddim_step(img, eps_buf, img, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev),
-                                                       dyn ? thres_buf : nullptr, clip_denoised, batch, m.cfg.channels, per_sample, st);
-        if (e == hipSuccess) e = vdx::launch_ddim_advance(t_dev, batch, seq, reinterpret_cast<unsigned long long*>(step_dev), st);
-        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
-        return VDX_OK;
-    };
-    vdx_handle::GraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
-    key.p[6] = alphas_cumprod; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = seq; key.p[11] = dyn ? (const void*)thres_buf : nullptr;
-    key.i[0] = seq_len; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch; key.i[3] = dyn ? timesteps : 0; key.ws = workspace_bytes;
-    key.f = dyn ? percentile : 0.f; key.seed = dyn ? (unsigned long long)(uintptr_t)tables : 0ull;
-    return run_steps(h, 1, key, nsteps, use_graph, st, step);
-}
-
-int vdx_ddim_sample_loop(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
-                         uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
-                         int clip_denoised, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
-    return vdx_ddim_sample_loop_dyn(h, params, packed, img, eps_buf, t_dev, step_dev, alphas_cumprod, seq, seq_len, nsteps, cond, clip_denoised,
-                                    nullptr, 0, 0.f, nullptr, workspace, workspace_bytes, batch, use_graph, stream);
 }
 
 int vdx_ddim_step_masked(const float* x, const float* eps_hat, float* out, const float* alphas_cumprod, const int* seq,
@@ -822,47 +714,6 @@ int vdx_ddim_step_masked(const float* x, const float* eps_hat, float* out, const
     VDX_HIP(vdx::launch_ddim_step_masked(x, eps_hat, out, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev), thres,
                                          clip_denoised, batch, channels, per_sample, m, timesteps, seed, (hipStream_t)stream));
     return VDX_OK;
-}
-
-int vdx_ddim_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
-                                uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
-                                int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf,
-                                const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
-                                void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
-    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !alphas_cumprod || !seq || !workspace || !known || !mask || !mask_tables)
-        VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: null argument");
-    if (!h->model.d_ss_layers) VDX_FAIL(VDX_ERR_STATE, "ddim_sample_loop_masked: handle was created without a GPU");
-    if (seq_len < 1 || nsteps < 0 || nsteps > seq_len) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: nsteps out of range");
-    if (timesteps < 1) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: timesteps (the row length of mask_tables) must be >= 1");
-    const bool dyn = percentile > 0.f && clip_denoised;
-    if (dyn && (!thres_buf || !tables || percentile > 1.f)) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: dynamic threshold needs tables, thres_buf and a percentile in (0, 1]");
-    const vdx::Model& m = h->model;
-    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
-    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: C*F*H*W must be a multiple of 4");
-    if (m.out_dim != m.cfg.channels) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: out_dim must equal channels");
-    if (!masked_aligned(img, known, img, mask)) VDX_FAIL(VDX_ERR_INVALID, "ddim_sample_loop_masked: img / known must be 16-byte and mask 4-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const vdx::MaskArgs ma = {known, mask, mask_tables, 1, 0ull, nullptr};
-    auto step = [&]() -> int {
-        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
-        if (rc != VDX_OK) return rc;
-        hipError_t e = hipSuccess;
-        if (dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
-        if (e == hipSuccess) e = vdx::launch_ddim_step_masked(img, eps_buf, img, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev),
-                                                              dyn ? thres_buf : nullptr, clip_denoised, batch, m.cfg.channels, per_sample, ma,
-                                                              timesteps, seed, st);
-        if (e == hipSuccess) e = vdx::launch_ddim_advance(t_dev, batch, seq, reinterpret_cast<unsigned long long*>(step_dev), st);
-        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
-        return VDX_OK;
-    };
-    vdx_handle::GraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
-    key.p[6] = alphas_cumprod; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = seq; key.p[11] = dyn ? (const void*)thres_buf : nullptr;
-    key.p[12] = known; key.p[13] = mask; key.p[14] = mask_tables; key.p[15] = dyn ? (const void*)tables : nullptr;
-    key.seed = seed; key.i[0] = seq_len; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch; key.i[3] = timesteps;
-    key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
-    return run_steps(h, 3, key, nsteps, use_graph, st, step);
 }
 
 int vdx_dpm_step(const float* x, const float* eps_hat, float* out, float* hist, const float* alphas_cumprod, const int* seq,
@@ -897,72 +748,6 @@ int vdx_dpm_step_masked(const float* x, const float* eps_hat, float* out, float*
     return VDX_OK;
 }
 
-// the two DPM-Solver++ loops: ma == nullptr is the unmasked one (graph slot 4), else the masked one (slot 5)
-static int dpm_loop(const char* who, vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
-                    uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
-                    int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
-                    const vdx::MaskArgs* ma, uint64_t seed, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
-    char msg[160];
-#define DPM_FAIL(code, text) do { snprintf(msg, sizeof(msg), "%s: %s", who, text); VDX_FAIL(code, msg); } while (0)
-    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !alphas_cumprod || !seq || !workspace) DPM_FAIL(VDX_ERR_INVALID, "null argument");
-    if (ma && (!ma->known || !ma->mask || !ma->mtab)) DPM_FAIL(VDX_ERR_INVALID, "null argument");
-    if (!h->model.d_ss_layers) DPM_FAIL(VDX_ERR_STATE, "handle was created without a GPU");
-    if (order != 1 && order != 2) DPM_FAIL(VDX_ERR_INVALID, "order must be 1 or 2");
-    if (order == 2 && !hist) DPM_FAIL(VDX_ERR_INVALID, "order 2 needs hist");
-    if (seq_len < 1 || nsteps < 0 || nsteps > seq_len) DPM_FAIL(VDX_ERR_INVALID, "nsteps out of range");
-    if (ma && timesteps < 1) DPM_FAIL(VDX_ERR_INVALID, "timesteps (the row length of mask_tables) must be >= 1");
-    const bool dyn = percentile > 0.f && clip_denoised;
-    if (dyn && (!thres_buf || !tables || timesteps < 1 || percentile > 1.f)) DPM_FAIL(VDX_ERR_INVALID, "dynamic threshold needs tables, thres_buf and a percentile in (0, 1]");
-    const vdx::Model& m = h->model;
-    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
-    if (per_sample % 4) DPM_FAIL(VDX_ERR_INVALID, "C*F*H*W must be a multiple of 4");
-    if (m.out_dim != m.cfg.channels) DPM_FAIL(VDX_ERR_INVALID, "out_dim must equal channels");
-    if ((uintptr_t)img % 16 || (uintptr_t)hist % 16 || (ma && !masked_aligned(img, ma->known, img, ma->mask)))
-        DPM_FAIL(VDX_ERR_INVALID, "img / hist / known must be 16-byte and mask 4-byte aligned");
-#undef DPM_FAIL
-    hipStream_t st = (hipStream_t)stream;
-    auto step = [&]() -> int {
-        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
-        if (rc != VDX_OK) return rc;
-        hipError_t e = hipSuccess;
-        if (dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
-        if (e == hipSuccess) e = vdx::launch_dpm_step(img, eps_buf, img, hist, alphas_cumprod, seq, reinterpret_cast<const unsigned long long*>(step_dev),
-                                                      dyn ? thres_buf : nullptr, clip_denoised, order, batch, m.cfg.channels, per_sample, ma,
-                                                      timesteps, seed, st);
-        if (e == hipSuccess) e = vdx::launch_ddim_advance(t_dev, batch, seq, reinterpret_cast<unsigned long long*>(step_dev), st);
-        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
-        return VDX_OK;
-    };
-    vdx_handle::GraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
-    key.p[6] = alphas_cumprod; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = seq; key.p[11] = dyn ? (const void*)thres_buf : nullptr;
-    if (ma) { key.p[12] = ma->known; key.p[13] = ma->mask; key.p[14] = ma->mtab; }
-    key.p[15] = dyn ? (const void*)tables : nullptr; key.p[16] = hist;
-    key.seed = ma ? seed : 0ull; key.i[0] = seq_len; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch;
-    key.i[3] = (ma || dyn) ? timesteps : 0; key.i[5] = order;
-    key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
-    return run_steps(h, ma ? 5 : 4, key, nsteps, use_graph, st, step);
-}
-
-int vdx_dpm_sample_loop(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
-                        uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
-                        int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
-                        void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
-    return dpm_loop("dpm_sample_loop", h, params, packed, img, eps_buf, hist, t_dev, step_dev, alphas_cumprod, seq, seq_len, nsteps, cond,
-                    clip_denoised, order, tables, timesteps, percentile, thres_buf, nullptr, 0, workspace, workspace_bytes, batch, use_graph, stream);
-}
-
-int vdx_dpm_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
-                               uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
-                               int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
-                               const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
-                               void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
-    const vdx::MaskArgs ma = {known, mask, mask_tables, 1, 0ull, nullptr};
-    return dpm_loop("dpm_sample_loop_masked", h, params, packed, img, eps_buf, hist, t_dev, step_dev, alphas_cumprod, seq, seq_len, nsteps, cond,
-                    clip_denoised, order, tables, timesteps, percentile, thres_buf, &ma, seed, workspace, workspace_bytes, batch, use_graph, stream);
-}
-
 size_t vdx_cfg_scratch_doubles(int batch) { return batch > 0 ? vdx::cfg_scratch_doubles(batch) : 0; }
 
 int vdx_cfg_combine(const float* eps2, float* out, float cond_scale, float rescale, double* scratch, int batch, long per_sample, void* stream) {
@@ -975,82 +760,191 @@ int vdx_cfg_combine(const float* eps2, float* out, float cond_scale, float resca
     return VDX_OK;
 }
 
-// The three guided loops (classifier-free guidance; EXTENSION, parity unpinned: the reference's p_sample_loop drops cond).  kind 0 = the
-// ancestral chain, 1 = DDIM, 2 = DPM-Solver++; graph slot 6 + kind.  img / t_dev / eps_buf / workspace hold 2 * batch samples; the step
-// kernels, the threshold and the result use the first `batch`.
-static int guided_loop(const char* who, int kind, vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist,
-                       int* t_dev, uint64_t* step_dev, const float* tables, int timesteps, const float* alphas_cumprod, const int* seq, int seq_len,
-                       int nsteps, const float* cond, uint64_t seed, int clip_denoised, int order, float percentile, float* thres_buf,
-                       float cond_scale, float rescale, double* cfg_scratch, void* workspace, size_t workspace_bytes, int batch, int use_graph,
-                       void* stream) {
+// ---- the sampling loops: one step builder, eleven positional entry points ----
+
+// 0 <= x <= 1 by the bits of x (non-negative floats order like unsigned integers): the library is built with -fno-honor-nans, under
+// which a comparison may let a NaN through, and a NaN rescale has to be refused
+static bool in_unit_interval(float x) {
+    unsigned u;
+    memcpy(&u, &x, sizeof(u));
+    return u <= 0x3F800000u || u == 0x80000000u;       // [+0, 1] or -0
+}
+
+// The step of every loop, launch for launch: (guided: copy img[:B] -> img[B:]) -> model_forward over B samples (guided: 2B, the second
+// half with the null embedding) -> (guided: cfg_combine) -> (dynamic threshold) -> the chain's step kernel on B samples -> the chain's
+// advance (guided: over 2B).  Validates, derives the graph key from `a` and runs nsteps steps eagerly or as replays of one captured step.
+// Guided loops (classifier-free guidance; EXTENSION, parity unpinned: the reference's p_sample_loop drops cond): img / t_dev / eps_buf /
+// workspace hold 2 * batch samples; the step kernels, the threshold and the result use the first `batch`.
+static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int nsteps, int use_graph, void* stream) {
     char msg[160];
-#define CFG_FAIL(code, text) do { snprintf(msg, sizeof(msg), "%s: %s", who, text); VDX_FAIL(code, msg); } while (0)
-    if (!h || !params || !packed || !img || !eps_buf || !t_dev || !step_dev || !workspace || !cond || !cfg_scratch) CFG_FAIL(VDX_ERR_INVALID, "null argument");
-    if (kind == 0 ? !tables : (!alphas_cumprod || !seq)) CFG_FAIL(VDX_ERR_INVALID, "null argument");
-    if (!h->model.d_ss_layers) CFG_FAIL(VDX_ERR_STATE, "handle was created without a GPU");
-    if (!h->model.cfg.cond_dim) CFG_FAIL(VDX_ERR_INVALID, "the network has no condition (cond_dim == 0)");
-    if (batch < 1) CFG_FAIL(VDX_ERR_INVALID, "batch must be >= 1");
-    if (kind == 0 ? (timesteps < 1 || nsteps < 0 || nsteps > timesteps) : (seq_len < 1 || nsteps < 0 || nsteps > seq_len)) CFG_FAIL(VDX_ERR_INVALID, "nsteps out of range");
-    if (kind == 2 && order != 1 && order != 2) CFG_FAIL(VDX_ERR_INVALID, "order must be 1 or 2");
-    if (kind == 2 && order == 2 && !hist) CFG_FAIL(VDX_ERR_INVALID, "order 2 needs hist");
-    if (!(rescale >= 0.f && rescale <= 1.f)) CFG_FAIL(VDX_ERR_INVALID, "rescale must be in [0, 1]");
-    const bool dyn = percentile > 0.f && clip_denoised;
-    if (dyn && (!thres_buf || !tables || timesteps < 1 || percentile > 1.f)) CFG_FAIL(VDX_ERR_INVALID, "dynamic threshold needs tables, thres_buf and a percentile in (0, 1]");
+#define LOOP_FAIL(code, text) do { snprintf(msg, sizeof(msg), "%s: %s", who, text); VDX_FAIL(code, msg); } while (0)
+    const bool anc = a.chain == CHAIN_ANCESTRAL, dpm = a.chain == CHAIN_DPM, masked = a.masked != 0, guided = a.guided != 0;
+    if (!h || !a.params || !a.packed || !a.img || !a.eps_buf || !a.t_dev || !a.step_dev || !a.workspace) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
+    if (anc ? !a.tables : (!a.alphas_cumprod || !a.seq)) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
+    if (masked && (!a.known || !a.mask || !a.mask_tables)) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
+    if (guided && (!a.cond || !a.cfg_scratch)) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
+    if (!h->model.d_ss_layers) LOOP_FAIL(VDX_ERR_STATE, "handle was created without a GPU");
+    // the rules of the variants, keyed on chain / masked / guided (all VDX_ERR_INVALID)
     const vdx::Model& m = h->model;
     const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
-    if (per_sample % 4) CFG_FAIL(VDX_ERR_INVALID, "C*F*H*W must be a multiple of 4");
-    if (m.out_dim != m.cfg.channels) CFG_FAIL(VDX_ERR_INVALID, "out_dim must equal channels");
-    if ((uintptr_t)img % 16 || (uintptr_t)eps_buf % 16 || (uintptr_t)hist % 16 || (uintptr_t)cfg_scratch % 8)
-        CFG_FAIL(VDX_ERR_INVALID, "img / eps_buf / hist must be 16-byte and the cfg scratch 8-byte aligned");
-#undef CFG_FAIL
+    const bool dyn = a.percentile > 0.f && a.clip_denoised;
+    if (guided && !m.cfg.cond_dim) LOOP_FAIL(VDX_ERR_INVALID, "the network has no condition (cond_dim == 0)");
+    if (guided && a.batch < 1) LOOP_FAIL(VDX_ERR_INVALID, "batch must be >= 1");
+    if (guided && !in_unit_interval(a.rescale)) LOOP_FAIL(VDX_ERR_INVALID, "rescale must be in [0, 1]");
+    if (dpm && a.order != 1 && a.order != 2) LOOP_FAIL(VDX_ERR_INVALID, "order must be 1 or 2");
+    if (dpm && a.order == 2 && !a.hist) LOOP_FAIL(VDX_ERR_INVALID, "order 2 needs hist");
+    if (anc && masked && a.resample_steps < 1) LOOP_FAIL(VDX_ERR_INVALID, "resample_steps must be >= 1");
+    if ((masked || (anc && guided)) && a.timesteps < 1) LOOP_FAIL(VDX_ERR_INVALID, "timesteps (the row length of the tables) must be >= 1");
+    const long chain_len = !anc ? a.seq_len : masked ? (long)a.timesteps * a.resample_steps : a.timesteps;
+    if ((!anc && a.seq_len < 1) || nsteps < 0 || nsteps > chain_len) LOOP_FAIL(VDX_ERR_INVALID, "nsteps out of range");
+    if (dyn && (!a.thres_buf || a.percentile > 1.f)) LOOP_FAIL(VDX_ERR_INVALID, "dynamic threshold needs thres_buf and a percentile in (0, 1]");
+    if (dyn && !anc && (!a.tables || a.timesteps < 1)) LOOP_FAIL(VDX_ERR_INVALID, "dynamic threshold needs tables and timesteps >= 1");
+    // (ddim_step_kernel alone has a scalar form; every other step kernel, and cfg_combine, move four elements per thread)
+    if (per_sample % 4 && (a.chain != CHAIN_DDIM || masked || guided)) LOOP_FAIL(VDX_ERR_INVALID, "C*F*H*W must be a multiple of 4");
+    if (m.out_dim != m.cfg.channels) LOOP_FAIL(VDX_ERR_INVALID, "out_dim must equal channels");
+    if (masked && !masked_aligned(a.img, a.known, a.img, a.mask)) LOOP_FAIL(VDX_ERR_INVALID, "img / known must be 16-byte and mask 4-byte aligned");
+    if (dpm && ((uintptr_t)a.img % 16 || (uintptr_t)a.hist % 16)) LOOP_FAIL(VDX_ERR_INVALID, "img / hist must be 16-byte aligned");
+    if (guided && ((uintptr_t)a.img % 16 || (uintptr_t)a.eps_buf % 16 || (uintptr_t)a.hist % 16 || (uintptr_t)a.cfg_scratch % 8))
+        LOOP_FAIL(VDX_ERR_INVALID, "img / eps_buf / hist must be 16-byte and the cfg scratch 8-byte aligned");
+#undef LOOP_FAIL
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* sd = reinterpret_cast<unsigned long long*>(step_dev);
-    const unsigned char* cond_mask = vdx::cfg_scratch_mask(cfg_scratch, batch);
-    const size_t half_bytes = (size_t)batch * per_sample * sizeof(float);
-    VDX_HIP(vdx::launch_cfg_mask(cfg_scratch, batch, st));
+    unsigned long long* sd = reinterpret_cast<unsigned long long*>(a.step_dev);
+    const int B = a.batch, rows = guided ? 2 * B : B, C = m.cfg.channels;      // rows: what the forward and the advance cover
+    const float* th = dyn ? a.thres_buf : nullptr;
+    const unsigned char* cond_mask = guided ? vdx::cfg_scratch_mask(a.cfg_scratch, B) : nullptr;
+    // (ancestral: one Philox draw per step through step_dev, resampling or not; the sequence chains draw for the known region only)
+    const vdx::MaskArgs ma = {a.known, a.mask, a.mask_tables, anc ? a.resample_steps : 1, 0ull, anc ? sd : nullptr};
+    if (guided) VDX_HIP(vdx::launch_cfg_mask(a.cfg_scratch, B, st));
     auto step = [&]() -> int {
-        // both halves of the batched forward see the same x_t; the null rows never read cond (time_mlp), so cond stays [batch, cond_dim]
-        hipError_t e = hipMemcpyAsync(img + (size_t)batch * per_sample, img, half_bytes, hipMemcpyDeviceToDevice, st);
+        hipError_t e = hipSuccess;
+        // guided: both halves of the batched forward see the same x_t; the null rows never read cond (time_mlp), so cond stays [batch, cond_dim]
+        if (guided) e = hipMemcpyAsync(a.img + (size_t)B * per_sample, a.img, (size_t)B * per_sample * sizeof(float), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
-        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, cond_mask, 0, eps_buf, workspace, workspace_bytes, 2 * batch, st);
+        // reference p_sample_loop never forwards cond (Q10); when a cond tensor is supplied to an unguided loop it is used un-masked
+        int rc = vdx::model_forward(&m, a.params, a.packed, a.img, a.t_dev, a.cond, cond_mask, 0, a.eps_buf, a.workspace, a.workspace_bytes, rows, st);
         if (rc != VDX_OK) return rc;
-        e = vdx::launch_cfg_combine(eps_buf, eps_buf, cond_scale, rescale, cfg_scratch, batch, per_sample, st);
-        if (e == hipSuccess && dyn) e = vdx::launch_dyn_thres(img, eps_buf, t_dev, tables, timesteps, percentile, thres_buf, batch, m.cfg.channels, per_sample, st);
-        const float* th = dyn ? thres_buf : nullptr;
-        if (kind == 0) {
-            vdx::PSampleArgs a;
-            fill_psample(a, img, eps_buf, img, t_dev, tables, timesteps, nullptr, seed, 1, step_dev, th, clip_denoised, m.cfg.channels, per_sample);
-            if (e == hipSuccess) e = vdx::launch_p_sample(a, batch, st);
-            if (e == hipSuccess) e = vdx::launch_advance(t_dev, 2 * batch, sd, st);
+        if (guided) e = vdx::launch_cfg_combine(a.eps_buf, a.eps_buf, a.cond_scale, a.rescale, a.cfg_scratch, B, per_sample, st);
+        if (e == hipSuccess && dyn) e = vdx::launch_dyn_thres(a.img, a.eps_buf, a.t_dev, a.tables, a.timesteps, a.percentile, a.thres_buf, B, C, per_sample, st);
+        if (anc) {
+            const vdx::PSampleArgs pa = psample_args(a.img, a.eps_buf, a.img, a.t_dev, a.tables, a.timesteps, nullptr, a.seed, masked ? 0 : 1,
+                                                     masked ? nullptr : a.step_dev, th, a.clip_denoised, C, per_sample);
+            if (e == hipSuccess) e = masked ? vdx::launch_p_sample_masked(pa, ma, B, st) : vdx::launch_p_sample(pa, B, st);
+            if (e == hipSuccess) e = masked ? vdx::launch_resample_advance(a.t_dev, B, sd, a.resample_steps, st) : vdx::launch_advance(a.t_dev, rows, sd, st);
         } else {
-            if (e == hipSuccess && kind == 1) e = vdx::launch_ddim_step(img, eps_buf, img, alphas_cumprod, seq, sd, th, clip_denoised, batch, m.cfg.channels, per_sample, st);
-            if (e == hipSuccess && kind == 2) e = vdx::launch_dpm_step(img, eps_buf, img, hist, alphas_cumprod, seq, sd, th, clip_denoised, order, batch, m.cfg.channels,
-                                                                       per_sample, nullptr, 0, 0ull, st);
-            if (e == hipSuccess) e = vdx::launch_ddim_advance(t_dev, 2 * batch, seq, sd, st);
+            if (e == hipSuccess && dpm)
+                e = vdx::launch_dpm_step(a.img, a.eps_buf, a.img, a.hist, a.alphas_cumprod, a.seq, sd, th, a.clip_denoised, a.order, B, C, per_sample,
+                                         masked ? &ma : nullptr, a.timesteps, a.seed, st);
+            else if (e == hipSuccess && masked)
+                e = vdx::launch_ddim_step_masked(a.img, a.eps_buf, a.img, a.alphas_cumprod, a.seq, sd, th, a.clip_denoised, B, C, per_sample, ma, a.timesteps, a.seed, st);
+            else if (e == hipSuccess)
+                e = vdx::launch_ddim_step(a.img, a.eps_buf, a.img, a.alphas_cumprod, a.seq, sd, th, a.clip_denoised, B, C, per_sample, st);
+            if (e == hipSuccess) e = vdx::launch_ddim_advance(a.t_dev, rows, a.seq, sd, st);
         }
         if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
         return VDX_OK;
     };
+    // the key: `a` itself (zero-filled, then assigned field by field: loop_args) with what this step does not read set to zero
     vdx_handle::GraphKey key;
     memset(&key, 0, sizeof(key));
-    key.p[0] = params; key.p[1] = packed; key.p[2] = img; key.p[3] = eps_buf; key.p[4] = t_dev; key.p[5] = step_dev;
-    key.p[6] = kind == 0 ? tables : alphas_cumprod; key.p[7] = cond; key.p[8] = workspace; key.p[9] = stream; key.p[10] = seq;
-    key.p[11] = dyn ? (const void*)thres_buf : nullptr; key.p[15] = (dyn && kind != 0) ? (const void*)tables : nullptr; key.p[16] = hist;
-    key.p[17] = cfg_scratch;
-    key.seed = kind == 0 ? seed : 0ull; key.i[0] = kind == 0 ? timesteps : seq_len; key.i[1] = clip_denoised | (h->model.act16 << 8); key.i[2] = batch;
-    key.i[3] = (dyn && kind != 0) ? timesteps : 0; key.i[5] = kind == 2 ? order : 0;
-    key.ws = workspace_bytes; key.f = dyn ? percentile : 0.f;
-    memcpy(&key.cfg[0], &cond_scale, sizeof(float)); memcpy(&key.cfg[1], &rescale, sizeof(float));
-    return run_steps(h, 6 + kind, key, nsteps, use_graph, st, step);
+    memcpy(&key.a, &a, sizeof(a));
+    key.stream = stream; key.act16 = m.act16;
+    LoopArgs& k = key.a;
+    if (!dyn) { k.percentile = 0.f; k.thres_buf = nullptr; }
+    if (anc) { k.alphas_cumprod = nullptr; k.seq = nullptr; k.seq_len = 0; }
+    if (!anc && !dyn) { k.tables = nullptr; if (!masked) k.timesteps = 0; }
+    if (!anc && !masked) k.seed = 0;
+    if (!dpm) { k.hist = nullptr; k.order = 0; }
+    if (!masked) { k.known = nullptr; k.mask = nullptr; k.mask_tables = nullptr; }
+    if (!masked || !anc) k.resample_steps = 0;
+    if (!guided) { k.cond_scale = 0.f; k.rescale = 0.f; k.cfg_scratch = nullptr; }
+    return run_steps(h, 3 * (guided ? 2 : masked ? 1 : 0) + a.chain, key, nsteps, use_graph, st, step);
+}
+
+// what all eleven entries share; the rest of `a` is zero (and so is its padding: the bytes of a LoopArgs are a graph key)
+static void loop_args(LoopArgs& a, int chain, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev, uint64_t* step_dev,
+                      const float* cond, int clip_denoised, float percentile, float* thres_buf, void* workspace, size_t workspace_bytes, int batch) {
+    memset(&a, 0, sizeof(a));
+    a.chain = chain; a.params = params; a.packed = packed; a.img = img; a.eps_buf = eps_buf; a.t_dev = t_dev; a.step_dev = step_dev;
+    a.cond = cond; a.clip_denoised = clip_denoised; a.percentile = percentile; a.thres_buf = thres_buf;
+    a.workspace = workspace; a.workspace_bytes = workspace_bytes; a.batch = batch;
+}
+static void set_sequence(LoopArgs& a, const float* alphas_cumprod, const int* seq, int seq_len, const float* tables, int timesteps) {
+    a.alphas_cumprod = alphas_cumprod; a.seq = seq; a.seq_len = seq_len; a.tables = tables; a.timesteps = timesteps;
+}
+static void set_masked(LoopArgs& a, const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed) {
+    a.masked = 1; a.known = known; a.mask = mask; a.mask_tables = mask_tables; a.seed = seed;
+}
+static void set_guided(LoopArgs& a, float cond_scale, float rescale, double* cfg_scratch) {
+    a.guided = 1; a.cond_scale = cond_scale; a.rescale = rescale; a.cfg_scratch = cfg_scratch;
+}
+
+int vdx_p_sample_loop_dyn(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                          uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                          int clip_denoised, float percentile, float* thres_buf, void* workspace, size_t workspace_bytes, int batch,
+                          int use_graph, void* stream) {
+    LoopArgs a;
+    loop_args(a, CHAIN_ANCESTRAL, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    a.tables = tables; a.timesteps = timesteps; a.seed = seed;
+    return sample_loop("p_sample_loop", h, a, nsteps, use_graph, stream);
+}
+
+int vdx_p_sample_loop(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                      uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                      int clip_denoised, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    return vdx_p_sample_loop_dyn(h, params, packed, img, eps_buf, t_dev, step_dev, tables, timesteps, nsteps, cond, seed, clip_denoised,
+                                 0.f, nullptr, workspace, workspace_bytes, batch, use_graph, stream);
+}
+
+int vdx_p_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                             uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                             int clip_denoised, float percentile, float* thres_buf, const float* known, const unsigned char* mask,
+                             const float* mask_tables, int resample_steps, void* workspace, size_t workspace_bytes, int batch,
+                             int use_graph, void* stream) {
+    LoopArgs a;
+    loop_args(a, CHAIN_ANCESTRAL, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    a.tables = tables; a.timesteps = timesteps; a.resample_steps = resample_steps;
+    set_masked(a, known, mask, mask_tables, seed);
+    return sample_loop("p_sample_loop_masked", h, a, nsteps, use_graph, stream);
 }
 
 int vdx_p_sample_loop_guided(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
                              uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
                              int clip_denoised, float percentile, float* thres_buf, float cond_scale, float rescale, double* cfg_scratch,
                              void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
-    return guided_loop("p_sample_loop_guided", 0, h, params, packed, img, eps_buf, nullptr, t_dev, step_dev, tables, timesteps, nullptr, nullptr, 0,
-                       nsteps, cond, seed, clip_denoised, 0, percentile, thres_buf, cond_scale, rescale, cfg_scratch, workspace, workspace_bytes,
-                       batch, use_graph, stream);
+    LoopArgs a;
+    loop_args(a, CHAIN_ANCESTRAL, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    a.tables = tables; a.timesteps = timesteps; a.seed = seed;
+    set_guided(a, cond_scale, rescale, cfg_scratch);
+    return sample_loop("p_sample_loop_guided", h, a, nsteps, use_graph, stream);
+}
+
+int vdx_ddim_sample_loop_dyn(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                             uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                             int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf, void* workspace,
+                             size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    LoopArgs a;
+    loop_args(a, CHAIN_DDIM, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    set_sequence(a, alphas_cumprod, seq, seq_len, tables, timesteps);
+    return sample_loop("ddim_sample_loop", h, a, nsteps, use_graph, stream);
+}
+
+int vdx_ddim_sample_loop(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                         uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                         int clip_denoised, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    return vdx_ddim_sample_loop_dyn(h, params, packed, img, eps_buf, t_dev, step_dev, alphas_cumprod, seq, seq_len, nsteps, cond, clip_denoised,
+                                    nullptr, 0, 0.f, nullptr, workspace, workspace_bytes, batch, use_graph, stream);
+}
+
+int vdx_ddim_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                                uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                                int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf,
+                                const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
+                                void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    LoopArgs a;
+    loop_args(a, CHAIN_DDIM, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    set_sequence(a, alphas_cumprod, seq, seq_len, tables, timesteps);
+    set_masked(a, known, mask, mask_tables, seed);
+    return sample_loop("ddim_sample_loop_masked", h, a, nsteps, use_graph, stream);
 }
 
 int vdx_ddim_sample_loop_guided(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
@@ -1058,9 +952,35 @@ int vdx_ddim_sample_loop_guided(vdx_handle* h, const float* params, const void* 
                                 int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf, float cond_scale,
                                 float rescale, double* cfg_scratch, void* workspace, size_t workspace_bytes, int batch, int use_graph,
                                 void* stream) {
-    return guided_loop("ddim_sample_loop_guided", 1, h, params, packed, img, eps_buf, nullptr, t_dev, step_dev, tables, timesteps, alphas_cumprod, seq,
-                       seq_len, nsteps, cond, 0, clip_denoised, 0, percentile, thres_buf, cond_scale, rescale, cfg_scratch, workspace,
-                       workspace_bytes, batch, use_graph, stream);
+    LoopArgs a;
+    loop_args(a, CHAIN_DDIM, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    set_sequence(a, alphas_cumprod, seq, seq_len, tables, timesteps);
+    set_guided(a, cond_scale, rescale, cfg_scratch);
+    return sample_loop("ddim_sample_loop_guided", h, a, nsteps, use_graph, stream);
+}
+
+int vdx_dpm_sample_loop(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
+                        uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                        int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
+                        void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    LoopArgs a;
+    loop_args(a, CHAIN_DPM, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    set_sequence(a, alphas_cumprod, seq, seq_len, tables, timesteps);
+    a.hist = hist; a.order = order;
+    return sample_loop("dpm_sample_loop", h, a, nsteps, use_graph, stream);
+}
+
+int vdx_dpm_sample_loop_masked(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
+                               uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                               int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
+                               const float* known, const unsigned char* mask, const float* mask_tables, uint64_t seed,
+                               void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    LoopArgs a;
+    loop_args(a, CHAIN_DPM, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    set_sequence(a, alphas_cumprod, seq, seq_len, tables, timesteps);
+    set_masked(a, known, mask, mask_tables, seed);
+    a.hist = hist; a.order = order;
+    return sample_loop("dpm_sample_loop_masked", h, a, nsteps, use_graph, stream);
 }
 
 int vdx_dpm_sample_loop_guided(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, float* hist, int* t_dev,
@@ -1068,9 +988,12 @@ int vdx_dpm_sample_loop_guided(vdx_handle* h, const float* params, const void* p
                                int clip_denoised, int order, const float* tables, int timesteps, float percentile, float* thres_buf,
                                float cond_scale, float rescale, double* cfg_scratch, void* workspace, size_t workspace_bytes, int batch,
                                int use_graph, void* stream) {
-    return guided_loop("dpm_sample_loop_guided", 2, h, params, packed, img, eps_buf, hist, t_dev, step_dev, tables, timesteps, alphas_cumprod, seq,
-                       seq_len, nsteps, cond, 0, clip_denoised, order, percentile, thres_buf, cond_scale, rescale, cfg_scratch, workspace,
-                       workspace_bytes, batch, use_graph, stream);
+    LoopArgs a;
+    loop_args(a, CHAIN_DPM, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    set_sequence(a, alphas_cumprod, seq, seq_len, tables, timesteps);
+    set_guided(a, cond_scale, rescale, cfg_scratch);
+    a.hist = hist; a.order = order;
+    return sample_loop("dpm_sample_loop_guided", h, a, nsteps, use_graph, stream);
 }
 
 int vdx_pack_conv_weights_t(int mode, const float* kernel, void* packed, int taps, int cin, int cout, void* stream) {

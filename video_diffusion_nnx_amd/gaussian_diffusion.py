@@ -7,6 +7,7 @@ closed-form accessors (q_mean_variance, predict_start_from_noise, q_posterior) a
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -48,6 +49,12 @@ vdx_dpm_sample_loop = L._sig('vdx_dpm_sample_loop', C.c_int, [_vp] * 10 + [C.c_i
                                                              C.c_size_t, C.c_int, C.c_int, _vp])
 vdx_dpm_sample_loop_masked = L._sig('vdx_dpm_sample_loop_masked', C.c_int, [_vp] * 10 + [C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_float]
                                     + [_vp] * 4 + [_u64, _vp, C.c_size_t, C.c_int, C.c_int, _vp])
+
+
+# the eleven loop entry points by (chain, variant); the two without a dynamic threshold are the _dyn ones with percentile 0
+_LOOPS = {('ddpm', 'plain'): vdx_p_sample_loop_dyn, ('ddpm', 'masked'): vdx_p_sample_loop_masked, ('ddpm', 'guided'): L.vdx_p_sample_loop_guided,
+          ('ddim', 'plain'): vdx_ddim_sample_loop_dyn, ('ddim', 'masked'): vdx_ddim_sample_loop_masked, ('ddim', 'guided'): L.vdx_ddim_sample_loop_guided,
+          ('dpm', 'plain'): vdx_dpm_sample_loop, ('dpm', 'masked'): vdx_dpm_sample_loop_masked, ('dpm', 'guided'): L.vdx_dpm_sample_loop_guided}
 
 
 def extend_plan(have: int, num_new: int, num_frames: int, context_frames: int):
@@ -296,109 +303,12 @@ class GaussianDiffusion:
                                   x.shape[0], self.channels, self._per_sample(x), L.stream_ptr()))
         return out
 
-    def _guided_loop(self, kind, unet, shape, seed, cond, cond_scale, guidance_rescale, use_graph, x_T, seq=None, steps=0, order=2):
-        """The classifier-free-guidance loops (EXTENSION, parity unpinned: the reference's p_sample_loop drops cond): kind 'ddpm' | 'ddim' |
-        'dpm' -> vdx_p_sample_loop_guided / vdx_ddim_sample_loop_guided / vdx_dpm_sample_loop_guided on the current stream.  One forward
-        over 2B samples (conditioned | null embedding), vdx_cfg_combine and the unguided step kernel per step, captured in a hipGraph
-        (use_graph) or run eagerly by the same step function.  Returns x_0 [B,C,F,H,W], still in [-1, 1]."""
-        B, T = shape[0], self.num_timesteps
-        per = int(np.prod(shape[1:]))
-        img = torch.empty((2 * B,) + tuple(shape[1:]), dtype=torch.float32, device=self.device)
-        if x_T is None:
-            L.check(vdx_randn(L.ptr(img), B * per, seed, 0, 0, L.stream_ptr()))          # x_T of the B videos: the first half
-        else:
-            img[:B].copy_(self._dev(x_T))
-        condd = self._dev(cond)
-        assert tuple(condd.shape) == (B, unet.cond_dim), f'cond must be [{B}, {unet.cond_dim}], got {tuple(condd.shape)}'
-        h = unet.handle(self.num_frames, self.image_size)
-        unet.apply_activation_storage(h)
-        ws = unet.workspace(2 * B, self.num_frames, self.image_size)
-        eps = torch.empty(2 * B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=self.device)
-        t_dev = torch.full((2 * B,), T - 1 if seq is None else int(seq[0]), dtype=torch.int32, device=self.device)
-        step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-        thres = torch.empty(B, dtype=torch.float32, device=self.device) if self.use_dynamic_thres else None
-        perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
-        scratch = torch.empty(L.vdx_cfg_scratch_doubles(B), dtype=torch.float64, device=self.device)
-        tail = (float(cond_scale), float(guidance_rescale), L.ptr(scratch), L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr())
-        if kind == 'ddpm':
-            L.check(L.vdx_p_sample_loop_guided(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(t_dev),
-                                               L.ptr(step_dev), L.ptr(self._ptab), T, T, L.ptr(condd), seed, 1, perc, L.ptr(thres), *tail))
-        elif kind == 'ddim':
-            seq_dev = torch.from_numpy(seq).to(self.device)
-            L.check(L.vdx_ddim_sample_loop_guided(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(t_dev),
-                                                  L.ptr(step_dev), L.ptr(self.alphas_cumprod), L.ptr(seq_dev), steps, steps, L.ptr(condd), 1,
-                                                  L.ptr(self._ptab), T, perc, L.ptr(thres), *tail))
-        else:
-            seq_dev = torch.from_numpy(seq).to(self.device)
-            hist = torch.empty((B,) + tuple(shape[1:]), dtype=torch.float32, device=self.device)
-            L.check(L.vdx_dpm_sample_loop_guided(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(hist),
-                                                 L.ptr(t_dev), L.ptr(step_dev), L.ptr(self.alphas_cumprod), L.ptr(seq_dev), steps, steps,
-                                                 L.ptr(condd), 1, order, L.ptr(self._ptab), T, perc, L.ptr(thres), *tail))
-        return img[:B]
-
-    def p_sample_loop(self, shape, key, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None,
-                      guidance_rescale: float = 0.0):
-        """reference :264-320.  As there, the caller's spatial `shape` is replaced by the model's own (Q10).
-
-        x_T = Philox(key, draw 0); step k (t = T-1-k) uses draw 1+k.  Returns unnormalize_img(x_0) in [0,1].
-        With cond given and cond_scale != 1 the loop is the guided one (classifier-free guidance: one forward over 2B samples per
-        step, inside the captured step like the unguided loop; _guided_loop) -- an EXTENSION, parity unpinned: the reference drops cond
-        here.  guidance_rescale phi in [0, 1] (extension; Lin et al. 2023, sec. 3.4): the guided eps is scaled per sample by
-        phi std(eps(c)) / std(eps_guided) + 1 - phi; 0 = off.
-        """
-        guidance_rescale = check_guidance_rescale(guidance_rescale)
-        B = int(shape[0])
-        shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
-        seed = int(key) & 0xFFFFFFFFFFFFFFFF
+    # -- the sampling loops ------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _sampling(self):
+        """What every sampling loop runs inside: the side stream (ordered after the current one, and the current one after it on
+        the way out) as the current stream, and the UNet's sampling-time activation storage, put back whatever happens."""
         unet = self.denoise_fn
-        T = self.num_timesteps
-        if self._sample_stream is None:
-            self._sample_stream = torch.cuda.Stream(device=self.device)
-        cur = torch.cuda.current_stream(self.device)
-        st = self._sample_stream
-        st.wait_stream(cur)
-        keep_storage = unet.act_bf16
-        unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
-        try:
-            out = self._p_sample_loop_on(st, unet, shape, B, T, seed, cond, cond_scale, use_graph, x_T, guidance_rescale)
-        finally:
-            unet.act_bf16 = keep_storage
-        cur.wait_stream(st)
-        return out
-
-    def _p_sample_loop_on(self, st, unet, shape, B, T, seed, cond, cond_scale, use_graph, x_T, guidance_rescale=0.0):
-        with torch.cuda.stream(st):
-            guided = cond is not None and unet.has_cond and cond_scale != 1
-            if guided:
-                img = self._guided_loop('ddpm', unet, shape, seed, cond, cond_scale, guidance_rescale, use_graph, x_T)
-            else:
-                img = self.randn(shape, seed, 0) if x_T is None else self._dev(x_T).clone()
-                condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
-                h = unet.handle(self.num_frames, self.image_size)
-                unet.apply_activation_storage(h)
-                ws = unet.workspace(B, self.num_frames, self.image_size)
-                eps = torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=self.device)
-                t_dev = torch.full((B,), T - 1, dtype=torch.int32, device=self.device)
-                step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-                thres = torch.empty(B, dtype=torch.float32, device=self.device) if self.use_dynamic_thres else None
-                L.check(vdx_p_sample_loop_dyn(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(t_dev),
-                                              L.ptr(step_dev), L.ptr(self._ptab), T, T, L.ptr(condd), seed, 1,
-                                              float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0, L.ptr(thres),
-                                              L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
-            out = torch.empty_like(img)
-            L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
-        return out
-
-    def ddim_sample_loop(self, shape, key, steps: int = 100, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None,
-                         guidance_rescale: float = 0.0):
-        """DDIM sampling with eta = 0 in `steps` network evaluations (EXTENSION, BASELINE.json configs[3]; the reference has ancestral
-        sampling only).  x_T = Philox(key, draw 0), deterministic afterwards.  Returns unnormalize_img(x_0) in [0, 1].  cond with
-        cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
-        guidance_rescale = check_guidance_rescale(guidance_rescale)
-        B = int(shape[0])
-        shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
-        unet = self.denoise_fn
-        seq_host = ddim_time_sequence(self.num_timesteps, steps)
         if self._sample_stream is None:
             self._sample_stream = torch.cuda.Stream(device=self.device)
         cur, st = torch.cuda.current_stream(self.device), self._sample_stream
@@ -407,32 +317,150 @@ class GaussianDiffusion:
         unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
         try:
             with torch.cuda.stream(st):
-                guided = cond is not None and unet.has_cond and cond_scale != 1
-                if guided:
-                    img = self._guided_loop('ddim', unet, shape, int(key) & 0xFFFFFFFFFFFFFFFF, cond, cond_scale, guidance_rescale, use_graph, x_T,
-                                            seq=seq_host, steps=int(steps))
-                else:
-                    img = self.randn(shape, int(key) & 0xFFFFFFFFFFFFFFFF, 0) if x_T is None else self._dev(x_T).clone()
-                    seq = torch.from_numpy(seq_host).to(self.device)
-                    condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
-                    h = unet.handle(self.num_frames, self.image_size)
-                    unet.apply_activation_storage(h)
-                    ws = unet.workspace(B, self.num_frames, self.image_size)
-                    eps = torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=self.device)
-                    t_dev = torch.full((B,), int(seq_host[0]), dtype=torch.int32, device=self.device)
-                    step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-                    thres = torch.empty(B, dtype=torch.float32, device=self.device) if self.use_dynamic_thres else None
-                    L.check(vdx_ddim_sample_loop_dyn(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(t_dev),
-                                                     L.ptr(step_dev), L.ptr(self.alphas_cumprod), L.ptr(seq), steps, steps, L.ptr(condd), 1,
-                                                     L.ptr(self._ptab), self.num_timesteps,
-                                                     float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0, L.ptr(thres),
-                                                     L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
-                out = torch.empty_like(img)
-                L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
+                yield
         finally:
             unet.act_bf16 = keep_storage
         cur.wait_stream(st)
+
+    def _run_chain(self, chain, B, key, *, steps=0, order=2, cond=None, cond_scale=1.0, guidance_rescale=0.0, use_graph=True, x_T=None,
+                   masked=None):
+        """One whole chain on the current stream (inside _sampling()): chain 'ddpm' (the T-step ancestral one) | 'ddim' | 'dpm' (the
+        two over ddim_time_sequence(T, steps)), as the plain, the masked or the guided variant -> the vdx_*_sample_loop* entry of
+        _LOOPS, captured in a hipGraph (use_graph) or run eagerly by the same step function.  x_T = Philox(key, draw 0) unless given.
+        Guided (cond given, the network has a condition, cond_scale != 1; classifier-free guidance, EXTENSION, parity unpinned: the
+        reference's p_sample_loop drops cond): one forward over 2B samples (conditioned | null embedding) per step, so img / eps /
+        t hold 2B rows and the first B are the result.  masked = (video, element mask, mask table, resample_steps): the loop of
+        inpaint() on the persistent _inpaint_bufs; masked and guided together run eagerly (_masked_guided_steps).
+        Returns unnormalize_img(x_0) [B,C,F,H,W] in [0, 1]."""
+        unet, T, dev = self.denoise_fn, self.num_timesteps, self.device
+        seed = int(key) & 0xFFFFFFFFFFFFFFFF
+        shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
+        guided = cond is not None and unet.has_cond and cond_scale != 1
+        seq_host = None if chain == 'ddpm' else ddim_time_sequence(T, steps)
+        t0 = T - 1 if seq_host is None else int(seq_host[0])
+        rows = 2 * B if guided and masked is None else B           # what the forward covers
+        perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
+        if masked is not None:
+            video, m, mtab, U = masked
+            buf = self._inpaint_bufs(B, steps)
+            img, known, mk = buf['img'], buf['known'], buf['mask']
+            if x_T is None:
+                L.check(vdx_randn(L.ptr(img), img.numel(), seed, 0, 0, L.stream_ptr()))
+            else:
+                img.copy_(self._dev(x_T))
+            vd = self._dev(video)
+            L.check(vdx_affine(L.ptr(vd), L.ptr(known), img.numel(), 2.0, -1.0, L.stream_ptr()))      # normalize_img
+            mk.copy_(m)
+            L.check(vdx_inpaint_init(L.ptr(img), L.ptr(known), L.ptr(mk), L.ptr(mtab), T, t0, img.numel(), L.stream_ptr()))
+            if chain == 'dpm' and 'hist' not in buf:
+                buf['hist'] = torch.empty_like(img)
+            eps, hist, t_dev, step_dev, seq = buf['eps'], buf.get('hist'), buf['t'], buf['step'], buf['seq']
+            thres = buf['thres'] if self.use_dynamic_thres else None
+            variant = 'masked', (L.ptr(known), L.ptr(mk), L.ptr(mtab), U if chain == 'ddpm' else seed)
+        else:
+            if guided:
+                img = torch.empty((rows,) + shape[1:], dtype=torch.float32, device=dev)
+                if x_T is None:
+                    L.check(vdx_randn(L.ptr(img), img.numel() // 2, seed, 0, 0, L.stream_ptr()))      # x_T of the B videos: the first half
+                else:
+                    img[:B].copy_(self._dev(x_T))
+            else:
+                img = self.randn(shape, seed, 0) if x_T is None else self._dev(x_T).clone()
+            hist = torch.empty(shape, dtype=torch.float32, device=dev) if chain == 'dpm' else None
+            seq = None if seq_host is None else torch.from_numpy(seq_host).to(dev)
+            eps = torch.empty(rows, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=dev)
+            t_dev = torch.empty(rows, dtype=torch.int32, device=dev)
+            step_dev = torch.empty(1, dtype=torch.int64, device=dev)
+            thres = torch.empty(B, dtype=torch.float32, device=dev) if self.use_dynamic_thres else None
+            variant = 'plain', ()
+        if guided and masked is not None:
+            self._masked_guided_steps(chain, buf, seq_host, cond, cond_scale, order, U, mtab, seed)
+        else:
+            if guided:
+                condd = self._dev(cond)
+                assert tuple(condd.shape) == (B, unet.cond_dim), f'cond must be [{B}, {unet.cond_dim}], got {tuple(condd.shape)}'
+                scratch = torch.empty(L.vdx_cfg_scratch_doubles(B), dtype=torch.float64, device=dev)
+                variant = 'guided', (float(cond_scale), float(guidance_rescale), L.ptr(scratch))
+            else:
+                condd = None if (cond is None or not unet.has_cond) else self._dev(cond)      # used un-masked (the reference drops it, Q10)
+            h = unet.handle(self.num_frames, self.image_size)
+            unet.apply_activation_storage(h)
+            ws = unet.workspace(rows, self.num_frames, self.image_size)
+            t_dev.fill_(t0)
+            step_dev.zero_()
+            head = (h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps)) + ((L.ptr(hist),) if chain == 'dpm' else ()) \
+                + (L.ptr(t_dev), L.ptr(step_dev))
+            if chain == 'ddpm':
+                n = T * U if masked is not None else T
+                body = (L.ptr(self._ptab), T, n, L.ptr(condd), seed, 1, perc, L.ptr(thres))
+            else:
+                body = (L.ptr(self.alphas_cumprod), L.ptr(seq), steps, steps, L.ptr(condd), 1) + ((order,) if chain == 'dpm' else ()) \
+                    + (L.ptr(self._ptab), T, perc, L.ptr(thres))
+            L.check(_LOOPS[chain, variant[0]](*head, *body, *variant[1], L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
+        img = img[:B]
+        out = torch.empty_like(img)
+        L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
         return out
+
+    def _masked_guided_steps(self, chain, buf, seq_host, cond, cond_scale, order, U, mtab, seed):
+        """The masked chain under guidance, in place on buf['img']: two forwards per step (forward_with_cond_scale) and the masked step
+        kernels, eagerly, with the step numbering of the captured loops."""
+        unet, T = self.denoise_fn, self.num_timesteps
+        img, known, mk = buf['img'], buf['known'], buf['mask']
+        B, per = img.shape[0], self._per_sample(img)
+
+        def eps_and_thres(t):
+            eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
+            return eps_hat, (self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None)
+
+        if chain == 'ddpm':
+            s = 0
+            for i in reversed(range(T)):
+                t = torch.full((B,), i, dtype=torch.int32, device=self.device)
+                for _ in range(U):
+                    eps_hat, th = eps_and_thres(t)
+                    L.check(vdx_p_sample_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(t), L.ptr(self._ptab), T, L.ptr(known),
+                                                     L.ptr(mk), L.ptr(mtab), U, seed, s, 0, L.ptr(th), 1, B, self.channels, per, L.stream_ptr()))
+                    s += 1
+            return
+        for j in range(len(seq_host) - 1):
+            t = torch.full((B,), int(seq_host[j]), dtype=torch.int32, device=self.device)
+            eps_hat, th = eps_and_thres(t)
+            buf['step'].fill_(j)
+            if chain == 'dpm':
+                L.check(vdx_dpm_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(buf['hist']), L.ptr(self.alphas_cumprod),
+                                            L.ptr(buf['seq']), L.ptr(buf['step']), L.ptr(th), 1, order, L.ptr(known), L.ptr(mk),
+                                            L.ptr(mtab), T, seed, B, self.channels, per, L.stream_ptr()))
+            else:
+                L.check(vdx_ddim_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']),
+                                             L.ptr(buf['step']), L.ptr(th), 1, L.ptr(known), L.ptr(mk), L.ptr(mtab), T, seed,
+                                             B, self.channels, per, L.stream_ptr()))
+
+    def p_sample_loop(self, shape, key, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None,
+                      guidance_rescale: float = 0.0):
+        """reference :264-320.  As there, the caller's spatial `shape` is replaced by the model's own (Q10).
+
+        x_T = Philox(key, draw 0); step k (t = T-1-k) uses draw 1+k.  Returns unnormalize_img(x_0) in [0,1].
+        With cond given and cond_scale != 1 the loop is the guided one (classifier-free guidance: one forward over 2B samples per
+        step, inside the captured step like the unguided loop; _run_chain) -- an EXTENSION, parity unpinned: the reference drops cond
+        here.  guidance_rescale phi in [0, 1] (extension; Lin et al. 2023, sec. 3.4): the guided eps is scaled per sample by
+        phi std(eps(c)) / std(eps_guided) + 1 - phi; 0 = off.
+        """
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        with self._sampling():
+            return self._run_chain('ddpm', int(shape[0]), key, cond=cond, cond_scale=cond_scale, guidance_rescale=guidance_rescale,
+                                   use_graph=use_graph, x_T=x_T)
+
+    def ddim_sample_loop(self, shape, key, steps: int = 100, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None,
+                         guidance_rescale: float = 0.0):
+        """DDIM sampling with eta = 0 in `steps` network evaluations (EXTENSION, BASELINE.json configs[3]; the reference has ancestral
+        sampling only).  x_T = Philox(key, draw 0), deterministic afterwards.  Returns unnormalize_img(x_0) in [0, 1].  cond with
+        cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
+        ddim_time_sequence(self.num_timesteps, steps)                     # (its range check, before any device work)
+        with self._sampling():
+            return self._run_chain('ddim', int(shape[0]), key, steps=int(steps), cond=cond, cond_scale=cond_scale,
+                                   guidance_rescale=guidance_rescale, use_graph=use_graph, x_T=x_T)
 
     def dpm_sample_loop(self, shape, key, steps: int = 20, order: int = 2, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True,
                         x_T=None, guidance_rescale: float = 0.0):
@@ -442,46 +470,20 @@ class GaussianDiffusion:
         unnormalize_img(x_0) in [0, 1].  cond with cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
         check_dpm_args(self.num_timesteps, steps, order)
         guidance_rescale = check_guidance_rescale(guidance_rescale)
-        steps = int(steps)
-        B = int(shape[0])
-        shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
-        unet = self.denoise_fn
-        seq_host = ddim_time_sequence(self.num_timesteps, steps)
-        if self._sample_stream is None:
-            self._sample_stream = torch.cuda.Stream(device=self.device)
-        cur, st = torch.cuda.current_stream(self.device), self._sample_stream
-        st.wait_stream(cur)
-        keep_storage = unet.act_bf16
-        unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
-        try:
-            with torch.cuda.stream(st):
-                guided = cond is not None and unet.has_cond and cond_scale != 1
-                if guided:
-                    img = self._guided_loop('dpm', unet, shape, int(key) & 0xFFFFFFFFFFFFFFFF, cond, cond_scale, guidance_rescale, use_graph, x_T,
-                                            seq=seq_host, steps=steps, order=order)
-                else:
-                    img = self.randn(shape, int(key) & 0xFFFFFFFFFFFFFFFF, 0) if x_T is None else self._dev(x_T).clone()
-                    hist = torch.empty_like(img)
-                    seq = torch.from_numpy(seq_host).to(self.device)
-                    condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
-                    h = unet.handle(self.num_frames, self.image_size)
-                    unet.apply_activation_storage(h)
-                    ws = unet.workspace(B, self.num_frames, self.image_size)
-                    eps = torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=self.device)
-                    t_dev = torch.full((B,), int(seq_host[0]), dtype=torch.int32, device=self.device)
-                    step_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
-                    thres = torch.empty(B, dtype=torch.float32, device=self.device) if self.use_dynamic_thres else None
-                    L.check(vdx_dpm_sample_loop(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps), L.ptr(hist), L.ptr(t_dev),
-                                                L.ptr(step_dev), L.ptr(self.alphas_cumprod), L.ptr(seq), steps, steps, L.ptr(condd), 1, order,
-                                                L.ptr(self._ptab), self.num_timesteps,
-                                                float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0, L.ptr(thres),
-                                                L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
-                out = torch.empty_like(img)
-                L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
-        finally:
-            unet.act_bf16 = keep_storage
-        cur.wait_stream(st)
-        return out
+        with self._sampling():
+            return self._run_chain('dpm', int(shape[0]), key, steps=int(steps), order=order, cond=cond, cond_scale=cond_scale,
+                                   guidance_rescale=guidance_rescale, use_graph=use_graph, x_T=x_T)
+
+    @staticmethod
+    def _shard(key, batch, *tensors):
+        """This rank's share of a data-parallel sampling batch: (key, batch, *tensors) with the rank's rows of every tensor that is not
+        None and its own Philox stream shard_key(key, rank); outside a group (one rank) everything as given."""
+        rank, world = dist_rank_world()
+        if world == 1:
+            return (key, batch) + tensors
+        assert batch % world == 0, 'batch_size must be divisible by number of devices'      # as reference trainer.py:163
+        per = batch // world
+        return (shard_key(key, rank, world), per) + tuple(None if t is None else t[rank * per:(rank + 1) * per] for t in tensors)
 
     def sample(self, key, cond=None, cond_scale: float = 1.0, batch_size: int = 16, *, ddim_steps: Optional[int] = None,
                dpm_steps: Optional[int] = None, dpm_order: int = 2, guidance_rescale: float = 0.0, **kw):
@@ -500,13 +502,7 @@ class GaussianDiffusion:
                                       'pass a ready [B, 768] tensor instead')
         if cond is not None:
             batch_size = cond.shape[0]
-        rank, world = dist_rank_world()
-        if world > 1:
-            assert batch_size % world == 0, 'batch_size must be divisible by number of devices'      # as reference trainer.py:163
-            per = batch_size // world
-            batch_size, key = per, shard_key(key, rank, world)
-            if cond is not None:
-                cond = cond[rank * per:(rank + 1) * per]
+        key, batch_size, cond = self._shard(key, batch_size, cond)
         shape = (batch_size, self.channels, self.num_frames, self.image_size, self.image_size)
         if dpm_steps is not None:
             return self.dpm_sample_loop(shape, key, steps=int(dpm_steps), order=dpm_order, cond=cond, cond_scale=cond_scale, **kw)
@@ -527,32 +523,33 @@ class GaussianDiffusion:
         clean_context=True is for a denoiser trained with frame conditioning (Trainer.frame_cond_max > 0; RaMViD, Hoeppe et al. 2022):
         the known region is `video` itself, un-noised, in the start tensor and after every step of all three chains (the same kernels
         with the (1, 0) mask table, vdx.h), as such a network saw its context frames in training.  Not with resample_steps > 1."""
-        shape = self._check_inpaint(video, ddim_steps, resample_steps, x_T, dpm_steps, dpm_order, clean_context)
-        m = frame_mask(mask, shape)
-        rank, world = dist_rank_world()
-        if world > 1:
-            assert shape[0] % world == 0, 'batch_size must be divisible by number of devices'
-            rows = slice(rank * shape[0] // world, (rank + 1) * shape[0] // world)
-            video, m, key = video[rows], m[rows], shard_key(key, rank, world)
-            cond = None if cond is None else cond[rows]
-            x_T = None if x_T is None else x_T[rows]
-        return self._inpaint_local(key, video, m, cond, cond_scale, ddim_steps, int(resample_steps), use_graph, x_T, dpm_steps, dpm_order,
-                                   bool(clean_context))
+        opts = self._inpaint_options(video, dict(cond_scale=cond_scale, ddim_steps=ddim_steps, resample_steps=resample_steps, use_graph=use_graph,
+                                                 x_T=x_T, dpm_steps=dpm_steps, dpm_order=dpm_order, clean_context=clean_context))
+        m = frame_mask(mask, tuple(video.shape))
+        key, _, video, m, cond, opts['x_T'] = self._shard(key, video.shape[0], video, m, cond, x_T)
+        return self._inpaint_local(key, video, m, cond, **opts)
 
-    def _check_inpaint(self, video, ddim_steps, resample_steps, x_T, dpm_steps=None, dpm_order=2, clean_context=False):
-        if int(resample_steps) < 1:
-            raise ValueError(f'resample_steps must be >= 1, got {resample_steps}')
-        if clean_context and int(resample_steps) > 1:
+    def _inpaint_options(self, video, kw):
+        """The sampler options of inpaint() / extend() out of the keywords `kw`, resolved and checked once, before any device work:
+        the keywords of _inpaint_local.  `video`: a tensor of the shape one call of the loop works on."""
+        o = dict(cond_scale=kw.get('cond_scale', 1.0), use_graph=kw.get('use_graph', True), x_T=kw.get('x_T'),
+                 resample_steps=kw.get('resample_steps', 1), dpm_order=kw.get('dpm_order', 2), clean_context=bool(kw.get('clean_context', False)))
+        ddim_steps, dpm_steps = kw.get('ddim_steps'), kw.get('dpm_steps')
+        if int(o['resample_steps']) < 1:
+            raise ValueError(f"resample_steps must be >= 1, got {o['resample_steps']}")
+        if o['clean_context'] and int(o['resample_steps']) > 1:
             raise ValueError('clean_context keeps the known frames un-noised; resampling (resample_steps > 1) re-noises the whole tensor')
-        check_dpm_args(self.num_timesteps, dpm_steps, dpm_order, ddim_steps, resample_steps)
-        if ddim_steps and int(resample_steps) > 1:
+        check_dpm_args(self.num_timesteps, dpm_steps, o['dpm_order'], ddim_steps, o['resample_steps'])
+        if ddim_steps and int(o['resample_steps']) > 1:
             raise ValueError('resampling (resample_steps > 1) is defined for the ancestral chain only, not with ddim_steps')
         shape = tuple(video.shape)
         if len(shape) != 5 or shape[1:] != (self.channels, self.num_frames, self.image_size, self.image_size):
             raise ValueError(f'video must be [B, {self.channels}, {self.num_frames}, {self.image_size}, {self.image_size}], got {shape}')
-        if x_T is not None and tuple(x_T.shape) != shape:
-            raise ValueError(f'x_T must have the shape of video {shape}, got {tuple(x_T.shape)}')
-        return shape
+        if o['x_T'] is not None and tuple(o['x_T'].shape) != shape:
+            raise ValueError(f"x_T must have the shape of video {shape}, got {tuple(o['x_T'].shape)}")
+        o['resample_steps'] = int(o['resample_steps'])
+        o['chain'], o['steps'] = ('dpm', int(dpm_steps)) if dpm_steps is not None else ('ddim', int(ddim_steps)) if ddim_steps else ('ddpm', 0)
+        return o
 
     def _inpaint_bufs(self, B, steps):
         """Device buffers of the masked loops, kept across calls of the same batch size: the captured step bakes their addresses
@@ -570,96 +567,12 @@ class GaussianDiffusion:
             self._ibuf_key = key
         return self._ibuf
 
-    def _inpaint_local(self, key, video, m, cond, cond_scale, ddim_steps, U, use_graph, x_T, dpm_steps=None, dpm_order=2,
-                       clean_context=False):
-        seed = int(key) & 0xFFFFFFFFFFFFFFFF
+    def _inpaint_local(self, key, video, m, cond, *, chain, steps, cond_scale, resample_steps, use_graph, x_T, dpm_order, clean_context):
+        """inpaint() on this rank's rows, with the options of _inpaint_options."""
         mtab = self._mtab_clean if clean_context else self._mtab      # (1, 0) rows: the known region is `known` at every level
-        B = video.shape[0]
-        dpm = dpm_steps is not None                      # S-step chain over ddim_time_sequence with the DPM-Solver++ step
-        S = int(dpm_steps) if dpm else int(ddim_steps) if ddim_steps else 0
-        unet = self.denoise_fn
-        T = self.num_timesteps
-        if self._sample_stream is None:
-            self._sample_stream = torch.cuda.Stream(device=self.device)
-        cur, st = torch.cuda.current_stream(self.device), self._sample_stream
-        st.wait_stream(cur)
-        keep_storage = unet.act_bf16
-        unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
-        try:
-            with torch.cuda.stream(st):
-                buf = self._inpaint_bufs(B, S)
-                img, known, mk = buf['img'], buf['known'], buf['mask']
-                n, per = img.numel(), self._per_sample(img)
-                if x_T is None:
-                    L.check(vdx_randn(L.ptr(img), n, seed, 0, 0, L.stream_ptr()))
-                else:
-                    img.copy_(self._dev(x_T))
-                vd = self._dev(video)
-                L.check(vdx_affine(L.ptr(vd), L.ptr(known), n, 2.0, -1.0, L.stream_ptr()))      # normalize_img
-                mk.copy_(m)
-                seq_host = ddim_time_sequence(T, S) if S else None
-                t0 = int(seq_host[0]) if S else T - 1
-                L.check(vdx_inpaint_init(L.ptr(img), L.ptr(known), L.ptr(mk), L.ptr(mtab), T, t0, n, L.stream_ptr()))
-                guided = cond is not None and unet.has_cond and cond_scale != 1
-                thres = buf['thres'] if self.use_dynamic_thres else None
-                perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
-                if dpm and 'hist' not in buf:
-                    buf['hist'] = torch.empty_like(img)
-                if guided:                                   # two forwards per step: eager, with the numbering of the captured loops
-                    if S:
-                        for j in range(S):
-                            t = torch.full((B,), int(seq_host[j]), dtype=torch.int32, device=self.device)
-                            eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
-                            buf['step'].fill_(j)
-                            th = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
-                            if dpm:
-                                L.check(vdx_dpm_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(buf['hist']), L.ptr(self.alphas_cumprod),
-                                                            L.ptr(buf['seq']), L.ptr(buf['step']), L.ptr(th), 1, dpm_order, L.ptr(known), L.ptr(mk),
-                                                            L.ptr(mtab), T, seed, B, self.channels, per, L.stream_ptr()))
-                            else:
-                                L.check(vdx_ddim_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']),
-                                                             L.ptr(buf['step']), L.ptr(th), 1, L.ptr(known), L.ptr(mk), L.ptr(mtab), T, seed,
-                                                             B, self.channels, per, L.stream_ptr()))
-                    else:
-                        s = 0
-                        for i in reversed(range(T)):
-                            t = torch.full((B,), i, dtype=torch.int32, device=self.device)
-                            for _ in range(U):
-                                eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
-                                th = self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None
-                                L.check(vdx_p_sample_step_masked(L.ptr(img), L.ptr(eps_hat), L.ptr(img), L.ptr(t), L.ptr(self._ptab), T, L.ptr(known),
-                                                                 L.ptr(mk), L.ptr(mtab), U, seed, s, 0, L.ptr(th), 1, B, self.channels, per,
-                                                                 L.stream_ptr()))
-                                s += 1
-                else:
-                    condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
-                    h = unet.handle(self.num_frames, self.image_size)
-                    unet.apply_activation_storage(h)
-                    ws = unet.workspace(B, self.num_frames, self.image_size)
-                    buf['t'].fill_(t0)
-                    buf['step'].zero_()
-                    if dpm:
-                        L.check(vdx_dpm_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
-                                                           L.ptr(buf['hist']), L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self.alphas_cumprod),
-                                                           L.ptr(buf['seq']), S, S, L.ptr(condd), 1, dpm_order, L.ptr(self._ptab), T, perc, L.ptr(thres),
-                                                           L.ptr(known), L.ptr(mk), L.ptr(mtab), seed, L.ptr(ws), ws.numel(), B, int(use_graph),
-                                                           L.stream_ptr()))
-                    elif S:
-                        L.check(vdx_ddim_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
-                                                            L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self.alphas_cumprod), L.ptr(buf['seq']), S, S,
-                                                            L.ptr(condd), 1, L.ptr(self._ptab), T, perc, L.ptr(thres), L.ptr(known), L.ptr(mk),
-                                                            L.ptr(mtab), seed, L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
-                    else:
-                        L.check(vdx_p_sample_loop_masked(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(buf['eps']),
-                                                         L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(self._ptab), T, T * U, L.ptr(condd), seed, 1,
-                                                         perc, L.ptr(thres), L.ptr(known), L.ptr(mk), L.ptr(mtab), U, L.ptr(ws), ws.numel(),
-                                                         B, int(use_graph), L.stream_ptr()))
-                out = torch.empty_like(img)
-                L.check(vdx_affine(L.ptr(img), L.ptr(out), n, 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
-        finally:
-            unet.act_bf16 = keep_storage
-        cur.wait_stream(st)
-        return out
+        with self._sampling():
+            return self._run_chain(chain, video.shape[0], key, steps=steps, order=dpm_order, cond=cond, cond_scale=cond_scale,
+                                   use_graph=use_graph, x_T=x_T, masked=(video, m, mtab, resample_steps))
 
     def extend(self, key, video, num_new_frames: int, *, context_frames: Optional[int] = None, **inpaint_kw):
         """Grow `video` ([B,C,F0,H,W] in [0,1], any F0 >= 1) by `num_new_frames` frames, autoregressively (EXTENSION): window w
@@ -672,31 +585,21 @@ class GaussianDiffusion:
         if video.dim() != 5 or tuple(video.shape[1:2] + video.shape[3:]) != (self.channels, self.image_size, self.image_size):
             raise ValueError(f'video must be [B, {self.channels}, F, {self.image_size}, {self.image_size}], got {tuple(video.shape)}')
         plan = extend_plan(video.shape[2], int(num_new_frames), self.num_frames, ctx)
-        if plan:
-            probe = video.new_zeros((video.shape[0], self.channels, self.num_frames, self.image_size, self.image_size))
-            self._check_inpaint(probe, inpaint_kw.get('ddim_steps'), inpaint_kw.get('resample_steps', 1), inpaint_kw.get('x_T'),
-                                inpaint_kw.get('dpm_steps'), inpaint_kw.get('dpm_order', 2), inpaint_kw.get('clean_context', False))
-        rank, world = dist_rank_world()
-        cond = inpaint_kw.pop('cond', None)
-        if world > 1:
-            assert video.shape[0] % world == 0, 'batch_size must be divisible by number of devices'
-            rows = slice(rank * video.shape[0] // world, (rank + 1) * video.shape[0] // world)
-            video, key = video[rows], shard_key(key, rank, world)
-            cond = None if cond is None else cond[rows]
+        # (a keyword inpaint() does not have is ignored here, as it always was; with nothing to generate nothing is checked either)
+        opts = self._inpaint_options(video.new_zeros((video.shape[0], self.channels, self.num_frames, self.image_size, self.image_size)),
+                                     inpaint_kw) if plan else None
+        key, _, video, cond = self._shard(key, video.shape[0], video, inpaint_kw.get('cond'))
         video = self._dev(video)
         B, F0 = video.shape[0], video.shape[2]
         clip = torch.empty(B, self.channels, F0 + int(num_new_frames), self.image_size, self.image_size, device=self.device)
         clip[:, :, :F0] = video
         window = torch.zeros(B, self.channels, self.num_frames, self.image_size, self.image_size, device=self.device)
-        ddim_steps, U = inpaint_kw.pop('ddim_steps', None), int(inpaint_kw.pop('resample_steps', 1))
-        dpm_steps, dpm_order = inpaint_kw.pop('dpm_steps', None), inpaint_kw.pop('dpm_order', 2)
         have = F0
         for (c, n), k in zip(plan, split_key(key, len(plan))):
             window[:, :, :c] = clip[:, :, have - c:have]
             frames = torch.arange(self.num_frames, device=self.device) < c
             m = frame_mask(frames, tuple(window.shape))
-            out = self._inpaint_local(k, window, m, cond, inpaint_kw.get('cond_scale', 1.0), ddim_steps, U, inpaint_kw.get('use_graph', True),
-                                      inpaint_kw.get('x_T'), dpm_steps, dpm_order, bool(inpaint_kw.get('clean_context', False)))
+            out = self._inpaint_local(k, window, m, cond, **opts)
             clip[:, :, have:have + n] = out[:, :, c:c + n]
             have += n
         return clip
