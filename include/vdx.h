@@ -173,6 +173,23 @@ int vdx_attention_forward_bias(int mode, const void* x, void* y, int io_bf16, co
                                const void* wo_packed, const float* bo, const float* bias, int batch, int frames, int h, int w, int c,
                                int heads, int temporal, void* stream);
 
+/* The attention block with the per-sample focus-present mask, as the network runs the temporal blocks of downs / mid / ups under
+ * vdx_set_focus_present(mode 2): focus_dev is device memory, focus_n bytes; sequence s belongs to sample s / (h * w) when temporal (s itself
+ * otherwise) and reads focus_dev[sample % focus_n].  A set byte masks every score of the sample with key != query to -1e30 -- after the bias,
+ * in the place of the key mask -- so each of its tokens attends to itself only: the softmax row is exactly one-hot and the block's output
+ * for that sample is x + bo + Wo . rd(Wv x + bv) (rd: the mode's operand rounding).  bias_or_null: as in vdx_attention_forward_bias, or null
+ * for no bias.  Unmasked samples are bit-equal to vdx_attention_forward_bias on the same inputs.  Always the generic fused kernels. */
+int vdx_attention_forward_focus(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                                const void* wo_packed, const float* bo, const float* bias_or_null, const unsigned char* focus_dev, int focus_n,
+                                int batch, int frames, int h, int w, int c, int heads, int temporal, void* stream);
+
+/* The block of a batch in which EVERY sample is focus-present (vdx_set_focus_present(mode 1)): y = x + bo + Wo . rd(Wv x + bv) in one launch
+ * of attention_present_kernel -- pointwise over the token rows, reads only the v rows of wqkv_packed; no q, no k, no scores.
+ * C % 4 == 0 (8 for bf16 tensors), C <= 1024; any number of tokens. */
+int vdx_attention_present_forward(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                                  const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads, int temporal,
+                                  void* stream);
+
 /* SpatialLinearAttention + residual (reference: modules.py:64-129 inside Residual(PreNorm(..)), unet3d.py:170-178).
  * heads must be 8, head dim 32.  wq/wk/wv_packed: packed [C,256]; wo_packed: packed [256,C].
  * workspace: vdx_sla_workspace_bytes(mode, batch*frames, h*w, heads). */
@@ -313,6 +330,24 @@ int vdx_get_attention_fp8(const vdx_handle* h);
  * stage scatters it to the embedding's gradient).  VDX_ERR_STATE together with fp8 attention, VDX_ERR_INVALID for more than 64 frames. */
 int vdx_set_temporal_pos_bias(vdx_handle* h, int on, const int* buckets);
 int vdx_get_temporal_pos_bias(const vdx_handle* h);
+
+/* Focus-present mask: joint image-video training and "image mode" sampling (Video Diffusion Models, Ho et al. 2022, section 3.1; reference:
+ * the focus_present_mask keyword that PreNorm drops; DESIGN.md 9: an extension, parity unpinned).  A focus-present sample is
+ * treated as a bag of images: in the nine temporal attention blocks of downs, mid and ups every frame attends to itself only.  The mask
+ * is applied BEFORE the softmax (scores with key != query become -1e30, after the position bias when that is on), so the softmax row is
+ * exactly one-hot; the reference's dead code would mask after it.  init_temporal_attn and the mid spatial attention are never masked.
+ * GroupNorm statistics span the frames, so the frames of a masked sample are still not independent of each other.
+ *   mode 0: off (default): bit for bit and launch for launch what the handle did before.
+ *   mode 1: every sample.  The forward runs attention_present_kernel (one launch per block); the backward the masked generic cores.
+ *   mode 2: per sample.  mask_dev is the CALLER's device pointer to n bytes; it is stored, not copied, and read when the kernels run: its
+ *           contents may change between calls (and between replays of a captured sampling graph) without a new call.  Row r of a forward,
+ *           backward or sampling loop reads mask_dev[r % n] (a guided 2B-row forward works with a [B] mask); a batch that is no multiple
+ *           of n fails with VDX_ERR_INVALID.  The temporal blocks run the generic fused kernels (FOCUS instantiations) and the generic
+ *           backward route, as under vdx_set_temporal_pos_bias, with which it combines.
+ * Any change of mode, pointer or n drops the handle's cached sampling graphs.  VDX_ERR_STATE together with fp8 attention, VDX_ERR_INVALID
+ * for more than 64 frames. */
+int vdx_set_focus_present(vdx_handle* h, int mode, const unsigned char* mask_dev, int n);
+int vdx_get_focus_present(const vdx_handle* h);
 
 /* Flat fp32 parameter buffer layout (names = nnx state-tree paths, shapes = Flax shapes). */
 int vdx_param_count(const vdx_handle* h);
@@ -693,6 +728,13 @@ size_t vdx_attention_bias_backward_scratch_floats(int heads, int tokens);
 int vdx_attention_core_backward_bias(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias,
                                      float* dbias, float* scratch, size_t scratch_floats, int batch, int frames, int h, int w, int heads,
                                      int temporal, int bf16_operands, void* stream);
+
+/* vdx_attention_core_backward_bias with the focus-present mask of vdx_attention_forward_focus on the recomputed probabilities.  For a masked
+ * sample, exactly: dq == dk == 0, dv == dO, o == v, and a contribution of 0 to dbias.  bias_or_null / dbias_or_null come together; without
+ * them scratch may be null. */
+int vdx_attention_core_backward_focus(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias_or_null,
+                                      float* dbias_or_null, float* scratch, size_t scratch_floats, const unsigned char* focus_dev, int focus_n,
+                                      int batch, int frames, int h, int w, int heads, int temporal, int bf16_operands, void* stream);
 
 /* vdx_temporal_attention_backward_fused with x_bf16 (model_bwd.hip:219-227 under bf16 activation storage): x holds bf16. */
 int vdx_temporal_attention_backward_fused_ex(const void* x, int x_bf16, const float* dy, const void* packed_wqkv, const float* bqkv,

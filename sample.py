@@ -39,6 +39,8 @@ FLAGS = (   # (flag, kwargs)
     ('--resample-steps', dict(type=int, default=1, help='with --context: RePaint resampling steps per noise level (ancestral chain only)')),
     ('--temporal-pos-bias', dict(action='store_true', help='temporal attention adds the relative position bias before the softmax (frame order; '
                                                            'also unet.temporal_pos_bias in the YAML; for checkpoints trained with it)')),
+    ('--focus-present', dict(action='store_true', help='"image mode" sampling from a jointly trained checkpoint (train.py --focus_present): in '
+                                                       'the temporal blocks every frame attends to itself only; not with --context / --attn-fp8')),
     ('--clean-context', dict(action='store_true', help='with --context: keep the given frames clean at every step (frame-conditioned '
                                                        'checkpoints, train.py --frame_cond_max); not with --resample-steps > 1')),
     ('--cond-path', dict(type=str, default=None, help='float32 [B, cond_dim] .npy of conditions: one video per row (sets the batch); '
@@ -48,15 +50,17 @@ FLAGS = (   # (flag, kwargs)
 )
 
 
-def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=False):
+def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=False, focus_present=False):
     """temporal_pos_bias: the command-line flag; the YAML's unet.temporal_pos_bias (absent = false) switches it on as well.  An architecture
-    argument like dim: checkpoints do not store it, so a model trained with it is sampled with it."""
+    argument like dim: checkpoints do not store it, so a model trained with it is sampled with it.  focus_present: the same for the
+    focus-present switch (unet.focus_present in the YAML, absent = false)."""
     from video_diffusion_nnx_amd.gaussian_diffusion import GaussianDiffusion
     from video_diffusion_nnx_amd.unet3d import Rngs, Unet3D
     u, d = cfg['unet'], cfg['diffusion']
     unet = Unet3D(dim=u['dim'], rngs=Rngs(u['rngs_seed']), dim_mults=tuple(u['dim_mults']), channels=u['channels'],
                   use_bert_text_cond=u['use_bert_text_cond'], mode=mode, attn_fp8=attn_fp8,
-                  temporal_pos_bias=bool(temporal_pos_bias or u.get('temporal_pos_bias', False)))
+                  temporal_pos_bias=bool(temporal_pos_bias or u.get('temporal_pos_bias', False)),
+                  focus_present=bool(focus_present or u.get('focus_present', False)))
     gd = GaussianDiffusion(denoise_fn=unet, image_size=d['image_size'], num_frames=d['num_frames'], channels=d['channels'],
                            timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'])
     return unet, gd
@@ -143,7 +147,13 @@ def _run(a, ap, rank, world):
         ap.error('--cond-path needs a config whose unet.use_bert_text_cond is true (a conditioned network)')
     if a.attn_fp8 and (a.temporal_pos_bias or cfg['unet'].get('temporal_pos_bias')):
         ap.error('--attn-fp8 and the temporal position bias exclude each other')
-    unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8, temporal_pos_bias=a.temporal_pos_bias)
+    if a.focus_present and a.attn_fp8:
+        ap.error('--attn-fp8 and --focus-present exclude each other')
+    if a.focus_present and a.context:
+        ap.error('--focus-present samples from noise: not together with --context')
+    unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8, temporal_pos_bias=a.temporal_pos_bias,
+                            **(dict(focus_present=True) if a.focus_present else {}))
+    fp_kw = dict(focus_present=True) if a.focus_present else {}
     if not a.random_init:
         ckpt = pathlib.Path(a.checkpoint_path).resolve()
         gd, _ = load_checkpoint(gd, a.step, str(ckpt), load_ema_params=a.load_ema_params)
@@ -166,10 +176,10 @@ def _run(a, ap, rank, world):
         except ValueError as e:
             ap.error(str(e))
         videos = gd.sample(a.seed, cond=torch.from_numpy(cond), cond_scale=a.cond_scale, ddim_steps=a.ddim_steps, dpm_steps=a.dpm_steps,
-                           dpm_order=a.dpm_order, guidance_rescale=a.guidance_rescale)      # this rank's shard of the global batch
+                           dpm_order=a.dpm_order, guidance_rescale=a.guidance_rescale, **fp_kw)      # this rank's shard of the global batch
     else:
         videos = gd.sample(a.seed, batch_size=a.batch_size, ddim_steps=a.ddim_steps, dpm_steps=a.dpm_steps,
-                           dpm_order=a.dpm_order)                       # this rank's shard of the global batch
+                           dpm_order=a.dpm_order, **fp_kw)              # this rank's shard of the global batch
     logging.info('rank %d drew %d videos', rank, len(videos))
     lo_hi = None
     if world > 1:                                      # the uint8 scaling is batch-GLOBAL (reference sample.py:107-110): two scalars cross ranks

@@ -11,7 +11,9 @@ context frames per sample enter the network clean and carry no loss; sample such
 the condition of video i; every sample's condition is replaced by the null embedding with the given probability; needs a config with
 use_bert_text_cond; sample with sample.py --cond-path); --temporal_pos_bias (or unet.temporal_pos_bias: true in the YAML: the temporal
 attention blocks add the relative position bias before the softmax, so the network can learn frame order; sample with
-sample.py --temporal-pos-bias or the same YAML key)."""
+sample.py --temporal-pos-bias or the same YAML key); --focus_present [--prob_focus_present P] (or unet.focus_present: true and
+trainer.prob_focus_present: P in the YAML; joint image-video training: with probability P a sample is trained as a bag of images, each
+frame attending to itself only in the temporal blocks; sample.py --focus-present draws frames in that image mode)."""
 import argparse
 import logging
 import os
@@ -33,6 +35,10 @@ FLAGS = (
     ('--frame_cond_mode', dict(choices=('random', 'prefix'), default=None, help="with --frame_cond_max: any K frames, or the first K")),
     ('--temporal_pos_bias', dict(action='store_true', help='temporal attention adds the relative position bias before the softmax: the network '
                                                            'learns frame order (also unet.temporal_pos_bias in the YAML; not stored in checkpoints)')),
+    ('--focus_present', dict(action='store_true', help='joint image-video training: the network honours the focus-present mask (also '
+                                                       'unet.focus_present in the YAML; not stored in checkpoints)')),
+    ('--prob_focus_present', dict(type=float, default=None, help='with --focus_present: probability that a sample is trained as a bag of '
+                                                                 'images (also trainer.prob_focus_present in the YAML; default 0)')),
     ('--cond_path', dict(type=str, default=None, help='conditional training: float32 [N, cond_dim] .npy, row i = the condition of video i')),
     ('--null_cond_prob', dict(type=float, default=None, help='with --cond_path: probability of training a sample on the null embedding (0.1)')),
 )
@@ -62,8 +68,18 @@ def main(argv=None):
     seed = a.rng_seed if a.rng_seed is not None else cfg.get('rng_seed', 0)
     logging.info('config %s, master seed %s', a.config, seed)
     # (the keyword only when the flag is given: callers that replace build_models with a (cfg, mode) function keep working)
-    _, gd = build_models(cfg, a.mode, **(dict(temporal_pos_bias=True) if a.temporal_pos_bias else {}))
+    _, gd = build_models(cfg, a.mode, **(dict(temporal_pos_bias=True) if a.temporal_pos_bias else {}),
+                         **(dict(focus_present=True) if a.focus_present else {}))
     tc = dict(cfg['trainer'])
+    p_fp = tc.pop('prob_focus_present', None)        # (a Trainer attribute, not a constructor argument)
+    if a.prob_focus_present is not None:
+        if not (a.focus_present or cfg['unet'].get('focus_present')):
+            ap.error('--prob_focus_present needs --focus_present (or unet.focus_present: true in the YAML)')
+        p_fp = a.prob_focus_present
+    if p_fp is not None:
+        if not 0.0 <= float(p_fp) <= 1.0:
+            ap.error(f'prob_focus_present must be in [0, 1], got {p_fp}')
+        Trainer.prob_focus_present = float(p_fp)
     if a.train_num_steps is not None:
         tc['train_num_steps'] = a.train_num_steps
     if a.dataset_path is not None:

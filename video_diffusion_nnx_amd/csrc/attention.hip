@@ -22,7 +22,9 @@
 namespace vdx {
 
 // BIAS: P.pos_bias[h][i][j] (fp32, [heads][L][L]) is added to the scaled scores before the key mask and the softmax
-template <int MODE, int LP, int TMO, bool BIAS = false>
+// FOCUS (with BIAS; P.pos_bias may be null then): the sequences of a sample whose P.focus flag is set keep only the score of key == query
+// (all others -1e30 with the key mask): the softmax row is exactly one-hot and O == v in operand precision
+template <int MODE, int LP, int TMO, bool BIAS = false, bool FOCUS = false>
 __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs P) {
     using M = Mma<MODE>;
     constexpr int KT = M::KT, KC = M::KC, RS = ROW_STRIDE;
@@ -166,7 +168,9 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs P) {
                     M::mma(s[jt], a, bq);
                 }
             }
-            if constexpr (BIAS) {                             // lane (lp, q) of tile jt: query i = qt * 16 + lp, keys j = jt * 16 + 4q + r
+            bool fm = false;                                  // this wave's sequence belongs to a focus-present sample (wave-uniform)
+            if constexpr (FOCUS) fm = P.focus[(int)((((long)blockIdx.x * NSEQ + sl) / P.inner) % P.focus_n)] != 0;
+            if (BIAS && (!FOCUS || P.pos_bias)) {             // lane (lp, q) of tile jt: query i = qt * 16 + lp, keys j = jt * 16 + 4q + r
                 const int qi = qt * 16 + lp;
                 const float* brow = P.pos_bias + ((size_t)h * P.L + qi) * P.L;
 #pragma unroll
@@ -183,6 +187,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs P) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     if (jt * 16 + 4 * q + r >= P.L) s[jt][r] = -1e30f;
+                    if constexpr (FOCUS) { if (fm && jt * 16 + 4 * q + r != qt * 16 + lp) s[jt][r] = -1e30f; }
                     mx = fmaxf(mx, s[jt][r]);
                 }
             mx = max_q(mx);
@@ -256,7 +261,8 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs P) {
 //                                          B = the normalised scores, still in their accumulator registers
 //   y[c,i]   += sum_d Wo[c, h*32+d] O^T[d,i] : B = the O^T accumulator tiles, A = 4-element weight fragments from L2
 // never leave the register file: no q/k/v/P/O round trips through LDS, two workgroup barriers per head (weight tile only).
-template <int MODE, int TMA, bool F8, bool BIAS = false>   // TMA = C / 16 output-channel tiles (all owned by every wave, for its 16 rows); F8: fp8 QK^T / PV
+// BIAS / FOCUS: as in attention_kernel (wave w's sequence is blockIdx.x * 4 + w: the flag is wave-uniform)
+template <int MODE, int TMA, bool F8, bool BIAS = false, bool FOCUS = false>   // TMA = C / 16 output-channel tiles (all owned by every wave, for its 16 rows); F8: fp8 QK^T / PV
 __global__ __launch_bounds__(256) void attention_reg_kernel(const AttnArgs P) {
     using M = Mma<MODE>;
     constexpr int KT = M::KT, RS = ROW_STRIDE;
@@ -286,6 +292,8 @@ __global__ __launch_bounds__(256) void attention_reg_kernel(const AttnArgs P) {
     f32x4 oacc[TMA];
 #pragma unroll
     for (int i = 0; i < TMA; ++i) oacc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bool fm = false;
+    if constexpr (FOCUS) fm = P.focus[(int)((((long)blockIdx.x * 4 + w) / P.inner) % P.focus_n)] != 0;
     const char* wq = reinterpret_cast<const char*>(P.wqkv);
     const char* wo = reinterpret_cast<const char*>(P.wo);
     const int nkt = P.CPad / KT;
@@ -370,14 +378,18 @@ __global__ __launch_bounds__(256) void attention_reg_kernel(const AttnArgs P) {
         f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
         core_mma16<M, F8>(s, ak[0], aq[0]);
         core_mma16<M, F8>(s, ak[1], aq[1]);
-        if constexpr (BIAS) {                                 // pos_bias[h][i = lp][j = 4q + r] on the scaled scores, before the key mask
+        if (BIAS && (!FOCUS || P.pos_bias)) {                 // pos_bias[h][i = lp][j = 4q + r] on the scaled scores, before the key mask
             const float* brow = P.pos_bias + ((size_t)h * P.L + lp) * P.L;
 #pragma unroll
             for (int r = 0; r < 4; ++r) if (lp < P.L && 4 * q + r < P.L) s[r] += brow[4 * q + r];
         }
         float mx = -1e30f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) { if (4 * q + r >= P.L) s[r] = -1e30f; mx = fmaxf(mx, s[r]); }
+        for (int r = 0; r < 4; ++r) {
+            if (4 * q + r >= P.L) s[r] = -1e30f;
+            if constexpr (FOCUS) { if (fm && 4 * q + r != lp) s[r] = -1e30f; }
+            mx = fmaxf(mx, s[r]);
+        }
         mx = max_q(mx);
         float sum = 0.f;
 #pragma unroll
@@ -1233,6 +1245,13 @@ static hipError_t launch_attn_reg_t(const AttnArgs& a, hipStream_t st) {
     const size_t lds = 512 + (size_t)(64 + 96) * ROW_STRIDE + (size_t)TMA * 16 * (32 * Mma<MODE>::ES + 16);
     const long blocks = (a.nseq + 3) / 4;
     const AttnWork aw = attn_work(a, Mma<MODE>::ES, true);
+    if (a.focus) {                                     // per-sample focus-present mask, with or without the bias (vdx_set_focus_present)
+        auto kfn = attention_reg_kernel<MODE, TMA, false, true, true>;
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
+        LaunchScope ls(st, "attention_reg_kernel", aw.flops, aw.bytes, a.pos_bias ? "<%d, %d, bias+focus> C%d L%d nseq%ld io16 %d" : "<%d, %d, focus> C%d L%d nseq%ld io16 %d", MODE, TMA, a.C, a.L, a.nseq, a.io_bf16);
+        hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, st, a);
+        return hipGetLastError();
+    }
     if (a.pos_bias) {                                  // pre-softmax bias (never together with the fp8 core: vdx_set_temporal_pos_bias)
         auto kfn = attention_reg_kernel<MODE, TMA, false, true>;
         if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
@@ -1258,34 +1277,49 @@ static hipError_t launch_attn_reg(const AttnArgs& a, hipStream_t st) {
     return hipErrorInvalidValue;
 }
 
-template <int MODE, int LP, int TMO, bool BIAS = false>
+template <int MODE, int LP, int TMO, bool BIAS = false, bool FOCUS = false>
 static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t st) {
     constexpr int KC = Mma<MODE>::KC;
     constexpr int NSEQ = 64 / LP;
     constexpr int NCHL = (LP + KC - 1) / KC;
     constexpr int RSV = NCHL * 64 + 16;
     const size_t lds = 512 + (size_t)(64 * 4 + 96) * ROW_STRIDE + (size_t)(NSEQ * 32 + 64) * RSV;
-    auto kfn = attention_kernel<MODE, LP, TMO, BIAS>;
+    auto kfn = attention_kernel<MODE, LP, TMO, BIAS, FOCUS>;
     if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const long blocks = (a.nseq + NSEQ - 1) / NSEQ;
     const AttnWork aw = attn_work(a, Mma<MODE>::ES, true);
-    LaunchScope ls(st, "attention_kernel", aw.flops, aw.bytes, BIAS ? "<%d, %d, %d, bias> C%d L%d nseq%ld io16 %d" : "<%d, %d, %d> C%d L%d nseq%ld io16 %d", MODE, LP, TMO, a.C, a.L, a.nseq, a.io_bf16);
+    LaunchScope ls(st, "attention_kernel", aw.flops, aw.bytes,
+                   FOCUS ? (a.pos_bias ? "<%d, %d, %d, bias+focus> C%d L%d nseq%ld io16 %d" : "<%d, %d, %d, focus> C%d L%d nseq%ld io16 %d")
+                         : BIAS ? "<%d, %d, %d, bias> C%d L%d nseq%ld io16 %d" : "<%d, %d, %d> C%d L%d nseq%ld io16 %d", MODE, LP, TMO, a.C, a.L, a.nseq, a.io_bf16);
     hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, st, a);
     return hipGetLastError();
 }
 
-template <int MODE, int LP, bool BIAS = false>
+template <int MODE, int LP, bool BIAS = false, bool FOCUS = false>
 static hipError_t launch_attn_l(const AttnArgs& a, hipStream_t st) {
-    if (a.C <= 64) return launch_attn_t<MODE, LP, 1, BIAS>(a, st);
-    if (a.C <= 128) return launch_attn_t<MODE, LP, 2, BIAS>(a, st);
-    if (a.C <= 256) return launch_attn_t<MODE, LP, 4, BIAS>(a, st);
-    if (a.C <= 512) return launch_attn_t<MODE, LP, 8, BIAS>(a, st);
-    if (a.C <= 1024) return launch_attn_t<MODE, LP, 16, BIAS>(a, st);
+    if (a.C <= 64) return launch_attn_t<MODE, LP, 1, BIAS, FOCUS>(a, st);
+    if (a.C <= 128) return launch_attn_t<MODE, LP, 2, BIAS, FOCUS>(a, st);
+    if (a.C <= 256) return launch_attn_t<MODE, LP, 4, BIAS, FOCUS>(a, st);
+    if (a.C <= 512) return launch_attn_t<MODE, LP, 8, BIAS, FOCUS>(a, st);
+    if (a.C <= 1024) return launch_attn_t<MODE, LP, 16, BIAS, FOCUS>(a, st);
     return hipErrorInvalidValue;
 }
 
 template <int MODE>
 static hipError_t launch_attn_m(const AttnArgs& a, hipStream_t st) {
+    if (a.focus) {
+        // per-sample focus-present mask: the generic fused kernels only, as for the bias below (FOCUS instantiations; the bias is optional)
+        if (a.fp8_core || a.focus_n < 1) return hipErrorInvalidValue;
+        if (a.L <= 16) {
+            if constexpr (MODE == MODE_F32) {
+                if (a.C > 512) return a.C <= 1024 ? launch_attn_t<MODE, 16, 16, true, true>(a, st) : hipErrorInvalidValue;
+            }
+            return launch_attn_reg<MODE>(a, st);
+        }
+        if (a.L <= 32) return launch_attn_l<MODE, 32, true, true>(a, st);
+        if (a.L <= 64) return launch_attn_l<MODE, 64, true, true>(a, st);
+        return hipErrorInvalidValue;
+    }
     if (a.pos_bias) {
         // pre-softmax bias: the generic fused kernels only (the one-wave-per-head / per-group kernels have no bias instantiation yet)
         if (a.fp8_core) return hipErrorInvalidValue;
@@ -1406,6 +1440,172 @@ hipError_t launch_pos_bias_table(const float* emb, const int* buckets, float* ta
     LaunchScope ls(st, "pos_bias_table_kernel", 0.0, 8.0 * total, "heads%d n%d", heads, n);
     hipLaunchKernelGGL(pos_bias_table_kernel, dim3((total + 255) / 256), dim3(256), 0, st, emb, buckets, table, heads, n * n);
     return hipGetLastError();
+}
+
+// ---- the block of a batch in which every sample is focus-present (vdx_set_focus_present, mode 1) ----
+// Each token attends to itself only, so softmax is the identity matrix and the block is pointwise over token rows:
+//   y = x + bo + Wo . rd(Wv . x + bv)            rd = the rounding to the mode's operand type that O gets in the attention kernels
+// No q, no k, no scores: a third of attention_kernel's projection MFMAs and none of its core.  A workgroup owns 64 token rows (row r of the
+// launch = token r % L of sequence r / L, the addressing of attention_kernel; the last tile may be ragged).  Per head
+//   GEMM1  v_h[32, 64] = Wv_h[32, C] . x^T    the 32 v rows [2 HD + 32 h, +32) of the packed wqkv, K tiles staged in LDS (double-buffered:
+//                                             two barriers per head when x fits one K tile); wave (wc, wr) owns d tile wc x row tiles
+//                                             2 wr, 2 wr + 1
+//   v_h + bv -> os [row][d] in operand precision (LDS; v never touches HBM)
+//   GEMM2  y[C, 64] += Wo[:, 32 h : 32 h + 32] . v_h^T      accumulated in registers across the heads, as in attention_kernel
+template <int MODE, int TMO>
+__global__ __launch_bounds__(256) void attention_present_kernel(const AttnArgs P) {
+    using M = Mma<MODE>;
+    constexpr int KT = M::KT, KC = M::KC, RS = ROW_STRIDE;
+    constexpr int APIECES = KT / 4;
+    constexpr int D = 32, NCHD = D / KC;
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    long* rowoff = reinterpret_cast<long*>(smem);               // [64]
+    char* xs = smem + 512;                                      // [64][RS]
+    char* ws = xs + 64 * RS;                                    // [2][32][RS]: two weight tiles, so a tile costs one barrier
+    char* os = ws + 64 * RS;                                    // [64][RS]
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int lp = lane & 15, q = lane >> 4;
+    const int wc = w & 1, wr = w >> 1;
+    const int HD = P.heads * D;
+
+    if (tid < 64) {
+        const long r = (long)blockIdx.x * 64 + tid;
+        long off = -1;
+        if (r < P.nseq * P.L) {
+            const long sg = r / P.L, tok = r - sg * P.L;
+            off = (sg / P.inner) * P.outer_stride + (sg % P.inner) * P.inner_stride + tok * P.tok_stride;
+        }
+        rowoff[tid] = off;
+    }
+    __syncthreads();
+
+    f32x4 oacc[TMO][4];
+#pragma unroll
+    for (int i = 0; i < TMO; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) oacc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    const char* wq = reinterpret_cast<const char*>(P.wqkv);
+    const char* wo = reinterpret_cast<const char*>(P.wo);
+    const int nkt = P.CPad / KT;
+    const bool x_resident = (nkt == 1);                         // else re-staged per head from L2
+    auto stage_x = [&](int kt) {
+        for (int i = tid; i < 64 * APIECES; i += 256) {
+            const int row = i / APIECES, pc = i % APIECES;
+            const int c = kt * KT + pc * 4;
+            const long ro = rowoff[row];
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ro >= 0 && c < P.C) v = load4_f32_or_bf16(P.x, (size_t)(ro + c), P.io_bf16);
+            M::store4(xs + row * RS, pc * 4, v);
+        }
+    };
+    // the head's v weight tile (32 rows x 128 B: one 16-byte piece per thread) prefetched through a register one K tile ahead
+    uint4 wp = make_uint4(0, 0, 0, 0);
+    const int wrow_ = tid >> 3, wpc_ = tid & 7;
+    auto wfetch = [&](int h, int kt) {
+        wp = *reinterpret_cast<const uint4*>(wq + ((size_t)(2 * HD + h * D + wrow_) * P.CPad + (size_t)kt * KT) * M::ES + wpc_ * 16);
+    };
+    if (x_resident) stage_x(0);
+    wfetch(0, 0);
+
+    int it = 0;
+    for (int h = 0; h < P.heads; ++h) {
+        f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+        for (int kt = 0; kt < nkt; ++kt) {
+            // weight tile `it` goes to buffer it & 1: its previous readers (tile it - 2) passed the barrier of tile it - 1.  os is
+            // rewritten only after this tile's barrier, which every wave reaches after its GEMM2 of the previous head
+            char* wsb = ws + (it & 1) * 32 * RS;
+            ++it;
+            if (!x_resident) { __syncthreads(); stage_x(kt); }   // (previous readers of xs are done)
+            *reinterpret_cast<uint4*>(wsb + wrow_ * RS + wpc_ * 16) = wp;
+            __syncthreads();
+            {
+                int nh = h, nk = kt + 1;
+                if (nk == nkt) { nk = 0; nh = h + 1; }
+                if (nh < P.heads) wfetch(nh, nk);
+            }
+#pragma unroll
+            for (int ch = 0; ch < 2; ++ch) {
+                const uint4 af = *reinterpret_cast<const uint4*>(wsb + (wc * 16 + lp) * RS + ch * 64 + q * 16);
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn) {
+                    const uint4 bf = *reinterpret_cast<const uint4*>(xs + ((wr * 2 + tn) * 16 + lp) * RS + ch * 64 + q * 16);
+                    M::mma(acc[tn], af, bf);
+                }
+            }
+        }
+        {
+            const int d0 = wc * 16 + 4 * q;
+            const float4 bv = *reinterpret_cast<const float4*>(P.bqkv + 2 * HD + h * D + d0);
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn) {
+                const int row = (wr * 2 + tn) * 16 + lp;
+                M::store4(os + row * RS, d0, make_float4(acc[tn][0] + bv.x, acc[tn][1] + bv.y, acc[tn][2] + bv.z, acc[tn][3] + bv.w));
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int ch = 0; ch < NCHD; ++ch) {
+            uint4 bf[4];
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn) bf[tn] = *reinterpret_cast<const uint4*>(os + (tn * 16 + lp) * RS + ch * 64 + q * 16);
+#pragma unroll
+            for (int tmo = 0; tmo < TMO; ++tmo) {
+                const int co = (w * TMO + tmo) * 16 + lp;
+                uint4 a = make_uint4(0, 0, 0, 0);
+                if (co < P.C) a = *reinterpret_cast<const uint4*>(wo + ((size_t)co * P.HDPad + (size_t)h * D) * M::ES + ch * 64 + q * 16);
+#pragma unroll
+                for (int tn = 0; tn < 4; ++tn) M::mma(oacc[tmo][tn], a, bf[tn]);
+            }
+        }
+    }
+    // epilogue: + bias + residual
+#pragma unroll
+    for (int tmo = 0; tmo < TMO; ++tmo) {
+        const int co = (w * TMO + tmo) * 16 + 4 * q;
+        if (co >= P.C) continue;
+        const float4 bo = *reinterpret_cast<const float4*>(P.bo + co);
+#pragma unroll
+        for (int tn = 0; tn < 4; ++tn) {
+            const long ro = rowoff[tn * 16 + lp];
+            if (ro < 0) continue;
+            const float4 xr = load4_f32_or_bf16(P.x, (size_t)(ro + co), P.io_bf16);
+            float4 v;
+            v.x = oacc[tmo][tn][0] + bo.x + xr.x; v.y = oacc[tmo][tn][1] + bo.y + xr.y;
+            v.z = oacc[tmo][tn][2] + bo.z + xr.z; v.w = oacc[tmo][tn][3] + bo.w + xr.w;
+            store4_f32_or_bf16(P.y, (size_t)(ro + co), v, P.io_bf16);
+        }
+    }
+}
+
+template <int MODE, int TMO>
+static hipError_t launch_attn_present_t(const AttnArgs& a, hipStream_t st) {
+    const size_t lds = 512 + (size_t)(64 + 64 + 64) * ROW_STRIDE;
+    const long rows = a.nseq * a.L, blocks = (rows + 63) / 64;
+    const int es = a.io_bf16 ? 2 : 4;
+    LaunchScope ls(st, "attention_present_kernel", 4.0 * rows * a.C * a.heads * 32, (double)rows * a.C * es * 3, "<%d, %d> C%d rows%ld io16 %d", MODE, TMO, a.C, rows, a.io_bf16);
+    hipLaunchKernelGGL((attention_present_kernel<MODE, TMO>), dim3((unsigned)blocks), dim3(256), lds, st, a);
+    return hipGetLastError();
+}
+
+template <int MODE>
+static hipError_t launch_attn_present_m(const AttnArgs& a, hipStream_t st) {
+    if (a.C <= 64) return launch_attn_present_t<MODE, 1>(a, st);
+    if (a.C <= 128) return launch_attn_present_t<MODE, 2>(a, st);
+    if (a.C <= 256) return launch_attn_present_t<MODE, 4>(a, st);
+    if (a.C <= 512) return launch_attn_present_t<MODE, 8>(a, st);
+    return launch_attn_present_t<MODE, 16>(a, st);
+}
+
+hipError_t launch_attention_present(int mode, AttnArgs a, hipStream_t st) {
+    if (a.C < 4 || a.C % (a.io_bf16 ? 8 : 4) || a.C > 1024 || a.heads < 1 || a.L < 1 || a.nseq < 1 || a.inner < 1) return hipErrorInvalidValue;
+    if (a.io_bf16 && mode != MODE_BF16) return hipErrorInvalidValue;
+    if ((a.nseq * a.L + 63) / 64 >= (1L << 31)) return hipErrorInvalidValue;
+    a.CPad = conv_cin_pad(mode, a.C);
+    a.HDPad = conv_cin_pad(mode, a.heads * 32);
+    return mode == MODE_F32 ? launch_attn_present_m<MODE_F32>(a, st) : mode == MODE_F16 ? launch_attn_present_m<MODE_F16>(a, st) : launch_attn_present_m<MODE_BF16>(a, st);
 }
 
 hipError_t launch_attention(int mode, AttnArgs a, hipStream_t st) {

@@ -12,7 +12,9 @@ namespace vdx {
 // one workgroup = one (sequence, head) of L <= 64 tokens (blockIdx.y = head).  qkv [npix][3*HD] (+bias, q unscaled), dO [npix][HD]
 // -> O, dq, dk, dv [npix][HD] each.  Token t of sequence s is pixel row (s / inner) * outer_p + (s % inner) + t * tok_p.
 // BIAS: the scores get P.bias[h][a][b] before the softmax, and the thread adds the dS elements it owns (i = tid + 256 u) into dacc[u]
-template <bool BIAS>
+// FOCUS (with BIAS; P.bias may be null then): the scores of a sequence whose sample has its P.focus flag set are -1e30 off the diagonal,
+// so P is exactly the identity, dS exactly 0 and dv = dO
+template <bool BIAS, bool FOCUS = false>
 __device__ __forceinline__ void attn_core_bwd_seq(const AttnBwdArgs& P, float* sm, const long s, const int h, float (&dacc)[16]) {
     const int L = P.L, LD = 33, LP1 = L + 1;
     float* q = sm; float* k = q + L * LD; float* v = k + L * LD; float* dO = v + L * LD;
@@ -21,6 +23,8 @@ __device__ __forceinline__ void attn_core_bwd_seq(const AttnBwdArgs& P, float* s
     const int tid = threadIdx.x;
     const long row0 = (s / P.inner) * P.outer_p + (s % P.inner);
     const int HD = P.heads * 32;
+    bool fm = false;
+    if constexpr (FOCUS) fm = P.focus[(int)((s / P.inner) % P.focus_n)] != 0;
     {
         for (int i = tid; i < L * 32; i += 256) {
             const int t = i >> 5, d = i & 31;
@@ -35,7 +39,8 @@ __device__ __forceinline__ void attn_core_bwd_seq(const AttnBwdArgs& P, float* s
             float acc = 0.f, acc2 = 0.f;
 #pragma unroll 8
             for (int d = 0; d < 32; ++d) { acc = fmaf(q[a * LD + d], k[b * LD + d], acc); acc2 = fmaf(dO[a * LD + d], v[b * LD + d], acc2); }
-            if constexpr (BIAS) acc += P.bias[((size_t)h * L + a) * L + b];
+            if (BIAS && (!FOCUS || P.bias)) acc += P.bias[((size_t)h * L + a) * L + b];
+            if constexpr (FOCUS) { if (fm && a != b) acc = -1e30f; }
             Pm[a * LP1 + b] = acc; dS[a * LP1 + b] = acc2;           // scores, dP
         }
         __syncthreads();
@@ -50,7 +55,7 @@ __device__ __forceinline__ void attn_core_bwd_seq(const AttnBwdArgs& P, float* s
             for (int j = 0; j < L; ++j) dS[tid * LP1 + j] = Pm[tid * LP1 + j] * (dS[tid * LP1 + j] - dr);
         }
         __syncthreads();
-        if constexpr (BIAS) {
+        if (BIAS && (!FOCUS || P.part)) {
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
                 const int i = tid + 256 * u;
@@ -81,22 +86,34 @@ __global__ __launch_bounds__(256) void attn_core_bwd_kernel(AttnBwdArgs P) {
 
 // Bias form: a FIXED grid (gridDim.x slots, blockIdx.y = head); workgroup x walks the sequences x, x + gridDim.x, ... in order and stores
 // the sum of their dS into its own slot P.part[x][h][L][L] -- no atomics, so dBias is bit-reproducible (second pass: attn_dbias_sum_kernel)
-__global__ __launch_bounds__(256) void attn_core_bwd_bias_kernel(AttnBwdArgs P) {
-    extern __shared__ float sm[];
+template <bool FOCUS>
+__device__ __forceinline__ void attn_core_bwd_grid(const AttnBwdArgs& P, float* sm) {
     const int L = P.L, h = blockIdx.y, tid = threadIdx.x;
     float dacc[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) dacc[u] = 0.f;
     for (long s = blockIdx.x; s < P.nseq; s += gridDim.x) {
         __syncthreads();                                     // the previous sequence's readers of the LDS tiles are done
-        attn_core_bwd_seq<true>(P, sm, s, h, dacc);
+        attn_core_bwd_seq<true, FOCUS>(P, sm, s, h, dacc);
     }
+    if (FOCUS && !P.part) return;                            // focus without the position bias: no dBias
     float* slot = P.part + ((size_t)blockIdx.x * P.heads + h) * L * L;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
         const int i = tid + 256 * u;
         if (i < L * L) slot[i] = dacc[u];
     }
+}
+
+__global__ __launch_bounds__(256) void attn_core_bwd_bias_kernel(AttnBwdArgs P) {
+    extern __shared__ float sm[];
+    attn_core_bwd_grid<false>(P, sm);
+}
+
+// Focus form: the bias form with the per-sample focus-present mask (P.focus); P.bias / P.part may be null (no position bias, no dBias)
+__global__ __launch_bounds__(256) void attn_core_bwd_focus_kernel(AttnBwdArgs P) {
+    extern __shared__ float sm[];
+    attn_core_bwd_grid<true>(P, sm);
 }
 
 // dbias[e] += part[0][e] + part[1][e] + ... (in slot order), e over [heads][L][L]; slots are [heads][LS][LS] with LS >= L
@@ -130,7 +147,8 @@ __device__ __forceinline__ s16x4b pack4_bf16(const f32x4& v) {
 // The work of one wave on sequence s, heads [h0, h1).  BIAS: logits = scale q.k + P.bias[h][a][b] (the scale can no longer ride in the
 // exponent: it is applied to the scores, and the exponent's factor is log2 e alone), and dacc += dS^T of a live wave: lane (a = lp, q) holds
 // dBias[h][a][4q + e].  P comes by value: through a reference to the kernel argument the unbiased instantiations took 4 VGPRs more
-template <bool IO16, bool BIAS>
+// FOCUS (with BIAS; P.bias may be null then): both orientations of the scores of a flagged sample's sequence are -1e30 off the diagonal
+template <bool IO16, bool BIAS, bool FOCUS = false>
 __device__ __forceinline__ void attn_core_bwd16_seq(const AttnBwdArgs P, char* img, const long s, const int h0, const int h1, f32x4& dacc) {
     const int lane = threadIdx.x & 63;
     const int lp = lane & 15, q = lane >> 4;
@@ -148,6 +166,8 @@ __device__ __forceinline__ void attn_core_bwd16_seq(const AttnBwdArgs P, char* i
     const size_t orow = (size_t)(row0 + (long)lp * P.tok_p);          // output: lane (token lp, q) writes channels 4q..4q+3 (+16)
     const bool ovalid = live && lp < P.L;
     const float SL2E = (BIAS ? 1.0f : P.scale) * 1.44269504088896f;   // softmax(scale * s) = exp2((s - max s) * scale * log2 e) / sum
+    bool fm = false;
+    if constexpr (FOCUS) fm = P.focus[(int)((sc / P.inner) % P.focus_n)] != 0;
     for (int h = h0; h < h1; ++h) {
         // ---- stage the four images (wave-private: LDS ops of one wave stay in order).  q stays UNSCALED here: 1/sqrt(d) is folded
         //      into the exponent of both softmaxes and into the dq / dk outputs ----
@@ -193,7 +213,7 @@ __device__ __forceinline__ void attn_core_bwd16_seq(const AttnBwdArgs P, char* i
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int r4 = 4 * q + e;
-                const bool in = lp < P.L && r4 < P.L;
+                const bool in = lp < P.L && r4 < P.L && (!FOCUS || P.bias);
                 ST[e] = fmaf(ST[e], P.scale, in ? bh[lp * P.L + r4] : 0.f);       // query lp, key 4q + e
                 S[e] = fmaf(S[e], P.scale, in ? bh[r4 * P.L + lp] : 0.f);         // query 4q + e, key lp
             }
@@ -203,7 +223,11 @@ __device__ __forceinline__ void attn_core_bwd16_seq(const AttnBwdArgs P, char* i
         {
             float mx = -1e30f;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { if (4 * q + e >= P.L) ST[e] = -1e30f; mx = fmaxf(mx, ST[e]); }
+            for (int e = 0; e < 4; ++e) {
+                if (4 * q + e >= P.L) ST[e] = -1e30f;
+                if constexpr (FOCUS) { if (fm && 4 * q + e != lp) ST[e] = -1e30f; }
+                mx = fmaxf(mx, ST[e]);
+            }
             mx = max_q(mx);
             float sum = 0.f;
 #pragma unroll
@@ -221,7 +245,7 @@ __device__ __forceinline__ void attn_core_bwd16_seq(const AttnBwdArgs P, char* i
         f32x4 Pn, dSn;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float sv = (lp >= P.L) ? -1e30f : S[e];
+            const float sv = (lp >= P.L || (FOCUS && fm && lp != 4 * q + e)) ? -1e30f : S[e];
             const float mx = max16(sv);
             const float pe = __builtin_amdgcn_exp2f((sv - mx) * SL2E);
             const float pn = pe * __builtin_amdgcn_rcpf(reduce16(pe));
@@ -263,15 +287,15 @@ __global__ __launch_bounds__(256) void attn_core_bwd16_kernel(AttnBwdArgs P) {
 // Bias form: a FIXED grid (gridDim.x slots, blockIdx.y = head); workgroup x walks the groups of 4 sequences x, x + gridDim.x, ... in order
 // (a wave-uniform and workgroup-uniform trip count: dead waves of the last group run and add nothing), its 4 waves' sums meet in LDS in wave
 // order, and the workgroup stores P.part[x][h][16][16]
-template <bool IO16>
-__global__ __launch_bounds__(256) void attn_core_bwd16_bias_kernel(AttnBwdArgs P) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];      // [4 waves][4 images][16][AB_RS]
+template <bool IO16, bool FOCUS>
+__device__ __forceinline__ void attn_core_bwd16_grid(const AttnBwdArgs P, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int h = blockIdx.y;
     char* img = smem + w * (4 * 16 * AB_RS);
     f32x4 dacc = f32x4{0.f, 0.f, 0.f, 0.f};
     const long ngroups = (P.nseq + 3) / 4;
-    for (long g = blockIdx.x; g < ngroups; g += gridDim.x) attn_core_bwd16_seq<IO16, true>(P, img, g * 4 + w, h, h + 1, dacc);
+    for (long g = blockIdx.x; g < ngroups; g += gridDim.x) attn_core_bwd16_seq<IO16, true, FOCUS>(P, img, g * 4 + w, h, h + 1, dacc);
+    if (FOCUS && !P.part) return;                                    // focus without the position bias: no dBias (workgroup-uniform)
     *reinterpret_cast<f32x4*>(img + lane * 16) = dacc;               // the wave's own image region: its last reads are behind the fence above
     __syncthreads();
     if (w == 0) {
@@ -281,6 +305,19 @@ __global__ __launch_bounds__(256) void attn_core_bwd16_bias_kernel(AttnBwdArgs P
         const int lp = lane & 15, q = lane >> 4;
         *reinterpret_cast<f32x4*>(P.part + (((size_t)blockIdx.x * P.heads + h) * 16 + lp) * 16 + 4 * q) = t;
     }
+}
+
+template <bool IO16>
+__global__ __launch_bounds__(256) void attn_core_bwd16_bias_kernel(AttnBwdArgs P) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // [4 waves][4 images][16][AB_RS]
+    attn_core_bwd16_grid<IO16, false>(P, smem);
+}
+
+// Focus form: the bias form with the per-sample focus-present mask (P.focus); P.bias / P.part may be null (no position bias, no dBias)
+template <bool IO16>
+__global__ __launch_bounds__(256) void attn_core_bwd16_focus_kernel(AttnBwdArgs P) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_core_bwd16_grid<IO16, true>(P, smem);
 }
 
 // ---- fused form for the temporal attention of the widest level (bf16 mode, C == 64, 8 heads, <= 16 tokens) ------------------
@@ -857,6 +894,33 @@ __global__ __launch_bounds__(256) void sla_bwd_b16_kernel(SlaBwdArgs P) {
 constexpr int ATTN_BIAS_SLOTS = 128;       // workgroups per head of the bias forms = slots of the deterministic dBias sum (fixed: not a device property)
 size_t attn_bwd_bias_scratch_floats(int heads, int L) { const size_t ls = L <= 16 ? 16 : L; return (size_t)ATTN_BIAS_SLOTS * heads * ls * ls; }
 
+// the focus forms (a.focus set): the same fixed grid; with a.bias they also emit dBias, without it bias / dbias / part are all null
+static hipError_t launch_attn_core_bwd_focus(const AttnBwdArgs& a, hipStream_t st) {
+    if (a.focus_n < 1 || a.L < 1 || a.L > 64 || a.nseq < 1) return hipErrorInvalidValue;
+    if (a.bias ? (!a.dbias || !a.part || a.part_cap < attn_bwd_bias_scratch_floats(a.heads, a.L)) : (a.dbias || a.part)) return hipErrorInvalidValue;
+    int slots, LS;
+    if (a.bf16_mma && a.L <= 16) {
+        slots = (int)std::min<long>((a.nseq + 3) / 4, ATTN_BIAS_SLOTS); LS = 16;
+        LaunchScope ls(st, "attn_core_bwd16_focus_kernel", 0.0, 0.0, "<io16 %d, bias %d> L%d nseq%ld heads%d", a.io_bf16, a.bias ? 1 : 0, a.L, a.nseq, a.heads);
+        if (a.io_bf16) hipLaunchKernelGGL(attn_core_bwd16_focus_kernel<true>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
+        else hipLaunchKernelGGL(attn_core_bwd16_focus_kernel<false>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
+    } else {
+        if (a.io_bf16) return hipErrorInvalidValue;
+        slots = (int)std::min<long>(a.nseq, ATTN_BIAS_SLOTS); LS = a.L;
+        const size_t lds = ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
+        auto kfn = attn_core_bwd_focus_kernel;
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
+        LaunchScope ls(st, "attn_core_bwd_focus_kernel", 0.0, 0.0, "<bias %d> L%d nseq%ld heads%d", a.bias ? 1 : 0, a.L, a.nseq, a.heads);
+        hipLaunchKernelGGL(kfn, dim3(slots, a.heads), dim3(256), lds, st, a);
+    }
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (!a.bias) return hipSuccess;
+    const int total = a.heads * a.L * a.L;
+    LaunchScope ls(st, "attn_dbias_sum_kernel", 0.0, 0.0, "slots%d heads%d L%d", slots, a.heads, a.L);
+    hipLaunchKernelGGL(attn_dbias_sum_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a.part, slots, a.heads, a.L, LS, a.dbias);
+    return hipGetLastError();
+}
+
 static hipError_t launch_attn_core_bwd_bias(const AttnBwdArgs& a, hipStream_t st) {
     if (!a.dbias || !a.part || a.L < 1 || a.L > 64 || a.nseq < 1 || a.part_cap < attn_bwd_bias_scratch_floats(a.heads, a.L)) return hipErrorInvalidValue;
     int slots, LS;
@@ -899,6 +963,7 @@ hipError_t launch_pos_bias_scatter(const float* dbias, const int* buckets, float
 }
 
 hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st) {
+    if (a.focus) return launch_attn_core_bwd_focus(a, st);
     if (a.bias) return launch_attn_core_bwd_bias(a, st);
     if (a.bf16_mma && a.L <= 16) {
         const long blocks = (a.nseq + 3) / 4;

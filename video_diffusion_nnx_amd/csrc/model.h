@@ -37,6 +37,10 @@ struct Model {
     // to the handle (not to the workspace: its size and the slot table do not depend on the switch): the host's bucket map [F][F], the bias
     // table [heads][F][F] every forward rebuilds from the embedding, and the backward's accumulator of dL/d(table)
     int pos_bias = 0; int* d_pos_buckets = nullptr; float* d_pos_table = nullptr; float* d_pos_dbias = nullptr;
+    // focus-present mask of the nine temporal blocks of downs / mid / ups (vdx_set_focus_present): 0 off, 1 every sample (the forward runs
+    // attention_present_kernel, the backward the masked generic route on the handle's own one-byte mask d_focus_ones), 2 per sample
+    // (focus_mask: the CALLER's device bytes, focus_n of them, read at run time; batch % focus_n == 0)
+    int focus = 0; const unsigned char* focus_mask = nullptr; int focus_n = 0; unsigned char* d_focus_ones = nullptr;
     int act16 = 0;                       // bf16 mode only: store every inter-kernel activation as bf16.  1 = inference (every fusion on); 2 = training forward
                                          // (every slot vdx_unet_backward reads is materialised: the 1x1 res_conv output is not folded into the block tail)
     std::vector<ParamInfo> params; long param_total = 0;

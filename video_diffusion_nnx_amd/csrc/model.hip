@@ -432,6 +432,11 @@ hipError_t attention_block_forward(int mode, AttnArgs a, bool temporal, int NF, 
         c.NF = NF; c.F = Fr; c.H = H; c.W = W; c.kind = 0; c.kh = c.kw = 1; c.stride = 1; c.pad = 0;
         return launch_conv(mode, c, st);
     };
+    // every sample focus-present: the block is pointwise, one launch of attention_present_kernel (no q, no k, no scores)
+    if (a.present) {
+        if (require != ATTN_ANY) return hipErrorInvalidValue;
+        return launch_attention_present(mode, a, st);
+    }
     if (a.L > 64) {
         // long sequences (spatial attention of a bottleneck larger than 8 x 8): q|k|v projection and out-projection (+ bias + residual)
         // as 1x1 convs around the fp32 core of attention.hip; token-major rows = the channel-last tensor as it is
@@ -447,8 +452,8 @@ hipError_t attention_block_forward(int mode, AttnArgs a, bool temporal, int NF, 
         return conv1x1(o, HD, 0, a.wo, a.bo, a.y, a.C, a.io_bf16, a.x, a.io_bf16);
     }
     // wide levels in bf16 mode: per-head kernel (weights resident in LDS) + the out-projection as a 1x1 conv
-    // (a pre-softmax bias is served by the generic fused kernels only: launch_attention)
-    if (mode == MODE_BF16 && !a.pos_bias && (temporal ? a.L <= 16 : a.L <= 64) && a.heads == 8 && a.C >= 256 && a.C % 128 == 0 &&
+    // (a pre-softmax bias or a focus mask is served by the generic fused kernels only: launch_attention)
+    if (mode == MODE_BF16 && !a.pos_bias && !a.focus && (temporal ? a.L <= 16 : a.L <= 64) && a.heads == 8 && a.C >= 256 && a.C % 128 == 0 &&
         (size_t)96 * (a.C * 2 + 32) <= 160 * 1024 && scratch && rows * a.heads * 64 <= scratch_bytes) {
         if (require != ATTN_ANY && require != ATTN_HEADS) return hipErrorInvalidValue;
         a.oscratch = scratch;
@@ -473,6 +478,12 @@ static hipError_t run_attn(const Fwd& f, const AttnP& ap, const float* x, float*
     a.io_bf16 = f.a16;
     a.fp8_core = (m->attn_fp8 && m->mode == MODE_BF16) ? 1 : 0;
     if (temporal && m->pos_bias) a.pos_bias = m->d_pos_table;  // the mid spatial attention gets none (the reference passes pos_bias to temporal blocks only)
+    // focus-present: the nine temporal blocks of downs / mid / ups, not init_temporal_attn (the reference hands it pos_bias only) and not
+    // the mid spatial attention
+    if (temporal && m->focus && &ap != &m->init_attn) {
+        if (m->focus == 1) a.present = 1;
+        else { a.focus = m->focus_mask; a.focus_n = m->focus_n; }
+    }
     return attention_block_forward(m->mode, a, temporal, f.B * (int)Fr, (int)Fr, (int)S, (int)S, f.sla_ws, m->sla_ws_bytes_per_sample * f.B, ATTN_ANY, f.st);
 }
 
@@ -552,6 +563,11 @@ int model_forward(const Model* m, const float* params, const void* packed, const
         if (!m->d_pos_buckets || !m->d_pos_table) return vdx_set_error(VDX_ERR_STATE, "forward: temporal position bias is on without its bucket map", __FILE__, __LINE__);
         if (m->attn_fp8) return vdx_set_error(VDX_ERR_STATE, "forward: temporal position bias and fp8 attention exclude each other", __FILE__, __LINE__);
         VDX_E(launch_pos_bias_table(params + m->rel_pos_emb, m->d_pos_buckets, m->d_pos_table, c.attn_heads, Fr, st));
+    }
+    if (m->focus) {
+        if (m->attn_fp8) return vdx_set_error(VDX_ERR_STATE, "forward: focus-present and fp8 attention exclude each other", __FILE__, __LINE__);
+        if (m->focus == 2 && (!m->focus_mask || m->focus_n < 1 || B % m->focus_n))
+            return vdx_set_error(VDX_ERR_INVALID, "forward: the batch is not a multiple of the focus-present mask's length", __FILE__, __LINE__);
     }
     // time embedding + every ResnetBlock's (scale, shift)   (unet3d.py:288-298, modules.py:233-238)
     {

@@ -217,7 +217,9 @@ void attn_bwd(Bwd& b, const AttnP& ap, const float* g, const float* x, int lvl, 
     const int io16 = (m->mode == MODE_BF16 && (temporal ? Fr : hw) <= 16) ? 1 : 0;
     b.writes(b.S);                                                 // the scratch is rewritten from here on
     const bool biased = temporal && m->pos_bias;                   // pre-softmax position bias: the generic route, whose cores have a bias form
-    if (m->mode == MODE_BF16 && temporal && C == 64 && H == 8 && Fr <= 16 && !biased) {
+    // focus-present (vdx_set_focus_present): the nine temporal blocks of downs / mid / ups take the generic route too, whose cores mask
+    const bool focused = temporal && m->focus && &ap != &m->init_attn;
+    if (m->mode == MODE_BF16 && temporal && C == 64 && H == 8 && Fr <= 16 && !biased && !focused) {
         // widest level: one fused kernel (attn_bwd16x_kernel) instead of recompute / dO projection / core / dx projection
         AttnBwdXArgs f;
         memset(&f, 0, sizeof(f));
@@ -243,6 +245,8 @@ void attn_bwd(Bwd& b, const AttnP& ap, const float* g, const float* x, int lvl, 
     a.bf16_mma = (m->mode == MODE_BF16);
     // the ten temporal blocks add into ONE accumulator, in the order of the reverse walk (main stream); the stem scatters it to the embedding
     if (biased) { a.bias = m->d_pos_table; a.dbias = m->d_pos_dbias; a.part = b.part_main; a.part_cap = WG_PART_FLOATS; }
+    // an all-present batch runs the same masked cores on the handle's one-byte mask (a v-only backward is a follow-up)
+    if (focused) { a.focus = m->focus == 1 ? m->d_focus_ones : m->focus_mask; a.focus_n = m->focus == 1 ? 1 : m->focus_n; }
     b.ok(launch_attn_core_bwd(a, b.writes(b.S)));
     wgrad1x1(b, O, HD, g, C, ap.o_w, ap.o_b, lvl, io16);
     wgrad1x1_qkv(b, x, C, dq, HD, ap.w, ap.b, lvl, io16, b.a16);
@@ -343,6 +347,8 @@ int model_backward(const Model* m, BwdState* state, const float* params, const v
         if (sb * sb > 64 || c.num_frames > 64)
             return vdx_set_error(VDX_ERR_INVALID, "backward: attention over more than 64 tokens (frames larger than 64 x 64, or more than 64 frames) is forward-only", __FILE__, __LINE__);
     }
+    if (m->focus && (m->focus == 1 ? !m->d_focus_ones : (!m->focus_mask || m->focus_n < 1 || B % m->focus_n)))
+        return vdx_set_error(VDX_ERR_INVALID, "backward: the batch is not a multiple of the focus-present mask's length", __FILE__, __LINE__);
     if (m->pos_bias && (!m->d_pos_buckets || !m->d_pos_table || !m->d_pos_dbias))
         return vdx_set_error(VDX_ERR_STATE, "backward: temporal position bias is on without its buffers", __FILE__, __LINE__);
     if (m->pos_bias && attn_bwd_bias_scratch_floats(c.attn_heads, c.num_frames) > WG_PART_FLOATS)

@@ -305,6 +305,45 @@ int vdx_attention_forward_bias(int mode, const void* x, void* y, int io_bf16, co
     return VDX_OK;
 }
 
+// shared checks + arguments of the two focus-present block entries
+static int fill_attn_block(vdx::AttnArgs& a, const char* who, int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                           const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads, int temporal) {
+    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo) return vdx_set_error(VDX_ERR_INVALID, who, __FILE__, __LINE__);
+    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) return vdx_set_error(VDX_ERR_INVALID, "bad mode", __FILE__, __LINE__);
+    if (io_bf16 && mode != VDX_MODE_BF16) return vdx_set_error(VDX_ERR_INVALID, "bf16 tensors need VDX_MODE_BF16", __FILE__, __LINE__);
+    if (c < 4 || c % (io_bf16 ? 8 : 4) || c > 1024 || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1)
+        return vdx_set_error(VDX_ERR_INVALID, "C must be a multiple of 4 (8 for bf16 tensors) and <= 1024", __FILE__, __LINE__);
+    memset(&a, 0, sizeof(a));
+    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
+    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = heads;
+    fill_attn_geometry(a, batch, frames, h, w, c, temporal);
+    return VDX_OK;
+}
+
+int vdx_attention_forward_focus(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                                const void* wo_packed, const float* bo, const float* bias_or_null, const unsigned char* focus_dev, int focus_n,
+                                int batch, int frames, int h, int w, int c, int heads, int temporal, void* stream) {
+    vdx::AttnArgs a;
+    if (int rc = fill_attn_block(a, "attention_forward_focus: null tensor", mode, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal)) return rc;
+    if (!focus_dev || focus_n < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_focus: null or empty mask");
+    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_focus: more than 64 tokens per sequence is not supported");
+    a.pos_bias = bias_or_null; a.focus = focus_dev; a.focus_n = focus_n;
+    // the route of the network's masked temporal blocks under vdx_set_focus_present(mode 2) (model.hip: attention_block_forward)
+    VDX_HIP(vdx::attention_block_forward(mode, a, temporal != 0, batch * frames, frames, h, w, nullptr, 0, vdx::ATTN_ANY, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_attention_present_forward(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                                  const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads, int temporal,
+                                  void* stream) {
+    vdx::AttnArgs a;
+    if (int rc = fill_attn_block(a, "attention_present_forward: null tensor", mode, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal)) return rc;
+    a.present = 1;
+    // the route of the network's temporal blocks under vdx_set_focus_present(mode 1)
+    VDX_HIP(vdx::attention_block_forward(mode, a, temporal != 0, batch * frames, frames, h, w, nullptr, 0, vdx::ATTN_ANY, (hipStream_t)stream));
+    return VDX_OK;
+}
+
 size_t vdx_sla_workspace_bytes(int mode, int nframes, int npix, int heads) { return vdx::sla_workspace_bytes(mode, nframes, npix, heads); }
 
 int vdx_sla_forward(int mode, const float* x, float* y, const void* wq_packed, const void* wk_packed, const void* wv_packed,
@@ -503,6 +542,7 @@ void vdx_destroy(vdx_handle* h) {
     vdx::comm_destroy(&h->comm);
     vdx::bwd_state_free(&h->bwd);
     free_pos_bias(h->model);
+    if (h->model.d_focus_ones) (void)hipFree(h->model.d_focus_ones);
     if (h->model.d_ss_layers) (void)hipFree(h->model.d_ss_layers);
     if (h->model.d_pack_jobs) (void)hipFree(h->model.d_pack_jobs);
     if (h->model.d_pack_t_jobs) (void)hipFree(h->model.d_pack_t_jobs);
@@ -526,6 +566,7 @@ int vdx_set_attention_fp8(vdx_handle* h, int on) {
     if (!h) VDX_FAIL(VDX_ERR_INVALID, "set_attention_fp8: null handle");
     if (on && h->model.mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "fp8 attention needs a VDX_MODE_BF16 handle");
     if (on && h->model.pos_bias) VDX_FAIL(VDX_ERR_STATE, "set_attention_fp8: fp8 attention and the temporal position bias exclude each other (the fp8 cores have no bias form)");
+    if (on && h->model.focus) VDX_FAIL(VDX_ERR_STATE, "set_attention_fp8: fp8 attention and focus-present exclude each other (the fp8 cores have no mask form)");
     const int v = on ? 1 : 0;
     if (v != h->model.attn_fp8) { h->drop_graphs(); h->model.attn_fp8 = v; }
     return VDX_OK;
@@ -564,6 +605,35 @@ int vdx_set_temporal_pos_bias(vdx_handle* h, int on, const int* buckets) {
     return VDX_OK;
 }
 int vdx_get_temporal_pos_bias(const vdx_handle* h) { return h ? h->model.pos_bias : 0; }
+
+int vdx_set_focus_present(vdx_handle* h, int mode, const unsigned char* mask_dev, int n) {
+    if (!h) VDX_FAIL(VDX_ERR_INVALID, "set_focus_present: null handle");
+    vdx::Model& m = h->model;
+    if (mode < 0 || mode > 2) VDX_FAIL(VDX_ERR_INVALID, "set_focus_present: mode 0 (off), 1 (every sample) or 2 (per-sample mask)");
+    if (mode == 0) {
+        if (m.focus) { h->drop_graphs(); m.focus = 0; m.focus_mask = nullptr; m.focus_n = 0; }
+        return VDX_OK;
+    }
+    if (m.attn_fp8) VDX_FAIL(VDX_ERR_STATE, "set_focus_present: focus-present and fp8 attention exclude each other (the fp8 cores have no mask form)");
+    if (m.cfg.num_frames < 1 || m.cfg.num_frames > 64) VDX_FAIL(VDX_ERR_INVALID, "set_focus_present: 1..64 frames");
+    if (mode == 2 && (!mask_dev || n < 1)) VDX_FAIL(VDX_ERR_INVALID, "set_focus_present: mode 2 needs a device mask of n >= 1 bytes");
+    if (!m.d_ss_layers) VDX_FAIL(VDX_ERR_STATE, "set_focus_present: handle was created without a GPU");
+    if (mode == 1) { mask_dev = nullptr; n = 0; }
+    if (mode == m.focus && mask_dev == m.focus_mask && n == m.focus_n) return VDX_OK;
+    if (!m.d_focus_ones) {                           // the one-byte all-ones mask of the backward of an all-present batch (read as focus[r % 1])
+        const unsigned char one = 1;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&m.d_focus_ones), 16);
+        if (e == hipSuccess) e = hipMemcpy(m.d_focus_ones, &one, 1, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (m.d_focus_ones) { (void)hipFree(m.d_focus_ones); m.d_focus_ones = nullptr; }
+            return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        }
+    }
+    h->drop_graphs();                                // a cached sampling graph holds the other route's kernels / the other pointer
+    m.focus = mode; m.focus_mask = mask_dev; m.focus_n = n;
+    return VDX_OK;
+}
+int vdx_get_focus_present(const vdx_handle* h) { return h ? h->model.focus : 0; }
 
 int vdx_param_count(const vdx_handle* h) { return h ? (int)h->model.params.size() : 0; }
 long vdx_param_total(const vdx_handle* h) { return h ? h->model.param_total : 0; }
@@ -1229,6 +1299,33 @@ int vdx_attention_core_backward_bias(const void* qkv, const void* d_o, void* o, 
     a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)2 * HD * es);
     a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
     a.bias = bias; a.dbias = dbias; a.part = scratch; a.part_cap = scratch_floats;
+    VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_attention_core_backward_focus(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias_or_null,
+                                      float* dbias_or_null, float* scratch, size_t scratch_floats, const unsigned char* focus_dev, int focus_n,
+                                      int batch, int frames, int h, int w, int heads, int temporal, int bf16_operands, void* stream) {
+    if (!qkv || !d_o || !o || !dqkv || !focus_dev || focus_n < 1 || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: bad argument");
+    if ((bias_or_null != nullptr) != (dbias_or_null != nullptr)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: bias and dbias come together");
+    const int HD = heads * 32;
+    if (dstride < 3 * HD || dstride % 8) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: dstride must be a multiple of 8, at least 3 * heads * 32 (one [rows][dq|dk|dv] buffer)");
+    vdx::AttnBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    const long hw = (long)h * w;
+    if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
+    else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
+    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: more than 64 tokens per sequence");
+    if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: bf16 tensors need bf16_operands and at most 16 tokens per sequence");
+    if (bias_or_null && (!scratch || scratch_floats < vdx::attn_bwd_bias_scratch_floats(heads, a.L))) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: scratch too small (vdx_attention_bias_backward_scratch_floats)");
+    a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
+    a.dq = (float*)dqkv;
+    const size_t es = io_bf16 ? 2 : 4;
+    a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)HD * es);
+    a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)2 * HD * es);
+    a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
+    if (bias_or_null) { a.bias = bias_or_null; a.dbias = dbias_or_null; a.part = scratch; a.part_cap = scratch_floats; }
+    a.focus = focus_dev; a.focus_n = focus_n;
     VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
     return VDX_OK;
 }

@@ -139,8 +139,16 @@ struct AttnArgs {
     int CPad, HDPad;                          // completed by the launcher
     const float* pos_bias;                    // [heads][L][L] fp32 added to the scaled scores before the softmax (vdx_set_temporal_pos_bias), or null:
                                               // the generic kernels only (attention_reg_kernel / attention_kernel, BIAS instantiations)
+    // focus-present mask (vdx_set_focus_present): sequence s belongs to sample s / inner, whose flag is focus[(s / inner) % focus_n]; a set
+    // flag masks every score with key != query to -1e30 (after the bias, with the key mask): each token attends to itself only.  Device
+    // bytes, or null.  The generic kernels only (FOCUS instantiations; pos_bias may be null there)
+    const unsigned char* focus; int focus_n;
+    int present;                              // every sample is focus-present: attention_block_forward runs launch_attention_present instead
 };
 hipError_t launch_attention(int mode, AttnArgs a, hipStream_t st);
+// the block when every token attends to itself only: y = x + bo + Wo . rd(Wv . x + bv) in one launch (attention_present_kernel), rd = the
+// operand rounding of the mode; reads the v rows of the packed wqkv only.  C % 4 == 0 (8 for bf16 tensors), C <= 1024
+hipError_t launch_attention_present(int mode, AttnArgs a, hipStream_t st);
 // table[h][i][j] = emb[buckets[i * n + j]][h]: the [heads][n][n] bias of the temporal attention blocks from the [32][heads] embedding
 hipError_t launch_pos_bias_table(const float* emb, const int* buckets, float* table, int heads, int n, hipStream_t st);
 // bf16 mode, <= 16 tokens, 8 heads: q/k/v projection + attention core per head (one workgroup per head: its weights resident in LDS,
@@ -304,6 +312,10 @@ struct AttnBwdArgs {
     // STORES the sum of dS over its sequences into its own slot of `part`, and a second pass adds the slots in order into dbias (+=)
     const float* bias; float* dbias;                                 // [heads][L][L] each, or null / null
     float* part; size_t part_cap;                                    // scratch for the slots and its capacity in floats (attn_bwd_bias_scratch_floats)
+    // focus-present mask as in AttnArgs (sample of sequence s = s / inner, flag focus[sample % focus_n]): the recomputed P of a flagged
+    // sample is one-hot, so its dS, dq, dk and its share of dBias are exactly 0 and dv = dO.  The focus forms run on the fixed grid of the
+    // bias forms; bias / dbias / part may all be null there (focus without the position bias)
+    const unsigned char* focus; int focus_n;
 };
 size_t attn_bwd_bias_scratch_floats(int heads, int L);
 hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st);

@@ -305,10 +305,16 @@ class GaussianDiffusion:
 
     # -- the sampling loops ------------------------------------------------------------------------
     @contextlib.contextmanager
-    def _sampling(self):
+    def _sampling(self, focus_present=None, batch: int = 0):
         """What every sampling loop runs inside: the side stream (ordered after the current one, and the current one after it on
-        the way out) as the current stream, and the UNet's sampling-time activation storage, put back whatever happens."""
+        the way out) as the current stream, and the UNet's sampling-time activation storage, put back whatever happens.
+        focus_present (True, or a [n] mask with batch % n == 0; needs Unet3D(focus_present=True)): the network's focus-present state
+        for the loop -- "image mode" sampling from a jointly trained checkpoint (Unet3D docstring)."""
         unet = self.denoise_fn
+        if focus_present is not None and focus_present is not False:
+            if not unet.focus_present:
+                raise ValueError('focus_present sampling needs Unet3D(focus_present=True)')
+            unet._focus = unet.resolve_focus(batch, focus_present)
         if self._sample_stream is None:
             self._sample_stream = torch.cuda.Stream(device=self.device)
         cur, st = torch.cuda.current_stream(self.device), self._sample_stream
@@ -320,6 +326,7 @@ class GaussianDiffusion:
                 yield
         finally:
             unet.act_bf16 = keep_storage
+            unet._focus = None
         cur.wait_stream(st)
 
     def _run_chain(self, chain, B, key, *, steps=0, order=2, cond=None, cond_scale=1.0, guidance_rescale=0.0, use_graph=True, x_T=None,
@@ -437,7 +444,7 @@ class GaussianDiffusion:
                                              B, self.channels, per, L.stream_ptr()))
 
     def p_sample_loop(self, shape, key, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None,
-                      guidance_rescale: float = 0.0):
+                      guidance_rescale: float = 0.0, focus_present=None):
         """reference :264-320.  As there, the caller's spatial `shape` is replaced by the model's own (Q10).
 
         x_T = Philox(key, draw 0); step k (t = T-1-k) uses draw 1+k.  Returns unnormalize_img(x_0) in [0,1].
@@ -447,30 +454,30 @@ class GaussianDiffusion:
         phi std(eps(c)) / std(eps_guided) + 1 - phi; 0 = off.
         """
         guidance_rescale = check_guidance_rescale(guidance_rescale)
-        with self._sampling():
+        with self._sampling(focus_present, int(shape[0])):
             return self._run_chain('ddpm', int(shape[0]), key, cond=cond, cond_scale=cond_scale, guidance_rescale=guidance_rescale,
                                    use_graph=use_graph, x_T=x_T)
 
     def ddim_sample_loop(self, shape, key, steps: int = 100, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None,
-                         guidance_rescale: float = 0.0):
+                         guidance_rescale: float = 0.0, focus_present=None):
         """DDIM sampling with eta = 0 in `steps` network evaluations (EXTENSION, BASELINE.json configs[3]; the reference has ancestral
         sampling only).  x_T = Philox(key, draw 0), deterministic afterwards.  Returns unnormalize_img(x_0) in [0, 1].  cond with
         cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         ddim_time_sequence(self.num_timesteps, steps)                     # (its range check, before any device work)
-        with self._sampling():
+        with self._sampling(focus_present, int(shape[0])):
             return self._run_chain('ddim', int(shape[0]), key, steps=int(steps), cond=cond, cond_scale=cond_scale,
                                    guidance_rescale=guidance_rescale, use_graph=use_graph, x_T=x_T)
 
     def dpm_sample_loop(self, shape, key, steps: int = 20, order: int = 2, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True,
-                        x_T=None, guidance_rescale: float = 0.0):
+                        x_T=None, guidance_rescale: float = 0.0, focus_present=None):
         """DPM-Solver++(2M) sampling in `steps` network evaluations (EXTENSION, parity unpinned: no reference code; Lu et al. 2022,
         data-prediction multistep form, the step of vdx.h).  order 2 reaches in 15-25 steps what DDIM (= order 1) needs about 100 for;
         the cost per step is DDIM's plus one history tensor.  x_T = Philox(key, draw 0), deterministic afterwards.  Returns
         unnormalize_img(x_0) in [0, 1].  cond with cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
         check_dpm_args(self.num_timesteps, steps, order)
         guidance_rescale = check_guidance_rescale(guidance_rescale)
-        with self._sampling():
+        with self._sampling(focus_present, int(shape[0])):
             return self._run_chain('dpm', int(shape[0]), key, steps=int(steps), order=order, cond=cond, cond_scale=cond_scale,
                                    guidance_rescale=guidance_rescale, use_graph=use_graph, x_T=x_T)
 
@@ -486,7 +493,7 @@ class GaussianDiffusion:
         return (shard_key(key, rank, world), per) + tuple(None if t is None else t[rank * per:(rank + 1) * per] for t in tensors)
 
     def sample(self, key, cond=None, cond_scale: float = 1.0, batch_size: int = 16, *, ddim_steps: Optional[int] = None,
-               dpm_steps: Optional[int] = None, dpm_order: int = 2, guidance_rescale: float = 0.0, **kw):
+               dpm_steps: Optional[int] = None, dpm_order: int = 2, guidance_rescale: float = 0.0, focus_present=None, **kw):
         """reference :323-357.  ddim_steps (extension): sample with an S-step DDIM chain instead of the T-step ancestral one.
         dpm_steps (extension): an S-step DPM-Solver++(2M) chain of order dpm_order (dpm_sample_loop); not together with ddim_steps.
         guidance_rescale (extension): the rescale phi in [0, 1] of the guided loops (cond given, cond_scale != 1; p_sample_loop).
@@ -502,7 +509,12 @@ class GaussianDiffusion:
                                       'pass a ready [B, 768] tensor instead')
         if cond is not None:
             batch_size = cond.shape[0]
-        key, batch_size, cond = self._shard(key, batch_size, cond)
+        # focus_present (extension): True, or a [batch] mask sharded over the ranks with the batch -- the loops' focus_present
+        fp = focus_present if isinstance(focus_present, (bool, type(None))) else torch.as_tensor(focus_present)
+        if isinstance(fp, torch.Tensor) and fp.shape != (batch_size,):
+            raise ValueError(f'focus_present must be True or a [{batch_size}] mask, got {tuple(fp.shape)}')
+        key, batch_size, cond, fp_shard = self._shard(key, batch_size, cond, fp if isinstance(fp, torch.Tensor) else None)
+        kw['focus_present'] = fp_shard if isinstance(fp, torch.Tensor) else fp
         shape = (batch_size, self.channels, self.num_frames, self.image_size, self.image_size)
         if dpm_steps is not None:
             return self.dpm_sample_loop(shape, key, steps=int(dpm_steps), order=dpm_order, cond=cond, cond_scale=cond_scale, **kw)
@@ -511,7 +523,7 @@ class GaussianDiffusion:
         return self.p_sample_loop(shape, key, cond=cond, cond_scale=cond_scale, **kw)
 
     def inpaint(self, key, video, mask, *, cond=None, cond_scale: float = 1.0, ddim_steps: Optional[int] = None, resample_steps: int = 1,
-                use_graph: bool = True, x_T=None, dpm_steps: Optional[int] = None, dpm_order: int = 2, clean_context: bool = False):
+                use_graph: bool = True, x_T=None, dpm_steps: Optional[int] = None, dpm_order: int = 2, clean_context: bool = False, focus_present=None):
         """Frame-conditioned sampling (EXTENSION): generate the unknown part of `video` ([B,C,F,H,W] in [0,1]) with the
         unconditionally trained denoiser by the replacement method (Ho et al. 2022, sec. 3.1); resample_steps U > 1 adds RePaint
         resampling (Lugmayr et al. 2022, ancestral chain only).  mask: [F], [B,F] or broadcastable to `video`, bool / uint8, 1 = known
@@ -523,6 +535,8 @@ class GaussianDiffusion:
         clean_context=True is for a denoiser trained with frame conditioning (Trainer.frame_cond_max > 0; RaMViD, Hoeppe et al. 2022):
         the known region is `video` itself, un-noised, in the start tensor and after every step of all three chains (the same kernels
         with the (1, 0) mask table, vdx.h), as such a network saw its context frames in training.  Not with resample_steps > 1."""
+        if focus_present is not None:
+            raise ValueError('inpaint / extend do not take focus_present (frame-conditioned sampling of a focus-present sample is out of scope)')
         opts = self._inpaint_options(video, dict(cond_scale=cond_scale, ddim_steps=ddim_steps, resample_steps=resample_steps, use_graph=use_graph,
                                                  x_T=x_T, dpm_steps=dpm_steps, dpm_order=dpm_order, clean_context=clean_context))
         m = frame_mask(mask, tuple(video.shape))

@@ -183,6 +183,40 @@ def attention_forward_bias(x, packed, bias, heads, temporal, mode):
     return y
 
 
+_attn_fwd_focus = L._sig('vdx_attention_forward_focus', C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 8 + [C.c_void_p])
+_attn_present = L._sig('vdx_attention_present_forward', C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p])
+
+
+def attention_forward_focus(x, packed, focus, heads, temporal, mode, bias=None):
+    """The attention block with the per-sample focus-present mask (Unet3D(focus_present=True), a mixed batch): focus [n] bool / uint8
+    with B % n == 0, sample b reads focus[b % n]; a flagged sample's tokens attend to themselves only.  bias: optional pre-softmax
+    [heads, L, L] fp32 as attention_forward_bias.  x fp32 or bfloat16 (mode 'bf16') channel-last [B, F, H, W, C]; y has x's dtype."""
+    B, Fr, H, W, C_ = x.shape
+    Ltok = Fr if temporal else H * W
+    if bias is not None:
+        bias = bias.to(x.device, torch.float32).contiguous()
+        assert tuple(bias.shape) == (heads, Ltok, Ltok)
+    focus = (torch.as_tensor(focus) != 0).to(x.device, torch.uint8).contiguous()
+    assert x.is_contiguous() and focus.dim() == 1 and B % focus.numel() == 0
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    wqkv, bqkv, wo, bo = packed
+    L.check(_attn_fwd_focus(_mode(mode), L.ptr(x), L.ptr(y), _is16(x), L.ptr(wqkv), L.ptr(bqkv), L.ptr(wo), L.ptr(bo), L.ptr(bias),
+                            L.ptr(focus), focus.numel(), B, Fr, H, W, C_, heads, int(temporal), L.stream_ptr()))
+    return y
+
+
+def attention_present_forward(x, packed, heads, temporal, mode, out=None):
+    """The block of an all-focus-present batch in one launch: y = x + bo + Wo . rd(Wv x + bv) (attention_present_kernel).  x fp32 or
+    bfloat16 (mode 'bf16') channel-last [B, F, H, W, C]; y (or `out`) has x's dtype."""
+    B, Fr, H, W, C_ = x.shape
+    assert x.is_contiguous()
+    y = torch.empty(x.shape, dtype=x.dtype, device=x.device) if out is None else out
+    wqkv, bqkv, wo, bo = packed
+    L.check(_attn_present(_mode(mode), L.ptr(x), L.ptr(y), _is16(x), L.ptr(wqkv), L.ptr(bqkv), L.ptr(wo), L.ptr(bo),
+                          B, Fr, H, W, C_, heads, int(temporal), L.stream_ptr()))
+    return y
+
+
 def sla_forward(x, wq, wk, wv, wo, heads, mode):
     """wq/wk/wv: Flax (1, C, 256); wo: (1, 256, C)."""
     B, Fr, H, W, C_ = x.shape
@@ -555,6 +589,32 @@ def attention_core_backward_bias(qkv, d_o, bias, B, Fr, H, W, heads, temporal, b
     scratch = torch.empty(_attn_bias_scr(heads, Ltok), dtype=torch.float32, device=qkv.device)
     L.check(_attn_core_bwd_bias(L.ptr(qkv), L.ptr(d_o), L.ptr(o), L.ptr(dqkv), 3 * HD, _is16(qkv), L.ptr(bias), L.ptr(dbias), L.ptr(scratch),
                                 scratch.numel(), B, Fr, H, W, heads, int(temporal), int(bool(bf16_operands)), L.stream_ptr()))
+    return o, dqkv, dbias
+
+
+_attn_core_bwd_focus = L._sig('vdx_attention_core_backward_focus', C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] +
+                              [C.c_void_p, C.c_int] + [C.c_int] * 7 + [C.c_void_p])
+
+
+def attention_core_backward_focus(qkv, d_o, focus, B, Fr, H, W, heads, temporal, bf16_operands=True, bias=None):
+    """attention_core_backward_bias with the per-sample focus-present mask focus [n] (B % n == 0) -> o, dqkv, dbias (None without bias).
+    For a flagged sample exactly: dq == dk == 0, dv == dO, o == v, and nothing added to dbias."""
+    assert qkv.dtype == d_o.dtype
+    HD = heads * 32
+    Ltok = Fr if temporal else H * W
+    focus = (torch.as_tensor(focus) != 0).to(qkv.device, torch.uint8).contiguous()
+    assert focus.dim() == 1 and B % focus.numel() == 0
+    o = torch.empty(d_o.shape, dtype=d_o.dtype, device=d_o.device)
+    dqkv = torch.empty(d_o.shape[0], 3 * HD, dtype=d_o.dtype, device=d_o.device)
+    dbias = scratch = None
+    if bias is not None:
+        bias = bias.to(qkv.device, torch.float32).contiguous()
+        assert tuple(bias.shape) == (heads, Ltok, Ltok)
+        dbias = torch.zeros_like(bias)
+        scratch = torch.empty(_attn_bias_scr(heads, Ltok), dtype=torch.float32, device=qkv.device)
+    L.check(_attn_core_bwd_focus(L.ptr(qkv), L.ptr(d_o), L.ptr(o), L.ptr(dqkv), 3 * HD, _is16(qkv), L.ptr(bias), L.ptr(dbias), L.ptr(scratch),
+                                 0 if scratch is None else scratch.numel(), L.ptr(focus), focus.numel(), B, Fr, H, W, heads, int(temporal),
+                                 int(bool(bf16_operands)), L.stream_ptr()))
     return o, dqkv, dbias
 
 

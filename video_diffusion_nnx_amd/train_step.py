@@ -83,6 +83,27 @@ def cond_drop_mask(batch: int, p: float, generator=None) -> torch.Tensor:
     return (torch.rand(int(batch), generator=generator) < float(p)).to(torch.uint8)
 
 
+def focus_present_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
+    """Key of the focus-present mask draw of micro-step j of optimizer step `step` (joint image-video training): child 3 of the loss key,
+    the last child that micro_step_keys' `_, noise_key, _ = split(loss_key, 3)` discards.  No other draw uses it (child 1 is the
+    condition dropout's, child 2 the noise's; t and the frame masks hang off the micro-step key), so turning the feature on moves none
+    of the t / noise / frame-mask / condition-dropout streams."""
+    step_key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
+    if j > 0:
+        step_key = split_key(step_key, 3 + j)[-1]
+    loss_key = split_key(step_key, 3)[2]
+    return split_key(loss_key, 3)[2]
+
+
+def focus_present_draw(batch: int, p: float, generator=None) -> torch.Tensor:
+    """The focus-present mask of one micro-batch (Video Diffusion Models, Ho et al. 2022, section 3.1): uint8 [batch], Bernoulli(p),
+    1 = the sample is trained as a bag of images (each frame attends to itself only in the temporal blocks).  Pure host function of
+    (arguments, generator state); p = 0 gives all 0, p = 1 all 1."""
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f'prob_focus_present must be in [0, 1], got {p}')
+    return (torch.rand(int(batch), generator=generator) < float(p)).to(torch.uint8)
+
+
 def frame_cond_masks(batch: int, frames: int, k_max: int, uncond_prob: float = 0.25, mode: str = 'random', generator=None) -> torch.Tensor:
     """The context-frame masks of one micro-batch of frame-conditioned training (RaMViD, Hoeppe et al. 2022): uint8 [batch, frames],
     1 = the frame enters the network clean and carries no loss.  Per sample: with probability uncond_prob no frame is known (the
@@ -107,7 +128,7 @@ def frame_cond_masks(batch: int, frames: int, k_max: int, uncond_prob: float = 0
 
 
 def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, j: int = 0, grads: torch.Tensor = None,
-                     reducer=None, frame_mask=None, cond=None, cond_mask=None) -> torch.Tensor:
+                     reducer=None, frame_mask=None, cond=None, cond_mask=None, focus_present_mask=None) -> torch.Tensor:
     """loss, grads = value_and_grad(p_losses) (trainer.py:337-361) of one micro-batch; returns the device scalar loss.
 
     frame_mask ([F], [B,F] or anything gaussian_diffusion.frame_mask takes; default: drawn by frame_cond_masks under frame_cond_key when
@@ -119,6 +140,10 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     sample, handed to the forward; the backward uses what the forward recorded.  cond_mask [B] (1 = null embedding; default: drawn by
     cond_drop_mask under cond_drop_key when tr.null_cond_prob > 0, else none: every sample sees its condition).  tr.last_cond_mask
     holds the mask as given or drawn.  Without cond nothing here runs, whatever tr.null_cond_prob is.
+
+    focus_present_mask [B] (joint image-video training; needs Unet3D(focus_present=True), without it nothing here runs; default: drawn by
+    focus_present_draw under focus_present_key when 0 < tr.prob_focus_present, else none): the samples whose temporal blocks see each
+    frame alone (Unet3D docstring).  tr.last_focus_mask holds the mask as given or drawn (None without one).
 
     `grads` (default tr.grads) receives the gradient: the head stage of the backward zeroes it.  With a `reducer` the backward runs
     in stage groups and hands finished buckets of tr.grads to it; when `grads` is a second buffer (micro-steps j >= 1), each finished
@@ -169,11 +194,26 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
                 cm = cm.pin_memory().to(dev, non_blocking=True)           # as t: no pageable copy, no host sync
             cm = cm.to(dev).contiguous()
     tr.last_cond_mask = cond_mask if cond is not None else None
+    fp = None
+    if unet.focus_present:
+        p_fp = float(getattr(tr, 'prob_focus_present', 0.0))
+        if focus_present_mask is None and p_fp > 0:
+            g = torch.Generator().manual_seed(focus_present_key(tr.rng_seed, tr.rank, step, j) & 0x7FFFFFFFFFFFFFFF)
+            focus_present_mask = focus_present_draw(B, p_fp, g)
+        if focus_present_mask is not None:
+            fp = torch.as_tensor(focus_present_mask).to(torch.uint8)
+            if fp.shape != (B,):
+                raise ValueError(f'focus_present_mask must be [{B}], got {tuple(fp.shape)}')
+            if p_fp >= 1 and fp.device.type == 'cpu' and bool(fp.all()):
+                fp = True                                                 # p = 1: every sample, the one-launch block (attention_present_kernel)
+            elif fp.device.type == 'cpu' and dev.type == 'cuda':
+                fp = fp.pin_memory().to(dev, non_blocking=True)           # as t: no pageable copy, no host sync
+    tr.last_focus_mask = focus_present_mask if unet.focus_present else None
     x_noisy = gd.q_sample(x, t, noise=noise, frame_mask=mk, _pre=(2.0, -1.0))     # normalize_img folded in (:499)
     keep_storage = unet.act_bf16
     unet.act_bf16 = 2 if (unet.mode == 'bf16' and tr.train_act_bf16) else False
     try:
-        eps_hat = unet(x_noisy, t, cond=cond, cond_mask=cm)
+        eps_hat = unet(x_noisy, t, cond=cond, cond_mask=cm, focus_present_mask=fp)
     finally:
         unet.act_bf16 = keep_storage
     fhw = x.numel() // (B * gd.channels)
@@ -249,28 +289,32 @@ def optimizer_tail(tr, step: int, world: int, accum: int = 1, max_grad_norm=None
 
 
 def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, noise: torch.Tensor = None, frame_mask=None,
-                   cond=None, cond_mask=None) -> torch.Tensor:
+                   cond=None, cond_mask=None, focus_present_mask=None) -> torch.Tensor:
     """loss, grads = value_and_grad(p_losses); Adam; EMA  (trainer.py:337-382) for this rank's shard of the batch.
 
     `t` [B] / `noise` [B,C,F,H,W] override this rank's own draws (the reference threads `noise` through p_losses the same way,
     gaussian_diffusion.py:423-445); the data-parallel tests use them to give N ranks the shards of ONE global draw.  frame_mask: the
     shard's context-frame mask (forward_backward); each shard divides its loss by its own count of noised elements.  cond / cond_mask:
-    the shard's conditions and its condition-dropout mask (forward_backward)."""
+    the shard's conditions and its condition-dropout mask (forward_backward).  focus_present_mask: the shard's focus-present mask
+    (forward_backward)."""
     reducer = tr.make_reducer()
-    loss = forward_backward(tr, batch, step, t, noise, reducer=reducer, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask)
+    loss = forward_backward(tr, batch, step, t, noise, reducer=reducer, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask,
+                            focus_present_mask=focus_present_mask)
     reducer.finish()
     optimizer_tail(tr, step, reducer.world)
     return loss
 
 
-def run_train_step_accum(tr, batches, step: int, ts=None, noises=None, frame_masks=None, conds=None, cond_masks=None) -> torch.Tensor:
+def run_train_step_accum(tr, batches, step: int, ts=None, noises=None, frame_masks=None, conds=None, cond_masks=None,
+                         focus_present_masks=None) -> torch.Tensor:
     """One optimizer step on the mean gradient of K = len(batches) micro-batches of this rank (Trainer.apply_grad_args).
 
     Micro-step 0 is run_train_step's path into tr.grads; micro-steps j >= 1 write tr.micro_grads and are added into tr.grads.  Only the
     last micro-step runs the staged backward and starts the all-reduce, bucket by bucket, after the bucket's accumulation: one
     reduction per optimizer step, still overlapped with the backward.  Returns the mean of the K device losses.  frame_masks: optional
     list of K context-frame masks (forward_backward); every micro-batch divides by its own count, then the K gradients are averaged.
-    conds / cond_masks: optional lists of K conditions / condition-dropout masks (forward_backward)."""
+    conds / cond_masks: optional lists of K conditions / condition-dropout masks (forward_backward).  focus_present_masks: optional
+    list of K focus-present masks (forward_backward)."""
     K = len(batches)
     assert K >= 1
     ts = [None] * K if ts is None else ts
@@ -278,6 +322,7 @@ def run_train_step_accum(tr, batches, step: int, ts=None, noises=None, frame_mas
     fms = [None] * K if frame_masks is None else frame_masks
     cds = [None] * K if conds is None else conds
     cms = [None] * K if cond_masks is None else cond_masks
+    fps = [None] * K if focus_present_masks is None else focus_present_masks
     if K > 1 and getattr(tr, 'micro_grads', None) is None:
         tr.micro_grads = torch.zeros_like(tr.grads)
     reducer = tr.make_reducer()
@@ -286,12 +331,12 @@ def run_train_step_accum(tr, batches, step: int, ts=None, noises=None, frame_mas
         grads = tr.grads if j == 0 else tr.micro_grads
         if j < K - 1:
             losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, frame_mask=fms[j], cond=cds[j],
-                                           cond_mask=cms[j]))
+                                           cond_mask=cms[j], focus_present_mask=fps[j]))
             if j > 0:
                 L.check(vdx_grad_accumulate(L.ptr(tr.grads), L.ptr(grads), grads.numel(), L.stream_ptr()))
         else:
             losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, reducer=reducer, frame_mask=fms[j],
-                                           cond=cds[j], cond_mask=cms[j]))
+                                           cond=cds[j], cond_mask=cms[j], focus_present_mask=fps[j]))
     reducer.finish()
     max_norm = tr.max_grad_norm
     optimizer_tail(tr, step, reducer.world, accum=K, max_grad_norm=max_norm, want_norm=tr.track_grad_norm)

@@ -156,6 +156,11 @@ class Trainer:
     # sample(cond=, cond_scale=) / sample.py --cond-path.  Class attributes for the same reason as the ones above.
     cond_path = None
     null_cond_prob = 0.0
+    # Joint image-video training (extension; Video Diffusion Models, Ho et al. 2022, section 3.1; needs Unet3D(focus_present=True), without
+    # it nothing changes): every sample is focus-present with probability prob_focus_present -- in the temporal blocks each of its frames
+    # attends to itself only, so the sample is trained as a bag of images (train_step.focus_present_draw under
+    # train_step.focus_present_key).  train(prob_focus_present, focus_present_mask) override it for that run.
+    prob_focus_present = 0.0
 
     def __init__(self, diffusion_model, folder: str, *, rng_seed: int = 0, dataset_path: str, num_frames: int = 16,
                  train_batch_size: int = 4, train_lr: float = 1e-4, train_num_steps: int = 100000,
@@ -199,6 +204,7 @@ class Trainer:
         self.last_grad_norm = None                               # device float of the last pre-clip gradient norm
         self.last_frame_mask = None                              # context-frame mask of the last micro-batch (frame_cond_max > 0)
         self.last_cond_mask = None                               # condition-dropout mask of the last micro-batch (null_cond_prob > 0)
+        self.last_focus_mask = None                              # focus-present mask of the last micro-batch (prob_focus_present > 0)
         from .train_step import stage_of_param
         nlev = len(self.unet.dim_mults)
         self.buckets = make_buckets(self.unet.param_table, n, lambda nm: stage_of_param(nm, nlev), stage_of_param('__count__', nlev),
@@ -216,6 +222,8 @@ class Trainer:
         assert len(self.ds) > 0, 'Dataset is empty. Check path and format.'
         if not 0.0 <= float(self.null_cond_prob) <= 1.0:
             raise ValueError(f'null_cond_prob must be in [0, 1], got {self.null_cond_prob}')
+        if not 0.0 <= float(self.prob_focus_present) <= 1.0:
+            raise ValueError(f'prob_focus_present must be in [0, 1], got {self.prob_focus_present}')
         if self.cond_path is not None:
             from .datasets import CondPairs, load_cond_file
             self.ds = CondPairs(self.ds, load_cond_file(self.cond_path, len(self.ds), self.unet.cond_dim))
@@ -290,32 +298,43 @@ class Trainer:
             red.enabled = False
         return red
 
-    def train_step(self, batch: torch.Tensor, step: int, t=None, noise=None, frame_mask=None, cond=None, cond_mask=None) -> torch.Tensor:
+    def train_step(self, batch: torch.Tensor, step: int, t=None, noise=None, frame_mask=None, cond=None, cond_mask=None,
+                   focus_present_mask=None) -> torch.Tensor:
         """One `_pjit_train_step` on this rank's shard of the batch.  Returns the (device) scalar loss of the shard.
         t / noise: optional explicit timesteps / noise of the shard (default: this rank's own Philox draws).  frame_mask: optional
         explicit context-frame mask of the shard ([F] or [B,F], 1 = clean context; default: drawn when frame_cond_max > 0).  cond: the
         shard's conditions [B, cond_dim] (a conditioned UNet needs them); cond_mask: optional explicit condition-dropout mask [B], 1 = null
-        embedding (default: drawn when null_cond_prob > 0)."""
+        embedding (default: drawn when null_cond_prob > 0).  focus_present_mask: optional explicit focus-present mask [B] of the shard
+        (Unet3D(focus_present=True); default: drawn when prob_focus_present > 0)."""
         from .train_step import run_train_step
-        return run_train_step(self, batch, step, t=t, noise=noise, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask)
+        return run_train_step(self, batch, step, t=t, noise=noise, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask,
+                              focus_present_mask=focus_present_mask)
 
     @property
     def accum_steps(self) -> int:
         """Micro-batches per optimizer step: gradient_accumulate_every behind apply_grad_args, else 1."""
         return max(1, int(self.gradient_accumulate_every)) if self.apply_grad_args else 1
 
-    def train_step_accum(self, batches, step: int, ts=None, noises=None, frame_masks=None, conds=None, cond_masks=None) -> torch.Tensor:
+    def train_step_accum(self, batches, step: int, ts=None, noises=None, frame_masks=None, conds=None, cond_masks=None,
+                         focus_present_masks=None) -> torch.Tensor:
         """One optimizer step on K = len(batches) shards of this rank: the gradient is the mean over the K micro-batches (and the
         ranks), clipped to max_grad_norm when that is set.  Returns the (device) mean of the K losses; `last_grad_norm` holds the
-        device float of the pre-clip norm when one was computed.  ts / noises / frame_masks / conds / cond_masks: optional
-        per-micro-batch lists, as train_step's."""
+        device float of the pre-clip norm when one was computed.  ts / noises / frame_masks / conds / cond_masks /
+        focus_present_masks: optional per-micro-batch lists, as train_step's."""
         from .train_step import run_train_step_accum
         assert self.apply_grad_args, 'train_step_accum is the path behind Trainer.apply_grad_args = True'
         return run_train_step_accum(self, list(batches), step, ts=ts, noises=noises, frame_masks=frame_masks, conds=conds,
-                                    cond_masks=cond_masks)
+                                    cond_masks=cond_masks, focus_present_masks=focus_present_masks)
 
-    def train(self, prob_focus_present: float = 0.0, focus_present_mask=None, log_fn=noop):
+    def train(self, prob_focus_present: Optional[float] = None, focus_present_mask=None, log_fn=noop):
+        """The training loop.  prob_focus_present (default: the attribute of that name) / focus_present_mask ([train_batch_size] mask of
+        the GLOBAL batch, used for every step; wins over the probability): joint image-video training, honoured when the network was
+        built with Unet3D(focus_present=True) and without effect otherwise, as in the reference."""
         assert callable(log_fn)
+        if prob_focus_present is not None:
+            if not 0.0 <= float(prob_focus_present) <= 1.0:
+                raise ValueError(f'prob_focus_present must be in [0, 1], got {prob_focus_present}')
+            self.prob_focus_present = float(prob_focus_present)
         logging.info(f'Starting training loop from step {self.step}...')
         import torch.distributed as dist
         from .datasets import DevicePrefetcher
@@ -332,6 +351,10 @@ class Trainer:
             except Exception:                                    # marker library absent: tracing is optional
                 pass
         first_step = self.step
+        fp_kw, fp_kw_accum = {}, {}
+        if focus_present_mask is not None:
+            fp_shard = torch.as_tensor(focus_present_mask).reshape(-1)[lo:hi]
+            fp_kw, fp_kw_accum = {'focus_present_mask': fp_shard}, {'focus_present_masks': [fp_shard] * self.accum_steps}
         while self.step < self.train_num_steps:
             shard = [next(shards) for _ in range(self.accum_steps)] if self.apply_grad_args else next(shards)
             t0 = time.time()
@@ -339,11 +362,11 @@ class Trainer:
             if traced:
                 _range(True, f'train_step {self.step}')
             if self.cond_path is None:
-                loss = self.train_step_accum(shard, self.step) if self.apply_grad_args else self.train_step(shard, self.step)
+                loss = self.train_step_accum(shard, self.step, **fp_kw_accum) if self.apply_grad_args else self.train_step(shard, self.step, **fp_kw)
             elif self.apply_grad_args:                           # the prefetcher hands (video, cond) pairs on
-                loss = self.train_step_accum([s[0] for s in shard], self.step, conds=[s[1] for s in shard])
+                loss = self.train_step_accum([s[0] for s in shard], self.step, conds=[s[1] for s in shard], **fp_kw_accum)
             else:
-                loss = self.train_step(shard[0], self.step, cond=shard[1])
+                loss = self.train_step(shard[0], self.step, cond=shard[1], **fp_kw)
             if traced:
                 _range(False)
             if self.dist_on and self.world > 1:                  # global mean loss = mean of equal-size shard means (C2)

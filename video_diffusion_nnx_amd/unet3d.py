@@ -61,6 +61,8 @@ vdx_set_activation_storage = L._sig('vdx_set_activation_storage', C.c_int, [_vp,
 vdx_set_attention_fp8 = L._sig('vdx_set_attention_fp8', C.c_int, [_vp, C.c_int])
 vdx_set_temporal_pos_bias = L._sig('vdx_set_temporal_pos_bias', C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)])
 vdx_get_temporal_pos_bias = L._sig('vdx_get_temporal_pos_bias', C.c_int, [_vp])
+vdx_set_focus_present = L._sig('vdx_set_focus_present', C.c_int, [_vp, C.c_int, C.c_void_p, C.c_int])
+vdx_get_focus_present = L._sig('vdx_get_focus_present', C.c_int, [_vp])
 vdx_get_activation_storage = L._sig('vdx_get_activation_storage', C.c_int, [_vp])
 vdx_packed_bwd_bytes = L._sig('vdx_packed_bwd_bytes', C.c_size_t, [_vp])
 vdx_pack_params_bwd = L._sig('vdx_pack_params_bwd', C.c_int, [_vp, _vp, _vp, _vp])
@@ -148,12 +150,19 @@ class Unet3D:
     `time_rel_pos_bias.relative_attention_bias.embedding` to its scores before the softmax -- the network can tell frame order.  Off,
     the reference's behaviour: the parameter is dead and the network equivariant under frame permutations.  An architecture argument
     like `dim`: not stored in checkpoints.  Excludes `attn_fp8`.
+    `focus_present` (also a settable attribute; off by default): honour the keywords `focus_present_mask` / `prob_focus_present` of
+    __call__ -- joint image-video training (Video Diffusion Models, Ho et al. 2022, section 3.1).  In the nine temporal attention blocks
+    of downs, mid and ups every frame of a focus-present sample attends to itself only (masked before the softmax: the row is exactly
+    one-hot); `init_temporal_attn` and the mid spatial attention are never masked, and GroupNorm statistics still span the frames, so
+    the frames of such a sample are not independent of each other.  Off, the keywords are accepted and ignored, as in the reference
+    (PreNorm drops them).  Combines with `temporal_pos_bias`; excludes `attn_fp8`.  Not stored in checkpoints.
     """
 
     def __init__(self, dim: int, rngs=0, dim_mults=(1, 2, 4, 8), cond_dim=None, out_dim=None, channels=3,
                  attn_heads=8, attn_dim_head=32, use_bert_text_cond=False, init_dim=None, init_kernel_size=7,
                  use_sparse_linear_attn=True, block_type='resnet', resnet_groups=8, log_dims=False,
-                 *, mode: str = 'bf16', device=None, attn_fp8: bool = False, temporal_pos_bias: bool = False):
+                 *, mode: str = 'bf16', device=None, attn_fp8: bool = False, temporal_pos_bias: bool = False,
+                 focus_present: bool = False):
         assert init_kernel_size % 2 == 1                                       # unet3d.py:105
         self.dim = dim
         self.dim_mults = tuple(dim_mults)
@@ -179,6 +188,13 @@ class Unet3D:
         if attn_fp8 and temporal_pos_bias:
             raise ValueError('attn_fp8 and temporal_pos_bias exclude each other (the fp8 attention cores have no bias form)')
         self.temporal_pos_bias = bool(temporal_pos_bias)
+        if attn_fp8 and focus_present:
+            raise ValueError('attn_fp8 and focus_present exclude each other (the fp8 attention cores have no mask form)')
+        self.focus_present = bool(focus_present)
+        # what the next forward / sampling loop masks (resolve_focus): None, True (every sample) or a [n] uint8 mask; ignored while
+        # focus_present is off.  __call__ sets it from its keywords, GaussianDiffusion's sampling loops for their duration
+        self._focus = None
+        self._focus_bufs: Dict[Tuple[int, int], torch.Tensor] = {}          # (id(handle), n) -> persistent device mask
         # default: the process's CURRENT device (a rank launched by torch.distributed.run has called set_device(LOCAL_RANK))
         if device is not None:
             self.device = torch.device(device)
@@ -332,10 +348,11 @@ class Unet3D:
         """Reverse pass of the LAST __call__ (same inputs, same workspace): accumulates dL/dparams into the flat `grads`
         (zeroed by the head stage).  d_out = dL/d(output) [B,F,H,W,out_dim].  Stages descend from num_stages-1 to 0."""
         assert self._last_fwd is not None, 'backward() needs a preceding forward'
-        x, t32, cond, cm, null_all, B, Fr, S = self._last_fwd
+        x, t32, cond, cm, null_all, B, Fr, S, focus = self._last_fwd
         if stage_hi is None:
             stage_hi = self.num_stages - 1
         h = self.handle(Fr, S)
+        self._apply_focus(h, focus)                       # the mask the forward ran under (a per-sample one: its persistent buffer)
         ws, bws = self.workspace(B, Fr, S), self.bwd_workspace(B, Fr, S)
         L.check(vdx_unet_backward(h.ptr, L.ptr(self.flat_params), L.ptr(self.packed()), L.ptr(self.packed_t()), L.ptr(x), L.ptr(t32),
                                   L.ptr(cond) if self.has_cond else 0, L.ptr(cm), null_all, L.ptr(d_out), L.ptr(ws), L.ptr(bws), bws.numel(),
@@ -347,6 +364,9 @@ class Unet3D:
         L.check(vdx_set_activation_storage(h.ptr, 2 if self.act_bf16 == 2 and self.act_bf16 is not True else int(bool(self.act_bf16))))
         if self.attn_fp8 and self.temporal_pos_bias:
             raise ValueError('attn_fp8 and temporal_pos_bias exclude each other (the fp8 attention cores have no bias form)')
+        if self.attn_fp8 and self.focus_present:
+            raise ValueError('attn_fp8 and focus_present exclude each other (the fp8 attention cores have no mask form)')
+        self._apply_focus(h, self._focus if self.focus_present else None)
         on = int(bool(self.temporal_pos_bias))
         if not on:
             if vdx_get_temporal_pos_bias(h.ptr):
@@ -359,6 +379,49 @@ class Unet3D:
             host = relative_position_buckets(n).to(torch.int32).contiguous().view(-1)
             arr = (C.c_int * (n * n))(*host.tolist())
             L.check(vdx_set_temporal_pos_bias(h.ptr, 1, arr))
+
+    def resolve_focus(self, batch: int, focus_present_mask=None, prob_focus_present=0.0, generator=None):
+        """What a forward over `batch` rows masks: None (nothing), True (every sample) or a uint8 [n] mask with batch % n == 0.  An explicit
+        mask wins over the probability (the reference's default(...)); p == 1 is every sample, p == 0 nothing, in between a Bernoulli
+        draw on the host.  None while the switch is off."""
+        if not self.focus_present:
+            return None
+        if focus_present_mask is not None:
+            if focus_present_mask is True:
+                return True
+            m = torch.as_tensor(focus_present_mask)
+            if m.dim() != 1 or m.numel() < 1 or batch % m.numel():
+                raise ValueError(f'focus_present_mask must be [n] with the batch ({batch}) a multiple of n, got {tuple(m.shape)}')
+            return (m != 0).to(torch.uint8)
+        p = float(prob_focus_present)
+        if p >= 1:
+            return True
+        if p <= 0:
+            return None
+        return (torch.rand(batch, generator=generator) < p).to(torch.uint8)
+
+    def _apply_focus(self, h, focus) -> None:
+        """Put the handle into the focus state `focus` (None | True | [n] mask or its persistent buffer).  A per-sample mask lives in one
+        persistent device buffer per (handle, n), written with copy_: the pointer the handle stores is stable, so cached sampling graphs
+        survive a change of the mask's contents."""
+        if focus is None:
+            if vdx_get_focus_present(h.ptr):
+                L.check(vdx_set_focus_present(h.ptr, 0, None, 0))
+            return
+        if focus is True:
+            L.check(vdx_set_focus_present(h.ptr, 1, None, 0))
+            return
+        key = (id(h), int(focus.numel()))
+        buf = self._focus_bufs.get(key)
+        if buf is None:
+            buf = self._focus_bufs[key] = torch.zeros(focus.numel(), dtype=torch.uint8, device=self.device)
+        if focus is not buf:
+            buf.copy_(focus, non_blocking=True)
+        L.check(vdx_set_focus_present(h.ptr, 2, L.ptr(buf), buf.numel()))
+
+    def focus_buffer(self, h, n: int):
+        """The persistent device mask buffer of (handle, n), or None before its first use."""
+        return self._focus_bufs.get((id(h), int(n)))
 
     def workspace(self, batch: int, frames: int, size: int) -> torch.Tensor:
         key = (batch, frames, size)
@@ -380,8 +443,9 @@ class Unet3D:
                  *, cond_mask=None, out=None):
         """x [B,C,F,H,W], time [B] int -> [B,F,H,W,out_dim] (channel-last, reference unet3d.py:387).
 
-        focus_present_mask / prob_focus_present are accepted and have no effect, exactly as in the reference
-        (PreNorm drops them, modules.py:146-148).
+        focus_present_mask ([n] bool / uint8 with B % n == 0, or True) / prob_focus_present: honoured when the attribute `focus_present`
+        is on (class docstring; resolve_focus); otherwise accepted without effect, exactly as in the reference (PreNorm drops them,
+        modules.py:146-148).
         """
         self._require_gpu()
         assert not (self.has_cond and cond is None), 'cond must be passed in if cond_dim specified'   # unet3d.py:271-273
@@ -404,6 +468,7 @@ class Unet3D:
             else:   # prob_mask_like (utils.py:85-101) with the host generator (Q14)
                 cm = (torch.rand(B, device=self.device) < null_cond_prob).to(torch.uint8)
         h = self.handle(Fr, H)
+        self._focus = self.resolve_focus(B, focus_present_mask, prob_focus_present)
         self.apply_activation_storage(h)
         ws = self.workspace(B, Fr, H)
         if out is None:
@@ -413,7 +478,11 @@ class Unet3D:
         L.check(vdx_unet_forward(h.ptr, L.ptr(self.flat_params), L.ptr(self.packed()), L.ptr(x), L.ptr(t32),
                                  L.ptr(cond) if self.has_cond else 0, L.ptr(cm), null_all, L.ptr(out), L.ptr(ws), ws.numel(), B,
                                  L.stream_ptr()))
-        self._last_fwd = (x, t32, cond if self.has_cond else None, cm, null_all, B, Fr, H)     # inputs kept alive for backward()
+        focus = self._focus if self.focus_present else None
+        if isinstance(focus, torch.Tensor):
+            focus = self.focus_buffer(h, focus.numel())
+        self._focus = None
+        self._last_fwd = (x, t32, cond if self.has_cond else None, cm, null_all, B, Fr, H, focus)     # inputs kept alive for backward()
         return out
 
     def forward_with_cond_scale(self, *args, cond_scale=2.0, **kwargs):
