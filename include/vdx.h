@@ -767,6 +767,18 @@ int vdx_time_mlp_backward(const int* time, const float* w1, const float* b1, con
                           int null_all, int cond_dim, const float* dtemb, float* dw1, float* db1, float* dw2, float* db2, float* dnull, int batch,
                           void* stream);
 
+/* Backward of vdx_resblock_scale_shift as model_bwd.hip's ss_bwd() launches it (launch_resblock_ss_bwd: the LayerNorm backward per
+ * (layer, sample), then the Linear's, then the fixed-order sum of the per-layer d(temb) slots).  The layer table is the forward's;
+ * grads is laid out like params, lin and dss like the forward's lin / ss (layer l, sample b at [out_off * batch + b * n, + n); n <= 2048).
+ * dss holds d(scale|shift) on entry and d(lin) on return.  dW, db, d gamma, d beta of every listed layer (in grads) and
+ * dtemb [batch][temb_dim] are ACCUMULATED: one add per element and call.  slots / slots_cap: scratch of at least
+ * nlayers * batch * temb_dim floats, uninitialised, for the per-layer d(temb) contributions (added in table order: two runs are
+ * bit-identical); NULL with 0, or a capacity below that, adds them with float atomics instead.  nlayers >= 8 gives a workgroup 8 rows of
+ * the Linear, fewer layers 1 (the staged backward passes 2 layers per call). */
+int vdx_resblock_scale_shift_backward(const float* params, float* grads, const float* temb, const vdx_ss_layer* layers_dev, int nlayers,
+                                      const float* lin, float* dss, float* dtemb, int temb_dim, int batch, float* slots, size_t slots_cap,
+                                      void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Train step (reference trainer.py:322-392).
  * ---------------------------------------------------------------------------------------------- */

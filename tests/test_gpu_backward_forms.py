@@ -663,3 +663,18 @@ def test_backward_form_entry_points_reject_invalid_combinations():
         ops.init_conv_backward_weights(z(1, 1, 2, 8, 8), z(1, 2, 8, 8, 16), 4)
     with pytest.raises(VdxError):      # time MLP: dim not a multiple of 4
         ops.time_mlp_backward(torch.zeros(2, dtype=torch.int32, device=DEV), z(6, 24), z(24), z(24, 24), z(24), z(2, 24))
+    # ResnetBlock time-MLP backward: one layer of 32 columns over temb [2, 8]
+    layer = dict(w_off=0, b_off=256, g_off=288, be_off=320, out_off=0, n=32)
+    ss_args = lambda: (z(352), z(352), z(2, 8), [layer], z(64), z(64), z(2, 8))
+    with pytest.raises(VdxError):      # no layers
+        ops.resblock_scale_shift_backward(*ss_args()[:3], [], *ss_args()[4:])
+    with pytest.raises(VdxError):      # a slot capacity without slots
+        ops.resblock_scale_shift_backward(*ss_args(), scratch=None, scratch_floats=64)
+    with pytest.raises(VdxError):      # slots without a capacity
+        ops.resblock_scale_shift_backward(*ss_args(), scratch=z(64), scratch_floats=0)
+    with pytest.raises(VdxError):      # an empty batch
+        ops.resblock_scale_shift_backward(z(352), z(352), z(0, 8), [layer], z(64), z(64), z(0, 8))
+    with pytest.raises(VdxError):      # no d(temb)
+        ops.resblock_scale_shift_backward(*ss_args()[:6], None)
+    with pytest.raises(VdxError):      # one row of the Linear per workgroup: temb_dim beyond the grid
+        ops.resblock_scale_shift_backward(z(352), z(352), z(1, 65536), [layer], z(64), z(64), z(1, 65536))

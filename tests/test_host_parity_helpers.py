@@ -720,3 +720,86 @@ def test_f16_prologue_tile_bound_and_rounding_against_the_final_maximum():
         d, floor = P.view_rels(final, c['cmp'], v).max().item(), P.view_rels(c['emu32'], c['cmp'], v).max().item()
         print(f'[final-maximum emulation] per {n}: {d:.3e} from the running-maximum emulation, flip floor {floor:.3e}')
     assert P.view_rels(final, c['cmp'], P.frame_view).max().item() > P.view_rels(c['emu32'], c['cmp'], P.frame_view).max().item()
+
+
+# ---- ResnetBlock time-MLP backward (tests/test_gpu_ss_backward.py) -----------------------------------------------------------------------
+# The only other check of resblock_ss_bwd_kernel / resblock_ss_bwd_w_kernel is the whole-network gradient test: 5 x tol per tensor, 1e-3 on
+# an f32 network and 0.3 on a bf16 one.  kernel_steps restates the two kernels' steps in fp64; one fault at a time goes in, and each proof
+# states what the per-tensor figures of the faulted layer and the per-(layer, sample) bound on d(lin) make of it.
+
+import _ss_backward_cases as SC
+
+NET_F32, NET_BF16 = 1e-3, 0.3          # 5 x tol of tests/test_gpu_backward.py
+
+
+def _ss_figures(c, out):
+    """-> (worst rel of a dW / db / d gamma / d beta tensor, worst d(lin) group as (rel / bound, rel, bound, layer, sample))"""
+    tens = max(P.rel(out[k][i], c['ref'][k][i]) for k in ('dW', 'db', 'dg', 'dbe') for i in range(len(c['layers'])))
+    groups = [(r / c['b_dlin'][i][1][lab], r, c['b_dlin'][i][1][lab], i, lab) for i in range(len(c['layers']))
+              for lab, r in P.slice_rels(out['dlin'][i], c['ref']['dlin'][i], c['sl'])]
+    return tens, max(groups)
+
+
+@pytest.mark.parametrize('name', ['corner', 't96_b9', 'ragged_kb8', 'offset'])
+def test_ss_backward_kernel_steps_are_the_autograd_reference(name):
+    c = SC.case(name)
+    out = SC.kernel_steps(c['temb'], c['tensors'], c['lin_r'], c['dss_rows'])
+    tens, (ratio, r, bound, i, lab) = _ss_figures(c, out)
+    assert tens < 1e-11 and r < 1e-11 and P.rel(out['dtemb'], c['ref']['dtemb']) < 1e-11
+    # ... and evaluated in fp32 they pass every bound (the bounds leave room for a correct fp32 evaluation in another order)
+    out32 = SC.kernel_steps(c['temb'], c['tensors'], c['lin_r'], c['dss_rows'], dt=torch.float32)
+    for i in range(len(c['layers'])):
+        bound, sb = c['b_dlin'][i]
+        P.assert_exact_products(out32['dlin'][i], c['ref']['dlin'][i], bound, c['sl'], sb, None, f'{name} fp32 steps d(lin) layer {i}')
+        for k in ('dW', 'db', 'dg', 'dbe'):
+            P.assert_exact_products(out32[k][i], c['ref'][k][i], c['b_par'][k][i], what=f'{name} fp32 steps {k} layer {i}')
+    P.assert_exact_products(out32['dtemb'], c['ref']['dtemb'], c['b_dtemb'][0], c['sl'], c['b_dtemb'][1], None, f'{name} fp32 steps d(temb)')
+
+
+def test_ss_backward_norm_eps_ten_times_too_small():
+    """NORM_EPS = 1e-7 instead of 1e-6.  At the widths and embeddings of the table (var(lin) ~ 0.4) the fault moves rstd by 1e-6 of
+    itself: the *.mlp.* tensors move by under 1e-6 -- three orders below the whole-network 1e-3 -- and d(lin) by 1.2e-6 of a (layer,
+    sample), which the 2e-6 bound does NOT reject either: fp32 cannot tell the two epsilons apart there.  The `small_var` case exists for
+    this fault: var(lin) ~ 1e-4, where the per-(layer, sample) bound rejects it by three orders (and where a per-tensor 1e-3 would see
+    it too, had the parity networks such a layer)."""
+    c = SC.case('t96_b19')
+    bad = SC.kernel_steps(c['temb'], c['tensors'], c['lin_r'], c['dss_rows'], eps=R.NORM_EPS / 10)
+    tens, (ratio, r, bound, i, lab) = _ss_figures(c, bad)
+    print(f'[eps / 10, t96_b19] worst *.mlp.* tensor rel {tens:.3e} (whole-network bound {NET_F32:.0e}); worst d(lin) layer {i} {lab} rel {r:.3e} = '
+          f'{ratio:.2f} x its bound {bound:.2e}')
+    assert tens < NET_F32 / 100
+    assert ratio < 1.0, 'the table shapes were not expected to tell 1e-7 from 1e-6'
+    c = SC.case('small_var')
+    var = min(v.double().var(1, unbiased=False).min().item() for v in c['lin_r'])
+    bad = SC.kernel_steps(c['temb'], c['tensors'], c['lin_r'], c['dss_rows'], eps=R.NORM_EPS / 10)
+    tens, (ratio, r, bound, i, lab) = _ss_figures(c, bad)
+    print(f'[eps / 10, small_var: var(lin) >= {var:.1e}] worst tensor rel {tens:.3e}; worst d(lin) layer {i} {lab} rel {r:.3e} = {ratio:.0f} x its bound {bound:.2e}')
+    assert ratio > 100
+    for i in range(len(c['layers'])):
+        with pytest.raises(AssertionError, match='slice'):
+            P.assert_exact_products(bad['dlin'][i], c['ref']['dlin'][i], 10.0, c['sl'], c['b_dlin'][i][1], None, f'eps / 10, layer {i}, per sample only')
+
+
+def test_ss_backward_m2_of_the_previous_sample():
+    """Sample 11 of the 2048-column layer at B = 19 takes m2 from sample 10 (a stale red[] between two rounds of the `for b` loop).
+    d(lin) of that (layer, sample) is off by 3e-2: four orders above its bound.  The layer's tensors: d gamma and d beta do not depend on
+    m2; db moves by 4e-3 and dW by 7e-3 -- ABOVE 1e-3, so an f32 whole-network test does see this one (at B = 2, where one sample is half
+    the sum, by 7e-2); the bf16 networks (0.3) do not, and the N-shape table runs in bf16 only."""
+    c = SC.case('t96_b19')
+    bad = SC.kernel_steps(c['temb'], c['tensors'], c['lin_r'], c['dss_rows'], stale_m2=(2, 11))
+    per = {k: P.rel(bad[k][2], c['ref'][k][2]) for k in ('dW', 'db', 'dg', 'dbe')}
+    tens, (ratio, r, bound, i, lab) = _ss_figures(c, bad)
+    print(f'[stale m2, t96_b19 layer 2 sample 11] tensors {", ".join(f"{k} {v:.3e}" for k, v in per.items())} (whole-network bounds {NET_F32:.0e} f32, '
+          f'{NET_BF16} bf16); d(lin) layer {i} {lab} rel {r:.3e} = {ratio:.0f} x its bound {bound:.2e}; d(temb) rel {P.rel(bad["dtemb"], c["ref"]["dtemb"]):.3e}')
+    assert (i, lab) == (2, 'sample11') and ratio > 1000
+    assert per['dg'] == 0 and per['dbe'] == 0 and NET_F32 < per['db'] < per['dW'] < NET_BF16 / 10      # visible at 1e-3 after all, not at 0.3
+    for j in (0, 1):           # the other layers are untouched
+        P.assert_exact_products(bad['dlin'][j], c['ref']['dlin'][j], c['b_dlin'][j][0], c['sl'], c['b_dlin'][j][1], None, f'stale m2: layer {j}')
+    with pytest.raises(AssertionError, match=r'slice\(s\) over their bound, first sample11'):
+        P.assert_exact_products(bad['dlin'][2], c['ref']['dlin'][2], 10.0, c['sl'], c['b_dlin'][2][1], None, 'stale m2, per sample only')
+    # the network's own corner (B = 2): one sample is half of every sum
+    c = SC.case('corner')
+    bad = SC.kernel_steps(c['temb'], c['tensors'], c['lin_r'], c['dss_rows'], stale_m2=(1, 1))
+    tens, (ratio, r, bound, i, lab) = _ss_figures(c, bad)
+    print(f'[stale m2, corner layer 1 sample 1] worst tensor rel {tens:.3e}; d(lin) layer {i} {lab} rel {r:.3e} = {ratio:.0f} x its bound {bound:.2e}')
+    assert NET_F32 < tens < NET_BF16 and ratio > 1000

@@ -119,14 +119,12 @@ __device__ __forceinline__ float dsilu2_f(float z) {
     return sg * (1.0f + z * (1.0f - sg));
 }
 
-// per-ResnetBlock time MLP backward.  grid = nlayers.  dss (in: d(scale|shift), overwritten by d(lin)) laid out like ss.
-// lin = the forward's pre-LayerNorm values.  dtemb [B][temb_dim] accumulated (atomics across layers).
+// per-ResnetBlock time MLP backward, first half: the LayerNorm.  grid = nlayers.  dss (in: d(scale|shift), overwritten by d(lin)) laid
+// out like ss.  lin = the forward's pre-LayerNorm values.  N <= 2048 (8 columns per thread), as in resblock_ss_norm_kernel.
 __global__ __launch_bounds__(256) void resblock_ss_bwd_kernel(const float* __restrict__ params, float* __restrict__ grads, const float* __restrict__ temb,
                                                               const SsLayer* __restrict__ layers, const float* __restrict__ lin_base,
                                                               float* __restrict__ dss_base, float* __restrict__ dtemb, int temb_dim, int B) {
-    extern __shared__ float sm[];                  // act[B][temb_dim] | red[16]
-    float* act = sm;
-    float* red = sm + (size_t)B * temb_dim;
+    __shared__ float red[16];
     const int tid = threadIdx.x;
     const SsLayer L = layers[blockIdx.x];
     const int N = L.n;
@@ -134,7 +132,12 @@ __global__ __launch_bounds__(256) void resblock_ss_bwd_kernel(const float* __res
     float* db = grads + L.b_off; float* dg = grads + L.g_off; float* dbe = grads + L.be_off;
     const float* lin = lin_base + (size_t)L.out_off * B;
     float* dss = dss_base + (size_t)L.out_off * B;
-    // LayerNorm backward per sample (in place: dss <- dlin), parameter gradients accumulated over samples
+    // this workgroup owns the layer's parameters: their gradients are summed over the samples in registers (sample order, from 0) and
+    // added to grads ONCE at the end -- no atomics, and a call on grads that already hold a value adds exactly the sum a call on zeros stores
+    float adg[8], adbe[8], adb[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) adg[j] = adbe[j] = adb[j] = 0.f;
+    // LayerNorm backward per sample (in place: dss <- dlin)
     for (int b = 0; b < B; ++b) {
         float s = 0.f, ss = 0.f;
         for (int n = tid; n < N; n += 256) { const float v = lin[(size_t)b * N + n]; s += v; ss += v * v; }
@@ -145,23 +148,36 @@ __global__ __launch_bounds__(256) void resblock_ss_bwd_kernel(const float* __res
         s = red[0] + red[1] + red[2] + red[3]; ss = red[4] + red[5] + red[6] + red[7];
         const float mean = s / N, rstd = rsqrtf(fmaxf(ss / N - mean * mean, 0.f) + NORM_EPS);
         float m1 = 0.f, m2 = 0.f;
-        for (int n = tid; n < N; n += 256) {
-            const float xh = (lin[(size_t)b * N + n] - mean) * rstd, d = dss[(size_t)b * N + n], gd = g[n] * d;
-            m1 += gd; m2 += gd * xh;
-            dg[n] += d * xh; dbe[n] += d;                       // this workgroup owns the layer's parameters: no atomics
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int n = tid + 256 * j;
+            if (n < N) {
+                const float xh = (lin[(size_t)b * N + n] - mean) * rstd, d = dss[(size_t)b * N + n], gd = g[n] * d;
+                m1 += gd; m2 += gd * xh;
+                adg[j] += d * xh; adbe[j] += d;
+            }
         }
         for (int o = 1; o < 64; o <<= 1) { m1 += __shfl_xor(m1, o); m2 += __shfl_xor(m2, o); }
         __syncthreads();
         if ((tid & 63) == 0) { red[8 + (tid >> 6)] = m1; red[12 + (tid >> 6)] = m2; }
         __syncthreads();
         m1 = (red[8] + red[9] + red[10] + red[11]) / N; m2 = (red[12] + red[13] + red[14] + red[15]) / N;
-        for (int n = tid; n < N; n += 256) {
-            const float xh = (lin[(size_t)b * N + n] - mean) * rstd;
-            const float dl = rstd * (g[n] * dss[(size_t)b * N + n] - m1 - xh * m2);
-            dss[(size_t)b * N + n] = dl;
-            db[n] += dl;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int n = tid + 256 * j;
+            if (n < N) {
+                const float xh = (lin[(size_t)b * N + n] - mean) * rstd;
+                const float dl = rstd * (g[n] * dss[(size_t)b * N + n] - m1 - xh * m2);
+                dss[(size_t)b * N + n] = dl;
+                adb[j] += dl;
+            }
         }
         __syncthreads();
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int n = tid + 256 * j;
+        if (n < N) { dg[n] += adg[j]; dbe[n] += adbe[j]; db[n] += adb[j]; }
     }
 }
 
@@ -337,10 +353,7 @@ hipError_t launch_init_conv_wgrad(const float* x, const float* dy, float* dW, fl
 
 hipError_t launch_resblock_ss_bwd(const float* params, float* grads, const float* temb, const SsLayer* layers, int nlayers, const float* lin_base,
                                   float* dss_base, float* dtemb, int temb_dim, int B, hipStream_t st, float* part, size_t part_cap) {
-    const size_t lds = ((size_t)B * temb_dim + 16) * 4;
-    auto kfn = resblock_ss_bwd_kernel;
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kfn, dim3(nlayers), dim3(256), lds, st, params, grads, temb, layers, lin_base, dss_base, dtemb, temb_dim, B);
+    hipLaunchKernelGGL(resblock_ss_bwd_kernel, dim3(nlayers), dim3(256), 0, st, params, grads, temb, layers, lin_base, dss_base, dtemb, temb_dim, B);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     // rows of the Linear per workgroup: the per-stage launches of the staged backward cover 2 layers each (data-parallel bucket

@@ -1397,6 +1397,18 @@ int vdx_time_mlp_backward(const int* time, const float* w1, const float* b1, con
     return VDX_OK;
 }
 
+int vdx_resblock_scale_shift_backward(const float* params, float* grads, const float* temb, const vdx_ss_layer* layers_dev, int nlayers,
+                                      const float* lin, float* dss, float* dtemb, int temb_dim, int batch, float* slots, size_t slots_cap,
+                                      void* stream) {
+    if (!params || !grads || !temb || !layers_dev || !lin || !dss || !dtemb) VDX_FAIL(VDX_ERR_INVALID, "scale_shift_backward: null tensor");
+    if (nlayers < 1 || temb_dim < 1 || batch < 1) VDX_FAIL(VDX_ERR_INVALID, "scale_shift_backward: bad geometry");
+    if (temb_dim > 65535) VDX_FAIL(VDX_ERR_INVALID, "scale_shift_backward: temb_dim exceeds the grid (one row of the Linear per workgroup)");
+    if ((slots == nullptr) != (slots_cap == 0)) VDX_FAIL(VDX_ERR_INVALID, "scale_shift_backward: slots and slots_cap go together");
+    VDX_HIP(vdx::launch_resblock_ss_bwd(params, grads, temb, reinterpret_cast<const vdx::SsLayer*>(layers_dev), nlayers, lin, dss, dtemb, temb_dim,
+                                        batch, (hipStream_t)stream, slots, slots_cap));
+    return VDX_OK;
+}
+
 int vdx_num_stages(const vdx_handle* h) { return h ? 2 * h->model.cfg.n_mults + 3 : 0; }
 size_t vdx_packed_bwd_bytes(const vdx_handle* h) { return h ? h->model.packed_t_bytes : 0; }
 size_t vdx_bwd_workspace_bytes(const vdx_handle* h, int batch) { return h ? vdx::model_bwd_workspace_bytes(&h->model, batch) : 0; }

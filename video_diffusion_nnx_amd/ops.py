@@ -335,15 +335,21 @@ def init_conv_ex(x, kernel, bias, mode, y_bf16=False):
     return y
 
 
+def _ss_table(layers, device):
+    """list of dicts (w_off, b_off, g_off, be_off, out_off, n) -> the vdx_ss_layer table as a uint8 device tensor"""
+    tab = (L.SsLayer * len(layers))()
+    for t, l in zip(tab, layers):
+        t.w_off, t.b_off, t.g_off, t.be_off, t.out_off, t.n = l['w_off'], l['b_off'], l['g_off'], l['be_off'], l['out_off'], l['n']
+    # (an empty table is still a valid pointer: the library refuses nlayers = 0 itself)
+    return torch.frombuffer(bytearray(bytes(tab)) or bytearray(C.sizeof(L.SsLayer)), dtype=torch.uint8).to(device)
+
+
 def resblock_scale_shift(params, temb, layers):
     """Every ResnetBlock's (scale, shift) rows in one launch pair.  params: flat fp32 buffer; temb [B, temb_dim]; layers: list of dicts
     (w_off, b_off, g_off, be_off, out_off, n), offsets in floats (out_off per sample).  -> (ss, lin): flat fp32 buffers, layer l /
     sample b at [out_off * B + b * n, + n)."""
     B, temb_dim = temb.shape
-    tab = (L.SsLayer * len(layers))()
-    for t, l in zip(tab, layers):
-        t.w_off, t.b_off, t.g_off, t.be_off, t.out_off, t.n = l['w_off'], l['b_off'], l['g_off'], l['be_off'], l['out_off'], l['n']
-    raw = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(params.device)
+    raw = _ss_table(layers, params.device)
     total = max(l['out_off'] + l['n'] for l in layers) * B
     ss, lin = _nan((total,), torch.float32, params.device), _nan((total,), torch.float32, params.device)
     L.check(L.vdx_resblock_scale_shift(L.ptr(params), L.ptr(temb), L.ptr(raw), len(layers), L.ptr(ss), L.ptr(lin), temb_dim, B,
@@ -695,6 +701,22 @@ def time_mlp_backward(time, w1, b1, w2, b2, dtemb, cond_dim=0, cond_mask=None, n
     L.check(_time_mlp_bwd(L.ptr(t32), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(b2), dim, L.ptr(cm), int(null_all), cond_dim, L.ptr(dtemb),
                           *[L.ptr(t) for t in outs], L.ptr(dnull), B, L.stream_ptr()))
     return (*outs, dnull)
+
+
+_ss_bwd = L._sig('vdx_resblock_scale_shift_backward', C.c_int, [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                                   C.c_void_p])
+
+
+def resblock_scale_shift_backward(params, grads, temb, layers, lin, dss, dtemb, scratch=None, scratch_floats=None):
+    """Backward of resblock_scale_shift over `layers` (the forward's table, or any part of it), in place: dss (d(scale|shift), laid out
+    like the forward's ss) becomes d(lin); grads (flat, laid out like params) and dtemb [B, temb_dim] are accumulated into.  scratch:
+    float32 tensor for the per-layer d(temb) slots (fixed-order sum) or None (float atomics); scratch_floats: the capacity reported
+    instead of scratch.numel()."""
+    B, temb_dim = temb.shape
+    raw = _ss_table(layers, params.device)
+    cap = scratch_floats if scratch_floats is not None else (0 if scratch is None else scratch.numel())
+    L.check(_ss_bwd(L.ptr(params), L.ptr(grads), L.ptr(temb), L.ptr(raw), len(layers), L.ptr(lin), L.ptr(dss), L.ptr(dtemb), temb_dim, B,
+                    L.ptr(scratch), cap, L.stream_ptr()))
 
 
 _loss_grad = L._sig('vdx_loss_grad', C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p])
