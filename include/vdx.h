@@ -228,7 +228,8 @@ int vdx_attention_heads_forward(const void* x, void* y, int io_bf16, const void*
 
 /* Spatial attention over more than 64 tokens as run_attn launches it: 1x1 q|k|v conv -> fp32 core (attention_long_core_kernel) -> 1x1
  * out-projection + bias + residual.  scratch: vdx_attention_long_scratch_bytes, holds qkv [rows][3*heads*32] then o [rows][heads*32],
- * fp32.  io_bf16 needs VDX_MODE_BF16.  h*w <= 64 is VDX_ERR_INVALID. */
+ * fp32.  io_bf16 needs VDX_MODE_BF16.  h*w <= 64 is VDX_ERR_INVALID.  The forward serves every h*w up to 640; the backward of this block
+ * (vdx_unet_backward, vdx_attention_core_backward*) serves the multiples of 64 among them. */
 int vdx_attention_long_forward(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
                                const void* wo_packed, const float* bo, void* scratch, size_t scratch_bytes, int batch, int frames, int h,
                                int w, int c, int heads, void* stream);
@@ -629,11 +630,17 @@ int vdx_norm_act_backward(const float* dact, const float* y, float* dy, const do
 
 /* Attention core backward (autodiff of modules.py:294-323 per sequence and head).  qkv [npix][3*heads*32] = x Wqkv + b
  * (q unscaled), d_o [npix][heads*32] = dy Wo^T; writes o (attention output before the out projection), dq, dk, dv
- * [npix][heads*32].  temporal != 0: sequences over F per (b,h,w), else over (h w) per (b,f). */
+ * [npix][heads*32].  temporal != 0: sequences over F per (b,h,w), else over (h w) per (b,f).
+ * Lengths: up to 64 tokens per sequence in both directions.  Spatial sequences (temporal == 0) are also served at every multiple of 64
+ * up to 640 tokens (the limit of the forward core): a tiled exact-fp32 core on the matrix cores, three launches
+ * (attn_long_bwd_stats / dkv / dq_kernel) without scratch -- between them the three softmax scalars of a row travel in the first
+ * columns of the row's own dq slot, which the last launch overwrites with dq -- no float atomics, bit-reproducible.  Any other h*w above
+ * 64, and temporal != 0 with more than 64 frames, is VDX_ERR_INVALID with nothing launched. */
 int vdx_attention_core_backward(const float* qkv, const float* d_o, float* o, float* dq, float* dk, float* dv, int batch, int frames,
                                 int h, int w, int heads, int temporal, void* stream);
 /* Same with a choice of arithmetic: bf16_operands != 0 = the form a VDX_MODE_BF16 handle's backward uses for sequences of <= 16
- * tokens (q, k, v, d_o rounded to bf16, every product on MFMA, fp32 accumulate); 0 = exact fp32. */
+ * tokens (q, k, v, d_o rounded to bf16, every product on MFMA, fp32 accumulate); 0 = exact fp32.  Above 16 tokens the flag is accepted
+ * and ignored: those cores (17..64 tokens, and the tiled one above 64) compute in fp32 in every mode. */
 int vdx_attention_core_backward_ex(const float* qkv, const float* d_o, float* o, float* dq, float* dk, float* dv, int batch, int frames,
                                    int h, int w, int heads, int temporal, int bf16_operands, void* stream);
 
@@ -716,14 +723,16 @@ int vdx_norm_act_backward_ex(const float* dact, const void* y, int y_bf16, void*
  * dstride = 3 * heads * 32 in the network (a wider row, a multiple of 8, leaves the columns behind dq|dk|dv untouched; dk / dv start
  * heads*32 / 2*heads*32 elements into the row, in the buffer's own element size); io_bf16:
  * qkv, d_o, o, dqkv hold bf16.  bf16 tensors exist for the bf16 MFMA kernel only: io_bf16 without bf16_operands, or with more than
- * 16 tokens per sequence, is VDX_ERR_INVALID. */
+ * 16 tokens per sequence, is VDX_ERR_INVALID.  Lengths as vdx_attention_core_backward: above 64 tokens only spatial sequences of a
+ * multiple of 64 up to 640 tokens, fp32 tensors. */
 int vdx_attention_core_backward_io(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, int batch, int frames,
                                    int h, int w, int heads, int temporal, int bf16_operands, void* stream);
 
 /* vdx_attention_core_backward_io with the pre-softmax bias of vdx_attention_forward_bias: logits = q_i . k_j / sqrt(d) + bias[h][i][j]
  * (bias device fp32 [heads][L][L]); besides o and dqkv it ADDS dBias[h][i][j] = sum over the sequences of dS[h][i][j] into dbias
  * (fp32 [heads][L][L]; the caller zeroes it).  Deterministic: a fixed grid of workgroups stores per-workgroup sums into `scratch`
- * (scratch_floats >= vdx_attention_bias_backward_scratch_floats(heads, L)) and a second pass adds them in order -- no float atomics. */
+ * (scratch_floats >= vdx_attention_bias_backward_scratch_floats(heads, L)) and a second pass adds them in order -- no float atomics.
+ * At most 64 tokens per sequence (this form and the focus form below): more is VDX_ERR_INVALID. */
 size_t vdx_attention_bias_backward_scratch_floats(int heads, int tokens);
 int vdx_attention_core_backward_bias(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias,
                                      float* dbias, float* scratch, size_t scratch_floats, int batch, int frames, int h, int w, int heads,
@@ -791,7 +800,11 @@ int vdx_resblock_scale_shift_backward(const float* params, float* grads, const f
  * packed_t: vdx_pack_params_bwd (transposed packing for the data gradients).
  * The gradients are bit-reproducible run to run (round 3): no sum of the pass depends on the arrival order of workgroups or of the
  * two streams it runs on (per-workgroup partial slots in bwd_workspace + a fixed-order second pass; vdx_bwd_workspace_bytes includes
- * 2 x 48 MB for them). */
+ * 2 x 48 MB for them).
+ * Sizes: at most 64 frames; the bottleneck (image_size >> (levels - 1), squared, tokens per frame) either has at most 64 tokens or a
+ * multiple of 64 up to 640 (sides 16 and 24: e.g. 128 x 128 frames with four levels).  Any other bottleneck above 64 tokens (96 x 96
+ * frames -> 144) is VDX_ERR_INVALID before anything is launched.  The tiled core needs no room in bwd_workspace (see
+ * vdx_attention_core_backward), so a one-level network whose only level has such a token count is served as well. */
 int vdx_num_stages(const vdx_handle* h);
 size_t vdx_packed_bwd_bytes(const vdx_handle* h);
 int vdx_pack_params_bwd(const vdx_handle* h, const float* params, void* packed_t, void* stream);

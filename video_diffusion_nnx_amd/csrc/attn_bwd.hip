@@ -965,8 +965,10 @@ hipError_t launch_pos_bias_scatter(const float* dbias, const int* buckets, float
 hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st) {
     if (a.focus) return launch_attn_core_bwd_focus(a, st);
     if (a.bias) return launch_attn_core_bwd_bias(a, st);
+    if (a.L > 64) return launch_attn_core_bwd_long(a, st);          // multiples of 64 up to 640 tokens (attn_long_bwd.hip); anything else is refused there
     if (a.bf16_mma && a.L <= 16) {
         const long blocks = (a.nseq + 3) / 4;
+        LaunchScope ls(st, "attn_core_bwd16_kernel", 0.0, 0.0, "<io16 %d> L%d nseq%ld heads%d", a.io_bf16, a.L, a.nseq, a.heads);
         if (a.io_bf16) hipLaunchKernelGGL(attn_core_bwd16_kernel<true>, dim3((unsigned)blocks), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
         else hipLaunchKernelGGL(attn_core_bwd16_kernel<false>, dim3((unsigned)blocks), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
         return hipGetLastError();
@@ -974,6 +976,7 @@ hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st) {
     const size_t lds = ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
     auto kfn = attn_core_bwd_kernel;
     if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
+    LaunchScope ls(st, "attn_core_bwd_kernel", 0.0, 0.0, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads);
     hipLaunchKernelGGL(kfn, dim3((unsigned)a.nseq, (unsigned)a.heads), dim3(256), lds, st, a);
     return hipGetLastError();
 }

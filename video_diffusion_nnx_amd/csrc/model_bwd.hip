@@ -344,8 +344,11 @@ int model_backward(const Model* m, BwdState* state, const float* params, const v
     if (bwd_workspace_bytes < model_bwd_workspace_bytes(m, B)) return vdx_set_error(VDX_ERR_NOMEM, "backward: workspace too small", __FILE__, __LINE__);
     {
         const long sb = c.image_size >> (c.n_mults - 1);
-        if (sb * sb > 64 || c.num_frames > 64)
-            return vdx_set_error(VDX_ERR_INVALID, "backward: attention over more than 64 tokens (frames larger than 64 x 64, or more than 64 frames) is forward-only", __FILE__, __LINE__);
+        if (c.num_frames > 64)
+            return vdx_set_error(VDX_ERR_INVALID, "backward: temporal attention over more than 64 frames is not served", __FILE__, __LINE__);
+        if (sb * sb > 64 && !attn_bwd_long_served((int)std::min<long>(sb * sb, 1 << 20)))
+            return vdx_set_error(VDX_ERR_INVALID, "backward: the bottleneck spatial attention runs over more than 64 tokens per frame; above 64 only multiples "
+                                 "of 64 up to 640 tokens are served (bottleneck sides 16 and 24, or non-square counts through the block entry points)", __FILE__, __LINE__);
     }
     if (m->focus && (m->focus == 1 ? !m->d_focus_ones : (!m->focus_mask || m->focus_n < 1 || B % m->focus_n)))
         return vdx_set_error(VDX_ERR_INVALID, "backward: the batch is not a multiple of the focus-present mask's length", __FILE__, __LINE__);

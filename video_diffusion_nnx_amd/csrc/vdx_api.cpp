@@ -1127,7 +1127,8 @@ int vdx_attention_core_backward_ex(const float* qkv, const float* d_o, float* o,
     const long hw = (long)h * w;
     if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
     else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
-    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward: more than 64 tokens per sequence");
+    if (a.L > 64 && temporal) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward: temporal sequences of more than 64 frames are not served");
+    if (a.L > 64 && !vdx::attn_bwd_long_served(a.L)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward: above 64 tokens per sequence only multiples of 64 up to 640 are served");
     a.bf16_mma = bf16_operands ? 1 : 0;
     a.dstride = heads * 32;
     VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
@@ -1261,7 +1262,8 @@ int vdx_attention_core_backward_io(const void* qkv, const void* d_o, void* o, vo
     const long hw = (long)h * w;
     if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
     else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
-    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: more than 64 tokens per sequence");
+    if (a.L > 64 && temporal) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: temporal sequences of more than 64 frames are not served");
+    if (a.L > 64 && !vdx::attn_bwd_long_served(a.L)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: above 64 tokens per sequence only multiples of 64 up to 640 are served");
     // bf16 tensors exist for the bf16 MFMA kernel only (vdx_internal.h AttnBwdArgs::io_bf16): never hand bf16 pointers to the fp32 kernel
     if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: bf16 tensors need bf16_operands and at most 16 tokens per sequence");
     a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
@@ -1281,6 +1283,8 @@ size_t vdx_attention_bias_backward_scratch_floats(int heads, int tokens) {
 int vdx_attention_core_backward_bias(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias,
                                      float* dbias, float* scratch, size_t scratch_floats, int batch, int frames, int h, int w, int heads,
                                      int temporal, int bf16_operands, void* stream) {
+    // (before the null checks: a caller that sizes the scratch by vdx_attention_bias_backward_scratch_floats has none above 64 tokens)
+    if ((temporal ? (long)frames : (long)h * w) > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: this form serves at most 64 tokens per sequence (the plain core alone goes beyond)");
     if (!qkv || !d_o || !o || !dqkv || !bias || !dbias || !scratch || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: bad argument");
     const int HD = heads * 32;
     if (dstride < 3 * HD || dstride % 8) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: dstride must be a multiple of 8, at least 3 * heads * 32 (one [rows][dq|dk|dv] buffer)");
@@ -1289,7 +1293,6 @@ int vdx_attention_core_backward_bias(const void* qkv, const void* d_o, void* o, 
     const long hw = (long)h * w;
     if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
     else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
-    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: more than 64 tokens per sequence");
     if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: bf16 tensors need bf16_operands and at most 16 tokens per sequence");
     if (scratch_floats < vdx::attn_bwd_bias_scratch_floats(heads, a.L)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: scratch too small (vdx_attention_bias_backward_scratch_floats)");
     a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
@@ -1306,6 +1309,8 @@ int vdx_attention_core_backward_bias(const void* qkv, const void* d_o, void* o, 
 int vdx_attention_core_backward_focus(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias_or_null,
                                       float* dbias_or_null, float* scratch, size_t scratch_floats, const unsigned char* focus_dev, int focus_n,
                                       int batch, int frames, int h, int w, int heads, int temporal, int bf16_operands, void* stream) {
+    // (before the null checks: a caller that sizes the scratch by vdx_attention_bias_backward_scratch_floats has none above 64 tokens)
+    if ((temporal ? (long)frames : (long)h * w) > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: this form serves at most 64 tokens per sequence (the plain core alone goes beyond)");
     if (!qkv || !d_o || !o || !dqkv || !focus_dev || focus_n < 1 || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: bad argument");
     if ((bias_or_null != nullptr) != (dbias_or_null != nullptr)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: bias and dbias come together");
     const int HD = heads * 32;
@@ -1315,7 +1320,6 @@ int vdx_attention_core_backward_focus(const void* qkv, const void* d_o, void* o,
     const long hw = (long)h * w;
     if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
     else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
-    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: more than 64 tokens per sequence");
     if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: bf16 tensors need bf16_operands and at most 16 tokens per sequence");
     if (bias_or_null && (!scratch || scratch_floats < vdx::attn_bwd_bias_scratch_floats(heads, a.L))) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: scratch too small (vdx_attention_bias_backward_scratch_floats)");
     a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);

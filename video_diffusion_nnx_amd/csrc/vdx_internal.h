@@ -319,6 +319,11 @@ struct AttnBwdArgs {
 };
 size_t attn_bwd_bias_scratch_floats(int heads, int L);
 hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st);
+// more than 64 tokens (attn_long_bwd.hip): served for L a multiple of 64 up to 640 (attn_bwd_long_served), fp32 tensors, no bias, no focus;
+// three launches (stats -> dkv -> dq) whose per-row softmax scalars travel in the rows' own dq columns, so there is no scratch.
+// launch_attn_core_bwd routes every L > 64 here; anything unserved is hipErrorInvalidValue with nothing launched
+bool attn_bwd_long_served(int L);
+hipError_t launch_attn_core_bwd_long(const AttnBwdArgs& a, hipStream_t st);
 // demb[b][h] = sum over (i, j) with buckets[i * n + j] == b, in (i, j) order, of dbias[h][i][j]   (one thread per (b, h): no atomics)
 hipError_t launch_pos_bias_scatter(const float* dbias, const int* buckets, float* demb, int heads, int n, hipStream_t st);
 // fused attention backward of the widest level (bf16 mode, C == 64, 8 heads x 32, <= 16 tokens): q/k/v recompute, dO = g Wo^T, the

@@ -438,6 +438,9 @@ _sla_core_bwd = L._sig('vdx_sla_core_backward_ex', C.c_int, [C.c_void_p] * 9 + [
 
 
 def attention_core_backward(qkv, d_o, B, Fr, H, W, heads, temporal, bf16_operands=False):
+    """Attention core backward: qkv [rows][3*heads*32] (biased, q unscaled), d_o [rows][heads*32], fp32 -> o, dq, dk, dv.
+    Up to 64 tokens per sequence, spatial or temporal; spatial sequences (temporal=False) also at every multiple of 64 up to 640 tokens
+    (the tiled exact-fp32 core, three launches).  Any other length raises VdxError; bf16_operands only matters up to 16 tokens."""
     outs = [torch.empty_like(d_o) for _ in range(4)]
     L.check(_attn_core_bwd(L.ptr(qkv), L.ptr(d_o), *[L.ptr(t) for t in outs], B, Fr, H, W, heads, int(temporal), int(bool(bf16_operands)),
                            L.stream_ptr()))
@@ -564,7 +567,8 @@ def norm_act_backward_ex(dact, y, stats, gamma, beta, groups=8, scale_shift=None
 
 def attention_core_backward_io(qkv, d_o, B, Fr, H, W, heads, temporal, bf16_operands=True, sentinel=None, pad_cols=0):
     """Interleaved form: qkv / d_o fp32 or bfloat16 (same dtype) -> o [rows][heads*32], dqkv [rows][3*heads*32 + pad_cols] of that dtype
-    (the network's buffer has pad_cols = 0).  sentinel: value dqkv is pre-filled with; the pad columns must keep it."""
+    (the network's buffer has pad_cols = 0).  sentinel: value dqkv is pre-filled with; the pad columns must keep it.
+    Lengths as attention_core_backward: above 64 tokens only spatial sequences of a multiple of 64 up to 640 tokens, fp32 tensors."""
     assert qkv.dtype == d_o.dtype
     HD = heads * 32
     o = torch.empty_like(d_o)
@@ -583,7 +587,7 @@ _attn_core_bwd_bias = L._sig('vdx_attention_core_backward_bias', C.c_int, [C.c_v
 
 def attention_core_backward_bias(qkv, d_o, bias, B, Fr, H, W, heads, temporal, bf16_operands=True):
     """attention_core_backward_io with the pre-softmax bias [heads, L, L] fp32 -> o, dqkv (dtype of qkv), dbias [heads, L, L] fp32
-    (the sum of dS over the sequences; deterministic: per-workgroup slots + an ordered second pass)."""
+    (the sum of dS over the sequences; deterministic: per-workgroup slots + an ordered second pass).  At most 64 tokens per sequence."""
     assert qkv.dtype == d_o.dtype
     HD = heads * 32
     Ltok = Fr if temporal else H * W
@@ -604,7 +608,7 @@ _attn_core_bwd_focus = L._sig('vdx_attention_core_backward_focus', C.c_int, [C.c
 
 def attention_core_backward_focus(qkv, d_o, focus, B, Fr, H, W, heads, temporal, bf16_operands=True, bias=None):
     """attention_core_backward_bias with the per-sample focus-present mask focus [n] (B % n == 0) -> o, dqkv, dbias (None without bias).
-    For a flagged sample exactly: dq == dk == 0, dv == dO, o == v, and nothing added to dbias."""
+    For a flagged sample exactly: dq == dk == 0, dv == dO, o == v, and nothing added to dbias.  At most 64 tokens per sequence."""
     assert qkv.dtype == d_o.dtype
     HD = heads * 32
     Ltok = Fr if temporal else H * W
