@@ -467,14 +467,13 @@ hipError_t attention_block_forward(int mode, AttnArgs a, bool temporal, int NF, 
 
 static hipError_t run_attn(const Fwd& f, const AttnP& ap, const float* x, float* y, int lvl, bool temporal) {
     const Model* m = f.m;
-    const long S = m->cfg.image_size >> lvl, hw = S * S, Fr = m->cfg.num_frames;
+    const long S = m->cfg.image_size >> lvl, Fr = m->cfg.num_frames;
     AttnArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.y = y; a.wqkv = f.pk + ap.pk_qkv; a.bqkv = reinterpret_cast<const float*>(f.pk + ap.pk_bqkv);
     a.wo = f.pk + ap.pk_o; a.bo = f.p + ap.o_b; a.C = ap.C; a.heads = m->cfg.attn_heads;
     a.scale = 1.0f / sqrtf((float)m->cfg.attn_dim_head);
-    if (temporal) { a.L = (int)Fr; a.nseq = f.B * hw; a.inner = hw; a.inner_stride = ap.C; a.outer_stride = Fr * hw * ap.C; a.tok_stride = hw * ap.C; }
-    else { a.L = (int)hw; a.nseq = f.B * Fr; a.inner = 1; a.inner_stride = 0; a.outer_stride = hw * ap.C; a.tok_stride = ap.C; }
+    attn_token_geometry(a, f.B, Fr, S, S, ap.C, temporal);
     a.io_bf16 = f.a16;
     a.fp8_core = (m->attn_fp8 && m->mode == MODE_BF16) ? 1 : 0;
     if (temporal && m->pos_bias) a.pos_bias = m->d_pos_table;  // the mid spatial attention gets none (the reference passes pos_bias to temporal blocks only)

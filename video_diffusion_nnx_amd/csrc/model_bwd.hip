@@ -224,7 +224,8 @@ void attn_bwd(Bwd& b, const AttnP& ap, const float* g, const float* x, int lvl, 
         AttnBwdXArgs f;
         memset(&f, 0, sizeof(f));
         f.x = x; f.x_bf16 = b.a16; f.g = g; f.wqkv = b.pk + ap.pk_qkv; f.bqkv = reinterpret_cast<const float*>(b.pk + ap.pk_bqkv); f.woT = b.pt + ap.pt_o;
-        f.O = O; f.dqkv = dq; f.dx = out; f.L = (int)Fr; f.nseq = b.B * hw; f.inner = hw; f.outer_p = Fr * hw; f.tok_p = hw;
+        f.O = O; f.dqkv = dq; f.dx = out;
+        attn_pixel_geometry(f, b.B, Fr, b.size(lvl), b.size(lvl), true);
         f.scale = 1.0f / sqrtf((float)m->cfg.attn_dim_head);
         b.writes(out);
         b.ok(launch_attn_bwd_fused(f, b.st));
@@ -238,10 +239,8 @@ void attn_bwd(Bwd& b, const AttnP& ap, const float* g, const float* x, int lvl, 
     memset(&a, 0, sizeof(a));
     a.qkv = qkv; a.dO = dO; a.O = O; a.dq = dq; a.heads = H; a.scale = 1.0f / sqrtf((float)m->cfg.attn_dim_head);
     a.dstride = 3 * HD; a.io_bf16 = io16;                                                            // one [rows][dq|dk|dv] buffer
-    if (io16) { a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dq) + HD * 2); a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dq) + 2 * HD * 2); }
-    else { a.dk = dq + HD; a.dv = dq + 2 * HD; }
-    if (temporal) { a.L = (int)Fr; a.nseq = b.B * hw; a.inner = hw; a.outer_p = Fr * hw; a.tok_p = hw; }
-    else { a.L = (int)hw; a.nseq = b.B * Fr; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
+    split_dqkv(dq, HD, io16, a.dk, a.dv);
+    attn_pixel_geometry(a, b.B, Fr, b.size(lvl), b.size(lvl), temporal);
     a.bf16_mma = (m->mode == MODE_BF16);
     // the ten temporal blocks add into ONE accumulator, in the order of the reverse walk (main stream); the stem scatters it to the embedding
     if (biased) { a.bias = m->d_pos_table; a.dbias = m->d_pos_dbias; a.part = b.part_main; a.part_cap = WG_PART_FLOATS; }
@@ -268,8 +267,7 @@ void sla_bwd(Bwd& b, const SlaP& sp, const float* g, const float* x, int lvl, fl
     SlaBwdArgs a;
     memset(&a, 0, sizeof(a));
     a.q = q; a.k = k; a.v = v; a.dOut = dOut; a.O = O; a.dq = dq; a.dstride = 3 * HD; a.io_bf16 = io16; a.A = b.sla_a;
-    if (io16) { a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dq) + HD * 2); a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dq) + 2 * HD * 2); }
-    else { a.dk = dq + HD; a.dv = dq + 2 * HD; }
+    split_dqkv(dq, HD, io16, a.dk, a.dv);
     a.NF = b.B * m->cfg.num_frames; a.N = b.size(lvl) * b.size(lvl); a.heads = m->cfg.attn_heads;
     a.bf16_mma = (m->mode == MODE_BF16);
     b.ok(launch_sla_bwd(a, b.writes(b.S)));

@@ -59,6 +59,10 @@ int vdx_set_error(int code, const char* msg, const char* file, int line) {
 #define VDX_FAIL(code, msg) return vdx_set_error((code), (msg), __FILE__, __LINE__)
 #define VDX_HIP(expr)                                                                   \
     do { hipError_t _e = (expr); if (_e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(_e), __FILE__, __LINE__); } while (0)
+// a refused call of a family's builder: "<entry>: <rule>", so that the rule's text exists once for all the entries of the family
+#define VDX_REFUSE(who, rule) do { char msg_[256]; snprintf(msg_, sizeof(msg_), "%s: %s", (who), (rule)); VDX_FAIL(VDX_ERR_INVALID, msg_); } while (0)
+
+static bool mode_ok(int mode) { return mode == VDX_MODE_F32 || mode == VDX_MODE_BF16 || mode == VDX_MODE_F16; }
 
 // runs `step` nsteps times on `st`: eagerly, or (use_graph) captured once into the handle's graph slot `which` and replayed
 template <class Step>
@@ -94,7 +98,6 @@ static int run_steps(vdx_handle* h, int which, const vdx_handle::GraphKey& key, 
 
 extern "C" {
 
-static void fill_attn_geometry(vdx::AttnArgs& a, int batch, int frames, int h, int w, int c, int temporal);
 static void free_pos_bias(vdx::Model& m);
 
 const char* vdx_last_error(void) { return g_err; }
@@ -104,7 +107,7 @@ size_t vdx_packed_conv_bytes(int mode, int taps, int cin, int cout) { return vdx
 
 int vdx_pack_conv_weights(int mode, const float* kernel, void* packed, int taps, int cin, int cout, void* stream) {
     if (!kernel || !packed || taps <= 0 || cin <= 0 || cout <= 0) VDX_FAIL(VDX_ERR_INVALID, "pack_conv_weights: bad argument");
-    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
+    if (!mode_ok(mode)) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
     VDX_HIP(vdx::launch_pack_weights(mode, kernel, packed, taps, cin, cout, (hipStream_t)stream));
     return VDX_OK;
 }
@@ -115,7 +118,7 @@ size_t vdx_gn_stats_bytes(int batch, int groups) { return (size_t)batch * 32 /*G
 
 static int conv_forward_rows(int mode, const vdx_conv_desc* d, int w_rows, int w_row0, void* stream) {
     if (!d || !d->x0 || !d->packed_w || !d->y) VDX_FAIL(VDX_ERR_INVALID, "conv: null tensor");
-    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
+    if (!mode_ok(mode)) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
     if (d->c0 % 4 || d->c1 % 4 || d->cout % 4) VDX_FAIL(VDX_ERR_INVALID, "conv: channel counts must be multiples of 4");
     if (d->c1 && !d->x1) VDX_FAIL(VDX_ERR_INVALID, "conv: x1 missing");
     if (d->batch <= 0 || d->frames <= 0 || d->h <= 0 || d->w <= 0) VDX_FAIL(VDX_ERR_INVALID, "conv: bad geometry");
@@ -168,33 +171,55 @@ int vdx_conv_forward_rows(int mode, const vdx_conv_desc* d, int w_rows, int w_ro
     return conv_forward_rows(mode, d, w_rows, w_row0, stream);
 }
 
+// ---- the ResnetBlock tail.  What its four entries share: the GroupNorm / LayerNorm operands and the shape rules of the tail kernels
+static int tail_args(vdx::TailArgs& a, const char* who, const void* y2, int y2_bf16, const double* stats, const float* gn_gamma, const float* gn_beta,
+                     int groups, const float* ln_gamma, const float* ln_beta, int c, int batch, long pix_per_sample) {
+    if (!y2 || !stats || !gn_gamma || !gn_beta || !ln_gamma || !ln_beta) VDX_REFUSE(who, "null tensor");
+    if (c < 1 || batch < 1 || pix_per_sample < 1 || groups < 1 || groups > 32 || c % groups)
+        VDX_REFUSE(who, "c, batch and pix_per_sample must be >= 1 and groups (1..32) divide c");
+    memset(&a, 0, sizeof(a));
+    a.y2 = (const float*)y2; a.y2_bf16 = y2_bf16 ? 1 : 0; a.stats = stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.groups = groups;
+    a.ln_gamma = ln_gamma; a.ln_beta = ln_beta; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
+    return VDX_OK;
+}
+// the two rc entries: the fused 1x1 res_conv over concat(x0, x1) stands in for `r`; every tensor is bf16
+static int tail_rc_args(vdx::TailArgs& a, const char* who, const void* x0, const void* x1, int c0, int c1, const void* rc_w_packed, const float* rc_bias) {
+    if (!x0 || !rc_w_packed || !rc_bias || (c1 && !x1)) VDX_REFUSE(who, "null tensor");
+    if (c1 < 0 || !vdx::tail_rc16_supported(c0 + c1, c0, a.C, a.pix_per_sample)) VDX_REFUSE(who, "shape not served");
+    a.y2_bf16 = a.r_bf16 = a.out_bf16 = 1;
+    a.x0 = (const float*)x0; a.x1 = (const float*)x1; a.C0 = c0; a.C1 = c1; a.rc_w = rc_w_packed; a.rc_b = rc_bias;
+    return VDX_OK;
+}
+// vdx_resblock_tail and _ex: `r` is a tensor
+static int tail_r(const char* who, const void* y2, int y2_bf16, const void* r, int r_bf16, void* out, int out_bf16, const double* stats,
+                  const float* gn_gamma, const float* gn_beta, int groups, const float* ln_gamma, const float* ln_beta, int c, int batch,
+                  long pix_per_sample, void* stream) {
+    vdx::TailArgs a;
+    if (int rc = tail_args(a, who, y2, y2_bf16, stats, gn_gamma, gn_beta, groups, ln_gamma, ln_beta, c, batch, pix_per_sample)) return rc;
+    if (!r || !out) VDX_REFUSE(who, "null tensor");
+    if (c % 4 || c > 1024) VDX_REFUSE(who, "c must be a multiple of 4 up to 1024");
+    if ((y2_bf16 || r_bf16 || out_bf16) && c % 8) VDX_REFUSE(who, "bf16 tensors need c % 8 == 0");
+    a.r = (const float*)r; a.r_bf16 = r_bf16 ? 1 : 0; a.out = (float*)out; a.out_bf16 = out_bf16 ? 1 : 0;
+    VDX_HIP(vdx::launch_resblock_tail(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
 int vdx_resblock_tail(const float* y2, const float* r, float* out, const double* stats, const float* gn_gamma,
                       const float* gn_beta, int groups, const float* ln_gamma, const float* ln_beta, int c, int batch,
                       long pix_per_sample, void* stream) {
-    if (!y2 || !r || !out || !stats || !gn_gamma || !gn_beta || !ln_gamma || !ln_beta) VDX_FAIL(VDX_ERR_INVALID, "tail: null tensor");
-    if (c % 4 || c > 1024 || groups <= 0 || groups > 32 || c % groups) VDX_FAIL(VDX_ERR_INVALID, "tail: bad channels/groups");
-    vdx::TailArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y2 = y2; a.r = r; a.out = out; a.stats = stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.groups = groups;
-    a.ln_gamma = ln_gamma; a.ln_beta = ln_beta; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
-    VDX_HIP(vdx::launch_resblock_tail(a, (hipStream_t)stream));
-    return VDX_OK;
+    return tail_r("resblock_tail", y2, 0, r, 0, out, 0, stats, gn_gamma, gn_beta, groups, ln_gamma, ln_beta, c, batch, pix_per_sample, stream);
 }
 
 int vdx_resblock_tail_rc_bf16(const void* y2, const void* x0, const void* x1, int c0, int c1, const void* rc_w_packed,
                               const float* rc_bias, void* out, const double* stats, const float* gn_gamma, const float* gn_beta,
                               int groups, const float* ln_gamma, const float* ln_beta, int c, int batch, long pix_per_sample,
                               void* stream) {
-    if (!y2 || !x0 || !rc_w_packed || !rc_bias || !out || !stats || !gn_gamma || !gn_beta || !ln_gamma || !ln_beta || (c1 && !x1))
-        VDX_FAIL(VDX_ERR_INVALID, "tail_rc: null tensor");
-    if (c1 < 0 || batch < 1 || groups <= 0 || groups > 32 || c % groups || !vdx::tail_rc16_supported(c0 + c1, c0, c, pix_per_sample))
-        VDX_FAIL(VDX_ERR_INVALID, "tail_rc: shape not served");
+    const char* who = "resblock_tail_rc_bf16";
     vdx::TailArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y2 = (const float*)y2; a.y2_bf16 = 1; a.out = (float*)out; a.out_bf16 = 1; a.r_bf16 = 1;
-    a.stats = stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.groups = groups;
-    a.ln_gamma = ln_gamma; a.ln_beta = ln_beta; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
-    a.x0 = (const float*)x0; a.x1 = (const float*)x1; a.C0 = c0; a.C1 = c1; a.rc_w = rc_w_packed; a.rc_b = rc_bias;
+    if (int rc = tail_args(a, who, y2, 1, stats, gn_gamma, gn_beta, groups, ln_gamma, ln_beta, c, batch, pix_per_sample)) return rc;
+    if (!out) VDX_REFUSE(who, "null tensor");
+    if (int rc = tail_rc_args(a, who, x0, x1, c0, c1, rc_w_packed, rc_bias)) return rc;
+    a.out = (float*)out;
     VDX_HIP(vdx::launch_resblock_tail(a, (hipStream_t)stream));
     return VDX_OK;
 }
@@ -236,97 +261,75 @@ int vdx_time_mlp(const int* time, const float* w1, const float* b1, const float*
     return VDX_OK;
 }
 
-int vdx_attention_forward(int mode, const float* x, float* y, const void* wqkv_packed, const float* bqkv,
-                          const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads,
-                          int temporal, void* stream) {
-    return vdx_attention_forward_ex(mode, x, y, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal, 0, stream);
+// ---- the attention block forward.  What its eight entries share: the rules of the block's kernels and the arguments every route reads,
+// the token geometry as the network builds it (attn_token_geometry).  fused_only: the entries of the fused kernels (<= 64 tokens); else the
+// route decides (attention_block_forward)
+static int attn_args(vdx::AttnArgs& a, const char* who, int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
+                     const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads, int temporal, bool fused_only) {
+    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo) VDX_REFUSE(who, "null tensor");
+    if (!mode_ok(mode)) VDX_REFUSE(who, "bad mode");
+    if (io_bf16 && mode != VDX_MODE_BF16) VDX_REFUSE(who, "bf16 tensors need VDX_MODE_BF16");
+    if (batch < 1 || frames < 1 || h < 1 || w < 1 || heads < 1 || c < 4 || c % (io_bf16 ? 8 : 4) || c > 1024)
+        VDX_REFUSE(who, "batch, frames, h, w and heads must be >= 1 and C a multiple of 4 (8 for bf16 tensors) up to 1024");
+    memset(&a, 0, sizeof(a));
+    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
+    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = heads;
+    a.scale = 1.0f / sqrtf(32.0f);
+    vdx::attn_token_geometry(a, batch, frames, h, w, c, temporal != 0);
+    if (fused_only && a.L > 64) VDX_REFUSE(who, "more than 64 tokens per sequence is not supported");
+    return VDX_OK;
 }
 
-int vdx_attention_forward_ex(int mode, const float* x, float* y, const void* wqkv_packed, const float* bqkv,
-                             const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads,
-                             int temporal, int fp8_core, void* stream) {
-    if (fp8_core && mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "attention: the fp8 core needs VDX_MODE_BF16");
-    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo) VDX_FAIL(VDX_ERR_INVALID, "attention: null tensor");
-    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
-    if (c % 4 || c > 1024 || heads < 1) VDX_FAIL(VDX_ERR_INVALID, "attention: C must be a multiple of 4 and <= 1024");
+// vdx_attention_forward, _ex and _bf16: the fused kernels, on fp32 or bf16 tensors, with or without the fp8 core
+static int attn_fused(const char* who, int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv, const void* wo_packed,
+                      const float* bo, int batch, int frames, int h, int w, int c, int heads, int temporal, int fp8_core, void* stream) {
+    if (fp8_core && mode != VDX_MODE_BF16) VDX_REFUSE(who, "the fp8 core needs VDX_MODE_BF16");
     vdx::AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.y = y; a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = heads;
-    a.scale = 1.0f / sqrtf(32.0f);
-    const long hw = (long)h * w;
-    if (temporal) {
-        a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.inner_stride = c; a.outer_stride = (long)frames * hw * c; a.tok_stride = hw * c;
-    } else {
-        a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.inner_stride = 0; a.outer_stride = hw * c; a.tok_stride = c;
-    }
-    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention: more than 64 tokens per sequence is not supported");
+    if (int rc = attn_args(a, who, mode, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal, true)) return rc;
     a.fp8_core = fp8_core ? 1 : 0;
     VDX_HIP(vdx::launch_attention(mode, a, (hipStream_t)stream));
     return VDX_OK;
 }
 
+int vdx_attention_forward(int mode, const float* x, float* y, const void* wqkv_packed, const float* bqkv,
+                          const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads,
+                          int temporal, void* stream) {
+    return attn_fused("attention_forward", mode, x, y, 0, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal, 0, stream);
+}
+
+int vdx_attention_forward_ex(int mode, const float* x, float* y, const void* wqkv_packed, const float* bqkv,
+                             const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads,
+                             int temporal, int fp8_core, void* stream) {
+    return attn_fused("attention_forward_ex", mode, x, y, 0, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal, fp8_core, stream);
+}
+
 int vdx_attention_forward_bf16(const void* x_bf16, void* y_bf16, const void* wqkv_packed, const float* bqkv,
                                const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads,
                                int temporal, int fp8_core, void* stream) {
-    if (!x_bf16 || !y_bf16 || !wqkv_packed || !bqkv || !wo_packed || !bo) VDX_FAIL(VDX_ERR_INVALID, "attention: null tensor");
-    if (c % 8 || c > 1024 || heads < 1) VDX_FAIL(VDX_ERR_INVALID, "attention (bf16 tensors): C must be a multiple of 8 and <= 1024");
-    vdx::AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = reinterpret_cast<const float*>(x_bf16); a.y = reinterpret_cast<float*>(y_bf16); a.io_bf16 = 1;
-    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = heads;
-    a.scale = 1.0f / sqrtf(32.0f);
-    const long hw = (long)h * w;
-    if (temporal) {
-        a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.inner_stride = c; a.outer_stride = (long)frames * hw * c; a.tok_stride = hw * c;
-    } else {
-        a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.inner_stride = 0; a.outer_stride = hw * c; a.tok_stride = c;
-    }
-    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention: more than 64 tokens per sequence is not supported");
-    a.fp8_core = fp8_core ? 1 : 0;
-    VDX_HIP(vdx::launch_attention(VDX_MODE_BF16, a, (hipStream_t)stream));
-    return VDX_OK;
+    return attn_fused("attention_forward_bf16", VDX_MODE_BF16, x_bf16, y_bf16, 1, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal,
+                      fp8_core, stream);
 }
 
 int vdx_attention_forward_bias(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
                                const void* wo_packed, const float* bo, const float* bias, int batch, int frames, int h, int w, int c,
                                int heads, int temporal, void* stream) {
-    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo || !bias) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_bias: null tensor");
-    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
-    if (io_bf16 && mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_bias: bf16 tensors need VDX_MODE_BF16");
-    if (c % (io_bf16 ? 8 : 4) || c > 1024 || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_bias: C must be a multiple of 4 (8 for bf16 tensors) and <= 1024");
+    const char* who = "attention_forward_bias";
     vdx::AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
-    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = heads; a.pos_bias = bias;
-    fill_attn_geometry(a, batch, frames, h, w, c, temporal);
-    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_bias: more than 64 tokens per sequence is not supported");
+    if (int rc = attn_args(a, who, mode, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal, true)) return rc;
+    if (!bias) VDX_REFUSE(who, "null tensor");
+    a.pos_bias = bias;
     // the route of the network's temporal blocks with the switch on (model.hip: attention_block_forward)
     VDX_HIP(vdx::attention_block_forward(mode, a, temporal != 0, batch * frames, frames, h, w, nullptr, 0, vdx::ATTN_ANY, (hipStream_t)stream));
-    return VDX_OK;
-}
-
-// shared checks + arguments of the two focus-present block entries
-static int fill_attn_block(vdx::AttnArgs& a, const char* who, int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
-                           const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads, int temporal) {
-    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo) return vdx_set_error(VDX_ERR_INVALID, who, __FILE__, __LINE__);
-    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) return vdx_set_error(VDX_ERR_INVALID, "bad mode", __FILE__, __LINE__);
-    if (io_bf16 && mode != VDX_MODE_BF16) return vdx_set_error(VDX_ERR_INVALID, "bf16 tensors need VDX_MODE_BF16", __FILE__, __LINE__);
-    if (c < 4 || c % (io_bf16 ? 8 : 4) || c > 1024 || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1)
-        return vdx_set_error(VDX_ERR_INVALID, "C must be a multiple of 4 (8 for bf16 tensors) and <= 1024", __FILE__, __LINE__);
-    memset(&a, 0, sizeof(a));
-    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
-    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = heads;
-    fill_attn_geometry(a, batch, frames, h, w, c, temporal);
     return VDX_OK;
 }
 
 int vdx_attention_forward_focus(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
                                 const void* wo_packed, const float* bo, const float* bias_or_null, const unsigned char* focus_dev, int focus_n,
                                 int batch, int frames, int h, int w, int c, int heads, int temporal, void* stream) {
+    const char* who = "attention_forward_focus";
     vdx::AttnArgs a;
-    if (int rc = fill_attn_block(a, "attention_forward_focus: null tensor", mode, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal)) return rc;
-    if (!focus_dev || focus_n < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_focus: null or empty mask");
-    if (a.L > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_forward_focus: more than 64 tokens per sequence is not supported");
+    if (int rc = attn_args(a, who, mode, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal, true)) return rc;
+    if (!focus_dev || focus_n < 1) VDX_REFUSE(who, "null or empty mask");
     a.pos_bias = bias_or_null; a.focus = focus_dev; a.focus_n = focus_n;
     // the route of the network's masked temporal blocks under vdx_set_focus_present(mode 2) (model.hip: attention_block_forward)
     VDX_HIP(vdx::attention_block_forward(mode, a, temporal != 0, batch * frames, frames, h, w, nullptr, 0, vdx::ATTN_ANY, (hipStream_t)stream));
@@ -337,38 +340,10 @@ int vdx_attention_present_forward(int mode, const void* x, void* y, int io_bf16,
                                   const void* wo_packed, const float* bo, int batch, int frames, int h, int w, int c, int heads, int temporal,
                                   void* stream) {
     vdx::AttnArgs a;
-    if (int rc = fill_attn_block(a, "attention_present_forward: null tensor", mode, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal)) return rc;
+    if (int rc = attn_args(a, "attention_present_forward", mode, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, temporal, false)) return rc;
     a.present = 1;
     // the route of the network's temporal blocks under vdx_set_focus_present(mode 1)
     VDX_HIP(vdx::attention_block_forward(mode, a, temporal != 0, batch * frames, frames, h, w, nullptr, 0, vdx::ATTN_ANY, (hipStream_t)stream));
-    return VDX_OK;
-}
-
-size_t vdx_sla_workspace_bytes(int mode, int nframes, int npix, int heads) { return vdx::sla_workspace_bytes(mode, nframes, npix, heads); }
-
-int vdx_sla_forward(int mode, const float* x, float* y, const void* wq_packed, const void* wk_packed, const void* wv_packed,
-                    const void* wo_packed, void* workspace, int batch, int frames, int h, int w, int c, int heads, void* stream) {
-    if (!x || !y || !wq_packed || !wk_packed || !wv_packed || !wo_packed || !workspace) VDX_FAIL(VDX_ERR_INVALID, "sla: null tensor");
-    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
-    if (heads != 8 || c % 4 || c > 1024) VDX_FAIL(VDX_ERR_INVALID, "sla: needs 8 heads, C multiple of 4 and <= 1024");
-    vdx::SlaArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.y = y; a.wq = wq_packed; a.wk = wk_packed; a.wv = wv_packed; a.wo = wo_packed; a.workspace = workspace;
-    a.C = c; a.heads = heads; a.NF = batch * frames; a.N = h * w;
-    VDX_HIP(vdx::launch_sla(mode, a, (hipStream_t)stream));
-    return VDX_OK;
-}
-
-int vdx_sla_forward_bf16(const void* x_bf16, void* y_bf16, const void* wq_packed, const void* wk_packed, const void* wv_packed,
-                         const void* wo_packed, void* workspace, int batch, int frames, int h, int w, int c, int heads, void* stream) {
-    if (!x_bf16 || !y_bf16 || !wq_packed || !wk_packed || !wv_packed || !wo_packed || !workspace) VDX_FAIL(VDX_ERR_INVALID, "sla: null tensor");
-    if (heads != 8 || c % 8 || c > 1024) VDX_FAIL(VDX_ERR_INVALID, "sla (bf16 tensors): needs 8 heads, C multiple of 8 and <= 1024");
-    vdx::SlaArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = reinterpret_cast<const float*>(x_bf16); a.y = reinterpret_cast<float*>(y_bf16); a.io_bf16 = 1;
-    a.wq = wq_packed; a.wk = wk_packed; a.wv = wv_packed; a.wo = wo_packed; a.workspace = workspace;
-    a.C = c; a.heads = heads; a.NF = batch * frames; a.N = h * w;
-    VDX_HIP(vdx::launch_sla(VDX_MODE_BF16, a, (hipStream_t)stream));
     return VDX_OK;
 }
 
@@ -379,30 +354,18 @@ size_t vdx_attention_long_scratch_bytes(int batch, int frames, int h, int w, int
     return (size_t)batch * frames * h * w * heads * 32 * 4 * sizeof(float);
 }
 
-static void fill_attn_geometry(vdx::AttnArgs& a, int batch, int frames, int h, int w, int c, int temporal) {
-    const long hw = (long)h * w;
-    a.scale = 1.0f / sqrtf(32.0f);
-    if (temporal) {
-        a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.inner_stride = c; a.outer_stride = (long)frames * hw * c; a.tok_stride = hw * c;
-    } else {
-        a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.inner_stride = 0; a.outer_stride = hw * c; a.tok_stride = c;
-    }
-}
-
 int vdx_attention_heads_forward(const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv, const void* wo_packed,
                                 const float* bo, void* o_scratch, size_t o_scratch_bytes, int batch, int frames, int h, int w, int c,
                                 int temporal, int fp8_core, void* stream) {
-    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo || !o_scratch) VDX_FAIL(VDX_ERR_INVALID, "attention_heads: null tensor");
-    if (batch < 1 || frames < 1 || h < 1 || w < 1 || c < 8 || c % 8 || c > 1024) VDX_FAIL(VDX_ERR_INVALID, "attention_heads: bad geometry");
+    const char* who = "attention_heads_forward";
     vdx::AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
-    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = 8;
-    fill_attn_geometry(a, batch, frames, h, w, c, temporal);
+    if (int rc = attn_args(a, who, VDX_MODE_BF16, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, 8, temporal, false)) return rc;
+    if (!o_scratch) VDX_REFUSE(who, "null tensor");
+    if (c % 8) VDX_REFUSE(who, "C must be a multiple of 8");
     a.fp8_core = fp8_core ? 1 : 0;
     const hipError_t e = vdx::attention_block_forward(VDX_MODE_BF16, a, temporal != 0, batch * frames, frames, h, w, o_scratch, o_scratch_bytes,
                                                       vdx::ATTN_HEADS, (hipStream_t)stream);
-    if (e == hipErrorInvalidValue) VDX_FAIL(VDX_ERR_INVALID, "attention_heads: the network does not run this shape on the per-head kernel");
+    if (e == hipErrorInvalidValue) VDX_REFUSE(who, "the network does not run this shape on the per-head kernel");
     VDX_HIP(e);
     return VDX_OK;
 }
@@ -410,33 +373,63 @@ int vdx_attention_heads_forward(const void* x, void* y, int io_bf16, const void*
 int vdx_attention_long_forward(int mode, const void* x, void* y, int io_bf16, const void* wqkv_packed, const float* bqkv,
                                const void* wo_packed, const float* bo, void* scratch, size_t scratch_bytes, int batch, int frames, int h,
                                int w, int c, int heads, void* stream) {
-    if (!x || !y || !wqkv_packed || !bqkv || !wo_packed || !bo || !scratch) VDX_FAIL(VDX_ERR_INVALID, "attention_long: null tensor");
-    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
-    if (io_bf16 && mode != VDX_MODE_BF16) VDX_FAIL(VDX_ERR_INVALID, "attention_long: bf16 tensors need VDX_MODE_BF16");
-    if (batch < 1 || frames < 1 || h < 1 || w < 1 || heads < 1 || c % (io_bf16 ? 8 : 4) || c > 1024) VDX_FAIL(VDX_ERR_INVALID, "attention_long: bad geometry");
+    const char* who = "attention_long_forward";
     vdx::AttnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
-    a.wqkv = wqkv_packed; a.bqkv = bqkv; a.wo = wo_packed; a.bo = bo; a.C = c; a.heads = heads;
-    fill_attn_geometry(a, batch, frames, h, w, c, 0);
+    if (int rc = attn_args(a, who, mode, x, y, io_bf16, wqkv_packed, bqkv, wo_packed, bo, batch, frames, h, w, c, heads, 0, false)) return rc;
+    if (!scratch) VDX_REFUSE(who, "null tensor");
     const hipError_t e = vdx::attention_block_forward(mode, a, false, batch * frames, frames, h, w, scratch, scratch_bytes, vdx::ATTN_LONG, (hipStream_t)stream);
-    if (e == hipErrorInvalidValue) VDX_FAIL(VDX_ERR_INVALID, "attention_long: needs more than 64 tokens per frame and vdx_attention_long_scratch_bytes of scratch");
+    if (e == hipErrorInvalidValue) VDX_REFUSE(who, "needs more than 64 tokens per frame and vdx_attention_long_scratch_bytes of scratch");
     VDX_HIP(e);
     return VDX_OK;
+}
+
+// ---- the SpatialLinearAttention block forward.  What its three entries share: 8 heads x 32 and the rules of the SLA kernels
+size_t vdx_sla_workspace_bytes(int mode, int nframes, int npix, int heads) { return vdx::sla_workspace_bytes(mode, nframes, npix, heads); }
+
+static int sla_args(vdx::SlaArgs& a, const char* who, int mode, const void* x, void* y, int io_bf16, const void* wq_packed, const void* wk_packed,
+                    const void* wv_packed, const void* wo_packed, int batch, int frames, int h, int w, int c, int heads) {
+    if (!x || !y || !wq_packed || !wk_packed || !wv_packed || !wo_packed) VDX_REFUSE(who, "null tensor");
+    if (!mode_ok(mode)) VDX_REFUSE(who, "bad mode");
+    if (batch < 1 || frames < 1 || h < 1 || w < 1 || heads != 8 || c < 4 || c % (io_bf16 ? 8 : 4) || c > 1024)
+        VDX_REFUSE(who, "batch, frames, h and w must be >= 1, heads 8 and C a multiple of 4 (8 for bf16 tensors) up to 1024");
+    memset(&a, 0, sizeof(a));
+    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
+    a.wq = wq_packed; a.wk = wk_packed; a.wv = wv_packed; a.wo = wo_packed;
+    a.C = c; a.heads = heads; a.NF = batch * frames; a.N = h * w;
+    return VDX_OK;
+}
+
+// vdx_sla_forward and _bf16: the generic kernels on fp32 or bf16 tensors
+static int sla_generic(const char* who, int mode, const void* x, void* y, int io_bf16, const void* wq_packed, const void* wk_packed, const void* wv_packed,
+                       const void* wo_packed, void* workspace, int batch, int frames, int h, int w, int c, int heads, void* stream) {
+    vdx::SlaArgs a;
+    if (int rc = sla_args(a, who, mode, x, y, io_bf16, wq_packed, wk_packed, wv_packed, wo_packed, batch, frames, h, w, c, heads)) return rc;
+    if (!workspace) VDX_REFUSE(who, "null tensor");
+    a.workspace = workspace;
+    VDX_HIP(vdx::launch_sla(mode, a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_sla_forward(int mode, const float* x, float* y, const void* wq_packed, const void* wk_packed, const void* wv_packed,
+                    const void* wo_packed, void* workspace, int batch, int frames, int h, int w, int c, int heads, void* stream) {
+    return sla_generic("sla_forward", mode, x, y, 0, wq_packed, wk_packed, wv_packed, wo_packed, workspace, batch, frames, h, w, c, heads, stream);
+}
+
+int vdx_sla_forward_bf16(const void* x_bf16, void* y_bf16, const void* wq_packed, const void* wk_packed, const void* wv_packed,
+                         const void* wo_packed, void* workspace, int batch, int frames, int h, int w, int c, int heads, void* stream) {
+    return sla_generic("sla_forward_bf16", VDX_MODE_BF16, x_bf16, y_bf16, 1, wq_packed, wk_packed, wv_packed, wo_packed, workspace, batch, frames, h, w, c, heads, stream);
 }
 
 int vdx_sla_heads_forward(const void* x, void* y, int io_bf16, const void* wq_packed, const void* wk_packed, const void* wv_packed,
                           const void* wo_packed, void* o_scratch, size_t o_scratch_bytes, int batch, int frames, int h, int w, int c,
                           void* stream) {
-    if (!x || !y || !wq_packed || !wk_packed || !wv_packed || !wo_packed || !o_scratch) VDX_FAIL(VDX_ERR_INVALID, "sla_heads: null tensor");
-    if (batch < 1 || frames < 1 || h < 1 || w < 1 || c < 8 || c % 8 || c > 1024) VDX_FAIL(VDX_ERR_INVALID, "sla_heads: bad geometry");
+    const char* who = "sla_heads_forward";
     vdx::SlaArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x = reinterpret_cast<const float*>(x); a.y = reinterpret_cast<float*>(y); a.io_bf16 = io_bf16 ? 1 : 0;
-    a.wq = wq_packed; a.wk = wk_packed; a.wv = wv_packed; a.wo = wo_packed;
-    a.C = c; a.heads = 8; a.NF = batch * frames; a.N = h * w;
+    if (int rc = sla_args(a, who, VDX_MODE_BF16, x, y, io_bf16, wq_packed, wk_packed, wv_packed, wo_packed, batch, frames, h, w, c, 8)) return rc;
+    if (!o_scratch) VDX_REFUSE(who, "null tensor");
+    if (c % 8) VDX_REFUSE(who, "C must be a multiple of 8");
     const hipError_t e = vdx::sla_block_forward(VDX_MODE_BF16, a, frames, h, w, o_scratch, o_scratch_bytes, vdx::ATTN_HEADS, (hipStream_t)stream);
-    if (e == hipErrorInvalidValue) VDX_FAIL(VDX_ERR_INVALID, "sla_heads: the network does not run this shape on the per-head kernel");
+    if (e == hipErrorInvalidValue) VDX_REFUSE(who, "the network does not run this shape on the per-head kernel");
     VDX_HIP(e);
     return VDX_OK;
 }
@@ -444,34 +437,19 @@ int vdx_sla_heads_forward(const void* x, void* y, int io_bf16, const void* wq_pa
 int vdx_resblock_tail_ex(const void* y2, int y2_bf16, const void* r, int r_bf16, void* out, int out_bf16, const double* stats,
                          const float* gn_gamma, const float* gn_beta, int groups, const float* ln_gamma, const float* ln_beta, int c,
                          int batch, long pix_per_sample, void* stream) {
-    if (!y2 || !r || !out || !stats || !gn_gamma || !gn_beta || !ln_gamma || !ln_beta) VDX_FAIL(VDX_ERR_INVALID, "tail: null tensor");
-    if (c % 4 || c > 1024 || groups <= 0 || groups > 32 || c % groups || batch < 1 || pix_per_sample < 1) VDX_FAIL(VDX_ERR_INVALID, "tail: bad channels/groups");
-    if ((y2_bf16 || r_bf16 || out_bf16) && c % 8) VDX_FAIL(VDX_ERR_INVALID, "tail: bf16 tensors need c % 8 == 0");
-    vdx::TailArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y2 = (const float*)y2; a.r = (const float*)r; a.out = (float*)out;
-    a.y2_bf16 = y2_bf16 ? 1 : 0; a.r_bf16 = r_bf16 ? 1 : 0; a.out_bf16 = out_bf16 ? 1 : 0;
-    a.stats = stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.groups = groups;
-    a.ln_gamma = ln_gamma; a.ln_beta = ln_beta; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
-    VDX_HIP(vdx::launch_resblock_tail(a, (hipStream_t)stream));
-    return VDX_OK;
+    return tail_r("resblock_tail_ex", y2, y2_bf16, r, r_bf16, out, out_bf16, stats, gn_gamma, gn_beta, groups, ln_gamma, ln_beta, c, batch, pix_per_sample, stream);
 }
 
 int vdx_resblock_tail_rc_head_bf16(const void* y2, const void* x0, const void* x1, int c0, int c1, const void* rc_w_packed,
                                    const float* rc_bias, const double* stats, const float* gn_gamma, const float* gn_beta, int groups,
                                    const float* ln_gamma, const float* ln_beta, int c, const float* fin_w, const float* fin_b,
                                    float* fin_out, int batch, long pix_per_sample, void* stream) {
-    if (!y2 || !x0 || !x1 || !rc_w_packed || !rc_bias || !stats || !gn_gamma || !gn_beta || !ln_gamma || !ln_beta || !fin_w || !fin_b || !fin_out)
-        VDX_FAIL(VDX_ERR_INVALID, "tail_rc_head: null tensor");
-    if (c1 != c0 || batch < 1 || groups <= 0 || groups > 32 || c % groups || !((c0 + c1 == 128 && c == 64) || (c0 + c1 == 64 && c == 32)) ||
-        !vdx::tail_rc16_supported(c0 + c1, c0, c, pix_per_sample))
-        VDX_FAIL(VDX_ERR_INVALID, "tail_rc_head: shape not served");
+    const char* who = "resblock_tail_rc_head_bf16";
     vdx::TailArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y2 = (const float*)y2; a.y2_bf16 = 1; a.out_bf16 = 1; a.r_bf16 = 1;
-    a.stats = stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.groups = groups;
-    a.ln_gamma = ln_gamma; a.ln_beta = ln_beta; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
-    a.x0 = (const float*)x0; a.x1 = (const float*)x1; a.C0 = c0; a.C1 = c1; a.rc_w = rc_w_packed; a.rc_b = rc_bias;
+    if (int rc = tail_args(a, who, y2, 1, stats, gn_gamma, gn_beta, groups, ln_gamma, ln_beta, c, batch, pix_per_sample)) return rc;
+    if (!x1 || !fin_w || !fin_b || !fin_out) VDX_REFUSE(who, "null tensor");
+    if (c1 != c0 || !((c0 + c1 == 128 && c == 64) || (c0 + c1 == 64 && c == 32))) VDX_REFUSE(who, "shape not served");
+    if (int rc = tail_rc_args(a, who, x0, x1, c0, c1, rc_w_packed, rc_bias)) return rc;
     a.fin_w = fin_w; a.fin_b = fin_b; a.fin_out = fin_out;
     VDX_HIP(vdx::launch_resblock_tail(a, (hipStream_t)stream));
     return VDX_OK;
@@ -509,7 +487,7 @@ int vdx_resblock_scale_shift(const float* params, const float* temb, const vdx_s
 
 int vdx_create(const vdx_config* cfg, vdx_handle** out) {
     if (!cfg || !out) VDX_FAIL(VDX_ERR_INVALID, "create: null argument");
-    if (cfg->mode != VDX_MODE_F32 && cfg->mode != VDX_MODE_BF16 && cfg->mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
+    if (!mode_ok(cfg->mode)) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
     vdx_handle* h = new vdx_handle();
     h->model.cfg = *cfg;
     int rc = vdx::model_build(&h->model);
@@ -1068,26 +1046,62 @@ int vdx_dpm_sample_loop_guided(vdx_handle* h, const float* params, const void* p
 
 int vdx_pack_conv_weights_t(int mode, const float* kernel, void* packed, int taps, int cin, int cout, void* stream) {
     if (!kernel || !packed || taps <= 0 || cin <= 0 || cout <= 0) VDX_FAIL(VDX_ERR_INVALID, "pack_conv_weights_t: bad argument");
-    if (mode != VDX_MODE_F32 && mode != VDX_MODE_BF16 && mode != VDX_MODE_F16) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
+    if (!mode_ok(mode)) VDX_FAIL(VDX_ERR_INVALID, "bad mode");
     VDX_HIP(vdx::launch_pack_weights_t(mode, kernel, packed, taps, cin, cout, (hipStream_t)stream));
     return VDX_OK;
 }
 
-int vdx_conv_backward_weights(const vdx_wgrad_desc* d, void* stream) {
-    if (!d || !d->x0 || !d->dy || !d->dw) VDX_FAIL(VDX_ERR_INVALID, "wgrad: null tensor");
-    if (d->c0 % 4 || d->c1 % 4 || d->cout % 4 || (d->c1 && !d->x1)) VDX_FAIL(VDX_ERR_INVALID, "wgrad: bad channels");
-    vdx::WgradArgs a;
+}  // extern "C" (a template needs C++ linkage)
+
+// ---- the conv weight gradient.  What vdx_wgrad_desc and vdx_wgrad_ex_desc share, under the same field names: the rules of the wgrad
+// kernels and the arguments of the plain form
+template <class Desc>
+static int wgrad_args(vdx::WgradArgs& a, const char* who, const Desc* d) {
+    if (!d || !d->x0 || !d->dy || !d->dw) VDX_REFUSE(who, "null tensor");
+    if (d->c0 < 4 || d->c0 % 4 || d->c1 < 0 || d->c1 % 4 || d->cout < 4 || d->cout % 4 || (d->c1 && !d->x1)) VDX_REFUSE(who, "bad channels");
+    if (d->batch < 1 || d->frames < 1 || d->h < 1 || d->w < 1) VDX_REFUSE(who, "bad geometry");
+    if (d->kind == 0 && (d->kh != d->kw || d->kh < 1 || d->kh > 4 || (d->stride != 1 && d->stride != 2))) VDX_REFUSE(who, "unsupported kernel/stride");
     memset(&a, 0, sizeof(a));
-    a.x0 = d->x0; a.x1 = d->x1; a.C0 = d->c0; a.C1 = d->c1; a.dy = d->dy; a.Cout = d->cout; a.dW = d->dw;
+    a.x0 = (const float*)d->x0; a.x1 = (const float*)d->x1; a.C0 = d->c0; a.C1 = d->c1; a.dy = (const float*)d->dy; a.Cout = d->cout; a.dW = d->dw;
     a.NF = d->batch * d->frames; a.F = d->frames; a.H = d->h; a.W = d->w;
     a.kind = d->kind; a.kh = d->kind ? 4 : d->kh; a.kw = d->kind ? 4 : d->kw; a.stride = d->kind ? 1 : d->stride;
-    if (d->kind == 0 && (d->kh != d->kw || d->kh < 1 || d->kh > 4 || (d->stride != 1 && d->stride != 2))) VDX_FAIL(VDX_ERR_INVALID, "wgrad: unsupported kernel/stride");
     if (d->in_stats) {
-        if (d->c1 || !d->gamma || !d->beta || d->groups <= 0 || d->groups > 32) VDX_FAIL(VDX_ERR_INVALID, "wgrad: bad prologue");
+        if (d->c1 || !d->gamma || !d->beta || d->groups <= 0 || d->groups > 32 || d->c0 % d->groups) VDX_REFUSE(who, "bad prologue");
+        if (d->scale_shift && d->scale_shift_stride < 2 * d->c0) VDX_REFUSE(who, "scale_shift rows hold scale[c0] | shift[c0]");
         a.pro = 1; a.in_stats = d->in_stats; a.gamma = d->gamma; a.beta = d->beta; a.groups = d->groups; a.ss = d->scale_shift; a.ss_stride = d->scale_shift_stride;
     }
     a.bf16_mma = d->bf16_operands ? 1 : 0;
+    return VDX_OK;
+}
+
+extern "C" {
+
+int vdx_conv_backward_weights(const vdx_wgrad_desc* d, void* stream) {
+    vdx::WgradArgs a;
+    if (int rc = wgrad_args(a, "conv_backward_weights", d)) return rc;
     VDX_HIP(vdx::launch_conv_wgrad(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+// ---- the norm + activation backward: vdx_norm_act_backward is the _ex form on fp32 tensors without the deterministic rows
+static int norm_act_bwd(const char* who, const float* dact, const void* y, int y_bf16, void* dy, int dy_bf16, const double* stats, const float* gamma,
+                        const float* beta, int groups, const float* scale_shift, int scale_shift_stride, float* d_gamma, float* d_beta, float* dss,
+                        const void* r, int r_bf16, const float* ln_gamma, float* dr, float* d_ln_gamma, float* d_ln_beta, float* scratch, float* dgp, int c,
+                        int batch, long pix_per_sample, void* stream) {
+    if (!dact || !y || !dy || !stats || !gamma || !beta || !d_gamma || !d_beta || !scratch) VDX_REFUSE(who, "null tensor");
+    if (r && (!ln_gamma || !dr || !d_ln_gamma || !d_ln_beta)) VDX_REFUSE(who, "incomplete LayerNorm branch");
+    if (r_bf16 && !r) VDX_REFUSE(who, "r_bf16 without r");
+    if (c < 4 || c % 4 || c > 1024 || groups < 1 || groups > 32 || c % groups || batch < 1 || pix_per_sample < 1) VDX_REFUSE(who, "bad channels/groups/shape");
+    if (scale_shift && scale_shift_stride < 2 * c) VDX_REFUSE(who, "scale_shift rows hold scale[c] | shift[c]");
+    vdx::NormBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dact = dact; a.y = (const float*)y; a.y_bf16 = y_bf16 ? 1 : 0; a.dy = (float*)dy; a.dy_bf16 = dy_bf16 ? 1 : 0;
+    a.stats = stats; a.gamma = gamma; a.beta = beta; a.groups = groups;
+    a.ss = scale_shift; a.ss_stride = scale_shift_stride; a.d_gamma = d_gamma; a.d_beta = d_beta; a.dss = dss;
+    a.r = (const float*)r; a.r_bf16 = r_bf16 ? 1 : 0; a.ln_gamma = ln_gamma; a.dr = dr; a.d_ln_gamma = d_ln_gamma; a.d_ln_beta = d_ln_beta;
+    a.R = scratch; a.G = scratch + (vdx::norm_bwd_scratch_floats(c, batch, pix_per_sample) - (size_t)batch * 64);
+    a.dgp = dgp; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
+    VDX_HIP(vdx::launch_norm_bwd(a, (hipStream_t)stream));
     return VDX_OK;
 }
 
@@ -1095,22 +1109,35 @@ int vdx_norm_act_backward(const float* dact, const float* y, float* dy, const do
                           int groups, const float* scale_shift, int scale_shift_stride, float* d_gamma, float* d_beta, float* dss,
                           const float* r, const float* ln_gamma, float* dr, float* d_ln_gamma, float* d_ln_beta, float* scratch,
                           int c, int batch, long pix_per_sample, void* stream) {
-    if (!dact || !y || !dy || !stats || !gamma || !beta || !d_gamma || !d_beta || !scratch) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward: null tensor");
-    if (r && (!ln_gamma || !dr || !d_ln_gamma || !d_ln_beta)) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward: incomplete LayerNorm branch");
-    if (c % 4 || c > 1024 || groups < 1 || groups > 32 || c % groups) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward: bad channels/groups");
-    vdx::NormBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dact = dact; a.y = y; a.dy = dy; a.stats = stats; a.gamma = gamma; a.beta = beta; a.groups = groups;
-    a.ss = scale_shift; a.ss_stride = scale_shift_stride; a.d_gamma = d_gamma; a.d_beta = d_beta; a.dss = dss;
-    a.r = r; a.ln_gamma = ln_gamma; a.dr = dr; a.d_ln_gamma = d_ln_gamma; a.d_ln_beta = d_ln_beta;
-    a.R = scratch; a.G = scratch + (vdx::norm_bwd_scratch_floats(c, batch, pix_per_sample) - (size_t)batch * 64); a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
-    VDX_HIP(vdx::launch_norm_bwd(a, (hipStream_t)stream));
-    return VDX_OK;
+    return norm_act_bwd("norm_act_backward", dact, y, 0, dy, 0, stats, gamma, beta, groups, scale_shift, scale_shift_stride, d_gamma, d_beta, dss, r, 0, ln_gamma,
+                        dr, d_ln_gamma, d_ln_beta, scratch, nullptr, c, batch, pix_per_sample, stream);
 }
 
 size_t vdx_norm_act_backward_scratch_floats(int c, int batch, long pix_per_sample) {
     if (c < 4 || c % 4 || c > 1024 || batch < 1 || pix_per_sample < 1) return 0;
     return vdx::norm_bwd_scratch_floats(c, batch, pix_per_sample);
+}
+
+// ---- the attention core backward.  What its five entries share: the pixel geometry as the network builds it (attn_pixel_geometry), the
+// lengths the cores serve and the outputs' layout.  dk == dv == null: one [rows][dq | dk | dv] buffer at dq with row stride dstride
+// (split_dqkv); else three tensors of row stride heads * 32
+static int attn_bwd_args(vdx::AttnBwdArgs& a, const char* who, const void* qkv, const void* d_o, void* o, void* dq, void* dk, void* dv, int dstride,
+                         int io_bf16, int batch, int frames, int h, int w, int heads, int temporal, int bf16_operands) {
+    const bool interleaved = !dk && !dv;
+    if (!qkv || !d_o || !o || !dq || (!dk != !dv) || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_REFUSE(who, "bad argument");
+    const int HD = heads * 32;
+    if (interleaved && (dstride < 3 * HD || dstride % 8)) VDX_REFUSE(who, "dstride must be a multiple of 8, at least 3 * heads * 32 (one [rows][dq|dk|dv] buffer)");
+    memset(&a, 0, sizeof(a));
+    vdx::attn_pixel_geometry(a, batch, frames, h, w, temporal != 0);
+    if (a.L > 64 && temporal) VDX_REFUSE(who, "temporal sequences of more than 64 frames are not served");
+    if (a.L > 64 && !vdx::attn_bwd_long_served(a.L)) VDX_REFUSE(who, "above 64 tokens per sequence only multiples of 64 up to 640 are served");
+    // bf16 tensors exist for the bf16 MFMA kernel only (vdx_internal.h AttnBwdArgs::io_bf16): never hand bf16 pointers to the fp32 kernel
+    if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_REFUSE(who, "bf16 tensors need bf16_operands and at most 16 tokens per sequence");
+    a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
+    a.dq = (float*)dq; a.dk = (float*)dk; a.dv = (float*)dv;
+    if (interleaved) vdx::split_dqkv(a.dq, HD, io_bf16, a.dk, a.dv);
+    a.dstride = interleaved ? dstride : HD; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
+    return VDX_OK;
 }
 
 int vdx_attention_core_backward(const float* qkv, const float* d_o, float* o, float* dq, float* dk, float* dv, int batch, int frames,
@@ -1120,35 +1147,70 @@ int vdx_attention_core_backward(const float* qkv, const float* d_o, float* o, fl
 
 int vdx_attention_core_backward_ex(const float* qkv, const float* d_o, float* o, float* dq, float* dk, float* dv, int batch, int frames,
                                    int h, int w, int heads, int temporal, int bf16_operands, void* stream) {
-    if (!qkv || !d_o || !o || !dq || !dk || !dv || heads < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward: bad argument");
+    const char* who = "attention_core_backward";
+    if (!dk || !dv) VDX_REFUSE(who, "bad argument");
     vdx::AttnBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.qkv = qkv; a.dO = d_o; a.O = o; a.dq = dq; a.dk = dk; a.dv = dv; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
-    const long hw = (long)h * w;
-    if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
-    else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
-    if (a.L > 64 && temporal) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward: temporal sequences of more than 64 frames are not served");
-    if (a.L > 64 && !vdx::attn_bwd_long_served(a.L)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward: above 64 tokens per sequence only multiples of 64 up to 640 are served");
-    a.bf16_mma = bf16_operands ? 1 : 0;
-    a.dstride = heads * 32;
+    if (int rc = attn_bwd_args(a, who, qkv, d_o, o, dq, dk, dv, 0, 0, batch, frames, h, w, heads, temporal, bf16_operands)) return rc;
     VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+// vdx_attention_core_backward_bias and _focus: the interleaved form on the fixed grid of <= 64 tokens.  focus_form: the mask is required
+// and bias / dbias / scratch are optional (null together); else the bias is required and there is no mask
+static int attn_core_bwd_fixed_grid(const char* who, bool focus_form, const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16,
+                                    const float* bias, float* dbias, float* scratch, size_t scratch_floats, const unsigned char* focus_dev, int focus_n,
+                                    int batch, int frames, int h, int w, int heads, int temporal, int bf16_operands, void* stream) {
+    // (before the null checks: a caller that sizes the scratch by vdx_attention_bias_backward_scratch_floats has none above 64 tokens)
+    if ((temporal ? (long)frames : (long)h * w) > 64) VDX_REFUSE(who, "this form serves at most 64 tokens per sequence (the plain core alone goes beyond)");
+    if (focus_form ? (!focus_dev || focus_n < 1) : (!bias || !dbias || !scratch)) VDX_REFUSE(who, "bad argument");
+    if ((bias != nullptr) != (dbias != nullptr)) VDX_REFUSE(who, "bias and dbias come together");
+    vdx::AttnBwdArgs a;
+    if (int rc = attn_bwd_args(a, who, qkv, d_o, o, dqkv, nullptr, nullptr, dstride, io_bf16, batch, frames, h, w, heads, temporal, bf16_operands)) return rc;
+    if (bias && (!scratch || scratch_floats < vdx::attn_bwd_bias_scratch_floats(heads, a.L))) VDX_REFUSE(who, "scratch too small (vdx_attention_bias_backward_scratch_floats)");
+    if (bias) { a.bias = bias; a.dbias = dbias; a.part = scratch; a.part_cap = scratch_floats; }
+    if (focus_form) { a.focus = focus_dev; a.focus_n = focus_n; }
+    VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+// ---- the fused temporal attention backward: the plain entry is the _ex form on an fp32 x
+static int attn_bwd_fused(const char* who, const void* x, int x_bf16, const float* dy, const void* packed_wqkv, const float* bqkv, const void* packed_wo_t,
+                          void* o_bf16, void* dqkv_bf16, float* dx, int batch, int frames, int h, int w, void* stream) {
+    if (!x || !dy || !packed_wqkv || !bqkv || !packed_wo_t || !o_bf16 || !dqkv_bf16 || !dx) VDX_REFUSE(who, "null argument");
+    if (batch < 1 || frames < 1 || frames > 16 || h < 1 || w < 1) VDX_REFUSE(who, "1..16 frames");
+    vdx::AttnBwdXArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const float*)x; a.x_bf16 = x_bf16 ? 1 : 0; a.g = dy; a.wqkv = packed_wqkv; a.bqkv = bqkv; a.woT = packed_wo_t; a.O = o_bf16; a.dqkv = dqkv_bf16; a.dx = dx;
+    vdx::attn_pixel_geometry(a, batch, frames, h, w, true);
+    a.scale = 1.0f / sqrtf(32.0f);
+    VDX_HIP(vdx::launch_attn_bwd_fused(a, (hipStream_t)stream));
     return VDX_OK;
 }
 
 int vdx_temporal_attention_backward_fused(const float* x, const float* dy, const void* packed_wqkv, const float* bqkv, const void* packed_wo_t,
                                           void* o_bf16, void* dqkv_bf16, float* dx, int batch, int frames, int h, int w, void* stream) {
-    if (!x || !dy || !packed_wqkv || !bqkv || !packed_wo_t || !o_bf16 || !dqkv_bf16 || !dx) VDX_FAIL(VDX_ERR_INVALID, "temporal_attention_backward_fused: null argument");
-    if (batch < 1 || frames < 1 || frames > 16 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "temporal_attention_backward_fused: 1..16 frames");
-    vdx::AttnBwdXArgs a;
-    memset(&a, 0, sizeof(a));
-    const long hw = (long)h * w;
-    a.x = x; a.g = dy; a.wqkv = packed_wqkv; a.bqkv = bqkv; a.woT = packed_wo_t; a.O = o_bf16; a.dqkv = dqkv_bf16; a.dx = dx;
-    a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; a.scale = 1.0f / sqrtf(32.0f);
-    VDX_HIP(vdx::launch_attn_bwd_fused(a, (hipStream_t)stream));
-    return VDX_OK;
+    return attn_bwd_fused("temporal_attention_backward_fused", x, 0, dy, packed_wqkv, bqkv, packed_wo_t, o_bf16, dqkv_bf16, dx, batch, frames, h, w, stream);
 }
 
 size_t vdx_sla_backward_scratch_floats(int nframes, int heads) { return vdx::sla_bwd_scratch_floats(nframes, heads); }
+
+// ---- the SLA core backward.  What its three entries share; the outputs' layout as in attn_bwd_args (256 columns per tensor)
+static int sla_core_bwd(const char* who, const void* q, const void* k, const void* v, const void* d_out, void* o, void* dq, void* dk, void* dv, int dstride,
+                        int io_bf16, float* scratch, int nframes, int npix, int heads, int bf16_operands, void* stream) {
+    const bool interleaved = !dk && !dv;
+    if (!q || !k || !v || !d_out || !o || !dq || (!dk != !dv) || !scratch || heads != 8 || nframes < 1 || npix < 1) VDX_REFUSE(who, "bad argument");
+    if (interleaved && (dstride < 768 || dstride % 8)) VDX_REFUSE(who, "dstride must be a multiple of 8, at least 768 (one [rows][dq|dk|dv] buffer)");
+    if (io_bf16 && !bf16_operands) VDX_REFUSE(who, "bf16 tensors need bf16_operands");
+    vdx::SlaBwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q = (const float*)q; a.k = (const float*)k; a.v = (const float*)v; a.dOut = (const float*)d_out; a.O = (float*)o;
+    a.dq = (float*)dq; a.dk = (float*)dk; a.dv = (float*)dv;
+    if (interleaved) vdx::split_dqkv(a.dq, 256, io_bf16, a.dk, a.dv);
+    a.A = scratch; a.NF = nframes; a.N = npix; a.heads = heads;
+    a.dstride = interleaved ? dstride : 256; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
+    VDX_HIP(vdx::launch_sla_bwd(a, (hipStream_t)stream));
+    return VDX_OK;
+}
 
 int vdx_sla_core_backward(const float* q, const float* k, const float* v, const float* d_out, float* o, float* dq, float* dk, float* dv,
                           float* scratch, int nframes, int npix, int heads, void* stream) {
@@ -1157,14 +1219,8 @@ int vdx_sla_core_backward(const float* q, const float* k, const float* v, const 
 
 int vdx_sla_core_backward_ex(const float* q, const float* k, const float* v, const float* d_out, float* o, float* dq, float* dk, float* dv,
                              float* scratch, int nframes, int npix, int heads, int bf16_operands, void* stream) {
-    if (!q || !k || !v || !d_out || !o || !dq || !dk || !dv || !scratch || heads != 8) VDX_FAIL(VDX_ERR_INVALID, "sla_core_backward: bad argument");
-    vdx::SlaBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.q = q; a.k = k; a.v = v; a.dOut = d_out; a.O = o; a.dq = dq; a.dk = dk; a.dv = dv; a.A = scratch; a.NF = nframes; a.N = npix; a.heads = heads;
-    a.bf16_mma = bf16_operands ? 1 : 0;
-    a.dstride = 256;
-    VDX_HIP(vdx::launch_sla_bwd(a, (hipStream_t)stream));
-    return VDX_OK;
+    if (!dk || !dv) VDX_REFUSE("sla_core_backward", "bad argument");
+    return sla_core_bwd("sla_core_backward", q, k, v, d_out, o, dq, dk, dv, 0, 0, scratch, nframes, npix, heads, bf16_operands, stream);
 }
 
 int vdx_colsum(const float* x, float* out, long rows, int c, void* stream) {
@@ -1176,43 +1232,33 @@ int vdx_colsum(const float* x, float* out, long rows, int c, void* stream) {
 // ---- test-facing entry points for the forms only vdx_unet_backward sets on the launchers (vdx.h: "Backward forms of the network") ----
 
 int vdx_conv_backward_weights_ex(const vdx_wgrad_ex_desc* d, void* stream) {
-    if (!d || !d->x0 || !d->dy || !d->dw) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: null tensor");
-    if (d->c0 < 4 || d->c0 % 4 || d->c1 < 0 || d->c1 % 4 || d->cout < 4 || d->cout % 4 || (d->c1 && !d->x1)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bad channels");
-    if (d->batch < 1 || d->frames < 1 || d->h < 1 || d->w < 1) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bad geometry");
-    if (d->kind != 0 && d->kind != 1) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bad kind");
+    const char* who = "conv_backward_weights_ex";
+    vdx::WgradArgs a;
+    if (int rc = wgrad_args(a, who, d)) return rc;
+    if (d->kind != 0 && d->kind != 1) VDX_REFUSE(who, "bad kind");
     // only the forms model_bwd.hip launches: 1x1 and 3x3 at stride 1, Downsample 4x4 at stride 2, Upsample (kind 1)
     if (d->kind == 0) {
         const bool s1 = d->stride == 1 && d->kh == d->kw && (d->kh == 1 || d->kh == 3);
         const bool s2 = d->stride == 2 && d->kh == 4 && d->kw == 4;
-        if (!s1 && !s2) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: kernel/stride must be 1x1 or 3x3 at stride 1, or 4x4 at stride 2");
-        if (s2 && (d->h % 2 || d->w % 2)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: stride 2 needs even H, W");
+        if (!s1 && !s2) VDX_REFUSE(who, "kernel/stride must be 1x1 or 3x3 at stride 1, or 4x4 at stride 2");
+        if (s2 && (d->h % 2 || d->w % 2)) VDX_REFUSE(who, "stride 2 needs even H, W");
     }
-    if (d->in_stats && (d->kind != 0 || d->kh != 3 || d->stride != 1 || d->split)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: the prologue form is the 3x3 stride-1 conv without split");
-    if (d->split && (d->kind != 0 || d->kh != 1)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: split is the 1x1 (q|k|v projection) form");
-    if ((d->x_bf16 || d->dy_bf16) && !d->bf16_operands) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bf16 tensors need bf16_operands (the exact-f32 kernel reads fp32 tensors only)");
-    if (d->x_bf16 && (d->c0 % 8 || d->c1 % 8)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bf16 inputs need channel counts that are multiples of 8");
-    if (d->dy_bf16 && d->cout % 8) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: a bf16 dy needs cout a multiple of 8");
+    if (d->in_stats && (d->kind != 0 || d->kh != 3 || d->stride != 1 || d->split)) VDX_REFUSE(who, "the prologue form is the 3x3 stride-1 conv without split");
+    if (d->split && (d->kind != 0 || d->kh != 1)) VDX_REFUSE(who, "split is the 1x1 (q|k|v projection) form");
+    if ((d->x_bf16 || d->dy_bf16) && !d->bf16_operands) VDX_REFUSE(who, "bf16 tensors need bf16_operands (the exact-f32 kernel reads fp32 tensors only)");
+    if (d->x_bf16 && (d->c0 % 8 || d->c1 % 8)) VDX_REFUSE(who, "bf16 inputs need channel counts that are multiples of 8");
+    if (d->dy_bf16 && d->cout % 8) VDX_REFUSE(who, "a bf16 dy needs cout a multiple of 8");
     if (d->split) {
         // a 64-wide output tile never straddles two tensors (wgrad.hip); at most three targets
-        if (d->split < 0 || d->split % 64 || d->cout % d->split || d->cout / d->split > 3) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: split must be a multiple of 64 that divides cout into at most 3 blocks");
+        if (d->split < 0 || d->split % 64 || d->cout % d->split || d->cout / d->split > 3) VDX_REFUSE(who, "split must be a multiple of 64 that divides cout into at most 3 blocks");
         const int nb = d->cout / d->split;
-        if ((nb >= 2 && !d->dw1) || (nb >= 3 && !d->dw2)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: split needs dw1 / dw2");
-        if (d->db && ((nb >= 2 && !d->db1) || (nb >= 3 && !d->db2))) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: split with db needs db1 / db2");
-    } else if (d->dw1 || d->dw2 || d->db1 || d->db2) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: dw1 / dw2 / db1 / db2 need split");
-    if (!d->db && (d->db1 || d->db2)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: db1 / db2 need db");
-    if ((d->scratch == nullptr) != (d->scratch_floats == 0)) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: scratch and scratch_floats go together");
-    vdx::WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x0 = (const float*)d->x0; a.x1 = (const float*)d->x1; a.C0 = d->c0; a.C1 = d->c1; a.dy = (const float*)d->dy; a.Cout = d->cout;
-    a.dW = d->dw; a.dW1 = d->dw1; a.dW2 = d->dw2; a.db = d->db; a.db1 = d->db1; a.db2 = d->db2; a.split = d->split;
-    a.NF = d->batch * d->frames; a.F = d->frames; a.H = d->h; a.W = d->w;
-    a.kind = d->kind; a.kh = d->kind ? 4 : d->kh; a.kw = d->kind ? 4 : d->kw; a.stride = d->kind ? 1 : d->stride;
-    if (d->in_stats) {
-        if (d->c1 || !d->gamma || !d->beta || d->groups <= 0 || d->groups > 32 || d->c0 % d->groups) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: bad prologue");
-        if (d->scale_shift && d->scale_shift_stride < 2 * d->c0) VDX_FAIL(VDX_ERR_INVALID, "wgrad_ex: scale_shift rows hold scale[c0] | shift[c0]");
-        a.pro = 1; a.in_stats = d->in_stats; a.gamma = d->gamma; a.beta = d->beta; a.groups = d->groups; a.ss = d->scale_shift; a.ss_stride = d->scale_shift_stride;
-    }
-    a.x0_bf16 = d->x_bf16 ? 1 : 0; a.dy_bf16 = d->dy_bf16 ? 1 : 0; a.bf16_mma = d->bf16_operands ? 1 : 0;
+        if ((nb >= 2 && !d->dw1) || (nb >= 3 && !d->dw2)) VDX_REFUSE(who, "split needs dw1 / dw2");
+        if (d->db && ((nb >= 2 && !d->db1) || (nb >= 3 && !d->db2))) VDX_REFUSE(who, "split with db needs db1 / db2");
+    } else if (d->dw1 || d->dw2 || d->db1 || d->db2) VDX_REFUSE(who, "dw1 / dw2 / db1 / db2 need split");
+    if (!d->db && (d->db1 || d->db2)) VDX_REFUSE(who, "db1 / db2 need db");
+    if ((d->scratch == nullptr) != (d->scratch_floats == 0)) VDX_REFUSE(who, "scratch and scratch_floats go together");
+    a.dW1 = d->dw1; a.dW2 = d->dw2; a.db = d->db; a.db1 = d->db1; a.db2 = d->db2; a.split = d->split;
+    a.x0_bf16 = d->x_bf16 ? 1 : 0; a.dy_bf16 = d->dy_bf16 ? 1 : 0;
     a.part = d->scratch; a.part_cap = d->scratch_floats;
     VDX_HIP(vdx::launch_conv_wgrad(a, (hipStream_t)stream));
     return VDX_OK;
@@ -1235,43 +1281,14 @@ int vdx_norm_act_backward_ex(const float* dact, const void* y, int y_bf16, void*
                              const float* beta, int groups, const float* scale_shift, int scale_shift_stride, float* d_gamma, float* d_beta,
                              float* dss, const void* r, int r_bf16, const float* ln_gamma, float* dr, float* d_ln_gamma, float* d_ln_beta,
                              float* scratch, float* dgp, int c, int batch, long pix_per_sample, void* stream) {
-    if (!dact || !y || !dy || !stats || !gamma || !beta || !d_gamma || !d_beta || !scratch) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: null tensor");
-    if (r && (!ln_gamma || !dr || !d_ln_gamma || !d_ln_beta)) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: incomplete LayerNorm branch");
-    if (r_bf16 && !r) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: r_bf16 without r");
-    if (c < 4 || c % 4 || c > 1024 || groups < 1 || groups > 32 || c % groups || batch < 1 || pix_per_sample < 1) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: bad channels/groups/shape");
-    if (scale_shift && scale_shift_stride < 2 * c) VDX_FAIL(VDX_ERR_INVALID, "norm_act_backward_ex: scale_shift rows hold scale[c] | shift[c]");
-    vdx::NormBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dact = dact; a.y = (const float*)y; a.y_bf16 = y_bf16 ? 1 : 0; a.dy = (float*)dy; a.dy_bf16 = dy_bf16 ? 1 : 0;
-    a.stats = stats; a.gamma = gamma; a.beta = beta; a.groups = groups;
-    a.ss = scale_shift; a.ss_stride = scale_shift_stride; a.d_gamma = d_gamma; a.d_beta = d_beta; a.dss = dss;
-    a.r = (const float*)r; a.r_bf16 = r_bf16 ? 1 : 0; a.ln_gamma = ln_gamma; a.dr = dr; a.d_ln_gamma = d_ln_gamma; a.d_ln_beta = d_ln_beta;
-    a.R = scratch; a.G = scratch + (vdx::norm_bwd_scratch_floats(c, batch, pix_per_sample) - (size_t)batch * 64);
-    a.dgp = dgp; a.C = c; a.batch = batch; a.pix_per_sample = pix_per_sample;
-    VDX_HIP(vdx::launch_norm_bwd(a, (hipStream_t)stream));
-    return VDX_OK;
+    return norm_act_bwd("norm_act_backward_ex", dact, y, y_bf16, dy, dy_bf16, stats, gamma, beta, groups, scale_shift, scale_shift_stride, d_gamma, d_beta, dss, r,
+                        r_bf16, ln_gamma, dr, d_ln_gamma, d_ln_beta, scratch, dgp, c, batch, pix_per_sample, stream);
 }
 
 int vdx_attention_core_backward_io(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, int batch, int frames,
                                    int h, int w, int heads, int temporal, int bf16_operands, void* stream) {
-    if (!qkv || !d_o || !o || !dqkv || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: bad argument");
-    const int HD = heads * 32;
-    if (dstride < 3 * HD || dstride % 8) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: dstride must be a multiple of 8, at least 3 * heads * 32 (one [rows][dq|dk|dv] buffer)");
     vdx::AttnBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    const long hw = (long)h * w;
-    if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
-    else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
-    if (a.L > 64 && temporal) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: temporal sequences of more than 64 frames are not served");
-    if (a.L > 64 && !vdx::attn_bwd_long_served(a.L)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: above 64 tokens per sequence only multiples of 64 up to 640 are served");
-    // bf16 tensors exist for the bf16 MFMA kernel only (vdx_internal.h AttnBwdArgs::io_bf16): never hand bf16 pointers to the fp32 kernel
-    if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_io: bf16 tensors need bf16_operands and at most 16 tokens per sequence");
-    a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
-    a.dq = (float*)dqkv;
-    const size_t es = io_bf16 ? 2 : 4;
-    a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)HD * es);
-    a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)2 * HD * es);
-    a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
+    if (int rc = attn_bwd_args(a, "attention_core_backward_io", qkv, d_o, o, dqkv, nullptr, nullptr, dstride, io_bf16, batch, frames, h, w, heads, temporal, bf16_operands)) return rc;
     VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
     return VDX_OK;
 }
@@ -1283,86 +1300,26 @@ size_t vdx_attention_bias_backward_scratch_floats(int heads, int tokens) {
 int vdx_attention_core_backward_bias(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias,
                                      float* dbias, float* scratch, size_t scratch_floats, int batch, int frames, int h, int w, int heads,
                                      int temporal, int bf16_operands, void* stream) {
-    // (before the null checks: a caller that sizes the scratch by vdx_attention_bias_backward_scratch_floats has none above 64 tokens)
-    if ((temporal ? (long)frames : (long)h * w) > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: this form serves at most 64 tokens per sequence (the plain core alone goes beyond)");
-    if (!qkv || !d_o || !o || !dqkv || !bias || !dbias || !scratch || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: bad argument");
-    const int HD = heads * 32;
-    if (dstride < 3 * HD || dstride % 8) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: dstride must be a multiple of 8, at least 3 * heads * 32 (one [rows][dq|dk|dv] buffer)");
-    vdx::AttnBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    const long hw = (long)h * w;
-    if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
-    else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
-    if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: bf16 tensors need bf16_operands and at most 16 tokens per sequence");
-    if (scratch_floats < vdx::attn_bwd_bias_scratch_floats(heads, a.L)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_bias: scratch too small (vdx_attention_bias_backward_scratch_floats)");
-    a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
-    a.dq = (float*)dqkv;
-    const size_t es = io_bf16 ? 2 : 4;
-    a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)HD * es);
-    a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)2 * HD * es);
-    a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
-    a.bias = bias; a.dbias = dbias; a.part = scratch; a.part_cap = scratch_floats;
-    VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
-    return VDX_OK;
+    return attn_core_bwd_fixed_grid("attention_core_backward_bias", false, qkv, d_o, o, dqkv, dstride, io_bf16, bias, dbias, scratch, scratch_floats, nullptr, 0,
+                                    batch, frames, h, w, heads, temporal, bf16_operands, stream);
 }
 
 int vdx_attention_core_backward_focus(const void* qkv, const void* d_o, void* o, void* dqkv, int dstride, int io_bf16, const float* bias_or_null,
                                       float* dbias_or_null, float* scratch, size_t scratch_floats, const unsigned char* focus_dev, int focus_n,
                                       int batch, int frames, int h, int w, int heads, int temporal, int bf16_operands, void* stream) {
-    // (before the null checks: a caller that sizes the scratch by vdx_attention_bias_backward_scratch_floats has none above 64 tokens)
-    if ((temporal ? (long)frames : (long)h * w) > 64) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: this form serves at most 64 tokens per sequence (the plain core alone goes beyond)");
-    if (!qkv || !d_o || !o || !dqkv || !focus_dev || focus_n < 1 || heads < 1 || batch < 1 || frames < 1 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: bad argument");
-    if ((bias_or_null != nullptr) != (dbias_or_null != nullptr)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: bias and dbias come together");
-    const int HD = heads * 32;
-    if (dstride < 3 * HD || dstride % 8) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: dstride must be a multiple of 8, at least 3 * heads * 32 (one [rows][dq|dk|dv] buffer)");
-    vdx::AttnBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    const long hw = (long)h * w;
-    if (temporal) { a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; }
-    else { a.L = (int)hw; a.nseq = (long)batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
-    if (io_bf16 && (!bf16_operands || a.L > 16)) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: bf16 tensors need bf16_operands and at most 16 tokens per sequence");
-    if (bias_or_null && (!scratch || scratch_floats < vdx::attn_bwd_bias_scratch_floats(heads, a.L))) VDX_FAIL(VDX_ERR_INVALID, "attention_core_backward_focus: scratch too small (vdx_attention_bias_backward_scratch_floats)");
-    a.qkv = (const float*)qkv; a.dO = (const float*)d_o; a.O = (float*)o; a.heads = heads; a.scale = 1.0f / sqrtf(32.0f);
-    a.dq = (float*)dqkv;
-    const size_t es = io_bf16 ? 2 : 4;
-    a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)HD * es);
-    a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + (size_t)2 * HD * es);
-    a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
-    if (bias_or_null) { a.bias = bias_or_null; a.dbias = dbias_or_null; a.part = scratch; a.part_cap = scratch_floats; }
-    a.focus = focus_dev; a.focus_n = focus_n;
-    VDX_HIP(vdx::launch_attn_core_bwd(a, (hipStream_t)stream));
-    return VDX_OK;
+    return attn_core_bwd_fixed_grid("attention_core_backward_focus", true, qkv, d_o, o, dqkv, dstride, io_bf16, bias_or_null, dbias_or_null, scratch, scratch_floats,
+                                    focus_dev, focus_n, batch, frames, h, w, heads, temporal, bf16_operands, stream);
 }
 
 int vdx_temporal_attention_backward_fused_ex(const void* x, int x_bf16, const float* dy, const void* packed_wqkv, const float* bqkv,
                                              const void* packed_wo_t, void* o_bf16, void* dqkv_bf16, float* dx, int batch, int frames, int h,
                                              int w, void* stream) {
-    if (!x || !dy || !packed_wqkv || !bqkv || !packed_wo_t || !o_bf16 || !dqkv_bf16 || !dx) VDX_FAIL(VDX_ERR_INVALID, "temporal_attention_backward_fused_ex: null argument");
-    if (batch < 1 || frames < 1 || frames > 16 || h < 1 || w < 1) VDX_FAIL(VDX_ERR_INVALID, "temporal_attention_backward_fused_ex: 1..16 frames");
-    vdx::AttnBwdXArgs a;
-    memset(&a, 0, sizeof(a));
-    const long hw = (long)h * w;
-    a.x = (const float*)x; a.x_bf16 = x_bf16 ? 1 : 0; a.g = dy; a.wqkv = packed_wqkv; a.bqkv = bqkv; a.woT = packed_wo_t; a.O = o_bf16; a.dqkv = dqkv_bf16; a.dx = dx;
-    a.L = frames; a.nseq = (long)batch * hw; a.inner = hw; a.outer_p = (long)frames * hw; a.tok_p = hw; a.scale = 1.0f / sqrtf(32.0f);
-    VDX_HIP(vdx::launch_attn_bwd_fused(a, (hipStream_t)stream));
-    return VDX_OK;
+    return attn_bwd_fused("temporal_attention_backward_fused_ex", x, x_bf16, dy, packed_wqkv, bqkv, packed_wo_t, o_bf16, dqkv_bf16, dx, batch, frames, h, w, stream);
 }
 
 int vdx_sla_core_backward_io(const void* q, const void* k, const void* v, const void* d_out, void* o, void* dqkv, int dstride, int io_bf16,
                              float* scratch, int nframes, int npix, int heads, int bf16_operands, void* stream) {
-    if (!q || !k || !v || !d_out || !o || !dqkv || !scratch || heads != 8 || nframes < 1 || npix < 1) VDX_FAIL(VDX_ERR_INVALID, "sla_core_backward_io: bad argument");
-    if (dstride < 768 || dstride % 8) VDX_FAIL(VDX_ERR_INVALID, "sla_core_backward_io: dstride must be a multiple of 8, at least 768 (one [rows][dq|dk|dv] buffer)");
-    if (io_bf16 && !bf16_operands) VDX_FAIL(VDX_ERR_INVALID, "sla_core_backward_io: bf16 tensors need bf16_operands");
-    vdx::SlaBwdArgs a;
-    memset(&a, 0, sizeof(a));
-    const size_t es = io_bf16 ? 2 : 4;
-    a.q = (const float*)q; a.k = (const float*)k; a.v = (const float*)v; a.dOut = (const float*)d_out; a.O = (float*)o; a.dq = (float*)dqkv;
-    a.dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + 256 * es);
-    a.dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dqkv) + 512 * es);
-    a.A = scratch; a.NF = nframes; a.N = npix; a.heads = heads;
-    a.dstride = dstride; a.io_bf16 = io_bf16 ? 1 : 0; a.bf16_mma = bf16_operands ? 1 : 0;
-    VDX_HIP(vdx::launch_sla_bwd(a, (hipStream_t)stream));
-    return VDX_OK;
+    return sla_core_bwd("sla_core_backward_io", q, k, v, d_out, o, dqkv, nullptr, nullptr, dstride, io_bf16, scratch, nframes, npix, heads, bf16_operands, stream);
 }
 
 int vdx_final_conv_backward(const void* x, int x_bf16, const float* d_out, const float* kernel, float* dx, float* dw, float* db, long npix, int d,

@@ -349,6 +349,28 @@ struct SlaBwdArgs {
 size_t sla_bwd_scratch_floats(int NF, int heads);
 hipError_t launch_sla_bwd(const SlaBwdArgs& a, hipStream_t st);
 
+// ---- geometry and layout of the attention blocks over a channel-last [batch][frames][h][w][C] tensor, defined once for the network
+// (model.hip, model_bwd.hip) and for the block-level entry points that stand for it in the tests (vdx_api.cpp).  temporal: sequences
+// over the frames of one pixel, else over the pixels of one frame
+inline void attn_token_geometry(AttnArgs& a, long batch, long frames, long h, long w, long C, bool temporal) {
+    const long hw = h * w;
+    if (temporal) { a.L = (int)frames; a.nseq = batch * hw; a.inner = hw; a.inner_stride = C; a.outer_stride = frames * hw * C; a.tok_stride = hw * C; }
+    else { a.L = (int)hw; a.nseq = batch * frames; a.inner = 1; a.inner_stride = 0; a.outer_stride = hw * C; a.tok_stride = C; }
+}
+// the same in pixels (rows of the backward's token-major tensors): AttnBwdArgs and AttnBwdXArgs
+template <class Args>
+inline void attn_pixel_geometry(Args& a, long batch, long frames, long h, long w, bool temporal) {
+    const long hw = h * w;
+    if (temporal) { a.L = (int)frames; a.nseq = batch * hw; a.inner = hw; a.outer_p = frames * hw; a.tok_p = hw; }
+    else { a.L = (int)hw; a.nseq = batch * frames; a.inner = 1; a.outer_p = hw; a.tok_p = 1; }
+}
+// dk and dv of one interleaved [rows][dq | dk | dv] buffer of hd = heads * 32 columns each, by the element size of its tensors
+inline void split_dqkv(float* dq, int hd, int io_bf16, float*& dk, float*& dv) {
+    const size_t es = io_bf16 ? 2 : 4;
+    dk = reinterpret_cast<float*>(reinterpret_cast<char*>(dq) + (size_t)hd * es);
+    dv = reinterpret_cast<float*>(reinterpret_cast<char*>(dq) + (size_t)2 * hd * es);
+}
+
 hipError_t launch_final_conv_bwd(const float* x, const float* dout, const float* w, float* dx, float* dW, float* db, long npix, int D, int Cout, int x_bf16, hipStream_t st, float* part = nullptr, size_t part_cap = 0);
 hipError_t launch_init_conv_wgrad(const float* x, const float* dy, float* dW, float* db, int B, int Cin, int F, int H, int W, int Cout, int K, hipStream_t st, float* part = nullptr, size_t part_cap = 0);
 hipError_t launch_resblock_ss_bwd(const float* params, float* grads, const float* temb, const SsLayer* layers, int nlayers, const float* lin_base,
