@@ -767,8 +767,6 @@ static hipError_t launch_attn_h8_t(const AttnArgs& a, hipStream_t st) {
     using M = Mma<MODE>;
     constexpr int NBUF = (MODE == MODE_BF16 && NKT == 1) ? 2 : 1;     // PIPE (see the kernel): os and ys double-buffered
     const size_t lds = 2 * (size_t)NKT * 64 * ROW_STRIDE + NBUF * ((size_t)64 * (256 * M::ES + 16) + (size_t)64 * (NKT * M::KT * 4 + 16));
-    auto kfn = attention_h8_kernel<MODE, NKT, TMO, TNO, IO16, F8, FULL>;
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const long subtiles = (a.nseq + 3) / 4;
     // sub-tiles per workgroup: the per-head weight fragments (12 KB per wave) are loaded once per workgroup, so fatter workgroups
     // amortise them as long as ~1024 workgroups remain to fill the chip
@@ -776,9 +774,8 @@ static hipError_t launch_attn_h8_t(const AttnArgs& a, hipStream_t st) {
     const int nsub = (int)std::min<long>(nsub_cap, std::max<long>(1, subtiles / 1024));
     const long blocks = (subtiles + nsub - 1) / nsub;
     const AttnWork aw = attn_work(a, M::ES, true);
-    LaunchScope ls(st, "attention_h8_kernel", aw.flops, aw.bytes, "<%d, %d, %d, %d, %d, %d, %d> C%d L%d nseq%ld", MODE, NKT, TMO, TNO, (int)IO16, (int)F8, (int)FULL, a.C, a.L, a.nseq);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(512), lds, st, a, nsub);
-    return hipGetLastError();
+    return LaunchScope(st, "attention_h8_kernel", aw.flops, aw.bytes, "<%d, %d, %d, %d, %d, %d, %d> C%d L%d nseq%ld", MODE, NKT, TMO, TNO, (int)IO16, (int)F8, (int)FULL, a.C, a.L, a.nseq)
+        .launch(attention_h8_kernel<MODE, NKT, TMO, TNO, IO16, F8, FULL>, dim3((unsigned)blocks), dim3(512), lds, a, nsub);
 }
 
 // ---- level 0 (C = 64, 16 tokens, 8 heads, bf16 tensors): one WAVE per group of 4 sequences, all heads in the wave ("attention_w") ------
@@ -1056,11 +1053,9 @@ static hipError_t launch_attn_w(const AttnArgs& a, hipStream_t st) {
     const int gpw = (int)s.per;
     const long blocks = (s.workers + VDX_AW_NW - 1) / VDX_AW_NW;
     const AttnWork aw = attn_work(a, 2, true);
-    auto go = [&](auto kfn) -> hipError_t {
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-        LaunchScope ls(st, "attention_w_kernel", aw.flops, aw.bytes, "<fp8 %d> C%d L%d nseq%ld", (int)F8, a.C, a.L, a.nseq);
-        hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(64 * VDX_AW_NW), lds, st, a, gpw, ngroups);
-        return hipGetLastError();
+    auto go = [&](auto kfn) {
+        return LaunchScope(st, "attention_w_kernel", aw.flops, aw.bytes, "<fp8 %d> C%d L%d nseq%ld", (int)F8, a.C, a.L, a.nseq)
+            .launch(kfn, dim3((unsigned)blocks), dim3(64 * VDX_AW_NW), lds, a, gpw, ngroups);
     };
     if (a.C == 64) return a.L == 16 ? go(attention_w_kernel<F8, 64, true>) : go(attention_w_kernel<F8, 64, false>);
     return a.L == 16 ? go(attention_w_kernel<F8, 32, true>) : go(attention_w_kernel<F8, 32, false>);
@@ -1226,12 +1221,10 @@ hipError_t launch_attention_heads(AttnArgs a, hipStream_t st) {
     long spb = std::max<long>(8 * NS, (a.nseq * a.heads + 511) / 512);
     spb = (spb + 8 * NS - 1) / (8 * NS) * (8 * NS);
     const long chunks = (a.nseq + spb - 1) / spb;
-    auto go = [&](auto kfn) -> hipError_t {
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-        const AttnWork aw = attn_work(a, 2, false);
-        LaunchScope ls(st, "attention_head_kernel", aw.flops, aw.bytes, "<io16 %d, %d, fp8 %d, lt %d> C%d L%d nseq%ld", a.io_bf16, TT, a.fp8_core, LT, a.C, a.L, a.nseq);
-        hipLaunchKernelGGL(kfn, dim3((unsigned)((chunks + 7) / 8 * 64)), dim3(512), lds, st, a, (int)spb, (int)chunks);
-        return hipGetLastError();
+    const AttnWork aw = attn_work(a, 2, false);
+    auto go = [&](auto kfn) {
+        return LaunchScope(st, "attention_head_kernel", aw.flops, aw.bytes, "<io16 %d, %d, fp8 %d, lt %d> C%d L%d nseq%ld", a.io_bf16, TT, a.fp8_core, LT, a.C, a.L, a.nseq)
+            .launch(kfn, dim3((unsigned)((chunks + 7) / 8 * 64)), dim3(512), lds, a, (int)spb, (int)chunks);
     };
     if (LT == 4) {                                     // (more than 16 tokens: the fp8 flag is ignored, as in the LDS-staged kernel)
         return a.io_bf16 ? go(attention_head_kernel<true, TT, false, 4>) : go(attention_head_kernel<false, TT, false, 4>);
@@ -1245,36 +1238,23 @@ static hipError_t launch_attn_reg_t(const AttnArgs& a, hipStream_t st) {
     const size_t lds = 512 + (size_t)(64 + 96) * ROW_STRIDE + (size_t)TMA * 16 * (32 * Mma<MODE>::ES + 16);
     const long blocks = (a.nseq + 3) / 4;
     const AttnWork aw = attn_work(a, Mma<MODE>::ES, true);
-    if (a.focus) {                                     // per-sample focus-present mask, with or without the bias (vdx_set_focus_present)
-        auto kfn = attention_reg_kernel<MODE, TMA, false, true, true>;
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-        LaunchScope ls(st, "attention_reg_kernel", aw.flops, aw.bytes, a.pos_bias ? "<%d, %d, bias+focus> C%d L%d nseq%ld io16 %d" : "<%d, %d, focus> C%d L%d nseq%ld io16 %d", MODE, TMA, a.C, a.L, a.nseq, a.io_bf16);
-        hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, st, a);
-        return hipGetLastError();
+    // the form and its name in the label: the per-sample focus-present mask with or without the bias (vdx_set_focus_present), the
+    // pre-softmax bias (vdx_set_temporal_pos_bias), or the plain kernel, whose core may run on fp8 operands in bf16 mode (launch_attn_m
+    // refuses the fp8 core together with the mask or the bias)
+    auto kfn = attention_reg_kernel<MODE, TMA, false>;
+    const char* form = "fp8 0";
+    if (a.focus) { kfn = attention_reg_kernel<MODE, TMA, false, true, true>; form = a.pos_bias ? "bias+focus" : "focus"; }
+    else if (a.pos_bias) { kfn = attention_reg_kernel<MODE, TMA, false, true>; form = "bias"; }
+    else if constexpr (MODE == MODE_BF16) {
+        if (a.fp8_core) { kfn = attention_reg_kernel<MODE, TMA, true>; form = "fp8 1"; }
     }
-    if (a.pos_bias) {                                  // pre-softmax bias (never together with the fp8 core: vdx_set_temporal_pos_bias)
-        auto kfn = attention_reg_kernel<MODE, TMA, false, true>;
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-        LaunchScope ls(st, "attention_reg_kernel", aw.flops, aw.bytes, "<%d, %d, bias> C%d L%d nseq%ld io16 %d", MODE, TMA, a.C, a.L, a.nseq, a.io_bf16);
-        hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, st, a);
-        return hipGetLastError();
-    }
-    LaunchScope ls(st, "attention_reg_kernel", aw.flops, aw.bytes, "<%d, %d, fp8 %d> C%d L%d nseq%ld io16 %d", MODE, TMA, a.fp8_core, a.C, a.L, a.nseq, a.io_bf16);
-    if constexpr (MODE == MODE_BF16) {
-        if (a.fp8_core) { hipLaunchKernelGGL((attention_reg_kernel<MODE, TMA, true>), dim3((unsigned)blocks), dim3(256), lds, st, a); return hipGetLastError(); }
-    }
-    hipLaunchKernelGGL((attention_reg_kernel<MODE, TMA, false>), dim3((unsigned)blocks), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return LaunchScope(st, "attention_reg_kernel", aw.flops, aw.bytes, "<%d, %d, %s> C%d L%d nseq%ld io16 %d", MODE, TMA, form, a.C, a.L, a.nseq, a.io_bf16)
+        .launch(kfn, dim3((unsigned)blocks), dim3(256), lds, a);
 }
 
 template <int MODE>
-static hipError_t launch_attn_reg(const AttnArgs& a, hipStream_t st) {
-    if (a.C <= 64) return launch_attn_reg_t<MODE, 4>(a, st);
-    if (a.C <= 128) return launch_attn_reg_t<MODE, 8>(a, st);
-    if (a.C <= 256) return launch_attn_reg_t<MODE, 16>(a, st);
-    if (a.C <= 512) return launch_attn_reg_t<MODE, 32>(a, st);
-    if (a.C <= 1024) return launch_attn_reg_t<MODE, 64>(a, st);
-    return hipErrorInvalidValue;
+static hipError_t launch_attn_reg(const AttnArgs& a, hipStream_t st) {        // 16-channel tiles of the projection: 4 per 64 channels
+    return with_channel_tiles(a.C, [&](auto t) { return launch_attn_reg_t<MODE, 4 * decltype(t)::value>(a, st); });
 }
 
 template <int MODE, int LP, int TMO, bool BIAS = false, bool FOCUS = false>
@@ -1284,55 +1264,33 @@ static hipError_t launch_attn_t(const AttnArgs& a, hipStream_t st) {
     constexpr int NCHL = (LP + KC - 1) / KC;
     constexpr int RSV = NCHL * 64 + 16;
     const size_t lds = 512 + (size_t)(64 * 4 + 96) * ROW_STRIDE + (size_t)(NSEQ * 32 + 64) * RSV;
-    auto kfn = attention_kernel<MODE, LP, TMO, BIAS, FOCUS>;
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const long blocks = (a.nseq + NSEQ - 1) / NSEQ;
     const AttnWork aw = attn_work(a, Mma<MODE>::ES, true);
-    LaunchScope ls(st, "attention_kernel", aw.flops, aw.bytes,
-                   FOCUS ? (a.pos_bias ? "<%d, %d, %d, bias+focus> C%d L%d nseq%ld io16 %d" : "<%d, %d, %d, focus> C%d L%d nseq%ld io16 %d")
-                         : BIAS ? "<%d, %d, %d, bias> C%d L%d nseq%ld io16 %d" : "<%d, %d, %d> C%d L%d nseq%ld io16 %d", MODE, LP, TMO, a.C, a.L, a.nseq, a.io_bf16);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return LaunchScope(st, "attention_kernel", aw.flops, aw.bytes, "<%d, %d, %d%s> C%d L%d nseq%ld io16 %d", MODE, LP, TMO,
+                       FOCUS ? (a.pos_bias ? ", bias+focus" : ", focus") : BIAS ? ", bias" : "", a.C, a.L, a.nseq, a.io_bf16)
+        .launch(attention_kernel<MODE, LP, TMO, BIAS, FOCUS>, dim3((unsigned)blocks), dim3(256), lds, a);
 }
 
-template <int MODE, int LP, bool BIAS = false, bool FOCUS = false>
-static hipError_t launch_attn_l(const AttnArgs& a, hipStream_t st) {
-    if (a.C <= 64) return launch_attn_t<MODE, LP, 1, BIAS, FOCUS>(a, st);
-    if (a.C <= 128) return launch_attn_t<MODE, LP, 2, BIAS, FOCUS>(a, st);
-    if (a.C <= 256) return launch_attn_t<MODE, LP, 4, BIAS, FOCUS>(a, st);
-    if (a.C <= 512) return launch_attn_t<MODE, LP, 8, BIAS, FOCUS>(a, st);
-    if (a.C <= 1024) return launch_attn_t<MODE, LP, 16, BIAS, FOCUS>(a, st);
+// the generic fused kernels by sequence length: attention_reg_kernel up to 16 tokens, the LDS-staged attention_kernel up to 32 and 64.
+// BIAS / FOCUS: the pre-softmax bias and the per-sample focus-present mask exist in these kernels only (the one-wave-per-head / per-group
+// kernels have no such instantiation yet); the FOCUS instantiations carry the bias code, with a bias that may be null
+template <int MODE, bool BIAS, bool FOCUS>
+static hipError_t launch_attn_generic(const AttnArgs& a, hipStream_t st) {
+    if (a.L <= 16) {
+        if constexpr (MODE == MODE_F32) {              // f32 weight tiles of 512 < C <= 1024 exceed the LDS: staged form
+            if (a.C > 512) return a.C <= 1024 ? launch_attn_t<MODE, 16, 16, BIAS, FOCUS>(a, st) : hipErrorInvalidValue;
+        }
+        return launch_attn_reg<MODE>(a, st);
+    }
+    if (a.L <= 32) return with_channel_tiles(a.C, [&](auto t) { return launch_attn_t<MODE, 32, decltype(t)::value, BIAS, FOCUS>(a, st); });
+    if (a.L <= 64) return with_channel_tiles(a.C, [&](auto t) { return launch_attn_t<MODE, 64, decltype(t)::value, BIAS, FOCUS>(a, st); });
     return hipErrorInvalidValue;
 }
 
 template <int MODE>
 static hipError_t launch_attn_m(const AttnArgs& a, hipStream_t st) {
-    if (a.focus) {
-        // per-sample focus-present mask: the generic fused kernels only, as for the bias below (FOCUS instantiations; the bias is optional)
-        if (a.fp8_core || a.focus_n < 1) return hipErrorInvalidValue;
-        if (a.L <= 16) {
-            if constexpr (MODE == MODE_F32) {
-                if (a.C > 512) return a.C <= 1024 ? launch_attn_t<MODE, 16, 16, true, true>(a, st) : hipErrorInvalidValue;
-            }
-            return launch_attn_reg<MODE>(a, st);
-        }
-        if (a.L <= 32) return launch_attn_l<MODE, 32, true, true>(a, st);
-        if (a.L <= 64) return launch_attn_l<MODE, 64, true, true>(a, st);
-        return hipErrorInvalidValue;
-    }
-    if (a.pos_bias) {
-        // pre-softmax bias: the generic fused kernels only (the one-wave-per-head / per-group kernels have no bias instantiation yet)
-        if (a.fp8_core) return hipErrorInvalidValue;
-        if (a.L <= 16) {
-            if constexpr (MODE == MODE_F32) {
-                if (a.C > 512) return a.C <= 1024 ? launch_attn_t<MODE, 16, 16, true>(a, st) : hipErrorInvalidValue;
-            }
-            return launch_attn_reg<MODE>(a, st);
-        }
-        if (a.L <= 32) return launch_attn_l<MODE, 32, true>(a, st);
-        if (a.L <= 64) return launch_attn_l<MODE, 64, true>(a, st);
-        return hipErrorInvalidValue;
-    }
+    if (a.focus) return (a.fp8_core || a.focus_n < 1) ? hipErrorInvalidValue : launch_attn_generic<MODE, true, true>(a, st);
+    if (a.pos_bias) return a.fp8_core ? hipErrorInvalidValue : launch_attn_generic<MODE, true, false>(a, st);
     const bool h8_ok = a.L <= 16 && a.heads == 8 && a.inner % 4 == 0 && a.nseq % 4 == 0 && a.nseq < (1L << 31) &&
                        3 * a.inner_stride + 15 * a.tok_stride + a.C < (1L << 31);
     if constexpr (MODE != MODE_F16) {                  // (the one-wave-per-head kernels hard-code the bf16 / f32 register formats)
@@ -1358,15 +1316,7 @@ static hipError_t launch_attn_m(const AttnArgs& a, hipStream_t st) {
         if (a.C == 128 && nkt == 2) return launch_attn_h8_t<MODE, 2, 1, 4, false>(a, st);
     }
     }
-    if (a.L <= 16) {
-        if constexpr (MODE == MODE_F32) {              // f32 weight tiles of 512 < C <= 1024 exceed the LDS: staged form
-            if (a.C > 512) return a.C <= 1024 ? launch_attn_t<MODE, 16, 16>(a, st) : hipErrorInvalidValue;
-        }
-        return launch_attn_reg<MODE>(a, st);
-    }
-    if (a.L <= 32) return launch_attn_l<MODE, 32>(a, st);
-    if (a.L <= 64) return launch_attn_l<MODE, 64>(a, st);
-    return hipErrorInvalidValue;
+    return launch_attn_generic<MODE, false, false>(a, st);
 }
 
 // ---- long sequences (L > 64: the bottleneck spatial attention of frames larger than 64 x 64, e.g. 16 x 16 = 256 tokens at 128 x 128) ----
@@ -1416,11 +1366,8 @@ __global__ __launch_bounds__(256) void attention_long_core_kernel(const float* _
 hipError_t launch_attention_long_core(const float* qkv, float* o, long nseq, int L, int heads, float scale, hipStream_t st) {
     const size_t lds = (size_t)L * 64 * 4;
     if (lds > 160 * 1024 || nseq <= 0 || nseq >= (1L << 31)) return hipErrorInvalidValue;            // L <= 640 tokens
-    auto kfn = attention_long_core_kernel;
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-    LaunchScope ls(st, "attention_long_core_kernel", 4.0 * nseq * L * L * heads * 32, 4.0 * nseq * L * heads * 32 * 4, "L%d nseq%ld heads%d", L, nseq, heads);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)nseq, heads), dim3(256), lds, st, qkv, o, L, heads, scale);
-    return hipGetLastError();
+    return LaunchScope(st, "attention_long_core_kernel", 4.0 * nseq * L * L * heads * 32, 4.0 * nseq * L * heads * 32 * 4, "L%d nseq%ld heads%d", L, nseq, heads)
+        .launch(attention_long_core_kernel, dim3((unsigned)nseq, heads), dim3(256), lds, qkv, o, L, heads, scale);
 }
 
 // ---- relative position bias of the temporal attention blocks (vdx_set_temporal_pos_bias) ----
@@ -1437,9 +1384,8 @@ __global__ __launch_bounds__(256) void pos_bias_table_kernel(const float* __rest
 hipError_t launch_pos_bias_table(const float* emb, const int* buckets, float* table, int heads, int n, hipStream_t st) {
     if (!emb || !buckets || !table || heads < 1 || n < 1 || n > 64) return hipErrorInvalidValue;
     const int total = heads * n * n;
-    LaunchScope ls(st, "pos_bias_table_kernel", 0.0, 8.0 * total, "heads%d n%d", heads, n);
-    hipLaunchKernelGGL(pos_bias_table_kernel, dim3((total + 255) / 256), dim3(256), 0, st, emb, buckets, table, heads, n * n);
-    return hipGetLastError();
+    return LaunchScope(st, "pos_bias_table_kernel", 0.0, 8.0 * total, "heads%d n%d", heads, n)
+        .launch(pos_bias_table_kernel, dim3((total + 255) / 256), dim3(256), 0, emb, buckets, table, heads, n * n);
 }
 
 // ---- the block of a batch in which every sample is focus-present (vdx_set_focus_present, mode 1) ----
@@ -1585,18 +1531,13 @@ static hipError_t launch_attn_present_t(const AttnArgs& a, hipStream_t st) {
     const size_t lds = 512 + (size_t)(64 + 64 + 64) * ROW_STRIDE;
     const long rows = a.nseq * a.L, blocks = (rows + 63) / 64;
     const int es = a.io_bf16 ? 2 : 4;
-    LaunchScope ls(st, "attention_present_kernel", 4.0 * rows * a.C * a.heads * 32, (double)rows * a.C * es * 3, "<%d, %d> C%d rows%ld io16 %d", MODE, TMO, a.C, rows, a.io_bf16);
-    hipLaunchKernelGGL((attention_present_kernel<MODE, TMO>), dim3((unsigned)blocks), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return LaunchScope(st, "attention_present_kernel", 4.0 * rows * a.C * a.heads * 32, (double)rows * a.C * es * 3, "<%d, %d> C%d rows%ld io16 %d", MODE, TMO, a.C, rows, a.io_bf16)
+        .launch(attention_present_kernel<MODE, TMO>, dim3((unsigned)blocks), dim3(256), lds, a);
 }
 
 template <int MODE>
 static hipError_t launch_attn_present_m(const AttnArgs& a, hipStream_t st) {
-    if (a.C <= 64) return launch_attn_present_t<MODE, 1>(a, st);
-    if (a.C <= 128) return launch_attn_present_t<MODE, 2>(a, st);
-    if (a.C <= 256) return launch_attn_present_t<MODE, 4>(a, st);
-    if (a.C <= 512) return launch_attn_present_t<MODE, 8>(a, st);
-    return launch_attn_present_t<MODE, 16>(a, st);
+    return with_channel_tiles(a.C, [&](auto t) { return launch_attn_present_t<MODE, decltype(t)::value>(a, st); });
 }
 
 hipError_t launch_attention_present(int mode, AttnArgs a, hipStream_t st) {

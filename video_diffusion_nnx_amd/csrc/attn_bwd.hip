@@ -894,55 +894,52 @@ __global__ __launch_bounds__(256) void sla_bwd_b16_kernel(SlaBwdArgs P) {
 constexpr int ATTN_BIAS_SLOTS = 128;       // workgroups per head of the bias forms = slots of the deterministic dBias sum (fixed: not a device property)
 size_t attn_bwd_bias_scratch_floats(int heads, int L) { const size_t ls = L <= 16 ? 16 : L; return (size_t)ATTN_BIAS_SLOTS * heads * ls * ls; }
 
+// second pass of the bias forms: a.dbias += the slots of a.part, in order
+static hipError_t launch_attn_dbias_sum(const AttnBwdArgs& a, int slots, int LS, hipStream_t st) {
+    const int total = a.heads * a.L * a.L;
+    return LaunchScope(st, "attn_dbias_sum_kernel", 0.0, 0.0, "slots%d heads%d L%d", slots, a.heads, a.L)
+        .launch(attn_dbias_sum_kernel, dim3((total + 255) / 256), dim3(256), 0, a.part, slots, a.heads, a.L, LS, a.dbias);
+}
+
 // the focus forms (a.focus set): the same fixed grid; with a.bias they also emit dBias, without it bias / dbias / part are all null
 static hipError_t launch_attn_core_bwd_focus(const AttnBwdArgs& a, hipStream_t st) {
     if (a.focus_n < 1 || a.L < 1 || a.L > 64 || a.nseq < 1) return hipErrorInvalidValue;
     if (a.bias ? (!a.dbias || !a.part || a.part_cap < attn_bwd_bias_scratch_floats(a.heads, a.L)) : (a.dbias || a.part)) return hipErrorInvalidValue;
     int slots, LS;
+    hipError_t e;
     if (a.bf16_mma && a.L <= 16) {
         slots = (int)std::min<long>((a.nseq + 3) / 4, ATTN_BIAS_SLOTS); LS = 16;
-        LaunchScope ls(st, "attn_core_bwd16_focus_kernel", 0.0, 0.0, "<io16 %d, bias %d> L%d nseq%ld heads%d", a.io_bf16, a.bias ? 1 : 0, a.L, a.nseq, a.heads);
-        if (a.io_bf16) hipLaunchKernelGGL(attn_core_bwd16_focus_kernel<true>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
-        else hipLaunchKernelGGL(attn_core_bwd16_focus_kernel<false>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
+        e = LaunchScope(st, "attn_core_bwd16_focus_kernel", 0.0, 0.0, "<io16 %d, bias %d> L%d nseq%ld heads%d", a.io_bf16, a.bias ? 1 : 0, a.L, a.nseq, a.heads)
+                .launch(a.io_bf16 ? attn_core_bwd16_focus_kernel<true> : attn_core_bwd16_focus_kernel<false>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, a);
     } else {
         if (a.io_bf16) return hipErrorInvalidValue;
         slots = (int)std::min<long>(a.nseq, ATTN_BIAS_SLOTS); LS = a.L;
         const size_t lds = ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
-        auto kfn = attn_core_bwd_focus_kernel;
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-        LaunchScope ls(st, "attn_core_bwd_focus_kernel", 0.0, 0.0, "<bias %d> L%d nseq%ld heads%d", a.bias ? 1 : 0, a.L, a.nseq, a.heads);
-        hipLaunchKernelGGL(kfn, dim3(slots, a.heads), dim3(256), lds, st, a);
+        e = LaunchScope(st, "attn_core_bwd_focus_kernel", 0.0, 0.0, "<bias %d> L%d nseq%ld heads%d", a.bias ? 1 : 0, a.L, a.nseq, a.heads)
+                .launch(attn_core_bwd_focus_kernel, dim3(slots, a.heads), dim3(256), lds, a);
     }
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (e != hipSuccess) return e;
     if (!a.bias) return hipSuccess;
-    const int total = a.heads * a.L * a.L;
-    LaunchScope ls(st, "attn_dbias_sum_kernel", 0.0, 0.0, "slots%d heads%d L%d", slots, a.heads, a.L);
-    hipLaunchKernelGGL(attn_dbias_sum_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a.part, slots, a.heads, a.L, LS, a.dbias);
-    return hipGetLastError();
+    return launch_attn_dbias_sum(a, slots, LS, st);
 }
 
 static hipError_t launch_attn_core_bwd_bias(const AttnBwdArgs& a, hipStream_t st) {
     if (!a.dbias || !a.part || a.L < 1 || a.L > 64 || a.nseq < 1 || a.part_cap < attn_bwd_bias_scratch_floats(a.heads, a.L)) return hipErrorInvalidValue;
     int slots, LS;
+    hipError_t e;
     if (a.bf16_mma && a.L <= 16) {
         slots = (int)std::min<long>((a.nseq + 3) / 4, ATTN_BIAS_SLOTS); LS = 16;
-        LaunchScope ls(st, "attn_core_bwd16_bias_kernel", 0.0, 0.0, "<io16 %d> L%d nseq%ld heads%d", a.io_bf16, a.L, a.nseq, a.heads);
-        if (a.io_bf16) hipLaunchKernelGGL(attn_core_bwd16_bias_kernel<true>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
-        else hipLaunchKernelGGL(attn_core_bwd16_bias_kernel<false>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
+        e = LaunchScope(st, "attn_core_bwd16_bias_kernel", 0.0, 0.0, "<io16 %d> L%d nseq%ld heads%d", a.io_bf16, a.L, a.nseq, a.heads)
+                .launch(a.io_bf16 ? attn_core_bwd16_bias_kernel<true> : attn_core_bwd16_bias_kernel<false>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, a);
     } else {
         if (a.io_bf16) return hipErrorInvalidValue;
         slots = (int)std::min<long>(a.nseq, ATTN_BIAS_SLOTS); LS = a.L;
         const size_t lds = ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
-        auto kfn = attn_core_bwd_bias_kernel;
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-        LaunchScope ls(st, "attn_core_bwd_bias_kernel", 0.0, 0.0, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads);
-        hipLaunchKernelGGL(kfn, dim3(slots, a.heads), dim3(256), lds, st, a);
+        e = LaunchScope(st, "attn_core_bwd_bias_kernel", 0.0, 0.0, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads)
+                .launch(attn_core_bwd_bias_kernel, dim3(slots, a.heads), dim3(256), lds, a);
     }
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    const int total = a.heads * a.L * a.L;
-    LaunchScope ls(st, "attn_dbias_sum_kernel", 0.0, 0.0, "slots%d heads%d L%d", slots, a.heads, a.L);
-    hipLaunchKernelGGL(attn_dbias_sum_kernel, dim3((total + 255) / 256), dim3(256), 0, st, a.part, slots, a.heads, a.L, LS, a.dbias);
-    return hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_attn_dbias_sum(a, slots, LS, st);
 }
 
 // demb[b][h] = sum of dbias[h][i][j] over the (i, j) of bucket b, in (i, j) order: one thread per (b, h)
@@ -957,9 +954,8 @@ __global__ __launch_bounds__(256) void pos_bias_scatter_kernel(const float* __re
 
 hipError_t launch_pos_bias_scatter(const float* dbias, const int* buckets, float* demb, int heads, int n, hipStream_t st) {
     if (!dbias || !buckets || !demb || heads < 1 || n < 1) return hipErrorInvalidValue;
-    LaunchScope ls(st, "pos_bias_scatter_kernel", 0.0, 0.0, "heads%d n%d", heads, n);
-    hipLaunchKernelGGL(pos_bias_scatter_kernel, dim3((32 * heads + 255) / 256), dim3(256), 0, st, dbias, buckets, demb, heads, n * n);
-    return hipGetLastError();
+    return LaunchScope(st, "pos_bias_scatter_kernel", 0.0, 0.0, "heads%d n%d", heads, n)
+        .launch(pos_bias_scatter_kernel, dim3((32 * heads + 255) / 256), dim3(256), 0, dbias, buckets, demb, heads, n * n);
 }
 
 hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st) {
@@ -968,17 +964,12 @@ hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st) {
     if (a.L > 64) return launch_attn_core_bwd_long(a, st);          // multiples of 64 up to 640 tokens (attn_long_bwd.hip); anything else is refused there
     if (a.bf16_mma && a.L <= 16) {
         const long blocks = (a.nseq + 3) / 4;
-        LaunchScope ls(st, "attn_core_bwd16_kernel", 0.0, 0.0, "<io16 %d> L%d nseq%ld heads%d", a.io_bf16, a.L, a.nseq, a.heads);
-        if (a.io_bf16) hipLaunchKernelGGL(attn_core_bwd16_kernel<true>, dim3((unsigned)blocks), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
-        else hipLaunchKernelGGL(attn_core_bwd16_kernel<false>, dim3((unsigned)blocks), dim3(256), 4 * 4 * 16 * AB_RS, st, a);
-        return hipGetLastError();
+        return LaunchScope(st, "attn_core_bwd16_kernel", 0.0, 0.0, "<io16 %d> L%d nseq%ld heads%d", a.io_bf16, a.L, a.nseq, a.heads)
+            .launch(a.io_bf16 ? attn_core_bwd16_kernel<true> : attn_core_bwd16_kernel<false>, dim3((unsigned)blocks), dim3(256), 4 * 4 * 16 * AB_RS, a);
     }
     const size_t lds = ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
-    auto kfn = attn_core_bwd_kernel;
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-    LaunchScope ls(st, "attn_core_bwd_kernel", 0.0, 0.0, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads);
-    hipLaunchKernelGGL(kfn, dim3((unsigned)a.nseq, (unsigned)a.heads), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return LaunchScope(st, "attn_core_bwd_kernel", 0.0, 0.0, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads)
+        .launch(attn_core_bwd_kernel, dim3((unsigned)a.nseq, (unsigned)a.heads), dim3(256), lds, a);
 }
 
 size_t sla_bwd_scratch_floats(int NF, int heads) { return (size_t)NF * heads * SLA_A; }

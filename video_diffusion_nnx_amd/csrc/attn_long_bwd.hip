@@ -229,25 +229,14 @@ hipError_t launch_attn_core_bwd_long(const AttnBwdArgs& a, hipStream_t st) {
     if (a.nseq >= (1L << 31) / nt) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(a.nseq * nt), (unsigned)a.heads);
     const double mm = 2.0 * a.nseq * a.heads * (double)a.L * a.L * 32, el = (double)a.nseq * a.L * a.heads * 32 * 4;     // one L x L x 32 product; one tensor
-    {
-        auto kfn = attn_long_bwd_stats_kernel;
-        if (hipError_t e = lds_opt_in(kfn, AL_LDS_STATS); e != hipSuccess) return e;
-        LaunchScope ls(st, "attn_long_bwd_stats_kernel", 2 * mm, 5 * el + 2 * el * (double)nt, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads);
-        hipLaunchKernelGGL(kfn, grid, dim3(256), AL_LDS_STATS, st, a);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    {
-        auto kfn = attn_long_bwd_dkv_kernel;
-        if (hipError_t e = lds_opt_in(kfn, AL_LDS_DKV); e != hipSuccess) return e;
-        LaunchScope ls(st, "attn_long_bwd_dkv_kernel", 4 * mm, 4 * el + 2 * el * (double)nt, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads);
-        hipLaunchKernelGGL(kfn, grid, dim3(256), AL_LDS_DKV, st, a);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    auto kfn = attn_long_bwd_dq_kernel;
-    if (hipError_t e = lds_opt_in(kfn, AL_LDS_DQ); e != hipSuccess) return e;
-    LaunchScope ls(st, "attn_long_bwd_dq_kernel", 3 * mm, 3 * el + 2 * el * (double)nt, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads);
-    hipLaunchKernelGGL(kfn, grid, dim3(256), AL_LDS_DQ, st, a);
-    return hipGetLastError();
+    hipError_t e = LaunchScope(st, "attn_long_bwd_stats_kernel", 2 * mm, 5 * el + 2 * el * (double)nt, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads)
+                       .launch(attn_long_bwd_stats_kernel, grid, dim3(256), AL_LDS_STATS, a);
+    if (e != hipSuccess) return e;
+    e = LaunchScope(st, "attn_long_bwd_dkv_kernel", 4 * mm, 4 * el + 2 * el * (double)nt, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads)
+            .launch(attn_long_bwd_dkv_kernel, grid, dim3(256), AL_LDS_DKV, a);
+    if (e != hipSuccess) return e;
+    return LaunchScope(st, "attn_long_bwd_dq_kernel", 3 * mm, 3 * el + 2 * el * (double)nt, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads)
+        .launch(attn_long_bwd_dq_kernel, grid, dim3(256), AL_LDS_DQ, a);
 }
 
 }  // namespace vdx

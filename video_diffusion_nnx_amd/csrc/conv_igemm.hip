@@ -826,18 +826,10 @@ __global__ __launch_bounds__(512) void conv64d_kernel(const ConvArgs P, const in
 
 // the persistent 16 x 16-tile kernels of this file: 512-thread workgroups, at most `slots` of them, each walking a contiguous tile range
 template <typename K>
-static hipError_t launch_tiles16(K kfn, const ConvArgs& a, size_t lds, long slots, hipStream_t st) {
+static hipError_t launch_tiles16(LaunchScope&& ls, K kfn, const ConvArgs& a, size_t lds, long slots) {
     const int total = a.NF * (a.H >> 4) * (a.W >> 4);
     const PersistentSplit s = persistent_split(total, slots);
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)s.workers), dim3(512), lds, st, a, (int)s.per, total);
-    return hipGetLastError();
-}
-
-static hipError_t launch_conv64d(const ConvArgs& a, hipStream_t st) {
-    if (a.pro || !a.x0_bf16 || !a.res || a.res_bf16) return hipErrorInvalidValue;
-    const size_t lds = 9 * 64 * 128 + 2 * (size_t)C64D_APL + 128 * 8;
-    return launch_tiles16(a.y_bf16 ? conv64d_kernel<true, true> : conv64d_kernel<false, true>, a, lds, device_cus(), st);
+    return ls.launch(kfn, dim3((unsigned)s.workers), dim3(512), lds, a, (int)s.per, total);
 }
 
 // ---- weights-in-registers form of the persistent 64 -> 64 conv (bf16 tensors, no prologue): "conv64r" ---------------------------------
@@ -1016,12 +1008,6 @@ __global__ __launch_bounds__(512) void conv64r_kernel(const ConvArgs P, const in
         __syncthreads();                              // tile t + 1 landed everywhere; everybody is done reading tile t
     }
     flush_stats(bcur);
-}
-
-static hipError_t launch_conv64r(const ConvArgs& a, hipStream_t st) {
-    if (a.pro || !a.x0_bf16 || a.res) return hipErrorInvalidValue;
-    const size_t lds = 3 * (size_t)C64D_APL + 128 * 8 + 64 * 4;
-    return launch_tiles16(a.y_bf16 ? conv64r_kernel<true> : conv64r_kernel<false>, a, lds, device_cus(), st);
 }
 
 // ---- "conv64q": the weights-in-registers scheme with 16 output channels x 128 pixels per wave ------------------------------------------
@@ -1340,37 +1326,6 @@ __global__ __launch_bounds__(512) void conv64q_kernel(const ConvArgs P, const in
     flush_stats(bcur);
 }
 
-static hipError_t launch_conv64q(const ConvArgs& a, hipStream_t st) {
-    if (!a.x0_bf16 || a.res || (a.C1 && !a.x1_bf16)) return hipErrorInvalidValue;
-    const size_t lds = 3 * (size_t)C64D_APL + 128 * 8 + 64 * 4 + (64 + 64 + 64) * 4;
-    auto launch = [&](auto kfn) { return launch_tiles16(kfn, a, lds, device_cus(), st); };
-    if (a.Cout == 32) {                               // dim-32 networks: 64 (= 32 + 32 or 64) or 128 (= 64 + 64) input channels, bf16 output
-        if (a.pro || !a.y_bf16) return hipErrorInvalidValue;
-        return a.C0 + a.C1 == 128 ? launch(conv64q_kernel<128, false, true, 32>) : launch(conv64q_kernel<64, false, true, 32>);
-    }
-    if (a.C0 + a.C1 == 128) {
-        if (a.pro) return hipErrorInvalidValue;
-        return a.y_bf16 ? launch(conv64q_kernel<128, false, true>) : launch(conv64q_kernel<128, false, false>);
-    }
-    if (!a.pro) return hipErrorInvalidValue;          // (the plain 64 -> 64 conv is conv64r_kernel)
-    return a.y_bf16 ? launch(conv64q_kernel<64, true, true>) : launch(conv64q_kernel<64, true, false>);
-}
-
-static hipError_t launch_conv64p(const ConvArgs& a, hipStream_t st) {
-    if (a.res) return hipErrorInvalidValue;
-    if (a.Cout == 32) {                               // C = 32 form: bf16 tensors only; 62 KB of LDS, two workgroups per CU
-        if (!a.x0_bf16 || !a.y_bf16) return hipErrorInvalidValue;
-        const size_t lds = 9 * 32 * 64 + 2 * (size_t)C64_HALO * 64 + (64 + 64 + 64) * 4 + 128 * 8 + 64 * 4;
-        const long slots = (long)((a.pro ? VDX_C32_PRO_WAVES : 4) / 2) * device_cus();
-        return launch_tiles16(a.pro ? conv64p_kernel<true, true, true, false, 32> : conv64p_kernel<true, false, true, false, 32>, a, lds, slots, st);
-    }
-    if (a.x0_bf16) return hipErrorInvalidValue;       // (bf16 input: conv64q / conv64r / conv64d)
-    const size_t lds = 9 * 64 * 128 + 2 * (size_t)C64_HALO * 128 + (64 + 64 + 64) * 4 + 128 * 8 + 64 * 4;      // weights, 2 halo tiles, coefA / coefD / gmean, chs, bias
-    auto launch = [&](auto kfn) { return launch_tiles16(kfn, a, lds, device_cus(), st); };
-    if (a.pro) return a.y_bf16 ? launch(conv64p_kernel<false, true, true>) : launch(conv64p_kernel<false, true, false>);
-    return a.y_bf16 ? launch(conv64p_kernel<false, false, true>) : launch(conv64p_kernel<false, false, false>);
-}
-
 // Flax kernel [taps][Cin][Cout] fp32  ->  packed [taps][Cout][CinPad] in the MMA element type, zero padded.
 template <int MODE>
 __global__ void pack_weights_kernel(const float* __restrict__ src, void* __restrict__ dst, int taps, int Cin, int Cout, int CinPad) {
@@ -1520,9 +1475,7 @@ hipError_t launch_pack_weights_t(int mode, const float* src, void* dst, int taps
 
 // instrumentation (vdx.h: vdx_set_launch_hook): algorithmic work of one conv launch -- 2 * pixels_out * Cin * Cout * taps FLOP (ConvTranspose:
 // 4 effective taps per output pixel) and input + output (+ residual) tensors in their storage type + the packed weights
-namespace {
-struct ConvWork { double flops, bytes; char shape[128]; };
-ConvWork conv_work(int mode, const ConvArgs& a) {
+static ConvWork conv_work(int mode, const ConvArgs& a) {
     ConvWork w;
     const double es = mode == MODE_F32 ? 4.0 : 2.0;
     const int taps = a.kind ? 16 : a.kh * a.kw;
@@ -1535,10 +1488,9 @@ ConvWork conv_work(int mode, const ConvArgs& a) {
              a.NF, a.H, a.W, a.stride == 2 ? " s2" : "", a.pro ? " +prologue" : "", a.res ? " +res" : "", a.C1 ? " concat" : "");
     return w;
 }
-}  // namespace
 
-// ---- routing of the level-0 persistent forms: one predicate per (kernel, case), tried by launch_conv in this order.  Their channel shapes
-//      are disjoint, so at most one holds for a conv.  Common to all: bf16 mode, 3x3 / stride 1, whole 16 x 16 tiles, at least 1024 of them.
+// ---- routing of the level-0 persistent forms: one record per (kernel, case), tried by conv_route in the order of conv_routes.  Their channel
+//      shapes are disjoint, so at most one holds for a conv.  Common to all: bf16 mode, 3x3 / stride 1, whole 16 x 16 tiles, at least 1024 of them.
 static bool tiles16_3x3(int mode, const ConvArgs& a) {
     return mode == MODE_BF16 && a.kind == 0 && a.kh == 3 && a.kw == 3 && a.stride == 1 && a.H % 16 == 0 && a.W % 16 == 0 &&
            (long)a.NF * (a.H / 16) * (a.W / 16) >= 1024;
@@ -1550,32 +1502,147 @@ static bool conv64_shape(int mode, const ConvArgs& a) {
            (!a.res || (!a.pro && a.x0_bf16 && !a.res_bf16)) && (size_t)a.NF * a.H * a.W * 64 * (a.y_bf16 ? 2 : 4) < 0xFFFFFFF0ull &&
            (!a.pro || (a.groups <= 32 && 64 % a.groups == 0)) && (!a.out_stats || (a.out_groups <= 32 && 64 % a.out_groups == 0));
 }
-static bool conv64q_pro_eligible(int mode, const ConvArgs& a) { return conv64_shape(mode, a) && a.x0_bf16 && a.pro; }
-static bool conv64r_eligible(int mode, const ConvArgs& a) { return conv64_shape(mode, a) && a.x0_bf16 && !a.pro && !a.res; }
-static bool conv64d_eligible(int mode, const ConvArgs& a) { return conv64_shape(mode, a) && a.x0_bf16 && !a.pro && a.res; }
-static bool conv64p_eligible(int mode, const ConvArgs& a) { return conv64_shape(mode, a) && !a.x0_bf16; }
+static bool conv64q_pro_plan(int mode, const ConvArgs& a, ConvPlan&) { return conv64_shape(mode, a) && a.x0_bf16 && a.pro; }
+static bool conv64r_plan(int mode, const ConvArgs& a, ConvPlan&) { return conv64_shape(mode, a) && a.x0_bf16 && !a.pro && !a.res; }
+static bool conv64d_plan(int mode, const ConvArgs& a, ConvPlan&) { return conv64_shape(mode, a) && a.x0_bf16 && !a.pro && a.res; }
+static bool conv64p_plan(int mode, const ConvArgs& a, ConvPlan&) { return conv64_shape(mode, a) && !a.x0_bf16; }
 // 32 -> 32 (level 0 of dim-32 networks, the YAML-literal config_v2_2): conv64p_kernel with 32-channel tiles, bf16 tensors
-static bool conv64p_c32_eligible(int mode, const ConvArgs& a) {
+static bool conv64p_c32_plan(int mode, const ConvArgs& a, ConvPlan&) {
     return tiles16_3x3(mode, a) && a.C0 == 32 && a.C1 == 0 && a.Cout == 32 && a.wrows == 32 && a.wrow0 == 0 && a.CinPad == 64 && a.x0_bf16 &&
            a.y_bf16 && !a.res && (!a.pro || (a.groups <= 32 && 32 % a.groups == 0)) && (!a.out_stats || (a.out_groups <= 32 && 32 % a.out_groups == 0));
 }
 // concat inputs of dim-32 networks with 32 output channels: 64 = 32 + 32 -> 32 at level 0, 128 = 64 + 64 -> 32 at level 1 (they ran on the
 // generic kernel: 278 / 117 us at B = 64)
-static bool conv64q_cout32_eligible(int mode, const ConvArgs& a) {
+static bool conv64q_cout32_plan(int mode, const ConvArgs& a, ConvPlan&) {
     return tiles16_3x3(mode, a) && a.Cout == 32 && a.x0_bf16 && a.x1_bf16 && !a.pro && a.y_bf16 && ((a.C0 == 32 && a.C1 == 32) || (a.C0 == 64 && a.C1 == 64)) &&
            a.CinPad == a.C0 + a.C1 && a.wrows == 32 && a.wrow0 == 0 && !a.res &&
            (!a.out_stats || (a.out_groups <= 32 && 32 % a.out_groups == 0 && (32 / a.out_groups) <= 8 && 8 % (32 / a.out_groups) == 0));
 }
 // 128 -> 64: a 64 + 64 concat or one 128-channel tensor, bf16 inputs; 32-bit offsets of the 256-byte input pixels (larger: generic kernel)
-static bool conv64q_cin128_eligible(int mode, const ConvArgs& a) {
+static bool conv64q_cin128_plan(int mode, const ConvArgs& a, ConvPlan&) {
     return tiles16_3x3(mode, a) && a.Cout == 64 && a.x0_bf16 && (!a.C1 || a.x1_bf16) && !a.pro && ((a.C0 == 64 && a.C1 == 64) || (a.C0 == 128 && a.C1 == 0)) &&
            a.wrows == 64 && a.wrow0 == 0 && !a.res && (!a.out_stats || (a.out_groups <= 32 && 32 % (64 / a.out_groups) == 0 && 64 % a.out_groups == 0)) &&
            (long)a.NF * a.H * a.W * 256 < 0xFFFFFFF0l;
 }
 
+// their launches: the plan has fixed the form, the remaining flags pick the instantiation and stand in the label as instantiated
+template <int CIN, bool PRO, bool OUT16, int COUT = 64>
+static hipError_t launch_conv64q(const ConvArgs& a, const ConvWork& w, hipStream_t st) {
+    const size_t lds = 3 * (size_t)C64D_APL + 128 * 8 + 64 * 4 + (64 + 64 + 64) * 4;
+    return launch_tiles16(LaunchScope(st, "conv64q_kernel", w.flops, w.bytes, "<cin %d, pro %d, y16 %d%s> %s", CIN, (int)PRO, (int)OUT16, COUT == 32 ? ", cout 32" : "", w.shape),
+                          conv64q_kernel<CIN, PRO, OUT16, COUT>, a, lds, device_cus());
+}
+static hipError_t conv64q_pro_launch(int, const ConvArgs& a, const ConvPlan&, const ConvWork& w, hipStream_t st) {
+    return a.y_bf16 ? launch_conv64q<64, true, true>(a, w, st) : launch_conv64q<64, true, false>(a, w, st);
+}
+static hipError_t conv64q_cout32_launch(int, const ConvArgs& a, const ConvPlan&, const ConvWork& w, hipStream_t st) {
+    return a.C0 + a.C1 == 128 ? launch_conv64q<128, false, true, 32>(a, w, st) : launch_conv64q<64, false, true, 32>(a, w, st);
+}
+static hipError_t conv64q_cin128_launch(int, const ConvArgs& a, const ConvPlan&, const ConvWork& w, hipStream_t st) {
+    return a.y_bf16 ? launch_conv64q<128, false, true>(a, w, st) : launch_conv64q<128, false, false>(a, w, st);
+}
+static hipError_t conv64r_launch(int, const ConvArgs& a, const ConvPlan&, const ConvWork& w, hipStream_t st) {
+    const size_t lds = 3 * (size_t)C64D_APL + 128 * 8 + 64 * 4;
+    return with_bool(a.y_bf16 != 0, [&](auto y16) {
+        constexpr bool OUT16 = decltype(y16)::value;
+        return launch_tiles16(LaunchScope(st, "conv64r_kernel", w.flops, w.bytes, "<pro 0, y16 %d> %s", (int)OUT16, w.shape), conv64r_kernel<OUT16>, a, lds, device_cus());
+    });
+}
+static hipError_t conv64d_launch(int, const ConvArgs& a, const ConvPlan&, const ConvWork& w, hipStream_t st) {
+    const size_t lds = 9 * 64 * 128 + 2 * (size_t)C64D_APL + 128 * 8;
+    return with_bool(a.y_bf16 != 0, [&](auto y16) {
+        constexpr bool OUT16 = decltype(y16)::value;
+        return launch_tiles16(LaunchScope(st, "conv64d_kernel", w.flops, w.bytes, "<x16 1, pro 0, y16 %d, res 1> %s", (int)OUT16, w.shape), conv64d_kernel<OUT16, true>, a,
+                              lds, device_cus());
+    });
+}
+// conv64p_kernel: C = 64 with fp32 input (weights, 2 halo tiles, coefA / coefD / gmean, chs, bias in LDS), or the C = 32 form with bf16
+// tensors (62 KB of LDS, two workgroups per CU)
+template <bool IN16, bool PRO, bool OUT16, int C>
+static hipError_t launch_conv64p(const ConvArgs& a, const ConvWork& w, hipStream_t st) {
+    const size_t lds = 9 * C * 2 * C + 2 * (size_t)C64_HALO * 2 * C + (64 + 64 + 64) * 4 + 128 * 8 + 64 * 4;
+    const long slots = C == 32 ? (long)((PRO ? VDX_C32_PRO_WAVES : 4) / 2) * device_cus() : device_cus();
+    return launch_tiles16(LaunchScope(st, "conv64p_kernel", w.flops, w.bytes, "<x16 %d, pro %d, y16 %d, res 0%s> %s", (int)IN16, (int)PRO, (int)OUT16, C == 32 ? ", C 32" : "", w.shape),
+                          conv64p_kernel<IN16, PRO, OUT16, false, C>, a, lds, slots);
+}
+static hipError_t conv64p_launch(int, const ConvArgs& a, const ConvPlan&, const ConvWork& w, hipStream_t st) {
+    if (a.pro) return a.y_bf16 ? launch_conv64p<false, true, true, 64>(a, w, st) : launch_conv64p<false, true, false, 64>(a, w, st);
+    return a.y_bf16 ? launch_conv64p<false, false, true, 64>(a, w, st) : launch_conv64p<false, false, false, 64>(a, w, st);
+}
+static hipError_t conv64p_c32_launch(int, const ConvArgs& a, const ConvPlan&, const ConvWork& w, hipStream_t st) {
+    return a.pro ? launch_conv64p<true, true, true, 32>(a, w, st) : launch_conv64p<true, false, true, 32>(a, w, st);
+}
+
+// ---- the generic form, conv_igemm_kernel: serves what no other record takes.  Input format of the instantiation: 0 fp32 tensors, 1 one
+//      bf16 tensor, 2 bf16 tensors with channel counts % 8 == 0, 3 anything else (fp32 mode: 0 or 3; fp16 mode keeps every tensor fp32 in HBM)
+static bool conv_igemm_plan(int mode, const ConvArgs& a, ConvPlan& p) {
+    const int K = a.kind ? 2 : a.kh;
+    // variant: 64-channel tiles take 256 pixels per workgroup (stride 1) so every wave owns a 64x64 tile
+    p.BC = a.Cout <= 64 ? 64 : 128;
+    // 8-wave workgroups (each wave 32 pixels x 64 channels of the same workgroup tile): 4 waves per SIMD instead of 2;
+    // (small launches -- the deep levels at the training batch, 128 tiles of 128 x 128 -- as 256 four-wave workgroups of 128 x 64 were
+    // measured slower: 16.95 vs 16.75 ms per train step; the halo tile is staged twice as often)
+    p.TN = (p.BC == 64 && a.stride == 2) ? 2 : 4;
+    const int BM = 16 * p.TN * (4 / (p.BC / 64));
+    choose_patch(BM, a.NF, a.F, a.Ho, a.Wo, a.stride, K, p.PH, p.PW, p.NP);
+    const int IH = (p.PH - 1) * a.stride + K, IW = (p.PW - 1) * a.stride + K;
+    if (IW < 2 || p.PW < 2) return false;                  // (the kernel divides by multiplication: every divisor >= 2)
+    const int HPX = p.NP * IH * IW;
+    p.lds = 2 * p.BC * 8 + ((HPX * 4 + 15) / 16) * 16 + (a.pro ? (2 * a.CinPad * 4 + 64 * 4) : 0) + (size_t)HPX * ROW_STRIDE + 3 * (size_t)p.BC * 128;
+    if (p.lds > 160 * 1024) return false;
+    const bool in16 = mode == MODE_BF16 && a.x0_bf16 && (!a.C1 || a.x1_bf16) && (a.C0 % 8 == 0) && (a.C1 % 8 == 0);
+    const int inf = in16 ? 2 : (!a.x0_bf16 && !(a.C1 && a.x1_bf16)) ? 0 : (mode == MODE_BF16 && a.x0_bf16 && !a.C1) ? 1 : 3;
+    p.inf = (mode == MODE_BF16 || inf == 0) ? inf : 3;
+    return mode != MODE_F16 || p.inf == 0;
+}
+
+static hipError_t conv_igemm_launch(int mode, const ConvArgs& a0, const ConvPlan& p, const ConvWork& w, hipStream_t st) {
+    ConvArgs a = a0;
+    const int K = a.kind ? 2 : a.kh;
+    a.PH = p.PH; a.PW = p.PW; a.NP = p.NP;
+    a.tiles_y = (a.Ho + a.PH - 1) / a.PH;
+    a.tiles_x = (a.Wo + a.PW - 1) / a.PW;
+    const int IH = (a.PH - 1) * a.stride + K, IW = (a.PW - 1) * a.stride + K;
+    auto magic = [](int d) { return (unsigned)((1ull << 32) / (unsigned)d) + 1u; };      // every divisor here is >= 2
+    a.m_ihiw = magic(IH * IW); a.m_iw = magic(IW); a.m_phpw = magic(a.PH * a.PW); a.m_pw = magic(a.PW);
+    const dim3 grid((a.NF / a.NP) * a.tiles_y * a.tiles_x, (a.Cout + p.BC - 1) / p.BC, a.kind ? 4 : 1);
+    auto go = [&](auto mode_c, auto inf_c) {
+        auto tile = [&](auto bc_c, auto nw_c) {
+            constexpr int MODE = decltype(mode_c)::value, INF = decltype(inf_c)::value, BC = decltype(bc_c)::value, NW = decltype(nw_c)::value;
+            return LaunchScope(st, "conv_igemm_kernel", w.flops, w.bytes, "<%d, %d, 2, %d, %d> %s", MODE, BC, NW, INF, w.shape)
+                .launch(conv_igemm_kernel<MODE, BC, 2, NW, INF>, grid, dim3(64 * NW), p.lds, a);
+        };
+        // 64-pixel-per-wave shapes run as 8 waves x 32 pixels (measured better than 4 waves x 64 pixels); stride-2 64-channel tiles as 4 x 32
+        return p.BC == 128 ? tile(Int<128>{}, Int<8>{}) : p.TN == 4 ? tile(Int<64>{}, Int<8>{}) : tile(Int<64>{}, Int<4>{});
+    };
+    if (mode == MODE_F32) return p.inf == 0 ? go(Int<MODE_F32>{}, Int<0>{}) : go(Int<MODE_F32>{}, Int<3>{});
+    if (mode == MODE_F16) return go(Int<MODE_F16>{}, Int<0>{});
+    return p.inf == 0 ? go(Int<MODE_BF16>{}, Int<0>{}) : p.inf == 1 ? go(Int<MODE_BF16>{}, Int<1>{}) : p.inf == 2 ? go(Int<MODE_BF16>{}, Int<2>{}) : go(Int<MODE_BF16>{}, Int<3>{});
+}
+
+// the forms in the order they are tried; the generic one takes what is left
+static const ConvRoute conv_routes[] = {
+    {conv3x3_ws_plan, conv3x3_ws_launch},                  // wide levels: persistent weight-streaming kernel
+    {conv4x4_ws_plan, conv4x4_ws_launch},                  // 4x4 resampling convs of the wide levels
+    {resample32_plan, resample32_launch},                  // 32-channel resampling convs (level 0 of dim-32 networks)
+    {conv1x1_pw_plan, conv1x1_pw_launch},                  // 1x1 convs of the wide levels (bf16 tensors)
+    {conv64q_pro_plan, conv64q_pro_launch},                // level-0 persistent forms: 64 -> 64, bf16 input, prologue
+    {conv64r_plan, conv64r_launch},                        // 64 -> 64, bf16 input
+    {conv64d_plan, conv64d_launch},                        // 64 -> 64, bf16 input, fp32 residual
+    {conv64p_plan, conv64p_launch},                        // 64 -> 64, fp32 input
+    {conv64p_c32_plan, conv64p_c32_launch},                // 32 -> 32 (level 0 of dim-32 networks)
+    {conv64q_cout32_plan, conv64q_cout32_launch},          // concat -> 32 (levels 0 / 1 of dim-32 networks)
+    {conv64q_cin128_plan, conv64q_cin128_launch},          // 128 -> 64
+    {conv_igemm_plan, conv_igemm_launch},
+};
+static const ConvRoute* conv_route(int mode, const ConvArgs& a, ConvPlan& p) {
+    for (const ConvRoute& r : conv_routes)
+        if (r.plan(mode, a, p)) return &r;
+    return nullptr;
+}
+
 hipError_t launch_conv(int mode, ConvArgs a, hipStream_t st) {
     // geometry completion
-    const int K = a.kind ? 2 : a.kh;
     if (a.kind) { a.stride = 1; a.Ho = a.H; a.Wo = a.W; a.Hy = 2 * a.H; a.Wy = 2 * a.W; }
     else { a.Ho = (a.H + a.stride - 1) / a.stride; a.Wo = (a.W + a.stride - 1) / a.stride; a.Hy = a.Ho; a.Wy = a.Wo; }
     a.CinPad = conv_cin_pad(mode, a.C0 + a.C1);
@@ -1585,109 +1652,11 @@ hipError_t launch_conv(int mode, ConvArgs a, hipStream_t st) {
     const size_t b0 = npix * a.C0 * (a.x0_bf16 ? 2 : 4), b1 = npix * a.C1 * (a.x1_bf16 ? 2 : 4), bw = (size_t)(a.kind ? 16 : a.kh * a.kw) * a.wrows * a.CinPad * ES;
     if (b0 >= 0xFFFFFFF0ull || b1 >= 0xFFFFFFF0ull || bw >= 0xFFFFFFF0ull) return hipErrorInvalidValue;   // 32-bit buffer offsets
     a.x0_bytes = (unsigned)b0; a.x1_bytes = (unsigned)b1; a.w_bytes = (unsigned)bw;
-    if (conv3x3_ws_eligible(mode, a)) {                                      // wide levels: persistent weight-streaming kernel
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv3x3_ws_kernel", cw.flops, cw.bytes, "<%d, %s> %s", conv3x3_ws_geo(a), a.pro ? "true" : "false", cw.shape);
-        return launch_conv3x3_ws(a, st);
-    }
-    if (conv4x4_ws_eligible(mode, a)) {                                      // 4x4 resampling convs of the wide levels
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv4x4_ws_kernel", cw.flops, cw.bytes, "<%d, %d, %d> %s", a.kind == 1 ? a.H : a.H / 2, a.kind == 1 ? 2 : 1, a.Cout == 64 ? 64 : 128, cw.shape);
-        return launch_conv4x4_ws(a, st);
-    }
-    if (resample32_eligible(mode, a)) {                                      // 32-channel resampling convs (level 0 of dim-32 networks)
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "resample32_kernel", cw.flops, cw.bytes, "<%d> %s", a.kind, cw.shape);
-        return launch_resample32(a, st);
-    }
-    if (conv1x1_pw_eligible(mode, a)) {                                      // 1x1 convs of the wide levels (bf16 tensors)
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv1x1_pw_kernel", cw.flops, cw.bytes, "<%d> %s", conv1x1_pw_rows(a), cw.shape);
-        return launch_conv1x1_pw(a, st);
-    }
-    if (conv64q_pro_eligible(mode, a)) {                                      // level-0 persistent forms: 64 -> 64, bf16 input, prologue
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv64q_kernel", cw.flops, cw.bytes, "<cin 64, pro %d, y16 %d> %s", a.pro, a.y_bf16, cw.shape);
-        return launch_conv64q(a, st);
-    }
-    if (conv64r_eligible(mode, a)) {                                          // 64 -> 64, bf16 input
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv64r_kernel", cw.flops, cw.bytes, "<pro 0, y16 %d> %s", a.y_bf16, cw.shape);
-        return launch_conv64r(a, st);
-    }
-    if (conv64d_eligible(mode, a)) {                                          // 64 -> 64, bf16 input, fp32 residual
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv64d_kernel", cw.flops, cw.bytes, "<x16 %d, pro %d, y16 %d, res %d> %s", a.x0_bf16, a.pro, a.y_bf16, a.res ? 1 : 0, cw.shape);
-        return launch_conv64d(a, st);
-    }
-    if (conv64p_eligible(mode, a)) {                                          // 64 -> 64, fp32 input
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv64p_kernel", cw.flops, cw.bytes, "<x16 %d, pro %d, y16 %d, res %d> %s", a.x0_bf16, a.pro, a.y_bf16, a.res ? 1 : 0, cw.shape);
-        return launch_conv64p(a, st);
-    }
-    if (conv64p_c32_eligible(mode, a)) {                                      // 32 -> 32 (level 0 of dim-32 networks)
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv64p_kernel", cw.flops, cw.bytes, "<x16 1, pro %d, y16 1, res 0, C 32> %s", a.pro, cw.shape);
-        return launch_conv64p(a, st);
-    }
-    if (conv64q_cout32_eligible(mode, a)) {                                   // concat -> 32 (levels 0 / 1 of dim-32 networks)
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv64q_kernel", cw.flops, cw.bytes, "<cin %d, pro 0, y16 1, cout 32> %s", a.C0 + a.C1, cw.shape);
-        return launch_conv64q(a, st);
-    }
-    if (conv64q_cin128_eligible(mode, a)) {                                   // 128 -> 64
-        const ConvWork cw = conv_work(mode, a);
-        LaunchScope ls(st, "conv64q_kernel", cw.flops, cw.bytes, "<cin 128, pro 0, y16 %d> %s", a.y_bf16, cw.shape);
-        return launch_conv64q(a, st);
-    }
-    // variant: 64-channel tiles take 256 pixels per workgroup (stride 1) so every wave owns a 64x64 tile
-    const int BC = a.Cout <= 64 ? 64 : 128;
-    // 8-wave workgroups (each wave 32 pixels x 64 channels of the same workgroup tile): 4 waves per SIMD instead of 2;
-    // (small launches -- the deep levels at the training batch, 128 tiles of 128 x 128 -- as 256 four-wave workgroups of 128 x 64 were
-    // measured slower: 16.95 vs 16.75 ms per train step; the halo tile is staged twice as often)
-    const int TN = (BC == 64 && a.stride == 2) ? 2 : 4;
-    const int BM = 16 * TN * (4 / (BC / 64));
-    choose_patch(BM, a.NF, a.F, a.Ho, a.Wo, a.stride, K, a.PH, a.PW, a.NP);
-    a.tiles_y = (a.Ho + a.PH - 1) / a.PH;
-    a.tiles_x = (a.Wo + a.PW - 1) / a.PW;
-    const int IH = (a.PH - 1) * a.stride + K, IW = (a.PW - 1) * a.stride + K;
-    const int HPX = a.NP * IH * IW;
-    auto magic = [](int d) { return (unsigned)((1ull << 32) / (unsigned)d) + 1u; };      // every divisor here is >= 2
-    a.m_ihiw = magic(IH * IW); a.m_iw = magic(IW); a.m_phpw = magic(a.PH * a.PW); a.m_pw = magic(a.PW);
-    if (IW < 2 || a.PW < 2) return hipErrorInvalidValue;
-    size_t lds = 2 * BC * 8 + ((HPX * 4 + 15) / 16) * 16 + (a.pro ? (2 * a.CinPad * 4 + 64 * 4) : 0)
-               + (size_t)HPX * ROW_STRIDE + 3 * (size_t)BC * 128;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    dim3 grid((a.NF / a.NP) * a.tiles_y * a.tiles_x, (a.Cout + BC - 1) / BC, a.kind ? 4 : 1);
-    const bool in16 = mode == MODE_BF16 && a.x0_bf16 && (!a.C1 || a.x1_bf16) && (a.C0 % 8 == 0) && (a.C1 % 8 == 0);
-    const int inf = in16 ? 2 : (!a.x0_bf16 && !(a.C1 && a.x1_bf16)) ? 0 : (mode == MODE_BF16 && a.x0_bf16 && !a.C1) ? 1 : 3;
-    const ConvWork cw = conv_work(mode, a);
-    LaunchScope ls(st, "conv_igemm_kernel", cw.flops, cw.bytes, "<%d, %d, 2, %d, %d> %s", mode, BC, (BC == 128 || TN == 4) ? 8 : 4, (mode == MODE_BF16 || inf == 0) ? inf : 3, cw.shape);
-#define VDX_LAUNCH_CONV_K(KFN_, NTH_)                                                                    \
-    do {                                                                                                  \
-        auto kfn = KFN_;                                                                                  \
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;                               \
-        hipLaunchKernelGGL(kfn, grid, dim3(NTH_), lds, st, a);                                            \
-    } while (0)
-    // 64-pixel-per-wave shapes run as 8 waves x 32 pixels (measured better than 4 waves x 64 pixels); stride-2 64-channel tiles as 4 x 32
-#define VDX_LAUNCH_CONV_T(MODE_, INF_)                                                                   \
-    do {                                                                                                  \
-        if (BC == 128) VDX_LAUNCH_CONV_K((conv_igemm_kernel<MODE_, 128, 2, 8, INF_>), 512);              \
-        else if (TN == 4) VDX_LAUNCH_CONV_K((conv_igemm_kernel<MODE_, 64, 2, 8, INF_>), 512);            \
-        else VDX_LAUNCH_CONV_K((conv_igemm_kernel<MODE_, 64, 2, 4, INF_>), 256);                          \
-    } while (0)
-    if (mode == MODE_F32) {
-        if (inf == 0) VDX_LAUNCH_CONV_T(MODE_F32, 0); else VDX_LAUNCH_CONV_T(MODE_F32, 3);
-    } else if (mode == MODE_F16) {
-        if (inf != 0) return hipErrorInvalidValue;           // fp16 operand mode keeps every tensor fp32 in HBM
-        VDX_LAUNCH_CONV_T(MODE_F16, 0);
-    } else {
-        if (inf == 0) VDX_LAUNCH_CONV_T(MODE_BF16, 0); else if (inf == 1) VDX_LAUNCH_CONV_T(MODE_BF16, 1);
-        else if (inf == 2) VDX_LAUNCH_CONV_T(MODE_BF16, 2); else VDX_LAUNCH_CONV_T(MODE_BF16, 3);
-    }
-#undef VDX_LAUNCH_CONV_T
-#undef VDX_LAUNCH_CONV_K
-    return hipGetLastError();
+    ConvPlan plan{};
+    const ConvRoute* route = conv_route(mode, a, plan);
+    if (!route) return hipErrorInvalidValue;
+    const ConvWork cw = g_launch_hook ? conv_work(mode, a) : ConvWork{};        // (the hook's figures and shape text: nothing is formatted without one)
+    return route->launch(mode, a, plan, cw, st);
 }
 
 }  // namespace vdx

@@ -171,14 +171,15 @@ __global__ __launch_bounds__(512) void conv1x1_pw_kernel(const ConvArgs P, const
     }
 }
 
-int conv1x1_pw_rows(const ConvArgs& a) {
+static int conv1x1_pw_rows(const ConvArgs& a) {
     const int cin = a.C0 + a.C1;
     // 128-row tiles when the weight image fits (rows x (2 Cin + 16) bytes <= ~136 KB) and Cout allows, else 64
     if (a.Cout % 128 == 0 && (size_t)128 * (cin * 2 + 16) + 128 * 4 <= 140 * 1024) return 128;
     return 64;
 }
 
-bool conv1x1_pw_eligible(int mode, const ConvArgs& a) {
+// 1x1 convs of the wide levels on bf16 tensors: weight rows resident in LDS, x straight into fragments (p.geo = rows of a weight tile)
+bool conv1x1_pw_plan(int mode, const ConvArgs& a, ConvPlan& p) {
     if (mode != MODE_BF16 || a.kind != 0 || a.kh != 1 || a.kw != 1 || a.stride != 1 || a.pad != 0 || a.pro || a.out_stats) return false;
     if (!a.x0_bf16 || (a.C1 && !a.x1_bf16)) return false;
     const bool out32 = !a.y_bf16;                          // fp32 y (+ fp32 res): the dx projections of the attention / SLA backward
@@ -194,12 +195,12 @@ bool conv1x1_pw_eligible(int mode, const ConvArgs& a) {
     if (npix * (size_t)std::max(std::max(a.C0, a.C1), a.Cout) * 2 >= 0xFFFF0000ull) return false;
     const int rows = conv1x1_pw_rows(a);
     if ((size_t)rows * (cin * 2 + 16) + rows * 4 > 160 * 1024) return false;
+    p.geo = rows; p.nct = a.Cout / rows; p.total = (int)(npix / 32);
     return true;
 }
 
-hipError_t launch_conv1x1_pw(const ConvArgs& a, hipStream_t st) {
-    const int cin = a.C0 + a.C1, rows = conv1x1_pw_rows(a), nct = a.Cout / rows;
-    const int ngroups = (int)((size_t)a.NF * a.H * a.W / 32);
+hipError_t conv1x1_pw_launch(int, const ConvArgs& a, const ConvPlan& p, const ConvWork& w, hipStream_t st) {
+    const int cin = a.C0 + a.C1, rows = p.geo, nct = p.nct, ngroups = p.total;
     const int cus = device_cus();
     // ranges: a multiple of 8 (XCD decode), ~ cus / nct of them, each a multiple of 8 groups (one per wave and pass)
     const size_t lds = (size_t)rows * (cin * 2 + 16) + rows * 4;
@@ -209,14 +210,13 @@ hipError_t launch_conv1x1_pw(const ConvArgs& a, hipStream_t st) {
     int nranges = std::max(8, (cus * wg_per_cu / nct) / 8 * 8);
     int gpr = ((ngroups + nranges - 1) / nranges + 7) / 8 * 8;
     nranges = ((ngroups + gpr - 1) / gpr + 7) / 8 * 8;
-    auto go = [&](auto kfn) -> hipError_t {
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kfn, dim3(nranges * nct), dim3(512), lds, st, a, nct, gpr, ngroups);
-        return hipGetLastError();
+    auto go = [&](auto rows_c) {
+        constexpr int ROWS = decltype(rows_c)::value;
+        auto kfn = !a.y_bf16 ? conv1x1_pw_kernel<ROWS, 4, true> : cin == 64 ? conv1x1_pw_kernel<ROWS, 2> : conv1x1_pw_kernel<ROWS>;
+        return LaunchScope(st, "conv1x1_pw_kernel", w.flops, w.bytes, "<%d> %s", ROWS, w.shape)
+            .launch(kfn, dim3(nranges * nct), dim3(512), lds, a, nct, gpr, ngroups);
     };
-    if (!a.y_bf16) return rows == 128 ? go(conv1x1_pw_kernel<128, 4, true>) : go(conv1x1_pw_kernel<64, 4, true>);
-    if (cin == 64) return rows == 128 ? go(conv1x1_pw_kernel<128, 2>) : go(conv1x1_pw_kernel<64, 2>);
-    return rows == 128 ? go(conv1x1_pw_kernel<128>) : go(conv1x1_pw_kernel<64>);
+    return rows == 128 ? go(Int<128>{}) : go(Int<64>{});
 }
 
 }  // namespace vdx

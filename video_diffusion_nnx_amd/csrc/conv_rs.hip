@@ -101,7 +101,8 @@ __global__ __launch_bounds__(256) void resample32_kernel(const ConvArgs P, const
     }
 }
 
-bool resample32_eligible(int mode, const ConvArgs& a) {
+// Downsample / Upsample of 32-channel bf16 tensors (dim-32 networks)
+bool resample32_plan(int mode, const ConvArgs& a, ConvPlan&) {
     if (mode != MODE_BF16 || a.C0 != 32 || a.C1 != 0 || a.Cout != 32 || !a.x0_bf16 || !a.y_bf16 || a.res || a.pro || a.out_stats) return false;
     if (a.wrows != 32 || a.wrow0 != 0 || a.CinPad != 64) return false;
     const bool down = a.kind == 0 && a.kh == 4 && a.kw == 4 && a.stride == 2 && a.pad == 1 && a.H % 2 == 0 && a.W % 32 == 0;
@@ -111,15 +112,17 @@ bool resample32_eligible(int mode, const ConvArgs& a) {
     return in_b < 0xFFFFFFF0ull && out_b < 0xFFFFFFF0ull;
 }
 
-hipError_t launch_resample32(const ConvArgs& a, hipStream_t st) {
+hipError_t resample32_launch(int, const ConvArgs& a, const ConvPlan&, const ConvWork& w, hipStream_t st) {
     const bool down = a.kind == 0;
     const long tiles = (long)a.NF * (down ? a.H / 2 : a.H) * ((down ? a.W / 2 : a.W) / 16);
     const PersistentSplit s = persistent_split(tiles, (long)device_cus() * 8);      // over waves: 8 per CU (two workgroups of 4 at <= 256 registers)
     const int tpw = (int)s.per;
     const long blocks = (s.workers + 3) / 4;
-    if (down) hipLaunchKernelGGL(resample32_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, st, a, tpw, tiles);
-    else hipLaunchKernelGGL(resample32_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, st, a, tpw, tiles);
-    return hipGetLastError();
+    return with_bool(!down, [&](auto up_c) {
+        constexpr int KIND = decltype(up_c)::value ? 1 : 0;
+        return LaunchScope(st, "resample32_kernel", w.flops, w.bytes, "<%d> %s", KIND, w.shape)
+            .launch(resample32_kernel<KIND>, dim3((unsigned)blocks), dim3(256), 0, a, tpw, tiles);
+    });
 }
 
 }  // namespace vdx

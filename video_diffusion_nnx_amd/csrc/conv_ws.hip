@@ -649,8 +649,6 @@ static int ws_geo(const ConvArgs& a) {                    // 0: 16 x 16 tiles, 8
     return -1;
 }
 
-int conv3x3_ws_geo(const ConvArgs& a) { return ws_geo(a); }
-
 // frame size of the 256-pixel whole-frame tiles of the 4x4 resampling kernel (output frames of Downsample, input frames of Upsample), or 0
 static int ws4_geo(const ConvArgs& a) {
     const bool down = a.kind == 0 && a.kh == 4 && a.kw == 4 && a.stride == 2, up = a.kind == 1;
@@ -663,7 +661,18 @@ static int ws4_geo(const ConvArgs& a) {
     return 0;
 }
 
-bool conv4x4_ws_eligible(int mode, const ConvArgs& a) {
+// grid of the persistent weight-streaming kernels: nct output-channel tiles x ranges of `tpr` consecutive pixel tiles, in units of
+// 8 * nct workgroups (the decode deals ranges to the 8 XCDs)
+static void ws_ranges(int total, int nct, int& grid, int& tpr) {
+    const int unit = 8 * nct;
+    grid = std::max(unit, device_cus() / unit * unit);
+    grid = std::min(grid, (total * nct + unit - 1) / unit * unit);
+    const int nranges = grid / nct;
+    tpr = (total + nranges - 1) / nranges;
+}
+
+// Downsample / Upsample of the wide levels on the weight-streaming machinery
+bool conv4x4_ws_plan(int mode, const ConvArgs& a, ConvPlan& p) {
     if (mode != MODE_BF16 || a.res || a.pro || a.out_stats || a.C1 || !a.x0_bf16) return false;
     const int geo = ws4_geo(a);
     if (!geo) return false;
@@ -674,34 +683,30 @@ bool conv4x4_ws_eligible(int mode, const ConvArgs& a) {
     const long vtiles = (long)a.NF * geo * geo / 256 * (a.kind == 1 ? 4 : 1);
     if (vtiles * nct < 128) return false;
     if ((size_t)a.NF * a.H * a.W * (size_t)a.C0 * 2 >= 0xFFFF0000ull || (size_t)a.NF * 4 * geo * geo >= 0x7FFFFFFFull) return false;
+    p.geo = geo; p.nct = nct; p.total = (int)vtiles;
     return true;
 }
 
-hipError_t launch_conv4x4_ws(const ConvArgs& a, hipStream_t st) {
-    const int geo = ws4_geo(a), bco = a.Cout == 64 ? 64 : 128, nct = a.Cout / bco, up = a.kind == 1;
-    const int total = (int)((long)a.NF * geo * geo / 256) * (up ? 4 : 1);
-    const int cus = device_cus();
-    const int unit = 8 * nct;
-    int grid = std::max(unit, cus / unit * unit);
-    grid = std::min(grid, (total * nct + unit - 1) / unit * unit);
-    const int nranges = grid / nct;
-    int tpr = (total + nranges - 1) / nranges;
+hipError_t conv4x4_ws_launch(int, const ConvArgs& a, const ConvPlan& p, const ConvWork& w, hipStream_t st) {
+    const bool up = a.kind == 1;
+    int grid, tpr;
+    ws_ranges(p.total, p.nct, grid, tpr);
     if (up) tpr = (tpr + 3) / 4 * 4;                      // a range = whole groups of 4 phases (the weight stream's phase follows t & 3)
-    const size_t lds = (size_t)WS_NS * bco * 128 + 2 * (size_t)(geo == 32 ? 321 : 257) * 128 + 512;
-    auto go = [&](auto kfn) -> hipError_t {
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, st, a, tpr, total, nct);
-        return hipGetLastError();
+    auto go = [&](auto geo_c, auto bco_c) {
+        constexpr int GEO = decltype(geo_c)::value, BCO = decltype(bco_c)::value;
+        const size_t lds = (size_t)WS_NS * BCO * 128 + 2 * (size_t)(GEO == 32 ? 321 : 257) * 128 + 512;
+        return with_bool(up, [&](auto up_c) {
+            constexpr int PH = decltype(up_c)::value ? 2 : 1;
+            return LaunchScope(st, "conv4x4_ws_kernel", w.flops, w.bytes, "<%d, %d, %d> %s", GEO, PH, BCO, w.shape)
+                .launch(conv4x4_ws_kernel<GEO, PH, BCO>, dim3(grid), dim3(512), lds, a, tpr, p.total, p.nct);
+        });
     };
-#define VDX_WS4(G_) do { if (bco == 64) return up ? go(conv4x4_ws_kernel<G_, 2, 64>) : go(conv4x4_ws_kernel<G_, 1, 64>);       \
-                         return up ? go(conv4x4_ws_kernel<G_, 2, 128>) : go(conv4x4_ws_kernel<G_, 1, 128>); } while (0)
-    if (geo == 8) VDX_WS4(8);
-    if (geo == 16) VDX_WS4(16);
-    VDX_WS4(32);
-#undef VDX_WS4
+    auto with_geo = [&](auto bco_c) { return p.geo == 8 ? go(Int<8>{}, bco_c) : p.geo == 16 ? go(Int<16>{}, bco_c) : go(Int<32>{}, bco_c); };
+    return a.Cout == 64 ? with_geo(Int<64>{}) : with_geo(Int<128>{});
 }
 
-bool conv3x3_ws_eligible(int mode, const ConvArgs& a) {
+// persistent weight-streaming 3x3 kernel for Cout % 128 == 0 with bf16 tensors
+bool conv3x3_ws_plan(int mode, const ConvArgs& a, ConvPlan& p) {
     if (mode != MODE_BF16 || a.kind != 0 || a.kh != 3 || a.kw != 3 || a.stride != 1 || a.res) return false;
     if (!a.x0_bf16 || (a.C1 && !a.x1_bf16)) return false;
     if (a.C0 % 64 || a.C1 % 64 || a.Cout % 128) return false;
@@ -717,38 +722,31 @@ bool conv3x3_ws_eligible(int mode, const ConvArgs& a) {
     const long tiles = geo == 0 ? (long)a.NF * (a.H / 16) * (a.W / 16) : (long)(a.NF / a.F) * ((a.F + npf - 1) / npf);
     if (tiles * nct < 128) return false;                 // too few tiles to feed the chip from persistent workgroups: generic kernel
     if ((size_t)a.NF * a.H * a.W * (size_t)std::max(a.C0, a.C1) * 2 >= 0xFFFF0000ull) return false;     // 32-bit byte offsets
+    p.geo = geo; p.nct = nct; p.total = (int)tiles;
     return true;
 }
 
-hipError_t launch_conv3x3_ws(const ConvArgs& a, hipStream_t st) {
-    const int geo = ws_geo(a);
-    const int nct = a.Cout / 128;
-    const int npf = geo == 0 ? 1 : 256 / (a.H * a.W);
-    const int total = geo == 0 ? a.NF * (a.H / 16) * (a.W / 16) : (a.NF / a.F) * ((a.F + npf - 1) / npf);
-    const int cus = device_cus();
-    const int unit = 8 * nct;                             // the decode deals ranges to the 8 XCDs
-    int grid = std::max(unit, cus / unit * unit);
-    grid = std::min(grid, (total * nct + unit - 1) / unit * unit);
-    const int nranges = grid / nct;
-    const int tpr = (total + nranges - 1) / nranges;
-    const int HPX = geo == 0 ? 18 * 18 : 257;
-    const size_t lds = (size_t)WS_NS * WS_SLAB + 2 * (size_t)HPX * 128 + 512 + (a.pro ? (size_t)a.CinPad * 8 + 256 : 0);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    auto go = [&](auto kfn) -> hipError_t {
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
 #ifndef VDX_WS_PIN_MB
 #define VDX_WS_PIN_MB 0        // pin output-channel tiles to XCDs when their weights together exceed this many MB (0: never).  Measured with 3 (r03, 512 -> 512 at 8 x 8):
                                // same time (251 vs 250 us plain, 307 vs 317 with the prologue) for MORE HBM traffic (401-454 vs 290-326 MB per launch: the input tiles
                                // are then fetched by four XCDs) -- the Infinity Cache serves the weight stream as fast as the L2 does; off
 #endif
-        const size_t wbytes = (size_t)9 * a.Cout * a.CinPad * 2;
-        const int pin = (VDX_WS_PIN_MB > 0 && nct > 1 && wbytes > (size_t)VDX_WS_PIN_MB * 1024 * 1024) ? 1 : 0;
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), lds, st, a, tpr, total, nct, pin);
-        return hipGetLastError();
+hipError_t conv3x3_ws_launch(int, const ConvArgs& a, const ConvPlan& p, const ConvWork& w, hipStream_t st) {
+    int grid, tpr;
+    ws_ranges(p.total, p.nct, grid, tpr);
+    const size_t wbytes = (size_t)9 * a.Cout * a.CinPad * 2;
+    const int pin = (VDX_WS_PIN_MB > 0 && p.nct > 1 && wbytes > (size_t)VDX_WS_PIN_MB * 1024 * 1024) ? 1 : 0;
+    auto go = [&](auto geo_c) {
+        constexpr int GEO = decltype(geo_c)::value;
+        return with_bool(a.pro != 0, [&](auto pro_c) {
+            constexpr bool PRO = decltype(pro_c)::value;
+            // (at most 154 KB: the prologue's coefficient tables are bounded by the plan's C0 <= 1024)
+            const size_t lds = (size_t)WS_NS * WS_SLAB + 2 * (size_t)WsGeo<GEO>::HPX * 128 + 512 + (PRO ? (size_t)a.CinPad * 8 + 256 : 0);
+            return LaunchScope(st, "conv3x3_ws_kernel", w.flops, w.bytes, "<%d, %s> %s", GEO, PRO ? "true" : "false", w.shape)
+                .launch(conv3x3_ws_kernel<GEO, PRO>, dim3(grid), dim3(512), lds, a, tpr, p.total, p.nct, pin);
+        });
     };
-    if (geo == 0) return a.pro ? go(conv3x3_ws_kernel<0, true>) : go(conv3x3_ws_kernel<0, false>);
-    if (geo == 8) return a.pro ? go(conv3x3_ws_kernel<8, true>) : go(conv3x3_ws_kernel<8, false>);
-    return a.pro ? go(conv3x3_ws_kernel<16, true>) : go(conv3x3_ws_kernel<16, false>);
+    return p.geo == 0 ? go(Int<0>{}) : p.geo == 8 ? go(Int<8>{}) : go(Int<16>{});
 }
 
 }  // namespace vdx

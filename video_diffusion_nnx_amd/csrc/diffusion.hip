@@ -689,78 +689,59 @@ hipError_t launch_q_sample(const float* x0, const int* t, const float* noise, fl
 }
 
 hipError_t launch_p_sample(const PSampleArgs& a, int B, hipStream_t st) {
-    LaunchScope ls(st, "p_sample_kernel", 0.0, 12.0 * B * a.per_sample, "B%d px%ld", B, a.per_sample);
-    hipLaunchKernelGGL(p_sample_kernel, dim3(ew_blocks((a.per_sample + 3) / 4), B), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return LaunchScope(st, "p_sample_kernel", 0.0, 12.0 * B * a.per_sample, "B%d px%ld", B, a.per_sample)
+        .launch(p_sample_kernel, dim3(ew_blocks((a.per_sample + 3) / 4), B), dim3(256), 0, a);
 }
 
 hipError_t launch_p_sample_masked(const PSampleArgs& a, const MaskArgs& m, int B, hipStream_t st) {
-    LaunchScope ls(st, "p_sample_masked_kernel", 0.0, 17.0 * B * a.per_sample, "B%d px%ld", B, a.per_sample);
-    hipLaunchKernelGGL(p_sample_masked_kernel, dim3(ew_blocks(a.per_sample / 4), B), dim3(256), 0, st, a, m);
-    return hipGetLastError();
+    return LaunchScope(st, "p_sample_masked_kernel", 0.0, 17.0 * B * a.per_sample, "B%d px%ld", B, a.per_sample)
+        .launch(p_sample_masked_kernel, dim3(ew_blocks(a.per_sample / 4), B), dim3(256), 0, a, m);
 }
 
 hipError_t launch_resample_advance(int* t, int B, unsigned long long* step_dev, int U, hipStream_t st) {
-    LaunchScope ls(st, "resample_advance_kernel", 0.0, 0.0, "B%d", B);
-    hipLaunchKernelGGL(resample_advance_kernel, dim3(1), dim3(1024), 0, st, t, B, step_dev, U);
-    return hipGetLastError();
+    return LaunchScope(st, "resample_advance_kernel", 0.0, 0.0, "B%d", B).launch(resample_advance_kernel, dim3(1), dim3(1024), 0, t, B, step_dev, U);
 }
 
 hipError_t launch_inpaint_init(float* x, const float* known, const unsigned char* mask, const float* mtab, int T, int t0, long n, hipStream_t st) {
-    LaunchScope ls(st, "inpaint_init_kernel", 0.0, 13.0 * n, "n%ld", n);
-    hipLaunchKernelGGL(inpaint_init_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, st, x, known, mask, mtab, T, t0, n);
-    return hipGetLastError();
+    return LaunchScope(st, "inpaint_init_kernel", 0.0, 13.0 * n, "n%ld", n).launch(inpaint_init_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, x, known, mask, mtab, T, t0, n);
 }
 
 hipError_t launch_advance(int* t, int B, unsigned long long* dev_offset, hipStream_t st) {
-    LaunchScope ls(st, "advance_kernel", 0.0, 0.0, "B%d", B);
-    hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1024), 0, st, t, B, dev_offset);
-    return hipGetLastError();
+    return LaunchScope(st, "advance_kernel", 0.0, 0.0, "B%d", B).launch(advance_kernel, dim3(1), dim3(1024), 0, t, B, dev_offset);
 }
 
 hipError_t launch_ddim_step(const float* x, const float* eps, float* out, const float* ac, const int* seq, const unsigned long long* step_dev,
                             const float* thres, int clip, int B, int C, long per_sample, hipStream_t st) {
-    LaunchScope ls(st, "ddim_step_kernel", 0.0, 12.0 * B * per_sample, "B%d px%ld", B, per_sample);
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(ew_blocks(per_sample), B), dim3(256), 0, st, x, eps, out, ac, seq, step_dev, thres, clip, C, per_sample);
-    return hipGetLastError();
+    return LaunchScope(st, "ddim_step_kernel", 0.0, 12.0 * B * per_sample, "B%d px%ld", B, per_sample)
+        .launch(ddim_step_kernel, dim3(ew_blocks(per_sample), B), dim3(256), 0, x, eps, out, ac, seq, step_dev, thres, clip, C, per_sample);
 }
 
 hipError_t launch_ddim_step_masked(const float* x, const float* eps, float* out, const float* ac, const int* seq, const unsigned long long* step_dev,
                                    const float* thres, int clip, int B, int C, long per_sample, const MaskArgs& m, int T, unsigned long long seed,
                                    hipStream_t st) {
-    LaunchScope ls(st, "ddim_step_masked_kernel", 0.0, 17.0 * B * per_sample, "B%d px%ld", B, per_sample);
-    hipLaunchKernelGGL(ddim_step_masked_kernel, dim3(ew_blocks(per_sample / 4), B), dim3(256), 0, st, x, eps, out, ac, seq, step_dev, thres, clip, C,
-                       per_sample, m, T, seed);
-    return hipGetLastError();
+    return LaunchScope(st, "ddim_step_masked_kernel", 0.0, 17.0 * B * per_sample, "B%d px%ld", B, per_sample)
+        .launch(ddim_step_masked_kernel, dim3(ew_blocks(per_sample / 4), B), dim3(256), 0, x, eps, out, ac, seq, step_dev, thres, clip, C, per_sample, m, T, seed);
 }
 
 hipError_t launch_dpm_step(const float* x, const float* eps, float* out, float* hist, const float* ac, const int* seq,
                            const unsigned long long* step_dev, const float* thres, int clip, int order, int B, int C, long per_sample,
                            const MaskArgs* m, int T, unsigned long long seed, hipStream_t st) {
     const dim3 grid(ew_blocks(per_sample / 4), B);
-    if (m) {
-        LaunchScope ls(st, "dpm_step_masked_kernel", 0.0, 25.0 * B * per_sample, "B%d px%ld o%d", B, per_sample, order);
-        hipLaunchKernelGGL(dpm_step_kernel<true>, grid, dim3(256), 0, st, x, eps, out, hist, ac, seq, step_dev, thres, clip, order, C, per_sample,
-                           *m, T, seed);
-    } else {
-        LaunchScope ls(st, "dpm_step_kernel", 0.0, 20.0 * B * per_sample, "B%d px%ld o%d", B, per_sample, order);
-        hipLaunchKernelGGL(dpm_step_kernel<false>, grid, dim3(256), 0, st, x, eps, out, hist, ac, seq, step_dev, thres, clip, order, C, per_sample,
-                           MaskArgs{}, 0, 0ull);
-    }
-    return hipGetLastError();
+    if (m)
+        return LaunchScope(st, "dpm_step_masked_kernel", 0.0, 25.0 * B * per_sample, "B%d px%ld o%d", B, per_sample, order)
+            .launch(dpm_step_kernel<true>, grid, dim3(256), 0, x, eps, out, hist, ac, seq, step_dev, thres, clip, order, C, per_sample, *m, T, seed);
+    return LaunchScope(st, "dpm_step_kernel", 0.0, 20.0 * B * per_sample, "B%d px%ld o%d", B, per_sample, order)
+        .launch(dpm_step_kernel<false>, grid, dim3(256), 0, x, eps, out, hist, ac, seq, step_dev, thres, clip, order, C, per_sample, MaskArgs{}, 0, 0ull);
 }
 
 hipError_t launch_ddim_advance(int* t, int B, const int* seq, unsigned long long* step_dev, hipStream_t st) {
-    LaunchScope ls(st, "ddim_advance_kernel", 0.0, 0.0, "B%d", B);
-    hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(256), 0, st, t, B, seq, step_dev);
-    return hipGetLastError();
+    return LaunchScope(st, "ddim_advance_kernel", 0.0, 0.0, "B%d", B).launch(ddim_advance_kernel, dim3(1), dim3(256), 0, t, B, seq, step_dev);
 }
 
 hipError_t launch_dyn_thres(const float* x, const float* eps, const int* t, const float* tables, int T, float q, float* out, int B, int C,
                             long per_sample, hipStream_t st) {
-    LaunchScope ls(st, "dyn_thres_kernel", 0.0, 8.0 * B * per_sample, "B%d px%ld", B, per_sample);
-    hipLaunchKernelGGL(dyn_thres_kernel, dim3(B), dim3(1024), 0, st, x, eps, t, tables, T, q, out, C, per_sample);
-    return hipGetLastError();
+    return LaunchScope(st, "dyn_thres_kernel", 0.0, 8.0 * B * per_sample, "B%d px%ld", B, per_sample)
+        .launch(dyn_thres_kernel, dim3(B), dim3(1024), 0, x, eps, t, tables, T, q, out, C, per_sample);
 }
 
 hipError_t launch_loss(const float* eps_hat, const float* noise, double* acc, int B, int Cc, long fhw, int l2, hipStream_t st) {
@@ -800,16 +781,14 @@ hipError_t launch_cfg_combine(const float* eps2, float* out, float cond_scale, f
     double* factor = nullptr;
     if (rescale > 0.f) {
         factor = scratch + cfg_factor_offset(B);
-        {
-            LaunchScope ls(st, "cfg_stats_partial_kernel", 0.0, 8.0 * B * per_sample, "B%d px%ld", B, per_sample);
-            hipLaunchKernelGGL(cfg_stats_partial_kernel, dim3(kCfgBlocks, B), dim3(256), 0, st, eps2, cond_scale, scratch, B, per_sample);
-        }
-        LaunchScope ls(st, "cfg_stats_final_kernel", 0.0, 0.0, "B%d", B);
-        hipLaunchKernelGGL(cfg_stats_final_kernel, dim3(1), dim3(256), 0, st, scratch, factor, rescale, B, per_sample);
+        hipError_t e = LaunchScope(st, "cfg_stats_partial_kernel", 0.0, 8.0 * B * per_sample, "B%d px%ld", B, per_sample)
+                           .launch(cfg_stats_partial_kernel, dim3(kCfgBlocks, B), dim3(256), 0, eps2, cond_scale, scratch, B, per_sample);
+        if (e != hipSuccess) return e;
+        e = LaunchScope(st, "cfg_stats_final_kernel", 0.0, 0.0, "B%d", B).launch(cfg_stats_final_kernel, dim3(1), dim3(256), 0, scratch, factor, rescale, B, per_sample);
+        if (e != hipSuccess) return e;
     }
-    LaunchScope ls(st, "cfg_combine_kernel", 0.0, 12.0 * B * per_sample, "B%d px%ld", B, per_sample);
-    hipLaunchKernelGGL(cfg_combine_kernel, dim3(ew_blocks(per_sample / 4), B), dim3(256), 0, st, eps2, out, cond_scale, factor, B, per_sample);
-    return hipGetLastError();
+    return LaunchScope(st, "cfg_combine_kernel", 0.0, 12.0 * B * per_sample, "B%d px%ld", B, per_sample)
+        .launch(cfg_combine_kernel, dim3(ew_blocks(per_sample / 4), B), dim3(256), 0, eps2, out, cond_scale, factor, B, per_sample);
 }
 
 hipError_t launch_affine(const float* x, float* y, long n, float a, float b, hipStream_t st) {

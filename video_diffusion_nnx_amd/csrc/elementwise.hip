@@ -188,9 +188,8 @@ hipError_t launch_gn_silu_apply16(float* y_bf16, const double* stats, const floa
     if (C % 8 || C > 1024 || groups <= 0 || groups > 32 || C % groups) return hipErrorInvalidValue;
     const long n = pix_per_sample * (C / 8);
     const int gx = (int)std::max<long>(1, std::min<long>((n + 1023) / 1024, 2048));
-    LaunchScope ls(st, "gn_silu_apply16_kernel", 8.0 * batch * pix_per_sample * C, 4.0 * batch * pix_per_sample * C, "C%d px%ld x %d", C, pix_per_sample, batch);
-    hipLaunchKernelGGL(gn_silu_apply16_kernel, dim3(gx, batch), dim3(256), 0, st, reinterpret_cast<unsigned*>(y_bf16), stats, gamma, beta, ss, ss_stride, groups, C, pix_per_sample);
-    return hipGetLastError();
+    return LaunchScope(st, "gn_silu_apply16_kernel", 8.0 * batch * pix_per_sample * C, 4.0 * batch * pix_per_sample * C, "C%d px%ld x %d", C, pix_per_sample, batch)
+        .launch(gn_silu_apply16_kernel, dim3(gx, batch), dim3(256), 0, reinterpret_cast<unsigned*>(y_bf16), stats, gamma, beta, ss, ss_stride, groups, C, pix_per_sample);
 }
 
 // ---- tail with the 1x1 res_conv inside (bf16 tensors, bf16 MFMA operands) ---------------------------------------------------------
@@ -351,14 +350,12 @@ static hipError_t launch_tail_rc16(const TailArgs& a, hipStream_t st) {
     // least ~2048 workgroups in the launch
     const long need = (a.pix_per_sample / 16 + 3) / 4;
     const long gx = std::min<long>(need, std::max<long>(std::max<long>(1, need / 8), (2048 + a.batch - 1) / std::max(1, a.batch)));
-    auto go = [&](auto kfn) -> hipError_t {
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
+    auto go = [&](auto kfn) {
         const double px = (double)a.batch * a.pix_per_sample;       // y2, x (concat) in + out, bf16; the 1x1 res_conv on the MFMA
-        LaunchScope ls(st, "resblock_tail_rc16_kernel", 2.0 * px * CIN * COUT + (a.fin_w ? 2.0 * px * COUT : 0.0),
-                       px * (CIN + (a.fin_w ? 1.0 : 2.0) * COUT) * 2 + (a.fin_w ? px * 4 : 0.0) + 2.0 * CIN * COUT, "<%d, %d, %s> px%ld x %d", CIN, COUT,
-                       a.fin_w ? "true, head" : (a.C1 ? "true" : "false"), a.pix_per_sample, a.batch);
-        hipLaunchKernelGGL(kfn, dim3((unsigned)gx, a.batch), dim3(256), lds, st, a);
-        return hipGetLastError();
+        return LaunchScope(st, "resblock_tail_rc16_kernel", 2.0 * px * CIN * COUT + (a.fin_w ? 2.0 * px * COUT : 0.0),
+                           px * (CIN + (a.fin_w ? 1.0 : 2.0) * COUT) * 2 + (a.fin_w ? px * 4 : 0.0) + 2.0 * CIN * COUT, "<%d, %d, %s> px%ld x %d", CIN, COUT,
+                           a.fin_w ? "true, head" : (a.C1 ? "true" : "false"), a.pix_per_sample, a.batch)
+            .launch(kfn, dim3((unsigned)gx, a.batch), dim3(256), lds, a);
     };
     if constexpr ((CIN == 128 && COUT == 64) || (CIN == 64 && COUT == 32)) {      // (the last block of a dim-64 / dim-32 network: a concat)
         if (a.fin_w) return a.C1 ? go(resblock_tail_rc16_kernel<CIN, COUT, true, true>) : hipErrorInvalidValue;
@@ -396,13 +393,9 @@ hipError_t launch_resblock_tail(TailArgs a, hipStream_t st) {
         const int gx = (int)std::min<long>(need, std::max<long>(1, std::min<long>(2048, total / std::max(1, a.batch))));
         dim3 grid(gx, a.batch);
         const double el = (double)a.batch * a.pix_per_sample * a.C;
-        LaunchScope ls(st, "resblock_tail16_kernel", 10.0 * el, 3.0 * el * 2, "<%d> C%d px%ld x %d", vpl, a.C, a.pix_per_sample, a.batch);
-        switch (vpl) {
-            case 1: hipLaunchKernelGGL(resblock_tail16_kernel<1>, grid, dim3(256), 0, st, a); break;
-            case 2: hipLaunchKernelGGL(resblock_tail16_kernel<2>, grid, dim3(256), 0, st, a); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+        if (vpl != 1 && vpl != 2) return hipErrorInvalidValue;
+        return LaunchScope(st, "resblock_tail16_kernel", 10.0 * el, 3.0 * el * 2, "<%d> C%d px%ld x %d", vpl, a.C, a.pix_per_sample, a.batch)
+            .launch(vpl == 1 ? resblock_tail16_kernel<1> : resblock_tail16_kernel<2>, grid, dim3(256), 0, a);
     }
     const int quads = a.C / 4;
     int lpp = 1;
@@ -416,15 +409,10 @@ hipError_t launch_resblock_tail(TailArgs a, hipStream_t st) {
     int gx = (int)std::min<long>(need32, std::max<long>(1, std::min<long>(2048, total32 / std::max(1, a.batch))));
     dim3 grid(gx, a.batch);
     const double el = (double)a.batch * a.pix_per_sample * a.C;
-    LaunchScope ls(st, "resblock_tail_kernel", 10.0 * el, el * ((a.y2_bf16 ? 2.0 : 4.0) + (a.r_bf16 ? 2.0 : 4.0) + (a.out_bf16 ? 2.0 : 4.0)), "<%d> C%d px%ld x %d y2_16 %d", vpl == 3 ? 4 : vpl,
-                   a.C, a.pix_per_sample, a.batch, a.y2_bf16);
-    switch (vpl) {
-        case 1: hipLaunchKernelGGL(resblock_tail_kernel<1>, grid, dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(resblock_tail_kernel<2>, grid, dim3(256), 0, st, a); break;
-        case 3: case 4: hipLaunchKernelGGL(resblock_tail_kernel<4>, grid, dim3(256), 0, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (vpl < 1 || vpl > 4) return hipErrorInvalidValue;
+    return LaunchScope(st, "resblock_tail_kernel", 10.0 * el, el * ((a.y2_bf16 ? 2.0 : 4.0) + (a.r_bf16 ? 2.0 : 4.0) + (a.out_bf16 ? 2.0 : 4.0)), "<%d> C%d px%ld x %d y2_16 %d",
+                       vpl == 3 ? 4 : vpl, a.C, a.pix_per_sample, a.batch, a.y2_bf16)
+        .launch(vpl == 1 ? resblock_tail_kernel<1> : vpl == 2 ? resblock_tail_kernel<2> : resblock_tail_kernel<4>, grid, dim3(256), 0, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -595,16 +583,14 @@ hipError_t launch_init_conv_mode(int mode, const float* x, const float* w, const
         const size_t lds = ((23 * 23 * 4 + 15) / 16) * 16 + (size_t)(64 + 256) * (64 * 2 + 16);
         dim3 grid(((W + 15) / 16) * ((H + 15) / 16), B * F);
         const double px = (double)B * F * H * W;
-        LaunchScope ls(st, "init_conv_mfma_kernel", 2.0 * px * K * K * Cout, px * (4.0 + Cout * (y_bf16 ? 2.0 : 4.0)), "k%d 1->%d %dx%dx%d", K, Cout, B * F, H, W);
-        hipLaunchKernelGGL(init_conv_mfma_kernel, grid, dim3(256), lds, st, x, w, bias, y, B, F, H, W, Cout, K, y_bf16);
-        return hipGetLastError();
+        return LaunchScope(st, "init_conv_mfma_kernel", 2.0 * px * K * K * Cout, px * (4.0 + Cout * (y_bf16 ? 2.0 : 4.0)), "k%d 1->%d %dx%dx%d", K, Cout, B * F, H, W)
+            .launch(init_conv_mfma_kernel, grid, dim3(256), lds, x, w, bias, y, B, F, H, W, Cout, K, y_bf16);
     }
     const int TW = 16 + K - 1;
     dim3 grid(((W + 15) / 16) * ((H + 15) / 16), B * F, (Cout + 15) / 16);
     const double px = (double)B * F * H * W;
-    LaunchScope ls(st, "init_conv_kernel", 2.0 * px * K * K * Cin * Cout, px * (4.0 * Cin + Cout * (y_bf16 ? 2.0 : 4.0)), "k%d %d->%d %dx%dx%d", K, Cin, Cout, B * F, H, W);
-    hipLaunchKernelGGL(init_conv_kernel, grid, dim3(256), (size_t)Cin * TW * TW * 4, st, x, w, bias, y, B, Cin, F, H, W, Cout, K, y_bf16);
-    return hipGetLastError();
+    return LaunchScope(st, "init_conv_kernel", 2.0 * px * K * K * Cin * Cout, px * (4.0 * Cin + Cout * (y_bf16 ? 2.0 : 4.0)), "k%d %d->%d %dx%dx%d", K, Cin, Cout, B * F, H, W)
+        .launch(init_conv_kernel, grid, dim3(256), (size_t)Cin * TW * TW * 4, x, w, bias, y, B, Cin, F, H, W, Cout, K, y_bf16);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -681,14 +667,9 @@ hipError_t launch_final_conv(const float* x, const float* w, const float* bias, 
     if (x_bf16 && D % 8 == 0 && D <= 128 && ((D / 8) & (D / 8 - 1)) == 0 && Cout >= 1 && Cout <= 4) {
         const int lpp = D / 8, ppb = 256 / lpp;
         const int blocks = (int)std::min<long>((npix + 4L * ppb - 1) / (4L * ppb), 4096);
-        LaunchScope ls(st, "final_conv16_kernel", 2.0 * npix * D * Cout, (double)npix * (D * 2.0 + Cout * 4.0), "<%d> D%d px%ld", Cout, D, npix);
-        switch (Cout) {
-            case 1: hipLaunchKernelGGL(final_conv16_kernel<1>, dim3(blocks), dim3(256), 0, st, x, w, bias, y, npix, D, lpp); break;
-            case 2: hipLaunchKernelGGL(final_conv16_kernel<2>, dim3(blocks), dim3(256), 0, st, x, w, bias, y, npix, D, lpp); break;
-            case 3: hipLaunchKernelGGL(final_conv16_kernel<3>, dim3(blocks), dim3(256), 0, st, x, w, bias, y, npix, D, lpp); break;
-            default: hipLaunchKernelGGL(final_conv16_kernel<4>, dim3(blocks), dim3(256), 0, st, x, w, bias, y, npix, D, lpp); break;
-        }
-        return hipGetLastError();
+        auto kfn = Cout == 1 ? final_conv16_kernel<1> : Cout == 2 ? final_conv16_kernel<2> : Cout == 3 ? final_conv16_kernel<3> : final_conv16_kernel<4>;
+        return LaunchScope(st, "final_conv16_kernel", 2.0 * npix * D * Cout, (double)npix * (D * 2.0 + Cout * 4.0), "<%d> D%d px%ld", Cout, D, npix)
+            .launch(kfn, dim3(blocks), dim3(256), 0, x, w, bias, y, npix, D, lpp);
     }
     const int per = (x_bf16 && D % 8 == 0) ? 8 : 4;       // channels per lane and pass
     if (per == 4) x_bf16 = x_bf16 ? -1 : 0;
@@ -697,9 +678,8 @@ hipError_t launch_final_conv(const float* x, const float* w, const float* bias, 
     while (lpp * per < D && lpp < 16) lpp <<= 1;
     const int ppb = 256 / lpp;
     const int blocks = (int)std::min<long>((npix + ppb - 1) / ppb, 4096);
-    LaunchScope ls(st, "final_conv_kernel", 2.0 * npix * D * Cout, (double)npix * (D * (x_bf16 ? 2.0 : 4.0) + Cout * 4.0), "D%d->%d px%ld", D, Cout, npix);
-    hipLaunchKernelGGL(final_conv_kernel, dim3(blocks), dim3(256), 0, st, x, w, bias, y, npix, D, Cout, lpp, x_bf16);
-    return hipGetLastError();
+    return LaunchScope(st, "final_conv_kernel", 2.0 * npix * D * Cout, (double)npix * (D * (x_bf16 ? 2.0 : 4.0) + Cout * 4.0), "D%d->%d px%ld", D, Cout, npix)
+        .launch(final_conv_kernel, dim3(blocks), dim3(256), 0, x, w, bias, y, npix, D, Cout, lpp, x_bf16);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -755,9 +735,8 @@ __global__ __launch_bounds__(256) void time_mlp_kernel(TimeMlpArgs P) {
 }
 
 hipError_t launch_time_mlp(const TimeMlpArgs& a, int B, hipStream_t st) {
-    LaunchScope ls(st, "time_mlp_kernel", 2.0 * B * (a.dim * a.time_dim + (double)a.time_dim * a.time_dim), 4.0 * (a.dim * a.time_dim + (double)a.time_dim * a.time_dim), "dim%d B%d", a.dim, B);
-    hipLaunchKernelGGL(time_mlp_kernel, dim3(B), dim3(256), (size_t)(a.dim + a.time_dim) * 4, st, a);
-    return hipGetLastError();
+    return LaunchScope(st, "time_mlp_kernel", 2.0 * B * (a.dim * a.time_dim + (double)a.time_dim * a.time_dim), 4.0 * (a.dim * a.time_dim + (double)a.time_dim * a.time_dim), "dim%d B%d", a.dim, B)
+        .launch(time_mlp_kernel, dim3(B), dim3(256), (size_t)(a.dim + a.time_dim) * 4, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -841,16 +820,11 @@ hipError_t launch_resblock_ss(const float* params, const float* temb, const SsLa
     // lin_base (the pre-LayerNorm values, also what the backward reads) is required scratch
     if (!lin_base || nlayers <= 0) return hipErrorInvalidValue;
     const size_t lds = ((size_t)SS_BG * temb_dim + 4 * SS_BG * 64) * 4;
-    hipError_t e;
-    {
-        LaunchScope ls(st, "resblock_ss_lin_kernel", 0.0, 0.0, "layers%d B%d", nlayers, B);
-        hipLaunchKernelGGL(resblock_ss_lin_kernel, dim3(nlayers, (max_n + 63) / 64, (B + SS_BG - 1) / SS_BG), dim3(256), lds, st, params, temb, layers,
-                           lin_base, temb_dim, B);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    LaunchScope ls(st, "resblock_ss_norm_kernel", 0.0, 0.0, "layers%d B%d", nlayers, B);
-    hipLaunchKernelGGL(resblock_ss_norm_kernel, dim3(B, nlayers), dim3(256), 0, st, params, layers, lin_base, ss_base, B);
-    return hipGetLastError();
+    const hipError_t e = LaunchScope(st, "resblock_ss_lin_kernel", 0.0, 0.0, "layers%d B%d", nlayers, B)
+                             .launch(resblock_ss_lin_kernel, dim3(nlayers, (max_n + 63) / 64, (B + SS_BG - 1) / SS_BG), dim3(256), lds, params, temb, layers, lin_base, temb_dim, B);
+    if (e != hipSuccess) return e;
+    return LaunchScope(st, "resblock_ss_norm_kernel", 0.0, 0.0, "layers%d B%d", nlayers, B)
+        .launch(resblock_ss_norm_kernel, dim3(B, nlayers), dim3(256), 0, params, layers, lin_base, ss_base, B);
 }
 
 }  // namespace vdx

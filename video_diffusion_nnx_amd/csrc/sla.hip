@@ -1102,12 +1102,10 @@ hipError_t launch_sla_heads(SlaArgs a, void* O, hipStream_t st) {
     long fpb = (a.NF * (long)a.heads + 255) / 256;       // one round of workgroups over the chip (one 8-wave workgroup per CU: ~200 VGPRs)
     fpb = std::max<long>(8, (fpb + 7) / 8 * 8);
     const long chunks = (a.NF + fpb - 1) / fpb;
-    auto go = [&](auto kfn) -> hipError_t {
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-        const SlaWork sw = sla_work(a, 2, true, true, false);
-        LaunchScope ls(st, "sla_head_kernel", sw.flops, sw.bytes, "<io16 %d, %d> C%d N%d NF%d", a.io_bf16, a.N % 64 == 0 ? 4 : 1, a.C, a.N, a.NF);
-        hipLaunchKernelGGL(kfn, dim3((unsigned)((chunks + 7) / 8 * 64)), dim3(512), lds, st, a, O, (int)fpb, (int)chunks);
-        return hipGetLastError();
+    const SlaWork sw = sla_work(a, 2, true, true, false);
+    auto go = [&](auto kfn) {
+        return LaunchScope(st, "sla_head_kernel", sw.flops, sw.bytes, "<io16 %d, %d> C%d N%d NF%d", a.io_bf16, a.N % 64 == 0 ? 4 : 1, a.C, a.N, a.NF)
+            .launch(kfn, dim3((unsigned)((chunks + 7) / 8 * 64)), dim3(512), lds, a, O, (int)fpb, (int)chunks);
     };
     if (a.N % 64 == 0) return a.io_bf16 ? go(sla_head_kernel<true, 4>) : go(sla_head_kernel<false, 4>);
     return a.io_bf16 ? go(sla_head_kernel<true, 1>) : go(sla_head_kernel<false, 1>);
@@ -1135,13 +1133,10 @@ static hipError_t launch_sla_out_t(const SlaArgs& a, hipStream_t st) {
     constexpr int RSQ = (MODE == MODE_F32) ? 160 : 80;
     constexpr int RSO = 256 * M::ES + 16;
     const size_t lds = std::max<size_t>((size_t)(64 + 256) * ROW_STRIDE, (size_t)4 * 64 * RSQ + (size_t)64 * RSO);
-    auto kfn = sla_out_kernel<MODE, TMO>;
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const int tiles = (a.N + 63) / 64;
     const SlaWork sw = sla_work(a, M::ES, false, true, true);
-    LaunchScope ls(st, "sla_out_kernel", sw.flops, sw.bytes, "<%d, %d> C%d N%d NF%d io16 %d", MODE, TMO, a.C, a.N, a.NF, a.io_bf16);
-    hipLaunchKernelGGL(kfn, dim3(a.NF * tiles), dim3(256), lds, st, a);
-    return hipGetLastError();
+    return LaunchScope(st, "sla_out_kernel", sw.flops, sw.bytes, "<%d, %d> C%d N%d NF%d io16 %d", MODE, TMO, a.C, a.N, a.NF, a.io_bf16)
+        .launch(sla_out_kernel<MODE, TMO>, dim3(a.NF * tiles), dim3(256), lds, a);
 }
 
 #ifndef VDX_SLA_W_MIN_N
@@ -1153,14 +1148,16 @@ static bool sla_out_w_eligible(const SlaArgs& a) {
 }
 static hipError_t launch_sla_out_w(const SlaArgs& a, hipStream_t st) {
     const size_t lds = 256 * 128 + 64 * 512 + 2 * 256 * 72;
-    auto kfn = sla_out_w_kernel<0>;
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const PersistentSplit s = persistent_split(a.NF, device_cus());
     const int fpb = (int)s.per, blocks = (int)s.workers;
     const SlaWork sw = sla_work(a, 2, false, true, true);
-    LaunchScope ls(st, "sla_out_w_kernel", sw.flops, sw.bytes, "C%d N%d NF%d", a.C, a.N, a.NF);
-    hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, st, a, fpb);
-    return hipGetLastError();
+    return LaunchScope(st, "sla_out_w_kernel", sw.flops, sw.bytes, "C%d N%d NF%d", a.C, a.N, a.NF).launch(sla_out_w_kernel<0>, dim3(blocks), dim3(512), lds, a, fpb);
+}
+
+template <int MODE>
+static hipError_t launch_sla_combine(const SlaArgs& a, hipStream_t st) {
+    return LaunchScope(st, "sla_combine_kernel", 0.0, (double)a.NF * a.nchunk * a.heads * SLA_PART * 4, "<%d> NF%d nchunk%d", MODE, a.NF, a.nchunk)
+        .launch(sla_combine_kernel<MODE>, dim3(a.NF * a.heads), dim3(256), 0, a.part, a.ctxT, a.nchunk, a.heads);
 }
 
 template <int MODE, int NKT, int TMO, int TNO, bool IO16>
@@ -1169,29 +1166,19 @@ static hipError_t launch_sla8_t(const SlaArgs& a, hipStream_t st) {
     using T = SlaTile<MODE, NKT, IO16>;
     const size_t lds_ctx = 2 * (size_t)T::BUF;
     const size_t lds_out = lds_ctx + (size_t)64 * (256 * M::ES + 16) + (IO16 ? (size_t)64 * (NKT * M::KT * 4 + 16) : 0);
-    auto kc = sla_ctx8_kernel<MODE, NKT, IO16>;
-    auto ko = sla_out8_kernel<MODE, NKT, TMO, TNO, IO16>;
-    hipError_t e;
-    if ((e = lds_opt_in(kc, lds_ctx)) != hipSuccess) return e;
-    if ((e = lds_opt_in(ko, lds_out)) != hipSuccess) return e;
-    {
-        const SlaWork sw = sla_work(a, M::ES, true, false, false);
-        LaunchScope ls(st, "sla_ctx8_kernel", sw.flops, sw.bytes, "<%d, %d, %d> C%d N%d NF%d nchunk%d", MODE, NKT, (int)IO16, a.C, a.N, a.NF, a.nchunk);
-        hipLaunchKernelGGL(kc, dim3(a.NF * a.nchunk), dim3(512), lds_ctx, st, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    const SlaWork swc = sla_work(a, M::ES, true, false, false);
+    hipError_t e = LaunchScope(st, "sla_ctx8_kernel", swc.flops, swc.bytes, "<%d, %d, %d> C%d N%d NF%d nchunk%d", MODE, NKT, (int)IO16, a.C, a.N, a.NF, a.nchunk)
+                       .launch(sla_ctx8_kernel<MODE, NKT, IO16>, dim3(a.NF * a.nchunk), dim3(512), lds_ctx, a);
+    if (e != hipSuccess) return e;
     if (a.nchunk > 1) {                                       // (one chunk per frame: sla_ctx8_kernel wrote ctxT itself)
-        LaunchScope ls(st, "sla_combine_kernel", 0.0, (double)a.NF * a.nchunk * a.heads * SLA_PART * 4, "<%d> NF%d nchunk%d", MODE, a.NF, a.nchunk);
-        hipLaunchKernelGGL(sla_combine_kernel<MODE>, dim3(a.NF * a.heads), dim3(256), 0, st, a.part, a.ctxT, a.nchunk, a.heads);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = launch_sla_combine<MODE>(a, st)) != hipSuccess) return e;
     }
     if constexpr (MODE == MODE_BF16 && IO16 && NKT == 1 && TNO == 2) {
         if (sla_out_w_eligible(a)) return launch_sla_out_w(a, st);      // C = 64, many frames: one wave per 64 pixels
     }
     const SlaWork sw = sla_work(a, M::ES, false, true, true);
-    LaunchScope ls(st, "sla_out8_kernel", sw.flops, sw.bytes, "<%d, %d, %d, %d, %d> C%d N%d NF%d", MODE, NKT, TMO, TNO, (int)IO16, a.C, a.N, a.NF);
-    hipLaunchKernelGGL(ko, dim3(a.NF * a.nchunk), dim3(512), lds_out, st, a);
-    return hipGetLastError();
+    return LaunchScope(st, "sla_out8_kernel", sw.flops, sw.bytes, "<%d, %d, %d, %d, %d> C%d N%d NF%d", MODE, NKT, TMO, TNO, (int)IO16, a.C, a.N, a.NF)
+        .launch(sla_out8_kernel<MODE, NKT, TMO, TNO, IO16>, dim3(a.NF * a.nchunk), dim3(512), lds_out, a);
 }
 
 template <int MODE>
@@ -1227,24 +1214,12 @@ static hipError_t launch_sla_m(SlaArgs a, hipStream_t st) {
         if (nkt == 2 && a.C == 128) return launch_sla8_t<MODE, 2, 1, 4, false>(a, st);
     }
     const size_t lds1 = 1024 + (size_t)128 * ROW_STRIDE + (size_t)64 * RSE;
-    hipError_t e;
-    {
-        const SlaWork sw = sla_work(a, M::ES, true, false, false);
-        LaunchScope ls(st, "sla_ctx_kernel", sw.flops, sw.bytes, "<%d> C%d N%d NF%d nchunk%d io16 %d", MODE, a.C, a.N, a.NF, a.nchunk, a.io_bf16);
-        hipLaunchKernelGGL(sla_ctx_kernel<MODE>, dim3(((a.NF * a.nchunk + 7) / 8) * 8 * a.heads), dim3(256), lds1, st, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    {
-        LaunchScope ls(st, "sla_combine_kernel", 0.0, (double)a.NF * a.nchunk * a.heads * SLA_PART * 4, "<%d> NF%d nchunk%d", MODE, a.NF, a.nchunk);
-        hipLaunchKernelGGL(sla_combine_kernel<MODE>, dim3(a.NF * a.heads), dim3(256), 0, st, a.part, a.ctxT, a.nchunk, a.heads);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    if (a.C <= 64) return launch_sla_out_t<MODE, 1>(a, st);
-    if (a.C <= 128) return launch_sla_out_t<MODE, 2>(a, st);
-    if (a.C <= 256) return launch_sla_out_t<MODE, 4>(a, st);
-    if (a.C <= 512) return launch_sla_out_t<MODE, 8>(a, st);
-    if (a.C <= 1024) return launch_sla_out_t<MODE, 16>(a, st);     // dim 128: the 1024-channel bottleneck level
-    return hipErrorInvalidValue;
+    const SlaWork sw = sla_work(a, M::ES, true, false, false);
+    hipError_t e = LaunchScope(st, "sla_ctx_kernel", sw.flops, sw.bytes, "<%d> C%d N%d NF%d nchunk%d io16 %d", MODE, a.C, a.N, a.NF, a.nchunk, a.io_bf16)
+                       .launch(sla_ctx_kernel<MODE>, dim3(((a.NF * a.nchunk + 7) / 8) * 8 * a.heads), dim3(256), lds1, a);
+    if (e != hipSuccess) return e;
+    if ((e = launch_sla_combine<MODE>(a, st)) != hipSuccess) return e;
+    return with_channel_tiles(a.C, [&](auto t) { return launch_sla_out_t<MODE, decltype(t)::value>(a, st); });     // (16: the 1024-channel bottleneck of dim 128)
 }
 
 hipError_t launch_sla(int mode, SlaArgs a, hipStream_t st) {

@@ -5,14 +5,25 @@
 #include <stddef.h>
 #include <stdio.h>
 #include <algorithm>
+#include <type_traits>
 #include "../../include/vdx.h"
 
 int vdx_set_error(int code, const char* msg, const char* file, int line);
 
 namespace vdx {
 
+// A kernel launched with more than the default 64 KB of dynamic LDS has to opt in first; at or below it nothing is set.
+template <typename K>
+inline hipError_t lds_opt_in(K kfn, size_t lds) {
+    if (lds <= 64 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 // Instrumentation hook (vdx.h: vdx_set_launch_hook).  A LaunchScope brackets ONE kernel launch: its constructor calls the hook with
-// phase 0, its destructor with phase 1.  Costs one load + branch when no hook is installed.
+// phase 0, its destructor with phase 1.  Costs one load + branch when no hook is installed (nothing is formatted then).
+// Every instrumented launch is one expression, LaunchScope(st, kernel, flops, bytes, label...).launch(kfn, grid, block, lds, args...):
+// hook, LDS opt-in, launch, hipGetLastError() in that order everywhere, so the hook has seen the route of a call before its first
+// runtime call can fail (tests/test_host_routes.py reads the routes on a machine without a device).
 extern vdx_launch_hook g_launch_hook;
 extern void* g_launch_hook_user;
 struct LaunchScope {
@@ -27,6 +38,12 @@ struct LaunchScope {
         g_launch_hook(g_launch_hook_user, 0, &info, st);
     }
     ~LaunchScope() { if (on && g_launch_hook) g_launch_hook(g_launch_hook_user, 1, &info, st); }
+    template <typename K, typename... A>
+    hipError_t launch(K kfn, dim3 grid, dim3 block, size_t lds, const A&... args) {
+        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
+        hipLaunchKernelGGL(kfn, grid, block, lds, st, args...);
+        return hipGetLastError();
+    }
     LaunchScope(const LaunchScope&) = delete;
     LaunchScope& operator=(const LaunchScope&) = delete;
 };
@@ -45,13 +62,6 @@ inline PersistentSplit persistent_split(long total, long slots) {
     const long n = std::min(total, slots);
     const long per = (total + n - 1) / n;
     return {per, (total + per - 1) / per};
-}
-
-// A kernel launched with more than the default 64 KB of dynamic LDS has to opt in first; at or below it nothing is set.
-template <typename K>
-inline hipError_t lds_opt_in(K kfn, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
 // Arguments of conv_igemm_kernel (POD, passed by value).  Caller fills the first block; launch_conv
@@ -381,20 +391,42 @@ size_t conv_packed_bytes(int mode, int taps, int Cin, int Cout);
 int conv_cin_pad(int mode, int Cin);
 hipError_t launch_pack_weights(int mode, const float* src, void* dst, int taps, int Cin, int Cout, hipStream_t st);
 hipError_t launch_conv(int mode, ConvArgs a, hipStream_t st);
-int conv3x3_ws_geo(const ConvArgs& a);
-bool conv4x4_ws_eligible(int mode, const ConvArgs& a);     // Downsample / Upsample of the wide levels on the weight-streaming machinery
-hipError_t launch_conv4x4_ws(const ConvArgs& a, hipStream_t st);       // 0 / 8 / 16: the GEO template argument launch_conv3x3_ws will use
+// ---- routing of launch_conv: geometry completion, conv_route(), launch.  A kernel form is ONE ConvRoute record.  `plan` is its only gate;
+// it makes no runtime call and hands what it computed on the way (tile geometry, channel tiles, tile count) to `launch`, which picks the
+// template instantiation, composes the hook's label from the values it instantiates with, and launches through LaunchScope::launch.
+struct ConvPlan {
+    int geo, nct, total;                                               // tile geometry (conv1x1_pw: weight rows), output-channel tiles, tiles of the launch
+    int BC, TN, inf, PH, PW, NP; size_t lds;                           // conv_igemm_kernel: channel tile, wave tile, input format, pixel patch, LDS bytes
+};
+struct ConvWork { double flops, bytes; char shape[128]; };             // what the hook is told about the call (conv_igemm.hip: conv_work)
+struct ConvRoute {
+    bool (*plan)(int mode, const ConvArgs& a, ConvPlan& p);            // `a` geometry-completed by launch_conv
+    hipError_t (*launch)(int mode, const ConvArgs& a, const ConvPlan& p, const ConvWork& w, hipStream_t st);
+};
+// the records whose kernels live outside conv_igemm.hip (conv_ws.hip, conv_rs.hip, conv_pw.hip); the list itself is conv_igemm.hip's conv_routes
+#define VDX_CONV_ROUTE_DECL(NAME_)                                                                                  \
+    bool NAME_##_plan(int mode, const ConvArgs& a, ConvPlan& p);                                                    \
+    hipError_t NAME_##_launch(int mode, const ConvArgs& a, const ConvPlan& p, const ConvWork& w, hipStream_t st)
+VDX_CONV_ROUTE_DECL(conv3x3_ws);
+VDX_CONV_ROUTE_DECL(conv4x4_ws);
+VDX_CONV_ROUTE_DECL(resample32);
+VDX_CONV_ROUTE_DECL(conv1x1_pw);
+#undef VDX_CONV_ROUTE_DECL
+// a run-time flag / size as a template argument: f(std::true_type{}) or f(std::false_type{}); Int<V>{} for the sizes
+template <int V> using Int = std::integral_constant<int, V>;
+template <typename F> inline auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+// f(Int<T>{}) with T = 1, 2, 4, 8, 16: the 64-channel tiles that cover C <= 1024 channels, the output tiling of the attention and SLA kernels
+template <typename F> inline hipError_t with_channel_tiles(int C, F&& f) {
+    if (C <= 64) return f(Int<1>{});
+    if (C <= 128) return f(Int<2>{});
+    if (C <= 256) return f(Int<4>{});
+    if (C <= 512) return f(Int<8>{});
+    if (C <= 1024) return f(Int<16>{});
+    return hipErrorInvalidValue;
+}
 // y <- SiLU(GroupNorm(y) * (scale + 1) + shift) in place on a bf16 tensor [batch][pix][C] (the Block prologue as its own pass; elementwise.hip)
 hipError_t launch_gn_silu_apply16(float* y_bf16, const double* stats, const float* gamma, const float* beta, const float* ss, int ss_stride, int groups,
                                   int C, int batch, long pix_per_sample, hipStream_t st);
-bool resample32_eligible(int mode, const ConvArgs& a);      // Downsample / Upsample of 32-channel bf16 tensors (dim-32 networks): everything in registers (conv_rs.hip)
-hipError_t launch_resample32(const ConvArgs& a, hipStream_t st);
-bool conv1x1_pw_eligible(int mode, const ConvArgs& a);     // 1x1 convs of the wide levels on bf16 tensors: weight rows resident in LDS, x straight into fragments (conv_pw.hip)
-hipError_t launch_conv1x1_pw(const ConvArgs& a, hipStream_t st);
-int conv1x1_pw_rows(const ConvArgs& a);                    // 64 / 128: the ROWS template argument launch_conv1x1_pw will use
-// persistent weight-streaming 3x3 kernel for Cout % 128 == 0 with bf16 tensors (conv_ws.hip); `a` geometry-completed by launch_conv
-bool conv3x3_ws_eligible(int mode, const ConvArgs& a);
-hipError_t launch_conv3x3_ws(const ConvArgs& a, hipStream_t st);
 hipError_t launch_pack_weights_t(int mode, const float* src, void* dst, int taps, int Cin, int Cout, hipStream_t st);
 
 }  // namespace vdx
