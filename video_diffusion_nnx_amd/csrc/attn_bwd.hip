@@ -502,14 +502,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd16x_kernel(AttnBwdXArgs P) {
     }
 }
 
+// 1..16 frames (vdx_api.cpp's attn_bwd_fused and model_bwd.hip's attn_bwd see to it)
 hipError_t launch_attn_bwd_fused(const AttnBwdXArgs& a, hipStream_t st) {
-    if (a.L < 1 || a.L > 16 || a.nseq < 1) return hipErrorInvalidValue;
     const size_t lds = (size_t)768 * AX_RSW + 768 * 4 + (size_t)8 * 4 * 16 * AB_RS;
-    auto kfn = attn_bwd16x_kernel;
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
     const long want = (a.nseq + 7) / 8;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)std::min<long>(want, device_cus())), dim3(512), lds, st, a);
-    return hipGetLastError();
+    return LaunchScope(st, "attn_bwd16x_kernel", 0.0, 0.0, "<x16 %d> L%d nseq%ld", a.x_bf16, a.L, a.nseq)
+        .launch(attn_bwd16x_kernel, dim3((unsigned)std::min<long>(want, device_cus())), dim3(512), lds, a);
 }
 
 constexpr int SLA_A = 2 * 1024 + 96;     // floats per (frame, head): ctx | dctx | kmax | ksum | T
@@ -901,44 +899,28 @@ static hipError_t launch_attn_dbias_sum(const AttnBwdArgs& a, int slots, int LS,
         .launch(attn_dbias_sum_kernel, dim3((total + 255) / 256), dim3(256), 0, a.part, slots, a.heads, a.L, LS, a.dbias);
 }
 
-// the focus forms (a.focus set): the same fixed grid; with a.bias they also emit dBias, without it bias / dbias / part are all null
-static hipError_t launch_attn_core_bwd_focus(const AttnBwdArgs& a, hipStream_t st) {
-    if (a.focus_n < 1 || a.L < 1 || a.L > 64 || a.nseq < 1) return hipErrorInvalidValue;
-    if (a.bias ? (!a.dbias || !a.part || a.part_cap < attn_bwd_bias_scratch_floats(a.heads, a.L)) : (a.dbias || a.part)) return hipErrorInvalidValue;
-    int slots, LS;
+// the bias and focus forms (a.bias and / or a.focus set; at most 64 tokens): a fixed grid whose workgroups store their share of dBias into
+// their slots of a.part, and with a bias the pass that adds the slots.  Without a bias, bias / dbias / part are all null.  The callers
+// (vdx_api.cpp's attn_core_bwd_fixed_grid, model_backward) see to the length, to bias / dbias / part coming together with
+// attn_bwd_bias_scratch_floats of scratch, to focus_n >= 1 and to bf16 tensors only where the bf16 form runs
+static hipError_t launch_attn_core_bwd_masked(const AttnBwdArgs& a, hipStream_t st) {
+    const bool mma16 = a.bf16_mma && a.L <= 16;
+    const int slots = (int)std::min<long>(mma16 ? (a.nseq + 3) / 4 : a.nseq, ATTN_BIAS_SLOTS), LS = mma16 ? 16 : a.L;
+    const dim3 grid(slots, a.heads);
+    const size_t lds = mma16 ? (size_t)4 * 4 * 16 * AB_RS : ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
     hipError_t e;
-    if (a.bf16_mma && a.L <= 16) {
-        slots = (int)std::min<long>((a.nseq + 3) / 4, ATTN_BIAS_SLOTS); LS = 16;
+    if (mma16 && a.focus)
         e = LaunchScope(st, "attn_core_bwd16_focus_kernel", 0.0, 0.0, "<io16 %d, bias %d> L%d nseq%ld heads%d", a.io_bf16, a.bias ? 1 : 0, a.L, a.nseq, a.heads)
-                .launch(a.io_bf16 ? attn_core_bwd16_focus_kernel<true> : attn_core_bwd16_focus_kernel<false>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, a);
-    } else {
-        if (a.io_bf16) return hipErrorInvalidValue;
-        slots = (int)std::min<long>(a.nseq, ATTN_BIAS_SLOTS); LS = a.L;
-        const size_t lds = ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
-        e = LaunchScope(st, "attn_core_bwd_focus_kernel", 0.0, 0.0, "<bias %d> L%d nseq%ld heads%d", a.bias ? 1 : 0, a.L, a.nseq, a.heads)
-                .launch(attn_core_bwd_focus_kernel, dim3(slots, a.heads), dim3(256), lds, a);
-    }
-    if (e != hipSuccess) return e;
-    if (!a.bias) return hipSuccess;
-    return launch_attn_dbias_sum(a, slots, LS, st);
-}
-
-static hipError_t launch_attn_core_bwd_bias(const AttnBwdArgs& a, hipStream_t st) {
-    if (!a.dbias || !a.part || a.L < 1 || a.L > 64 || a.nseq < 1 || a.part_cap < attn_bwd_bias_scratch_floats(a.heads, a.L)) return hipErrorInvalidValue;
-    int slots, LS;
-    hipError_t e;
-    if (a.bf16_mma && a.L <= 16) {
-        slots = (int)std::min<long>((a.nseq + 3) / 4, ATTN_BIAS_SLOTS); LS = 16;
+                .launch(a.io_bf16 ? attn_core_bwd16_focus_kernel<true> : attn_core_bwd16_focus_kernel<false>, grid, dim3(256), lds, a);
+    else if (mma16)
         e = LaunchScope(st, "attn_core_bwd16_bias_kernel", 0.0, 0.0, "<io16 %d> L%d nseq%ld heads%d", a.io_bf16, a.L, a.nseq, a.heads)
-                .launch(a.io_bf16 ? attn_core_bwd16_bias_kernel<true> : attn_core_bwd16_bias_kernel<false>, dim3(slots, a.heads), dim3(256), 4 * 4 * 16 * AB_RS, a);
-    } else {
-        if (a.io_bf16) return hipErrorInvalidValue;
-        slots = (int)std::min<long>(a.nseq, ATTN_BIAS_SLOTS); LS = a.L;
-        const size_t lds = ((size_t)4 * a.L * 33 + 2 * a.L * (a.L + 1)) * 4;
-        e = LaunchScope(st, "attn_core_bwd_bias_kernel", 0.0, 0.0, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads)
-                .launch(attn_core_bwd_bias_kernel, dim3(slots, a.heads), dim3(256), lds, a);
-    }
-    if (e != hipSuccess) return e;
+                .launch(a.io_bf16 ? attn_core_bwd16_bias_kernel<true> : attn_core_bwd16_bias_kernel<false>, grid, dim3(256), lds, a);
+    else if (a.focus)
+        e = LaunchScope(st, "attn_core_bwd_focus_kernel", 0.0, 0.0, "<bias %d> L%d nseq%ld heads%d", a.bias ? 1 : 0, a.L, a.nseq, a.heads)
+                .launch(attn_core_bwd_focus_kernel, grid, dim3(256), lds, a);
+    else
+        e = LaunchScope(st, "attn_core_bwd_bias_kernel", 0.0, 0.0, "L%d nseq%ld heads%d", a.L, a.nseq, a.heads).launch(attn_core_bwd_bias_kernel, grid, dim3(256), lds, a);
+    if (e != hipSuccess || !a.bias) return e;
     return launch_attn_dbias_sum(a, slots, LS, st);
 }
 
@@ -959,8 +941,7 @@ hipError_t launch_pos_bias_scatter(const float* dbias, const int* buckets, float
 }
 
 hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st) {
-    if (a.focus) return launch_attn_core_bwd_focus(a, st);
-    if (a.bias) return launch_attn_core_bwd_bias(a, st);
+    if (a.focus || a.bias) return launch_attn_core_bwd_masked(a, st);
     if (a.L > 64) return launch_attn_core_bwd_long(a, st);          // multiples of 64 up to 640 tokens (attn_long_bwd.hip); anything else is refused there
     if (a.bf16_mma && a.L <= 16) {
         const long blocks = (a.nseq + 3) / 4;
@@ -974,17 +955,16 @@ hipError_t launch_attn_core_bwd(const AttnBwdArgs& a, hipStream_t st) {
 
 size_t sla_bwd_scratch_floats(int NF, int heads) { return (size_t)NF * heads * SLA_A; }
 
+// pass A (one workgroup per (frame, head)), then pass B (256-pixel tiles) of the same form: exact fp32, or bf16 MFMA on fp32 / bf16 tensors
 hipError_t launch_sla_bwd(const SlaBwdArgs& a, hipStream_t st) {
-    if (a.bf16_mma && a.io_bf16) hipLaunchKernelGGL(sla_bwd_a16_kernel<true>, dim3(a.NF, a.heads), dim3(256), 0, st, a);
-    else if (a.bf16_mma) hipLaunchKernelGGL(sla_bwd_a16_kernel<false>, dim3(a.NF, a.heads), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(sla_bwd_a_kernel, dim3(a.NF, a.heads), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const int tiles = (a.N + 255) / 256;
-    if (a.bf16_mma && a.io_bf16) hipLaunchKernelGGL(sla_bwd_b16_kernel<true>, dim3(a.NF * tiles), dim3(256), 0, st, a);
-    else if (a.bf16_mma) hipLaunchKernelGGL(sla_bwd_b16_kernel<false>, dim3(a.NF * tiles), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(sla_bwd_b_kernel, dim3(a.NF * tiles), dim3(256), 0, st, a);
-    return hipGetLastError();
+    auto go = [&](const char* name_a, auto pass_a, const char* name_b, auto pass_b, const char* targs) {
+        const hipError_t e = LaunchScope(st, name_a, 0.0, 0.0, "%sN%d NF%d heads%d", targs, a.N, a.NF, a.heads).launch(pass_a, dim3(a.NF, a.heads), dim3(256), 0, a);
+        if (e != hipSuccess) return e;
+        return LaunchScope(st, name_b, 0.0, 0.0, "%sN%d NF%d heads%d", targs, a.N, a.NF, a.heads).launch(pass_b, dim3(a.NF * ((a.N + 255) / 256)), dim3(256), 0, a);
+    };
+    if (!a.bf16_mma) return go("sla_bwd_a_kernel", sla_bwd_a_kernel, "sla_bwd_b_kernel", sla_bwd_b_kernel, "");
+    return a.io_bf16 ? go("sla_bwd_a16_kernel", sla_bwd_a16_kernel<true>, "sla_bwd_b16_kernel", sla_bwd_b16_kernel<true>, "<io16 1> ")
+                     : go("sla_bwd_a16_kernel", sla_bwd_a16_kernel<false>, "sla_bwd_b16_kernel", sla_bwd_b16_kernel<false>, "<io16 0> ");
 }
 
 }  // namespace vdx

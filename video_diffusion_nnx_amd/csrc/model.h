@@ -60,9 +60,25 @@ struct Model {
 
 int model_build(Model* m);
 void model_build_pack_tables(Model* m);        // fills pack_jobs / pack_t_jobs (host); the handle uploads them
-size_t model_workspace_bytes(const Model* m, int B);
+// The forward workspace act | temb | ss | ss_lin | stats | sla (each rounded up to 256 bytes) and the backward workspace are each laid
+// out by ONE walk: with a base pointer it returns the views, with a null base the views are null and only `bytes`, the total, is meant.
+struct FwdWorkspace {
+    float* act; float* temb; float* ss; float* ss_lin;       // activation slots, time embedding, scale/shift rows and their pre-LayerNorm values
+    double* stats; size_t stats_bytes;                       // GroupNorm statistics slabs (zeroed by every forward)
+    char* sla_ws;                                            // scratch of the SLA / attention blocks
+    size_t bytes;
+};
+FwdWorkspace model_fwd_workspace(const Model* m, int B, void* base);
+inline size_t model_workspace_bytes(const Model* m, int B) { return model_fwd_workspace(m, B, nullptr).bytes; }
+struct LevelBufs { float* ga; float* gb; float* t1; float* t2; float* t3; float* t4; float* gskip; };
+struct BwdWorkspace {
+    std::vector<LevelBufs> lv; float* gr; float* Sbuf[2]; float* dss; float* dtemb; float* normscr; float* sla_a;
+    float* part_side; float* part_main;                      // slots of the deterministic accumulations (WG_PART_FLOATS each): one per stream, used in stream order
+    size_t bytes;
+};
+BwdWorkspace model_bwd_workspace(const Model* m, int B, void* base);
 hipError_t model_pack(const Model* m, const float* params, void* packed, hipStream_t st);
-size_t model_bwd_workspace_bytes(const Model* m, int B);
+inline size_t model_bwd_workspace_bytes(const Model* m, int B) { return model_bwd_workspace(m, B, nullptr).bytes; }
 hipError_t model_pack_t(const Model* m, const float* params, void* packed_t, hipStream_t st);
 // Reverse pass over stages [stage_lo, stage_hi] (descending; 2n+2 = head ... 0 = stem).  A full pass calls the stages in
 // order; `state` carries the running activation gradient between calls.

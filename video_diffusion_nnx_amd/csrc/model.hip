@@ -269,14 +269,17 @@ int model_build(Model* m) {
     return VDX_OK;
 }
 
-size_t model_workspace_bytes(const Model* m, int B) {
-    size_t b = 0;
-    b += ((size_t)m->act_floats_per_sample * B * 4 + 255) / 256 * 256;
-    b += ((size_t)m->temb_dim * B * 4 + 255) / 256 * 256;
-    b += 2 * (((size_t)m->ss_floats_per_sample * B * 4 + 255) / 256 * 256);       // scale/shift + pre-LayerNorm values
-    b += ((size_t)m->n_stats * B * GN_SLOTS * m->cfg.resnet_groups * 2 * 8 + 255) / 256 * 256;
-    b += (m->sla_ws_bytes_per_sample * B + 255) / 256 * 256;
-    return b;
+FwdWorkspace model_fwd_workspace(const Model* m, int B, void* base) {
+    FwdWorkspace w = {};
+    auto take = [&](size_t bytes) { char* p = base ? reinterpret_cast<char*>(base) + w.bytes : nullptr; w.bytes += (bytes + 255) / 256 * 256; return p; };
+    w.act = reinterpret_cast<float*>(take((size_t)m->act_floats_per_sample * B * 4));
+    w.temb = reinterpret_cast<float*>(take((size_t)m->temb_dim * B * 4));
+    w.ss = reinterpret_cast<float*>(take((size_t)m->ss_floats_per_sample * B * 4));
+    w.ss_lin = reinterpret_cast<float*>(take((size_t)m->ss_floats_per_sample * B * 4));
+    w.stats_bytes = (size_t)m->n_stats * B * GN_SLOTS * m->cfg.resnet_groups * 2 * 8;
+    w.stats = reinterpret_cast<double*>(take(w.stats_bytes));
+    w.sla_ws = take(m->sla_ws_bytes_per_sample * B);
+    return w;
 }
 
 // ---- packing ------------------------------------------------------------------------------------------------
@@ -541,15 +544,9 @@ int model_forward(const Model* m, const float* params, const void* packed, const
     Fwd f;
     f.m = m; f.p = params; f.pk = reinterpret_cast<const char*>(packed); f.B = B; f.st = st;
     f.a16 = (m->act16 && m->mode == MODE_BF16) ? 1 : 0;
-    char* w = reinterpret_cast<char*>(workspace);
-    f.act = reinterpret_cast<float*>(w); w += ((size_t)m->act_floats_per_sample * B * 4 + 255) / 256 * 256;
-    f.temb = reinterpret_cast<float*>(w); w += ((size_t)m->temb_dim * B * 4 + 255) / 256 * 256;
-    f.ss = reinterpret_cast<float*>(w); w += ((size_t)m->ss_floats_per_sample * B * 4 + 255) / 256 * 256;
-    f.ss_lin = reinterpret_cast<float*>(w); w += ((size_t)m->ss_floats_per_sample * B * 4 + 255) / 256 * 256;
-    f.stats = reinterpret_cast<double*>(w);
-    const size_t stats_bytes = (size_t)m->n_stats * B * GN_SLOTS * c.resnet_groups * 2 * 8;
-    w += (stats_bytes + 255) / 256 * 256;
-    f.sla_ws = w;
+    const FwdWorkspace w = model_fwd_workspace(m, B, workspace);
+    f.act = w.act; f.temb = w.temb; f.ss = w.ss; f.ss_lin = w.ss_lin; f.stats = w.stats; f.sla_ws = w.sla_ws;
+    const size_t stats_bytes = w.stats_bytes;
     hipError_t e;
 #define VDX_E(x) do { e = (x); if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__); } while (0)
     {

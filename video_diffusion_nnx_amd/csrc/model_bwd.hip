@@ -14,17 +14,12 @@ namespace vdx {
 
 namespace {
 
-struct LevelBufs { float* ga; float* gb; float* t1; float* t2; float* t3; float* t4; float* gskip; };
-constexpr int LVL_BUFS = 7;
-
-struct Bwd {
+struct Bwd : BwdWorkspace {
     const Model* m; const float* p; const char* pk; const char* pt; float* grads; int B; hipStream_t st;
     int a16 = 0;                                    // the forward stored its inter-kernel activations as bf16 (Model::act16 == 2): every slot read here is a bf16 tensor
     // forward workspace views
     float* act; float* temb; float* ss; float* ss_lin; double* stats;
-    // backward workspace views
-    std::vector<LevelBufs> lv; float* gr; float* S; float* Sbuf[2]; int s_cur = 0; float* dss; float* dtemb; float* normscr; float* sla_a;
-    float* part_side; float* part_main;             // slots of the deterministic accumulations (WG_PART_FLOATS each): one per stream, used in stream order
+    float* S; int s_cur = 0;                        // the attention scratch in use (Sbuf[s_cur])
     float* slot(int s) const { return act + (size_t)m->slots[s].offset_per_sample * B; }
     double* stat(int i) const { return stats + (size_t)i * B * GN_SLOTS * m->cfg.resnet_groups * 2; }
     long pix(int lvl) const { const long s = m->cfg.image_size >> lvl; return (long)m->cfg.num_frames * s * s; }
@@ -99,19 +94,28 @@ void dgrad(Bwd& b, const float* dy, int Cdy, const void* wpt, int rows_total, in
     b.ok(launch_conv(b.m->mode, a, b.writes(out)));
 }
 
-void wgrad(Bwd& b, const float* x0, int c0, const float* x1, int c1, const float* dy, int Cout, long w_off, long b_off, int lvl_in, int kind, int k, int stride,
-           const double* in_stats = nullptr, const float* gamma = nullptr, const float* beta = nullptr, const float* ss = nullptr, int ss_stride = 0,
-           int dy_bf16 = 0) {
+// what every weight gradient of the pass shares: x0 (x0_bf16: stored as bf16) -> dy (dy_bf16) of Cout columns at level lvl_in, dW at
+// w_off and db at b_off (< 0: none) of the flat gradient, the slots of the side stream (every weight gradient runs there, in order).
+// The callers add what is theirs (concat, prologue, split) and launch
+WgradArgs wgrad_args(const Bwd& b, const float* x0, int c0, int x0_bf16, const float* dy, int dy_bf16, int Cout, long w_off, long b_off, int lvl_in,
+                     int kind = 0, int k = 1, int stride = 1) {
     WgradArgs a;
     memset(&a, 0, sizeof(a));
-    a.dy_bf16 = dy_bf16;
-    a.x0_bf16 = b.a16;                                             // x0 / x1 are forward slots (block inputs); y1 (prologue form) is bf16 in bf16 mode either way
-    a.x0 = x0; a.x1 = x1; a.C0 = c0; a.C1 = c1; a.dy = dy; a.Cout = Cout; a.dW = b.grads + w_off; a.db = b_off >= 0 ? b.grads + b_off : nullptr;
+    a.x0 = x0; a.C0 = c0; a.x0_bf16 = x0_bf16; a.dy = dy; a.dy_bf16 = dy_bf16; a.Cout = Cout; a.dW = b.grads + w_off; a.db = b_off >= 0 ? b.grads + b_off : nullptr;
     a.NF = b.B * b.m->cfg.num_frames; a.F = b.m->cfg.num_frames; a.H = a.W = b.size(lvl_in);
     a.kind = kind; a.kh = a.kw = kind ? 4 : k; a.stride = kind ? 1 : stride;
     a.bf16_mma = (b.m->mode == MODE_BF16);
-    if (in_stats) { a.x0_bf16 = (b.m->mode == MODE_BF16); a.pro = 1; a.in_stats = in_stats; a.gamma = gamma; a.beta = beta; a.groups = b.m->cfg.resnet_groups; a.ss = ss; a.ss_stride = ss_stride; }
-    a.part = b.part_side; a.part_cap = WG_PART_FLOATS;             // (every weight gradient runs on the side stream, in order)
+    a.part = b.part_side; a.part_cap = WG_PART_FLOATS;
+    return a;
+}
+
+void wgrad(Bwd& b, const float* x0, int c0, const float* x1, int c1, const float* dy, int Cout, long w_off, long b_off, int lvl_in, int kind, int k, int stride,
+           const double* in_stats = nullptr, const float* gamma = nullptr, const float* beta = nullptr, const float* ss = nullptr, int ss_stride = 0,
+           int dy_bf16 = 0) {
+    // x0 / x1 are forward slots (block inputs); y1 (prologue form) is bf16 in bf16 mode either way
+    WgradArgs a = wgrad_args(b, x0, c0, in_stats ? (b.m->mode == MODE_BF16) : b.a16, dy, dy_bf16, Cout, w_off, b_off, lvl_in, kind, k, stride);
+    a.x1 = x1; a.C1 = c1;
+    if (in_stats) { a.pro = 1; a.in_stats = in_stats; a.gamma = gamma; a.beta = beta; a.groups = b.m->cfg.resnet_groups; a.ss = ss; a.ss_stride = ss_stride; }
     b.ok(launch_conv_wgrad(a, b.side()));
     b.side_done(dy);
 }
@@ -124,16 +128,21 @@ void res_bwd(Bwd& b, const ResP& r, const float* g, const float* x0, int c0, con
     const long npix = b.pix(lvl) * b.B;
     LevelBufs& L = b.lv[lvl];
     const float* rsrc = r.has_res ? b.slot(r.s_rc) : x0;
+    const int d16 = (m->mode == MODE_BF16) ? 1 : 0;      // bf16 mode: y1, y2 and dL/d(y2), dL/d(y1) are bf16 tensors (only convolutions read the gradients)
+    // dact -> dy through SiLU(GroupNorm(y)) with the statistics slab `st` and the norm's parameters at g_off / b_off: what the tail and the prologue share
+    auto norm_args = [&](const float* dact, int s_y, int st, long g_off, long b_off, float* dy) {
+        NormBwdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.dact = dact; a.y = b.slot(s_y); a.y_bf16 = d16; a.dy = dy; a.dy_bf16 = d16; a.stats = b.stat(st); a.gamma = b.p + g_off; a.beta = b.p + b_off; a.groups = G;
+        a.d_gamma = b.grads + g_off; a.d_beta = b.grads + b_off;
+        // R at a fixed offset of the scratch: zeroed once per backward, the finalize pass leaves it zero again
+        a.G = b.normscr; a.R = b.normscr + (size_t)b.B * 64; a.C = r.cout; a.batch = b.B; a.pix_per_sample = b.pix(lvl);
+        a.dgp = b.part_main;
+        return a;
+    };
     // 1. tail: out = SiLU(GN2(y2)) + LN(r)
-    NormBwdArgs t;
-    memset(&t, 0, sizeof(t));
-    const int d16 = (m->mode == MODE_BF16) ? 1 : 0;      // bf16 mode: dL/d(y2), dL/d(y1) are bf16 tensors (only convolutions read them)
-    t.dact = g; t.y = b.slot(r.s_y2); t.y_bf16 = (m->mode == MODE_BF16); t.dy = L.t1; t.dy_bf16 = d16; t.stats = b.stat(r.st2); t.gamma = b.p + r.b2_gs; t.beta = b.p + r.b2_gb; t.groups = G;
-    t.d_gamma = b.grads + r.b2_gs; t.d_beta = b.grads + r.b2_gb;
+    NormBwdArgs t = norm_args(g, r.s_y2, r.st2, r.b2_gs, r.b2_gb, L.t1);
     t.r = rsrc; t.r_bf16 = b.a16; t.ln_gamma = b.p + r.n2_s; t.dr = L.t2; t.d_ln_gamma = b.grads + r.n2_s; t.d_ln_beta = b.grads + r.n2_b;
-    // R at a fixed offset of the scratch: zeroed once per backward, the finalize pass leaves it zero again
-    t.G = b.normscr; t.R = b.normscr + (size_t)b.B * 64; t.C = r.cout; t.batch = b.B; t.pix_per_sample = b.pix(lvl);
-    t.dgp = b.part_main;
     b.ok(launch_norm_bwd(t, b.writes(L.t1, L.t2)));
     // 2. conv2: y2 = conv(SiLU(GN1(y1)*(1+s)+sh)); the weight gradients that only need the tail's outputs go to the side stream now
     const float* ssrow = r.has_mlp ? b.ss + (size_t)m->ss_layers[r.ss_index].out_off * b.B : nullptr;
@@ -141,13 +150,9 @@ void res_bwd(Bwd& b, const ResP& r, const float* g, const float* x0, int c0, con
     if (r.has_res) wgrad(b, x0, c0, x1, c1, L.t2, r.cout, r.rc_w, r.rc_b, lvl, 0, 1, 1);
     dgrad(b, L.t1, r.cout, b.pt + r.pt_b2, r.cout, 0, r.cout, lvl, 0, 3, 1, nullptr, L.t3, d16);       // dL/d(act1)
     // 3. prologue: act1 = SiLU((GN1(y1))*(1+s)+sh)
-    NormBwdArgs q;
-    memset(&q, 0, sizeof(q));
-    q.dact = L.t3; q.y = b.slot(r.s_y1); q.y_bf16 = (m->mode == MODE_BF16); q.dy = L.t4; q.dy_bf16 = d16; q.stats = b.stat(r.st1); q.gamma = b.p + r.b1_gs; q.beta = b.p + r.b1_gb; q.groups = G;
-    q.ss = ssrow; q.ss_stride = 2 * r.cout; q.d_gamma = b.grads + r.b1_gs; q.d_beta = b.grads + r.b1_gb;
+    NormBwdArgs q = norm_args(L.t3, r.s_y1, r.st1, r.b1_gs, r.b1_gb, L.t4);
+    q.ss = ssrow; q.ss_stride = 2 * r.cout;
     q.dss = r.has_mlp ? b.dss + (size_t)m->ss_layers[r.ss_index].out_off * b.B : nullptr;
-    q.G = b.normscr; q.R = b.normscr + (size_t)b.B * 64; q.C = r.cout; q.batch = b.B; q.pix_per_sample = b.pix(lvl);
-    q.dgp = b.part_main;
     b.ok(launch_norm_bwd(q, b.writes(L.t4)));                                                           // t4 = dL/d(y1) (not t1: conv2's weight gradient may still be reading it)
     // 4. conv1 + residual branch
     wgrad(b, x0, c0, x1, c1, L.t4, r.cout, r.b1_w, r.b1_b, lvl, 0, 3, 1, nullptr, nullptr, nullptr, nullptr, 0, d16);
@@ -177,30 +182,15 @@ void proj(Bwd& b, const float* x, int cin, const void* wp, const float* bias, in
 }
 
 void wgrad1x1(Bwd& b, const float* x, int cin, const float* dy, int cout, long w_off, long b_off, int lvl, int x_bf16 = 0) {
-    WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.x0_bf16 = x_bf16;
-    a.x0 = x; a.C0 = cin; a.dy = dy; a.Cout = cout; a.dW = b.grads + w_off; a.db = b_off >= 0 ? b.grads + b_off : nullptr;
-    a.NF = b.B * b.m->cfg.num_frames; a.F = b.m->cfg.num_frames; a.H = a.W = b.size(lvl);
-    a.kind = 0; a.kh = a.kw = 1; a.stride = 1;
-    a.bf16_mma = (b.m->mode == MODE_BF16);
-    a.part = b.part_side; a.part_cap = WG_PART_FLOATS;             // (every weight gradient runs on the side stream, in order)
-    b.ok(launch_conv_wgrad(a, b.side()));
+    b.ok(launch_conv_wgrad(wgrad_args(b, x, cin, x_bf16, dy, 0, cout, w_off, b_off, lvl), b.side()));
     b.side_done(b.S, dy);                                          // x = O lives in the attention scratch
 }
 
 // the q, k and v projection weight gradients of one block in ONE launch: dy = [rows][dq | dk | dv], x read once
 void wgrad1x1_qkv(Bwd& b, const float* x, int cin, const float* dqkv, int hd, const long (&w_off)[3], const long* b_off, int lvl, int dy_bf16 = 0, int x_bf16 = 0) {
-    WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dy_bf16 = dy_bf16; a.x0_bf16 = x_bf16;
-    a.x0 = x; a.C0 = cin; a.dy = dqkv; a.Cout = 3 * hd; a.split = hd;
-    a.dW = b.grads + w_off[0]; a.dW1 = b.grads + w_off[1]; a.dW2 = b.grads + w_off[2];
-    if (b_off) { a.db = b.grads + b_off[0]; a.db1 = b.grads + b_off[1]; a.db2 = b.grads + b_off[2]; }
-    a.NF = b.B * b.m->cfg.num_frames; a.F = b.m->cfg.num_frames; a.H = a.W = b.size(lvl);
-    a.kind = 0; a.kh = a.kw = 1; a.stride = 1;
-    a.bf16_mma = (b.m->mode == MODE_BF16);
-    a.part = b.part_side; a.part_cap = WG_PART_FLOATS;             // (every weight gradient runs on the side stream, in order)
+    WgradArgs a = wgrad_args(b, x, cin, x_bf16, dqkv, dy_bf16, 3 * hd, w_off[0], b_off ? b_off[0] : -1, lvl);
+    a.split = hd; a.dW1 = b.grads + w_off[1]; a.dW2 = b.grads + w_off[2];
+    if (b_off) { a.db1 = b.grads + b_off[1]; a.db2 = b.grads + b_off[2]; }
     b.ok(launch_conv_wgrad(a, b.side()));
     b.side_done(b.S);                                              // dq | dk | dv live in the attention scratch
 }
@@ -296,8 +286,6 @@ void bwd_state_free(BwdState* s) {
     for (int i = 0; i < BWD_EVENTS; ++i) if (s->ev[i]) { (void)hipEventDestroy(s->ev[i]); s->ev[i] = nullptr; }
 }
 
-static size_t al(size_t floats) { return (floats + 63) / 64 * 64; }
-
 // norm backward scratch: G [B][64] + the largest per-workgroup partials block of any level (norm_bwd.hip)
 static size_t norm_scratch_floats(const Model* m, int B) {
     size_t mx = 0;
@@ -309,22 +297,28 @@ static size_t norm_scratch_floats(const Model* m, int B) {
     return (size_t)B * 64 + mx;
 }
 
-size_t model_bwd_workspace_bytes(const Model* m, int B) {
-    const int nl = m->cfg.n_mults;
-    size_t fl = 0;
-    for (int l = 0; l < nl; ++l) {
-        const long s = m->cfg.image_size >> l;
-        fl += LVL_BUFS * al((size_t)B * m->cfg.num_frames * s * s * lvl_width(m, l));
+BwdWorkspace model_bwd_workspace(const Model* m, int B, void* base) {
+    const vdx_config& c = m->cfg;
+    BwdWorkspace w = {};
+    size_t fl = 0;                                                 // floats so far; every view starts on a multiple of 64
+    auto take = [&](size_t floats) { float* p = base ? reinterpret_cast<float*>(base) + fl : nullptr; fl += (floats + 63) / 64 * 64; return p; };
+    w.lv.resize(c.n_mults);
+    for (int l = 0; l < c.n_mults; ++l) {
+        const long s = c.image_size >> l;
+        LevelBufs& L = w.lv[l];
+        for (float** p : {&L.ga, &L.gb, &L.t1, &L.t2, &L.t3, &L.t4, &L.gskip}) *p = take((size_t)B * c.num_frames * s * s * lvl_width(m, l));
     }
-    const size_t pix0 = (size_t)B * m->cfg.num_frames * m->cfg.image_size * m->cfg.image_size;
-    fl += al(pix0 * m->init_dim);                                  // gr
-    fl += 2 * al(pix0 * (size_t)(m->cfg.attn_heads * 32) * 8);     // S (two, alternating per attention block)
-    fl += al((size_t)m->ss_floats_per_sample * B);                 // dss
-    fl += al((size_t)m->temb_dim * B);                             // dtemb
-    fl += al(norm_scratch_floats(m, B));                           // norm scratch
-    fl += al(sla_bwd_scratch_floats(B * m->cfg.num_frames, m->cfg.attn_heads));
-    fl += 2 * al(WG_PART_FLOATS);                                   // deterministic accumulation slots: side stream, main stream
-    return fl * 4;
+    const size_t pix0 = (size_t)B * c.num_frames * c.image_size * c.image_size;
+    w.gr = take(pix0 * m->init_dim);
+    for (float*& S : w.Sbuf) S = take(pix0 * (size_t)(c.attn_heads * 32) * 8);     // two, alternating per attention block
+    w.dss = take((size_t)m->ss_floats_per_sample * B);
+    w.dtemb = take((size_t)m->temb_dim * B);
+    w.normscr = take(norm_scratch_floats(m, B));
+    w.sla_a = take(sla_bwd_scratch_floats(B * c.num_frames, c.attn_heads));
+    w.part_side = take(WG_PART_FLOATS);
+    w.part_main = take(WG_PART_FLOATS);
+    w.bytes = fl * 4;
+    return w;
 }
 
 hipError_t model_pack_t(const Model* m, const float* p, void* packed_t, hipStream_t st) {
@@ -360,33 +354,10 @@ int model_backward(const Model* m, BwdState* state, const float* params, const v
     b.m = m; b.p = params; b.pk = reinterpret_cast<const char*>(packed); b.pt = reinterpret_cast<const char*>(packed_t);
     b.grads = grads; b.B = B; b.st = st; b.state = state;
     b.a16 = (m->act16 == 2 && m->mode == MODE_BF16) ? 1 : 0;
-    {   // forward workspace carve (must match model_forward)
-        char* w = reinterpret_cast<char*>(fwd_workspace);
-        b.act = reinterpret_cast<float*>(w); w += ((size_t)m->act_floats_per_sample * B * 4 + 255) / 256 * 256;
-        b.temb = reinterpret_cast<float*>(w); w += ((size_t)m->temb_dim * B * 4 + 255) / 256 * 256;
-        b.ss = reinterpret_cast<float*>(w); w += ((size_t)m->ss_floats_per_sample * B * 4 + 255) / 256 * 256;
-        b.ss_lin = reinterpret_cast<float*>(w); w += ((size_t)m->ss_floats_per_sample * B * 4 + 255) / 256 * 256;
-        b.stats = reinterpret_cast<double*>(w);
-    }
-    {   // backward workspace carve
-        float* w = reinterpret_cast<float*>(bwd_workspace);
-        b.lv.resize(nl);
-        for (int l = 0; l < nl; ++l) {
-            const long s = c.image_size >> l;
-            const size_t n = al((size_t)B * c.num_frames * s * s * lvl_width(m, l));
-            b.lv[l].ga = w; w += n; b.lv[l].gb = w; w += n; b.lv[l].t1 = w; w += n; b.lv[l].t2 = w; w += n; b.lv[l].t3 = w; w += n; b.lv[l].t4 = w; w += n; b.lv[l].gskip = w; w += n;
-        }
-        const size_t pix0 = (size_t)B * c.num_frames * c.image_size * c.image_size;
-        b.gr = w; w += al(pix0 * m->init_dim);
-        for (int i = 0; i < 2; ++i) { b.Sbuf[i] = w; w += al(pix0 * (size_t)(c.attn_heads * 32) * 8); }
-        b.S = b.Sbuf[0];
-        b.dss = w; w += al((size_t)m->ss_floats_per_sample * B);
-        b.dtemb = w; w += al((size_t)m->temb_dim * B);
-        b.normscr = w; w += al(norm_scratch_floats(m, B));
-        b.sla_a = w; w += al(sla_bwd_scratch_floats(B * c.num_frames, c.attn_heads));
-        b.part_side = w; w += al(WG_PART_FLOATS);
-        b.part_main = w;
-    }
+    static_cast<BwdWorkspace&>(b) = model_bwd_workspace(m, B, bwd_workspace);
+    b.S = b.Sbuf[0];
+    const FwdWorkspace fw = model_fwd_workspace(m, B, fwd_workspace);
+    b.act = fw.act; b.temb = fw.temb; b.ss = fw.ss; b.ss_lin = fw.ss_lin; b.stats = fw.stats;
     hipError_t e;
     if (!state->side) {
         if (hipStreamCreateWithFlags(&state->side, hipStreamNonBlocking) != hipSuccess) return vdx_set_error(VDX_ERR_HIP, "backward: side stream", __FILE__, __LINE__);

@@ -327,52 +327,42 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(NormBwdArgs P) {
     }
 }
 
-// workgroups per sample of the reduce pass: every workgroup walks >= 2 passes of U pixels per lane group, at most 256 per sample
-// (measured at the N shape, B = 4: 128 per sample 55 us per launch, 256: 49-50, 512: 50)
-static int norm_bwd_reduce_wgs(int C, long pix_per_sample) {
+// thread layout of the reduce and apply passes: lanes per pixel, float4 values per lane (instantiated for 1, 2, 4), pixels per 256-thread
+// pass, and the workgroups per sample of the reduce pass: every workgroup walks >= 2 passes of U pixels per lane group, at most 256 per
+// sample (measured at the N shape, B = 4: 128 per sample 55 us per launch, 256: 49-50, 512: 50)
+struct NormBwdPlan { int lpp, vpl, ppb, nwg; };
+static NormBwdPlan norm_bwd_plan(int C, long pix_per_sample) {
     const int quads = C / 4;
     int lpp = 1;
     while (lpp < quads && lpp < 64) lpp <<= 1;
     const int vpl = (quads + lpp - 1) / lpp, ppb = 256 / lpp, U = vpl == 1 ? VDX_NB_U : VDX_NB_U / 2;
-    return (int)std::max<long>(1, std::min<long>(256, (pix_per_sample + (long)ppb * U * 2 - 1) / ((long)ppb * U * 2)));
+    return {lpp, vpl, ppb, (int)std::max<long>(1, std::min<long>(256, (pix_per_sample + (long)ppb * U * 2 - 1) / ((long)ppb * U * 2)))};
 }
 
 // floats of NormBwdArgs::R (+ G behind it): [B][workgroups][4][C] partials + [B][32 groups][2]
 size_t norm_bwd_scratch_floats(int C, int batch, long pix_per_sample) {
-    return (size_t)batch * norm_bwd_reduce_wgs(C, pix_per_sample) * 4 * C + (size_t)batch * 64;
+    return (size_t)batch * norm_bwd_plan(C, pix_per_sample).nwg * 4 * C + (size_t)batch * 64;
 }
 
+// C <= 1024 in whole groups (the entry points and model_build see to both): at most 4 values per lane, and the finalize tile below divides C
 hipError_t launch_norm_bwd(NormBwdArgs a, hipStream_t st) {
-    const int quads = a.C / 4;
-    int lpp = 1;
-    while (lpp < quads && lpp < 64) lpp <<= 1;
-    a.lpp = lpp;
-    const int vpl = (quads + lpp - 1) / lpp;
-    const int ppb = 256 / lpp;
-    const int gx = norm_bwd_reduce_wgs(a.C, a.pix_per_sample);
-    a.nwg = gx;
-    dim3 grid(gx, a.batch);
-    switch (vpl) {
-        case 1: hipLaunchKernelGGL(norm_bwd_reduce_kernel<1>, grid, dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(norm_bwd_reduce_kernel<2>, grid, dim3(256), 0, st, a); break;
-        case 3: case 4: hipLaunchKernelGGL(norm_bwd_reduce_kernel<4>, grid, dim3(256), 0, st, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    {   // channel tile of the finalize pass: whole groups, >= 8 channels (<= 32 groups of it in LDS), at most 256
-        const int cpg = a.C / a.groups;
-        int ct = cpg;
-        while (ct < 8 && ct * 2 <= a.C && a.C % (ct * 2) == 0) ct *= 2;
-        if (a.C % ct || ct / cpg > 32) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(norm_bwd_finalize_kernel, dim3(a.C / ct, a.batch), dim3(256), 0, st, a, ct);
-    }
-    const int gx2 = (int)std::max<long>(1, std::min<long>((a.pix_per_sample + ppb - 1) / ppb, 2048));
-    dim3 grid2(gx2, a.batch);
-    switch (vpl) {
-        case 1: hipLaunchKernelGGL(norm_bwd_apply_kernel<1>, grid2, dim3(256), 0, st, a); break;
-        case 2: hipLaunchKernelGGL(norm_bwd_apply_kernel<2>, grid2, dim3(256), 0, st, a); break;
-        default: hipLaunchKernelGGL(norm_bwd_apply_kernel<4>, grid2, dim3(256), 0, st, a); break;
-    }
-    return hipGetLastError();
+    const NormBwdPlan p = norm_bwd_plan(a.C, a.pix_per_sample);
+    a.lpp = p.lpp; a.nwg = p.nwg;
+    // channel tile of the finalize pass: whole groups, >= 8 channels where C allows
+    int ct = a.C / a.groups;
+    while (ct < 8 && ct * 2 <= a.C && a.C % (ct * 2) == 0) ct *= 2;
+    const int gx2 = (int)std::max<long>(1, std::min<long>((a.pix_per_sample + p.ppb - 1) / p.ppb, 2048));
+    char shape[96];
+    snprintf(shape, sizeof(shape), "C%d batch%d pix%ld nwg%d ln %d ss %d dss %d dgp %d", a.C, a.batch, a.pix_per_sample, a.nwg, a.r ? 1 : 0, a.ss ? 1 : 0, a.dss ? 1 : 0, a.dgp ? 1 : 0);
+    auto go = [&](auto vpl_c) {
+        constexpr int VPL = decltype(vpl_c)::value;
+        hipError_t e = LaunchScope(st, "norm_bwd_reduce_kernel", 0.0, 0.0, "<%d> %s", VPL, shape).launch(norm_bwd_reduce_kernel<VPL>, dim3(p.nwg, a.batch), dim3(256), 0, a);
+        if (e != hipSuccess) return e;
+        e = LaunchScope(st, "norm_bwd_finalize_kernel", 0.0, 0.0, "ct%d %s", ct, shape).launch(norm_bwd_finalize_kernel, dim3(a.C / ct, a.batch), dim3(256), 0, a, ct);
+        if (e != hipSuccess) return e;
+        return LaunchScope(st, "norm_bwd_apply_kernel", 0.0, 0.0, "<%d> %s", VPL, shape).launch(norm_bwd_apply_kernel<VPL>, dim3(gx2, a.batch), dim3(256), 0, a);
+    };
+    return p.vpl == 1 ? go(Int<1>{}) : p.vpl == 2 ? go(Int<2>{}) : go(Int<4>{});
 }
 
 }  // namespace vdx

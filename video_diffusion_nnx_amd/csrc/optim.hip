@@ -165,16 +165,16 @@ __global__ __launch_bounds__(256) void grad_sqnorm_final_kernel(const double* __
 hipError_t launch_loss_grad(const float* eps_hat, const float* noise, float* d_eps, int B, int Cc, long fhw, int l2, hipStream_t st) {
     const long n = (long)B * Cc * fhw;
     const int blocks = (int)std::max<long>(1, std::min<long>((n + 255) / 256, 2048));
-    hipLaunchKernelGGL(loss_grad_kernel, dim3(blocks), dim3(256), 0, st, eps_hat, noise, d_eps, B, Cc, fhw, l2, 1.0f / (float)n);
-    return hipGetLastError();
+    return LaunchScope(st, "loss_grad_kernel", 0.0, 0.0, "B%d C%d fhw%ld l2 %d", B, Cc, fhw, l2)
+        .launch(loss_grad_kernel, dim3(blocks), dim3(256), 0, eps_hat, noise, d_eps, B, Cc, fhw, l2, 1.0f / (float)n);
 }
 
 hipError_t launch_loss_grad_masked(const float* eps_hat, const float* noise, const unsigned char* mask, const double* count_dev, float* d_eps,
                                    int B, int Cc, long fhw, int l2, hipStream_t st) {
     const long quads = (long)B * Cc * fhw / 4;
     const int blocks = (int)std::max<long>(1, std::min<long>((quads + 255) / 256, 2048));
-    hipLaunchKernelGGL(loss_grad_masked_kernel, dim3(blocks), dim3(256), 0, st, eps_hat, noise, mask, count_dev, d_eps, B, Cc, fhw, l2);
-    return hipGetLastError();
+    return LaunchScope(st, "loss_grad_masked_kernel", 0.0, 0.0, "B%d C%d fhw%ld l2 %d", B, Cc, fhw, l2)
+        .launch(loss_grad_masked_kernel, dim3(blocks), dim3(256), 0, eps_hat, noise, mask, count_dev, d_eps, B, Cc, fhw, l2);
 }
 
 hipError_t launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
@@ -182,8 +182,8 @@ hipError_t launch_adam_ema(float* p, const float* g, float* m, float* v, float* 
     const double t = (double)step_count + 1.0;                    // optax: bias correction with count + 1
     const float bc1 = (float)(1.0 - pow((double)b1, t)), bc2 = (float)(1.0 - pow((double)b2, t));
     const int blocks = (int)std::max<long>(1, std::min<long>((n / 4 + 255) / 256, 4096));
-    hipLaunchKernelGGL(adam_ema_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, ema, n, lr, b1, b2, eps, bc1, bc2, grad_scale, do_ema, decay);
-    return hipGetLastError();
+    return LaunchScope(st, "adam_ema_kernel", 0.0, 0.0, "n%ld ema %d", n, do_ema ? 1 : 0)
+        .launch(adam_ema_kernel, dim3(blocks), dim3(256), 0, p, g, m, v, ema, n, lr, b1, b2, eps, bc1, bc2, grad_scale, do_ema, decay);
 }
 
 hipError_t launch_adam_ema_clip(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
@@ -192,25 +192,27 @@ hipError_t launch_adam_ema_clip(float* p, const float* g, float* m, float* v, fl
     const double t = (double)step_count + 1.0;
     const float bc1 = (float)(1.0 - pow((double)b1, t)), bc2 = (float)(1.0 - pow((double)b2, t));
     const int blocks = (int)std::max<long>(1, std::min<long>((n / 4 + 255) / 256, 4096));
-    hipLaunchKernelGGL(adam_ema_clip_kernel, dim3(blocks), dim3(256), 0, st, p, g, m, v, ema, n, lr, b1, b2, eps, bc1, bc2, grad_scale, do_ema,
-                       decay, sqnorm, max_grad_norm, norm_out);
-    return hipGetLastError();
+    return LaunchScope(st, "adam_ema_clip_kernel", 0.0, 0.0, "n%ld ema %d", n, do_ema ? 1 : 0)
+        .launch(adam_ema_clip_kernel, dim3(blocks), dim3(256), 0, p, g, m, v, ema, n, lr, b1, b2, eps, bc1, bc2, grad_scale, do_ema, decay, sqnorm,
+                max_grad_norm, norm_out);
 }
 
 hipError_t launch_grad_accumulate(float* acc, const float* g, long n, hipStream_t st) {
     const long head = std::min<long>(n, (long)((4 - (((uintptr_t)acc >> 2) & 3)) & 3));
     const long quads = (n - head) / 4;
     const int blocks = (int)std::max<long>(1, std::min<long>((quads + 255) / 256, 2048));
-    hipLaunchKernelGGL(grad_accumulate_kernel, dim3(blocks), dim3(256), 0, st, acc, g, n, head, quads);
-    return hipGetLastError();
+    return LaunchScope(st, "grad_accumulate_kernel", 0.0, 0.0, "n%ld head%ld", n, head)
+        .launch(grad_accumulate_kernel, dim3(blocks), dim3(256), 0, acc, g, n, head, quads);
 }
 
 size_t grad_sqnorm_scratch_doubles() { return kSqnormBlocks; }
 
 hipError_t launch_grad_sqnorm(const float* g, long n, double* scratch, double* out, hipStream_t st) {
-    hipLaunchKernelGGL(grad_sqnorm_partial_kernel, dim3(kSqnormBlocks), dim3(256), 0, st, g, n, scratch);
-    hipLaunchKernelGGL(grad_sqnorm_final_kernel, dim3(1), dim3(256), 0, st, scratch, out);
-    return hipGetLastError();
+    const hipError_t e = LaunchScope(st, "grad_sqnorm_partial_kernel", 0.0, 0.0, "n%ld blocks%d", n, kSqnormBlocks)
+                             .launch(grad_sqnorm_partial_kernel, dim3(kSqnormBlocks), dim3(256), 0, g, n, scratch);
+    if (e != hipSuccess) return e;
+    return LaunchScope(st, "grad_sqnorm_final_kernel", 0.0, 0.0, "blocks%d", kSqnormBlocks)
+        .launch(grad_sqnorm_final_kernel, dim3(1), dim3(256), 0, scratch, out);
 }
 
 }  // namespace vdx

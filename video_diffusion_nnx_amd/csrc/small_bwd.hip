@@ -325,16 +325,15 @@ __global__ __launch_bounds__(256) void time_mlp_bwd_kernel(TimeMlpArgs P, const 
 hipError_t launch_final_conv_bwd(const float* x, const float* dout, const float* w, float* dx, float* dW, float* db, long npix, int D, int Cout, int x_bf16, hipStream_t st, float* part, size_t part_cap) {
     if (D > 256 || Cout > 4) return hipErrorInvalidValue;
     const int blocks = (int)std::max<long>(1, std::min<long>((npix * (D / 4) + 255) / 256, 4096));
-    hipLaunchKernelGGL(final_conv_dx_kernel, dim3(blocks), dim3(256), 0, st, dout, w, dx, npix, D, Cout);
+    hipError_t e = LaunchScope(st, "final_conv_dx_kernel", 0.0, 0.0, "D%d Cout%d npix%ld", D, Cout, npix).launch(final_conv_dx_kernel, dim3(blocks), dim3(256), 0, dout, w, dx, npix, D, Cout);
+    if (e != hipSuccess) return e;
     const int PL = 256 / D;
     const int b2 = (int)std::max<long>(1, std::min<long>((npix + PL - 1) / PL, 512));
-    if (part && (size_t)b2 * (D + 1) * Cout > part_cap) part = nullptr;
-    hipLaunchKernelGGL(final_conv_dw_kernel, dim3(b2), dim3(256), 0, st, x, dout, dW, db, npix, D, Cout, x_bf16, part);
-    hipError_t e = hipGetLastError();
+    part = slots_if_fit(part, (size_t)b2 * (D + 1) * Cout, part_cap);
+    e = LaunchScope(st, "final_conv_dw_kernel", 0.0, 0.0, "<x16 %d> D%d Cout%d npix%ld slots%d det %d", x_bf16, D, Cout, npix, b2, part ? 1 : 0)
+                       .launch(final_conv_dw_kernel, dim3(b2), dim3(256), 0, x, dout, dW, db, npix, D, Cout, x_bf16, part);
     if (e != hipSuccess || !part) return e;
-    e = launch_slot_sum(part, b2, (size_t)D * Cout, (long)D * Cout, Cout, 0, dW, nullptr, nullptr, st);
-    if (e != hipSuccess) return e;
-    return launch_slot_sum(part + (size_t)b2 * D * Cout, b2, (size_t)Cout, Cout, Cout, 0, db, nullptr, nullptr, st);
+    return launch_slot_sum_dw_db(part, b2, (long)D * Cout, Cout, 0, {dW, nullptr, nullptr}, {db, nullptr, nullptr}, st);
 }
 
 hipError_t launch_init_conv_wgrad(const float* x, const float* dy, float* dW, float* db, int B, int Cin, int F, int H, int W, int Cout, int K, hipStream_t st, float* part, size_t part_cap) {
@@ -342,27 +341,24 @@ hipError_t launch_init_conv_wgrad(const float* x, const float* dy, float* dW, fl
     dim3 grid(((W + 15) / 16) * ((H + 15) / 16), B * F, (Cout + 15) / 16);
     const size_t lds = ((size_t)Cin * TW * TW + 256 * 17) * 4;
     const size_t E = (size_t)K * K * Cin * Cout, nslots = (size_t)grid.x * grid.y;
-    if (part && nslots * (E + Cout) > part_cap) part = nullptr;
-    hipLaunchKernelGGL(init_conv_wgrad_kernel, grid, dim3(256), lds, st, x, dy, dW, db, B, Cin, F, H, W, Cout, K, part);
-    hipError_t e = hipGetLastError();
+    part = slots_if_fit(part, nslots * (E + Cout), part_cap);
+    hipError_t e = LaunchScope(st, "init_conv_wgrad_kernel", 0.0, 0.0, "conv%dx%d %d->%d %dx%dx%d slots%zu det %d", K, K, Cin, Cout, B * F, H, W, nslots, part ? 1 : 0)
+                       .launch(init_conv_wgrad_kernel, grid, dim3(256), lds, x, dy, dW, db, B, Cin, F, H, W, Cout, K, part);
     if (e != hipSuccess || !part) return e;
-    e = launch_slot_sum(part, (int)nslots, E, (long)E, Cout, 0, dW, nullptr, nullptr, st);
-    if (e != hipSuccess) return e;
-    return launch_slot_sum(part + nslots * E, (int)nslots, (size_t)Cout, Cout, Cout, 0, db, nullptr, nullptr, st);
+    return launch_slot_sum_dw_db(part, (int)nslots, (long)E, Cout, 0, {dW, nullptr, nullptr}, {db, nullptr, nullptr}, st);
 }
 
 hipError_t launch_resblock_ss_bwd(const float* params, float* grads, const float* temb, const SsLayer* layers, int nlayers, const float* lin_base,
                                   float* dss_base, float* dtemb, int temb_dim, int B, hipStream_t st, float* part, size_t part_cap) {
-    hipLaunchKernelGGL(resblock_ss_bwd_kernel, dim3(nlayers), dim3(256), 0, st, params, grads, temb, layers, lin_base, dss_base, dtemb, temb_dim, B);
-    hipError_t e = hipGetLastError();
+    hipError_t e = LaunchScope(st, "resblock_ss_bwd_kernel", 0.0, 0.0, "layers%d temb%d B%d", nlayers, temb_dim, B)
+                       .launch(resblock_ss_bwd_kernel, dim3(nlayers), dim3(256), 0, params, grads, temb, layers, lin_base, dss_base, dtemb, temb_dim, B);
     if (e != hipSuccess) return e;
     // rows of the Linear per workgroup: the per-stage launches of the staged backward cover 2 layers each (data-parallel bucket
     // readiness, model_bwd.hip ss_bwd), so they take one row per workgroup to still fill the chip
     const int kb = nlayers >= 8 ? 8 : 1;
-    if (part && (size_t)nlayers * B * temb_dim > part_cap) part = nullptr;
-    hipLaunchKernelGGL(resblock_ss_bwd_w_kernel, dim3(nlayers, (temb_dim + kb - 1) / kb), dim3(256), 0, st, params, grads, temb, layers,
-                       dss_base, dtemb, temb_dim, B, kb, part);
-    e = hipGetLastError();
+    part = slots_if_fit(part, (size_t)nlayers * B * temb_dim, part_cap);
+    e = LaunchScope(st, "resblock_ss_bwd_w_kernel", 0.0, 0.0, "layers%d temb%d B%d kb%d det %d", nlayers, temb_dim, B, kb, part ? 1 : 0)
+            .launch(resblock_ss_bwd_w_kernel, dim3(nlayers, (temb_dim + kb - 1) / kb), dim3(256), 0, params, grads, temb, layers, dss_base, dtemb, temb_dim, B, kb, part);
     if (e != hipSuccess || !part) return e;
     return launch_slot_sum(part, nlayers, (size_t)B * temb_dim, (long)B * temb_dim, temb_dim, 0, dtemb, nullptr, nullptr, st);
 }
@@ -370,10 +366,8 @@ hipError_t launch_resblock_ss_bwd(const float* params, float* grads, const float
 hipError_t launch_time_mlp_bwd(const TimeMlpArgs& a, const float* dtemb, float* dw1, float* db1, float* dw2, float* db2, float* dnull, int B, hipStream_t st) {
     const size_t lds = (size_t)B * (a.dim + 2 * a.time_dim + 64) * 4;
     if (lds > 150 * 1024) return hipErrorInvalidValue;             // B <= ~60 at the N shape
-    auto kfn = time_mlp_bwd_kernel;
-    if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(kfn, dim3((a.time_dim + 63) / 64), dim3(256), lds, st, a, dtemb, dw1, db1, dw2, db2, dnull, B);
-    return hipGetLastError();
+    return LaunchScope(st, "time_mlp_bwd_kernel", 0.0, 0.0, "dim%d time_dim%d cond%d B%d", a.dim, a.time_dim, a.cond_dim, B)
+        .launch(time_mlp_bwd_kernel, dim3((a.time_dim + 63) / 64), dim3(256), lds, a, dtemb, dw1, db1, dw2, db2, dnull, B);
 }
 
 }  // namespace vdx

@@ -288,6 +288,12 @@ hipError_t launch_colsum(const float* x, float* out, long rows, int C, hipStream
 // dst[e] (+= the split targets: column block co / split of a [rows][Cout] layout goes to d0 / d1 / d2) += sum over slots k < nslots, in
 // order, of part[k * slot_stride + e], e < E: the second half of every deterministic accumulation of the backward
 hipError_t launch_slot_sum(const float* part, int nslots, size_t slot_stride, long E, int Cout, int split, float* d0, float* d1, float* d2, hipStream_t st);
+// what follows a launch that stored `nslots` slots of E weight-gradient floats and, behind them, `nslots` rows of Cout bias sums: dW
+// (+ its split targets) += the slots, then db += the rows (db[0] null: no bias gradient)
+hipError_t launch_slot_sum_dw_db(const float* part, int nslots, long E, int Cout, int split, float* const (&dW)[3], float* const (&db)[3], hipStream_t st);
+// the slot scratch of a deterministic accumulation if the launch's slots fit it, else null: the kernel then adds with float atomics and
+// two runs no longer give the same bits (the label of every such launch says which: `det 1|0`)
+inline float* slots_if_fit(float* part, size_t need, size_t cap) { return part && need <= cap ? part : nullptr; }
 constexpr size_t WG_PART_FLOATS = (size_t)12 << 20;        // scratch per stream for the slots (48 MB; a launch that needs more falls back to atomics)
 hipError_t launch_add_inplace(float* y, const float* x, long n, hipStream_t st);
 

@@ -697,34 +697,34 @@ __global__ __launch_bounds__(256) void slot_sum16_kernel(const float* __restrict
 }
 hipError_t launch_slot_sum(const float* part, int nslots, size_t slot_stride, long E, int Cout, int split, float* d0, float* d1, float* d2, hipStream_t st) {
     if (nslots >= 32 && (E + 15) / 16 <= 65535 * 16) {
-        hipLaunchKernelGGL(slot_sum16_kernel, dim3((unsigned)((E + 15) / 16)), dim3(256), 0, st, part, nslots, slot_stride, E, Cout, split, d0, d1, d2);
-        return hipGetLastError();
+        return LaunchScope(st, "slot_sum16_kernel", 0.0, 0.0, "slots%d E%ld Cout%d split%d", nslots, E, Cout, split)
+            .launch(slot_sum16_kernel, dim3((unsigned)((E + 15) / 16)), dim3(256), 0, part, nslots, slot_stride, E, Cout, split, d0, d1, d2);
     }
     const int blocks = (int)std::max<long>(1, std::min<long>((E + 255) / 256, 2048));
-    hipLaunchKernelGGL(slot_sum_kernel, dim3(blocks), dim3(256), 0, st, part, nslots, slot_stride, E, Cout, split, d0, d1, d2);
-    return hipGetLastError();
+    return LaunchScope(st, "slot_sum_kernel", 0.0, 0.0, "slots%d E%ld Cout%d split%d", nslots, E, Cout, split)
+        .launch(slot_sum_kernel, dim3(blocks), dim3(256), 0, part, nslots, slot_stride, E, Cout, split, d0, d1, d2);
 }
-static hipError_t launch_wgrad_finalize(const float* part, int nslots, long E, int Cout, int split, float* d0, float* d1, float* d2, hipStream_t st) {
-    return launch_slot_sum(part, nslots, (size_t)E, E, Cout, split, d0, d1, d2, st);
+hipError_t launch_slot_sum_dw_db(const float* part, int nslots, long E, int Cout, int split, float* const (&dW)[3], float* const (&db)[3], hipStream_t st) {
+    hipError_t e = launch_slot_sum(part, nslots, (size_t)E, E, Cout, split, dW[0], dW[1], dW[2], st);
+    if (e != hipSuccess || !db[0]) return e;
+    return launch_slot_sum(part + (size_t)nslots * E, nslots, (size_t)Cout, Cout, Cout, split, db[0], db[1], db[2], st);
 }
-// slots a launch needs: `chunks` dW tiles of E floats + `chunks` bias rows
+// slots a launch needs: `chunks` dW tiles of E floats + `chunks` bias rows behind them; false: the kernels add with float atomics
 static bool wgrad_det_setup(WgradArgs& a, long chunks, long E) {
-    a.part_E = E; a.part_b = nullptr;
-    if (!a.part) return false;
-    const size_t need = (size_t)chunks * ((size_t)E + (size_t)a.Cout);
-    if (need > a.part_cap) { a.part = nullptr; return false; }
-    a.part_b = a.part + (size_t)chunks * E;
-    return true;
+    a.part_E = E;
+    a.part = slots_if_fit(a.part, (size_t)chunks * ((size_t)E + (size_t)a.Cout), a.part_cap);
+    a.part_b = a.part ? a.part + (size_t)chunks * E : nullptr;
+    return a.part != nullptr;
 }
-static hipError_t wgrad_det_finish(const WgradArgs& a, long chunks, hipStream_t st) {
-    hipError_t e = launch_wgrad_finalize(a.part, (int)chunks, a.part_E, a.Cout, a.split, a.dW, a.dW1, a.dW2, st);
-    if (e != hipSuccess || !a.db) return e;
-    return launch_wgrad_finalize(a.part_b, (int)chunks, a.Cout, a.Cout, a.split, a.db, a.db1, a.db2, st);
+// behind the main launch of a weight gradient: when it stored slots (det), add them in order into dW, then db
+static hipError_t wgrad_det_finish(hipError_t launched, bool det, const WgradArgs& a, long chunks, hipStream_t st) {
+    if (launched != hipSuccess || !det) return launched;
+    return launch_slot_sum_dw_db(a.part, (int)chunks, a.part_E, a.Cout, a.split, {a.dW, a.dW1, a.dW2}, {a.db, a.db1, a.db2}, st);
 }
 
-template <bool X16, bool DY16, int NCO>
-static hipError_t launch_wgrad1x1_t(const WgradArgs& a0, long target_wgs, hipStream_t st) {
-    WgradArgs a = a0;
+// the projections' split-K GEMM form: NCO 64-column output tiles per workgroup, about target_wgs workgroups
+template <int NCO>
+static hipError_t launch_wgrad1x1(WgradArgs a, long target_wgs, hipStream_t st) {
     const long rows = (long)a.NF * a.H * a.W;
     const int Cin = a.C0 + a.C1;
     const int ci_tiles = (Cin + 63) / 64, co_tiles = (a.Cout + 64 * NCO - 1) / (64 * NCO);
@@ -734,10 +734,12 @@ static hipError_t launch_wgrad1x1_t(const WgradArgs& a0, long target_wgs, hipStr
     const long nslots = (ntiles + per - 1) / per;
     const size_t lds = 64 * WG_RSB + 64 * (NCO * 128 + 16) + 64 * NCO * 4;
     const bool det = wgrad_det_setup(a, nslots, (long)Cin * a.Cout);
-    hipLaunchKernelGGL((wgrad1x1_kernel<X16, DY16, NCO>), dim3((unsigned)nslots, ci_tiles, co_tiles), dim3(256), lds, st, a, rows, per);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !det) return e;
-    return wgrad_det_finish(a, nslots, st);
+    const hipError_t e = with_bool(a.x0_bf16, [&](auto x16_c) { return with_bool(a.dy_bf16, [&](auto dy16_c) {
+        constexpr bool X16 = decltype(x16_c)::value, DY16 = decltype(dy16_c)::value;
+        return LaunchScope(st, "wgrad1x1_kernel", 0.0, 0.0, "<X16 %d, DY16 %d, NCO %d> conv1x1 %d->%d rows%ld split%d slots%ld det %d", (int)X16, (int)DY16, NCO, Cin,
+                           a.Cout, rows, a.split, nslots, det ? 1 : 0)
+            .launch(wgrad1x1_kernel<X16, DY16, NCO>, dim3((unsigned)nslots, ci_tiles, co_tiles), dim3(256), lds, a, rows, per); }); });
+    return wgrad_det_finish(e, det, a, nslots, st);
 }
 
 // out[c] += sum over rows of x[row][c]   (bias / LayerNorm-beta gradients); x is [rows][C] fp32
@@ -790,80 +792,60 @@ hipError_t launch_conv_wgrad(WgradArgs a, hipStream_t st) {
     } else {
         a.sa = 1; a.sb = 2; a.ext = 3; a.halo = 1; a.Hm = a.H; a.Wm = a.W; a.Hy = 2 * a.H; a.Wy = 2 * a.W; a.PH = 4; a.PW = 8;
     }
-    const int wide_patch = 1;
-    if (a.bf16_mma && a.kind == 0 && a.stride == 1 && a.kh == 3 && wide_patch && a.W >= 16) { a.PH = 8; a.PW = 16; }   // bf16 form: 128 positions per patch
+    if (a.bf16_mma && a.kind == 0 && a.stride == 1 && a.kh == 3 && a.W >= 16) { a.PH = 8; a.PW = 16; }   // bf16 form: 128 positions per patch
     const int NT = a.taps <= 9 ? (a.taps == 1 ? 1 : 9) : 8;
     const int tap_groups = (a.taps + NT - 1) / NT;
     a.co_tiles = (a.Cout + 63) / 64;
     const int ci_tiles = (Cin + 63) / 64;
     const int IH = (a.PH - 1) * a.sa + a.ext, IW = (a.PW - 1) * a.sa + a.ext;
-    const size_t lds = ((size_t)IH * IW + (size_t)a.PH * a.sb * a.PW * a.sb) * WG_LD * 4 + 3 * 64 * 4 + 32 * 4;
-    const long patches = (long)a.NF * ((a.Hm + a.PH - 1) / a.PH) * ((a.Wm + a.PW - 1) / a.PW);
-    const long tiles = (long)ci_tiles * a.co_tiles * tap_groups;
-    const long target_wgs = 1024;
-    // multi-tap tiles: the epilogue is 64 x 64 x NT atomic adds per workgroup and the chip sustains about one 256-byte atomic wave
-    // instruction per 50 ns per CU, so 1024 workgroups spend ~115 us in the epilogue alone; 256 (one per CU) measured best
-    const long target_wgs9 = 256;
-    long chunks = std::max<long>(1, std::min<long>(patches, (a.taps > 1 ? target_wgs9 : target_wgs) / std::max<long>(1, tiles)));
-    dim3 grid((unsigned)chunks, ci_tiles, a.co_tiles * tap_groups);
-    float* const part_in = a.part;                        // (the 1x1 GEMM form below sizes its own slots)
-    const bool det = wgrad_det_setup(a, chunks, (long)a.taps * Cin * a.Cout);
-    if (a.bf16_mma && (a.PW == 8 || a.PW == 16)) {
+    const size_t window = (size_t)IH * IW + (size_t)a.PH * a.sb * a.PW * a.sb;      // staged positions: input window + dY patch
+    if (a.bf16_mma) {
         a.pwl = a.PW == 8 ? 3 : 4;
-        const size_t lds16 = ((size_t)IH * IW + (size_t)a.PH * a.sb * a.PW * a.sb) * WG_RSB + 4 * 64 * 4 + 32 * 4;
-#define VDX_WG16(NT_, NG_, PF_, X16_, DY16_) do { auto kfn = conv_wgrad16_kernel<NT_, NG_, PF_, X16_, DY16_>;                                                \
-        if (hipError_t e = lds_opt_in(kfn, lds16); e != hipSuccess) return e; \
-        hipLaunchKernelGGL(kfn, grid, dim3(256 * NG_), lds16, st, a); } while (0)
         a.m_iw = (unsigned)((1ull << 32) / (unsigned)IW) + 1u;
         a.m_bw = (unsigned)((1ull << 32) / (unsigned)(a.PW * a.sb)) + 1u;
-        {   // register staging capacity of conv_wgrad16_kernel (XA = 6, XB = 4 float4 pieces per thread)
-            const long nth = NT == 1 ? 256 : 512;
-            if ((long)IH * IW * 16 > 6 * nth || (long)a.PH * a.sb * a.PW * a.sb * 16 > 4 * nth) return hipErrorInvalidValue;
-        }
+        // register staging capacity of conv_wgrad16_kernel (XA = 6, XB = 4 float4 pieces per thread): of the forms the entry points let
+        // through only the 1x1 at stride 2 (a 7 x 15 window on 256 threads) exceeds it
+        const long nth = NT == 1 ? 256 : 512;
+        if ((long)IH * IW * 16 > 6 * nth || (long)a.PH * a.sb * a.PW * a.sb * 16 > 4 * nth) return hipErrorInvalidValue;
         // projections: the split-K GEMM form (wide output tiles when Cout allows: x is staged Cout / 256 times instead of Cout / 64)
-        if (NT == 1 && a.kind == 0 && a.stride == 1 && !a.pro) {
-            const long wgs4 = 512;
-            a.part = part_in;
-            if (a.Cout % 256 == 0) {
-                if (a.x0_bf16) return a.dy_bf16 ? launch_wgrad1x1_t<true, true, 4>(a, wgs4, st) : launch_wgrad1x1_t<true, false, 4>(a, wgs4, st);
-                return a.dy_bf16 ? launch_wgrad1x1_t<false, true, 4>(a, wgs4, st) : launch_wgrad1x1_t<false, false, 4>(a, wgs4, st);
-            }
-            if (a.x0_bf16) return a.dy_bf16 ? launch_wgrad1x1_t<true, true, 1>(a, target_wgs, st) : launch_wgrad1x1_t<true, false, 1>(a, target_wgs, st);
-            return a.dy_bf16 ? launch_wgrad1x1_t<false, true, 1>(a, target_wgs, st) : launch_wgrad1x1_t<false, false, 1>(a, target_wgs, st);
-        }
-#define VDX_WG16_IO(NT_, NG_, PF_) do { if (a.x0_bf16) { if (a.dy_bf16) VDX_WG16(NT_, NG_, PF_, true, true); else VDX_WG16(NT_, NG_, PF_, true, false); } \
-                                        else { if (a.dy_bf16) VDX_WG16(NT_, NG_, PF_, false, true); else VDX_WG16(NT_, NG_, PF_, false, false); } } while (0)
-        if (NT == 1) VDX_WG16_IO(1, 1, false);
-        else if (NT == 9) VDX_WG16_IO(9, 2, true);
-        else VDX_WG16_IO(8, 2, true);
-#undef VDX_WG16_IO
-#undef VDX_WG16
-        { hipError_t e = hipGetLastError(); if (e != hipSuccess || !det) return e; }
-        return wgrad_det_finish(a, chunks, st);
+        if (NT == 1 && a.kind == 0 && a.stride == 1 && !a.pro) return a.Cout % 256 == 0 ? launch_wgrad1x1<4>(a, 512, st) : launch_wgrad1x1<1>(a, 1024, st);
     }
-#define VDX_WG(NT_) do { auto kfn = conv_wgrad_kernel<NT_>;                                                           \
-        if (hipError_t e = lds_opt_in(kfn, lds); e != hipSuccess) return e; \
-        hipLaunchKernelGGL(kfn, grid, dim3(256), lds, st, a); } while (0)
-    if (NT == 1) VDX_WG(1); else if (NT == 9) VDX_WG(9); else VDX_WG(8);
-#undef VDX_WG
-    { hipError_t e = hipGetLastError(); if (e != hipSuccess || !det) return e; }
-    return wgrad_det_finish(a, chunks, st);
+    const long patches = (long)a.NF * ((a.Hm + a.PH - 1) / a.PH) * ((a.Wm + a.PW - 1) / a.PW);
+    const long tiles = (long)ci_tiles * a.co_tiles * tap_groups;
+    // multi-tap tiles: the epilogue is 64 x 64 x NT atomic adds per workgroup and the chip sustains about one 256-byte atomic wave
+    // instruction per 50 ns per CU, so 1024 workgroups spend ~115 us in the epilogue alone; 256 (one per CU) measured best
+    const long target_wgs = a.taps > 1 ? 256 : 1024;
+    const long chunks = std::max<long>(1, std::min<long>(patches, target_wgs / std::max<long>(1, tiles)));
+    const dim3 grid((unsigned)chunks, ci_tiles, a.co_tiles * tap_groups);
+    const bool det = wgrad_det_setup(a, chunks, (long)a.taps * Cin * a.Cout);
+    char shape[128];
+    snprintf(shape, sizeof(shape), "conv%dx%d %d->%d %dx%dx%d%s%s%s%s patch %dx%d chunks%ld det %d", a.kh, a.kw, Cin, a.Cout, a.NF, a.H, a.W,
+             a.kind ? " up" : (a.stride == 2 ? " s2" : ""), a.C1 ? " concat" : "", a.pro ? " +prologue" : "", a.db ? " +db" : "", a.PH, a.PW, chunks, det ? 1 : 0);
+    auto go = [&](auto nt_c, auto ng_c) {                       // NT taps per workgroup; bf16 form: NG x 256 threads, prefetch with two groups
+        constexpr int NT_ = decltype(nt_c)::value, NG = decltype(ng_c)::value;
+        if (!a.bf16_mma)
+            return LaunchScope(st, "conv_wgrad_kernel", 0.0, 0.0, "<NT %d> %s", NT_, shape).launch(conv_wgrad_kernel<NT_>, grid, dim3(256), window * WG_LD * 4 + 3 * 64 * 4 + 32 * 4, a);
+        return with_bool(a.x0_bf16, [&](auto x16_c) { return with_bool(a.dy_bf16, [&](auto dy16_c) {
+            constexpr bool PF = NG == 2, X16 = decltype(x16_c)::value, DY16 = decltype(dy16_c)::value;
+            return LaunchScope(st, "conv_wgrad16_kernel", 0.0, 0.0, "<NT %d, NG %d, PF %d, X16 %d, DY16 %d> %s", NT_, NG, (int)PF, (int)X16, (int)DY16, shape)
+                .launch(conv_wgrad16_kernel<NT_, NG, PF, X16, DY16>, grid, dim3(256 * NG), window * WG_RSB + 4 * 64 * 4 + 32 * 4, a); }); });
+    };
+    return wgrad_det_finish(NT == 1 ? go(Int<1>{}, Int<1>{}) : NT == 9 ? go(Int<9>{}, Int<2>{}) : go(Int<8>{}, Int<2>{}), det, a, chunks, st);
 }
 
 hipError_t launch_colsum(const float* x, float* out, long rows, int C, hipStream_t st, float* part, size_t part_cap) {
     const int cpt = (C + 3) / 4, lanes_c = cpt < 256 ? cpt : 256, rl = 256 / lanes_c;
     const int blocks = (int)std::max<long>(1, std::min<long>((rows + rl - 1) / rl, 1024));
-    if (part && (size_t)blocks * C > part_cap) part = nullptr;
-    hipLaunchKernelGGL(colsum_kernel, dim3(blocks), dim3(256), 0, st, x, out, rows, C, part);
-    hipError_t e = hipGetLastError();
+    part = slots_if_fit(part, (size_t)blocks * C, part_cap);
+    hipError_t e = LaunchScope(st, "colsum_kernel", 0.0, 0.0, "rows%ld C%d slots%d det %d", rows, C, blocks, part ? 1 : 0)
+                       .launch(colsum_kernel, dim3(blocks), dim3(256), 0, x, out, rows, C, part);
     if (e != hipSuccess || !part) return e;
-    return launch_wgrad_finalize(part, blocks, C, C, 0, out, nullptr, nullptr, st);      // every workgroup wrote its row of column sums: add them in order
+    return launch_slot_sum(part, blocks, (size_t)C, C, C, 0, out, nullptr, nullptr, st);      // every workgroup wrote its row of column sums: add them in order
 }
 
 hipError_t launch_add_inplace(float* y, const float* x, long n, hipStream_t st) {
     const int blocks = (int)std::max<long>(1, std::min<long>((n / 4 + 255) / 256, 2048));
-    hipLaunchKernelGGL(add_inplace_kernel, dim3(blocks), dim3(256), 0, st, y, x, n);
-    return hipGetLastError();
+    return LaunchScope(st, "add_inplace_kernel", 0.0, 0.0, "n%ld", n).launch(add_inplace_kernel, dim3(blocks), dim3(256), 0, y, x, n);
 }
 
 }  // namespace vdx
