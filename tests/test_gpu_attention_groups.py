@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 import _attention_cases as AC
 import _parity as P
+import _parity_routes as PR
 from _launch_hook import assert_launches, launches
 
 # (tests/test_gpu_f16_forms.py runs the shapes that only fp16 mode needs through _run_attention / _run_sla / _check of this module)
@@ -123,6 +124,7 @@ ATTN16 = [
     ((1, 16, 8, 8, 128), False, False, 'attention_h8_kernel', ['<1, 2, 1, 4, 1, 0, 1>', 'C128 L16 nseq64']),   # C = 128 (attention_w serves 64 / 32 only), full
     ((1, 10, 6, 6, 128), False, False, 'attention_h8_kernel', ['<1, 2, 1, 4, 1, 0, 0>', 'C128 L10 nseq36']),   # C = 128 masked, 9 workgroups
     ((1, 10, 8, 8, 32), False, False, 'attention_h8_kernel', ['<1, 1, 1, 1, 1, 0, 0>', 'C32 L10 nseq64']),     # C = 32 below the threshold
+    ((1, 10, 6, 6, 128), True, False, 'attention_h8_kernel', ['<1, 2, 1, 4, 1, 1, 0>', 'C128 L10 nseq36']),    # C = 128 masked with the e4m3 core: level 1 of the N shape's fp8 sampling
 ]
 
 
@@ -132,6 +134,32 @@ def test_attention_bf16_tensors_per_group(shape, fp8, iso, kernel, parts):
     what = f'attention bf16 tensors {shape} fp8={int(fp8)} iso={int(iso)}'
     y, rec = _run_attention(c, 'bf16', True, fp8, what)
     assert_launches(rec, [(kernel, parts)], what)
+    PR.assert_first(PR.cid('attention16', shape, fp8, iso), rec)
+    assert y.dtype == BF
+    _check(c, y, what)
+
+
+# What vdx_attention_forward_bf16 runs where neither attention_w nor attention_h8 has a form: attention_kernel <1, LP, TMO> for 17..64 tokens
+# (the dim-128 configuration on bf16 tensors: 32 frames, every width of its levels) and attention_reg_kernel <1, TMA, fp8> for channel
+# counts / sequence counts attention_h8 does not take (the dim-16 model).  Both scale q before they round it; "io16 1" in the shape string.
+ATTN16_GENERIC = [
+    # shape (B, F, H, W, C), temporal, kernel, parts of the shape string
+    ((1, 32, 1, 3, 128), True, 'attention_kernel', ['<1, 32, 2>', 'C128 L32 nseq3', 'io16 1']),            # 3 sequences, 2 per workgroup: the last one half empty
+    ((1, 32, 1, 3, 256), True, 'attention_kernel', ['<1, 32, 4>', 'C256 L32 nseq3', 'io16 1']),
+    ((1, 20, 1, 3, 512), True, 'attention_kernel', ['<1, 32, 8>', 'C512 L20 nseq3', 'io16 1']),            # keys 20..31 masked
+    ((1, 32, 1, 2, 1024), True, 'attention_kernel', ['<1, 32, 16>', 'C1024 L32 nseq2', 'io16 1']),
+    ((2, 4, 3, 3, 16), True, 'attention_reg_kernel', ['<1, 4, fp8 0>', 'C16 L4 nseq18', 'io16 1']),        # 18 sequences: 5 workgroups of 4, the last one half empty
+    ((1, 2, 2, 2, 128), False, 'attention_reg_kernel', ['<1, 8, fp8 0>', 'C128 L4 nseq2', 'io16 1']),      # 4 tokens of a 2 x 2 bottleneck, 2 sequences
+]
+
+
+@pytest.mark.parametrize('shape,temporal,kernel,parts', ATTN16_GENERIC)
+def test_attention_bf16_tensors_generic_kernels_per_group(shape, temporal, kernel, parts):
+    c = AC.attn_case(shape, temporal, True, 'bf16', False, False, True)
+    what = f'attention bf16 tensors, generic kernels {shape} temporal={int(temporal)}'
+    y, rec = _run_attention(c, 'bf16', True, False, what)
+    assert_launches(rec, [(kernel, parts)], what)
+    PR.assert_first(PR.cid('attention16 generic', shape, temporal), rec)
     assert y.dtype == BF
     _check(c, y, what)
 
@@ -178,6 +206,7 @@ def test_attention_fp32_tensors_per_group(shape, temporal, iso, expect, mode):
     what = f'attention fp32 tensors {shape} temporal={int(temporal)} {mode}'
     y, rec = _run_attention(c, mode, False, False, what)
     assert_launches(rec, [(kernel, parts)], what)
+    PR.assert_first(PR.cid('attention32', shape, temporal, iso, mode), rec)
     _check(c, y, what)
 
 
@@ -209,6 +238,9 @@ SLA16 = [
     ((2, 10, 16, 16, 32), False, _sla16(32, 256, 20, 1, 1)),           # C = 32 form
     ((1, 4, 16, 16, 128), False, _sla16(128, 256, 4, 1, 4)),           # C = 128 form
     ((32, 16, 64, 32, 64), False, _sla16(64, 2048, 512, 2, 'w')),      # 512 frames: 512 x (32 / 16) = 1024 workgroups -> nsub doubled to 16, 2 chunks: the many-frames plan of the benchmark
+    # widths without a one-wave-per-head form (16 of the dim-16 model, 1024 of the dim-128 bottleneck): the generic kernels on bf16 tensors
+    ((1, 2, 8, 8, 16), False, [('sla_ctx_kernel', ['<1>', 'C16 N64 NF2 nchunk1', 'io16 1']), ('sla_combine_kernel', ['<1>', 'NF2 nchunk1']),
+                               ('sla_out_kernel', ['<1, 1>', 'C16 N64 NF2', 'io16 1'])]),
 ]
 
 
@@ -218,6 +250,7 @@ def test_sla_bf16_tensors_per_group(shape, iso, expect):
     what = f'SLA bf16 tensors {shape} iso={int(iso)}'
     y, rec = _run_sla(c, 'bf16', True, what)
     assert_launches(rec, expect, what)
+    PR.assert_first(PR.cid('sla16', shape, iso), rec)
     assert y.dtype == BF
     _check(c, y, what)
 
@@ -256,4 +289,5 @@ def test_sla_fp32_tensors_per_group(shape, iso, nchunk, mode):
     what = f'SLA fp32 tensors {shape} {mode} iso={int(iso)}'
     y, rec = _run_sla(c, mode, False, what)
     assert_launches(rec, _sla32(mode, C, H * W, B * Fr, nchunk), what)
+    PR.assert_first(PR.cid('sla32', shape, iso, mode), rec)
     _check(c, y, what)

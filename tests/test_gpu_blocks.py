@@ -6,6 +6,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import _parity as P
+import _parity_routes as PR
 from oracle import unet3d_ref as R
 
 DEV = 'cuda:0'
@@ -192,7 +193,8 @@ def test_attention(mode, case):
     x = torch.randn(B, Fr, H, W, C, generator=g)
     p = _mha_params(C, heads, g)
     packed = ops.pack_mha(*[(p[f'a.{n}.kernel'].to(DEV), p[f'a.{n}.bias'].to(DEV)) for n in ('q', 'k', 'v', 'out')], mode)
-    y = ops.attention_forward(x.to(DEV), packed, heads, temporal, mode)
+    with PR.bound(PR.cid('blocks attention', mode, case)):       # (the first launch against tests/golden/parity_routes.json)
+        y = ops.attention_forward(x.to(DEV), packed, heads, temporal, mode)
     pd = {k: v.double() for k, v in p.items()}
     xd = x.double()
     if temporal:
@@ -226,6 +228,10 @@ ATTN16_CASES = [
 ]
 
 
+ATTN16_FP8 = (ATTN16_CASES[0], ATTN16_CASES[7])     # the cases that run the fp8 (e4m3) core as well
+ATTN16_KERNEL = {c: 'attention_w_kernel' if c[2] * c[3] >= 256 and c[4] in (32, 64) else 'attention_h8_kernel' for c in ATTN16_CASES}    # what the comments of the table say
+
+
 @pytest.mark.parametrize('case', ATTN16_CASES)
 def test_attention_bf16_tensors(case):
     from video_diffusion_nnx_amd import ops
@@ -234,7 +240,8 @@ def test_attention_bf16_tensors(case):
     x = torch.randn(B, Fr, H, W, C, generator=g).bfloat16()
     p = _mha_params(C, 8, g)
     packed = ops.pack_mha(*[(p[f'a.{n}.kernel'].to(DEV), p[f'a.{n}.bias'].to(DEV)) for n in ('q', 'k', 'v', 'out')], 'bf16')
-    y = ops.attention_forward_bf16(x.to(DEV), packed, 8, True)
+    with PR.bound(PR.cid('blocks attention16', case)):
+        y = ops.attention_forward_bf16(x.to(DEV), packed, 8, True)
     xd = x.double()
     xt = xd.permute(0, 2, 3, 1, 4).reshape(B, H * W, Fr, C)
     o = R.multihead_attention({k: v.double() for k, v in p.items()}, 'a', xt, 32).reshape(B, H, W, Fr, C).permute(0, 3, 1, 2, 4)
@@ -245,8 +252,9 @@ def test_attention_bf16_tensors(case):
     assert rel_branch < 4e-2 and rel < 1e-2, (case, rel_branch, rel)
     y2 = ops.attention_forward_bf16(x.to(DEV), packed, 8, True)
     assert torch.equal(y, y2)                      # no order-dependent sums: bit-reproducible
-    if case in (ATTN16_CASES[0], ATTN16_CASES[7]):  # the fp8 (e4m3) QK^T / PV core of the same kernels (parity unpinned; stated 1e-1 as above)
-        y8 = ops.attention_forward_bf16(x.to(DEV), packed, 8, True, fp8_core=True).cpu().double()
+    if case in ATTN16_FP8:  # the fp8 (e4m3) QK^T / PV core of the same kernels (parity unpinned; stated 1e-1 as above)
+        with PR.bound(PR.cid('blocks attention16', case, 'fp8')):
+            y8 = ops.attention_forward_bf16(x.to(DEV), packed, 8, True, fp8_core=True).cpu().double()
         r8 = _rel(y8 - xd, o)
         print(f'   fp8 core: branch {r8:.3e}')
         assert rel_branch * 1.5 < r8 < 1e-1, (case, r8, rel_branch)
@@ -268,8 +276,10 @@ def test_attention_fp8_core(case):
     x = torch.randn(B, Fr, H, W, C, generator=g)
     p = _mha_params(C, heads, g)
     packed = ops.pack_mha(*[(p[f'a.{n}.kernel'].to(DEV), p[f'a.{n}.bias'].to(DEV)) for n in ('q', 'k', 'v', 'out')], 'bf16')
-    y16 = ops.attention_forward(x.to(DEV), packed, heads, temporal, 'bf16')
-    y8 = ops.attention_forward(x.to(DEV), packed, heads, temporal, 'bf16', fp8_core=True)
+    with PR.bound(PR.cid('blocks fp8', case, False)):
+        y16 = ops.attention_forward(x.to(DEV), packed, heads, temporal, 'bf16')
+    with PR.bound(PR.cid('blocks fp8', case, True)):
+        y8 = ops.attention_forward(x.to(DEV), packed, heads, temporal, 'bf16', fp8_core=True)
     pd = {k: v.double() for k, v in p.items()}
     xd = x.double()
     if temporal:
@@ -318,7 +328,8 @@ def test_sla_bf16_tensors(case):
     x = x.bfloat16()
     p = {f'a.{n}.kernel': torch.randn(1, C, 256, generator=g) / C ** 0.5 * 3 for n in ('q', 'k', 'v')}
     p['a.to_out.kernel'] = torch.randn(1, 256, C, generator=g) / 16
-    y = ops.sla_forward_bf16(x.to(DEV), *[p[f'a.{n}.kernel'].to(DEV) for n in ('q', 'k', 'v', 'to_out')])
+    with PR.bound(PR.cid('blocks sla16', case)):
+        y = ops.sla_forward_bf16(x.to(DEV), *[p[f'a.{n}.kernel'].to(DEV) for n in ('q', 'k', 'v', 'to_out')])
     xd = x.double()
     o = R.spatial_linear_attention({k: v.bfloat16().double() for k, v in p.items()}, 'a', xd, 8)
     yd = y.cpu().double()
@@ -341,8 +352,9 @@ def test_sla(mode, case):
     p['a.to_out.kernel'] = torch.randn(1, 256, C, generator=g) / 16
     # spike some k logits so the running max jumps between sub-tiles (forces the rescale branch)
     x[:, :, H // 2, W // 2] *= 6
-    y = ops.sla_forward(x.to(DEV), p['a.q.kernel'].to(DEV), p['a.k.kernel'].to(DEV), p['a.v.kernel'].to(DEV),
-                        p['a.to_out.kernel'].to(DEV), 8, mode)
+    with PR.bound(PR.cid('blocks sla', mode, case)):
+        y = ops.sla_forward(x.to(DEV), p['a.q.kernel'].to(DEV), p['a.k.kernel'].to(DEV), p['a.v.kernel'].to(DEV),
+                            p['a.to_out.kernel'].to(DEV), 8, mode)
     o = R.spatial_linear_attention({k: v.double() for k, v in p.items()}, 'a', x.double(), 8)
     rel = _rel(y.cpu().double() - x.double(), o)
     assert rel < TOL[mode], (mode, case, rel)

@@ -22,7 +22,8 @@ import _parity as P
 from _launch_hook import assert_launches, launches, nan_outputs
 from oracle import unet3d_ref as R
 from test_gpu_attention_groups import _check, _dev, _nan_like, _run_attention, _run_sla, _sla32
-from test_gpu_conv import CASES as FWD_CASES
+import _parity_routes as PR
+from test_gpu_conv import CASES as FWD_CASES, _conv_chain, _conv_form
 from test_gpu_conv_backward import CASES as BWD_CASES
 
 DEV = 'cuda:0'
@@ -52,6 +53,7 @@ def test_attention_f16_per_group(shape, temporal, iso, kernel, parts):
     what = f'attention f16 {shape} temporal={int(temporal)} iso={int(iso)}'
     y, rec = _run_attention(c, 'f16', False, False, what)
     assert_launches(rec, [(kernel, parts)], what)
+    PR.assert_first(PR.cid('attention f16', shape, temporal, iso), rec)
     assert y.dtype == F32
     _check(c, y, what)
 
@@ -73,6 +75,7 @@ def test_sla_f16_per_group(shape, iso, nchunk):
     what = f'SLA f16 {shape} iso={int(iso)}'
     y, rec = _run_sla(c, 'f16', False, what)
     assert_launches(rec, _sla32('f16', C, H * W, B * Fr, nchunk), what)
+    PR.assert_first(PR.cid('sla f16', shape, iso), rec)
     _check(c, y, what)
 
 
@@ -136,6 +139,7 @@ def test_conv_f16_per_tile(case):
         return (y, stats) if stats is not None else (y,)
     out, rec = _conv_twice(go, what)
     assert_launches(rec, [(IGEMM, _igemm_parts(Cout, stride))], what)
+    PR.assert_first(PR.cid('conv f16', case), rec)
     _assert_tiles_exact(out[0], ref32, ref64, what)
     if len(out) > 1:
         tiles = -(-ref64[0].numel() // Cout // 256)
@@ -160,6 +164,7 @@ def test_conv_f16_concat_and_prologue():
         return ops.conv_forward(_dev(xa), pw, Cout, mode='f16', bias=_dev(bias), x1=_dev(xb), out_stats=stats), stats
     (y1, stats1), rec = _conv_twice(first, 'conv f16 concat')
     assert_launches(rec, [(IGEMM, _igemm_parts(Cout, 1) + ['concat'])], 'conv f16 concat')
+    PR.assert_first(PR.cid('conv f16 concat'), rec)
     _assert_tiles_exact(y1, ref32, ref64, 'conv f16 concat')
     P.assert_gn_stats(ops.gn_stats_reduce(stats1, B, 8), ref64, ref32, 1, what='conv f16 concat')
     gamma, beta = 1 + 0.1 * torch.randn(Cout, generator=g), 0.1 * torch.randn(Cout, generator=g)
@@ -185,10 +190,39 @@ def test_conv_f16_concat_and_prologue():
             (y2,), rec = _conv_twice(lambda: ops.conv_forward(y1d, pw2, Cout, mode='f16', in_stats=sd, gamma=_dev(gamma), beta=_dev(beta),
                                                               scale_shift=_dev(ss) if use_ss else None), what)
             assert_launches(rec, [(IGEMM, _igemm_parts(Cout, 1) + ['+prologue'])], what)
+            PR.assert_first(PR.cid('conv f16 prologue', use_ss), rec)
             P.assert_tiles(y2, ref2, bound, what=what)
 
 
-@pytest.mark.parametrize('shape,cin,cout', [((1, 2, 9, 9), 256, 128), ((1, 3, 5, 7), 40, 48)])
+F16_CHAINS = [
+    # mode, bf16 tensors, B, F, H, W, C0, C1, Cout   (tests/test_gpu_conv.py GENERIC_CHAINS: what the dim-128 network at fp16 operands launches)
+    ('f16', False, 2, 3, 16, 16, 24, 16, 72),        # <2, 128, 2, 8, 0> conv3x3 concat, then <2, 128, 2, 8, 0> conv3x3 +prologue (128-channel workgroup tile)
+]
+F16_FORMS = [
+    # mode, bf16 tensors, B, F, H, W, C0, C1, Cout, k, stride, kind, res   (tests/test_gpu_conv.py GENERIC_FORMS)
+    ('f16', False, 1, 3, 6, 10, 24, 16, 40, 1, 1, 0, None),        # <2, 64, 2, 8, 0> conv1x1 concat
+    ('f16', False, 1, 3, 6, 10, 24, 24, 72, 1, 1, 0, None),        # <2, 128, 2, 8, 0> conv1x1 concat
+    ('f16', False, 1, 3, 12, 20, 40, 0, 72, 4, 2, 0, None),        # <2, 128, 2, 8, 0> conv4x4 s2
+]
+
+
+@pytest.mark.parametrize('mode,t16,B,Fr,H,W,C0,C1,Cout', F16_CHAINS)
+def test_conv_f16_chain(mode, t16, B, Fr, H, W, C0, C1, Cout):
+    """The 128-channel workgroup tile of the fp16 generic conv on a concat input, then its fused-prologue form: per (frame, tile), the
+    prologue at max(2e-6, 4 x the flip floor of the activation rounded to fp16), below an eighth of the bf16 form's 5e-3."""
+    _conv_chain(mode, t16, B, Fr, H, W, C0, C1, Cout, 'f16 chain', 5e-3 / 8)
+
+
+@pytest.mark.parametrize('mode,t16,B,Fr,H,W,C0,C1,Cout,k,stride,kind,res', F16_FORMS)
+def test_conv_f16_form(mode, t16, B, Fr, H, W, C0, C1, Cout, k, stride, kind, res):
+    """Pointwise convs on a concat input (the res_conv of the up blocks) and the Downsample with more than 64 output channels."""
+    _conv_form(mode, t16, B, Fr, H, W, C0, C1, Cout, k, stride, kind, res, 'f16 form')
+
+
+PW_F16 = [((1, 2, 9, 9), 256, 128), ((1, 3, 5, 7), 40, 48)]
+
+
+@pytest.mark.parametrize('shape,cin,cout', PW_F16)
 def test_pointwise_conv_f16_bias_and_residual(shape, cin, cout):
     """The out-projection of the long attention: 1x1, bias, fp32 residual; 40 -> 48: ragged channels on both sides."""
     from video_diffusion_nnx_amd import ops
@@ -201,6 +235,7 @@ def test_pointwise_conv_f16_bias_and_residual(shape, cin, cout):
     what = f'1x1 conv f16 {shape} {cin}->{cout} + bias + res'
     (y,), rec = _conv_twice(lambda: ops.conv_forward(_dev(x), pw, cout, mode='f16', bias=_dev(bias), k=1, res=_dev(res)), what)
     assert_launches(rec, [(IGEMM, _igemm_parts(cout, 1) + ['+res'])], what)
+    PR.assert_first(PR.cid('pw f16', shape, cin, cout), rec)
     _assert_tiles_exact(y, ref(F32), ref(F64), what)
 
 
@@ -242,6 +277,7 @@ def test_conv_f16_subnormal_operands():
     what = 'conv f16 subnormal operands'
     (y,), rec = _conv_twice(lambda: ops.conv_forward(_dev(x), pw, Cout, mode='f16'), what)
     assert_launches(rec, [(IGEMM, _igemm_parts(Cout, 1))], what)
+    PR.assert_first(PR.cid('conv f16 subnormal'), rec)
     assert torch.isfinite(y).all()
     sl = P.tile_slices(y.shape)
     verdict, refs = {}, []

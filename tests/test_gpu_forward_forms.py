@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 
 import _forward_cases as FC
 import _parity as P
+import _parity_routes as PR
 from _launch_hook import assert_launches, launches
 from oracle import unet3d_ref as R
 
@@ -47,7 +48,10 @@ def _finite(t, what):
 
 _HEADS = ([(s, True, io16, False) for s in FC.ATTN_HEADS_TEMPORAL for io16 in (False, True)] +
           [(FC.ATTN_HEADS_TEMPORAL[0], True, io16, True) for io16 in (False, True)] +
-          [(s, False, io16, False) for s in FC.ATTN_HEADS_SPATIAL for io16 in (False, True)])
+          [(s, False, io16, False) for s in FC.ATTN_HEADS_SPATIAL for io16 in (False, True)] +
+          # the fp8 flag on 64 tokens, as the fp8 network sets it on mid_spatial_attn: launch_attention_head reports "fp8 1, lt 4" and runs
+          # the bf16 core (sequences of more than 16 tokens ignore the flag) -- the output must be that of the unflagged call, bit for bit
+          [(FC.ATTN_HEADS_SPATIAL[0], False, True, True)])
 
 
 def _run_heads(c, temporal, io16, fp8):
@@ -61,14 +65,19 @@ def _run_heads(c, temporal, io16, fp8):
 @pytest.mark.parametrize('shape,temporal,io16,fp8', _HEADS)
 def test_attention_heads(shape, temporal, io16, fp8):
     """attention_head_kernel<IO16, 4, F8, LT = 1 | 4> + the 1x1 out-projection with residual (model.hip attention_block_forward)."""
-    c = FC.attn_heads_case(shape, temporal, io16, fp8)
-    y, o = _run_heads(c, temporal, io16, fp8)
+    core8 = fp8 and (shape[1] if temporal else shape[2] * shape[3]) <= 16       # the e4m3 core exists for sequences of at most 16 tokens
+    c = FC.attn_heads_case(shape, temporal, io16, core8)
+    with PR.bound(PR.cid('heads', shape, temporal, io16, fp8)):
+        y, o = _run_heads(c, temporal, io16, fp8)
     what = f'attention heads {shape} temporal={int(temporal)} io16={int(io16)} fp8={int(fp8)}'
     _finite(o, what + ' o'); _finite(y, what + ' y')
     assert y.dtype == (BF if io16 else F32) and o.dtype == BF
     P.assert_groups(c['og'](o.double()), c['og'](c['o64']), (c['nseq'], 8), c['bound_o'], what + ' o per (sequence, head)')
     P.assert_groups(FC.seq_groups(y.double(), temporal), FC.seq_groups(c['y64'], temporal), (c['nseq'],), c['bound_y'], what + ' y per sequence')
-    if fp8:
+    if fp8 and not core8:
+        y0, o0 = _run_heads(c, temporal, io16, False)
+        assert torch.equal(o.view(torch.uint8), o0.view(torch.uint8)) and torch.equal(y.view(torch.uint8), y0.view(torch.uint8)), f'{what}: the flag changed the output'
+    if core8:
         # the fp8 core must actually run: its error sits well above the bf16 operands' (the check the fp8 tests of test_gpu_blocks.py use)
         c16 = FC.attn_heads_case(shape, temporal, io16, False)
         _, o16 = _run_heads(c16, temporal, io16, False)
@@ -96,7 +105,10 @@ def test_attention_heads_rejects_what_the_network_routes_elsewhere():
 
 # ---- long attention core ------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize('mode,io16', [('f32', False), ('bf16', False), ('bf16', True), ('f16', False)])
+LONG_MODES = [('f32', False), ('bf16', False), ('bf16', True), ('f16', False)]
+
+
+@pytest.mark.parametrize('mode,io16', LONG_MODES)
 @pytest.mark.parametrize('shape', FC.ATTN_LONG)
 def test_attention_long(shape, mode, io16):
     """1x1 q|k|v conv -> attention_long_core_kernel -> 1x1 out-projection + residual (more than 64 tokens).  Each stage is judged on
@@ -111,6 +123,7 @@ def test_attention_long(shape, mode, io16):
     what = f'long attention {shape} {mode} io16={int(io16)}'
     with launches() as rec:                     # (ops.attention_long_forward NaN-fills y and the scratch itself)
         y, qkv, o = _twice(lambda: ops.attention_long_forward(x, packed, 8, mode))
+    PR.assert_first(PR.cid('long', shape, mode, io16), rec)
     if mode == 'f16':           # both projections on the fp16 form of the generic conv (x and the weights here are fp16 numbers as well)
         assert_launches(rec[:3], [('conv_igemm_kernel', ['<2, 128, 2, 8, 0>', 'conv1x1 128->768']), ('attention_long_core_kernel', [f"L{c['L']}"]),
                                   ('conv_igemm_kernel', ['<2, 128, 2, 8, 0>', 'conv1x1 256->128', '+res'])], what)
@@ -155,7 +168,8 @@ def test_sla_heads(shape, io16):
     c = FC.sla_heads_case(shape, io16)
     x = _dev(c['x'], BF if io16 else F32)
     w = [_dev(t.reshape(1, *t.shape)) for t in c['w']]
-    y, o = _twice(lambda: ops.sla_heads_forward(x, *w))
+    with PR.bound(PR.cid('sla heads', shape, io16)):
+        y, o = _twice(lambda: ops.sla_heads_forward(x, *w))
     what = f'sla heads {shape} io16={int(io16)}'
     _finite(o, what + ' o'); _finite(y, what + ' y')
     P.assert_groups(c['og'](o.double()), c['og'](c['o64']), (c['NF'], 8), c['bound_o'], what + ' o per (frame, head)')
