@@ -591,6 +591,47 @@ int vdx_dpm_sample_loop_guided(vdx_handle* h, const float* params, const void* p
                                float cond_scale, float rescale, double* cfg_scratch, void* workspace, size_t workspace_bytes, int batch,
                                int use_graph, void* stream);
 
+/* Held-out evaluation (EXTENSION, no reference code: Ho et al. 2020, eq. 5; Nichol & Dhariwal 2021, calc_bpd_loop): the terms of the
+ * variational bound of a video x [batch,C,F,H,W] in [0, 1], in bits per dimension (means over the C*F*H*W elements of a sample, nats /
+ * ln 2).  x0 = 2 x - 1 is formed in the kernels.  vlb_tables [VDX_VLB_ROWS][timesteps] DOUBLES (device; make_vlb_tables of the Python
+ * host): rows 0-5 = sqrt_ac | sqrt(1 - ac) | sqrt_recip_ac | sqrt_recipm1_ac | posterior_mean_coef1 | coef2, the fp32 schedule values
+ * the sampling kernels use, widened; row 6 = w_t = coef1_t^2 / (2 post_var_t ln 2) formed in double; row 7 = the decoder's
+ * log-variance, log post_var_max(t,1); row 8 = alphas_cumprod.  With t = t[b] per sample and eps = `noise` [batch,C,F,H,W] or, when
+ * noise is NULL, Philox(seed, draw + *step_dev) indexed by the element index of the whole tensor (vdx_p_sample_step's stream):
+ *   x_t   = sqrt_ac[t] x0 + sqrt(1 - ac[t]) eps                              (formed in double, exact products and one fused multiply-add;
+ *                                                                            vdx_vlb_noise rounds it to fp32 once for the network, vdx_vlb_terms
+ *                                                                            uses the double itself: the two differ by one correct rounding)
+ *   x0^   = sqrt_recip_ac[t] x_t - sqrt_recipm1_ac[t] eps_hat, clamped to [-1, 1] when clip_denoised (no dynamic threshold); in double, as are
+ *           the differences below
+ *   mse = mean (eps_hat - eps)^2      xstart_mse = mean (x0^ - x0)^2
+ *   t >= 1:  vb = mean w_t (x0 - x0^)^2         -- KL(q(x_{t-1} | x_t, x0) || p(x_{t-1} | x_t)) with both variances post_var_t
+ *   t == 0:  vb = -mean log2 P(x0)              -- discretized Gaussian on the 8-bit grid (bin half-width 1/255), mean coef1_0 x0^ +
+ *            coef2_0 x_t, log-variance row 7; P = max(Phi(z+), 1e-12) for x0 < -0.999, max(1 - Phi(z-), 1e-12) for x0 > 0.999,
+ *            max(Phi(z+) - Phi(z-), 1e-12) otherwise, z+- = (x0 - mean +- 1/255) / sigma, evaluated in double
+ * eps_hat is channel-last [batch,F,H,W,C].  vdx_vlb_terms: out [batch][3] = (vb, mse, xstart_mse); vdx_vlb_prior: out [batch] =
+ * mean 0.5 (-1 - log(1 - ac_{T-1}) + (1 - ac_{T-1}) + ac_{T-1} x0^2) / ln 2.  The sums are taken in double by a fixed grid with a fixed
+ * quad-to-thread map, a fixed-order tree per workgroup and an in-order sum of the workgroups' partials: no atomics, the bits of out
+ * depend on the inputs only.  partial: vdx_vlb_scratch_doubles(batch) doubles.  per_sample % 4 == 0 and % channels == 0; x / xt /
+ * noise 16-byte, partial / out / vlb_tables 8-byte aligned; timesteps >= 2 (all VDX_ERR_INVALID). */
+#define VDX_VLB_ROWS 9
+size_t vdx_vlb_scratch_doubles(int batch);
+int vdx_vlb_noise(const float* x, float* xt, const int* t, const double* vlb_tables, int timesteps, const float* noise, uint64_t seed,
+                  uint64_t draw, const uint64_t* step_dev, int batch, long per_sample, void* stream);
+int vdx_vlb_terms(const float* x, const float* eps_hat, const int* t, const double* vlb_tables, int timesteps, const float* noise,
+                  uint64_t seed, uint64_t draw, const uint64_t* step_dev, int clip_denoised, double* partial, double* out, int batch,
+                  int channels, long per_sample, void* stream);
+int vdx_vlb_prior(const float* x, const double* vlb_tables, int timesteps, double* partial, double* out, int batch, long per_sample,
+                  void* stream);
+/* nsteps repetitions of  vdx_vlb_noise(x -> xt_buf, draw 1 + k) ; the forward (xt_buf, t_dev, cond un-masked -> eps_buf) ; the terms ;
+ * an advance that writes out[k][batch][3], sets t_dev[:] = max(seq[k + 1], 0) and k = *step_dev += 1 -- eagerly or (use_graph) as
+ * replays of one captured step in a graph slot of its own (no sampling loop's graph is evicted).  seq: seq_len + 1 descending levels
+ * ending in -1 (the DDIM loops' sequence).  On entry t_dev[0..batch) = seq[0] and *step_dev = 0, or where an earlier call over the
+ * same buffers left them: the loop may be issued in pieces.  out [seq_len][batch][3]. */
+int vdx_vlb_loop(vdx_handle* h, const float* params, const void* packed, const float* x, float* xt_buf, float* eps_buf, int* t_dev,
+                 uint64_t* step_dev, const double* vlb_tables, int timesteps, const int* seq, int seq_len, int nsteps, const float* cond,
+                 uint64_t seed, int clip_denoised, double* partial, double* out, void* workspace, size_t workspace_bytes, int batch,
+                 int use_graph, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */

@@ -123,3 +123,9 @@ vdx_ddim_sample_loop_guided = _sig('vdx_ddim_sample_loop_guided', c_int, [c_void
                                                                           c_float, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p])
 vdx_dpm_sample_loop_guided = _sig('vdx_dpm_sample_loop_guided', c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p,
                                                                         c_float, c_float, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p])
+
+# held-out evaluation (vdx.h: "Held-out evaluation"): the captured loop; the single-step entries are bound in ops.py
+VLB_ROWS = 9                                     # VDX_VLB_ROWS: the rows of the table of doubles (gaussian_diffusion.make_vlb_tables)
+vdx_vlb_scratch_doubles = _sig('vdx_vlb_scratch_doubles', c_size_t, [c_int])
+vdx_vlb_loop = _sig('vdx_vlb_loop', c_int, [c_void_p] * 9 + [c_int, c_void_p, c_int, c_int, c_void_p, _u64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                            c_int, c_int, c_void_p])

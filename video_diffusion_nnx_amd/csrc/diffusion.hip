@@ -7,6 +7,8 @@
 //   loss ............. mean |eps_hat - eps| or (eps_hat - eps)^2                 gaussian_diffusion.py:460-468
 //   p_sample_loop .... T x { Unet3D forward ; p_sample_step ; t -= 1 } on one stream, the step captured once
 //                      in a hipGraph and replayed (no host work per step)      gaussian_diffusion.py:264-320
+//   vlb_* ............ held-out evaluation (extension): x_t, then the terms of the variational bound in bits/dim as deterministic
+//                      per-sample sums; the loop is vdx_vlb_loop in vdx_api.cpp
 // External tensors are [B,C,F,H,W]; the UNet output eps_hat is channel-last [B,F,H,W,C] (unet3d.py:387) and is
 // re-indexed on the fly (the reference's rearrange at gaussian_diffusion.py:197,460).
 #include "vdx_common.h"
@@ -668,6 +670,151 @@ __global__ void cfg_mask_kernel(unsigned char* mask, int B) {
     for (int i = threadIdx.x; i < 2 * B; i += blockDim.x) mask[i] = i >= B ? 1 : 0;
 }
 
+// Held-out evaluation: the terms of the variational bound in bits/dim (vdx.h: "Held-out evaluation"; EXTENSION, no reference code).
+// tab [VDX_VLB_ROWS][T] doubles.  Both kernels run a fixed grid (kVlbBlocks, B), whatever per_sample or the device: quad q of a sample
+// belongs to thread q mod (kVlbBlocks * 256) of the sample's workgroups.
+constexpr int kVlbBlocks = 64;                 // one quad per thread at 16 x 64 x 64 x 1
+
+// x0 = 2 x - 1 and x_t = a x0 + s eps of one element in double: the products of two floats are exact there, so x_t carries one double
+// rounding.  vlb_noise_kernel rounds it to fp32 once for the network -- the correctly rounded value of the x_t vlb_term_kernel uses.
+__device__ __forceinline__ double vlb_x0(float x) { return 2.0 * (double)x - 1.0; }
+__device__ __forceinline__ double vlb_xt(float a, float s, float x, float n) { return fma((double)a, vlb_x0(x), (double)s * (double)n); }
+
+__device__ __forceinline__ int vlb_level(const int* t, int b, int T) { return min(max(t[b], 0), T - 1); }
+
+// the noise of quad q of sample b: the explicit tensor, or the Philox draw indexed by the element index of the whole tensor
+__device__ __forceinline__ float4 vlb_eps4(const VlbArgs& P, size_t base, long q, unsigned long long draw) {
+    if (P.noise) return *reinterpret_cast<const float4*>(P.noise + base + 4 * q);
+    return randn4((unsigned long long)(base / 4 + q), P.seed, draw);
+}
+
+__global__ __launch_bounds__(256) void vlb_noise_kernel(VlbArgs P) {
+    const int b = blockIdx.y;
+    const int tb = vlb_level(P.t, b, P.T);
+    const float a = (float)P.tab[tb], s = (float)P.tab[P.T + tb];
+    const unsigned long long draw = P.draw + (P.step_dev ? *P.step_dev : 0ull);
+    const size_t base = (size_t)b * P.per_sample;
+    const long quads = P.per_sample / 4;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+        const float4 x4 = *reinterpret_cast<const float4*>(P.x + base + 4 * q);
+        const float4 n4 = vlb_eps4(P, base, q, draw);
+        *reinterpret_cast<float4*>(P.xt + base + 4 * q) =
+            make_float4((float)vlb_xt(a, s, x4.x, n4.x), (float)vlb_xt(a, s, x4.y, n4.y), (float)vlb_xt(a, s, x4.z, n4.z), (float)vlb_xt(a, s, x4.w, n4.w));
+    }
+}
+
+// Phi(z) of the standard normal, in double
+__device__ __forceinline__ double vlb_phi(double z) { return 0.5 * erfc(-z * 0.70710678118654752440); }
+
+// -log2 of the discretized Gaussian's mass on the bin of x0 (half-width 1/255); on the upper tail the difference is taken between
+// the two small complements
+__device__ double vlb_decoder_bits(double x0, double mu, double inv_sigma) {
+    const double zp = (x0 - mu + 1.0 / 255.0) * inv_sigma, zm = (x0 - mu - 1.0 / 255.0) * inv_sigma;
+    double p;
+    if (x0 < -0.999) p = vlb_phi(zp);
+    else if (x0 > 0.999) p = vlb_phi(-zm);
+    else p = zm > 0.0 ? vlb_phi(-zm) - vlb_phi(-zp) : vlb_phi(zp) - vlb_phi(zm);
+    return -log(fmax(p, 1e-12)) * 1.44269504088896340736;
+}
+
+// the three doubles of every thread -> one triple per workgroup, by a fixed-order tree in LDS (the scheme of loss_masked_partial_kernel)
+__device__ __forceinline__ void vlb_block_reduce(double (&red)[3][256], const double (&a)[3], double* __restrict__ partial, int b) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) red[k][threadIdx.x] = a[k];
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) partial[((size_t)b * kVlbBlocks + blockIdx.x) * 3 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+__global__ __launch_bounds__(256) void vlb_term_kernel(VlbArgs P) {
+    __shared__ double red[3][256];
+    const int b = blockIdx.y;
+    const int tb = vlb_level(P.t, b, P.T);
+    const double* tab = P.tab;
+    const float a = (float)tab[tb], s = (float)tab[P.T + tb];
+    const float kr = (float)tab[2 * P.T + tb], km = (float)tab[3 * P.T + tb];
+    const double c1 = tab[4 * P.T + tb], c2 = tab[5 * P.T + tb], w = tab[6 * P.T + tb];
+    const double inv_sigma = exp(-0.5 * tab[7 * P.T + tb]);
+    const unsigned long long draw = P.draw + (P.step_dev ? *P.step_dev : 0ull);
+    const long per = P.per_sample, fhw = P.per_sample / P.C, quads = P.per_sample / 4;
+    const size_t base = (size_t)b * per;
+    double acc[3] = {0.0, 0.0, 0.0};                                        // vb, mse, xstart_mse
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+        const long i = 4 * q;
+        const float4 x4 = *reinterpret_cast<const float4*>(P.x + base + i);
+        const float4 n4 = vlb_eps4(P, base, q, draw);
+        const float xv[4] = {x4.x, x4.y, x4.z, x4.w}, nv[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long e = i + k, c = e / fhw, r = e - c * fhw;                 // [C,F,H,W] -> channel-last [F,H,W,C]
+            const float ev = P.eps[base + r * P.C + c];
+            // x0, x_t (vlb_noise_kernel's expression: the network read its fp32 rounding) and x0_hat in double; at the low levels, where
+            // x0_hat - x0 is a difference of nearly equal numbers, fp32 here would be the whole error of xstart_mse
+            const double x0 = vlb_x0(xv[k]);
+            const double xt = vlb_xt(a, s, xv[k], nv[k]);
+            double xh = (double)kr * xt - (double)km * (double)ev;              // predict_start_from_noise
+            if (P.clip) xh = fmin(fmax(xh, -1.0), 1.0);
+            const double de = (double)ev - (double)nv[k], dx = xh - x0;
+            acc[1] += de * de;
+            acc[2] += dx * dx;
+            if (tb > 0) acc[0] += w * (dx * dx);
+            else acc[0] += vlb_decoder_bits(x0, c1 * xh + c2 * xt, inv_sigma);
+        }
+    }
+    vlb_block_reduce(red, acc, P.partial, b);
+}
+
+// the prior term's sum, KL(q(x_{T-1} | x0) || N(0, 1)) in bits, as the first entry of the workgroup's triple
+__global__ __launch_bounds__(256) void vlb_prior_kernel(const float* __restrict__ x, const double* __restrict__ tab, int T,
+                                                        double* __restrict__ partial, long per_sample) {
+    __shared__ double red[3][256];
+    const int b = blockIdx.y;
+    const double ac = tab[8 * T + T - 1];
+    const double k0 = -log1p(-ac) - ac;                                   // -1 - log(1 - ac) + (1 - ac), without the cancellation
+    const size_t base = (size_t)b * per_sample;
+    const long quads = per_sample / 4;
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+        const float4 x4 = *reinterpret_cast<const float4*>(x + base + 4 * q);
+        const float xv[4] = {x4.x, x4.y, x4.z, x4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double x0 = vlb_x0(xv[k]);
+            acc[0] += 0.5 * (k0 + ac * x0 * x0) * 1.44269504088896340736;
+        }
+    }
+    vlb_block_reduce(red, acc, partial, b);
+}
+
+// One workgroup, thread b = sample b: the sample's kVlbBlocks triples added in index order, / per_sample, the first nout of them to
+// out[(k * B + b) * nout ..] with k = *step_dev (or 0).  With seq (the loop): t[:] = max(seq[k + 1], 0) for the next forward and k += 1;
+// a step past the end of the sequence (k >= seq_len) writes nothing.
+__global__ __launch_bounds__(256) void vlb_advance_kernel(const double* __restrict__ partial, double* __restrict__ out, int nout, int B,
+                                                          long per_sample, int* t, const int* __restrict__ seq, int seq_len,
+                                                          unsigned long long* step_dev) {
+    const unsigned long long k = step_dev ? *step_dev : 0ull;
+    const bool live = !seq || k < (unsigned long long)seq_len;
+    if (live) {
+        const int tn = seq ? max(seq[k + 1], 0) : 0;
+        for (int b = threadIdx.x; b < B; b += blockDim.x) {
+            double a[3] = {0.0, 0.0, 0.0};
+            for (int i = 0; i < kVlbBlocks; ++i)
+                for (int j = 0; j < 3; ++j) a[j] += partial[((size_t)b * kVlbBlocks + i) * 3 + j];
+            for (int j = 0; j < nout; ++j) out[((size_t)k * B + b) * nout + j] = a[j] / (double)per_sample;
+            if (seq) t[b] = tn;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && seq && live) *step_dev = k + 1;
+}
+
 __global__ void affine_kernel(const float* __restrict__ x, float* __restrict__ y, long n, float a, float b) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = fmaf(x[i], a, b);
 }
@@ -789,6 +936,30 @@ hipError_t launch_cfg_combine(const float* eps2, float* out, float cond_scale, f
     }
     return LaunchScope(st, "cfg_combine_kernel", 0.0, 12.0 * B * per_sample, "B%d px%ld", B, per_sample)
         .launch(cfg_combine_kernel, dim3(ew_blocks(per_sample / 4), B), dim3(256), 0, eps2, out, cond_scale, factor, B, per_sample);
+}
+
+int vlb_blocks() { return kVlbBlocks; }
+
+hipError_t launch_vlb_noise(const VlbArgs& a, int B, hipStream_t st) {
+    return LaunchScope(st, "vlb_noise_kernel", 0.0, 8.0 * B * a.per_sample, "B%d px%ld %s", B, a.per_sample, a.noise ? "noise" : "philox")
+        .launch(vlb_noise_kernel, dim3(kVlbBlocks, B), dim3(256), 0, a);
+}
+
+hipError_t launch_vlb_terms(const VlbArgs& a, int B, hipStream_t st) {
+    return LaunchScope(st, "vlb_term_kernel", 0.0, 8.0 * B * a.per_sample, "B%d px%ld C%d %s clip%d", B, a.per_sample, a.C,
+                       a.noise ? "noise" : "philox", a.clip)
+        .launch(vlb_term_kernel, dim3(kVlbBlocks, B), dim3(256), 0, a);
+}
+
+hipError_t launch_vlb_prior(const float* x, const double* tab, int T, double* partial, int B, long per_sample, hipStream_t st) {
+    return LaunchScope(st, "vlb_prior_kernel", 0.0, 4.0 * B * per_sample, "B%d px%ld", B, per_sample)
+        .launch(vlb_prior_kernel, dim3(kVlbBlocks, B), dim3(256), 0, x, tab, T, partial, per_sample);
+}
+
+hipError_t launch_vlb_advance(const double* partial, double* out, int nout, int B, long per_sample, int* t, const int* seq, int seq_len,
+                              unsigned long long* step_dev, hipStream_t st) {
+    return LaunchScope(st, "vlb_advance_kernel", 0.0, 0.0, "B%d n%d", B, nout)
+        .launch(vlb_advance_kernel, dim3(1), dim3(256), 0, partial, out, nout, B, per_sample, t, seq, seq_len, step_dev);
 }
 
 hipError_t launch_affine(const float* x, float* y, long n, float a, float b, hipStream_t st) {

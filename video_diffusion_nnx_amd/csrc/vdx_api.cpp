@@ -8,7 +8,8 @@
 
 // Everything a sampling step can bake into its captured graph: what the eleven vdx_*_sample_loop* entry points fill in and sample_loop()
 // runs.  A field the entry does not have stays zero.
-enum { CHAIN_ANCESTRAL = 0, CHAIN_DDIM = 1, CHAIN_DPM = 2 };
+// (CHAIN_VLB tags the graph key of vdx_vlb_loop only: it never goes through sample_loop, whose slot arithmetic 3 * variant + chain takes 0..2)
+enum { CHAIN_ANCESTRAL = 0, CHAIN_DDIM = 1, CHAIN_DPM = 2, CHAIN_VLB = 3 };
 struct LoopArgs {
     int chain, masked, guided;                          // CHAIN_*; the masked (inpainting) step; classifier-free guidance over 2 * batch rows
     const float* params; const void* packed;
@@ -19,6 +20,7 @@ struct LoopArgs {
     float percentile; float* thres_buf;                 // dynamic threshold: percentile > 0 && clip_denoised
     const float* known; const unsigned char* mask; const float* mask_tables; int resample_steps;
     float cond_scale, rescale; double* cfg_scratch;
+    const float* vlb_x; const double* vlb_tables; double* vlb_partial; double* vlb_out;     // the evaluation loop (vdx_vlb_loop) alone
     void* workspace; size_t workspace_bytes; int batch;
 };
 
@@ -29,7 +31,7 @@ struct vdx_handle {
     // is zero-filled before the fields are assigned
     struct GraphKey { LoopArgs a; const void* stream; int act16; };
     // one cached graph per (chain, variant): slot = 3 * variant + chain with variant 0 = plain, 1 = masked, 2 = guided and chain 0 = the
-    // ancestral loop, 1 = DDIM, 2 = DPM-Solver++ -- no loop ever evicts another one's graph
+    // ancestral loop, 1 = DDIM, 2 = DPM-Solver++; slot 9 = the evaluation loop (vdx_vlb_loop) -- no loop ever evicts another one's graph
     // `last` = the stream the exec was last launched on: replays may still be running when the graph has to go
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key; hipStream_t last = nullptr;
@@ -39,7 +41,7 @@ struct vdx_handle {
             if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
             last = nullptr;
         }
-    } gs[9];
+    } gs[10];
     void drop_graphs() { for (GraphSlot& g : gs) g.drop(); }
     vdx::BwdState bwd;
     vdx::Comm comm;
@@ -1042,6 +1044,105 @@ int vdx_dpm_sample_loop_guided(vdx_handle* h, const float* params, const void* p
     set_guided(a, cond_scale, rescale, cfg_scratch);
     a.hist = hist; a.order = order;
     return sample_loop("dpm_sample_loop_guided", h, a, nsteps, use_graph, stream);
+}
+
+// ---- held-out evaluation (vdx.h: "Held-out evaluation"): the three single-step entries and the loop ----
+
+size_t vdx_vlb_scratch_doubles(int batch) { return batch > 0 ? (size_t)batch * vdx::vlb_blocks() * 3 : 0; }
+
+// what the entries share: the rules of the vlb kernels (who-prefixed, all VDX_ERR_INVALID)
+static int vlb_rules(const char* who, const void* x, const void* xt, const void* noise, const char* names16, const void* tables, const void* partial,
+                     const void* out, int timesteps, int batch, int channels, long per_sample) {
+    if (batch < 1 || channels < 1 || per_sample < 1) VDX_REFUSE(who, "batch, channels and per_sample must be >= 1");
+    if (timesteps < 2) VDX_REFUSE(who, "timesteps must be >= 2");
+    if (per_sample % 4 || per_sample % channels) VDX_REFUSE(who, "per_sample must be a multiple of 4 and of channels");
+    if ((uintptr_t)x % 16 || (uintptr_t)xt % 16 || (uintptr_t)noise % 16) { char r_[96]; snprintf(r_, sizeof(r_), "%s must be 16-byte aligned", names16); VDX_REFUSE(who, r_); }
+    if ((uintptr_t)tables % 8 || (uintptr_t)partial % 8 || (uintptr_t)out % 8) VDX_REFUSE(who, "vlb_tables / partial / out must be 8-byte aligned");
+    return VDX_OK;
+}
+
+static vdx::VlbArgs vlb_args(const float* x, const float* eps_hat, float* xt, const float* noise, const int* t, const double* tables, int timesteps,
+                             uint64_t seed, uint64_t draw, const uint64_t* step_dev, int clip, int channels, long per_sample, double* partial) {
+    vdx::VlbArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.eps = eps_hat; a.xt = xt; a.noise = noise; a.t = t; a.tab = tables; a.T = timesteps;
+    a.seed = seed; a.draw = draw; a.step_dev = reinterpret_cast<const unsigned long long*>(step_dev);
+    a.clip = clip ? 1 : 0; a.C = channels; a.per_sample = per_sample; a.partial = partial;
+    return a;
+}
+
+int vdx_vlb_noise(const float* x, float* xt, const int* t, const double* vlb_tables, int timesteps, const float* noise, uint64_t seed,
+                  uint64_t draw, const uint64_t* step_dev, int batch, long per_sample, void* stream) {
+    const char* who = "vlb_noise";
+    if (!x || !xt || !t || !vlb_tables) VDX_REFUSE(who, "null tensor");
+    if (int rc = vlb_rules(who, x, xt, noise, "x / xt / noise", vlb_tables, nullptr, nullptr, timesteps, batch, 1, per_sample)) return rc;
+    const vdx::VlbArgs a = vlb_args(x, nullptr, xt, noise, t, vlb_tables, timesteps, seed, draw, step_dev, 0, 1, per_sample, nullptr);
+    VDX_HIP(vdx::launch_vlb_noise(a, batch, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_vlb_terms(const float* x, const float* eps_hat, const int* t, const double* vlb_tables, int timesteps, const float* noise,
+                  uint64_t seed, uint64_t draw, const uint64_t* step_dev, int clip_denoised, double* partial, double* out, int batch,
+                  int channels, long per_sample, void* stream) {
+    const char* who = "vlb_terms";
+    if (!x || !eps_hat || !t || !vlb_tables || !partial || !out) VDX_REFUSE(who, "null tensor");
+    if (int rc = vlb_rules(who, x, nullptr, noise, "x / noise", vlb_tables, partial, out, timesteps, batch, channels, per_sample)) return rc;
+    const vdx::VlbArgs a = vlb_args(x, eps_hat, nullptr, noise, t, vlb_tables, timesteps, seed, draw, step_dev, clip_denoised, channels, per_sample, partial);
+    VDX_HIP(vdx::launch_vlb_terms(a, batch, (hipStream_t)stream));
+    VDX_HIP(vdx::launch_vlb_advance(partial, out, 3, batch, per_sample, nullptr, nullptr, 0, nullptr, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_vlb_prior(const float* x, const double* vlb_tables, int timesteps, double* partial, double* out, int batch, long per_sample,
+                  void* stream) {
+    const char* who = "vlb_prior";
+    if (!x || !vlb_tables || !partial || !out) VDX_REFUSE(who, "null tensor");
+    if (int rc = vlb_rules(who, x, nullptr, nullptr, "x", vlb_tables, partial, out, timesteps, batch, 1, per_sample)) return rc;
+    VDX_HIP(vdx::launch_vlb_prior(x, vlb_tables, timesteps, partial, batch, per_sample, (hipStream_t)stream));
+    VDX_HIP(vdx::launch_vlb_advance(partial, out, 1, batch, per_sample, nullptr, nullptr, 0, nullptr, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_vlb_loop(vdx_handle* h, const float* params, const void* packed, const float* x, float* xt_buf, float* eps_buf, int* t_dev,
+                 uint64_t* step_dev, const double* vlb_tables, int timesteps, const int* seq, int seq_len, int nsteps, const float* cond,
+                 uint64_t seed, int clip_denoised, double* partial, double* out, void* workspace, size_t workspace_bytes, int batch,
+                 int use_graph, void* stream) {
+    const char* who = "vlb_loop";
+    if (!h || !params || !packed || !x || !xt_buf || !eps_buf || !t_dev || !step_dev || !vlb_tables || !seq || !partial || !out || !workspace)
+        VDX_REFUSE(who, "null argument");
+    if (!h->model.d_ss_layers) { char msg_[96]; snprintf(msg_, sizeof(msg_), "%s: handle was created without a GPU", who); VDX_FAIL(VDX_ERR_STATE, msg_); }
+    const vdx::Model& m = h->model;
+    const int C = m.cfg.channels;
+    const long per_sample = (long)C * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
+    if (int rc = vlb_rules(who, x, xt_buf, eps_buf, "x / xt_buf / eps_buf", vlb_tables, partial, out, timesteps, batch, C, per_sample)) return rc;
+    if (m.out_dim != C) VDX_REFUSE(who, "out_dim must equal channels");
+    if (seq_len < 1) VDX_REFUSE(who, "seq_len must be >= 1");
+    if (nsteps < 0 || nsteps > seq_len) VDX_REFUSE(who, "nsteps out of range");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* sd = reinterpret_cast<unsigned long long*>(step_dev);
+    const vdx::VlbArgs na = vlb_args(x, nullptr, xt_buf, nullptr, t_dev, vlb_tables, timesteps, seed, 1, step_dev, 0, C, per_sample, nullptr);
+    const vdx::VlbArgs ta = vlb_args(x, eps_buf, nullptr, nullptr, t_dev, vlb_tables, timesteps, seed, 1, step_dev, clip_denoised, C, per_sample, partial);
+    auto step = [&]() -> int {
+        hipError_t e = vdx::launch_vlb_noise(na, batch, st);
+        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        // cond is used un-masked, as in the unguided sampling loops
+        int rc = vdx::model_forward(&m, params, packed, xt_buf, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
+        if (rc != VDX_OK) return rc;
+        e = vdx::launch_vlb_terms(ta, batch, st);
+        if (e == hipSuccess) e = vdx::launch_vlb_advance(partial, out, 3, batch, per_sample, t_dev, seq, seq_len, sd, st);
+        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        return VDX_OK;
+    };
+    // the key, built like the sampling loops': a zero-filled LoopArgs with every field this step reads
+    vdx_handle::GraphKey key;
+    memset(&key, 0, sizeof(key));
+    LoopArgs& k = key.a;
+    k.chain = CHAIN_VLB; k.params = params; k.packed = packed; k.img = xt_buf; k.eps_buf = eps_buf; k.t_dev = t_dev; k.step_dev = step_dev;
+    k.timesteps = timesteps; k.seq = seq; k.seq_len = seq_len; k.cond = cond; k.seed = seed; k.clip_denoised = clip_denoised ? 1 : 0;
+    k.vlb_x = x; k.vlb_tables = vlb_tables; k.vlb_partial = partial; k.vlb_out = out;
+    k.workspace = workspace; k.workspace_bytes = workspace_bytes; k.batch = batch;
+    key.stream = stream; key.act16 = m.act16;
+    return run_steps(h, 9, key, nsteps, use_graph, st, step);
 }
 
 int vdx_pack_conv_weights_t(int mode, const float* kernel, void* packed, int taps, int cin, int cout, void* stream) {

@@ -238,6 +238,25 @@ unsigned char* cfg_scratch_mask(double* scratch, int B);
 hipError_t launch_cfg_mask(double* scratch, int B, hipStream_t st);
 hipError_t launch_cfg_combine(const float* eps2, float* out, float cond_scale, float rescale, double* scratch, int B, long per_sample,
                               hipStream_t st);
+// Held-out evaluation (variational bound in bits/dim; vdx.h: "Held-out evaluation").  x [B,C,F,H,W] in [0, 1]; tab [VDX_VLB_ROWS][T]
+// doubles; draw index = draw + *step_dev.  launch_vlb_noise writes xt (the double x_t rounded to fp32 once); launch_vlb_terms forms the same double again and leaves one
+// (vb, mse, xstart_mse) triple per workgroup in partial [B][vlb_blocks()][3]; launch_vlb_prior leaves (prior, 0, 0) there;
+// launch_vlb_advance adds the partials in index order into out[(k * B + b) * nout ..] (k = *step_dev, or 0) and, with seq, sets
+// t[:] = max(seq[k + 1], 0) and k += 1 (nothing is written once k >= seq_len).
+struct VlbArgs {
+    const float* x; const float* eps; float* xt;        // eps channel-last [B,F,H,W,C] (terms); xt [B,C,F,H,W] (noise)
+    const float* noise;                                 // explicit eps [B,C,F,H,W], or null -> Philox(seed, draw + *step_dev)
+    const int* t; const double* tab; int T;
+    unsigned long long seed, draw; const unsigned long long* step_dev;
+    int clip; int C; long per_sample;
+    double* partial;
+};
+int vlb_blocks();
+hipError_t launch_vlb_noise(const VlbArgs& a, int B, hipStream_t st);
+hipError_t launch_vlb_terms(const VlbArgs& a, int B, hipStream_t st);
+hipError_t launch_vlb_prior(const float* x, const double* tab, int T, double* partial, int B, long per_sample, hipStream_t st);
+hipError_t launch_vlb_advance(const double* partial, double* out, int nout, int B, long per_sample, int* t, const int* seq, int seq_len,
+                              unsigned long long* step_dev, hipStream_t st);
 // frame-conditioned training (mask [B,C,F,H,W] bytes, nonzero = clean context): masked q_sample, the deterministic (sum, count) of the
 // loss over the mask-0 elements (scratch: loss_masked_scratch_doubles()), and its gradient with the count read from the device
 hipError_t launch_q_sample_masked(const float* x0, const int* t, const float* noise, const unsigned char* mask, float* out, const float* sqrt_ac,

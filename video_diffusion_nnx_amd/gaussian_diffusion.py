@@ -163,6 +163,34 @@ def make_tables(timesteps: int) -> dict:
     return {k: v.astype(np.float32) for k, v in t.items()}
 
 
+VLB_ROWS = L.VLB_ROWS
+
+
+def make_vlb_tables(timesteps: int) -> np.ndarray:
+    """The [VLB_ROWS, T] float64 table of the evaluation kernels (vdx.h: "Held-out evaluation").  Rows 0-5 and 8 are make_tables' fp32
+    values, widened: the numbers the sampling kernels use, so the bound is that of the model that samples.  Row 6, w_t = coef1_t^2 /
+    (2 post_var_t ln 2), and row 7, the decoder's log-variance log post_var_max(t, 1), are formed from them in float64; w_0 = 0 (level
+    0 is the decoder term)."""
+    if int(timesteps) < 2:
+        raise ValueError(f'the variational bound needs timesteps >= 2, got {timesteps}')
+    tabs = {k: v.astype(np.float64) for k, v in make_tables(int(timesteps)).items()}
+    pv, c1 = tabs['posterior_variance'], tabs['posterior_mean_coef1']
+    w = np.zeros_like(pv)
+    w[1:] = c1[1:] ** 2 / (2.0 * pv[1:] * np.log(2.0))
+    dec = np.log(np.concatenate([pv[1:2], pv[1:]]))
+    return np.ascontiguousarray(np.stack([tabs['sqrt_alphas_cumprod'], tabs['sqrt_one_minus_alphas_cumprod'], tabs['sqrt_recip_alphas_cumprod'],
+                                          tabs['sqrt_recipm1_alphas_cumprod'], c1, tabs['posterior_mean_coef2'], w, dec, tabs['alphas_cumprod']]))
+
+
+def vlb_time_sequence(timesteps: int, steps=None) -> np.ndarray:
+    """The levels calc_bpd_loop visits, then -1: every level T-1 .. 0 (steps None) or the ddim_time_sequence(T, steps) ones."""
+    if steps is None:
+        return np.ascontiguousarray(np.arange(int(timesteps) - 1, -2, -1, dtype=np.int32))
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= int(steps) <= int(timesteps):
+        raise ValueError(f'timesteps must be None or an int in [1, {int(timesteps)}], got {steps!r}')
+    return ddim_time_sequence(int(timesteps), int(steps))
+
+
 def split_key(key: int, num: int = 2):
     """Deterministic seed derivation standing in for jax.random.split (splitmix64 of (key, index))."""
     out = []
@@ -480,6 +508,56 @@ class GaussianDiffusion:
         with self._sampling(focus_present, int(shape[0])):
             return self._run_chain('dpm', int(shape[0]), key, steps=int(steps), order=order, cond=cond, cond_scale=cond_scale,
                                    guidance_rescale=guidance_rescale, use_graph=use_graph, x_T=x_T)
+
+    def calc_bpd_loop(self, x, key, *, cond=None, clip_denoised: bool = True, timesteps: Optional[int] = None, use_graph: bool = True,
+                      focus_present=None):
+        """The variational bound of held-out videos x [B,C,F,H,W] in [0, 1] in bits per dimension, term by term (EXTENSION, no reference
+        code: Ho et al. 2020, eq. 5; Nichol & Dhariwal 2021, calc_bpd_loop; the math is vdx.h's "Held-out evaluation").  One network
+        evaluation per level inside a captured step (vdx_vlb_loop), the noise of step k = Philox(key, draw 1 + k), the per-sample sums
+        deterministic.  timesteps None: all T levels, T-1 .. 0; an int S: the ddim_time_sequence(T, S) levels, a cheap per-t curve.
+        cond is used un-masked, as the unguided sampling loops use it.  Returns CPU float64 tensors: vb, mse, xstart_mse [B,S] (column
+        k = level t[k]), t [S], prior_bpd [B] and total_bpd [B] = prior_bpd + sum_t vb, None unless every level was visited.
+        The model's variance is the posterior variance p_sample uses; the dynamic threshold has no place in the bound."""
+        return self._bpd_chain(x, key, cond, clip_denoised, timesteps, use_graph, focus_present, None)
+
+    def _bpd_chain(self, x, key, cond, clip_denoised, timesteps, use_graph, focus_present, pieces):
+        """calc_bpd_loop; pieces: the step counts of the vdx_vlb_loop calls the chain is issued in (None: one call over all of it)."""
+        if self.use_dynamic_thres:
+            raise ValueError('calc_bpd_loop evaluates the statically clipped x0 only: a diffusion with use_dynamic_thres is not supported')
+        unet, T, dev = self.denoise_fn, self.num_timesteps, self.device
+        seq_host = vlb_time_sequence(T, timesteps)
+        S = len(seq_host) - 1
+        x = torch.as_tensor(x)
+        shape = (self.channels, self.num_frames, self.image_size, self.image_size)
+        if x.dim() != 5 or tuple(x.shape[1:]) != shape:
+            raise ValueError(f'x must be [B, {shape[0]}, {shape[1]}, {shape[2]}, {shape[3]}], got {tuple(x.shape)}')
+        from . import ops
+        B, seed = x.shape[0], int(key) & 0xFFFFFFFFFFFFFFFF
+        tab = torch.from_numpy(make_vlb_tables(T)).to(dev)
+        with self._sampling(focus_present, B):
+            xd = self._dev(x)
+            condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
+            prior = ops.vlb_prior(xd, tab)
+            xt = torch.empty_like(xd)
+            eps = torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=dev)
+            t_dev = torch.full((B,), int(seq_host[0]), dtype=torch.int32, device=dev)
+            step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+            seq = torch.from_numpy(seq_host).to(dev)
+            partial = torch.empty(L.vdx_vlb_scratch_doubles(B), dtype=torch.float64, device=dev)
+            out = torch.empty(S, B, 3, dtype=torch.float64, device=dev)
+            h = unet.handle(self.num_frames, self.image_size)
+            unet.apply_activation_storage(h)
+            ws = unet.workspace(B, self.num_frames, self.image_size)
+            for n in (pieces or (S,)):
+                L.check(L.vdx_vlb_loop(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(xd), L.ptr(xt), L.ptr(eps), L.ptr(t_dev),
+                                       L.ptr(step_dev), L.ptr(tab), T, L.ptr(seq), S, int(n), L.ptr(condd), seed, int(bool(clip_denoised)),
+                                       L.ptr(partial), L.ptr(out), L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
+            res = out.cpu()
+            prior = prior.cpu()
+        vb = res[:, :, 0].t().contiguous()
+        return dict(vb=vb, mse=res[:, :, 1].t().contiguous(), xstart_mse=res[:, :, 2].t().contiguous(),
+                    t=torch.from_numpy(seq_host[:-1].astype(np.int64)), prior_bpd=prior,
+                    total_bpd=prior + vb.sum(1) if S == T else None)
 
     @staticmethod
     def _shard(key, batch, *tensors):

@@ -771,3 +771,48 @@ def adam_ema_step_clip(p, g, m, v, ema, sqnorm, max_grad_norm, *, lr, b1, b2, ep
     L.check(_adam_ema_clip(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), L.ptr(ema), p.numel(), lr, b1, b2, eps, step_count, grad_scale, int(bool(do_ema)),
                            ema_decay, L.ptr(sqnorm), max_grad_norm, L.ptr(norm), L.stream_ptr()))
     return norm
+
+
+# held-out evaluation (vdx.h: "Held-out evaluation"): tables = GaussianDiffusion's make_vlb_tables(T) as a [VLB_ROWS, T] float64 device tensor
+_u64 = C.c_uint64
+VLB_ROWS = L.VLB_ROWS
+_vlb_scratch = L._sig('vdx_vlb_scratch_doubles', C.c_size_t, [C.c_int])
+_vlb_noise = L._sig('vdx_vlb_noise', C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, _u64, _u64, C.c_void_p, C.c_int, C.c_long, C.c_void_p])
+_vlb_terms = L._sig('vdx_vlb_terms', C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p, _u64, _u64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_long, C.c_void_p])
+_vlb_prior = L._sig('vdx_vlb_prior', C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_void_p])
+
+
+def _vlb_check(x, tables):
+    assert x.dtype == torch.float32 and x.dim() == 5 and tables.dtype == torch.float64 and tables.shape[0] == VLB_ROWS
+    return x.shape[0], x.numel() // x.shape[0], tables.shape[1]
+
+
+def vlb_noise(x, t, tables, *, noise=None, seed=0, draw=0, step_dev=None):
+    """x [B,C,F,H,W] in [0, 1], t int32 [B] -> x_t = sqrt_ac[t] (2 x - 1) + sqrt(1 - ac[t]) eps with eps = `noise` or the Philox draw
+    `draw` (+ *step_dev) of `seed`."""
+    B, per, T = _vlb_check(x, tables)
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    L.check(_vlb_noise(L.ptr(x), L.ptr(out), L.ptr(t), L.ptr(tables), T, L.ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw), L.ptr(step_dev),
+                       B, per, L.stream_ptr()))
+    return out
+
+
+def vlb_terms(x, eps_hat, t, tables, *, noise=None, seed=0, draw=0, step_dev=None, clip=True):
+    """x [B,C,F,H,W] in [0, 1], eps_hat channel-last [B,F,H,W,C], t int32 [B] -> float64 [B, 3] = (vb, mse, xstart_mse) per sample in
+    bits/dim (vb) and per element (the two MSEs), with the noise of vlb_noise."""
+    B, per, T = _vlb_check(x, tables)
+    partial = torch.empty(_vlb_scratch(B), dtype=torch.float64, device=x.device)
+    out = torch.empty(B, 3, dtype=torch.float64, device=x.device)
+    L.check(_vlb_terms(L.ptr(x), L.ptr(eps_hat), L.ptr(t), L.ptr(tables), T, L.ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw), L.ptr(step_dev),
+                       int(bool(clip)), L.ptr(partial), L.ptr(out), B, x.shape[1], per, L.stream_ptr()))
+    return out
+
+
+def vlb_prior(x, tables):
+    """x [B,C,F,H,W] in [0, 1] -> float64 [B]: KL(q(x_{T-1} | x0) || N(0, 1)) in bits/dim."""
+    B, per, T = _vlb_check(x, tables)
+    partial = torch.empty(_vlb_scratch(B), dtype=torch.float64, device=x.device)
+    out = torch.empty(B, dtype=torch.float64, device=x.device)
+    L.check(_vlb_prior(L.ptr(x), L.ptr(tables), T, L.ptr(partial), L.ptr(out), B, per, L.stream_ptr()))
+    return out
