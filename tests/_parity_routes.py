@@ -18,7 +18,8 @@ here by hand; the label in their row carries channels and frame sizes, so a test
     VDX_LIB=/path/to/libvdx.so python tests/_parity_routes.py > tests/golden/parity_routes.json
 
 records {case id: [status, [[kernel, label], ...]]} without a device, like the other two tables.  The backward (backward_routes.json)
-can be added as a second pair network_forms / parity_calls over tests/_bwd_route_cases.py; form() and closure() do not care."""
+has its own pair network_forms / parity_calls over tests/_bwd_route_cases.py in tests/_bwd_parity_routes.py, which reuses the word
+splitting, cid and form_str of this file."""
 import contextlib
 import json
 import os

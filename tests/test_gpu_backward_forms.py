@@ -6,7 +6,12 @@ Every input is made bf16-representable on the host before it goes to either side
 References are fp64 torch.autograd through oracle/unet3d_ref.py (the attention cores: the fp64 closed forms of tests/_parity.py, which
 tests/test_host_parity_helpers.py pins to autograd).  Every bound comes from the reference side and is printed next to the measured
 value (run with -s); tests/_parity.py says where each number comes from, tests/test_host_parity_helpers.py shows on the CPU that a
-dropped patch row, a dropped slot, a misplaced column block, a truncating store and an unwritten sequence are rejected at these bounds."""
+dropped patch row, a dropped slot, a misplaced column block, a truncating store and an unwritten sequence are rejected at these bounds.
+
+Every call of a kernel under test runs under BR.bound(case id) (tests/_bwd_parity_routes.py): its first launch is the one recorded for
+that case on the CPU (tests/golden/bwd_parity_routes.json) and the launches behind it are tail_forms of that first launch, so a case
+cannot drift to another kernel form unnoticed, and tests/test_host_bwd_parity_routes.py holds that every form the reverse pass of the
+networks routes to has a case here or in the three sibling files."""
 import functools
 
 import pytest
@@ -14,6 +19,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import _bwd_parity_routes as BR
 import _parity as P
 from _launch_hook import assert_launches, launches, nan_outputs
 from oracle import train_ref as TR
@@ -49,6 +55,12 @@ WG_CASES = {
     'ragged_20x24': (1, 3, 20, 24, 24, 0, 40, 3, 1, 0, False, 0),
     'ragged_9x17': (1, 3, 9, 17, 24, 0, 40, 3, 1, 0, False, 0),
     'ragged_9x17_pro': (2, 3, 9, 17, 24, 0, 40, 3, 1, 0, True, 0),
+    # W < 16 with the prologue (conv2 of every block at 8 x 8 frames): 8 x 8 patches, two 64-channel tiles each way; and ragged: H, W no multiple of 8
+    'l3_128_pro': (2, 3, 8, 8, 128, 0, 128, 3, 1, 0, True, 0),
+    'ragged_7x9_pro': (2, 3, 7, 9, 24, 0, 40, 3, 1, 0, True, 0),
+    # W < 16 over a two-pointer concat (conv1 of the first up block): unequal halves, so a wrong pointer switch moves a tile boundary
+    'l3_concat_128_64': (1, 4, 8, 8, 128, 64, 64, 3, 1, 0, False, 0),
+    'ragged_7x9_concat': (1, 3, 7, 9, 24, 16, 40, 3, 1, 0, False, 0),
     'down_64': (1, 4, 64, 64, 64, 0, 64, 4, 2, 0, False, 0),
     'up_64': (1, 4, 32, 32, 64, 0, 64, 4, 1, 1, False, 0),
     'down_128': (1, 8, 16, 16, 128, 0, 128, 4, 2, 0, False, 0),
@@ -167,19 +179,24 @@ def test_wgrad_bf16_tensors_split_bias_slots(name, x16, dy16, slots):
     got = {}
     for label, scr in (('atomics', None), ('slots', slots), ('slots too small', tiny)):
         what = f'wgrad {name} x16={int(x16)} dy16={int(dy16)} {label}'
-        dw, db = _run_wgrad(name, c, x16, dy16, scr, bias=True)
+        with BR.bound(BR.cid('wg16', name, x16, dy16, label), db=True):
+            dw, db = _run_wgrad(name, c, x16, dy16, scr, bias=True)
         P.assert_exact_products(dw, c['ref'], c['bound'], c['sl'], c['sb'], P._view3, what)
         # bias sums: exact products with 1 (no prologue on dy), fp32 accumulate: the stated weight-gradient figure
         P.assert_exact_products(db, c['refb'], P.WGRAD_STATED, what=what + ' db')
         got[label] = (dw, db)
-    dw2, db2 = _run_wgrad(name, c, x16, dy16, slots, bias=True)
+    with BR.bound(BR.cid('wg16', name, x16, dy16, 'slots'), db=True):
+        dw2, db2 = _run_wgrad(name, c, x16, dy16, slots, bias=True)
     assert torch.equal(dw2, got['slots'][0]) and torch.equal(db2, got['slots'][1]), f'{name}: two runs with slots are not bit-identical'
     r = P.rel(got['slots'][0], got['atomics'][0])
     print(f'[wgrad {name}] slots vs atomics rel {r:.3e} (bound {c["bound"]:.3e})')
     assert r < c['bound']
 
 
-@pytest.mark.parametrize('name', ['ragged_20x24', 'ragged_9x17_pro', 'down_128', 'up_128', 'qkv_64_768_ragged', 'rc_128_128_256'])
+WG32_NAMES = ['ragged_20x24', 'ragged_9x17_pro', 'down_128', 'up_128', 'qkv_64_768_ragged', 'rc_128_128_256', 'ragged_7x9_concat']
+
+
+@pytest.mark.parametrize('name', WG32_NAMES)
 def test_wgrad_f32_operands_split_bias_slots(name, slots):
     """The exact-f32 kernel with the same epilogues (what an f32-mode handle's backward launches): fp32 tensors only."""
     c = _wg_case(name)
@@ -192,15 +209,26 @@ def test_wgrad_f32_operands_split_bias_slots(name, slots):
         B, Fr, H, W, c0, c1, cout, k, stride, kind, _, split = WG_CASES[name]
         ref = _conv_wgrad_ref(_prologue(c['x0'], gamma, beta, ss, F64), c['dy'].double(), k, stride, kind)
     for label, scr in (('atomics', None), ('slots', slots)):
-        dw, db = _run_wgrad(name, c, False, False, scr, bias=True, bf16_operands=False)
+        with BR.bound(BR.cid('wg32', name, True, label), db=True):
+            dw, db = _run_wgrad(name, c, False, False, scr, bias=True, bf16_operands=False)
         P.assert_exact_products(dw, ref, bound, c['sl'], None, P._view3, f'wgrad f32 {name} {label}')
         P.assert_exact_products(db, c['refb'], P.WGRAD_STATED, what=f'wgrad f32 {name} {label} db')
-    dw2, db2 = _run_wgrad(name, c, False, False, slots, bias=True, bf16_operands=False)
+    with BR.bound(BR.cid('wg32', name, True, 'slots'), db=True):
+        dw2, db2 = _run_wgrad(name, c, False, False, slots, bias=True, bf16_operands=False)
     assert torch.equal(dw2, dw) and torch.equal(db2, db)
+    # without the bias sums (the SLA projections' launch: slots, no +db)
+    with BR.bound(BR.cid('wg32', name, False, 'slots'), db=False):
+        dw3, db3 = _run_wgrad(name, c, False, False, slots, bias=False, bf16_operands=False)
+    assert db3 is None
+    P.assert_exact_products(dw3, ref, bound, c['sl'], None, P._view3, f'wgrad f32 {name} slots, no bias sums')
 
 
-@pytest.mark.parametrize('nslots', [1, 7, 31, 32, 40, 257])
-@pytest.mark.parametrize('E,cout,split', [(1, 0, 0), (15, 0, 0), (17, 0, 0), (1000, 0, 0), (4099, 0, 0), (3 * 768, 768, 256), (5 * 128, 128, 64)])
+SLOT_COUNTS = [1, 7, 31, 32, 40, 257]
+SLOT_SHAPES = [(1, 0, 0), (15, 0, 0), (17, 0, 0), (1000, 0, 0), (4099, 0, 0), (3 * 768, 768, 256), (5 * 128, 128, 64)]
+
+
+@pytest.mark.parametrize('nslots', SLOT_COUNTS)
+@pytest.mark.parametrize('E,cout,split', SLOT_SHAPES)
 def test_slot_sum_fixed_order_pass(nslots, E, cout, split):
     """Slots filled with a known integer pattern (tests/_parity.py slot_pattern): a dropped slot or a ragged tail is an exact mismatch.
     nslots >= 32 runs slot_sum16_kernel, fewer slot_sum_kernel; the destination is accumulated into (pre-filled with 5)."""
@@ -209,7 +237,9 @@ def test_slot_sum_fixed_order_pass(nslots, E, cout, split):
     part, exp = P.slot_pattern(nslots, E, stride)
     nb = cout // split if split else 1
     dsts = [torch.full((E // nb,), 5.0, dtype=F32, device=DEV) for _ in range(nb)]
-    ops.slot_sum(part.to(DEV), nslots, stride, E, dsts, cout, split)
+    part = part.to(DEV)
+    with BR.bound(BR.cid('slot_sum', nslots, E, cout, split)):
+        ops.slot_sum(part, nslots, stride, E, dsts, cout, split)
     torch.cuda.synchronize()
     want = P.split_columns(exp, cout, split) if split else [exp]
     for i in range(nb):
@@ -221,7 +251,8 @@ def test_slot_sum_fixed_order_pass(nslots, E, cout, split):
 NORM_CASES = [(16, 2, (3, 5, 5), True, False), (64, 2, (4, 8, 8), True, False), (64, 1, (2, 8, 8), False, True),
               (256, 2, (2, 4, 4), False, True), (512, 1, (2, 2, 2), True, False), (1024, 1, (2, 2, 2), False, True),
               (24, 1, (2, 3, 3), False, True),
-              (64, 2, (16, 64, 64), True, False), (64, 2, (16, 64, 64), False, True), (128, 2, (16, 32, 32), True, True)]
+              (64, 2, (16, 64, 64), True, False), (64, 2, (16, 64, 64), False, True), (128, 2, (16, 32, 32), True, True),
+              (512, 2, (2, 4, 4), False, True)]           # two values per lane with the tail branch (the 512-channel blocks)
 # The fp32-tensor twin of the kernel is held to 3e-5 of the fp64 reference (tests/test_gpu_conv_backward.py::test_norm_act_backward).
 # The bf16-tensor form computes the same fp32 values from bf16-representable inputs and rounds dy once, so 3e-5 is the error that may
 # move a value across a bf16 rounding boundary (fp32_floor of assert_bf16_store), and the bound of every fp32 output.
@@ -260,8 +291,9 @@ def test_norm_act_backward_bf16_tensors(C, B, shape, use_ss, tail):
     runs = {}
     for det in (False, True):
         for rep in range(2 if det else 1):
-            res = ops.norm_act_backward_ex(_dev(dout32), _dev(y32, BF), stats, _dev(gamma32), _dev(beta32), 8, scale_shift=_dev(ss32),
-                                           r=_dev(r32, BF), ln_gamma=_dev(lg32), dy_bf16=True, deterministic=det)
+            with BR.bound(BR.cid('norm16', (C, B, shape, use_ss, tail), f'dgp {int(det)}')):
+                res = ops.norm_act_backward_ex(_dev(dout32), _dev(y32, BF), stats, _dev(gamma32), _dev(beta32), 8, scale_shift=_dev(ss32),
+                                               r=_dev(r32, BF), ln_gamma=_dev(lg32), dy_bf16=True, deterministic=det)
             torch.cuda.synchronize()
             res = {k: v.cpu() for k, v in res.items() if v is not None}
             what = f'norm C={C} B={B} {shape} ss={int(use_ss)} tail={int(tail)} dgp={int(det)}'
@@ -276,8 +308,9 @@ def test_norm_act_backward_bf16_tensors(C, B, shape, use_ss, tail):
     for k in runs[(True, 0)]:
         assert torch.equal(runs[(True, 0)][k], runs[(True, 1)][k]), f'{k}: two runs with dgp are not bit-identical'
     # fp32 dy from bf16 y / r (the storage-only combination): the twin's bound, per sample as well
-    res = ops.norm_act_backward_ex(_dev(dout32), _dev(y32, BF), stats, _dev(gamma32), _dev(beta32), 8, scale_shift=_dev(ss32),
-                                   r=_dev(r32, BF), ln_gamma=_dev(lg32), dy_bf16=False, deterministic=True)
+    with BR.bound(BR.cid('norm16', (C, B, shape, use_ss, tail), 'fp32 dy')):
+        res = ops.norm_act_backward_ex(_dev(dout32), _dev(y32, BF), stats, _dev(gamma32), _dev(beta32), 8, scale_shift=_dev(ss32),
+                                       r=_dev(r32, BF), ln_gamma=_dev(lg32), dy_bf16=False, deterministic=True)
     P.assert_exact_products(res['dy'].cpu(), ref['dy'], NORM_FP32, P.sample_slices(ref['dy'].shape), what=f'norm C={C} {shape} fp32 dy from bf16 y')
     if tail:
         P.assert_exact_products(res['dr'].cpu(), ref['dr'], NORM_FP32, P.sample_slices(ref['dr'].shape), what=f'norm C={C} {shape} dr from bf16 r')
@@ -324,7 +357,8 @@ def test_attention_core_backward_interleaved(B, Fr, H, W, heads, temporal, io16)
     else:
         tol = gb_o = gb_g = 2e-5                     # longer sequences run the exact fp32 kernel: the twin's figure, per sequence too
     for pad in (0, PAD):
-        o, dqkv = ops.attention_core_backward_io(_dev(qkv, dt), _dev(d_o, dt), B, Fr, H, W, heads, temporal, sentinel=SENTINEL, pad_cols=pad)
+        with BR.bound(BR.cid('core io', (B, Fr, H, W, heads, temporal), io16, pad)):
+            o, dqkv = ops.attention_core_backward_io(_dev(qkv, dt), _dev(d_o, dt), B, Fr, H, W, heads, temporal, sentinel=SENTINEL, pad_cols=pad)
         torch.cuda.synchronize()
         o, dqkv = o.cpu().double(), dqkv.cpu().double()
         what = f'attn core {(B, Fr, H, W, heads, temporal)} io16={int(io16)} pad={pad}'
@@ -339,8 +373,11 @@ def test_attention_core_backward_interleaved(B, Fr, H, W, heads, temporal, io16)
         P.assert_groups(_seqs(dqkv, B, Fr, HW, temporal), _seqs(g_ref, B, Fr, HW, temporal), groups, gb_g, what + ' dqkv per sequence')
 
 
+FUSED_CASES = [(1, 16, 4, 4), (2, 5, 3, 3), (1, 16, 16, 16), (1, 16, 64, 64), (2, 10, 24, 22), (1, 10, 5, 7)]
+
+
 @pytest.mark.parametrize('x16', [True, False])
-@pytest.mark.parametrize('B,Fr,H,W', [(1, 16, 4, 4), (2, 5, 3, 3), (1, 16, 16, 16), (1, 16, 64, 64), (2, 10, 24, 22), (1, 10, 5, 7)])
+@pytest.mark.parametrize('B,Fr,H,W', FUSED_CASES)
 def test_temporal_attention_backward_fused_bf16_input(B, Fr, H, W, x16):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(100 + B + Fr + H)
@@ -353,7 +390,8 @@ def test_temporal_attention_backward_fused_bf16_input(B, Fr, H, W, x16):
     dx_em, o_em, g_em = P.fused_attention(x, dy, wqkv, bqkv, wo, B, Fr, HW, emulate=True)
     dyr = dy.double().reshape(-1, 64)
     sq = lambda t: _seqs(t, B, Fr, HW, True)
-    dx, o, dqkv = ops.temporal_attention_backward_fused_ex(_dev(x, BF if x16 else F32), _dev(dy), _dev(wqkv), _dev(bqkv), _dev(wo))
+    with BR.bound(BR.cid('fused ex', (B, Fr, H, W), x16)):
+        dx, o, dqkv = ops.temporal_attention_backward_fused_ex(_dev(x, BF if x16 else F32), _dev(dy), _dev(wqkv), _dev(bqkv), _dev(wo))
     torch.cuda.synchronize()
     dx, o, dqkv = dx.cpu().double().reshape(-1, 64), o.float().cpu().double(), dqkv.float().cpu().double()
     what = f'fused attention {(B, Fr, H, W)} x16={int(x16)}'
@@ -364,8 +402,11 @@ def test_temporal_attention_backward_fused_bf16_input(B, Fr, H, W, x16):
         P.assert_groups(sq(got), sq(ref), (B, HW), P.group_bound(sq(em), sq(ref), (B, HW)), f'{what} {nm} per sequence')
 
 
+SLA_CASES = [(2, 8, 8), (3, 5, 7), (1, 20, 20), (2, 64, 64)]      # N = 35: ragged tiles; N = 4096: the level-0 frame
+
+
 @pytest.mark.parametrize('io16', [True, False])
-@pytest.mark.parametrize('NF,H,W', [(2, 8, 8), (3, 5, 7), (1, 20, 20), (2, 64, 64)])      # N = 35: ragged tiles; N = 4096: the level-0 frame
+@pytest.mark.parametrize('NF,H,W', SLA_CASES)
 def test_sla_core_backward_interleaved(NF, H, W, io16):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(NF + H)
@@ -377,7 +418,8 @@ def test_sla_core_backward_interleaved(NF, H, W, io16):
     fh = lambda t: t.reshape(NF, N, -1, 8, 32).permute(0, 3, 1, 2, 4)        # (frame, head) groups
     dt = BF if io16 else F32
     for pad in (0, PAD):
-        o, dqkv = ops.sla_core_backward_io(_dev(q, dt), _dev(k, dt), _dev(v, dt), _dev(d_out, dt), NF, N, sentinel=SENTINEL, pad_cols=pad)
+        with BR.bound(BR.cid('sla io', (NF, H, W), io16, pad)):
+            o, dqkv = ops.sla_core_backward_io(_dev(q, dt), _dev(k, dt), _dev(v, dt), _dev(d_out, dt), NF, N, sentinel=SENTINEL, pad_cols=pad)
         torch.cuda.synchronize()
         o, dqkv = o.cpu().double(), dqkv.cpu().double()
         what = f'sla core NF={NF} N={N} io16={int(io16)} pad={pad}'
@@ -397,10 +439,15 @@ def test_sla_core_backward_interleaved(NF, H, W, io16):
 # ---- data gradient through a row slice of the transposed packing ----------------------------------------------------------------------
 
 
-@pytest.mark.parametrize('mode,dy16', [('f32', False), ('bf16', False), ('bf16', True), ('f16', False)])
-@pytest.mark.parametrize('k,B,Fr,H,W,cin,cout', [(3, 1, 16, 64, 64, 128, 64),       # ups level 0 block1 (concat 64 | 64): the persistent 64-channel kernel
-                                                 (1, 1, 16, 16, 16, 512, 256),      # res_conv of a wide level (256 | 256)
-                                                 (3, 1, 3, 9, 17, 48, 40)])         # generic kernel, ragged
+DGRAD_MODES = [('f32', False), ('bf16', False), ('bf16', True), ('f16', False)]
+DGRAD_CASES = [(3, 1, 16, 64, 64, 128, 64),       # ups level 0 block1 (concat 64 | 64): the persistent 64-channel kernel
+               (1, 1, 16, 16, 16, 512, 256),      # res_conv of a wide level (256 | 256)
+               (3, 1, 3, 9, 17, 48, 40),          # generic kernel, ragged
+               (3, 1, 2, 9, 17, 256, 128)]        # two row slices of 128: the 128-column tile of the generic kernel with +res (conv1.dx at 128 channels and up)
+
+
+@pytest.mark.parametrize('mode,dy16', DGRAD_MODES)
+@pytest.mark.parametrize('k,B,Fr,H,W,cin,cout', DGRAD_CASES)
 def test_dgrad_row_slice_with_res(mode, dy16, k, B, Fr, H, W, cin, cout):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(k + cin + cout)
@@ -420,6 +467,7 @@ def test_dgrad_row_slice_with_res(mode, dy16, k, B, Fr, H, W, cin, cout):
     pwt = ops.pack_conv_weights_t(_dev(kern), mode)
     half = cin // 2
     for row0 in (0, half):
+        case_id = BR.cid('dgrad rows', (k, B, Fr, H, W, cin, cout), mode, dy16, row0)
         sl = P.sample_slices(ref.shape) + [(f'frame{f}', (slice(None), f)) for f in range(Fr)]
         r64, r32 = ref[..., row0:row0 + half], ref32[..., row0:row0 + half]
         bound, sb, floor = P.exact_products_bounds(r32, r64, sl, stated=P.FWD_STATED)
@@ -429,11 +477,13 @@ def test_dgrad_row_slice_with_res(mode, dy16, k, B, Fr, H, W, cin, cout):
             with launches() as rec, nan_outputs():
                 got, again = run(), run()
                 torch.cuda.synchronize()
+            BR.assert_chain(case_id, rec, calls=2)
             assert torch.equal(got.view(torch.uint8), again.view(torch.uint8)), f'{what}: two runs are not bit-identical'
             print(f'[{what}] launched: {rec}')
             assert_launches(rec, 2 * [('conv_igemm_kernel', [f'<2, {64 if half <= 64 else 128}, 2, 8, 0>', f'conv{k}x{k} {cout}->{half}', '+res'])], what)
         else:
-            got = run()
+            with BR.bound(case_id):
+                got = run()
         torch.cuda.synchronize()
         P.assert_exact_products(got.cpu(), r64, bound, sl, sb, what=f'dgrad rows k={k} {cin}->({half}|{half}) row0={row0} {mode} dy16={int(dy16)} (CPU floor {floor:.1e})')
 
@@ -465,8 +515,11 @@ def _sum_bound(ref32, ref64, scale, terms):
     return 4.0 * max(_sum_err(ref32, ref64, scale), 2.0 ** -24 * terms ** 0.5)
 
 
+FINAL_CASES = [(64, 1, (1, 3, 7, 5)), (16, 3, (1, 3, 7, 5)), (32, 2, (1, 3, 7, 5)), (64, 1, (2, 16, 64, 64))]
+
+
 @pytest.mark.parametrize('x16', [False, True])
-@pytest.mark.parametrize('D,Cout,lead', [(64, 1, (1, 3, 7, 5)), (16, 3, (1, 3, 7, 5)), (32, 2, (1, 3, 7, 5)), (64, 1, (2, 16, 64, 64))])
+@pytest.mark.parametrize('D,Cout,lead', FINAL_CASES)
 def test_final_conv_backward(D, Cout, lead, x16, slots):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(2 + D)
@@ -485,7 +538,8 @@ def test_final_conv_backward(D, Cout, lead, x16, slots):
     outs = {}
     for label, scr in (('atomics', None), ('slots', slots), ('slots again', slots)):
         slots.fill_(float('nan'))
-        dx, dw, db = ops.final_conv_backward(_dev(x, BF if x16 else F32), _dev(d_out), _dev(kern), scratch=scr)
+        with BR.bound(BR.cid('final_conv', D, Cout, lead, x16, 'atomics' if scr is None else 'slots'), x16=x16, det=scr is not None):
+            dx, dw, db = ops.final_conv_backward(_dev(x, BF if x16 else F32), _dev(d_out), _dev(kern), scratch=scr)
         torch.cuda.synchronize()
         outs[label] = got = (dx.cpu(), dw.cpu().reshape(1, D, Cout), db.cpu())
         for nm, a, b, bd, sc in zip(('dx', 'dw', 'db'), got, ref, bounds, scale):
@@ -495,7 +549,10 @@ def test_final_conv_backward(D, Cout, lead, x16, slots):
     assert all(torch.equal(a, b) for a, b in zip(outs['slots'], outs['slots again'])), 'two runs with slots are not bit-identical'
 
 
-@pytest.mark.parametrize('Cin,D,k', [(1, 64, 7), (3, 16, 7), (3, 40, 3)])
+INIT_CASES = [(1, 64, 7), (3, 16, 7), (3, 40, 3)]
+
+
+@pytest.mark.parametrize('Cin,D,k', INIT_CASES)
 def test_init_conv_backward_weights(Cin, D, k, slots):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(1)
@@ -513,7 +570,8 @@ def test_init_conv_backward_weights(Cin, D, k, slots):
     outs = {}
     for label, scr in (('atomics', None), ('slots', slots), ('slots again', slots)):
         slots.fill_(float('nan'))
-        outs[label] = got = tuple(t.cpu() for t in ops.init_conv_backward_weights(_dev(x), _dev(dy), k, scratch=scr))
+        with BR.bound(BR.cid('init_conv', Cin, D, k, 'atomics' if scr is None else 'slots')):
+            outs[label] = got = tuple(t.cpu() for t in ops.init_conv_backward_weights(_dev(x), _dev(dy), k, scratch=scr))
         for nm, a, b, bd, sc in zip(('dw', 'db'), got, ref, bounds, scale):
             rr = _sum_err(a, b, sc)
             print(f'[init_conv Cin={Cin} D={D} k={k} {label}] {nm}: rel {rr:.3e} (bound {bd:.3e})')
@@ -521,7 +579,10 @@ def test_init_conv_backward_weights(Cin, D, k, slots):
     assert all(torch.equal(a, b) for a, b in zip(outs['slots'], outs['slots again'])), 'two runs with slots are not bit-identical'
 
 
-@pytest.mark.parametrize('dim,cond_dim', [(64, 0), (16, 32), (32, 768)])
+TIME_MLP_CASES = [(64, 0), (16, 32), (32, 768)]
+
+
+@pytest.mark.parametrize('dim,cond_dim', TIME_MLP_CASES)
 def test_time_mlp_backward(dim, cond_dim):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(3)
@@ -545,8 +606,9 @@ def test_time_mlp_backward(dim, cond_dim):
     # the fp32 evaluation carries the fp32 sin/cos of arguments up to ~1e3 rad, as the kernel's recompute does (tests/test_gpu_blocks.py
     # test_time_mlp holds the forward to 2e-4 for the same reason)
     ref, ref32 = grads(F64), grads(F32)
-    got = ops.time_mlp_backward(t.to(DEV), _dev(w1), _dev(b1), _dev(w2), _dev(b2), _dev(dtemb), cond_dim=cond_dim,
-                                cond_mask=None if mask is None else mask.to(DEV))
+    with BR.bound(BR.cid('time_mlp', dim, cond_dim)):
+        got = ops.time_mlp_backward(t.to(DEV), _dev(w1), _dev(b1), _dev(w2), _dev(b2), _dev(dtemb), cond_dim=cond_dim,
+                                    cond_mask=None if mask is None else mask.to(DEV))
     torch.cuda.synchronize()
     for nm, a, b, b32 in zip(('dw1', 'db1', 'dw2', 'db2', 'dnull'), got, ref, ref32):
         bd, rr = _small_bound(b32, b), P.rel(a.cpu().reshape(b.shape), b)

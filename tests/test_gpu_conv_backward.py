@@ -4,6 +4,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import _bwd_parity_routes as BR
 from oracle import unet3d_ref as R
 
 DEV = 'cuda:0'
@@ -55,21 +56,26 @@ def test_conv_dgrad_wgrad_bias(mode, case):
     dyd = dy.float().to(DEV)
     # data gradient = forward kernel with the transposed/flipped packing (and Down <-> Up swapped)
     pwt = ops.pack_conv_weights_t(kern.detach().float().to(DEV), mode)
-    if kind == 1:
-        dx = ops.conv_forward(dyd, pwt, Cin, mode=mode, k=4, stride=2)
-    elif stride == 2:
-        dx = ops.conv_forward(dyd, pwt, Cin, mode=mode, kind=1)
-    else:
-        dx = ops.conv_forward(dyd, pwt, Cin, mode=mode, k=k)
+    with BR.bound(BR.cid('cb dgrad', mode, case)):
+        if kind == 1:
+            dx = ops.conv_forward(dyd, pwt, Cin, mode=mode, k=4, stride=2)
+        elif stride == 2:
+            dx = ops.conv_forward(dyd, pwt, Cin, mode=mode, kind=1)
+        else:
+            dx = ops.conv_forward(dyd, pwt, Cin, mode=mode, k=k)
     tol = 2e-6 if mode == 'f32' else 8e-3
     assert dx.shape == gx.shape
     assert _rel(dx.cpu().double(), gx) < tol, (mode, case, _rel(dx.cpu().double(), gx))
-    dw = ops.conv_backward_weights(x.detach().float().to(DEV), dyd, kern.shape, kind=kind, k=k, stride=stride)
+    xd = x.detach().float().to(DEV)
+    with BR.bound(BR.cid('cb wgrad', mode, case, 0)):
+        dw = ops.conv_backward_weights(xd, dyd, kern.shape, kind=kind, k=k, stride=stride)
     assert _rel(dw.cpu().double(), gk) < 5e-6, (case, _rel(dw.cpu().double(), gk))      # exact-f32 MFMA form
     if mode == 'bf16':     # the form a bf16-mode handle's backward uses: operands rounded to bf16 (transposing LDS reads), fp32 accumulate
-        dw16 = ops.conv_backward_weights(x.detach().float().to(DEV), dyd, kern.shape, kind=kind, k=k, stride=stride, bf16_operands=True)
+        with BR.bound(BR.cid('cb wgrad', mode, case, 1)):
+            dw16 = ops.conv_backward_weights(xd, dyd, kern.shape, kind=kind, k=k, stride=stride, bf16_operands=True)
         assert _rel(dw16.cpu().double(), gk) < 8e-3, (case, _rel(dw16.cpu().double(), gk))
-    db = ops.colsum(dyd)
+    with BR.bound(BR.cid('cb colsum', mode, case)):
+        db = ops.colsum(dyd)
     assert _rel(db.cpu().double(), gb) < 5e-6
 
 
@@ -83,7 +89,8 @@ def test_wgrad_concat_and_prologue():
     y = R.conv_1kk(torch.cat((xa, xb), -1), kern, None)
     dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
     (gk,) = torch.autograd.grad(y, kern, dy)
-    dw = ops.conv_backward_weights(xa.float().to(DEV), dy.float().to(DEV), kern.shape, x1=xb.float().to(DEV))
+    with BR.bound(BR.cid('cb concat', 0)):
+        dw = ops.conv_backward_weights(xa.float().to(DEV), dy.float().to(DEV), kern.shape, x1=xb.float().to(DEV))
     assert _rel(dw.cpu().double(), gk) < 5e-6
     # prologue: Xhat = SiLU(GN(y1) * (s+1) + sh) recomputed inside the wgrad kernel
     y1 = torch.randn(B, Fr, H, W, Cout, generator=g, dtype=torch.float64)
@@ -97,27 +104,34 @@ def test_wgrad_concat_and_prologue():
     yg = y1.reshape(B, -1, 8, Cout // 8)
     stats = torch.zeros(B, 32, 8, 2, dtype=torch.float64)
     stats[:, 0, :, 0] = yg.sum(dim=(1, 3)); stats[:, 0, :, 1] = (yg * yg).sum(dim=(1, 3))
-    dw2 = ops.conv_backward_weights(y1.float().to(DEV), dy2.float().to(DEV), k2.shape, in_stats=stats.reshape(-1).to(DEV),
-                                    gamma=gamma.float().to(DEV), beta=beta.float().to(DEV), scale_shift=ss.float().to(DEV))
+    with BR.bound(BR.cid('cb prologue', 0)):
+        dw2 = ops.conv_backward_weights(y1.float().to(DEV), dy2.float().to(DEV), k2.shape, in_stats=stats.reshape(-1).to(DEV),
+                                        gamma=gamma.float().to(DEV), beta=beta.float().to(DEV), scale_shift=ss.float().to(DEV))
     assert _rel(dw2.cpu().double(), gk2) < 2e-5
     # bf16-operand form of both
-    dw16 = ops.conv_backward_weights(xa.float().to(DEV), dy.float().to(DEV), kern.shape, x1=xb.float().to(DEV), bf16_operands=True)
+    with BR.bound(BR.cid('cb concat', 1)):
+        dw16 = ops.conv_backward_weights(xa.float().to(DEV), dy.float().to(DEV), kern.shape, x1=xb.float().to(DEV), bf16_operands=True)
     assert _rel(dw16.cpu().double(), gk) < 8e-3
-    dw216 = ops.conv_backward_weights(y1.float().to(DEV), dy2.float().to(DEV), k2.shape, in_stats=stats.reshape(-1).to(DEV),
-                                      gamma=gamma.float().to(DEV), beta=beta.float().to(DEV), scale_shift=ss.float().to(DEV), bf16_operands=True)
+    with BR.bound(BR.cid('cb prologue', 1)):
+        dw216 = ops.conv_backward_weights(y1.float().to(DEV), dy2.float().to(DEV), k2.shape, in_stats=stats.reshape(-1).to(DEV),
+                                          gamma=gamma.float().to(DEV), beta=beta.float().to(DEV), scale_shift=ss.float().to(DEV), bf16_operands=True)
     assert _rel(dw216.cpu().double(), gk2) < 8e-3
     # pointwise conv over a concat input, wide output (the split-K GEMM form of bf16 mode)
     kp = (torch.randn(1, 1, 1, C0 + C1, 256, generator=g, dtype=torch.float64) / 7).requires_grad_(True)
     yp = R.conv_pointwise(torch.cat((xa, xb), -1), kp[0], None)
     dyp = torch.randn(yp.shape, generator=g, dtype=torch.float64)
     (gkp,) = torch.autograd.grad(yp, kp, dyp)
-    dwp = ops.conv_backward_weights(xa.float().to(DEV), dyp.float().to(DEV), kp.shape, x1=xb.float().to(DEV), k=1, bf16_operands=True)
+    with BR.bound(BR.cid('cb concat 1x1 256')):
+        dwp = ops.conv_backward_weights(xa.float().to(DEV), dyp.float().to(DEV), kp.shape, x1=xb.float().to(DEV), k=1, bf16_operands=True)
     assert _rel(dwp.cpu().double(), gkp) < 8e-3
 
 
-@pytest.mark.parametrize('C,B,shape,use_ss,tail', [(16, 2, (3, 5, 5), True, False), (64, 2, (4, 8, 8), True, False), (64, 1, (2, 8, 8), False, True),
-                                                   (256, 2, (2, 4, 4), False, True), (512, 1, (2, 2, 2), True, False), (1024, 1, (2, 2, 2), False, True),
-                                                   (24, 1, (2, 3, 3), False, True)])
+NORM_CASES = [(16, 2, (3, 5, 5), True, False), (64, 2, (4, 8, 8), True, False), (64, 1, (2, 8, 8), False, True),
+              (256, 2, (2, 4, 4), False, True), (512, 1, (2, 2, 2), True, False), (1024, 1, (2, 2, 2), False, True),
+              (24, 1, (2, 3, 3), False, True)]
+
+
+@pytest.mark.parametrize('C,B,shape,use_ss,tail', NORM_CASES)
 def test_norm_act_backward(C, B, shape, use_ss, tail):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(C + B)
@@ -143,7 +157,8 @@ def test_norm_act_backward(C, B, shape, use_ss, tail):
     stats = torch.zeros(B, 32, 8, 2, dtype=D)
     stats[:, 0, :, 0] = yg.sum(dim=(1, 3)); stats[:, 0, :, 1] = (yg * yg).sum(dim=(1, 3))
     f = lambda t: None if t is None else t.detach().float().to(DEV)
-    res = ops.norm_act_backward(f(dout), f(y), stats.reshape(-1).to(DEV), f(gamma), f(beta), 8, scale_shift=f(ss), r=f(r), ln_gamma=f(lg))
+    with BR.bound(BR.cid('cb norm', (C, B, shape, use_ss, tail))):
+        res = ops.norm_act_backward(f(dout), f(y), stats.reshape(-1).to(DEV), f(gamma), f(beta), 8, scale_shift=f(ss), r=f(r), ln_gamma=f(lg))
     assert _rel(res['dy'].cpu().double(), gy) < 3e-5, _rel(res['dy'].cpu().double(), gy)
     assert _rel(res['d_gamma'].cpu().double(), ggam) < 3e-5 and _rel(res['d_beta'].cpu().double(), gbet) < 3e-5
     i = 3
@@ -155,7 +170,10 @@ def test_norm_act_backward(C, B, shape, use_ss, tail):
         assert _rel(res['d_ln_gamma'].cpu().double(), grads[i + 1]) < 3e-5 and _rel(res['d_ln_beta'].cpu().double(), grads[i + 2]) < 3e-5
 
 
-@pytest.mark.parametrize('B,Fr,H,W,heads,temporal', [(1, 16, 4, 4, 8, True), (2, 10, 2, 3, 8, True), (1, 2, 8, 8, 8, False), (1, 3, 5, 5, 4, False)])
+ATTN_CASES = [(1, 16, 4, 4, 8, True), (2, 10, 2, 3, 8, True), (1, 2, 8, 8, 8, False), (1, 3, 5, 5, 4, False)]
+
+
+@pytest.mark.parametrize('B,Fr,H,W,heads,temporal', ATTN_CASES)
 def test_attention_core_backward(B, Fr, H, W, heads, temporal):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(B + Fr + H)
@@ -174,12 +192,14 @@ def test_attention_core_backward(B, Fr, H, W, heads, temporal):
     o = torch.einsum('...hij,...jhd->...ihd', torch.softmax(sim, -1), v)
     o_rows = (o.permute(0, 2, 1, 3, 4) if temporal else o).reshape(npix, HD)
     (gqkv,) = torch.autograd.grad(o_rows, qkv, d_o)
-    og, dq, dk, dv = ops.attention_core_backward(qkv.detach().float().to(DEV), d_o.float().to(DEV), B, Fr, H, W, heads, temporal)
+    with BR.bound(BR.cid('cb core', (B, Fr, H, W, heads, temporal), 0)):
+        og, dq, dk, dv = ops.attention_core_backward(qkv.detach().float().to(DEV), d_o.float().to(DEV), B, Fr, H, W, heads, temporal)
     assert _rel(og.cpu().double(), o_rows.detach()) < 1e-5
     got = torch.cat([dq, dk, dv], -1).cpu().double()
     assert _rel(got, gqkv) < 2e-5, _rel(got, gqkv)
     # bf16-operand MFMA form (what a bf16-mode handle's backward runs for <= 16 tokens; longer sequences fall back to fp32)
-    og, dq, dk, dv = ops.attention_core_backward(qkv.detach().float().to(DEV), d_o.float().to(DEV), B, Fr, H, W, heads, temporal, bf16_operands=True)
+    with BR.bound(BR.cid('cb core', (B, Fr, H, W, heads, temporal), 1)):
+        og, dq, dk, dv = ops.attention_core_backward(qkv.detach().float().to(DEV), d_o.float().to(DEV), B, Fr, H, W, heads, temporal, bf16_operands=True)
     tol = 1.5e-2 if (Fr if temporal else H * W) <= 16 else 2e-5
     assert _rel(og.cpu().double(), o_rows.detach()) < tol
     assert _rel(torch.cat([dq, dk, dv], -1).cpu().double(), gqkv) < tol
@@ -188,7 +208,10 @@ def test_attention_core_backward(B, Fr, H, W, heads, temporal):
 # y = MHA(x) + x over the frames of every pixel (modules.py:271-327 under Residual); the fused kernel returns dx and the two tensors
 # the weight-gradient kernels read (o = attention output before the out projection, d(q|k|v)).  bf16 operands: 1.5e-2 (as the unfused
 # bf16 core above); 16 frames = full tiles, 5 frames = masked keys / zero rows, odd pixel counts = ragged last workgroup.
-@pytest.mark.parametrize('B,Fr,H,W', [(1, 16, 4, 4), (2, 5, 3, 3), (1, 16, 16, 16)])
+FUSED_CASES = [(1, 16, 4, 4), (2, 5, 3, 3), (1, 16, 16, 16)]
+
+
+@pytest.mark.parametrize('B,Fr,H,W', FUSED_CASES)
 def test_temporal_attention_backward_fused(B, Fr, H, W):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(100 + B + Fr + H)
@@ -207,8 +230,9 @@ def test_temporal_attention_backward_fused(B, Fr, H, W):
     y = (o @ wo).reshape(x.shape) + x
     o.retain_grad(); qkv.retain_grad()
     y.backward(dy)
-    dx, og, dqkv = ops.temporal_attention_backward_fused(x.detach().float().to(DEV), dy.float().to(DEV), wqkv.detach().float().to(DEV),
-                                                         bqkv.detach().float().to(DEV), wo.detach().float().to(DEV))
+    with BR.bound(BR.cid('cb fused', (B, Fr, H, W))):
+        dx, og, dqkv = ops.temporal_attention_backward_fused(x.detach().float().to(DEV), dy.float().to(DEV), wqkv.detach().float().to(DEV),
+                                                             bqkv.detach().float().to(DEV), wo.detach().float().to(DEV))
     torch.cuda.synchronize()
     assert _rel(og.float().cpu().double(), o.detach()) < 1.5e-2
     assert _rel(dqkv.float().cpu().double(), qkv.grad) < 1.5e-2, _rel(dqkv.float().cpu().double(), qkv.grad)
@@ -217,7 +241,10 @@ def test_temporal_attention_backward_fused(B, Fr, H, W):
     assert _rel(dx.cpu().double() - dy, x.grad - dy) < 2.5e-2
 
 
-@pytest.mark.parametrize('NF,H,W', [(2, 8, 8), (3, 5, 7), (1, 20, 20)])
+SLA_CASES = [(2, 8, 8), (3, 5, 7), (1, 20, 20)]
+
+
+@pytest.mark.parametrize('NF,H,W', SLA_CASES)
 def test_sla_core_backward(NF, H, W):
     from video_diffusion_nnx_amd import ops
     g = torch.Generator().manual_seed(NF + H)
@@ -232,12 +259,14 @@ def test_sla_core_backward(NF, H, W):
     out = torch.einsum('bhde,bhdn->bhen', ctx, qs).permute(0, 3, 1, 2).reshape(NF * N, 256)
     gq, gk, gv = torch.autograd.grad(out, (q, k, v), d_out)
     f = lambda t: t.detach().float().to(DEV)
-    o, dq, dk, dv = ops.sla_core_backward(f(q), f(k), f(v), f(d_out), NF, N)
+    with BR.bound(BR.cid('cb sla', (NF, H, W), 0)):
+        o, dq, dk, dv = ops.sla_core_backward(f(q), f(k), f(v), f(d_out), NF, N)
     assert _rel(o.cpu().double(), out.detach()) < 1e-5
     for got, ref, nm in ((dq, gq, 'dq'), (dk, gk, 'dk'), (dv, gv, 'dv')):
         assert _rel(got.cpu().double(), ref) < 3e-5, (nm, _rel(got.cpu().double(), ref))
     # bf16-operand reductions (pass A on MFMA; pass B unchanged): what a bf16-mode handle's backward uses
-    o, dq, dk, dv = ops.sla_core_backward(f(q), f(k), f(v), f(d_out), NF, N, bf16_operands=True)
+    with BR.bound(BR.cid('cb sla', (NF, H, W), 1)):
+        o, dq, dk, dv = ops.sla_core_backward(f(q), f(k), f(v), f(d_out), NF, N, bf16_operands=True)
     assert _rel(o.cpu().double(), out.detach()) < 1e-2
     for got, ref, nm in ((dq, gq, 'dq'), (dk, gk, 'dk'), (dv, gv, 'dv')):
         assert _rel(got.cpu().double(), ref) < 2e-2, ('bf16', nm, _rel(got.cpu().double(), ref))

@@ -16,6 +16,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import _bwd_parity_routes as BR
 import _parity as P
 from _launch_hook import assert_launches, launches, nan_outputs
 from oracle import philox_ref, train_ref, unet3d_ref as R
@@ -85,6 +86,7 @@ def _run_core(case, peaked=False):
         o, dq, dk, dv = ops.attention_core_backward(_dev(qkv), _dev(d_o), B, Fr, H, W, heads, False)
         torch.cuda.synchronize()
     assert_launches(rec, _expect(L, B * Fr, heads), what)
+    BR.assert_chain(BR.cid('long', case, 'separate'), rec)
     assert 'attn_core_bwd_kernel' not in [k for k, _ in rec]
     _judge(o, torch.cat([dq, dk, dv], dim=1), o_ref, g_ref, B, Fr, L, heads, what + ' separate')
     for pad in (0, PAD):
@@ -93,6 +95,7 @@ def _run_core(case, peaked=False):
                                                      sentinel=SENTINEL if pad else None, pad_cols=pad)
             torch.cuda.synchronize()
         assert_launches(rec, _expect(L, B * Fr, heads), what)
+        BR.assert_chain(BR.cid('long', case, 'io', pad), rec)
         dqkv = dqkv.cpu()
         if pad:
             assert torch.equal(dqkv[:, 3 * HD:], torch.full((npix, pad), SENTINEL)), what + ': columns behind dq|dk|dv were written'
@@ -156,6 +159,7 @@ def test_64_tokens_keep_their_kernel():
         o, dq, dk, dv = ops.attention_core_backward(_dev(qkv), _dev(d_o), B, Fr, H, W, heads, False)
         torch.cuda.synchronize()
     assert_launches(rec, [('attn_core_bwd_kernel', ['L64 nseq2 heads8'])], '64 tokens')
+    BR.assert_chain(BR.cid('long', '64 tokens'), rec)
     assert P.rel(o.cpu(), o_ref) < TOL_O and P.rel(torch.cat([dq, dk, dv], dim=1).cpu(), g_ref) < TOL_G
 
 

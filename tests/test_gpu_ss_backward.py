@@ -14,6 +14,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import _bwd_parity_routes as BR
 import _parity as P
 import _ss_backward_cases as SC
 from oracle import unet3d_ref as R
@@ -59,8 +60,10 @@ class _Run:
         need = len(layers) * c['B'] * c['temb_dim']
         if scratch is not None:
             scratch.fill_(float('nan'))          # every run: a slot read without having been written in THIS call shows
-        ops.resblock_scale_shift_backward(self.params, self.grads, self.temb, layers, self.lin, self.dss, self.dtemb, scratch=scratch,
-                                          scratch_floats=need - 1 if short else None)
+        label = 'short' if short else ('atomics' if scratch is None else 'slots')
+        with BR.bound(BR.cid('ss', c['name'], len(layers), label), det=label == 'slots'):
+            ops.resblock_scale_shift_backward(self.params, self.grads, self.temb, layers, self.lin, self.dss, self.dtemb, scratch=scratch,
+                                              scratch_floats=need - 1 if short else None)
         torch.cuda.synchronize()
         if scratch is not None:
             used = 0 if short else need
@@ -203,8 +206,9 @@ def test_chain_norm_backward_to_time_mlp_backward(slots):
             ss = ss_r[i].to(dt).requires_grad_(True)
             h = R.group_norm(k['y'].to(dt), k['gamma'].to(dt), k['beta'].to(dt), 8) * (ss[:, None, None, None, :C] + 1) + ss[:, None, None, None, C:]
             return torch.autograd.grad(R.silu(h), ss, k['dact'].to(dt))[0]
-        res = ops.norm_act_backward_ex(_dev(k['dact']), _dev(k['y'], BF), P.gn_stats_slab(k['y']).reshape(-1).to(DEV), _dev(k['gamma']), _dev(k['beta']), 8,
-                                       scale_shift=_dev(ss_r[i]), dy_bf16=True, deterministic=True)
+        with BR.bound(BR.cid('ss chain', 'norm')):
+            res = ops.norm_act_backward_ex(_dev(k['dact']), _dev(k['y'], BF), P.gn_stats_slab(k['y']).reshape(-1).to(DEV), _dev(k['gamma']), _dev(k['beta']), 8,
+                                           scale_shift=_dev(ss_r[i]), dy_bf16=True, deterministic=True)
         torch.cuda.synchronize()
         dss_got.append(res['dss'].cpu())
         # the bound test_norm_act_backward_bf16_tensors holds this output to (NORM_FP32)
@@ -217,7 +221,8 @@ def test_chain_norm_backward_to_time_mlp_backward(slots):
     params, grads = _dev(SC.pack_params(layers, tensors, total)), torch.zeros(total, dtype=F32, device=DEV)
     dss, dtemb = _dev(SC.pack_rows(layers, dss_got, cols, B)), torch.zeros(B, td, dtype=F32, device=DEV)
     slots.fill_(float('nan'))
-    ops.resblock_scale_shift_backward(params, grads, _dev(temb_r), layers, _dev(SC.pack_rows(layers, lin_r, cols, B)), dss, dtemb, scratch=slots)
+    with BR.bound(BR.cid('ss chain', 'ss'), det=True):
+        ops.resblock_scale_shift_backward(params, grads, _dev(temb_r), layers, _dev(SC.pack_rows(layers, lin_r, cols, B)), dss, dtemb, scratch=slots)
     torch.cuda.synchronize()
     sl = P.sample_slices((B,))
     for i, got in enumerate(SC.unpack_rows(dss.cpu(), layers, B)):
@@ -235,7 +240,8 @@ def test_chain_norm_backward_to_time_mlp_backward(slots):
         ps = [p.to(dt).requires_grad_(True) for p in (w1, b1, w2, b2)]
         return torch.autograd.grad(R.gelu_tanh(R.sinusoidal_pos_emb(t, dim, dt) @ ps[0] + ps[1]) @ ps[2] + ps[3], ps, dtemb_in.to(dt))
 
-    got3 = ops.time_mlp_backward(t.to(DEV), _dev(w1), _dev(b1), _dev(w2), _dev(b2), dtemb)
+    with BR.bound(BR.cid('ss chain', 'time_mlp')):
+        got3 = ops.time_mlp_backward(t.to(DEV), _dev(w1), _dev(b1), _dev(w2), _dev(b2), dtemb)
     torch.cuda.synchronize()
     ref3, ref3_32 = stem(F64, dtemb_got), stem(F32, dtemb_got)
     for nm, a, r64, r32, e64, e32 in zip(('dw1', 'db1', 'dw2', 'db2'), got3, ref3, ref3_32, end64, end32):

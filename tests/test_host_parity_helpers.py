@@ -803,3 +803,33 @@ def test_ss_backward_m2_of_the_previous_sample():
     tens, (ratio, r, bound, i, lab) = _ss_figures(c, bad)
     print(f'[stale m2, corner layer 1 sample 1] worst tensor rel {tens:.3e}; d(lin) layer {i} {lab} rel {r:.3e} = {ratio:.0f} x its bound {bound:.2e}')
     assert NET_F32 < tens < NET_BF16 and ratio > 1000
+
+
+# ---- the 8 x 8-patch weight-gradient cases (W < 16 with the prologue, and over a two-pointer concat) --------------------------------
+
+import test_gpu_backward_forms as BF_
+
+
+@pytest.mark.parametrize('name', ['l3_128_pro', 'ragged_7x9_pro', 'l3_concat_128_64', 'ragged_7x9_concat'])
+def test_8x8_patch_cases_reject_a_dropped_patch_row_and_x1_read_through_x0(name):
+    """The case's own bounds (built by _wg_case from the reference side, within their caps) pass the clean CPU evaluation and reject
+    (a) one row of one 8 x 8 patch left out of the sum, and, for the concat cases, (b) the x1 channel block read through the x0 pointer."""
+    c = BF_._wg_case(name)
+    B, Fr, H, W, c0, c1, cout, k, stride, kind, pro, split = BF_.WG_CASES[name]
+    dy = c['dy'].double()
+    if pro:
+        stats, gamma, beta, ss = c['pro']
+        xin = P.bf16r(BF_._prologue(c['x0'], gamma, beta, ss, torch.float32)).double()      # the fp32-then-rounded activation: the bound's own floor
+    else:
+        xin = torch.cat((c['x0'], c['x1']), -1).double()
+    ev = lambda x, d: BF_._conv_wgrad_ref(x, d, k, stride, kind)
+    clean = ev(xin.float().double(), dy) if pro else ev(xin.float(), dy.float())
+    P.assert_exact_products(clean, c['ref'], c['bound'], c['sl'], c['sb'], P._view3, f'{name}: clean CPU evaluation')
+    dropped = dy.clone()
+    dropped[B - 1, Fr - 1, H - 1, :8] = 0                        # the last row of the first 8 x 8 patch of the last frame
+    with pytest.raises(AssertionError):
+        P.assert_exact_products(ev(xin, dropped), c['ref'], c['bound'], c['sl'], c['sb'], P._view3, f'{name}: dropped patch row')
+    if c1:
+        swapped = torch.cat((c['x0'], c['x0'][..., :c1]), -1).double()
+        with pytest.raises(AssertionError):
+            P.assert_exact_products(ev(swapped, dy), c['ref'], c['bound'], c['sl'], c['sb'], P._view3, f'{name}: x1 read through the x0 pointer')
