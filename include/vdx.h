@@ -632,6 +632,60 @@ int vdx_vlb_loop(vdx_handle* h, const float* params, const void* packed, const f
                  uint64_t seed, int clip_denoised, double* partial, double* out, void* workspace, size_t workspace_bytes, int batch,
                  int use_graph, void* stream);
 
+/* Learned variances (EXTENSION, parity unpinned: no reference code.  Nichol & Dhariwal 2021, "Improved DDPM": learned reverse-process
+ * variances, the hybrid loss, respaced ancestral sampling).  Off unless these entries are called: every entry above keeps refusing a
+ * network with out_dim != channels.  The network has out_dim = 2 C (C = channels); its channel-last output out2 [batch,F,H,W,2C] holds
+ * eps_hat in channels [0, C) and v in [C, 2C).  With f = (v + 1) / 2 (v is NOT clamped, it may extrapolate):
+ *   log sigma^2 = f max_log + (1 - f) min_log,   max_log = log beta_t,   min_log = log beta~_t  (min_log[0] = log beta~_1)
+ * Tables (make_lv_tables of the Python host, fp64; a respaced chain over S of the T levels has alpha_bar'_i = alpha_bar_{seq_i},
+ * beta'_i = 1 - alpha_bar'_i / alpha_bar'_{i-1} and everything else derived from them; the network is still called with t = seq_i):
+ *   lv_tables       float  [6][S]            sqrt_recip_ac | sqrt_recipm1_ac | coef1 | coef2 | max_log | min_log     (the step)
+ *   lv_tables64     double [VDX_LV_ROWS][T]  sqrt_ac | sqrt(1 - ac) | sqrt_recip_ac | sqrt_recipm1_ac | coef1 | coef2 | max_log | min_log | ac
+ *                                            (the loss and the bound; rows 0, 1 and 8 sit where vdx_vlb_noise / vdx_vlb_prior read them)
+ *
+ * vdx_p_sample_step_lv: x0^ = sqrt_recip_ac x - sqrt_recipm1_ac eps_hat, clamped to [-1, 1] when clip_denoised; mean = coef1 x0^ + coef2 x;
+ *   out = mean + 1[i != 0] exp(0.5 log sigma^2) z, at level i = level_dev[b] or, when level_dev is NULL, S - 1 - (step + *step_dev).
+ *   z = noise, or Philox(seed, offset + *dev_offset) indexed as vdx_p_sample_step does (per_sample % 4 == 0 then).  On level 0 the result
+ *   is out * post_scale + post_shift (unnormalize_img folded into the last step; 1, 0 = none).  The arithmetic is vdx_p_sample_step's: at
+ *   v = -1 and min_log = posterior_log_variance_clipped the two write the same bits.  Any per_sample; x and out may alias.
+ * vdx_p_sample_loop_lv: nsteps x { forward at t_dev -> out2_buf ; the step at level S - 1 - k, draw 1 + k ; t_dev[:] = max(seq[k + 1], 0),
+ *   k = *step_dev += 1 }, captured once in a hipGraph slot of its own like vdx_p_sample_loop (use_graph = 0: eagerly, the same launches).
+ *   seq: device int32 [S + 1], the chain's levels descending then -1 (vdx_ddim_sample_loop's sequence; S = T: T-1 .. 0, -1).  On entry
+ *   t_dev[:] = seq[0], *step_dev = 0, img = x_T; a loop may be issued in pieces.  post_scale / post_shift as in the step.
+ * vdx_hybrid_loss: L = mean |eps_hat - eps|^p + w mean vb over all batch * per_sample elements (p = 2 when l2 else 1), vb in bits per
+ *   element with eps_hat DETACHED inside it: with x0 = x pre_scale + pre_shift, x_t = sqrt_ac x0 + sqrt(1 - ac) noise formed in double (as
+ *   vdx_vlb_terms does), x0^ unclipped, for t >= 1 vb = KL(N(mu~, beta~_t) || N(mu, sigma^2)) / ln 2 with
+ *   KL = 0.5 (expm1(D) - D + (mu~ - mu)^2 e^{-log sigma^2}), D = log beta~_t - log sigma^2, and for t = 0 the discretized-Gaussian decoder
+ *   term of vdx_vlb_terms (exact erfc, the same tail rules and 1e-12 floor) with sigma = exp(0.5 log sigma^2).  out [2 batch + 3] doubles:
+ *   the per-sample means (mse_b, vb_b), then (mean mse, mean vb, L).  d_out (may be NULL: no gradient) [batch,F,H,W,2C] fp32 = dL/d out2:
+ *   the eps_hat half is vdx_loss_grad's value bit for bit, the v half d vb / d log sigma^2 * 0.5 (max_log - min_log) * w / (N ln 2) with
+ *   d KL / d log sigma^2 = 0.5 (1 - e^D - (mu~ - mu)^2 e^{-log sigma^2}) and, at t = 0, 0.5 (phi(z+) z+ - phi(z-) z-) / P (without the
+ *   absent term on a tail, 0 where P is floored).  Everything in double, sums by the fixed-order scheme of vdx_vlb_terms: no atomics, no
+ *   host read.  scratch: vdx_hybrid_scratch_doubles(batch) doubles.  Any per_sample that is a multiple of channels.
+ * vdx_vlb_terms_lv / vdx_vlb_loop_lv: vdx_vlb_terms / vdx_vlb_loop (same arguments, rules, output triple and graph contract, a graph slot
+ *   of its own) with the model's log sigma^2 in the KL and decoder terms: eps_hat = out2, vlb_tables = lv_tables64.
+ * Refused before any launch (VDX_ERR_INVALID): a network whose out_dim is not 2 * channels ("out_dim must equal 2 * channels"), S outside
+ * [1, timesteps] ("S must be in [1, timesteps]"). */
+#define VDX_LV_ROWS 9
+int vdx_p_sample_step_lv(const float* x, const float* out2, float* out, const int* level_dev, const float* lv_tables, int S, uint64_t step,
+                         const uint64_t* step_dev, const float* noise, uint64_t seed, uint64_t offset, const uint64_t* dev_offset,
+                         int clip_denoised, float post_scale, float post_shift, int batch, int channels, long per_sample, void* stream);
+int vdx_p_sample_loop_lv(vdx_handle* h, const float* params, const void* packed, float* img, float* out2_buf, int* t_dev, uint64_t* step_dev,
+                         const float* lv_tables, const int* seq, int S, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                         int clip_denoised, float post_scale, float post_shift, void* workspace, size_t workspace_bytes, int batch,
+                         int use_graph, void* stream);
+size_t vdx_hybrid_scratch_doubles(int batch);
+int vdx_hybrid_loss(const float* x, const float* noise, const float* out2, const int* t, const double* lv_tables64, int timesteps,
+                    float pre_scale, float pre_shift, int l2, double vlb_weight, int want_grad, float* d_out, double* scratch, double* out,
+                    int batch, int channels, long per_sample, void* stream);
+int vdx_vlb_terms_lv(const float* x, const float* out2, const int* t, const double* lv_tables64, int timesteps, const float* noise,
+                     uint64_t seed, uint64_t draw, const uint64_t* step_dev, int clip_denoised, double* partial, double* out, int batch,
+                     int channels, long per_sample, void* stream);
+int vdx_vlb_loop_lv(vdx_handle* h, const float* params, const void* packed, const float* x, float* xt_buf, float* out2_buf, int* t_dev,
+                    uint64_t* step_dev, const double* lv_tables64, int timesteps, const int* seq, int seq_len, int nsteps, const float* cond,
+                    uint64_t seed, int clip_denoised, double* partial, double* out, void* workspace, size_t workspace_bytes, int batch,
+                    int use_graph, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */
@@ -805,6 +859,10 @@ int vdx_conv_forward_rows(int mode, const vdx_conv_desc* d, int w_rows, int w_ro
  * d a multiple of 4, <= 256; cout <= 4.  scratch: optional slots for the fixed-order sums (atomics when NULL or too small). */
 int vdx_final_conv_backward(const void* x, int x_bf16, const float* d_out, const float* kernel, float* dx, float* dw, float* db, long npix, int d,
                             int cout, float* scratch, size_t scratch_floats, void* stream);
+/* The same launches as the network makes them for the eps | v head of a learned-variance network: cout up to 6 (cout <= 4 writes
+ * vdx_final_conv_backward's bits). */
+int vdx_final_conv_backward_wide(const void* x, int x_bf16, const float* d_out, const float* kernel, float* dx, float* dw, float* db, long npix,
+                                 int d, int cout, float* scratch, size_t scratch_floats, void* stream);
 
 /* Weight and bias gradient of vdx_init_conv (model_bwd.hip:465): x external [B,Cin,F,H,W], dy channel-last [B,F,H,W,Cout];
  * dw Flax (k,k,Cin,Cout), db [Cout] ACCUMULATED.  scratch as above. */

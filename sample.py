@@ -30,6 +30,8 @@ FLAGS = (   # (flag, kwargs)
     ('--ddim-steps', dict(type=int, default=None, help='sample with an S-step DDIM chain (eta = 0) instead of the T-step ancestral one')),
     ('--dpm-steps', dict(type=int, default=None, help='sample with an S-step DPM-Solver++(2M) chain (about 20 steps do what DDIM needs 100 for); '
                                                       'not together with --ddim-steps')),
+    ('--steps', dict(type=int, default=None, help='learned-variance configs (diffusion.learned_variance): sample with the respaced S-level '
+                                                  'ancestral chain instead of all T levels')),
     ('--dpm-order', dict(type=int, choices=(1, 2), default=2, help='with --dpm-steps: 2 = second-order multistep, 1 = first order (= DDIM)')),
     ('--attn-fp8', dict(action='store_true', help='bf16 mode: fp8 (e4m3) QK^T / PV in the attention blocks over <= 16 tokens')),
     ('--context', dict(type=str, default=None, help='[B,C,F,H,W] .npy clip (float in [0,1], or uint8 / 255): generate its continuation '
@@ -53,16 +55,20 @@ FLAGS = (   # (flag, kwargs)
 def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=False, focus_present=False):
     """temporal_pos_bias: the command-line flag; the YAML's unet.temporal_pos_bias (absent = false) switches it on as well.  An architecture
     argument like dim: checkpoints do not store it, so a model trained with it is sampled with it.  focus_present: the same for the
-    focus-present switch (unet.focus_present in the YAML, absent = false)."""
+    focus-present switch (unet.focus_present in the YAML, absent = false).  diffusion.learned_variance (absent = false; optionally with
+    diffusion.vlb_weight): the UNet gets out_dim = 2 * channels (eps | v) and the diffusion the learned-variance paths; checkpoints do not
+    store the switch, the final conv's shape does (load_state_dict fails loudly on a mismatch)."""
     from video_diffusion_nnx_amd.gaussian_diffusion import GaussianDiffusion
     from video_diffusion_nnx_amd.unet3d import Rngs, Unet3D
     u, d = cfg['unet'], cfg['diffusion']
-    unet = Unet3D(dim=u['dim'], rngs=Rngs(u['rngs_seed']), dim_mults=tuple(u['dim_mults']), channels=u['channels'],
+    lv = bool(d.get('learned_variance', False))
+    lv_kw = dict(learned_variance=True, vlb_weight=d.get('vlb_weight')) if lv else {}
+    unet = Unet3D(**(dict(out_dim=2 * u['channels']) if lv else {}), dim=u['dim'], rngs=Rngs(u['rngs_seed']), dim_mults=tuple(u['dim_mults']), channels=u['channels'],
                   use_bert_text_cond=u['use_bert_text_cond'], mode=mode, attn_fp8=attn_fp8,
                   temporal_pos_bias=bool(temporal_pos_bias or u.get('temporal_pos_bias', False)),
                   focus_present=bool(focus_present or u.get('focus_present', False)))
     gd = GaussianDiffusion(denoise_fn=unet, image_size=d['image_size'], num_frames=d['num_frames'], channels=d['channels'],
-                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'])
+                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'], **lv_kw)
     return unet, gd
 
 
@@ -105,6 +111,8 @@ def main(argv=None):
     if a.dpm_steps is not None and a.ddim_steps is not None:
         ap.error('--dpm-steps and --ddim-steps are two samplers: give one of them')
 
+    if a.steps is not None and (a.dpm_steps is not None or a.ddim_steps is not None or a.context or a.cond_path):
+        ap.error('--steps is the respaced learned-variance chain: not with --ddim-steps / --dpm-steps / --context / --cond-path')
     if a.cond_path and a.context:
         ap.error('--cond-path samples from noise: not together with --context')
     if not 0.0 <= a.guidance_rescale <= 1.0:
@@ -154,6 +162,10 @@ def _run(a, ap, rank, world):
     unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8, temporal_pos_bias=a.temporal_pos_bias,
                             **(dict(focus_present=True) if a.focus_present else {}))
     fp_kw = dict(focus_present=True) if a.focus_present else {}
+    if a.steps is not None:
+        if not gd.learned_variance:
+            ap.error('--steps needs a config with diffusion.learned_variance: true')
+        fp_kw['steps'] = a.steps
     if not a.random_init:
         ckpt = pathlib.Path(a.checkpoint_path).resolve()
         gd, _ = load_checkpoint(gd, a.step, str(ckpt), load_ema_params=a.load_ema_params)

@@ -129,3 +129,17 @@ VLB_ROWS = 9                                     # VDX_VLB_ROWS: the rows of the
 vdx_vlb_scratch_doubles = _sig('vdx_vlb_scratch_doubles', c_size_t, [c_int])
 vdx_vlb_loop = _sig('vdx_vlb_loop', c_int, [c_void_p] * 9 + [c_int, c_void_p, c_int, c_int, c_void_p, _u64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                             c_int, c_int, c_void_p])
+
+# learned variances (vdx.h: "Learned variances"): the step, the captured sampling loop, the hybrid loss and the bound with the model's variance
+LV_ROWS = 9                                      # VDX_LV_ROWS: the rows of the table of doubles (gaussian_diffusion.make_lv_tables)
+vdx_p_sample_step_lv = _sig('vdx_p_sample_step_lv', c_int, [c_void_p] * 5 + [c_int, _u64, c_void_p, c_void_p, _u64, _u64, c_void_p, c_int, c_float, c_float,
+                                                            c_int, c_int, c_long, c_void_p])
+vdx_p_sample_loop_lv = _sig('vdx_p_sample_loop_lv', c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_void_p, _u64, c_int, c_float, c_float, c_void_p, c_size_t,
+                                                            c_int, c_int, c_void_p])
+vdx_hybrid_scratch_doubles = _sig('vdx_hybrid_scratch_doubles', c_size_t, [c_int])
+vdx_hybrid_loss = _sig('vdx_hybrid_loss', c_int, [c_void_p] * 5 + [c_int, c_float, c_float, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                                  c_int, c_int, c_long, c_void_p])
+vdx_vlb_terms_lv = _sig('vdx_vlb_terms_lv', c_int, [c_void_p] * 4 + [c_int, c_void_p, _u64, _u64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p])
+vdx_vlb_loop_lv = _sig('vdx_vlb_loop_lv', c_int, [c_void_p] * 9 + [c_int, c_void_p, c_int, c_int, c_void_p, _u64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                  c_int, c_int, c_void_p])
+vdx_final_conv_backward_wide = _sig('vdx_final_conv_backward_wide', c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_long, c_int, c_int, c_void_p, c_size_t, c_void_p])

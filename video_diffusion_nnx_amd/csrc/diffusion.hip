@@ -815,6 +815,235 @@ __global__ __launch_bounds__(256) void vlb_advance_kernel(const double* __restri
     if (threadIdx.x == 0 && seq && live) *step_dev = k + 1;
 }
 
+// Learned reverse-process variances (vdx.h: "Learned variances"; EXTENSION, no reference code: Nichol & Dhariwal 2021).  The network's
+// channel-last output [B,F,H,W,2C] holds eps_hat in channels [0, C) and v in [C, 2C); log sigma^2 = f max_log + (1 - f) min_log with
+// f = (v + 1) / 2, v not clamped.
+
+// p_step_elem with every rounding spelled out, in the order p_sample_kernel is compiled to (its two products of x0 and of the mean are
+// rounded on their own -- packed multiplies -- and only c1 x0 + (c2 x) and the affine are fused): with sigma per element the compiler
+// would otherwise pick other contractions, and at v = -1 the step has to be p_sample_kernel's bit for bit (as ddim_elem / cfg_g do it)
+__device__ __forceinline__ float lv_step_elem(const PStepCoef& k, float sigma, float x, float eps, float z, float ps, float sh) {
+#pragma clang fp contract(off)
+    const float t1 = k.k_recip * x;
+    const float t2 = k.k_recipm1 * eps;
+    float x0 = t1 - t2;
+    if (k.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float m2 = k.c2 * x;
+    const float mean = fmaf(k.c1, x0, m2);
+    const float sz = sigma * z;
+    const float o = sz + mean;
+    return fmaf(ps, o, sh);
+}
+
+// one reverse step with the model's variance.  tables [6][S] = sqrt_recip_ac | sqrt_recipm1_ac | coef1 | coef2 | max_log | min_log of the
+// (respaced) chain; level i = idx[b], or S - 1 - (step + *step_dev).  The element arithmetic is p_sample_kernel's with sigma per element
+// (lv_step_elem), so at v = -1 (log sigma^2 = min_log exactly) and min_log = the posterior log-variance the output is its bit for bit.  The
+// affine post_scale / post_shift is applied on level 0 only (the last step of a chain).  x and out may alias.
+__global__ __launch_bounds__(256) void p_sample_lv_kernel(LvStepArgs P) {
+    const int b = blockIdx.y;
+    const long k = (long)(P.step + (P.step_dev ? *P.step_dev : 0ull));
+    const int lvl = P.idx ? P.idx[b] : (int)((long)P.S - 1 - k);
+    const int i_lv = min(max(lvl, 0), P.S - 1);
+    PStepCoef kc;
+    kc.k_recip = P.tables[i_lv]; kc.k_recipm1 = P.tables[P.S + i_lv];
+    kc.c1 = P.tables[2 * P.S + i_lv]; kc.c2 = P.tables[3 * P.S + i_lv];
+    kc.sigma = 0.f; kc.s = 1.0f; kc.clip = P.clip;
+    const float max_log = P.tables[4 * P.S + i_lv], min_log = P.tables[5 * P.S + i_lv];
+    const float ps = i_lv == 0 ? P.post_scale : 1.0f, sh = i_lv == 0 ? P.post_shift : 0.0f;
+    unsigned long long off = P.offset;
+    if (P.dev_offset) off += *P.dev_offset;
+    const long per = P.per_sample, fhw = P.per_sample / P.C;
+    const int C2 = 2 * P.C;
+    const size_t base = (size_t)b * per, base2 = 2 * base;
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; 4 * q < per; q += (long)gridDim.x * blockDim.x) {
+        const long i = 4 * q;
+        float xv[4], ev[4], vv[4], nv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long e = i + j;
+            xv[j] = ev[j] = 0.f; vv[j] = -1.f;
+            if (e < per) {
+                xv[j] = P.x[base + e];
+                const long c = e / fhw, r = e - c * fhw;                 // [C,F,H,W] -> channel-last [F,H,W,2C]
+                ev[j] = P.out2[base2 + r * C2 + c];
+                vv[j] = P.out2[base2 + r * C2 + P.C + c];
+            }
+        }
+        if (P.noise) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) nv[j] = (i + j < per) ? P.noise[base + i + j] : 0.f;
+        } else {
+            const float4 z = randn4((unsigned long long)(base / 4 + q), P.seed, off);   // element index of the whole tensor
+            nv[0] = z.x; nv[1] = z.y; nv[2] = z.z; nv[3] = z.w;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float f = (vv[j] + 1.0f) * 0.5f;
+            const float sigma = (i_lv == 0) ? 0.f : expf(0.5f * (f * max_log + (1.0f - f) * min_log));
+            const float o = lv_step_elem(kc, sigma, xv[j], ev[j], nv[j], ps, sh);
+            if (i + j < per) P.out[base + i + j] = o;
+        }
+    }
+}
+
+// log sigma^2 of the model in double
+__device__ __forceinline__ double lv_logvar(double v, double max_log, double min_log) {
+    const double f = 0.5 * (v + 1.0);
+    return f * max_log + (1.0 - f) * min_log;
+}
+
+// KL(N(mu~, beta~) || N(mu, sigma^2)) in nats with dmu = mu~ - mu, D = log beta~ - log sigma^2: 0.5 (expm1(D) - D + dmu^2 e^{-log sigma^2});
+// *dlv = its derivative in log sigma^2, 0.5 (1 - e^D - dmu^2 e^{-log sigma^2})
+__device__ __forceinline__ double lv_kl(double dmu, double min_true, double lv, double* dlv) {
+    const double delta = min_true - lv, em1 = expm1(delta), qd = dmu * dmu * exp(-lv);
+    *dlv = 0.5 * (-em1 - qd);
+    return 0.5 * (em1 - delta + qd);
+}
+
+// -ln of the discretized Gaussian's mass on the bin of x0 (vlb_decoder_bits' rules: tails, complements, the 1e-12 floor) with
+// sigma = exp(0.5 lv); *dlv = its derivative in lv, 0.5 (phi(z+) z+ - phi(z-) z-) / p without the absent term on a tail, 0 where p is floored
+__device__ double lv_decoder_nll(double x0, double mu, double lv, double* dlv) {
+    const double inv_sigma = exp(-0.5 * lv);
+    const double zp = (x0 - mu + 1.0 / 255.0) * inv_sigma, zm = (x0 - mu - 1.0 / 255.0) * inv_sigma;
+    const double gp = 0.39894228040143267794 * exp(-0.5 * zp * zp) * zp, gm = 0.39894228040143267794 * exp(-0.5 * zm * zm) * zm;
+    double p, g;
+    if (x0 < -0.999) { p = vlb_phi(zp); g = gp; }
+    else if (x0 > 0.999) { p = vlb_phi(-zm); g = -gm; }
+    else { p = zm > 0.0 ? vlb_phi(-zm) - vlb_phi(-zp) : vlb_phi(zp) - vlb_phi(zm); g = gp - gm; }
+    const bool floored = !(p > 1e-12);
+    *dlv = floored ? 0.0 : 0.5 * g / p;
+    return -log(floored ? 1e-12 : p);
+}
+
+// what the hybrid loss and the bound read of one level of the [VDX_LV_ROWS][T] double table
+struct LvLevel { float a, s; double kr, km, c1, c2, max_log, min_log; };
+__device__ __forceinline__ LvLevel lv_level(const double* tab, int T, int tb) {
+    LvLevel L;
+    L.a = (float)tab[tb]; L.s = (float)tab[T + tb];
+    L.kr = tab[2 * T + tb]; L.km = tab[3 * T + tb]; L.c1 = tab[4 * T + tb]; L.c2 = tab[5 * T + tb];
+    L.max_log = tab[6 * T + tb]; L.min_log = tab[7 * T + tb];
+    return L;
+}
+
+// the variational term of one element in bits and its derivative in log sigma^2 (nats): the KL at t >= 1 (min_log[t] = log beta~_t
+// there), the decoder at t = 0
+__device__ __forceinline__ double lv_vb_elem(const LvLevel& L, int tb, double x0, double xt, double xh, double lv, double* dlv) {
+    const double nats = tb > 0 ? lv_kl(L.c1 * (x0 - xh), L.min_log, lv, dlv) : lv_decoder_nll(x0, L.c1 * xh + L.c2 * xt, lv, dlv);
+    return nats * 1.44269504088896340736;
+}
+
+// Hybrid loss L_simple + w L_vlb (Nichol & Dhariwal 2021, eq. 16) in one pass over x0, the noise and the network output: per-workgroup
+// (mse, vb) sums in double into partial [B][kVlbBlocks][3] and, with d_out, the gradient [B,F,H,W,2C] in fp32.  x_t is formed again from
+// x0 = x pre_scale + pre_shift and the noise as vlb_xt does.  eps_hat is detached inside vb: the eps_hat half of d_out is
+// loss_grad_kernel's expression (the same bits), the v half dvb/dlogvar * 0.5 (max_log - min_log) * vscale with vscale = w / (N ln 2).
+// Fixed grid (kVlbBlocks, B), element quads guarded, so any per_sample; no atomics.
+__global__ __launch_bounds__(256) void hybrid_loss_kernel(HybridArgs P) {
+    __shared__ double red[3][256];
+    const int b = blockIdx.y;
+    const int tb = vlb_level(P.t, b, P.T);
+    const LvLevel L = lv_level(P.tab, P.T, tb);
+    const double dv_scale = 0.5 * (L.max_log - L.min_log) * P.vscale;
+    const long per = P.per_sample, fhw = P.per_sample / P.C;
+    const int C2 = 2 * P.C;
+    const size_t base = (size_t)b * per, base2 = 2 * base;
+    const bool vec = (per & 3) == 0;
+    double acc[3] = {0.0, 0.0, 0.0};                                        // mse, vb
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; 4 * q < per; q += (long)gridDim.x * blockDim.x) {
+        const long i = 4 * q;
+        float xv[4], nv[4];
+        if (vec) {
+            const float4 x4 = *reinterpret_cast<const float4*>(P.x + base + i);
+            const float4 n4 = *reinterpret_cast<const float4*>(P.noise + base + i);
+            xv[0] = x4.x; xv[1] = x4.y; xv[2] = x4.z; xv[3] = x4.w;
+            nv[0] = n4.x; nv[1] = n4.y; nv[2] = n4.z; nv[3] = n4.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool ok = i + k < per;
+                xv[k] = ok ? P.x[base + i + k] : 0.f;
+                nv[k] = ok ? P.noise[base + i + k] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long e = i + k;
+            if (e >= per) continue;
+            const long c = e / fhw, r = e - c * fhw;                            // [C,F,H,W] -> channel-last [F,H,W,2C]
+            const size_t j = base2 + (size_t)r * C2 + c;
+            const float ev = P.out2[j], vv = P.out2[j + P.C];
+            const double x0 = fma((double)xv[k], (double)P.pre_scale, (double)P.pre_shift);
+            const double xt = fma((double)L.a, x0, (double)L.s * (double)nv[k]);
+            const double xh = L.kr * xt - L.km * (double)ev;                    // predict_start_from_noise, not clipped in training
+            const double de = (double)ev - (double)nv[k];
+            double dlv;
+            acc[0] += P.l2 ? de * de : fabs(de);
+            acc[1] += lv_vb_elem(L, tb, x0, xt, xh, lv_logvar((double)vv, L.max_log, L.min_log), &dlv);
+            if (P.d_out) {
+                const float d = ev - nv[k];
+                P.d_out[j] = P.l2 ? 2.0f * d * P.inv_count : ((d > 0.f) - (d < 0.f)) * P.inv_count;
+                P.d_out[j + P.C] = (float)(dlv * dv_scale);
+            }
+        }
+    }
+    vlb_block_reduce(red, acc, P.partial, b);
+}
+
+// One workgroup: thread b adds sample b's partials in index order -> out[2 b ..] = the sample's means (mse, vb); then thread 0 adds the
+// samples' sums in index order -> out[2 B ..] = (mean mse, mean vb, mean mse + w mean vb) over the batch
+__global__ __launch_bounds__(256) void hybrid_final_kernel(const double* __restrict__ partial, double* __restrict__ out, int B, long per_sample,
+                                                           double w, double* __restrict__ sums) {
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        double a[2] = {0.0, 0.0};
+        for (int i = 0; i < kVlbBlocks; ++i)
+            for (int j = 0; j < 2; ++j) a[j] += partial[((size_t)b * kVlbBlocks + i) * 3 + j];
+        sums[2 * b] = a[0]; sums[2 * b + 1] = a[1];
+        out[2 * b] = a[0] / (double)per_sample; out[2 * b + 1] = a[1] / (double)per_sample;
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s0 = 0.0, s1 = 0.0;
+        for (int b = 0; b < B; ++b) { s0 += sums[2 * b]; s1 += sums[2 * b + 1]; }
+        const double n = (double)B * (double)per_sample;
+        out[2 * B] = s0 / n; out[2 * B + 1] = s1 / n; out[2 * B + 2] = s0 / n + w * (s1 / n);
+    }
+}
+
+// vlb_term_kernel with the model's log sigma^2 in the KL and decoder terms: eps = the [B,F,H,W,2C] output, tab [VDX_LV_ROWS][T]
+__global__ __launch_bounds__(256) void vlb_term_lv_kernel(VlbArgs P) {
+    __shared__ double red[3][256];
+    const int b = blockIdx.y;
+    const int tb = vlb_level(P.t, b, P.T);
+    const LvLevel L = lv_level(P.tab, P.T, tb);
+    const unsigned long long draw = P.draw + (P.step_dev ? *P.step_dev : 0ull);
+    const long per = P.per_sample, fhw = P.per_sample / P.C, quads = P.per_sample / 4;
+    const int C2 = 2 * P.C;
+    const size_t base = (size_t)b * per, base2 = 2 * base;
+    double acc[3] = {0.0, 0.0, 0.0};                                        // vb, mse, xstart_mse
+    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (long)gridDim.x * blockDim.x) {
+        const long i = 4 * q;
+        const float4 x4 = *reinterpret_cast<const float4*>(P.x + base + i);
+        const float4 n4 = vlb_eps4(P, base, q, draw);
+        const float xv[4] = {x4.x, x4.y, x4.z, x4.w}, nv[4] = {n4.x, n4.y, n4.z, n4.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long e = i + k, c = e / fhw, r = e - c * fhw;                 // [C,F,H,W] -> channel-last [F,H,W,2C]
+            const size_t j = base2 + (size_t)r * C2 + c;
+            const float ev = P.eps[j], vv = P.eps[j + P.C];
+            const double x0 = vlb_x0(xv[k]);
+            const double xt = vlb_xt(L.a, L.s, xv[k], nv[k]);
+            double xh = L.kr * xt - L.km * (double)ev;
+            if (P.clip) xh = fmin(fmax(xh, -1.0), 1.0);
+            const double de = (double)ev - (double)nv[k], dx = xh - x0;
+            double dlv;
+            acc[0] += lv_vb_elem(L, tb, x0, xt, xh, lv_logvar((double)vv, L.max_log, L.min_log), &dlv);
+            acc[1] += de * de;
+            acc[2] += dx * dx;
+        }
+    }
+    vlb_block_reduce(red, acc, P.partial, b);
+}
+
 __global__ void affine_kernel(const float* __restrict__ x, float* __restrict__ y, long n, float a, float b) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = fmaf(x[i], a, b);
 }
@@ -960,6 +1189,28 @@ hipError_t launch_vlb_advance(const double* partial, double* out, int nout, int 
                               unsigned long long* step_dev, hipStream_t st) {
     return LaunchScope(st, "vlb_advance_kernel", 0.0, 0.0, "B%d n%d", B, nout)
         .launch(vlb_advance_kernel, dim3(1), dim3(256), 0, partial, out, nout, B, per_sample, t, seq, seq_len, step_dev);
+}
+
+hipError_t launch_p_sample_lv(const LvStepArgs& a, int B, hipStream_t st) {
+    return LaunchScope(st, "p_sample_lv_kernel", 0.0, 16.0 * B * a.per_sample, "B%d px%ld S%d", B, a.per_sample, a.S)
+        .launch(p_sample_lv_kernel, dim3(ew_blocks((a.per_sample + 3) / 4), B), dim3(256), 0, a);
+}
+
+size_t hybrid_scratch_doubles(int B) { return (size_t)B * kVlbBlocks * 3 + (size_t)2 * B; }
+
+hipError_t launch_hybrid_loss(const HybridArgs& a, double* out, double w, int B, hipStream_t st) {
+    hipError_t e = LaunchScope(st, "hybrid_loss_kernel", 0.0, (a.d_out ? 24.0 : 16.0) * B * a.per_sample, "B%d px%ld C%d l2 %d grad %d", B,
+                               a.per_sample, a.C, a.l2, a.d_out ? 1 : 0)
+                       .launch(hybrid_loss_kernel, dim3(kVlbBlocks, B), dim3(256), 0, a);
+    if (e != hipSuccess) return e;
+    return LaunchScope(st, "hybrid_final_kernel", 0.0, 0.0, "B%d", B)
+        .launch(hybrid_final_kernel, dim3(1), dim3(256), 0, (const double*)a.partial, out, B, a.per_sample, w, a.partial + (size_t)B * kVlbBlocks * 3);
+}
+
+hipError_t launch_vlb_terms_lv(const VlbArgs& a, int B, hipStream_t st) {
+    return LaunchScope(st, "vlb_term_lv_kernel", 0.0, 12.0 * B * a.per_sample, "B%d px%ld C%d %s clip%d", B, a.per_sample, a.C,
+                       a.noise ? "noise" : "philox", a.clip)
+        .launch(vlb_term_lv_kernel, dim3(kVlbBlocks, B), dim3(256), 0, a);
 }
 
 hipError_t launch_affine(const float* x, float* y, long n, float a, float b, hipStream_t st) {

@@ -22,18 +22,20 @@ __global__ __launch_bounds__(256) void final_conv_dx_kernel(const float* __restr
     }
 }
 
-// final conv: dW[c][co] += sum_pix x[pix][c] dout[pix][co] ; db[co] += sum_pix dout[pix][co]     (D <= 256, Cout <= 4)
+// final conv: dW[c][co] += sum_pix x[pix][c] dout[pix][co] ; db[co] += sum_pix dout[pix][co]     (D <= 256, Cout <= NCO)
 // part (deterministic mode): this workgroup's sums go to part[blockIdx.x][D * Cout] and, behind all of those, [blockIdx.x][Cout]
+// NCO = 4 is the text the kernel always had (Cout <= 4: the same bits); NCO = 6 serves the eps | v head of a learned-variance network at C = 3
+template <int NCO>
 __global__ __launch_bounds__(256) void final_conv_dw_kernel(const float* __restrict__ x, const float* __restrict__ dout, float* __restrict__ dW,
                                                             float* __restrict__ db, long npix, int D, int Cout, int x_bf16, float* __restrict__ part) {
     __shared__ float red[256 * 4];
     const int c = threadIdx.x % D, pl = threadIdx.x / D, PL = 256 / D;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f}, accb[4] = {0.f, 0.f, 0.f, 0.f};
+    float acc[NCO] = {}, accb[NCO] = {};
     if (pl < PL) {
         // 8 pixels per pass, every load issued before the first use (one dependent load per pass was a 128-step latency chain: 112 us)
         const long stride = (long)gridDim.x * PL;
         for (long pix0 = (long)blockIdx.x * PL + pl; pix0 < npix; pix0 += stride * 8) {
-            float xv[8], dv[8][4];
+            float xv[8], dv[8][NCO];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const long pix = pix0 + u * stride;
@@ -41,11 +43,11 @@ __global__ __launch_bounds__(256) void final_conv_dw_kernel(const float* __restr
                 const long pe = ok ? pix : 0;
                 xv[u] = x_bf16 ? __uint_as_float((unsigned)reinterpret_cast<const unsigned short*>(x)[pe * D + c] << 16) : x[pe * D + c];
                 if (!ok) xv[u] = 0.f;
-                for (int co = 0; co < 4; ++co) dv[u][co] = (ok && co < Cout) ? dout[pe * Cout + co] : 0.f;
+                for (int co = 0; co < NCO; ++co) dv[u][co] = (ok && co < Cout) ? dout[pe * Cout + co] : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u)
-                for (int co = 0; co < 4; ++co) { acc[co] = fmaf(xv[u], dv[u][co], acc[co]); accb[co] += dv[u][co]; }
+                for (int co = 0; co < NCO; ++co) { acc[co] = fmaf(xv[u], dv[u][co], acc[co]); accb[co] += dv[u][co]; }
         }
     }
     for (int co = 0; co < Cout; ++co) {
@@ -323,7 +325,7 @@ __global__ __launch_bounds__(256) void time_mlp_bwd_kernel(TimeMlpArgs P, const 
 }
 
 hipError_t launch_final_conv_bwd(const float* x, const float* dout, const float* w, float* dx, float* dW, float* db, long npix, int D, int Cout, int x_bf16, hipStream_t st, float* part, size_t part_cap) {
-    if (D > 256 || Cout > 4) return hipErrorInvalidValue;
+    if (D > 256 || Cout > 6) return hipErrorInvalidValue;
     const int blocks = (int)std::max<long>(1, std::min<long>((npix * (D / 4) + 255) / 256, 4096));
     hipError_t e = LaunchScope(st, "final_conv_dx_kernel", 0.0, 0.0, "D%d Cout%d npix%ld", D, Cout, npix).launch(final_conv_dx_kernel, dim3(blocks), dim3(256), 0, dout, w, dx, npix, D, Cout);
     if (e != hipSuccess) return e;
@@ -331,7 +333,7 @@ hipError_t launch_final_conv_bwd(const float* x, const float* dout, const float*
     const int b2 = (int)std::max<long>(1, std::min<long>((npix + PL - 1) / PL, 512));
     part = slots_if_fit(part, (size_t)b2 * (D + 1) * Cout, part_cap);
     e = LaunchScope(st, "final_conv_dw_kernel", 0.0, 0.0, "<x16 %d> D%d Cout%d npix%ld slots%d det %d", x_bf16, D, Cout, npix, b2, part ? 1 : 0)
-                       .launch(final_conv_dw_kernel, dim3(b2), dim3(256), 0, x, dout, dW, db, npix, D, Cout, x_bf16, part);
+                       .launch(Cout <= 4 ? final_conv_dw_kernel<4> : final_conv_dw_kernel<6>, dim3(b2), dim3(256), 0, x, dout, dW, db, npix, D, Cout, x_bf16, part);
     if (e != hipSuccess || !part) return e;
     return launch_slot_sum_dw_db(part, b2, (long)D * Cout, Cout, 0, {dW, nullptr, nullptr}, {db, nullptr, nullptr}, st);
 }

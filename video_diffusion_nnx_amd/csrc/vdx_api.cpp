@@ -9,7 +9,8 @@
 // Everything a sampling step can bake into its captured graph: what the eleven vdx_*_sample_loop* entry points fill in and sample_loop()
 // runs.  A field the entry does not have stays zero.
 // (CHAIN_VLB tags the graph key of vdx_vlb_loop only: it never goes through sample_loop, whose slot arithmetic 3 * variant + chain takes 0..2)
-enum { CHAIN_ANCESTRAL = 0, CHAIN_DDIM = 1, CHAIN_DPM = 2, CHAIN_VLB = 3 };
+// (CHAIN_LV / CHAIN_VLB_LV: the learned-variance loops, vdx_p_sample_loop_lv / vdx_vlb_loop_lv, likewise outside sample_loop)
+enum { CHAIN_ANCESTRAL = 0, CHAIN_DDIM = 1, CHAIN_DPM = 2, CHAIN_VLB = 3, CHAIN_LV = 4, CHAIN_VLB_LV = 5 };
 struct LoopArgs {
     int chain, masked, guided;                          // CHAIN_*; the masked (inpainting) step; classifier-free guidance over 2 * batch rows
     const float* params; const void* packed;
@@ -20,6 +21,7 @@ struct LoopArgs {
     float percentile; float* thres_buf;                 // dynamic threshold: percentile > 0 && clip_denoised
     const float* known; const unsigned char* mask; const float* mask_tables; int resample_steps;
     float cond_scale, rescale; double* cfg_scratch;
+    float post_scale, post_shift;                       // the learned-variance sampling loop (vdx_p_sample_loop_lv) alone
     const float* vlb_x; const double* vlb_tables; double* vlb_partial; double* vlb_out;     // the evaluation loop (vdx_vlb_loop) alone
     void* workspace; size_t workspace_bytes; int batch;
 };
@@ -31,7 +33,8 @@ struct vdx_handle {
     // is zero-filled before the fields are assigned
     struct GraphKey { LoopArgs a; const void* stream; int act16; };
     // one cached graph per (chain, variant): slot = 3 * variant + chain with variant 0 = plain, 1 = masked, 2 = guided and chain 0 = the
-    // ancestral loop, 1 = DDIM, 2 = DPM-Solver++; slot 9 = the evaluation loop (vdx_vlb_loop) -- no loop ever evicts another one's graph
+    // ancestral loop, 1 = DDIM, 2 = DPM-Solver++; slot 9 = the evaluation loop (vdx_vlb_loop), 10 / 11 = the learned-variance sampling and
+    // evaluation loops -- no loop ever evicts another one's graph
     // `last` = the stream the exec was last launched on: replays may still be running when the graph has to go
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key; hipStream_t last = nullptr;
@@ -41,7 +44,7 @@ struct vdx_handle {
             if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
             last = nullptr;
         }
-    } gs[10];
+    } gs[12];
     void drop_graphs() { for (GraphSlot& g : gs) g.drop(); }
     vdx::BwdState bwd;
     vdx::Comm comm;
@@ -1103,11 +1106,11 @@ int vdx_vlb_prior(const float* x, const double* vlb_tables, int timesteps, doubl
     return VDX_OK;
 }
 
-int vdx_vlb_loop(vdx_handle* h, const float* params, const void* packed, const float* x, float* xt_buf, float* eps_buf, int* t_dev,
-                 uint64_t* step_dev, const double* vlb_tables, int timesteps, const int* seq, int seq_len, int nsteps, const float* cond,
-                 uint64_t seed, int clip_denoised, double* partial, double* out, void* workspace, size_t workspace_bytes, int batch,
-                 int use_graph, void* stream) {
-    const char* who = "vlb_loop";
+// the two evaluation loops: lv = the learned-variance one (out_dim = 2 * channels, vlb_term_lv_kernel, graph slot 11)
+static int vlb_loop(const char* who, bool lv, vdx_handle* h, const float* params, const void* packed, const float* x, float* xt_buf, float* eps_buf, int* t_dev,
+                    uint64_t* step_dev, const double* vlb_tables, int timesteps, const int* seq, int seq_len, int nsteps, const float* cond,
+                    uint64_t seed, int clip_denoised, double* partial, double* out, void* workspace, size_t workspace_bytes, int batch,
+                    int use_graph, void* stream) {
     if (!h || !params || !packed || !x || !xt_buf || !eps_buf || !t_dev || !step_dev || !vlb_tables || !seq || !partial || !out || !workspace)
         VDX_REFUSE(who, "null argument");
     if (!h->model.d_ss_layers) { char msg_[96]; snprintf(msg_, sizeof(msg_), "%s: handle was created without a GPU", who); VDX_FAIL(VDX_ERR_STATE, msg_); }
@@ -1115,7 +1118,8 @@ int vdx_vlb_loop(vdx_handle* h, const float* params, const void* packed, const f
     const int C = m.cfg.channels;
     const long per_sample = (long)C * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
     if (int rc = vlb_rules(who, x, xt_buf, eps_buf, "x / xt_buf / eps_buf", vlb_tables, partial, out, timesteps, batch, C, per_sample)) return rc;
-    if (m.out_dim != C) VDX_REFUSE(who, "out_dim must equal channels");
+    if (!lv && m.out_dim != C) VDX_REFUSE(who, "out_dim must equal channels");
+    if (lv && m.out_dim != 2 * C) VDX_REFUSE(who, "out_dim must equal 2 * channels");
     if (seq_len < 1) VDX_REFUSE(who, "seq_len must be >= 1");
     if (nsteps < 0 || nsteps > seq_len) VDX_REFUSE(who, "nsteps out of range");
     hipStream_t st = (hipStream_t)stream;
@@ -1128,7 +1132,7 @@ int vdx_vlb_loop(vdx_handle* h, const float* params, const void* packed, const f
         // cond is used un-masked, as in the unguided sampling loops
         int rc = vdx::model_forward(&m, params, packed, xt_buf, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
         if (rc != VDX_OK) return rc;
-        e = vdx::launch_vlb_terms(ta, batch, st);
+        e = lv ? vdx::launch_vlb_terms_lv(ta, batch, st) : vdx::launch_vlb_terms(ta, batch, st);
         if (e == hipSuccess) e = vdx::launch_vlb_advance(partial, out, 3, batch, per_sample, t_dev, seq, seq_len, sd, st);
         if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
         return VDX_OK;
@@ -1137,12 +1141,136 @@ int vdx_vlb_loop(vdx_handle* h, const float* params, const void* packed, const f
     vdx_handle::GraphKey key;
     memset(&key, 0, sizeof(key));
     LoopArgs& k = key.a;
-    k.chain = CHAIN_VLB; k.params = params; k.packed = packed; k.img = xt_buf; k.eps_buf = eps_buf; k.t_dev = t_dev; k.step_dev = step_dev;
+    k.chain = lv ? CHAIN_VLB_LV : CHAIN_VLB; k.params = params; k.packed = packed; k.img = xt_buf; k.eps_buf = eps_buf; k.t_dev = t_dev; k.step_dev = step_dev;
     k.timesteps = timesteps; k.seq = seq; k.seq_len = seq_len; k.cond = cond; k.seed = seed; k.clip_denoised = clip_denoised ? 1 : 0;
     k.vlb_x = x; k.vlb_tables = vlb_tables; k.vlb_partial = partial; k.vlb_out = out;
     k.workspace = workspace; k.workspace_bytes = workspace_bytes; k.batch = batch;
     key.stream = stream; key.act16 = m.act16;
-    return run_steps(h, 9, key, nsteps, use_graph, st, step);
+    return run_steps(h, lv ? 11 : 9, key, nsteps, use_graph, st, step);
+}
+
+int vdx_vlb_loop(vdx_handle* h, const float* params, const void* packed, const float* x, float* xt_buf, float* eps_buf, int* t_dev,
+                 uint64_t* step_dev, const double* vlb_tables, int timesteps, const int* seq, int seq_len, int nsteps, const float* cond,
+                 uint64_t seed, int clip_denoised, double* partial, double* out, void* workspace, size_t workspace_bytes, int batch,
+                 int use_graph, void* stream) {
+    return vlb_loop("vlb_loop", false, h, params, packed, x, xt_buf, eps_buf, t_dev, step_dev, vlb_tables, timesteps, seq, seq_len, nsteps, cond, seed,
+                    clip_denoised, partial, out, workspace, workspace_bytes, batch, use_graph, stream);
+}
+
+// ---- learned variances (vdx.h: "Learned variances"): the step, the sampling loop, the hybrid loss, the bound ----
+
+static vdx::LvStepArgs lv_step_args(const float* x, const float* out2, float* out, const int* level_dev, const float* lv_tables, int S, uint64_t step,
+                                    const uint64_t* step_dev, const float* noise, uint64_t seed, uint64_t offset, const uint64_t* dev_offset, int clip,
+                                    float post_scale, float post_shift, int channels, long per_sample) {
+    vdx::LvStepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.out2 = out2; a.out = out; a.tables = lv_tables; a.S = S; a.idx = level_dev; a.step = step;
+    a.step_dev = reinterpret_cast<const unsigned long long*>(step_dev); a.noise = noise; a.seed = seed; a.offset = offset;
+    a.dev_offset = reinterpret_cast<const unsigned long long*>(dev_offset); a.clip = clip ? 1 : 0; a.C = channels; a.per_sample = per_sample;
+    a.post_scale = post_scale; a.post_shift = post_shift;
+    return a;
+}
+
+// the rules the learned-variance entries share (who-prefixed, VDX_ERR_INVALID)
+static int lv_rules(const char* who, int S, int timesteps, int batch, int channels, long per_sample) {
+    if (batch < 1 || channels < 1 || per_sample < 1) VDX_REFUSE(who, "batch, channels and per_sample must be >= 1");
+    if (per_sample % channels) VDX_REFUSE(who, "per_sample must be a multiple of channels");
+    if (S < 1 || S > timesteps) VDX_REFUSE(who, "S must be in [1, timesteps]");
+    return VDX_OK;
+}
+
+int vdx_p_sample_step_lv(const float* x, const float* out2, float* out, const int* level_dev, const float* lv_tables, int S, uint64_t step,
+                         const uint64_t* step_dev, const float* noise, uint64_t seed, uint64_t offset, const uint64_t* dev_offset,
+                         int clip_denoised, float post_scale, float post_shift, int batch, int channels, long per_sample, void* stream) {
+    const char* who = "p_sample_step_lv";
+    if (!x || !out2 || !out || !lv_tables) VDX_REFUSE(who, "null tensor");
+    if (int rc = lv_rules(who, S, S, batch, channels, per_sample)) return rc;
+    if (!level_dev && !step_dev && step >= (uint64_t)S) VDX_REFUSE(who, "step must be below S");
+    if (!noise && per_sample % 4) VDX_REFUSE(who, "generated noise needs per_sample % 4 == 0");
+    const vdx::LvStepArgs a = lv_step_args(x, out2, out, level_dev, lv_tables, S, step, step_dev, noise, seed, offset, dev_offset, clip_denoised,
+                                           post_scale, post_shift, channels, per_sample);
+    VDX_HIP(vdx::launch_p_sample_lv(a, batch, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_p_sample_loop_lv(vdx_handle* h, const float* params, const void* packed, float* img, float* out2_buf, int* t_dev, uint64_t* step_dev,
+                         const float* lv_tables, const int* seq, int S, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                         int clip_denoised, float post_scale, float post_shift, void* workspace, size_t workspace_bytes, int batch,
+                         int use_graph, void* stream) {
+    const char* who = "p_sample_loop_lv";
+    if (!h || !params || !packed || !img || !out2_buf || !t_dev || !step_dev || !lv_tables || !seq || !workspace) VDX_REFUSE(who, "null argument");
+    const vdx::Model& m = h->model;
+    const int C = m.cfg.channels;
+    const long per_sample = (long)C * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
+    if (m.out_dim != 2 * C) VDX_REFUSE(who, "out_dim must equal 2 * channels");
+    if (int rc = lv_rules(who, S, timesteps, batch, C, per_sample)) return rc;
+    if (per_sample % 4) VDX_REFUSE(who, "C*F*H*W must be a multiple of 4");
+    if (nsteps < 0 || nsteps > S) VDX_REFUSE(who, "nsteps out of range");
+    if (!m.d_ss_layers) { char msg_[96]; snprintf(msg_, sizeof(msg_), "%s: handle was created without a GPU", who); VDX_FAIL(VDX_ERR_STATE, msg_); }
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* sd = reinterpret_cast<unsigned long long*>(step_dev);
+    const vdx::LvStepArgs sa = lv_step_args(img, out2_buf, img, nullptr, lv_tables, S, 0, step_dev, nullptr, seed, 1, step_dev, clip_denoised, post_scale,
+                                            post_shift, C, per_sample);
+    auto step = [&]() -> int {
+        // cond is used un-masked, as in the unguided sampling loops
+        int rc = vdx::model_forward(&m, params, packed, img, t_dev, cond, nullptr, 0, out2_buf, workspace, workspace_bytes, batch, st);
+        if (rc != VDX_OK) return rc;
+        hipError_t e = vdx::launch_p_sample_lv(sa, batch, st);
+        if (e == hipSuccess) e = vdx::launch_ddim_advance(t_dev, batch, seq, sd, st);
+        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        return VDX_OK;
+    };
+    vdx_handle::GraphKey key;
+    memset(&key, 0, sizeof(key));
+    LoopArgs& k = key.a;
+    k.chain = CHAIN_LV; k.params = params; k.packed = packed; k.img = img; k.eps_buf = out2_buf; k.t_dev = t_dev; k.step_dev = step_dev;
+    k.tables = lv_tables; k.timesteps = timesteps; k.seq = seq; k.seq_len = S; k.cond = cond; k.seed = seed; k.clip_denoised = clip_denoised ? 1 : 0;
+    k.post_scale = post_scale; k.post_shift = post_shift;
+    k.workspace = workspace; k.workspace_bytes = workspace_bytes; k.batch = batch;
+    key.stream = stream; key.act16 = m.act16;
+    return run_steps(h, 10, key, nsteps, use_graph, st, step);
+}
+
+size_t vdx_hybrid_scratch_doubles(int batch) { return batch > 0 ? vdx::hybrid_scratch_doubles(batch) : 0; }
+
+int vdx_hybrid_loss(const float* x, const float* noise, const float* out2, const int* t, const double* lv_tables64, int timesteps,
+                    float pre_scale, float pre_shift, int l2, double vlb_weight, int want_grad, float* d_out, double* scratch, double* out,
+                    int batch, int channels, long per_sample, void* stream) {
+    const char* who = "hybrid_loss";
+    if (!x || !noise || !out2 || !t || !lv_tables64 || !scratch || !out) VDX_REFUSE(who, "null tensor");
+    if (want_grad && !d_out) VDX_REFUSE(who, "want_grad needs d_out");
+    if (int rc = lv_rules(who, 1, 1, batch, channels, per_sample)) return rc;
+    if (timesteps < 2) VDX_REFUSE(who, "timesteps must be >= 2");
+    if ((uintptr_t)x % 16 || (uintptr_t)noise % 16) VDX_REFUSE(who, "x / noise must be 16-byte aligned");
+    if ((uintptr_t)lv_tables64 % 8 || (uintptr_t)scratch % 8 || (uintptr_t)out % 8) VDX_REFUSE(who, "lv_tables64 / scratch / out must be 8-byte aligned");
+    const double n = (double)batch * (double)per_sample;
+    vdx::HybridArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.noise = noise; a.out2 = out2; a.d_out = want_grad ? d_out : nullptr; a.t = t; a.tab = lv_tables64; a.T = timesteps;
+    a.l2 = l2 ? 1 : 0; a.C = channels; a.per_sample = per_sample; a.pre_scale = pre_scale; a.pre_shift = pre_shift;
+    a.inv_count = 1.0f / (float)((long)batch * per_sample); a.vscale = vlb_weight / (n * 0.69314718055994530942); a.partial = scratch;
+    VDX_HIP(vdx::launch_hybrid_loss(a, out, vlb_weight, batch, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_vlb_terms_lv(const float* x, const float* out2, const int* t, const double* lv_tables64, int timesteps, const float* noise,
+                     uint64_t seed, uint64_t draw, const uint64_t* step_dev, int clip_denoised, double* partial, double* out, int batch,
+                     int channels, long per_sample, void* stream) {
+    const char* who = "vlb_terms_lv";
+    if (!x || !out2 || !t || !lv_tables64 || !partial || !out) VDX_REFUSE(who, "null tensor");
+    if (int rc = vlb_rules(who, x, nullptr, noise, "x / noise", lv_tables64, partial, out, timesteps, batch, channels, per_sample)) return rc;
+    const vdx::VlbArgs a = vlb_args(x, out2, nullptr, noise, t, lv_tables64, timesteps, seed, draw, step_dev, clip_denoised, channels, per_sample, partial);
+    VDX_HIP(vdx::launch_vlb_terms_lv(a, batch, (hipStream_t)stream));
+    VDX_HIP(vdx::launch_vlb_advance(partial, out, 3, batch, per_sample, nullptr, nullptr, 0, nullptr, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_vlb_loop_lv(vdx_handle* h, const float* params, const void* packed, const float* x, float* xt_buf, float* out2_buf, int* t_dev,
+                    uint64_t* step_dev, const double* lv_tables64, int timesteps, const int* seq, int seq_len, int nsteps, const float* cond,
+                    uint64_t seed, int clip_denoised, double* partial, double* out, void* workspace, size_t workspace_bytes, int batch,
+                    int use_graph, void* stream) {
+    return vlb_loop("vlb_loop_lv", true, h, params, packed, x, xt_buf, out2_buf, t_dev, step_dev, lv_tables64, timesteps, seq, seq_len, nsteps, cond, seed,
+                    clip_denoised, partial, out, workspace, workspace_bytes, batch, use_graph, stream);
 }
 
 int vdx_pack_conv_weights_t(int mode, const float* kernel, void* packed, int taps, int cin, int cout, void* stream) {
@@ -1428,6 +1556,15 @@ int vdx_final_conv_backward(const void* x, int x_bf16, const float* d_out, const
     if (!x || !d_out || !kernel || !dx || !dw || !db || npix < 1) VDX_FAIL(VDX_ERR_INVALID, "final_conv_backward: bad argument");
     if (d < 4 || d % 4 || d > 256 || cout < 1 || cout > 4) VDX_FAIL(VDX_ERR_INVALID, "final_conv_backward: d a multiple of 4 up to 256, cout 1..4");
     if ((scratch == nullptr) != (scratch_floats == 0)) VDX_FAIL(VDX_ERR_INVALID, "final_conv_backward: scratch and scratch_floats go together");
+    VDX_HIP(vdx::launch_final_conv_bwd((const float*)x, d_out, kernel, dx, dw, db, npix, d, cout, x_bf16 ? 1 : 0, (hipStream_t)stream, scratch, scratch_floats));
+    return VDX_OK;
+}
+
+int vdx_final_conv_backward_wide(const void* x, int x_bf16, const float* d_out, const float* kernel, float* dx, float* dw, float* db, long npix,
+                                 int d, int cout, float* scratch, size_t scratch_floats, void* stream) {
+    if (!x || !d_out || !kernel || !dx || !dw || !db || npix < 1) VDX_FAIL(VDX_ERR_INVALID, "final_conv_backward_wide: bad argument");
+    if (d < 4 || d % 4 || d > 256 || cout < 1 || cout > 6) VDX_FAIL(VDX_ERR_INVALID, "final_conv_backward_wide: d a multiple of 4 up to 256, cout 1..6");
+    if ((scratch == nullptr) != (scratch_floats == 0)) VDX_FAIL(VDX_ERR_INVALID, "final_conv_backward_wide: scratch and scratch_floats go together");
     VDX_HIP(vdx::launch_final_conv_bwd((const float*)x, d_out, kernel, dx, dw, db, npix, d, cout, x_bf16 ? 1 : 0, (hipStream_t)stream, scratch, scratch_floats));
     return VDX_OK;
 }

@@ -257,6 +257,31 @@ hipError_t launch_vlb_terms(const VlbArgs& a, int B, hipStream_t st);
 hipError_t launch_vlb_prior(const float* x, const double* tab, int T, double* partial, int B, long per_sample, hipStream_t st);
 hipError_t launch_vlb_advance(const double* partial, double* out, int nout, int B, long per_sample, int* t, const int* seq, int seq_len,
                               unsigned long long* step_dev, hipStream_t st);
+// Learned reverse-process variances (vdx.h: "Learned variances").  out2 = the network's channel-last output [B,F,H,W,2C], eps_hat | v.
+struct LvStepArgs {
+    const float* x; const float* out2; float* out;      // x/out [B,C,F,H,W] (may alias)
+    const float* tables; int S;                         // [6][S] of the (respaced) chain, level-indexed
+    const int* idx;                                     // device level per sample [B], or null -> S - 1 - (step + *step_dev)
+    unsigned long long step; const unsigned long long* step_dev;
+    const float* noise;                                 // explicit z [B,C,F,H,W], or null -> Philox(seed, offset + *dev_offset)
+    unsigned long long seed, offset; const unsigned long long* dev_offset;
+    int clip; int C; long per_sample;
+    float post_scale, post_shift;                       // applied on level 0 only
+};
+hipError_t launch_p_sample_lv(const LvStepArgs& a, int B, hipStream_t st);
+struct HybridArgs {
+    const float* x; const float* noise; const float* out2; float* d_out;   // d_out [B,F,H,W,2C] or null (no gradient)
+    const int* t; const double* tab; int T;             // tab [VDX_LV_ROWS][T] doubles
+    int l2; int C; long per_sample;
+    float pre_scale, pre_shift;                         // x0 = x pre_scale + pre_shift (normalize_img)
+    float inv_count; double vscale;                     // 1 / N as launch_loss_grad forms it; w / (N ln 2)
+    double* partial;                                    // hybrid_scratch_doubles(B)
+};
+size_t hybrid_scratch_doubles(int B);
+// out [2 B + 3] doubles: per-sample means (mse, vb), then the batch's (mse, vb, mse + w vb)
+hipError_t launch_hybrid_loss(const HybridArgs& a, double* out, double w, int B, hipStream_t st);
+// launch_vlb_terms with the model's variance: a.eps = out2, a.tab = the [VDX_LV_ROWS][T] table
+hipError_t launch_vlb_terms_lv(const VlbArgs& a, int B, hipStream_t st);
 // frame-conditioned training (mask [B,C,F,H,W] bytes, nonzero = clean context): masked q_sample, the deterministic (sum, count) of the
 // loss over the mask-0 elements (scratch: loss_masked_scratch_doubles()), and its gradient with the count read from the device
 hipError_t launch_q_sample_masked(const float* x0, const int* t, const float* noise, const unsigned char* mask, float* out, const float* sqrt_ac,

@@ -182,6 +182,53 @@ def make_vlb_tables(timesteps: int) -> np.ndarray:
                                           tabs['sqrt_recipm1_alphas_cumprod'], c1, tabs['posterior_mean_coef2'], w, dec, tabs['alphas_cumprod']]))
 
 
+LV_ROWS = L.LV_ROWS
+
+
+def make_lv_tables(timesteps: int, seq=None) -> dict:
+    """The float64 tables of the learned-variance paths (vdx.h: "Learned variances"; Nichol & Dhariwal 2021), level by level of an
+    S-level chain over the T-step schedule.  seq: the increasing levels the chain keeps (None: all T).  From the project's betas
+    (cosine_beta_schedule, widened) alpha_bar = cumprod(1 - beta) in float64, then for every chain -- the full one included, so that
+    seq = range(T) is the unrespaced table bit for bit -- alpha_bar'_i = alpha_bar[seq_i], beta'_i = 1 - alpha_bar'_i / alpha_bar'_{i-1}
+    (alpha_bar'_{-1} = 1) and everything else from those two: the posterior coefficients c1, c2, sqrt(1 / alpha_bar'),
+    sqrt(1 / alpha_bar' - 1), max_log = log beta' and min_log = log beta~' with min_log[0] = log beta~'_1 (the Improved-DDPM convention;
+    a one-level chain has no beta~'_1 and takes max_log[0]: level 0 adds no noise).  The network is still called with t = seq_i.
+    Returns the named float64 arrays [S] plus 'seq' (int32 [S]), 'step' (float32 [6, S]: the rows of vdx_p_sample_step_lv) and 'tab64'
+    (float64 [LV_ROWS, S]: the rows of vdx_hybrid_loss / vdx_vlb_terms_lv).  The fp32 tables of make_tables are not touched."""
+    T = int(timesteps)
+    if T < 1:
+        raise ValueError(f'timesteps must be >= 1, got {timesteps}')
+    lv = np.arange(T, dtype=np.int64) if seq is None else np.asarray(list(seq), dtype=np.int64).reshape(-1)
+    if lv.size < 1 or lv.size > T or lv[0] < 0 or lv[-1] >= T or np.any(np.diff(lv) <= 0):
+        raise ValueError(f'seq must be an increasing sequence of 1 to {T} levels in [0, {T - 1}]')
+    ac_all = np.cumprod(1.0 - cosine_beta_schedule(T).astype(np.float64))
+    ac = ac_all[lv]
+    ac_prev = np.concatenate([np.ones(1), ac[:-1]])
+    betas = 1.0 - ac / ac_prev
+    pv = betas * (1.0 - ac_prev) / (1.0 - ac)
+    max_log = np.log(betas)
+    min_log = np.log(np.concatenate([pv[1:2], pv[1:]])) if lv.size > 1 else max_log.copy()
+    t = {'betas': betas, 'alphas_cumprod': ac, 'sqrt_alphas_cumprod': np.sqrt(ac), 'sqrt_one_minus_alphas_cumprod': np.sqrt(1.0 - ac),
+         'sqrt_recip_alphas_cumprod': np.sqrt(1.0 / ac), 'sqrt_recipm1_alphas_cumprod': np.sqrt(1.0 / ac - 1.0),
+         'posterior_mean_coef1': betas * np.sqrt(ac_prev) / (1.0 - ac), 'posterior_mean_coef2': (1.0 - ac_prev) * np.sqrt(1.0 - betas) / (1.0 - ac),
+         'max_log': max_log, 'min_log': min_log}
+    step_rows = ('sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod', 'posterior_mean_coef1', 'posterior_mean_coef2', 'max_log', 'min_log')
+    t['tab64'] = np.ascontiguousarray(np.stack([t['sqrt_alphas_cumprod'], t['sqrt_one_minus_alphas_cumprod']] + [t[k] for k in step_rows] + [ac]))
+    t['step'] = np.ascontiguousarray(np.stack([t[k] for k in step_rows]).astype(np.float32))
+    t['seq'] = lv.astype(np.int32)
+    return t
+
+
+def lv_time_sequence(timesteps: int, steps=None) -> np.ndarray:
+    """The S + 1 entries of the learned-variance chain's device sequence: its levels descending, then -1 (steps None: all T levels;
+    an int S: the ddim_time_sequence(T, S) ones).  Its first S entries reversed are make_lv_tables' seq."""
+    if steps is None:
+        steps = int(timesteps)
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not 1 <= int(steps) <= int(timesteps):
+        raise ValueError(f'steps must be None or an int in [1, {int(timesteps)}], got {steps!r}')
+    return ddim_time_sequence(int(timesteps), int(steps))
+
+
 def vlb_time_sequence(timesteps: int, steps=None) -> np.ndarray:
     """The levels calc_bpd_loop visits, then -1: every level T-1 .. 0 (steps None) or the ddim_time_sequence(T, steps) ones."""
     if steps is None:
@@ -230,10 +277,30 @@ def is_list_str(x) -> bool:
 class GaussianDiffusion:
     def __init__(self, denoise_fn: Unet3D, *, image_size: int, num_frames: int, text_use_bert_cls: bool = False,
                  channels: int = 3, timesteps: int = 1000, loss_type: str = 'l1', use_dynamic_thres: bool = False,
-                 dynamic_thres_percentile: float = 0.9, sample_act_bf16: bool = True):
+                 dynamic_thres_percentile: float = 0.9, sample_act_bf16: bool = True, learned_variance: bool = False,
+                 vlb_weight: Optional[float] = None):
         # sample_act_bf16 (extension): with a mode='bf16' Unet3D the sampling loops store the UNet's inter-kernel activations
         # as bf16 (vdx_set_activation_storage); training forwards are unaffected
         self.sample_act_bf16 = sample_act_bf16
+        # learned_variance (extension, off by default; Nichol & Dhariwal 2021): the denoiser has out_dim = 2 * channels, eps_hat | v, and
+        # log sigma^2 = f log beta + (1 - f) log beta~ with f = (v + 1) / 2.  Training minimises the hybrid loss L_simple + vlb_weight * L_vlb
+        # (vlb_weight defaults to timesteps / 1000, lambda = 0.001 on the T-term sum; last_loss_terms keeps the device doubles (mse, vb) of
+        # the last loss), sampling and calc_bpd_loop use the model's variance; steps=S samples with the respaced S-level chain.
+        self.learned_variance = bool(learned_variance)
+        self.vlb_weight = None
+        self.last_loss_terms = None
+        if self.learned_variance:
+            if getattr(denoise_fn, 'out_dim', None) != 2 * channels:
+                raise ValueError(f'learned_variance needs a denoiser with out_dim == 2 * channels = {2 * channels}, got '
+                                 f'{getattr(denoise_fn, "out_dim", None)}')
+            if use_dynamic_thres:
+                raise ValueError('learned_variance does not support use_dynamic_thres (a follow-up)')
+            if int(timesteps) < 2:
+                raise ValueError(f'learned_variance needs timesteps >= 2, got {timesteps}')
+            self.vlb_weight = float(timesteps) / 1000.0 if vlb_weight is None else float(vlb_weight)
+            self._lv_cache = {}
+        elif vlb_weight is not None:
+            raise ValueError('vlb_weight is the weight of the hybrid loss: it needs learned_variance=True')
         self.channels = channels
         self.image_size = image_size
         self.num_frames = num_frames
@@ -304,11 +371,100 @@ class GaussianDiffusion:
                                       L.stream_ptr()))
         return s
 
+    # -- learned variances ---------------------------------------------------------------------------
+    def _lv_refuse(self, **given):
+        """ValueError for what the learned-variance paths do not serve yet (follow-ups: they need only the eps half)."""
+        if not self.learned_variance:
+            return
+        off = dict(cond_scale=1.0, guidance_rescale=0.0)
+        for name, val in given.items():
+            if val is None or val is False or (name in off and float(val) == off[name]):
+                continue
+            raise ValueError(f'learned_variance does not support {name} yet (a follow-up; DESIGN.md 9)')
+
+    def _lv_tables(self, steps=None):
+        """(descending device sequence [S + 1], float32 step table [6, S], S) of the S-level learned-variance chain, kept per S: the
+        captured step bakes the addresses in."""
+        seq_host = lv_time_sequence(self.num_timesteps, steps)
+        S = len(seq_host) - 1
+        if S not in self._lv_cache:
+            tabs = make_lv_tables(self.num_timesteps, seq_host[:-1][::-1])
+            self._lv_cache[S] = (torch.from_numpy(seq_host).to(self.device), torch.from_numpy(tabs['step']).to(self.device))
+        return self._lv_cache[S] + (S,)
+
+    def _lv_tab64(self):
+        """The [LV_ROWS, T] float64 table of the hybrid loss and the bound, on the device."""
+        if 'tab64' not in self._lv_cache:
+            self._lv_cache['tab64'] = torch.from_numpy(make_lv_tables(self.num_timesteps)['tab64']).to(self.device)
+        return self._lv_cache['tab64']
+
+    def _lv_out(self, x, t32, cond):
+        if is_list_str(cond):
+            raise NotImplementedError('pass text conditioning as a ready embedding tensor')
+        return self.denoise_fn(x, t32, cond=cond)
+
+    def model_log_variance(self, out2, t):
+        """log sigma^2 [B,C,F,H,W] of the network output out2 [B,F,H,W,2C] at levels t of the full chain (torch, on out2's device)."""
+        tab = self._lv_tab64()
+        v = out2[..., self.channels:].permute(0, 4, 1, 2, 3).double()
+        f = 0.5 * (v + 1.0)
+        shape = (-1, 1, 1, 1, 1)
+        return (f * tab[6][t.long()].reshape(shape) + (1.0 - f) * tab[7][t.long()].reshape(shape)).float()
+
+    def hybrid_loss(self, x_start, noise, out2, t32, *, want_grad: bool = False, _pre=(1.0, 0.0)):
+        """(loss, d_out): the hybrid loss of the network output out2 [B,F,H,W,2C] as a float32 device scalar and, with want_grad, its
+        gradient in out2 (vdx_hybrid_loss: one pass, no host read).  last_loss_terms = the device doubles (mse, vb)."""
+        B = x_start.shape[0]
+        scratch = torch.empty(L.vdx_hybrid_scratch_doubles(B), dtype=torch.float64, device=self.device)
+        out = torch.empty(2 * B + 3, dtype=torch.float64, device=self.device)
+        d_out = torch.empty_like(out2) if want_grad else None
+        L.check(L.vdx_hybrid_loss(L.ptr(x_start), L.ptr(noise), L.ptr(out2), L.ptr(t32), L.ptr(self._lv_tab64()), self.num_timesteps,
+                                  float(_pre[0]), float(_pre[1]), int(self.loss_type == 'l2'), self.vlb_weight, int(want_grad), L.ptr(d_out),
+                                  L.ptr(scratch), L.ptr(out), B, self.channels, self._per_sample(x_start), L.stream_ptr()))
+        self.last_loss_terms = out[2 * B:2 * B + 2]
+        self.last_loss_per_sample = out[:2 * B].reshape(B, 2)
+        return out[2 * B + 2].to(torch.float32).reshape(()), d_out
+
+    def _p_step_lv(self, x, t32, cond, clip_denoised, key, noise, zero_noise=False):
+        out2 = self._lv_out(x, t32, cond)
+        _, tab, _ = self._lv_tables(None)
+        out = torch.empty_like(x)
+        nz = torch.zeros_like(x) if zero_noise else (None if noise is None else self._dev(noise))
+        L.check(L.vdx_p_sample_step_lv(L.ptr(x), L.ptr(out2), L.ptr(out), L.ptr(t32), L.ptr(tab), self.num_timesteps, 0, 0, L.ptr(nz),
+                                       int(key or 0) & 0xFFFFFFFFFFFFFFFF, 0, 0, int(clip_denoised), 1.0, 0.0, x.shape[0], self.channels,
+                                       self._per_sample(x), L.stream_ptr()))
+        return out, out2
+
+    def _run_chain_lv(self, B, key, *, steps=None, cond=None, use_graph=True, x_T=None):
+        """The learned-variance ancestral chain on the current stream (inside _sampling()): S = steps (None: T) levels, one captured
+        step (vdx_p_sample_loop_lv), x_T = Philox(key, draw 0), step k draws 1 + k; unnormalize_img is folded into the last step."""
+        unet, T, dev = self.denoise_fn, self.num_timesteps, self.device
+        seed = int(key) & 0xFFFFFFFFFFFFFFFF
+        seq, tab, S = self._lv_tables(steps)
+        shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
+        img = self.randn(shape, seed, 0) if x_T is None else self._dev(x_T).clone()
+        out2 = torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=dev)
+        t_dev = torch.full((B,), int(seq[0]), dtype=torch.int32, device=dev)
+        step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
+        h = unet.handle(self.num_frames, self.image_size)
+        unet.apply_activation_storage(h)
+        ws = unet.workspace(B, self.num_frames, self.image_size)
+        L.check(L.vdx_p_sample_loop_lv(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(out2), L.ptr(t_dev), L.ptr(step_dev),
+                                       L.ptr(tab), L.ptr(seq), S, T, S, L.ptr(condd), seed, 1, 0.5, 0.5, L.ptr(ws), ws.numel(), B, int(use_graph),
+                                       L.stream_ptr()))
+        return img
+
     # -- reverse process ---------------------------------------------------------------------------
     def p_mean_variance(self, x, t, clip_denoised: bool, cond=None, cond_scale: float = 1.0):
-        """reference :162-228 (returns (mean, variance, log_variance))."""
+        """reference :162-228 (returns (mean, variance, log_variance)).  learned_variance: the model's variance, per element."""
         x = self._dev(x)
         t32 = self._dev(t, torch.int32)
+        if self.learned_variance:
+            self._lv_refuse(cond_scale=cond_scale)
+            mean, out2 = self._p_step_lv(x, t32, cond, clip_denoised, 0, None, zero_noise=True)
+            logvar = self.model_log_variance(out2, t32)
+            return mean, logvar.exp(), logvar
         eps_hat = self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
         thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
         mean = torch.empty_like(x)
@@ -322,6 +478,9 @@ class GaussianDiffusion:
         """reference :231-261.  `key`: seed of the noise draw (ignored when explicit `noise` is given)."""
         x = self._dev(x)
         t32 = self._dev(t, torch.int32)
+        if self.learned_variance:
+            self._lv_refuse(cond_scale=cond_scale)
+            return self._p_step_lv(x, t32, cond, clip_denoised, key, noise)[0]
         eps_hat = self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
         thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
         out = torch.empty_like(x)
@@ -472,7 +631,7 @@ class GaussianDiffusion:
                                              B, self.channels, per, L.stream_ptr()))
 
     def p_sample_loop(self, shape, key, cond=None, cond_scale: float = 1.0, *, use_graph: bool = True, x_T=None,
-                      guidance_rescale: float = 0.0, focus_present=None):
+                      guidance_rescale: float = 0.0, focus_present=None, steps: Optional[int] = None):
         """reference :264-320.  As there, the caller's spatial `shape` is replaced by the model's own (Q10).
 
         x_T = Philox(key, draw 0); step k (t = T-1-k) uses draw 1+k.  Returns unnormalize_img(x_0) in [0,1].
@@ -480,8 +639,16 @@ class GaussianDiffusion:
         step, inside the captured step like the unguided loop; _run_chain) -- an EXTENSION, parity unpinned: the reference drops cond
         here.  guidance_rescale phi in [0, 1] (extension; Lin et al. 2023, sec. 3.4): the guided eps is scaled per sample by
         phi std(eps(c)) / std(eps_guided) + 1 - phi; 0 = off.
+        steps (learned_variance only): sample with the respaced S-level ancestral chain (make_lv_tables) instead of all T levels.
         """
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        if self.learned_variance:
+            self._lv_refuse(cond_scale=cond_scale, guidance_rescale=guidance_rescale, focus_present=focus_present)
+            lv_time_sequence(self.num_timesteps, steps)                   # (its range check, before any device work)
+            with self._sampling(None, int(shape[0])):
+                return self._run_chain_lv(int(shape[0]), key, steps=steps, cond=cond, use_graph=use_graph, x_T=x_T)
+        if steps is not None:
+            raise ValueError('steps is the respaced chain of a learned_variance diffusion; use ddim_steps / dpm_steps otherwise')
         with self._sampling(focus_present, int(shape[0])):
             return self._run_chain('ddpm', int(shape[0]), key, cond=cond, cond_scale=cond_scale, guidance_rescale=guidance_rescale,
                                    use_graph=use_graph, x_T=x_T)
@@ -491,6 +658,7 @@ class GaussianDiffusion:
         """DDIM sampling with eta = 0 in `steps` network evaluations (EXTENSION, BASELINE.json configs[3]; the reference has ancestral
         sampling only).  x_T = Philox(key, draw 0), deterministic afterwards.  Returns unnormalize_img(x_0) in [0, 1].  cond with
         cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
+        self._lv_refuse(ddim_steps=steps)
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         ddim_time_sequence(self.num_timesteps, steps)                     # (its range check, before any device work)
         with self._sampling(focus_present, int(shape[0])):
@@ -503,6 +671,7 @@ class GaussianDiffusion:
         data-prediction multistep form, the step of vdx.h).  order 2 reaches in 15-25 steps what DDIM (= order 1) needs about 100 for;
         the cost per step is DDIM's plus one history tensor.  x_T = Philox(key, draw 0), deterministic afterwards.  Returns
         unnormalize_img(x_0) in [0, 1].  cond with cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
+        self._lv_refuse(dpm_steps=steps)
         check_dpm_args(self.num_timesteps, steps, order)
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         with self._sampling(focus_present, int(shape[0])):
@@ -517,7 +686,9 @@ class GaussianDiffusion:
         deterministic.  timesteps None: all T levels, T-1 .. 0; an int S: the ddim_time_sequence(T, S) levels, a cheap per-t curve.
         cond is used un-masked, as the unguided sampling loops use it.  Returns CPU float64 tensors: vb, mse, xstart_mse [B,S] (column
         k = level t[k]), t [S], prior_bpd [B] and total_bpd [B] = prior_bpd + sum_t vb, None unless every level was visited.
-        The model's variance is the posterior variance p_sample uses; the dynamic threshold has no place in the bound."""
+        The model's variance is the posterior variance p_sample uses; the dynamic threshold has no place in the bound.
+        learned_variance: the KL and decoder terms use the model's own log sigma^2 (vdx_vlb_loop_lv)."""
+        self._lv_refuse(focus_present=focus_present)
         return self._bpd_chain(x, key, cond, clip_denoised, timesteps, use_graph, focus_present, None)
 
     def _bpd_chain(self, x, key, cond, clip_denoised, timesteps, use_graph, focus_present, pieces):
@@ -533,7 +704,8 @@ class GaussianDiffusion:
             raise ValueError(f'x must be [B, {shape[0]}, {shape[1]}, {shape[2]}, {shape[3]}], got {tuple(x.shape)}')
         from . import ops
         B, seed = x.shape[0], int(key) & 0xFFFFFFFFFFFFFFFF
-        tab = torch.from_numpy(make_vlb_tables(T)).to(dev)
+        tab = self._lv_tab64() if self.learned_variance else torch.from_numpy(make_vlb_tables(T)).to(dev)
+        vlb_loop = L.vdx_vlb_loop_lv if self.learned_variance else L.vdx_vlb_loop
         with self._sampling(focus_present, B):
             xd = self._dev(x)
             condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
@@ -549,7 +721,7 @@ class GaussianDiffusion:
             unet.apply_activation_storage(h)
             ws = unet.workspace(B, self.num_frames, self.image_size)
             for n in (pieces or (S,)):
-                L.check(L.vdx_vlb_loop(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(xd), L.ptr(xt), L.ptr(eps), L.ptr(t_dev),
+                L.check(vlb_loop(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(xd), L.ptr(xt), L.ptr(eps), L.ptr(t_dev),
                                        L.ptr(step_dev), L.ptr(tab), T, L.ptr(seq), S, int(n), L.ptr(condd), seed, int(bool(clip_denoised)),
                                        L.ptr(partial), L.ptr(out), L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
             res = out.cpu()
@@ -571,15 +743,24 @@ class GaussianDiffusion:
         return (shard_key(key, rank, world), per) + tuple(None if t is None else t[rank * per:(rank + 1) * per] for t in tensors)
 
     def sample(self, key, cond=None, cond_scale: float = 1.0, batch_size: int = 16, *, ddim_steps: Optional[int] = None,
-               dpm_steps: Optional[int] = None, dpm_order: int = 2, guidance_rescale: float = 0.0, focus_present=None, **kw):
+               dpm_steps: Optional[int] = None, dpm_order: int = 2, guidance_rescale: float = 0.0, focus_present=None,
+               steps: Optional[int] = None, **kw):
         """reference :323-357.  ddim_steps (extension): sample with an S-step DDIM chain instead of the T-step ancestral one.
         dpm_steps (extension): an S-step DPM-Solver++(2M) chain of order dpm_order (dpm_sample_loop); not together with ddim_steps.
         guidance_rescale (extension): the rescale phi in [0, 1] of the guided loops (cond given, cond_scale != 1; p_sample_loop).
+        steps (extension, learned_variance only): the respaced S-level ancestral chain with the model's variance (p_sample_loop).
 
         Data parallel (reference :278-298: the batch is split over the local devices, `P('data')`): inside an initialised
         torch.distributed group of W > 1 ranks, `batch_size` (and `cond`) describe the GLOBAL batch; rank r draws videos
         [r * per, (r + 1) * per), per = batch_size / W, from its own Philox stream shard_key(key, r) and returns ITS shard --
         no data-path collective.  W = 1 uses `key` itself (single-process behaviour unchanged)."""
+        self._lv_refuse(cond_scale=cond_scale, ddim_steps=ddim_steps, dpm_steps=dpm_steps, guidance_rescale=guidance_rescale,
+                        focus_present=focus_present)
+        if steps is not None:
+            if not self.learned_variance:
+                raise ValueError('steps is the respaced chain of a learned_variance diffusion; use ddim_steps / dpm_steps otherwise')
+            lv_time_sequence(self.num_timesteps, steps)                       # (its range check, before any device work)
+            kw['steps'] = int(steps)
         check_dpm_args(self.num_timesteps, dpm_steps, dpm_order, ddim_steps)
         kw['guidance_rescale'] = check_guidance_rescale(guidance_rescale)
         if is_list_str(cond):
@@ -613,6 +794,7 @@ class GaussianDiffusion:
         clean_context=True is for a denoiser trained with frame conditioning (Trainer.frame_cond_max > 0; RaMViD, Hoeppe et al. 2022):
         the known region is `video` itself, un-noised, in the start tensor and after every step of all three chains (the same kernels
         with the (1, 0) mask table, vdx.h), as such a network saw its context frames in training.  Not with resample_steps > 1."""
+        self._lv_refuse(inpaint=True)
         if focus_present is not None:
             raise ValueError('inpaint / extend do not take focus_present (frame-conditioned sampling of a focus-present sample is out of scope)')
         opts = self._inpaint_options(video, dict(cond_scale=cond_scale, ddim_steps=ddim_steps, resample_steps=resample_steps, use_graph=use_graph,
@@ -672,6 +854,7 @@ class GaussianDiffusion:
         defaults to num_frames // 2).  Window keys: split_key(key, n_windows).  Returns [B,C,F0 + N,H,W]; its first F0 frames are
         `video` itself.  Data parallel as sample(): sharded once (rows and shard_key), not per window.  clean_context=True (with a
         frame-conditioned denoiser): every window keeps its context frames un-noised, see inpaint()."""
+        self._lv_refuse(extend=True)
         ctx = self.num_frames // 2 if context_frames is None else int(context_frames)
         video = torch.as_tensor(video)
         if video.dim() != 5 or tuple(video.shape[1:2] + video.shape[3:]) != (self.channels, self.image_size, self.image_size):
@@ -736,6 +919,7 @@ class GaussianDiffusion:
         elements, sum / max(count, 1), formed on the device (vdx_loss_sum_masked)."""
         if self.loss_type not in ('l1', 'l2'):
             raise ValueError(f'Unsupported loss type: {self.loss_type}')
+        self._lv_refuse(frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
         x_start = self._dev(x_start)
         t32 = self._dev(t, torch.int32)
         if noise is None:
@@ -748,6 +932,8 @@ class GaussianDiffusion:
         if is_list_str(cond):
             raise NotImplementedError('pass text conditioning as a ready embedding tensor')
         eps_hat = self.denoise_fn(x_noisy, t32, cond=cond, **kwargs)
+        if self.learned_variance:                                         # eps_hat | v -> the hybrid loss, the total as the value
+            return self.hybrid_loss(x_start, noise, eps_hat, t32, _pre=_pre)[0]
         B = x_start.shape[0]
         fhw = self._per_sample(x_start) // self.channels
         if mk is not None:

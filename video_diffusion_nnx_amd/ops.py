@@ -816,3 +816,56 @@ def vlb_prior(x, tables):
     out = torch.empty(B, dtype=torch.float64, device=x.device)
     L.check(_vlb_prior(L.ptr(x), L.ptr(tables), T, L.ptr(partial), L.ptr(out), B, per, L.stream_ptr()))
     return out
+
+
+# ---- learned variances (vdx.h: "Learned variances"): out2 = the network's channel-last output [B,F,H,W,2C], eps_hat | v ----
+
+def p_sample_step_lv(x, out2, tables, *, level=None, step=0, step_dev=None, noise=None, seed=0, offset=0, dev_offset=None, clip=True,
+                     post=(1.0, 0.0), out=None):
+    """One reverse step with the model's variance.  x [B,C,F,H,W], tables float32 [6, S] (make_lv_tables(...)['step']); the level is
+    `level` (int32 [B] on the device) or S - 1 - (step + *step_dev).  z = `noise` or Philox(seed, offset + *dev_offset).  out may be x."""
+    assert x.dtype == torch.float32 and x.dim() == 5 and tables.dtype == torch.float32 and tables.shape[0] == 6
+    B, per = x.shape[0], x.numel() // x.shape[0]
+    out = torch.empty_like(x) if out is None else out
+    L.check(L.vdx_p_sample_step_lv(L.ptr(x), L.ptr(out2), L.ptr(out), L.ptr(level), L.ptr(tables), tables.shape[1], int(step), L.ptr(step_dev),
+                                   L.ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset), L.ptr(dev_offset), int(bool(clip)), float(post[0]),
+                                   float(post[1]), B, x.shape[1], per, L.stream_ptr()))
+    return out
+
+
+def hybrid_loss(x, noise, out2, t, tables64, *, pre=(1.0, 0.0), l2=False, vlb_weight=1.0, want_grad=True):
+    """mean |eps_hat - eps|^p + vlb_weight * mean vb (bits per element, eps_hat detached) -> (out float64 [2B + 3] = per-sample means
+    (mse, vb) then the batch's (mse, vb, total), d_out float32 like out2 or None).  x [B,C,F,H,W] (x0 = x pre[0] + pre[1]), t int32 [B],
+    tables64 float64 [LV_ROWS, T] (make_lv_tables(T)['tab64'])."""
+    assert x.dtype == torch.float32 and x.dim() == 5 and tables64.dtype == torch.float64 and tables64.shape[0] == L.LV_ROWS
+    B, per = x.shape[0], x.numel() // x.shape[0]
+    scratch = torch.empty(L.vdx_hybrid_scratch_doubles(B), dtype=torch.float64, device=x.device)
+    out = torch.empty(2 * B + 3, dtype=torch.float64, device=x.device)
+    d_out = torch.empty_like(out2) if want_grad else None
+    L.check(L.vdx_hybrid_loss(L.ptr(x), L.ptr(noise), L.ptr(out2), L.ptr(t), L.ptr(tables64), tables64.shape[1], float(pre[0]), float(pre[1]),
+                              int(bool(l2)), float(vlb_weight), int(bool(want_grad)), L.ptr(d_out), L.ptr(scratch), L.ptr(out), B, x.shape[1], per,
+                              L.stream_ptr()))
+    return out, d_out
+
+
+def vlb_terms_lv(x, out2, t, tables64, *, noise=None, seed=0, draw=0, step_dev=None, clip=True):
+    """vlb_terms with the model's variance: out2 [B,F,H,W,2C], tables64 float64 [LV_ROWS, T] -> float64 [B, 3] = (vb, mse, xstart_mse)."""
+    assert x.dtype == torch.float32 and x.dim() == 5 and tables64.dtype == torch.float64 and tables64.shape[0] == L.LV_ROWS
+    B, per = x.shape[0], x.numel() // x.shape[0]
+    partial = torch.empty(_vlb_scratch(B), dtype=torch.float64, device=x.device)
+    out = torch.empty(B, 3, dtype=torch.float64, device=x.device)
+    L.check(L.vdx_vlb_terms_lv(L.ptr(x), L.ptr(out2), L.ptr(t), L.ptr(tables64), tables64.shape[1], L.ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                               int(draw), L.ptr(step_dev), int(bool(clip)), L.ptr(partial), L.ptr(out), B, x.shape[1], per, L.stream_ptr()))
+    return out
+
+
+def final_conv_backward_wide(x, d_out, kernel, scratch=None):
+    """final_conv_backward for up to 6 output channels (the eps | v head of a learned-variance network)."""
+    D_, cout = kernel.shape[-2], kernel.shape[-1]
+    npix = x.numel() // D_
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    dw = torch.zeros(D_, cout, dtype=torch.float32, device=x.device)
+    db = torch.zeros(cout, dtype=torch.float32, device=x.device)
+    L.check(L.vdx_final_conv_backward_wide(L.ptr(x), _is16(x), L.ptr(d_out), L.ptr(kernel.contiguous()), L.ptr(dx), L.ptr(dw), L.ptr(db), npix, D_, cout,
+                                           L.ptr(scratch), 0 if scratch is None else scratch.numel(), L.stream_ptr()))
+    return dx, dw, db

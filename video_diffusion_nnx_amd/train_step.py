@@ -209,6 +209,8 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
             elif fp.device.type == 'cpu' and dev.type == 'cuda':
                 fp = fp.pin_memory().to(dev, non_blocking=True)           # as t: no pageable copy, no host sync
     tr.last_focus_mask = focus_present_mask if unet.focus_present else None
+    if gd.learned_variance:
+        gd._lv_refuse(frame_mask=frame_mask, focus_present=fp)
     x_noisy = gd.q_sample(x, t, noise=noise, frame_mask=mk, _pre=(2.0, -1.0))     # normalize_img folded in (:499)
     keep_storage = unet.act_bf16
     unet.act_bf16 = 2 if (unet.mode == 'bf16' and tr.train_act_bf16) else False
@@ -218,8 +220,12 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
         unet.act_bf16 = keep_storage
     fhw = x.numel() // (B * gd.channels)
     l2 = int(gd.loss_type == 'l2')
-    d_eps = torch.empty_like(eps_hat)
-    if mk is not None:
+    d_eps = None if gd.learned_variance else torch.empty_like(eps_hat)
+    if gd.learned_variance:
+        # eps_hat | v: the hybrid loss and its gradient in one pass (vdx_hybrid_loss); the returned loss is the total, gd.last_loss_terms
+        # keeps the device (mse, vb)
+        loss, d_eps = gd.hybrid_loss(x, noise, eps_hat, t, want_grad=True, _pre=(2.0, -1.0))
+    elif mk is not None:
         loss, acc = gd.masked_loss(eps_hat, noise, mk)                            # acc = device (sum, count | scratch)
         L.check(vdx_loss_grad_masked(L.ptr(eps_hat), L.ptr(noise), L.ptr(mk), acc.data_ptr() + 8, L.ptr(d_eps), B, gd.channels, fhw, l2,
                                      L.stream_ptr()))
