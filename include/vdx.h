@@ -686,6 +686,50 @@ int vdx_vlb_loop_lv(vdx_handle* h, const float* params, const void* packed, cons
                     uint64_t seed, int clip_denoised, double* partial, double* out, void* workspace, size_t workspace_bytes, int batch,
                     int use_graph, void* stream);
 
+/* Cascaded super-resolution (EXTENSION, parity unpinned: no reference code.  Ho et al. 2021, "Cascaded Diffusion Models"; the second
+ * stage of Video Diffusion Models / Imagen Video).  Off unless these entries are called: the eleven loops above keep refusing a network
+ * with out_dim != channels and perform the launches they always did.  The denoiser has channels = 2 C and out_dim = C; its input is
+ *   xin [batch, 2C, F, S, S]:  planes [0, C) of each sample = x_t,  planes [C, 2C) = u = aug(up(2 lo - 1))
+ * with lo [batch, C, F/ft, S/fs, S/fs] in [0, 1] the low-resolution clip (ft, fs >= 1 integers dividing F and S; (1, 1) = plain concat
+ * conditioning).  up: separable linear interpolation in frames, rows and columns with half-pixel centres, src = (dst + 0.5) in / out - 0.5,
+ * neighbours clamped at both edges (torch's interpolate(mode='trilinear', align_corners=False)); normalise first, then interpolate.
+ * aug: noise conditioning augmentation, blind (the network is not told the level): per sample u = sqrt_ac[s_b] up + sqrt(1 - ac[s_b]) z
+ * with z = Philox(seed, draw) over the element index of [batch, C, F, S, S] as vdx_randn lays it out; s_b < 0 (or aug_level NULL): u = up
+ * exactly, nothing is drawn.  Levels above timesteps - 1 are read as timesteps - 1.
+ *
+ * vdx_lowres_down: lo = the box mean of x [batch, C, F, S, S] over ft x fs x fs blocks: an fp32 sum in (frame, row, column) order, then one
+ *   multiply by 1 / n (ft = fs = 1: the bits of x).
+ * vdx_lowres_input: one pass over both halves of xin.  x0 != NULL: planes [0, C) = sqrt_ac[t] (x0 pre_scale + pre_shift) + sqrt_1m_ac[t]
+ *   noise, vdx_q_sample's expression and bits; x0 == NULL: only planes [C, 2C) are written (the sampling-time form; t / noise are not
+ *   read).  Any S and per_sample, sample bases off 16 bytes included.
+ * vdx_lowres_pack: xin[b, 0 : per_sample] = img[b, :] for img [batch, per_sample] and xin rows of pitch 2 per_sample; the second half
+ *   of every row is not touched.  float4 where per_sample % 4 == 0 and both bases are 16-byte aligned, scalar otherwise.
+ * vdx_p_sample_loop_sr / vdx_ddim_sample_loop_sr / vdx_dpm_sample_loop_sr: vdx_p_sample_loop_dyn / vdx_ddim_sample_loop_dyn /
+ *   vdx_dpm_sample_loop (same arguments and contract) with xin after img: img / eps_buf / hist are over C = out_dim channels, the step is
+ *   vdx_lowres_pack(img -> xin) -> forward on xin -> (dynamic threshold) -> the unchanged step kernel on img -> advance.  The caller fills
+ *   planes [C, 2C) of xin once (vdx_lowres_input with x0 = NULL; draw VDX_DRAW_LOWRES of the chain's seed when augmented).  Graph slots
+ *   of their own: no other loop's graph is evicted.
+ * Refused before any launch: a NULL pointer, a network whose channels is not 2 * out_dim ("channels must equal 2 * out_dim"), img / xin
+ *   off 16 bytes (VDX_ERR_INVALID); a handle created without a GPU (VDX_ERR_STATE). */
+#define VDX_DRAW_LOWRES (1ull << 61)
+int vdx_lowres_down(const float* x, float* lo, int batch, int channels, int frames, int size, int ft, int fs, void* stream);
+int vdx_lowres_input(const float* x0, const int* t, const float* noise, const float* lo, const int* aug_level, float* xin, const float* sqrt_ac,
+                     const float* sqrt_one_minus_ac, int timesteps, uint64_t seed, uint64_t draw, float pre_scale, float pre_shift, int batch,
+                     int channels, int frames, int size, int ft, int fs, void* stream);
+int vdx_lowres_pack(const float* img, float* xin, int batch, long per_sample, void* stream);
+int vdx_p_sample_loop_sr(vdx_handle* h, const float* params, const void* packed, float* img, float* xin, float* eps_buf, int* t_dev,
+                         uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                         int clip_denoised, float percentile, float* thres_buf, void* workspace, size_t workspace_bytes, int batch,
+                         int use_graph, void* stream);
+int vdx_ddim_sample_loop_sr(vdx_handle* h, const float* params, const void* packed, float* img, float* xin, float* eps_buf, int* t_dev,
+                            uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                            int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf, void* workspace,
+                            size_t workspace_bytes, int batch, int use_graph, void* stream);
+int vdx_dpm_sample_loop_sr(vdx_handle* h, const float* params, const void* packed, float* img, float* xin, float* eps_buf, float* hist,
+                           int* t_dev, uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps,
+                           const float* cond, int clip_denoised, int order, const float* tables, int timesteps, float percentile,
+                           float* thres_buf, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */

@@ -7,7 +7,10 @@ Extensions: --mode {bf16,f16,f32}; --random-init (no checkpoint); --timesteps N 
 --context PATH.npy [--context-frames K] [--extend-frames N] [--resample-steps U] (video prediction / extension from given frames);
 --clean-context (with --context, for a checkpoint trained with train.py --frame_cond_max: the given frames stay un-noised at every step);
 --cond-path FILE.npy [--cond-scale 2.0] [--guidance-rescale 0.0] (classifier-free guidance with ready-made embeddings: the rows of the
-float32 [B, cond_dim] file are the batch; needs a config with use_bert_text_cond; works with --ddim-steps and --dpm-steps)."""
+float32 [B, cond_dim] file are the batch; needs a config with use_bert_text_cond; works with --ddim-steps and --dpm-steps);
+--lowres-path FILE.npy [--lowres-aug-level s] (the second stage of a cascade: a config with diffusion.lowres_cond upsamples the
+[N,C,f,s,s] clips of the file; works with --ddim-steps and --dpm-steps); --save-npy (also write samples.npy, float32 [B,C,F,H,W] in
+[0,1], beside the gifs: what a second stage reads with --lowres-path)."""
 import argparse
 import logging
 import os
@@ -49,6 +52,12 @@ FLAGS = (   # (flag, kwargs)
                                                       'classifier-free guidance, needs a config with use_bert_text_cond')),
     ('--cond-scale', dict(type=float, default=2.0, help='with --cond-path: guidance scale s in eps(0) + s (eps(c) - eps(0)); 1 = no guidance')),
     ('--guidance-rescale', dict(type=float, default=0.0, help='with --cond-path: guidance rescale phi in [0, 1] (Lin et al. 2023); 0 = off')),
+    ('--lowres-path', dict(type=str, default=None, help='super-resolution configs (diffusion.lowres_cond): [N,C,f,s,s] .npy of low-resolution '
+                                                        'clips (float in [0,1], or uint8 / 255) to upsample; sets the batch')),
+    ('--lowres-aug-level', dict(type=int, default=None, help='with --lowres-path: noise the upsampled clips to level s before conditioning on '
+                                                             'them (noise conditioning augmentation at sampling time; default: none)')),
+    ('--save-npy', dict(action='store_true', help='also write samples.npy (float32 [B,C,F,H,W] in [0,1]) beside the gifs, for any sampler: '
+                                                  'the input of a second stage (--lowres-path)')),
 )
 
 
@@ -57,18 +66,23 @@ def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=Fa
     argument like dim: checkpoints do not store it, so a model trained with it is sampled with it.  focus_present: the same for the
     focus-present switch (unet.focus_present in the YAML, absent = false).  diffusion.learned_variance (absent = false; optionally with
     diffusion.vlb_weight): the UNet gets out_dim = 2 * channels (eps | v) and the diffusion the learned-variance paths; checkpoints do not
-    store the switch, the final conv's shape does (load_state_dict fails loudly on a mismatch)."""
+    store the switch, the final conv's shape does (load_state_dict fails loudly on a mismatch).  diffusion.lowres_cond: {temporal: ft,
+    spatial: fs, aug_max: L} (absent = off): a super-resolution stage -- the UNet gets channels = 2 * channels, out_dim = channels and
+    the diffusion lowres_cond=(ft, fs), lowres_aug_max=L (aug_max absent = 0); again the conv shapes are what a checkpoint stores."""
     from video_diffusion_nnx_amd.gaussian_diffusion import GaussianDiffusion
     from video_diffusion_nnx_amd.unet3d import Rngs, Unet3D
     u, d = cfg['unet'], cfg['diffusion']
     lv = bool(d.get('learned_variance', False))
     lv_kw = dict(learned_variance=True, vlb_weight=d.get('vlb_weight')) if lv else {}
-    unet = Unet3D(**(dict(out_dim=2 * u['channels']) if lv else {}), dim=u['dim'], rngs=Rngs(u['rngs_seed']), dim_mults=tuple(u['dim_mults']), channels=u['channels'],
+    sr = d.get('lowres_cond')
+    sr_kw = dict(lowres_cond=(sr['temporal'], sr['spatial']), lowres_aug_max=sr.get('aug_max', 0)) if sr else {}
+    unet = Unet3D(**(dict(out_dim=2 * u['channels']) if lv else dict(out_dim=u['channels']) if sr else {}), dim=u['dim'], rngs=Rngs(u['rngs_seed']),
+                  dim_mults=tuple(u['dim_mults']), channels=(2 if sr else 1) * u['channels'],
                   use_bert_text_cond=u['use_bert_text_cond'], mode=mode, attn_fp8=attn_fp8,
                   temporal_pos_bias=bool(temporal_pos_bias or u.get('temporal_pos_bias', False)),
                   focus_present=bool(focus_present or u.get('focus_present', False)))
     gd = GaussianDiffusion(denoise_fn=unet, image_size=d['image_size'], num_frames=d['num_frames'], channels=d['channels'],
-                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'], **lv_kw)
+                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'], **lv_kw, **sr_kw)
     return unet, gd
 
 
@@ -93,6 +107,16 @@ def load_context(path, num_frames, context_frames=None, extend_frames=0):
     return np.ascontiguousarray(v[:, :, :k]), total - k
 
 
+def load_lowres(path, shape):
+    """--lowres-path: the clips to upsample as float32 [N, *shape] in [0,1] (shape = (C, F/ft, S/fs, S/fs) of the config)."""
+    import numpy as np
+    v = np.load(path)
+    if v.ndim != 5 or v.shape[0] < 1 or tuple(v.shape[1:]) != tuple(shape):
+        raise ValueError(f'--lowres-path must hold a [N, {", ".join(str(n) for n in shape)}] array, got shape {v.shape}')
+    v = v.astype(np.float32) / 255.0 if v.dtype == np.uint8 else v.astype(np.float32)
+    return np.ascontiguousarray(v)
+
+
 def load_cond(path, cond_dim):
     """--cond-path: the float32 [B, cond_dim] conditions of the batch."""
     import numpy as np
@@ -115,6 +139,10 @@ def main(argv=None):
         ap.error('--steps is the respaced learned-variance chain: not with --ddim-steps / --dpm-steps / --context / --cond-path')
     if a.cond_path and a.context:
         ap.error('--cond-path samples from noise: not together with --context')
+    if a.lowres_path and (a.context or a.cond_path or a.steps is not None or a.focus_present):
+        ap.error('--lowres-path upsamples given clips: not together with --context / --cond-path / --steps / --focus-present')
+    if a.lowres_aug_level is not None and not a.lowres_path:
+        ap.error('--lowres-aug-level needs --lowres-path')
     if not 0.0 <= a.guidance_rescale <= 1.0:
         ap.error(f'--guidance-rescale must be in [0, 1], got {a.guidance_rescale}')
     if a.clean_context and not a.context:
@@ -166,11 +194,25 @@ def _run(a, ap, rank, world):
         if not gd.learned_variance:
             ap.error('--steps needs a config with diffusion.learned_variance: true')
         fp_kw['steps'] = a.steps
+    if bool(a.lowres_path) != (gd.lowres_cond is not None):
+        ap.error('--lowres-path and a config with diffusion.lowres_cond go together: a super-resolution model needs the clips to upsample, '
+                 'any other model takes none')
+    if world > 1 and a.lowres_path:
+        ap.error('--lowres-path runs in a single process')
     if not a.random_init:
         ckpt = pathlib.Path(a.checkpoint_path).resolve()
         gd, _ = load_checkpoint(gd, a.step, str(ckpt), load_ema_params=a.load_ema_params)
         logging.info('restored step %d from %s', a.step, ckpt)
-    if a.context:
+    if a.lowres_path:
+        import torch
+        ft, fs = gd.lowres_cond
+        try:
+            lowres = load_lowres(a.lowres_path, (gd.channels, gd.num_frames // ft, gd.image_size // fs, gd.image_size // fs))
+            videos = gd.sample(a.seed, lowres=torch.from_numpy(lowres), lowres_aug_level=a.lowres_aug_level, ddim_steps=a.ddim_steps,
+                               dpm_steps=a.dpm_steps, dpm_order=a.dpm_order)
+        except ValueError as e:
+            ap.error(str(e))
+    elif a.context:
         import torch
         try:
             ctx, n_new = load_context(a.context, gd.num_frames, a.context_frames, a.extend_frames)
@@ -201,6 +243,11 @@ def _run(a, ap, rank, world):
         dist.all_reduce(mm, op=dist.ReduceOp.MIN)
         lo_hi = (float(mm[0].item()), float(-mm[1].item()))
     first = rank * len(videos)
+    if a.save_npy:
+        import numpy as np
+        target = out_dir / ('samples.npy' if world == 1 else f'samples_rank{rank}.npy')
+        np.save(target, videos.cpu().numpy().astype(np.float32))
+        logging.info('wrote %s', target)
     for i, frames in enumerate(videos_to_uint8(videos.cpu().numpy(), lo_hi=lo_hi)):
         target = out_dir / f'sample_{first + i}.gif'
         video_array_to_gif(frames, target)

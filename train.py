@@ -13,7 +13,10 @@ use_bert_text_cond; sample with sample.py --cond-path); --temporal_pos_bias (or 
 attention blocks add the relative position bias before the softmax, so the network can learn frame order; sample with
 sample.py --temporal-pos-bias or the same YAML key); --focus_present [--prob_focus_present P] (or unet.focus_present: true and
 trainer.prob_focus_present: P in the YAML; joint image-video training: with probability P a sample is trained as a bag of images, each
-frame attending to itself only in the temporal blocks; sample.py --focus-present draws frames in that image mode)."""
+frame attending to itself only in the temporal blocks; sample.py --focus-present draws frames in that image mode);
+diffusion.lowres_cond: {temporal: ft, spatial: fs, aug_max: L} in the YAML (no flag; sample.build_models reads it): the second stage of
+a cascade -- the network is trained on [ x_t | the batch's own ft x fs x fs box mean, upsampled and noised to a level below L ]; sample
+such a model with sample.py --lowres-path; not with --frame_cond_max or --focus_present)."""
 import argparse
 import logging
 import os

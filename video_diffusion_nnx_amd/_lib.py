@@ -143,3 +143,15 @@ vdx_vlb_terms_lv = _sig('vdx_vlb_terms_lv', c_int, [c_void_p] * 4 + [c_int, c_vo
 vdx_vlb_loop_lv = _sig('vdx_vlb_loop_lv', c_int, [c_void_p] * 9 + [c_int, c_void_p, c_int, c_int, c_void_p, _u64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                                   c_int, c_int, c_void_p])
 vdx_final_conv_backward_wide = _sig('vdx_final_conv_backward_wide', c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_long, c_int, c_int, c_void_p, c_size_t, c_void_p])
+
+# cascaded super-resolution (vdx.h: "Cascaded super-resolution"): the kernels around xin = [ x_t | u ] and the three loops over it
+DRAW_LOWRES = 1 << 61                            # VDX_DRAW_LOWRES: the augmentation draw of the sampling chains
+vdx_lowres_down = _sig('vdx_lowres_down', c_int, [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p])
+vdx_lowres_input = _sig('vdx_lowres_input', c_int, [c_void_p] * 8 + [c_int, _u64, _u64, c_float, c_float] + [c_int] * 6 + [c_void_p])
+vdx_lowres_pack = _sig('vdx_lowres_pack', c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p])
+vdx_p_sample_loop_sr = _sig('vdx_p_sample_loop_sr', c_int, [c_void_p] * 9 + [c_int, c_int, c_void_p, _u64, c_int, c_float, c_void_p, c_void_p, c_size_t,
+                                                            c_int, c_int, c_void_p])
+vdx_ddim_sample_loop_sr = _sig('vdx_ddim_sample_loop_sr', c_int, [c_void_p] * 10 + [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                                                  c_size_t, c_int, c_int, c_void_p])
+vdx_dpm_sample_loop_sr = _sig('vdx_dpm_sample_loop_sr', c_int, [c_void_p] * 11 + [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                                                c_size_t, c_int, c_int, c_void_p])

@@ -6,8 +6,9 @@
 #include "model.h"
 #include "comm.h"
 
-// Everything a sampling step can bake into its captured graph: what the eleven vdx_*_sample_loop* entry points fill in and sample_loop()
-// runs.  A field the entry does not have stays zero.
+// Everything a sampling step can bake into its captured graph: what the fourteen vdx_*_sample_loop* entry points (the eleven over a
+// network with out_dim == channels and the three super-resolution ones, vdx_*_sample_loop_sr) fill in and sample_loop() runs.  A field
+// the entry does not have stays zero.
 // (CHAIN_VLB tags the graph key of vdx_vlb_loop only: it never goes through sample_loop, whose slot arithmetic 3 * variant + chain takes 0..2)
 // (CHAIN_LV / CHAIN_VLB_LV: the learned-variance loops, vdx_p_sample_loop_lv / vdx_vlb_loop_lv, likewise outside sample_loop)
 enum { CHAIN_ANCESTRAL = 0, CHAIN_DDIM = 1, CHAIN_DPM = 2, CHAIN_VLB = 3, CHAIN_LV = 4, CHAIN_VLB_LV = 5 };
@@ -15,6 +16,7 @@ struct LoopArgs {
     int chain, masked, guided;                          // CHAIN_*; the masked (inpainting) step; classifier-free guidance over 2 * batch rows
     const float* params; const void* packed;
     float* img; float* eps_buf; float* hist; int* t_dev; uint64_t* step_dev;
+    float* xin;                                         // the super-resolution loops alone: the network's input [batch, 2C, F, S, S]
     const float* tables; int timesteps;                 // [5][T]: the ancestral step and the dynamic threshold; T is also mask_tables' row length
     const float* alphas_cumprod; const int* seq; int seq_len;     // the two sequence chains
     const float* cond; uint64_t seed; int clip_denoised, order;
@@ -34,7 +36,7 @@ struct vdx_handle {
     struct GraphKey { LoopArgs a; const void* stream; int act16; };
     // one cached graph per (chain, variant): slot = 3 * variant + chain with variant 0 = plain, 1 = masked, 2 = guided and chain 0 = the
     // ancestral loop, 1 = DDIM, 2 = DPM-Solver++; slot 9 = the evaluation loop (vdx_vlb_loop), 10 / 11 = the learned-variance sampling and
-    // evaluation loops -- no loop ever evicts another one's graph
+    // evaluation loops, 12 + chain = the super-resolution loops (vdx_*_sample_loop_sr) -- no loop ever evicts another one's graph
     // `last` = the stream the exec was last launched on: replays may still be running when the graph has to go
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key; hipStream_t last = nullptr;
@@ -44,7 +46,7 @@ struct vdx_handle {
             if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
             last = nullptr;
         }
-    } gs[12];
+    } gs[15];
     void drop_graphs() { for (GraphSlot& g : gs) g.drop(); }
     vdx::BwdState bwd;
     vdx::Comm comm;
@@ -813,7 +815,7 @@ int vdx_cfg_combine(const float* eps2, float* out, float cond_scale, float resca
     return VDX_OK;
 }
 
-// ---- the sampling loops: one step builder, eleven positional entry points ----
+// ---- the sampling loops: one step builder, fourteen positional entry points ----
 
 // 0 <= x <= 1 by the bits of x (non-negative floats order like unsigned integers): the library is built with -fno-honor-nans, under
 // which a comparison may let a NaN through, and a NaN rescale has to be refused
@@ -823,8 +825,8 @@ static bool in_unit_interval(float x) {
     return u <= 0x3F800000u || u == 0x80000000u;       // [+0, 1] or -0
 }
 
-// The step of every loop, launch for launch: (guided: copy img[:B] -> img[B:]) -> model_forward over B samples (guided: 2B, the second
-// half with the null embedding) -> (guided: cfg_combine) -> (dynamic threshold) -> the chain's step kernel on B samples -> the chain's
+// The step of every loop, launch for launch: (guided: copy img[:B] -> img[B:]) -> (super-resolution, a.xin: lowres_pack img -> the
+// first half of xin, the forward then reads xin) -> model_forward over B samples (guided: 2B, the second half with the null embedding) -> (guided: cfg_combine) -> (dynamic threshold) -> the chain's step kernel on B samples -> the chain's
 // advance (guided: over 2B).  Validates, derives the graph key from `a` and runs nsteps steps eagerly or as replays of one captured step.
 // Guided loops (classifier-free guidance; EXTENSION, parity unpinned: the reference's p_sample_loop drops cond): img / t_dev / eps_buf /
 // workspace hold 2 * batch samples; the step kernels, the threshold and the result use the first `batch`.
@@ -836,10 +838,14 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
     if (anc ? !a.tables : (!a.alphas_cumprod || !a.seq)) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
     if (masked && (!a.known || !a.mask || !a.mask_tables)) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
     if (guided && (!a.cond || !a.cfg_scratch)) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
+    // super-resolution (a.xin; vdx.h: "Cascaded super-resolution"): the network reads xin [batch, 2C, F, S, S], everything else is over
+    // C = out_dim channels.  Plain variants only: there is no masked or guided entry that sets xin
+    const bool sr = a.xin != nullptr;
+    if (sr && h->model.cfg.channels != 2 * h->model.out_dim) LOOP_FAIL(VDX_ERR_INVALID, "channels must equal 2 * out_dim");
     if (!h->model.d_ss_layers) LOOP_FAIL(VDX_ERR_STATE, "handle was created without a GPU");
     // the rules of the variants, keyed on chain / masked / guided (all VDX_ERR_INVALID)
     const vdx::Model& m = h->model;
-    const long per_sample = (long)m.cfg.channels * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
+    const long per_sample = (long)(sr ? m.out_dim : m.cfg.channels) * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
     const bool dyn = a.percentile > 0.f && a.clip_denoised;
     if (guided && !m.cfg.cond_dim) LOOP_FAIL(VDX_ERR_INVALID, "the network has no condition (cond_dim == 0)");
     if (guided && a.batch < 1) LOOP_FAIL(VDX_ERR_INVALID, "batch must be >= 1");
@@ -854,7 +860,8 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
     if (dyn && !anc && (!a.tables || a.timesteps < 1)) LOOP_FAIL(VDX_ERR_INVALID, "dynamic threshold needs tables and timesteps >= 1");
     // (ddim_step_kernel alone has a scalar form; every other step kernel, and cfg_combine, move four elements per thread)
     if (per_sample % 4 && (a.chain != CHAIN_DDIM || masked || guided)) LOOP_FAIL(VDX_ERR_INVALID, "C*F*H*W must be a multiple of 4");
-    if (m.out_dim != m.cfg.channels) LOOP_FAIL(VDX_ERR_INVALID, "out_dim must equal channels");
+    if (!sr && m.out_dim != m.cfg.channels) LOOP_FAIL(VDX_ERR_INVALID, "out_dim must equal channels");
+    if (sr && ((uintptr_t)a.img % 16 || (uintptr_t)a.xin % 16)) LOOP_FAIL(VDX_ERR_INVALID, "img / xin must be 16-byte aligned");
     if (masked && !masked_aligned(a.img, a.known, a.img, a.mask)) LOOP_FAIL(VDX_ERR_INVALID, "img / known must be 16-byte and mask 4-byte aligned");
     if (dpm && ((uintptr_t)a.img % 16 || (uintptr_t)a.hist % 16)) LOOP_FAIL(VDX_ERR_INVALID, "img / hist must be 16-byte aligned");
     if (guided && ((uintptr_t)a.img % 16 || (uintptr_t)a.eps_buf % 16 || (uintptr_t)a.hist % 16 || (uintptr_t)a.cfg_scratch % 8))
@@ -862,7 +869,7 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
 #undef LOOP_FAIL
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* sd = reinterpret_cast<unsigned long long*>(a.step_dev);
-    const int B = a.batch, rows = guided ? 2 * B : B, C = m.cfg.channels;      // rows: what the forward and the advance cover
+    const int B = a.batch, rows = guided ? 2 * B : B, C = sr ? m.out_dim : m.cfg.channels;      // rows: what the forward and the advance cover
     const float* th = dyn ? a.thres_buf : nullptr;
     const unsigned char* cond_mask = guided ? vdx::cfg_scratch_mask(a.cfg_scratch, B) : nullptr;
     // (ancestral: one Philox draw per step through step_dev, resampling or not; the sequence chains draw for the known region only)
@@ -874,7 +881,9 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
         if (guided) e = hipMemcpyAsync(a.img + (size_t)B * per_sample, a.img, (size_t)B * per_sample * sizeof(float), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
         // reference p_sample_loop never forwards cond (Q10); when a cond tensor is supplied to an unguided loop it is used un-masked
-        int rc = vdx::model_forward(&m, a.params, a.packed, a.img, a.t_dev, a.cond, cond_mask, 0, a.eps_buf, a.workspace, a.workspace_bytes, rows, st);
+        if (sr) e = vdx::launch_lowres_pack(a.img, a.xin, B, per_sample, st);
+        if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
+        int rc = vdx::model_forward(&m, a.params, a.packed, sr ? a.xin : a.img, a.t_dev, a.cond, cond_mask, 0, a.eps_buf, a.workspace, a.workspace_bytes, rows, st);
         if (rc != VDX_OK) return rc;
         if (guided) e = vdx::launch_cfg_combine(a.eps_buf, a.eps_buf, a.cond_scale, a.rescale, a.cfg_scratch, B, per_sample, st);
         if (e == hipSuccess && dyn) e = vdx::launch_dyn_thres(a.img, a.eps_buf, a.t_dev, a.tables, a.timesteps, a.percentile, a.thres_buf, B, C, per_sample, st);
@@ -910,10 +919,10 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
     if (!masked) { k.known = nullptr; k.mask = nullptr; k.mask_tables = nullptr; }
     if (!masked || !anc) k.resample_steps = 0;
     if (!guided) { k.cond_scale = 0.f; k.rescale = 0.f; k.cfg_scratch = nullptr; }
-    return run_steps(h, 3 * (guided ? 2 : masked ? 1 : 0) + a.chain, key, nsteps, use_graph, st, step);
+    return run_steps(h, sr ? 12 + a.chain : 3 * (guided ? 2 : masked ? 1 : 0) + a.chain, key, nsteps, use_graph, st, step);
 }
 
-// what all eleven entries share; the rest of `a` is zero (and so is its padding: the bytes of a LoopArgs are a graph key)
+// what all fourteen entries share; the rest of `a` is zero (and so is its padding: the bytes of a LoopArgs are a graph key)
 static void loop_args(LoopArgs& a, int chain, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev, uint64_t* step_dev,
                       const float* cond, int clip_denoised, float percentile, float* thres_buf, void* workspace, size_t workspace_bytes, int batch) {
     memset(&a, 0, sizeof(a));
@@ -1047,6 +1056,89 @@ int vdx_dpm_sample_loop_guided(vdx_handle* h, const float* params, const void* p
     set_guided(a, cond_scale, rescale, cfg_scratch);
     a.hist = hist; a.order = order;
     return sample_loop("dpm_sample_loop_guided", h, a, nsteps, use_graph, stream);
+}
+
+// ---- cascaded super-resolution (vdx.h: "Cascaded super-resolution"): the three loops over xin = [ x_t | u ] and the kernels around them ----
+
+int vdx_p_sample_loop_sr(vdx_handle* h, const float* params, const void* packed, float* img, float* xin, float* eps_buf, int* t_dev,
+                         uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                         int clip_denoised, float percentile, float* thres_buf, void* workspace, size_t workspace_bytes, int batch,
+                         int use_graph, void* stream) {
+    const char* who = "p_sample_loop_sr";
+    if (!xin) VDX_REFUSE(who, "null argument");
+    LoopArgs a;
+    loop_args(a, CHAIN_ANCESTRAL, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    a.tables = tables; a.timesteps = timesteps; a.seed = seed; a.xin = xin;
+    return sample_loop(who, h, a, nsteps, use_graph, stream);
+}
+
+int vdx_ddim_sample_loop_sr(vdx_handle* h, const float* params, const void* packed, float* img, float* xin, float* eps_buf, int* t_dev,
+                            uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps, const float* cond,
+                            int clip_denoised, const float* tables, int timesteps, float percentile, float* thres_buf, void* workspace,
+                            size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    const char* who = "ddim_sample_loop_sr";
+    if (!xin) VDX_REFUSE(who, "null argument");
+    LoopArgs a;
+    loop_args(a, CHAIN_DDIM, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    set_sequence(a, alphas_cumprod, seq, seq_len, tables, timesteps);
+    a.xin = xin;
+    return sample_loop(who, h, a, nsteps, use_graph, stream);
+}
+
+int vdx_dpm_sample_loop_sr(vdx_handle* h, const float* params, const void* packed, float* img, float* xin, float* eps_buf, float* hist,
+                           int* t_dev, uint64_t* step_dev, const float* alphas_cumprod, const int* seq, int seq_len, int nsteps,
+                           const float* cond, int clip_denoised, int order, const float* tables, int timesteps, float percentile,
+                           float* thres_buf, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    const char* who = "dpm_sample_loop_sr";
+    if (!xin) VDX_REFUSE(who, "null argument");
+    LoopArgs a;
+    loop_args(a, CHAIN_DPM, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    set_sequence(a, alphas_cumprod, seq, seq_len, tables, timesteps);
+    a.hist = hist; a.order = order; a.xin = xin;
+    return sample_loop(who, h, a, nsteps, use_graph, stream);
+}
+
+// the geometry rules the lowres kernels share (who-prefixed, VDX_ERR_INVALID)
+static int lowres_rules(const char* who, int batch, int channels, int frames, int size, int ft, int fs) {
+    if (batch < 1 || channels < 1 || frames < 1 || size < 1) VDX_REFUSE(who, "batch, channels, frames and size must be >= 1");
+    if (ft < 1 || fs < 1) VDX_REFUSE(who, "the factors ft and fs must be >= 1");
+    if (frames % ft || size % fs) VDX_REFUSE(who, "ft must divide frames and fs must divide size");
+    return VDX_OK;
+}
+
+int vdx_lowres_down(const float* x, float* lo, int batch, int channels, int frames, int size, int ft, int fs, void* stream) {
+    const char* who = "lowres_down";
+    if (!x || !lo) VDX_REFUSE(who, "null tensor");
+    if (int rc = lowres_rules(who, batch, channels, frames, size, ft, fs)) return rc;
+    VDX_HIP(vdx::launch_lowres_down(x, lo, batch, channels, frames, size, ft, fs, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_lowres_input(const float* x0, const int* t, const float* noise, const float* lo, const int* aug_level, float* xin, const float* sqrt_ac,
+                     const float* sqrt_one_minus_ac, int timesteps, uint64_t seed, uint64_t draw, float pre_scale, float pre_shift, int batch,
+                     int channels, int frames, int size, int ft, int fs, void* stream) {
+    const char* who = "lowres_input";
+    if (!lo || !xin) VDX_REFUSE(who, "null tensor");
+    if (x0 && (!t || !noise)) VDX_REFUSE(who, "x0 needs t and noise");
+    if ((x0 || aug_level) && (!sqrt_ac || !sqrt_one_minus_ac || timesteps < 1)) VDX_REFUSE(who, "x0 / aug_level need the tables and timesteps >= 1");
+    if (int rc = lowres_rules(who, batch, channels, frames, size, ft, fs)) return rc;
+    if ((uintptr_t)x0 % 4 || (uintptr_t)noise % 4 || (uintptr_t)lo % 4 || (uintptr_t)xin % 4) VDX_REFUSE(who, "x0 / noise / lo / xin must be 4-byte aligned");
+    vdx::LowresArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x0 = x0; a.t = t; a.noise = noise; a.lo = lo; a.aug = aug_level; a.xin = xin; a.sqrt_ac = sqrt_ac; a.sqrt_1mac = sqrt_one_minus_ac;
+    a.T = timesteps; a.seed = seed; a.draw = draw; a.pre_scale = pre_scale; a.pre_shift = pre_shift;
+    a.C = channels; a.F = frames; a.S = size; a.ft = ft; a.fs = fs;
+    VDX_HIP(vdx::launch_lowres_input(a, batch, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_lowres_pack(const float* img, float* xin, int batch, long per_sample, void* stream) {
+    const char* who = "lowres_pack";
+    if (!img || !xin) VDX_REFUSE(who, "null tensor");
+    if (batch < 1 || per_sample < 1) VDX_REFUSE(who, "batch and per_sample must be >= 1");
+    if ((uintptr_t)img % 4 || (uintptr_t)xin % 4) VDX_REFUSE(who, "img / xin must be 4-byte aligned");
+    VDX_HIP(vdx::launch_lowres_pack(img, xin, batch, per_sample, (hipStream_t)stream));
+    return VDX_OK;
 }
 
 // ---- held-out evaluation (vdx.h: "Held-out evaluation"): the three single-step entries and the loop ----

@@ -282,6 +282,19 @@ size_t hybrid_scratch_doubles(int B);
 hipError_t launch_hybrid_loss(const HybridArgs& a, double* out, double w, int B, hipStream_t st);
 // launch_vlb_terms with the model's variance: a.eps = out2, a.tab = the [VDX_LV_ROWS][T] table
 hipError_t launch_vlb_terms_lv(const VlbArgs& a, int B, hipStream_t st);
+// Cascaded super-resolution (vdx.h: "Cascaded super-resolution"; lowres.hip).  xin [B,2C,F,S,S] = [ x_t | aug(up(2 lo - 1)) ].
+struct LowresArgs {
+    const float* x0; const int* t; const float* noise;  // x0 [B,C,F,S,S] (null: the second half alone; t / noise are not read then)
+    const float* lo; const int* aug;                    // lo [B,C,F/ft,S/fs,S/fs]; device levels [B] (< 0 = none) or null (none)
+    float* xin;
+    const float* sqrt_ac; const float* sqrt_1mac; int T;
+    unsigned long long seed, draw;                      // the augmentation noise: Philox(seed, draw) over the index of [B,C,F,S,S]
+    float pre_scale, pre_shift;                         // x0 pre_scale + pre_shift (normalize_img), as launch_q_sample
+    int C, F, S, ft, fs;
+};
+hipError_t launch_lowres_down(const float* x, float* lo, int B, int C, int F, int S, int ft, int fs, hipStream_t st);
+hipError_t launch_lowres_input(const LowresArgs& a, int B, hipStream_t st);
+hipError_t launch_lowres_pack(const float* img, float* xin, int B, long per_sample, hipStream_t st);
 // frame-conditioned training (mask [B,C,F,H,W] bytes, nonzero = clean context): masked q_sample, the deterministic (sum, count) of the
 // loss over the mask-0 elements (scratch: loss_masked_scratch_doubles()), and its gradient with the count read from the device
 hipError_t launch_q_sample_masked(const float* x0, const int* t, const float* noise, const unsigned char* mask, float* out, const float* sqrt_ac,

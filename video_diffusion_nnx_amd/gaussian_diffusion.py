@@ -249,6 +249,19 @@ def split_key(key: int, num: int = 2):
     return out
 
 
+def lowres_aug_key(key: int) -> int:
+    """Key of the super-resolution augmentation (the level draw and the noise) under a loss key: child 4 of it.  p_losses'
+    `_, noise_key, _ = split(key, 3)` takes children 1-3 (the train step gives 1 to the condition dropout and 3 to the focus-present
+    draw), so no other stream moves."""
+    return split_key(key, 4)[3]
+
+
+def lowres_aug_levels(batch: int, aug_max: int, key: int) -> torch.Tensor:
+    """The augmentation levels of one batch: int32 [batch], uniform on {0..aug_max-1}, drawn on the host under `key`."""
+    g = torch.Generator().manual_seed(int(key) & 0x7FFFFFFFFFFFFFFF)
+    return torch.randint(0, int(aug_max), (int(batch),), generator=g, dtype=torch.int32)
+
+
 def dist_rank_world():
     """(rank, world) of the default torch.distributed group, (0, 1) outside one."""
     import torch.distributed as dist
@@ -274,11 +287,47 @@ def is_list_str(x) -> bool:
     return isinstance(x, (list, tuple)) and all(type(el) == str for el in x)
 
 
+def check_lowres_cond(lowres_cond, num_frames: int, image_size: int):
+    """(ft, fs) of a super-resolution diffusion's lowres_cond: two integers >= 1 that divide num_frames and image_size."""
+    try:
+        ft, fs = lowres_cond
+    except (TypeError, ValueError):
+        raise ValueError(f'lowres_cond must be a pair (temporal factor, spatial factor), got {lowres_cond!r}') from None
+    for name, v in (('temporal', ft), ('spatial', fs)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            raise ValueError(f'lowres_cond: the {name} factor must be an integer >= 1, got {v!r}')
+    if int(num_frames) % int(ft) or int(image_size) % int(fs):
+        raise ValueError(f'lowres_cond ({ft}, {fs}): the temporal factor must divide num_frames = {num_frames} and the spatial one '
+                         f'image_size = {image_size}')
+    return int(ft), int(fs)
+
+
 class GaussianDiffusion:
+    # super-resolution switches (instance attributes only on a super-resolution diffusion: a plain one keeps the attributes it had)
+    lowres_cond = None
+    lowres_aug_max = 0
+
     def __init__(self, denoise_fn: Unet3D, *, image_size: int, num_frames: int, text_use_bert_cls: bool = False,
                  channels: int = 3, timesteps: int = 1000, loss_type: str = 'l1', use_dynamic_thres: bool = False,
                  dynamic_thres_percentile: float = 0.9, sample_act_bf16: bool = True, learned_variance: bool = False,
-                 vlb_weight: Optional[float] = None):
+                 vlb_weight: Optional[float] = None, lowres_cond=None, lowres_aug_max: int = 0):
+        # lowres_cond = (ft, fs) (extension, off by default; Ho et al. 2021, "Cascaded Diffusion Models"): the second stage of a cascade.
+        # The denoiser has channels = 2 * channels and out_dim = channels; its input is [ x_t | u ], u = the low-resolution clip
+        # [B,C,F/ft,S/fs,S/fs] normalised, upsampled linearly and, in training, noised to a level drawn from {0..lowres_aug_max-1}
+        # (blind noise conditioning augmentation; 0 = none).  vdx.h: "Cascaded super-resolution".
+        if lowres_cond is not None:
+            ft_fs = check_lowres_cond(lowres_cond, num_frames, image_size)
+            if learned_variance:
+                raise ValueError('lowres_cond does not support learned_variance yet (a follow-up; DESIGN.md 9)')
+            if getattr(denoise_fn, 'channels', None) != 2 * channels or getattr(denoise_fn, 'out_dim', None) != channels:
+                raise ValueError(f'lowres_cond needs a denoiser with channels == 2 * channels = {2 * channels} and out_dim == channels = '
+                                 f'{channels}, got channels {getattr(denoise_fn, "channels", None)}, out_dim {getattr(denoise_fn, "out_dim", None)}')
+            if isinstance(lowres_aug_max, bool) or not isinstance(lowres_aug_max, (int, np.integer)) or not 0 <= int(lowres_aug_max) <= int(timesteps):
+                raise ValueError(f'lowres_aug_max must be an integer in [0, {int(timesteps)}], got {lowres_aug_max!r}')
+            self.lowres_cond = ft_fs
+            self.lowres_aug_max = int(lowres_aug_max)
+        elif lowres_aug_max:
+            raise ValueError('lowres_aug_max is the augmentation range of a super-resolution diffusion: it needs lowres_cond=(ft, fs)')
         # sample_act_bf16 (extension): with a mode='bf16' Unet3D the sampling loops store the UNet's inter-kernel activations
         # as bf16 (vdx_set_activation_storage); training forwards are unaffected
         self.sample_act_bf16 = sample_act_bf16
@@ -403,6 +452,154 @@ class GaussianDiffusion:
             raise NotImplementedError('pass text conditioning as a ready embedding tensor')
         return self.denoise_fn(x, t32, cond=cond)
 
+    # -- cascaded super-resolution -------------------------------------------------------------------
+    def _sr_refuse(self, **given):
+        """ValueError for what a super-resolution diffusion does not serve yet (follow-ups)."""
+        if self.lowres_cond is None:
+            return
+        off = dict(cond_scale=1.0, guidance_rescale=0.0)
+        for name, val in given.items():
+            if val is None or val is False or (name in off and float(val) == off[name]):
+                continue
+            raise ValueError(f'lowres_cond (super-resolution) does not support {name} yet (a follow-up; DESIGN.md 9)')
+
+    def _sr_need_lowres(self, who, instead):
+        if self.lowres_cond is not None:
+            raise ValueError(f'lowres_cond (super-resolution): {who} has no low-resolution clip to condition on; use {instead}')
+
+    def _sr_lowres(self, lowres, batch=None):
+        """`lowres` checked against [B, C, F/ft, S/fs, S/fs] (before any device work) -> its shape."""
+        if self.lowres_cond is None:
+            raise ValueError('lowres needs a super-resolution diffusion (lowres_cond=(ft, fs))')
+        ft, fs = self.lowres_cond
+        want = (self.channels, self.num_frames // ft, self.image_size // fs, self.image_size // fs)
+        shape = tuple(lowres.shape)
+        if len(shape) != 5 or shape[1:] != want or (batch is not None and shape[0] != batch):
+            raise ValueError(f'lowres must be [{"B" if batch is None else batch}, {want[0]}, {want[1]}, {want[2]}, {want[3]}], got {shape}')
+        return shape
+
+    def _sr_levels(self, aug_level, B):
+        """The augmentation levels of a batch as host int32 [B] or None (none): an int (every sample) or [B] values in [-1, T-1]."""
+        if aug_level is None:
+            return None
+        lv = torch.as_tensor(aug_level).to(torch.int32).reshape(-1).cpu()
+        if lv.numel() == 1:
+            lv = lv.expand(B).contiguous()
+        if lv.numel() != B or int(lv.min()) < -1 or int(lv.max()) >= self.num_timesteps:
+            raise ValueError(f'the augmentation level must be an int or [{B}] values in [-1, {self.num_timesteps - 1}], got {aug_level!r}')
+        return lv
+
+    def lowres_condition(self, lowres, key=None, aug_level=None, *, draw: int = 0, out=None):
+        """u = aug(up(2 lowres - 1)) [B,C,F,S,S] of the low-resolution clip `lowres` [B,C,F/ft,S/fs,S/fs] in [0, 1] (vdx_lowres_input,
+        the sampling-time form).  aug_level: None (none), an int or [B] levels (-1 = none for that sample); the noise is Philox(key,
+        draw) in randn's layout (the sampling chains use draw VDX_DRAW_LOWRES of their seed).  out: an xin [B,2C,F,S,S] whose second
+        half receives u (the first half is not touched); the result is then a view of it."""
+        from . import ops
+        B = self._sr_lowres(lowres)[0]
+        lv = self._sr_levels(aug_level, B)
+        if lv is not None and key is None:
+            raise ValueError('an augmentation level needs a key for its noise')
+        ft, fs = self.lowres_cond
+        xin = ops.lowres_input(self._dev(lowres), ft, fs, tables=(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod),
+                               aug_levels=None if lv is None else lv.to(self.device), seed=int(key or 0), draw=draw, out=out)
+        u = xin[:, self.channels:]
+        return u if out is not None else u.contiguous()
+
+    def sr_input(self, x_start, t32, noise, *, lowres=None, aug_levels=None, key: int = 0, _pre=(1.0, 0.0)):
+        """The training input xin [B,2C,F,S,S] of a super-resolution denoiser in two launches: lowres = the box mean of the raw clip
+        x_start (vdx_lowres_down; skipped when `lowres` is given), then q_sample of x_start * _pre[0] + _pre[1] into the first half and
+        aug(up(2 lowres - 1)) into the second (vdx_lowres_input; the augmentation noise is Philox(key, draw 0)).  x_start, t32, noise on
+        the device; aug_levels: host or device int32 [B] or None."""
+        from . import ops
+        ft, fs = self.lowres_cond
+        lo = ops.lowres_down(x_start, ft, fs) if lowres is None else self._dev(lowres)
+        lv = None
+        if aug_levels is not None:
+            lv = torch.as_tensor(aug_levels).to(torch.int32)
+            if lv.device.type == 'cpu' and self.device.type == 'cuda':
+                lv = lv.pin_memory().to(self.device, non_blocking=True)   # as t in the train step: no pageable copy, no host sync
+            lv = lv.to(self.device).contiguous()
+        return ops.lowres_input(lo, ft, fs, x0=x_start, t=t32, noise=noise, tables=(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod),
+                                aug_levels=lv, seed=key, draw=0, pre=_pre)
+
+    def _sr_eps(self, x, t32, lowres_cond, cond):
+        """eps_hat of a super-resolution denoiser on [ x | u ]."""
+        if lowres_cond is None:
+            raise ValueError('a super-resolution diffusion needs lowres_cond=u (lowres_condition(lowres)) here')
+        u = self._dev(lowres_cond)
+        if tuple(u.shape) != tuple(x.shape):
+            raise ValueError(f'lowres_cond must have the shape of x {tuple(x.shape)}, got {tuple(u.shape)}')
+        if is_list_str(cond):
+            raise NotImplementedError('pass text conditioning as a ready embedding tensor')
+        return self.denoise_fn(torch.cat([x, u], dim=1), t32, cond=cond)
+
+    def _run_chain_sr(self, chain, lowres, key, *, aug_level=None, steps=0, order=2, cond=None, use_graph=True, x_T=None):
+        """One super-resolution chain on the current stream (inside _sampling()): u is written once into the second half of xin
+        (vdx_lowres_input, augmentation draw VDX_DRAW_LOWRES of the chain's seed), then the vdx_*_sample_loop_sr entry of the chain runs
+        its captured step: lowres_pack -> forward(xin) -> the plain chain's step kernel on img.  x_T = Philox(key, draw 0), step k draws
+        1 + k, as the plain loops.  The buffers are kept per batch size: a second call replays the cached graph."""
+        unet, T, dev = self.denoise_fn, self.num_timesteps, self.device
+        seed = int(key) & 0xFFFFFFFFFFFFFFFF
+        B = lowres.shape[0]
+        shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
+        buf = getattr(self, '_sr_buf', None)
+        if buf is None or buf['key'] != (B, chain, steps):
+            seq_host = None if chain == 'ddpm' else ddim_time_sequence(T, steps)
+            buf = self._sr_buf = dict(
+                key=(B, chain, steps), img=torch.empty(shape, dtype=torch.float32, device=dev),
+                xin=torch.zeros((B, 2 * self.channels) + shape[2:], dtype=torch.float32, device=dev),
+                eps=torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=dev),
+                hist=torch.empty(shape, dtype=torch.float32, device=dev) if chain == 'dpm' else None,
+                t=torch.empty(B, dtype=torch.int32, device=dev), step=torch.empty(1, dtype=torch.int64, device=dev),
+                thres=torch.empty(B, dtype=torch.float32, device=dev) if self.use_dynamic_thres else None,
+                seq=None if seq_host is None else torch.from_numpy(seq_host).to(dev), t0=T - 1 if seq_host is None else int(seq_host[0]))
+        img, xin, eps, hist, t_dev, step_dev, thres, seq = (buf[k] for k in ('img', 'xin', 'eps', 'hist', 't', 'step', 'thres', 'seq'))
+        if x_T is None:
+            L.check(vdx_randn(L.ptr(img), img.numel(), seed, 0, 0, L.stream_ptr()))
+        else:
+            img.copy_(self._dev(x_T))
+        self.lowres_condition(lowres, seed, aug_level, draw=L.DRAW_LOWRES, out=xin)
+        perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
+        condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
+        h = unet.handle(self.num_frames, self.image_size)
+        unet.apply_activation_storage(h)
+        ws = unet.workspace(B, self.num_frames, self.image_size)
+        t_dev.fill_(buf['t0'])
+        step_dev.zero_()
+        head = (h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(xin), L.ptr(eps)) + ((L.ptr(hist),) if chain == 'dpm' else ()) \
+            + (L.ptr(t_dev), L.ptr(step_dev))
+        if chain == 'ddpm':
+            body = (L.ptr(self._ptab), T, T, L.ptr(condd), seed, 1, perc, L.ptr(thres))
+        else:
+            body = (L.ptr(self.alphas_cumprod), L.ptr(seq), steps, steps, L.ptr(condd), 1) + ((order,) if chain == 'dpm' else ()) \
+                + (L.ptr(self._ptab), T, perc, L.ptr(thres))
+        loop = {'ddpm': L.vdx_p_sample_loop_sr, 'ddim': L.vdx_ddim_sample_loop_sr, 'dpm': L.vdx_dpm_sample_loop_sr}[chain]
+        L.check(loop(*head, *body, L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
+        out = torch.empty_like(img)
+        L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
+        return out
+
+    def upsample(self, key, lowres, *, aug_level=None, cond=None, ddim_steps: Optional[int] = None, dpm_steps: Optional[int] = None,
+                 dpm_order: int = 2, use_graph: bool = True, x_T=None):
+        """The second stage of a cascade (EXTENSION): sample [B,C,F,S,S] in [0, 1] conditioned on the low-resolution clip `lowres`
+        [B,C,F/ft,S/fs,S/fs] in [0, 1] (a base model's sample, say) with the T-step ancestral chain, an S-step DDIM chain (ddim_steps)
+        or an S-step DPM-Solver++(2M) chain (dpm_steps, dpm_order).  aug_level: the noise conditioning augmentation level at sampling
+        time (None = none; an int or [B] levels in [-1, T-1]), drawn as Philox(key, VDX_DRAW_LOWRES).  Single process: no rank sharding."""
+        if self.lowres_cond is None:
+            raise ValueError('upsample needs a super-resolution diffusion (lowres_cond=(ft, fs))')
+        lowres = torch.as_tensor(lowres)
+        B = self._sr_lowres(lowres)[0]
+        self._sr_levels(aug_level, B)                                     # (its range check, before any device work)
+        check_dpm_args(self.num_timesteps, dpm_steps, dpm_order, ddim_steps)
+        if ddim_steps:
+            ddim_time_sequence(self.num_timesteps, ddim_steps)
+        if x_T is not None and tuple(x_T.shape) != (B, self.channels, self.num_frames, self.image_size, self.image_size):
+            raise ValueError(f'x_T must be [{B}, {self.channels}, {self.num_frames}, {self.image_size}, {self.image_size}], got {tuple(x_T.shape)}')
+        chain, steps = ('dpm', int(dpm_steps)) if dpm_steps is not None else ('ddim', int(ddim_steps)) if ddim_steps else ('ddpm', 0)
+        with self._sampling(None, B):
+            return self._run_chain_sr(chain, lowres, key, aug_level=aug_level, steps=steps, order=dpm_order, cond=cond, use_graph=use_graph,
+                                      x_T=x_T)
+
     def model_log_variance(self, out2, t):
         """log sigma^2 [B,C,F,H,W] of the network output out2 [B,F,H,W,2C] at levels t of the full chain (torch, on out2's device)."""
         tab = self._lv_tab64()
@@ -456,8 +653,12 @@ class GaussianDiffusion:
         return img
 
     # -- reverse process ---------------------------------------------------------------------------
-    def p_mean_variance(self, x, t, clip_denoised: bool, cond=None, cond_scale: float = 1.0):
-        """reference :162-228 (returns (mean, variance, log_variance)).  learned_variance: the model's variance, per element."""
+    def p_mean_variance(self, x, t, clip_denoised: bool, cond=None, cond_scale: float = 1.0, *, lowres_cond=None):
+        """reference :162-228 (returns (mean, variance, log_variance)).  learned_variance: the model's variance, per element.
+        lowres_cond (a super-resolution diffusion only, and required there): u = lowres_condition(lowres), the network sees [ x | u ]."""
+        self._sr_refuse(cond_scale=cond_scale)
+        if self.lowres_cond is None and lowres_cond is not None:
+            raise ValueError('lowres_cond needs a super-resolution diffusion (lowres_cond=(ft, fs))')
         x = self._dev(x)
         t32 = self._dev(t, torch.int32)
         if self.learned_variance:
@@ -465,7 +666,8 @@ class GaussianDiffusion:
             mean, out2 = self._p_step_lv(x, t32, cond, clip_denoised, 0, None, zero_noise=True)
             logvar = self.model_log_variance(out2, t32)
             return mean, logvar.exp(), logvar
-        eps_hat = self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
+        eps_hat = self._sr_eps(x, t32, lowres_cond, cond) if self.lowres_cond is not None else \
+            self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
         thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
         mean = torch.empty_like(x)
         zeros = torch.zeros_like(x)      # z = 0 turns the fused step into the posterior mean
@@ -474,14 +676,18 @@ class GaussianDiffusion:
                                   self._per_sample(x), L.stream_ptr()))
         return mean, extract(self.posterior_variance, t32, x.shape), extract(self.posterior_log_variance_clipped, t32, x.shape)
 
-    def p_sample(self, x, t, key, cond=None, cond_scale: float = 1.0, clip_denoised: bool = True, *, noise=None):
-        """reference :231-261.  `key`: seed of the noise draw (ignored when explicit `noise` is given)."""
+    def p_sample(self, x, t, key, cond=None, cond_scale: float = 1.0, clip_denoised: bool = True, *, noise=None, lowres_cond=None):
+        """reference :231-261.  `key`: seed of the noise draw (ignored when explicit `noise` is given).  lowres_cond: as p_mean_variance."""
+        self._sr_refuse(cond_scale=cond_scale)
+        if self.lowres_cond is None and lowres_cond is not None:
+            raise ValueError('lowres_cond needs a super-resolution diffusion (lowres_cond=(ft, fs))')
         x = self._dev(x)
         t32 = self._dev(t, torch.int32)
         if self.learned_variance:
             self._lv_refuse(cond_scale=cond_scale)
             return self._p_step_lv(x, t32, cond, clip_denoised, key, noise)[0]
-        eps_hat = self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
+        eps_hat = self._sr_eps(x, t32, lowres_cond, cond) if self.lowres_cond is not None else \
+            self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
         thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
         out = torch.empty_like(x)
         nz = None if noise is None else self._dev(noise)
@@ -642,6 +848,7 @@ class GaussianDiffusion:
         steps (learned_variance only): sample with the respaced S-level ancestral chain (make_lv_tables) instead of all T levels.
         """
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        self._sr_need_lowres('p_sample_loop', 'upsample(key, lowres)')
         if self.learned_variance:
             self._lv_refuse(cond_scale=cond_scale, guidance_rescale=guidance_rescale, focus_present=focus_present)
             lv_time_sequence(self.num_timesteps, steps)                   # (its range check, before any device work)
@@ -659,6 +866,7 @@ class GaussianDiffusion:
         sampling only).  x_T = Philox(key, draw 0), deterministic afterwards.  Returns unnormalize_img(x_0) in [0, 1].  cond with
         cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
         self._lv_refuse(ddim_steps=steps)
+        self._sr_need_lowres('ddim_sample_loop', 'upsample(key, lowres, ddim_steps=S)')
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         ddim_time_sequence(self.num_timesteps, steps)                     # (its range check, before any device work)
         with self._sampling(focus_present, int(shape[0])):
@@ -672,6 +880,7 @@ class GaussianDiffusion:
         the cost per step is DDIM's plus one history tensor.  x_T = Philox(key, draw 0), deterministic afterwards.  Returns
         unnormalize_img(x_0) in [0, 1].  cond with cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
         self._lv_refuse(dpm_steps=steps)
+        self._sr_need_lowres('dpm_sample_loop', 'upsample(key, lowres, dpm_steps=S)')
         check_dpm_args(self.num_timesteps, steps, order)
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         with self._sampling(focus_present, int(shape[0])):
@@ -689,6 +898,7 @@ class GaussianDiffusion:
         The model's variance is the posterior variance p_sample uses; the dynamic threshold has no place in the bound.
         learned_variance: the KL and decoder terms use the model's own log sigma^2 (vdx_vlb_loop_lv)."""
         self._lv_refuse(focus_present=focus_present)
+        self._sr_refuse(calc_bpd_loop=True)
         return self._bpd_chain(x, key, cond, clip_denoised, timesteps, use_graph, focus_present, None)
 
     def _bpd_chain(self, x, key, cond, clip_denoised, timesteps, use_graph, focus_present, pieces):
@@ -744,8 +954,9 @@ class GaussianDiffusion:
 
     def sample(self, key, cond=None, cond_scale: float = 1.0, batch_size: int = 16, *, ddim_steps: Optional[int] = None,
                dpm_steps: Optional[int] = None, dpm_order: int = 2, guidance_rescale: float = 0.0, focus_present=None,
-               steps: Optional[int] = None, **kw):
-        """reference :323-357.  ddim_steps (extension): sample with an S-step DDIM chain instead of the T-step ancestral one.
+               steps: Optional[int] = None, lowres=None, lowres_aug_level=None, **kw):
+        """reference :323-357.  lowres (a super-resolution diffusion only, and required there): the low-resolution clips; the call is
+        upsample(key, lowres, aug_level=lowres_aug_level, ...) -- single process, no rank sharding.  ddim_steps (extension): sample with an S-step DDIM chain instead of the T-step ancestral one.
         dpm_steps (extension): an S-step DPM-Solver++(2M) chain of order dpm_order (dpm_sample_loop); not together with ddim_steps.
         guidance_rescale (extension): the rescale phi in [0, 1] of the guided loops (cond given, cond_scale != 1; p_sample_loop).
         steps (extension, learned_variance only): the respaced S-level ancestral chain with the model's variance (p_sample_loop).
@@ -756,6 +967,14 @@ class GaussianDiffusion:
         no data-path collective.  W = 1 uses `key` itself (single-process behaviour unchanged)."""
         self._lv_refuse(cond_scale=cond_scale, ddim_steps=ddim_steps, dpm_steps=dpm_steps, guidance_rescale=guidance_rescale,
                         focus_present=focus_present)
+        if self.lowres_cond is not None:
+            self._sr_refuse(cond_scale=cond_scale, guidance_rescale=guidance_rescale, focus_present=focus_present, steps=steps)
+            if lowres is None:
+                raise ValueError('lowres_cond (super-resolution): sample needs lowres=[B, C, F/ft, S/fs, S/fs], the clips to upsample')
+            return self.upsample(key, lowres, aug_level=lowres_aug_level, cond=cond, ddim_steps=ddim_steps, dpm_steps=dpm_steps,
+                                 dpm_order=dpm_order, **{k: v for k, v in kw.items() if k in ('use_graph', 'x_T')})
+        if lowres is not None or lowres_aug_level is not None:
+            raise ValueError('lowres / lowres_aug_level need a super-resolution diffusion (lowres_cond=(ft, fs))')
         if steps is not None:
             if not self.learned_variance:
                 raise ValueError('steps is the respaced chain of a learned_variance diffusion; use ddim_steps / dpm_steps otherwise')
@@ -795,6 +1014,7 @@ class GaussianDiffusion:
         the known region is `video` itself, un-noised, in the start tensor and after every step of all three chains (the same kernels
         with the (1, 0) mask table, vdx.h), as such a network saw its context frames in training.  Not with resample_steps > 1."""
         self._lv_refuse(inpaint=True)
+        self._sr_refuse(inpaint=True)
         if focus_present is not None:
             raise ValueError('inpaint / extend do not take focus_present (frame-conditioned sampling of a focus-present sample is out of scope)')
         opts = self._inpaint_options(video, dict(cond_scale=cond_scale, ddim_steps=ddim_steps, resample_steps=resample_steps, use_graph=use_graph,
@@ -855,6 +1075,7 @@ class GaussianDiffusion:
         `video` itself.  Data parallel as sample(): sharded once (rows and shard_key), not per window.  clean_context=True (with a
         frame-conditioned denoiser): every window keeps its context frames un-noised, see inpaint()."""
         self._lv_refuse(extend=True)
+        self._sr_refuse(extend=True)
         ctx = self.num_frames // 2 if context_frames is None else int(context_frames)
         video = torch.as_tensor(video)
         if video.dim() != 5 or tuple(video.shape[1:2] + video.shape[3:]) != (self.channels, self.image_size, self.image_size):
@@ -913,13 +1134,20 @@ class GaussianDiffusion:
                              float(_pre[0]), float(_pre[1]), L.stream_ptr()))
         return out
 
-    def p_losses(self, x_start, t, key=None, cond=None, noise=None, *, frame_mask=None, _pre=(1.0, 0.0), **kwargs):
+    def p_losses(self, x_start, t, key=None, cond=None, noise=None, *, frame_mask=None, _pre=(1.0, 0.0), lowres=None, aug_levels=None, **kwargs):
         """reference :423-470 (forward value; the training step with gradients lives in trainer.py).  frame_mask (extension, RaMViD
         frame conditioning; forms as q_sample's): the masked frames enter the denoiser clean and the loss is the mean over the other
         elements, sum / max(count, 1), formed on the device (vdx_loss_sum_masked)."""
         if self.loss_type not in ('l1', 'l2'):
             raise ValueError(f'Unsupported loss type: {self.loss_type}')
         self._lv_refuse(frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
+        self._sr_refuse(frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
+        if self.lowres_cond is None and (lowres is not None or aug_levels is not None):
+            raise ValueError('lowres / aug_levels need a super-resolution diffusion (lowres_cond=(ft, fs))')
+        if self.lowres_cond is not None:
+            if lowres is not None:
+                self._sr_lowres(lowres, x_start.shape[0])
+            aug_levels = self._sr_levels(aug_levels, x_start.shape[0])
         x_start = self._dev(x_start)
         t32 = self._dev(t, torch.int32)
         if noise is None:
@@ -927,6 +1155,20 @@ class GaussianDiffusion:
             _, noise_key, _ = split_key(key, 3)
             noise = self.randn(x_start.shape, noise_key, 0)
         noise = self._dev(noise)
+        if self.lowres_cond is not None:
+            # super-resolution: lowres defaults to the box mean of the raw clip; aug_levels to a draw from {0..lowres_aug_max-1} under
+            # lowres_aug_key(key) (none with lowres_aug_max = 0); the loss is the plain one over the C output channels
+            if is_list_str(cond):
+                raise NotImplementedError('pass text conditioning as a ready embedding tensor')
+            if aug_levels is None and self.lowres_aug_max > 0:
+                assert key is not None, 'A key must be provided to p_losses for the augmentation draw.'
+                aug_levels = lowres_aug_levels(x_start.shape[0], self.lowres_aug_max, lowres_aug_key(key))
+            xin = self.sr_input(x_start, t32, noise, lowres=lowres, aug_levels=aug_levels, key=lowres_aug_key(key) if key is not None else 0, _pre=_pre)
+            eps_hat = self.denoise_fn(xin, t32, cond=cond, **kwargs)
+            acc = torch.zeros(1, dtype=torch.float64, device=self.device)
+            L.check(vdx_loss_sum(L.ptr(eps_hat), L.ptr(noise), L.ptr(acc), x_start.shape[0], self.channels, self._per_sample(x_start) // self.channels,
+                                 int(self.loss_type == 'l2'), L.stream_ptr()))
+            return (acc / float(x_start.numel())).to(torch.float32).reshape(())
         mk = None if frame_mask is None else self._dev_mask(frame_mask, x_start.shape)
         x_noisy = self.q_sample(x_start, t32, noise=noise, frame_mask=mk, _pre=_pre)
         if is_list_str(cond):

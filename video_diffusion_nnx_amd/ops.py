@@ -869,3 +869,48 @@ def final_conv_backward_wide(x, d_out, kernel, scratch=None):
     L.check(L.vdx_final_conv_backward_wide(L.ptr(x), _is16(x), L.ptr(d_out), L.ptr(kernel.contiguous()), L.ptr(dx), L.ptr(dw), L.ptr(db), npix, D_, cout,
                                            L.ptr(scratch), 0 if scratch is None else scratch.numel(), L.stream_ptr()))
     return dx, dw, db
+
+
+# ---- cascaded super-resolution (vdx.h: "Cascaded super-resolution"): xin [B,2C,F,S,S] = [ x_t | aug(up(2 lo - 1)) ] ----
+
+def lowres_down(x, ft: int, fs: int):
+    """The box mean of x [B,C,F,S,S] over ft x fs x fs blocks -> [B,C,F/ft,S/fs,S/fs] (fp32 sums in a fixed order; (1, 1): x's bits)."""
+    assert x.dtype == torch.float32 and x.dim() == 5 and x.shape[3] == x.shape[4]
+    B, Cc, Fr, S, _ = x.shape
+    ft, fs = int(ft), int(fs)
+    lo = torch.empty(B, Cc, Fr // max(ft, 1), S // max(fs, 1), S // max(fs, 1), dtype=torch.float32, device=x.device)
+    L.check(L.vdx_lowres_down(L.ptr(x.contiguous()), L.ptr(lo), B, Cc, Fr, S, ft, fs, L.stream_ptr()))
+    return lo
+
+
+def lowres_input(lo, ft: int, fs: int, *, x0=None, t=None, noise=None, tables=None, aug_levels=None, seed=0, draw=0, pre=(1.0, 0.0), out=None):
+    """One launch that builds the super-resolution network input xin [B,2C,F,S,S] from lo [B,C,F/ft,S/fs,S/fs] in [0, 1]: planes [C, 2C)
+    = aug(up(2 lo - 1)); with x0 [B,C,F,S,S] (and t int32 [B], noise like x0) planes [0, C) = vdx_q_sample's x_t on x0 pre[0] + pre[1],
+    without x0 they are left as they are (zeros in a fresh tensor).  tables = (sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod),
+    float32 [T] on the device: needed with x0 or aug_levels.  aug_levels int32 [B] on the device (-1 = none for that sample): the noise is
+    Philox(seed, draw) in randn's layout.  out: an xin to write into."""
+    assert lo.dtype == torch.float32 and lo.dim() == 5 and lo.shape[3] == lo.shape[4]
+    B, Cc, f, s, _ = lo.shape
+    ft, fs = int(ft), int(fs)
+    Fr, S = f * ft, s * fs
+    if out is None:
+        out = (torch.empty if x0 is not None else torch.zeros)(B, 2 * Cc, Fr, S, S, dtype=torch.float32, device=lo.device)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (B, 2 * Cc, Fr, S, S)
+    if x0 is not None:
+        assert tuple(x0.shape) == (B, Cc, Fr, S, S) and tuple(noise.shape) == tuple(x0.shape) and t.dtype == torch.int32
+    if aug_levels is not None:
+        assert aug_levels.dtype == torch.int32 and tuple(aug_levels.shape) == (B,)
+    sa, sm = (None, None) if tables is None else tables
+    L.check(L.vdx_lowres_input(L.ptr(x0), L.ptr(t), L.ptr(noise), L.ptr(lo), L.ptr(aug_levels), L.ptr(out), L.ptr(sa), L.ptr(sm),
+                               0 if sa is None else sa.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, float(pre[0]),
+                               float(pre[1]), B, Cc, Fr, S, ft, fs, L.stream_ptr()))
+    return out
+
+
+def lowres_pack(img, xin):
+    """xin[:, :C] = img for img [B,C,F,S,S] and xin [B,2C,F,S,S] (the first launch of a super-resolution sampling step); xin[:, C:] is
+    not touched.  Returns xin."""
+    B, per = img.shape[0], img.numel() // img.shape[0]
+    assert img.dtype == torch.float32 and xin.dtype == torch.float32 and xin.numel() == 2 * img.numel() and xin.shape[0] == B
+    L.check(L.vdx_lowres_pack(L.ptr(img), L.ptr(xin), B, per, L.stream_ptr()))
+    return xin

@@ -9,7 +9,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .gaussian_diffusion import frame_mask as expand_frame_mask, split_key, vdx_loss_sum, vdx_q_sample
+from .gaussian_diffusion import frame_mask as expand_frame_mask, lowres_aug_levels, split_key, vdx_loss_sum, vdx_q_sample
 
 _vp = C.c_void_p
 vdx_loss_grad = L._sig('vdx_loss_grad', C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_long, C.c_int, _vp])
@@ -95,6 +95,18 @@ def focus_present_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
     return split_key(loss_key, 3)[2]
 
 
+def lowres_aug_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
+    """Key of the super-resolution augmentation (the host draw of the levels and the Philox noise of the kernel) of micro-step j of
+    optimizer step `step`: child 4 of the loss key (gaussian_diffusion.lowres_aug_key of it).  Children 1-3 are the condition dropout's,
+    the noise's and the focus-present draw's; t and the frame masks hang off the micro-step key -- turning the augmentation on moves
+    none of those streams."""
+    step_key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
+    if j > 0:
+        step_key = split_key(step_key, 3 + j)[-1]
+    loss_key = split_key(step_key, 3)[2]
+    return split_key(loss_key, 4)[3]
+
+
 def focus_present_draw(batch: int, p: float, generator=None) -> torch.Tensor:
     """The focus-present mask of one micro-batch (Video Diffusion Models, Ho et al. 2022, section 3.1): uint8 [batch], Bernoulli(p),
     1 = the sample is trained as a bag of images (each frame attends to itself only in the temporal blocks).  Pure host function of
@@ -128,7 +140,8 @@ def frame_cond_masks(batch: int, frames: int, k_max: int, uncond_prob: float = 0
 
 
 def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, j: int = 0, grads: torch.Tensor = None,
-                     reducer=None, frame_mask=None, cond=None, cond_mask=None, focus_present_mask=None) -> torch.Tensor:
+                     reducer=None, frame_mask=None, cond=None, cond_mask=None, focus_present_mask=None, aug_levels=None,
+                     lowres=None) -> torch.Tensor:
     """loss, grads = value_and_grad(p_losses) (trainer.py:337-361) of one micro-batch; returns the device scalar loss.
 
     frame_mask ([F], [B,F] or anything gaussian_diffusion.frame_mask takes; default: drawn by frame_cond_masks under frame_cond_key when
@@ -144,6 +157,13 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     focus_present_mask [B] (joint image-video training; needs Unet3D(focus_present=True), without it nothing here runs; default: drawn by
     focus_present_draw under focus_present_key when 0 < tr.prob_focus_present, else none): the samples whose temporal blocks see each
     frame alone (Unet3D docstring).  tr.last_focus_mask holds the mask as given or drawn (None without one).
+
+    aug_levels [B] / lowres [B,C,F/ft,S/fs,S/fs] (a super-resolution diffusion, gd.lowres_cond, only): the network input is
+    xin = [ x_t | aug(up(2 lowres - 1)) ], built by one vdx_lowres_down (lowres defaults to the box mean of the raw batch) and one
+    vdx_lowres_input launch (gd.sr_input); aug_levels defaults to a host draw from {0..gd.lowres_aug_max-1} under lowres_aug_key (none
+    when lowres_aug_max is 0; -1 = none for that sample), the augmentation noise is Philox(lowres_aug_key, draw 0).  The forward and the
+    staged backward run on xin; the loss, its gradient and everything after them are the plain ones over gd.channels.
+    tr.last_aug_levels holds the levels as given or drawn.
 
     `grads` (default tr.grads) receives the gradient: the head stage of the backward zeroes it.  With a `reducer` the backward runs
     in stage groups and hands finished buckets of tr.grads to it; when `grads` is a second buffer (micro-steps j >= 1), each finished
@@ -211,7 +231,19 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     tr.last_focus_mask = focus_present_mask if unet.focus_present else None
     if gd.learned_variance:
         gd._lv_refuse(frame_mask=frame_mask, focus_present=fp)
-    x_noisy = gd.q_sample(x, t, noise=noise, frame_mask=mk, _pre=(2.0, -1.0))     # normalize_img folded in (:499)
+    if gd.lowres_cond is None:
+        if aug_levels is not None or lowres is not None:
+            raise ValueError('aug_levels / lowres need a super-resolution diffusion (lowres_cond=(ft, fs))')
+        x_noisy = gd.q_sample(x, t, noise=noise, frame_mask=mk, _pre=(2.0, -1.0))     # normalize_img folded in (:499)
+    else:
+        gd._sr_refuse(frame_mask=frame_mask, focus_present=fp)
+        aug_key = lowres_aug_key(tr.rng_seed, tr.rank, step, j)
+        if aug_levels is None and gd.lowres_aug_max > 0:
+            aug_levels = lowres_aug_levels(B, gd.lowres_aug_max, aug_key)
+        tr.last_aug_levels = aug_levels
+        if lowres is not None:
+            gd._sr_lowres(lowres, B)
+        x_noisy = gd.sr_input(x, t, noise, lowres=lowres, aug_levels=aug_levels, key=aug_key, _pre=(2.0, -1.0))      # [ x_t | u ]
     keep_storage = unet.act_bf16
     unet.act_bf16 = 2 if (unet.mode == 'bf16' and tr.train_act_bf16) else False
     try:
@@ -295,17 +327,19 @@ def optimizer_tail(tr, step: int, world: int, accum: int = 1, max_grad_norm=None
 
 
 def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, noise: torch.Tensor = None, frame_mask=None,
-                   cond=None, cond_mask=None, focus_present_mask=None) -> torch.Tensor:
+                   cond=None, cond_mask=None, focus_present_mask=None, aug_levels=None, lowres=None) -> torch.Tensor:
     """loss, grads = value_and_grad(p_losses); Adam; EMA  (trainer.py:337-382) for this rank's shard of the batch.
 
     `t` [B] / `noise` [B,C,F,H,W] override this rank's own draws (the reference threads `noise` through p_losses the same way,
     gaussian_diffusion.py:423-445); the data-parallel tests use them to give N ranks the shards of ONE global draw.  frame_mask: the
     shard's context-frame mask (forward_backward); each shard divides its loss by its own count of noised elements.  cond / cond_mask:
     the shard's conditions and its condition-dropout mask (forward_backward).  focus_present_mask: the shard's focus-present mask
+    (forward_backward).  aug_levels / lowres: the shard's augmentation levels and low-resolution clips of a super-resolution diffusion
     (forward_backward)."""
     reducer = tr.make_reducer()
+    sr_kw = {} if (aug_levels is None and lowres is None) else dict(aug_levels=aug_levels, lowres=lowres)
     loss = forward_backward(tr, batch, step, t, noise, reducer=reducer, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask,
-                            focus_present_mask=focus_present_mask)
+                            focus_present_mask=focus_present_mask, **sr_kw)
     reducer.finish()
     optimizer_tail(tr, step, reducer.world)
     return loss

@@ -299,16 +299,18 @@ class Trainer:
         return red
 
     def train_step(self, batch: torch.Tensor, step: int, t=None, noise=None, frame_mask=None, cond=None, cond_mask=None,
-                   focus_present_mask=None) -> torch.Tensor:
+                   focus_present_mask=None, aug_levels=None, lowres=None) -> torch.Tensor:
         """One `_pjit_train_step` on this rank's shard of the batch.  Returns the (device) scalar loss of the shard.
         t / noise: optional explicit timesteps / noise of the shard (default: this rank's own Philox draws).  frame_mask: optional
         explicit context-frame mask of the shard ([F] or [B,F], 1 = clean context; default: drawn when frame_cond_max > 0).  cond: the
         shard's conditions [B, cond_dim] (a conditioned UNet needs them); cond_mask: optional explicit condition-dropout mask [B], 1 = null
         embedding (default: drawn when null_cond_prob > 0).  focus_present_mask: optional explicit focus-present mask [B] of the shard
-        (Unet3D(focus_present=True); default: drawn when prob_focus_present > 0)."""
+        (Unet3D(focus_present=True); default: drawn when prob_focus_present > 0).  aug_levels / lowres (a super-resolution diffusion,
+        GaussianDiffusion(lowres_cond=...), only): optional explicit augmentation levels [B] (-1 = none; default: drawn from
+        {0..lowres_aug_max-1}) and low-resolution clips (default: the box mean of the batch)."""
         from .train_step import run_train_step
         return run_train_step(self, batch, step, t=t, noise=noise, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask,
-                              focus_present_mask=focus_present_mask)
+                              focus_present_mask=focus_present_mask, aug_levels=aug_levels, lowres=lowres)
 
     @property
     def accum_steps(self) -> int:
