@@ -730,6 +730,43 @@ int vdx_dpm_sample_loop_sr(vdx_handle* h, const float* params, const void* packe
                            const float* cond, int clip_denoised, int order, const float* tables, int timesteps, float percentile,
                            float* thres_buf, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
 
+/* Loss-aware timestep sampling (EXTENSION, parity unpinned: no reference code.  Nichol & Dhariwal 2021, "Improved DDPM", section 3.3;
+ * improved-diffusion's LossSecondMomentResampler, restated in fp64 in tests/_tsampler_ref.py).  Off unless these entries are called.
+ * State (the caller's device memory): hist double [T][H], the last H = history losses seen at each of the T = timesteps levels (oldest
+ * first), and count int32 [T], how many of a row's slots are filled.  Probabilities, with eps = uniform_prob:
+ *   cold (any count[t] < H):  p_t = 1 / T
+ *   warm:  w_t = sqrt((sum_j hist[t][j]^2) / H),  W = sum_t w_t,  p_t = (w_t / W)(1 - eps) + eps / T;  W zero or not finite: p_t = 1 / T
+ * No atomics in any of these kernels and every sum in a fixed order: the bits of every output depend on the inputs only.
+ *
+ * vdx_tsampler_draw: one workgroup; w, p and the inclusive prefix sum of p in double in LDS (2 T doubles: the cap T <= 4096).  Sample b:
+ *   r = Philox4x32-10(counter (b, 0, draw lo, draw hi), key (seed lo, seed hi)),  m = (r0 << 21) | (r1 >> 11),  u = (m + 0.5) 2^-53;
+ *   cold: t = min(floor(u T), T - 1), iw = 1.0 exactly;  warm: t = the first index whose prefix sum exceeds u (binary search), at most
+ *   T - 1, iw = 1 / (T p_t).  t_given (may be NULL) [batch]: nothing is drawn, t_out = t_given and iw is that of the current p (1.0 when
+ *   cold; a level outside [0, T) reads the nearest one).  p_out (may be NULL) [T] receives p.  Any batch >= 1.
+ *   Refused before any launch (VDX_ERR_INVALID): timesteps outside [1, 4096], history outside [1, 32], uniform_prob outside (0, 1],
+ *   batch < 1.
+ * vdx_tsampler_update: entries double [n][2] = (t, loss), applied as if one after the other in index order: an entry whose loss or level
+ *   is not finite, or whose level is outside [0, T), is skipped; count[t] == H: the row moves left by one and the loss goes last;
+ *   otherwise hist[t][count[t]++] = loss.  (One workgroup; the first entry of each level applies that level's entries in order.)
+ * vdx_loss_weighted: the plain loss per sample and its importance-weighted gradient in ONE pass over eps_hat (channel-last [B,F,H,W,C])
+ *   and noise ([B,C,F,H,W]): d = eps_hat - noise in fp32 as vdx_loss_sum / vdx_loss_grad form it, |d| (l2 == 0) or d^2 added in double
+ *   through a fixed-order tree and an in-order final.  out [batch + 1] doubles: out[b] = l_b, the sample's mean, out[batch] =
+ *   (1 / batch) sum_b iw_b l_b.  d_eps_hat (may be NULL) = l2 ? 2.0f d f_b : sign(d) f_b with f_b = (float)iw_b * inv_count, inv_count
+ *   the float vdx_loss_grad uses: with iw NULL (all weights 1) or iw_b == 1 the gradient is vdx_loss_grad's bit for bit.  scratch:
+ *   vdx_loss_weighted_scratch_doubles(batch) doubles.  Any channels * fhw.
+ * vdx_hybrid_loss_w: vdx_hybrid_loss with importance weights iw [batch] (NULL: vdx_hybrid_loss bit for bit): the three totals
+ *   out[2 batch ..] are (1 / batch) sum_b iw_b (.)_b and both halves of d_out carry iw_b -- formed in double and rounded to fp32 once
+ *   where iw_b != 1, the unweighted expressions and bits where iw_b == 1; the per-sample pairs out[0 .. 2 batch) stay unweighted. */
+int vdx_tsampler_draw(const double* hist, const int* count, int timesteps, int history, double uniform_prob, const int* t_given, uint64_t seed,
+                      uint64_t draw, int* t_out, double* iw_out, double* p_out, int batch, void* stream);
+int vdx_tsampler_update(double* hist, int* count, int timesteps, int history, const double* entries, int n, void* stream);
+size_t vdx_loss_weighted_scratch_doubles(int batch);
+int vdx_loss_weighted(const float* eps_hat, const float* noise, const double* iw, float* d_eps_hat, double* scratch, double* out, int batch,
+                      int channels, long fhw, int l2, void* stream);
+int vdx_hybrid_loss_w(const float* x, const float* noise, const float* out2, const int* t, const double* lv_tables64, int timesteps,
+                      float pre_scale, float pre_shift, int l2, double vlb_weight, int want_grad, float* d_out, double* scratch, double* out,
+                      int batch, int channels, long per_sample, const double* iw, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */

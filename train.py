@@ -16,7 +16,12 @@ trainer.prob_focus_present: P in the YAML; joint image-video training: with prob
 frame attending to itself only in the temporal blocks; sample.py --focus-present draws frames in that image mode);
 diffusion.lowres_cond: {temporal: ft, spatial: fs, aug_max: L} in the YAML (no flag; sample.build_models reads it): the second stage of
 a cascade -- the network is trained on [ x_t | the batch's own ft x fs x fs box mean, upsampled and noised to a level below L ]; sample
-such a model with sample.py --lowres-path; not with --frame_cond_max or --focus_present)."""
+such a model with sample.py --lowres-path; not with --frame_cond_max or --focus_present);
+--timestep_sampler {uniform,loss-second-moment} [--sampler_history H] [--sampler_uniform_prob P] (or trainer.timestep_sampler /
+sampler_history / sampler_uniform_prob in the YAML; absent = uniform: Improved DDPM's loss-aware sampler -- t is drawn on the device with
+probability ~ the root of the second moment of the last H losses seen at each level, mixed with P of the uniform distribution, and each
+sample's loss is weighted by 1 / (T p_t); uniform until every level has H losses; the state is not checkpointed, a resumed run restarts it
+cold; not with --frame_cond_max)."""
 import argparse
 import logging
 import os
@@ -44,6 +49,11 @@ FLAGS = (
                                                                  'images (also trainer.prob_focus_present in the YAML; default 0)')),
     ('--cond_path', dict(type=str, default=None, help='conditional training: float32 [N, cond_dim] .npy, row i = the condition of video i')),
     ('--null_cond_prob', dict(type=float, default=None, help='with --cond_path: probability of training a sample on the null embedding (0.1)')),
+    ('--timestep_sampler', dict(choices=('uniform', 'loss-second-moment'), default=None,
+                                help='how t is drawn: uniformly (default), or on the device by the second moment of the per-level loss '
+                                     'history with importance weights (also trainer.timestep_sampler in the YAML)')),
+    ('--sampler_history', dict(type=int, default=None, help='with loss-second-moment: losses kept per level, 1..32 (10)')),
+    ('--sampler_uniform_prob', dict(type=float, default=None, help='with loss-second-moment: share of the uniform distribution, (0, 1] (0.001)')),
 )
 
 
@@ -83,6 +93,23 @@ def main(argv=None):
         if not 0.0 <= float(p_fp) <= 1.0:
             ap.error(f'prob_focus_present must be in [0, 1], got {p_fp}')
         Trainer.prob_focus_present = float(p_fp)
+    # loss-aware timestep sampling: Trainer attributes as well; absent = off
+    ts_kind, ts_hist, ts_prob = tc.pop('timestep_sampler', None), tc.pop('sampler_history', None), tc.pop('sampler_uniform_prob', None)
+    ts_kind = a.timestep_sampler if a.timestep_sampler is not None else ts_kind
+    ts_hist = a.sampler_history if a.sampler_history is not None else ts_hist
+    ts_prob = a.sampler_uniform_prob if a.sampler_uniform_prob is not None else ts_prob
+    if ts_kind is not None:
+        if ts_kind not in ('uniform', 'loss-second-moment'):
+            ap.error(f"timestep_sampler must be 'uniform' or 'loss-second-moment', got {ts_kind!r}")
+        Trainer.timestep_sampler = ts_kind
+    if ts_hist is not None:
+        if not 1 <= int(ts_hist) <= 32:
+            ap.error(f'sampler_history must be in [1, 32], got {ts_hist}')
+        Trainer.sampler_history = int(ts_hist)
+    if ts_prob is not None:
+        if not 0.0 < float(ts_prob) <= 1.0:
+            ap.error(f'sampler_uniform_prob must be in (0, 1], got {ts_prob}')
+        Trainer.sampler_uniform_prob = float(ts_prob)
     if a.train_num_steps is not None:
         tc['train_num_steps'] = a.train_num_steps
     if a.dataset_path is not None:

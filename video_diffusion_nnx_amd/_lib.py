@@ -139,6 +139,9 @@ vdx_p_sample_loop_lv = _sig('vdx_p_sample_loop_lv', c_int, [c_void_p] * 9 + [c_i
 vdx_hybrid_scratch_doubles = _sig('vdx_hybrid_scratch_doubles', c_size_t, [c_int])
 vdx_hybrid_loss = _sig('vdx_hybrid_loss', c_int, [c_void_p] * 5 + [c_int, c_float, c_float, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p,
                                                   c_int, c_int, c_long, c_void_p])
+# (vdx.h: "Loss-aware timestep sampling": vdx_hybrid_loss with importance weights; the sampler's own entries are bound in timestep_sampler.py)
+vdx_hybrid_loss_w = _sig('vdx_hybrid_loss_w', c_int, [c_void_p] * 5 + [c_int, c_float, c_float, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p,
+                                                      c_int, c_int, c_long, c_void_p, c_void_p])
 vdx_vlb_terms_lv = _sig('vdx_vlb_terms_lv', c_int, [c_void_p] * 4 + [c_int, c_void_p, _u64, _u64, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p])
 vdx_vlb_loop_lv = _sig('vdx_vlb_loop_lv', c_int, [c_void_p] * 9 + [c_int, c_void_p, c_int, c_int, c_void_p, _u64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                                   c_int, c_int, c_void_p])

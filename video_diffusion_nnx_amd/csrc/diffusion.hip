@@ -914,6 +914,10 @@ __global__ __launch_bounds__(256) void hybrid_loss_kernel(HybridArgs P) {
     const int tb = vlb_level(P.t, b, P.T);
     const LvLevel L = lv_level(P.tab, P.T, tb);
     const double dv_scale = 0.5 * (L.max_log - L.min_log) * P.vscale;
+    // importance weight of the sample (vdx_hybrid_loss_w): none, or exactly 1 -> the unweighted expressions and their bits
+    const double iwb = P.iw ? P.iw[b] : 1.0;
+    const bool plain = iwb == 1.0;
+    const double g_scale = P.inv_count64 * iwb;
     const long per = P.per_sample, fhw = P.per_sample / P.C;
     const int C2 = 2 * P.C;
     const size_t base = (size_t)b * per, base2 = 2 * base;
@@ -951,8 +955,13 @@ __global__ __launch_bounds__(256) void hybrid_loss_kernel(HybridArgs P) {
             acc[1] += lv_vb_elem(L, tb, x0, xt, xh, lv_logvar((double)vv, L.max_log, L.min_log), &dlv);
             if (P.d_out) {
                 const float d = ev - nv[k];
-                P.d_out[j] = P.l2 ? 2.0f * d * P.inv_count : ((d > 0.f) - (d < 0.f)) * P.inv_count;
-                P.d_out[j + P.C] = (float)(dlv * dv_scale);
+                if (plain) {
+                    P.d_out[j] = P.l2 ? 2.0f * d * P.inv_count : ((d > 0.f) - (d < 0.f)) * P.inv_count;
+                    P.d_out[j + P.C] = (float)(dlv * dv_scale);
+                } else {                                                        // both halves in double, rounded once
+                    P.d_out[j] = (float)((P.l2 ? 2.0 * de : (double)((de > 0.0) - (de < 0.0))) * g_scale);
+                    P.d_out[j + P.C] = (float)(dlv * dv_scale * iwb);
+                }
             }
         }
     }
@@ -962,7 +971,7 @@ __global__ __launch_bounds__(256) void hybrid_loss_kernel(HybridArgs P) {
 // One workgroup: thread b adds sample b's partials in index order -> out[2 b ..] = the sample's means (mse, vb); then thread 0 adds the
 // samples' sums in index order -> out[2 B ..] = (mean mse, mean vb, mean mse + w mean vb) over the batch
 __global__ __launch_bounds__(256) void hybrid_final_kernel(const double* __restrict__ partial, double* __restrict__ out, int B, long per_sample,
-                                                           double w, double* __restrict__ sums) {
+                                                           double w, double* __restrict__ sums, const double* __restrict__ iw) {
     for (int b = threadIdx.x; b < B; b += blockDim.x) {
         double a[2] = {0.0, 0.0};
         for (int i = 0; i < kVlbBlocks; ++i)
@@ -974,7 +983,8 @@ __global__ __launch_bounds__(256) void hybrid_final_kernel(const double* __restr
     __syncthreads();
     if (threadIdx.x == 0) {
         double s0 = 0.0, s1 = 0.0;
-        for (int b = 0; b < B; ++b) { s0 += sums[2 * b]; s1 += sums[2 * b + 1]; }
+        if (iw) for (int b = 0; b < B; ++b) { s0 += iw[b] * sums[2 * b]; s1 += iw[b] * sums[2 * b + 1]; }      // the totals carry iw_b
+        else for (int b = 0; b < B; ++b) { s0 += sums[2 * b]; s1 += sums[2 * b + 1]; }
         const double n = (double)B * (double)per_sample;
         out[2 * B] = s0 / n; out[2 * B + 1] = s1 / n; out[2 * B + 2] = s0 / n + w * (s1 / n);
     }
@@ -1175,7 +1185,8 @@ hipError_t launch_hybrid_loss(const HybridArgs& a, double* out, double w, int B,
                        .launch(hybrid_loss_kernel, dim3(kVlbBlocks, B), dim3(256), 0, a);
     if (e != hipSuccess) return e;
     return LaunchScope(st, "hybrid_final_kernel", 0.0, 0.0, "B%d", B)
-        .launch(hybrid_final_kernel, dim3(1), dim3(256), 0, (const double*)a.partial, out, B, a.per_sample, w, a.partial + (size_t)B * kVlbBlocks * 3);
+        .launch(hybrid_final_kernel, dim3(1), dim3(256), 0, (const double*)a.partial, out, B, a.per_sample, w, a.partial + (size_t)B * kVlbBlocks * 3,
+                a.iw);
 }
 
 hipError_t launch_vlb_terms_lv(const VlbArgs& a, int B, hipStream_t st) {

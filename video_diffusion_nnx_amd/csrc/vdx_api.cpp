@@ -1325,10 +1325,9 @@ int vdx_p_sample_loop_lv(vdx_handle* h, const float* params, const void* packed,
 
 size_t vdx_hybrid_scratch_doubles(int batch) { return batch > 0 ? vdx::hybrid_scratch_doubles(batch) : 0; }
 
-int vdx_hybrid_loss(const float* x, const float* noise, const float* out2, const int* t, const double* lv_tables64, int timesteps,
-                    float pre_scale, float pre_shift, int l2, double vlb_weight, int want_grad, float* d_out, double* scratch, double* out,
-                    int batch, int channels, long per_sample, void* stream) {
-    const char* who = "hybrid_loss";
+static int hybrid_loss_call(const char* who, const float* x, const float* noise, const float* out2, const int* t, const double* lv_tables64,
+                            int timesteps, float pre_scale, float pre_shift, int l2, double vlb_weight, int want_grad, float* d_out,
+                            double* scratch, double* out, const double* iw, int batch, int channels, long per_sample, void* stream) {
     if (!x || !noise || !out2 || !t || !lv_tables64 || !scratch || !out) VDX_REFUSE(who, "null tensor");
     if (want_grad && !d_out) VDX_REFUSE(who, "want_grad needs d_out");
     if (int rc = lv_rules(who, 1, 1, batch, channels, per_sample)) return rc;
@@ -1341,7 +1340,63 @@ int vdx_hybrid_loss(const float* x, const float* noise, const float* out2, const
     a.x = x; a.noise = noise; a.out2 = out2; a.d_out = want_grad ? d_out : nullptr; a.t = t; a.tab = lv_tables64; a.T = timesteps;
     a.l2 = l2 ? 1 : 0; a.C = channels; a.per_sample = per_sample; a.pre_scale = pre_scale; a.pre_shift = pre_shift;
     a.inv_count = 1.0f / (float)((long)batch * per_sample); a.vscale = vlb_weight / (n * 0.69314718055994530942); a.partial = scratch;
+    a.iw = iw; a.inv_count64 = 1.0 / n;
     VDX_HIP(vdx::launch_hybrid_loss(a, out, vlb_weight, batch, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_hybrid_loss(const float* x, const float* noise, const float* out2, const int* t, const double* lv_tables64, int timesteps,
+                    float pre_scale, float pre_shift, int l2, double vlb_weight, int want_grad, float* d_out, double* scratch, double* out,
+                    int batch, int channels, long per_sample, void* stream) {
+    return hybrid_loss_call("hybrid_loss", x, noise, out2, t, lv_tables64, timesteps, pre_scale, pre_shift, l2, vlb_weight, want_grad, d_out, scratch,
+                            out, nullptr, batch, channels, per_sample, stream);
+}
+
+int vdx_hybrid_loss_w(const float* x, const float* noise, const float* out2, const int* t, const double* lv_tables64, int timesteps,
+                      float pre_scale, float pre_shift, int l2, double vlb_weight, int want_grad, float* d_out, double* scratch, double* out,
+                      int batch, int channels, long per_sample, const double* iw, void* stream) {
+    if ((uintptr_t)iw % 8) VDX_REFUSE("hybrid_loss_w", "iw must be 8-byte aligned");
+    return hybrid_loss_call("hybrid_loss_w", x, noise, out2, t, lv_tables64, timesteps, pre_scale, pre_shift, l2, vlb_weight, want_grad, d_out,
+                            scratch, out, iw, batch, channels, per_sample, stream);
+}
+
+// ---- loss-aware timestep sampling (vdx.h: "Loss-aware timestep sampling") ----
+
+int vdx_tsampler_draw(const double* hist, const int* count, int timesteps, int history, double uniform_prob, const int* t_given, uint64_t seed,
+                      uint64_t draw, int* t_out, double* iw_out, double* p_out, int batch, void* stream) {
+    const char* who = "tsampler_draw";
+    if (timesteps < 1 || timesteps > 4096) VDX_REFUSE(who, "timesteps must be in [1, 4096]");
+    if (history < 1 || history > 32) VDX_REFUSE(who, "history must be in [1, 32]");
+    if (!(uniform_prob > 0.0 && uniform_prob <= 1.0)) VDX_REFUSE(who, "uniform_prob must be in (0, 1]");
+    if (batch < 1) VDX_REFUSE(who, "batch must be >= 1");
+    if (!hist || !count || !t_out || !iw_out) VDX_REFUSE(who, "null tensor");
+    if ((uintptr_t)hist % 8 || (uintptr_t)iw_out % 8 || (uintptr_t)p_out % 8) VDX_REFUSE(who, "hist / iw_out / p_out must be 8-byte aligned");
+    VDX_HIP(vdx::launch_tsampler_draw(hist, count, timesteps, history, uniform_prob, t_given, seed, draw, t_out, iw_out, p_out, batch,
+                                      (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_tsampler_update(double* hist, int* count, int timesteps, int history, const double* entries, int n, void* stream) {
+    const char* who = "tsampler_update";
+    if (timesteps < 1 || timesteps > 4096) VDX_REFUSE(who, "timesteps must be in [1, 4096]");
+    if (history < 1 || history > 32) VDX_REFUSE(who, "history must be in [1, 32]");
+    if (n < 0) VDX_REFUSE(who, "n must be >= 0");
+    if (!hist || !count || (n > 0 && !entries)) VDX_REFUSE(who, "null tensor");
+    if ((uintptr_t)hist % 8 || (uintptr_t)entries % 8) VDX_REFUSE(who, "hist / entries must be 8-byte aligned");
+    if (n == 0) return VDX_OK;
+    VDX_HIP(vdx::launch_tsampler_update(hist, count, timesteps, history, entries, n, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+size_t vdx_loss_weighted_scratch_doubles(int batch) { return batch > 0 ? vdx::loss_weighted_scratch_doubles(batch) : 0; }
+
+int vdx_loss_weighted(const float* eps_hat, const float* noise, const double* iw, float* d_eps_hat, double* scratch, double* out, int batch,
+                      int channels, long fhw, int l2, void* stream) {
+    const char* who = "loss_weighted";
+    if (!eps_hat || !noise || !scratch || !out) VDX_REFUSE(who, "null tensor");
+    if (batch < 1 || channels < 1 || fhw < 1) VDX_REFUSE(who, "batch, channels and fhw must be >= 1");
+    if ((uintptr_t)iw % 8 || (uintptr_t)scratch % 8 || (uintptr_t)out % 8) VDX_REFUSE(who, "iw / scratch / out must be 8-byte aligned");
+    VDX_HIP(vdx::launch_loss_weighted(eps_hat, noise, iw, d_eps_hat, scratch, out, batch, channels, fhw, l2 ? 1 : 0, (hipStream_t)stream));
     return VDX_OK;
 }
 

@@ -276,6 +276,7 @@ struct HybridArgs {
     float pre_scale, pre_shift;                         // x0 = x pre_scale + pre_shift (normalize_img)
     float inv_count; double vscale;                     // 1 / N as launch_loss_grad forms it; w / (N ln 2)
     double* partial;                                    // hybrid_scratch_doubles(B)
+    const double* iw; double inv_count64;               // importance weights [B] or null (vdx_hybrid_loss_w); 1 / N in double
 };
 size_t hybrid_scratch_doubles(int B);
 // out [2 B + 3] doubles: per-sample means (mse, vb), then the batch's (mse, vb, mse + w vb)
@@ -306,6 +307,15 @@ hipError_t launch_loss_grad_masked(const float* eps_hat, const float* noise, con
                                    int B, int Cc, long fhw, int l2, hipStream_t st);
 
 hipError_t launch_loss_grad(const float* eps_hat, const float* noise, float* d_eps, int B, int Cc, long fhw, int l2, hipStream_t st);
+// Loss-aware timestep sampling (vdx.h: "Loss-aware timestep sampling"; tsampler.hip).  hist double [T][H], count int [T]; one workgroup each.
+size_t tsampler_draw_lds_bytes(int T);
+hipError_t launch_tsampler_draw(const double* hist, const int* count, int T, int H, double eps, const int* t_given, unsigned long long seed,
+                                unsigned long long draw, int* t_out, double* iw_out, double* p_out, int batch, hipStream_t st);
+hipError_t launch_tsampler_update(double* hist, int* count, int T, int H, const double* entries, int n, hipStream_t st);
+size_t loss_weighted_scratch_doubles(int B);
+// out [B + 1] doubles: the per-sample means, then (1 / B) sum_b iw_b l_b; d_eps (may be null) channel-last like eps_hat
+hipError_t launch_loss_weighted(const float* eps_hat, const float* noise, const double* iw, float* d_eps, double* scratch, double* out, int B,
+                                int Cc, long fhw, int l2, hipStream_t st);
 hipError_t launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
                            long step_count, float grad_scale, int do_ema, float decay, hipStream_t st);
 hipError_t launch_adam_ema_clip(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,

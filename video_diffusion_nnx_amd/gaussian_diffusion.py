@@ -608,16 +608,24 @@ class GaussianDiffusion:
         shape = (-1, 1, 1, 1, 1)
         return (f * tab[6][t.long()].reshape(shape) + (1.0 - f) * tab[7][t.long()].reshape(shape)).float()
 
-    def hybrid_loss(self, x_start, noise, out2, t32, *, want_grad: bool = False, _pre=(1.0, 0.0)):
+    def hybrid_loss(self, x_start, noise, out2, t32, *, want_grad: bool = False, _pre=(1.0, 0.0), iw=None):
         """(loss, d_out): the hybrid loss of the network output out2 [B,F,H,W,2C] as a float32 device scalar and, with want_grad, its
-        gradient in out2 (vdx_hybrid_loss: one pass, no host read).  last_loss_terms = the device doubles (mse, vb)."""
+        gradient in out2 (vdx_hybrid_loss: one pass, no host read).  last_loss_terms = the device doubles (mse, vb).  iw (float64 [B] on
+        the device; loss-aware timestep sampling): the totals and the gradient carry the importance weights (vdx_hybrid_loss_w), the
+        per-sample pairs stay unweighted."""
         B = x_start.shape[0]
         scratch = torch.empty(L.vdx_hybrid_scratch_doubles(B), dtype=torch.float64, device=self.device)
         out = torch.empty(2 * B + 3, dtype=torch.float64, device=self.device)
         d_out = torch.empty_like(out2) if want_grad else None
-        L.check(L.vdx_hybrid_loss(L.ptr(x_start), L.ptr(noise), L.ptr(out2), L.ptr(t32), L.ptr(self._lv_tab64()), self.num_timesteps,
-                                  float(_pre[0]), float(_pre[1]), int(self.loss_type == 'l2'), self.vlb_weight, int(want_grad), L.ptr(d_out),
-                                  L.ptr(scratch), L.ptr(out), B, self.channels, self._per_sample(x_start), L.stream_ptr()))
+        if iw is None:
+            L.check(L.vdx_hybrid_loss(L.ptr(x_start), L.ptr(noise), L.ptr(out2), L.ptr(t32), L.ptr(self._lv_tab64()), self.num_timesteps,
+                                      float(_pre[0]), float(_pre[1]), int(self.loss_type == 'l2'), self.vlb_weight, int(want_grad), L.ptr(d_out),
+                                      L.ptr(scratch), L.ptr(out), B, self.channels, self._per_sample(x_start), L.stream_ptr()))
+        else:
+            L.check(L.vdx_hybrid_loss_w(L.ptr(x_start), L.ptr(noise), L.ptr(out2), L.ptr(t32), L.ptr(self._lv_tab64()), self.num_timesteps,
+                                        float(_pre[0]), float(_pre[1]), int(self.loss_type == 'l2'), self.vlb_weight, int(want_grad),
+                                        L.ptr(d_out), L.ptr(scratch), L.ptr(out), B, self.channels, self._per_sample(x_start), L.ptr(iw),
+                                        L.stream_ptr()))
         self.last_loss_terms = out[2 * B:2 * B + 2]
         self.last_loss_per_sample = out[:2 * B].reshape(B, 2)
         return out[2 * B + 2].to(torch.float32).reshape(()), d_out

@@ -833,15 +833,21 @@ def p_sample_step_lv(x, out2, tables, *, level=None, step=0, step_dev=None, nois
     return out
 
 
-def hybrid_loss(x, noise, out2, t, tables64, *, pre=(1.0, 0.0), l2=False, vlb_weight=1.0, want_grad=True):
+def hybrid_loss(x, noise, out2, t, tables64, *, pre=(1.0, 0.0), l2=False, vlb_weight=1.0, want_grad=True, weighted=False, iw=None):
     """mean |eps_hat - eps|^p + vlb_weight * mean vb (bits per element, eps_hat detached) -> (out float64 [2B + 3] = per-sample means
     (mse, vb) then the batch's (mse, vb, total), d_out float32 like out2 or None).  x [B,C,F,H,W] (x0 = x pre[0] + pre[1]), t int32 [B],
-    tables64 float64 [LV_ROWS, T] (make_lv_tables(T)['tab64'])."""
+    tables64 float64 [LV_ROWS, T] (make_lv_tables(T)['tab64']).  weighted: through vdx_hybrid_loss_w with the importance weights iw
+    (float64 [B], or None: its null form)."""
     assert x.dtype == torch.float32 and x.dim() == 5 and tables64.dtype == torch.float64 and tables64.shape[0] == L.LV_ROWS
     B, per = x.shape[0], x.numel() // x.shape[0]
     scratch = torch.empty(L.vdx_hybrid_scratch_doubles(B), dtype=torch.float64, device=x.device)
     out = torch.empty(2 * B + 3, dtype=torch.float64, device=x.device)
     d_out = torch.empty_like(out2) if want_grad else None
+    if weighted or iw is not None:
+        L.check(L.vdx_hybrid_loss_w(L.ptr(x), L.ptr(noise), L.ptr(out2), L.ptr(t), L.ptr(tables64), tables64.shape[1], float(pre[0]), float(pre[1]),
+                                    int(bool(l2)), float(vlb_weight), int(bool(want_grad)), L.ptr(d_out), L.ptr(scratch), L.ptr(out), B, x.shape[1],
+                                    per, L.ptr(iw), L.stream_ptr()))
+        return out, d_out
     L.check(L.vdx_hybrid_loss(L.ptr(x), L.ptr(noise), L.ptr(out2), L.ptr(t), L.ptr(tables64), tables64.shape[1], float(pre[0]), float(pre[1]),
                               int(bool(l2)), float(vlb_weight), int(bool(want_grad)), L.ptr(d_out), L.ptr(scratch), L.ptr(out), B, x.shape[1], per,
                               L.stream_ptr()))

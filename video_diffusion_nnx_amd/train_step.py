@@ -9,6 +9,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from .timestep_sampler import loss_weighted
 from .gaussian_diffusion import frame_mask as expand_frame_mask, lowres_aug_levels, split_key, vdx_loss_sum, vdx_q_sample
 
 _vp = C.c_void_p
@@ -165,6 +166,12 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     staged backward run on xin; the loss, its gradient and everything after them are the plain ones over gd.channels.
     tr.last_aug_levels holds the levels as given or drawn.
 
+    Loss-aware timestep sampling (tr.sampler, Trainer.timestep_sampler = 'loss-second-moment'): t and the importance weights iw come from
+    one vdx_tsampler_draw launch under t_key (draw 0) in place of the host randint (an explicit t only gets its weights); the per-sample
+    losses, the weighted mean (the returned loss: what is optimised) and the weighted gradient from one vdx_loss_weighted pass (or
+    vdx_hybrid_loss_w); after the backward is enqueued the (t_b, l_b) enter the sampler's history (_sampler_update).  No host read is
+    added.  tr.last_iw / tr.last_loss_per_sample hold the device tensors of the micro-batch.  Refuses frame_mask / frame_cond_max.
+
     `grads` (default tr.grads) receives the gradient: the head stage of the backward zeroes it.  With a `reducer` the backward runs
     in stage groups and hands finished buckets of tr.grads to it; when `grads` is a second buffer (micro-steps j >= 1), each finished
     bucket is first added into tr.grads on the current stream.  Without a reducer the backward is one call and nothing is reduced
@@ -177,16 +184,27 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     assert tuple(x.shape[1:]) == (gd.channels, gd.num_frames, gd.image_size, gd.image_size), \
         f'expected [b, {gd.channels}, {gd.num_frames}, {gd.image_size}, {gd.image_size}], got {tuple(x.shape)}'     # check_shape (:490)
     t_key, noise_key = micro_step_keys(tr.rng_seed, tr.rank, step, j)
-    if t is None:
+    smp = getattr(tr, 'sampler', None)
+    if smp is not None and (frame_mask is not None or int(tr.frame_cond_max) > 0):
+        raise ValueError('timestep_sampler=loss-second-moment does not serve frame-conditioned training (frame_mask / frame_cond_max): the '
+                         'masked loss has no per-sample form')
+    if t is None and smp is None:
         g = torch.Generator().manual_seed(t_key & 0x7FFFFFFFFFFFFFFF)
         t = torch.randint(0, gd.num_timesteps, (B,), generator=g, dtype=torch.int32)
-    t = torch.as_tensor(t)
-    if t.device.type == 'cpu' and dev.type == 'cuda':
+    t = None if t is None else torch.as_tensor(t)
+    if t is None:
+        pass
+    elif t.device.type == 'cpu' and dev.type == 'cuda':
         # (pinned + non-blocking: a pageable host-to-device copy waits for the stream to drain -- one host sync per step that kept the
         # launch queue from running ahead of the GPU)
         t = t.to(torch.int32).pin_memory().to(dev, non_blocking=True)
     else:
         t = t.to(dev, torch.int32)
+    iw = None
+    if smp is not None:
+        # the device draw under the same t_key (draw 0) replaces the host randint; an explicit t only gets its weights
+        t, iw = smp.draw(B, t_key, 0, t=t)
+    tr.last_iw = iw
     noise = gd.randn(x.shape, noise_key, 0) if noise is None else torch.as_tensor(noise).to(dev, torch.float32).contiguous()
     tr.last_t, tr.last_noise_key = t, noise_key
     if frame_mask is None and int(tr.frame_cond_max) > 0:
@@ -252,15 +270,22 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
         unet.act_bf16 = keep_storage
     fhw = x.numel() // (B * gd.channels)
     l2 = int(gd.loss_type == 'l2')
-    d_eps = None if gd.learned_variance else torch.empty_like(eps_hat)
+    d_eps = None if (gd.learned_variance or smp is not None) else torch.empty_like(eps_hat)
     if gd.learned_variance:
         # eps_hat | v: the hybrid loss and its gradient in one pass (vdx_hybrid_loss); the returned loss is the total, gd.last_loss_terms
         # keeps the device (mse, vb)
-        loss, d_eps = gd.hybrid_loss(x, noise, eps_hat, t, want_grad=True, _pre=(2.0, -1.0))
+        loss, d_eps = gd.hybrid_loss(x, noise, eps_hat, t, want_grad=True, _pre=(2.0, -1.0), iw=iw)
+        if smp is not None:
+            tr.last_loss_per_sample = gd.last_loss_per_sample[:, 0] + gd.vlb_weight * gd.last_loss_per_sample[:, 1]
     elif mk is not None:
         loss, acc = gd.masked_loss(eps_hat, noise, mk)                            # acc = device (sum, count | scratch)
         L.check(vdx_loss_grad_masked(L.ptr(eps_hat), L.ptr(noise), L.ptr(mk), acc.data_ptr() + 8, L.ptr(d_eps), B, gd.channels, fhw, l2,
                                      L.stream_ptr()))
+    elif smp is not None:
+        # the per-sample losses, the weighted mean (what is optimised) and the weighted gradient in one pass (vdx_loss_weighted)
+        out, d_eps = loss_weighted(eps_hat, noise, iw, l2=bool(l2), want_grad=True)
+        loss = out[B].to(torch.float32).reshape(())
+        tr.last_loss_per_sample = out[:B]
     else:
         acc = torch.zeros(1, dtype=torch.float64, device=dev)
         L.check(vdx_loss_sum(L.ptr(eps_hat), L.ptr(noise), L.ptr(acc), B, gd.channels, fhw, l2, L.stream_ptr()))
@@ -268,6 +293,7 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
         L.check(vdx_loss_grad(L.ptr(eps_hat), L.ptr(noise), L.ptr(d_eps), B, gd.channels, fhw, l2, L.stream_ptr()))
     if reducer is None:
         unet.backward(d_eps, grads)
+        _sampler_update(tr, t)
         return loss
     # reverse pass in groups of stages that end where a gradient bucket becomes complete: finished buckets are all-reduced (RCCL)
     # while earlier stages still run.  One call per group, not per stage: a call ends with the main stream waiting for the
@@ -286,7 +312,28 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
         hi = lo - 1
     if grads is not tr.grads:
         _accumulate_ready(tr, grads, nxt, -1)
+    _sampler_update(tr, t)
     return loss
+
+
+def _sampler_update(tr, t: torch.Tensor) -> None:
+    """Loss-aware timestep sampling: the (t_b, l_b) of the micro-batch enter the sampler's history, after the backward is enqueued.  On
+    more than one rank every rank applies the entries of all ranks, in (rank, sample) order, so that every rank holds the same history
+    (torch.distributed.all_gather of the [B][2] entries).  Launches only: the host reads nothing (RCCL; gloo stages device tensors through
+    the host, in the one-GPU tests)."""
+    smp = getattr(tr, 'sampler', None)
+    if smp is None:
+        return
+    entries = torch.stack([t.to(torch.float64), tr.last_loss_per_sample.to(torch.float64)], 1).contiguous()
+    if tr.dist_on and tr.world > 1:
+        if tr.comm_backend == 'abi':
+            raise ValueError("timestep_sampler=loss-second-moment needs comm_backend='torch' on more than one rank: the C communicator has "
+                             'no gather')
+        import torch.distributed as dist
+        parts = [torch.empty_like(entries) for _ in range(tr.world)]
+        dist.all_gather(parts, entries)
+        entries = torch.cat(parts, 0)
+    smp.update(entries)
 
 
 def _accumulate_ready(tr, micro: torch.Tensor, nxt: int, stage: int) -> int:

@@ -161,6 +161,15 @@ class Trainer:
     # attends to itself only, so the sample is trained as a bag of images (train_step.focus_present_draw under
     # train_step.focus_present_key).  train(prob_focus_present, focus_present_mask) override it for that run.
     prob_focus_present = 0.0
+    # Loss-aware timestep sampling (extension; Nichol & Dhariwal 2021, section 3.3; timestep_sampler.LossSecondMomentSampler).  'uniform':
+    # t is drawn uniformly on the host, the objective, kernels, launches and random streams of before.  'loss-second-moment': t is drawn
+    # on the device with p_t ~ sqrt(E[l_t^2]) over the last sampler_history losses seen at each level, mixed with sampler_uniform_prob of
+    # the uniform distribution, and every sample's loss is weighted by 1 / (T p_t); uniform with weights 1 until every level has a full
+    # history.  The state lives on the device (tr.sampler), is the same on every rank and is not checkpointed: a resumed run restarts it
+    # cold, as it restarts Adam's moments.  Class attributes for the same reason as the ones above.
+    timestep_sampler = 'uniform'
+    sampler_history = 10
+    sampler_uniform_prob = 0.001
 
     def __init__(self, diffusion_model, folder: str, *, rng_seed: int = 0, dataset_path: str, num_frames: int = 16,
                  train_batch_size: int = 4, train_lr: float = 1e-4, train_num_steps: int = 100000,
@@ -224,6 +233,23 @@ class Trainer:
             raise ValueError(f'null_cond_prob must be in [0, 1], got {self.null_cond_prob}')
         if not 0.0 <= float(self.prob_focus_present) <= 1.0:
             raise ValueError(f'prob_focus_present must be in [0, 1], got {self.prob_focus_present}')
+        from . import timestep_sampler as TS
+        if self.timestep_sampler not in TS.SAMPLERS:
+            raise ValueError(f'timestep_sampler must be one of {TS.SAMPLERS}, got {self.timestep_sampler!r}')
+        TS.validate(1, self.sampler_history, self.sampler_uniform_prob)
+        self.sampler = None                                      # the device-resident sampler ('loss-second-moment' only)
+        self.last_iw = None                                      # importance weights of the last micro-batch (device float64 [B])
+        self.last_loss_per_sample = None                         # unweighted per-sample losses of the last micro-batch (device float64 [B])
+        if self.timestep_sampler == 'loss-second-moment':
+            TS.validate(diffusion_model.num_timesteps, self.sampler_history, self.sampler_uniform_prob)
+            if int(self.frame_cond_max) > 0:
+                raise ValueError('timestep_sampler=loss-second-moment does not serve frame-conditioned training (frame_cond_max > 0): the '
+                                 'masked loss has no per-sample form')
+            if self.comm_backend == 'abi' and self.world > 1:
+                raise ValueError("timestep_sampler=loss-second-moment needs comm_backend='torch' on more than one rank: the C communicator "
+                                 'has no gather')
+            self.sampler = TS.LossSecondMomentSampler(diffusion_model.num_timesteps, self.sampler_history, self.sampler_uniform_prob,
+                                                      device=self.device)
         if self.cond_path is not None:
             from .datasets import CondPairs, load_cond_file
             self.ds = CondPairs(self.ds, load_cond_file(self.cond_path, len(self.ds), self.unet.cond_dim))
