@@ -6,7 +6,8 @@ curves (GaussianDiffusion.calc_bpd_loop; an extension, the reference has no eval
 --num-videos N, --batch-size B, --seed, --eval-steps S (S evenly spaced levels instead of all T: the per-level curves only, no total),
 --no-clip, --cond-path FILE.npy (float32 [N, cond_dim], row i the condition of video i), --output FILE.json.
 Writes one JSON document: total_bpd and prior_bpd (means over the videos; total_bpd is null with --eval-steps below T), the length-S
-arrays t, vb, mse and xstart_mse (means over the videos), num_videos, mode and seed.  One process: the evaluation is not sharded."""
+arrays t, vb, mse and xstart_mse (means over the videos), num_videos, mode and seed.  One process: the evaluation is not sharded.
+A config with diffusion.frame_noise_alpha > 0 (the mixed noise prior) is refused: the bound under a frame-correlated prior is a follow-up."""
 import argparse
 import json
 import logging
@@ -87,6 +88,9 @@ def main(argv=None):
         ap.error('--cond-path needs a config whose unet.use_bert_text_cond is true (a conditioned network)')
     unet, gd = sample.build_models(cfg, a.mode, a.timesteps, temporal_pos_bias=a.temporal_pos_bias,
                                    **(dict(focus_present=True) if a.focus_present else {}))
+    if gd.frame_noise_alpha:
+        ap.error('frame_noise_alpha does not support calc_bpd_loop yet (a follow-up; DESIGN.md 9): the bound of a model trained under the mixed '
+                 'noise prior needs the inverse frame covariance in its KL terms')
     if a.eval_steps is not None and a.eval_steps > gd.num_timesteps:
         ap.error(f'--eval-steps must be in [1, {gd.num_timesteps}], got {a.eval_steps}')
     if not a.random_init:

@@ -767,6 +767,38 @@ int vdx_hybrid_loss_w(const float* x, const float* noise, const float* out2, con
                       float pre_scale, float pre_shift, int l2, double vlb_weight, int want_grad, float* d_out, double* scratch, double* out,
                       int batch, int channels, long per_sample, const double* iw, void* stream);
 
+/* Mixed noise (EXTENSION, parity unpinned: no reference code.  Ge et al. 2023, "Preserve Your Own Correlation", section 3.2, the mixed
+ * noise model): a temporally correlated noise prior for video.  Off unless these entries are called.  Over a [batch,C,F,H,W] tensor
+ *   z[b,c,f,h,w] = a s[b,c,h,w] + b e[b,c,f,h,w],   s, e ~ N(0, 1),   a = alpha / sqrt(1 + alpha^2),  b = 1 / sqrt(1 + alpha^2)
+ * so each element is N(0, 1) and two frames of one clip correlate with rho = a^2 at the same pixel.  Draws: e is vdx_randn's element of
+ * the [batch,C,F,H,W] tensor at draw d; s is the stream at draw VDX_DRAW_SHARED + d, indexed as vdx_randn would index a [batch,C,H,W]
+ * tensor (flat index (b C + c) HW + hw, counter = index / 4, lane = index % 4).  d < 2^60: no draw of any entry above collides (0 .. T,
+ * VDX_DRAW_LOWRES, VDX_DRAW_KNOWN + s, VDX_DRAW_RENOISE + s).  The two products and the sum are rounded to fp32 one by one (no fused
+ * multiply-add), so z is a * S + b * E formed in fp32 from vdx_randn's two tensors, bit for bit.  Where HW % 4 == 0 one shared counter
+ * serves four consecutive elements; elsewhere a quad may straddle frames or channels and takes up to four: the values are the same.
+ *
+ * vdx_randn_mixed: out [batch,channels,frames,hw] = z at draw `draw` (+ *dev_draw when given).  Any sizes >= 1.
+ * vdx_p_sample_step_mixed: vdx_p_sample_step with z generated in the kernel at draw offset (+ *dev_offset): `frames, a, b` stand where
+ *   `noise` stands there.  One fused kernel; the bits of vdx_p_sample_step(noise = vdx_randn_mixed(...)).  per_sample % 4 == 0 and
+ *   % (channels * frames) == 0; x / out 16-byte aligned (they may alias).
+ * vdx_p_sample_loop_mixed: vdx_p_sample_loop_guided's arguments plus a, b: the ancestral loop with vdx_p_sample_step_mixed's kernel as
+ *   its step (draw 1 + k at step k; frames and H W are the handle's).  cond_scale == 1 or cfg_scratch NULL: the plain loop
+ *   (vdx_p_sample_loop_dyn's buffers: `batch` rows; rescale is not read), otherwise the guided one (2 batch rows, as
+ *   vdx_p_sample_loop_guided).  The dynamic threshold, the guidance combine and the advance are those loops'.  Two graph slots of its own
+ *   (plain, guided): no other loop's graph is evicted.  There is no masked and no super-resolution form.
+ * Refused before any launch (VDX_ERR_INVALID): a NULL tensor, a size < 1, a or b negative or not finite, |a^2 + b^2 - 1| > 1e-5, a draw
+ *   (offset) >= 2^60; for the loop also what vdx_p_sample_loop_dyn / _guided refuse. */
+#define VDX_DRAW_SHARED (1ull << 60)
+int vdx_randn_mixed(float* out, int batch, int channels, int frames, long hw, float a, float b, uint64_t seed, uint64_t draw,
+                    const uint64_t* dev_draw, void* stream);
+int vdx_p_sample_step_mixed(const float* x, const float* eps_hat, float* out, const int* t, const float* tables, int timesteps,
+                            int frames, float a, float b, uint64_t seed, uint64_t offset, const uint64_t* dev_offset, const float* thres,
+                            int clip_denoised, int batch, int channels, long per_sample, void* stream);
+int vdx_p_sample_loop_mixed(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                            uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                            int clip_denoised, float percentile, float* thres_buf, float cond_scale, float rescale, double* cfg_scratch,
+                            float a, float b, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */

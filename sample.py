@@ -10,7 +10,10 @@ Extensions: --mode {bf16,f16,f32}; --random-init (no checkpoint); --timesteps N 
 float32 [B, cond_dim] file are the batch; needs a config with use_bert_text_cond; works with --ddim-steps and --dpm-steps);
 --lowres-path FILE.npy [--lowres-aug-level s] (the second stage of a cascade: a config with diffusion.lowres_cond upsamples the
 [N,C,f,s,s] clips of the file; works with --ddim-steps and --dpm-steps); --save-npy (also write samples.npy, float32 [B,C,F,H,W] in
-[0,1], beside the gifs: what a second stage reads with --lowres-path)."""
+[0,1], beside the gifs: what a second stage reads with --lowres-path); --frame-noise-alpha A (or diffusion.frame_noise_alpha: A in the
+YAML, absent = 0: the mixed noise prior of "Preserve Your Own Correlation" -- x_T and the ancestral steps' noise share a component across
+the frames of a clip, correlation A^2 / (1 + A^2); for checkpoints trained with train.py --frame_noise_alpha A; works with --ddim-steps,
+--dpm-steps and --cond-path, not with --context, learned-variance or super-resolution configs)."""
 import argparse
 import logging
 import os
@@ -58,17 +61,23 @@ FLAGS = (   # (flag, kwargs)
                                                              'them (noise conditioning augmentation at sampling time; default: none)')),
     ('--save-npy', dict(action='store_true', help='also write samples.npy (float32 [B,C,F,H,W] in [0,1]) beside the gifs, for any sampler: '
                                                   'the input of a second stage (--lowres-path)')),
+    ('--frame-noise-alpha', dict(type=float, default=None, help='mixed noise prior: the noise of a clip\'s frames shares a component, correlation '
+                                                                'A^2 / (1 + A^2) (overrides diffusion.frame_noise_alpha in the YAML; 0 = i.i.d.; for '
+                                                                'checkpoints trained with it; not stored in checkpoints); not with --context')),
 )
 
 
-def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=False, focus_present=False):
+def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=False, focus_present=False, frame_noise_alpha=None):
     """temporal_pos_bias: the command-line flag; the YAML's unet.temporal_pos_bias (absent = false) switches it on as well.  An architecture
     argument like dim: checkpoints do not store it, so a model trained with it is sampled with it.  focus_present: the same for the
     focus-present switch (unet.focus_present in the YAML, absent = false).  diffusion.learned_variance (absent = false; optionally with
     diffusion.vlb_weight): the UNet gets out_dim = 2 * channels (eps | v) and the diffusion the learned-variance paths; checkpoints do not
     store the switch, the final conv's shape does (load_state_dict fails loudly on a mismatch).  diffusion.lowres_cond: {temporal: ft,
     spatial: fs, aug_max: L} (absent = off): a super-resolution stage -- the UNet gets channels = 2 * channels, out_dim = channels and
-    the diffusion lowres_cond=(ft, fs), lowres_aug_max=L (aug_max absent = 0); again the conv shapes are what a checkpoint stores."""
+    the diffusion lowres_cond=(ft, fs), lowres_aug_max=L (aug_max absent = 0); again the conv shapes are what a checkpoint stores.
+    diffusion.frame_noise_alpha: A (absent = 0 = off; the keyword, the command-line flag, overrides it): the mixed noise prior of
+    GaussianDiffusion(frame_noise_alpha=A) for training and sampling.  Checkpoints do not store it, and no shape depends on it: a model
+    trained with it is sampled with the same A."""
     from video_diffusion_nnx_amd.gaussian_diffusion import GaussianDiffusion
     from video_diffusion_nnx_amd.unet3d import Rngs, Unet3D
     u, d = cfg['unet'], cfg['diffusion']
@@ -76,13 +85,15 @@ def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=Fa
     lv_kw = dict(learned_variance=True, vlb_weight=d.get('vlb_weight')) if lv else {}
     sr = d.get('lowres_cond')
     sr_kw = dict(lowres_cond=(sr['temporal'], sr['spatial']), lowres_aug_max=sr.get('aug_max', 0)) if sr else {}
+    fa = d.get('frame_noise_alpha', 0) if frame_noise_alpha is None else frame_noise_alpha
+    fa_kw = dict(frame_noise_alpha=fa) if (fa or isinstance(fa, bool)) else {}       # (0 takes the constructor's default: nothing new is passed)
     unet = Unet3D(**(dict(out_dim=2 * u['channels']) if lv else dict(out_dim=u['channels']) if sr else {}), dim=u['dim'], rngs=Rngs(u['rngs_seed']),
                   dim_mults=tuple(u['dim_mults']), channels=(2 if sr else 1) * u['channels'],
                   use_bert_text_cond=u['use_bert_text_cond'], mode=mode, attn_fp8=attn_fp8,
                   temporal_pos_bias=bool(temporal_pos_bias or u.get('temporal_pos_bias', False)),
                   focus_present=bool(focus_present or u.get('focus_present', False)))
     gd = GaussianDiffusion(denoise_fn=unet, image_size=d['image_size'], num_frames=d['num_frames'], channels=d['channels'],
-                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'], **lv_kw, **sr_kw)
+                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'], **lv_kw, **sr_kw, **fa_kw)
     return unet, gd
 
 
@@ -145,6 +156,11 @@ def main(argv=None):
         ap.error('--lowres-aug-level needs --lowres-path')
     if not 0.0 <= a.guidance_rescale <= 1.0:
         ap.error(f'--guidance-rescale must be in [0, 1], got {a.guidance_rescale}')
+    if a.frame_noise_alpha is not None and not (0.0 <= a.frame_noise_alpha < float('inf')):
+        ap.error(f'--frame-noise-alpha must be a finite number >= 0, got {a.frame_noise_alpha}')
+    if a.frame_noise_alpha and a.context:
+        ap.error('--frame-noise-alpha samples from noise: not together with --context (frame-conditioned sampling under the mixed prior is a '
+                 'follow-up)')
     if a.clean_context and not a.context:
         ap.error('--clean-context needs --context')
     if a.clean_context and a.resample_steps > 1:
@@ -187,8 +203,17 @@ def _run(a, ap, rank, world):
         ap.error('--attn-fp8 and --focus-present exclude each other')
     if a.focus_present and a.context:
         ap.error('--focus-present samples from noise: not together with --context')
-    unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8, temporal_pos_bias=a.temporal_pos_bias,
-                            **(dict(focus_present=True) if a.focus_present else {}))
+    try:
+        unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8, temporal_pos_bias=a.temporal_pos_bias,
+                                **(dict(focus_present=True) if a.focus_present else {}),
+                                **(dict(frame_noise_alpha=a.frame_noise_alpha) if a.frame_noise_alpha is not None else {}))
+    except ValueError as e:
+        if 'frame_noise_alpha' not in str(e):
+            raise
+        ap.error(str(e))
+    if gd.frame_noise_alpha and a.context:
+        ap.error('diffusion.frame_noise_alpha samples from noise: not together with --context (frame-conditioned sampling under the mixed '
+                 'prior is a follow-up)')
     fp_kw = dict(focus_present=True) if a.focus_present else {}
     if a.steps is not None:
         if not gd.learned_variance:

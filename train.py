@@ -21,7 +21,10 @@ such a model with sample.py --lowres-path; not with --frame_cond_max or --focus_
 sampler_history / sampler_uniform_prob in the YAML; absent = uniform: Improved DDPM's loss-aware sampler -- t is drawn on the device with
 probability ~ the root of the second moment of the last H losses seen at each level, mixed with P of the uniform distribution, and each
 sample's loss is weighted by 1 / (T p_t); uniform until every level has H losses; the state is not checkpointed, a resumed run restarts it
-cold; not with --frame_cond_max)."""
+cold; not with --frame_cond_max);
+--frame_noise_alpha A (or diffusion.frame_noise_alpha: A in the YAML, absent = 0: train under the mixed noise prior of "Preserve Your Own
+Correlation" -- the noise of a clip's frames shares a component, correlation A^2 / (1 + A^2); nothing else in the step changes; not stored
+in checkpoints: sample with sample.py --frame-noise-alpha A or the same YAML key; not with learned-variance or super-resolution configs)."""
 import argparse
 import logging
 import os
@@ -54,6 +57,9 @@ FLAGS = (
                                      'history with importance weights (also trainer.timestep_sampler in the YAML)')),
     ('--sampler_history', dict(type=int, default=None, help='with loss-second-moment: losses kept per level, 1..32 (10)')),
     ('--sampler_uniform_prob', dict(type=float, default=None, help='with loss-second-moment: share of the uniform distribution, (0, 1] (0.001)')),
+    ('--frame_noise_alpha', dict(type=float, default=None, help='mixed noise prior: the training noise of a clip\'s frames shares a component, '
+                                                                'correlation A^2 / (1 + A^2) (overrides diffusion.frame_noise_alpha in the YAML; '
+                                                                '0 = i.i.d.; not stored in checkpoints)')),
 )
 
 
@@ -81,8 +87,11 @@ def main(argv=None):
     seed = a.rng_seed if a.rng_seed is not None else cfg.get('rng_seed', 0)
     logging.info('config %s, master seed %s', a.config, seed)
     # (the keyword only when the flag is given: callers that replace build_models with a (cfg, mode) function keep working)
+    if a.frame_noise_alpha is not None and not (0.0 <= a.frame_noise_alpha < float('inf')):
+        ap.error(f'--frame_noise_alpha must be a finite number >= 0, got {a.frame_noise_alpha}')
     _, gd = build_models(cfg, a.mode, **(dict(temporal_pos_bias=True) if a.temporal_pos_bias else {}),
-                         **(dict(focus_present=True) if a.focus_present else {}))
+                         **(dict(focus_present=True) if a.focus_present else {}),
+                         **(dict(frame_noise_alpha=a.frame_noise_alpha) if a.frame_noise_alpha is not None else {}))
     tc = dict(cfg['trainer'])
     p_fp = tc.pop('prob_focus_present', None)        # (a Trainer attribute, not a constructor argument)
     if a.prob_focus_present is not None:

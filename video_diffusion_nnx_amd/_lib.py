@@ -158,3 +158,12 @@ vdx_ddim_sample_loop_sr = _sig('vdx_ddim_sample_loop_sr', c_int, [c_void_p] * 10
                                                                   c_size_t, c_int, c_int, c_void_p])
 vdx_dpm_sample_loop_sr = _sig('vdx_dpm_sample_loop_sr', c_int, [c_void_p] * 11 + [c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p,
                                                                 c_size_t, c_int, c_int, c_void_p])
+
+# mixed noise (vdx.h: "Mixed noise"): the generator, the ancestral step that draws it in the kernel, and the loop over that step
+# (vdx_p_sample_loop_guided's arguments with a, b after the cfg scratch)
+DRAW_SHARED = 1 << 60                            # VDX_DRAW_SHARED: the shared component of draw d is draw DRAW_SHARED + d
+vdx_randn_mixed = _sig('vdx_randn_mixed', c_int, [c_void_p, c_int, c_int, c_int, c_long, c_float, c_float, _u64, _u64, c_void_p, c_void_p])
+vdx_p_sample_step_mixed = _sig('vdx_p_sample_step_mixed', c_int, [c_void_p] * 5 + [c_int, c_int, c_float, c_float, _u64, _u64, c_void_p, c_void_p, c_int, c_int,
+                                                                  c_int, c_long, c_void_p])
+vdx_p_sample_loop_mixed = _sig('vdx_p_sample_loop_mixed', c_int, [c_void_p] * 8 + [c_int, c_int, c_void_p, _u64, c_int, c_float, c_void_p, c_float, c_float,
+                                                                  c_void_p, c_float, c_float, c_void_p, c_size_t, c_int, c_int, c_void_p])

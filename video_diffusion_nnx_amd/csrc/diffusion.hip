@@ -15,6 +15,7 @@
 #include "vdx_internal.h"
 #include "model.h"
 #include "vdx_philox.h"
+#include "vdx_pstep.h"
 
 namespace vdx {
 
@@ -77,25 +78,7 @@ __global__ __launch_bounds__(256) void q_sample_masked_kernel(const float* __res
     }
 }
 
-// the per-element arithmetic of one ancestral reverse step, shared by p_sample_kernel and p_sample_masked_kernel
-struct PStepCoef { float k_recip, k_recipm1, c1, c2, sigma, s; int clip; };
-
-__device__ __forceinline__ PStepCoef p_step_coef(const PSampleArgs& P, int b, int tb) {
-    PStepCoef k;
-    k.k_recip = P.tables[tb]; k.k_recipm1 = P.tables[P.T + tb];
-    k.c1 = P.tables[2 * P.T + tb]; k.c2 = P.tables[3 * P.T + tb];
-    k.sigma = (tb == 0) ? 0.f : expf(0.5f * P.tables[4 * P.T + tb]);
-    k.s = P.thres ? P.thres[b] : 1.0f;
-    k.clip = P.clip;
-    return k;
-}
-
-__device__ __forceinline__ float p_step_elem(const PStepCoef& k, float x, float eps, float z) {
-    float x0 = k.k_recip * x - k.k_recipm1 * eps;                      // predict_start_from_noise  (:133-136)
-    if (k.clip) x0 = fminf(fmaxf(x0, -k.s), k.s) / k.s;                 // :220
-    const float mean = k.c1 * x0 + k.c2 * x;                           // q_posterior (:153-156)
-    return mean + k.sigma * z;                                         // :261
-}
+// (the per-element arithmetic of one ancestral reverse step, p_step_coef / p_step_elem: vdx_pstep.h)
 
 // one reverse step.  tables: [5][T] = sqrt_recip_ac | sqrt_recipm1_ac | post_mean_coef1 | post_mean_coef2 | post_logvar_clipped
 __global__ __launch_bounds__(256) void p_sample_kernel(PSampleArgs P) {
@@ -1030,8 +1013,6 @@ __global__ void affine_kernel(const float* __restrict__ x, float* __restrict__ y
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------
-
-static int ew_blocks(long work_items) { return (int)std::max<long>(1, std::min<long>((work_items + 255) / 256, 2048)); }
 
 hipError_t launch_randn(float* out, long n, unsigned long long seed, unsigned long long offset, const unsigned long long* dev_offset, hipStream_t st) {
     hipLaunchKernelGGL(randn_kernel, dim3(ew_blocks((n + 3) / 4)), dim3(256), 0, st, out, n, seed, offset, dev_offset);

@@ -6,9 +6,9 @@
 #include "model.h"
 #include "comm.h"
 
-// Everything a sampling step can bake into its captured graph: what the fourteen vdx_*_sample_loop* entry points (the eleven over a
-// network with out_dim == channels and the three super-resolution ones, vdx_*_sample_loop_sr) fill in and sample_loop() runs.  A field
-// the entry does not have stays zero.
+// Everything a sampling step can bake into its captured graph: what the fifteen vdx_*_sample_loop* entry points (the eleven over a
+// network with out_dim == channels, the three super-resolution ones, vdx_*_sample_loop_sr, and the mixed-noise ancestral one,
+// vdx_p_sample_loop_mixed) fill in and sample_loop() runs.  A field the entry does not have stays zero.
 // (CHAIN_VLB tags the graph key of vdx_vlb_loop only: it never goes through sample_loop, whose slot arithmetic 3 * variant + chain takes 0..2)
 // (CHAIN_LV / CHAIN_VLB_LV: the learned-variance loops, vdx_p_sample_loop_lv / vdx_vlb_loop_lv, likewise outside sample_loop)
 enum { CHAIN_ANCESTRAL = 0, CHAIN_DDIM = 1, CHAIN_DPM = 2, CHAIN_VLB = 3, CHAIN_LV = 4, CHAIN_VLB_LV = 5 };
@@ -23,6 +23,7 @@ struct LoopArgs {
     float percentile; float* thres_buf;                 // dynamic threshold: percentile > 0 && clip_denoised
     const float* known; const unsigned char* mask; const float* mask_tables; int resample_steps;
     float cond_scale, rescale; double* cfg_scratch;
+    float mix_a, mix_b;                                 // vdx_p_sample_loop_mixed alone: the step is p_sample_mixed_kernel; (0, 0) everywhere else
     float post_scale, post_shift;                       // the learned-variance sampling loop (vdx_p_sample_loop_lv) alone
     const float* vlb_x; const double* vlb_tables; double* vlb_partial; double* vlb_out;     // the evaluation loop (vdx_vlb_loop) alone
     void* workspace; size_t workspace_bytes; int batch;
@@ -36,7 +37,8 @@ struct vdx_handle {
     struct GraphKey { LoopArgs a; const void* stream; int act16; };
     // one cached graph per (chain, variant): slot = 3 * variant + chain with variant 0 = plain, 1 = masked, 2 = guided and chain 0 = the
     // ancestral loop, 1 = DDIM, 2 = DPM-Solver++; slot 9 = the evaluation loop (vdx_vlb_loop), 10 / 11 = the learned-variance sampling and
-    // evaluation loops, 12 + chain = the super-resolution loops (vdx_*_sample_loop_sr) -- no loop ever evicts another one's graph
+    // evaluation loops, 12 + chain = the super-resolution loops (vdx_*_sample_loop_sr), 15 / 16 = the plain and the guided mixed-noise
+    // ancestral loop (vdx_p_sample_loop_mixed) -- no loop ever evicts another one's graph
     // `last` = the stream the exec was last launched on: replays may still be running when the graph has to go
     struct GraphSlot {
         hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; GraphKey key; hipStream_t last = nullptr;
@@ -46,7 +48,7 @@ struct vdx_handle {
             if (graph) { (void)hipGraphDestroy(graph); graph = nullptr; }
             last = nullptr;
         }
-    } gs[15];
+    } gs[17];
     void drop_graphs() { for (GraphSlot& g : gs) g.drop(); }
     vdx::BwdState bwd;
     vdx::Comm comm;
@@ -699,6 +701,46 @@ int vdx_p_sample_step(const float* x, const float* eps_hat, float* out, const in
     return VDX_OK;
 }
 
+// a >= 0, b >= 0, both finite, a^2 + b^2 = 1 within 1e-5, by the bits of the floats (the library is built with -fno-honor-nans, under
+// which a comparison may let a NaN through): the weights of the mixed noise
+static bool mix_weights_ok(float a, float b) {
+    unsigned ua, ub;
+    memcpy(&ua, &a, sizeof(ua));
+    memcpy(&ub, &b, sizeof(ub));
+    if ((ua >= 0x7F800000u && ua != 0x80000000u) || (ub >= 0x7F800000u && ub != 0x80000000u)) return false;      // negative, inf or NaN
+    const double d = (double)a * (double)a + (double)b * (double)b - 1.0;
+    return d >= -1e-5 && d <= 1e-5;
+}
+#define VDX_MIX_WEIGHTS_RULE "a and b must be finite, >= 0 and a^2 + b^2 = 1 (within 1e-5)"
+
+int vdx_randn_mixed(float* out, int batch, int channels, int frames, long hw, float a, float b, uint64_t seed, uint64_t draw,
+                    const uint64_t* dev_draw, void* stream) {
+    if (!out) VDX_FAIL(VDX_ERR_INVALID, "randn_mixed: null out");
+    if (batch < 1 || channels < 1 || frames < 1 || hw < 1) VDX_FAIL(VDX_ERR_INVALID, "randn_mixed: batch, channels, frames and hw must be >= 1");
+    if (!mix_weights_ok(a, b)) VDX_FAIL(VDX_ERR_INVALID, "randn_mixed: " VDX_MIX_WEIGHTS_RULE);
+    if (draw >= VDX_DRAW_SHARED) VDX_FAIL(VDX_ERR_INVALID, "randn_mixed: draw must be below 2^60 (VDX_DRAW_SHARED)");
+    if ((uintptr_t)out % 16) VDX_FAIL(VDX_ERR_INVALID, "randn_mixed: out must be 16-byte aligned");
+    const vdx::MixArgs m = {frames, hw, a, b};
+    VDX_HIP(vdx::launch_randn_mixed(out, batch, channels, m, seed, draw, reinterpret_cast<const unsigned long long*>(dev_draw), (hipStream_t)stream));
+    return VDX_OK;
+}
+
+int vdx_p_sample_step_mixed(const float* x, const float* eps_hat, float* out, const int* t, const float* tables, int timesteps,
+                            int frames, float a, float b, uint64_t seed, uint64_t offset, const uint64_t* dev_offset, const float* thres,
+                            int clip_denoised, int batch, int channels, long per_sample, void* stream) {
+    if (!x || !eps_hat || !out || !t || !tables || timesteps < 1 || batch < 1 || channels < 1 || frames < 1 || per_sample < 1)
+        VDX_FAIL(VDX_ERR_INVALID, "p_sample_mixed: bad argument");
+    if (per_sample % ((long)channels * frames)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_mixed: per_sample must be a multiple of channels * frames");
+    if (per_sample % 4) VDX_FAIL(VDX_ERR_INVALID, "p_sample_mixed: generated noise needs per_sample % 4 == 0");
+    if (!mix_weights_ok(a, b)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_mixed: " VDX_MIX_WEIGHTS_RULE);
+    if (offset >= VDX_DRAW_SHARED) VDX_FAIL(VDX_ERR_INVALID, "p_sample_mixed: offset must be below 2^60 (VDX_DRAW_SHARED)");
+    if ((uintptr_t)x % 16 || (uintptr_t)out % 16) VDX_FAIL(VDX_ERR_INVALID, "p_sample_mixed: x / out must be 16-byte aligned");
+    const vdx::PSampleArgs pa = psample_args(x, eps_hat, out, t, tables, timesteps, nullptr, seed, offset, dev_offset, thres, clip_denoised, channels, per_sample);
+    const vdx::MixArgs m = {frames, per_sample / ((long)channels * frames), a, b};
+    VDX_HIP(vdx::launch_p_sample_mixed(pa, m, batch, (hipStream_t)stream));
+    return VDX_OK;
+}
+
 int vdx_loss_sum(const float* eps_hat, const float* noise, double* acc, int batch, int channels, long fhw, int l2, void* stream) {
     if (!eps_hat || !noise || !acc) VDX_FAIL(VDX_ERR_INVALID, "loss: null tensor");
     VDX_HIP(vdx::launch_loss(eps_hat, noise, acc, batch, channels, fhw, l2, (hipStream_t)stream));
@@ -815,7 +857,7 @@ int vdx_cfg_combine(const float* eps2, float* out, float cond_scale, float resca
     return VDX_OK;
 }
 
-// ---- the sampling loops: one step builder, fourteen positional entry points ----
+// ---- the sampling loops: one step builder, fifteen positional entry points ----
 
 // 0 <= x <= 1 by the bits of x (non-negative floats order like unsigned integers): the library is built with -fno-honor-nans, under
 // which a comparison may let a NaN through, and a NaN rescale has to be refused
@@ -827,13 +869,15 @@ static bool in_unit_interval(float x) {
 
 // The step of every loop, launch for launch: (guided: copy img[:B] -> img[B:]) -> (super-resolution, a.xin: lowres_pack img -> the
 // first half of xin, the forward then reads xin) -> model_forward over B samples (guided: 2B, the second half with the null embedding) -> (guided: cfg_combine) -> (dynamic threshold) -> the chain's step kernel on B samples -> the chain's
-// advance (guided: over 2B).  Validates, derives the graph key from `a` and runs nsteps steps eagerly or as replays of one captured step.
+// advance (guided: over 2B).  Mixed noise (a.mix_a / a.mix_b, the ancestral chain only): p_sample_mixed_kernel is that step kernel.
+// Validates, derives the graph key from `a` and runs nsteps steps eagerly or as replays of one captured step.
 // Guided loops (classifier-free guidance; EXTENSION, parity unpinned: the reference's p_sample_loop drops cond): img / t_dev / eps_buf /
 // workspace hold 2 * batch samples; the step kernels, the threshold and the result use the first `batch`.
 static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int nsteps, int use_graph, void* stream) {
     char msg[160];
 #define LOOP_FAIL(code, text) do { snprintf(msg, sizeof(msg), "%s: %s", who, text); VDX_FAIL(code, msg); } while (0)
     const bool anc = a.chain == CHAIN_ANCESTRAL, dpm = a.chain == CHAIN_DPM, masked = a.masked != 0, guided = a.guided != 0;
+    const bool mixed = a.mix_a != 0.f || a.mix_b != 0.f;                  // (the entry has checked the pair: a^2 + b^2 = 1)
     if (!h || !a.params || !a.packed || !a.img || !a.eps_buf || !a.t_dev || !a.step_dev || !a.workspace) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
     if (anc ? !a.tables : (!a.alphas_cumprod || !a.seq)) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
     if (masked && (!a.known || !a.mask || !a.mask_tables)) LOOP_FAIL(VDX_ERR_INVALID, "null argument");
@@ -863,6 +907,7 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
     if (!sr && m.out_dim != m.cfg.channels) LOOP_FAIL(VDX_ERR_INVALID, "out_dim must equal channels");
     if (sr && ((uintptr_t)a.img % 16 || (uintptr_t)a.xin % 16)) LOOP_FAIL(VDX_ERR_INVALID, "img / xin must be 16-byte aligned");
     if (masked && !masked_aligned(a.img, a.known, a.img, a.mask)) LOOP_FAIL(VDX_ERR_INVALID, "img / known must be 16-byte and mask 4-byte aligned");
+    if (mixed && (uintptr_t)a.img % 16) LOOP_FAIL(VDX_ERR_INVALID, "img must be 16-byte aligned");
     if (dpm && ((uintptr_t)a.img % 16 || (uintptr_t)a.hist % 16)) LOOP_FAIL(VDX_ERR_INVALID, "img / hist must be 16-byte aligned");
     if (guided && ((uintptr_t)a.img % 16 || (uintptr_t)a.eps_buf % 16 || (uintptr_t)a.hist % 16 || (uintptr_t)a.cfg_scratch % 8))
         LOOP_FAIL(VDX_ERR_INVALID, "img / eps_buf / hist must be 16-byte and the cfg scratch 8-byte aligned");
@@ -874,6 +919,7 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
     const unsigned char* cond_mask = guided ? vdx::cfg_scratch_mask(a.cfg_scratch, B) : nullptr;
     // (ancestral: one Philox draw per step through step_dev, resampling or not; the sequence chains draw for the known region only)
     const vdx::MaskArgs ma = {a.known, a.mask, a.mask_tables, anc ? a.resample_steps : 1, 0ull, anc ? sd : nullptr};
+    const vdx::MixArgs mx = {m.cfg.num_frames, (long)m.cfg.image_size * m.cfg.image_size, a.mix_a, a.mix_b};
     if (guided) VDX_HIP(vdx::launch_cfg_mask(a.cfg_scratch, B, st));
     auto step = [&]() -> int {
         hipError_t e = hipSuccess;
@@ -890,7 +936,8 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
         if (anc) {
             const vdx::PSampleArgs pa = psample_args(a.img, a.eps_buf, a.img, a.t_dev, a.tables, a.timesteps, nullptr, a.seed, masked ? 0 : 1,
                                                      masked ? nullptr : a.step_dev, th, a.clip_denoised, C, per_sample);
-            if (e == hipSuccess) e = masked ? vdx::launch_p_sample_masked(pa, ma, B, st) : vdx::launch_p_sample(pa, B, st);
+            if (e == hipSuccess)
+                e = masked ? vdx::launch_p_sample_masked(pa, ma, B, st) : mixed ? vdx::launch_p_sample_mixed(pa, mx, B, st) : vdx::launch_p_sample(pa, B, st);
             if (e == hipSuccess) e = masked ? vdx::launch_resample_advance(a.t_dev, B, sd, a.resample_steps, st) : vdx::launch_advance(a.t_dev, rows, sd, st);
         } else {
             if (e == hipSuccess && dpm)
@@ -919,10 +966,11 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
     if (!masked) { k.known = nullptr; k.mask = nullptr; k.mask_tables = nullptr; }
     if (!masked || !anc) k.resample_steps = 0;
     if (!guided) { k.cond_scale = 0.f; k.rescale = 0.f; k.cfg_scratch = nullptr; }
-    return run_steps(h, sr ? 12 + a.chain : 3 * (guided ? 2 : masked ? 1 : 0) + a.chain, key, nsteps, use_graph, st, step);
+    const int slot = mixed ? 15 + (guided ? 1 : 0) : sr ? 12 + a.chain : 3 * (guided ? 2 : masked ? 1 : 0) + a.chain;
+    return run_steps(h, slot, key, nsteps, use_graph, st, step);
 }
 
-// what all fourteen entries share; the rest of `a` is zero (and so is its padding: the bytes of a LoopArgs are a graph key)
+// what all fifteen entries share; the rest of `a` is zero (and so is its padding: the bytes of a LoopArgs are a graph key)
 static void loop_args(LoopArgs& a, int chain, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev, uint64_t* step_dev,
                       const float* cond, int clip_denoised, float percentile, float* thres_buf, void* workspace, size_t workspace_bytes, int batch) {
     memset(&a, 0, sizeof(a));
@@ -978,6 +1026,19 @@ int vdx_p_sample_loop_guided(vdx_handle* h, const float* params, const void* pac
     a.tables = tables; a.timesteps = timesteps; a.seed = seed;
     set_guided(a, cond_scale, rescale, cfg_scratch);
     return sample_loop("p_sample_loop_guided", h, a, nsteps, use_graph, stream);
+}
+
+int vdx_p_sample_loop_mixed(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,
+                            uint64_t* step_dev, const float* tables, int timesteps, int nsteps, const float* cond, uint64_t seed,
+                            int clip_denoised, float percentile, float* thres_buf, float cond_scale, float rescale, double* cfg_scratch,
+                            float a, float b, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream) {
+    if (!mix_weights_ok(a, b)) VDX_FAIL(VDX_ERR_INVALID, "p_sample_loop_mixed: " VDX_MIX_WEIGHTS_RULE);
+    LoopArgs la;
+    loop_args(la, CHAIN_ANCESTRAL, params, packed, img, eps_buf, t_dev, step_dev, cond, clip_denoised, percentile, thres_buf, workspace, workspace_bytes, batch);
+    la.tables = tables; la.timesteps = timesteps; la.seed = seed;
+    la.mix_a = a; la.mix_b = b;
+    if (cond_scale != 1.f && cfg_scratch) set_guided(la, cond_scale, rescale, cfg_scratch);
+    return sample_loop("p_sample_loop_mixed", h, la, nsteps, use_graph, stream);
 }
 
 int vdx_ddim_sample_loop_dyn(vdx_handle* h, const float* params, const void* packed, float* img, float* eps_buf, int* t_dev,

@@ -193,6 +193,10 @@ hipError_t launch_sla_heads(SlaArgs a, void* O, hipStream_t st);
 
 hipError_t sla_block_forward(int mode, SlaArgs a, int Fr, int H, int W, void* scratch, size_t scratch_bytes, int require, hipStream_t st);
 
+// grid of the elementwise kernels of diffusion.hip / mixnoise.hip: one 256-thread workgroup per 256 work items, at most 2048 (the
+// kernels stride over the rest)
+inline int ew_blocks(long work_items) { return (int)std::max<long>(1, std::min<long>((work_items + 255) / 256, 2048)); }
+
 struct PSampleArgs {
     const float* x; const float* eps; float* out;       // x/out [B,C,F,H,W] (may alias); eps channel-last [B,F,H,W,C]
     const int* t; const float* tables; int T;           // device t[B]; tables [5][T]
@@ -207,6 +211,12 @@ hipError_t launch_q_sample(const float* x0, const int* t, const float* noise, fl
                            int B, long per_sample, float pre_scale, float pre_shift, hipStream_t st);
 hipError_t launch_p_sample(const PSampleArgs& a, int B, hipStream_t st);
 hipError_t launch_advance(int* t, int B, unsigned long long* dev_offset, hipStream_t st);
+// Temporally correlated noise (vdx.h: "Mixed noise"; mixnoise.hip): z = a s + b e over [B,C,F,H,W], s shared by the F frames of a (b, c)
+struct MixArgs { int F; long hw; float a, b; };         // frames, H * W, the two weights
+hipError_t launch_randn_mixed(float* out, int B, int C, const MixArgs& m, unsigned long long seed, unsigned long long draw,
+                              const unsigned long long* dev_draw, hipStream_t st);
+// launch_p_sample with z generated in the kernel: P.noise is not read, the draw is P.offset + *P.dev_offset; per_sample % 4 == 0
+hipError_t launch_p_sample_mixed(const PSampleArgs& a, const MixArgs& m, int B, hipStream_t st);
 struct MaskArgs {                                        // the known region of a masked (inpainting) reverse step
     const float* known; const unsigned char* mask;       // k = 2 video - 1 and the element mask (1 = known), both [B,C,F,H,W]
     const float* mtab;                                   // [4][T] = sqrt_ac | sqrt_1mac | sqrt(alpha) | sqrt(beta)

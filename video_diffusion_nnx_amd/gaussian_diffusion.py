@@ -302,15 +302,52 @@ def check_lowres_cond(lowres_cond, num_frames: int, image_size: int):
     return int(ft), int(fs)
 
 
+def check_frame_noise_alpha(alpha) -> float:
+    """PYoCo's mixed-noise parameter as a float: a finite number >= 0 (0 = i.i.d. noise); anything else (a bool included) raises
+    ValueError."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float, np.integer, np.floating)):
+        raise ValueError(f'frame_noise_alpha must be a finite number >= 0, got {alpha!r}')
+    al = float(alpha)
+    if not (al >= 0.0 and al != float('inf')):
+        raise ValueError(f'frame_noise_alpha must be a finite number >= 0, got {alpha!r}')
+    return al
+
+
+def mixed_noise_coef(alpha):
+    """(a, b) = (alpha, 1) / sqrt(1 + alpha^2) of the mixed noise z = a s + b e (Ge et al. 2023, sec. 3.2), formed in double and rounded
+    once to fp32 (returned as Python floats holding the fp32 values: what the kernels receive)."""
+    al = check_frame_noise_alpha(alpha)
+    h = float(np.hypot(1.0, al))
+    return float(np.float32(al / h)), float(np.float32(1.0 / h))
+
+
 class GaussianDiffusion:
     # super-resolution switches (instance attributes only on a super-resolution diffusion: a plain one keeps the attributes it had)
     lowres_cond = None
     lowres_aug_max = 0
+    # mixed-noise switch (instance attributes only when it is on, likewise)
+    frame_noise_alpha = 0.0
 
     def __init__(self, denoise_fn: Unet3D, *, image_size: int, num_frames: int, text_use_bert_cls: bool = False,
                  channels: int = 3, timesteps: int = 1000, loss_type: str = 'l1', use_dynamic_thres: bool = False,
                  dynamic_thres_percentile: float = 0.9, sample_act_bf16: bool = True, learned_variance: bool = False,
-                 vlb_weight: Optional[float] = None, lowres_cond=None, lowres_aug_max: int = 0):
+                 vlb_weight: Optional[float] = None, lowres_cond=None, lowres_aug_max: int = 0, frame_noise_alpha: float = 0.0):
+        # frame_noise_alpha = alpha (extension, off by default; Ge et al. 2023, "Preserve Your Own Correlation", sec. 3.2, the mixed noise
+        # model): every noise tensor drawn by key -- q_sample's eps, x_T, the z of the ancestral steps -- is z = a s + b e with s shared by
+        # the frames of a clip, a = alpha / sqrt(1 + alpha^2), b = 1 / sqrt(1 + alpha^2): still N(0, 1) per element, two frames correlate
+        # with frame_noise_corr = a^2 at the same pixel.  The model is trained and sampled under that prior (noise(); vdx.h: "Mixed
+        # noise").  Like the other switches it is not stored in checkpoints: sample a model with the alpha it was trained with.  0: no new
+        # state, no new path.
+        alpha = check_frame_noise_alpha(frame_noise_alpha)
+        if alpha > 0:
+            if learned_variance:
+                raise ValueError('frame_noise_alpha does not support learned_variance yet (a follow-up; DESIGN.md 9): the KL of the hybrid loss '
+                                 'needs the inverse frame covariance')
+            if lowres_cond is not None:
+                raise ValueError('frame_noise_alpha does not support lowres_cond yet (a follow-up; DESIGN.md 9): the super-resolution loops have '
+                                 'no mixed-noise entry')
+            self.frame_noise_alpha = alpha
+            self._mix = mixed_noise_coef(alpha)
         # lowres_cond = (ft, fs) (extension, off by default; Ho et al. 2021, "Cascaded Diffusion Models"): the second stage of a cascade.
         # The denoiser has channels = 2 * channels and out_dim = channels; its input is [ x_t | u ], u = the low-resolution clip
         # [B,C,F/ft,S/fs,S/fs] normalised, upsampled linearly and, in training, noised to a level drawn from {0..lowres_aug_max-1}
@@ -400,6 +437,36 @@ class GaussianDiffusion:
         out = torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
         L.check(vdx_randn(L.ptr(out), out.numel(), int(key) & 0xFFFFFFFFFFFFFFFF, offset, 0, L.stream_ptr()))
         return out
+
+    @property
+    def frame_noise_corr(self) -> float:
+        """rho = alpha^2 / (1 + alpha^2): the correlation of two frames of one clip's noise at the same pixel (0 = i.i.d.)."""
+        al = self.frame_noise_alpha
+        return al * al / (1.0 + al * al) if al < 1e150 else 1.0
+
+    def noise(self, shape, key: int, draw: int = 0, *, out=None) -> torch.Tensor:
+        """The noise tensor of `shape` = [B,C,F,H,W] at draw `draw` of stream `key` under the diffusion's prior: randn with
+        frame_noise_alpha = 0 (the same launch), else the mixed noise a s + b e (vdx_randn_mixed: e = randn's tensor, s = the stream's draw
+        VDX_DRAW_SHARED + draw over [B,C,H,W]).  Everything that draws noise by key goes through here.  out: a contiguous float32 device
+        tensor whose first prod(shape) elements receive it (the guided chains' 2B-row buffer)."""
+        shape = tuple(int(n) for n in shape)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        n = int(np.prod(shape))
+        seed = int(key) & 0xFFFFFFFFFFFFFFFF
+        if not self.frame_noise_alpha:
+            L.check(vdx_randn(L.ptr(out), n, seed, draw, 0, L.stream_ptr()))
+            return out
+        if len(shape) != 5:
+            raise ValueError(f'frame_noise_alpha: the mixed noise is defined over [B, C, F, H, W], got shape {shape}')
+        B, C, Fr, H, W = shape
+        L.check(L.vdx_randn_mixed(L.ptr(out), B, C, Fr, H * W, self._mix[0], self._mix[1], seed, draw, 0, L.stream_ptr()))
+        return out
+
+    def _mix_refuse(self, what):
+        """ValueError for what the mixed-noise prior does not serve yet (follow-ups)."""
+        if self.frame_noise_alpha:
+            raise ValueError(f'frame_noise_alpha does not support {what} yet (a follow-up; DESIGN.md 9)')
 
     def _dev_mask(self, mask, shape):
         """frame_mask(mask, shape) on the device; an element mask that is already there goes through untouched."""
@@ -699,6 +766,11 @@ class GaussianDiffusion:
         thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
         out = torch.empty_like(x)
         nz = None if noise is None else self._dev(noise)
+        if nz is None and self.frame_noise_alpha:                         # z = a s + b e drawn inside the step kernel
+            L.check(L.vdx_p_sample_step_mixed(L.ptr(x), L.ptr(eps_hat), L.ptr(out), L.ptr(t32), L.ptr(self._ptab), self.num_timesteps,
+                                              x.shape[2], self._mix[0], self._mix[1], int(key or 0) & 0xFFFFFFFFFFFFFFFF, 0, 0, L.ptr(thres),
+                                              int(clip_denoised), x.shape[0], self.channels, self._per_sample(x), L.stream_ptr()))
+            return out
         L.check(vdx_p_sample_step(L.ptr(x), L.ptr(eps_hat), L.ptr(out), L.ptr(t32), L.ptr(self._ptab), self.num_timesteps,
                                   L.ptr(nz), int(key or 0) & 0xFFFFFFFFFFFFFFFF, 0, 0, L.ptr(thres), int(clip_denoised),
                                   x.shape[0], self.channels, self._per_sample(x), L.stream_ptr()))
@@ -734,7 +806,9 @@ class GaussianDiffusion:
                    masked=None):
         """One whole chain on the current stream (inside _sampling()): chain 'ddpm' (the T-step ancestral one) | 'ddim' | 'dpm' (the
         two over ddim_time_sequence(T, steps)), as the plain, the masked or the guided variant -> the vdx_*_sample_loop* entry of
-        _LOOPS, captured in a hipGraph (use_graph) or run eagerly by the same step function.  x_T = Philox(key, draw 0) unless given.
+        _LOOPS, captured in a hipGraph (use_graph) or run eagerly by the same step function.  x_T = noise(shape, key, 0) unless given
+        (Philox(key, draw 0); the mixed noise with frame_noise_alpha > 0, where the 'ddpm' chain is vdx_p_sample_loop_mixed, plain or
+        guided, and the two deterministic chains change in x_T only).
         Guided (cond given, the network has a condition, cond_scale != 1; classifier-free guidance, EXTENSION, parity unpinned: the
         reference's p_sample_loop drops cond): one forward over 2B samples (conditioned | null embedding) per step, so img / eps /
         t hold 2B rows and the first B are the result.  masked = (video, element mask, mask table, resample_steps): the loop of
@@ -769,11 +843,11 @@ class GaussianDiffusion:
             if guided:
                 img = torch.empty((rows,) + shape[1:], dtype=torch.float32, device=dev)
                 if x_T is None:
-                    L.check(vdx_randn(L.ptr(img), img.numel() // 2, seed, 0, 0, L.stream_ptr()))      # x_T of the B videos: the first half
+                    self.noise(shape, seed, 0, out=img)                                                # x_T of the B videos: the first half
                 else:
                     img[:B].copy_(self._dev(x_T))
             else:
-                img = self.randn(shape, seed, 0) if x_T is None else self._dev(x_T).clone()
+                img = self.noise(shape, seed, 0) if x_T is None else self._dev(x_T).clone()
             hist = torch.empty(shape, dtype=torch.float32, device=dev) if chain == 'dpm' else None
             seq = None if seq_host is None else torch.from_numpy(seq_host).to(dev)
             eps = torch.empty(rows, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=dev)
@@ -804,7 +878,10 @@ class GaussianDiffusion:
             else:
                 body = (L.ptr(self.alphas_cumprod), L.ptr(seq), steps, steps, L.ptr(condd), 1) + ((order,) if chain == 'dpm' else ()) \
                     + (L.ptr(self._ptab), T, perc, L.ptr(thres))
-            L.check(_LOOPS[chain, variant[0]](*head, *body, *variant[1], L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
+            loop, extra = _LOOPS[chain, variant[0]], variant[1]
+            if chain == 'ddpm' and self.frame_noise_alpha:                # the mixed ancestral loop: the guided entry's arguments + (a, b)
+                loop, extra = L.vdx_p_sample_loop_mixed, (variant[1] if guided else (1.0, 0.0, 0)) + self._mix
+            L.check(loop(*head, *body, *extra, L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
         img = img[:B]
         out = torch.empty_like(img)
         L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
@@ -907,6 +984,7 @@ class GaussianDiffusion:
         learned_variance: the KL and decoder terms use the model's own log sigma^2 (vdx_vlb_loop_lv)."""
         self._lv_refuse(focus_present=focus_present)
         self._sr_refuse(calc_bpd_loop=True)
+        self._mix_refuse('calc_bpd_loop')                                 # (the KL terms need the inverse frame covariance)
         return self._bpd_chain(x, key, cond, clip_denoised, timesteps, use_graph, focus_present, None)
 
     def _bpd_chain(self, x, key, cond, clip_denoised, timesteps, use_graph, focus_present, pieces):
@@ -1023,6 +1101,7 @@ class GaussianDiffusion:
         with the (1, 0) mask table, vdx.h), as such a network saw its context frames in training.  Not with resample_steps > 1."""
         self._lv_refuse(inpaint=True)
         self._sr_refuse(inpaint=True)
+        self._mix_refuse('inpaint')                                       # (the known region's noise would have to share s with the generated frames)
         if focus_present is not None:
             raise ValueError('inpaint / extend do not take focus_present (frame-conditioned sampling of a focus-present sample is out of scope)')
         opts = self._inpaint_options(video, dict(cond_scale=cond_scale, ddim_steps=ddim_steps, resample_steps=resample_steps, use_graph=use_graph,
@@ -1084,6 +1163,7 @@ class GaussianDiffusion:
         frame-conditioned denoiser): every window keeps its context frames un-noised, see inpaint()."""
         self._lv_refuse(extend=True)
         self._sr_refuse(extend=True)
+        self._mix_refuse('extend')
         ctx = self.num_frames // 2 if context_frames is None else int(context_frames)
         video = torch.as_tensor(video)
         if video.dim() != 5 or tuple(video.shape[1:2] + video.shape[3:]) != (self.channels, self.image_size, self.image_size):
@@ -1128,7 +1208,7 @@ class GaussianDiffusion:
         t32 = self._dev(t, torch.int32)
         if noise is None:
             assert key is not None, 'A key must be provided to q_sample if noise is not.'
-            noise = self.randn(x_start.shape, key, 0)
+            noise = self.noise(x_start.shape, key, 0)
         noise = self._dev(noise)
         out = torch.empty_like(x_start)
         if frame_mask is not None:
@@ -1161,7 +1241,7 @@ class GaussianDiffusion:
         if noise is None:
             assert key is not None
             _, noise_key, _ = split_key(key, 3)
-            noise = self.randn(x_start.shape, noise_key, 0)
+            noise = self.noise(x_start.shape, noise_key, 0)
         noise = self._dev(noise)
         if self.lowres_cond is not None:
             # super-resolution: lowres defaults to the box mean of the raw clip; aug_levels to a draw from {0..lowres_aug_max-1} under

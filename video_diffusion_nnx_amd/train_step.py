@@ -205,7 +205,7 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
         # the device draw under the same t_key (draw 0) replaces the host randint; an explicit t only gets its weights
         t, iw = smp.draw(B, t_key, 0, t=t)
     tr.last_iw = iw
-    noise = gd.randn(x.shape, noise_key, 0) if noise is None else torch.as_tensor(noise).to(dev, torch.float32).contiguous()
+    noise = gd.noise(x.shape, noise_key, 0) if noise is None else torch.as_tensor(noise).to(dev, torch.float32).contiguous()
     tr.last_t, tr.last_noise_key = t, noise_key
     if frame_mask is None and int(tr.frame_cond_max) > 0:
         g = torch.Generator().manual_seed(frame_cond_key(tr.rng_seed, tr.rank, step, j) & 0x7FFFFFFFFFFFFFFF)
