@@ -104,7 +104,8 @@ def main():
                 e1.synchronize()
                 return round(1e3 * e0.elapsed_time(e1) / n, 2)
             # the same three, inside real train steps: device events around each call site (the launch plus what it waits for on the stream)
-            from video_diffusion_nnx_amd import train_step as TSTEP
+            # (the weighted objective is GaussianDiffusion.loss_and_grad's call of timestep_sampler.loss_weighted, looked up on the module)
+            from video_diffusion_nnx_amd import timestep_sampler as TSMOD
             spans = {'tsampler_draw': [], 'loss_weighted': [], 'tsampler_update': []}
 
             def spanned(name, fn):
@@ -116,16 +117,16 @@ def main():
                     spans[name].append((e0, e1))
                     return r
                 return wrapper
-            keep = tr.sampler.draw, tr.sampler.update, TSTEP.loss_weighted
+            keep = tr.sampler.draw, tr.sampler.update, TSMOD.loss_weighted
             tr.sampler.draw, tr.sampler.update = spanned('tsampler_draw', keep[0]), spanned('tsampler_update', keep[1])
-            TSTEP.loss_weighted = spanned('loss_weighted', keep[2])
+            TSMOD.loss_weighted = spanned('loss_weighted', keep[2])
             try:
                 for _ in range(a.train_steps):
                     tr.train_step(batch, step=count['on'])
                     count['on'] += 1
                 torch.cuda.synchronize()
             finally:
-                tr.sampler.draw, tr.sampler.update, TSTEP.loss_weighted = keep
+                tr.sampler.draw, tr.sampler.update, TSMOD.loss_weighted = keep
             out['in_step_us'] = {k: round(1e3 * statistics.median(e0.elapsed_time(e1) for e0, e1 in v), 2) for k, v in spans.items()}
             from video_diffusion_nnx_amd import _lib as L
             from video_diffusion_nnx_amd.train_step import vdx_loss_grad, vdx_loss_sum

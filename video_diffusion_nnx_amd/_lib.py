@@ -1,7 +1,8 @@
 """ctypes binding of libvdx.so (the C ABI declared in include/vdx.h).
 
-This is the only place the Python host touches native code.  There is NO fallback: if the shared
-library is missing or a symbol cannot be resolved, importing this module raises.
+The library is loaded here and nowhere else; the modules that call an entry bind it with `_sig` (here, or next to its caller:
+gaussian_diffusion.py, train_step.py, ops.py, unet3d.py, timestep_sampler.py).  There is NO fallback: if the shared library is
+missing or a symbol cannot be resolved, importing the binding module raises.
 """
 from __future__ import annotations
 

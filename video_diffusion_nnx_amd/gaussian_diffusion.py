@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import timestep_sampler as TS
 from .unet3d import Unet3D
 
 _vp = C.c_void_p
@@ -51,10 +52,35 @@ vdx_dpm_sample_loop_masked = L._sig('vdx_dpm_sample_loop_masked', C.c_int, [_vp]
                                     + [_vp] * 4 + [_u64, _vp, C.c_size_t, C.c_int, C.c_int, _vp])
 
 
-# the eleven loop entry points by (chain, variant); the two without a dynamic threshold are the _dyn ones with percentile 0
+vdx_loss_grad = L._sig('vdx_loss_grad', C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_long, C.c_int, _vp])
+vdx_loss_grad_masked = L._sig('vdx_loss_grad_masked', C.c_int, [_vp] * 5 + [C.c_int, C.c_int, C.c_long, C.c_int, _vp])
+
+
+# The loop entry points by (chain, variant): fourteen of the library's sixteen (the other two, vdx_p_sample_loop and vdx_ddim_sample_loop,
+# are the plain _dyn entries with percentile 0).  'mixed' and 'lv' exist for the ancestral chain only; the two deterministic chains
+# change under the mixed prior in x_T alone and run their plain / guided entries.
 _LOOPS = {('ddpm', 'plain'): vdx_p_sample_loop_dyn, ('ddpm', 'masked'): vdx_p_sample_loop_masked, ('ddpm', 'guided'): L.vdx_p_sample_loop_guided,
+          ('ddpm', 'mixed'): L.vdx_p_sample_loop_mixed, ('ddpm', 'sr'): L.vdx_p_sample_loop_sr, ('ddpm', 'lv'): L.vdx_p_sample_loop_lv,
           ('ddim', 'plain'): vdx_ddim_sample_loop_dyn, ('ddim', 'masked'): vdx_ddim_sample_loop_masked, ('ddim', 'guided'): L.vdx_ddim_sample_loop_guided,
-          ('dpm', 'plain'): vdx_dpm_sample_loop, ('dpm', 'masked'): vdx_dpm_sample_loop_masked, ('dpm', 'guided'): L.vdx_dpm_sample_loop_guided}
+          ('ddim', 'sr'): L.vdx_ddim_sample_loop_sr,
+          ('dpm', 'plain'): vdx_dpm_sample_loop, ('dpm', 'masked'): vdx_dpm_sample_loop_masked, ('dpm', 'guided'): L.vdx_dpm_sample_loop_guided,
+          ('dpm', 'sr'): L.vdx_dpm_sample_loop_sr}
+_CFG = ' cond_scale rescale scratch'
+_LOOP_EXTRA = {'plain': '', 'sr': '', 'lv': '', 'guided': _CFG, 'mixed': _CFG + ' mix_a mix_b', 'masked': ' known mask mtab'}
+
+
+def loop_args(chain: str, variant: str, named: dict) -> list:
+    """The positional arguments of the entry _LOOPS[chain, variant] out of `named` (argument name -> value), in the order include/vdx.h
+    declares them: head | chain block | variant block | tail."""
+    sig = 'h params packed img' + (' xin' if variant == 'sr' else '') + ' eps' + (' hist' if chain == 'dpm' else '') + ' t_dev step_dev'
+    if variant == 'lv':
+        sig += ' lv_tab seq seq_len timesteps nsteps cond seed clip post_scale post_shift'
+    elif chain == 'ddpm':
+        sig += ' tables timesteps nsteps cond seed clip percentile thres'
+    else:
+        sig += ' ac seq seq_len nsteps cond clip' + (' order' if chain == 'dpm' else '') + ' tables timesteps percentile thres'
+    sig += _LOOP_EXTRA[variant] + ((' resample' if chain == 'ddpm' else ' seed') if variant == 'masked' else '')
+    return [named[n] for n in (sig + ' ws ws_bytes batch use_graph stream').split()]
 
 
 def extend_plan(have: int, num_new: int, num_frames: int, context_frames: int):
@@ -116,6 +142,13 @@ def check_dpm_args(timesteps: int, dpm_steps, dpm_order=2, ddim_steps=None, resa
         raise ValueError(f'dpm_order must be 1 or 2, got {dpm_order}')
     if not 1 <= int(dpm_steps) <= int(timesteps):
         raise ValueError(f'dpm_steps must be in [1, {int(timesteps)}], got {dpm_steps}')
+
+
+def chain_choice(timesteps: int, ddim_steps=None, dpm_steps=None, dpm_order=2, resample_steps: int = 1):
+    """(chain, steps) of the sampler keywords, after check_dpm_args: ('dpm', S) with dpm_steps, ('ddim', S) with ddim_steps, else the
+    T-step ancestral chain ('ddpm', 0)."""
+    check_dpm_args(timesteps, dpm_steps, dpm_order, ddim_steps, resample_steps)
+    return ('dpm', int(dpm_steps)) if dpm_steps is not None else ('ddim', int(ddim_steps)) if ddim_steps else ('ddpm', 0)
 
 
 def check_guidance_rescale(guidance_rescale) -> float:
@@ -280,6 +313,17 @@ def extract(a: torch.Tensor, t: torch.Tensor, x_shape) -> torch.Tensor:
     """reference utils.py:225-238."""
     b = t.shape[0]
     return a.gather(-1, t.long()).reshape(b, *((1,) * (len(x_shape) - 1)))
+
+
+def _stage(x, dtype, dev) -> torch.Tensor:
+    """`x` as a contiguous tensor of `dtype` (None: its own) on `dev`.  A host tensor goes through pinned memory and a non-blocking copy:
+    a pageable host-to-device copy waits for the stream to drain -- one host sync per train step that kept the launch queue from
+    running ahead of the GPU."""
+    x = torch.as_tensor(x)
+    x = x if dtype is None else x.to(dtype)
+    if x.device.type == 'cpu' and dev.type == 'cuda':
+        x = x.pin_memory().to(dev, non_blocking=True)
+    return x.to(dev).contiguous()
 
 
 def is_list_str(x) -> bool:
@@ -463,10 +507,22 @@ class GaussianDiffusion:
         L.check(L.vdx_randn_mixed(L.ptr(out), B, C, Fr, H * W, self._mix[0], self._mix[1], seed, draw, 0, L.stream_ptr()))
         return out
 
-    def _mix_refuse(self, what):
-        """ValueError for what the mixed-noise prior does not serve yet (follow-ups)."""
-        if self.frame_noise_alpha:
-            raise ValueError(f'frame_noise_alpha does not support {what} yet (a follow-up; DESIGN.md 9)')
+    # the optional features that refuse what they do not serve yet: message prefix, "is it on"
+    _FEATURES = {'learned_variance': ('learned_variance', lambda gd: gd.learned_variance),
+                 'lowres_cond': ('lowres_cond (super-resolution)', lambda gd: gd.lowres_cond is not None),
+                 'frame_noise_alpha': ('frame_noise_alpha', lambda gd: bool(gd.frame_noise_alpha))}
+
+    def _refuse(self, feature, **given):
+        """ValueError for the first of the keywords `given` that is in use (not None / False / its neutral value) while `feature` is on:
+        what the feature does not serve yet (follow-ups)."""
+        prefix, on = self._FEATURES[feature]
+        if not on(self):
+            return
+        off = dict(cond_scale=1.0, guidance_rescale=0.0)
+        for name, val in given.items():
+            if val is None or val is False or (name in off and float(val) == off[name]):
+                continue
+            raise ValueError(f'{prefix} does not support {name} yet (a follow-up; DESIGN.md 9)')
 
     def _dev_mask(self, mask, shape):
         """frame_mask(mask, shape) on the device; an element mask that is already there goes through untouched."""
@@ -488,16 +544,6 @@ class GaussianDiffusion:
         return s
 
     # -- learned variances ---------------------------------------------------------------------------
-    def _lv_refuse(self, **given):
-        """ValueError for what the learned-variance paths do not serve yet (follow-ups: they need only the eps half)."""
-        if not self.learned_variance:
-            return
-        off = dict(cond_scale=1.0, guidance_rescale=0.0)
-        for name, val in given.items():
-            if val is None or val is False or (name in off and float(val) == off[name]):
-                continue
-            raise ValueError(f'learned_variance does not support {name} yet (a follow-up; DESIGN.md 9)')
-
     def _lv_tables(self, steps=None):
         """(descending device sequence [S + 1], float32 step table [6, S], S) of the S-level learned-variance chain, kept per S: the
         captured step bakes the addresses in."""
@@ -520,16 +566,6 @@ class GaussianDiffusion:
         return self.denoise_fn(x, t32, cond=cond)
 
     # -- cascaded super-resolution -------------------------------------------------------------------
-    def _sr_refuse(self, **given):
-        """ValueError for what a super-resolution diffusion does not serve yet (follow-ups)."""
-        if self.lowres_cond is None:
-            return
-        off = dict(cond_scale=1.0, guidance_rescale=0.0)
-        for name, val in given.items():
-            if val is None or val is False or (name in off and float(val) == off[name]):
-                continue
-            raise ValueError(f'lowres_cond (super-resolution) does not support {name} yet (a follow-up; DESIGN.md 9)')
-
     def _sr_need_lowres(self, who, instead):
         if self.lowres_cond is not None:
             raise ValueError(f'lowres_cond (super-resolution): {who} has no low-resolution clip to condition on; use {instead}')
@@ -580,12 +616,7 @@ class GaussianDiffusion:
         from . import ops
         ft, fs = self.lowres_cond
         lo = ops.lowres_down(x_start, ft, fs) if lowres is None else self._dev(lowres)
-        lv = None
-        if aug_levels is not None:
-            lv = torch.as_tensor(aug_levels).to(torch.int32)
-            if lv.device.type == 'cpu' and self.device.type == 'cuda':
-                lv = lv.pin_memory().to(self.device, non_blocking=True)   # as t in the train step: no pageable copy, no host sync
-            lv = lv.to(self.device).contiguous()
+        lv = None if aug_levels is None else _stage(aug_levels, torch.int32, self.device)
         return ops.lowres_input(lo, ft, fs, x0=x_start, t=t32, noise=noise, tables=(self.sqrt_alphas_cumprod, self.sqrt_one_minus_alphas_cumprod),
                                 aug_levels=lv, seed=key, draw=0, pre=_pre)
 
@@ -600,52 +631,6 @@ class GaussianDiffusion:
             raise NotImplementedError('pass text conditioning as a ready embedding tensor')
         return self.denoise_fn(torch.cat([x, u], dim=1), t32, cond=cond)
 
-    def _run_chain_sr(self, chain, lowres, key, *, aug_level=None, steps=0, order=2, cond=None, use_graph=True, x_T=None):
-        """One super-resolution chain on the current stream (inside _sampling()): u is written once into the second half of xin
-        (vdx_lowres_input, augmentation draw VDX_DRAW_LOWRES of the chain's seed), then the vdx_*_sample_loop_sr entry of the chain runs
-        its captured step: lowres_pack -> forward(xin) -> the plain chain's step kernel on img.  x_T = Philox(key, draw 0), step k draws
-        1 + k, as the plain loops.  The buffers are kept per batch size: a second call replays the cached graph."""
-        unet, T, dev = self.denoise_fn, self.num_timesteps, self.device
-        seed = int(key) & 0xFFFFFFFFFFFFFFFF
-        B = lowres.shape[0]
-        shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
-        buf = getattr(self, '_sr_buf', None)
-        if buf is None or buf['key'] != (B, chain, steps):
-            seq_host = None if chain == 'ddpm' else ddim_time_sequence(T, steps)
-            buf = self._sr_buf = dict(
-                key=(B, chain, steps), img=torch.empty(shape, dtype=torch.float32, device=dev),
-                xin=torch.zeros((B, 2 * self.channels) + shape[2:], dtype=torch.float32, device=dev),
-                eps=torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=dev),
-                hist=torch.empty(shape, dtype=torch.float32, device=dev) if chain == 'dpm' else None,
-                t=torch.empty(B, dtype=torch.int32, device=dev), step=torch.empty(1, dtype=torch.int64, device=dev),
-                thres=torch.empty(B, dtype=torch.float32, device=dev) if self.use_dynamic_thres else None,
-                seq=None if seq_host is None else torch.from_numpy(seq_host).to(dev), t0=T - 1 if seq_host is None else int(seq_host[0]))
-        img, xin, eps, hist, t_dev, step_dev, thres, seq = (buf[k] for k in ('img', 'xin', 'eps', 'hist', 't', 'step', 'thres', 'seq'))
-        if x_T is None:
-            L.check(vdx_randn(L.ptr(img), img.numel(), seed, 0, 0, L.stream_ptr()))
-        else:
-            img.copy_(self._dev(x_T))
-        self.lowres_condition(lowres, seed, aug_level, draw=L.DRAW_LOWRES, out=xin)
-        perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
-        condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
-        h = unet.handle(self.num_frames, self.image_size)
-        unet.apply_activation_storage(h)
-        ws = unet.workspace(B, self.num_frames, self.image_size)
-        t_dev.fill_(buf['t0'])
-        step_dev.zero_()
-        head = (h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(xin), L.ptr(eps)) + ((L.ptr(hist),) if chain == 'dpm' else ()) \
-            + (L.ptr(t_dev), L.ptr(step_dev))
-        if chain == 'ddpm':
-            body = (L.ptr(self._ptab), T, T, L.ptr(condd), seed, 1, perc, L.ptr(thres))
-        else:
-            body = (L.ptr(self.alphas_cumprod), L.ptr(seq), steps, steps, L.ptr(condd), 1) + ((order,) if chain == 'dpm' else ()) \
-                + (L.ptr(self._ptab), T, perc, L.ptr(thres))
-        loop = {'ddpm': L.vdx_p_sample_loop_sr, 'ddim': L.vdx_ddim_sample_loop_sr, 'dpm': L.vdx_dpm_sample_loop_sr}[chain]
-        L.check(loop(*head, *body, L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
-        out = torch.empty_like(img)
-        L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
-        return out
-
     def upsample(self, key, lowres, *, aug_level=None, cond=None, ddim_steps: Optional[int] = None, dpm_steps: Optional[int] = None,
                  dpm_order: int = 2, use_graph: bool = True, x_T=None):
         """The second stage of a cascade (EXTENSION): sample [B,C,F,S,S] in [0, 1] conditioned on the low-resolution clip `lowres`
@@ -657,15 +642,14 @@ class GaussianDiffusion:
         lowres = torch.as_tensor(lowres)
         B = self._sr_lowres(lowres)[0]
         self._sr_levels(aug_level, B)                                     # (its range check, before any device work)
-        check_dpm_args(self.num_timesteps, dpm_steps, dpm_order, ddim_steps)
+        chain, steps = chain_choice(self.num_timesteps, ddim_steps, dpm_steps, dpm_order)
         if ddim_steps:
             ddim_time_sequence(self.num_timesteps, ddim_steps)
         if x_T is not None and tuple(x_T.shape) != (B, self.channels, self.num_frames, self.image_size, self.image_size):
             raise ValueError(f'x_T must be [{B}, {self.channels}, {self.num_frames}, {self.image_size}, {self.image_size}], got {tuple(x_T.shape)}')
-        chain, steps = ('dpm', int(dpm_steps)) if dpm_steps is not None else ('ddim', int(ddim_steps)) if ddim_steps else ('ddpm', 0)
         with self._sampling(None, B):
-            return self._run_chain_sr(chain, lowres, key, aug_level=aug_level, steps=steps, order=dpm_order, cond=cond, use_graph=use_graph,
-                                      x_T=x_T)
+            return self._run_chain(chain, B, key, steps=steps, order=dpm_order, cond=cond, use_graph=use_graph, x_T=x_T, lowres=lowres,
+                                   aug_level=aug_level)
 
     def model_log_variance(self, out2, t):
         """log sigma^2 [B,C,F,H,W] of the network output out2 [B,F,H,W,2C] at levels t of the full chain (torch, on out2's device)."""
@@ -697,84 +681,50 @@ class GaussianDiffusion:
         self.last_loss_per_sample = out[:2 * B].reshape(B, 2)
         return out[2 * B + 2].to(torch.float32).reshape(()), d_out
 
-    def _p_step_lv(self, x, t32, cond, clip_denoised, key, noise, zero_noise=False):
-        out2 = self._lv_out(x, t32, cond)
-        _, tab, _ = self._lv_tables(None)
-        out = torch.empty_like(x)
-        nz = torch.zeros_like(x) if zero_noise else (None if noise is None else self._dev(noise))
-        L.check(L.vdx_p_sample_step_lv(L.ptr(x), L.ptr(out2), L.ptr(out), L.ptr(t32), L.ptr(tab), self.num_timesteps, 0, 0, L.ptr(nz),
-                                       int(key or 0) & 0xFFFFFFFFFFFFFFFF, 0, 0, int(clip_denoised), 1.0, 0.0, x.shape[0], self.channels,
-                                       self._per_sample(x), L.stream_ptr()))
-        return out, out2
-
-    def _run_chain_lv(self, B, key, *, steps=None, cond=None, use_graph=True, x_T=None):
-        """The learned-variance ancestral chain on the current stream (inside _sampling()): S = steps (None: T) levels, one captured
-        step (vdx_p_sample_loop_lv), x_T = Philox(key, draw 0), step k draws 1 + k; unnormalize_img is folded into the last step."""
-        unet, T, dev = self.denoise_fn, self.num_timesteps, self.device
-        seed = int(key) & 0xFFFFFFFFFFFFFFFF
-        seq, tab, S = self._lv_tables(steps)
-        shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
-        img = self.randn(shape, seed, 0) if x_T is None else self._dev(x_T).clone()
-        out2 = torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=dev)
-        t_dev = torch.full((B,), int(seq[0]), dtype=torch.int32, device=dev)
-        step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-        condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
-        h = unet.handle(self.num_frames, self.image_size)
-        unet.apply_activation_storage(h)
-        ws = unet.workspace(B, self.num_frames, self.image_size)
-        L.check(L.vdx_p_sample_loop_lv(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(out2), L.ptr(t_dev), L.ptr(step_dev),
-                                       L.ptr(tab), L.ptr(seq), S, T, S, L.ptr(condd), seed, 1, 0.5, 0.5, L.ptr(ws), ws.numel(), B, int(use_graph),
-                                       L.stream_ptr()))
-        return img
-
     # -- reverse process ---------------------------------------------------------------------------
-    def p_mean_variance(self, x, t, clip_denoised: bool, cond=None, cond_scale: float = 1.0, *, lowres_cond=None):
-        """reference :162-228 (returns (mean, variance, log_variance)).  learned_variance: the model's variance, per element.
-        lowres_cond (a super-resolution diffusion only, and required there): u = lowres_condition(lowres), the network sees [ x | u ]."""
-        self._sr_refuse(cond_scale=cond_scale)
+    def _p_step(self, x, t, clip_denoised, cond, cond_scale, lowres_cond, key=0, noise=None, zero_noise=False):
+        """One eager reverse step -> (x_{t-1}, t on the device, the network output of a learned-variance diffusion or None).  The noise
+        is `noise` when given, zero with zero_noise (the fused step is then the posterior mean), else drawn inside the step kernel as
+        Philox(key, draw 0) under the diffusion's prior."""
+        self._refuse('lowres_cond', cond_scale=cond_scale)
         if self.lowres_cond is None and lowres_cond is not None:
             raise ValueError('lowres_cond needs a super-resolution diffusion (lowres_cond=(ft, fs))')
         x = self._dev(x)
         t32 = self._dev(t, torch.int32)
+        self._refuse('learned_variance', cond_scale=cond_scale)
+        seed = int(key or 0) & 0xFFFFFFFFFFFFFFFF
+        out = torch.empty_like(x)
+        nz = torch.zeros_like(x) if zero_noise else (None if noise is None else self._dev(noise))
+        size = lambda: (x.shape[0], self.channels, self._per_sample(x), L.stream_ptr())        # (the tail of every step entry)
         if self.learned_variance:
-            self._lv_refuse(cond_scale=cond_scale)
-            mean, out2 = self._p_step_lv(x, t32, cond, clip_denoised, 0, None, zero_noise=True)
-            logvar = self.model_log_variance(out2, t32)
-            return mean, logvar.exp(), logvar
+            out2 = self._lv_out(x, t32, cond)
+            L.check(L.vdx_p_sample_step_lv(L.ptr(x), L.ptr(out2), L.ptr(out), L.ptr(t32), L.ptr(self._lv_tables(None)[1]), self.num_timesteps,
+                                           0, 0, L.ptr(nz), seed, 0, 0, int(clip_denoised), 1.0, 0.0, *size()))
+            return out, t32, out2
         eps_hat = self._sr_eps(x, t32, lowres_cond, cond) if self.lowres_cond is not None else \
             self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
         thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
-        mean = torch.empty_like(x)
-        zeros = torch.zeros_like(x)      # z = 0 turns the fused step into the posterior mean
-        L.check(vdx_p_sample_step(L.ptr(x), L.ptr(eps_hat), L.ptr(mean), L.ptr(t32), L.ptr(self._ptab), self.num_timesteps,
-                                  L.ptr(zeros), 0, 0, 0, L.ptr(thres), int(clip_denoised), x.shape[0], self.channels,
-                                  self._per_sample(x), L.stream_ptr()))
-        return mean, extract(self.posterior_variance, t32, x.shape), extract(self.posterior_log_variance_clipped, t32, x.shape)
+        if nz is None and self.frame_noise_alpha:                         # z = a s + b e drawn inside the step kernel
+            L.check(L.vdx_p_sample_step_mixed(L.ptr(x), L.ptr(eps_hat), L.ptr(out), L.ptr(t32), L.ptr(self._ptab), self.num_timesteps,
+                                              x.shape[2], self._mix[0], self._mix[1], seed, 0, 0, L.ptr(thres), int(clip_denoised), *size()))
+        else:
+            L.check(vdx_p_sample_step(L.ptr(x), L.ptr(eps_hat), L.ptr(out), L.ptr(t32), L.ptr(self._ptab), self.num_timesteps, L.ptr(nz),
+                                      seed, 0, 0, L.ptr(thres), int(clip_denoised), *size()))
+        return out, t32, None
+
+    def p_mean_variance(self, x, t, clip_denoised: bool, cond=None, cond_scale: float = 1.0, *, lowres_cond=None):
+        """reference :162-228 (returns (mean, variance, log_variance)): the reverse step with z = 0, and the variance look-ups.
+        learned_variance: the model's variance, per element.  lowres_cond (a super-resolution diffusion only, and required there):
+        u = lowres_condition(lowres), the network sees [ x | u ]."""
+        mean, t32, out2 = self._p_step(x, t, clip_denoised, cond, cond_scale, lowres_cond, zero_noise=True)
+        if out2 is not None:
+            logvar = self.model_log_variance(out2, t32)
+            return mean, logvar.exp(), logvar
+        return mean, extract(self.posterior_variance, t32, mean.shape), extract(self.posterior_log_variance_clipped, t32, mean.shape)
 
     def p_sample(self, x, t, key, cond=None, cond_scale: float = 1.0, clip_denoised: bool = True, *, noise=None, lowres_cond=None):
         """reference :231-261.  `key`: seed of the noise draw (ignored when explicit `noise` is given).  lowres_cond: as p_mean_variance."""
-        self._sr_refuse(cond_scale=cond_scale)
-        if self.lowres_cond is None and lowres_cond is not None:
-            raise ValueError('lowres_cond needs a super-resolution diffusion (lowres_cond=(ft, fs))')
-        x = self._dev(x)
-        t32 = self._dev(t, torch.int32)
-        if self.learned_variance:
-            self._lv_refuse(cond_scale=cond_scale)
-            return self._p_step_lv(x, t32, cond, clip_denoised, key, noise)[0]
-        eps_hat = self._sr_eps(x, t32, lowres_cond, cond) if self.lowres_cond is not None else \
-            self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
-        thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
-        out = torch.empty_like(x)
-        nz = None if noise is None else self._dev(noise)
-        if nz is None and self.frame_noise_alpha:                         # z = a s + b e drawn inside the step kernel
-            L.check(L.vdx_p_sample_step_mixed(L.ptr(x), L.ptr(eps_hat), L.ptr(out), L.ptr(t32), L.ptr(self._ptab), self.num_timesteps,
-                                              x.shape[2], self._mix[0], self._mix[1], int(key or 0) & 0xFFFFFFFFFFFFFFFF, 0, 0, L.ptr(thres),
-                                              int(clip_denoised), x.shape[0], self.channels, self._per_sample(x), L.stream_ptr()))
-            return out
-        L.check(vdx_p_sample_step(L.ptr(x), L.ptr(eps_hat), L.ptr(out), L.ptr(t32), L.ptr(self._ptab), self.num_timesteps,
-                                  L.ptr(nz), int(key or 0) & 0xFFFFFFFFFFFFFFFF, 0, 0, L.ptr(thres), int(clip_denoised),
-                                  x.shape[0], self.channels, self._per_sample(x), L.stream_ptr()))
-        return out
+        return self._p_step(x, t, clip_denoised, cond, cond_scale, lowres_cond, key, noise)[0]
 
     # -- the sampling loops ------------------------------------------------------------------------
     @contextlib.contextmanager
@@ -802,86 +752,116 @@ class GaussianDiffusion:
             unet._focus = None
         cur.wait_stream(st)
 
+    _chain_buf = None      # the kept buffer set of the masked / super-resolution chains (an instance attribute once there is one)
+
+    def _chain_bufs(self, B, rows=None, *, xin=False, known=False, hist=False, seq_host=None, keep=None):
+        """The device buffers of one chain of B videos over `rows` network rows (default B; 2B under guidance), by name: img, eps, t
+        [rows], step, thres (with use_dynamic_thres) and, on request, xin [B,2C,...] (zeroed), known + mask, hist [B] and seq (the
+        upload of seq_host).  keep: a key, (variant, B, chain, steps), under which the set is kept across calls -- a captured step bakes
+        addresses in, so a second call with the same key, seed and stream replays the cached graph; one set is kept, so a call under
+        another key (the other sequence chain with the same S, say) allocates anew.  None: fresh tensors."""
+        if keep is not None and self._chain_buf is not None and self._chain_buf['key'] == keep:
+            return self._chain_buf
+        dev, unet, rows = self.device, self.denoise_fn, rows or B
+        one = (B, self.channels, self.num_frames, self.image_size, self.image_size)
+        shape = (rows, self.channels, self.num_frames, self.image_size, self.image_size)
+        new = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device=dev)
+        buf = dict(key=keep, img=new(shape), eps=new(rows, self.num_frames, self.image_size, self.image_size, unet.out_dim),
+                   t=new(rows, dtype=torch.int32), step=new(1, dtype=torch.int64), thres=new(B) if self.use_dynamic_thres else None,
+                   xin=torch.zeros((B, 2 * self.channels) + shape[2:], dtype=torch.float32, device=dev) if xin else None,
+                   known=new(one) if known else None, mask=new(one, dtype=torch.uint8) if known else None,
+                   hist=new(one) if hist else None, seq=None if seq_host is None else torch.from_numpy(seq_host).to(dev))
+        if keep is not None:
+            self._chain_buf = buf
+        return buf
+
+    def _chain_net(self, rows, cond):
+        """(cond on the device or None, handle, workspace) of a chain over `rows` network rows, the handle's activation storage set.  A
+        condition is used un-masked (the reference drops it, Q10); a network without one ignores it."""
+        unet = self.denoise_fn
+        condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
+        h = unet.handle(self.num_frames, self.image_size)
+        unet.apply_activation_storage(h)
+        return condd, h, unet.workspace(rows, self.num_frames, self.image_size)
+
     def _run_chain(self, chain, B, key, *, steps=0, order=2, cond=None, cond_scale=1.0, guidance_rescale=0.0, use_graph=True, x_T=None,
-                   masked=None):
+                   masked=None, lowres=None, aug_level=None):
         """One whole chain on the current stream (inside _sampling()): chain 'ddpm' (the T-step ancestral one) | 'ddim' | 'dpm' (the
-        two over ddim_time_sequence(T, steps)), as the plain, the masked or the guided variant -> the vdx_*_sample_loop* entry of
-        _LOOPS, captured in a hipGraph (use_graph) or run eagerly by the same step function.  x_T = noise(shape, key, 0) unless given
-        (Philox(key, draw 0); the mixed noise with frame_noise_alpha > 0, where the 'ddpm' chain is vdx_p_sample_loop_mixed, plain or
-        guided, and the two deterministic chains change in x_T only).
-        Guided (cond given, the network has a condition, cond_scale != 1; classifier-free guidance, EXTENSION, parity unpinned: the
-        reference's p_sample_loop drops cond): one forward over 2B samples (conditioned | null embedding) per step, so img / eps /
-        t hold 2B rows and the first B are the result.  masked = (video, element mask, mask table, resample_steps): the loop of
-        inpaint() on the persistent _inpaint_bufs; masked and guided together run eagerly (_masked_guided_steps).
+        two over ddim_time_sequence(T, steps)) -> the entry _LOOPS[chain, variant], captured in a hipGraph (use_graph) or run eagerly by
+        the same step function.  x_T = noise(shape, key, 0) unless given (Philox(key, draw 0)), step k draws 1 + k.  The variants:
+          plain
+          guided  cond given, the network has a condition, cond_scale != 1 (classifier-free guidance, EXTENSION, parity unpinned: the
+                  reference's p_sample_loop drops cond): one forward over 2B rows (conditioned | null embedding) per step, so img / eps /
+                  t hold 2B rows and the first B are the result.
+          mixed   frame_noise_alpha > 0 on the ancestral chain, plain or guided (the guided entry's arguments + (a, b)); the two
+                  deterministic chains change in x_T only.
+          masked  masked = (video, element mask, mask table, resample_steps): the loop of inpaint() on kept buffers; masked and guided
+                  together run eagerly (_masked_guided_steps).
+          sr      lowres given (a super-resolution diffusion): u is written once into the second half of xin (vdx_lowres_input,
+                  augmentation draw VDX_DRAW_LOWRES of the seed), the captured step is lowres_pack -> forward(xin) -> the plain step on
+                  img; kept buffers.
+          lv      a learned-variance diffusion: steps = S (None: T) levels of the respaced ancestral chain; unnormalize_img is folded into
+                  the last step (post_scale = post_shift = 0.5), every other variant runs it as a launch of its own.
         Returns unnormalize_img(x_0) [B,C,F,H,W] in [0, 1]."""
-        unet, T, dev = self.denoise_fn, self.num_timesteps, self.device
+        unet, T = self.denoise_fn, self.num_timesteps
         seed = int(key) & 0xFFFFFFFFFFFFFFFF
         shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
         guided = cond is not None and unet.has_cond and cond_scale != 1
-        seq_host = None if chain == 'ddpm' else ddim_time_sequence(T, steps)
+        variant = 'sr' if lowres is not None else 'lv' if self.learned_variance else 'masked' if masked is not None else \
+            'guided' if guided else 'plain'
+        named = {}
+        if variant == 'lv':
+            seq, lv_tab, steps = self._lv_tables(steps)
+            seq_host = None
+            named.update(lv_tab=L.ptr(lv_tab), post_scale=0.5, post_shift=0.5)
+        else:
+            seq_host = None if chain == 'ddpm' else ddim_time_sequence(T, steps)
+        # (the lv chain's sequence is lv_time_sequence's, whose first level is T - 1 for every S: no read of the device sequence for it)
         t0 = T - 1 if seq_host is None else int(seq_host[0])
-        rows = 2 * B if guided and masked is None else B           # what the forward covers
-        perc = float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0
-        if masked is not None:
+        rows = 2 * B if variant == 'guided' else B                 # what the forward covers
+        buf = self._chain_bufs(B, rows, xin=variant == 'sr', known=variant == 'masked', hist=chain == 'dpm', seq_host=seq_host,
+                               keep=(variant, B, chain, steps) if variant in ('masked', 'sr') else None)
+        img = buf['img']
+        # the start state: x_T in the first B rows (and, for the captured loops below, every row at level t0, step 0)
+        if x_T is None:
+            self.noise(shape, seed, 0, out=img)
+        else:
+            img[:B].copy_(self._dev(x_T))
+        nsteps = T if (chain == 'ddpm' and variant != 'lv') else steps
+        if variant == 'masked':
             video, m, mtab, U = masked
-            buf = self._inpaint_bufs(B, steps)
-            img, known, mk = buf['img'], buf['known'], buf['mask']
-            if x_T is None:
-                L.check(vdx_randn(L.ptr(img), img.numel(), seed, 0, 0, L.stream_ptr()))
-            else:
-                img.copy_(self._dev(x_T))
-            vd = self._dev(video)
-            L.check(vdx_affine(L.ptr(vd), L.ptr(known), img.numel(), 2.0, -1.0, L.stream_ptr()))      # normalize_img
+            known, mk = buf['known'], buf['mask']
+            L.check(vdx_affine(L.ptr(self._dev(video)), L.ptr(known), img.numel(), 2.0, -1.0, L.stream_ptr()))      # normalize_img
             mk.copy_(m)
             L.check(vdx_inpaint_init(L.ptr(img), L.ptr(known), L.ptr(mk), L.ptr(mtab), T, t0, img.numel(), L.stream_ptr()))
-            if chain == 'dpm' and 'hist' not in buf:
-                buf['hist'] = torch.empty_like(img)
-            eps, hist, t_dev, step_dev, seq = buf['eps'], buf.get('hist'), buf['t'], buf['step'], buf['seq']
-            thres = buf['thres'] if self.use_dynamic_thres else None
-            variant = 'masked', (L.ptr(known), L.ptr(mk), L.ptr(mtab), U if chain == 'ddpm' else seed)
-        else:
-            if guided:
-                img = torch.empty((rows,) + shape[1:], dtype=torch.float32, device=dev)
-                if x_T is None:
-                    self.noise(shape, seed, 0, out=img)                                                # x_T of the B videos: the first half
-                else:
-                    img[:B].copy_(self._dev(x_T))
-            else:
-                img = self.noise(shape, seed, 0) if x_T is None else self._dev(x_T).clone()
-            hist = torch.empty(shape, dtype=torch.float32, device=dev) if chain == 'dpm' else None
-            seq = None if seq_host is None else torch.from_numpy(seq_host).to(dev)
-            eps = torch.empty(rows, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=dev)
-            t_dev = torch.empty(rows, dtype=torch.int32, device=dev)
-            step_dev = torch.empty(1, dtype=torch.int64, device=dev)
-            thres = torch.empty(B, dtype=torch.float32, device=dev) if self.use_dynamic_thres else None
-            variant = 'plain', ()
-        if guided and masked is not None:
+            named.update(known=L.ptr(known), mask=L.ptr(mk), mtab=L.ptr(mtab), resample=U)
+            nsteps *= U if chain == 'ddpm' else 1
+        elif variant == 'sr':
+            self.lowres_condition(lowres, seed, aug_level, draw=L.DRAW_LOWRES, out=buf['xin'])
+        if guided and variant == 'masked':
             self._masked_guided_steps(chain, buf, seq_host, cond, cond_scale, order, U, mtab, seed)
         else:
-            if guided:
-                condd = self._dev(cond)
+            buf['t'].fill_(t0)
+            buf['step'].zero_()
+            condd, h, ws = self._chain_net(rows, cond)
+            named.update(cond_scale=1.0, rescale=0.0, scratch=0)
+            if variant == 'guided':
                 assert tuple(condd.shape) == (B, unet.cond_dim), f'cond must be [{B}, {unet.cond_dim}], got {tuple(condd.shape)}'
-                scratch = torch.empty(L.vdx_cfg_scratch_doubles(B), dtype=torch.float64, device=dev)
-                variant = 'guided', (float(cond_scale), float(guidance_rescale), L.ptr(scratch))
-            else:
-                condd = None if (cond is None or not unet.has_cond) else self._dev(cond)      # used un-masked (the reference drops it, Q10)
-            h = unet.handle(self.num_frames, self.image_size)
-            unet.apply_activation_storage(h)
-            ws = unet.workspace(rows, self.num_frames, self.image_size)
-            t_dev.fill_(t0)
-            step_dev.zero_()
-            head = (h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(img), L.ptr(eps)) + ((L.ptr(hist),) if chain == 'dpm' else ()) \
-                + (L.ptr(t_dev), L.ptr(step_dev))
-            if chain == 'ddpm':
-                n = T * U if masked is not None else T
-                body = (L.ptr(self._ptab), T, n, L.ptr(condd), seed, 1, perc, L.ptr(thres))
-            else:
-                body = (L.ptr(self.alphas_cumprod), L.ptr(seq), steps, steps, L.ptr(condd), 1) + ((order,) if chain == 'dpm' else ()) \
-                    + (L.ptr(self._ptab), T, perc, L.ptr(thres))
-            loop, extra = _LOOPS[chain, variant[0]], variant[1]
-            if chain == 'ddpm' and self.frame_noise_alpha:                # the mixed ancestral loop: the guided entry's arguments + (a, b)
-                loop, extra = L.vdx_p_sample_loop_mixed, (variant[1] if guided else (1.0, 0.0, 0)) + self._mix
-            L.check(loop(*head, *body, *extra, L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
+                scratch = torch.empty(L.vdx_cfg_scratch_doubles(B), dtype=torch.float64, device=self.device)
+                named.update(cond_scale=float(cond_scale), rescale=float(guidance_rescale), scratch=L.ptr(scratch))
+            entry = variant
+            if chain == 'ddpm' and self.frame_noise_alpha and variant in ('plain', 'guided'):
+                entry = 'mixed'
+                named.update(mix_a=self._mix[0], mix_b=self._mix[1])
+            named.update(h=h.ptr, params=L.ptr(unet.flat_params), packed=L.ptr(unet.packed()), img=L.ptr(img), xin=L.ptr(buf['xin']),
+                         eps=L.ptr(buf['eps']), hist=L.ptr(buf['hist']), t_dev=L.ptr(buf['t']), step_dev=L.ptr(buf['step']),
+                         tables=L.ptr(self._ptab), timesteps=T, nsteps=nsteps, cond=L.ptr(condd), seed=seed, clip=1, order=order,
+                         percentile=float(self.dynamic_thres_percentile) if self.use_dynamic_thres else 0.0, thres=L.ptr(buf['thres']),
+                         ac=L.ptr(self.alphas_cumprod), seq=L.ptr(seq if variant == 'lv' else buf['seq']), seq_len=steps,
+                         ws=L.ptr(ws), ws_bytes=ws.numel(), batch=B, use_graph=int(use_graph), stream=L.stream_ptr())
+            L.check(_LOOPS[chain, entry](*loop_args(chain, entry, named)))
+        if variant == 'lv':
+            return img
         img = img[:B]
         out = torch.empty_like(img)
         L.check(vdx_affine(L.ptr(img), L.ptr(out), img.numel(), 0.5, 0.5, L.stream_ptr()))     # unnormalize_img
@@ -935,10 +915,10 @@ class GaussianDiffusion:
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         self._sr_need_lowres('p_sample_loop', 'upsample(key, lowres)')
         if self.learned_variance:
-            self._lv_refuse(cond_scale=cond_scale, guidance_rescale=guidance_rescale, focus_present=focus_present)
+            self._refuse('learned_variance', cond_scale=cond_scale, guidance_rescale=guidance_rescale, focus_present=focus_present)
             lv_time_sequence(self.num_timesteps, steps)                   # (its range check, before any device work)
             with self._sampling(None, int(shape[0])):
-                return self._run_chain_lv(int(shape[0]), key, steps=steps, cond=cond, use_graph=use_graph, x_T=x_T)
+                return self._run_chain('ddpm', int(shape[0]), key, steps=steps, cond=cond, use_graph=use_graph, x_T=x_T)
         if steps is not None:
             raise ValueError('steps is the respaced chain of a learned_variance diffusion; use ddim_steps / dpm_steps otherwise')
         with self._sampling(focus_present, int(shape[0])):
@@ -950,7 +930,7 @@ class GaussianDiffusion:
         """DDIM sampling with eta = 0 in `steps` network evaluations (EXTENSION, BASELINE.json configs[3]; the reference has ancestral
         sampling only).  x_T = Philox(key, draw 0), deterministic afterwards.  Returns unnormalize_img(x_0) in [0, 1].  cond with
         cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
-        self._lv_refuse(ddim_steps=steps)
+        self._refuse('learned_variance', ddim_steps=steps)
         self._sr_need_lowres('ddim_sample_loop', 'upsample(key, lowres, ddim_steps=S)')
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         ddim_time_sequence(self.num_timesteps, steps)                     # (its range check, before any device work)
@@ -964,7 +944,7 @@ class GaussianDiffusion:
         data-prediction multistep form, the step of vdx.h).  order 2 reaches in 15-25 steps what DDIM (= order 1) needs about 100 for;
         the cost per step is DDIM's plus one history tensor.  x_T = Philox(key, draw 0), deterministic afterwards.  Returns
         unnormalize_img(x_0) in [0, 1].  cond with cond_scale != 1 and guidance_rescale: as p_sample_loop (the guided loop, captured too)."""
-        self._lv_refuse(dpm_steps=steps)
+        self._refuse('learned_variance', dpm_steps=steps)
         self._sr_need_lowres('dpm_sample_loop', 'upsample(key, lowres, dpm_steps=S)')
         check_dpm_args(self.num_timesteps, steps, order)
         guidance_rescale = check_guidance_rescale(guidance_rescale)
@@ -982,9 +962,9 @@ class GaussianDiffusion:
         k = level t[k]), t [S], prior_bpd [B] and total_bpd [B] = prior_bpd + sum_t vb, None unless every level was visited.
         The model's variance is the posterior variance p_sample uses; the dynamic threshold has no place in the bound.
         learned_variance: the KL and decoder terms use the model's own log sigma^2 (vdx_vlb_loop_lv)."""
-        self._lv_refuse(focus_present=focus_present)
-        self._sr_refuse(calc_bpd_loop=True)
-        self._mix_refuse('calc_bpd_loop')                                 # (the KL terms need the inverse frame covariance)
+        self._refuse('learned_variance', focus_present=focus_present)
+        self._refuse('lowres_cond', calc_bpd_loop=True)
+        self._refuse('frame_noise_alpha', calc_bpd_loop=True)             # (the KL terms need the inverse frame covariance)
         return self._bpd_chain(x, key, cond, clip_denoised, timesteps, use_graph, focus_present, None)
 
     def _bpd_chain(self, x, key, cond, clip_denoised, timesteps, use_graph, focus_present, pieces):
@@ -1004,22 +984,17 @@ class GaussianDiffusion:
         vlb_loop = L.vdx_vlb_loop_lv if self.learned_variance else L.vdx_vlb_loop
         with self._sampling(focus_present, B):
             xd = self._dev(x)
-            condd = None if (cond is None or not unet.has_cond) else self._dev(cond)
             prior = ops.vlb_prior(xd, tab)
-            xt = torch.empty_like(xd)
-            eps = torch.empty(B, self.num_frames, self.image_size, self.image_size, unet.out_dim, dtype=torch.float32, device=dev)
-            t_dev = torch.full((B,), int(seq_host[0]), dtype=torch.int32, device=dev)
-            step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
-            seq = torch.from_numpy(seq_host).to(dev)
+            buf = self._chain_bufs(B, seq_host=seq_host)                  # (img serves as x_t)
+            buf['t'].fill_(int(seq_host[0]))
+            buf['step'].zero_()
             partial = torch.empty(L.vdx_vlb_scratch_doubles(B), dtype=torch.float64, device=dev)
             out = torch.empty(S, B, 3, dtype=torch.float64, device=dev)
-            h = unet.handle(self.num_frames, self.image_size)
-            unet.apply_activation_storage(h)
-            ws = unet.workspace(B, self.num_frames, self.image_size)
+            condd, h, ws = self._chain_net(B, cond)
             for n in (pieces or (S,)):
-                L.check(vlb_loop(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(xd), L.ptr(xt), L.ptr(eps), L.ptr(t_dev),
-                                       L.ptr(step_dev), L.ptr(tab), T, L.ptr(seq), S, int(n), L.ptr(condd), seed, int(bool(clip_denoised)),
-                                       L.ptr(partial), L.ptr(out), L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
+                L.check(vlb_loop(h.ptr, L.ptr(unet.flat_params), L.ptr(unet.packed()), L.ptr(xd), L.ptr(buf['img']), L.ptr(buf['eps']),
+                                 L.ptr(buf['t']), L.ptr(buf['step']), L.ptr(tab), T, L.ptr(buf['seq']), S, int(n), L.ptr(condd), seed,
+                                 int(bool(clip_denoised)), L.ptr(partial), L.ptr(out), L.ptr(ws), ws.numel(), B, int(use_graph), L.stream_ptr()))
             res = out.cpu()
             prior = prior.cpu()
         vb = res[:, :, 0].t().contiguous()
@@ -1051,10 +1026,10 @@ class GaussianDiffusion:
         torch.distributed group of W > 1 ranks, `batch_size` (and `cond`) describe the GLOBAL batch; rank r draws videos
         [r * per, (r + 1) * per), per = batch_size / W, from its own Philox stream shard_key(key, r) and returns ITS shard --
         no data-path collective.  W = 1 uses `key` itself (single-process behaviour unchanged)."""
-        self._lv_refuse(cond_scale=cond_scale, ddim_steps=ddim_steps, dpm_steps=dpm_steps, guidance_rescale=guidance_rescale,
-                        focus_present=focus_present)
+        self._refuse('learned_variance', cond_scale=cond_scale, ddim_steps=ddim_steps, dpm_steps=dpm_steps, guidance_rescale=guidance_rescale,
+                     focus_present=focus_present)
         if self.lowres_cond is not None:
-            self._sr_refuse(cond_scale=cond_scale, guidance_rescale=guidance_rescale, focus_present=focus_present, steps=steps)
+            self._refuse('lowres_cond', cond_scale=cond_scale, guidance_rescale=guidance_rescale, focus_present=focus_present, steps=steps)
             if lowres is None:
                 raise ValueError('lowres_cond (super-resolution): sample needs lowres=[B, C, F/ft, S/fs, S/fs], the clips to upsample')
             return self.upsample(key, lowres, aug_level=lowres_aug_level, cond=cond, ddim_steps=ddim_steps, dpm_steps=dpm_steps,
@@ -1066,7 +1041,7 @@ class GaussianDiffusion:
                 raise ValueError('steps is the respaced chain of a learned_variance diffusion; use ddim_steps / dpm_steps otherwise')
             lv_time_sequence(self.num_timesteps, steps)                       # (its range check, before any device work)
             kw['steps'] = int(steps)
-        check_dpm_args(self.num_timesteps, dpm_steps, dpm_order, ddim_steps)
+        chain, chain_steps = chain_choice(self.num_timesteps, ddim_steps, dpm_steps, dpm_order)
         kw['guidance_rescale'] = check_guidance_rescale(guidance_rescale)
         if is_list_str(cond):
             raise NotImplementedError('text -> BERT embedding needs the external video_diffusion_pytorch.text (network fetch); '
@@ -1080,10 +1055,10 @@ class GaussianDiffusion:
         key, batch_size, cond, fp_shard = self._shard(key, batch_size, cond, fp if isinstance(fp, torch.Tensor) else None)
         kw['focus_present'] = fp_shard if isinstance(fp, torch.Tensor) else fp
         shape = (batch_size, self.channels, self.num_frames, self.image_size, self.image_size)
-        if dpm_steps is not None:
-            return self.dpm_sample_loop(shape, key, steps=int(dpm_steps), order=dpm_order, cond=cond, cond_scale=cond_scale, **kw)
-        if ddim_steps:
-            return self.ddim_sample_loop(shape, key, steps=int(ddim_steps), cond=cond, cond_scale=cond_scale, **kw)
+        if chain == 'dpm':
+            return self.dpm_sample_loop(shape, key, steps=chain_steps, order=dpm_order, cond=cond, cond_scale=cond_scale, **kw)
+        if chain == 'ddim':
+            return self.ddim_sample_loop(shape, key, steps=chain_steps, cond=cond, cond_scale=cond_scale, **kw)
         return self.p_sample_loop(shape, key, cond=cond, cond_scale=cond_scale, **kw)
 
     def inpaint(self, key, video, mask, *, cond=None, cond_scale: float = 1.0, ddim_steps: Optional[int] = None, resample_steps: int = 1,
@@ -1099,9 +1074,9 @@ class GaussianDiffusion:
         clean_context=True is for a denoiser trained with frame conditioning (Trainer.frame_cond_max > 0; RaMViD, Hoeppe et al. 2022):
         the known region is `video` itself, un-noised, in the start tensor and after every step of all three chains (the same kernels
         with the (1, 0) mask table, vdx.h), as such a network saw its context frames in training.  Not with resample_steps > 1."""
-        self._lv_refuse(inpaint=True)
-        self._sr_refuse(inpaint=True)
-        self._mix_refuse('inpaint')                                       # (the known region's noise would have to share s with the generated frames)
+        self._refuse('learned_variance', inpaint=True)
+        self._refuse('lowres_cond', inpaint=True)
+        self._refuse('frame_noise_alpha', inpaint=True)       # (the known region's noise would have to share s with the generated frames)
         if focus_present is not None:
             raise ValueError('inpaint / extend do not take focus_present (frame-conditioned sampling of a focus-present sample is out of scope)')
         opts = self._inpaint_options(video, dict(cond_scale=cond_scale, ddim_steps=ddim_steps, resample_steps=resample_steps, use_graph=use_graph,
@@ -1120,7 +1095,7 @@ class GaussianDiffusion:
             raise ValueError(f"resample_steps must be >= 1, got {o['resample_steps']}")
         if o['clean_context'] and int(o['resample_steps']) > 1:
             raise ValueError('clean_context keeps the known frames un-noised; resampling (resample_steps > 1) re-noises the whole tensor')
-        check_dpm_args(self.num_timesteps, dpm_steps, o['dpm_order'], ddim_steps, o['resample_steps'])
+        o['chain'], o['steps'] = chain_choice(self.num_timesteps, ddim_steps, dpm_steps, o['dpm_order'], o['resample_steps'])
         if ddim_steps and int(o['resample_steps']) > 1:
             raise ValueError('resampling (resample_steps > 1) is defined for the ancestral chain only, not with ddim_steps')
         shape = tuple(video.shape)
@@ -1129,24 +1104,7 @@ class GaussianDiffusion:
         if o['x_T'] is not None and tuple(o['x_T'].shape) != shape:
             raise ValueError(f"x_T must have the shape of video {shape}, got {tuple(o['x_T'].shape)}")
         o['resample_steps'] = int(o['resample_steps'])
-        o['chain'], o['steps'] = ('dpm', int(dpm_steps)) if dpm_steps is not None else ('ddim', int(ddim_steps)) if ddim_steps else ('ddpm', 0)
         return o
-
-    def _inpaint_bufs(self, B, steps):
-        """Device buffers of the masked loops, kept across calls of the same batch size: the captured step bakes their addresses
-        in, so a second call (another window of extend(), say) replays the cached graph when the seed is the same."""
-        key = (B, steps)
-        if getattr(self, '_ibuf_key', None) != key:
-            shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
-            dev = self.device
-            self._ibuf = dict(img=torch.empty(shape, device=dev), known=torch.empty(shape, device=dev),
-                              mask=torch.empty(shape, dtype=torch.uint8, device=dev),
-                              eps=torch.empty(B, self.num_frames, self.image_size, self.image_size, self.denoise_fn.out_dim, device=dev),
-                              t=torch.empty(B, dtype=torch.int32, device=dev), step=torch.zeros(1, dtype=torch.int64, device=dev),
-                              thres=torch.empty(B, device=dev),
-                              seq=None if not steps else torch.from_numpy(ddim_time_sequence(self.num_timesteps, steps)).to(dev))
-            self._ibuf_key = key
-        return self._ibuf
 
     def _inpaint_local(self, key, video, m, cond, *, chain, steps, cond_scale, resample_steps, use_graph, x_T, dpm_order, clean_context):
         """inpaint() on this rank's rows, with the options of _inpaint_options."""
@@ -1161,9 +1119,9 @@ class GaussianDiffusion:
         defaults to num_frames // 2).  Window keys: split_key(key, n_windows).  Returns [B,C,F0 + N,H,W]; its first F0 frames are
         `video` itself.  Data parallel as sample(): sharded once (rows and shard_key), not per window.  clean_context=True (with a
         frame-conditioned denoiser): every window keeps its context frames un-noised, see inpaint()."""
-        self._lv_refuse(extend=True)
-        self._sr_refuse(extend=True)
-        self._mix_refuse('extend')
+        self._refuse('learned_variance', extend=True)
+        self._refuse('lowres_cond', extend=True)
+        self._refuse('frame_noise_alpha', extend=True)
         ctx = self.num_frames // 2 if context_frames is None else int(context_frames)
         video = torch.as_tensor(video)
         if video.dim() != 5 or tuple(video.shape[1:2] + video.shape[3:]) != (self.channels, self.image_size, self.image_size):
@@ -1228,8 +1186,8 @@ class GaussianDiffusion:
         elements, sum / max(count, 1), formed on the device (vdx_loss_sum_masked)."""
         if self.loss_type not in ('l1', 'l2'):
             raise ValueError(f'Unsupported loss type: {self.loss_type}')
-        self._lv_refuse(frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
-        self._sr_refuse(frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
+        self._refuse('learned_variance', frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
+        self._refuse('lowres_cond', frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
         if self.lowres_cond is None and (lowres is not None or aug_levels is not None):
             raise ValueError('lowres / aug_levels need a super-resolution diffusion (lowres_cond=(ft, fs))')
         if self.lowres_cond is not None:
@@ -1243,34 +1201,53 @@ class GaussianDiffusion:
             _, noise_key, _ = split_key(key, 3)
             noise = self.noise(x_start.shape, noise_key, 0)
         noise = self._dev(noise)
-        if self.lowres_cond is not None:
-            # super-resolution: lowres defaults to the box mean of the raw clip; aug_levels to a draw from {0..lowres_aug_max-1} under
-            # lowres_aug_key(key) (none with lowres_aug_max = 0); the loss is the plain one over the C output channels
-            if is_list_str(cond):
-                raise NotImplementedError('pass text conditioning as a ready embedding tensor')
-            if aug_levels is None and self.lowres_aug_max > 0:
-                assert key is not None, 'A key must be provided to p_losses for the augmentation draw.'
-                aug_levels = lowres_aug_levels(x_start.shape[0], self.lowres_aug_max, lowres_aug_key(key))
-            xin = self.sr_input(x_start, t32, noise, lowres=lowres, aug_levels=aug_levels, key=lowres_aug_key(key) if key is not None else 0, _pre=_pre)
-            eps_hat = self.denoise_fn(xin, t32, cond=cond, **kwargs)
-            acc = torch.zeros(1, dtype=torch.float64, device=self.device)
-            L.check(vdx_loss_sum(L.ptr(eps_hat), L.ptr(noise), L.ptr(acc), x_start.shape[0], self.channels, self._per_sample(x_start) // self.channels,
-                                 int(self.loss_type == 'l2'), L.stream_ptr()))
-            return (acc / float(x_start.numel())).to(torch.float32).reshape(())
-        mk = None if frame_mask is None else self._dev_mask(frame_mask, x_start.shape)
-        x_noisy = self.q_sample(x_start, t32, noise=noise, frame_mask=mk, _pre=_pre)
         if is_list_str(cond):
             raise NotImplementedError('pass text conditioning as a ready embedding tensor')
+        mk = None if frame_mask is None else self._dev_mask(frame_mask, x_start.shape)
+        x_noisy, _ = self._net_input(x_start, t32, noise, mask=mk, lowres=lowres, aug_levels=aug_levels,
+                                     aug_key=None if key is None else lowres_aug_key(key), _pre=_pre)
         eps_hat = self.denoise_fn(x_noisy, t32, cond=cond, **kwargs)
-        if self.learned_variance:                                         # eps_hat | v -> the hybrid loss, the total as the value
-            return self.hybrid_loss(x_start, noise, eps_hat, t32, _pre=_pre)[0]
-        B = x_start.shape[0]
-        fhw = self._per_sample(x_start) // self.channels
-        if mk is not None:
-            return self.masked_loss(eps_hat, noise, mk)[0]
+        return self.loss_and_grad(eps_hat, x_start, noise, t32, mask=mk, _pre=_pre)[0]
+
+    def _net_input(self, x_start, t32, noise, *, mask=None, lowres=None, aug_levels=None, aug_key=None, _pre=(1.0, 0.0)):
+        """(network input, augmentation levels) of the objective, everything on the device: q_sample of x_start (masked with `mask`) or,
+        for a super-resolution diffusion, xin = [ x_t | aug(up(2 lowres - 1)) ] (sr_input): lowres defaults to the box mean of the raw
+        clip, aug_levels to a host draw from {0..lowres_aug_max-1} under aug_key (none with lowres_aug_max = 0), and the augmentation
+        noise is Philox(aug_key, draw 0)."""
+        if self.lowres_cond is None:
+            return self.q_sample(x_start, t32, noise=noise, frame_mask=mask, _pre=_pre), None
+        if aug_levels is None and self.lowres_aug_max > 0:
+            assert aug_key is not None, 'A key must be provided to p_losses for the augmentation draw.'
+            aug_levels = lowres_aug_levels(x_start.shape[0], self.lowres_aug_max, aug_key)
+        return self.sr_input(x_start, t32, noise, lowres=lowres, aug_levels=aug_levels, key=aug_key or 0, _pre=_pre), aug_levels
+
+    def loss_and_grad(self, eps_hat, x_start, noise, t32, *, mask=None, iw=None, want_grad: bool = False, _pre=(1.0, 0.0)):
+        """(loss, d_eps): the objective of the network output eps_hat as a float32 device scalar and, with want_grad, its gradient in
+        eps_hat (else None); the host reads nothing.  By what is on:
+          learned_variance  the hybrid loss of eps_hat | v (hybrid_loss: last_loss_terms, last_loss_per_sample; iw -> vdx_hybrid_loss_w)
+          mask              the mean over the mask-0 elements (masked_loss, vdx_loss_grad_masked: the count stays on the device)
+          iw                float64 [B] importance weights (loss-aware timestep sampling): the weighted mean and gradient from one
+                            vdx_loss_weighted pass; last_loss_per_sample = the unweighted per-sample losses
+          otherwise         the plain mean (vdx_loss_sum, vdx_loss_grad)"""
+        if self.learned_variance:
+            return self.hybrid_loss(x_start, noise, eps_hat, t32, want_grad=want_grad, _pre=_pre, iw=iw)
+        B, fhw, l2 = x_start.shape[0], self._per_sample(x_start) // self.channels, int(self.loss_type == 'l2')
+        if mask is None and iw is not None:
+            out, d_eps = TS.loss_weighted(eps_hat, noise, iw, l2=bool(l2), want_grad=want_grad)
+            self.last_loss_per_sample = out[:B]
+            return out[B].to(torch.float32).reshape(()), d_eps
+        d_eps = torch.empty_like(eps_hat) if want_grad else None
+        if mask is not None:
+            loss, acc = self.masked_loss(eps_hat, noise, mask)                # acc = device (sum, count | scratch)
+            if want_grad:
+                L.check(vdx_loss_grad_masked(L.ptr(eps_hat), L.ptr(noise), L.ptr(mask), acc.data_ptr() + 8, L.ptr(d_eps), B, self.channels,
+                                             fhw, l2, L.stream_ptr()))
+            return loss, d_eps
         acc = torch.zeros(1, dtype=torch.float64, device=self.device)
-        L.check(vdx_loss_sum(L.ptr(eps_hat), L.ptr(noise), L.ptr(acc), B, self.channels, fhw, int(self.loss_type == 'l2'), L.stream_ptr()))
-        return (acc / float(x_start.numel())).to(torch.float32).reshape(())
+        L.check(vdx_loss_sum(L.ptr(eps_hat), L.ptr(noise), L.ptr(acc), B, self.channels, fhw, l2, L.stream_ptr()))
+        if want_grad:
+            L.check(vdx_loss_grad(L.ptr(eps_hat), L.ptr(noise), L.ptr(d_eps), B, self.channels, fhw, l2, L.stream_ptr()))
+        return (acc / float(x_start.numel())).to(torch.float32).reshape(()), d_eps
 
     def masked_loss(self, eps_hat, noise, mk):
         """(loss, acc) of the masked objective: acc[0:2] = device doubles (sum, count) over the mask-0 elements (vdx_loss_sum_masked, the

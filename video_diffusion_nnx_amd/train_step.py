@@ -4,17 +4,17 @@ gradient all-reduce of finished buckets overlaps the rest of the backward.  Two 
 Trainer.apply_grad_args) K micro-batches and one tail with optional global-norm clipping."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import torch
 
 from . import _lib as L
-from .timestep_sampler import loss_weighted
-from .gaussian_diffusion import frame_mask as expand_frame_mask, lowres_aug_levels, split_key, vdx_loss_sum, vdx_q_sample
+from .gaussian_diffusion import _stage, frame_mask as expand_frame_mask, split_key
+# (bound next to the objective now; tests and tools import these three from here)
+from .gaussian_diffusion import vdx_loss_grad, vdx_loss_grad_masked, vdx_loss_sum  # noqa: F401
 
 _vp = C.c_void_p
-vdx_loss_grad = L._sig('vdx_loss_grad', C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_long, C.c_int, _vp])
-vdx_loss_grad_masked = L._sig('vdx_loss_grad_masked', C.c_int, [_vp] * 5 + [C.c_int, C.c_int, C.c_long, C.c_int, _vp])
 vdx_adam_ema_step = L._sig('vdx_adam_ema_step', C.c_int, [_vp] * 5 + [C.c_long] + [C.c_float] * 4 + [C.c_long, C.c_float, C.c_int, C.c_float, _vp])
 vdx_grad_accumulate = L._sig('vdx_grad_accumulate', C.c_int, [_vp, _vp, C.c_long, _vp])
 vdx_grad_sqnorm_scratch_doubles = L._sig('vdx_grad_sqnorm_scratch_doubles', C.c_size_t, [])
@@ -43,37 +43,50 @@ def stage_of_param(name: str, n_levels: int) -> int:
     raise KeyError(name)
 
 
-def micro_step_keys(rng_seed: int, rank: int, step: int, j: int = 0):
-    """(t_key, noise_key) of micro-step j of optimizer step `step`: one stream per (seed, rank), split per step like
-    `key, step_key = split(key)` (trainer.py:541).  j = 0 is the plain train step's pair; micro-step j >= 1 first moves to child 3 + j of
-    the step key (children 1-3 belong to the split below)."""
-    step_key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
+StepKeys = collections.namedtuple('StepKeys', 't noise frame_cond cond_drop focus_present lowres_aug')
+
+
+def step_keys(rng_seed: int, rank: int, step: int, j: int = 0) -> StepKeys:
+    """Every key of micro-step j of optimizer step `step`, one stream per (seed, rank), split per step like `key, step_key = split(key)`
+    (trainer.py:541) and then as the reference's `__call__` / `p_losses` split:
+
+        step key = split(split(rng_seed, rank + 1)[-1], step + 1)[-1]
+          j > 0: the micro-step key is child 3 + j of it (children 1-3 belong to the split below); j = 0: the step key itself
+          micro-step key -> child 1  frame_cond     the frame-conditioning mask draw (the child `_, t_key, loss_key` discards)
+                            child 2  t              the timesteps (the host randint, or draw 0 of the device sampler)
+                            child 3  loss key  ->   child 1  cond_drop      the condition-dropout draw
+                                                    child 2  noise          the Philox stream of q_sample's noise
+                                                    child 3  focus_present  the focus-present draw
+                                                    child 4  lowres_aug     the super-resolution augmentation (levels and noise)
+
+    split(key, n)[i] does not depend on n, so every draw has a child of its own: turning one feature on moves no other stream."""
+    key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
     if j > 0:
-        step_key = split_key(step_key, 3 + j)[-1]
-    _, t_key, loss_key = split_key(step_key, 3)
-    _, noise_key, _ = split_key(loss_key, 3)
-    return t_key, noise_key
+        key = split_key(key, 3 + j)[-1]
+    frame_cond, t, loss_key = split_key(key, 3)
+    cond_drop, noise, focus_present, lowres_aug = split_key(loss_key, 4)
+    return StepKeys(t, noise, frame_cond, cond_drop, focus_present, lowres_aug)
+
+
+def micro_step_keys(rng_seed: int, rank: int, step: int, j: int = 0):
+    """(t_key, noise_key) of step_keys."""
+    return tuple(step_keys(rng_seed, rank, step, j)[:2])
 
 
 def frame_cond_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
-    """Key of the frame-conditioning mask draw of micro-step j of optimizer step `step`: child 1 of the micro-step key, the child that
-    micro_step_keys' `_, t_key, loss_key = split(key, 3)` discards.  No other draw uses it (t and the noise hang off children 2 and 3,
-    the micro-steps j >= 1 off children 3 + j of the step key), so turning the masks on moves neither t nor the noise."""
-    step_key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
-    if j > 0:
-        step_key = split_key(step_key, 3 + j)[-1]
-    return split_key(step_key, 3)[0]
+    return step_keys(rng_seed, rank, step, j).frame_cond
 
 
 def cond_drop_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
-    """Key of the condition-dropout draw of micro-step j of optimizer step `step` (conditional training, classifier-free guidance): child
-    1 of the loss key, the first child that micro_step_keys' `_, noise_key, _ = split(loss_key, 3)` discards.  No other draw uses it (t
-    and the frame masks hang off the micro-step key, the noise off child 2 of the loss key), so turning the dropout on moves none of them."""
-    step_key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
-    if j > 0:
-        step_key = split_key(step_key, 3 + j)[-1]
-    loss_key = split_key(step_key, 3)[2]
-    return split_key(loss_key, 3)[0]
+    return step_keys(rng_seed, rank, step, j).cond_drop
+
+
+def focus_present_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
+    return step_keys(rng_seed, rank, step, j).focus_present
+
+
+def lowres_aug_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
+    return step_keys(rng_seed, rank, step, j).lowres_aug
 
 
 def cond_drop_mask(batch: int, p: float, generator=None) -> torch.Tensor:
@@ -82,30 +95,6 @@ def cond_drop_mask(batch: int, p: float, generator=None) -> torch.Tensor:
     if not 0.0 <= float(p) <= 1.0:
         raise ValueError(f'null_cond_prob must be in [0, 1], got {p}')
     return (torch.rand(int(batch), generator=generator) < float(p)).to(torch.uint8)
-
-
-def focus_present_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
-    """Key of the focus-present mask draw of micro-step j of optimizer step `step` (joint image-video training): child 3 of the loss key,
-    the last child that micro_step_keys' `_, noise_key, _ = split(loss_key, 3)` discards.  No other draw uses it (child 1 is the
-    condition dropout's, child 2 the noise's; t and the frame masks hang off the micro-step key), so turning the feature on moves none
-    of the t / noise / frame-mask / condition-dropout streams."""
-    step_key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
-    if j > 0:
-        step_key = split_key(step_key, 3 + j)[-1]
-    loss_key = split_key(step_key, 3)[2]
-    return split_key(loss_key, 3)[2]
-
-
-def lowres_aug_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
-    """Key of the super-resolution augmentation (the host draw of the levels and the Philox noise of the kernel) of micro-step j of
-    optimizer step `step`: child 4 of the loss key (gaussian_diffusion.lowres_aug_key of it).  Children 1-3 are the condition dropout's,
-    the noise's and the focus-present draw's; t and the frame masks hang off the micro-step key -- turning the augmentation on moves
-    none of those streams."""
-    step_key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
-    if j > 0:
-        step_key = split_key(step_key, 3 + j)[-1]
-    loss_key = split_key(step_key, 3)[2]
-    return split_key(loss_key, 4)[3]
 
 
 def focus_present_draw(batch: int, p: float, generator=None) -> torch.Tensor:
@@ -183,114 +172,69 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     B = x.shape[0]
     assert tuple(x.shape[1:]) == (gd.channels, gd.num_frames, gd.image_size, gd.image_size), \
         f'expected [b, {gd.channels}, {gd.num_frames}, {gd.image_size}, {gd.image_size}], got {tuple(x.shape)}'     # check_shape (:490)
-    t_key, noise_key = micro_step_keys(tr.rng_seed, tr.rank, step, j)
+    keys = step_keys(tr.rng_seed, tr.rank, step, j)
+    host_gen = lambda key: torch.Generator().manual_seed(key & 0x7FFFFFFFFFFFFFFF)
     smp = getattr(tr, 'sampler', None)
     if smp is not None and (frame_mask is not None or int(tr.frame_cond_max) > 0):
         raise ValueError('timestep_sampler=loss-second-moment does not serve frame-conditioned training (frame_mask / frame_cond_max): the '
                          'masked loss has no per-sample form')
     if t is None and smp is None:
-        g = torch.Generator().manual_seed(t_key & 0x7FFFFFFFFFFFFFFF)
-        t = torch.randint(0, gd.num_timesteps, (B,), generator=g, dtype=torch.int32)
-    t = None if t is None else torch.as_tensor(t)
-    if t is None:
-        pass
-    elif t.device.type == 'cpu' and dev.type == 'cuda':
-        # (pinned + non-blocking: a pageable host-to-device copy waits for the stream to drain -- one host sync per step that kept the
-        # launch queue from running ahead of the GPU)
-        t = t.to(torch.int32).pin_memory().to(dev, non_blocking=True)
-    else:
-        t = t.to(dev, torch.int32)
+        t = torch.randint(0, gd.num_timesteps, (B,), generator=host_gen(keys.t), dtype=torch.int32)
+    t = None if t is None else _stage(t, torch.int32, dev)
     iw = None
     if smp is not None:
-        # the device draw under the same t_key (draw 0) replaces the host randint; an explicit t only gets its weights
-        t, iw = smp.draw(B, t_key, 0, t=t)
+        # the device draw under the same t key (draw 0) replaces the host randint; an explicit t only gets its weights
+        t, iw = smp.draw(B, keys.t, 0, t=t)
     tr.last_iw = iw
-    noise = gd.noise(x.shape, noise_key, 0) if noise is None else torch.as_tensor(noise).to(dev, torch.float32).contiguous()
-    tr.last_t, tr.last_noise_key = t, noise_key
+    noise = gd.noise(x.shape, keys.noise, 0) if noise is None else torch.as_tensor(noise).to(dev, torch.float32).contiguous()
+    tr.last_t, tr.last_noise_key = t, keys.noise
     if frame_mask is None and int(tr.frame_cond_max) > 0:
-        g = torch.Generator().manual_seed(frame_cond_key(tr.rng_seed, tr.rank, step, j) & 0x7FFFFFFFFFFFFFFF)
-        frame_mask = frame_cond_masks(B, gd.num_frames, tr.frame_cond_max, tr.frame_cond_uncond_prob, tr.frame_cond_mode, g)
+        frame_mask = frame_cond_masks(B, gd.num_frames, tr.frame_cond_max, tr.frame_cond_uncond_prob, tr.frame_cond_mode, host_gen(keys.frame_cond))
     tr.last_frame_mask = frame_mask
-    mk = None
-    if frame_mask is not None:
-        fm = torch.as_tensor(frame_mask)
-        if fm.device.type == 'cpu' and dev.type == 'cuda':
-            fm = fm.pin_memory().to(dev, non_blocking=True)               # as t: no pageable copy, no host sync
-        mk = expand_frame_mask(fm.to(dev), tuple(x.shape))
+    mk = None if frame_mask is None else expand_frame_mask(_stage(frame_mask, None, dev), tuple(x.shape))
     cm = None
     if cond is not None:
-        cond = torch.as_tensor(cond)
-        if cond.device.type == 'cpu' and dev.type == 'cuda':
-            cond = cond.to(torch.float32).pin_memory().to(dev, non_blocking=True)
-        cond = cond.to(dev, torch.float32).contiguous()
+        cond = _stage(cond, torch.float32, dev)
         if cond_mask is None and float(tr.null_cond_prob) > 0:
-            g = torch.Generator().manual_seed(cond_drop_key(tr.rng_seed, tr.rank, step, j) & 0x7FFFFFFFFFFFFFFF)
-            cond_mask = cond_drop_mask(B, tr.null_cond_prob, g)
-        if cond_mask is not None:
-            cm = torch.as_tensor(cond_mask).to(torch.uint8)
-            if cm.device.type == 'cpu' and dev.type == 'cuda':
-                cm = cm.pin_memory().to(dev, non_blocking=True)           # as t: no pageable copy, no host sync
-            cm = cm.to(dev).contiguous()
+            cond_mask = cond_drop_mask(B, tr.null_cond_prob, host_gen(keys.cond_drop))
+        cm = None if cond_mask is None else _stage(cond_mask, torch.uint8, dev)
     tr.last_cond_mask = cond_mask if cond is not None else None
     fp = None
     if unet.focus_present:
         p_fp = float(getattr(tr, 'prob_focus_present', 0.0))
         if focus_present_mask is None and p_fp > 0:
-            g = torch.Generator().manual_seed(focus_present_key(tr.rng_seed, tr.rank, step, j) & 0x7FFFFFFFFFFFFFFF)
-            focus_present_mask = focus_present_draw(B, p_fp, g)
+            focus_present_mask = focus_present_draw(B, p_fp, host_gen(keys.focus_present))
         if focus_present_mask is not None:
             fp = torch.as_tensor(focus_present_mask).to(torch.uint8)
             if fp.shape != (B,):
                 raise ValueError(f'focus_present_mask must be [{B}], got {tuple(fp.shape)}')
             if p_fp >= 1 and fp.device.type == 'cpu' and bool(fp.all()):
                 fp = True                                                 # p = 1: every sample, the one-launch block (attention_present_kernel)
-            elif fp.device.type == 'cpu' and dev.type == 'cuda':
-                fp = fp.pin_memory().to(dev, non_blocking=True)           # as t: no pageable copy, no host sync
+            elif fp.device.type == 'cpu':
+                fp = _stage(fp, None, dev)
     tr.last_focus_mask = focus_present_mask if unet.focus_present else None
-    if gd.learned_variance:
-        gd._lv_refuse(frame_mask=frame_mask, focus_present=fp)
+    gd._refuse('learned_variance', frame_mask=frame_mask, focus_present=fp)
+    gd._refuse('lowres_cond', frame_mask=frame_mask, focus_present=fp)
     if gd.lowres_cond is None:
         if aug_levels is not None or lowres is not None:
             raise ValueError('aug_levels / lowres need a super-resolution diffusion (lowres_cond=(ft, fs))')
-        x_noisy = gd.q_sample(x, t, noise=noise, frame_mask=mk, _pre=(2.0, -1.0))     # normalize_img folded in (:499)
-    else:
-        gd._sr_refuse(frame_mask=frame_mask, focus_present=fp)
-        aug_key = lowres_aug_key(tr.rng_seed, tr.rank, step, j)
-        if aug_levels is None and gd.lowres_aug_max > 0:
-            aug_levels = lowres_aug_levels(B, gd.lowres_aug_max, aug_key)
+    elif lowres is not None:
+        gd._sr_lowres(lowres, B)
+    # the (masked) q_sample with normalize_img folded in (:499), or [ x_t | u ] of a super-resolution diffusion
+    x_noisy, aug_levels = gd._net_input(x, t, noise, mask=mk, lowres=lowres, aug_levels=aug_levels, aug_key=keys.lowres_aug, _pre=(2.0, -1.0))
+    if gd.lowres_cond is not None:
         tr.last_aug_levels = aug_levels
-        if lowres is not None:
-            gd._sr_lowres(lowres, B)
-        x_noisy = gd.sr_input(x, t, noise, lowres=lowres, aug_levels=aug_levels, key=aug_key, _pre=(2.0, -1.0))      # [ x_t | u ]
     keep_storage = unet.act_bf16
     unet.act_bf16 = 2 if (unet.mode == 'bf16' and tr.train_act_bf16) else False
     try:
         eps_hat = unet(x_noisy, t, cond=cond, cond_mask=cm, focus_present_mask=fp)
     finally:
         unet.act_bf16 = keep_storage
-    fhw = x.numel() // (B * gd.channels)
-    l2 = int(gd.loss_type == 'l2')
-    d_eps = None if (gd.learned_variance or smp is not None) else torch.empty_like(eps_hat)
-    if gd.learned_variance:
-        # eps_hat | v: the hybrid loss and its gradient in one pass (vdx_hybrid_loss); the returned loss is the total, gd.last_loss_terms
-        # keeps the device (mse, vb)
-        loss, d_eps = gd.hybrid_loss(x, noise, eps_hat, t, want_grad=True, _pre=(2.0, -1.0), iw=iw)
-        if smp is not None:
-            tr.last_loss_per_sample = gd.last_loss_per_sample[:, 0] + gd.vlb_weight * gd.last_loss_per_sample[:, 1]
-    elif mk is not None:
-        loss, acc = gd.masked_loss(eps_hat, noise, mk)                            # acc = device (sum, count | scratch)
-        L.check(vdx_loss_grad_masked(L.ptr(eps_hat), L.ptr(noise), L.ptr(mk), acc.data_ptr() + 8, L.ptr(d_eps), B, gd.channels, fhw, l2,
-                                     L.stream_ptr()))
-    elif smp is not None:
-        # the per-sample losses, the weighted mean (what is optimised) and the weighted gradient in one pass (vdx_loss_weighted)
-        out, d_eps = loss_weighted(eps_hat, noise, iw, l2=bool(l2), want_grad=True)
-        loss = out[B].to(torch.float32).reshape(())
-        tr.last_loss_per_sample = out[:B]
-    else:
-        acc = torch.zeros(1, dtype=torch.float64, device=dev)
-        L.check(vdx_loss_sum(L.ptr(eps_hat), L.ptr(noise), L.ptr(acc), B, gd.channels, fhw, l2, L.stream_ptr()))
-        loss = (acc / float(x.numel())).to(torch.float32).reshape(())
-        L.check(vdx_loss_grad(L.ptr(eps_hat), L.ptr(noise), L.ptr(d_eps), B, gd.channels, fhw, l2, L.stream_ptr()))
+    # the loss (the returned one is what is optimised: the hybrid total, the masked mean, the weighted mean) and its gradient in eps_hat
+    loss, d_eps = gd.loss_and_grad(eps_hat, x, noise, t, mask=mk, iw=iw, want_grad=True, _pre=(2.0, -1.0))
+    if smp is not None:
+        per = gd.last_loss_per_sample                                     # hybrid: the per-sample (mse, vb) pairs
+        tr.last_loss_per_sample = per[:, 0] + gd.vlb_weight * per[:, 1] if gd.learned_variance else per
     if reducer is None:
         unet.backward(d_eps, grads)
         _sampler_update(tr, t)
@@ -384,9 +328,8 @@ def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, n
     (forward_backward).  aug_levels / lowres: the shard's augmentation levels and low-resolution clips of a super-resolution diffusion
     (forward_backward)."""
     reducer = tr.make_reducer()
-    sr_kw = {} if (aug_levels is None and lowres is None) else dict(aug_levels=aug_levels, lowres=lowres)
     loss = forward_backward(tr, batch, step, t, noise, reducer=reducer, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask,
-                            focus_present_mask=focus_present_mask, **sr_kw)
+                            focus_present_mask=focus_present_mask, aug_levels=aug_levels, lowres=lowres)
     reducer.finish()
     optimizer_tail(tr, step, reducer.world)
     return loss
@@ -404,26 +347,17 @@ def run_train_step_accum(tr, batches, step: int, ts=None, noises=None, frame_mas
     list of K focus-present masks (forward_backward)."""
     K = len(batches)
     assert K >= 1
-    ts = [None] * K if ts is None else ts
-    noises = [None] * K if noises is None else noises
-    fms = [None] * K if frame_masks is None else frame_masks
-    cds = [None] * K if conds is None else conds
-    cms = [None] * K if cond_masks is None else cond_masks
-    fps = [None] * K if focus_present_masks is None else focus_present_masks
+    ts, noises, fms, cds, cms, fps = ([None] * K if v is None else v for v in (ts, noises, frame_masks, conds, cond_masks, focus_present_masks))
     if K > 1 and getattr(tr, 'micro_grads', None) is None:
         tr.micro_grads = torch.zeros_like(tr.grads)
     reducer = tr.make_reducer()
     losses = []
     for j in range(K):
         grads = tr.grads if j == 0 else tr.micro_grads
-        if j < K - 1:
-            losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, frame_mask=fms[j], cond=cds[j],
-                                           cond_mask=cms[j], focus_present_mask=fps[j]))
-            if j > 0:
-                L.check(vdx_grad_accumulate(L.ptr(tr.grads), L.ptr(grads), grads.numel(), L.stream_ptr()))
-        else:
-            losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, reducer=reducer, frame_mask=fms[j],
-                                           cond=cds[j], cond_mask=cms[j], focus_present_mask=fps[j]))
+        losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, reducer=reducer if j == K - 1 else None,
+                                       frame_mask=fms[j], cond=cds[j], cond_mask=cms[j], focus_present_mask=fps[j]))
+        if 0 < j < K - 1:
+            L.check(vdx_grad_accumulate(L.ptr(tr.grads), L.ptr(grads), grads.numel(), L.stream_ptr()))
     reducer.finish()
     max_norm = tr.max_grad_norm
     optimizer_tail(tr, step, reducer.world, accum=K, max_grad_norm=max_norm, want_norm=tr.track_grad_norm)
