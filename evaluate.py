@@ -7,7 +7,8 @@ curves (GaussianDiffusion.calc_bpd_loop; an extension, the reference has no eval
 --no-clip, --cond-path FILE.npy (float32 [N, cond_dim], row i the condition of video i), --output FILE.json.
 Writes one JSON document: total_bpd and prior_bpd (means over the videos; total_bpd is null with --eval-steps below T), the length-S
 arrays t, vb, mse and xstart_mse (means over the videos), num_videos, mode and seed.  One process: the evaluation is not sharded.
-A config with diffusion.frame_noise_alpha > 0 (the mixed noise prior) is refused: the bound under a frame-correlated prior is a follow-up."""
+A config with diffusion.frame_noise_alpha > 0 (the mixed noise prior) is refused: the bound under a frame-correlated prior is a follow-up.
+A config with diffusion.objective: pred_v evaluates a v-predicting network: the loop converts its output to eps_hat behind every forward."""
 import argparse
 import json
 import logging

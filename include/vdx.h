@@ -799,6 +799,46 @@ int vdx_p_sample_loop_mixed(vdx_handle* h, const float* params, const void* pack
                             int clip_denoised, float percentile, float* thres_buf, float cond_scale, float rescale, double* cfg_scratch,
                             float a, float b, void* workspace, size_t workspace_bytes, int batch, int use_graph, void* stream);
 
+/* v-prediction (EXTENSION, parity unpinned: no reference code.  Salimans & Ho 2022, "Progressive Distillation", appendix D; the loss
+ * weights: Hang et al. 2023, min-SNR-gamma).  Off unless these entries are called.  The network predicts
+ *   v = sqrt(ac_t) eps - sqrt(1 - ac_t) x0,   and exactly   eps = sqrt(ac_t) v + sqrt(1 - ac_t) x_t,   x0 = sqrt(ac_t) x_t - sqrt(1 - ac_t) v.
+ * One conversion point: the network output is overwritten with eps_hat by one streaming launch directly behind the forward; every step
+ * kernel, the dynamic threshold, vdx_cfg_combine and the bits/dim terms take eps_hat as they always did.  No atomics in these kernels and
+ * every sum in a fixed order.
+ *
+ * vdx_v_to_eps: out [rows][F,H,W,C] (channel-last, the network's v_hat) is overwritten with eps_hat; x [rows][C,F,H,W] = x_t; t [rows]
+ *   int32 (a level outside [0, timesteps) reads the nearest one).  Per element eps_hat = fl(fl(sa v) + fl(s1 x)) with sa = sqrt_ac[t_b],
+ *   s1 = sqrt_1mac[t_b]: no fused multiply-add, so fp32 `sa * v + s1 * x` restates it bit for bit.  Fixed grid, four elements per thread,
+ *   tails guarded: any per_sample that is a multiple of channels, any alignment (the float4 forms only where per_sample % 4 == 0 and
+ *   the bases are 16-byte aligned).  Refused before any launch (VDX_ERR_INVALID): a NULL tensor, rows, channels, timesteps or
+ *   per_sample < 1, per_sample % channels != 0.
+ * vdx_v_loss: the loss of the network output `out` (channel-last [batch,F,H,W,C]) per sample, with a weight per level, and its gradient
+ *   in ONE pass (vdx_loss_weighted's shape: per-workgroup partials in double, a fixed-order tree, an in-order final).
+ *     kind 1: target = fl(fl(sa noise) - fl(s1 x0n)), x0n = fma(x0, pre_scale, pre_shift) as vdx_q_sample forms it (x0, noise [batch,C,F,H,W])
+ *     kind 0: target = noise (x0, the tables and the pre_* are not read): min-SNR weighting of the eps objective
+ *   d = out - target in fp32, |d| (l2 == 0) or d^2 added in double.  w_b = wtab[t_b] (double [timesteps]; NULL: 1), g_b = iw[b] w_b
+ *   (iw double [batch]; NULL: 1).  result [batch + 1] doubles: result[b] = w_b (mean of sample b), result[batch] = (1 / batch) sum_b
+ *   iw_b result[b].  d_out (may be NULL) = l2 ? 2.0f d f_b : sign(d) f_b with f_b = (float)g_b * inv_count, inv_count the float
+ *   vdx_loss_grad uses: kind 0 with wtab NULL gives vdx_loss_weighted's result and gradient bit for bit.  t may be NULL with kind 0 and
+ *   wtab NULL.  scratch: vdx_v_loss_scratch_doubles(batch) doubles.  Any channels * fhw.  Refused before any launch (VDX_ERR_INVALID):
+ *   a kind other than 0 / 1, a NULL out / noise / scratch / result, kind 1 without x0 or a table, levels (kind 1 or wtab) without t or
+ *   with timesteps < 1, a size < 1, doubles off 8 bytes.
+ * vdx_set_prediction: what the handle's network predicts, for the loops: kind 0 = eps (always accepted; clears the tables), kind 1 = v
+ *   with the caller's device tables sqrt_ac | sqrt_1mac [timesteps] floats (they must outlive the setting).  With kind 1 the step of
+ *   every vdx_*_sample_loop* entry and of vdx_vlb_loop launches vdx_v_to_eps's kernel over the rows of the forward (2 batch under
+ *   guidance, before vdx_cfg_combine: guidance and its rescale act on eps_hat) directly behind it, with x = img (xt_buf) and t = t_dev.
+ *   kind and the two pointers are part of every loop's graph key: a change re-captures, no graph is evicted for it.  VDX_ERR_INVALID:
+ *   another kind, kind 1 without a table or with timesteps < 1.  vdx_p_sample_loop_lv and vdx_vlb_loop_lv return VDX_ERR_STATE while
+ *   kind 1 is set, before any launch.  Like the other handle settings it needs no GPU. */
+int vdx_v_to_eps(float* out, const float* x, const int* t, const float* sqrt_ac, const float* sqrt_1mac, int timesteps, int rows, int channels,
+                 long per_sample, void* stream);
+size_t vdx_v_loss_scratch_doubles(int batch);
+int vdx_v_loss(const float* out, const float* x0, const float* noise, const int* t, const float* sqrt_ac, const float* sqrt_1mac,
+               const double* wtab, const double* iw, int timesteps, int kind, float pre_scale, float pre_shift, int l2, float* d_out,
+               double* scratch, double* result, int batch, int channels, long fhw, void* stream);
+int vdx_set_prediction(vdx_handle* h, int kind, const float* sqrt_ac, const float* sqrt_1mac, int timesteps);
+int vdx_get_prediction(const vdx_handle* h);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */

@@ -13,7 +13,9 @@ float32 [B, cond_dim] file are the batch; needs a config with use_bert_text_cond
 [0,1], beside the gifs: what a second stage reads with --lowres-path); --frame-noise-alpha A (or diffusion.frame_noise_alpha: A in the
 YAML, absent = 0: the mixed noise prior of "Preserve Your Own Correlation" -- x_T and the ancestral steps' noise share a component across
 the frames of a clip, correlation A^2 / (1 + A^2); for checkpoints trained with train.py --frame_noise_alpha A; works with --ddim-steps,
---dpm-steps and --cond-path, not with --context, learned-variance or super-resolution configs)."""
+--dpm-steps and --cond-path, not with --context, learned-variance or super-resolution configs); --objective pred_v (or diffusion.objective:
+pred_v in the YAML, absent = pred_noise: the network predicts v = sqrt(ac) eps - sqrt(1 - ac) x0; for checkpoints trained with train.py
+--objective pred_v; works with every sampler and option above except learned-variance configs)."""
 import argparse
 import logging
 import os
@@ -64,10 +66,14 @@ FLAGS = (   # (flag, kwargs)
     ('--frame-noise-alpha', dict(type=float, default=None, help='mixed noise prior: the noise of a clip\'s frames shares a component, correlation '
                                                                 'A^2 / (1 + A^2) (overrides diffusion.frame_noise_alpha in the YAML; 0 = i.i.d.; for '
                                                                 'checkpoints trained with it; not stored in checkpoints); not with --context')),
+    ('--objective', dict(choices=('pred_noise', 'pred_v'), default=None, help='what the network predicts (overrides diffusion.objective in the '
+                                                                              'YAML; pred_v for checkpoints trained with it; not stored in '
+                                                                              'checkpoints)')),
 )
 
 
-def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=False, focus_present=False, frame_noise_alpha=None):
+def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=False, focus_present=False, frame_noise_alpha=None,
+                 objective=None, min_snr_gamma=None):
     """temporal_pos_bias: the command-line flag; the YAML's unet.temporal_pos_bias (absent = false) switches it on as well.  An architecture
     argument like dim: checkpoints do not store it, so a model trained with it is sampled with it.  focus_present: the same for the
     focus-present switch (unet.focus_present in the YAML, absent = false).  diffusion.learned_variance (absent = false; optionally with
@@ -77,7 +83,10 @@ def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=Fa
     the diffusion lowres_cond=(ft, fs), lowres_aug_max=L (aug_max absent = 0); again the conv shapes are what a checkpoint stores.
     diffusion.frame_noise_alpha: A (absent = 0 = off; the keyword, the command-line flag, overrides it): the mixed noise prior of
     GaussianDiffusion(frame_noise_alpha=A) for training and sampling.  Checkpoints do not store it, and no shape depends on it: a model
-    trained with it is sampled with the same A."""
+    trained with it is sampled with the same A.  diffusion.objective: pred_noise | pred_v and diffusion.min_snr_gamma: gamma (absent = off; the
+    keywords, the command-line flags, override them): what the network predicts and the min-SNR loss weighting of
+    GaussianDiffusion(objective=..., min_snr_gamma=gamma).  Checkpoints do not store them either: a model trained to predict v is sampled
+    with objective pred_v."""
     from video_diffusion_nnx_amd.gaussian_diffusion import GaussianDiffusion
     from video_diffusion_nnx_amd.unet3d import Rngs, Unet3D
     u, d = cfg['unet'], cfg['diffusion']
@@ -87,13 +96,16 @@ def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=Fa
     sr_kw = dict(lowres_cond=(sr['temporal'], sr['spatial']), lowres_aug_max=sr.get('aug_max', 0)) if sr else {}
     fa = d.get('frame_noise_alpha', 0) if frame_noise_alpha is None else frame_noise_alpha
     fa_kw = dict(frame_noise_alpha=fa) if (fa or isinstance(fa, bool)) else {}       # (0 takes the constructor's default: nothing new is passed)
+    ob = d.get('objective') if objective is None else objective
+    mg = d.get('min_snr_gamma') if min_snr_gamma is None else min_snr_gamma
+    ob_kw = dict(**(dict(objective=ob) if ob is not None else {}), **(dict(min_snr_gamma=mg) if mg is not None else {}))
     unet = Unet3D(**(dict(out_dim=2 * u['channels']) if lv else dict(out_dim=u['channels']) if sr else {}), dim=u['dim'], rngs=Rngs(u['rngs_seed']),
                   dim_mults=tuple(u['dim_mults']), channels=(2 if sr else 1) * u['channels'],
                   use_bert_text_cond=u['use_bert_text_cond'], mode=mode, attn_fp8=attn_fp8,
                   temporal_pos_bias=bool(temporal_pos_bias or u.get('temporal_pos_bias', False)),
                   focus_present=bool(focus_present or u.get('focus_present', False)))
     gd = GaussianDiffusion(denoise_fn=unet, image_size=d['image_size'], num_frames=d['num_frames'], channels=d['channels'],
-                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'], **lv_kw, **sr_kw, **fa_kw)
+                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'], **lv_kw, **sr_kw, **fa_kw, **ob_kw)
     return unet, gd
 
 
@@ -206,9 +218,10 @@ def _run(a, ap, rank, world):
     try:
         unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8, temporal_pos_bias=a.temporal_pos_bias,
                                 **(dict(focus_present=True) if a.focus_present else {}),
-                                **(dict(frame_noise_alpha=a.frame_noise_alpha) if a.frame_noise_alpha is not None else {}))
+                                **(dict(frame_noise_alpha=a.frame_noise_alpha) if a.frame_noise_alpha is not None else {}),
+                                **(dict(objective=a.objective) if a.objective is not None else {}))
     except ValueError as e:
-        if 'frame_noise_alpha' not in str(e):
+        if not any(w in str(e) for w in ('frame_noise_alpha', 'objective', 'min_snr_gamma')):
             raise
         ap.error(str(e))
     if gd.frame_noise_alpha and a.context:

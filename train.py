@@ -24,7 +24,11 @@ sample's loss is weighted by 1 / (T p_t); uniform until every level has H losses
 cold; not with --frame_cond_max);
 --frame_noise_alpha A (or diffusion.frame_noise_alpha: A in the YAML, absent = 0: train under the mixed noise prior of "Preserve Your Own
 Correlation" -- the noise of a clip's frames shares a component, correlation A^2 / (1 + A^2); nothing else in the step changes; not stored
-in checkpoints: sample with sample.py --frame-noise-alpha A or the same YAML key; not with learned-variance or super-resolution configs)."""
+in checkpoints: sample with sample.py --frame-noise-alpha A or the same YAML key; not with learned-variance or super-resolution configs);
+--objective pred_v [--min_snr_gamma 5] (or diffusion.objective / diffusion.min_snr_gamma in the YAML, absent = pred_noise, unweighted: the
+network is trained to predict v = sqrt(ac) eps - sqrt(1 - ac) x0, and with gamma a sample's loss at level t is weighted with the min-SNR
+weight min(SNR_t, gamma) / (SNR_t + 1) -- for pred_noise min(SNR_t, gamma) / SNR_t; not stored in checkpoints: sample with sample.py
+--objective pred_v or the same YAML key; not with learned-variance configs or --frame_cond_max)."""
 import argparse
 import logging
 import os
@@ -60,6 +64,10 @@ FLAGS = (
     ('--frame_noise_alpha', dict(type=float, default=None, help='mixed noise prior: the training noise of a clip\'s frames shares a component, '
                                                                 'correlation A^2 / (1 + A^2) (overrides diffusion.frame_noise_alpha in the YAML; '
                                                                 '0 = i.i.d.; not stored in checkpoints)')),
+    ('--objective', dict(choices=('pred_noise', 'pred_v'), default=None, help='what the network is trained to predict (overrides '
+                                                                              'diffusion.objective in the YAML; not stored in checkpoints)')),
+    ('--min_snr_gamma', dict(type=float, default=None, help='min-SNR-gamma loss weighting, gamma > 0 (5 is the usual choice; overrides '
+                                                            'diffusion.min_snr_gamma in the YAML; absent = unweighted)')),
 )
 
 
@@ -89,9 +97,18 @@ def main(argv=None):
     # (the keyword only when the flag is given: callers that replace build_models with a (cfg, mode) function keep working)
     if a.frame_noise_alpha is not None and not (0.0 <= a.frame_noise_alpha < float('inf')):
         ap.error(f'--frame_noise_alpha must be a finite number >= 0, got {a.frame_noise_alpha}')
-    _, gd = build_models(cfg, a.mode, **(dict(temporal_pos_bias=True) if a.temporal_pos_bias else {}),
-                         **(dict(focus_present=True) if a.focus_present else {}),
-                         **(dict(frame_noise_alpha=a.frame_noise_alpha) if a.frame_noise_alpha is not None else {}))
+    if a.min_snr_gamma is not None and not (0.0 < a.min_snr_gamma < float('inf')):
+        ap.error(f'--min_snr_gamma must be a finite number > 0, got {a.min_snr_gamma}')
+    try:
+        _, gd = build_models(cfg, a.mode, **(dict(temporal_pos_bias=True) if a.temporal_pos_bias else {}),
+                             **(dict(focus_present=True) if a.focus_present else {}),
+                             **(dict(frame_noise_alpha=a.frame_noise_alpha) if a.frame_noise_alpha is not None else {}),
+                             **(dict(objective=a.objective) if a.objective is not None else {}),
+                             **(dict(min_snr_gamma=a.min_snr_gamma) if a.min_snr_gamma is not None else {}))
+    except ValueError as e:
+        if not any(w in str(e) for w in ('objective', 'min_snr_gamma')):
+            raise
+        ap.error(str(e))
     tc = dict(cfg['trainer'])
     p_fp = tc.pop('prob_focus_present', None)        # (a Trainer attribute, not a constructor argument)
     if a.prob_focus_present is not None:

@@ -168,3 +168,10 @@ vdx_p_sample_step_mixed = _sig('vdx_p_sample_step_mixed', c_int, [c_void_p] * 5 
                                                                   c_int, c_long, c_void_p])
 vdx_p_sample_loop_mixed = _sig('vdx_p_sample_loop_mixed', c_int, [c_void_p] * 8 + [c_int, c_int, c_void_p, _u64, c_int, c_float, c_void_p, c_float, c_float,
                                                                   c_void_p, c_float, c_float, c_void_p, c_size_t, c_int, c_int, c_void_p])
+
+# v-prediction (vdx.h: "v-prediction"): the conversion behind the forward, the weighted loss pass and the handle's prediction state
+vdx_v_to_eps = _sig('vdx_v_to_eps', c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_long, c_void_p])
+vdx_v_loss_scratch_doubles = _sig('vdx_v_loss_scratch_doubles', c_size_t, [c_int])
+vdx_v_loss = _sig('vdx_v_loss', c_int, [c_void_p] * 8 + [c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p])
+vdx_set_prediction = _sig('vdx_set_prediction', c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int])
+vdx_get_prediction = _sig('vdx_get_prediction', c_int, [c_void_p])

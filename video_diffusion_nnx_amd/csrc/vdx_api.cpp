@@ -33,8 +33,8 @@ struct vdx_handle {
     vdx::Model model;
     // the key of a captured sampling step: the LoopArgs of the call with every field its step does not read set to zero (sample_loop()),
     // the stream and the activation storage.  Full pointers: two workspaces / streams never alias one key.  Compared with memcmp, so it
-    // is zero-filled before the fields are assigned
-    struct GraphKey { LoopArgs a; const void* stream; int act16; };
+    // is zero-filled before the fields are assigned.  pred / pred_sa / pred_s1: the prediction the step converts (vdx_set_prediction)
+    struct GraphKey { LoopArgs a; const void* stream; int act16; int pred; const float* pred_sa; const float* pred_s1; };
     // one cached graph per (chain, variant): slot = 3 * variant + chain with variant 0 = plain, 1 = masked, 2 = guided and chain 0 = the
     // ancestral loop, 1 = DDIM, 2 = DPM-Solver++; slot 9 = the evaluation loop (vdx_vlb_loop), 10 / 11 = the learned-variance sampling and
     // evaluation loops, 12 + chain = the super-resolution loops (vdx_*_sample_loop_sr), 15 / 16 = the plain and the guided mixed-noise
@@ -50,6 +50,9 @@ struct vdx_handle {
         }
     } gs[17];
     void drop_graphs() { for (GraphSlot& g : gs) g.drop(); }
+    // what the network predicts (vdx_set_prediction): 0 = eps, 1 = v with the caller's device tables sqrt(ac) | sqrt(1 - ac) [pred_T]
+    int pred = 0; const float* pred_sa = nullptr; const float* pred_s1 = nullptr; int pred_T = 0;
+    void key_prediction(GraphKey& k) const { k.pred = pred; k.pred_sa = pred_sa; k.pred_s1 = pred_s1; }
     vdx::BwdState bwd;
     vdx::Comm comm;
 };
@@ -622,6 +625,16 @@ int vdx_set_focus_present(vdx_handle* h, int mode, const unsigned char* mask_dev
 }
 int vdx_get_focus_present(const vdx_handle* h) { return h ? h->model.focus : 0; }
 
+int vdx_set_prediction(vdx_handle* h, int kind, const float* sqrt_ac, const float* sqrt_1mac, int timesteps) {
+    if (!h) VDX_FAIL(VDX_ERR_INVALID, "set_prediction: null handle");
+    if (kind != 0 && kind != 1) VDX_FAIL(VDX_ERR_INVALID, "set_prediction: kind 0 (eps) or 1 (v)");
+    if (kind == 1 && (!sqrt_ac || !sqrt_1mac || timesteps < 1)) VDX_FAIL(VDX_ERR_INVALID, "set_prediction: kind 1 needs both tables and timesteps >= 1");
+    // (no graph is dropped: kind and the two pointers are part of every loop's graph key, so a change re-captures)
+    h->pred = kind; h->pred_sa = kind ? sqrt_ac : nullptr; h->pred_s1 = kind ? sqrt_1mac : nullptr; h->pred_T = kind ? timesteps : 0;
+    return VDX_OK;
+}
+int vdx_get_prediction(const vdx_handle* h) { return h ? h->pred : 0; }
+
 int vdx_param_count(const vdx_handle* h) { return h ? (int)h->model.params.size() : 0; }
 long vdx_param_total(const vdx_handle* h) { return h ? h->model.param_total : 0; }
 
@@ -868,7 +881,8 @@ static bool in_unit_interval(float x) {
 }
 
 // The step of every loop, launch for launch: (guided: copy img[:B] -> img[B:]) -> (super-resolution, a.xin: lowres_pack img -> the
-// first half of xin, the forward then reads xin) -> model_forward over B samples (guided: 2B, the second half with the null embedding) -> (guided: cfg_combine) -> (dynamic threshold) -> the chain's step kernel on B samples -> the chain's
+// first half of xin, the forward then reads xin) -> model_forward over B samples (guided: 2B, the second half with the null embedding) ->
+// (v-prediction, vdx_set_prediction kind 1: v_to_eps over the forward's rows, in place on eps_buf, x = img) -> (guided: cfg_combine) -> (dynamic threshold) -> the chain's step kernel on B samples -> the chain's
 // advance (guided: over 2B).  Mixed noise (a.mix_a / a.mix_b, the ancestral chain only): p_sample_mixed_kernel is that step kernel.
 // Validates, derives the graph key from `a` and runs nsteps steps eagerly or as replays of one captured step.
 // Guided loops (classifier-free guidance; EXTENSION, parity unpinned: the reference's p_sample_loop drops cond): img / t_dev / eps_buf /
@@ -931,7 +945,9 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
         if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
         int rc = vdx::model_forward(&m, a.params, a.packed, sr ? a.xin : a.img, a.t_dev, a.cond, cond_mask, 0, a.eps_buf, a.workspace, a.workspace_bytes, rows, st);
         if (rc != VDX_OK) return rc;
-        if (guided) e = vdx::launch_cfg_combine(a.eps_buf, a.eps_buf, a.cond_scale, a.rescale, a.cfg_scratch, B, per_sample, st);
+        // v-prediction: the output becomes eps_hat before anything reads it (both halves of a guided batch: guidance acts on eps_hat)
+        if (h->pred) e = vdx::launch_v_to_eps(a.eps_buf, a.img, a.t_dev, h->pred_sa, h->pred_s1, h->pred_T, rows, C, per_sample, st);
+        if (e == hipSuccess && guided) e = vdx::launch_cfg_combine(a.eps_buf, a.eps_buf, a.cond_scale, a.rescale, a.cfg_scratch, B, per_sample, st);
         if (e == hipSuccess && dyn) e = vdx::launch_dyn_thres(a.img, a.eps_buf, a.t_dev, a.tables, a.timesteps, a.percentile, a.thres_buf, B, C, per_sample, st);
         if (anc) {
             const vdx::PSampleArgs pa = psample_args(a.img, a.eps_buf, a.img, a.t_dev, a.tables, a.timesteps, nullptr, a.seed, masked ? 0 : 1,
@@ -956,7 +972,7 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
     vdx_handle::GraphKey key;
     memset(&key, 0, sizeof(key));
     memcpy(&key.a, &a, sizeof(a));
-    key.stream = stream; key.act16 = m.act16;
+    key.stream = stream; key.act16 = m.act16; h->key_prediction(key);
     LoopArgs& k = key.a;
     if (!dyn) { k.percentile = 0.f; k.thres_buf = nullptr; }
     if (anc) { k.alphas_cumprod = nullptr; k.seq = nullptr; k.seq_len = 0; }
@@ -1266,6 +1282,7 @@ static int vlb_loop(const char* who, bool lv, vdx_handle* h, const float* params
                     int use_graph, void* stream) {
     if (!h || !params || !packed || !x || !xt_buf || !eps_buf || !t_dev || !step_dev || !vlb_tables || !seq || !partial || !out || !workspace)
         VDX_REFUSE(who, "null argument");
+    if (lv && h->pred) { char msg_[128]; snprintf(msg_, sizeof(msg_), "%s: v-prediction (vdx_set_prediction) has no learned-variance form", who); VDX_FAIL(VDX_ERR_STATE, msg_); }
     if (!h->model.d_ss_layers) { char msg_[96]; snprintf(msg_, sizeof(msg_), "%s: handle was created without a GPU", who); VDX_FAIL(VDX_ERR_STATE, msg_); }
     const vdx::Model& m = h->model;
     const int C = m.cfg.channels;
@@ -1285,7 +1302,8 @@ static int vlb_loop(const char* who, bool lv, vdx_handle* h, const float* params
         // cond is used un-masked, as in the unguided sampling loops
         int rc = vdx::model_forward(&m, params, packed, xt_buf, t_dev, cond, nullptr, 0, eps_buf, workspace, workspace_bytes, batch, st);
         if (rc != VDX_OK) return rc;
-        e = lv ? vdx::launch_vlb_terms_lv(ta, batch, st) : vdx::launch_vlb_terms(ta, batch, st);
+        if (h->pred) e = vdx::launch_v_to_eps(eps_buf, xt_buf, t_dev, h->pred_sa, h->pred_s1, h->pred_T, batch, C, per_sample, st);      // (never with lv)
+        if (e == hipSuccess) e = lv ? vdx::launch_vlb_terms_lv(ta, batch, st) : vdx::launch_vlb_terms(ta, batch, st);
         if (e == hipSuccess) e = vdx::launch_vlb_advance(partial, out, 3, batch, per_sample, t_dev, seq, seq_len, sd, st);
         if (e != hipSuccess) return vdx_set_error(VDX_ERR_HIP, hipGetErrorString(e), __FILE__, __LINE__);
         return VDX_OK;
@@ -1298,7 +1316,7 @@ static int vlb_loop(const char* who, bool lv, vdx_handle* h, const float* params
     k.timesteps = timesteps; k.seq = seq; k.seq_len = seq_len; k.cond = cond; k.seed = seed; k.clip_denoised = clip_denoised ? 1 : 0;
     k.vlb_x = x; k.vlb_tables = vlb_tables; k.vlb_partial = partial; k.vlb_out = out;
     k.workspace = workspace; k.workspace_bytes = workspace_bytes; k.batch = batch;
-    key.stream = stream; key.act16 = m.act16;
+    key.stream = stream; key.act16 = m.act16; h->key_prediction(key);
     return run_steps(h, lv ? 11 : 9, key, nsteps, use_graph, st, step);
 }
 
@@ -1352,6 +1370,7 @@ int vdx_p_sample_loop_lv(vdx_handle* h, const float* params, const void* packed,
                          int use_graph, void* stream) {
     const char* who = "p_sample_loop_lv";
     if (!h || !params || !packed || !img || !out2_buf || !t_dev || !step_dev || !lv_tables || !seq || !workspace) VDX_REFUSE(who, "null argument");
+    if (h->pred) VDX_FAIL(VDX_ERR_STATE, "p_sample_loop_lv: v-prediction (vdx_set_prediction) has no learned-variance form");
     const vdx::Model& m = h->model;
     const int C = m.cfg.channels;
     const long per_sample = (long)C * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
@@ -1458,6 +1477,39 @@ int vdx_loss_weighted(const float* eps_hat, const float* noise, const double* iw
     if (batch < 1 || channels < 1 || fhw < 1) VDX_REFUSE(who, "batch, channels and fhw must be >= 1");
     if ((uintptr_t)iw % 8 || (uintptr_t)scratch % 8 || (uintptr_t)out % 8) VDX_REFUSE(who, "iw / scratch / out must be 8-byte aligned");
     VDX_HIP(vdx::launch_loss_weighted(eps_hat, noise, iw, d_eps_hat, scratch, out, batch, channels, fhw, l2 ? 1 : 0, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+// ---- v-prediction (vdx.h: "v-prediction") ----
+
+int vdx_v_to_eps(float* out, const float* x, const int* t, const float* sqrt_ac, const float* sqrt_1mac, int timesteps, int rows, int channels,
+                 long per_sample, void* stream) {
+    const char* who = "v_to_eps";
+    if (!out || !x || !t || !sqrt_ac || !sqrt_1mac) VDX_REFUSE(who, "null tensor");
+    if (rows < 1 || channels < 1 || timesteps < 1 || per_sample < 1) VDX_REFUSE(who, "rows, channels, timesteps and per_sample must be >= 1");
+    if (per_sample % channels) VDX_REFUSE(who, "per_sample must be a multiple of channels");
+    VDX_HIP(vdx::launch_v_to_eps(out, x, t, sqrt_ac, sqrt_1mac, timesteps, rows, channels, per_sample, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+size_t vdx_v_loss_scratch_doubles(int batch) { return batch > 0 ? vdx::v_loss_scratch_doubles(batch) : 0; }
+
+int vdx_v_loss(const float* out, const float* x0, const float* noise, const int* t, const float* sqrt_ac, const float* sqrt_1mac,
+               const double* wtab, const double* iw, int timesteps, int kind, float pre_scale, float pre_shift, int l2, float* d_out,
+               double* scratch, double* result, int batch, int channels, long fhw, void* stream) {
+    const char* who = "v_loss";
+    if (kind != 0 && kind != 1) VDX_REFUSE(who, "kind 0 (target noise) or 1 (target v)");
+    if (!out || !noise || !scratch || !result) VDX_REFUSE(who, "null tensor");
+    if (kind == 1 && (!x0 || !sqrt_ac || !sqrt_1mac)) VDX_REFUSE(who, "kind 1 needs x0 and both tables");
+    if ((kind == 1 || wtab) && (!t || timesteps < 1)) VDX_REFUSE(who, "levels: t and timesteps >= 1");
+    if (batch < 1 || channels < 1 || fhw < 1) VDX_REFUSE(who, "batch, channels and fhw must be >= 1");
+    if ((uintptr_t)wtab % 8 || (uintptr_t)iw % 8 || (uintptr_t)scratch % 8 || (uintptr_t)result % 8)
+        VDX_REFUSE(who, "wtab / iw / scratch / result must be 8-byte aligned");
+    vdx::VLossArgs a;
+    memset(&a, 0, sizeof(a));
+    a.out = out; a.x0 = kind ? x0 : nullptr; a.noise = noise; a.d_out = d_out; a.t = t; a.sqrt_ac = sqrt_ac; a.sqrt_1mac = sqrt_1mac; a.T = timesteps;
+    a.wtab = wtab; a.iw = iw; a.kind = kind; a.l2 = l2 ? 1 : 0; a.C = channels; a.fhw = fhw; a.pre_scale = pre_scale; a.pre_shift = pre_shift;
+    VDX_HIP(vdx::launch_v_loss(a, scratch, result, batch, (hipStream_t)stream));
     return VDX_OK;
 }
 

@@ -326,6 +326,21 @@ size_t loss_weighted_scratch_doubles(int B);
 // out [B + 1] doubles: the per-sample means, then (1 / B) sum_b iw_b l_b; d_eps (may be null) channel-last like eps_hat
 hipError_t launch_loss_weighted(const float* eps_hat, const float* noise, const double* iw, float* d_eps, double* scratch, double* out, int B,
                                 int Cc, long fhw, int l2, hipStream_t st);
+// v-prediction (vdx.h: "v-prediction"; vpred.hip).  launch_v_to_eps: out [rows][F,H,W,C] (the network's v_hat) <- eps_hat in place, x
+// [rows][C,F,H,W] = x_t.  launch_v_loss: result [B + 1] doubles, the per-sample weighted means, then (1 / B) sum_b iw_b result[b].
+hipError_t launch_v_to_eps(float* out, const float* x, const int* t, const float* sqrt_ac, const float* sqrt_1mac, int T, int rows, int Cc,
+                           long per_sample, hipStream_t st);
+struct VLossArgs {
+    const float* out; const float* x0; const float* noise; float* d_out;   // out / d_out channel-last [B,F,H,W,C]; d_out or null (no gradient)
+    const int* t; const float* sqrt_ac; const float* sqrt_1mac; int T;     // t may be null with kind 0 and no wtab
+    const double* wtab; const double* iw;                                  // per-level weights [T] / importance weights [B], or null (all 1)
+    int kind, l2, C; long fhw;                                             // kind 1: target v; kind 0: target noise
+    float pre_scale, pre_shift;                                            // x0n = x0 pre_scale + pre_shift (normalize_img), as launch_q_sample
+    // completed by the launcher
+    float inv_count; int vec; double* partial;
+};
+size_t v_loss_scratch_doubles(int B);
+hipError_t launch_v_loss(VLossArgs a, double* scratch, double* result, int B, hipStream_t st);
 hipError_t launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
                            long step_count, float grad_scale, int do_ema, float decay, hipStream_t st);
 hipError_t launch_adam_ema_clip(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,

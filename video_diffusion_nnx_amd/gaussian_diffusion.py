@@ -365,7 +365,48 @@ def mixed_noise_coef(alpha):
     return float(np.float32(al / h)), float(np.float32(1.0 / h))
 
 
+OBJECTIVES = ('pred_noise', 'pred_v')
+
+
+def check_objective(objective) -> str:
+    """What the network predicts: 'pred_noise' (eps, the reference) or 'pred_v' (v = sqrt(ac) eps - sqrt(1 - ac) x0); anything else raises
+    ValueError."""
+    if not isinstance(objective, str) or objective not in OBJECTIVES:
+        raise ValueError(f"objective must be 'pred_noise' or 'pred_v', got {objective!r}")
+    return objective
+
+
+def check_min_snr_gamma(gamma):
+    """The min-SNR clamp gamma as a float, or None (no loss weighting): a finite number > 0; anything else (a bool included) raises
+    ValueError."""
+    if gamma is None:
+        return None
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)):
+        raise ValueError(f'min_snr_gamma must be None or a finite number > 0, got {gamma!r}')
+    g = float(gamma)
+    if not (g > 0.0 and g != float('inf')):
+        raise ValueError(f'min_snr_gamma must be None or a finite number > 0, got {gamma!r}')
+    return g
+
+
+def min_snr_weights(timesteps: int, objective: str = 'pred_noise', gamma=None):
+    """The loss weight of every level as float64 [T] (Hang et al. 2023, min-SNR-gamma), or None without gamma.  SNR_t = ac_t / (1 - ac_t)
+    from make_tables' alphas_cumprod widened to double (the numbers q_sample noises with); the weight is the one on the x0 loss,
+    min(SNR, gamma), restated for what the network predicts: pred_noise min(SNR, gamma) / SNR, pred_v min(SNR, gamma) / (SNR + 1).  Both
+    are <= 1, and w_v = w_eps SNR / (SNR + 1)."""
+    objective, g = check_objective(objective), check_min_snr_gamma(gamma)
+    if g is None:
+        return None
+    ac = make_tables(int(timesteps))['alphas_cumprod'].astype(np.float64)
+    snr = ac / (1.0 - ac)
+    return np.minimum(snr, g) / (snr + 1.0 if objective == 'pred_v' else snr)
+
+
 class GaussianDiffusion:
+    # the objective's switches (instance attributes only when they are on: a plain instance keeps the attributes it had)
+    objective = 'pred_noise'
+    min_snr_gamma = None
+    _loss_w = None
     # super-resolution switches (instance attributes only on a super-resolution diffusion: a plain one keeps the attributes it had)
     lowres_cond = None
     lowres_aug_max = 0
@@ -375,7 +416,24 @@ class GaussianDiffusion:
     def __init__(self, denoise_fn: Unet3D, *, image_size: int, num_frames: int, text_use_bert_cls: bool = False,
                  channels: int = 3, timesteps: int = 1000, loss_type: str = 'l1', use_dynamic_thres: bool = False,
                  dynamic_thres_percentile: float = 0.9, sample_act_bf16: bool = True, learned_variance: bool = False,
-                 vlb_weight: Optional[float] = None, lowres_cond=None, lowres_aug_max: int = 0, frame_noise_alpha: float = 0.0):
+                 vlb_weight: Optional[float] = None, lowres_cond=None, lowres_aug_max: int = 0, frame_noise_alpha: float = 0.0,
+                 objective: str = 'pred_noise', min_snr_gamma: Optional[float] = None):
+        # objective = 'pred_v' (extension, off by default; Salimans & Ho 2022, "Progressive Distillation"): the network predicts
+        # v = sqrt(ac_t) eps - sqrt(1 - ac_t) x0, well conditioned at both ends of the schedule.  Training regresses on v (vdx_v_loss);
+        # everywhere else the network output is converted once, in place, to eps_hat = sqrt(ac_t) v_hat + sqrt(1 - ac_t) x_t directly behind
+        # the forward (_eps_from_out; in the captured loops the handle's prediction state, _sampling) and everything downstream is the
+        # eps-model it was.  min_snr_gamma = gamma (extension, off by default; Hang et al. 2023): the loss of a sample at level t is weighted
+        # with min_snr_weights, for either objective.  Neither is stored in checkpoints: sample a model with the objective it was trained
+        # with.  vdx.h: "v-prediction".
+        objective, gamma = check_objective(objective), check_min_snr_gamma(min_snr_gamma)
+        for name, on in (("objective='pred_v'", objective == 'pred_v'), ('min_snr_gamma', gamma is not None)):
+            if on and learned_variance:
+                raise ValueError(f'{name} does not support learned_variance yet (a follow-up; DESIGN.md 9): the hybrid loss and the '
+                                 'learned-variance loops take eps_hat | v of an eps-model')
+        if objective == 'pred_v':
+            self.objective = objective
+        if gamma is not None:
+            self.min_snr_gamma = gamma
         # frame_noise_alpha = alpha (extension, off by default; Ge et al. 2023, "Preserve Your Own Correlation", sec. 3.2, the mixed noise
         # model): every noise tensor drawn by key -- q_sample's eps, x_T, the z of the ancestral steps -- is z = a s + b e with s shared by
         # the frames of a clip, a = alpha / sqrt(1 + alpha^2), b = 1 / sqrt(1 + alpha^2): still N(0, 1) per element, two frames correlate
@@ -457,6 +515,8 @@ class GaussianDiffusion:
         self._mtab_clean[0] = 1.0
         self._mtab_clean[1] = 0.0
         self._sample_stream = None
+        if self.min_snr_gamma is not None:
+            self._loss_w = torch.from_numpy(min_snr_weights(self.num_timesteps, self.objective, self.min_snr_gamma)).to(self.device)
 
     # -- closed forms (table look-ups) -------------------------------------------------------------
     def q_mean_variance(self, x_start, t):
@@ -468,6 +528,24 @@ class GaussianDiffusion:
     def predict_start_from_noise(self, x_t, t, noise):
         return (extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t
                 - extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape) * noise)
+
+    def predict_v(self, x_start, t, noise):
+        """The target of the pred_v objective: v = sqrt(ac_t) noise - sqrt(1 - ac_t) x_start."""
+        return (extract(self.sqrt_alphas_cumprod, t, x_start.shape) * noise
+                - extract(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * x_start)
+
+    def predict_start_from_v(self, x_t, t, v):
+        return (extract(self.sqrt_alphas_cumprod, t, x_t.shape) * x_t
+                - extract(self.sqrt_one_minus_alphas_cumprod, t, x_t.shape) * v)
+
+    def predict_noise_from_v(self, x_t, t, v):
+        return (extract(self.sqrt_alphas_cumprod, t, x_t.shape) * v
+                + extract(self.sqrt_one_minus_alphas_cumprod, t, x_t.shape) * x_t)
+
+    @property
+    def loss_weights(self):
+        """The min-SNR loss weights as a float64 [T] device tensor (min_snr_weights), or None without min_snr_gamma."""
+        return self._loss_w
 
     def q_posterior(self, x_start, x_t, t):
         mean = (extract(self.posterior_mean_coef1, t, x_t.shape) * x_start + extract(self.posterior_mean_coef2, t, x_t.shape) * x_t)
@@ -510,7 +588,8 @@ class GaussianDiffusion:
     # the optional features that refuse what they do not serve yet: message prefix, "is it on"
     _FEATURES = {'learned_variance': ('learned_variance', lambda gd: gd.learned_variance),
                  'lowres_cond': ('lowres_cond (super-resolution)', lambda gd: gd.lowres_cond is not None),
-                 'frame_noise_alpha': ('frame_noise_alpha', lambda gd: bool(gd.frame_noise_alpha))}
+                 'frame_noise_alpha': ('frame_noise_alpha', lambda gd: bool(gd.frame_noise_alpha)),
+                 'objective': ("objective='pred_v' / min_snr_gamma", lambda gd: gd.objective == 'pred_v' or gd.min_snr_gamma is not None)}
 
     def _refuse(self, feature, **given):
         """ValueError for the first of the keywords `given` that is in use (not None / False / its neutral value) while `feature` is on:
@@ -533,6 +612,16 @@ class GaussianDiffusion:
 
     def _per_sample(self, x):
         return x.numel() // x.shape[0]
+
+    def _eps_from_out(self, out, x, t32):
+        """eps_hat of the network output `out` [rows,F,H,W,C] at x_t = `x` [rows,C,F,H,W], levels t32: `out` itself for pred_noise; for
+        pred_v `out` is overwritten with sqrt(ac_t) out + sqrt(1 - ac_t) x (vdx_v_to_eps, one launch) and returned.  Every eager consumer
+        of the network output goes through here; the captured loops run the same kernel inside their step (_sampling)."""
+        if self.objective != 'pred_v':
+            return out
+        L.check(L.vdx_v_to_eps(L.ptr(out), L.ptr(x), L.ptr(t32), L.ptr(self.sqrt_alphas_cumprod), L.ptr(self.sqrt_one_minus_alphas_cumprod),
+                               self.num_timesteps, x.shape[0], self.channels, self._per_sample(x), L.stream_ptr()))
+        return out
 
     def _dynamic_threshold(self, x, t, eps_hat):
         """Imagen dynamic thresholding (reference :205-217): s = max(quantile(|x0_hat| per sample, percentile), 1), exact radix
@@ -703,6 +792,7 @@ class GaussianDiffusion:
             return out, t32, out2
         eps_hat = self._sr_eps(x, t32, lowres_cond, cond) if self.lowres_cond is not None else \
             self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
+        eps_hat = self._eps_from_out(eps_hat, x, t32)
         thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
         if nz is None and self.frame_noise_alpha:                         # z = a s + b e drawn inside the step kernel
             L.check(L.vdx_p_sample_step_mixed(L.ptr(x), L.ptr(eps_hat), L.ptr(out), L.ptr(t32), L.ptr(self._ptab), self.num_timesteps,
@@ -744,10 +834,18 @@ class GaussianDiffusion:
         st.wait_stream(cur)
         keep_storage = unet.act_bf16
         unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
+        # pred_v: the handle's loops convert the network output behind the forward (vdx_set_prediction); kind 0 goes back on the way out,
+        # so a network shared with another diffusion is that diffusion's eps-model again
+        h = unet.handle(self.num_frames, self.image_size) if self.objective == 'pred_v' else None
         try:
+            if h is not None:
+                L.check(L.vdx_set_prediction(h.ptr, 1, L.ptr(self.sqrt_alphas_cumprod), L.ptr(self.sqrt_one_minus_alphas_cumprod),
+                                             self.num_timesteps))
             with torch.cuda.stream(st):
                 yield
         finally:
+            if h is not None:
+                L.check(L.vdx_set_prediction(h.ptr, 0, None, None, 0))
             unet.act_bf16 = keep_storage
             unet._focus = None
         cur.wait_stream(st)
@@ -875,7 +973,7 @@ class GaussianDiffusion:
         B, per = img.shape[0], self._per_sample(img)
 
         def eps_and_thres(t):
-            eps_hat = unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale)
+            eps_hat = self._eps_from_out(unet.forward_with_cond_scale(img, t, cond=cond, cond_scale=cond_scale), img, t)
             return eps_hat, (self._dynamic_threshold(img, t, eps_hat) if self.use_dynamic_thres else None)
 
         if chain == 'ddpm':
@@ -1188,6 +1286,7 @@ class GaussianDiffusion:
             raise ValueError(f'Unsupported loss type: {self.loss_type}')
         self._refuse('learned_variance', frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
         self._refuse('lowres_cond', frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
+        self._refuse('objective', frame_mask=frame_mask)                  # (the masked loss is a (sum, count) form without levels)
         if self.lowres_cond is None and (lowres is not None or aug_levels is not None):
             raise ValueError('lowres / aug_levels need a super-resolution diffusion (lowres_cond=(ft, fs))')
         if self.lowres_cond is not None:
@@ -1228,10 +1327,25 @@ class GaussianDiffusion:
           mask              the mean over the mask-0 elements (masked_loss, vdx_loss_grad_masked: the count stays on the device)
           iw                float64 [B] importance weights (loss-aware timestep sampling): the weighted mean and gradient from one
                             vdx_loss_weighted pass; last_loss_per_sample = the unweighted per-sample losses
+          pred_v / min_snr_gamma   eps_hat is the network output against the v target (pred_v) or the noise, weighted per level with
+                            loss_weights and per sample with iw, from one vdx_v_loss pass; last_loss_per_sample = w_b * (the sample's
+                            mean) and the loss is (1 / B) sum_b iw_b of them: what is optimised
           otherwise         the plain mean (vdx_loss_sum, vdx_loss_grad)"""
         if self.learned_variance:
             return self.hybrid_loss(x_start, noise, eps_hat, t32, want_grad=want_grad, _pre=_pre, iw=iw)
         B, fhw, l2 = x_start.shape[0], self._per_sample(x_start) // self.channels, int(self.loss_type == 'l2')
+        if self.objective == 'pred_v' or self._loss_w is not None:
+            if mask is not None:
+                self._refuse('objective', frame_mask=True)
+            scratch = torch.empty(L.vdx_v_loss_scratch_doubles(B), dtype=torch.float64, device=self.device)
+            out = torch.empty(B + 1, dtype=torch.float64, device=self.device)
+            d_out = torch.empty_like(eps_hat) if want_grad else None
+            L.check(L.vdx_v_loss(L.ptr(eps_hat), L.ptr(x_start), L.ptr(noise), L.ptr(t32), L.ptr(self.sqrt_alphas_cumprod),
+                                 L.ptr(self.sqrt_one_minus_alphas_cumprod), L.ptr(self._loss_w), L.ptr(iw), self.num_timesteps,
+                                 int(self.objective == 'pred_v'), float(_pre[0]), float(_pre[1]), l2, L.ptr(d_out), L.ptr(scratch), L.ptr(out),
+                                 B, self.channels, fhw, L.stream_ptr()))
+            self.last_loss_per_sample = out[:B]
+            return out[B].to(torch.float32).reshape(()), d_out
         if mask is None and iw is not None:
             out, d_eps = TS.loss_weighted(eps_hat, noise, iw, l2=bool(l2), want_grad=want_grad)
             self.last_loss_per_sample = out[:B]

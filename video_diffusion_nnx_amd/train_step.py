@@ -215,6 +215,7 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     tr.last_focus_mask = focus_present_mask if unet.focus_present else None
     gd._refuse('learned_variance', frame_mask=frame_mask, focus_present=fp)
     gd._refuse('lowres_cond', frame_mask=frame_mask, focus_present=fp)
+    gd._refuse('objective', frame_mask=frame_mask)                        # (given, or drawn under frame_cond_max)
     if gd.lowres_cond is None:
         if aug_levels is not None or lowres is not None:
             raise ValueError('aug_levels / lowres need a super-resolution diffusion (lowres_cond=(ft, fs))')
