@@ -305,17 +305,20 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const ConvArgs P, co
     // 64 of them, was measured slower: r02, spills.)
     uint4 pb[4], pa;
     ldB(pb, 0, 0); pa = ldA1(0, 0, 0);
-    // one K chunk = 9 taps on input buffer hbuf; (tnext, ccnext) = the buffer to fetch meanwhile.  AFTER_EPI: the 16 stores of the
+    // one K chunk = 9 taps on input buffer hbuf; (tnext, ccnext) = the buffer to fetch meanwhile.  after_epi (uniform): the 16 stores of the
     // previous tile's epilogue sit between the weight slabs in flight, so the first two syncs leave that many more operations outstanding.
-    auto run_chunk = [&](auto after_epi, int tnext, int ccnext, bool xform) {
-        constexpr int EPI = decltype(after_epi)::value ? WS_STORES : 0;
+    // A branch around those two waits, NOT a second instantiation of the loop body: with two copies meeting in the chunk loop the register
+    // allocator kept the fragments of both alive (251-255 VGPRs, the prologue forms spilled 60 B); one copy needs 181-195 and no scratch,
+    // and every form ran 3-15 % faster (profiles/ws_pipeline.md).
+    auto run_chunk = [&](bool after_epi, int tnext, int ccnext, bool xform) {
+        constexpr int EPI = WS_STORES;
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             // sync of tap: every wave's part of slab (tap + 1) has landed (issued two taps ago; at most the younger slab, and at taps
             // 0 / 1 the input pieces and the epilogue stores, may still be in flight), every wave is done with slab (tap - 1) and, at
             // tap 0, with the other input buffer; at tap 2 the input pieces issued at tap 0 (older than slab 3) have landed too
-            if (tap == 0) wait_vm<WIN + EPI>();
-            else if (tap == 1) wait_vm<WIN + NUMIN + EPI>();
+            if (tap == 0) { if (after_epi) wait_vm<WIN + EPI>(); else wait_vm<WIN>(); }
+            else if (tap == 1) { if (after_epi) wait_vm<WIN + NUMIN + EPI>(); else wait_vm<WIN + NUMIN>(); }
             else wait_vm<WIN>();
             __builtin_amdgcn_s_barrier();
             if (tap == 0) issue_halo(tnext, ccnext, hbuf ^ 1);
@@ -374,8 +377,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws_kernel(const ConvArgs P, co
                 const int bn = sample_of(tnext);
                 if (bn != bcoef) { make_coef(bn); bcoef = bn; }      // uniform; the tables are only read by transform() below
             }
-            if (after_epilogue) run_chunk(std::true_type{}, tnext, ccnext, more);
-            else run_chunk(std::false_type{}, tnext, ccnext, more);
+            run_chunk(after_epilogue, tnext, ccnext, more);
             after_epilogue = false;
         }
         // ---- epilogue of tile t: +bias, store, statistics --------------------------------------------------------------
