@@ -8,6 +8,7 @@ curves (GaussianDiffusion.calc_bpd_loop; an extension, the reference has no eval
 Writes one JSON document: total_bpd and prior_bpd (means over the videos; total_bpd is null with --eval-steps below T), the length-S
 arrays t, vb, mse and xstart_mse (means over the videos), num_videos, mode and seed.  One process: the evaluation is not sharded.
 A config with diffusion.frame_noise_alpha > 0 (the mixed noise prior) is refused: the bound under a frame-correlated prior is a follow-up.
+A config with diffusion.self_condition: true (self-conditioning) is refused by name as well: the bound has no form for it yet.
 A config with diffusion.objective: pred_v evaluates a v-predicting network: the loop converts its output to eps_hat behind every forward."""
 import argparse
 import json
@@ -92,6 +93,9 @@ def main(argv=None):
     if gd.frame_noise_alpha:
         ap.error('frame_noise_alpha does not support calc_bpd_loop yet (a follow-up; DESIGN.md 9): the bound of a model trained under the mixed '
                  'noise prior needs the inverse frame covariance in its KL terms')
+    if gd.self_condition:
+        ap.error('self_condition does not support calc_bpd_loop yet (a follow-up; DESIGN.md 9): the bound of a chain that feeds on its own '
+                 'estimates is not defined here')
     if a.eval_steps is not None and a.eval_steps > gd.num_timesteps:
         ap.error(f'--eval-steps must be in [1, {gd.num_timesteps}], got {a.eval_steps}')
     if not a.random_init:

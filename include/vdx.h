@@ -839,6 +839,34 @@ int vdx_v_loss(const float* out, const float* x0, const float* noise, const int*
 int vdx_set_prediction(vdx_handle* h, int kind, const float* sqrt_ac, const float* sqrt_1mac, int timesteps);
 int vdx_get_prediction(const vdx_handle* h);
 
+/* Self-conditioning (EXTENSION, parity unpinned: no reference code.  Chen et al. 2022, "Analog Bits", section 2.2; used by Imagen Video
+ * and RIN).  Off unless these entries are called.  The denoiser has channels = 2 C and out_dim = C, as a super-resolution one; its input is
+ *   xin [batch, 2C, F, H, W]:  planes [0, C) of each sample = x_t,  planes [C, 2C) = x0~, the network's own previous estimate of x0
+ * (zero where there is none: the first step of a chain, and the training steps whose coin says so).
+ *
+ * vdx_selfcond_x0: x0~ = clip(sqrt(1 / ac_t) x - sqrt(1 / ac_t - 1) eps_hat), written into planes [C, 2C) of xin (row pitch 2 per_sample;
+ *   planes [0, C) are not touched).  x [batch][C,F,H,W] with sample b at x + b * x_pitch floats (x_pitch >= per_sample: img of a loop with
+ *   x_pitch = per_sample, or xin itself with x_pitch = 2 per_sample); eps_hat channel-last [batch,F,H,W,C], dense; t [batch] int32 (a level
+ *   outside [0, timesteps) reads the nearest one); tables: the [5][timesteps] step tables of vdx_p_sample_step, rows 0 and 1 are read;
+ *   thres (may be NULL) [batch]: the dynamic threshold s of vdx_dynamic_threshold, NULL: s = 1.  Per element
+ *     x0 = fl(fl(k_recip x) - fl(k_recipm1 eps_hat)),  and with clip_denoised  x0 = fminf(fmaxf(x0, -s), s) / s
+ *   with no fused multiply-add, so fp32 torch restates it bit for bit.  Four consecutive elements per thread, tails guarded: any
+ *   per_sample that is a multiple of channels, any channels, sample bases off 16 bytes (the float4 forms only where a whole quad's
+ *   address allows them).  Refused before any launch (VDX_ERR_INVALID): a NULL x / eps_hat / t / tables / xin, batch, channels, timesteps
+ *   or per_sample < 1, per_sample % channels != 0, x_pitch < per_sample, a tensor off 4 bytes.
+ * vdx_set_self_condition: the handle's self-condition state, for the loops: on = 0 (always accepted; clears the table) or 1 with the
+ *   caller's device step tables [5][timesteps] (they must outlive the setting).  With on = 1 the step of vdx_p_sample_loop_sr /
+ *   vdx_ddim_sample_loop_sr / vdx_dpm_sample_loop_sr gains ONE launch, vdx_selfcond_x0's kernel with x = img, thres = the step's dynamic
+ *   threshold (or NULL), clip = clip_denoised and the levels of t_dev, behind vdx_v_to_eps's and the threshold's and in front of the
+ *   chain's step kernel: the next step's forward reads it.  The caller zeroes planes [C, 2C) of xin before the first step.  The state
+ *   (on, the pointer, timesteps) is part of every loop's graph key: a change re-captures, no graph is evicted for it.  While it is on,
+ *   every loop entry without xin, vdx_p_sample_loop_lv, vdx_vlb_loop and vdx_vlb_loop_lv return VDX_ERR_STATE before any launch.
+ *   VDX_ERR_INVALID: on other than 0 / 1, on = 1 without tables or with timesteps < 1.  Like the other handle settings it needs no GPU. */
+int vdx_selfcond_x0(const float* x, long x_pitch, const float* eps_hat, const int* t, const float* tables, int timesteps, const float* thres,
+                    int clip_denoised, float* xin, int batch, int channels, long per_sample, void* stream);
+int vdx_set_self_condition(vdx_handle* h, int on, const float* tables, int timesteps);
+int vdx_get_self_condition(const vdx_handle* h);
+
 /* ------------------------------------------------------------------------------------------------
  * Backward building blocks (autodiff of the forward operators; reference trainer.py:361 jax.value_and_grad).
  * ---------------------------------------------------------------------------------------------- */

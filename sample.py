@@ -15,7 +15,11 @@ YAML, absent = 0: the mixed noise prior of "Preserve Your Own Correlation" -- x_
 the frames of a clip, correlation A^2 / (1 + A^2); for checkpoints trained with train.py --frame_noise_alpha A; works with --ddim-steps,
 --dpm-steps and --cond-path, not with --context, learned-variance or super-resolution configs); --objective pred_v (or diffusion.objective:
 pred_v in the YAML, absent = pred_noise: the network predicts v = sqrt(ac) eps - sqrt(1 - ac) x0; for checkpoints trained with train.py
---objective pred_v; works with every sampler and option above except learned-variance configs)."""
+--objective pred_v; works with every sampler and option above except learned-variance configs); --self-condition (or
+diffusion.self_condition: true in the YAML, absent = off: self-conditioning of "Analog Bits" -- the stem takes 2 * channels planes and every
+step of the chain feeds its clipped estimate of x0 to the next one, inside the captured step; for checkpoints trained with train.py
+--self_condition; works with --ddim-steps, --dpm-steps, --objective pred_v, --focus-present and an un-guided --cond-path (--cond-scale 1),
+not with --context, --lowres-path, guidance, learned-variance configs or --frame-noise-alpha)."""
 import argparse
 import logging
 import os
@@ -69,11 +73,14 @@ FLAGS = (   # (flag, kwargs)
     ('--objective', dict(choices=('pred_noise', 'pred_v'), default=None, help='what the network predicts (overrides diffusion.objective in the '
                                                                               'YAML; pred_v for checkpoints trained with it; not stored in '
                                                                               'checkpoints)')),
+    ('--self-condition', dict(action='store_true', help='self-conditioning: every step feeds its estimate of x0 to the next one (also '
+                                                        'diffusion.self_condition in the YAML; for checkpoints trained with it; not stored '
+                                                        'in checkpoints); not with --context / --lowres-path / guidance')),
 )
 
 
 def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=False, focus_present=False, frame_noise_alpha=None,
-                 objective=None, min_snr_gamma=None):
+                 objective=None, min_snr_gamma=None, self_condition=None):
     """temporal_pos_bias: the command-line flag; the YAML's unet.temporal_pos_bias (absent = false) switches it on as well.  An architecture
     argument like dim: checkpoints do not store it, so a model trained with it is sampled with it.  focus_present: the same for the
     focus-present switch (unet.focus_present in the YAML, absent = false).  diffusion.learned_variance (absent = false; optionally with
@@ -86,7 +93,9 @@ def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=Fa
     trained with it is sampled with the same A.  diffusion.objective: pred_noise | pred_v and diffusion.min_snr_gamma: gamma (absent = off; the
     keywords, the command-line flags, override them): what the network predicts and the min-SNR loss weighting of
     GaussianDiffusion(objective=..., min_snr_gamma=gamma).  Checkpoints do not store them either: a model trained to predict v is sampled
-    with objective pred_v."""
+    with objective pred_v.  diffusion.self_condition: true (absent = off; the keyword, the command-line flag, switches it on as well):
+    self-conditioning -- the UNet gets channels = 2 * channels, out_dim = channels, as for lowres_cond, and the diffusion
+    self_condition=True.  Checkpoints do not store the switch; the stem's shape is what they store."""
     from video_diffusion_nnx_amd.gaussian_diffusion import GaussianDiffusion
     from video_diffusion_nnx_amd.unet3d import Rngs, Unet3D
     u, d = cfg['unet'], cfg['diffusion']
@@ -99,13 +108,16 @@ def build_models(cfg, mode, timesteps=None, attn_fp8=False, temporal_pos_bias=Fa
     ob = d.get('objective') if objective is None else objective
     mg = d.get('min_snr_gamma') if min_snr_gamma is None else min_snr_gamma
     ob_kw = dict(**(dict(objective=ob) if ob is not None else {}), **(dict(min_snr_gamma=mg) if mg is not None else {}))
-    unet = Unet3D(**(dict(out_dim=2 * u['channels']) if lv else dict(out_dim=u['channels']) if sr else {}), dim=u['dim'], rngs=Rngs(u['rngs_seed']),
-                  dim_mults=tuple(u['dim_mults']), channels=(2 if sr else 1) * u['channels'],
+    sc = d.get('self_condition', False) if self_condition is None else self_condition
+    sc_kw = dict(self_condition=sc) if (sc or not isinstance(sc, bool)) else {}       # (False takes the constructor's default)
+    wide = bool(sr) or sc is True                                                      # the stem of [ x_t | u ] or [ x_t | x0~ ]
+    unet = Unet3D(**(dict(out_dim=2 * u['channels']) if lv else dict(out_dim=u['channels']) if wide else {}), dim=u['dim'], rngs=Rngs(u['rngs_seed']),
+                  dim_mults=tuple(u['dim_mults']), channels=(2 if wide else 1) * u['channels'],
                   use_bert_text_cond=u['use_bert_text_cond'], mode=mode, attn_fp8=attn_fp8,
                   temporal_pos_bias=bool(temporal_pos_bias or u.get('temporal_pos_bias', False)),
                   focus_present=bool(focus_present or u.get('focus_present', False)))
     gd = GaussianDiffusion(denoise_fn=unet, image_size=d['image_size'], num_frames=d['num_frames'], channels=d['channels'],
-                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'], **lv_kw, **sr_kw, **fa_kw, **ob_kw)
+                           timesteps=timesteps or d['timesteps'], loss_type=d['loss_type'], **lv_kw, **sr_kw, **fa_kw, **ob_kw, **sc_kw)
     return unet, gd
 
 
@@ -173,6 +185,8 @@ def main(argv=None):
     if a.frame_noise_alpha and a.context:
         ap.error('--frame-noise-alpha samples from noise: not together with --context (frame-conditioned sampling under the mixed prior is a '
                  'follow-up)')
+    if a.self_condition and (a.context or a.lowres_path or a.steps is not None):
+        ap.error('--self-condition runs the plain chains: not together with --context / --lowres-path / --steps')
     if a.clean_context and not a.context:
         ap.error('--clean-context needs --context')
     if a.clean_context and a.resample_steps > 1:
@@ -219,14 +233,18 @@ def _run(a, ap, rank, world):
         unet, gd = build_models(cfg, a.mode, a.timesteps, attn_fp8=a.attn_fp8, temporal_pos_bias=a.temporal_pos_bias,
                                 **(dict(focus_present=True) if a.focus_present else {}),
                                 **(dict(frame_noise_alpha=a.frame_noise_alpha) if a.frame_noise_alpha is not None else {}),
-                                **(dict(objective=a.objective) if a.objective is not None else {}))
+                                **(dict(objective=a.objective) if a.objective is not None else {}),
+                                **(dict(self_condition=True) if a.self_condition else {}))
     except ValueError as e:
-        if not any(w in str(e) for w in ('frame_noise_alpha', 'objective', 'min_snr_gamma')):
+        if not any(w in str(e) for w in ('frame_noise_alpha', 'objective', 'min_snr_gamma', 'self_condition')):
             raise
         ap.error(str(e))
     if gd.frame_noise_alpha and a.context:
         ap.error('diffusion.frame_noise_alpha samples from noise: not together with --context (frame-conditioned sampling under the mixed '
                  'prior is a follow-up)')
+    if gd.self_condition and (a.context or a.lowres_path or (a.cond_path and a.cond_scale != 1.0)):
+        ap.error('self_condition does not support inpaint / extend / upsample / cond_scale yet (a follow-up; DESIGN.md 9): not with '
+                 '--context, --lowres-path or --cond-scale other than 1')
     fp_kw = dict(focus_present=True) if a.focus_present else {}
     if a.steps is not None:
         if not gd.learned_variance:

@@ -28,7 +28,12 @@ in checkpoints: sample with sample.py --frame-noise-alpha A or the same YAML key
 --objective pred_v [--min_snr_gamma 5] (or diffusion.objective / diffusion.min_snr_gamma in the YAML, absent = pred_noise, unweighted: the
 network is trained to predict v = sqrt(ac) eps - sqrt(1 - ac) x0, and with gamma a sample's loss at level t is weighted with the min-SNR
 weight min(SNR_t, gamma) / (SNR_t + 1) -- for pred_noise min(SNR_t, gamma) / SNR_t; not stored in checkpoints: sample with sample.py
---objective pred_v or the same YAML key; not with learned-variance configs or --frame_cond_max)."""
+--objective pred_v or the same YAML key; not with learned-variance configs or --frame_cond_max);
+--self_condition [--self_cond_prob P] (or diffusion.self_condition: true and trainer.self_cond_prob: P in the YAML, absent = off, P = 0.5:
+self-conditioning of "Analog Bits" -- the stem takes 2 * channels planes, [ x_t | the network's own clipped estimate of x0 ]; with
+probability P a step first runs the network on [ x_t | 0 ], without gradient, for that estimate, otherwise it trains on [ x_t | 0 ]; not
+stored in checkpoints, the stem's shape is: sample with sample.py --self-condition or the same YAML key; not with learned-variance or
+super-resolution configs, --frame_noise_alpha or --frame_cond_max)."""
 import argparse
 import logging
 import os
@@ -68,6 +73,10 @@ FLAGS = (
                                                                               'diffusion.objective in the YAML; not stored in checkpoints)')),
     ('--min_snr_gamma', dict(type=float, default=None, help='min-SNR-gamma loss weighting, gamma > 0 (5 is the usual choice; overrides '
                                                             'diffusion.min_snr_gamma in the YAML; absent = unweighted)')),
+    ('--self_condition', dict(action='store_true', help='self-conditioning: the network also sees its own previous estimate of x0 (also '
+                                                        'diffusion.self_condition in the YAML; not stored in checkpoints)')),
+    ('--self_cond_prob', dict(type=float, default=None, help='with --self_condition: probability that a step runs the first, gradient-free '
+                                                             'forward (also trainer.self_cond_prob in the YAML; default 0.5)')),
 )
 
 
@@ -104,9 +113,10 @@ def main(argv=None):
                              **(dict(focus_present=True) if a.focus_present else {}),
                              **(dict(frame_noise_alpha=a.frame_noise_alpha) if a.frame_noise_alpha is not None else {}),
                              **(dict(objective=a.objective) if a.objective is not None else {}),
-                             **(dict(min_snr_gamma=a.min_snr_gamma) if a.min_snr_gamma is not None else {}))
+                             **(dict(min_snr_gamma=a.min_snr_gamma) if a.min_snr_gamma is not None else {}),
+                             **(dict(self_condition=True) if a.self_condition else {}))
     except ValueError as e:
-        if not any(w in str(e) for w in ('objective', 'min_snr_gamma')):
+        if not any(w in str(e) for w in ('objective', 'min_snr_gamma', 'self_condition')):
             raise
         ap.error(str(e))
     tc = dict(cfg['trainer'])
@@ -136,6 +146,16 @@ def main(argv=None):
         if not 0.0 < float(ts_prob) <= 1.0:
             ap.error(f'sampler_uniform_prob must be in (0, 1], got {ts_prob}')
         Trainer.sampler_uniform_prob = float(ts_prob)
+    # self-conditioned training: a Trainer attribute as well; absent = 0.5, used with a self-conditioned diffusion only
+    p_sc = tc.pop('self_cond_prob', None)
+    if a.self_cond_prob is not None:
+        if not getattr(gd, 'self_condition', False):      # (callers that replace build_models may hand no diffusion on)
+            ap.error('--self_cond_prob needs --self_condition (or diffusion.self_condition: true in the YAML)')
+        p_sc = a.self_cond_prob
+    if p_sc is not None:
+        if isinstance(p_sc, bool) or not 0.0 <= float(p_sc) <= 1.0:
+            ap.error(f'self_cond_prob must be in [0, 1], got {p_sc}')
+        Trainer.self_cond_prob = float(p_sc)
     if a.train_num_steps is not None:
         tc['train_num_steps'] = a.train_num_steps
     if a.dataset_path is not None:
@@ -146,6 +166,8 @@ def main(argv=None):
         frames = cfg.get('diffusion', {}).get('num_frames')
         if a.frame_cond_max < 0 or (frames is not None and a.frame_cond_max > frames - 1):
             ap.error(f'--frame_cond_max must be in [0, num_frames - 1], got {a.frame_cond_max}')
+        if a.frame_cond_max > 0 and getattr(gd, 'self_condition', False):
+            ap.error('self_condition does not support frame_mask yet (a follow-up; DESIGN.md 9): not with --frame_cond_max')
         Trainer.frame_cond_max = a.frame_cond_max
     if a.frame_cond_uncond_prob is not None:
         if not 0.0 <= a.frame_cond_uncond_prob <= 1.0:

@@ -175,3 +175,9 @@ vdx_v_loss_scratch_doubles = _sig('vdx_v_loss_scratch_doubles', c_size_t, [c_int
 vdx_v_loss = _sig('vdx_v_loss', c_int, [c_void_p] * 8 + [c_int, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p])
 vdx_set_prediction = _sig('vdx_set_prediction', c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int])
 vdx_get_prediction = _sig('vdx_get_prediction', c_int, [c_void_p])
+
+# self-conditioning (vdx.h: "Self-conditioning"): the x0 estimate behind the forward and the handle's self-condition state
+vdx_selfcond_x0 = _sig('vdx_selfcond_x0', c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_long,
+                                                  c_void_p])
+vdx_set_self_condition = _sig('vdx_set_self_condition', c_int, [c_void_p, c_int, c_void_p, c_int])
+vdx_get_self_condition = _sig('vdx_get_self_condition', c_int, [c_void_p])

@@ -33,8 +33,9 @@ struct vdx_handle {
     vdx::Model model;
     // the key of a captured sampling step: the LoopArgs of the call with every field its step does not read set to zero (sample_loop()),
     // the stream and the activation storage.  Full pointers: two workspaces / streams never alias one key.  Compared with memcmp, so it
-    // is zero-filled before the fields are assigned.  pred / pred_sa / pred_s1: the prediction the step converts (vdx_set_prediction)
-    struct GraphKey { LoopArgs a; const void* stream; int act16; int pred; const float* pred_sa; const float* pred_s1; };
+    // is zero-filled before the fields are assigned.  pred / pred_sa / pred_s1: the prediction the step converts (vdx_set_prediction);
+    // sc / sc_T / sc_tab: the self-condition state (vdx_set_self_condition), whose tables the sequence chains' steps read as well
+    struct GraphKey { LoopArgs a; const void* stream; int act16; int pred; const float* pred_sa; const float* pred_s1; int sc; int sc_T; const float* sc_tab; };
     // one cached graph per (chain, variant): slot = 3 * variant + chain with variant 0 = plain, 1 = masked, 2 = guided and chain 0 = the
     // ancestral loop, 1 = DDIM, 2 = DPM-Solver++; slot 9 = the evaluation loop (vdx_vlb_loop), 10 / 11 = the learned-variance sampling and
     // evaluation loops, 12 + chain = the super-resolution loops (vdx_*_sample_loop_sr), 15 / 16 = the plain and the guided mixed-noise
@@ -52,7 +53,10 @@ struct vdx_handle {
     void drop_graphs() { for (GraphSlot& g : gs) g.drop(); }
     // what the network predicts (vdx_set_prediction): 0 = eps, 1 = v with the caller's device tables sqrt(ac) | sqrt(1 - ac) [pred_T]
     int pred = 0; const float* pred_sa = nullptr; const float* pred_s1 = nullptr; int pred_T = 0;
-    void key_prediction(GraphKey& k) const { k.pred = pred; k.pred_sa = pred_sa; k.pred_s1 = pred_s1; }
+    // self-conditioning (vdx_set_self_condition): 1 = the step of an xin loop writes x0~ into planes [C, 2C) of xin, with rows 0, 1 of the
+    // caller's [5][sc_T] device step tables
+    int sc = 0; const float* sc_tab = nullptr; int sc_T = 0;
+    void key_prediction(GraphKey& k) const { k.pred = pred; k.pred_sa = pred_sa; k.pred_s1 = pred_s1; k.sc = sc; k.sc_T = sc_T; k.sc_tab = sc_tab; }
     vdx::BwdState bwd;
     vdx::Comm comm;
 };
@@ -635,6 +639,17 @@ int vdx_set_prediction(vdx_handle* h, int kind, const float* sqrt_ac, const floa
 }
 int vdx_get_prediction(const vdx_handle* h) { return h ? h->pred : 0; }
 
+int vdx_set_self_condition(vdx_handle* h, int on, const float* tables, int timesteps) {
+    if (!h) VDX_FAIL(VDX_ERR_INVALID, "set_self_condition: null handle");
+    if (on != 0 && on != 1) VDX_FAIL(VDX_ERR_INVALID, "set_self_condition: on is 0 or 1");
+    if (on && (!tables || timesteps < 1)) VDX_FAIL(VDX_ERR_INVALID, "set_self_condition: on = 1 needs the step tables and timesteps >= 1");
+    // (no graph is dropped: the state is part of every loop's graph key, so a step captured under another state is not replayed)
+    h->sc = on; h->sc_tab = on ? tables : nullptr; h->sc_T = on ? timesteps : 0;
+    return VDX_OK;
+}
+
+int vdx_get_self_condition(const vdx_handle* h) { return h ? h->sc : 0; }
+
 int vdx_param_count(const vdx_handle* h) { return h ? (int)h->model.params.size() : 0; }
 long vdx_param_total(const vdx_handle* h) { return h ? h->model.param_total : 0; }
 
@@ -882,8 +897,9 @@ static bool in_unit_interval(float x) {
 
 // The step of every loop, launch for launch: (guided: copy img[:B] -> img[B:]) -> (super-resolution, a.xin: lowres_pack img -> the
 // first half of xin, the forward then reads xin) -> model_forward over B samples (guided: 2B, the second half with the null embedding) ->
-// (v-prediction, vdx_set_prediction kind 1: v_to_eps over the forward's rows, in place on eps_buf, x = img) -> (guided: cfg_combine) -> (dynamic threshold) -> the chain's step kernel on B samples -> the chain's
-// advance (guided: over 2B).  Mixed noise (a.mix_a / a.mix_b, the ancestral chain only): p_sample_mixed_kernel is that step kernel.
+// (v-prediction, vdx_set_prediction kind 1: v_to_eps over the forward's rows, in place on eps_buf, x = img) -> (guided: cfg_combine) -> (dynamic threshold) ->
+// (self-conditioning, vdx_set_self_condition, an xin loop: selfcond_x0 of img and eps_buf at t_dev -> planes [C, 2C) of xin, what the next
+// step's forward reads) -> the chain's step kernel on B samples -> the chain's advance (guided: over 2B).  Mixed noise (a.mix_a / a.mix_b, the ancestral chain only): p_sample_mixed_kernel is that step kernel.
 // Validates, derives the graph key from `a` and runs nsteps steps eagerly or as replays of one captured step.
 // Guided loops (classifier-free guidance; EXTENSION, parity unpinned: the reference's p_sample_loop drops cond): img / t_dev / eps_buf /
 // workspace hold 2 * batch samples; the step kernels, the threshold and the result use the first `batch`.
@@ -899,6 +915,7 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
     // super-resolution (a.xin; vdx.h: "Cascaded super-resolution"): the network reads xin [batch, 2C, F, S, S], everything else is over
     // C = out_dim channels.  Plain variants only: there is no masked or guided entry that sets xin
     const bool sr = a.xin != nullptr;
+    if (h->sc && !sr) LOOP_FAIL(VDX_ERR_STATE, "self-conditioning (vdx_set_self_condition) needs a loop over xin (vdx_*_sample_loop_sr)");
     if (sr && h->model.cfg.channels != 2 * h->model.out_dim) LOOP_FAIL(VDX_ERR_INVALID, "channels must equal 2 * out_dim");
     if (!h->model.d_ss_layers) LOOP_FAIL(VDX_ERR_STATE, "handle was created without a GPU");
     // the rules of the variants, keyed on chain / masked / guided (all VDX_ERR_INVALID)
@@ -949,6 +966,11 @@ static int sample_loop(const char* who, vdx_handle* h, const LoopArgs& a, int ns
         if (h->pred) e = vdx::launch_v_to_eps(a.eps_buf, a.img, a.t_dev, h->pred_sa, h->pred_s1, h->pred_T, rows, C, per_sample, st);
         if (e == hipSuccess && guided) e = vdx::launch_cfg_combine(a.eps_buf, a.eps_buf, a.cond_scale, a.rescale, a.cfg_scratch, B, per_sample, st);
         if (e == hipSuccess && dyn) e = vdx::launch_dyn_thres(a.img, a.eps_buf, a.t_dev, a.tables, a.timesteps, a.percentile, a.thres_buf, B, C, per_sample, st);
+        // self-conditioning: x0~ of this step (the level is t_dev's for all three chains) is the second half of the next step's input
+        if (e == hipSuccess && h->sc) {
+            const vdx::SelfcondArgs sa = {a.img, per_sample, a.eps_buf, a.t_dev, h->sc_tab, h->sc_T, th, a.clip_denoised, a.xin, C, per_sample};
+            e = vdx::launch_selfcond_x0(sa, B, st);
+        }
         if (anc) {
             const vdx::PSampleArgs pa = psample_args(a.img, a.eps_buf, a.img, a.t_dev, a.tables, a.timesteps, nullptr, a.seed, masked ? 0 : 1,
                                                      masked ? nullptr : a.step_dev, th, a.clip_denoised, C, per_sample);
@@ -1283,6 +1305,7 @@ static int vlb_loop(const char* who, bool lv, vdx_handle* h, const float* params
     if (!h || !params || !packed || !x || !xt_buf || !eps_buf || !t_dev || !step_dev || !vlb_tables || !seq || !partial || !out || !workspace)
         VDX_REFUSE(who, "null argument");
     if (lv && h->pred) { char msg_[128]; snprintf(msg_, sizeof(msg_), "%s: v-prediction (vdx_set_prediction) has no learned-variance form", who); VDX_FAIL(VDX_ERR_STATE, msg_); }
+    if (h->sc) { char msg_[128]; snprintf(msg_, sizeof(msg_), "%s: self-conditioning (vdx_set_self_condition) has no bits/dim form", who); VDX_FAIL(VDX_ERR_STATE, msg_); }
     if (!h->model.d_ss_layers) { char msg_[96]; snprintf(msg_, sizeof(msg_), "%s: handle was created without a GPU", who); VDX_FAIL(VDX_ERR_STATE, msg_); }
     const vdx::Model& m = h->model;
     const int C = m.cfg.channels;
@@ -1371,6 +1394,7 @@ int vdx_p_sample_loop_lv(vdx_handle* h, const float* params, const void* packed,
     const char* who = "p_sample_loop_lv";
     if (!h || !params || !packed || !img || !out2_buf || !t_dev || !step_dev || !lv_tables || !seq || !workspace) VDX_REFUSE(who, "null argument");
     if (h->pred) VDX_FAIL(VDX_ERR_STATE, "p_sample_loop_lv: v-prediction (vdx_set_prediction) has no learned-variance form");
+    if (h->sc) VDX_FAIL(VDX_ERR_STATE, "p_sample_loop_lv: self-conditioning (vdx_set_self_condition) has no learned-variance form");
     const vdx::Model& m = h->model;
     const int C = m.cfg.channels;
     const long per_sample = (long)C * m.cfg.num_frames * m.cfg.image_size * m.cfg.image_size;
@@ -1489,6 +1513,21 @@ int vdx_v_to_eps(float* out, const float* x, const int* t, const float* sqrt_ac,
     if (rows < 1 || channels < 1 || timesteps < 1 || per_sample < 1) VDX_REFUSE(who, "rows, channels, timesteps and per_sample must be >= 1");
     if (per_sample % channels) VDX_REFUSE(who, "per_sample must be a multiple of channels");
     VDX_HIP(vdx::launch_v_to_eps(out, x, t, sqrt_ac, sqrt_1mac, timesteps, rows, channels, per_sample, (hipStream_t)stream));
+    return VDX_OK;
+}
+
+// ---- self-conditioning (vdx.h: "Self-conditioning") ----
+
+int vdx_selfcond_x0(const float* x, long x_pitch, const float* eps_hat, const int* t, const float* tables, int timesteps, const float* thres,
+                    int clip_denoised, float* xin, int batch, int channels, long per_sample, void* stream) {
+    const char* who = "selfcond_x0";
+    if (!x || !eps_hat || !t || !tables || !xin) VDX_REFUSE(who, "null tensor");
+    if (batch < 1 || channels < 1 || timesteps < 1 || per_sample < 1) VDX_REFUSE(who, "batch, channels, timesteps and per_sample must be >= 1");
+    if (per_sample % channels) VDX_REFUSE(who, "per_sample must be a multiple of channels");
+    if (x_pitch < per_sample) VDX_REFUSE(who, "x_pitch must be >= per_sample");
+    if ((uintptr_t)x % 4 || (uintptr_t)eps_hat % 4 || (uintptr_t)xin % 4) VDX_REFUSE(who, "x / eps_hat / xin must be 4-byte aligned");
+    const vdx::SelfcondArgs a = {x, x_pitch, eps_hat, t, tables, timesteps, thres, clip_denoised ? 1 : 0, xin, channels, per_sample};
+    VDX_HIP(vdx::launch_selfcond_x0(a, batch, (hipStream_t)stream));
     return VDX_OK;
 }
 

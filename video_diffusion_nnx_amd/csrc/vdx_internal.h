@@ -341,6 +341,15 @@ struct VLossArgs {
 };
 size_t v_loss_scratch_doubles(int B);
 hipError_t launch_v_loss(VLossArgs a, double* scratch, double* result, int B, hipStream_t st);
+// Self-conditioning (vdx.h: "Self-conditioning"; selfcond.hip): x0~ of (x, eps_hat) at levels t into planes [C, 2C) of xin [B,2C,F,H,W]
+struct SelfcondArgs {
+    const float* x; long x_pitch;                       // x_t [B][C,F,H,W], sample b at x + b * x_pitch (floats; >= per_sample)
+    const float* eps; const int* t;                     // eps_hat channel-last [B,F,H,W,C]; levels [B], clamped to [0, T - 1]
+    const float* tables; int T;                         // rows 0, 1 of the [5][T] step tables: sqrt(1 / ac) | sqrt(1 / ac - 1)
+    const float* thres; int clip;                       // the dynamic threshold s [B] or null (s = 1); clip: min(max(x0, -s), s) / s
+    float* xin; int C; long per_sample;                 // per_sample = C * F * H * W
+};
+hipError_t launch_selfcond_x0(const SelfcondArgs& a, int B, hipStream_t st);
 hipError_t launch_adam_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,
                            long step_count, float grad_scale, int do_ema, float decay, hipStream_t st);
 hipError_t launch_adam_ema_clip(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps,

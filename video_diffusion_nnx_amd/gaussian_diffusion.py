@@ -295,6 +295,20 @@ def lowres_aug_levels(batch: int, aug_max: int, key: int) -> torch.Tensor:
     return torch.randint(0, int(aug_max), (int(batch),), generator=g, dtype=torch.int32)
 
 
+def self_cond_key(key: int) -> int:
+    """Key of the self-conditioning coin under a loss key: child 5 of it (children 1-4: lowres_aug_key), so no other stream moves."""
+    return split_key(key, 5)[4]
+
+
+def self_cond_draw(p: float, generator=None) -> bool:
+    """The coin of one micro-batch of self-conditioned training (Chen et al. 2022, sec. 2.2: "with probability 50%"): True = the step runs
+    the first forward and conditions on its estimate.  One coin per micro-batch, not per sample: every sample then costs the same, and so
+    does every rank.  Pure host function of (p, generator state); p = 0 is never True, p = 1 always."""
+    if isinstance(p, bool) or not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f'self_cond_prob must be in [0, 1], got {p}')
+    return bool(float(torch.rand((), generator=generator)) < float(p))
+
+
 def dist_rank_world():
     """(rank, world) of the default torch.distributed group, (0, 1) outside one."""
     import torch.distributed as dist
@@ -412,12 +426,36 @@ class GaussianDiffusion:
     lowres_aug_max = 0
     # mixed-noise switch (instance attributes only when it is on, likewise)
     frame_noise_alpha = 0.0
+    # self-conditioning switch (an instance attribute only when it is on, likewise)
+    self_condition = False
 
     def __init__(self, denoise_fn: Unet3D, *, image_size: int, num_frames: int, text_use_bert_cls: bool = False,
                  channels: int = 3, timesteps: int = 1000, loss_type: str = 'l1', use_dynamic_thres: bool = False,
                  dynamic_thres_percentile: float = 0.9, sample_act_bf16: bool = True, learned_variance: bool = False,
                  vlb_weight: Optional[float] = None, lowres_cond=None, lowres_aug_max: int = 0, frame_noise_alpha: float = 0.0,
-                 objective: str = 'pred_noise', min_snr_gamma: Optional[float] = None):
+                 objective: str = 'pred_noise', min_snr_gamma: Optional[float] = None, self_condition: bool = False):
+        # self_condition = True (extension, off by default; Chen et al. 2022, "Analog Bits", sec. 2.2): the denoiser has channels =
+        # 2 * channels and out_dim = channels; its input is [ x_t | x0~ ], x0~ = its own previous estimate of x0, clipped (zero where there
+        # is none).  Training runs a first, gradient-free forward on [ x_t | 0 ] for a fraction Trainer.self_cond_prob of the steps and
+        # regresses from [ x_t | x0~ ] (train_step.forward_backward); the sampling chains feed the estimate of step k to step k + 1 inside
+        # the captured step (the handle's self-condition state, _sampling; the super-resolution loop entries, which carry xin).  Not stored
+        # in checkpoints, the stem's shape is.  vdx.h: "Self-conditioning".
+        if not isinstance(self_condition, (bool, np.bool_)):
+            raise ValueError(f'self_condition must be True or False, got {self_condition!r}')
+        if self_condition:
+            if lowres_cond is not None:
+                raise ValueError('self_condition does not support lowres_cond yet (a follow-up; DESIGN.md 9): the denoiser would take '
+                                 '3 * channels input planes')
+            if learned_variance:
+                raise ValueError('self_condition does not support learned_variance yet (a follow-up; DESIGN.md 9): the learned-variance loops '
+                                 'have no xin')
+            if check_frame_noise_alpha(frame_noise_alpha) > 0:
+                raise ValueError('self_condition does not support frame_noise_alpha yet (a follow-up; DESIGN.md 9): the loops over xin have no '
+                                 'mixed-noise step')
+            if getattr(denoise_fn, 'channels', None) != 2 * channels or getattr(denoise_fn, 'out_dim', None) != channels:
+                raise ValueError(f'self_condition needs a denoiser with channels == 2 * channels = {2 * channels} and out_dim == channels = '
+                                 f'{channels}, got channels {getattr(denoise_fn, "channels", None)}, out_dim {getattr(denoise_fn, "out_dim", None)}')
+            self.self_condition = True
         # objective = 'pred_v' (extension, off by default; Salimans & Ho 2022, "Progressive Distillation"): the network predicts
         # v = sqrt(ac_t) eps - sqrt(1 - ac_t) x0, well conditioned at both ends of the schedule.  Training regresses on v (vdx_v_loss);
         # everywhere else the network output is converted once, in place, to eps_hat = sqrt(ac_t) v_hat + sqrt(1 - ac_t) x_t directly behind
@@ -589,7 +627,8 @@ class GaussianDiffusion:
     _FEATURES = {'learned_variance': ('learned_variance', lambda gd: gd.learned_variance),
                  'lowres_cond': ('lowres_cond (super-resolution)', lambda gd: gd.lowres_cond is not None),
                  'frame_noise_alpha': ('frame_noise_alpha', lambda gd: bool(gd.frame_noise_alpha)),
-                 'objective': ("objective='pred_v' / min_snr_gamma", lambda gd: gd.objective == 'pred_v' or gd.min_snr_gamma is not None)}
+                 'objective': ("objective='pred_v' / min_snr_gamma", lambda gd: gd.objective == 'pred_v' or gd.min_snr_gamma is not None),
+                 'self_condition': ('self_condition', lambda gd: gd.self_condition)}
 
     def _refuse(self, feature, **given):
         """ValueError for the first of the keywords `given` that is in use (not None / False / its neutral value) while `feature` is on:
@@ -631,6 +670,62 @@ class GaussianDiffusion:
                                       float(self.dynamic_thres_percentile), L.ptr(s), x.shape[0], self.channels, self._per_sample(x),
                                       L.stream_ptr()))
         return s
+
+    # -- self-conditioning ---------------------------------------------------------------------------
+    def _self_cond_x0(self, x, x_pitch, eps_hat, t32, xin, *, thres=None, clip: bool = True):
+        """x0~ of (x_t, eps_hat) at levels t32 into planes [C, 2C) of xin [B,2C,F,H,W] (vdx_selfcond_x0, one launch).  x: a device
+        tensor whose sample b starts x_pitch floats after sample b - 1 (img with pitch per_sample, or xin itself with 2 per_sample)."""
+        B, per = xin.shape[0], xin.numel() // xin.shape[0] // 2
+        L.check(L.vdx_selfcond_x0(x.data_ptr(), int(x_pitch), L.ptr(eps_hat), L.ptr(t32), L.ptr(self._ptab), self.num_timesteps, L.ptr(thres),
+                                  int(bool(clip)), L.ptr(xin), B, self.channels, per, L.stream_ptr()))
+        return xin
+
+    def self_cond_estimate(self, x, t, out, *, clip_denoised: bool = True, xin=None):
+        """The self-condition x0~ [B,C,F,H,W] of the network output `out` [B,F,H,W,C] at x_t = `x`, levels t: clip(sqrt(1 / ac_t) x -
+        sqrt(1 / ac_t - 1) eps_hat), clipped statically or, with use_dynamic_thres, by the dynamic threshold -- what the captured chains
+        feed to their next step.  pred_v: `out` is converted to eps_hat in place first (_eps_from_out).  xin: an [B,2C,F,H,W] input whose
+        second half receives the estimate (the first is not touched); the result is then a view of it."""
+        if not self.self_condition:
+            raise ValueError('self_cond_estimate needs a self-conditioned diffusion (self_condition=True)')
+        x, t32 = self._dev(x), self._dev(t, torch.int32)
+        eps_hat = self._eps_from_out(out, x, t32)
+        thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
+        buf = torch.empty((x.shape[0], 2 * self.channels) + tuple(x.shape[2:]), dtype=torch.float32, device=self.device) if xin is None else xin
+        if tuple(buf.shape) != (x.shape[0], 2 * self.channels) + tuple(x.shape[2:]) or buf.dtype != torch.float32:
+            raise ValueError(f'xin must be float32 [{x.shape[0]}, {2 * self.channels}, ...] over the shape of x, got {tuple(buf.shape)}')
+        self._self_cond_x0(x, self._per_sample(x), eps_hat, t32, buf, thres=thres, clip=clip_denoised)
+        est = buf[:, self.channels:]
+        return est if xin is not None else est.contiguous()
+
+    def self_cond_input(self, x_t, t32, self_cond, forward):
+        """The training input xin [B,2C,F,H,W] = [ x_t | x0~ ] of a self-conditioned denoiser: zeros with x_t packed into the first half
+        (vdx_lowres_pack), then by `self_cond`: False -- x0~ = 0; True -- pass 1: out = forward(xin), the very call pass 2 makes (same
+        condition, masks and activation storage), converted to eps_hat for pred_v, and x0~ = the statically clipped estimate written
+        into the second half (vdx_selfcond_x0 with x = the first half of xin, pitch 2 per_sample); a [B,C,F,H,W] tensor -- a ready
+        estimate.  The estimate is a constant of the step: the backward runs from what the forward on the finished xin records."""
+        from . import ops
+        xin = torch.zeros((x_t.shape[0], 2 * self.channels) + tuple(x_t.shape[2:]), dtype=torch.float32, device=self.device)
+        ops.lowres_pack(x_t, xin)
+        if torch.is_tensor(self_cond):
+            if tuple(self_cond.shape) != tuple(x_t.shape):
+                raise ValueError(f'self_cond must be None, False, True or a {tuple(x_t.shape)} tensor, got shape {tuple(self_cond.shape)}')
+            xin[:, self.channels:].copy_(self_cond.to(self.device, torch.float32))
+        elif self_cond:
+            eps_hat = self._eps_from_out(forward(xin), x_t, t32)
+            self._self_cond_x0(xin, 2 * self._per_sample(x_t), eps_hat, t32, xin, clip=True)
+        return xin
+
+    def _self_cond_eps(self, x, t32, x_self_cond, cond):
+        """The network output of a self-conditioned denoiser on [ x | x0~ ] (x_self_cond None: zeros)."""
+        if x_self_cond is None:
+            sc = torch.zeros_like(x)
+        else:
+            sc = self._dev(x_self_cond)
+            if tuple(sc.shape) != tuple(x.shape):
+                raise ValueError(f'x_self_cond must have the shape of x {tuple(x.shape)}, got {tuple(sc.shape)}')
+        if is_list_str(cond):
+            raise NotImplementedError('pass text conditioning as a ready embedding tensor')
+        return self.denoise_fn(torch.cat([x, sc], dim=1), t32, cond=cond)
 
     # -- learned variances ---------------------------------------------------------------------------
     def _lv_tables(self, steps=None):
@@ -726,6 +821,7 @@ class GaussianDiffusion:
         [B,C,F/ft,S/fs,S/fs] in [0, 1] (a base model's sample, say) with the T-step ancestral chain, an S-step DDIM chain (ddim_steps)
         or an S-step DPM-Solver++(2M) chain (dpm_steps, dpm_order).  aug_level: the noise conditioning augmentation level at sampling
         time (None = none; an int or [B] levels in [-1, T-1]), drawn as Philox(key, VDX_DRAW_LOWRES).  Single process: no rank sharding."""
+        self._refuse('self_condition', upsample=True)
         if self.lowres_cond is None:
             raise ValueError('upsample needs a super-resolution diffusion (lowres_cond=(ft, fs))')
         lowres = torch.as_tensor(lowres)
@@ -771,11 +867,14 @@ class GaussianDiffusion:
         return out[2 * B + 2].to(torch.float32).reshape(()), d_out
 
     # -- reverse process ---------------------------------------------------------------------------
-    def _p_step(self, x, t, clip_denoised, cond, cond_scale, lowres_cond, key=0, noise=None, zero_noise=False):
+    def _p_step(self, x, t, clip_denoised, cond, cond_scale, lowres_cond, key=0, noise=None, zero_noise=False, x_self_cond=None):
         """One eager reverse step -> (x_{t-1}, t on the device, the network output of a learned-variance diffusion or None).  The noise
         is `noise` when given, zero with zero_noise (the fused step is then the posterior mean), else drawn inside the step kernel as
         Philox(key, draw 0) under the diffusion's prior."""
         self._refuse('lowres_cond', cond_scale=cond_scale)
+        self._refuse('self_condition', cond_scale=cond_scale)
+        if not self.self_condition and x_self_cond is not None:
+            raise ValueError('x_self_cond needs a self-conditioned diffusion (self_condition=True)')
         if self.lowres_cond is None and lowres_cond is not None:
             raise ValueError('lowres_cond needs a super-resolution diffusion (lowres_cond=(ft, fs))')
         x = self._dev(x)
@@ -791,6 +890,7 @@ class GaussianDiffusion:
                                            0, 0, L.ptr(nz), seed, 0, 0, int(clip_denoised), 1.0, 0.0, *size()))
             return out, t32, out2
         eps_hat = self._sr_eps(x, t32, lowres_cond, cond) if self.lowres_cond is not None else \
+            self._self_cond_eps(x, t32, x_self_cond, cond) if self.self_condition else \
             self.denoise_fn.forward_with_cond_scale(x, t32, cond=cond, cond_scale=cond_scale)
         eps_hat = self._eps_from_out(eps_hat, x, t32)
         thres = self._dynamic_threshold(x, t32, eps_hat) if (clip_denoised and self.use_dynamic_thres) else None
@@ -802,19 +902,22 @@ class GaussianDiffusion:
                                       seed, 0, 0, L.ptr(thres), int(clip_denoised), *size()))
         return out, t32, None
 
-    def p_mean_variance(self, x, t, clip_denoised: bool, cond=None, cond_scale: float = 1.0, *, lowres_cond=None):
+    def p_mean_variance(self, x, t, clip_denoised: bool, cond=None, cond_scale: float = 1.0, *, lowres_cond=None, x_self_cond=None):
         """reference :162-228 (returns (mean, variance, log_variance)): the reverse step with z = 0, and the variance look-ups.
         learned_variance: the model's variance, per element.  lowres_cond (a super-resolution diffusion only, and required there):
-        u = lowres_condition(lowres), the network sees [ x | u ]."""
-        mean, t32, out2 = self._p_step(x, t, clip_denoised, cond, cond_scale, lowres_cond, zero_noise=True)
+        u = lowres_condition(lowres), the network sees [ x | u ].  x_self_cond (a self-conditioned diffusion only): the estimate x0~ of
+        the previous step (self_cond_estimate), the network sees [ x | x0~ ]; None = zeros."""
+        mean, t32, out2 = self._p_step(x, t, clip_denoised, cond, cond_scale, lowres_cond, zero_noise=True, x_self_cond=x_self_cond)
         if out2 is not None:
             logvar = self.model_log_variance(out2, t32)
             return mean, logvar.exp(), logvar
         return mean, extract(self.posterior_variance, t32, mean.shape), extract(self.posterior_log_variance_clipped, t32, mean.shape)
 
-    def p_sample(self, x, t, key, cond=None, cond_scale: float = 1.0, clip_denoised: bool = True, *, noise=None, lowres_cond=None):
-        """reference :231-261.  `key`: seed of the noise draw (ignored when explicit `noise` is given).  lowres_cond: as p_mean_variance."""
-        return self._p_step(x, t, clip_denoised, cond, cond_scale, lowres_cond, key, noise)[0]
+    def p_sample(self, x, t, key, cond=None, cond_scale: float = 1.0, clip_denoised: bool = True, *, noise=None, lowres_cond=None,
+                 x_self_cond=None):
+        """reference :231-261.  `key`: seed of the noise draw (ignored when explicit `noise` is given).  lowres_cond / x_self_cond: as
+        p_mean_variance."""
+        return self._p_step(x, t, clip_denoised, cond, cond_scale, lowres_cond, key, noise, x_self_cond=x_self_cond)[0]
 
     # -- the sampling loops ------------------------------------------------------------------------
     @contextlib.contextmanager
@@ -836,16 +939,23 @@ class GaussianDiffusion:
         unet.act_bf16 = bool(self.sample_act_bf16 and unet.mode == 'bf16')
         # pred_v: the handle's loops convert the network output behind the forward (vdx_set_prediction); kind 0 goes back on the way out,
         # so a network shared with another diffusion is that diffusion's eps-model again
+        # self_condition: likewise the handle's self-condition state (vdx_set_self_condition): the step of the loops over xin writes x0~
+        # behind the forward; off again on the way out, so a network shared with a super-resolution diffusion runs that one's step again
         h = unet.handle(self.num_frames, self.image_size) if self.objective == 'pred_v' else None
+        hs = unet.handle(self.num_frames, self.image_size) if self.self_condition else None
         try:
             if h is not None:
                 L.check(L.vdx_set_prediction(h.ptr, 1, L.ptr(self.sqrt_alphas_cumprod), L.ptr(self.sqrt_one_minus_alphas_cumprod),
                                              self.num_timesteps))
+            if hs is not None:
+                L.check(L.vdx_set_self_condition(hs.ptr, 1, L.ptr(self._ptab), self.num_timesteps))
             with torch.cuda.stream(st):
                 yield
         finally:
             if h is not None:
                 L.check(L.vdx_set_prediction(h.ptr, 0, None, None, 0))
+            if hs is not None:
+                L.check(L.vdx_set_self_condition(hs.ptr, 0, None, 0))
             unet.act_bf16 = keep_storage
             unet._focus = None
         cur.wait_stream(st)
@@ -897,7 +1007,8 @@ class GaussianDiffusion:
                   together run eagerly (_masked_guided_steps).
           sr      lowres given (a super-resolution diffusion): u is written once into the second half of xin (vdx_lowres_input,
                   augmentation draw VDX_DRAW_LOWRES of the seed), the captured step is lowres_pack -> forward(xin) -> the plain step on
-                  img; kept buffers.
+                  img; kept buffers.  A self-conditioned diffusion runs the same entries: the second half of xin is zeroed here and
+                  the step (the handle's self-condition state, _sampling) writes x0~ into it behind the forward, for the next one.
           lv      a learned-variance diffusion: steps = S (None: T) levels of the respaced ancestral chain; unnormalize_img is folded into
                   the last step (post_scale = post_shift = 0.5), every other variant runs it as a launch of its own.
         Returns unnormalize_img(x_0) [B,C,F,H,W] in [0, 1]."""
@@ -905,7 +1016,9 @@ class GaussianDiffusion:
         seed = int(key) & 0xFFFFFFFFFFFFFFFF
         shape = (B, self.channels, self.num_frames, self.image_size, self.image_size)
         guided = cond is not None and unet.has_cond and cond_scale != 1
-        variant = 'sr' if lowres is not None else 'lv' if self.learned_variance else 'masked' if masked is not None else \
+        if self.self_condition and (guided or masked is not None or lowres is not None):
+            raise ValueError('self_condition runs the plain chains over xin: no guidance, no known region, no low-resolution clip')
+        variant = 'sr' if (lowres is not None or self.self_condition) else 'lv' if self.learned_variance else 'masked' if masked is not None else \
             'guided' if guided else 'plain'
         named = {}
         if variant == 'lv':
@@ -934,6 +1047,8 @@ class GaussianDiffusion:
             L.check(vdx_inpaint_init(L.ptr(img), L.ptr(known), L.ptr(mk), L.ptr(mtab), T, t0, img.numel(), L.stream_ptr()))
             named.update(known=L.ptr(known), mask=L.ptr(mk), mtab=L.ptr(mtab), resample=U)
             nsteps *= U if chain == 'ddpm' else 1
+        elif self.self_condition:
+            buf['xin'][:, self.channels:].zero_()                         # x0~ = 0 at step 0 (the buffers are kept across calls)
         elif variant == 'sr':
             self.lowres_condition(lowres, seed, aug_level, draw=L.DRAW_LOWRES, out=buf['xin'])
         if guided and variant == 'masked':
@@ -1012,6 +1127,7 @@ class GaussianDiffusion:
         """
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         self._sr_need_lowres('p_sample_loop', 'upsample(key, lowres)')
+        self._refuse('self_condition', cond_scale=cond_scale, guidance_rescale=guidance_rescale)
         if self.learned_variance:
             self._refuse('learned_variance', cond_scale=cond_scale, guidance_rescale=guidance_rescale, focus_present=focus_present)
             lv_time_sequence(self.num_timesteps, steps)                   # (its range check, before any device work)
@@ -1031,6 +1147,7 @@ class GaussianDiffusion:
         self._refuse('learned_variance', ddim_steps=steps)
         self._sr_need_lowres('ddim_sample_loop', 'upsample(key, lowres, ddim_steps=S)')
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        self._refuse('self_condition', cond_scale=cond_scale, guidance_rescale=guidance_rescale)
         ddim_time_sequence(self.num_timesteps, steps)                     # (its range check, before any device work)
         with self._sampling(focus_present, int(shape[0])):
             return self._run_chain('ddim', int(shape[0]), key, steps=int(steps), cond=cond, cond_scale=cond_scale,
@@ -1046,6 +1163,7 @@ class GaussianDiffusion:
         self._sr_need_lowres('dpm_sample_loop', 'upsample(key, lowres, dpm_steps=S)')
         check_dpm_args(self.num_timesteps, steps, order)
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        self._refuse('self_condition', cond_scale=cond_scale, guidance_rescale=guidance_rescale)
         with self._sampling(focus_present, int(shape[0])):
             return self._run_chain('dpm', int(shape[0]), key, steps=int(steps), order=order, cond=cond, cond_scale=cond_scale,
                                    guidance_rescale=guidance_rescale, use_graph=use_graph, x_T=x_T)
@@ -1063,6 +1181,7 @@ class GaussianDiffusion:
         self._refuse('learned_variance', focus_present=focus_present)
         self._refuse('lowres_cond', calc_bpd_loop=True)
         self._refuse('frame_noise_alpha', calc_bpd_loop=True)             # (the KL terms need the inverse frame covariance)
+        self._refuse('self_condition', calc_bpd_loop=True)                # (the bound of a chain that feeds on its own estimates: a follow-up)
         return self._bpd_chain(x, key, cond, clip_denoised, timesteps, use_graph, focus_present, None)
 
     def _bpd_chain(self, x, key, cond, clip_denoised, timesteps, use_graph, focus_present, pieces):
@@ -1126,6 +1245,7 @@ class GaussianDiffusion:
         no data-path collective.  W = 1 uses `key` itself (single-process behaviour unchanged)."""
         self._refuse('learned_variance', cond_scale=cond_scale, ddim_steps=ddim_steps, dpm_steps=dpm_steps, guidance_rescale=guidance_rescale,
                      focus_present=focus_present)
+        self._refuse('self_condition', cond_scale=cond_scale, guidance_rescale=guidance_rescale)
         if self.lowres_cond is not None:
             self._refuse('lowres_cond', cond_scale=cond_scale, guidance_rescale=guidance_rescale, focus_present=focus_present, steps=steps)
             if lowres is None:
@@ -1175,6 +1295,7 @@ class GaussianDiffusion:
         self._refuse('learned_variance', inpaint=True)
         self._refuse('lowres_cond', inpaint=True)
         self._refuse('frame_noise_alpha', inpaint=True)       # (the known region's noise would have to share s with the generated frames)
+        self._refuse('self_condition', inpaint=True)          # (there is no masked loop over xin)
         if focus_present is not None:
             raise ValueError('inpaint / extend do not take focus_present (frame-conditioned sampling of a focus-present sample is out of scope)')
         opts = self._inpaint_options(video, dict(cond_scale=cond_scale, ddim_steps=ddim_steps, resample_steps=resample_steps, use_graph=use_graph,
@@ -1220,6 +1341,7 @@ class GaussianDiffusion:
         self._refuse('learned_variance', extend=True)
         self._refuse('lowres_cond', extend=True)
         self._refuse('frame_noise_alpha', extend=True)
+        self._refuse('self_condition', extend=True)
         ctx = self.num_frames // 2 if context_frames is None else int(context_frames)
         video = torch.as_tensor(video)
         if video.dim() != 5 or tuple(video.shape[1:2] + video.shape[3:]) != (self.channels, self.image_size, self.image_size):
@@ -1278,15 +1400,21 @@ class GaussianDiffusion:
                              float(_pre[0]), float(_pre[1]), L.stream_ptr()))
         return out
 
-    def p_losses(self, x_start, t, key=None, cond=None, noise=None, *, frame_mask=None, _pre=(1.0, 0.0), lowres=None, aug_levels=None, **kwargs):
+    def p_losses(self, x_start, t, key=None, cond=None, noise=None, *, frame_mask=None, _pre=(1.0, 0.0), lowres=None, aug_levels=None,
+                 self_cond=None, self_cond_prob: float = 0.5, **kwargs):
         """reference :423-470 (forward value; the training step with gradients lives in trainer.py).  frame_mask (extension, RaMViD
         frame conditioning; forms as q_sample's): the masked frames enter the denoiser clean and the loss is the mean over the other
-        elements, sum / max(count, 1), formed on the device (vdx_loss_sum_masked)."""
+        elements, sum / max(count, 1), formed on the device (vdx_loss_sum_masked).  self_cond (a self-conditioned diffusion only): None
+        -- the coin of the two-pass objective is drawn with probability self_cond_prob under self_cond_key(key) (without a key: False);
+        False / True / a ready [B,C,F,H,W] estimate: self_cond_input."""
         if self.loss_type not in ('l1', 'l2'):
             raise ValueError(f'Unsupported loss type: {self.loss_type}')
         self._refuse('learned_variance', frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
         self._refuse('lowres_cond', frame_mask=frame_mask, focus_present=kwargs.get('focus_present_mask'))
         self._refuse('objective', frame_mask=frame_mask)                  # (the masked loss is a (sum, count) form without levels)
+        self._refuse('self_condition', frame_mask=frame_mask)
+        if self_cond is not None and not self.self_condition:
+            raise ValueError('self_cond needs a self-conditioned diffusion (self_condition=True)')
         if self.lowres_cond is None and (lowres is not None or aug_levels is not None):
             raise ValueError('lowres / aug_levels need a super-resolution diffusion (lowres_cond=(ft, fs))')
         if self.lowres_cond is not None:
@@ -1305,6 +1433,12 @@ class GaussianDiffusion:
         mk = None if frame_mask is None else self._dev_mask(frame_mask, x_start.shape)
         x_noisy, _ = self._net_input(x_start, t32, noise, mask=mk, lowres=lowres, aug_levels=aug_levels,
                                      aug_key=None if key is None else lowres_aug_key(key), _pre=_pre)
+        if self.self_condition:
+            # the coin of the two-pass objective: given, or drawn under child 5 of the loss key with probability self_cond_prob
+            if self_cond is None:
+                g = None if key is None else torch.Generator().manual_seed(self_cond_key(key) & 0x7FFFFFFFFFFFFFFF)
+                self_cond = False if key is None else self_cond_draw(self_cond_prob, g)
+            x_noisy = self.self_cond_input(x_noisy, t32, self_cond, lambda xin: self.denoise_fn(xin, t32, cond=cond, **kwargs))
         eps_hat = self.denoise_fn(x_noisy, t32, cond=cond, **kwargs)
         return self.loss_and_grad(eps_hat, x_start, noise, t32, mask=mk, _pre=_pre)[0]
 

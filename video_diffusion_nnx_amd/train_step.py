@@ -11,6 +11,7 @@ import torch
 
 from . import _lib as L
 from .gaussian_diffusion import _stage, frame_mask as expand_frame_mask, split_key
+from .gaussian_diffusion import self_cond_draw, self_cond_key as _loss_self_cond_key  # noqa: F401  (self_cond_draw: the coin, re-exported)
 # (bound next to the objective now; tests and tools import these three from here)
 from .gaussian_diffusion import vdx_loss_grad, vdx_loss_grad_masked, vdx_loss_sum  # noqa: F401
 
@@ -89,6 +90,16 @@ def lowres_aug_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
     return step_keys(rng_seed, rank, step, j).lowres_aug
 
 
+def self_cond_key(rng_seed: int, rank: int, step: int, j: int = 0) -> int:
+    """Key of the self-conditioning coin of micro-step j (a self-conditioned diffusion only): child 5 of the loss key of step_keys' tree.
+    split(key, n)[i] does not depend on n, so StepKeys stays as it is and no other stream moves.  The train step draws the coin under
+    rank 0's key on every rank: data-parallel ranks then run the same number of forwards per step."""
+    key = split_key(split_key(rng_seed, rank + 1)[-1], step + 1)[-1]
+    if j > 0:
+        key = split_key(key, 3 + j)[-1]
+    return _loss_self_cond_key(split_key(key, 3)[-1])
+
+
 def cond_drop_mask(batch: int, p: float, generator=None) -> torch.Tensor:
     """The condition-dropout mask of one micro-batch (Ho & Salimans 2022): uint8 [batch], Bernoulli(p), 1 = the sample sees the null
     embedding instead of its condition.  Pure host function of (arguments, generator state); p = 0 gives all 0, p = 1 all 1."""
@@ -131,7 +142,7 @@ def frame_cond_masks(batch: int, frames: int, k_max: int, uncond_prob: float = 0
 
 def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, j: int = 0, grads: torch.Tensor = None,
                      reducer=None, frame_mask=None, cond=None, cond_mask=None, focus_present_mask=None, aug_levels=None,
-                     lowres=None) -> torch.Tensor:
+                     lowres=None, self_cond=None) -> torch.Tensor:
     """loss, grads = value_and_grad(p_losses) (trainer.py:337-361) of one micro-batch; returns the device scalar loss.
 
     frame_mask ([F], [B,F] or anything gaussian_diffusion.frame_mask takes; default: drawn by frame_cond_masks under frame_cond_key when
@@ -154,6 +165,14 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     when lowres_aug_max is 0; -1 = none for that sample), the augmentation noise is Philox(lowres_aug_key, draw 0).  The forward and the
     staged backward run on xin; the loss, its gradient and everything after them are the plain ones over gd.channels.
     tr.last_aug_levels holds the levels as given or drawn.
+
+    self_cond (a self-conditioned diffusion, gd.self_condition, only; Chen et al. 2022, sec. 2.2): None -- the coin of the micro-batch is
+    drawn by self_cond_draw with probability tr.self_cond_prob under RANK 0's self_cond_key on every rank; False / True -- the coin as
+    given; a [B,C,F,H,W] tensor -- a ready estimate.  The network input is xin = [ x_t | x0~ ] (gd.self_cond_input): zeros, x_t packed
+    into the first half (vdx_lowres_pack) and, when the coin says so, pass 1 -- the same forward call as pass 2, then vdx_v_to_eps for
+    pred_v and one vdx_selfcond_x0 launch (static clip) that writes the estimate into the second half.  Pass 2 -- the forward on xin,
+    the loss, its gradient and the staged backward -- is the plain step over gd.channels; the estimate is a constant, nothing of pass 1
+    is differentiated.  tr.last_self_cond holds the coin (or the tensor).  Refuses frame_mask / frame_cond_max.
 
     Loss-aware timestep sampling (tr.sampler, Trainer.timestep_sampler = 'loss-second-moment'): t and the importance weights iw come from
     one vdx_tsampler_draw launch under t_key (draw 0) in place of the host randint (an explicit t only gets its weights); the per-sample
@@ -178,6 +197,10 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     if smp is not None and (frame_mask is not None or int(tr.frame_cond_max) > 0):
         raise ValueError('timestep_sampler=loss-second-moment does not serve frame-conditioned training (frame_mask / frame_cond_max): the '
                          'masked loss has no per-sample form')
+    if gd.self_condition and (frame_mask is not None or int(tr.frame_cond_max) > 0):
+        gd._refuse('self_condition', frame_mask=True)                     # (given, or to be drawn under frame_cond_max)
+    if self_cond is not None and not gd.self_condition:
+        raise ValueError('self_cond needs a self-conditioned diffusion (self_condition=True)')
     if t is None and smp is None:
         t = torch.randint(0, gd.num_timesteps, (B,), generator=host_gen(keys.t), dtype=torch.int32)
     t = None if t is None else _stage(t, torch.int32, dev)
@@ -216,6 +239,12 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     gd._refuse('learned_variance', frame_mask=frame_mask, focus_present=fp)
     gd._refuse('lowres_cond', frame_mask=frame_mask, focus_present=fp)
     gd._refuse('objective', frame_mask=frame_mask)                        # (given, or drawn under frame_cond_max)
+    if gd.self_condition:
+        if self_cond is None:
+            self_cond = self_cond_draw(tr.self_cond_prob, host_gen(self_cond_key(tr.rng_seed, 0, step, j)))
+        elif not torch.is_tensor(self_cond):
+            self_cond = bool(self_cond)
+        tr.last_self_cond = self_cond
     if gd.lowres_cond is None:
         if aug_levels is not None or lowres is not None:
             raise ValueError('aug_levels / lowres need a super-resolution diffusion (lowres_cond=(ft, fs))')
@@ -228,7 +257,10 @@ def forward_backward(tr, batch: torch.Tensor, step: int, t=None, noise=None, *, 
     keep_storage = unet.act_bf16
     unet.act_bf16 = 2 if (unet.mode == 'bf16' and tr.train_act_bf16) else False
     try:
-        eps_hat = unet(x_noisy, t, cond=cond, cond_mask=cm, focus_present_mask=fp)
+        forward = lambda xin: unet(xin, t, cond=cond, cond_mask=cm, focus_present_mask=fp)
+        if gd.self_condition:
+            x_noisy = gd.self_cond_input(x_noisy, t, self_cond, forward)
+        eps_hat = forward(x_noisy)
     finally:
         unet.act_bf16 = keep_storage
     # the loss (the returned one is what is optimised: the hybrid total, the masked mean, the weighted mean) and its gradient in eps_hat
@@ -319,7 +351,7 @@ def optimizer_tail(tr, step: int, world: int, accum: int = 1, max_grad_norm=None
 
 
 def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, noise: torch.Tensor = None, frame_mask=None,
-                   cond=None, cond_mask=None, focus_present_mask=None, aug_levels=None, lowres=None) -> torch.Tensor:
+                   cond=None, cond_mask=None, focus_present_mask=None, aug_levels=None, lowres=None, self_cond=None) -> torch.Tensor:
     """loss, grads = value_and_grad(p_losses); Adam; EMA  (trainer.py:337-382) for this rank's shard of the batch.
 
     `t` [B] / `noise` [B,C,F,H,W] override this rank's own draws (the reference threads `noise` through p_losses the same way,
@@ -327,17 +359,17 @@ def run_train_step(tr, batch: torch.Tensor, step: int, t: torch.Tensor = None, n
     shard's context-frame mask (forward_backward); each shard divides its loss by its own count of noised elements.  cond / cond_mask:
     the shard's conditions and its condition-dropout mask (forward_backward).  focus_present_mask: the shard's focus-present mask
     (forward_backward).  aug_levels / lowres: the shard's augmentation levels and low-resolution clips of a super-resolution diffusion
-    (forward_backward)."""
+    (forward_backward).  self_cond: the coin (or the ready estimate) of a self-conditioned diffusion (forward_backward)."""
     reducer = tr.make_reducer()
     loss = forward_backward(tr, batch, step, t, noise, reducer=reducer, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask,
-                            focus_present_mask=focus_present_mask, aug_levels=aug_levels, lowres=lowres)
+                            focus_present_mask=focus_present_mask, aug_levels=aug_levels, lowres=lowres, self_cond=self_cond)
     reducer.finish()
     optimizer_tail(tr, step, reducer.world)
     return loss
 
 
 def run_train_step_accum(tr, batches, step: int, ts=None, noises=None, frame_masks=None, conds=None, cond_masks=None,
-                         focus_present_masks=None) -> torch.Tensor:
+                         focus_present_masks=None, self_conds=None) -> torch.Tensor:
     """One optimizer step on the mean gradient of K = len(batches) micro-batches of this rank (Trainer.apply_grad_args).
 
     Micro-step 0 is run_train_step's path into tr.grads; micro-steps j >= 1 write tr.micro_grads and are added into tr.grads.  Only the
@@ -345,10 +377,12 @@ def run_train_step_accum(tr, batches, step: int, ts=None, noises=None, frame_mas
     reduction per optimizer step, still overlapped with the backward.  Returns the mean of the K device losses.  frame_masks: optional
     list of K context-frame masks (forward_backward); every micro-batch divides by its own count, then the K gradients are averaged.
     conds / cond_masks: optional lists of K conditions / condition-dropout masks (forward_backward).  focus_present_masks: optional
-    list of K focus-present masks (forward_backward)."""
+    list of K focus-present masks (forward_backward).  self_conds: optional list of K self-conditioning coins / estimates
+    (forward_backward; default: every micro-step draws its own)."""
     K = len(batches)
     assert K >= 1
-    ts, noises, fms, cds, cms, fps = ([None] * K if v is None else v for v in (ts, noises, frame_masks, conds, cond_masks, focus_present_masks))
+    ts, noises, fms, cds, cms, fps, scs = ([None] * K if v is None else v
+                                           for v in (ts, noises, frame_masks, conds, cond_masks, focus_present_masks, self_conds))
     if K > 1 and getattr(tr, 'micro_grads', None) is None:
         tr.micro_grads = torch.zeros_like(tr.grads)
     reducer = tr.make_reducer()
@@ -356,7 +390,7 @@ def run_train_step_accum(tr, batches, step: int, ts=None, noises=None, frame_mas
     for j in range(K):
         grads = tr.grads if j == 0 else tr.micro_grads
         losses.append(forward_backward(tr, batches[j], step, ts[j], noises[j], j=j, grads=grads, reducer=reducer if j == K - 1 else None,
-                                       frame_mask=fms[j], cond=cds[j], cond_mask=cms[j], focus_present_mask=fps[j]))
+                                       frame_mask=fms[j], cond=cds[j], cond_mask=cms[j], focus_present_mask=fps[j], self_cond=scs[j]))
         if 0 < j < K - 1:
             L.check(vdx_grad_accumulate(L.ptr(tr.grads), L.ptr(grads), grads.numel(), L.stream_ptr()))
     reducer.finish()

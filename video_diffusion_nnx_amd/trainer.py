@@ -170,6 +170,12 @@ class Trainer:
     timestep_sampler = 'uniform'
     sampler_history = 10
     sampler_uniform_prob = 0.001
+    # Self-conditioned training (extension; Chen et al. 2022, "Analog Bits", section 2.2; a GaussianDiffusion(self_condition=True) only,
+    # without one nothing changes): with probability self_cond_prob a (micro-)step first runs the network on [ x_t | 0 ], without
+    # gradient, and then regresses from [ x_t | x0~ ] with x0~ its clipped estimate of x0; otherwise from [ x_t | 0 ]
+    # (train_step.self_cond_draw under train_step.self_cond_key of rank 0: one coin per micro-step, the same on every rank).  A step at
+    # 0.5 costs half a forward more on average.  A class attribute for the same reason as the ones above.
+    self_cond_prob = 0.5
 
     def __init__(self, diffusion_model, folder: str, *, rng_seed: int = 0, dataset_path: str, num_frames: int = 16,
                  train_batch_size: int = 4, train_lr: float = 1e-4, train_num_steps: int = 100000,
@@ -214,6 +220,7 @@ class Trainer:
         self.last_frame_mask = None                              # context-frame mask of the last micro-batch (frame_cond_max > 0)
         self.last_cond_mask = None                               # condition-dropout mask of the last micro-batch (null_cond_prob > 0)
         self.last_focus_mask = None                              # focus-present mask of the last micro-batch (prob_focus_present > 0)
+        self.last_self_cond = None                               # self-conditioning coin of the last micro-batch (a self-conditioned diffusion)
         from .train_step import stage_of_param
         nlev = len(self.unet.dim_mults)
         self.buckets = make_buckets(self.unet.param_table, n, lambda nm: stage_of_param(nm, nlev), stage_of_param('__count__', nlev),
@@ -233,6 +240,10 @@ class Trainer:
             raise ValueError(f'null_cond_prob must be in [0, 1], got {self.null_cond_prob}')
         if not 0.0 <= float(self.prob_focus_present) <= 1.0:
             raise ValueError(f'prob_focus_present must be in [0, 1], got {self.prob_focus_present}')
+        if isinstance(self.self_cond_prob, bool) or not 0.0 <= float(self.self_cond_prob) <= 1.0:
+            raise ValueError(f'self_cond_prob must be in [0, 1], got {self.self_cond_prob}')
+        if getattr(diffusion_model, 'self_condition', False) and int(self.frame_cond_max) > 0:
+            raise ValueError('self_condition does not support frame_mask yet (a follow-up; DESIGN.md 9): frame_cond_max > 0 draws one')
         from . import timestep_sampler as TS
         if self.timestep_sampler not in TS.SAMPLERS:
             raise ValueError(f'timestep_sampler must be one of {TS.SAMPLERS}, got {self.timestep_sampler!r}')
@@ -325,7 +336,7 @@ class Trainer:
         return red
 
     def train_step(self, batch: torch.Tensor, step: int, t=None, noise=None, frame_mask=None, cond=None, cond_mask=None,
-                   focus_present_mask=None, aug_levels=None, lowres=None) -> torch.Tensor:
+                   focus_present_mask=None, aug_levels=None, lowres=None, self_cond=None) -> torch.Tensor:
         """One `_pjit_train_step` on this rank's shard of the batch.  Returns the (device) scalar loss of the shard.
         t / noise: optional explicit timesteps / noise of the shard (default: this rank's own Philox draws).  frame_mask: optional
         explicit context-frame mask of the shard ([F] or [B,F], 1 = clean context; default: drawn when frame_cond_max > 0).  cond: the
@@ -333,10 +344,12 @@ class Trainer:
         embedding (default: drawn when null_cond_prob > 0).  focus_present_mask: optional explicit focus-present mask [B] of the shard
         (Unet3D(focus_present=True); default: drawn when prob_focus_present > 0).  aug_levels / lowres (a super-resolution diffusion,
         GaussianDiffusion(lowres_cond=...), only): optional explicit augmentation levels [B] (-1 = none; default: drawn from
-        {0..lowres_aug_max-1}) and low-resolution clips (default: the box mean of the batch)."""
+        {0..lowres_aug_max-1}) and low-resolution clips (default: the box mean of the batch).  self_cond (a self-conditioned diffusion,
+        GaussianDiffusion(self_condition=True), only): None = the coin of the two-pass step is drawn with probability self_cond_prob;
+        False / True = the coin as given; a [B,C,F,H,W] tensor = a ready estimate (train_step.forward_backward)."""
         from .train_step import run_train_step
         return run_train_step(self, batch, step, t=t, noise=noise, frame_mask=frame_mask, cond=cond, cond_mask=cond_mask,
-                              focus_present_mask=focus_present_mask, aug_levels=aug_levels, lowres=lowres)
+                              focus_present_mask=focus_present_mask, aug_levels=aug_levels, lowres=lowres, self_cond=self_cond)
 
     @property
     def accum_steps(self) -> int:
@@ -344,15 +357,15 @@ class Trainer:
         return max(1, int(self.gradient_accumulate_every)) if self.apply_grad_args else 1
 
     def train_step_accum(self, batches, step: int, ts=None, noises=None, frame_masks=None, conds=None, cond_masks=None,
-                         focus_present_masks=None) -> torch.Tensor:
+                         focus_present_masks=None, self_conds=None) -> torch.Tensor:
         """One optimizer step on K = len(batches) shards of this rank: the gradient is the mean over the K micro-batches (and the
         ranks), clipped to max_grad_norm when that is set.  Returns the (device) mean of the K losses; `last_grad_norm` holds the
         device float of the pre-clip norm when one was computed.  ts / noises / frame_masks / conds / cond_masks /
-        focus_present_masks: optional per-micro-batch lists, as train_step's."""
+        focus_present_masks / self_conds: optional per-micro-batch lists, as train_step's."""
         from .train_step import run_train_step_accum
         assert self.apply_grad_args, 'train_step_accum is the path behind Trainer.apply_grad_args = True'
         return run_train_step_accum(self, list(batches), step, ts=ts, noises=noises, frame_masks=frame_masks, conds=conds,
-                                    cond_masks=cond_masks, focus_present_masks=focus_present_masks)
+                                    cond_masks=cond_masks, focus_present_masks=focus_present_masks, self_conds=self_conds)
 
     def train(self, prob_focus_present: Optional[float] = None, focus_present_mask=None, log_fn=noop):
         """The training loop.  prob_focus_present (default: the attribute of that name) / focus_present_mask ([train_batch_size] mask of
